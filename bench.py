@@ -3,7 +3,7 @@
 8x8 4-bpp range quantiser of 3 planes) on an 8192x8192 RGBA frame of synthetic "YAIK-synth v1" data, inputs resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size 8192] [--mode3] [--in-flight F] [--no-cpu] [--no-parity]
-                  [--stage encode|all|corners|range1d|decode|lut3d] [--layout frames|stripes]
+                  [--stage encode|all|corners|range1d|decode|lut3d] [--layout frames|stripes] [--dump-outputs DIR]
 
 Default (--stage encode --layout frames) is the headline line described below.  --stage all = every GPU stage of ConvertHotPath per frame
 (encode + corner streams + live 1-D range path) with frames in flight; --stage corners | range1d | decode | lut3d time the other
@@ -513,6 +513,46 @@ def abi_gather_check(enc, dist, dev, rank, world, blob, need, allsums, checksum)
     return True, int(n.value), f"yk_gather_maps over a {int(n.value)}-rank communicator of its own: every payload arrived byte for byte"
 
 
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files together
+
+
+def frame_outputs(enc) -> dict:
+    """What a caller of the encode path receives for the frame the handle holds: alpha reject result, the seven tile bitmaps and
+    corner-colour streams, the per-pass tile counts and the three planes' range streams (tile defs + nibbles)."""
+    import numpy as np
+    a = enc.alpha_result()
+    out = {"alpha_bitmap": a["bitmap"], "alpha_bounds": a["bounds"], "alpha_tile_bbox": a["tile_bbox"],
+           "alpha_has_chunk_remaining": np.array([int(a["has_chunk"]), a["remaining"]]), "gradient_counts": enc.gradient_counts()}
+    for p in range(7):
+        out[f"gradient_bitmap_{p}"] = enc.gradient_bitmap(p)
+        out[f"gradient_corners_{p}"] = enc.gradient_corners(p)
+    for p in range(3):
+        defs, nib, nn = enc.range_streams(p)
+        out[f"range_defs_{p}"], out[f"range_nibbles_{p}"], out[f"range_nibble_count_{p}"] = defs, nib, np.array([nn])
+    return out
+
+
+def dump_outputs(directory: str, outputs: dict) -> None:
+    """Writes every array as DIR/<name>.npy in float32 (float64 where a value would not be exact in float32).  Each array gets an equal
+    share of DUMP_MAX_BYTES; a longer one is replaced by its elements at sorted indices drawn from a generator seeded by its length, so
+    two builds that produce the same length sample the same places.  DIR/lengths.npy holds the full length of every array, in name order."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    cap = DUMP_MAX_BYTES // 8 // (len(outputs) + 1)
+    lengths, total = [], 0
+    for name in sorted(outputs):
+        a = np.asarray(outputs[name]).reshape(-1)
+        lengths.append(a.size)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(a.size).integers(0, a.size, cap))]
+        exact32 = a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24)
+        a = a.astype(np.float32 if exact32 else np.float64)
+        total += a.nbytes
+        np.save(os.path.join(directory, name + ".npy"), a)
+    np.save(os.path.join(directory, "lengths.npy"), np.array(lengths, dtype=np.float64))
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs wrote {total} bytes, more than {DUMP_MAX_BYTES}"
+
+
 def measured_copy_roof(dev, nbytes: int = 1 << 30, reps: int = 5) -> float:
     """GB/s of a device-to-device copy of `nbytes` on this GPU (read + write counted), outside any timed region (the
     measured roof next to the 8 TB/s specification)."""
@@ -616,7 +656,12 @@ def main() -> int:
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-parity", action="store_true", help="skip the full-size bit-exactness check against the oracle")
     ap.add_argument("--cpu-size", type=int, default=0, help="side of the centred crop timed on the CPU (default: whole frame)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="--stage encode: after the timed steps, write what the last step "
+                    "computed for every frame of this rank as DIR/<name>.npy (float32/float64, at most 64 MB in all; long arrays as a fixed, seeded sample)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.stage != "encode" or args.layout != "frames"):
+        print("--dump-outputs covers the headline path (--stage encode --layout frames)", file=sys.stderr)
+        return 2
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus)                       # before anything touches the GPU in this process
@@ -750,6 +795,16 @@ def main() -> int:
         elapsed = float(tt.item())
     for n in kms:
         kms[n] /= max(1, args.steps)
+    if args.dump_outputs:
+        outputs = {}
+        for j in range(K):
+            if BF:
+                enc.select_frame(j)
+            tag = f"frame{j}_" if world == 1 else f"rank{rank}_frame{j}_"
+            outputs.update({tag + k: v for k, v in frame_outputs(enc if BF else encs[j]).items()})
+        if BF:
+            enc.select_frame(0)                # the parity check below reads frame 0
+        dump_outputs(args.dump_outputs, outputs)
 
     # ---- N > 1: check the collective's data path outside the timed region: every rank's payload must arrive on rank 0 byte for
     # byte (compared through 64-bit checksums), through the pipeline the timed loop used and through the C-ABI gather (yk_gather_maps)

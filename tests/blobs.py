@@ -1,5 +1,9 @@
 """Recomputes, with the CPU oracle, the named blobs that oracle/ref_driver.cpp dumps from the unmodified reference,
-so that golden fixtures (tests/golden/*.npz, hashes.json) and live reference runs can be compared name by name."""
+so that golden fixtures (tests/golden/*.npz, hashes.json, reference_digests.json) and live reference runs can be compared name by name."""
+import hashlib
+import json
+import os
+
 import numpy as np
 
 from oracle.pyoracle import (PASSES, OracleDecoder, OracleEncoder, dec_mask, image_builder, palette_decompress)
@@ -21,6 +25,7 @@ def oracle_blobs(planes: np.ndarray) -> dict:
         out["_mip_bitmap"] = mip["bitmap"].tobytes()
         out["_mip_tile_bbox"] = mip["tile_bbox"].astype(np.int16).tobytes()
         out["_mip_has_chunk"] = bytes([int(mip["has_chunk"])])
+        out["_mip_level"] = bytes([4])                        # MipPrefilter always writes the 16x16 level (EncoderContext.cpp:1367-1396)
     counts, streams = [], []
     for i, (sx, sy) in enumerate(PASSES):
         cnt, bm, rgb = enc.fitting_quad_smooth(sx, sy)
@@ -142,16 +147,13 @@ def oracle_partial_blobs(planes: np.ndarray) -> dict:
     return out
 
 
+def partial_view(ref: dict) -> dict:
+    """The blobs of a `ref_driver ... partial` run that compare_partial checks."""
+    return {k: bytes(v) for k, v in ref.items() if k.startswith(PP_KEEP)}
+
+
 def compare_partial(ref: dict, ours: dict) -> list:
-    bad = []
-    for k, v in ref.items():
-        if not k.startswith(PP_KEEP):
-            continue
-        if k not in ours:
-            bad.append(f"missing {k}")
-        elif bytes(v) != ours[k]:
-            bad.append(f"{k}: {len(v)} vs {len(ours[k])} bytes")
-    return bad
+    return compare_view(partial_view(ref), ours)
 
 
 LUT_PASSES = ((4, 3), (3, 4), (3, 3), (3, 2), (2, 3), (2, 2))          # Correlation3DSearch calls of Convert(), EncoderContext.cpp:9144-9199
@@ -233,17 +235,14 @@ def oracle_lut_blobs(planes: np.ndarray, patterns, tables: bool = True) -> dict:
     return out
 
 
-def compare_lut(ref: dict, ours: dict, tables: bool = True) -> list:
-    bad = []
+def lut_view(ref: dict, tables: bool = True) -> dict:
+    """The blobs of a `ref_driver ... lut3d` run that compare_lut checks."""
     keep = LUT_KEEP + (("lut_factors", "lut_distanceField", "lut_positions") if tables else ())
-    for k, v in ref.items():
-        if not k.startswith(keep):
-            continue
-        if k not in ours:
-            bad.append(f"missing {k}")
-        elif bytes(v) != ours[k]:
-            bad.append(f"{k}: {len(v)} vs {len(ours[k])} bytes")
-    return bad
+    return {k: bytes(v) for k, v in ref.items() if k.startswith(keep)}
+
+
+def compare_lut(ref: dict, ours: dict, tables: bool = True) -> list:
+    return compare_view(lut_view(ref, tables), ours)
 
 
 def parse_mip_chunk(chunk: bytes):
@@ -257,22 +256,61 @@ def parse_mip_chunk(chunk: bytes):
     return bbox, level, np.frombuffer(chunk[24:24 + nbytes], np.uint8).copy()
 
 
-def compare_with_reference(ref: dict, ours: dict, decode_ok: bool = True) -> list:
-    bad = []
-    for k, v in ref.items():
-        if k in SKIP or (not decode_ok and k.startswith("dec_")):
-            continue
-        if k not in ours:
-            bad.append(f"missing {k}")
-        elif bytes(v) != ours[k]:
-            bad.append(f"{k}: {len(v)} vs {len(ours[k])} bytes")
+def reference_view(ref: dict, decode_ok: bool = True) -> dict:
+    """The blobs of a plain `ref_driver` run that compare_with_reference checks; the 'MIPM' chunk enters in parsed form
+    (_mip_has_chunk, and with a chunk _mip_tile_bbox, _mip_level, _mip_bitmap) because its header is partly uninitialised."""
+    view = {k: bytes(v) for k, v in ref.items() if k not in SKIP and (decode_ok or not k.startswith("dec_"))}
     if "mip_chunk" in ref:
         parsed = parse_mip_chunk(bytes(ref["mip_chunk"]))
-        has = ours["_mip_has_chunk"] == b"\x01"
-        if (parsed is not None) != has:
-            bad.append("mip chunk presence")
-        elif parsed is not None:
+        view["_mip_has_chunk"] = bytes([int(parsed is not None)])
+        if parsed is not None:
             bbox, level, bm = parsed
-            if bbox.tobytes() != ours["_mip_tile_bbox"] or level != 4 or bm.tobytes() != ours["_mip_bitmap"]:
-                bad.append("mip chunk content")
+            view["_mip_tile_bbox"], view["_mip_level"], view["_mip_bitmap"] = bbox.tobytes(), bytes([level]), bm.tobytes()
+    return view
+
+
+def compare_view(view: dict, ours: dict) -> list:
+    bad = []
+    for k, v in view.items():
+        if k not in ours:
+            bad.append(f"missing {k}")
+        elif v != bytes(ours[k]):
+            bad.append(f"{k}: {len(v)} vs {len(ours[k])} bytes")
     return bad
+
+
+def compare_with_reference(ref: dict, ours: dict, decode_ok: bool = True) -> list:
+    return compare_view(reference_view(ref, decode_ok), ours)
+
+
+# ---- reference outputs kept as digests (tests/golden/reference_digests.json, written by tests/golden/make_golden.py) ----------------
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_digests.json")
+
+
+def digest(view: dict) -> dict:
+    """{blob name: "<bytes>:<sha256>"}: how the digest fixture keeps a view of the reference's output."""
+    return {k: f"{len(v)}:{hashlib.sha256(bytes(v)).hexdigest()}" for k, v in view.items()}
+
+
+def compare_digest(ref: dict, ours: dict, exact_names: bool = False) -> list:
+    """compare_view against a digest; exact_names also reports blobs of ours that the reference does not have."""
+    bad = []
+    for k, d in ref.items():
+        if k not in ours:
+            bad.append(f"missing {k}")
+        elif digest({k: ours[k]})[k] != d:
+            bad.append(f"{k}: {d.split(':')[0]} vs {len(ours[k])} bytes")
+    if exact_names:
+        bad += [f"extra {k}" for k in ours if k not in ref]
+    return bad
+
+
+def reference_digest(group: str, name: str, live) -> dict:
+    """The committed digest of the reference's output for case `name` of `group`.  Where the reference build exists, live(name) (the
+    same view computed from a fresh reference run) must still match it, so a stale fixture fails instead of passing quietly."""
+    from oracle.refrun import have_ref
+    with open(DIGESTS) as f:
+        ref = json.load(f)[group][name]
+    if have_ref():
+        assert digest(live(name)) == ref, f"{DIGESTS} is stale for {group}/{name}: rerun tests/golden/make_golden.py"
+    return ref

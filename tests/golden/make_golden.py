@@ -3,6 +3,7 @@ oracle/Makefile from the sources under /root/reference).  The reference ships no
 these captured outputs are the parity anchor that travels with the repo; the reference itself never does.
 
     python tests/golden/make_golden.py          # needs oracle/_ref/ref_driver (i.e. a checkout with /root/reference present)
+    python tests/golden/make_golden.py digests  # reference_digests.json + reference_chunks.npz alone
 
 Fixtures are data only: inputs are regenerated from seeds (yaik_amd.synth / tests.images), outputs are the blobs the
 reference produced: small images keep every blob (npz, compressed), larger ones keep a SHA-256 per blob.
@@ -68,6 +69,25 @@ def write_photo_input():
     np.savez_compressed(PHOTO_INPUT, rgb=np.ascontiguousarray(im[32:288, 96:352]))
 
 
+def write_reference_digests():
+    """The comparison cases of the CPU suite that have no full fixture: reference_digests.json keeps a SHA-256 per compared blob
+    (tests/blobs.py: digest), reference_chunks.npz the reference's raw chunk stream (compared in parsed form, tests/test_host_chunks.py)."""
+    from tests import test_host_chunks, test_lut3d, test_oracle_vs_reference, test_partial_planes
+    from tests.blobs import DIGESTS, digest
+    groups = {
+        "oracle_vs_reference": (test_oracle_vs_reference.CASES, test_oracle_vs_reference.reference_case),
+        "oracle_vs_reference_fuzz": ([str(s) for s in test_oracle_vs_reference.FUZZ_SEEDS], test_oracle_vs_reference.reference_fuzz_case),
+        "partial_planes": (test_partial_planes.LIVE, test_partial_planes.reference_case),
+        "lut3d": (test_lut3d.LIVE, test_lut3d.reference_case),
+    }
+    out = {g: {name: digest(live(name)) for name in sorted(cases)} for g, (cases, live) in groups.items()}
+    with open(DIGESTS, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    streams = {name: np.frombuffer(run_reference(mk())["chunks_file"], dtype=np.uint8) for name, mk in test_host_chunks.LIVE.items()}
+    np.savez_compressed(os.path.join(HERE, "reference_chunks.npz"), **streams)
+    print("reference_digests.json:", sum(len(v) for v in out.values()), "cases; reference_chunks.npz:", len(streams), "streams")
+
+
 def main():
     only = sys.argv[1] if len(sys.argv) > 1 else None                # `make_golden.py <lut fixture name>`: that fixture alone
     if only in LUT3D:
@@ -81,6 +101,9 @@ def main():
     if not have_ref():
         print("oracle/_ref/ref_driver is missing: run `make -C oracle` on a machine that has /root/reference", file=sys.stderr)
         return 1
+    write_reference_digests()
+    if only == "digests":
+        return 0
     for name, mk in FULL.items():
         blobs = run_reference(mk())
         keep = {k: np.frombuffer(v, dtype=np.uint8) for k, v in blobs.items() if not k.startswith(DROP_PREFIX)}

@@ -1,13 +1,14 @@
 """CPU suite, SURVEY 8(f)4: the 3-D LUT tile search (Load3DPattern / Set3DPointCloud / Correlation3DSearch / computeValues3D and the stream
 finishing of EndCorrelationSearch), oracle vs the unmodified reference on a SYNTHETIC bank (tests/lutbank.py; the reference's own bank is
-not in its repository) -- committed fixtures tests/golden/lut_*.npz, live where the reference build exists."""
+not in its repository) -- committed fixtures tests/golden/lut_*.npz, and digests of more cases in tests/golden/reference_digests.json,
+checked against a live run where the reference build exists."""
 import os
 
 import numpy as np
 import pytest
 
-from oracle.refrun import have_ref, run_reference
-from tests.blobs import compare_lut, oracle_lut_blobs
+from oracle.refrun import run_reference
+from tests.blobs import compare_digest, compare_lut, lut_view, oracle_lut_blobs, reference_digest
 from tests.golden.make_golden import LUT3D
 from tests.lutbank import bank_bytes, bank_patterns, lut_image, random_bank
 
@@ -33,13 +34,17 @@ LIVE = {
 }
 
 
-@pytest.mark.skipif(not have_ref(), reason="oracle/_ref/ref_driver not built (needs /root/reference)")
+def reference_case(name):
+    planes, pats = LIVE[name]()
+    n, h, w = planes.shape
+    ref = lut_view(run_reference(planes, lut_bank=bank_bytes(pats)))         # incl. every table of every pattern
+    if w % 16 or h % 16:                                                      # the decode loops need whole 16x16 tiles
+        ref = {k: v for k, v in ref.items() if not k.startswith(("lut_dec_", "dec_"))}
+    return ref
+
+
 @pytest.mark.parametrize("name", sorted(LIVE))
 def test_oracle_lut_search_matches_reference_live(oracle_built, name):
-    planes, pats = LIVE[name]()
-    ours = oracle_lut_blobs(planes, pats)
-    ref = run_reference(planes, lut_bank=bank_bytes(pats))
-    if "lut_dec_planes" not in ours:                                          # the decode loops need whole 16x16 tiles
-        ref = {k: v for k, v in ref.items() if not k.startswith(("lut_dec_", "dec_"))}
-    bad = compare_lut(ref, ours)                                              # incl. every table of every pattern
+    ref = reference_digest("lut3d", name, reference_case)
+    bad = compare_digest(ref, oracle_lut_blobs(*LIVE[name]()))
     assert not bad, bad

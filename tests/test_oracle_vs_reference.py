@@ -1,12 +1,10 @@
-"""CPU suite: live comparison of the oracle restatement with the unmodified reference (oracle/_ref/ref_driver).
-Skipped where the reference build is absent (e.g. a checkout without /root/reference); the golden-vector test covers that case."""
+"""CPU suite: the oracle restatement against the unmodified reference (oracle/_ref/ref_driver), through the digests of the reference's
+outputs committed in tests/golden/reference_digests.json; where the reference build exists, each digest is also checked against a live run."""
 import pytest
 
-from oracle.refrun import have_ref, run_reference
-from tests.blobs import compare_with_reference, oracle_blobs
+from oracle.refrun import run_reference
+from tests.blobs import compare_digest, oracle_blobs, reference_digest, reference_view
 from tests.images import edge_image, lineart_image, natural_photo, synth_planes
-
-pytestmark = pytest.mark.skipif(not have_ref(), reason="oracle/_ref/ref_driver not built (needs /root/reference)")
 
 CASES = {
     "synth128_rgb": lambda: synth_planes(128, n_planes=3),
@@ -25,20 +23,36 @@ CASES = {
 }
 
 
-@pytest.mark.parametrize("name", sorted(CASES))
-def test_oracle_equals_reference(oracle_built, name):
+def reference_case(name):
     planes = CASES[name]()
     n, h, w = planes.shape
-    bad = compare_with_reference(run_reference(planes), oracle_blobs(planes), decode_ok=(w % 16 == 0 and h % 16 == 0))
+    return reference_view(run_reference(planes), decode_ok=(w % 16 == 0 and h % 16 == 0))
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_oracle_equals_reference(oracle_built, name):
+    ref = reference_digest("oracle_vs_reference", name, reference_case)
+    bad = compare_digest(ref, oracle_blobs(CASES[name]()))
     assert not bad, bad
 
 
-@pytest.mark.parametrize("seed", [1000, 1003, 1004, 1007, 1009, 1014])
+FUZZ_SEEDS = [1000, 1003, 1004, 1007, 1009, 1014]
+
+
+def fuzz_planes(seed):
+    from tests.test_gpu_fuzz_parity import _image
+    size = 256 if seed % 2 else 128                     # the reference's RGBA path needs >= 256 (bad_alloc below)
+    return _image(seed, size, 4 if seed % 2 else 3)
+
+
+def reference_fuzz_case(seed):
+    return reference_view(run_reference(fuzz_planes(int(seed))))
+
+
+@pytest.mark.parametrize("seed", FUZZ_SEEDS)
 def test_oracle_equals_reference_on_fuzz_regimes(oracle_built, seed):
     """The tile regimes of tests/test_gpu_fuzz_parity.py (ranges around 16, values >= 223, zeros, two-level tiles, accept-boundary
     gradients): the oracle must agree with the unmodified reference there too, so the GPU fuzz test is anchored."""
-    from tests.test_gpu_fuzz_parity import _image
-    size = 256 if seed % 2 else 128                     # the reference's RGBA path needs >= 256 (bad_alloc below)
-    planes = _image(seed, size, 4 if seed % 2 else 3)
-    bad = compare_with_reference(run_reference(planes), oracle_blobs(planes))
+    ref = reference_digest("oracle_vs_reference_fuzz", str(seed), reference_fuzz_case)
+    bad = compare_digest(ref, oracle_blobs(fuzz_planes(seed)))
     assert not bad, bad

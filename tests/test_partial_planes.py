@@ -1,12 +1,13 @@
 """CPU suite: FittingQuadSmooth with NULL planes + DecompressGradient4x4(planeBit 1..6), oracle vs the unmodified reference
-(committed fixtures tests/golden/pp_*.npz from `ref_driver ... partial`; live where the reference build exists)."""
+(committed fixtures tests/golden/pp_*.npz from `ref_driver ... partial`, and digests of more cases in tests/golden/reference_digests.json,
+checked against a live run where the reference build exists)."""
 import os
 
 import numpy as np
 import pytest
 
-from oracle.refrun import have_ref, run_reference
-from tests.blobs import compare_partial, oracle_partial_blobs
+from oracle.refrun import run_reference
+from tests.blobs import compare_digest, compare_partial, oracle_partial_blobs, partial_view, reference_digest
 from tests.golden.make_golden import PARTIAL
 from tests.images import edge_image, synth_planes
 
@@ -29,15 +30,19 @@ LIVE = {
 }
 
 
-@pytest.mark.skipif(not have_ref(), reason="oracle/_ref/ref_driver not built (needs /root/reference)")
+def reference_case(name):
+    planes = LIVE[name]()
+    n, h, w = planes.shape
+    ref = partial_view(run_reference(planes, partial=True))
+    if w % 16 or h % 16:                                                      # decode loops need whole 16x16 tiles
+        ref = {k: v for k, v in ref.items() if not k.startswith("pp_dec_")}
+    return ref
+
+
 @pytest.mark.parametrize("name", sorted(LIVE))
 def test_oracle_partial_passes_match_reference_live(oracle_built, name):
-    planes = LIVE[name]()
-    ours = oracle_partial_blobs(planes)
-    ref = run_reference(planes, partial=True)
-    if "pp_dec_planes_grad" not in ours:                                      # decode loops need whole 16x16 tiles
-        ref = {k: v for k, v in ref.items() if not k.startswith("pp_dec_")}
-    bad = compare_partial(ref, ours)
+    ref = reference_digest("partial_planes", name, reference_case)
+    bad = compare_digest(ref, oracle_partial_blobs(LIVE[name]()))
     assert not bad, bad
 
 
