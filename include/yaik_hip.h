@@ -93,6 +93,15 @@ int yk_alpha_result(yk_ctx* c, int32_t bounds[4], int* hasChunk, int* remainingP
 /* 'MIPM' payload: 1 bit per 16x16 tile inside tileBBox, row-major, LSB first, 1 = kept (:1317-1327).
  * For a stripe: only the bits of the owned rows are set (OR the stripes' buffers). cap >= (w*h+7)/8 of tileBBox. */
 int yk_alpha_bitmap(yk_ctx* c, uint8_t* hostOut, size_t cap, size_t* nBytes);
+/* EncoderContext::ProcessAlpha(force8Bit) (encoder/EncoderContext.cpp:1429-1682): the alpha VALUES of a whole single image, after
+ * yk_alpha_reject + yk_alpha_finish (the search region is their bounds, read on the device).  One kernel reduces the box of samples with
+ * v >> 2 != 0; one kernel reads the box rounded to 4 once for the class flags and the 8-bit payload; binary alpha (only 0 / 255 in the box)
+ * is packed again by a third kernel on the box re-aligned to 8 (make1BitStream, :317-355).  Two small readbacks (box, class) size the launches.
+ * out->mode = -1 (no chunk: no alpha plane, empty box, all 255), 1 (IS_1_BIT_FULL) or 6 (IS_8_BIT_FULL); bbox = {x, y, w, h};
+ * rawSize = the decompressed payload size (expectedDecompressionSize).  hostPayload may be NULL (size query); *n = rawSize.
+ * Only force8Bit = 1 (what Convert passes, :9027-9028) is implemented: 0 returns YK_ERR_BAD_ARG.  Synchronises. */
+typedef struct yk_alpha_info { int32_t mode; int32_t bbox[4]; uint32_t rawSize; } yk_alpha_info;
+int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostPayload, size_t cap, size_t* n);
 
 /* ---- a6 + a10..a13  fused tile encode ----------------------------------------------------------
  * One launch does what 7x EncoderContext::FittingQuadSmooth(rejectFactor, R,G,B, .., sx, sy)
@@ -345,6 +354,21 @@ const uint8_t* yk_decode_planes_device(yk_ctx* c, size_t* planeSize);
 int yk_decode_output(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA);
 int yk_decode_output_reference_rgba(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA);
 int yk_decode_tile4x4(yk_ctx* c, uint8_t* hostOut, size_t cap);
+/* 'ALPM' alpha values (chunk reader decoder/YAIK_API.cpp:750-833, unpackers decoder/YAIK_Alpha.cpp): the full w x h 8-bit alpha plane of the
+ * image begun by yk_decode_begin is written in HBM from the DECOMPRESSED payload (0 outside the box) and stays there for
+ * yk_decode_output_alpha.  mode = AlphaHeader::parameters & 7: 1 = 1 bit (0 / 255; box width a multiple of 8), 4 / 5 = 6 bit (/ inverted;
+ * width a multiple of 4), 6 = 8 bit, 2 / 3 = 6 bit (/ inverted) of the pixels the mipmap mask selects.  For 2 / 3, mask = the decoded
+ * 'MIPM' mask exactly as yk_decode_mask returns it and maskBBox = its box in pixels (tile box << 4); like the reference it is read linearly
+ * with stride maskBBox[2] from the alpha box's origin, and bits outside the buffer read 0.  bbox = {x, y, w, h} in pixels.
+ * refQuirk = 1 reproduces the reference's 1-bit row loop byte for byte (`while (--cnt)`, YAIK_Alpha.cpp:76: w/8 - 1 bytes per row, each row
+ * landing 8 pixels left of the previous one, the rest 0); 0 decodes what the encoder writes (w/8 bytes per row).
+ * Errors: YK_ERR_BAD_ARG for a box outside the image or empty, mode 0 or 7, a misaligned width; YK_ERR_RANGE for a payload shorter than the
+ * box (or the mask selection) needs.  Nothing is read or written out of bounds.  The mask modes synchronise once (the selected count). */
+int yk_decode_alpha(yk_ctx* c, int mode, const int32_t bbox[4], const uint8_t* payload, size_t n, const uint8_t* mask, size_t maskBytes,
+                    const int32_t maskBBox[4], int refQuirk);
+int yk_decode_alpha_plane(yk_ctx* c, uint8_t* hostOut, size_t cap);                       /* the plane back to the host (tests, custom builders) */
+/* yk_decode_output with the plane of yk_decode_alpha as alpha: RGBA 4 B/pixel; the alpha plane never leaves HBM */
+int yk_decode_output_alpha(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride);
 /* the three planes of tile4x4Mask back to back (planes 1 and 2 are meaningful once a partial-plane pass has split the masks) */
 int yk_decode_tile4x4_planes(yk_ctx* c, uint8_t* hostOut, size_t cap);
 

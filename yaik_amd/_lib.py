@@ -50,6 +50,7 @@ SIGNATURES = {
     "yk_alpha_finish": (C.c_int, [vp, vp]),
     "yk_alpha_result": (C.c_int, [vp, vp, ip, ip, vp]),
     "yk_alpha_bitmap": (C.c_int, [vp, vp, sz, szp]),
+    "yk_alpha_values": (C.c_int, [vp, C.c_int, vp, vp, sz, szp]),
     "yk_encode_tiles": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
     "yk_encode_frame": (C.c_int, [vp, C.c_int, C.c_int]),
     "yk_set_batch": (C.c_int, [vp, C.c_int]),
@@ -118,6 +119,9 @@ SIGNATURES = {
     "yk_measure_roof": (C.c_int, [vp, sz, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "yk_decode_output": (C.c_int, [vp, vp, sz, vp, C.c_int]),
     "yk_decode_output_reference_rgba": (C.c_int, [vp, vp, sz, vp, C.c_int]),
+    "yk_decode_alpha": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, sz, vp, C.c_int]),
+    "yk_decode_alpha_plane": (C.c_int, [vp, vp, sz]),
+    "yk_decode_output_alpha": (C.c_int, [vp, vp, sz]),
     "yk_decode_tile4x4": (C.c_int, [vp, vp, sz]),
     "yk_decode_tile4x4_planes": (C.c_int, [vp, vp, sz]),
     "yk_decode_gradient_planes": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, sz]),

@@ -1,0 +1,358 @@
+// 'ALPM' alpha value chunk on the device.
+//   yk_alpha_values   EncoderContext::ProcessAlpha (encoder/EncoderContext.cpp:1429-1682, make1BitStream :317-355): box, class, payload
+//   yk_decode_alpha   Decompress1BitMaskAlign8NoMask (decoder/YAIK_Alpha.cpp:25-112), Decompress6BitTo8BitAlphaNoMask (:114-235),
+//                     Decompress6BitTo8BitAlphaUsingMipmapMask (:237-376), Decompress8BitTo8BitAlphaNoMask (:377-444): the full w x h plane
+//                     in HBM (0 outside the box), kept for yk_decode_output_alpha.
+#include "yk_common.h"
+#include <climits>
+
+namespace {
+
+__device__ __forceinline__ uint8_t yk_av_expand6(uint32_t v6, bool inv) {
+    const uint32_t x = inv ? 63u - v6 : v6;
+    return (uint8_t)((x << 2) | (x >> 4));
+}
+// sample k of a 4-values-in-3-bytes stream (EncoderContext.cpp:1528-1541); bytes at or beyond n read as 0
+__device__ __forceinline__ uint32_t yk_av_sample6(const uint8_t* __restrict__ s, size_t n, size_t k) {
+    const size_t g = (k >> 2) * 3;
+    const uint32_t b0 = g < n ? s[g] : 0u, b1 = g + 1 < n ? s[g + 1] : 0u, b2 = g + 2 < n ? s[g + 2] : 0u;
+    switch (k & 3) {
+    case 0: return b0 & 63u;
+    case 1: return (b0 >> 6) | ((b1 & 15u) << 2);
+    case 2: return (b1 >> 4) | ((b2 & 3u) << 4);
+    default: return b2 >> 2;
+    }
+}
+
+// modes 1 (1 bit), 4 / 5 (6 bit, no mask), 6 (8 bit): the value of plane pixel i (flat index); every pixel of the plane is written.
+// refQuirk (mode 1 only): the reference's row loop `while (--cnt)` (YAIK_Alpha.cpp:76) decodes w/8 - 1 bytes per row and then skips
+// w - bw pixels, so every row lands 8 pixels left of the previous one; pixels it never writes are 0.
+__device__ __forceinline__ uint8_t yk_av_pixel(size_t i, int x, int y, const uint8_t* __restrict__ pay, size_t n, int mode, int refQuirk, int bx,
+                                               int by, int bw, int bh, int W) {
+    uint8_t v = 0;
+    if (mode == 1 && refQuirk) {
+        const long long rel = (long long)i - ((long long)by * W + bx);
+        const int blk = bw >> 3;
+        if (rel >= 0) {
+            const long long r = rel / (W - 8), o = rel % (W - 8);
+            if (r < bh && o < 8ll * (blk - 1)) {
+                const size_t byte = (size_t)r * (blk - 1) + (size_t)(o >> 3);
+                v = (byte < n && ((pay[byte] >> (o & 7)) & 1)) ? 255 : 0;
+            }
+        }
+    } else {
+        const int c = x - bx, r = y - by;
+        if (c >= 0 && c < bw && r >= 0 && r < bh) {
+            if (mode == 6) {
+                const size_t k = (size_t)r * bw + c;
+                v = k < n ? pay[k] : 0;
+            } else if (mode == 1) {
+                const size_t byte = (size_t)r * (bw >> 3) + (c >> 3);
+                v = (byte < n && ((pay[byte] >> (c & 7)) & 1)) ? 255 : 0;
+            } else {
+                const size_t k = (size_t)r * bw + c;      // bw is a multiple of 4: the rows are whole 3-byte groups
+                v = yk_av_expand6(yk_av_sample6(pay, n, k), mode == 5);
+            }
+        }
+    }
+    return v;
+}
+// one thread = 16 consecutive pixels of the plane (W is a multiple of 16: one row) and one 16-byte store
+__global__ __launch_bounds__(256) void yk_av_decode_kernel(const uint8_t* __restrict__ pay, size_t n, int mode, int refQuirk, int bx, int by, int bw, int bh,
+                                                           int W, int H, uint8_t* __restrict__ out) {
+    const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (i0 >= (size_t)W * H) return;
+    const int y = (int)((uint32_t)i0 / (uint32_t)W), x0 = (int)(i0 - (size_t)y * W);   // one 32-bit divide per thread (w * h < 2^31): its 16 pixels share a row
+    uint32_t word[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            v |= (uint32_t)yk_av_pixel(i0 + q * 4 + k, x0 + q * 4 + k, y, pay, n, mode, refQuirk, bx, by, bw, bh, W) << (8 * k);
+        word[q] = v;
+    }
+    *reinterpret_cast<uint4*>(out + i0) = make_uint4(word[0], word[1], word[2], word[3]);
+}
+
+// mask modes 2 / 3: the bit of box pixel (c, r) in the decoder's mipMapMask (read linearly with stride maskBBox.w from the alpha box's
+// origin, in 32-bit arithmetic like the reference's u32 mipmapPos); bits outside the mask buffer read 0
+__device__ __forceinline__ bool yk_av_maskbit(const uint8_t* __restrict__ mask, size_t maskBytes, uint32_t base, uint32_t stride, int r, int c) {
+    const uint32_t pos = base + stride * (uint32_t)r + (uint32_t)c;
+    return (size_t)(pos >> 3) < maskBytes && ((mask[pos >> 3] >> (pos & 7)) & 1);
+}
+// one wave per box row: count of mask-selected pixels
+__global__ __launch_bounds__(64) void yk_av_rowcount_kernel(const uint8_t* __restrict__ mask, size_t maskBytes, uint32_t base, uint32_t stride, int bw,
+                                                            uint32_t* __restrict__ rowCnt) {
+    const int r = blockIdx.x;
+    uint32_t cnt = 0;
+    for (int c = threadIdx.x; c < bw; c += 64) cnt += yk_av_maskbit(mask, maskBytes, base, stride, r, c) ? 1u : 0u;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+    if (threadIdx.x == 0) rowCnt[r] = cnt;
+}
+// one workgroup: exclusive prefix of the row counts, total in rowStart[bh].  Thread t owns a run of ceil(bh / 1024) rows; the run sums are
+// scanned in LDS
+__global__ __launch_bounds__(1024) void yk_av_rowscan_kernel(const uint32_t* __restrict__ rowCnt, int bh, uint32_t* __restrict__ rowStart) {
+    __shared__ uint32_t s[1024];
+    const int t = threadIdx.x, per = (bh + 1023) / 1024, r0 = t * per, r1 = min(r0 + per, bh);
+    uint32_t sum = 0;
+    for (int r = r0; r < r1; r++) sum += rowCnt[r];
+    s[t] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const uint32_t v = t >= o ? s[t - o] : 0u;
+        __syncthreads();
+        s[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = s[t] - sum;
+    for (int r = r0; r < r1; r++) { rowStart[r] = run; run += rowCnt[r]; }
+    if (t == 1023) rowStart[bh] = s[1023];
+}
+// one wave per box row: sample index of a selected pixel = rowStart + selected pixels to its left (ballot + popcount); the state of the
+// reference's 4-value cycle is that index, it carries across rows like `state` does (YAIK_Alpha.cpp:313)
+__global__ __launch_bounds__(64) void yk_av_maskdecode_kernel(const uint8_t* __restrict__ pay, size_t n, const uint8_t* __restrict__ mask, size_t maskBytes,
+                                                              uint32_t base, uint32_t stride, int bx, int by, int bw, int inv,
+                                                              const uint32_t* __restrict__ rowStart, int W, uint8_t* __restrict__ out) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    uint32_t k = rowStart[r];
+    uint8_t* row = out + (size_t)(by + r) * W + bx;
+    for (int c0 = 0; c0 < bw; c0 += 64) {
+        const int c = c0 + lane;
+        const bool sel = c < bw && yk_av_maskbit(mask, maskBytes, base, stride, r, c);
+        const unsigned long long b = __ballot(sel);
+        const uint32_t before = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        if (c < bw) row[c] = sel ? yk_av_expand6(yk_av_sample6(pay, n, (size_t)k + before), inv != 0) : 0;
+        k += (uint32_t)__popcll(b);
+    }
+}
+
+// ---- encode: EncoderContext::ProcessAlpha (encoder/EncoderContext.cpp:1429-1682) --------------------------------------------------
+// st[0..3] = bL, bT, bR, bB of the samples with v >> 2 != 0 (min / min / max / max, inclusive); st[4] = "a sample in 1..254 in the rounded box",
+// st[5] = "a sample != 255 in the rounded box".
+#define YK_AV_ROWS 16
+// box of v >> 2 != 0 inside the MipPrefilter bounds (read on the device from the alpha stage's result); one thread = 4 pixels of YK_AV_ROWS rows
+// 4 samples at p: one 16-byte load when the plane's rows are 16-byte aligned (VEC), 4 loads otherwise
+template <bool VEC>
+__device__ __forceinline__ int4 yk_ave_load4(const int32_t* __restrict__ p) {
+    if (VEC) return *reinterpret_cast<const int4*>(p);
+    return make_int4(p[0], p[1], p[2], p[3]);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void yk_ave_box_kernel(const int32_t* __restrict__ alpha, int stride, const int32_t* __restrict__ bounds, int W, int H,
+                                                         int32_t* __restrict__ st) {
+    // the region starts on a multiple of 16 (kept 16x16 tiles); the loads start on the multiple of 4 at or below it whatever it is
+    const int xs = max(bounds[0], 0), x0 = xs & ~3, y0 = max(bounds[1], 0), x1 = min(bounds[2], W), y1 = min(bounds[3], H);
+    const int x = x0 + ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4, yb = y0 + (int)blockIdx.y * YK_AV_ROWS;
+    int mnx = INT_MAX, mny = INT_MAX, mxx = -1, mxy = -1;
+    if (x < x1)
+        for (int y = yb; y < min(yb + YK_AV_ROWS, y1); y++) {
+            const int4 q = yk_ave_load4<VEC>(alpha + (size_t)y * stride + x);            // x < x1 <= W, W a multiple of 16: all 4 in the row
+            const int v[4] = { q.x, q.y, q.z, q.w };
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (x + k >= xs && x + k < x1 && (v[k] >> 2) != 0) { mnx = min(mnx, x + k); mxx = max(mxx, x + k); mny = min(mny, y); mxy = max(mxy, y); }
+        }
+    for (int o = 32; o > 0; o >>= 1) {
+        mnx = min(mnx, __shfl_xor(mnx, o, 64)); mny = min(mny, __shfl_xor(mny, o, 64));
+        mxx = max(mxx, __shfl_xor(mxx, o, 64)); mxy = max(mxy, __shfl_xor(mxy, o, 64));
+    }
+    // one lane per wave, and only the atomics that can still change the box: thousands of waves on four words would serialise in L2
+    // (a stale read only costs an unneeded atomic)
+    if ((threadIdx.x & 63) == 0 && mxx >= 0) {
+        const volatile int32_t* v = st;
+        if (mnx < v[0]) atomicMin(&st[0], mnx);
+        if (mny < v[1]) atomicMin(&st[1], mny);
+        if (mxx > v[2]) atomicMax(&st[2], mxx);
+        if (mxy > v[3]) atomicMax(&st[3], mxy);
+    }
+}
+// the three class flags over the box rounded to 4 in x (isAnalogAlpha, isAll1; isAll0 is false once the box is not empty) and, in the same
+// read, the 8-bit payload (every sample of the box, row-major): one thread = 4 pixels = one 4-byte store
+template <bool VEC>
+__global__ __launch_bounds__(256) void yk_ave_class_kernel(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh,
+                                                           uint8_t* __restrict__ pay, int32_t* __restrict__ st) {
+    const int c = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4, r = blockIdx.y;
+    bool analog = false, not255 = false;
+    if (c < bw) {
+        const int4 q = yk_ave_load4<VEC>(alpha + (size_t)(bT + r) * stride + bL + c);   // bL and c are multiples of 4
+        const int vs[4] = { q.x, q.y, q.z, q.w };
+        uint32_t word = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int v = vs[k];
+            analog |= v > 0 && v < 255; not255 |= v != 255;
+            word |= (uint32_t)(v & 255) << (8 * k);
+        }
+        *reinterpret_cast<uint32_t*>(pay + (size_t)r * bw + c) = word;      // bw and c are multiples of 4
+    }
+    const unsigned long long a = __ballot(analog), n = __ballot(not255);
+    if ((threadIdx.x & 63) == 0) {                                         // a flag is set once: later waves only read it
+        const volatile int32_t* v = st;
+        if (a && !v[4]) atomicOr(&st[4], 1);
+        if (n && !v[5]) atomicOr(&st[5], 1);
+    }
+}
+// make1BitStream (:317-355) on the box re-aligned to 8: bit (v & 1) of every sample, LSB first; one thread = one output byte
+__global__ __launch_bounds__(256) void yk_ave_pack1_kernel(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh,
+                                                           uint8_t* __restrict__ pay) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, perRow = (size_t)(bw >> 3);
+    if (i >= perRow * bh) return;
+    const int r = (int)(i / perRow), c = (int)(i % perRow) * 8;
+    const int32_t* p = alpha + (size_t)(bT + r) * stride + bL + c;
+    uint32_t b = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) b |= (uint32_t)(p[k] & 1) << k;
+    pay[i] = (uint8_t)b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int yk_decode_alpha(yk_ctx* c, int mode, const int32_t bbox[4], const uint8_t* payload, size_t n, const uint8_t* mask, size_t maskBytes,
+                    const int32_t maskBBox[4], int refQuirk) {
+    if (!c || !bbox || (!payload && n)) return YK_ERR_BAD_ARG;
+    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    const int W = c->dw, H = c->dh;
+    const int bx = bbox[0], by = bbox[1], bw = bbox[2], bh = bbox[3];
+    // CheckInBound2D (YAIK_Alpha.cpp:12-23) read as "in bounds passes" (it has no `return true`), for every mode; an empty box is refused
+    if (bx < 0 || by < 0 || bw <= 0 || bh <= 0 || bx >= W || by >= H || bx + bw > W || by + bh > H) return yk_fail(c, YK_ERR_BAD_ARG, "alpha box outside the image");
+    size_t need = 0;
+    switch (mode) {
+    case 1: if (bw & 7) return yk_fail(c, YK_ERR_BAD_ARG, "1-bit alpha box width not a multiple of 8");
+            need = (size_t)bh * ((bw >> 3) - (refQuirk ? 1 : 0)); break;
+    case 4: case 5: if (bw & 3) return yk_fail(c, YK_ERR_BAD_ARG, "6-bit alpha box width not a multiple of 4");
+            need = (size_t)bh * (bw >> 2) * 3; break;
+    case 6: need = (size_t)bw * bh; break;
+    case 2: case 3: if (!mask || !maskBBox || maskBBox[2] <= 0) return yk_fail(c, YK_ERR_BAD_ARG, "mask mode needs the decoded mipmap mask"); break;
+    default: return yk_fail(c, YK_ERR_BAD_ARG, "alpha mode not decodable");        // 0 (1 bit + mask) and 7
+    }
+    if (n < need) return yk_fail(c, YK_ERR_RANGE, "alpha payload shorter than its box");
+    YK_HIP(c, hipSetDevice(c->device));
+    const size_t plane = (size_t)W * H;
+    if (c->dAlphaBytes < plane) {
+        YK_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->dAlpha) { (void)hipFree(c->dAlpha); c->dAlpha = nullptr; c->dAlphaBytes = 0; }
+        YK_HIP(c, hipMalloc(&c->dAlpha, plane));
+        c->dAlphaBytes = plane;
+    }
+    c->dAlphaValid = false;
+    const size_t oPay = 0, oMask = (n + 255) & ~(size_t)255, oRows = oMask + ((maskBytes + 255) & ~(size_t)255);
+    const size_t scratch = oRows + ((size_t)bh * 2 + 2) * sizeof(uint32_t) + 64;
+    if (c->dAvScratchBytes < scratch) {
+        YK_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->dAvScratch) (void)hipFree(c->dAvScratch);
+        c->dAvScratch = nullptr; c->dAvScratchBytes = 0;
+        YK_HIP(c, hipMalloc(&c->dAvScratch, scratch));
+        c->dAvScratchBytes = scratch;
+    }
+    uint8_t* S = c->dAvScratch;
+    if (n) YK_HIP(c, hipMemcpyAsync(S + oPay, payload, n, hipMemcpyHostToDevice, c->stream));
+    if (mode == 2 || mode == 3) {
+        if (maskBytes) YK_HIP(c, hipMemcpyAsync(S + oMask, mask, maskBytes, hipMemcpyHostToDevice, c->stream));
+        uint32_t* rowCnt = reinterpret_cast<uint32_t*>(S + oRows);
+        uint32_t* rowStart = rowCnt + bh;
+        const uint32_t stride = (uint32_t)maskBBox[2];
+        const uint32_t base = (uint32_t)(bx - maskBBox[0]) + stride * (uint32_t)(by - maskBBox[1]);
+        YK_HIP(c, hipMemsetAsync(c->dAlpha, 0, plane, c->stream));
+        hipLaunchKernelGGL(yk_av_rowcount_kernel, dim3(bh), dim3(64), 0, c->stream, S + oMask, maskBytes, base, stride, bw, rowCnt);
+        hipLaunchKernelGGL(yk_av_rowscan_kernel, dim3(1), dim3(1024), 0, c->stream, rowCnt, bh, rowStart);
+        YK_HIP(c, hipGetLastError());
+        uint32_t total = 0;
+        YK_HIP(c, hipMemcpyAsync(&total, rowStart + bh, sizeof total, hipMemcpyDeviceToHost, c->stream));
+        YK_HIP(c, hipStreamSynchronize(c->stream));
+        const size_t needM = ((size_t)total * 6 + 7) / 8;
+        if (n < needM) return yk_fail(c, YK_ERR_RANGE, "alpha payload shorter than the mask selects");
+        hipLaunchKernelGGL(yk_av_maskdecode_kernel, dim3(bh), dim3(64), 0, c->stream, S + oPay, n, S + oMask, maskBytes, base, stride, bx, by, bw,
+                           mode == 3 ? 1 : 0, rowStart, W, c->dAlpha);
+    } else {
+        hipLaunchKernelGGL(yk_av_decode_kernel, dim3((unsigned)((plane / 16 + 255) / 256)), dim3(256), 0, c->stream, S + oPay, n, mode, refQuirk ? 1 : 0,
+                           bx, by, bw, bh, W, H, c->dAlpha);
+    }
+    YK_HIP(c, hipGetLastError());
+    c->dAlphaValid = true;
+    return YK_OK;
+}
+
+int yk_decode_alpha_plane(yk_ctx* c, uint8_t* hostOut, size_t cap) {
+    if (!c || !hostOut) return YK_ERR_BAD_ARG;
+    if (!c->dAlphaValid) return yk_fail(c, YK_ERR_STATE, "yk_decode_alpha first");
+    const size_t plane = (size_t)c->dw * c->dh;
+    if (cap < plane) return yk_fail(c, YK_ERR_RANGE, "alpha buffer too small");
+    YK_HIP(c, hipSetDevice(c->device));
+    YK_HIP(c, hipMemcpyAsync(hostOut, c->dAlpha, plane, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));
+    return YK_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostPayload, size_t cap, size_t* n) {
+    if (!c || !out) return YK_ERR_BAD_ARG;
+    out->mode = -1; out->bbox[0] = out->bbox[1] = out->bbox[2] = out->bbox[3] = 0; out->rawSize = 0;
+    if (n) *n = 0;
+    if (!force8Bit) return yk_fail(c, YK_ERR_BAD_ARG, "yk_alpha_values: only force8Bit = 1 (the argument Convert passes) is implemented");
+    if (c->nPlanes != 4) return YK_OK;                                                    // no alpha: no chunk (:1674-1680)
+    if (!c->alphaFinished) return yk_fail(c, YK_ERR_STATE, "yk_alpha_reject + yk_alpha_finish first");
+    if (c->nFrames != 1 || c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "yk_alpha_values works on a whole single image");
+    const int W = c->fullW, H = c->fullH;
+    YK_HIP(c, hipSetDevice(c->device));
+    if (!c->avState) YK_HIP(c, hipMalloc(&c->avState, 8 * sizeof(int32_t)));
+    if (c->avPayCap < (size_t)W * H) {
+        YK_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->avPay) (void)hipFree(c->avPay);
+        c->avPay = nullptr; c->avPayCap = 0;
+        YK_HIP(c, hipMalloc(&c->avPay, (size_t)W * H));
+        c->avPayCap = (size_t)W * H;
+    }
+    const int32_t init[8] = { INT_MAX, INT_MAX, -1, -1, 0, 0, 0, 0 };
+    YK_HIP(c, hipMemcpyAsync(c->avState, init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    // the search region is at most the image; the kernel clamps it to the bounds the alpha stage left on the device
+    const bool vec = ((reinterpret_cast<uintptr_t>(c->plane[3]) & 15) == 0) && ((c->strideElems & 3) == 0);
+    hipLaunchKernelGGL(vec ? yk_ave_box_kernel<true> : yk_ave_box_kernel<false>, dim3((unsigned)((W / 4 + 255) / 256), (unsigned)((H + YK_AV_ROWS - 1) / YK_AV_ROWS)), dim3(256), 0, c->stream,
+                       c->plane[3], c->strideElems, c->bounds + c->boundsOff, W, H, c->avState);
+    YK_HIP(c, hipGetLastError());
+    int32_t st[8];
+    YK_HIP(c, hipMemcpyAsync(st, c->avState, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 1: the box sizes every later launch
+    if (st[2] < 0) return YK_OK;                                                          // empty box: isAll0 and isAll1 stay true, no chunk
+    int bL = (st[0] >> 2) << 2, bR = ((st[2] + 1 + 3) >> 2) << 2;                         // :1465-1466
+    const int bT = st[1], bB = st[3] + 1;
+    if (bR > W) return yk_fail(c, YK_ERR_STATE, "alpha box beyond the image");
+    int bw = bR - bL;
+    const int bh = bB - bT;
+    hipLaunchKernelGGL(vec ? yk_ave_class_kernel<true> : yk_ave_class_kernel<false>, dim3((unsigned)((bw / 4 + 255) / 256), (unsigned)bh), dim3(256), 0, c->stream, c->plane[3], c->strideElems,
+                       bL, bT, bw, bh, c->avPay, c->avState);
+    YK_HIP(c, hipGetLastError());
+    YK_HIP(c, hipMemcpyAsync(st + 4, c->avState + 4, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 2: the class decides the payload
+    const bool analog = st[4] != 0, all1 = st[5] == 0;
+    size_t bytes;
+    if (analog) {
+        out->mode = 6; bytes = (size_t)bw * bh;                                           // IS_8_BIT_FULL, payload already written
+    } else if (all1) {
+        return YK_OK;                                                                     // all 255: no chunk
+    } else {                                                                              // binary: IS_1_BIT_FULL on the box re-aligned to 8
+        bL = (bL >> 3) << 3; bR = ((bR + 7) >> 3) << 3;
+        if (bR > W) return yk_fail(c, YK_ERR_STATE, "alpha box beyond the image");
+        bw = bR - bL;
+        bytes = (size_t)(bw >> 3) * bh;
+        out->mode = 1;
+        hipLaunchKernelGGL(yk_ave_pack1_kernel, dim3((unsigned)((bytes + 255) / 256)), dim3(256), 0, c->stream, c->plane[3], c->strideElems, bL, bT, bw, bh,
+                           c->avPay);
+        YK_HIP(c, hipGetLastError());
+    }
+    out->bbox[0] = bL; out->bbox[1] = bT; out->bbox[2] = bw; out->bbox[3] = bh; out->rawSize = (uint32_t)bytes;
+    if (n) *n = bytes;
+    if (hostPayload) {
+        if (cap < bytes) return yk_fail(c, YK_ERR_RANGE, "alpha payload buffer too small");
+        YK_HIP(c, hipMemcpyAsync(hostPayload, c->avPay, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    YK_HIP(c, hipStreamSynchronize(c->stream));
+    return YK_OK;
+}
+
+}  // extern "C"

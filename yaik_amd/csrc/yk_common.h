@@ -140,6 +140,9 @@ struct yk_ctx {
     uint8_t* dScratch = nullptr; size_t dScratchBytes = 0;
     uint8_t* dLoaded = nullptr;         // lattice point already popped from a colour stream (mapRGBMask)
     bool dSplit = false;
+    uint8_t* dAlpha = nullptr; size_t dAlphaBytes = 0; bool dAlphaValid = false;   // yk_decode_alpha: the w x h alpha plane of the image being decoded
+    uint8_t* dAvScratch = nullptr; size_t dAvScratchBytes = 0;                      // its payload, mask and row counts
+    int32_t* avState = nullptr; uint8_t* avPay = nullptr; size_t avPayCap = 0;      // yk_alpha_values: box + class flags, the payload
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
     // timing
     // timing events: a ring of YK_EV_RING sets {alpha begin, alpha end, encode begin, encode end, pack end} so that a caller can

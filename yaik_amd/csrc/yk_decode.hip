@@ -815,6 +815,7 @@ int yk_decode_begin(yk_ctx* c, int w, int h) {
     YK_HIP(c, hipMemsetAsync(c->dLoaded, 0, lat, c->stream));
     YK_HIP(c, hipMemsetAsync(c->dTile4, 0, ((3 * c->dTile4Size + 3) & ~(size_t)3) + 4, c->stream));
     c->dSplit = false;
+    c->dAlphaValid = false;                                                     // an 'ALPM' plane belongs to one image
     return YK_OK;
 }
 
@@ -1086,21 +1087,23 @@ int yk_decode_planes(yk_ctx* c, uint8_t* hostR, uint8_t* hostG, uint8_t* hostB, 
 // Shared body of the two output entry points.  The device image is packed tight (w * bpp bytes per row) and lands in the caller's
 // buffer by a 2-D copy with dpitch = outputImageStride: like the reference's loop, bytes of a row beyond the pixels are never
 // touched (outputImageStride exists to place the image INSIDE a larger buffer, include/YAIK.h:190).
-static int yk_decode_output_impl(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA, bool refRGBA) {
+static int yk_decode_output_impl(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA, bool refRGBA,
+                                 const uint8_t* devAlpha = nullptr) {
     if (!c || !hostOut) return YK_ERR_BAD_ARG;
     if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (devAlpha) { hostAlpha = devAlpha; strideA = c->dw; }                   // the plane yk_decode_alpha left in HBM: no host copy
     const int w = c->dw, h = c->dh, bpp = (hostAlpha && !refRGBA) ? 4 : 3;
     const size_t rowBytes = (size_t)w * bpp + (refRGBA && hostAlpha ? 1 : 0);
     if (outputImageStride < rowBytes || (hostAlpha && strideA < w)) return yk_fail(c, YK_ERR_BAD_ARG, "output stride too small");
     YK_HIP(c, hipSetDevice(c->device));
     const size_t dPitch = (rowBytes + 15) & ~(size_t)15;
-    const size_t outBytes = dPitch * h, aBytes = hostAlpha ? (size_t)strideA * h : 0, oA = (outBytes + 31) & ~(size_t)15;
+    const size_t outBytes = dPitch * h, aBytes = (hostAlpha && !devAlpha) ? (size_t)strideA * h : 0, oA = (outBytes + 31) & ~(size_t)15;
     int rc = yk_dec_scratch(c, oA + aBytes + 64); if (rc) return rc;
     rc = yk_dec_settle(c); if (rc) return rc;
-    if (hostAlpha) YK_HIP(c, hipMemcpyAsync(c->dScratch + oA, hostAlpha, aBytes, hipMemcpyHostToDevice, c->stream));
+    if (hostAlpha && !devAlpha) YK_HIP(c, hipMemcpyAsync(c->dScratch + oA, hostAlpha, aBytes, hipMemcpyHostToDevice, c->stream));
     { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc2) return rc2; }
     hipLaunchKernelGGL(yk_dec_detile_kernel, dim3((w + 255) / 256, (h + 3) / 4), dim3(256), 0, c->stream, c->dPlanes, c->dPlaneSize, w >> 3, w, h,
-                       (hostAlpha && !refRGBA) ? c->dScratch + oA : (const uint8_t*)nullptr, strideA, c->dScratch, dPitch);
+                       devAlpha ? devAlpha : (hostAlpha && !refRGBA) ? c->dScratch + oA : (const uint8_t*)nullptr, strideA, c->dScratch, dPitch);
     YK_HIP(c, hipGetLastError());
     { int rc2 = yk_stage_end(c, YK_STAGE_DEC_DETILE); if (rc2) return rc2; }
     if (refRGBA && hostAlpha) {
@@ -1114,6 +1117,12 @@ static int yk_decode_output_impl(yk_ctx* c, uint8_t* hostOut, size_t outputImage
 
 int yk_decode_output(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA) {
     return yk_decode_output_impl(c, hostOut, outputImageStride, hostAlpha, strideA, false);
+}
+
+int yk_decode_output_alpha(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!c->dAlphaValid) return yk_fail(c, YK_ERR_STATE, "yk_decode_alpha first");
+    return yk_decode_output_impl(c, hostOut, outputImageStride, nullptr, 0, false, c->dAlpha);
 }
 
 int yk_decode_output_reference_rgba(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA) {

@@ -1,7 +1,8 @@
 """Python plumbing over the decode half of the C-ABI (include/yaik_hip.h): the loops behind
 YAIK_DecodeImage's chunk switch (decoder/YAIK_API.cpp:731-1303), executed on the GPU.
 
-Method names follow the reference: DecompressGradient*, Decompress1D, Decompress1BitTiled.
+Method names follow the reference: DecompressGradient*, Decompress1D, Decompress1BitTiled; decompress_alpha = the four
+alpha value unpackers of decoder/YAIK_Alpha.cpp.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ class HipTileDecoder:
             raise YaikError(f"yk_create failed ({rc}): no usable HIP device -- the product path has no CPU fallback")
         self._h = h
         self.w = self.h = 0
+        self._has_alpha = False
 
     def close(self):
         if getattr(self, "_h", None):
@@ -32,6 +34,7 @@ class HipTileDecoder:
 
     def begin(self, w: int, h: int):
         self.w, self.h = w, h
+        self._has_alpha = False
         _chk(self._h, lib().yk_decode_begin(self._h, w, h))
 
     def decompress_gradient(self, sx: int, sy: int, bitmap: np.ndarray, rgb_dq: np.ndarray):
@@ -122,6 +125,24 @@ class HipTileDecoder:
         _chk(self._h, lib().yk_decode_mask(self._h, bits.ctypes.data, bw, bh, out.ctypes.data, out.size))
         return out
 
+    def decompress_alpha(self, mode: int, bbox, payload: np.ndarray, mask: np.ndarray | None = None, mask_bbox=None,
+                         reference_1bit: bool = False) -> np.ndarray:
+        """'ALPM' chunk: the w x h alpha plane from the DECOMPRESSED payload (yk_decode_alpha).  mode = AlphaHeader::parameters & 7,
+        bbox = (x, y, w, h) in pixels; the mask modes 2 / 3 take the decoded 'MIPM' mask (decompress_1bit_tiled) and its box in pixels.
+        reference_1bit reproduces the reference's 1-bit row loop byte for byte.  The plane stays on the device for image()."""
+        p = np.ascontiguousarray(payload, dtype=np.uint8)
+        b = np.ascontiguousarray(np.asarray(bbox, dtype=np.int32).reshape(4))
+        m = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
+        mb = np.ascontiguousarray(np.asarray(mask_bbox, dtype=np.int32).reshape(4)) if mask_bbox is not None else None
+        self._has_alpha = False
+        _chk(self._h, lib().yk_decode_alpha(self._h, int(mode), b.ctypes.data, p.ctypes.data if p.size else None, p.size,
+                                            m.ctypes.data if m is not None and m.size else None, m.size if m is not None else 0,
+                                            mb.ctypes.data if mb is not None else None, 1 if reference_1bit else 0))
+        self._has_alpha = True
+        out = np.empty((self.h, self.w), dtype=np.uint8)
+        _chk(self._h, lib().yk_decode_alpha_plane(self._h, out.ctypes.data, out.size))
+        return out
+
     def planes(self) -> np.ndarray:
         n = (self.w // 8) * (self.h // 8) * 64
         out = np.zeros((3, n), dtype=np.uint8)
@@ -131,7 +152,13 @@ class HipTileDecoder:
     def image(self, alpha: np.ndarray | None = None, stride: int | None = None, fill: int = 0, reference_rgba: bool = False) -> np.ndarray:
         """internal_imageBuilderFunc: interleaved RGB ([h, stride] bytes, 3 B/pixel) or RGBA when an alpha plane is given.
         Bytes of a row beyond the pixels keep `fill` (the call never writes them).  reference_rgba selects the reference's own
-        RGBA branch, defects included (yk_decode_output_reference_rgba)."""
+        RGBA branch, defects included (yk_decode_output_reference_rgba).  Without an explicit alpha, the plane of the last
+        decompress_alpha of this image (if any) is used on the device (yk_decode_output_alpha)."""
+        if alpha is None and self._has_alpha and not reference_rgba:
+            stride = stride or self.w * 4
+            out = np.full((self.h, stride), fill, dtype=np.uint8)
+            _chk(self._h, lib().yk_decode_output_alpha(self._h, out.ctypes.data, stride))
+            return out
         bpp = 4 if alpha is not None else 3
         stride = stride or self.w * bpp
         out = np.full((self.h, stride), fill, dtype=np.uint8)

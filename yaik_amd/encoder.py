@@ -125,6 +125,20 @@ class HipTileEncoder:
         _chk(self._h, L.yk_alpha_bitmap(self._h, out.ctypes.data, out.size, C.byref(nb)))
         return {"has_chunk": bool(has.value), "bounds": b, "remaining": rem.value, "tile_bbox": tb, "bitmap": out[:nb.value].copy()}
 
+    def alpha_values(self, force8bit: bool = True) -> dict | None:
+        """EncoderContext::ProcessAlpha on the GPU (yk_alpha_values), after mip_prefilter(): None when no 'ALPM' chunk is written, else
+        {"mode": AlphaHeader::parameters, "bbox": (x, y, w, h), "payload": decompressed payload (u8)}."""
+
+        class _Info(C.Structure):
+            _fields_ = [("mode", C.c_int32), ("bbox", C.c_int32 * 4), ("rawSize", C.c_uint32)]
+
+        info, n = _Info(), C.c_size_t()
+        out = np.empty(self.w * self.full_h, dtype=np.uint8)       # the payload is at most one byte per pixel
+        _chk(self._h, self._L.yk_alpha_values(self._h, int(force8bit), C.byref(info), out.ctypes.data, out.size, C.byref(n)))
+        if info.mode < 0:
+            return None
+        return {"mode": int(info.mode), "bbox": tuple(int(v) for v in info.bbox), "payload": out[:n.value].copy()}
+
     # ---- 7x FittingQuadSmooth + 3x DynamicTileEncode, one launch ---------------------------------------
     def encode(self, reject_factor: int = 3, mode3bit_only: bool = False, want_dst: bool = False, dst_fill: int = -1):
         L = self._L

@@ -20,9 +20,9 @@ static const int kPass[7][2] = { {4, 4}, {4, 3}, {3, 4}, {3, 3}, {3, 2}, {2, 3},
 EncoderContext::EncoderContext()
     : colorCompressionQuad(250), colorCompressionLUT3D(250), colorCompression1D(255), rangeCompression1D(15),
       mipMapTileSize(16), boundX0(0), boundY0(0), boundX1(0), boundY1(0), remainingPixels(0),
-      dumpImage(false), evaluateLUT(false), evaluateLUT2D(false), outFile(nullptr), fileOutSize(0), device(0),
+      dumpImage(false), evaluateLUT(false), evaluateLUT2D(false), outFile(nullptr), fileOutSize(0), emitAlpha(false), device(0),
       original(nullptr), ctx(nullptr), bound(false), alphaDone(false), encoded(false), enc3(false), encDst(false), oneDReady(false),
-      encReject(3), nextPass(0), nNibbles(0), cursor1d(0), mipHasChunk(false), lutMatched(0) { correlationPatternCount3D = 0; }
+      encReject(3), nextPass(0), nNibbles(0), cursor1d(0), mipHasChunk(false), alphaMode(-1), alphaBox{0, 0, 0, 0}, lutMatched(0) { correlationPatternCount3D = 0; }
 
 EncoderContext::~EncoderContext() { Release(); }
 
@@ -85,6 +85,26 @@ void EncoderContext::MipPrefilter(bool /*active*/) {
         }
     }
     alphaDone = true; encoded = false; nextPass = 0;
+}
+
+void EncoderContext::ProcessAlpha(bool force8Bit) {
+    alphaMode = -1; alphaPayload.clear(); alphaBox[0] = alphaBox[1] = alphaBox[2] = alphaBox[3] = 0;
+    if (!bound) { fail("ProcessAlpha: SetImageToEncode first"); return; }
+    if (!original->HasAlpha()) return;                                    // the reference fills plane 3 with 31 and writes nothing (:1674-1680)
+    if (!alphaDone) { fail("ProcessAlpha: MipPrefilter first"); return; }
+    const int w = original->GetWidth(), h = original->GetHeight();
+    yk_alpha_info info;
+    size_t n = 0;
+    alphaPayload.resize((size_t)w * h);
+    if (yk_alpha_values(ctx, force8Bit ? 1 : 0, &info, alphaPayload.data(), alphaPayload.size(), &n) != YK_OK) {
+        alphaPayload.clear(); fail("yk_alpha_values"); return;
+    }
+    alphaPayload.resize(n);
+    alphaMode = info.mode;
+    for (int k = 0; k < 4; k++) alphaBox[k] = info.bbox[k];
+    if (alphaMode < 0 || !outFile) return;
+    std::string e;
+    if (!yaikchunk::writeAlpha(outFile, alphaMode, alphaBox, alphaPayload.data(), alphaPayload.size(), e)) fail(("ProcessAlpha: " + e).c_str());
 }
 
 bool EncoderContext::ensureEncoded(int rejectFactor, bool mode3, bool wantDst) {
@@ -301,6 +321,7 @@ bool EncoderContext::ConvertHotPath(FILE* f) {
     const int w = original->GetWidth(), h = original->GetHeight();
     bool ok = yaikchunk::writeFileHeader(f, w, h, original->HasAlpha());
     if (ok && original->HasAlpha()) MipPrefilter(true);
+    if (ok && emitAlpha && original->HasAlpha()) { ProcessAlpha(true); ok = err.empty(); }
     PrepareQuadSmooth();
     for (int i = 0; ok && i < 7; i++) {
         FittingQuadSmooth(3, original->GetPlane(0), original->GetPlane(1), original->GetPlane(2), nullptr, false, kPass[i][0], kPass[i][1]);
@@ -495,6 +516,7 @@ bool EncoderContext::ConvertHotPathBegin(FILE* f, int threads) {
     bool ok = yaikchunk::writeFileHeader(f, st->w, st->h, original->HasAlpha());
     outFile = f; fileOutSize = 0;
     if (ok && original->HasAlpha()) MipPrefilter(true);                    // 'MIPM' is not compressed: written at once
+    if (ok && emitAlpha && original->HasAlpha()) { ProcessAlpha(true); ok = err.empty(); }   // 'ALPM' (opt-in) right after it
     outFile = nullptr;                                                     // the passes only collect their raw streams
     PrepareQuadSmooth();
     for (int i = 0; ok && i < 7; i++) {

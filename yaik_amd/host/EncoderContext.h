@@ -37,6 +37,12 @@ public:
     void CheckMipmapMask();                             // EncoderContext.cpp:2784
     void PrepareQuadSmooth();                           // empty in the reference too (:2796)
     void MipPrefilter(bool active);                     // :1257
+    // :1429-1682, on the GPU (yk_alpha_values) after MipPrefilter: the alpha VALUES.  With outFile set it appends the 'ALPM' chunk (none for
+    // an image without alpha, all-255 alpha or alpha below 4 everywhere).  Only force8Bit = true (what Convert passes, :9027-9028) is implemented.
+    void ProcessAlpha(bool force8Bit);
+    // opt-in: the ConvertHotPath* family calls ProcessAlpha(true) right after MipPrefilter, like the commented-out call in Convert()
+    // (:9027-9028).  Off by default: files stay byte for byte what they were.
+    bool emitAlpha;
     int  FittingQuadSmooth(int rejectFactor, Plane* a, Plane* b, Plane* c, Image* testOutput, bool useYCoCg,
                            int tileBitSizeX, int tileBitSizeY);                           // :3710, returns TileDone
     int  DynamicTileEncode(bool mode3BitOnly, Plane* plane, Plane* dst, bool isCo, bool isCg, bool isHalfX, bool isHalfY);   // :4365
@@ -87,6 +93,9 @@ public:
     size_t                  LastTileIndexCount() const { return nNibbles; }
     const std::vector<u8>&  MipmapBitmap() const { return mipBitmap; }                    // 'MIPM' payload (:1317-1327)
     bool                    MipmapHasChunk() const { return mipHasChunk; }
+    int                     AlphaMode() const { return alphaMode; }                        // AlphaHeader::parameters of the last ProcessAlpha, -1 = no chunk
+    const std::vector<u8>&  AlphaPayload() const { return alphaPayload; }                  // its decompressed payload
+    const int*              AlphaBBox() const { return alphaBox; }
     const std::vector<u8>&  TileTypeStream1D() const { return type1d; }                   // streamType (:8217)
     const char*             LastError() const { return err.c_str(); }
     int                     device;                                                        // HIP device ordinal, set before SetImageToEncode
@@ -107,6 +116,8 @@ private:
     std::vector<u16> tileDefs;
     size_t nNibbles, cursor1d;
     bool mipHasChunk;
+    int alphaMode, alphaBox[4];
+    std::vector<u8> alphaPayload;
     int lutMatched;
     std::vector<std::vector<u8>> lutPatterns;          // as loaded (count x 3, interleaved): the factor tables of the LUT file come from them
     std::string err;

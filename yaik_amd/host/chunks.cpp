@@ -45,6 +45,26 @@ bool writeMipmap(FILE* f, const int tb[4], int mipmapLevel, const u8* bits, size
     return putChunk(f, TAG_MIPMAP, &h, sizeof h, { &payload });
 }
 
+bool writeAlpha(FILE* f, int parameters, const int bbox[4], const u8* payload, size_t nBytes, std::string& err) {
+    if (!yaikzstd::available()) { err = yaikzstd::lastError(); return false; }
+    std::vector<u8> z(yaikzstd::compressBound(nBytes) + 16);
+    size_t best = (size_t)-1; int bestLevel = 5;
+    for (int level = 5; level < 22; level++) {                                          // :1575-1598
+        const size_t r = yaikzstd::compress(z.data(), z.size(), payload, nBytes, level);
+        const size_t size = r ? r : (size_t)-1;                                         // an error never wins and ends the sweep
+        if (size < best) { best = size; bestLevel = level; }
+        else if (size > best || r == 0) break;
+    }
+    const size_t r = yaikzstd::compress(z.data(), z.size(), payload, nBytes, bestLevel);
+    if (r == 0) { err = "ZSTD_compress failed"; return false; }
+    z.resize(r);
+    AlphaHeader h; memset(&h, 0, sizeof h);
+    h.bbox.x = (s16)bbox[0]; h.bbox.y = (s16)bbox[1]; h.bbox.w = (s16)bbox[2]; h.bbox.h = (s16)bbox[3];
+    h.streamSize = (u32)r; h.expectedDecompressionSize = (u32)nBytes; h.version = 1; h.parameters = (u8)parameters;
+    if (!putChunk(f, TAG_ALPHA, &h, sizeof h, { &z })) { err = "fwrite"; return false; }
+    return true;
+}
+
 void gradientExtent(int imgW, int imgH, int sx, int sy, const u8* bitmap, int out[4]) {
     u32 bigX, bigY, bitCount;
     out[0] = imgW; out[1] = imgH; out[2] = 0; out[3] = 0;

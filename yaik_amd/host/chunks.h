@@ -12,6 +12,9 @@ bool writeFileHeader(FILE* f, int width, int height, bool hasAlpha);            
 bool writeEndOfFile(FILE* f);                                                           // :9779-9781
 // 'MIPM' (:1367-1396): bbox in 16x16 tiles, 1 bit per tile, not compressed
 bool writeMipmap(FILE* f, const int tileBBox[4], int mipmapLevel, const u8* bits, size_t nBytes);
+// 'ALPM' (ProcessAlpha, :1568-1664): AlphaHeader (version 1) + the ZStd stream of the decompressed payload at the smallest of levels 5..21
+// (the sweep stops at the first level whose output grows; a level-5 error falls back to level 5), zero padding to 4 bytes
+bool writeAlpha(FILE* f, int parameters, const int bbox[4], const u8* payload, size_t nBytes, std::string& err);
 // 'GTIL' (:4239-4347).  Returns 1 = chunk written, 0 = nothing to write (no accepted tile / empty colour stream), -1 = error
 int  writeGradientTile(FILE* f, int imgW, int imgH, int tileShiftX, int tileShiftY, const u8* bitmap, size_t bitmapBytes,
                        u8* rgbStream, size_t rgbBytes, int colorCompression, int planeBit, std::string& err);

@@ -123,6 +123,8 @@ bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) {
         const uint8_t* p = (const uint8_t*)stream + sizeof(FileHeader);
         const uint8_t* const end = (const uint8_t*)stream + length;
         int state = 0; bool bad = false;
+        bool hasAlphaPlane = false;                                                                     // an 'ALPM' chunk was decoded (pCtx->alphaChannel)
+        std::vector<uint8_t> mask, alphaRaw; size_t maskBytes = 0; int32_t maskBox[4] = { 0, 0, 0, 0 };
         while (!bad) {
             if (p + 4 > end) { setError(YAIK_INVALID_TAG_ID); bad = true; break; }
             HeaderBase hb; memcpy(&hb.tag, p, 4);
@@ -139,8 +141,10 @@ bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) {
                 if (mh.mipmapLevel != 4) { setError(YAIK_INVALID_MIPMAP_LEVEL); bad = true; break; }         // only level 4 is implemented (YAIK_Mipmap.cpp:53-54)
                 const size_t need = ((size_t)mh.bbox.w * mh.bbox.h + 7) / 8;
                 if (mh.bbox.w <= 0 || mh.bbox.h <= 0 || body + sizeof mh + need > endBlock) { setError(YAIK_INVALID_STREAM); bad = true; break; }
-                std::vector<uint8_t> mask((size_t)w * h / 8 + 64);
+                mask.assign((size_t)w * h / 8 + 64, 0);
                 if (yk_decode_mask(s->ctx, body + sizeof mh, mh.bbox.w, mh.bbox.h, mask.data(), mask.size()) != YK_OK) { setError(YAIK_INVALID_STREAM); bad = true; break; }
+                maskBytes = (size_t)mh.bbox.w * mh.bbox.h * 32;                                             // pCtx->mipMapMask, box in pixels (YAIK_Mipmap.cpp:35-39)
+                maskBox[0] = mh.bbox.x << 4; maskBox[1] = mh.bbox.y << 4; maskBox[2] = mh.bbox.w << 4; maskBox[3] = mh.bbox.h << 4;
                 state = 1; break;
             }
             case TAG_GRADTILE: {
@@ -182,7 +186,28 @@ bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) {
                 if (yk_decode_1d(s->ctx, types.data(), dh.streamTypeUncmp, pix.data(), dh.streamPixelUncmp, dh.compressionRange) != YK_OK) { setError(YAIK_INVALID_STREAM); bad = true; }
                 break;
             }
-            case 0x4d504c41u: setError(YAIK_ALPHA_UNSUPPORTED_YET); bad = true; break;                      // 'ALPM': alpha value coder, off the path
+            case TAG_ALPHA: {                                                                              // decoder/YAIK_API.cpp:750-833
+                if (state >= 2) { setError(YAIK_INVALID_TAG_ID); bad = true; break; }                      // only before any 'GTIL' (:753-756)
+                if (hb.length < sizeof(AlphaHeader)) { setError(YAIK_INVALID_TAG_ID); bad = true; break; }
+                AlphaHeader ah; memcpy(&ah, body, sizeof ah);
+                if ((uint64_t)ah.streamSize > (uint64_t)(endBlock - body - sizeof ah)) { setError(YAIK_INVALID_TAG_ID); bad = true; break; }
+                // a payload is at most one byte per pixel: nothing is expanded for a larger claim
+                if (ah.streamSize == 0 || (uint64_t)ah.expectedDecompressionSize > (uint64_t)w * h) { setError(YAIK_INVALID_STREAM); bad = true; break; }
+                if (!zexpand(body + sizeof ah, ah.streamSize, ah.expectedDecompressionSize, alphaRaw, 0)) { bad = true; break; }   // DecompressData (:759)
+                const int mode = ah.parameters & 7;
+                if (mode == 7) { setError(YAIK_INVALID_ALPHA_FORMAT); bad = true; break; }
+                if (state == 0 && (mode == AlphaHeader::IS_1_BIT_USEMIPMAPMASK || mode == AlphaHeader::IS_6_BIT_USEMIPMAPMASK ||
+                                   mode == AlphaHeader::IS_6_BIT_USEMIPMAPMASK_INVERSE)) { setError(YAIK_ALPHA_FORMAT_IMPOSSIBLE); bad = true; break; }   // :779-785
+                if (mode == AlphaHeader::IS_1_BIT_USEMIPMAPMASK) { setError(YAIK_ALPHA_UNSUPPORTED_YET); bad = true; break; }   // state 1 (:799-801)
+                const bool masked = mode == AlphaHeader::IS_6_BIT_USEMIPMAPMASK || mode == AlphaHeader::IS_6_BIT_USEMIPMAPMASK_INVERSE;
+                const int32_t bb[4] = { ah.bbox.x, ah.bbox.y, ah.bbox.w, ah.bbox.h };
+                // 1-bit rows as the encoder writes them (refQuirk 0: the reference's own loop drops a byte per row)
+                if (yk_decode_alpha(s->ctx, mode, bb, alphaRaw.data(), ah.expectedDecompressionSize, masked ? mask.data() : nullptr, masked ? maskBytes : 0,
+                                    masked ? maskBox : nullptr, 0) != YK_OK) { setError(YAIK_INVALID_STREAM); bad = true; break; }
+                hasAlphaPlane = true;
+                state = 2;
+                break;
+            }
             case TAG_TILE3D: {                                                                             // decoder/YAIK_API.cpp:999-1300
                 if (state > 4) break;
                 state = 4;
@@ -231,16 +256,25 @@ bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) {
             if (yk_decode_planes(s->ctx, planes, planes + planeSize, planes + 2 * planeSize, planeSize) == YK_OK) {
                 YAIK_SCustomDataSource src;
                 src.planeR = planes; src.planeG = planes + planeSize; src.planeB = planes + 2 * planeSize; src.planeA = nullptr;
+                std::vector<uint8_t> alphaHost;
+                if (hasAlphaPlane) {                                                                    // linear alpha, strideA = w (:1306-1310)
+                    alphaHost.resize((size_t)w * h);
+                    if (yk_decode_alpha_plane(s->ctx, alphaHost.data(), alphaHost.size()) != YK_OK) { setError(YAIK_INVALID_STREAM); ua.customFree(ua.customContext, planes); break; }
+                    src.planeA = alphaHost.data();
+                }
                 src.strideR = src.strideG = src.strideB = (w / 8) * 64; src.strideA = w;
                 info->customImageOutput(info, &src);
                 res = true;
             } else setError(YAIK_INVALID_STREAM);
             ua.customFree(ua.customContext, planes);
         } else {
-            // default builder = the de-tile kernel.  The alpha value chunk ('ALPM') is not on this path, so like the reference's
-            // pCtx->alphaChannel the alpha plane is NULL and internal_imageBuilderFunc takes its RGB branch (3 B/pixel) whether or
-            // not the header says RGBA (YAIK_API.cpp:1316, YAIK_DefaultCallback.cpp:44,63); row padding is left untouched.
-            res = yk_decode_output(s->ctx, info->outputImage, (size_t)info->outputImageStride, nullptr, w) == YK_OK;
+            // default builder = the de-tile kernel.  Without an 'ALPM' chunk, like the reference's pCtx->alphaChannel the alpha plane is
+            // NULL and internal_imageBuilderFunc takes its RGB branch (3 B/pixel) whether or not the header says RGBA (YAIK_API.cpp:1316,
+            // YAIK_DefaultCallback.cpp:44,63); row padding is left untouched.
+            // with an 'ALPM' chunk: RGBA 4 B/pixel from the alpha plane kept in HBM (YAIK.h documents RGBA rows; the reference's own RGBA
+            // branch is defective)
+            res = (hasAlphaPlane ? yk_decode_output_alpha(s->ctx, info->outputImage, (size_t)info->outputImageStride)
+                                 : yk_decode_output(s->ctx, info->outputImage, (size_t)info->outputImageStride, nullptr, w)) == YK_OK;
             if (!res) setError(YAIK_INVALID_STREAM);
         }
     } while (false);

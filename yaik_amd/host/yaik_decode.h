@@ -4,10 +4,12 @@
 // types with identical layout, names and enumerator values so both sides agree on the ABI.
 //
 // On the path: file header, 'MIPM' (mask decode), 'GTIL' (gradient decode, all planes or a plane subset), '3DTL' (3-D LUT tiles, after
-// YAIK_AssignLUT), '1DTL' (range decode), terminator, the default image builder (RGB888 / RGBA8888 rows at outputImageStride) and the
+// YAIK_AssignLUT), '1DTL' (range decode), 'ALPM' (alpha values: the plane stays in HBM; RGBA 4 B/pixel rows from the default builder, a linear
+// planeA with strideA = w for a custom builder), terminator, the default image builder (RGB888 / RGBA8888 rows at outputImageStride) and the
 // custom-builder callback (8x8-tiled planes).
-// Off the path (SURVEY §8 out of scope), reported through the sticky error code instead of decoded: 'ALPM' alpha value chunks
-// (YAIK_ALPHA_UNSUPPORTED_YET); a '3DTL' chunk without an assigned LUT gives YAIK_INVALID_LUT.  Images whose sides are not multiples of 16 are refused
+// 'ALPM' keeps the reference's state rules and codes: a mipmap-mask mode at state 0 gives YAIK_ALPHA_FORMAT_IMPOSSIBLE, IS_1_BIT_USEMIPMAPMASK
+// YAIK_ALPHA_UNSUPPORTED_YET, parameters 7 YAIK_INVALID_ALPHA_FORMAT, a stream shorter than expectedDecompressionSize YAIK_INVALID_DECOMPRESSION,
+// a box outside the image or a payload shorter than the box YAIK_INVALID_STREAM.  A '3DTL' chunk without an assigned LUT gives YAIK_INVALID_LUT.  Images whose sides are not multiples of 16 are refused
 // (YAIK_INVALID_HEADER): the reference's own loops mis-stride there (decoder/YAIK_Gradient.cpp:15).
 #pragma once
 #include <stddef.h>

@@ -15,6 +15,7 @@ static const u32 TAG_GRADTILE = 0x4c495447u;   // 'G','T','I','L'  (:562)
 static const u32 TAG_TILE1D   = 0x4c544431u;   // '1','D','T','L'  (:564)
 static const u32 TAG_TILE3D   = 0x4c544433u;   // '3','D','T','L'  (EndCorrelationSearch, EncoderContext.cpp:7589-7593; reader decoder/YAIK_API.cpp:999)
 static const u32 TAG_PLANE    = 0x544e4c50u;   // 'P','L','N','T'  (written by DynamicTileEncode, EncoderContext.cpp:4541-4545; no reader)
+static const u32 TAG_ALPHA    = 0x4d504c41u;   // 'A','L','P','M'  (ProcessAlpha, EncoderContext.cpp:1600-1603; reader decoder/YAIK_API.cpp:750)
 static const u32 TAG_END      = 0xDEADBEEFu;   // terminator (EncoderContext.cpp:9779-9781)
 
 struct FileHeader {                             // YAIK_private.h:96-105
@@ -27,6 +28,13 @@ struct MipmapHeader {                           // :112-118
     BoundingBox bbox;                           // in 16x16 tiles
     u32 streamSize;                             // not written by the reference
     u8 version, mipmapLevel;
+};
+struct AlphaHeader {                            // :120-141
+    enum { IS_1_BIT_USEMIPMAPMASK = 0, IS_1_BIT_FULL = 1, IS_6_BIT_USEMIPMAPMASK = 2, IS_6_BIT_USEMIPMAPMASK_INVERSE = 3,
+           IS_6_BIT_FULL = 4, IS_6_BIT_FULL_INVERSE = 5, IS_8_BIT_FULL = 6 };
+    BoundingBox bbox;                           // pixels
+    u32 streamSize, expectedDecompressionSize;  // ZStd bytes after the header, decompressed payload bytes
+    u8 version, parameters;                     // version 1; parameters & 7 = one of the enum values
 };
 struct HeaderGradientTile {                     // :172-211
     BoundingBox bbox;
@@ -54,6 +62,7 @@ struct LUTHeader { u8 lutH[4]; u8 version, entryCount; u8 padding_extension[2]; 
 static_assert(sizeof(HeaderTile3D) == 76 && sizeof(LUTHeader) == 8, "3-D LUT chunk / file headers");
 static_assert(sizeof(FileHeader) == 12 && sizeof(HeaderBase) == 8, "file framing");
 static_assert(sizeof(MipmapHeader) == 16 && sizeof(HeaderGradientTile) == 28, "chunk headers");
+static_assert(sizeof(AlphaHeader) == 20, "alpha chunk header");
 static_assert(sizeof(PlaneTile) == 24 && sizeof(Header1D) == 20, "chunk headers");
 
 // HeaderGradientTile::getSwizzleSize (YAIK_private.h:212-276): swizzle block and tiles per block for a tile shape
