@@ -97,9 +97,13 @@ int yk_alpha_bitmap(yk_ctx* c, uint8_t* hostOut, size_t cap, size_t* nBytes);
  * yk_alpha_reject + yk_alpha_finish (the search region is their bounds, read on the device).  One kernel reduces the box of samples with
  * v >> 2 != 0; one kernel reads the box rounded to 4 once for the class flags and the 8-bit payload; binary alpha (only 0 / 255 in the box)
  * is packed again by a third kernel on the box re-aligned to 8 (make1BitStream, :317-355).  Two small readbacks (box, class) size the launches.
- * out->mode = -1 (no chunk: no alpha plane, empty box, all 255), 1 (IS_1_BIT_FULL) or 6 (IS_8_BIT_FULL); bbox = {x, y, w, h};
- * rawSize = the decompressed payload size (expectedDecompressionSize).  hostPayload may be NULL (size query); *n = rawSize.
- * Only force8Bit = 1 (what Convert passes, :9027-9028) is implemented: 0 returns YK_ERR_BAD_ARG.  Synchronises. */
+ * force8Bit = 0 (:1503-1565): analog alpha becomes IS_6_BIT_USEMIPMAPMASK_INVERSE, 63 - (v >> 2) of the box samples the mipmapMask selects
+ * (every pixel of a kept 16x16 tile, or every pixel when the kept tiles span the image), four values in three bytes; three more kernels
+ * (per-band tile prefixes from the keep flags, their scan, the pack from the u8 box) and a third readback (the selected count).
+ * Binary, all-255 and empty alpha are the same for both values of force8Bit.
+ * out->mode = -1 (no chunk: no alpha plane, empty box, all 255), 1 (IS_1_BIT_FULL), 3 (IS_6_BIT_USEMIPMAPMASK_INVERSE, force8Bit = 0) or
+ * 6 (IS_8_BIT_FULL, force8Bit = 1); bbox = {x, y, w, h}; rawSize = the decompressed payload size (expectedDecompressionSize).
+ * hostPayload may be NULL (size query); *n = rawSize.  Convert passes force8Bit = 1 (:9027-9028).  Synchronises. */
 typedef struct yk_alpha_info { int32_t mode; int32_t bbox[4]; uint32_t rawSize; } yk_alpha_info;
 int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostPayload, size_t cap, size_t* n);
 

@@ -1,5 +1,6 @@
 // 'ALPM' alpha value chunk on the device.
 //   yk_alpha_values   EncoderContext::ProcessAlpha (encoder/EncoderContext.cpp:1429-1682, make1BitStream :317-355): box, class, payload
+//                     (8-bit, 1-bit, and the 6-bit mask mode of force8Bit = false)
 //   yk_decode_alpha   Decompress1BitMaskAlign8NoMask (decoder/YAIK_Alpha.cpp:25-112), Decompress6BitTo8BitAlphaNoMask (:114-235),
 //                     Decompress6BitTo8BitAlphaUsingMipmapMask (:237-376), Decompress8BitTo8BitAlphaNoMask (:377-444): the full w x h plane
 //                     in HBM (0 outside the box), kept for yk_decode_output_alpha.
@@ -206,6 +207,57 @@ __global__ __launch_bounds__(256) void yk_ave_pack1_kernel(const int32_t* __rest
     pay[i] = (uint8_t)b;
 }
 
+// ---- force8Bit = false: IS_6_BIT_USEMIPMAPMASK_INVERSE (:1503-1565) -----------------------------------------------------------------------
+// The selected set is the reference's per-pixel mipmapMask as MipPrefilter leaves it: every pixel of a kept 16x16 tile, or every pixel when
+// the kept tiles span the image (no 'MIPM' chunk, the mask is set again to 255 at :1401).  So a box row's selected pixels are whole runs of
+// tile columns, the same for the 16 rows of a tile band, and a sample's output index follows from the keep flags alone.  bL, bR and the tile
+// edges are multiples of 4: every run is whole 4-sample groups, and a group of the box is one 3-byte group of the payload.
+__device__ __forceinline__ bool yk_ave_all_kept(const int32_t* __restrict__ b, int W, int H) { return b[0] == 0 && b[1] == 0 && b[2] == W && b[3] == H; }
+// one wave per tile band of the box: colPre[band][i] = selected samples of one band row left of tile column txB + i, bandS = per row,
+// bandCnt = per band (bandS x the band's rows in the box)
+__global__ __launch_bounds__(64) void yk_ave_band_kernel(const uint8_t* __restrict__ keep, int mtW, int mtH, const int32_t* __restrict__ bounds, int W, int H,
+                                                         int bL, int bT, int bR, int bB, int ncol, uint32_t* __restrict__ colPre, uint32_t* __restrict__ bandS,
+                                                         uint32_t* __restrict__ bandCnt) {
+    const int b = blockIdx.x, lane = threadIdx.x, ty = (bT >> 4) + b, txB = bL >> 4;
+    const bool all = yk_ave_all_kept(bounds, W, H);
+    uint32_t carry = 0;
+    for (int i0 = 0; i0 < ncol; i0 += 64) {
+        const int i = i0 + lane, tx = txB + i;
+        uint32_t v = 0;
+        if (i < ncol && tx < mtW && ty < mtH && (all || keep[(size_t)ty * mtW + tx])) v = (uint32_t)(min(bR, tx * 16 + 16) - max(bL, tx * 16));
+        uint32_t s = v;                                                    // inclusive scan over the wave
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(s, o, 64); if (lane >= o) s += t; }
+        if (i < ncol) colPre[(size_t)b * ncol + i] = carry + s - v;
+        carry += __shfl(s, 63, 64);
+    }
+    if (lane == 0) {
+        bandS[b] = carry;
+        bandCnt[b] = carry * (uint32_t)(min(bB, ty * 16 + 16) - max(bT, ty * 16));
+    }
+}
+// one thread = one 4-sample group of the u8 box the class kernel wrote (one 4-byte load) = one 3-byte group of the payload when its tile is
+// selected: index = band start + rows of the band above it x bandS + colPre + its offset in the tile's run; values 63 - (v >> 2), LSB first
+__global__ __launch_bounds__(256) void yk_ave_pack6_kernel(const uint8_t* __restrict__ box, int bL, int bT, int bw, int bh, const uint8_t* __restrict__ keep,
+                                                           int mtW, int mtH, const int32_t* __restrict__ bounds, int W, int H, int ncol, int nb,
+                                                           const uint32_t* __restrict__ colPre, const uint32_t* __restrict__ bandS,
+                                                           const uint32_t* __restrict__ bandStart, uint8_t* __restrict__ out, size_t cap) {
+    const int c = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4, r = blockIdx.y;
+    if (c >= bw || r >= bh) return;
+    const int x = bL + c, y = bT + r, tx = x >> 4, ty = y >> 4;
+    if (tx >= mtW || ty >= mtH) return;
+    if (!yk_ave_all_kept(bounds, W, H) && !keep[(size_t)ty * mtW + tx]) return;
+    const int b = ty - (bT >> 4), i = tx - (bL >> 4);
+    if (b < 0 || b >= nb || i < 0 || i >= ncol) return;
+    const uint32_t k = bandStart[b] + (uint32_t)(y - max(bT, ty * 16)) * bandS[b] + colPre[(size_t)b * ncol + i] + (uint32_t)(x - max(bL, tx * 16));
+    const size_t o = (size_t)(k >> 2) * 3;                                 // k is a multiple of 4
+    if (o + 3 > cap) return;
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(box + (size_t)r * bw + c);   // bw and c are multiples of 4
+    const uint32_t q0 = 63u - ((w >> 2) & 63u), q1 = 63u - ((w >> 10) & 63u), q2 = 63u - ((w >> 18) & 63u), q3 = 63u - (w >> 26);
+    out[o] = (uint8_t)(q0 | (q1 << 6));
+    out[o + 1] = (uint8_t)((q1 >> 2) | (q2 << 4));
+    out[o + 2] = (uint8_t)((q2 >> 4) | (q3 << 2));
+}
+
 }  // namespace
 
 extern "C" {
@@ -294,7 +346,6 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     if (!c || !out) return YK_ERR_BAD_ARG;
     out->mode = -1; out->bbox[0] = out->bbox[1] = out->bbox[2] = out->bbox[3] = 0; out->rawSize = 0;
     if (n) *n = 0;
-    if (!force8Bit) return yk_fail(c, YK_ERR_BAD_ARG, "yk_alpha_values: only force8Bit = 1 (the argument Convert passes) is implemented");
     if (c->nPlanes != 4) return YK_OK;                                                    // no alpha: no chunk (:1674-1680)
     if (!c->alphaFinished) return yk_fail(c, YK_ERR_STATE, "yk_alpha_reject + yk_alpha_finish first");
     if (c->nFrames != 1 || c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "yk_alpha_values works on a whole single image");
@@ -331,8 +382,40 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 2: the class decides the payload
     const bool analog = st[4] != 0, all1 = st[5] == 0;
     size_t bytes;
-    if (analog) {
+    const uint8_t* src = c->avPay;
+    if (analog && force8Bit) {
         out->mode = 6; bytes = (size_t)bw * bh;                                           // IS_8_BIT_FULL, payload already written
+    } else if (analog) {                                                                  // IS_6_BIT_USEMIPMAPMASK_INVERSE from the u8 box
+        if (!c->keep || (bL & 3) || (bw & 3)) return yk_fail(c, YK_ERR_STATE, "6-bit alpha: no keep flags or a box not aligned to 4");
+        const int nb = ((bB - 1) >> 4) - (bT >> 4) + 1, ncol = ((bR - 1) >> 4) - (bL >> 4) + 1;
+        const size_t nU32 = (size_t)nb * ncol + 3 * (size_t)nb + 1;
+        const size_t oPay = (nU32 * sizeof(uint32_t) + 255) & ~(size_t)255, payCap = (size_t)(bw >> 2) * 3 * bh;
+        if (c->av6Cap < oPay + payCap) {
+            YK_HIP(c, hipStreamSynchronize(c->stream));
+            if (c->av6) (void)hipFree(c->av6);
+            c->av6 = nullptr; c->av6Cap = 0;
+            YK_HIP(c, hipMalloc(&c->av6, oPay + payCap));
+            c->av6Cap = oPay + payCap;
+        }
+        uint32_t* colPre = reinterpret_cast<uint32_t*>(c->av6);
+        uint32_t* bandS = colPre + (size_t)nb * ncol;
+        uint32_t* bandCnt = bandS + nb;
+        uint32_t* bandStart = bandCnt + nb;
+        uint8_t* pay6 = c->av6 + oPay;
+        const int32_t* bounds = c->bounds + c->boundsOff;
+        hipLaunchKernelGGL(yk_ave_band_kernel, dim3((unsigned)nb), dim3(64), 0, c->stream, c->keep, c->mtW, c->mtH, bounds, W, H, bL, bT, bR, bB, ncol, colPre,
+                           bandS, bandCnt);
+        hipLaunchKernelGGL(yk_av_rowscan_kernel, dim3(1), dim3(1024), 0, c->stream, bandCnt, nb, bandStart);
+        hipLaunchKernelGGL(yk_ave_pack6_kernel, dim3((unsigned)((bw / 4 + 255) / 256), (unsigned)bh), dim3(256), 0, c->stream, c->avPay, bL, bT, bw, bh, c->keep,
+                           c->mtW, c->mtH, bounds, W, H, ncol, nb, colPre, bandS, bandStart, pay6, payCap);
+        YK_HIP(c, hipGetLastError());
+        uint32_t total = 0;
+        YK_HIP(c, hipMemcpyAsync(&total, bandStart + nb, sizeof total, hipMemcpyDeviceToHost, c->stream));
+        YK_HIP(c, hipStreamSynchronize(c->stream));                                       // readback 3: the selected count sizes the payload
+        static const size_t tail[4] = { 0, 1, 2, 3 };
+        bytes = (size_t)(total >> 2) * 3 + tail[total & 3];                                // :1549-1551 (total is a multiple of 4 here)
+        if (bytes > payCap) return yk_fail(c, YK_ERR_STATE, "6-bit alpha: selected count beyond the box");
+        out->mode = 3; src = pay6;
     } else if (all1) {
         return YK_OK;                                                                     // all 255: no chunk
     } else {                                                                              // binary: IS_1_BIT_FULL on the box re-aligned to 8
@@ -349,7 +432,7 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     if (n) *n = bytes;
     if (hostPayload) {
         if (cap < bytes) return yk_fail(c, YK_ERR_RANGE, "alpha payload buffer too small");
-        YK_HIP(c, hipMemcpyAsync(hostPayload, c->avPay, bytes, hipMemcpyDeviceToHost, c->stream));
+        YK_HIP(c, hipMemcpyAsync(hostPayload, src, bytes, hipMemcpyDeviceToHost, c->stream));
     }
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;

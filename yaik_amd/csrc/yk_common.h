@@ -143,6 +143,7 @@ struct yk_ctx {
     uint8_t* dAlpha = nullptr; size_t dAlphaBytes = 0; bool dAlphaValid = false;   // yk_decode_alpha: the w x h alpha plane of the image being decoded
     uint8_t* dAvScratch = nullptr; size_t dAvScratchBytes = 0;                      // its payload, mask and row counts
     int32_t* avState = nullptr; uint8_t* avPay = nullptr; size_t avPayCap = 0;      // yk_alpha_values: box + class flags, the payload
+    uint8_t* av6 = nullptr; size_t av6Cap = 0;                                      // its 6-bit mask mode: tile prefixes, band scan, packed payload
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
     // timing
     // timing events: a ring of YK_EV_RING sets {alpha begin, alpha end, encode begin, encode end, pack end} so that a caller can

@@ -126,7 +126,8 @@ class HipTileEncoder:
         return {"has_chunk": bool(has.value), "bounds": b, "remaining": rem.value, "tile_bbox": tb, "bitmap": out[:nb.value].copy()}
 
     def alpha_values(self, force8bit: bool = True) -> dict | None:
-        """EncoderContext::ProcessAlpha on the GPU (yk_alpha_values), after mip_prefilter(): None when no 'ALPM' chunk is written, else
+        """EncoderContext::ProcessAlpha(force8bit) on the GPU (yk_alpha_values), after mip_prefilter(); force8bit=False gives analog alpha in the
+        6-bit mask mode (3).  None when no 'ALPM' chunk is written, else
         {"mode": AlphaHeader::parameters, "bbox": (x, y, w, h), "payload": decompressed payload (u8)}."""
 
         class _Info(C.Structure):

@@ -20,7 +20,7 @@ static const int kPass[7][2] = { {4, 4}, {4, 3}, {3, 4}, {3, 3}, {3, 2}, {2, 3},
 EncoderContext::EncoderContext()
     : colorCompressionQuad(250), colorCompressionLUT3D(250), colorCompression1D(255), rangeCompression1D(15),
       mipMapTileSize(16), boundX0(0), boundY0(0), boundX1(0), boundY1(0), remainingPixels(0),
-      dumpImage(false), evaluateLUT(false), evaluateLUT2D(false), outFile(nullptr), fileOutSize(0), emitAlpha(false), device(0),
+      dumpImage(false), evaluateLUT(false), evaluateLUT2D(false), outFile(nullptr), fileOutSize(0), emitAlpha(false), alpha6Bit(false), device(0),
       original(nullptr), ctx(nullptr), bound(false), alphaDone(false), encoded(false), enc3(false), encDst(false), oneDReady(false),
       encReject(3), nextPass(0), nNibbles(0), cursor1d(0), mipHasChunk(false), alphaMode(-1), alphaBox{0, 0, 0, 0}, lutMatched(0) { correlationPatternCount3D = 0; }
 
@@ -67,7 +67,7 @@ void EncoderContext::CheckMipmapMask() {
 
 void EncoderContext::MipPrefilter(bool /*active*/) {
     if (!bound) { fail("MipPrefilter: SetImageToEncode first"); return; }
-    mipBitmap.clear(); mipHasChunk = false;
+    mipBitmap.clear(); mipHasChunk = false; mipTiles[0] = mipTiles[1] = mipTiles[2] = mipTiles[3] = 0;
     if (original->HasAlpha()) {
         if (yk_alpha_reject(ctx) != YK_OK || yk_alpha_finish(ctx, nullptr) != YK_OK) { fail("alpha reject"); return; }
     }
@@ -75,6 +75,7 @@ void EncoderContext::MipPrefilter(bool /*active*/) {
     if (yk_alpha_result(ctx, b, &has, &rem, tb) != YK_OK) { fail("yk_alpha_result"); return; }
     boundX0 = b[0]; boundY0 = b[1]; boundX1 = b[2]; boundY1 = b[3]; remainingPixels = rem; mipMapTileSize = 16; mipHasChunk = has != 0;
     if (has) {
+        for (int k = 0; k < 4; k++) mipTiles[k] = tb[k];
         mipBitmap.resize(((size_t)tb[2] * tb[3] + 7) / 8 + 8);
         size_t nb = 0;
         if (yk_alpha_bitmap(ctx, mipBitmap.data(), mipBitmap.size(), &nb) != YK_OK) { fail("yk_alpha_bitmap"); return; }
@@ -105,6 +106,15 @@ void EncoderContext::ProcessAlpha(bool force8Bit) {
     if (alphaMode < 0 || !outFile) return;
     std::string e;
     if (!yaikchunk::writeAlpha(outFile, alphaMode, alphaBox, alphaPayload.data(), alphaPayload.size(), e)) fail(("ProcessAlpha: " + e).c_str());
+}
+
+// the alpha6Bit fallback rule of the ConvertHotPath* family (ours, not the reference's): a 'MIPM' chunk with every tile bit set
+bool EncoderContext::alpha6BitDecodable() const {
+    if (!alpha6Bit || !mipHasChunk || mipBitmap.empty()) return false;
+    const size_t nBits = (size_t)mipTiles[2] * mipTiles[3];
+    for (size_t i = 0; i < nBits; i++)
+        if (!((mipBitmap[i >> 3] >> (i & 7)) & 1)) return false;
+    return nBits > 0;
 }
 
 bool EncoderContext::ensureEncoded(int rejectFactor, bool mode3, bool wantDst) {
@@ -321,7 +331,7 @@ bool EncoderContext::ConvertHotPath(FILE* f) {
     const int w = original->GetWidth(), h = original->GetHeight();
     bool ok = yaikchunk::writeFileHeader(f, w, h, original->HasAlpha());
     if (ok && original->HasAlpha()) MipPrefilter(true);
-    if (ok && emitAlpha && original->HasAlpha()) { ProcessAlpha(true); ok = err.empty(); }
+    if (ok && emitAlpha && original->HasAlpha()) { ProcessAlpha(!alpha6BitDecodable()); ok = err.empty(); }
     PrepareQuadSmooth();
     for (int i = 0; ok && i < 7; i++) {
         FittingQuadSmooth(3, original->GetPlane(0), original->GetPlane(1), original->GetPlane(2), nullptr, false, kPass[i][0], kPass[i][1]);
@@ -516,7 +526,7 @@ bool EncoderContext::ConvertHotPathBegin(FILE* f, int threads) {
     bool ok = yaikchunk::writeFileHeader(f, st->w, st->h, original->HasAlpha());
     outFile = f; fileOutSize = 0;
     if (ok && original->HasAlpha()) MipPrefilter(true);                    // 'MIPM' is not compressed: written at once
-    if (ok && emitAlpha && original->HasAlpha()) { ProcessAlpha(true); ok = err.empty(); }   // 'ALPM' (opt-in) right after it
+    if (ok && emitAlpha && original->HasAlpha()) { ProcessAlpha(!alpha6BitDecodable()); ok = err.empty(); }   // 'ALPM' (opt-in) right after it
     outFile = nullptr;                                                     // the passes only collect their raw streams
     PrepareQuadSmooth();
     for (int i = 0; ok && i < 7; i++) {

@@ -38,11 +38,16 @@ public:
     void PrepareQuadSmooth();                           // empty in the reference too (:2796)
     void MipPrefilter(bool active);                     // :1257
     // :1429-1682, on the GPU (yk_alpha_values) after MipPrefilter: the alpha VALUES.  With outFile set it appends the 'ALPM' chunk (none for
-    // an image without alpha, all-255 alpha or alpha below 4 everywhere).  Only force8Bit = true (what Convert passes, :9027-9028) is implemented.
+    // an image without alpha, all-255 alpha or alpha below 4 everywhere).  force8Bit = true is what Convert passes (:9027-9028); false writes
+    // analog alpha as IS_6_BIT_USEMIPMAPMASK_INVERSE over the pixels of the kept 16x16 tiles, exactly as the reference does.
     void ProcessAlpha(bool force8Bit);
-    // opt-in: the ConvertHotPath* family calls ProcessAlpha(true) right after MipPrefilter, like the commented-out call in Convert()
+    // opt-in: the ConvertHotPath* family calls ProcessAlpha right after MipPrefilter, like the commented-out call in Convert()
     // (:9027-9028).  Off by default: files stay byte for byte what they were.
     bool emitAlpha;
+    // opt-in with emitAlpha (not a reference option; Convert never passes false): ProcessAlpha(false) instead of ProcessAlpha(true), but only
+    // when a 'MIPM' chunk was written and every bit of its tile bitmap is set.  The decoder reads the mask of the 6-bit mask modes the way the
+    // reference does ("Mask-mode finding"), which gives the right pixels only then; otherwise the chunk is the 8-bit one.
+    bool alpha6Bit;
     int  FittingQuadSmooth(int rejectFactor, Plane* a, Plane* b, Plane* c, Image* testOutput, bool useYCoCg,
                            int tileBitSizeX, int tileBitSizeY);                           // :3710, returns TileDone
     int  DynamicTileEncode(bool mode3BitOnly, Plane* plane, Plane* dst, bool isCo, bool isCg, bool isHalfX, bool isHalfY);   // :4365
@@ -108,6 +113,7 @@ private:
     void retireOldestStage();
     bool ensureEncoded(int rejectFactor, bool mode3, bool wantDst);
     bool fail(const char* what);
+    bool alpha6BitDecodable() const;
     Image* original;
     yk_ctx* ctx;
     bool bound, alphaDone, encoded, enc3, encDst, oneDReady;
@@ -116,6 +122,7 @@ private:
     std::vector<u16> tileDefs;
     size_t nNibbles, cursor1d;
     bool mipHasChunk;
+    int mipTiles[4] = {0, 0, 0, 0};                    // MipmapHeader.bbox of the last 'MIPM' chunk, in 16-px tiles
     int alphaMode, alphaBox[4];
     std::vector<u8> alphaPayload;
     int lutMatched;

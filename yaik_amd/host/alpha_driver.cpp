@@ -1,6 +1,6 @@
 // Alpha values through the C++ drop-in, for tests:
-//   alpha_driver enc <in.bin> <out.yaik> <emitAlpha 0|1> [parallel]   ConvertHotPath (or ConvertHotPathParallel with 4 threads) with the
-//                                                                       'ALPM' opt-in off / on
+//   alpha_driver enc <in.bin> <out.yaik> <emitAlpha 0|1> [parallel] [alpha6]
+//        ConvertHotPath (or ConvertHotPathParallel with 4 threads) with the 'ALPM' opt-in off / on; alpha6 also sets alpha6Bit
 //   alpha_driver dec <in.yaik> <out.bin>                                YAIK_DecodeImage, default builder then a custom builder; out.bin =
 //        int32 {ok, errorCode, width, height, hasAlpha, bytesPerPixel, customOk, customErrorCode, customHasPlaneA, customStrideA}, the default
 //        builder's image (w * h * bytesPerPixel), then the custom builder's planeA (w * h bytes) when it had one
@@ -30,7 +30,13 @@ int main(int argc, char** argv) {
         if (!ctx->SetImageToEncode(img)) { fprintf(stderr, "%s\n", ctx->LastError()); return 3; }
         ctx->emitAlpha = atoi(argv[4]) != 0;
         FILE* f = fopen(argv[3], "wb"); if (!f) return 2;
-        const bool parallel = argc > 5 && std::string(argv[5]) == "parallel";
+        bool parallel = false;
+        for (int i = 5; i < argc; i++) {
+            const std::string opt = argv[i];
+            if (opt == "parallel") parallel = true;
+            else if (opt == "alpha6") ctx->alpha6Bit = true;
+            else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
+        }
         const bool ok = parallel ? ctx->ConvertHotPathParallel(f, 4) : ctx->ConvertHotPath(f);
         fclose(f);
         if (!ok) { fprintf(stderr, "ConvertHotPath: %s\n", ctx->LastError()); return 4; }
