@@ -293,7 +293,9 @@ int  yk_gather_maps_all(yk_ctx* const* ctxs, void* const* comms, int n, int root
 
 /* ---- decode side: the loops behind YAIK_DecodeImage's chunk switch (decoder/YAIK_API.cpp:731-1303) ----
  * Buffers mirror YAIK_Instance (include/YAIK_private.h:26-54): planeR/G/B u8 in 8x8 tiles, mapRGB lattice,
- * tile4x4Mask.  Width/height multiples of 16 (the reference loops mis-stride otherwise, YAIK_Gradient.cpp:15). */
+ * tile4x4Mask.  Width/height: the sizes the encoder accepts, multiples of 8 from 8 to 32760.  At sides of 8 (mod 16) the decode follows the
+ * project's consistent reading, not the reference's mis-strided loops (YAIK_Gradient.cpp:15): tiles that reach past the right or bottom
+ * edge are skipped and consume nothing.  Other sizes fail with YK_ERR_BAD_ARG. */
 int yk_decode_begin(yk_ctx* c, int w, int h);
 /* DecompressGradient16x16 .. 4x4 (decoder/YAIK_Gradient.cpp:28,203,401,599,800,999,1208), planeBit 7.
  * bitmap = swizzled tile bitmap, rgb = corner stream AFTER PaletteDecompressor (0..255). Host pointers. */

@@ -34,7 +34,7 @@ __device__ __forceinline__ uint8_t yk_av_pixel(size_t i, int x, int y, const uin
     if (mode == 1 && refQuirk) {
         const long long rel = (long long)i - ((long long)by * W + bx);
         const int blk = bw >> 3;
-        if (rel >= 0) {
+        if (rel >= 0 && W > 8) {                                                // W = 8: a row holds w/8 - 1 = 0 bytes
             const long long r = rel / (W - 8), o = rel % (W - 8);
             if (r < bh && o < 8ll * (blk - 1)) {
                 const size_t byte = (size_t)r * (blk - 1) + (size_t)(o >> 3);
@@ -58,20 +58,27 @@ __device__ __forceinline__ uint8_t yk_av_pixel(size_t i, int x, int y, const uin
     }
     return v;
 }
-// one thread = 16 consecutive pixels of the plane (W is a multiple of 16: one row) and one 16-byte store
+// one thread = 16 consecutive pixels of the flat plane and one 16-byte store (the plane is w * h bytes, a multiple of 64).  W a multiple of 16:
+// the 16 pixels lie in one row.  RAGGED (W = 8 mod 16): each half of 8 pixels lies in one row, the second half may start the next row
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void yk_av_decode_kernel(const uint8_t* __restrict__ pay, size_t n, int mode, int refQuirk, int bx, int by, int bw, int bh,
                                                            int W, int H, uint8_t* __restrict__ out) {
     const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
     if (i0 >= (size_t)W * H) return;
-    const int y = (int)((uint32_t)i0 / (uint32_t)W), x0 = (int)(i0 - (size_t)y * W);   // one 32-bit divide per thread (w * h < 2^31): its 16 pixels share a row
     uint32_t word[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        uint32_t v = 0;
+    for (int hf = 0; hf < 2; hf++) {
+        if (!RAGGED && hf) break;
+        const size_t ih = i0 + (RAGGED ? 8 * hf : 0);
+        const int y = (int)((uint32_t)ih / (uint32_t)W), x0 = (int)(ih - (size_t)y * W);   // one 32-bit divide per row piece (w * h < 2^31)
 #pragma unroll
-        for (int k = 0; k < 4; k++)
-            v |= (uint32_t)yk_av_pixel(i0 + q * 4 + k, x0 + q * 4 + k, y, pay, n, mode, refQuirk, bx, by, bw, bh, W) << (8 * k);
-        word[q] = v;
+        for (int q = (RAGGED ? 2 * hf : 0); q < (RAGGED ? 2 * hf + 2 : 4); q++) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                v |= (uint32_t)yk_av_pixel(i0 + q * 4 + k, x0 + (int)(i0 + q * 4 + k - ih), y, pay, n, mode, refQuirk, bx, by, bw, bh, W) << (8 * k);
+            word[q] = v;
+        }
     }
     *reinterpret_cast<uint4*>(out + i0) = make_uint4(word[0], word[1], word[2], word[3]);
 }
@@ -319,8 +326,8 @@ int yk_decode_alpha(yk_ctx* c, int mode, const int32_t bbox[4], const uint8_t* p
         hipLaunchKernelGGL(yk_av_maskdecode_kernel, dim3(bh), dim3(64), 0, c->stream, S + oPay, n, S + oMask, maskBytes, base, stride, bx, by, bw,
                            mode == 3 ? 1 : 0, rowStart, W, c->dAlpha);
     } else {
-        hipLaunchKernelGGL(yk_av_decode_kernel, dim3((unsigned)((plane / 16 + 255) / 256)), dim3(256), 0, c->stream, S + oPay, n, mode, refQuirk ? 1 : 0,
-                           bx, by, bw, bh, W, H, c->dAlpha);
+        hipLaunchKernelGGL((W & 15) ? yk_av_decode_kernel<true> : yk_av_decode_kernel<false>, dim3((unsigned)((plane / 16 + 255) / 256)), dim3(256), 0,
+                           c->stream, S + oPay, n, mode, refQuirk ? 1 : 0, bx, by, bw, bh, W, H, c->dAlpha);
     }
     YK_HIP(c, hipGetLastError());
     c->dAlphaValid = true;

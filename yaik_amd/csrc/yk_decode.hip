@@ -711,7 +711,7 @@ __global__ __launch_bounds__(256) void yk_dec_detile_kernel(const uint8_t* __res
                                                             const uint8_t* __restrict__ alpha, int strideA, uint8_t* __restrict__ out, size_t stride) {
     // one thread = 4 pixels of a row (half a tile row): one 4-byte load per plane, 12 (RGB) or 16 (RGBA) output bytes
     const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;                               // w is a multiple of 16
+    if (x >= w || y >= h) return;                               // w is a multiple of 8: a thread's 4 pixels lie inside one row
     const size_t ti = ((size_t)(y >> 3) * tileW + (x >> 3)) * 64 + (y & 7) * 8 + (x & 7);
     const uint32_t r = *reinterpret_cast<const uint32_t*>(planes + ti), g = *reinterpret_cast<const uint32_t*>(planes + planeSize + ti),
                    b = *reinterpret_cast<const uint32_t*>(planes + 2 * planeSize + ti);
@@ -789,7 +789,9 @@ static int yk_dec_settle(yk_ctx* c) {
 
 int yk_decode_begin(yk_ctx* c, int w, int h) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (w < 16 || h < 16 || (w & 15) || (h & 15) || w > 32752 || h > 32752) return yk_fail(c, YK_ERR_BAD_ARG, "decode needs width/height multiples of 16");
+    // the sizes the encoder accepts (yk_set_image).  At sides of 8 (mod 16) the 8x8-tiled planes have an odd tileW = w >> 3, the tile4x4Mask stride
+    // stays (w + 15) >> 4 (its last byte of a row holds one 8x8 tile) and every tile that reaches past the right or bottom edge is skipped
+    if (w < 8 || h < 8 || (w & 7) || (h & 7) || w > 32760 || h > 32760) return yk_fail(c, YK_ERR_BAD_ARG, "decode needs width/height multiples of 8 in 8..32760");
     YK_HIP(c, hipSetDevice(c->device));
     const size_t lat = (size_t)(w / 4 + 1) * (h / 4 + 1);
     if (!c->dPlanes || c->dw != w || c->dh != h) {                             // a stream of images of one shape keeps its buffers: only the clears below

@@ -931,7 +931,7 @@ __device__ __forceinline__ bool yk_dl_tile(const uint32_t* __restrict__ map, siz
     const uint32_t blk = (uint32_t)pos / (uint32_t)g.bitCount, t = (uint32_t)pos % (uint32_t)g.bitCount;
     x0 = (int)(blk % (uint32_t)g.xBB) * g.bigX + (int)(t % (uint32_t)g.tilesPerRow) * (1 << g.sx);
     y0 = (int)(blk / (uint32_t)g.xBB) * g.bigY + (int)(t / (uint32_t)g.tilesPerRow) * (1 << g.sy);
-    return x0 < w && y0 < h;
+    return x0 + (1 << g.sx) <= w && y0 + (1 << g.sy) <= h;                   // a tile that reaches past the right or bottom edge is skipped
 }
 __device__ __forceinline__ bool yk_dl_marked(const uint8_t* __restrict__ tile4, int stride4, int gx, int gy) {
     const int cx = gx >> 2, cy = gy >> 2;

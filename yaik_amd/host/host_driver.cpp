@@ -9,6 +9,8 @@
 //                                                   i modulo the devices present; distinct devices are gathered by one RCCL transfer) next to the whole-image passes
 //        host_driver <in.bin> <out.blobs> pp        the six plane-subset 4x4 passes of Convert() (:9261-9415) after the RGB passes, written
 //                                                   as a .yaik stream and decoded back (see run_partial below)
+//        host_driver decode <out.blobs> <a.yaik> [<b.yaik> ...]   the .yaik files decoded in turn through ONE decode slot (YAIK_Init(1)),
+//                                                   default builder: blobs seq_info_<i> (int32 ok, errorCode, width, height, bytesPerPixel) and seq_image_<i>
 // With the 4th argument the image is also converted to a .yaik stream (ConvertHotPath) and decoded back through the
 // YAIK_* decoder API, the way an application would use the two libraries.
 #include <cstdio>
@@ -198,8 +200,42 @@ static int run_lut(EncoderContext* ctx, Image* img, int w, int h, int np, const 
     return 0;
 }
 
+// one slot, several streams of different sizes: the slot's buffers follow the size of every image
+static int run_decode_sequence(int n, char** files) {
+    YAIK_LIB lib = YAIK_Init(1, nullptr);
+    if (!lib) return 5;
+    for (int i = 0; i < n; i++) {
+        FILE* fi = fopen(files[i], "rb"); if (!fi) return 2;
+        fseek(fi, 0, SEEK_END); const long len = ftell(fi); fseek(fi, 0, SEEK_SET);
+        std::vector<u32> stream(((size_t)len + 3) / 4 + 1);
+        if (fread(stream.data(), 1, (size_t)len, fi) != (size_t)len) return 2;
+        fclose(fi);
+        int info[5] = { 0, 0, 0, 0, 0 };
+        std::vector<u8> outImg;
+        YAIK_SDecodedImage di;
+        if (YAIK_DecodeImagePre(lib, stream.data(), (u32)len, &di)) {
+            const int bpp = di.hasAlpha ? 4 : 3;
+            info[2] = di.width; info[3] = di.height; info[4] = bpp;
+            outImg.assign((size_t)di.width * di.height * bpp, 0);
+            di.outputImage = outImg.data(); di.outputImageStride = di.width * bpp;
+            info[0] = YAIK_DecodeImage(stream.data(), (u32)len, &di) ? 1 : 0;
+        }
+        info[1] = (int)YAIK_GetErrorCode();
+        blob(nm("seq_info", i), info, sizeof info);
+        blob(nm("seq_image", i), outImg.data(), outImg.size());
+    }
+    YAIK_Release(lib);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: host_driver in.bin out.blobs [mode3]\n"); return 2; }
+    if (argc > 3 && std::string(argv[1]) == "decode") {
+        gOut = fopen(argv[2], "wb"); if (!gOut) return 2;
+        const int rc = run_decode_sequence(argc - 3, argv + 3);
+        fclose(gOut);
+        return rc;
+    }
     const bool mode3 = argc > 3 && atoi(argv[3]) != 0;
     FILE* fi = fopen(argv[1], "rb"); if (!fi) return 2;
     int hdr[3]; if (fread(hdr, 4, 3, fi) != 3) return 2;

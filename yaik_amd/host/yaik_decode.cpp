@@ -97,7 +97,7 @@ bool YAIK_DecodeImagePre(YAIK_LIB lib, void* stream, uint32_t length, YAIK_SDeco
     if (!lib || lib != gLib) { setError(YAIK_INVALID_LIBRARYCTX); return false; }
     const FileHeader* h = (const FileHeader*)stream;
     if (!h || length <= sizeof(FileHeader)) { setError(YAIK_INVALID_STREAM); return false; }
-    if (h->tag != TAG_FILE || (h->width & 15) || (h->height & 15) || h->width == 0 || h->height == 0) { setError(YAIK_INVALID_HEADER); return false; }
+    if (h->tag != TAG_FILE || (h->width & 7) || (h->height & 7) || h->width == 0 || h->height == 0) { setError(YAIK_INVALID_HEADER); return false; }
     Slot* s = nullptr;
     { std::lock_guard<std::mutex> g(gLib->lock); if (!gLib->freeStack.empty()) { s = gLib->freeStack.back(); gLib->freeStack.pop_back(); } }
     if (!s) { setError(YAIK_NO_EMPTYDECODE_SLOT); return false; }
@@ -141,7 +141,7 @@ bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) {
                 if (mh.mipmapLevel != 4) { setError(YAIK_INVALID_MIPMAP_LEVEL); bad = true; break; }         // only level 4 is implemented (YAIK_Mipmap.cpp:53-54)
                 const size_t need = ((size_t)mh.bbox.w * mh.bbox.h + 7) / 8;
                 if (mh.bbox.w <= 0 || mh.bbox.h <= 0 || body + sizeof mh + need > endBlock) { setError(YAIK_INVALID_STREAM); bad = true; break; }
-                mask.assign((size_t)w * h / 8 + 64, 0);
+                mask.assign((size_t)((w + 15) >> 4) * ((h + 15) >> 4) * 32 + 64, 0);                            // the tile grid, clipped edge tiles included
                 if (yk_decode_mask(s->ctx, body + sizeof mh, mh.bbox.w, mh.bbox.h, mask.data(), mask.size()) != YK_OK) { setError(YAIK_INVALID_STREAM); bad = true; break; }
                 maskBytes = (size_t)mh.bbox.w * mh.bbox.h * 32;                                             // pCtx->mipMapMask, box in pixels (YAIK_Mipmap.cpp:35-39)
                 maskBox[0] = mh.bbox.x << 4; maskBox[1] = mh.bbox.y << 4; maskBox[2] = mh.bbox.w << 4; maskBox[3] = mh.bbox.h << 4;

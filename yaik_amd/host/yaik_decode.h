@@ -9,8 +9,9 @@
 // custom-builder callback (8x8-tiled planes).
 // 'ALPM' keeps the reference's state rules and codes: a mipmap-mask mode at state 0 gives YAIK_ALPHA_FORMAT_IMPOSSIBLE, IS_1_BIT_USEMIPMAPMASK
 // YAIK_ALPHA_UNSUPPORTED_YET, parameters 7 YAIK_INVALID_ALPHA_FORMAT, a stream shorter than expectedDecompressionSize YAIK_INVALID_DECOMPRESSION,
-// a box outside the image or a payload shorter than the box YAIK_INVALID_STREAM.  A '3DTL' chunk without an assigned LUT gives YAIK_INVALID_LUT.  Images whose sides are not multiples of 16 are refused
-// (YAIK_INVALID_HEADER): the reference's own loops mis-stride there (decoder/YAIK_Gradient.cpp:15).
+// a box outside the image or a payload shorter than the box YAIK_INVALID_STREAM.  A '3DTL' chunk without an assigned LUT gives YAIK_INVALID_LUT.  Images whose sides are not multiples of 8 are refused
+// (YAIK_INVALID_HEADER).  Sides of 8 (mod 16) decode with the project's consistent reading of the format, not through the reference's
+// mis-strided loops (decoder/YAIK_Gradient.cpp:15).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
