@@ -77,6 +77,27 @@ int yk_bind_device_planes(yk_ctx* c, const int32_t* const devPlanes[4], int stri
  * lies outside; callers that bind device memory and cannot vouch for its contents call yk_validate_planes: *nOutOfRange = samples outside 0..255
  * in the bound planes (all frames of a batch; one streaming pass, synchronises). */
 int yk_validate_planes(yk_ctx* c, size_t* nOutOfRange);
+/* 8-bit interleaved pixels (new; the pixels Image::LoadPNG widens on the host, encoder/Image.cpp:200-229): one kernel writes the handle's OWN
+ * planes (the buffer yk_upload_planes fills, same layout) from rows of `channels` (3 = RGB, 4 = RGBA) bytes per pixel at a pitch of rowBytes:
+ * plane p at (x, y) = pixels[y * rowBytes + x * channels + p] for p < nPlanes.  Four channels into 3 planes drop the 4th byte (RGBX).  For a
+ * stripe the rows start at the stripe's first owned row and hold h + haloRows rows, as for planes.  Afterwards the handle is in the state
+ * yk_upload_planes leaves (same flags reset): every consumer works unchanged.  There is no validation pass (8-bit samples are always in
+ * range) and no allocation while the shape fits the buffers the handle already holds.  Any base address and pitch is accepted: a source
+ * whose base and rowBytes (and frameBytes) are multiples of 16 is read through aligned pointers, any other one through byte pointers with no
+ * alignment assumed (on gfx950 both read one 12- or 16-byte load per 4 pixels).
+ * Errors: YK_ERR_BAD_ARG for a NULL pointer, channels not 3 or 4, channels < nPlanes, rowBytes < w * channels (and, for a batch, frameBytes
+ * < rowBytes * fullH); YK_ERR_STATE before yk_set_image.  On any failure no planes are bound afterwards, as with yk_upload_planes' refusal.
+ * yk_upload_pixels_u8: host pixels, one 2-D host-to-device copy into a grow-only 8-bit staging buffer of the handle, then the kernel.  Single
+ * images and stripes only (YK_ERR_STATE for batches, like yk_upload_planes).  Returns when hostPixels may be reused. */
+int yk_upload_pixels_u8(yk_ctx* c, const uint8_t* hostPixels, size_t rowBytes, int channels);
+/* yk_load_device_pixels_u8: pixels in HBM on the handle's device; the kernel only, no host synchronisation.  With nFrames > 1 (yk_set_batch)
+ * frame f starts at devPixels + f * frameBytes (frameBytes >= rowBytes * fullH); frameBytes is ignored for one frame.
+ * ORDERING is the caller's, as for the yk_decode_*_device entry points: the source is read on THIS handle's stream, and nothing orders that
+ * stream behind the producer's.  Order the producer first (yk_stream_wait_for(c, producerStream), or a host fence such as synchronising the
+ * producer's stream), and leave the source unchanged until the handle's stream has passed the call (yk_stream_handoff(c, consumerStream),
+ * yk_synchronize, or a getter that synchronises).  Unlike with yk_bind_device_planes, the source may be reused after that: the planes the
+ * encode reads are the handle's own. */
+int yk_load_device_pixels_u8(yk_ctx* c, const uint8_t* devPixels, size_t rowBytes, size_t frameBytes, int channels);
 
 /* ---- a9  alpha tile-reject:  EncoderContext::MipPrefilter (EncoderContext.cpp:1257-1427) -----
  * stage 1 (per stripe): per aligned 16x16 block "all 256 alphas == 0" + bounding box of kept blocks. */
@@ -392,7 +413,8 @@ enum { YK_STAGE_CORNERS = 0,       /* yk_gradient_corners: lattice clear + owner
        YK_STAGE_DEC_GRADIENT = 3,  /* yk_decode_gradient: owner / corner / scan / render kernels of one pass per interval */
        YK_STAGE_DEC_1D = 4,        /* yk_decode_1d: count / scans / yk_dec1d_kernel */
        YK_STAGE_DEC_DETILE = 5,    /* yk_decode_output: yk_dec_detile_kernel */
-       YK_STAGE_LUT3D = 6 };       /* yk_lut_search: yk_lut_search_kernel (one interval per tile shape) */
+       YK_STAGE_LUT3D = 6,         /* yk_lut_search: yk_lut_search_kernel (one interval per tile shape) */
+       YK_STAGE_UNPACK = 7 };      /* yk_upload_pixels_u8 / yk_load_device_pixels_u8: yk_unpack_u8_kernel (the host copy is outside the interval) */
 int yk_stage_ms(yk_ctx* c, int stage, float* msSum, int* intervals);
 
 /* ---- diagnostics: the MEASURED HBM roof of this device (roofline fractions are quoted against the 8 TB/s specification

@@ -45,6 +45,8 @@ SIGNATURES = {
     "yk_upload_planes": (C.c_int, [vp, C.POINTER(vp), C.c_int]),
     "yk_bind_device_planes": (C.c_int, [vp, C.POINTER(vp), C.c_int]),
     "yk_validate_planes": (C.c_int, [vp, szp]),
+    "yk_upload_pixels_u8": (C.c_int, [vp, vp, sz, C.c_int]),
+    "yk_load_device_pixels_u8": (C.c_int, [vp, vp, sz, sz, C.c_int]),
     "yk_alpha_reject": (C.c_int, [vp]),
     "yk_get_stripe_bbox": (C.c_int, [vp, vp]),
     "yk_alpha_finish": (C.c_int, [vp, vp]),

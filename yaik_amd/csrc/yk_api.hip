@@ -201,11 +201,12 @@ void yk_destroy(yk_ctx* c) {
     yk_lut_destroy(c);
     yk_lut_dec_destroy(c);
     auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-    F(c->ownedPlanes); F(c->dPlanes); F(c->dMapRGB); F(c->dLatticeOwner); F(c->dTile4); F(c->dScratch); F(c->dLoaded); F(c->dAlpha); F(c->dAvScratch); F(c->avState); F(c->avPay); F(c->av6);
+    F(c->ownedPlanes); F(c->pxStage); F(c->dPlanes); F(c->dMapRGB); F(c->dLatticeOwner); F(c->dTile4); F(c->dScratch); F(c->dLoaded); F(c->dAlpha); F(c->dAvScratch); F(c->avState); F(c->avPay); F(c->av6);
     for (int r = 0; r < YK_EV_RING; r++) for (int i = 0; i < 5; i++) if (c->evRing[r][i]) (void)hipEventDestroy(c->evRing[r][i]);
     for (int st = 0; st < YK_NUM_STAGES; st++) for (int k = 0; k < YK_STAGE_RING; k++) for (int i = 0; i < 2; i++) if (c->stEv[st][k][i]) (void)hipEventDestroy(c->stEv[st][k][i]);
     if (c->frameGraph) (void)hipGraphExecDestroy(c->frameGraph);
     if (c->evHandoff) (void)hipEventDestroy(c->evHandoff);
+    if (c->evPixCopy) (void)hipEventDestroy(c->evPixCopy);
     if (c->evFusedAfter) (void)hipEventDestroy(c->evFusedAfter);
     if (c->auxStream) (void)hipStreamDestroy(c->auxStream);
     if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
@@ -393,6 +394,83 @@ int yk_bind_device_batch(yk_ctx* c, const int32_t* const frame0Planes[4], int st
     c->strideElems = strideElems;
     c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
     return YK_OK;
+}
+
+// ---- 8-bit interleaved pixels -> the handle's own planes (the kernel: yk_pixels.hip) -----------------------
+static void yk_unbind_planes(yk_ctx* c) { for (int i = 0; i < 4; i++) { c->B.plane[i] = nullptr; c->plane[i] = nullptr; } }
+
+static int yk_pixels_check(yk_ctx* c, const uint8_t* px, size_t rowBytes, int channels) {
+    if (!px) return yk_fail(c, YK_ERR_BAD_ARG, "null pixels");
+    if (channels != 3 && channels != 4) return yk_fail(c, YK_ERR_BAD_ARG, "channels must be 3 (RGB) or 4 (RGBA)");
+    if (!c->tileCount) return yk_fail(c, YK_ERR_STATE, "yk_set_image first");
+    if (channels < c->nPlanes) return yk_fail(c, YK_ERR_BAD_ARG, "3-channel pixels cannot fill 4 planes");
+    if (rowBytes < (size_t)c->fullW * channels) return yk_fail(c, YK_ERR_BAD_ARG, "rowBytes must cover a row of pixels (>= w * channels)");
+    return YK_OK;
+}
+
+// grow-only: while the shape fits, the owned planes keep their address (a replayed yk_encode_frame graph then reads the new contents)
+static int yk_own_planes(yk_ctx* c, size_t bytes) {
+    if (c->ownedPlanesBytes >= bytes) return YK_OK;
+    if (c->ownedPlanes) { YK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->ownedPlanes); c->ownedPlanes = nullptr; c->ownedPlanesBytes = 0; }
+    YK_HIP(c, hipMalloc(&c->ownedPlanes, bytes));
+    c->ownedPlanesBytes = bytes;
+    return YK_OK;
+}
+
+// the state yk_upload_planes (one frame) / yk_bind_device_batch (frames) leave: plane p of frame f at ownedPlanes + f * frameElems + p * planeElems
+static void yk_bind_owned(yk_ctx* c, size_t planeElems, size_t frameElems) {
+    for (int i = 0; i < 4; i++) c->B.plane[i] = i < c->nPlanes ? c->ownedPlanes + (size_t)i * planeElems : nullptr;
+    c->fs.plane = c->nFrames > 1 ? frameElems : 0;
+    yk_rebase(c, c->curFrame < c->nFrames ? c->curFrame : 0);
+    c->strideElems = c->fullW;
+    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+}
+
+static int yk_upload_pixels_run(yk_ctx* c, const uint8_t* hostPixels, size_t rowBytes, int channels) {
+    int rc = yk_pixels_check(c, hostPixels, rowBytes, channels); if (rc) return rc;
+    if (c->nFrames != 1) return yk_fail(c, YK_ERR_STATE, "batches load device pixels (yk_load_device_pixels_u8)");
+    YK_HIP(c, hipSetDevice(c->device));
+    const size_t rows = (size_t)c->h + c->halo, planeElems = rows * c->fullW, rowPx = (size_t)c->fullW * channels;
+    const size_t pitch = (rowPx + 15) & ~(size_t)15;                           // 16-byte rows: the kernel's fast path
+    rc = yk_own_planes(c, planeElems * c->nPlanes * sizeof(int32_t)); if (rc) return rc;
+    if (c->pxStageBytes < pitch * rows) {
+        if (c->pxStage) { YK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pxStage); c->pxStage = nullptr; c->pxStageBytes = 0; }
+        YK_HIP(c, hipMalloc(&c->pxStage, pitch * rows));
+        c->pxStageBytes = pitch * rows;
+    }
+    if (rowBytes == pitch) YK_HIP(c, hipMemcpyAsync(c->pxStage, hostPixels, (rows - 1) * pitch + rowPx, hipMemcpyHostToDevice, c->stream));
+    else YK_HIP(c, hipMemcpy2DAsync(c->pxStage, pitch, hostPixels, rowBytes, rowPx, rows, hipMemcpyHostToDevice, c->stream));
+    if (!c->evPixCopy) YK_HIP(c, hipEventCreateWithFlags(&c->evPixCopy, hipEventDisableTiming));
+    YK_HIP(c, hipEventRecord(c->evPixCopy, c->stream));
+    rc = yk_launch_unpack_u8(c, c->pxStage, pitch, 0, channels, (int)rows, 1, c->ownedPlanes, planeElems, 0); if (rc) return rc;
+    yk_bind_owned(c, planeElems, 0);
+    YK_HIP(c, hipEventSynchronize(c->evPixCopy));                               // the copy has read hostPixels: the caller may reuse them
+    return YK_OK;
+}
+
+static int yk_load_device_pixels_run(yk_ctx* c, const uint8_t* devPixels, size_t rowBytes, size_t frameBytes, int channels) {
+    int rc = yk_pixels_check(c, devPixels, rowBytes, channels); if (rc) return rc;
+    if (c->nFrames > 1 && frameBytes < rowBytes * (size_t)c->fullH) return yk_fail(c, YK_ERR_BAD_ARG, "frameBytes must cover a frame (>= rowBytes * fullH)");
+    YK_HIP(c, hipSetDevice(c->device));
+    const size_t rows = (size_t)c->h + c->halo, planeElems = rows * c->fullW, frameElems = planeElems * c->nPlanes;
+    rc = yk_own_planes(c, frameElems * c->nFrames * sizeof(int32_t)); if (rc) return rc;
+    rc = yk_launch_unpack_u8(c, devPixels, rowBytes, frameBytes, channels, (int)rows, c->nFrames, c->ownedPlanes, planeElems, frameElems); if (rc) return rc;
+    yk_bind_owned(c, planeElems, frameElems);
+    return YK_OK;
+}
+
+int yk_upload_pixels_u8(yk_ctx* c, const uint8_t* hostPixels, size_t rowBytes, int channels) {
+    if (!c) return YK_ERR_BAD_ARG;
+    const int rc = yk_upload_pixels_run(c, hostPixels, rowBytes, channels);
+    if (rc) yk_unbind_planes(c);                                                // as yk_upload_planes on its refusal: nothing bound
+    return rc;
+}
+
+int yk_load_device_pixels_u8(yk_ctx* c, const uint8_t* devPixels, size_t rowBytes, size_t frameBytes, int channels) {
+    if (!c) return YK_ERR_BAD_ARG;
+    const int rc = yk_load_device_pixels_run(c, devPixels, rowBytes, frameBytes, channels);
+    if (rc) yk_unbind_planes(c);
+    return rc;
 }
 
 // ---- alpha -----------------------------------------------------------------------------------------

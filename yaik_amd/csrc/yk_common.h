@@ -11,7 +11,7 @@
 #define YK_LROWS    65
 #define YK_EV_RING  64
 #define YK_SLOT     32      // bytes of nibble slot per 8x8 tile-plane (64 nibbles)
-#define YK_NUM_STAGES 7     // YK_STAGE_* of include/yaik_hip.h
+#define YK_NUM_STAGES 8     // YK_STAGE_* of include/yaik_hip.h
 #define YK_STAGE_RING 16
 
 // Batches: one handle can hold nFrames images of one shape; every per-image array is allocated nFrames times back to back and
@@ -83,6 +83,8 @@ struct yk_ctx {
     const int32_t* plane[4] = {nullptr, nullptr, nullptr, nullptr};
     int strideElems = 0;
     int32_t* ownedPlanes = nullptr; size_t ownedPlanesBytes = 0;
+    uint8_t* pxStage = nullptr; size_t pxStageBytes = 0;   // yk_upload_pixels_u8: grow-only HBM copy of the host's 8-bit rows (16-byte pitch)
+    hipEvent_t evPixCopy = nullptr;                         // ... recorded behind that copy: the call returns once the host rows are read
     // alpha
     uint8_t* keep = nullptr;            // mtW*mtH
     int32_t* bounds = nullptr;          // 16 ints: [0..4] the host-combined box of a striped image + its discard flag (yk_alpha_finish), [8..11] the box yk_alpha_kernel accumulates
@@ -176,6 +178,8 @@ int yk_launch_alpha_finish(yk_ctx* c, const int32_t* globalBBox);
 int yk_launch_encode(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst, bool batch = false);
 int yk_launch_pack(yk_ctx* c, bool batch = false);
 int yk_launch_corners(yk_ctx* c);
+int yk_launch_unpack_u8(yk_ctx* c, const uint8_t* src, size_t rowBytes, size_t frameBytes, int channels, int rows, int nFrames,
+                        int32_t* dst, size_t planeElems, size_t frameElems);   // yk_pixels.hip
 int yk_corners_finish(yk_ctx* c);                         // reads the corner streams' lengths back if that is still pending (synchronises)
 void yk_lut_dec_destroy(yk_ctx* c);
 void yk_lut_destroy(yk_ctx* c);                          // frees the 3-D LUT bank and streams (yk_lut3d.hip)

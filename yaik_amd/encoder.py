@@ -9,6 +9,7 @@ yaik_amd/host/ (the reference is compiled C++, so that is the drop-in; this modu
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -27,6 +28,47 @@ def _chk(h, rc: int, L=None):
         owner = L or _HANDLE_LIB.get(getattr(h, "value", h)) or lib()
         msg = owner.yk_last_error(h)
         raise YaikError(f"yaik_hip error {rc}: {msg.decode() if msg else '?'}")
+
+
+class PixelLayout(NamedTuple):
+    """How the 8-bit entry points (yk_upload_pixels_u8 / yk_load_device_pixels_u8) read an interleaved array: u8_pixel_layout."""
+    frames: int
+    rows: int
+    w: int
+    channels: int           # bytes per pixel: 3 (RGB) or 4 (RGBA)
+    n_planes: int           # planes filled: the first n_planes bytes of every pixel
+    row_bytes: int          # row pitch
+    frame_bytes: int        # frame stride (rows * row_bytes for a single image, where the library ignores it)
+
+
+def u8_pixel_layout(pixels, n_planes: int | None = None, batch: bool = False) -> PixelLayout:
+    """Layout of numpy or torch uint8 pixels [rows, w, C] (batch=True: [F, rows, w, C]), C = 3 or 4, n_planes (default C) <= C.  Row pitch and
+    frame stride are the array's own strides, so padded or row-sliced views need no copy; the bytes of a row must be contiguous (channel
+    stride 1, pixel stride C).  Reads only dtype, shape and strides."""
+    if hasattr(pixels, "data_ptr"):
+        import torch
+        if pixels.dtype != torch.uint8:
+            raise TypeError(f"8-bit pixels expected, got {pixels.dtype}")
+        shape, strides = tuple(pixels.shape), tuple(pixels.stride())      # elements = bytes for uint8
+    else:
+        if pixels.dtype != np.uint8:
+            raise TypeError(f"8-bit pixels expected, got {pixels.dtype}")
+        shape, strides = pixels.shape, pixels.strides
+    if len(shape) != (4 if batch else 3):
+        raise ValueError(f"pixels must be [{'F, ' if batch else ''}rows, w, C], got shape {tuple(shape)}")
+    rows, w, ch = shape[-3:]
+    n = ch if n_planes is None else int(n_planes)
+    if ch not in (3, 4) or n not in (3, 4) or n > ch:
+        raise ValueError(f"C must be 3 (RGB) or 4 (RGBA) and n_planes 3 or 4, at most C; got C = {ch}, n_planes = {n}")
+    if strides[-1] != 1 or strides[-2] != ch:
+        raise ValueError(f"the bytes of a row must be contiguous (channel stride 1, pixel stride {ch}); got strides {tuple(strides)}")
+    row_bytes = strides[-3]
+    if row_bytes < w * ch:
+        raise ValueError(f"row stride {row_bytes} is shorter than a row of {w * ch} bytes")
+    frames, frame_bytes = (shape[0], strides[0]) if batch else (1, rows * row_bytes)
+    if frames > 1 and frame_bytes < rows * row_bytes:
+        raise ValueError(f"frame stride {frame_bytes} is shorter than a frame of {rows * row_bytes} bytes")
+    return PixelLayout(frames, rows, w, ch, n, row_bytes, frame_bytes)
 
 
 class HipTileEncoder:
@@ -85,6 +127,30 @@ class HipTileEncoder:
             _chk(self._h, L.yk_upload_planes(self._h, ptrs, w))
             _chk(self._h, L.yk_synchronize(self._h))
         self._keepalive = planes
+
+    def set_image_u8(self, pixels, full_h: int | None = None, y0: int = 0, halo_rows: int = 0, n_planes: int | None = None):
+        """8-bit interleaved pixels [rows, w, C] (C = 3 RGB or 4 RGBA; rows = owned rows + halo_rows), widened on the GPU into the handle's
+        own int32 planes: numpy uint8 is uploaded (yk_upload_pixels_u8: one byte per sample crosses PCIe), a torch uint8 CUDA tensor is read
+        where it lies (yk_load_device_pixels_u8).  n_planes defaults to C (RGBA into 3 planes drops the 4th byte).  The row pitch is the
+        array's row stride (u8_pixel_layout): padded or row-sliced views need no copy."""
+        L = self._L
+        is_torch = hasattr(pixels, "data_ptr")
+        if not is_torch:
+            pixels = np.asarray(pixels)
+        lay = u8_pixel_layout(pixels, n_planes)
+        h = lay.rows - halo_rows
+        self.n, self.h, self.w = lay.n_planes, h, lay.w
+        self.full_h = full_h if full_h is not None else h
+        self.y0 = y0
+        _chk(self._h, L.yk_set_image(self._h, lay.w, self.full_h, lay.n_planes, y0, h, halo_rows))
+        if is_torch:
+            import torch
+            assert pixels.is_cuda
+            torch.cuda.current_stream(pixels.device).synchronize()          # hand-over fence, see set_image
+            _chk(self._h, L.yk_load_device_pixels_u8(self._h, C.c_void_p(pixels.data_ptr()), lay.row_bytes, lay.frame_bytes, lay.channels))
+        else:
+            _chk(self._h, L.yk_upload_pixels_u8(self._h, C.c_void_p(pixels.ctypes.data), lay.row_bytes, lay.channels))
+        self._keepalive = pixels
 
     def validate_planes(self) -> int:
         """Samples of the bound planes outside 0..255 (the precondition of the path; yk_upload_planes enforces it itself)."""
@@ -159,6 +225,20 @@ class HipTileEncoder:
         base = frames.data_ptr()
         ptrs = (C.c_void_p * 4)(*[base + i * h * w * 4 if i < n else None for i in range(4)])
         _chk(self._h, L.yk_bind_device_batch(self._h, ptrs, w, n * h * w))
+        self._keepalive = frames
+
+    def set_batch_u8(self, frames, n_planes: int | None = None):
+        """frames: torch uint8 CUDA tensor [F, h, w, C]: F equally shaped 8-bit images widened, in one launch, into the handle's own planes
+        (yk_set_batch + yk_load_device_pixels_u8).  Row pitch and frame stride come from the tensor's strides (u8_pixel_layout)."""
+        import torch
+        L = self._L
+        lay = u8_pixel_layout(frames, n_planes, batch=True)
+        assert frames.is_cuda
+        self.n, self.h, self.w, self.full_h, self.y0 = lay.n_planes, lay.rows, lay.w, lay.rows, 0
+        _chk(self._h, L.yk_set_image(self._h, lay.w, lay.rows, lay.n_planes, 0, lay.rows, 0))
+        _chk(self._h, L.yk_set_batch(self._h, lay.frames))
+        torch.cuda.current_stream(frames.device).synchronize()          # hand-over fence, see set_image
+        _chk(self._h, L.yk_load_device_pixels_u8(self._h, C.c_void_p(frames.data_ptr()), lay.row_bytes, lay.frame_bytes, lay.channels))
         self._keepalive = frames
 
     def encode_batch(self, reject_factor: int = 3, mode3bit_only: bool = False):

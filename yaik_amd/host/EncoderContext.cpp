@@ -40,7 +40,26 @@ void EncoderContext::Release() {
     bound = alphaDone = encoded = oneDReady = false;
 }
 
-bool EncoderContext::SetImageToEncode(Image* newImage) {
+bool EncoderContext::SetImageToEncode(Image* newImage) { return adoptImage(newImage, nullptr, 0); }
+
+bool EncoderContext::LoadImagePixels(const u8* pixels, int w, int h, int channels, size_t rowBytes) {
+    if (!pixels || (channels != 3 && channels != 4) || w <= 0 || h <= 0 || rowBytes < (size_t)w * channels) {
+        SetImageToEncode(nullptr);                                          // like LoadImagePNG on a failed load: no image afterwards
+        return fail("LoadImagePixels: pixels, 3 or 4 channels and rowBytes >= w * channels");
+    }
+    if ((w & 7) || (h & 7)) { SetImageToEncode(nullptr); return fail("LoadImagePixels: the image is not a multiple of 8 x 8 pixels"); }
+    Image* img = Image::CreateImage(w, h, channels, false);
+    int* dst[4] = { nullptr, nullptr, nullptr, nullptr };
+    for (int p = 0; p < channels; p++) dst[p] = img->GetPlane(p)->GetPixels();
+    for (int y = 0; y < h; y++) {                                           // Image::LoadPNG's loop (encoder/Image.cpp:211-221), with a pitch
+        const u8* s = pixels + (size_t)y * rowBytes;
+        for (int x = 0; x < w; x++, s += channels)
+            for (int p = 0; p < channels; p++) dst[p][(size_t)y * w + x] = s[p];
+    }
+    return adoptImage(img, pixels, rowBytes);
+}
+
+bool EncoderContext::adoptImage(Image* newImage, const u8* pixels, size_t rowBytes) {
     if (original) delete original;
     original = newImage;
     bound = alphaDone = encoded = oneDReady = false; nextPass = 0;
@@ -51,9 +70,14 @@ bool EncoderContext::SetImageToEncode(Image* newImage) {
     yk_set_pixel_cache(ctx, 1);
     const int w = original->GetWidth(), h = original->GetHeight(), n = original->HasAlpha() ? 4 : 3;
     if (yk_set_image(ctx, w, h, n, 0, h, 0) != YK_OK) return fail("yk_set_image");
-    const int32_t* p[4] = { nullptr, nullptr, nullptr, nullptr };
-    for (int i = 0; i < n; i++) p[i] = original->GetPlane(i)->GetPixels();
-    if (yk_upload_planes(ctx, p, w) != YK_OK) return fail("yk_upload_planes");
+    if (pixels) {
+        // the GPU widens the 8-bit rows itself: n bytes per pixel over PCIe instead of 4n, and no range check (8-bit samples are in range)
+        if (yk_upload_pixels_u8(ctx, pixels, rowBytes, n) != YK_OK) return fail("yk_upload_pixels_u8");
+    } else {
+        const int32_t* p[4] = { nullptr, nullptr, nullptr, nullptr };
+        for (int i = 0; i < n; i++) p[i] = original->GetPlane(i)->GetPixels();
+        if (yk_upload_planes(ctx, p, w) != YK_OK) return fail("yk_upload_planes");
+    }
     bound = true;
     return true;
 }

@@ -32,6 +32,15 @@ public:
     int fileOutSize;
 
     bool SetImageToEncode(Image* newImage);             // takes ownership, deletes the previous image (EncoderContext.cpp:1227-1233)
+    // EncoderContext::LoadImagePNG (:1235-1242) from the point stbi_load has decoded the file, for a caller that holds 8-bit interleaved
+    // pixels: rows of `channels` (3 = RGB, 4 = RGBA) bytes per pixel at a pitch of rowBytes; sides multiples of 8, as Image::LoadPNG
+    // requires.  Builds `original` as Image::LoadPNG does (encoder/Image.cpp:200-229): the host int32 planes are filled, because this class
+    // hands out Plane* and ConvertHotPathStripes reads them.  The GPU, however, is bound through yk_upload_pixels_u8 instead of
+    // yk_upload_planes: one byte per sample crosses PCIe and a kernel widens it.  Everything after it is unchanged, ConvertHotPath* included.
+    // The mirror still reads no PNG file itself.
+    bool LoadImagePixels(const u8* pixels, int w, int h, int channels, size_t rowBytes);
+    Image* ImageToEncode() { return original; }         // the image the passes read (the reference's protected `original`)
+    yk_ctx* Handle() const { return ctx; }              // the C-ABI handle behind the passes (e.g. for yk_stage_ms); owned by this object
     void Release();
 
     void CheckMipmapMask();                             // EncoderContext.cpp:2784
@@ -112,6 +121,7 @@ private:
     bool stagesOk = true; std::string stagesErr;
     void retireOldestStage();
     bool ensureEncoded(int rejectFactor, bool mode3, bool wantDst);
+    bool adoptImage(Image* newImage, const u8* pixels, size_t rowBytes);   // SetImageToEncode / LoadImagePixels (pixels != NULL)
     bool fail(const char* what);
     bool alpha6BitDecodable() const;
     Image* original;

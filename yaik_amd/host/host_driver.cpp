@@ -9,6 +9,9 @@
 //                                                   i modulo the devices present; distinct devices are gathered by one RCCL transfer) next to the whole-image passes
 //        host_driver <in.bin> <out.blobs> pp        the six plane-subset 4x4 passes of Convert() (:9261-9415) after the RGB passes, written
 //                                                   as a .yaik stream and decoded back (see run_partial below)
+//        host_driver <in.bin> <out.blobs> pixels <out.yaik>   the image as 8-bit interleaved rows (padded pitch) through LoadImagePixels, then
+//                                                   the default form's passes, blobs and .yaik file (which must come out identical), plus
+//                                                   the blob pixels_unpack_intervals: yk_stage_ms of the unpack stage right after the load
 //        host_driver decode <out.blobs> <a.yaik> [<b.yaik> ...]   the .yaik files decoded in turn through ONE decode slot (YAIK_Init(1)),
 //                                                   default builder: blobs seq_info_<i> (int32 ok, errorCode, width, height, bytesPerPixel) and seq_image_<i>
 // With the 4th argument the image is also converted to a .yaik stream (ConvertHotPath) and decoded back through the
@@ -246,7 +249,22 @@ int main(int argc, char** argv) {
     gOut = fopen(argv[2], "wb"); if (!gOut) return 2;
 
     EncoderContext* ctx = new EncoderContext();
-    if (!ctx->SetImageToEncode(img)) { fprintf(stderr, "%s\n", ctx->LastError()); return 3; }
+    if (argc > 4 && std::string(argv[3]) == "pixels") {
+        // the same image as 8-bit interleaved rows at a padded pitch, loaded through LoadImagePixels (yk_upload_pixels_u8); the passes below
+        // read the context's own image, and every blob and the .yaik file must be those of the default form
+        const size_t rowBytes = (size_t)w * np + 13;
+        std::vector<u8> px(rowBytes * h, 0x5A);
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++)
+                for (int p = 0; p < np; p++) px[(size_t)y * rowBytes + (size_t)x * np + p] = (u8)img->GetPlane(p)->GetPixels()[(size_t)y * w + x];
+        for (int p = 0; p < np; p++) delete img->GetPlane(p);
+        delete img;
+        if (!ctx->LoadImagePixels(px.data(), w, h, np, rowBytes)) { fprintf(stderr, "%s\n", ctx->LastError()); return 3; }
+        img = ctx->ImageToEncode();
+        float ms = 0.0f; int unpacks = -1;                          // the GPU widened the rows: one interval of the unpack stage
+        if (yk_stage_ms(ctx->Handle(), YK_STAGE_UNPACK, &ms, &unpacks) != YK_OK) return 4;
+        blob("pixels_unpack_intervals", &unpacks, sizeof unpacks);
+    } else if (!ctx->SetImageToEncode(img)) { fprintf(stderr, "%s\n", ctx->LastError()); return 3; }
     if (argc > 4 && std::string(argv[3]) == "lut") {
         const int rc = run_lut(ctx, img, w, h, np, argv[4]);
         fclose(gOut);
