@@ -396,6 +396,18 @@ int yk_decode_alpha(yk_ctx* c, int mode, const int32_t bbox[4], const uint8_t* p
 int yk_decode_alpha_plane(yk_ctx* c, uint8_t* hostOut, size_t cap);                       /* the plane back to the host (tests, custom builders) */
 /* yk_decode_output with the plane of yk_decode_alpha as alpha: RGBA 4 B/pixel; the alpha plane never leaves HBM */
 int yk_decode_output_alpha(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride);
+/* The default builder's de-tile into DEVICE memory (on this handle's device): 8-bit pixels of the image begun by yk_decode_begin at any base
+ * address and pitch, written by the kernel of yk_decode_output with no host copy and no host synchronisation.
+ *   planeBytes == 0: HWC, pixel (x, y) channel k at devOut[y * rowBytes + x * channels + k] (the RGB888 / RGBA8888 rows of yk_decode_output);
+ *   planeBytes >  0: CHW, at devOut[k * planeBytes + y * rowBytes + x] (the [C, H, W] layout of torch image tensors).
+ * channels = 3 (RGB) or 4 (RGBA).  With 4, alpha = -1 takes the plane yk_decode_alpha left in HBM, 0..255 that constant (opaque RGBA from an
+ * RGB file: 255); alpha is ignored with 3.  Only pixel bytes are written: row padding and the bytes between planes are never touched.
+ * Refusals write nothing: YK_ERR_BAD_ARG for a NULL devOut, channels other than 3 / 4, rowBytes < w * channels (HWC) or rowBytes < w /
+ * planeBytes < rowBytes * h (CHW), alpha outside -1..255 with channels 4; YK_ERR_STATE before yk_decode_begin, or alpha = -1 with no
+ * decoded 'ALPM' plane.  ORDERING is the caller's, as for the yk_decode_*_device entry points: devOut is written on THIS handle's stream.
+ * Order earlier work on devOut first (yk_stream_wait_for(c, producerStream)) and the consumer after the call (yk_stream_handoff(c,
+ * consumerStream) or yk_synchronize).  Timed as YK_STAGE_DEC_DETILE. */
+int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha);
 /* the three planes of tile4x4Mask back to back (planes 1 and 2 are meaningful once a partial-plane pass has split the masks) */
 int yk_decode_tile4x4_planes(yk_ctx* c, uint8_t* hostOut, size_t cap);
 
@@ -412,7 +424,7 @@ enum { YK_STAGE_CORNERS = 0,       /* yk_gradient_corners: lattice clear + owner
        YK_STAGE_RANGE1D_PACK = 2,  /* yk_range1d_encode: scans + yk_range1d_pack_kernel */
        YK_STAGE_DEC_GRADIENT = 3,  /* yk_decode_gradient: owner / corner / scan / render kernels of one pass per interval */
        YK_STAGE_DEC_1D = 4,        /* yk_decode_1d: count / scans / yk_dec1d_kernel */
-       YK_STAGE_DEC_DETILE = 5,    /* yk_decode_output: yk_dec_detile_kernel */
+       YK_STAGE_DEC_DETILE = 5,    /* yk_decode_output / _alpha / _reference_rgba / yk_decode_output_device: yk_dec_detile_kernel */
        YK_STAGE_LUT3D = 6,         /* yk_lut_search: yk_lut_search_kernel (one interval per tile shape) */
        YK_STAGE_UNPACK = 7 };      /* yk_upload_pixels_u8 / yk_load_device_pixels_u8: yk_unpack_u8_kernel (the host copy is outside the interval) */
 int yk_stage_ms(yk_ctx* c, int stage, float* msSum, int* intervals);

@@ -704,37 +704,139 @@ __global__ void yk_dec_mask_kernel(const uint8_t* __restrict__ bits, int bw, int
     A[0] = v; A[1] = v; A[2 * bw] = v; A[2 * bw + 1] = v;
 }
 
-// a20: the default image builder (decoder/YAIK_DefaultCallback.cpp:24-191): 8x8-tiled planes -> interleaved RGB rows at
-// outputImageStride.  With an alpha plane the reference never advances past the alpha byte (:53-60) and produces
-// 3-byte-strided garbage; this kernel writes proper RGBA (4 B/pixel) instead, which is what YAIK.h documents.
-__global__ __launch_bounds__(256) void yk_dec_detile_kernel(const uint8_t* __restrict__ planes, size_t planeSize, int tileW, int w, int h,
-                                                            const uint8_t* __restrict__ alpha, int strideA, uint8_t* __restrict__ out, size_t stride) {
-    // one thread = 4 pixels of a row (half a tile row): one 4-byte load per plane, 12 (RGB) or 16 (RGBA) output bytes
-    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;                               // w is a multiple of 8: a thread's 4 pixels lie inside one row
-    const size_t ti = ((size_t)(y >> 3) * tileW + (x >> 3)) * 64 + (y & 7) * 8 + (x & 7);
-    const uint32_t r = *reinterpret_cast<const uint32_t*>(planes + ti), g = *reinterpret_cast<const uint32_t*>(planes + planeSize + ti),
-                   b = *reinterpret_cast<const uint32_t*>(planes + 2 * planeSize + ti);
-    if (alpha) {
-        uint8_t* o = out + (size_t)y * stride + (size_t)x * 4;
-        const uint8_t* a = alpha + (size_t)y * strideA + x;
-        uint32_t px[4];
+// a20: the default image builder (decoder/YAIK_DefaultCallback.cpp:24-191) and its device form: the 8x8-tiled planes -> 8-bit pixels at any
+// address and pitch.  Pixel (x, y) channel k lands at out[y * rowBytes + x * C + k] (HWC: the builder's RGB888 / RGBA8888 rows) or at
+// out[k * planeBytes + y * rowBytes + x] (CHW), C = 3 or 4.  The 4th channel is the alpha plane (stride strideA) or a constant.  With an alpha
+// plane the reference never advances past the alpha byte (:53-60) and produces 3-byte-strided garbage; this kernel writes proper RGBA
+// (4 B/pixel) instead, which is what YAIK.h documents.  Only pixel bytes are written: row padding and the bytes between planes are not touched.
+// The planes are one linear array of tiles (64 B each, tile t = (tx, ty) at t = ty * tileW + tx).  A work unit is 16 consecutive tiles,
+// 1 KB per plane: lane l loads bytes 16l..16l+15 of each plane (rows 2(l&3), 2(l&3)+1 of tile 16u + (l>>2)), so every load instruction is
+// one dense 1 KB access, and writes its two 8-pixel row segments.  For a fixed l&3 the 16 lanes hold 16 consecutive tiles, so the stores of
+// a row pair fill four runs of 16 * 8 * C bytes (HWC).  A lane derives its own (tx, ty), so a run may wrap into the next row of tiles.
+// No LDS, no shuffles; w and h are multiples of 8, so only the last unit is partial.  A lane issues the loads of K units before its first store.
+// Stores and alpha loads go through byte pointers (__builtin_memcpy): gfx950 runs with unaligned global access enabled and hipcc emits
+// global_store_dwordx4 + dwordx2 per RGB segment, 2 x dwordx4 per RGBA segment, dwordx2 per CHW row and global_load_dwordx2 per alpha row for
+// them (checked in the ISA), the fewest instructions those bytes allow; so one path serves every base and pitch.
+#define YK_DT_THREADS 256
+#define YK_DT_K 4                                   // units per lane in flight
+#define YK_DT_TILES (YK_DT_THREADS / 4 * YK_DT_K)   // tiles per workgroup
+
+enum { YK_DT_ALPHA_NONE = 0, YK_DT_ALPHA_PLANE = 1, YK_DT_ALPHA_CONST = 2 };
+
+struct YkDetileArgs {
+    const uint8_t* planes; size_t planeSize;         // R, G, B at planes + p * planeSize
+    const uint8_t* alpha; size_t strideA;            // YK_DT_ALPHA_PLANE: row y at alpha + y * strideA
+    uint32_t alphaConst;                             // YK_DT_ALPHA_CONST: the byte in all four lanes of a dword
+    uint8_t* out; size_t rowBytes, planeBytes;
+    uint32_t tileW, nTiles;
+};
+
+typedef uint32_t yk_dt4 __attribute__((ext_vector_type(4)));
+
+// row segment of 8 pixels (dwords lo, hi of each plane) -> its bytes at o (HWC) or o + k * planeBytes (CHW)
+template <int C, bool PLANAR>
+__device__ __forceinline__ void yk_dt_emit(uint8_t* o, size_t planeBytes, uint32_t r0, uint32_t r1, uint32_t g0, uint32_t g1, uint32_t b0, uint32_t b1,
+                                           uint32_t a0, uint32_t a1) {
+    if constexpr (PLANAR) {
+        const uint32_t v[4][2] = { { r0, r1 }, { g0, g1 }, { b0, b1 }, { a0, a1 } };
 #pragma unroll
-        for (int k = 0; k < 4; k++) px[k] = ((r >> (8 * k)) & 255u) | (((g >> (8 * k)) & 255u) << 8) | (((b >> (8 * k)) & 255u) << 16) | ((uint32_t)a[k] << 24);
-        if ((reinterpret_cast<uintptr_t>(o) & 3) == 0) { uint32_t* o4 = reinterpret_cast<uint32_t*>(o); o4[0] = px[0]; o4[1] = px[1]; o4[2] = px[2]; o4[3] = px[3]; }
-        else for (int k = 0; k < 16; k++) o[k] = (uint8_t)(px[k >> 2] >> (8 * (k & 3)));
-    } else {
-        uint8_t* o = out + (size_t)y * stride + (size_t)x * 3;
-        const uint32_t r0 = r & 255u, r1 = (r >> 8) & 255u, r2 = (r >> 16) & 255u, r3 = r >> 24;
-        const uint32_t g0 = g & 255u, g1 = (g >> 8) & 255u, g2 = (g >> 16) & 255u, g3 = g >> 24;
-        const uint32_t b0 = b & 255u, b1 = (b >> 8) & 255u, b2 = (b >> 16) & 255u, b3 = b >> 24;
-        const uint32_t w0 = r0 | (g0 << 8) | (b0 << 16) | (r1 << 24), w1 = g1 | (b1 << 8) | (r2 << 16) | (g2 << 24), w2 = b2 | (r3 << 8) | (g3 << 16) | (b3 << 24);
-        if ((reinterpret_cast<uintptr_t>(o) & 3) == 0) { uint32_t* o4 = reinterpret_cast<uint32_t*>(o); o4[0] = w0; o4[1] = w1; o4[2] = w2; }
-        else {
-            const uint32_t ws[3] = { w0, w1, w2 };
-            for (int k = 0; k < 12; k++) o[k] = (uint8_t)(ws[k >> 2] >> (8 * (k & 3)));
+        for (int k = 0; k < C; k++) __builtin_memcpy(o + (size_t)k * planeBytes, v[k], 8);
+    } else if constexpr (C == 3) {
+        // 4 pixels of R, G, B dwords -> 12 bytes r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+        uint32_t wd[6];
+        const uint32_t rg[2][2] = { { __builtin_amdgcn_perm(g0, r0, 0x05010400u), __builtin_amdgcn_perm(g0, r0, 0x07030602u) },
+                                    { __builtin_amdgcn_perm(g1, r1, 0x05010400u), __builtin_amdgcn_perm(g1, r1, 0x07030602u) } };
+        const uint32_t bb[2] = { b0, b1 }, gg[2] = { g0, g1 };
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            wd[3 * h + 0] = __builtin_amdgcn_perm(bb[h], rg[h][0], 0x02040100u);
+            wd[3 * h + 1] = __builtin_amdgcn_perm(rg[h][1], __builtin_amdgcn_perm(bb[h], gg[h], 0x05010400u), 0x05040302u);
+            wd[3 * h + 2] = __builtin_amdgcn_perm(bb[h], rg[h][1], 0x07030206u);
         }
+        __builtin_memcpy(o, wd, 24);
+    } else {
+        // 4 pixels of R, G, B, A dwords -> 16 bytes r g b a x 4
+        yk_dt4 px[2];
+        const uint32_t rr[2] = { r0, r1 }, gg[2] = { g0, g1 }, bb[2] = { b0, b1 }, aa[2] = { a0, a1 };
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const uint32_t rgL = __builtin_amdgcn_perm(gg[h], rr[h], 0x05010400u), rgH = __builtin_amdgcn_perm(gg[h], rr[h], 0x07030602u);
+            const uint32_t baL = __builtin_amdgcn_perm(aa[h], bb[h], 0x05010400u), baH = __builtin_amdgcn_perm(aa[h], bb[h], 0x07030602u);
+            px[h] = yk_dt4{ __builtin_amdgcn_perm(baL, rgL, 0x05040100u), __builtin_amdgcn_perm(baL, rgL, 0x07060302u),
+                            __builtin_amdgcn_perm(baH, rgH, 0x05040100u), __builtin_amdgcn_perm(baH, rgH, 0x07060302u) };
+        }
+        __builtin_memcpy(o, px, 32);
     }
+}
+
+struct YkDtUnit { yk_dt4 r, g, b; uint32_t a[4]; size_t o; };
+
+template <int C, bool PLANAR, int ASRC>
+__device__ __forceinline__ void yk_dt_load(const YkDetileArgs& a, uint32_t t, uint32_t rp, YkDtUnit& u) {
+    const size_t ti = (size_t)t * 64 + rp * 16;
+    u.r = *reinterpret_cast<const yk_dt4*>(a.planes + ti);
+    u.g = *reinterpret_cast<const yk_dt4*>(a.planes + a.planeSize + ti);
+    u.b = *reinterpret_cast<const yk_dt4*>(a.planes + 2 * a.planeSize + ti);
+    const uint32_t ty = t / a.tileW, tx = t - ty * a.tileW;
+    const size_t y = (size_t)ty * 8 + rp * 2, x = (size_t)tx * 8;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) {
+        __builtin_memcpy(&u.a[0], a.alpha + y * a.strideA + x, 8);
+        __builtin_memcpy(&u.a[2], a.alpha + (y + 1) * a.strideA + x, 8);
+    }
+    u.o = y * a.rowBytes + x * (PLANAR ? 1 : C);
+}
+
+template <int C, bool PLANAR, int ASRC>
+__device__ __forceinline__ void yk_dt_store(const YkDetileArgs& a, const YkDtUnit& u) {
+    uint32_t al[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) al[i] = ASRC == YK_DT_ALPHA_PLANE ? u.a[i] : a.alphaConst;
+    uint8_t* o = a.out + u.o;
+    yk_dt_emit<C, PLANAR>(o, a.planeBytes, u.r.x, u.r.y, u.g.x, u.g.y, u.b.x, u.b.y, al[0], al[1]);
+    yk_dt_emit<C, PLANAR>(o + a.rowBytes, a.planeBytes, u.r.z, u.r.w, u.g.z, u.g.w, u.b.z, u.b.w, al[2], al[3]);
+}
+
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_kernel(YkDetileArgs a) {
+    const uint32_t lane = threadIdx.x & 63, rp = lane & 3;
+    // unit of step k: blockIdx.x * K * 4 + k * 4 + wave, so the four waves of a workgroup stream 4 KB of every plane per step
+    const uint32_t t0 = (blockIdx.x * (YK_DT_K * 4) + (threadIdx.x >> 6)) * 16 + (lane >> 2);
+    if ((blockIdx.x + 1) * (uint32_t)YK_DT_TILES <= a.nTiles) {
+        YkDtUnit u[YK_DT_K];                                                  // every unit of the workgroup exists: all loads first
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) yk_dt_load<C, PLANAR, ASRC>(a, t0 + k * 64, rp, u[k]);
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) yk_dt_store<C, PLANAR, ASRC>(a, u[k]);
+        return;
+    }
+    for (int k = 0; k < YK_DT_K; k++) {                                       // the last workgroup: tiles up to nTiles
+        const uint32_t t = t0 + k * 64;
+        if (t >= a.nTiles) continue;
+        YkDtUnit u;
+        yk_dt_load<C, PLANAR, ASRC>(a, t, rp, u);
+        yk_dt_store<C, PLANAR, ASRC>(a, u);
+    }
+}
+
+template <int C, bool PLANAR, int ASRC>
+static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((yk_dec_detile_kernel<C, PLANAR, ASRC>), dim3((a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES), dim3(YK_DT_THREADS), 0, s, a);
+}
+
+// the de-tile of the image begun on c into out; alpha: a plane (strideA bytes per row) or NULL with alphaConst 0..255 (channels 4)
+static int yk_dec_detile(yk_ctx* c, uint8_t* out, size_t rowBytes, size_t planeBytes, int channels, const uint8_t* alpha, size_t strideA, int alphaConst) {
+    YkDetileArgs a;
+    a.planes = c->dPlanes; a.planeSize = c->dPlaneSize;
+    a.alpha = alpha; a.strideA = strideA; a.alphaConst = (uint32_t)(alphaConst & 255) * 0x01010101u;
+    a.out = out; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
+    a.tileW = (uint32_t)(c->dw >> 3); a.nTiles = (uint32_t)(c->dw >> 3) * (uint32_t)(c->dh >> 3);
+    const bool planar = planeBytes > 0;
+    { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    if (channels == 3) { if (planar) yk_dt_launch<3, true, YK_DT_ALPHA_NONE>(a, c->stream); else yk_dt_launch<3, false, YK_DT_ALPHA_NONE>(a, c->stream); }
+    else if (alpha)    { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_PLANE>(a, c->stream); else yk_dt_launch<4, false, YK_DT_ALPHA_PLANE>(a, c->stream); }
+    else               { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_CONST>(a, c->stream); else yk_dt_launch<4, false, YK_DT_ALPHA_CONST>(a, c->stream); }
+    YK_HIP(c, hipGetLastError());
+    return yk_stage_end(c, YK_STAGE_DEC_DETILE);
 }
 
 // The reference's RGBA branch as it executes (decoder/YAIK_DefaultCallback.cpp:45-62): the alpha store does not advance dst, so a row is
@@ -1103,11 +1205,8 @@ static int yk_decode_output_impl(yk_ctx* c, uint8_t* hostOut, size_t outputImage
     int rc = yk_dec_scratch(c, oA + aBytes + 64); if (rc) return rc;
     rc = yk_dec_settle(c); if (rc) return rc;
     if (hostAlpha && !devAlpha) YK_HIP(c, hipMemcpyAsync(c->dScratch + oA, hostAlpha, aBytes, hipMemcpyHostToDevice, c->stream));
-    { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc2) return rc2; }
-    hipLaunchKernelGGL(yk_dec_detile_kernel, dim3((w + 255) / 256, (h + 3) / 4), dim3(256), 0, c->stream, c->dPlanes, c->dPlaneSize, w >> 3, w, h,
-                       devAlpha ? devAlpha : (hostAlpha && !refRGBA) ? c->dScratch + oA : (const uint8_t*)nullptr, strideA, c->dScratch, dPitch);
-    YK_HIP(c, hipGetLastError());
-    { int rc2 = yk_stage_end(c, YK_STAGE_DEC_DETILE); if (rc2) return rc2; }
+    rc = yk_dec_detile(c, c->dScratch, dPitch, 0, bpp, devAlpha ? devAlpha : bpp == 4 ? c->dScratch + oA : (const uint8_t*)nullptr, (size_t)strideA, 0);
+    if (rc) return rc;
     if (refRGBA && hostAlpha) {
         hipLaunchKernelGGL(yk_dec_ref_alpha_kernel, dim3((h + 255) / 256), dim3(256), 0, c->stream, c->dScratch + oA, strideA, aBytes, w, h, c->dScratch, dPitch);
         YK_HIP(c, hipGetLastError());
@@ -1129,6 +1228,22 @@ int yk_decode_output_alpha(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride
 
 int yk_decode_output_reference_rgba(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA) {
     return yk_decode_output_impl(c, hostOut, outputImageStride, hostAlpha, strideA, true);
+}
+
+int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!devOut) return yk_fail(c, YK_ERR_BAD_ARG, "devOut is NULL");
+    if (channels != 3 && channels != 4) return yk_fail(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_fail(c, YK_ERR_BAD_ARG, "alpha must be -1 (the decoded plane) or 0..255");
+    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    const size_t w = (size_t)c->dw, h = (size_t)c->dh;
+    if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
+        return yk_fail(c, YK_ERR_BAD_ARG, "row or plane pitch too small for the image");
+    const bool fromPlane = channels == 4 && alpha < 0;
+    if (fromPlane && !c->dAlphaValid) return yk_fail(c, YK_ERR_STATE, "alpha = -1 needs yk_decode_alpha first");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    return yk_dec_detile(c, devOut, rowBytes, planeBytes, channels, fromPlane ? c->dAlpha : nullptr, w, fromPlane ? 0 : alpha);
 }
 
 const uint8_t* yk_decode_planes_device(yk_ctx* c, size_t* planeSize) {

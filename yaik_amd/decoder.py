@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import YaikError, lib
-from .encoder import _chk
+from .encoder import _chk, u8_pixel_layout, u8_planar_layout
 
 
 class HipTileDecoder:
@@ -21,6 +21,7 @@ class HipTileDecoder:
         if rc != 0:
             raise YaikError(f"yk_create failed ({rc}): no usable HIP device -- the product path has no CPU fallback")
         self._h = h
+        self.device = device
         self.w = self.h = 0
         self._has_alpha = False
 
@@ -126,10 +127,11 @@ class HipTileDecoder:
         return out
 
     def decompress_alpha(self, mode: int, bbox, payload: np.ndarray, mask: np.ndarray | None = None, mask_bbox=None,
-                         reference_1bit: bool = False) -> np.ndarray:
+                         reference_1bit: bool = False, to_host: bool = True) -> np.ndarray | None:
         """'ALPM' chunk: the w x h alpha plane from the DECOMPRESSED payload (yk_decode_alpha).  mode = AlphaHeader::parameters & 7,
         bbox = (x, y, w, h) in pixels; the mask modes 2 / 3 take the decoded 'MIPM' mask (decompress_1bit_tiled) and its box in pixels.
-        reference_1bit reproduces the reference's 1-bit row loop byte for byte.  The plane stays on the device for image()."""
+        reference_1bit reproduces the reference's 1-bit row loop byte for byte.  The plane stays on the device for image() and
+        image_device(); to_host=False skips its copy to the host and returns None."""
         p = np.ascontiguousarray(payload, dtype=np.uint8)
         b = np.ascontiguousarray(np.asarray(bbox, dtype=np.int32).reshape(4))
         m = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
@@ -139,6 +141,8 @@ class HipTileDecoder:
                                             m.ctypes.data if m is not None and m.size else None, m.size if m is not None else 0,
                                             mb.ctypes.data if mb is not None else None, 1 if reference_1bit else 0))
         self._has_alpha = True
+        if not to_host:
+            return None
         out = np.empty((self.h, self.w), dtype=np.uint8)
         _chk(self._h, lib().yk_decode_alpha_plane(self._h, out.ctypes.data, out.size))
         return out
@@ -170,6 +174,37 @@ class HipTileDecoder:
     def image_into(self, out: np.ndarray) -> None:
         """RGB rows into a caller-owned [h, stride] uint8 array (no allocation per call)."""
         _chk(self._h, lib().yk_decode_output(self._h, out.ctypes.data, out.shape[1], None, 0))
+
+    def image_device(self, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
+        """The decoded image as 8-bit pixels in a torch.uint8 tensor on the handle's device (yk_decode_output_device): [h, w, C], or
+        [C, h, w] with planar=True.  channels defaults to 4 when an 'ALPM' plane was decoded, else 3 (as in image()).  With 4 channels,
+        alpha=None takes the decoded plane when there is one and 255 otherwise; an int 0..255 is a constant alpha.  `out` may be any view with
+        unit inner strides and any row or plane pitch (frames[f] of a batch, row-padded slices): only its pixel bytes are written.
+        No host fence: the handle's stream waits for torch's current stream before the write, and torch's current stream waits for the
+        write after it, so torch work queued afterwards sees the pixels.  Returns the tensor written."""
+        import torch
+        C4 = channels if channels is not None else (4 if self._has_alpha else 3)
+        a = (-1 if self._has_alpha else 255) if alpha is None else int(alpha)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((C4, self.h, self.w) if planar else (self.h, self.w, C4), dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        if planar:
+            lay = u8_planar_layout(out)
+            shape, row_bytes, plane_bytes = (lay.channels, lay.rows, lay.w), lay.row_bytes, lay.plane_bytes
+        else:
+            lay = u8_pixel_layout(out)
+            shape, row_bytes, plane_bytes = (lay.rows, lay.w, lay.channels), lay.row_bytes, 0
+        want = (C4, self.h, self.w) if planar else (self.h, self.w, C4)
+        if shape != want:
+            raise ValueError(f"out has shape {shape}, the image needs {want}")
+        L = lib()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_output_device(self._h, out.data_ptr(), row_bytes, plane_bytes, C4, a))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
 
     def synchronize(self):
         _chk(self._h, lib().yk_synchronize(self._h))

@@ -71,6 +71,43 @@ def u8_pixel_layout(pixels, n_planes: int | None = None, batch: bool = False) ->
     return PixelLayout(frames, rows, w, ch, n, row_bytes, frame_bytes)
 
 
+class PlanarLayout(NamedTuple):
+    """How yk_decode_output_device writes a planar [C, rows, w] uint8 array: u8_planar_layout."""
+    channels: int
+    rows: int
+    w: int
+    row_bytes: int          # row pitch inside a plane
+    plane_bytes: int        # plane stride
+
+
+def u8_planar_layout(pixels) -> PlanarLayout:
+    """Layout of numpy or torch uint8 pixels [C, rows, w], C = 3 or 4 (the [C, H, W] of torch image tensors).  Row pitch and plane stride are
+    the array's own strides, so padded or sliced views need no copy; the bytes of a row must be contiguous (pixel stride 1), and rows and planes
+    may not overlap.  Reads only dtype, shape and strides."""
+    if hasattr(pixels, "data_ptr"):
+        import torch
+        if pixels.dtype != torch.uint8:
+            raise TypeError(f"8-bit pixels expected, got {pixels.dtype}")
+        shape, strides = tuple(pixels.shape), tuple(pixels.stride())
+    else:
+        if pixels.dtype != np.uint8:
+            raise TypeError(f"8-bit pixels expected, got {pixels.dtype}")
+        shape, strides = pixels.shape, pixels.strides
+    if len(shape) != 3:
+        raise ValueError(f"pixels must be [C, rows, w], got shape {tuple(shape)}")
+    ch, rows, w = shape
+    if ch not in (3, 4):
+        raise ValueError(f"C must be 3 (RGB) or 4 (RGBA); got C = {ch}")
+    if strides[2] != 1:
+        raise ValueError(f"the bytes of a row must be contiguous (pixel stride 1); got strides {tuple(strides)}")
+    row_bytes, plane_bytes = strides[1], strides[0]
+    if row_bytes < w:
+        raise ValueError(f"row stride {row_bytes} is shorter than a row of {w} bytes")
+    if plane_bytes < rows * row_bytes:
+        raise ValueError(f"plane stride {plane_bytes} is shorter than a plane of {rows * row_bytes} bytes")
+    return PlanarLayout(ch, rows, w, row_bytes, plane_bytes)
+
+
 class HipTileEncoder:
     """One handle = one GPU = one image or one row stripe of an image."""
 

@@ -14,6 +14,10 @@
 //                                                   the blob pixels_unpack_intervals: yk_stage_ms of the unpack stage right after the load
 //        host_driver decode <out.blobs> <a.yaik> [<b.yaik> ...]   the .yaik files decoded in turn through ONE decode slot (YAIK_Init(1)),
 //                                                   default builder: blobs seq_info_<i> (int32 ok, errorCode, width, height, bytesPerPixel) and seq_image_<i>
+//        host_driver decode_device <out.blobs> <a.yaik> [...]   every file decoded twice through ONE slot, YAIK_DecodeImage into host rows and
+//                                                   YAIK_DecodeImageToDevice into a buffer of the driver's own handle (downloaded afterwards), same
+//                                                   tight pitch (bytes per pixel 4 with an 'ALPM' chunk, else 3): blobs dev_info_<i> (int32 host ok, error,
+//                                                   device ok, error, width, height, bytesPerPixel, custom-builder ok, its error), host_image_<i>, dev_image_<i>
 // With the 4th argument the image is also converted to a .yaik stream (ConvertHotPath) and decoded back through the
 // YAIK_* decoder API, the way an application would use the two libraries.
 #include <cstdio>
@@ -27,6 +31,7 @@
 #include "yaik_decode.h"
 #include "chunks.h"
 #include "palette.h"
+#include "yaik_format.h"
 
 static FILE* gOut;
 static void blob(const std::string& name, const void* data, size_t len) {
@@ -231,11 +236,69 @@ static int run_decode_sequence(int n, char** files) {
     return 0;
 }
 
+// the default builder writes RGBA rows when the stream has an 'ALPM' chunk (yaik_decode.cpp)
+static bool has_alpha_chunk(const u8* p, size_t len) {
+    for (size_t o = 12; o + 8 <= len;) {                                          // chunks after the file header, up to the terminator
+        u32 tag, n; memcpy(&tag, p + o, 4); memcpy(&n, p + o + 4, 4);
+        if (tag == yaikfmt::TAG_END) break;
+        if (tag == yaikfmt::TAG_ALPHA) return true;
+        o += 8 + (size_t)n;
+    }
+    return false;
+}
+
+static int run_decode_device(int n, char** files) {
+    YAIK_LIB lib = YAIK_Init(1, nullptr);
+    yk_ctx* h = nullptr;
+    if (!lib || yk_create(0, &h) != YK_OK) return 5;
+    for (int i = 0; i < n; i++) {
+        FILE* fi = fopen(files[i], "rb"); if (!fi) return 2;
+        fseek(fi, 0, SEEK_END); const long len = ftell(fi); fseek(fi, 0, SEEK_SET);
+        std::vector<u32> stream(((size_t)len + 3) / 4 + 1);
+        if (fread(stream.data(), 1, (size_t)len, fi) != (size_t)len) return 2;
+        fclose(fi);
+        int info[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+        std::vector<u8> hostImg, devImg;
+        YAIK_SDecodedImage di;
+        if (YAIK_DecodeImagePre(lib, stream.data(), (u32)len, &di)) {
+            const int bpp = has_alpha_chunk((const u8*)stream.data(), (size_t)len) ? 4 : 3, w = di.width, hh = di.height;
+            info[4] = w; info[5] = hh; info[6] = bpp;
+            const size_t bytes = (size_t)w * hh * bpp;
+            hostImg.assign(bytes, 0);
+            di.outputImage = hostImg.data(); di.outputImageStride = w * bpp;
+            info[0] = YAIK_DecodeImage(stream.data(), (u32)len, &di) ? 1 : 0;
+            info[1] = (int)YAIK_GetErrorCode();
+            void* dev = nullptr;
+            if (yk_device_alloc(h, bytes, &dev) != YK_OK) return 5;
+            if (YAIK_DecodeImagePre(lib, stream.data(), (u32)len, &di)) {
+                di.outputImage = (uint8_t*)dev; di.outputImageStride = w * bpp;
+                info[2] = YAIK_DecodeImageToDevice(stream.data(), (u32)len, &di) ? 1 : 0;
+            }
+            info[3] = (int)YAIK_GetErrorCode();
+            devImg.assign(bytes, 0);
+            if (info[2] && yk_device_download(h, devImg.data(), dev, bytes) != YK_OK) return 5;
+            if (YAIK_DecodeImagePre(lib, stream.data(), (u32)len, &di)) {                   // a custom builder takes host planes: refused
+                di.outputImage = (uint8_t*)dev; di.outputImageStride = w * bpp;
+                di.customImageOutput = [](YAIK_SDecodedImage*, YAIK_SCustomDataSource*) {};
+                info[7] = YAIK_DecodeImageToDevice(stream.data(), (u32)len, &di) ? 1 : 0;
+            }
+            info[8] = (int)YAIK_GetErrorCode();
+            yk_device_free(h, dev);
+        }
+        blob(nm("dev_info", i), info, sizeof info);
+        blob(nm("host_image", i), hostImg.data(), hostImg.size());
+        blob(nm("dev_image", i), devImg.data(), devImg.size());
+    }
+    yk_destroy(h);
+    YAIK_Release(lib);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: host_driver in.bin out.blobs [mode3]\n"); return 2; }
-    if (argc > 3 && std::string(argv[1]) == "decode") {
+    if (argc > 3 && (std::string(argv[1]) == "decode" || std::string(argv[1]) == "decode_device")) {
         gOut = fopen(argv[2], "wb"); if (!gOut) return 2;
-        const int rc = run_decode_sequence(argc - 3, argv + 3);
+        const int rc = std::string(argv[1]) == "decode" ? run_decode_sequence(argc - 3, argv + 3) : run_decode_device(argc - 3, argv + 3);
         fclose(gOut);
         return rc;
     }

@@ -108,13 +108,16 @@ bool YAIK_DecodeImagePre(YAIK_LIB lib, void* stream, uint32_t length, YAIK_SDeco
     return true;
 }
 
-bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) {
+// The chunk state machine of YAIK_DecodeImage and YAIK_DecodeImageToDevice; toDevice: outputImage is in device memory (default builder only)
+static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice) {
     if (!info || !info->internalTag || !gLib) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
     Slot* s = (Slot*)info->internalTag;
     bool res = false;
     std::vector<uint8_t> bitmap, pal, rgb, types, pix;
     const YAIK_SMemAlloc& ua = info->userMemoryAllocator;
+    const bool customBuilder = info->customImageOutput && info->customImageOutput != defaultImageBuilder;
     do {
+        if (toDevice && customBuilder) { setError(YAIK_DECIMG_INVALIDCTX); break; }               // a custom builder takes host planes
         if (!ua.customAlloc || !ua.customFree) { setError(YAIK_INVALID_CONTEXT_MEMALLOCATOR); break; }
         if (s->srcCheck != stream || s->srcLength != length) { setError(YAIK_DECIMG_DIFFSTREAM); break; }
         if (!info->outputImage) { setError(YAIK_DECIMG_BUFFERNOTSET); break; }
@@ -248,7 +251,7 @@ bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) {
             p = endBlock;
         }
         if (bad) break;
-        if (info->customImageOutput && info->customImageOutput != defaultImageBuilder) {
+        if (customBuilder) {
             // custom builder: hand over the 8x8-tiled planes exactly like the reference (:1303-1318)
             const size_t planeSize = (size_t)(w / 8) * (h / 8) * 64;
             uint8_t* planes = (uint8_t*)ua.customAlloc(ua.customContext, planeSize * 3);
@@ -273,8 +276,12 @@ bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) {
             // YAIK_DefaultCallback.cpp:44,63); row padding is left untouched.
             // with an 'ALPM' chunk: RGBA 4 B/pixel from the alpha plane kept in HBM (YAIK.h documents RGBA rows; the reference's own RGBA
             // branch is defective)
-            res = (hasAlphaPlane ? yk_decode_output_alpha(s->ctx, info->outputImage, (size_t)info->outputImageStride)
-                                 : yk_decode_output(s->ctx, info->outputImage, (size_t)info->outputImageStride, nullptr, w)) == YK_OK;
+            if (toDevice)                                                                           // the same kernel into device rows, then a fence:
+                res = info->outputImageStride > 0 && yk_decode_output_device(s->ctx, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1) == YK_OK &&
+                      yk_synchronize(s->ctx) == YK_OK;                                              // the slot's stream is idle before it is released
+            else
+                res = (hasAlphaPlane ? yk_decode_output_alpha(s->ctx, info->outputImage, (size_t)info->outputImageStride)
+                                     : yk_decode_output(s->ctx, info->outputImage, (size_t)info->outputImageStride, nullptr, w)) == YK_OK;
             if (!res) setError(YAIK_INVALID_STREAM);
         }
     } while (false);
@@ -282,3 +289,6 @@ bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) {
     info->internalTag = nullptr;
     return res;
 }
+
+bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) { return decodeImage(stream, length, info, false); }
+bool YAIK_DecodeImageToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info) { return decodeImage(stream, length, info, true); }

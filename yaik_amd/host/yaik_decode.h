@@ -67,6 +67,13 @@ YAIK_ERROR_CODE YAIK_GetErrorCode();
 
 // extension (not in the reference): HIP device used by the decode slots created by the next YAIK_Init (default 0)
 void            YAIK_SetDevice(int device);
+// extension: YAIK_DecodeImage into DEVICE memory.  context->outputImage is an address in HBM of the device YAIK_SetDevice named when YAIK_Init
+// created the slots, outputImageStride its row pitch; the rows are RGB888, or RGBA8888 when the stream has an 'ALPM' chunk (the default
+// builder's rule), and row padding is left untouched.  The pixels never cross PCIe: the de-tile kernel writes them in place.  The buffer
+// must not be in use by work still queued on other streams.  The call returns once the pixels are in place (it synchronises the slot's
+// stream before releasing the slot).  Everything else is YAIK_DecodeImage's contract; a custom customImageOutput (it takes host planes) is
+// refused with YAIK_DECIMG_INVALIDCTX, and the slot is released as after any other failure.
+bool            YAIK_DecodeImageToDevice(void* sourceStreamAligned, uint32_t streamLength, YAIK_SDecodedImage* context);
 // extension: how 'GTIL' chunks for one or two planes (HeaderGradientTile::plane 1..6) mark tile4x4Mask.  0 (default) = exactly what the
 // reference's DecompressGradient4x4R/G/B/RG/GB/RB loops do (R/G/B leave the mask alone, GB/RB put the B marks at tile4x4Mask +
 // tile4x4MaskSize/2; decoder/YAIK_Gradient.cpp:1420-2732), after which the reference's own Decompress1D reads a different number of
