@@ -289,10 +289,13 @@ int    yk_export_tile_maps_framed(yk_ctx* c, void* devDst, size_t cap, void* con
  *                         every rank, then yk_gather_maps per image / frame;
  *   one process, n GPUs:  yk_comm_init_all over n handles (one per device), then yk_gather_maps_all. */
 /* HBM scratch for hosts that do not link the HIP runtime themselves (the C++ mirror is plain g++): buffers on the handle's device;
- * yk_device_download copies to the host on the handle's stream and synchronises it. */
+ * yk_device_download copies to the host on the handle's stream and synchronises it; yk_device_copy queues a device-to-device copy on the
+ * handle's stream and does not synchronise (both buffers on the handle's device; e.g. an encoder's per-handle streams into a buffer that
+ * outlives its next yk_select_frame). */
 int  yk_device_alloc(yk_ctx* c, size_t bytes, void** dev);
 void yk_device_free(yk_ctx* c, void* dev);
 int  yk_device_download(yk_ctx* c, void* host, const void* dev, size_t bytes);
+int  yk_device_copy(yk_ctx* c, void* devDst, const void* devSrc, size_t bytes);
 int  yk_comm_available(void);                                           /* 1 when RCCL could be loaded */
 int  yk_comm_unique_id(void* id128);                                    /* 128 bytes (ncclUniqueId) */
 int  yk_comm_init_rank(yk_ctx* c, const void* id128, int nRanks, int rank, void** comm);
@@ -410,6 +413,47 @@ int yk_decode_output_alpha(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride
 int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha);
 /* the three planes of tile4x4Mask back to back (planes 1 and 2 are meaningful once a partial-plane pass has split the masks) */
 int yk_decode_tile4x4_planes(yk_ctx* c, uint8_t* hostOut, size_t cap);
+
+/* ---- decode batches: nFrames images of ONE shape on a handle, every kernel launched once over nFrames x blocks ----
+ * A frame of 2048 x 2048 or less is a fraction of the grids the decode kernels were tuned on, and one image costs about a dozen dependent stream
+ * operations; a batch costs the same dozen.  yk_decode_begin_batch allocates the 8x8-tiled planes, the mapRGB lattice, its `loaded` flags, the
+ * lattice owners and tile4x4Mask nFrames (1..1024) times back to back (frame f at base + f * stride, like the encoder's batches) and clears what a
+ * new image needs cleared, for all frames at once.  Buffers are kept while shape and frame count stay the same.  Size rules: yk_decode_begin,
+ * which is a batch of one.  An allocation that does not fit returns YK_ERR_HIP with every decode buffer released; the next begin starts afresh.
+ *
+ * yk_decode_select_frame (default 0) points the single-image entry points at one frame of the batch: yk_decode_gradient[_device],
+ * yk_decode_gradient_all_device, yk_decode_1d[_device], yk_decode_planes[_device], yk_decode_tile4x4[_planes], yk_decode_output and
+ * yk_decode_output_device then read and write that frame only, so a caller can mix both forms and cross-check them.  (yk_decode_planes and the
+ * output calls first zero what no chunk has written yet, in every frame.)  'ALPM', 'MIPM', '3DTL' and plane-subset chunks are not batched: with
+ * nFrames > 1, yk_decode_alpha, yk_decode_output_alpha, yk_decode_output_reference_rgba, yk_decode_gradient_planes, yk_decode_split_masks,
+ * yk_decode_lut3d and yk_decode_mask return YK_ERR_STATE and touch nothing.
+ *
+ * yk_decode_gradient_all_batch_device: yk_decode_gradient_all_device for every frame.  The pass list (nPasses <= 7, tile shapes, bitmapBytes[p]) is
+ * the same for all frames; devBitmap / devRgb / rgbBytes hold nFrames * nPasses entries, frame-major (entry f * nPasses + p).  A pass without
+ * tiles in some frame is an all-zero bitmap with rgbBytes 0 (devRgb may then be NULL).  The per-frame plans (pointers, lengths) are written once
+ * per call into a table in HBM.  There is no pass-after-pass fallback: a pass of 2^25 tile slots or more is refused.
+ * yk_decode_1d_batch_device: yk_decode_1d_device for every frame; four tables of nFrames entries.  A frame with empty streams (lengths 0, pointers
+ * may be NULL) reads nothing; like a frame whose streams end early, the quadrants nothing marked are zero afterwards.  Pixel streams are read in
+ * place and must be 16-byte aligned (the encoder's are).
+ * yk_decode_output_batch_device: yk_decode_output_device for every frame, frame f at devOut + f * frameBytes; HWC when planeBytes == 0, CHW
+ * otherwise; channels 3, or 4 with a constant alpha 0..255 (ignored with 3).  Only pixel bytes are written.
+ *
+ * Results per frame are bit-identical to decoding that frame alone.  None of the three calls synchronises with the host (the scratch buffer grows
+ * on the first call of a shape, as in the single-image calls; a call waits for a table copy only when four earlier batch calls are still queued).
+ * ORDERING is the caller's, exactly as for the yk_decode_*_device entry points above: streams are read and devOut is written on THIS handle's
+ * stream.  Timed as one YK_STAGE_DEC_GRADIENT / YK_STAGE_DEC_1D / YK_STAGE_DEC_DETILE interval per call.
+ * Every refusal writes nothing and leaves the handle usable: YK_ERR_BAD_ARG for nFrames outside 1..1024, a frame index out of range, a NULL table,
+ * a NULL bitmap pointer, rgbBytes != 0 (or a 1-D length != 0) with a NULL pointer, a misaligned pixel stream, an unsupported tile shape,
+ * nPasses > 7, a pass of >= 2^25 tile slots, a colour stream of 4 GB or more, compressionRange <= 0, the layout errors of yk_decode_output_device,
+ * frameBytes < rowBytes * h (HWC) or < planeBytes * channels (CHW) with more than one frame, alpha outside 0..255 with 4 channels; YK_ERR_RANGE
+ * for bitmapBytes[p] shorter than the shape needs; YK_ERR_STATE before any begin.  yk_last_error then holds the message of that refusal. */
+int yk_decode_begin_batch(yk_ctx* c, int w, int h, int nFrames);
+int yk_decode_select_frame(yk_ctx* c, int frame);
+int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileShiftX, const int* tileShiftY, const uint8_t* const* devBitmap,
+                                        const size_t* bitmapBytes, const uint8_t* const* devRgb, const size_t* rgbBytes, int remapRange);
+int yk_decode_1d_batch_device(yk_ctx* c, const uint8_t* const* devType, const size_t* typeBytes, const uint8_t* const* devPix,
+                              const size_t* pixBytes, int compressionRange);
+int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha);
 
 /* ---- timing hooks for bench.py: HIP events on the handle's stream around every alpha stage / fused kernel / compaction.
  * Returns the averages over the yk_encode_tiles calls since the previous query (a ring of 64 event sets, older ones are

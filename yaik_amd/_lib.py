@@ -95,6 +95,7 @@ SIGNATURES = {
     "yk_device_alloc": (C.c_int, [vp, sz, C.POINTER(vp)]),
     "yk_device_free": (None, [vp, vp]),
     "yk_device_download": (C.c_int, [vp, vp, vp, sz]),
+    "yk_device_copy": (C.c_int, [vp, vp, vp, sz]),
     "yk_comm_available": (C.c_int, []),
     "yk_comm_unique_id": (C.c_int, [vp]),
     "yk_comm_init_rank": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
@@ -127,6 +128,11 @@ SIGNATURES = {
     "yk_decode_output_device": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_int]),
     "yk_decode_tile4x4": (C.c_int, [vp, vp, sz]),
     "yk_decode_tile4x4_planes": (C.c_int, [vp, vp, sz]),
+    "yk_decode_begin_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+    "yk_decode_select_frame": (C.c_int, [vp, C.c_int]),
+    "yk_decode_gradient_all_batch_device": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int]),
+    "yk_decode_1d_batch_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_int]),
+    "yk_decode_output_batch_device": (C.c_int, [vp, vp, sz, sz, sz, C.c_int, C.c_int]),
     "yk_decode_gradient_planes": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, sz]),
     "yk_decode_split_masks": (C.c_int, [vp]),
     "yk_decode_assign_lut": (C.c_int, [vp, vp, sz]),

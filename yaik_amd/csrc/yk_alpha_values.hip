@@ -272,6 +272,7 @@ extern "C" {
 int yk_decode_alpha(yk_ctx* c, int mode, const int32_t bbox[4], const uint8_t* payload, size_t n, const uint8_t* mask, size_t maskBytes,
                     const int32_t maskBBox[4], int refQuirk) {
     if (!c || !bbox || (!payload && n)) return YK_ERR_BAD_ARG;
+    YK_DEC_NO_BATCH(c, "yk_decode_alpha");
     if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     const int W = c->dw, H = c->dh;
     const int bx = bbox[0], by = bbox[1], bw = bbox[2], bh = bbox[3];

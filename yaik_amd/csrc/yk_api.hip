@@ -17,6 +17,11 @@ int yk_fail(yk_ctx* c, int code, const char* what, hipError_t e) {
     return code;
 }
 
+int yk_refuse(yk_ctx* c, int code, const char* what) {
+    if (c) c->err = what ? what : "error";
+    return code;
+}
+
 void yk_rebase(yk_ctx* c, int f) {
     const YkFrameStrides& fs = c->fs; auto& B = c->B;
     c->curFrame = f;
@@ -201,7 +206,8 @@ void yk_destroy(yk_ctx* c) {
     yk_lut_destroy(c);
     yk_lut_dec_destroy(c);
     auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-    F(c->ownedPlanes); F(c->pxStage); F(c->dPlanes); F(c->dMapRGB); F(c->dLatticeOwner); F(c->dTile4); F(c->dScratch); F(c->dLoaded); F(c->dAlpha); F(c->dAvScratch); F(c->avState); F(c->avPay); F(c->av6);
+    yk_dec_free(c);
+    F(c->ownedPlanes); F(c->pxStage); F(c->dScratch); F(c->dAlpha); F(c->dAvScratch); F(c->avState); F(c->avPay); F(c->av6);
     for (int r = 0; r < YK_EV_RING; r++) for (int i = 0; i < 5; i++) if (c->evRing[r][i]) (void)hipEventDestroy(c->evRing[r][i]);
     for (int st = 0; st < YK_NUM_STAGES; st++) for (int k = 0; k < YK_STAGE_RING; k++) for (int i = 0; i < 2; i++) if (c->stEv[st][k][i]) (void)hipEventDestroy(c->stEv[st][k][i]);
     if (c->frameGraph) (void)hipGraphExecDestroy(c->frameGraph);

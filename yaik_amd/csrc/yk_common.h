@@ -147,6 +147,13 @@ struct yk_ctx {
     int32_t* avState = nullptr; uint8_t* avPay = nullptr; size_t avPayCap = 0;      // yk_alpha_values: box + class flags, the payload
     uint8_t* av6 = nullptr; size_t av6Cap = 0;                                      // its 6-bit mask mode: tile prefixes, band scan, packed payload
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
+    // decode batch (yk_decode_begin_batch): dPlanes / dMapRGB / dLatticeOwner / dLoaded / dTile4 above are those of frame `dCur`; dB holds the
+    // allocations (frame 0) and dStride the distance in BYTES from one frame's array to the next (yk_dec_rebase), like B / fs on the encode side
+    int dFrames = 1, dCur = 0;
+    struct DBases { uint8_t* planes; uint8_t* mapRGB; uint32_t* owner; uint8_t* loaded; uint8_t* tile4; } dB = {};
+    struct DStrides { size_t planes, mapRGB, owner, loaded, tile4; } dStride = {};
+    // the per-frame tables of the batch calls on their way to HBM: a ring of pinned host buffers, each with the event behind its copy
+    void* dTabHost[4] = {}; size_t dTabHostBytes[4] = {}; hipEvent_t dTabEv[4] = {}; unsigned dTabSeq = 0;
     // timing
     // timing events: a ring of YK_EV_RING sets {alpha begin, alpha end, encode begin, encode end, pack end} so that a caller can
     // run many frames back to back and read the per-kernel averages afterwards without synchronising every frame
@@ -167,7 +174,13 @@ struct yk_ctx {
 };
 
 int yk_fail(yk_ctx* c, int code, const char* what, hipError_t e = hipSuccess);
+// yk_fail keeps the FIRST message of a handle (its callers rely on that); yk_refuse is for entry points whose refusals leave the handle usable and are
+// met again and again (the decode batch calls): the message is always that of the latest refusal
+int yk_refuse(yk_ctx* c, int code, const char* what);
 #define YK_HIP(c, call) do { hipError_t _e = (call); if (_e != hipSuccess) return yk_fail((c), YK_ERR_HIP, #call, _e); } while (0)
+
+// 'ALPM', 'MIPM', '3DTL' and plane-subset chunks act on one image: with a decode batch of more than one frame they refuse, touching nothing
+#define YK_DEC_NO_BATCH(c, name) do { if ((c)->dFrames > 1) return yk_refuse((c), YK_ERR_STATE, name " is not supported in a batch (yk_decode_begin_batch with nFrames > 1)"); } while (0)
 
 // launchers implemented in the kernel TUs
 void yk_rebase(yk_ctx* c, int frame);                    // point the working pointers at `frame`
@@ -181,6 +194,7 @@ int yk_launch_corners(yk_ctx* c);
 int yk_launch_unpack_u8(yk_ctx* c, const uint8_t* src, size_t rowBytes, size_t frameBytes, int channels, int rows, int nFrames,
                         int32_t* dst, size_t planeElems, size_t frameElems);   // yk_pixels.hip
 int yk_corners_finish(yk_ctx* c);                         // reads the corner streams' lengths back if that is still pending (synchronises)
+void yk_dec_free(yk_ctx* c);                              // frees the decode buffers of every frame and the batch tables' host ring (yk_decode.hip)
 void yk_lut_dec_destroy(yk_ctx* c);
 void yk_lut_destroy(yk_ctx* c);                          // frees the 3-D LUT bank and streams (yk_lut3d.hip)
 int yk_pp_activate(yk_ctx* c);                           // per-plane coverage / corner flags for the passes behind the RGB passes

@@ -231,8 +231,10 @@ __device__ __forceinline__ DByteGeo yk_dbyte_geo(const DPassGeo& g, uint32_t bi)
     return b;
 }
 
-__global__ __launch_bounds__(256) void yk_decall_owner_kernel(const DecPlan pl, int w, int h, int latW, const uint8_t* __restrict__ loaded, uint32_t* __restrict__ owner) {
-    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
+// The bodies of the all-passes kernels are __device__ functions: the single-image kernels call them with the plan in their arguments and the image's
+// arrays, the batch kernels (yk_*_batch_kernel below) with frame blockIdx.y's plan from the table in HBM and that frame's arrays.  blk = blockIdx.x.
+__device__ __forceinline__ void yk_decall_owner_body(const DecPlan& pl, int w, int h, int latW, const uint8_t* __restrict__ loaded, uint32_t* __restrict__ owner, const uint32_t blk) {
+    const uint32_t gi = blk * blockDim.x + threadIdx.x;
     if (gi >= pl.byteStart[7]) return;
     const int pass = yk_dplan_find(pl.byteStart, gi);
     const uint32_t bi = gi - pl.byteStart[pass];
@@ -273,16 +275,20 @@ __global__ __launch_bounds__(256) void yk_decall_owner_kernel(const DecPlan pl, 
     }
 }
 
+__global__ __launch_bounds__(256) void yk_decall_owner_kernel(const DecPlan pl, int w, int h, int latW, const uint8_t* __restrict__ loaded, uint32_t* __restrict__ owner) {
+    yk_decall_owner_body(pl, w, h, latW, loaded, owner, blockIdx.x);
+}
+
 // COUNT: corners owned per thread (a byte, kept for the emit launch) and per workgroup, non-empty bitmap words per workgroup.
 // EMIT: the owners pop their colours off the pass's stream (offset = scanned corners before them x 3) into the lattice; the workgroup's
 // non-empty words are appended to the pass's render list.
 template <bool EMIT>
-__global__ __launch_bounds__(1024) void yk_decall_stream_kernel(const DecPlan pl, int w, int h, int latW, uint8_t* __restrict__ loaded, const uint32_t* __restrict__ owner,
-                                                                uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, uint32_t* __restrict__ perThread,
-                                                                uint8_t* __restrict__ mapRGB, uint32_t* __restrict__ wordList, uint32_t factor) {
+__device__ __forceinline__ void yk_decall_stream_body(const DecPlan& pl, int w, int h, int latW, uint8_t* __restrict__ loaded, const uint32_t* __restrict__ owner,
+                                                      uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, uint32_t* __restrict__ perThread,
+                                                      uint8_t* __restrict__ mapRGB, uint32_t* __restrict__ wordList, uint32_t factor, const uint32_t blk) {
     __shared__ uint32_t s_tmp[32];
-    const int pass = yk_dplan_find(pl.blockStart, blockIdx.x);
-    const uint32_t bi = (blockIdx.x - pl.blockStart[pass]) * 1024u + threadIdx.x;
+    const int pass = yk_dplan_find(pl.blockStart, blk);
+    const uint32_t bi = (blk - pl.blockStart[pass]) * 1024u + threadIdx.x;
     const uint32_t nBytes = pl.nBytes[pass];
     const size_t ti = (size_t)pl.byteStart[pass] + bi;
     const uint8_t* const bm = pl.bm[pass];
@@ -334,16 +340,16 @@ __global__ __launch_bounds__(1024) void yk_decall_stream_kernel(const DecPlan pl
         yk_block_exscan(cnt, s_tmp, &tot);
         yk_block_exscan(wordSet ? 1u : 0u, s_tmp, &totW);
         if (bi < nBytes) perThread[ti] = ownBits;
-        if (threadIdx.x == 0) { blockSums[blockIdx.x] = tot; blockWords[blockIdx.x] = totW; }
+        if (threadIdx.x == 0) { blockSums[blk] = tot; blockWords[blk] = totW; }
         return;
     }
     uint32_t tot, totW;
     const uint32_t ex = yk_block_exscan(cnt, s_tmp, &tot);
     const uint32_t exW = yk_block_exscan(wordSet ? 1u : 0u, s_tmp, &totW);
-    if (wordSet) wordList[pl.wordStart[pass] + (blockWords[blockIdx.x] - blockWords[pl.blockStart[pass]]) + exW] = bi >> 2;
+    if (wordSet) wordList[pl.wordStart[pass] + (blockWords[blk] - blockWords[pl.blockStart[pass]]) + exW] = bi >> 2;
     constexpr uint32_t kCap = 8192;                                          // colours listed per workgroup
     __shared__ uint32_t s_li[kCap];
-    const uint32_t blockOff = (blockSums[blockIdx.x] - blockSums[pl.blockStart[pass]]) * 3u;
+    const uint32_t blockOff = (blockSums[blk] - blockSums[pl.blockStart[pass]]) * 3u;
     const uint8_t* const rgb = pl.rgb[pass];
     const uint32_t rgbBytes = pl.rgbBytes[pass];
     auto colour = [&](const uint32_t li, const uint32_t j) {                 // the j-th colour of the workgroup goes to lattice point li (:97-136)
@@ -376,8 +382,15 @@ __global__ __launch_bounds__(1024) void yk_decall_stream_kernel(const DecPlan pl
     for (uint32_t j = threadIdx.x; j < tot; j += 1024) colour(s_li[j], j);
 }
 
+template <bool EMIT>
+__global__ __launch_bounds__(1024) void yk_decall_stream_kernel(const DecPlan pl, int w, int h, int latW, uint8_t* __restrict__ loaded, const uint32_t* __restrict__ owner,
+                                                                uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, uint32_t* __restrict__ perThread,
+                                                                uint8_t* __restrict__ mapRGB, uint32_t* __restrict__ wordList, uint32_t factor) {
+    yk_decall_stream_body<EMIT>(pl, w, h, latW, loaded, owner, blockSums, blockWords, perThread, mapRGB, wordList, factor, blockIdx.x);
+}
+
 // exclusive prefixes of both per-block arrays in place (one workgroup: thread t owns a run of consecutive blocks), words listed per pass
-__global__ __launch_bounds__(1024) void yk_decall_scan_kernel(uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, const DecPlan pl, uint32_t* __restrict__ passWords) {
+__device__ __forceinline__ void yk_decall_scan_body(uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, const DecPlan& pl, uint32_t* __restrict__ passWords) {
     __shared__ uint32_t s_tmp[32];
     __shared__ uint32_t s_totalW;
     const uint32_t n = pl.blockStart[7], per = (n + 1023) / 1024;
@@ -398,6 +411,10 @@ __global__ __launch_bounds__(1024) void yk_decall_scan_kernel(uint32_t* __restri
         const uint32_t hi = pl.blockStart[threadIdx.x + 1] < n ? blockWords[pl.blockStart[threadIdx.x + 1]] : s_totalW;
         passWords[threadIdx.x] = hi - lo;
     }
+}
+
+__global__ __launch_bounds__(1024) void yk_decall_scan_kernel(uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, const DecPlan pl, uint32_t* __restrict__ passWords) {
+    yk_decall_scan_body(blockSums, blockWords, pl, passWords);
 }
 
 // render of one pass from its list of non-empty bitmap words (a launch over every word of a sparse map is mostly workgroups that start and
@@ -422,12 +439,12 @@ __global__ __launch_bounds__(256) void yk_decall_render_kernel(const uint8_t* __
 // A later, overlapping tile still overwrites an earlier one like the reference (same workgroup, passes in order, stores of a pass acknowledged
 // before the next one starts); no lists of non-empty words are needed (an empty block costs its workgroup seven small loads), and seven dependent
 // launches of 16 us each (0.11 ms of the 0.33 ms decode of an 8192 x 8192 frame) become one.
-__global__ __launch_bounds__(256) void yk_decall_render_blocks_kernel(const DecPlan pl, int w, int h, int latW, const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes,
-                                                                      size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4) {
+__device__ __forceinline__ void yk_decall_render_blocks_body(const DecPlan& pl, int w, int h, int latW, const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes,
+                                                             size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4, const uint32_t blk) {
     __shared__ DRenderLdsN<8> L;
     __shared__ uint32_t s_word[7][8], s_idx[7][8];
     const int xB64 = (w + 63) >> 6;
-    const int bx64 = (int)(blockIdx.x % (unsigned)xB64), by64 = (int)(blockIdx.x / (unsigned)xB64);
+    const int bx64 = (int)(blk % (unsigned)xB64), by64 = (int)(blk / (unsigned)xB64);
     // the (up to 8) words of every pass that cover this block, fetched together: thread = pass * 8 + slot
     if (threadIdx.x < 56) {
         const int p = threadIdx.x >> 3, k = threadIdx.x & 7;
@@ -462,6 +479,44 @@ __global__ __launch_bounds__(256) void yk_decall_render_blocks_kernel(const DecP
         yk_dec_render_words<8>(L, idx8, bits8, g, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4);
         wrote = true;
     }
+}
+
+__global__ __launch_bounds__(256) void yk_decall_render_blocks_kernel(const DecPlan pl, int w, int h, int latW, const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes,
+                                                                      size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4) {
+    yk_decall_render_blocks_body(pl, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4, blockIdx.x);
+}
+
+// ---- the same five launches over a batch: frame = blockIdx.y -------------------------------------------------------------------------------
+// Every frame of a batch has the shape of every other, so byteStart / blockStart / wordStart, the grids and the scratch layout are those of one
+// image; the frames differ in their stream pointers and colour-stream lengths.  A DecPlan is 328 bytes: up to 1024 of them do not fit kernel
+// arguments, so the call writes them once into a table in HBM and a workgroup reads its frame's plan through scalar loads (uniform address).
+// Frame f's arrays lie at base + f * stride (bytes), its scratch arrays at scratch + f * sScratch + the offsets of the single-image call.
+struct DecBatch {
+    const DecPlan* plans;
+    uint8_t* loaded; uint8_t* owner; uint8_t* mapRGB; uint8_t* planes; uint8_t* tile4; uint8_t* scratch;
+    size_t sLoaded, sOwner, sMapRGB, sPlanes, sTile4, sScratch;
+    size_t oSums, oWords, oPassWords, oPerThread, oList;
+};
+__device__ __forceinline__ uint32_t* yk_dbatch_u32(const DecBatch& B, size_t f, size_t off) { return reinterpret_cast<uint32_t*>(B.scratch + f * B.sScratch + off); }
+
+__global__ __launch_bounds__(256) void yk_decall_owner_batch_kernel(const DecBatch B, int w, int h, int latW) {
+    const size_t f = blockIdx.y;
+    yk_decall_owner_body(B.plans[f], w, h, latW, B.loaded + f * B.sLoaded, reinterpret_cast<uint32_t*>(B.owner + f * B.sOwner), blockIdx.x);
+}
+template <bool EMIT>
+__global__ __launch_bounds__(1024) void yk_decall_stream_batch_kernel(const DecBatch B, int w, int h, int latW, uint32_t factor) {
+    const size_t f = blockIdx.y;
+    yk_decall_stream_body<EMIT>(B.plans[f], w, h, latW, B.loaded + f * B.sLoaded, reinterpret_cast<const uint32_t*>(B.owner + f * B.sOwner), yk_dbatch_u32(B, f, B.oSums),
+                                yk_dbatch_u32(B, f, B.oWords), yk_dbatch_u32(B, f, B.oPerThread), B.mapRGB + f * B.sMapRGB, yk_dbatch_u32(B, f, B.oList), factor, blockIdx.x);
+}
+__global__ __launch_bounds__(1024) void yk_decall_scan_batch_kernel(const DecBatch B) {       // one workgroup per frame
+    const size_t f = blockIdx.x;
+    yk_decall_scan_body(yk_dbatch_u32(B, f, B.oSums), yk_dbatch_u32(B, f, B.oWords), B.plans[f], yk_dbatch_u32(B, f, B.oPassWords));
+}
+__global__ __launch_bounds__(256) void yk_decall_render_blocks_batch_kernel(const DecBatch B, int w, int h, int latW, size_t planeSize, int tileW, int stride4) {
+    const size_t f = blockIdx.y;
+    yk_decall_render_blocks_body(B.plans[f], w, h, latW, B.mapRGB + f * B.sMapRGB, B.planes + f * B.sPlanes, planeSize, tileW,
+                                 reinterpret_cast<uint32_t*>(B.tile4 + f * B.sTile4), stride4, blockIdx.x);
 }
 
 // ---- partial planes: DecompressGradient4x4R / G / B / RG / GB / RB (decoder/YAIK_Gradient.cpp:1208-1226, :1420-2732) ------------
@@ -571,18 +626,23 @@ __device__ __forceinline__ int yk_d1_quads(const uint8_t* __restrict__ tile4, in
 __device__ __forceinline__ uint32_t yk_d1_packed_count(int q) { return (q != 0xF ? 1u : 0u) | ((16u * (4u - (uint32_t)__popc(q))) << 11); }
 
 // per block of 1024 tiles: coded tiles and pixel bytes, from the mask alone
-__global__ __launch_bounds__(1024) void yk_dec1d_count_kernel(const uint8_t* __restrict__ tile4, int stride4, int tilesW, size_t T8,
-                                                              uint32_t* __restrict__ blockTiles, uint32_t* __restrict__ blockPix, uint32_t* __restrict__ offInBlk) {
+// (bodies as __device__ functions, shared with the batch kernels below: bx = blockIdx.x)
+__device__ __forceinline__ void yk_dec1d_count_body(const uint8_t* __restrict__ tile4, int stride4, int tilesW, size_t T8,
+                                                    uint32_t* __restrict__ blockTiles, uint32_t* __restrict__ blockPix, uint32_t* __restrict__ offInBlk, const uint32_t bx) {
     __shared__ uint32_t s_tmp[32];
-    const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x;
+    const size_t i = (size_t)bx * 1024 + threadIdx.x;
     uint32_t tot;
     const int q = yk_d1_quads(tile4, stride4, tilesW, T8, i);
     const uint32_t e = yk_block_exscan(yk_d1_packed_count(q), s_tmp, &tot);
     if (i < T8) offInBlk[i] = e | ((uint32_t)q << 28);                         // the tile's packed offsets inside its block (28 bits) + its quadrant mask
-    if (threadIdx.x == 0) { blockTiles[blockIdx.x] = tot & 2047u; blockPix[blockIdx.x] = tot >> 11; }
+    if (threadIdx.x == 0) { blockTiles[bx] = tot & 2047u; blockPix[bx] = tot >> 11; }
+}
+__global__ __launch_bounds__(1024) void yk_dec1d_count_kernel(const uint8_t* __restrict__ tile4, int stride4, int tilesW, size_t T8,
+                                                              uint32_t* __restrict__ blockTiles, uint32_t* __restrict__ blockPix, uint32_t* __restrict__ offInBlk) {
+    yk_dec1d_count_body(tile4, stride4, tilesW, T8, blockTiles, blockPix, offInBlk, blockIdx.x);
 }
 // both block-sum arrays -> exclusive prefixes in place, totals[0] = coded tiles, totals[1] = pixel bytes (one launch)
-__global__ __launch_bounds__(1024) void yk_dec1d_scan_kernel(uint32_t* __restrict__ blockTiles, uint32_t* __restrict__ blockPix, int nBlocks, uint32_t* __restrict__ totals) {
+__device__ __forceinline__ void yk_dec1d_scan_body(uint32_t* __restrict__ blockTiles, uint32_t* __restrict__ blockPix, int nBlocks, uint32_t* __restrict__ totals) {
     __shared__ uint32_t s_tmp[32];
 #pragma unroll 1
     for (int a = 0; a < 2; a++) {
@@ -600,6 +660,10 @@ __global__ __launch_bounds__(1024) void yk_dec1d_scan_kernel(uint32_t* __restric
     }
 }
 
+__global__ __launch_bounds__(1024) void yk_dec1d_scan_kernel(uint32_t* __restrict__ blockTiles, uint32_t* __restrict__ blockPix, int nBlocks, uint32_t* __restrict__ totals) {
+    yk_dec1d_scan_body(blockTiles, blockPix, nBlocks, totals);
+}
+
 // FOUR lanes per tile, one lane per pair of rows of one half of the tile; a tile's offsets in the type and pixel streams come from the count
 // kernel's per-tile scan (offInBlk) + the scanned block sums, so the kernel is a plain stream: no workgroup scan, no barrier, every lane's loads
 // independent of every other lane's (the first form scanned 1024 tiles per workgroup of 1024 threads and then walked them in four rounds: two
@@ -610,11 +674,11 @@ __global__ __launch_bounds__(1024) void yk_dec1d_scan_kernel(uint32_t* __restric
 #ifndef YK_D1_TPL
 #define YK_D1_TPL 4
 #endif
-__global__ __launch_bounds__(256) void yk_dec1d_kernel(const uint32_t* __restrict__ offInBlk, size_t T8,
-                                                       const uint32_t* __restrict__ baseTiles, const uint32_t* __restrict__ basePix,
-                                                       const uint32_t* __restrict__ totals /*[0]=tiles,[1]=pix*/, const uint8_t* __restrict__ type, size_t typeBytes,
-                                                       const uint8_t* __restrict__ pix, size_t pixBytes, int invRange,
-                                                       uint8_t* __restrict__ planes, size_t planeSize, int planeOverride, const uint32_t* __restrict__ runBase) {
+__device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offInBlk, size_t T8,
+                                              const uint32_t* __restrict__ baseTiles, const uint32_t* __restrict__ basePix,
+                                              const uint32_t* __restrict__ totals /*[0]=tiles,[1]=pix*/, const uint8_t* __restrict__ type, size_t typeBytes,
+                                              const uint8_t* __restrict__ pix, size_t pixBytes, int invRange,
+                                              uint8_t* __restrict__ planes, size_t planeSize, int planeOverride, const uint32_t* __restrict__ runBase, const uint32_t bx) {
     // planeOverride < 0: the three planes share one mask (no partial-plane pass ran): plane = blockIdx.y, its streams start at
     // plane * totals.  Otherwise one plane per launch with its own mask, streams start at runBase (tiles, pixels of the planes before it).
     const int p = planeOverride < 0 ? (int)blockIdx.y : planeOverride;
@@ -627,7 +691,7 @@ __global__ __launch_bounds__(256) void yk_dec1d_kernel(const uint32_t* __restric
     uint32_t ow[YK_D1_TPL];
 #pragma unroll
     for (int rep = 0; rep < YK_D1_TPL; rep++) {
-        const size_t i = ((size_t)blockIdx.x * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
+        const size_t i = ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
         ow[rep] = i < T8 ? offInBlk[i] : 0xF0000000u;                           // past the end: a tile with nothing to decode
     }
     int tb[YK_D1_TPL]; uint4 L[YK_D1_TPL]; bool coded[YK_D1_TPL], live[YK_D1_TPL];
@@ -636,8 +700,8 @@ __global__ __launch_bounds__(256) void yk_dec1d_kernel(const uint32_t* __restric
         const int q = (int)(ow[rep] >> 28);
         const int qh = (q >> (half * 2)) & 3;                                    // bit 0: left quadrant filled, bit 1: right
         // the 64 tiles of a workgroup's round lie in one scan block: its two bases are scalar loads
-        const size_t blk = (((size_t)blockIdx.x * YK_D1_TPL + rep) * 64) >> 10;
-        const bool inRange = (((size_t)blockIdx.x * YK_D1_TPL + rep) * 64) < T8;
+        const size_t blk = (((size_t)bx * YK_D1_TPL + rep) * 64) >> 10;
+        const bool inRange = (((size_t)bx * YK_D1_TPL + rep) * 64) < T8;
         const uint32_t offT = (inRange ? baseTiles[blk] : 0u) + (ow[rep] & 2047u), offP = (inRange ? basePix[blk] : 0u) + ((ow[rep] >> 11) & 0x1FFFFu);
         const int nTop = 2 - (q & 1) - ((q >> 1) & 1);
         const size_t to = (baseT + offT) * 3;
@@ -659,7 +723,7 @@ __global__ __launch_bounds__(256) void yk_dec1d_kernel(const uint32_t* __restric
     }
 #pragma unroll
     for (int rep = 0; rep < YK_D1_TPL; rep++) {
-        const size_t i = ((size_t)blockIdx.x * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
+        const size_t i = ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
         const int q = (int)(ow[rep] >> 28);
         const int qh = (q >> (half * 2)) & 3;
         const int color0 = __builtin_amdgcn_update_dpp(0, tb[rep], 0x00, 0xF, 0xF, true), base = __builtin_amdgcn_update_dpp(0, tb[rep], 0x55, 0xF, 0xF, true),
@@ -693,6 +757,41 @@ __global__ __launch_bounds__(256) void yk_dec1d_kernel(const uint32_t* __restric
             *reinterpret_cast<uint32_t*>(o + 8 + side * 4) = dec4(L[rep].y);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void yk_dec1d_kernel(const uint32_t* __restrict__ offInBlk, size_t T8,
+                                                       const uint32_t* __restrict__ baseTiles, const uint32_t* __restrict__ basePix,
+                                                       const uint32_t* __restrict__ totals /*[0]=tiles,[1]=pix*/, const uint8_t* __restrict__ type, size_t typeBytes,
+                                                       const uint8_t* __restrict__ pix, size_t pixBytes, int invRange,
+                                                       uint8_t* __restrict__ planes, size_t planeSize, int planeOverride, const uint32_t* __restrict__ runBase) {
+    yk_dec1d_body(offInBlk, T8, baseTiles, basePix, totals, type, typeBytes, pix, pixBytes, invRange, planes, planeSize, planeOverride, runBase, blockIdx.x);
+}
+
+// ---- the 1-D chunk over a batch: the same three launches, frame = blockIdx.y (count), blockIdx.x (scan: one workgroup per frame), blockIdx.z
+// (decode: blockIdx.y stays the plane).  A frame's streams (pointers and lengths) come from a table in HBM; its mask, planes and scratch arrays
+// lie at base + f * stride.  The masks of a batch are never split (plane-subset chunks are refused), so the three planes share one count and scan.
+struct D1Frame { const uint8_t* type; const uint8_t* pix; unsigned long long typeBytes, pixBytes; };
+struct D1Batch {
+    const D1Frame* frames;
+    const uint8_t* tile4; uint8_t* planes; uint8_t* scratch;
+    size_t sTile4, sPlanes, sScratch;
+    size_t oBT, oBP, oTot, oOff;
+};
+__device__ __forceinline__ uint32_t* yk_d1batch_u32(const D1Batch& B, size_t f, size_t off) { return reinterpret_cast<uint32_t*>(B.scratch + f * B.sScratch + off); }
+
+__global__ __launch_bounds__(1024) void yk_dec1d_count_batch_kernel(const D1Batch B, int stride4, int tilesW, size_t T8) {
+    const size_t f = blockIdx.y;
+    yk_dec1d_count_body(B.tile4 + f * B.sTile4, stride4, tilesW, T8, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oOff), blockIdx.x);
+}
+__global__ __launch_bounds__(1024) void yk_dec1d_scan_batch_kernel(const D1Batch B, int nBlocks) {
+    const size_t f = blockIdx.x;
+    yk_dec1d_scan_body(yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), nBlocks, yk_d1batch_u32(B, f, B.oTot));
+}
+__global__ __launch_bounds__(256) void yk_dec1d_batch_kernel(const D1Batch B, size_t T8, int invRange, size_t planeSize) {
+    const size_t f = blockIdx.z;
+    const D1Frame& fr = B.frames[f];
+    yk_dec1d_body(yk_d1batch_u32(B, f, B.oOff), T8, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oTot), fr.type, (size_t)fr.typeBytes,
+                  fr.pix, (size_t)fr.pixBytes, invRange, B.planes + f * B.sPlanes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x);
 }
 
 __global__ void yk_dec_mask_kernel(const uint8_t* __restrict__ bits, int bw, int bh, unsigned long long* __restrict__ out) {
@@ -797,11 +896,11 @@ __device__ __forceinline__ void yk_dt_store(const YkDetileArgs& a, const YkDtUni
 }
 
 template <int C, bool PLANAR, int ASRC>
-__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_kernel(YkDetileArgs a) {
+__device__ __forceinline__ void yk_dec_detile_body(const YkDetileArgs& a, const uint32_t bx) {
     const uint32_t lane = threadIdx.x & 63, rp = lane & 3;
     // unit of step k: blockIdx.x * K * 4 + k * 4 + wave, so the four waves of a workgroup stream 4 KB of every plane per step
-    const uint32_t t0 = (blockIdx.x * (YK_DT_K * 4) + (threadIdx.x >> 6)) * 16 + (lane >> 2);
-    if ((blockIdx.x + 1) * (uint32_t)YK_DT_TILES <= a.nTiles) {
+    const uint32_t t0 = (bx * (YK_DT_K * 4) + (threadIdx.x >> 6)) * 16 + (lane >> 2);
+    if ((bx + 1) * (uint32_t)YK_DT_TILES <= a.nTiles) {
         YkDtUnit u[YK_DT_K];                                                  // every unit of the workgroup exists: all loads first
 #pragma unroll
         for (int k = 0; k < YK_DT_K; k++) yk_dt_load<C, PLANAR, ASRC>(a, t0 + k * 64, rp, u[k]);
@@ -819,22 +918,41 @@ __global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_kernel(YkDetileAr
 }
 
 template <int C, bool PLANAR, int ASRC>
-static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((yk_dec_detile_kernel<C, PLANAR, ASRC>), dim3((a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES), dim3(YK_DT_THREADS), 0, s, a);
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_kernel(YkDetileArgs a) {
+    yk_dec_detile_body<C, PLANAR, ASRC>(a, blockIdx.x);
+}
+// a batch: frame blockIdx.y's planes at a.planes + f * planesFrame, its pixels at a.out + f * outFrame
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_batch_kernel(YkDetileArgs a, size_t planesFrame, size_t outFrame) {
+    a.planes += (size_t)blockIdx.y * planesFrame; a.out += (size_t)blockIdx.y * outFrame;
+    yk_dec_detile_body<C, PLANAR, ASRC>(a, blockIdx.x);
+}
+
+// nFrames == 0: the image c->dPlanes points at (the existing single-image launch); otherwise nFrames frames, planesFrame / outFrame bytes apart
+template <int C, bool PLANAR, int ASRC>
+static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, size_t planesFrame = 0, size_t outFrame = 0) {
+    const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
+    if constexpr (ASRC != YK_DT_ALPHA_PLANE) {                                 // a batch has no alpha plane
+        if (nFrames) { hipLaunchKernelGGL((yk_dec_detile_batch_kernel<C, PLANAR, ASRC>), dim3(gx, (unsigned)nFrames), dim3(YK_DT_THREADS), 0, s, a, planesFrame, outFrame); return; }
+    }
+    hipLaunchKernelGGL((yk_dec_detile_kernel<C, PLANAR, ASRC>), dim3(gx), dim3(YK_DT_THREADS), 0, s, a);
 }
 
 // the de-tile of the image begun on c into out; alpha: a plane (strideA bytes per row) or NULL with alphaConst 0..255 (channels 4)
-static int yk_dec_detile(yk_ctx* c, uint8_t* out, size_t rowBytes, size_t planeBytes, int channels, const uint8_t* alpha, size_t strideA, int alphaConst) {
+// frameBytes / nFrames: every frame of a batch in one launch (alpha constant or none), frame f at out + f * frameBytes; nFrames == 0: the selected frame
+static int yk_dec_detile(yk_ctx* c, uint8_t* out, size_t rowBytes, size_t planeBytes, int channels, const uint8_t* alpha, size_t strideA, int alphaConst,
+                         int nFrames = 0, size_t frameBytes = 0) {
     YkDetileArgs a;
-    a.planes = c->dPlanes; a.planeSize = c->dPlaneSize;
+    a.planes = nFrames ? c->dB.planes : c->dPlanes; a.planeSize = c->dPlaneSize;
+    const size_t pf = c->dStride.planes;
     a.alpha = alpha; a.strideA = strideA; a.alphaConst = (uint32_t)(alphaConst & 255) * 0x01010101u;
     a.out = out; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
     a.tileW = (uint32_t)(c->dw >> 3); a.nTiles = (uint32_t)(c->dw >> 3) * (uint32_t)(c->dh >> 3);
     const bool planar = planeBytes > 0;
     { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
-    if (channels == 3) { if (planar) yk_dt_launch<3, true, YK_DT_ALPHA_NONE>(a, c->stream); else yk_dt_launch<3, false, YK_DT_ALPHA_NONE>(a, c->stream); }
+    if (channels == 3) { if (planar) yk_dt_launch<3, true, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes); else yk_dt_launch<3, false, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes); }
     else if (alpha)    { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_PLANE>(a, c->stream); else yk_dt_launch<4, false, YK_DT_ALPHA_PLANE>(a, c->stream); }
-    else               { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_CONST>(a, c->stream); else yk_dt_launch<4, false, YK_DT_ALPHA_CONST>(a, c->stream); }
+    else               { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes); else yk_dt_launch<4, false, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes); }
     YK_HIP(c, hipGetLastError());
     return yk_stage_end(c, YK_STAGE_DEC_DETILE);
 }
@@ -862,8 +980,8 @@ static int yk_dec_scratch(yk_ctx* c, size_t bytes) {
 extern "C" {
 
 // zero every 4x4 cell tile4x4Mask does not mark (thread = 8x8 tile and plane; the mask is shared by the planes until a plane-subset pass splits it)
-__global__ __launch_bounds__(256) void yk_dec_zero_unmarked_kernel(const uint8_t* __restrict__ tile4, size_t tile4Size, int split, int stride4, int tilesW, size_t T8,
-                                                                   uint8_t* __restrict__ planes, size_t planeSize) {
+__device__ __forceinline__ void yk_dec_zero_unmarked_body(const uint8_t* __restrict__ tile4, size_t tile4Size, int split, int stride4, int tilesW, size_t T8,
+                                                          uint8_t* __restrict__ planes, size_t planeSize) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int p = blockIdx.y;
     if (i >= T8) return;
@@ -878,48 +996,138 @@ __global__ __launch_bounds__(256) void yk_dec_zero_unmarked_kernel(const uint8_t
             if (!((m >> (sh + qy * 2 + qx)) & 1))
                 for (int r = 0; r < 4; r++) *reinterpret_cast<uint32_t*>(o + (qy * 4 + r) * 8 + qx * 4) = 0u;
 }
+__global__ __launch_bounds__(256) void yk_dec_zero_unmarked_kernel(const uint8_t* __restrict__ tile4, size_t tile4Size, int split, int stride4, int tilesW, size_t T8,
+                                                                   uint8_t* __restrict__ planes, size_t planeSize) {
+    yk_dec_zero_unmarked_body(tile4, tile4Size, split, stride4, tilesW, T8, planes, planeSize);
+}
+// every frame of a batch: frame = blockIdx.z (the masks of a batch are never split)
+__global__ __launch_bounds__(256) void yk_dec_zero_unmarked_batch_kernel(const uint8_t* __restrict__ tile4, size_t sTile4, size_t tile4Size, int stride4, int tilesW, size_t T8,
+                                                                         uint8_t* __restrict__ planes, size_t sPlanes, size_t planeSize) {
+    yk_dec_zero_unmarked_body(tile4 + (size_t)blockIdx.z * sTile4, tile4Size, 0, stride4, tilesW, T8, planes + (size_t)blockIdx.z * sPlanes, planeSize);
+}
 static int yk_dec_settle(yk_ctx* c) {
     if (!c->dPlanesStale) return YK_OK;
     const int w = c->dw, h = c->dh;
     const size_t T8 = (size_t)(w >> 3) * (h >> 3);
-    hipLaunchKernelGGL(yk_dec_zero_unmarked_kernel, dim3((unsigned)((T8 + 255) / 256), 3), dim3(256), 0, c->stream, c->dTile4, c->dTile4Size, c->dSplit ? 1 : 0,
-                       (w + 15) >> 4, w >> 3, T8, c->dPlanes, c->dPlaneSize);
+    if (c->dFrames == 1)
+        hipLaunchKernelGGL(yk_dec_zero_unmarked_kernel, dim3((unsigned)((T8 + 255) / 256), 3), dim3(256), 0, c->stream, c->dTile4, c->dTile4Size, c->dSplit ? 1 : 0,
+                           (w + 15) >> 4, w >> 3, T8, c->dPlanes, c->dPlaneSize);
+    else                                                                        // the flag is the handle's: what it says holds for every frame
+        hipLaunchKernelGGL(yk_dec_zero_unmarked_batch_kernel, dim3((unsigned)((T8 + 255) / 256), 3, (unsigned)c->dFrames), dim3(256), 0, c->stream, c->dB.tile4, c->dStride.tile4,
+                           c->dTile4Size, (w + 15) >> 4, w >> 3, T8, c->dB.planes, c->dStride.planes, c->dPlaneSize);
     YK_HIP(c, hipGetLastError());
     c->dPlanesStale = false;
     return YK_OK;
 }
 
-int yk_decode_begin(yk_ctx* c, int w, int h) {
-    if (!c) return YK_ERR_BAD_ARG;
+
+// point the working pointers at `frame` (yk_rebase of the decode side)
+static void yk_dec_rebase(yk_ctx* c, int f) {
+    c->dCur = f;
+    c->dPlanes = c->dB.planes + (size_t)f * c->dStride.planes; c->dMapRGB = c->dB.mapRGB + (size_t)f * c->dStride.mapRGB;
+    c->dLatticeOwner = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(c->dB.owner) + (size_t)f * c->dStride.owner);
+    c->dLoaded = c->dB.loaded + (size_t)f * c->dStride.loaded; c->dTile4 = c->dB.tile4 + (size_t)f * c->dStride.tile4;
+}
+
+static void yk_dec_free_frames(yk_ctx* c) {
+    auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
+    F(c->dB.planes); F(c->dB.mapRGB); F(c->dB.owner); F(c->dB.tile4); F(c->dB.loaded);
+    c->dPlanes = nullptr; c->dMapRGB = nullptr; c->dLatticeOwner = nullptr; c->dTile4 = nullptr; c->dLoaded = nullptr;
+    c->dw = c->dh = 0; c->dFrames = 1; c->dCur = 0;
+}
+
+}  // extern "C"
+void yk_dec_free(yk_ctx* c) {
+    yk_dec_free_frames(c);
+    for (int i = 0; i < 4; i++) {
+        if (c->dTabHost[i]) { (void)hipHostFree(c->dTabHost[i]); c->dTabHost[i] = nullptr; c->dTabHostBytes[i] = 0; }
+        if (c->dTabEv[i]) { (void)hipEventDestroy(c->dTabEv[i]); c->dTabEv[i] = nullptr; }
+    }
+}
+extern "C" {
+
+// Every per-image array nFrames times back to back, frame f at base + f * stride; strides are multiples of 16 bytes (the lattice is read a word
+// at a time, tile4x4Mask is marked with 32-bit atomics).  Buffers are kept while the shape and the frame count stay the same: only the clears run.
+static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
     // the sizes the encoder accepts (yk_set_image).  At sides of 8 (mod 16) the 8x8-tiled planes have an odd tileW = w >> 3, the tile4x4Mask stride
     // stays (w + 15) >> 4 (its last byte of a row holds one 8x8 tile) and every tile that reaches past the right or bottom edge is skipped
     if (w < 8 || h < 8 || (w & 7) || (h & 7) || w > 32760 || h > 32760) return yk_fail(c, YK_ERR_BAD_ARG, "decode needs width/height multiples of 8 in 8..32760");
     YK_HIP(c, hipSetDevice(c->device));
-    const size_t lat = (size_t)(w / 4 + 1) * (h / 4 + 1);
-    if (!c->dPlanes || c->dw != w || c->dh != h) {                             // a stream of images of one shape keeps its buffers: only the clears below
+    const size_t lat = (size_t)(w / 4 + 1) * (h / 4 + 1), N = (size_t)nFrames;
+    auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    if (!c->dB.planes || c->dw != w || c->dh != h || c->dFrames != nFrames) {   // a stream of images (or batches) of one shape keeps its buffers: only the clears below
         YK_HIP(c, hipStreamSynchronize(c->stream));
-        auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-        F(c->dPlanes); F(c->dMapRGB); F(c->dLatticeOwner); F(c->dTile4); F(c->dLoaded);
-        c->dw = w; c->dh = h;
+        yk_dec_free_frames(c);
         const int tileW = w >> 3, tileH = h >> 3;
         c->dPlaneSize = (size_t)tileW * tileH * 64;
         const int stride4 = (w + 15) >> 4;
         c->dTile4Size = (size_t)((stride4 << 2) * (((h + 7) >> 3) << 1)) >> 3;
-        YK_HIP(c, hipMalloc(&c->dPlanes, c->dPlaneSize * 3));
-        YK_HIP(c, hipMalloc(&c->dMapRGB, lat * 3 + 4));                              // + 4: the render reads a corner's three bytes as one word
-        YK_HIP(c, hipMalloc(&c->dLatticeOwner, lat * 4));
-        YK_HIP(c, hipMalloc(&c->dLoaded, lat));
-        YK_HIP(c, hipMalloc(&c->dTile4, ((3 * c->dTile4Size + 3) & ~(size_t)3) + 4));   // three planes once the masks are split
+        c->dStride.planes = c->dPlaneSize * 3;
+        c->dStride.mapRGB = up16(lat * 3 + 4);                                       // + 4: the render reads a corner's three bytes as one word
+        c->dStride.owner = up16(lat * 4);
+        c->dStride.loaded = up16(lat);
+        c->dStride.tile4 = up16(((3 * c->dTile4Size + 3) & ~(size_t)3) + 4);         // three planes once the masks are split
+        hipError_t e = hipMalloc(&c->dB.planes, c->dStride.planes * N);
+        if (e == hipSuccess) e = hipMalloc(&c->dB.mapRGB, c->dStride.mapRGB * N);
+        if (e == hipSuccess) e = hipMalloc(&c->dB.owner, c->dStride.owner * N);
+        if (e == hipSuccess) e = hipMalloc(&c->dB.loaded, c->dStride.loaded * N);
+        if (e == hipSuccess) e = hipMalloc(&c->dB.tile4, c->dStride.tile4 * N);
+        if (e != hipSuccess) {                                                       // what was allocated is released: the next begin starts afresh
+            (void)hipGetLastError();
+            yk_dec_free_frames(c);
+            return yk_refuse(c, YK_ERR_HIP, "the decode buffers of this shape and frame count do not fit in device memory");
+        }
+        c->dw = w; c->dh = h; c->dFrames = nFrames;
     }
+    yk_dec_rebase(c, 0);
     // The planes (3 B per pixel: 201 MB at 8192 x 8192, 40 us of every frame) are NOT cleared: every renderer marks what it writes in tile4x4Mask and
     // the 1-D decode writes every unmarked quadrant, so after a whole file nothing stale is left; a flow that stops earlier (or writes without
     // marking: the plane-subset loops) gets the unmarked cells zeroed when it needs them (yk_dec_settle).
     c->dPlanesStale = true;
-    YK_HIP(c, hipMemsetAsync(c->dMapRGB, 0, lat * 3, c->stream));
-    YK_HIP(c, hipMemsetAsync(c->dLoaded, 0, lat, c->stream));
-    YK_HIP(c, hipMemsetAsync(c->dTile4, 0, ((3 * c->dTile4Size + 3) & ~(size_t)3) + 4, c->stream));
+    YK_HIP(c, hipMemsetAsync(c->dB.mapRGB, 0, c->dStride.mapRGB * N, c->stream));
+    YK_HIP(c, hipMemsetAsync(c->dB.loaded, 0, c->dStride.loaded * N, c->stream));
+    YK_HIP(c, hipMemsetAsync(c->dB.tile4, 0, c->dStride.tile4 * N, c->stream));
     c->dSplit = false;
     c->dAlphaValid = false;                                                     // an 'ALPM' plane belongs to one image
+    return YK_OK;
+}
+
+int yk_decode_begin(yk_ctx* c, int w, int h) {
+    if (!c) return YK_ERR_BAD_ARG;
+    return yk_dec_begin(c, w, h, 1);
+}
+
+int yk_decode_begin_batch(yk_ctx* c, int w, int h, int nFrames) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (nFrames < 1 || nFrames > 1024) return yk_refuse(c, YK_ERR_BAD_ARG, "nFrames must be 1..1024");
+    return yk_dec_begin(c, w, h, nFrames);
+}
+
+int yk_decode_select_frame(yk_ctx* c, int frame) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (frame < 0 || frame >= c->dFrames) return yk_refuse(c, YK_ERR_BAD_ARG, "frame out of range");
+    yk_dec_rebase(c, frame);
+    return YK_OK;
+}
+
+// The per-frame tables of a batch call travel through a ring of four pinned host buffers: the call fills one, queues its copy into HBM and records
+// an event behind the copy.  A slot is waited for only when it comes round again, i.e. when the tables of four earlier batch calls are still queued.
+static int yk_dec_table_host(yk_ctx* c, size_t bytes, int* slot, void** host) {
+    const int k = (int)(c->dTabSeq++ & 3u);
+    if (c->dTabEv[k]) YK_HIP(c, hipEventSynchronize(c->dTabEv[k]));
+    else YK_HIP(c, hipEventCreateWithFlags(&c->dTabEv[k], hipEventDisableTiming));
+    if (c->dTabHostBytes[k] < bytes) {
+        if (c->dTabHost[k]) { (void)hipHostFree(c->dTabHost[k]); c->dTabHost[k] = nullptr; c->dTabHostBytes[k] = 0; }
+        YK_HIP(c, hipHostMalloc(&c->dTabHost[k], bytes, hipHostMallocDefault));
+        c->dTabHostBytes[k] = bytes;
+    }
+    *slot = k; *host = c->dTabHost[k];
+    return YK_OK;
+}
+static int yk_dec_table_upload(yk_ctx* c, int slot, void* dev, size_t bytes) {
+    YK_HIP(c, hipMemcpyAsync(dev, c->dTabHost[slot], bytes, hipMemcpyHostToDevice, c->stream));
+    YK_HIP(c, hipEventRecord(c->dTabEv[slot], c->stream));
     return YK_OK;
 }
 
@@ -993,7 +1201,7 @@ int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX,
     for (int p = 0; p < nPasses; p++) {
         bool found = false; for (auto& o : ok) found |= (o[0] == tileShiftX[p] && o[1] == tileShiftY[p]);
         if (!found) return yk_fail(c, YK_ERR_BAD_ARG, "unsupported tile format");
-        if (!devBitmap[p] || (rgbBytes[p] && !devRgb[p])) return YK_ERR_BAD_ARG;
+        if (!devBitmap[p] || (rgbBytes[p] && !devRgb[p])) return yk_fail(c, YK_ERR_BAD_ARG, "NULL tile bitmap, or NULL colour stream with a length");
         if (p < 7) {
             const DPassGeo g = yk_dpass_geo(tileShiftX[p], tileShiftY[p], w);
             need[p] = ((size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount) >> 3;
@@ -1048,6 +1256,79 @@ int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX,
     return YK_OK;
 }
 
+// The same over every frame of the batch begun by yk_decode_begin_batch: one clear, one table copy and the five launches, each over nFrames x blocks.
+int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileShiftX, const int* tileShiftY, const uint8_t* const* devBitmap, const size_t* bitmapBytes,
+                                        const uint8_t* const* devRgb, const size_t* rgbBytes, int remapRange) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (nPasses < 0 || nPasses > 7) return yk_refuse(c, YK_ERR_BAD_ARG, "a batch takes 0..7 gradient passes per call");
+    if (nPasses && (!tileShiftX || !tileShiftY || !devBitmap || !bitmapBytes || !devRgb || !rgbBytes)) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
+    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    if (nPasses == 0) return YK_OK;
+    const int w = c->dw, h = c->dh, latW = w / 4 + 1, N = c->dFrames;
+    static const int ok[7][2] = { {4,4},{4,3},{3,4},{3,3},{3,2},{2,3},{2,2} };
+    size_t need[7] = {};
+    for (int p = 0; p < nPasses; p++) {
+        bool found = false; for (auto& o : ok) found |= (o[0] == tileShiftX[p] && o[1] == tileShiftY[p]);
+        if (!found) return yk_refuse(c, YK_ERR_BAD_ARG, "unsupported tile format");
+        const DPassGeo g = yk_dpass_geo(tileShiftX[p], tileShiftY[p], w);
+        need[p] = ((size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount) >> 3;
+        if (need[p] * 8 >= ((size_t)1 << 25)) return yk_refuse(c, YK_ERR_BAD_ARG, "a pass of 2^25 tile slots or more does not fit a batch (decode such images one by one)");
+        if (bitmapBytes[p] < need[p]) return yk_refuse(c, YK_ERR_RANGE, "tile bitmap shorter than the image needs");
+    }
+    for (size_t i = 0; i < (size_t)N * nPasses; i++) {
+        if (!devBitmap[i]) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL tile bitmap");
+        if (rgbBytes[i] && !devRgb[i]) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL colour stream with a length");
+        if (rgbBytes[i] > 0xFFFFFFFFu) return yk_refuse(c, YK_ERR_BAD_ARG, "colour stream of 4 GB or more");
+    }
+    YK_HIP(c, hipSetDevice(c->device));
+    DecPlan pl = {};                                                          // what the frames share: the geometry
+    pl.n = nPasses;
+    for (int p = 0; p < 7; p++) {
+        const size_t nb = p < nPasses ? need[p] : 0;
+        pl.nBytes[p] = (uint32_t)nb;
+        pl.sx[p] = p < nPasses ? tileShiftX[p] : 4; pl.sy[p] = p < nPasses ? tileShiftY[p] : 4;
+        pl.byteStart[p + 1] = pl.byteStart[p] + (uint32_t)nb;
+        pl.blockStart[p + 1] = pl.blockStart[p] + (uint32_t)((nb + 1023) / 1024);
+        pl.wordStart[p + 1] = pl.wordStart[p] + (uint32_t)((nb + 3) / 4);
+    }
+    const size_t nbTot = pl.blockStart[7], nBytesTot = pl.byteStart[7], nWordsTot = pl.wordStart[7];
+    // scratch: [plan table] then per frame, at a fixed stride, the arrays of yk_decode_gradient_all_device
+    const size_t tabBytes = ((size_t)N * sizeof(DecPlan) + 255) & ~(size_t)255;
+    const size_t oS = 0, oW = oS + nbTot * 4, oP = oW + nbTot * 4, oT = oP + 64, oL = (oT + nBytesTot * 4 + 15) & ~(size_t)15;
+    const size_t sS = (oL + nWordsTot * 4 + 64 + 15) & ~(size_t)15;
+    { const int rc = yk_dec_scratch(c, tabBytes + (size_t)N * sS); if (rc) return rc; }
+    int slot; void* host;
+    { const int rc = yk_dec_table_host(c, (size_t)N * sizeof(DecPlan), &slot, &host); if (rc) return rc; }
+    DecPlan* tab = static_cast<DecPlan*>(host);
+    for (int f = 0; f < N; f++) {
+        tab[f] = pl;
+        for (int p = 0; p < nPasses; p++) {
+            const size_t i = (size_t)f * nPasses + p;
+            tab[f].bm[p] = devBitmap[i]; tab[f].rgb[p] = devRgb[i]; tab[f].rgbBytes[p] = (uint32_t)rgbBytes[i];
+        }
+    }
+    { const int rc = yk_dec_table_upload(c, slot, c->dScratch, (size_t)N * sizeof(DecPlan)); if (rc) return rc; }
+    DecBatch B;
+    B.plans = reinterpret_cast<const DecPlan*>(c->dScratch);
+    B.loaded = c->dB.loaded; B.owner = reinterpret_cast<uint8_t*>(c->dB.owner); B.mapRGB = c->dB.mapRGB; B.planes = c->dB.planes; B.tile4 = c->dB.tile4;
+    B.scratch = c->dScratch + tabBytes;
+    B.sLoaded = c->dStride.loaded; B.sOwner = c->dStride.owner; B.sMapRGB = c->dStride.mapRGB; B.sPlanes = c->dStride.planes; B.sTile4 = c->dStride.tile4; B.sScratch = sS;
+    B.oSums = oS; B.oWords = oW; B.oPassWords = oP; B.oPerThread = oT; B.oList = oL;
+    const uint32_t factor = remapRange > 0 ? (uint32_t)((255u << 16) / (uint32_t)remapRange) : 0u;
+    const unsigned F = (unsigned)N;
+    YK_HIP(c, hipMemsetAsync(c->dB.owner, 0xFF, c->dStride.owner * (size_t)N, c->stream));
+    { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
+    hipLaunchKernelGGL(yk_decall_owner_batch_kernel, dim3((unsigned)((nBytesTot + 255) / 256), F), dim3(256), 0, c->stream, B, w, h, latW);
+    hipLaunchKernelGGL(yk_decall_stream_batch_kernel<false>, dim3((unsigned)nbTot, F), dim3(1024), 0, c->stream, B, w, h, latW, 0u);
+    hipLaunchKernelGGL(yk_decall_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, B);
+    hipLaunchKernelGGL(yk_decall_stream_batch_kernel<true>, dim3((unsigned)nbTot, F), dim3(1024), 0, c->stream, B, w, h, latW, factor);
+    hipLaunchKernelGGL(yk_decall_render_blocks_batch_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64)), F), dim3(256), 0, c->stream, B, w, h, latW,
+                       c->dPlaneSize, w >> 3, (w + 15) >> 4);
+    YK_HIP(c, hipGetLastError());
+    { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
+    return YK_OK;
+}
+
 static int yk_dec_split(yk_ctx* c) {                                       // UpdateTileAndRGBMask (YAIK_API.cpp:530-544), once
     if (c->dSplit) return YK_OK;
     const size_t lat = (size_t)(c->dw / 4 + 1) * (c->dh / 4 + 1), n = lat > c->dTile4Size ? lat : c->dTile4Size;
@@ -1059,6 +1340,7 @@ static int yk_dec_split(yk_ctx* c) {                                       // Up
 
 int yk_decode_split_masks(yk_ctx* c) {
     if (!c) return YK_ERR_BAD_ARG;
+    YK_DEC_NO_BATCH(c, "yk_decode_split_masks");
     if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_HIP(c, hipSetDevice(c->device));
     return yk_dec_split(c);
@@ -1066,6 +1348,7 @@ int yk_decode_split_masks(yk_ctx* c) {
 
 int yk_decode_gradient_planes(yk_ctx* c, int planeBit, int consistentMarks, const uint8_t* bitmap, size_t bitmapBytes, const uint8_t* rgb, size_t rgbBytes) {
     if (!c || !bitmap) return YK_ERR_BAD_ARG;
+    YK_DEC_NO_BATCH(c, "yk_decode_gradient_planes");
     if (planeBit == 7) return yk_decode_gradient(c, 2, 2, bitmap, bitmapBytes, rgb, rgbBytes);
     if (planeBit < 1 || planeBit > 6) return yk_fail(c, YK_ERR_BAD_ARG, "planeBit must be 1..7");
     if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
@@ -1108,6 +1391,8 @@ static int yk_decode_1d_impl(yk_ctx* c, const uint8_t* typeStream, size_t typeBy
     if (!c || !typeStream || !pixStream || compressionRange <= 0) return YK_ERR_BAD_ARG;
     if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_HIP(c, hipSetDevice(c->device));
+    // dPlanesStale is the handle's: this call writes the unmarked quadrants of the SELECTED frame only, so on a batch the other frames get theirs zeroed first
+    if (c->dFrames > 1) { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
     const int w = c->dw, h = c->dh, tilesW = w >> 3;
     const size_t T8 = (size_t)tilesW * (h >> 3), nb = (T8 + 1023) / 1024;
     const size_t oTy = 0, oPx = (oTy + typeBytes + 31) & ~(size_t)15, oCT = (oPx + pixBytes + 31) & ~(size_t)15, oCP = oCT + 16,
@@ -1161,8 +1446,49 @@ int yk_decode_1d_device(yk_ctx* c, const uint8_t* devType, size_t typeBytes, con
     return yk_decode_1d_impl(c, devType, typeBytes, devPix, pixBytes, compressionRange, true);
 }
 
+// The '1DTL' chunk of every frame of a batch: count, scan (one workgroup per frame) and decode, each ONE launch over the frames.  A frame with
+// empty streams gets what yk_decode_1d_device gives it when its streams end early: zeros in every quadrant nothing marked, nothing read.
+int yk_decode_1d_batch_device(yk_ctx* c, const uint8_t* const* devType, const size_t* typeBytes, const uint8_t* const* devPix, const size_t* pixBytes, int compressionRange) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!devType || !typeBytes || !devPix || !pixBytes) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
+    if (compressionRange <= 0) return yk_refuse(c, YK_ERR_BAD_ARG, "compressionRange must be positive");
+    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    const int N = c->dFrames;
+    for (int f = 0; f < N; f++) {
+        if ((typeBytes[f] && !devType[f]) || (pixBytes[f] && !devPix[f])) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL 1-D stream with a length");
+        if (pixBytes[f] && (reinterpret_cast<uintptr_t>(devPix[f]) & 15)) return yk_refuse(c, YK_ERR_BAD_ARG, "the pixel streams of a batch are read in place: 16-byte aligned");
+    }
+    if (c->dSplit) return yk_decode_1d_impl(c, devType[0], typeBytes[0], devPix[0], pixBytes[0], compressionRange, true);   // a batch of one behind a plane-subset chunk: per-plane masks
+    YK_HIP(c, hipSetDevice(c->device));
+    const int w = c->dw, h = c->dh, tilesW = w >> 3;
+    const size_t T8 = (size_t)tilesW * (h >> 3), nb = (T8 + 1023) / 1024;
+    const size_t tabBytes = ((size_t)N * sizeof(D1Frame) + 255) & ~(size_t)255;
+    const size_t oBT = 0, oBP = oBT + nb * 4 + 16, oTot = oBP + nb * 4 + 16, oOff = oTot + 64, sS = (oOff + T8 * 4 + 64 + 15) & ~(size_t)15;
+    { const int rc = yk_dec_scratch(c, tabBytes + (size_t)N * sS); if (rc) return rc; }
+    int slot; void* host;
+    { const int rc = yk_dec_table_host(c, (size_t)N * sizeof(D1Frame), &slot, &host); if (rc) return rc; }
+    D1Frame* tab = static_cast<D1Frame*>(host);
+    for (int f = 0; f < N; f++) { tab[f].type = devType[f]; tab[f].pix = devPix[f]; tab[f].typeBytes = typeBytes[f]; tab[f].pixBytes = pixBytes[f]; }
+    { const int rc = yk_dec_table_upload(c, slot, c->dScratch, (size_t)N * sizeof(D1Frame)); if (rc) return rc; }
+    D1Batch B;
+    B.frames = reinterpret_cast<const D1Frame*>(c->dScratch);
+    B.tile4 = c->dB.tile4; B.planes = c->dB.planes; B.scratch = c->dScratch + tabBytes;
+    B.sTile4 = c->dStride.tile4; B.sPlanes = c->dStride.planes; B.sScratch = sS;
+    B.oBT = oBT; B.oBP = oBP; B.oTot = oTot; B.oOff = oOff;
+    const unsigned gTiles = (unsigned)((T8 + 64 * YK_D1_TPL - 1) / (64 * YK_D1_TPL)), F = (unsigned)N;
+    { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
+    hipLaunchKernelGGL(yk_dec1d_count_batch_kernel, dim3((unsigned)nb, F), dim3(1024), 0, c->stream, B, (w + 15) >> 4, tilesW, T8);
+    hipLaunchKernelGGL(yk_dec1d_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, B, (int)nb);
+    hipLaunchKernelGGL(yk_dec1d_batch_kernel, dim3(gTiles, 3, F), dim3(256), 0, c->stream, B, T8, (1 << 24) / compressionRange, c->dPlaneSize);
+    YK_HIP(c, hipGetLastError());
+    { int rc2 = yk_stage_end(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
+    c->dPlanesStale = false;                                                 // every unmarked quadrant of every plane of every frame has been written
+    return YK_OK;
+}
+
 int yk_decode_mask(yk_ctx* c, const uint8_t* bits, int bw, int bh, uint8_t* hostOut, size_t cap) {
     if (!c || !bits || !hostOut || bw <= 0 || bh <= 0) return YK_ERR_BAD_ARG;
+    YK_DEC_NO_BATCH(c, "yk_decode_mask");
     const size_t outBytes = (size_t)bw * bh * 32, inBytes = ((size_t)bw * bh + 7) / 8;
     if (cap < outBytes) return yk_fail(c, YK_ERR_RANGE, "mask buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
@@ -1222,11 +1548,14 @@ int yk_decode_output(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, cons
 
 int yk_decode_output_alpha(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride) {
     if (!c) return YK_ERR_BAD_ARG;
+    YK_DEC_NO_BATCH(c, "yk_decode_output_alpha");
     if (!c->dAlphaValid) return yk_fail(c, YK_ERR_STATE, "yk_decode_alpha first");
     return yk_decode_output_impl(c, hostOut, outputImageStride, nullptr, 0, false, c->dAlpha);
 }
 
 int yk_decode_output_reference_rgba(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA) {
+    if (!c) return YK_ERR_BAD_ARG;
+    YK_DEC_NO_BATCH(c, "yk_decode_output_reference_rgba");
     return yk_decode_output_impl(c, hostOut, outputImageStride, hostAlpha, strideA, true);
 }
 
@@ -1244,6 +1573,22 @@ int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t 
     YK_HIP(c, hipSetDevice(c->device));
     { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
     return yk_dec_detile(c, devOut, rowBytes, planeBytes, channels, fromPlane ? c->dAlpha : nullptr, w, fromPlane ? 0 : alpha);
+}
+
+int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "devOut is NULL");
+    if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
+    if (channels == 4 && (alpha < 0 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "alpha must be 0..255 (a batch has no decoded alpha plane)");
+    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    const size_t w = (size_t)c->dw, h = (size_t)c->dh;
+    if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "row or plane pitch too small for the image");
+    if (c->dFrames > 1 && (planeBytes == 0 ? frameBytes / h < rowBytes : frameBytes / (size_t)channels < planeBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "frame stride too small for a frame");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    return yk_dec_detile(c, devOut, rowBytes, planeBytes, channels, nullptr, w, alpha, c->dFrames, frameBytes);
 }
 
 const uint8_t* yk_decode_planes_device(yk_ctx* c, size_t* planeSize) {

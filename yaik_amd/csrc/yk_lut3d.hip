@@ -1046,6 +1046,7 @@ int yk_decode_assign_lut(yk_ctx* c, const uint8_t* lutFile, size_t lutBytes) {
 int yk_decode_lut3d(yk_ctx* c, const uint8_t* const maps[6], const size_t mapBytes[6], const uint16_t* tiles, size_t nTiles, const uint8_t* colors,
                     const uint8_t* const idx[4], const size_t idxBytes[4], size_t consumed[6]) {
     if (!c || !maps || !mapBytes || !idx || !idxBytes) return YK_ERR_BAD_ARG;
+    YK_DEC_NO_BATCH(c, "yk_decode_lut3d");
     if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     if (!c->lutDec) return yk_fail(c, YK_ERR_STATE, "yk_decode_assign_lut first");
     if (c->dSplit) return yk_fail(c, YK_ERR_STATE, "a '3DTL' chunk comes before the masks are split ('1DTL', plane-subset chunks)");

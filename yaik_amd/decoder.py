@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import YaikError, lib
-from .encoder import _chk, u8_pixel_layout, u8_planar_layout
+from .encoder import PASSES, _chk, u8_pixel_layout, u8_planar_batch_layout, u8_planar_layout
 
 
 class HipTileDecoder:
@@ -23,7 +23,10 @@ class HipTileDecoder:
         self._h = h
         self.device = device
         self.w = self.h = 0
+        self.frames = 1
         self._has_alpha = False
+        self._batch_stage = None         # torch buffers a queued batch decode may still read: the staging tensor of host streams ...
+        self._batch_streams = None       # ... and the copy of an encoder's per-handle streams (encoder_batch_streams)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -34,9 +37,160 @@ class HipTileDecoder:
         self.close()
 
     def begin(self, w: int, h: int):
-        self.w, self.h = w, h
+        self.w, self.h, self.frames = w, h, 1
         self._has_alpha = False
         _chk(self._h, lib().yk_decode_begin(self._h, w, h))
+
+    # ---- batches: n images of one shape, every kernel launched once over all of them (yk_decode_begin_batch) --------------------------------
+    def begin_batch(self, w: int, h: int, n: int):
+        """n (1..1024) images of w x h on this handle.  The single-image methods (decompress_gradient, decode_streams, decompress_1d, planes,
+        tile4x4, image, image_device) then act on the frame select_frame chose (0 after begin_batch); begin() goes back to one image."""
+        _chk(self._h, lib().yk_decode_begin_batch(self._h, w, h, n))
+        self.w, self.h, self.frames = w, h, n
+        self._has_alpha = False
+
+    def select_frame(self, f: int):
+        _chk(self._h, lib().yk_decode_select_frame(self._h, f))
+
+    def decode_batch_streams(self, frames: list, sync: bool = True, remap_range: int = 250) -> None:
+        """The gradient chunks + the 1-D chunk of every frame of the batch, one launch per kernel over all frames.  frames[f] is the call list
+        of encoder_streams for frame f: ("g", sx, sy, bitmap, nbytes, rgb, nbytes) entries, the same passes in the same order in every frame (a
+        pass without tiles in a frame: its all-zero bitmap and an empty stream), and at most one ("1", type, nbytes, pix, nbytes).  bitmap / rgb /
+        type / pix are device pointers (int, c_void_p) or numpy uint8 arrays; all host arrays are packed, each 16-byte aligned, into one torch
+        staging tensor that goes to the device in a single copy.  remap_range: PaletteFullRangeRemapping of the corner streams on the way in
+        (250 for an encoder's streams, 0 for streams that are remapped already)."""
+        import torch
+        L = lib()
+        if len(frames) != self.frames:
+            raise ValueError(f"{len(frames)} call lists for a batch of {self.frames} frames")
+        g = [[c for c in fr if c[0] == "g"] for fr in frames]
+        d1 = [[c for c in fr if c[0] == "1"] for fr in frames]
+        shapes = [(c[1], c[2]) for c in g[0]]
+        if any([(c[1], c[2]) for c in gf] != shapes for gf in g) or any(len(x) > 1 for x in d1):
+            raise ValueError("every frame needs the same gradient passes in the same order, and at most one 1-D entry")
+        chunks, size = [], 0
+
+        def place(v, nbytes):
+            nonlocal size
+            if isinstance(v, np.ndarray):
+                a = np.ascontiguousarray(v, dtype=np.uint8).ravel()
+                if a.size < nbytes:
+                    raise ValueError(f"a stream of {a.size} bytes was given a length of {nbytes}")
+                chunks.append((size, a[:nbytes]))
+                size = (size + nbytes + 15) & ~15
+                return ("h", chunks[-1][0])
+            v = v.value if isinstance(v, C.c_void_p) else v
+            return ("d", int(v) if v else 0)
+
+        bm = [[place(c[3], c[4]) for c in gf] for gf in g]
+        rgb = [[place(c[5], c[6]) for c in gf] for gf in g]
+        typ = [place(x[0][1], x[0][2]) if x else ("d", 0) for x in d1]
+        pix = [place(x[0][3], x[0][4]) if x else ("d", 0) for x in d1]
+        base = 0
+        if chunks:
+            buf = np.zeros(size + 16, dtype=np.uint8)
+            for off, a in chunks:
+                buf[off:off + a.size] = a
+            dev = torch.device("cuda", self.device)
+            if self._batch_stage is not None:
+                _chk(self._h, L.yk_synchronize(self._h))                   # a decode queued with sync=False may still read the previous staging tensor
+            stage = torch.from_numpy(buf).to(dev)
+            base = stage.data_ptr()
+            _chk(self._h, L.yk_stream_wait_for(self._h, torch.cuda.current_stream(dev).cuda_stream))
+            self._batch_stage = stage
+        addr = lambda e: (base + e[1] if e[0] == "h" else e[1]) or None
+        n, P = self.frames, len(shapes)
+        if P:
+            sx, sy = (C.c_int * P)(*[s[0] for s in shapes]), (C.c_int * P)(*[s[1] for s in shapes])
+            nb = (C.c_size_t * P)(*[min(gf[p][4] for gf in g) for p in range(P)])
+            t_bm = (C.c_void_p * (n * P))(*[addr(bm[f][p]) for f in range(n) for p in range(P)])
+            t_rgb = (C.c_void_p * (n * P))(*[addr(rgb[f][p]) if g[f][p][6] else None for f in range(n) for p in range(P)])
+            t_nr = (C.c_size_t * (n * P))(*[g[f][p][6] for f in range(n) for p in range(P)])
+            _chk(self._h, L.yk_decode_gradient_all_batch_device(self._h, P, sx, sy, t_bm, nb, t_rgb, t_nr, remap_range))
+        if any(d1):
+            nt = [x[0][2] if x else 0 for x in d1]
+            npx = [x[0][4] if x else 0 for x in d1]
+            t_ty = (C.c_void_p * n)(*[addr(typ[f]) if nt[f] else None for f in range(n)])
+            t_px = (C.c_void_p * n)(*[addr(pix[f]) if npx[f] else None for f in range(n)])
+            _chk(self._h, L.yk_decode_1d_batch_device(self._h, t_ty, (C.c_size_t * n)(*nt), t_px, (C.c_size_t * n)(*npx), 15))
+        if sync:
+            _chk(self._h, L.yk_synchronize(self._h))
+
+    def encoder_batch_streams(self, enc) -> list:
+        """The call lists of decode_batch_streams for an encoder that ran encode_batch (same device).  Frame after frame: select_frame, the
+        corner stage, yk_range1d_encode.  The tile bitmaps are per frame in the encoder and are referenced where they lie; the corner and 1-D
+        streams are ONE buffer per encoder handle, overwritten by the next frame's stages, so every frame's are copied device-to-device (on the
+        encoder's stream) into one torch buffer this decoder keeps alive until its next encoder_batch_streams.  Every pass is listed for every
+        frame (a pass without tiles: all-zero bitmap, empty stream).  Fences the encoder once at the end; the lengths cost a read-back per
+        frame.  The bitmap pointers go stale with the encoder's next encode, like those of encoder_streams."""
+        import torch
+        n = enc.frames
+        _chk(self._h, lib().yk_synchronize(self._h))                           # a queued decode may still read the buffer this call replaces
+        if (enc.w, enc.h, n) != (self.w, self.h, self.frames):
+            raise ValueError(f"the encoder holds {n} frames of {enc.w} x {enc.h}, the decoder batch {self.frames} of {self.w} x {self.h}")
+        EL = enc._L
+        up = lambda v: (v + 15) & ~15
+        lat3 = (self.w // 4 + 1) * (self.h // 4 + 1) * 3
+        n_px, n_ty = 3 * self.w * self.h, 3 * (self.w // 8) * (self.h // 8) * 3          # the most the 1-D streams of a frame can hold
+        per_frame = up(lat3) + 7 * 16 + up(n_px) + up(n_ty)
+        dev = torch.device("cuda", self.device)
+        keep = torch.empty(n * per_frame + 16, dtype=torch.uint8, device=dev)
+        _chk(enc._h, EL.yk_stream_wait_for(enc._h, torch.cuda.current_stream(dev).cuda_stream))   # torch may still use the memory it just handed out
+        frames = []
+        for f in range(n):
+            enc.select_frame(f)
+            at, end, calls = keep.data_ptr() + f * per_frame, keep.data_ptr() + (f + 1) * per_frame, []
+            for i, (sx, sy) in enumerate(PASSES):
+                src, nb = C.c_void_p(), C.c_size_t()
+                _chk(enc._h, EL.yk_gradient_corners_device(enc._h, i, C.byref(src), C.byref(nb)))
+                if at + nb.value > end:
+                    raise YaikError("the encoder's corner streams are longer than a frame can produce")
+                _chk(enc._h, EL.yk_device_copy(enc._h, at, src, nb.value))
+                calls.append(("g", sx, sy, EL.yk_gradient_bitmap_device(enc._h, i), EL.yk_gradient_bitmap_bytes(enc._h, i), at, nb.value))
+                at += up(nb.value)
+            _chk(enc._h, EL.yk_range1d_encode(enc._h))
+            pix, npx, typ, nty = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+            _chk(enc._h, EL.yk_range1d_streams_device(enc._h, C.byref(pix), C.byref(npx), C.byref(typ), C.byref(nty)))
+            if at + up(npx.value) + nty.value > end:
+                raise YaikError("the encoder's 1-D streams are longer than a frame can produce")
+            _chk(enc._h, EL.yk_device_copy(enc._h, at, pix, npx.value))
+            _chk(enc._h, EL.yk_device_copy(enc._h, at + up(npx.value), typ, nty.value))
+            calls.append(("1", at + up(npx.value), nty.value, at, npx.value))
+            frames.append(calls)
+        enc.synchronize()
+        self._batch_streams = keep
+        return frames
+
+    def decode_batch_from_encoder(self, enc, sync: bool = True) -> None:
+        self.decode_batch_streams(self.encoder_batch_streams(enc), sync)
+
+    def image_batch_device(self, out=None, channels: int = 3, alpha: int = 255, planar: bool = False):
+        """Every frame of the batch as 8-bit pixels in one torch.uint8 tensor on the handle's device (yk_decode_output_batch_device, one launch):
+        [N, h, w, C], or [N, C, h, w] with planar=True; C = 3, or 4 with the constant alpha 0..255.  `out` may be any view with unit inner
+        stride and any row, plane and frame pitch (u8_pixel_layout(batch=True) / u8_planar_batch_layout): only its pixel bytes are written.
+        Ordering against torch's current stream is that of image_device: no host fence."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        N = self.frames
+        if out is None:
+            out = torch.empty((N, channels, self.h, self.w) if planar else (N, self.h, self.w, channels), dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        if planar:
+            lay = u8_planar_batch_layout(out)
+            shape, plane_bytes = (lay.frames, lay.channels, lay.rows, lay.w), lay.plane_bytes
+        else:
+            lay = u8_pixel_layout(out, batch=True)
+            shape, plane_bytes = (lay.frames, lay.rows, lay.w, lay.channels), 0
+        want = (N, channels, self.h, self.w) if planar else (N, self.h, self.w, channels)
+        if shape != want:
+            raise ValueError(f"out has shape {shape}, the batch needs {want}")
+        L = lib()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_output_batch_device(self._h, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels, int(alpha)))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
 
     def decompress_gradient(self, sx: int, sy: int, bitmap: np.ndarray, rgb_dq: np.ndarray):
         bitmap = np.ascontiguousarray(bitmap, dtype=np.uint8)

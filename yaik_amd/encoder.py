@@ -108,6 +108,41 @@ def u8_planar_layout(pixels) -> PlanarLayout:
     return PlanarLayout(ch, rows, w, row_bytes, plane_bytes)
 
 
+class PlanarBatchLayout(NamedTuple):
+    """How yk_decode_output_batch_device writes a planar batch [F, C, rows, w] uint8 array: u8_planar_batch_layout."""
+    frames: int
+    channels: int
+    rows: int
+    w: int
+    row_bytes: int          # row pitch inside a plane
+    plane_bytes: int        # plane stride inside a frame
+    frame_bytes: int        # frame stride (channels * plane_bytes for a single frame, where the library ignores it)
+
+
+def u8_planar_batch_layout(pixels) -> PlanarBatchLayout:
+    """Layout of numpy or torch uint8 pixels [F, C, rows, w], C = 3 or 4 (the [N, C, H, W] of torch image batches): every frame as in
+    u8_planar_layout, frames at the array's own stride.  Padded or sliced views need no copy; the bytes of a row must be contiguous, and rows,
+    planes and frames may not overlap.  Reads only dtype, shape and strides."""
+    if hasattr(pixels, "data_ptr"):
+        import torch
+        if pixels.dtype != torch.uint8:
+            raise TypeError(f"8-bit pixels expected, got {pixels.dtype}")
+        shape, strides = tuple(pixels.shape), tuple(pixels.stride())
+    else:
+        if pixels.dtype != np.uint8:
+            raise TypeError(f"8-bit pixels expected, got {pixels.dtype}")
+        shape, strides = pixels.shape, pixels.strides
+    if len(shape) != 4:
+        raise ValueError(f"pixels must be [F, C, rows, w], got shape {tuple(shape)}")
+    if shape[0] < 1:
+        raise ValueError("a batch holds at least one frame")
+    lay = u8_planar_layout(pixels[0])
+    frames, frame_bytes = shape[0], (strides[0] if shape[0] > 1 else lay.channels * lay.plane_bytes)
+    if frame_bytes < lay.channels * lay.plane_bytes:
+        raise ValueError(f"frame stride {frame_bytes} is shorter than a frame of {lay.channels * lay.plane_bytes} bytes")
+    return PlanarBatchLayout(frames, lay.channels, lay.rows, lay.w, lay.row_bytes, lay.plane_bytes, frame_bytes)
+
+
 class HipTileEncoder:
     """One handle = one GPU = one image or one row stripe of an image."""
 
@@ -125,6 +160,7 @@ class HipTileEncoder:
         _HANDLE_LIB[h.value] = L
         self._keepalive = None
         self.w = self.h = self.n = 0
+        self.frames = 1                 # images bound: 1, or the F of set_batch / set_batch_u8
 
     def close(self):
         if getattr(self, "_h", None):
@@ -143,7 +179,7 @@ class HipTileEncoder:
         is_torch = hasattr(planes, "data_ptr")
         n, rows, w = planes.shape
         h = rows - halo_rows
-        self.n, self.h, self.w = n, h, w
+        self.n, self.h, self.w, self.frames = n, h, w, 1
         self.full_h = full_h if full_h is not None else h
         self.y0 = y0
         _chk(self._h, L.yk_set_image(self._h, w, self.full_h, n, y0, h, halo_rows))
@@ -176,7 +212,7 @@ class HipTileEncoder:
             pixels = np.asarray(pixels)
         lay = u8_pixel_layout(pixels, n_planes)
         h = lay.rows - halo_rows
-        self.n, self.h, self.w = lay.n_planes, h, lay.w
+        self.n, self.h, self.w, self.frames = lay.n_planes, h, lay.w, 1
         self.full_h = full_h if full_h is not None else h
         self.y0 = y0
         _chk(self._h, L.yk_set_image(self._h, lay.w, self.full_h, lay.n_planes, y0, h, halo_rows))
@@ -255,7 +291,7 @@ class HipTileEncoder:
         L = self._L
         assert frames.dtype == torch.int32 and frames.is_cuda and frames.is_contiguous() and frames.dim() == 4
         F, n, h, w = frames.shape
-        self.n, self.h, self.w, self.full_h, self.y0 = n, h, w, h, 0
+        self.n, self.h, self.w, self.full_h, self.y0, self.frames = n, h, w, h, 0, F
         _chk(self._h, L.yk_set_image(self._h, w, h, n, 0, h, 0))
         _chk(self._h, L.yk_set_batch(self._h, F))
         torch.cuda.current_stream(frames.device).synchronize()          # hand-over fence, see set_image
@@ -271,7 +307,7 @@ class HipTileEncoder:
         L = self._L
         lay = u8_pixel_layout(frames, n_planes, batch=True)
         assert frames.is_cuda
-        self.n, self.h, self.w, self.full_h, self.y0 = lay.n_planes, lay.rows, lay.w, lay.rows, 0
+        self.n, self.h, self.w, self.full_h, self.y0, self.frames = lay.n_planes, lay.rows, lay.w, lay.rows, 0, lay.frames
         _chk(self._h, L.yk_set_image(self._h, lay.w, lay.rows, lay.n_planes, 0, lay.rows, 0))
         _chk(self._h, L.yk_set_batch(self._h, lay.frames))
         torch.cuda.current_stream(frames.device).synchronize()          # hand-over fence, see set_image
