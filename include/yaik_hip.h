@@ -127,6 +127,22 @@ int yk_alpha_bitmap(yk_ctx* c, uint8_t* hostOut, size_t cap, size_t* nBytes);
  * hostPayload may be NULL (size query); *n = rawSize.  Convert passes force8Bit = 1 (:9027-9028).  Synchronises. */
 typedef struct yk_alpha_info { int32_t mode; int32_t bbox[4]; uint32_t rawSize; } yk_alpha_info;
 int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostPayload, size_t cap, size_t* n);
+/* yk_alpha_values(force8Bit = 1) for every frame of the handle (nFrames 1..1024), after the alpha stage of all frames: yk_encode_batch, or for a
+ * batch of one yk_alpha_reject + yk_alpha_finish.  infos[f] is exactly what yk_alpha_values returns for frame f bound alone (mode -1 / 1 / 6, box,
+ * rawSize) and the payload is byte-identical.  Whatever nFrames is, a call costs at most three kernel launches, two blocking read-backs and one
+ * table upload: the box reduction over all frames (frame = a grid dimension) and the read-back of every box; the host lays the payload slots out
+ * back to back in one buffer (slot = w * h bytes of the box rounded to 4, each offset rounded up to 16) and uploads one record per frame that has a
+ * box; the class flags + 8-bit payload kernel over those frames (grid sized from the largest box) and the read-back of the flags; the 1-bit pack
+ * over the frames classed binary, into the same slots (not launched when no frame is binary).  Frames without an alpha plane: mode -1 for all.
+ * The payloads stay in HBM: yk_alpha_payload_device hands out frame's slot (*dev = NULL, *nBytes = 0 for a frame without a chunk) without a host
+ * synchronisation -- read it on this handle's stream or behind yk_stream_handoff; valid until the next encode, yk_set_image or
+ * yk_alpha_values[_batch] of the handle.  yk_alpha_payload copies it to the host (*nBytes = rawSize, also when hostOut is too small) and synchronises.
+ * Refusals launch nothing and leave the handle usable: YK_ERR_BAD_ARG for NULL infos, and for force8Bit = 0 (the 6-bit mask mode is not batched: it
+ * needs every frame's mask selection); YK_ERR_STATE before the alpha stage has finished, or on a stripe.  The getters: YK_ERR_BAD_ARG for a frame
+ * out of range, YK_ERR_STATE before yk_alpha_values_batch, YK_ERR_RANGE for a short buffer. */
+int yk_alpha_values_batch(yk_ctx* c, int force8Bit, yk_alpha_info* infos /* nFrames */);
+int yk_alpha_payload_device(yk_ctx* c, int frame, const uint8_t** dev, size_t* nBytes);
+int yk_alpha_payload(yk_ctx* c, int frame, uint8_t* hostOut, size_t cap, size_t* nBytes);
 
 /* ---- a6 + a10..a13  fused tile encode ----------------------------------------------------------
  * One launch does what 7x EncoderContext::FittingQuadSmooth(rejectFactor, R,G,B, .., sx, sy)
@@ -424,7 +440,8 @@ int yk_decode_tile4x4_planes(yk_ctx* c, uint8_t* hostOut, size_t cap);
  * yk_decode_select_frame (default 0) points the single-image entry points at one frame of the batch: yk_decode_gradient[_device],
  * yk_decode_gradient_all_device, yk_decode_1d[_device], yk_decode_planes[_device], yk_decode_tile4x4[_planes], yk_decode_output and
  * yk_decode_output_device then read and write that frame only, so a caller can mix both forms and cross-check them.  (yk_decode_planes and the
- * output calls first zero what no chunk has written yet, in every frame.)  'ALPM', 'MIPM', '3DTL' and plane-subset chunks are not batched: with
+ * output calls first zero what no chunk has written yet, in every frame.)  'MIPM', '3DTL', plane-subset chunks and the single-image 'ALPM' call are
+ * not batched ('ALPM' has a batch call of its own below): with
  * nFrames > 1, yk_decode_alpha, yk_decode_output_alpha, yk_decode_output_reference_rgba, yk_decode_gradient_planes, yk_decode_split_masks,
  * yk_decode_lut3d and yk_decode_mask return YK_ERR_STATE and touch nothing.
  *
@@ -454,6 +471,22 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
 int yk_decode_1d_batch_device(yk_ctx* c, const uint8_t* const* devType, const size_t* typeBytes, const uint8_t* const* devPix,
                               const size_t* pixBytes, int compressionRange);
 int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha);
+/* 'ALPM' in a batch.  yk_decode_alpha_batch_device writes the w x h alpha plane of EVERY frame of the batch begun by yk_decode_begin_batch in one
+ * launch, frame f's at a stride of w * h rounded up to 16: modes[f] = 1, 4, 5 or 6 as in yk_decode_alpha (refQuirk = 0), bboxes[4 * f ..] = {x, y, w,
+ * h}, devPayload[f] / payBytes[f] = the DECOMPRESSED payload in device memory, read in place; modes[f] = -1 (no chunk: all 255, empty box, no alpha
+ * plane) gives a plane of the constant noChunkAlpha (0..255; 255 = opaque) and ignores the frame's other entries.  The records travel through the
+ * pinned ring and an HBM table like those of the other batch calls: no host synchronisation, ORDERING is the caller's.  Everything is validated on
+ * the host before the first launch; a refusal writes nothing and leaves earlier valid planes valid: YK_ERR_BAD_ARG for a NULL table, a box outside
+ * the image or empty, a width not a multiple of 8 (mode 1) or 4 (modes 4, 5), modes 0 and 7, modes 2 and 3 (the mask modes are not batched), a NULL
+ * payload with a length, noChunkAlpha outside 0..255; YK_ERR_RANGE for a payload shorter than its box needs; YK_ERR_STATE before any begin.
+ * Afterwards yk_decode_alpha_plane returns the SELECTED frame's plane and yk_decode_output_device(alpha = -1) de-tiles the selected frame with it;
+ * yk_decode_begin[_batch] invalidates the planes.
+ * yk_decode_output_batch_alpha_device: yk_decode_output_batch_device with four channels and every frame's alpha taken from those planes (HWC when
+ * planeBytes == 0, CHW otherwise; the same layout rules and refusals), YK_ERR_STATE when the batch has no valid alpha planes.  Timed as
+ * YK_STAGE_DEC_DETILE. */
+int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes /* nFrames */, const int32_t* bboxes /* nFrames x {x,y,w,h} */,
+                                 const uint8_t* const* devPayload, const size_t* payBytes, int noChunkAlpha);
+int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes);
 
 /* ---- timing hooks for bench.py: HIP events on the handle's stream around every alpha stage / fused kernel / compaction.
  * Returns the averages over the yk_encode_tiles calls since the previous query (a ring of 64 event sets, older ones are

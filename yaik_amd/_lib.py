@@ -53,6 +53,9 @@ SIGNATURES = {
     "yk_alpha_result": (C.c_int, [vp, vp, ip, ip, vp]),
     "yk_alpha_bitmap": (C.c_int, [vp, vp, sz, szp]),
     "yk_alpha_values": (C.c_int, [vp, C.c_int, vp, vp, sz, szp]),
+    "yk_alpha_values_batch": (C.c_int, [vp, C.c_int, vp]),
+    "yk_alpha_payload_device": (C.c_int, [vp, C.c_int, C.POINTER(vp), szp]),
+    "yk_alpha_payload": (C.c_int, [vp, C.c_int, vp, sz, szp]),
     "yk_encode_tiles": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
     "yk_encode_frame": (C.c_int, [vp, C.c_int, C.c_int]),
     "yk_set_batch": (C.c_int, [vp, C.c_int]),
@@ -133,6 +136,8 @@ SIGNATURES = {
     "yk_decode_gradient_all_batch_device": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int]),
     "yk_decode_1d_batch_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_int]),
     "yk_decode_output_batch_device": (C.c_int, [vp, vp, sz, sz, sz, C.c_int, C.c_int]),
+    "yk_decode_alpha_batch_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_int]),
+    "yk_decode_output_batch_alpha_device": (C.c_int, [vp, vp, sz, sz, sz]),
     "yk_decode_gradient_planes": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, sz]),
     "yk_decode_split_masks": (C.c_int, [vp]),
     "yk_decode_assign_lut": (C.c_int, [vp, vp, sz]),

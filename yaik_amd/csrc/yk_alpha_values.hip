@@ -61,9 +61,9 @@ __device__ __forceinline__ uint8_t yk_av_pixel(size_t i, int x, int y, const uin
 // one thread = 16 consecutive pixels of the flat plane and one 16-byte store (the plane is w * h bytes, a multiple of 64).  W a multiple of 16:
 // the 16 pixels lie in one row.  RAGGED (W = 8 mod 16): each half of 8 pixels lies in one row, the second half may start the next row
 template <bool RAGGED>
-__global__ __launch_bounds__(256) void yk_av_decode_kernel(const uint8_t* __restrict__ pay, size_t n, int mode, int refQuirk, int bx, int by, int bw, int bh,
-                                                           int W, int H, uint8_t* __restrict__ out) {
-    const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
+__device__ __forceinline__ void yk_av_decode_body(const uint8_t* __restrict__ pay, size_t n, int mode, int refQuirk, int bx, int by, int bw, int bh, int W, int H,
+                                                  uint8_t* __restrict__ out, uint32_t blk) {
+    const size_t i0 = ((size_t)blk * 256 + threadIdx.x) * 16;
     if (i0 >= (size_t)W * H) return;
     uint32_t word[4];
 #pragma unroll
@@ -81,6 +81,26 @@ __global__ __launch_bounds__(256) void yk_av_decode_kernel(const uint8_t* __rest
         }
     }
     *reinterpret_cast<uint4*>(out + i0) = make_uint4(word[0], word[1], word[2], word[3]);
+}
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void yk_av_decode_kernel(const uint8_t* __restrict__ pay, size_t n, int mode, int refQuirk, int bx, int by, int bw, int bh,
+                                                           int W, int H, uint8_t* __restrict__ out) {
+    yk_av_decode_body<RAGGED>(pay, n, mode, refQuirk, bx, by, bw, bh, W, H, out, blockIdx.x);
+}
+// a batch (yk_decode_alpha_batch_device): frame blockIdx.y's record is read through uniform loads, its plane is at out + f * planeStride.  A
+// frame without a chunk (mode -1) gets the constant `fill` (the byte in all four lanes of a dword), still one 16-byte store per thread
+struct YkAvDecFrame { const uint8_t* pay; unsigned long long n; int32_t mode, bx, by, bw, bh, pad[3]; };
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void yk_av_decode_batch_kernel(const YkAvDecFrame* __restrict__ tab, int W, int H, uint8_t* __restrict__ out, size_t planeStride,
+                                                                 uint32_t fill) {
+    const YkAvDecFrame r = tab[blockIdx.y];
+    out += (size_t)blockIdx.y * planeStride;
+    if (r.mode < 0) {
+        const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
+        if (i0 < (size_t)W * H) *reinterpret_cast<uint4*>(out + i0) = make_uint4(fill, fill, fill, fill);
+        return;
+    }
+    yk_av_decode_body<RAGGED>(r.pay, (size_t)r.n, r.mode, 0, r.bx, r.by, r.bw, r.bh, W, H, out, blockIdx.x);
 }
 
 // mask modes 2 / 3: the bit of box pixel (c, r) in the decoder's mipMapMask (read linearly with stride maskBBox.w from the alpha box's
@@ -147,11 +167,11 @@ __device__ __forceinline__ int4 yk_ave_load4(const int32_t* __restrict__ p) {
     return make_int4(p[0], p[1], p[2], p[3]);
 }
 template <bool VEC>
-__global__ __launch_bounds__(256) void yk_ave_box_kernel(const int32_t* __restrict__ alpha, int stride, const int32_t* __restrict__ bounds, int W, int H,
-                                                         int32_t* __restrict__ st) {
+__device__ __forceinline__ void yk_ave_box_body(const int32_t* __restrict__ alpha, int stride, const int32_t* __restrict__ bounds, int W, int H,
+                                                int32_t* __restrict__ st, int blkX, int blkY) {
     // the region starts on a multiple of 16 (kept 16x16 tiles); the loads start on the multiple of 4 at or below it whatever it is
     const int xs = max(bounds[0], 0), x0 = xs & ~3, y0 = max(bounds[1], 0), x1 = min(bounds[2], W), y1 = min(bounds[3], H);
-    const int x = x0 + ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4, yb = y0 + (int)blockIdx.y * YK_AV_ROWS;
+    const int x = x0 + (blkX * 256 + (int)threadIdx.x) * 4, yb = y0 + blkY * YK_AV_ROWS;
     int mnx = INT_MAX, mny = INT_MAX, mxx = -1, mxy = -1;
     if (x < x1)
         for (int y = yb; y < min(yb + YK_AV_ROWS, y1); y++) {
@@ -175,12 +195,24 @@ __global__ __launch_bounds__(256) void yk_ave_box_kernel(const int32_t* __restri
         if (mxy > v[3]) atomicMax(&st[3], mxy);
     }
 }
+template <bool VEC>
+__global__ __launch_bounds__(256) void yk_ave_box_kernel(const int32_t* __restrict__ alpha, int stride, const int32_t* __restrict__ bounds, int W, int H,
+                                                         int32_t* __restrict__ st) {
+    yk_ave_box_body<VEC>(alpha, stride, bounds, W, H, st, (int)blockIdx.x, (int)blockIdx.y);
+}
+// every frame of a batch: frame = blockIdx.z, its plane frameElems further, its bounds 16 ints, its state 8 ints
+template <bool VEC>
+__global__ __launch_bounds__(256) void yk_ave_box_batch_kernel(const int32_t* __restrict__ alpha, unsigned long long frameElems, int stride,
+                                                               const int32_t* __restrict__ bounds, int W, int H, int32_t* __restrict__ st) {
+    const size_t f = blockIdx.z;
+    yk_ave_box_body<VEC>(alpha + f * frameElems, stride, bounds + f * 16, W, H, st + f * 8, (int)blockIdx.x, (int)blockIdx.y);
+}
 // the three class flags over the box rounded to 4 in x (isAnalogAlpha, isAll1; isAll0 is false once the box is not empty) and, in the same
 // read, the 8-bit payload (every sample of the box, row-major): one thread = 4 pixels = one 4-byte store
 template <bool VEC>
-__global__ __launch_bounds__(256) void yk_ave_class_kernel(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh,
-                                                           uint8_t* __restrict__ pay, int32_t* __restrict__ st) {
-    const int c = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4, r = blockIdx.y;
+__device__ __forceinline__ void yk_ave_class_body(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh, uint8_t* __restrict__ pay,
+                                                  int32_t* __restrict__ st, int blkX, int r) {
+    const int c = (blkX * 256 + (int)threadIdx.x) * 4;
     bool analog = false, not255 = false;
     if (c < bw) {
         const int4 q = yk_ave_load4<VEC>(alpha + (size_t)(bT + r) * stride + bL + c);   // bL and c are multiples of 4
@@ -201,10 +233,15 @@ __global__ __launch_bounds__(256) void yk_ave_class_kernel(const int32_t* __rest
         if (n && !v[5]) atomicOr(&st[5], 1);
     }
 }
+template <bool VEC>
+__global__ __launch_bounds__(256) void yk_ave_class_kernel(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh,
+                                                           uint8_t* __restrict__ pay, int32_t* __restrict__ st) {
+    yk_ave_class_body<VEC>(alpha, stride, bL, bT, bw, bh, pay, st, (int)blockIdx.x, (int)blockIdx.y);
+}
 // make1BitStream (:317-355) on the box re-aligned to 8: bit (v & 1) of every sample, LSB first; one thread = one output byte
-__global__ __launch_bounds__(256) void yk_ave_pack1_kernel(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh,
-                                                           uint8_t* __restrict__ pay) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, perRow = (size_t)(bw >> 3);
+__device__ __forceinline__ void yk_ave_pack1_body(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh, uint8_t* __restrict__ pay,
+                                                  uint32_t blk) {
+    const size_t i = (size_t)blk * 256 + threadIdx.x, perRow = (size_t)(bw >> 3);
     if (i >= perRow * bh) return;
     const int r = (int)(i / perRow), c = (int)(i % perRow) * 8;
     const int32_t* p = alpha + (size_t)(bT + r) * stride + bL + c;
@@ -212,6 +249,31 @@ __global__ __launch_bounds__(256) void yk_ave_pack1_kernel(const int32_t* __rest
 #pragma unroll
     for (int k = 0; k < 8; k++) b |= (uint32_t)(p[k] & 1) << k;
     pay[i] = (uint8_t)b;
+}
+__global__ __launch_bounds__(256) void yk_ave_pack1_kernel(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh,
+                                                           uint8_t* __restrict__ pay) {
+    yk_ave_pack1_body(alpha, stride, bL, bT, bw, bh, pay, blockIdx.x);
+}
+// yk_alpha_values_batch: one record per frame that has a box (the box rounded to 4 in x, the frame, the offset of its payload slot); record
+// blockIdx.z is read through uniform loads.  The grids are sized from the largest box: workgroups outside this frame's box leave at once.
+struct YkAvFrame { int32_t bL, bT, bw, bh; unsigned long long off; int32_t frame, pad; };
+template <bool VEC>
+__global__ __launch_bounds__(256) void yk_ave_class_batch_kernel(const int32_t* __restrict__ alpha, unsigned long long frameElems, int stride,
+                                                                 const YkAvFrame* __restrict__ tab, uint8_t* __restrict__ pay, int32_t* __restrict__ st) {
+    const YkAvFrame r = tab[blockIdx.z];
+    if ((int)blockIdx.y >= r.bh || (int)blockIdx.x * 1024 >= r.bw) return;
+    yk_ave_class_body<VEC>(alpha + (size_t)r.frame * frameElems, stride, r.bL, r.bT, r.bw, r.bh, pay + r.off, st + (size_t)r.frame * 8, (int)blockIdx.x,
+                           (int)blockIdx.y);
+}
+// the frames the class kernel found binary (flags: not analog, not all 255): the box is re-aligned to 8 here as the host does it, the 1-bit
+// payload replaces the 8-bit one in the frame's slot (it is never longer)
+__global__ __launch_bounds__(256) void yk_ave_pack1_batch_kernel(const int32_t* __restrict__ alpha, unsigned long long frameElems, int stride,
+                                                                 const YkAvFrame* __restrict__ tab, uint8_t* __restrict__ pay, const int32_t* __restrict__ st) {
+    const YkAvFrame r = tab[blockIdx.z];
+    const int32_t* s = st + (size_t)r.frame * 8;
+    if (s[4] != 0 || s[5] == 0) return;
+    const int bL = (r.bL >> 3) << 3, bR = ((r.bL + r.bw + 7) >> 3) << 3;
+    yk_ave_pack1_body(alpha + (size_t)r.frame * frameElems, stride, bL, r.bT, bR - bL, r.bh, pay + r.off, blockIdx.x);
 }
 
 // ---- force8Bit = false: IS_6_BIT_USEMIPMAPMASK_INVERSE (:1503-1565) -----------------------------------------------------------------------
@@ -297,7 +359,7 @@ int yk_decode_alpha(yk_ctx* c, int mode, const int32_t bbox[4], const uint8_t* p
         YK_HIP(c, hipMalloc(&c->dAlpha, plane));
         c->dAlphaBytes = plane;
     }
-    c->dAlphaValid = false;
+    c->dAlphaValid = false; c->dAlphaBatch = false;
     const size_t oPay = 0, oMask = (n + 255) & ~(size_t)255, oRows = oMask + ((maskBytes + 255) & ~(size_t)255);
     const size_t scratch = oRows + ((size_t)bh * 2 + 2) * sizeof(uint32_t) + 64;
     if (c->dAvScratchBytes < scratch) {
@@ -341,7 +403,7 @@ int yk_decode_alpha_plane(yk_ctx* c, uint8_t* hostOut, size_t cap) {
     const size_t plane = (size_t)c->dw * c->dh;
     if (cap < plane) return yk_fail(c, YK_ERR_RANGE, "alpha buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, hipMemcpyAsync(hostOut, c->dAlpha, plane, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(hostOut, yk_dec_alpha_cur(c), plane, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }
@@ -359,6 +421,7 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     if (c->nFrames != 1 || c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "yk_alpha_values works on a whole single image");
     const int W = c->fullW, H = c->fullH;
     YK_HIP(c, hipSetDevice(c->device));
+    c->avBatchValid = false;                                                              // the batch payloads share avState / avPay
     if (!c->avState) YK_HIP(c, hipMalloc(&c->avState, 8 * sizeof(int32_t)));
     if (c->avPayCap < (size_t)W * H) {
         YK_HIP(c, hipStreamSynchronize(c->stream));
@@ -443,6 +506,201 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
         YK_HIP(c, hipMemcpyAsync(hostPayload, src, bytes, hipMemcpyDeviceToHost, c->stream));
     }
     YK_HIP(c, hipStreamSynchronize(c->stream));
+    return YK_OK;
+}
+
+
+// ProcessAlpha(true) for every frame of the handle: the three kernels above over all frames, the two read-backs and one record table per batch
+int yk_alpha_values_batch(yk_ctx* c, int force8Bit, yk_alpha_info* infos) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!infos) return yk_refuse(c, YK_ERR_BAD_ARG, "infos is NULL");
+    if (!force8Bit) return yk_refuse(c, YK_ERR_BAD_ARG, "the 6-bit mask mode (force8Bit = 0) is not batched: it needs every frame's mask selection");
+    const int N = c->nFrames;
+    if (c->nPlanes == 4) {
+        if (!c->alphaFinished) return yk_refuse(c, YK_ERR_STATE, "the alpha stage first: yk_encode_batch, or yk_alpha_reject + yk_alpha_finish");
+        if (c->y0 != 0 || c->h != c->fullH) return yk_refuse(c, YK_ERR_STATE, "yk_alpha_values_batch works on whole images, not on a stripe");
+        if (!c->B.plane[3] || (N > 1 && c->fs.plane == 0)) return yk_refuse(c, YK_ERR_STATE, "bind planes first");
+    }
+    for (int f = 0; f < N; f++) { infos[f].mode = -1; infos[f].bbox[0] = infos[f].bbox[1] = infos[f].bbox[2] = infos[f].bbox[3] = 0; infos[f].rawSize = 0; }
+    c->avBatchValid = false;
+    c->avBatch.assign((size_t)N, yk_ctx::AvSlot{ -1, 0, 0 });
+    if (c->nPlanes != 4) { c->avBatchValid = true; return YK_OK; }                        // no alpha: no chunk in any frame (:1674-1680)
+    const int W = c->fullW, H = c->fullH;
+    YK_HIP(c, hipSetDevice(c->device));
+    if (c->avStateFrames < N) {
+        YK_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->avState) (void)hipFree(c->avState);
+        c->avState = nullptr; c->avStateFrames = 0;
+        YK_HIP(c, hipMalloc(&c->avState, (size_t)N * 8 * sizeof(int32_t)));
+        c->avStateFrames = N;
+    }
+    std::vector<int32_t> st((size_t)N * 8);
+    for (int f = 0; f < N; f++) { int32_t* s = &st[(size_t)f * 8]; s[0] = s[1] = INT_MAX; s[2] = s[3] = -1; s[4] = s[5] = s[6] = s[7] = 0; }
+    YK_HIP(c, hipMemcpyAsync(c->avState, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    const int32_t* alpha = c->B.plane[3];
+    const unsigned long long fe = N > 1 ? c->fs.plane : 0;
+    const bool vec = ((reinterpret_cast<uintptr_t>(alpha) & 15) == 0) && ((c->strideElems & 3) == 0) && ((fe & 3) == 0);
+    hipLaunchKernelGGL(vec ? yk_ave_box_batch_kernel<true> : yk_ave_box_batch_kernel<false>,
+                       dim3((unsigned)((W / 4 + 255) / 256), (unsigned)((H + YK_AV_ROWS - 1) / YK_AV_ROWS), (unsigned)N), dim3(256), 0, c->stream, alpha, fe,
+                       c->strideElems, c->B.bounds + c->boundsOff, W, H, c->avState);
+    YK_HIP(c, hipGetLastError());
+    YK_HIP(c, hipMemcpyAsync(st.data(), c->avState, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 1: every frame's box
+    // the payload slots back to back, each on a multiple of 16: bw * bh bytes of the box rounded to 4 (the 1-bit payload of the box re-aligned
+    // to 8 is never longer)
+    std::vector<YkAvFrame> tab;
+    size_t total = 0;
+    int maxW = 0, maxH = 0;
+    for (int f = 0; f < N; f++) {
+        const int32_t* s = &st[(size_t)f * 8];
+        if (s[2] < 0) continue;                                                           // empty box: no chunk
+        const int bL = (s[0] >> 2) << 2, bR = ((s[2] + 1 + 3) >> 2) << 2, bT = s[1], bB = s[3] + 1;   // :1465-1466
+        if (bL < 0 || bT < 0 || bR > W || bB > H || ((bR + 7) & ~7) > W) return yk_fail(c, YK_ERR_STATE, "alpha box beyond the image");
+        YkAvFrame r;
+        r.bL = bL; r.bT = bT; r.bw = bR - bL; r.bh = bB - bT; r.off = total; r.frame = f; r.pad = 0;
+        tab.push_back(r);
+        total = (total + (size_t)r.bw * r.bh + 15) & ~(size_t)15;
+        maxW = max(maxW, r.bw); maxH = max(maxH, r.bh);
+    }
+    if (tab.empty()) { c->avBatchValid = true; return YK_OK; }
+    if (c->avPayCap < total) {
+        YK_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->avPay) (void)hipFree(c->avPay);
+        c->avPay = nullptr; c->avPayCap = 0;
+        YK_HIP(c, hipMalloc(&c->avPay, total));
+        c->avPayCap = total;
+    }
+    const size_t tabBytes = tab.size() * sizeof(YkAvFrame);
+    if (c->avTabBytes < tabBytes) {
+        YK_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->avTab) (void)hipFree(c->avTab);
+        c->avTab = nullptr; c->avTabBytes = 0;
+        YK_HIP(c, hipMalloc(&c->avTab, (size_t)N * sizeof(YkAvFrame)));
+        c->avTabBytes = (size_t)N * sizeof(YkAvFrame);
+    }
+    YK_HIP(c, hipMemcpyAsync(c->avTab, tab.data(), tabBytes, hipMemcpyHostToDevice, c->stream));
+    const YkAvFrame* dTab = reinterpret_cast<const YkAvFrame*>(c->avTab);
+    const unsigned nBox = (unsigned)tab.size();
+    hipLaunchKernelGGL(vec ? yk_ave_class_batch_kernel<true> : yk_ave_class_batch_kernel<false>, dim3((unsigned)((maxW / 4 + 255) / 256), (unsigned)maxH, nBox),
+                       dim3(256), 0, c->stream, alpha, fe, c->strideElems, dTab, c->avPay, c->avState);
+    YK_HIP(c, hipGetLastError());
+    YK_HIP(c, hipMemcpyAsync(st.data(), c->avState, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 2: every frame's class
+    size_t maxBytes1 = 0;
+    for (const YkAvFrame& r : tab) {
+        const int32_t* s = &st[(size_t)r.frame * 8];
+        const bool analog = s[4] != 0, all1 = s[5] == 0;
+        yk_alpha_info& o = infos[r.frame];
+        int bL = r.bL, bw = r.bw;
+        size_t bytes;
+        if (analog) { o.mode = 6; bytes = (size_t)bw * r.bh; }                            // IS_8_BIT_FULL, payload already written
+        else if (all1) continue;                                                          // all 255: no chunk
+        else {                                                                            // binary: IS_1_BIT_FULL on the box re-aligned to 8
+            const int bR = ((bL + bw + 7) >> 3) << 3;
+            bL = (bL >> 3) << 3; bw = bR - bL;
+            bytes = (size_t)(bw >> 3) * r.bh;
+            o.mode = 1;
+            maxBytes1 = bytes > maxBytes1 ? bytes : maxBytes1;
+        }
+        o.bbox[0] = bL; o.bbox[1] = r.bT; o.bbox[2] = bw; o.bbox[3] = r.bh; o.rawSize = (uint32_t)bytes;
+        c->avBatch[(size_t)r.frame] = yk_ctx::AvSlot{ o.mode, (size_t)r.off, bytes };
+    }
+    if (maxBytes1) {
+        hipLaunchKernelGGL(yk_ave_pack1_batch_kernel, dim3((unsigned)((maxBytes1 + 255) / 256), 1, nBox), dim3(256), 0, c->stream, alpha, fe, c->strideElems, dTab,
+                           c->avPay, c->avState);
+        YK_HIP(c, hipGetLastError());
+    }
+    c->avBatchValid = true;
+    return YK_OK;
+}
+
+int yk_alpha_payload_device(yk_ctx* c, int frame, const uint8_t** dev, size_t* nBytes) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (dev) *dev = nullptr;
+    if (nBytes) *nBytes = 0;
+    if (!dev || !nBytes) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL result pointer");
+    if (!c->avBatchValid) return yk_refuse(c, YK_ERR_STATE, "yk_alpha_values_batch first");
+    if (frame < 0 || frame >= (int)c->avBatch.size()) return yk_refuse(c, YK_ERR_BAD_ARG, "frame out of range");
+    const yk_ctx::AvSlot& s = c->avBatch[(size_t)frame];
+    if (s.mode < 0) return YK_OK;
+    *dev = c->avPay + s.off; *nBytes = s.bytes;
+    return YK_OK;
+}
+
+int yk_alpha_payload(yk_ctx* c, int frame, uint8_t* hostOut, size_t cap, size_t* nBytes) {
+    if (!c) return YK_ERR_BAD_ARG;
+    const uint8_t* dev = nullptr; size_t n = 0;
+    if (nBytes) *nBytes = 0;
+    { const int rc = yk_alpha_payload_device(c, frame, &dev, &n); if (rc) return rc; }
+    if (nBytes) *nBytes = n;
+    if (!n) return YK_OK;
+    if (!hostOut || cap < n) return yk_refuse(c, YK_ERR_RANGE, "alpha payload buffer too small");
+    YK_HIP(c, hipSetDevice(c->device));
+    YK_HIP(c, hipMemcpyAsync(hostOut, dev, n, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));
+    return YK_OK;
+}
+
+// The 'ALPM' plane of every frame of a decode batch in one launch; records through the pinned ring + an HBM table, no host synchronisation
+int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes, const int32_t* bboxes, const uint8_t* const* devPayload, const size_t* payBytes,
+                                 int noChunkAlpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!modes || !bboxes || !devPayload || !payBytes) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
+    if (noChunkAlpha < 0 || noChunkAlpha > 255) return yk_refuse(c, YK_ERR_BAD_ARG, "noChunkAlpha must be 0..255");
+    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    const int N = c->dFrames, W = c->dw, H = c->dh;
+    for (int f = 0; f < N; f++) {
+        const int mode = modes[f];
+        if (mode == -1) continue;
+        const int bx = bboxes[4 * f], by = bboxes[4 * f + 1], bw = bboxes[4 * f + 2], bh = bboxes[4 * f + 3];
+        if (bx < 0 || by < 0 || bw <= 0 || bh <= 0 || bx >= W || by >= H || bx + bw > W || by + bh > H) return yk_refuse(c, YK_ERR_BAD_ARG, "alpha box outside the image");
+        size_t need = 0;
+        switch (mode) {
+        case 1: if (bw & 7) return yk_refuse(c, YK_ERR_BAD_ARG, "1-bit alpha box width not a multiple of 8");
+                need = (size_t)bh * (bw >> 3); break;
+        case 4: case 5: if (bw & 3) return yk_refuse(c, YK_ERR_BAD_ARG, "6-bit alpha box width not a multiple of 4");
+                need = (size_t)bh * (bw >> 2) * 3; break;
+        case 6: need = (size_t)bw * bh; break;
+        case 2: case 3: return yk_refuse(c, YK_ERR_BAD_ARG, "the mask modes 2 and 3 are not batched: they need every frame's decoded mipmap mask");
+        default: return yk_refuse(c, YK_ERR_BAD_ARG, "alpha mode not decodable");          // 0 (1 bit + mask), 7, anything else
+        }
+        if (!devPayload[f] && payBytes[f]) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL alpha payload with a length");
+        if (payBytes[f] < need) return yk_refuse(c, YK_ERR_RANGE, "alpha payload shorter than its box");
+    }
+    YK_HIP(c, hipSetDevice(c->device));
+    const size_t plane = (size_t)W * H, stride = (plane + 15) & ~(size_t)15;
+    if (c->dAlphaBytes < stride * N) {
+        YK_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->dAlpha) { (void)hipFree(c->dAlpha); c->dAlpha = nullptr; c->dAlphaBytes = 0; }
+        c->dAlphaValid = false;
+        YK_HIP(c, hipMalloc(&c->dAlpha, stride * N));
+        c->dAlphaBytes = stride * N;
+    }
+    const size_t tabBytes = (size_t)N * sizeof(YkAvDecFrame);
+    if (c->dAvScratchBytes < tabBytes) {
+        YK_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->dAvScratch) (void)hipFree(c->dAvScratch);
+        c->dAvScratch = nullptr; c->dAvScratchBytes = 0;
+        YK_HIP(c, hipMalloc(&c->dAvScratch, tabBytes));
+        c->dAvScratchBytes = tabBytes;
+    }
+    int slot; void* host;
+    { const int rc = yk_dec_table_host(c, tabBytes, &slot, &host); if (rc) return rc; }
+    YkAvDecFrame* tab = static_cast<YkAvDecFrame*>(host);
+    for (int f = 0; f < N; f++) {
+        YkAvDecFrame& r = tab[f];
+        r.mode = modes[f]; r.pay = r.mode < 0 ? nullptr : devPayload[f]; r.n = r.mode < 0 ? 0 : payBytes[f];
+        const bool has = r.mode >= 0;
+        r.bx = has ? bboxes[4 * f] : 0; r.by = has ? bboxes[4 * f + 1] : 0; r.bw = has ? bboxes[4 * f + 2] : 0; r.bh = has ? bboxes[4 * f + 3] : 0;
+        r.pad[0] = r.pad[1] = r.pad[2] = 0;
+    }
+    c->dAlphaValid = false;
+    { const int rc = yk_dec_table_upload(c, slot, c->dAvScratch, tabBytes); if (rc) return rc; }
+    hipLaunchKernelGGL((W & 15) ? yk_av_decode_batch_kernel<true> : yk_av_decode_batch_kernel<false>, dim3((unsigned)((plane / 16 + 255) / 256), (unsigned)N),
+                       dim3(256), 0, c->stream, reinterpret_cast<const YkAvDecFrame*>(c->dAvScratch), W, H, c->dAlpha, stride,
+                       (uint32_t)noChunkAlpha * 0x01010101u);
+    YK_HIP(c, hipGetLastError());
+    c->dAlphaValid = true; c->dAlphaBatch = true; c->dAlphaStride = stride;
     return YK_OK;
 }
 

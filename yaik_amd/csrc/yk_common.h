@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <string>
+#include <vector>
 #include "../../include/yaik_hip.h"
 
 #define YK_BLK      64      // pixels per workgroup block side (= the 64x64 swizzle block of include/YAIK_private.h:212)
@@ -146,6 +147,13 @@ struct yk_ctx {
     uint8_t* dAvScratch = nullptr; size_t dAvScratchBytes = 0;                      // its payload, mask and row counts
     int32_t* avState = nullptr; uint8_t* avPay = nullptr; size_t avPayCap = 0;      // yk_alpha_values: box + class flags, the payload
     uint8_t* av6 = nullptr; size_t av6Cap = 0;                                      // its 6-bit mask mode: tile prefixes, band scan, packed payload
+    // yk_alpha_values_batch: avState holds 8 ints per frame (avStateFrames of them), avPay the frames' payload slots back to back, avTab the
+    // per-frame records in HBM; avBatch = what the payload getters hand out (valid while avBatchValid)
+    int avStateFrames = 0; uint8_t* avTab = nullptr; size_t avTabBytes = 0;
+    struct AvSlot { int32_t mode; size_t off, bytes; };
+    std::vector<AvSlot> avBatch; bool avBatchValid = false;
+    // yk_decode_alpha_batch_device: dAlpha holds dFrames planes dAlphaStride bytes apart (the selected frame's is yk_dec_alpha_cur)
+    bool dAlphaBatch = false; size_t dAlphaStride = 0;
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
     // decode batch (yk_decode_begin_batch): dPlanes / dMapRGB / dLatticeOwner / dLoaded / dTile4 above are those of frame `dCur`; dB holds the
     // allocations (frame 0) and dStride the distance in BYTES from one frame's array to the next (yk_dec_rebase), like B / fs on the encode side
@@ -194,6 +202,10 @@ int yk_launch_corners(yk_ctx* c);
 int yk_launch_unpack_u8(yk_ctx* c, const uint8_t* src, size_t rowBytes, size_t frameBytes, int channels, int rows, int nFrames,
                         int32_t* dst, size_t planeElems, size_t frameElems);   // yk_pixels.hip
 int yk_corners_finish(yk_ctx* c);                         // reads the corner streams' lengths back if that is still pending (synchronises)
+// the pinned ring behind the per-frame tables of the decode batch calls (yk_decode.hip)
+extern "C" int yk_dec_table_host(yk_ctx* c, size_t bytes, int* slot, void** host);
+extern "C" int yk_dec_table_upload(yk_ctx* c, int slot, void* dev, size_t bytes);
+inline const uint8_t* yk_dec_alpha_cur(const yk_ctx* c) { return c->dAlpha + (c->dAlphaBatch ? (size_t)c->dCur * c->dAlphaStride : 0); }
 void yk_dec_free(yk_ctx* c);                              // frees the decode buffers of every frame and the batch tables' host ring (yk_decode.hip)
 void yk_lut_dec_destroy(yk_ctx* c);
 void yk_lut_destroy(yk_ctx* c);                          // frees the 3-D LUT bank and streams (yk_lut3d.hip)

@@ -922,26 +922,27 @@ __global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_kernel(YkDetileAr
     yk_dec_detile_body<C, PLANAR, ASRC>(a, blockIdx.x);
 }
 // a batch: frame blockIdx.y's planes at a.planes + f * planesFrame, its pixels at a.out + f * outFrame
+// (YK_DT_ALPHA_PLANE: its alpha plane at a.alpha + f * alphaFrame, the planes of yk_decode_alpha_batch_device)
 template <int C, bool PLANAR, int ASRC>
-__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_batch_kernel(YkDetileArgs a, size_t planesFrame, size_t outFrame) {
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_batch_kernel(YkDetileArgs a, size_t planesFrame, size_t outFrame, size_t alphaFrame) {
     a.planes += (size_t)blockIdx.y * planesFrame; a.out += (size_t)blockIdx.y * outFrame;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) a.alpha += (size_t)blockIdx.y * alphaFrame;
     yk_dec_detile_body<C, PLANAR, ASRC>(a, blockIdx.x);
 }
 
 // nFrames == 0: the image c->dPlanes points at (the existing single-image launch); otherwise nFrames frames, planesFrame / outFrame bytes apart
 template <int C, bool PLANAR, int ASRC>
-static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, size_t planesFrame = 0, size_t outFrame = 0) {
+static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, size_t planesFrame = 0, size_t outFrame = 0, size_t alphaFrame = 0) {
     const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
-    if constexpr (ASRC != YK_DT_ALPHA_PLANE) {                                 // a batch has no alpha plane
-        if (nFrames) { hipLaunchKernelGGL((yk_dec_detile_batch_kernel<C, PLANAR, ASRC>), dim3(gx, (unsigned)nFrames), dim3(YK_DT_THREADS), 0, s, a, planesFrame, outFrame); return; }
-    }
+    if (nFrames) { hipLaunchKernelGGL((yk_dec_detile_batch_kernel<C, PLANAR, ASRC>), dim3(gx, (unsigned)nFrames), dim3(YK_DT_THREADS), 0, s, a, planesFrame, outFrame, alphaFrame); return; }
     hipLaunchKernelGGL((yk_dec_detile_kernel<C, PLANAR, ASRC>), dim3(gx), dim3(YK_DT_THREADS), 0, s, a);
 }
 
 // the de-tile of the image begun on c into out; alpha: a plane (strideA bytes per row) or NULL with alphaConst 0..255 (channels 4)
-// frameBytes / nFrames: every frame of a batch in one launch (alpha constant or none), frame f at out + f * frameBytes; nFrames == 0: the selected frame
+// frameBytes / nFrames: every frame of a batch in one launch, frame f at out + f * frameBytes, its alpha plane (if any) at alpha + f * alphaFrame;
+// nFrames == 0: the selected frame
 static int yk_dec_detile(yk_ctx* c, uint8_t* out, size_t rowBytes, size_t planeBytes, int channels, const uint8_t* alpha, size_t strideA, int alphaConst,
-                         int nFrames = 0, size_t frameBytes = 0) {
+                         int nFrames = 0, size_t frameBytes = 0, size_t alphaFrame = 0) {
     YkDetileArgs a;
     a.planes = nFrames ? c->dB.planes : c->dPlanes; a.planeSize = c->dPlaneSize;
     const size_t pf = c->dStride.planes;
@@ -951,7 +952,7 @@ static int yk_dec_detile(yk_ctx* c, uint8_t* out, size_t rowBytes, size_t planeB
     const bool planar = planeBytes > 0;
     { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
     if (channels == 3) { if (planar) yk_dt_launch<3, true, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes); else yk_dt_launch<3, false, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes); }
-    else if (alpha)    { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_PLANE>(a, c->stream); else yk_dt_launch<4, false, YK_DT_ALPHA_PLANE>(a, c->stream); }
+    else if (alpha)    { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_PLANE>(a, c->stream, nFrames, pf, frameBytes, alphaFrame); else yk_dt_launch<4, false, YK_DT_ALPHA_PLANE>(a, c->stream, nFrames, pf, frameBytes, alphaFrame); }
     else               { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes); else yk_dt_launch<4, false, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes); }
     YK_HIP(c, hipGetLastError());
     return yk_stage_end(c, YK_STAGE_DEC_DETILE);
@@ -1088,7 +1089,7 @@ static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
     YK_HIP(c, hipMemsetAsync(c->dB.loaded, 0, c->dStride.loaded * N, c->stream));
     YK_HIP(c, hipMemsetAsync(c->dB.tile4, 0, c->dStride.tile4 * N, c->stream));
     c->dSplit = false;
-    c->dAlphaValid = false;                                                     // an 'ALPM' plane belongs to one image
+    c->dAlphaValid = false; c->dAlphaBatch = false;                             // an 'ALPM' plane belongs to one image (or one batch)
     return YK_OK;
 }
 
@@ -1113,7 +1114,7 @@ int yk_decode_select_frame(yk_ctx* c, int frame) {
 
 // The per-frame tables of a batch call travel through a ring of four pinned host buffers: the call fills one, queues its copy into HBM and records
 // an event behind the copy.  A slot is waited for only when it comes round again, i.e. when the tables of four earlier batch calls are still queued.
-static int yk_dec_table_host(yk_ctx* c, size_t bytes, int* slot, void** host) {
+int yk_dec_table_host(yk_ctx* c, size_t bytes, int* slot, void** host) {
     const int k = (int)(c->dTabSeq++ & 3u);
     if (c->dTabEv[k]) YK_HIP(c, hipEventSynchronize(c->dTabEv[k]));
     else YK_HIP(c, hipEventCreateWithFlags(&c->dTabEv[k], hipEventDisableTiming));
@@ -1125,7 +1126,7 @@ static int yk_dec_table_host(yk_ctx* c, size_t bytes, int* slot, void** host) {
     *slot = k; *host = c->dTabHost[k];
     return YK_OK;
 }
-static int yk_dec_table_upload(yk_ctx* c, int slot, void* dev, size_t bytes) {
+int yk_dec_table_upload(yk_ctx* c, int slot, void* dev, size_t bytes) {
     YK_HIP(c, hipMemcpyAsync(dev, c->dTabHost[slot], bytes, hipMemcpyHostToDevice, c->stream));
     YK_HIP(c, hipEventRecord(c->dTabEv[slot], c->stream));
     return YK_OK;
@@ -1550,7 +1551,7 @@ int yk_decode_output_alpha(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride
     if (!c) return YK_ERR_BAD_ARG;
     YK_DEC_NO_BATCH(c, "yk_decode_output_alpha");
     if (!c->dAlphaValid) return yk_fail(c, YK_ERR_STATE, "yk_decode_alpha first");
-    return yk_decode_output_impl(c, hostOut, outputImageStride, nullptr, 0, false, c->dAlpha);
+    return yk_decode_output_impl(c, hostOut, outputImageStride, nullptr, 0, false, yk_dec_alpha_cur(c));
 }
 
 int yk_decode_output_reference_rgba(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA) {
@@ -1572,7 +1573,7 @@ int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t 
     if (fromPlane && !c->dAlphaValid) return yk_fail(c, YK_ERR_STATE, "alpha = -1 needs yk_decode_alpha first");
     YK_HIP(c, hipSetDevice(c->device));
     { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
-    return yk_dec_detile(c, devOut, rowBytes, planeBytes, channels, fromPlane ? c->dAlpha : nullptr, w, fromPlane ? 0 : alpha);
+    return yk_dec_detile(c, devOut, rowBytes, planeBytes, channels, fromPlane ? yk_dec_alpha_cur(c) : nullptr, w, fromPlane ? 0 : alpha);
 }
 
 int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha) {
@@ -1589,6 +1590,22 @@ int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, s
     YK_HIP(c, hipSetDevice(c->device));
     { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
     return yk_dec_detile(c, devOut, rowBytes, planeBytes, channels, nullptr, w, alpha, c->dFrames, frameBytes);
+}
+
+// yk_decode_output_batch_device with four channels, alpha from the planes yk_decode_alpha_batch_device left in HBM
+int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "devOut is NULL");
+    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    if (!c->dAlphaValid || !c->dAlphaBatch) return yk_refuse(c, YK_ERR_STATE, "yk_decode_alpha_batch_device first: the batch has no decoded alpha planes");
+    const size_t w = (size_t)c->dw, h = (size_t)c->dh;
+    if (planeBytes == 0 ? rowBytes < w * 4 : (rowBytes < w || planeBytes / h < rowBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "row or plane pitch too small for the image");
+    if (c->dFrames > 1 && (planeBytes == 0 ? frameBytes / h < rowBytes : frameBytes / 4 < planeBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "frame stride too small for a frame");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    return yk_dec_detile(c, devOut, rowBytes, planeBytes, 4, c->dAlpha, w, 0, c->dFrames, frameBytes, c->dAlphaStride);
 }
 
 const uint8_t* yk_decode_planes_device(yk_ctx* c, size_t* planeSize) {

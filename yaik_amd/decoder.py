@@ -7,11 +7,60 @@ alpha value unpackers of decoder/YAIK_Alpha.cpp.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
 from ._lib import YaikError, lib
 from .encoder import PASSES, _chk, u8_pixel_layout, u8_planar_batch_layout, u8_planar_layout
+
+
+class AlphaBatchPack(NamedTuple):
+    """The tables of yk_decode_alpha_batch_device for a list of per-frame entries: pack_alpha_batch."""
+    modes: np.ndarray       # int32 [N]: AlphaHeader::parameters & 7, -1 for a frame without a chunk
+    bboxes: np.ndarray      # int32 [N, 4]: (x, y, w, h), zeros for a frame without a chunk
+    nbytes: np.ndarray      # uint64 [N]: payload lengths
+    where: list             # per frame ("h", offset into staging), ("d", device address) or None
+    staging: np.ndarray     # uint8: every host payload at its offset, offsets are multiples of 16; empty when no entry is a host array
+
+
+def pack_alpha_batch(entries) -> AlphaBatchPack:
+    """entries[f]: None (no 'ALPM' chunk), or (mode, bbox, payload[, nbytes]) with payload a numpy uint8 array (nbytes defaults to its size) or a
+    device pointer (int / c_void_p; nbytes required).  Host payloads are laid out back to back in one staging array, each at a 16-byte aligned
+    offset, so that they reach the device in one copy.  Reads only the entries: no GPU."""
+    n = len(entries)
+    modes, bboxes, nbytes = np.full(n, -1, dtype=np.int32), np.zeros((n, 4), dtype=np.int32), np.zeros(n, dtype=np.uint64)
+    where, chunks, size = [None] * n, [], 0
+    for f, e in enumerate(entries):
+        if e is None:
+            continue
+        if len(e) not in (3, 4):
+            raise ValueError(f"entry {f}: (mode, bbox, payload[, nbytes]) or None expected")
+        mode, bbox, pay = int(e[0]), np.asarray(e[1], dtype=np.int64).reshape(-1), e[2]
+        if mode < 0 or bbox.size != 4:
+            raise ValueError(f"entry {f}: a mode >= 0 and a box (x, y, w, h) expected (None marks a frame without a chunk)")
+        modes[f], bboxes[f] = mode, bbox
+        if isinstance(pay, np.ndarray):
+            a = np.ascontiguousarray(pay, dtype=np.uint8).ravel()
+            nb = a.size if len(e) == 3 else int(e[3])
+            if nb < 0 or a.size < nb:
+                raise ValueError(f"entry {f}: a payload of {a.size} bytes was given a length of {nb}")
+            where[f] = ("h", size)
+            chunks.append((size, a[:nb]))
+            size = (size + nb + 15) & ~15
+        else:
+            if len(e) != 4:
+                raise ValueError(f"entry {f}: a device payload needs its length")
+            pay = pay.value if isinstance(pay, C.c_void_p) else pay
+            nb = int(e[3])
+            if nb < 0:
+                raise ValueError(f"entry {f}: negative length")
+            where[f] = ("d", int(pay) if pay else 0)
+        nbytes[f] = nb
+    staging = np.zeros(size, dtype=np.uint8)
+    for off, a in chunks:
+        staging[off:off + a.size] = a
+    return AlphaBatchPack(modes, bboxes, nbytes, where, staging)
 
 
 class HipTileDecoder:
@@ -25,8 +74,10 @@ class HipTileDecoder:
         self.w = self.h = 0
         self.frames = 1
         self._has_alpha = False
+        self._alpha_batch = False        # decompress_alpha_batch left a plane per frame of the batch on the device
         self._batch_stage = None         # torch buffers a queued batch decode may still read: the staging tensor of host streams ...
         self._batch_streams = None       # ... and the copy of an encoder's per-handle streams (encoder_batch_streams)
+        self._alpha_stage = None         # ... and the staging tensor of decompress_alpha_batch's host payloads
 
     def close(self):
         if getattr(self, "_h", None):
@@ -161,15 +212,63 @@ class HipTileDecoder:
         self._batch_streams = keep
         return frames
 
-    def decode_batch_from_encoder(self, enc, sync: bool = True) -> None:
-        self.decode_batch_streams(self.encoder_batch_streams(enc), sync)
+    def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False) -> None:
+        """decode_batch_streams of encoder_batch_streams(enc); alpha=True also runs the encoder's alpha_values_batch and decodes every frame's
+        'ALPM' payload where the encoder left it in HBM (decompress_alpha_batch; frames without a chunk are opaque)."""
+        frames = self.encoder_batch_streams(enc)
+        entries = None
+        if alpha:
+            entries = enc.alpha_payloads_device()
+            enc.synchronize()                                              # the payloads are written on the encoder's stream
+        self.decode_batch_streams(frames, sync and not alpha)
+        if alpha:
+            self.decompress_alpha_batch(entries, 255, sync)
 
-    def image_batch_device(self, out=None, channels: int = 3, alpha: int = 255, planar: bool = False):
-        """Every frame of the batch as 8-bit pixels in one torch.uint8 tensor on the handle's device (yk_decode_output_batch_device, one launch):
-        [N, h, w, C], or [N, C, h, w] with planar=True; C = 3, or 4 with the constant alpha 0..255.  `out` may be any view with unit inner
-        stride and any row, plane and frame pitch (u8_pixel_layout(batch=True) / u8_planar_batch_layout): only its pixel bytes are written.
-        Ordering against torch's current stream is that of image_device: no host fence."""
+    def decompress_alpha_batch(self, entries, no_chunk_alpha: int = 255, sync: bool = True) -> None:
+        """The 'ALPM' plane of every frame of the batch in one launch (yk_decode_alpha_batch_device).  entries[f] is None (no chunk: the plane is
+        the constant no_chunk_alpha) or (mode, bbox, payload[, nbytes]) with the DECOMPRESSED payload as a numpy uint8 array or a device pointer
+        with its length (HipTileEncoder.alpha_payloads_device); modes 1, 4, 5 and 6.  Host arrays are packed into one staging tensor
+        (pack_alpha_batch) and sent in one copy.  The planes stay on the device for image_batch_device(alpha_from_planes=True) and, frame by frame,
+        for image_device(alpha=-1) and alpha_plane()."""
         import torch
+        L = lib()
+        if len(entries) != self.frames:
+            raise ValueError(f"{len(entries)} entries for a batch of {self.frames} frames")
+        pk = pack_alpha_batch(entries)
+        base = 0
+        if pk.staging.size:
+            dev = torch.device("cuda", self.device)
+            if self._alpha_stage is not None:
+                _chk(self._h, L.yk_synchronize(self._h))                   # a decode queued with sync=False may still read the previous staging tensor
+            stage = torch.from_numpy(pk.staging).to(dev)
+            base = stage.data_ptr()
+            _chk(self._h, L.yk_stream_wait_for(self._h, torch.cuda.current_stream(dev).cuda_stream))
+            self._alpha_stage = stage
+        n = self.frames
+        ptrs = (C.c_void_p * n)(*[None if w is None else ((base + w[1] if w[0] == "h" else w[1]) or None) for w in pk.where])
+        sizes = (C.c_size_t * n)(*[int(v) for v in pk.nbytes])
+        self._alpha_batch = False
+        _chk(self._h, L.yk_decode_alpha_batch_device(self._h, pk.modes.ctypes.data, np.ascontiguousarray(pk.bboxes).ctypes.data, ptrs, sizes,
+                                                      int(no_chunk_alpha)))
+        self._alpha_batch = True
+        if sync:
+            _chk(self._h, L.yk_synchronize(self._h))
+
+    def alpha_plane(self) -> np.ndarray:
+        """The decoded 'ALPM' plane [h, w] of the image, or of the selected frame of a batch, back on the host (yk_decode_alpha_plane)."""
+        out = np.empty((self.h, self.w), dtype=np.uint8)
+        _chk(self._h, lib().yk_decode_alpha_plane(self._h, out.ctypes.data, out.size))
+        return out
+
+    def image_batch_device(self, out=None, channels: int = 3, alpha: int = 255, planar: bool = False, alpha_from_planes: bool = False):
+        """Every frame of the batch as 8-bit pixels in one torch.uint8 tensor on the handle's device (yk_decode_output_batch_device, one launch):
+        [N, h, w, C], or [N, C, h, w] with planar=True; C = 3, or 4 with the constant alpha 0..255.  alpha_from_planes=True (channels=4 only)
+        takes every frame's alpha from the planes decompress_alpha_batch left on the device instead (yk_decode_output_batch_alpha_device).  `out`
+        may be any view with unit inner stride and any row, plane and frame pitch (u8_pixel_layout(batch=True) / u8_planar_batch_layout): only
+        its pixel bytes are written.  Ordering against torch's current stream is that of image_device: no host fence."""
+        import torch
+        if alpha_from_planes and channels != 4:
+            raise ValueError("alpha_from_planes needs channels=4")
         dev = torch.device("cuda", self.device)
         N = self.frames
         if out is None:
@@ -188,7 +287,10 @@ class HipTileDecoder:
         L = lib()
         cur = torch.cuda.current_stream(dev).cuda_stream
         _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
-        _chk(self._h, L.yk_decode_output_batch_device(self._h, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels, int(alpha)))
+        if alpha_from_planes:
+            _chk(self._h, L.yk_decode_output_batch_alpha_device(self._h, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes))
+        else:
+            _chk(self._h, L.yk_decode_output_batch_device(self._h, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels, int(alpha)))
         _chk(self._h, L.yk_stream_handoff(self._h, cur))
         return out
 

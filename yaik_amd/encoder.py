@@ -259,7 +259,7 @@ class HipTileEncoder:
         b = np.zeros(4, dtype=np.int32); tb = np.zeros(4, dtype=np.int32)
         has, rem = C.c_int(), C.c_int()
         _chk(self._h, L.yk_alpha_result(self._h, b.ctypes.data, C.byref(has), C.byref(rem), tb.ctypes.data))
-        out = np.zeros(max(1, (self.w // 16) * (self.full_h // 16) // 8 + 8), dtype=np.uint8)
+        out = np.zeros(((self.w + 15) // 16) * ((self.full_h + 15) // 16) // 8 + 8, dtype=np.uint8)   # a side of 8 mod 16 ends in a part tile
         nb = C.c_size_t()
         _chk(self._h, L.yk_alpha_bitmap(self._h, out.ctypes.data, out.size, C.byref(nb)))
         return {"has_chunk": bool(has.value), "bounds": b, "remaining": rem.value, "tile_bbox": tb, "bitmap": out[:nb.value].copy()}
@@ -278,6 +278,42 @@ class HipTileEncoder:
         if info.mode < 0:
             return None
         return {"mode": int(info.mode), "bbox": tuple(int(v) for v in info.bbox), "payload": out[:n.value].copy()}
+
+    def _alpha_values_batch(self) -> list:
+        class _Info(C.Structure):
+            _fields_ = [("mode", C.c_int32), ("bbox", C.c_int32 * 4), ("rawSize", C.c_uint32)]
+
+        infos = (_Info * self.frames)()
+        _chk(self._h, self._L.yk_alpha_values_batch(self._h, 1, infos))
+        return [None if i.mode < 0 else (int(i.mode), tuple(int(v) for v in i.bbox), int(i.rawSize)) for i in infos]
+
+    def alpha_values_batch(self) -> list:
+        """ProcessAlpha(true) for every frame of the handle (yk_alpha_values_batch), after encode_batch() (or, for one frame, mip_prefilter()):
+        per frame the dict of alpha_values(), or None where no 'ALPM' chunk is written.  Three launches and two read-backs for the whole batch;
+        the payloads are then copied out frame by frame (alpha_payloads_device leaves them in HBM)."""
+        out = []
+        for f, e in enumerate(self._alpha_values_batch()):
+            if e is None:
+                out.append(None)
+                continue
+            pay, n = np.empty(e[2], dtype=np.uint8), C.c_size_t()
+            _chk(self._h, self._L.yk_alpha_payload(self._h, f, pay.ctypes.data if pay.size else None, pay.size, C.byref(n)))
+            out.append({"mode": e[0], "bbox": e[1], "payload": pay[:n.value]})
+        return out
+
+    def alpha_payloads_device(self) -> list:
+        """alpha_values_batch() without copying the payloads out: per frame None or (mode, bbox, device pointer, nbytes), the entries
+        HipTileDecoder.decompress_alpha_batch takes.  The payloads are written on this handle's stream (synchronize() or a stream hand-off before
+        another stream reads them) and stay valid until the next encode, set_image / set_batch or alpha_values[_batch] of the handle."""
+        out = []
+        for f, e in enumerate(self._alpha_values_batch()):
+            if e is None:
+                out.append(None)
+                continue
+            dev, n = C.c_void_p(), C.c_size_t()
+            _chk(self._h, self._L.yk_alpha_payload_device(self._h, f, C.byref(dev), C.byref(n)))
+            out.append((e[0], e[1], int(dev.value or 0), int(n.value)))
+        return out
 
     # ---- 7x FittingQuadSmooth + 3x DynamicTileEncode, one launch ---------------------------------------
     def encode(self, reject_factor: int = 3, mode3bit_only: bool = False, want_dst: bool = False, dst_fill: int = -1):
