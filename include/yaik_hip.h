@@ -163,11 +163,41 @@ int yk_encode_frame(yk_ctx* c, int rejectFactor, int mode3BitOnly);
  * (yk_set_image for the shape, then yk_set_batch) whose planes lie at frame0Planes[p] + f * frameStrideElems; yk_encode_batch
  * runs alpha reject + fused kernel + compaction over ALL frames with one launch per kernel (the grid simply spans
  * nFrames x strips), with the same per-frame results as yk_encode_frame.  yk_select_frame chooses the frame every getter,
- * yk_export_tile_maps, the corner streams and the 1-D path act on (default 0).  Whole images only, kernel version 2. */
+ * yk_export_tile_maps and the single-image corner streams (yk_gradient_corners*) and 1-D path (yk_range1d_*) act on (default 0);
+ * yk_encode_streams_batch below builds the corner and 1-D streams of ALL frames at once.  Whole images only, kernel version 2. */
 int yk_set_batch(yk_ctx* c, int nFrames);
 int yk_bind_device_batch(yk_ctx* c, const int32_t* const frame0Planes[4], int strideElems, size_t frameStrideElems);
 int yk_encode_batch(yk_ctx* c, int rejectFactor, int mode3BitOnly);
 int yk_select_frame(yk_ctx* c, int frame);
+
+/* The corner colour streams and the live 1-D streams of every frame of the handle, one launch per kernel (new).
+ * yk_encode_streams_batch(what = YK_STREAMS_CORNERS | YK_STREAMS_RANGE1D, 1..3) is valid after yk_encode_batch and, for a batch of one, after
+ * yk_encode_tiles / yk_encode_frame on a whole image.  Frame f's results are byte-identical to yk_select_frame(f) followed by yk_gradient_corners
+ * for the seven passes and by yk_range1d_encode + yk_range1d_streams.  Whatever nFrames (1..1024) is, the call makes at most seven kernel launches
+ * and the lattice clear, ONE blocking read-back (nine uint32 per frame: the stream lengths) and one upload of a table of stream bases; the streams
+ * are packed into one buffer in HBM, each at an offset that is a multiple of 16 (yk_decode_1d_batch_device reads pixel streams in place), with no
+ * worst-case regions: the buffer is as large as the streams are and only grows.  The stripe edge index (yk_gradient_corner_edges) is not
+ * produced and the pixel cache (yk_set_pixel_cache) is not used.  One interval of YK_STAGE_CORNERS (which spans the read-back), YK_STAGE_RANGE1D_PACK
+ * and YK_STAGE_RANGE1D per call, each only when that stage is requested.
+ * yk_batch_streams_table fills out[0..nFrames): bitmap[p] / bitmapBytes[p] are what yk_gradient_bitmap_device(p) / yk_gradient_bitmap_bytes(p) give
+ * for that frame; rgb[p] is the corner stream of pass p (CompressF(., 250) bytes, not remapped), pix the 1-D pixel stream (planes R, G, B
+ * appended), type the 1-D parameter triples; a stream that is empty or was not requested has a NULL pointer and length 0.  No synchronisation:
+ * the emit kernels may still be running, so read the streams on this handle's stream or behind yk_stream_handoff (yk_synchronize on the host).
+ * The batch's results live in buffers of their own: yk_select_frame and the single-image getters still work afterwards and do not disturb them.
+ * The table and the streams stay valid until the next yk_encode_tiles / yk_encode_frame / yk_encode_batch, yk_set_image, yk_set_batch, (re)bind
+ * or upload of planes or pixels, or yk_encode_streams_batch of the handle; yk_select_frame does not invalidate them.
+ * Refusals launch nothing and leave the handle and an earlier valid table usable (the message: yk_last_error): YK_ERR_BAD_ARG for `what` outside
+ * 1..3 or a NULL `out`; YK_ERR_STATE before an encode, on a stripe, with no planes bound, after a plane-subset pass (yk_gradient_partial_pass),
+ * and for yk_batch_streams_table without a valid table. */
+enum { YK_STREAMS_CORNERS = 1, YK_STREAMS_RANGE1D = 2 };
+typedef struct yk_frame_streams {
+    const uint8_t* bitmap[7]; size_t bitmapBytes[7];
+    const uint8_t* rgb[7];    size_t rgbBytes[7];
+    const uint8_t* pix;  size_t pixBytes;
+    const uint8_t* type; size_t typeBytes;
+} yk_frame_streams;
+int yk_encode_streams_batch(yk_ctx* c, int what);
+int yk_batch_streams_table(yk_ctx* c, yk_frame_streams* out /* nFrames */);
 
 /* ---- streams of frames on several handles (new) --------------------------------------------------------------------------
  * With two handles (two streams) in flight the HBM-bound alpha / compaction kernels of one frame run under the fused kernel of

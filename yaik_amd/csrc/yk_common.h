@@ -59,6 +59,21 @@ struct YkEncodeParams {
     YkFrameStrides fs;
 };
 
+// yk_encode_streams_batch (yk_streams_batch.hip): one record per frame in HBM, the bases of the frame's streams in the batch's output buffer
+// (nullptr: empty or not requested); the emit kernels read the record of their frame through uniform loads
+#define YK_SB_COUNTS 9          // uint32 read back per frame: corners of the 7 passes, coded 1-D tiles and 1-D pixel bytes of one plane
+struct YkStreamRec { uint8_t* rgb[7]; uint8_t* pix; uint8_t* type; };
+// the batch's own buffers (grow-only, freed with the image): they share nothing with the single-image corner / 1-D state
+struct YkStreamsBatch {
+    uint32_t* owner = nullptr; size_t ownerElems = 0;            // [F][lattice]
+    uint32_t* cScratch = nullptr; size_t cScratchElems = 0;      // [F][block sums], [F][ownership words]
+    uint32_t* r1Scratch = nullptr; size_t r1ScratchElems = 0;    // [F][offsets in block], [F][coded tiles per block], [F][pixel bytes per block]
+    uint32_t* counts = nullptr; size_t countsElems = 0;          // [F][YK_SB_COUNTS]
+    uint8_t* out = nullptr; size_t outCap = 0;                   // every stream of every frame, each on a multiple of 16
+    uint8_t* tab = nullptr; size_t tabCap = 0;                   // [F] YkStreamRec
+    std::vector<yk_frame_streams> table; bool valid = false;     // what yk_batch_streams_table hands out
+};
+
 // The layout of yk_ctx must NOT depend on YK_TEST_HOOKS: the product library and the test-hooks build of the same sources are loaded side by
 // side by the tests, each owning the handles it created (yaik_amd/encoder.py keeps a handle with its library); no member below is conditional.
 struct yk_ctx {
@@ -179,6 +194,7 @@ struct yk_ctx {
     hipGraphExec_t frameGraph = nullptr;
     unsigned long long frameGraphKey[12] = {};
     int kernelVersion = 2;              // 2 = yk_encode2_kernel; 1 = the registered cross-check launcher (tests/csrc/yk_encode_v1.hip)
+    YkStreamsBatch sb;                  // yk_encode_streams_batch
 };
 
 int yk_fail(yk_ctx* c, int code, const char* what, hipError_t e = hipSuccess);
@@ -201,6 +217,16 @@ int yk_launch_pack(yk_ctx* c, bool batch = false);
 int yk_launch_corners(yk_ctx* c);
 int yk_launch_unpack_u8(yk_ctx* c, const uint8_t* src, size_t rowBytes, size_t frameBytes, int channels, int rows, int nFrames,
                         int32_t* dst, size_t planeElems, size_t frameElems);   // yk_pixels.hip
+// yk_encode_streams_batch: count and emit phases over all frames (yk_corners.hip, yk_range1d.hip), the grow-only buffers and their release (yk_streams_batch.hip)
+int yk_corners_batch_count(yk_ctx* c);
+int yk_corners_batch_emit(yk_ctx* c);
+int yk_range1d_batch_count(yk_ctx* c);
+int yk_range1d_batch_emit(yk_ctx* c);
+int yk_sb_grow_bytes(yk_ctx* c, void** p, size_t* cap, size_t need);
+inline int yk_sb_grow(yk_ctx* c, uint32_t** p, size_t* capElems, size_t needElems) {
+    size_t cap = *capElems * 4; const int rc = yk_sb_grow_bytes(c, reinterpret_cast<void**>(p), &cap, needElems * 4); *capElems = cap / 4; return rc;
+}
+void yk_sb_free(yk_ctx* c);
 int yk_corners_finish(yk_ctx* c);                         // reads the corner streams' lengths back if that is still pending (synchronises)
 // the pinned ring behind the per-frame tables of the decode batch calls (yk_decode.hip)
 extern "C" int yk_dec_table_host(yk_ctx* c, size_t bytes, int* slot, void** host);

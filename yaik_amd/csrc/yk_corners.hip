@@ -43,7 +43,20 @@ __device__ __forceinline__ int yk_plan_find(const uint32_t (&start)[8], uint32_t
     return p;
 }
 
-__global__ __launch_bounds__(256) void yk_corner_owner_kernel(const CornerPlan pl, int w, int latW, uint32_t* __restrict__ owner) {
+// Batches (yk_encode_streams_batch): the kernels' bodies are __device__ functions; the single-image kernels call them with BATCH = false (the
+// arithmetic they always had), the batch kernels with the frame taken from blockIdx.y and the frame's arrays formed as base + f * stride.
+struct CornerBatch {
+    unsigned long long sBm[7];      // bytes from one frame's bitmap of pass p to the next frame's (YkFrameStrides::bitmap)
+    unsigned long long sPlane;      // int32 elements between the frames' planes
+    unsigned long long sOwner;      // lattice points per frame
+    unsigned long long sBlk;        // block sums per frame
+    unsigned long long sPer;        // ownership words per frame
+    const YkStreamRec* tab;         // the frames' stream bases (emit)
+};
+
+// BATCH: the bitmap bytes behind a pass's last byte (the padding of its last word) are not cleared per frame, they are masked here
+template <bool BATCH>
+__device__ __forceinline__ void yk_corner_owner_body(const CornerPlan& pl, const CornerBatch* cb, uint32_t f, int w, int latW, uint32_t* __restrict__ owner) {
     // One thread per bitmap byte (8 slots of one swizzle block: the block's coordinates are computed once, see yk_corner_stream_kernel).
     // Measured alternatives on the 8192x8192 bench frame (131 k accepted 16x16 tiles): one thread per word 41 us, per byte 41 us, per byte
     // with the atomics of corners a lower-positioned neighbour tile of the same pass also touches left out 47 us, per slot with that
@@ -53,7 +66,8 @@ __global__ __launch_bounds__(256) void yk_corner_owner_kernel(const CornerPlan p
     if (gi >= pl.wordStart[7] * 4u) return;
     const int pass = yk_plan_find(pl.wordStart, gi >> 2);
     const uint32_t bi = gi - pl.wordStart[pass] * 4u;
-    const uint32_t byte = reinterpret_cast<const uint8_t*>(pl.bm[pass])[bi];
+    if (BATCH && bi >= (uint32_t)(pl.bits[pass] >> 3)) return;
+    const uint32_t byte = (reinterpret_cast<const uint8_t*>(pl.bm[pass]) + (BATCH ? (size_t)f * cb->sBm[pass] : (size_t)0))[bi];
     if (!byte) return;
     const PassGeo g = yk_pass_geo(pass, w);
     const uint32_t pos0 = bi * 8u, blk = pos0 / (uint32_t)g.bitCount, t0 = pos0 % (uint32_t)g.bitCount;
@@ -80,6 +94,13 @@ __global__ __launch_bounds__(256) void yk_corner_owner_kernel(const CornerPlan p
         atomicMin(&owner[(size_t)(ly + dy) * latW + lx + dx], key | 3u);
     }
 }
+__global__ __launch_bounds__(256) void yk_corner_owner_kernel(const CornerPlan pl, int w, int latW, uint32_t* __restrict__ owner) {
+    yk_corner_owner_body<false>(pl, nullptr, 0u, w, latW, owner);
+}
+__global__ __launch_bounds__(256) void yk_corner_owner_batch_kernel(const CornerPlan pl, const CornerBatch cb, int w, int latW, uint32_t* __restrict__ owner) {
+    const uint32_t f = blockIdx.y;
+    yk_corner_owner_body<true>(pl, &cb, f, w, latW, owner + (size_t)f * cb.sOwner);
+}
 
 // One thread per bitmap BYTE (8 tile slots), 1024 bytes per workgroup.  (Round 1 ran one thread per slot: a block scan per 1024 slots of
 // mostly empty maps cost more than the work it ordered; one thread per 32-bit word serialises 32 dependent gather rounds in the dense
@@ -87,18 +108,20 @@ __global__ __launch_bounds__(256) void yk_corner_owner_kernel(const CornerPlan p
 // set read entry 0 and are masked), so a thread waits for memory once.  COUNT: corners owned per thread (kept as bytes for the emit
 // launch) and per workgroup.  EMIT: exclusive scan inside the workgroup + the scanned workgroup bases (relative to the pass's first
 // block) = byte offset of the thread's first owned corner; a thread walks its tiles in bit order = the reference's scan order.
-template <bool EMIT>
-__global__ __launch_bounds__(1024) void yk_corner_stream_kernel(const CornerPlan pl, int w, int latW,
-                                                                const uint32_t* __restrict__ owner, uint32_t* __restrict__ blockSums, uint32_t* __restrict__ perThread,
-                                                                const int32_t* const __restrict__ pR, const int32_t* const __restrict__ pG,
-                                                                const int32_t* const __restrict__ pB, int strideElems,
-                                                                uint8_t* __restrict__ out0, size_t region, uint32_t* __restrict__ edgeIdx, int latH, int hAvail) {
+// BATCH: pass p's colours go to the frame's own base for p (out0 = the frame's YkStreamRec::rgb), and no stripe edge index is kept
+template <bool EMIT, bool BATCH>
+__device__ __forceinline__ void yk_corner_stream_body(const CornerPlan& pl, const CornerBatch* cb, uint32_t f, int w, int latW,
+                                                      const uint32_t* __restrict__ owner, uint32_t* __restrict__ blockSums, uint32_t* __restrict__ perThread,
+                                                      const int32_t* const __restrict__ pR, const int32_t* const __restrict__ pG,
+                                                      const int32_t* const __restrict__ pB, int strideElems,
+                                                      uint8_t* __restrict__ out0, size_t region, uint32_t* __restrict__ edgeIdx, int latH, int hAvail) {
     __shared__ uint32_t s_tmp[32];
     const int pass = yk_plan_find(pl.blockStart, blockIdx.x);
     const uint32_t bi = (blockIdx.x - pl.blockStart[pass]) * 1024u + threadIdx.x;           // byte of the pass's bitmap
     const uint32_t nBytes = (pl.wordStart[pass + 1] - pl.wordStart[pass]) * 4u;
     const size_t ti = (size_t)pl.wordStart[pass] * 4u + bi;                                   // thread index over all passes
-    const uint32_t byte = bi < nBytes ? reinterpret_cast<const uint8_t*>(pl.bm[pass])[bi] : 0u;
+    const uint32_t byte = bi < (BATCH ? (uint32_t)(pl.bits[pass] >> 3) : nBytes)
+                              ? (reinterpret_cast<const uint8_t*>(pl.bm[pass]) + (BATCH ? (size_t)f * cb->sBm[pass] : (size_t)0))[bi] : 0u;
     const PassGeo g = yk_pass_geo(pass, w);
     const int dx = 1 << (g.sx - 2), dy = 1 << (g.sy - 2);
     // COUNT leaves the thread's ownership bits (4 per tile slot) for EMIT, which then neither repeats the 32 owner look-ups nor waits for them
@@ -154,7 +177,7 @@ __global__ __launch_bounds__(1024) void yk_corner_stream_kernel(const CornerPlan
     __shared__ uint32_t s_out[kCap * 3 / 4];
     __shared__ uint32_t s_li[kCap];                                          // lattice index of the workgroup's j-th colour, in stream order
     const uint32_t blockOff = (blockSums[blockIdx.x] - blockSums[pl.blockStart[pass]]) * 3u;
-    uint8_t* __restrict__ out = out0 + region * pass;
+    uint8_t* __restrict__ out = BATCH ? cb->tab[f].rgb[pass] : out0 + region * pass;
     const bool viaLds = tot <= kCap;
     uint8_t* const s_bytes = reinterpret_cast<uint8_t*>(s_out);
     auto colour = [&](const uint32_t li, const uint32_t j, const bool toLds) {   // j-th colour of the workgroup: lattice point li
@@ -162,8 +185,10 @@ __global__ __launch_bounds__(1024) void yk_corner_stream_kernel(const CornerPlan
         // GetPixelValue clamp (:3853-3856); a stripe's bottom lattice row is its halo row (= the next stripe's first row)
         const size_t src = (size_t)min(ly * 4, hAvail - 1) * strideElems + min(lx * 4, w - 1);
         // stripes: where along this pass's stream the first and last lattice rows were emitted (root-side de-duplication)
-        if (ly == 0) edgeIdx[lx] = blockOff / 3u + j;
-        if (ly == latH - 1) edgeIdx[latW + lx] = blockOff / 3u + j;
+        if (!BATCH) {
+            if (ly == 0) edgeIdx[lx] = blockOff / 3u + j;
+            if (ly == latH - 1) edgeIdx[latW + lx] = blockOff / 3u + j;
+        }
         const int v[3] = { pR[src], pG[src], pB[src] };
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
@@ -206,9 +231,28 @@ __global__ __launch_bounds__(1024) void yk_corner_stream_kernel(const CornerPlan
     const uint32_t tail0 = head + nWords * 4u;
     if (threadIdx.x < outBytes - tail0) dst[tail0 + threadIdx.x] = s_bytes[tail0 + threadIdx.x];
 }
+template <bool EMIT>
+__global__ __launch_bounds__(1024) void yk_corner_stream_kernel(const CornerPlan pl, int w, int latW,
+                                                                const uint32_t* __restrict__ owner, uint32_t* __restrict__ blockSums, uint32_t* __restrict__ perThread,
+                                                                const int32_t* const __restrict__ pR, const int32_t* const __restrict__ pG,
+                                                                const int32_t* const __restrict__ pB, int strideElems,
+                                                                uint8_t* __restrict__ out0, size_t region, uint32_t* __restrict__ edgeIdx, int latH, int hAvail) {
+    yk_corner_stream_body<EMIT, false>(pl, nullptr, 0u, w, latW, owner, blockSums, perThread, pR, pG, pB, strideElems, out0, region, edgeIdx, latH, hAvail);
+}
+// frame = blockIdx.y; the frame's record is read through uniform loads (f is the same for the whole workgroup), like the decode batch kernels' DecPlan
+template <bool EMIT>
+__global__ __launch_bounds__(1024) void yk_corner_stream_batch_kernel(const CornerPlan pl, const CornerBatch cb, int w, int latW,
+                                                                      const uint32_t* __restrict__ owner, uint32_t* __restrict__ blockSums, uint32_t* __restrict__ perThread,
+                                                                      const int32_t* const __restrict__ pR, const int32_t* const __restrict__ pG,
+                                                                      const int32_t* const __restrict__ pB, int strideElems, int latH, int hAvail) {
+    const uint32_t f = blockIdx.y;
+    const size_t po = (size_t)f * cb.sPlane;
+    yk_corner_stream_body<EMIT, true>(pl, &cb, f, w, latW, owner + (size_t)f * cb.sOwner, blockSums + (size_t)f * cb.sBlk, perThread + (size_t)f * cb.sPer,
+                                      pR + po, pG + po, pB + po, strideElems, nullptr, 0, nullptr, latH, hAvail);
+}
 
 // exclusive prefix of all block sums in place (one workgroup: thread t owns a run of consecutive blocks) + the corners per pass
-__global__ __launch_bounds__(1024) void yk_corner_scan_kernel(uint32_t* __restrict__ blockSums, const CornerPlan pl, uint32_t* __restrict__ passTotals) {
+__device__ __forceinline__ void yk_corner_scan_body(uint32_t* __restrict__ blockSums, const CornerPlan& pl, uint32_t* __restrict__ passTotals) {
     __shared__ uint32_t s_tmp[32];
     __shared__ uint32_t s_total;
     const uint32_t n = pl.blockStart[7], per = (n + 1023) / 1024;
@@ -226,6 +270,23 @@ __global__ __launch_bounds__(1024) void yk_corner_scan_kernel(uint32_t* __restri
         passTotals[threadIdx.x] = (pl.blockStart[threadIdx.x] < n) ? hi - lo : 0u;
     }
 }
+__global__ __launch_bounds__(1024) void yk_corner_scan_kernel(uint32_t* __restrict__ blockSums, const CornerPlan pl, uint32_t* __restrict__ passTotals) {
+    yk_corner_scan_body(blockSums, pl, passTotals);
+}
+// one workgroup per frame; the 7 pass totals of frame f go to counts[f * YK_SB_COUNTS + 0..6]
+__global__ __launch_bounds__(1024) void yk_corner_scan_batch_kernel(uint32_t* __restrict__ blockSums, const CornerPlan pl, unsigned long long sBlk, uint32_t* __restrict__ counts) {
+    yk_corner_scan_body(blockSums + (size_t)blockIdx.x * sBlk, pl, counts + (size_t)blockIdx.x * YK_SB_COUNTS);
+}
+
+static void yk_corner_plan(const yk_ctx* c, uint8_t* const bitmap[7], CornerPlan& pl) {
+    pl.wordStart[0] = 0; pl.blockStart[0] = 0;
+    for (int p = 0; p < 7; p++) {
+        pl.bits[p] = (unsigned long long)c->bitmapBytes[p] * 8;
+        pl.bm[p] = reinterpret_cast<const uint32_t*>(bitmap[p]);
+        pl.wordStart[p + 1] = pl.wordStart[p] + (uint32_t)((c->bitmapBytes[p] + 3) / 4);   // bitmap allocations are padded by 16 bytes; pass 0 words may be half used
+        pl.blockStart[p + 1] = pl.blockStart[p] + ((pl.wordStart[p + 1] - pl.wordStart[p]) * 4u + 1023u) / 1024u;   // 1024 bitmap bytes per workgroup
+    }
+}
 
 int yk_launch_corners(yk_ctx* c) {
     // Row stripes: the handle de-duplicates inside its own rows; its first and last lattice rows are shared with the
@@ -239,13 +300,7 @@ int yk_launch_corners(yk_ctx* c) {
     const size_t region = lat * 3 + 16;
     if (!c->cornerStream) { c->cornerCap = region * 7; YK_HIP(c, hipMalloc(&c->cornerStream, c->cornerCap)); }
     CornerPlan pl;
-    pl.wordStart[0] = 0; pl.blockStart[0] = 0;
-    for (int p = 0; p < 7; p++) {
-        pl.bits[p] = (unsigned long long)c->bitmapBytes[p] * 8;
-        pl.bm[p] = reinterpret_cast<const uint32_t*>(c->bitmap[p]);
-        pl.wordStart[p + 1] = pl.wordStart[p] + (uint32_t)((c->bitmapBytes[p] + 3) / 4);   // bitmap allocations are padded by 16 bytes; pass 0 words may be half used
-        pl.blockStart[p + 1] = pl.blockStart[p] + ((pl.wordStart[p + 1] - pl.wordStart[p]) * 4u + 1023u) / 1024u;   // 1024 bitmap bytes per workgroup
-    }
+    yk_corner_plan(c, c->bitmap, pl);
     const size_t nbTot = pl.blockStart[7], nWordsTot = pl.wordStart[7];
     // scratch: [block sums | 7 totals (+ pad) | ownership bits per thread (one word per bitmap byte)]
     if (!c->cornerScratch) { c->cornerScratchElems = nbTot + 64 + nWordsTot * 4; YK_HIP(c, hipMalloc(&c->cornerScratch, c->cornerScratchElems * 4)); }
@@ -272,6 +327,51 @@ int yk_launch_corners(yk_ctx* c) {
     for (int p = 0; p < 7; p++) c->cornerOff[p] = region * p;
     c->cornerTotalsDev = totalDev; c->cornerTotalsPending = true;
     c->cornersReady = true;
+    return YK_OK;
+}
+
+// ---- yk_encode_streams_batch: the corner streams of every frame (the sequence and the buffers: yk_streams_batch.hip) -----------------------
+// The frames' arrays: lattice owners [F][lat]; scratch [F][sBlk] block sums, then [F][sPer] ownership words (one per bitmap byte).
+static void yk_corner_batch_desc(const yk_ctx* c, const CornerPlan& pl, CornerBatch& cb, uint32_t*& blockSums, uint32_t*& perThread) {
+    const size_t F = (size_t)c->nFrames;
+    for (int p = 0; p < 7; p++) cb.sBm[p] = c->fs.bitmap[p];
+    cb.sPlane = F > 1 ? c->fs.plane : 0;
+    cb.sOwner = (unsigned long long)(c->fullW / 4 + 1) * (c->h / 4 + 1);
+    cb.sBlk = ((unsigned long long)pl.blockStart[7] + 3) & ~3ULL;
+    cb.sPer = (unsigned long long)pl.wordStart[7] * 4;
+    cb.tab = reinterpret_cast<const YkStreamRec*>(c->sb.tab);
+    blockSums = c->sb.cScratch; perThread = c->sb.cScratch + F * cb.sBlk;
+}
+
+// count phase: lattice clear, owners, corners per block (leaves the ownership bits), one scan workgroup per frame -> counts[f][0..6]
+int yk_corners_batch_count(yk_ctx* c) {
+    const int w = c->fullW, latW = w / 4 + 1;
+    const unsigned F = (unsigned)c->nFrames;
+    CornerPlan pl; CornerBatch cb; uint32_t* blockSums; uint32_t* perThread;
+    yk_corner_plan(c, c->B.bitmap, pl);
+    { const unsigned long long lat = (unsigned long long)latW * (c->h / 4 + 1), sBlk = ((unsigned long long)pl.blockStart[7] + 3) & ~3ULL;
+      int rc = yk_sb_grow(c, &c->sb.owner, &c->sb.ownerElems, (size_t)lat * F); if (rc) return rc;
+      rc = yk_sb_grow(c, &c->sb.cScratch, &c->sb.cScratchElems, (size_t)(sBlk + (unsigned long long)pl.wordStart[7] * 4) * F); if (rc) return rc; }
+    yk_corner_batch_desc(c, pl, cb, blockSums, perThread);
+    YK_HIP(c, hipMemsetAsync(c->sb.owner, 0xFF, (size_t)cb.sOwner * F * 4, c->stream));
+    hipLaunchKernelGGL(yk_corner_owner_batch_kernel, dim3((pl.wordStart[7] * 4u + 255u) / 256u, F), dim3(256), 0, c->stream, pl, cb, w, latW, c->sb.owner);
+    hipLaunchKernelGGL(yk_corner_stream_batch_kernel<false>, dim3(pl.blockStart[7], F), dim3(1024), 0, c->stream, pl, cb, w, latW, (const uint32_t*)c->sb.owner,
+                       blockSums, perThread, c->B.plane[0], c->B.plane[1], c->B.plane[2], c->strideElems, c->h / 4 + 1, c->h);
+    hipLaunchKernelGGL(yk_corner_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, blockSums, pl, cb.sBlk, c->sb.counts);
+    YK_HIP(c, hipGetLastError());
+    return YK_OK;
+}
+
+// emit phase: the table of stream bases is in HBM (c->sb.tab); every workgroup writes its run of its frame's pass
+int yk_corners_batch_emit(yk_ctx* c) {
+    const int w = c->fullW, latW = w / 4 + 1;
+    const unsigned F = (unsigned)c->nFrames;
+    CornerPlan pl; CornerBatch cb; uint32_t* blockSums; uint32_t* perThread;
+    yk_corner_plan(c, c->B.bitmap, pl);
+    yk_corner_batch_desc(c, pl, cb, blockSums, perThread);
+    hipLaunchKernelGGL(yk_corner_stream_batch_kernel<true>, dim3(pl.blockStart[7], F), dim3(1024), 0, c->stream, pl, cb, w, latW, (const uint32_t*)c->sb.owner,
+                       blockSums, perThread, c->B.plane[0], c->B.plane[1], c->B.plane[2], c->strideElems, c->h / 4 + 1, c->h);
+    YK_HIP(c, hipGetLastError());
     return YK_OK;
 }
 

@@ -23,11 +23,12 @@ __device__ __forceinline__ int yk_r1_div(int n, int d) { return __float2int_rz((
 // [strip][cell row][lane in that kernel's Morton order]) instead of the int32 planes (12 B per pixel): a lane's sixteen pixels are four 16-byte
 // loads, held in registers across the three planes -- no staging through LDS, and every input sample of the whole path is read from HBM once.
 struct R1Direct { const uint32_t* offInBlk; const uint32_t* blockT; const uint32_t* blockP; const uint32_t* totals; uint8_t* pixOut; uint8_t* typeOut; const uint4* pixCache; };
-template <bool DIRECT, bool CACHED = false>
-__global__ __launch_bounds__(64) void yk_range1d_kernel(const int32_t* __restrict__ pR, const int32_t* __restrict__ pG, const int32_t* __restrict__ pB,
-                                                        int strideElems, int w, int h, const uint16_t* __restrict__ coverage, int mtW,
-                                                        int tilesW, size_t T8, uint8_t* __restrict__ slots, uint8_t* __restrict__ params,
-                                                        uint32_t* __restrict__ cntTiles, uint32_t* __restrict__ cntPix, int onlyPlane, const R1Direct D) {
+// The body is a __device__ function: yk_range1d_kernel calls it as it always ran, yk_range1d_batch_kernel with the arrays of frame blockIdx.y.
+template <bool DIRECT, bool CACHED>
+__device__ __forceinline__ void yk_range1d_body(const int32_t* __restrict__ pR, const int32_t* __restrict__ pG, const int32_t* __restrict__ pB,
+                                                int strideElems, int w, int h, const uint16_t* __restrict__ coverage, int mtW,
+                                                int tilesW, size_t T8, uint8_t* __restrict__ slots, uint8_t* __restrict__ params,
+                                                uint32_t* __restrict__ cntTiles, uint32_t* __restrict__ cntPix, int onlyPlane, const R1Direct D) {
     // onlyPlane < 0: the three planes share `coverage` (no partial-plane pass ran).  Otherwise this launch codes plane `onlyPlane` alone
     // against that plane's own coverage (mapSmoothTile->GetPlane(p), EncoderContext.cpp:9451-9465).
     __shared__ __attribute__((aligned(16))) uint32_t s_px[16 * 16];          // 16 rows x 64 pixels, one byte each
@@ -258,11 +259,40 @@ __global__ __launch_bounds__(64) void yk_range1d_kernel(const int32_t* __restric
         }
     }
 }
+template <bool DIRECT, bool CACHED = false>
+__global__ __launch_bounds__(64) void yk_range1d_kernel(const int32_t* __restrict__ pR, const int32_t* __restrict__ pG, const int32_t* __restrict__ pB,
+                                                        int strideElems, int w, int h, const uint16_t* __restrict__ coverage, int mtW,
+                                                        int tilesW, size_t T8, uint8_t* __restrict__ slots, uint8_t* __restrict__ params,
+                                                        uint32_t* __restrict__ cntTiles, uint32_t* __restrict__ cntPix, int onlyPlane, const R1Direct D) {
+    yk_range1d_body<DIRECT, CACHED>(pR, pG, pB, strideElems, w, h, coverage, mtW, tilesW, T8, slots, params, cntTiles, cntPix, onlyPlane, D);
+}
+
+// yk_encode_streams_batch: the frames' arrays as base + f * stride.  Per frame: [sOff] offsets inside the block, [sBlk] coded tiles and [sBlk] pixel
+// bytes per block of 1024 tiles; the two totals of frame f are counts[f * YK_SB_COUNTS + 7..8].
+struct R1Batch {
+    const uint16_t* coverage; unsigned long long sCov;     // u16 elements between frames (YkFrameStrides::coverage)
+    unsigned long long sPlane;                             // int32 elements between the frames' planes
+    uint32_t* offInBlk; unsigned long long sOff;
+    uint32_t* blockT; uint32_t* blockP; unsigned long long sBlk;
+    uint32_t* counts;
+    const YkStreamRec* tab;                                // the frames' stream bases (coder)
+};
+// the coder over all frames, frame = blockIdx.y: direct form on the int32 planes (the pixel cache is not for batches); the frame's record and totals are
+// the same for the whole wave, so they are read through uniform loads
+__global__ __launch_bounds__(64) void yk_range1d_batch_kernel(const int32_t* __restrict__ pR, const int32_t* __restrict__ pG, const int32_t* __restrict__ pB,
+                                                              int strideElems, int w, int h, int mtW, int tilesW, size_t T8, const R1Batch Bt) {
+    const uint32_t f = blockIdx.y;
+    const size_t po = (size_t)f * Bt.sPlane;
+    R1Direct D;
+    D.offInBlk = Bt.offInBlk + (size_t)f * Bt.sOff; D.blockT = Bt.blockT + (size_t)f * Bt.sBlk; D.blockP = Bt.blockP + (size_t)f * Bt.sBlk;
+    D.totals = Bt.counts + (size_t)f * YK_SB_COUNTS + 7; D.pixOut = Bt.tab[f].pix; D.typeOut = Bt.tab[f].type; D.pixCache = nullptr;
+    yk_range1d_body<true, false>(pR + po, pG + po, pB + po, strideElems, w, h, Bt.coverage + (size_t)f * Bt.sCov, mtW, tilesW, T8, nullptr, nullptr, nullptr, nullptr, -1, D);
+}
 
 // Stream offsets from the coverage alone (thread = tile, 1024 tiles per workgroup): a tile emits 16 bytes per uncovered quadrant and one
 // parameter triple when it emits anything.  Packed like the decoder's scan: coded tiles in the low 11 bits, pixel bytes above.
-__global__ __launch_bounds__(1024) void yk_r1_offsets_kernel(const uint16_t* __restrict__ coverage, int mtW, int tilesW, size_t T8,
-                                                             uint32_t* __restrict__ offInBlk, uint32_t* __restrict__ blockT, uint32_t* __restrict__ blockP) {
+__device__ __forceinline__ void yk_r1_offsets_body(const uint16_t* __restrict__ coverage, int mtW, int tilesW, size_t T8,
+                                                   uint32_t* __restrict__ offInBlk, uint32_t* __restrict__ blockT, uint32_t* __restrict__ blockP) {
     __shared__ uint32_t s_tmp[32];
     const size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x;
     uint32_t cnt = 0;
@@ -278,8 +308,16 @@ __global__ __launch_bounds__(1024) void yk_r1_offsets_kernel(const uint16_t* __r
     if (i < T8) offInBlk[i] = e;
     if (threadIdx.x == 0) { blockT[blockIdx.x] = tot & 2047u; blockP[blockIdx.x] = tot >> 11; }
 }
+__global__ __launch_bounds__(1024) void yk_r1_offsets_kernel(const uint16_t* __restrict__ coverage, int mtW, int tilesW, size_t T8,
+                                                             uint32_t* __restrict__ offInBlk, uint32_t* __restrict__ blockT, uint32_t* __restrict__ blockP) {
+    yk_r1_offsets_body(coverage, mtW, tilesW, T8, offInBlk, blockT, blockP);
+}
+__global__ __launch_bounds__(1024) void yk_r1_offsets_batch_kernel(const R1Batch Bt, int mtW, int tilesW, size_t T8) {
+    const uint32_t f = blockIdx.y;
+    yk_r1_offsets_body(Bt.coverage + (size_t)f * Bt.sCov, mtW, tilesW, T8, Bt.offInBlk + (size_t)f * Bt.sOff, Bt.blockT + (size_t)f * Bt.sBlk, Bt.blockP + (size_t)f * Bt.sBlk);
+}
 // both block-sum arrays -> exclusive prefixes in place, totals[0] = coded tiles, totals[1] = pixel bytes of ONE plane
-__global__ __launch_bounds__(1024) void yk_r1_scan_kernel(uint32_t* __restrict__ blockT, uint32_t* __restrict__ blockP, int nBlocks, uint32_t* __restrict__ totals) {
+__device__ __forceinline__ void yk_r1_scan_body(uint32_t* __restrict__ blockT, uint32_t* __restrict__ blockP, int nBlocks, uint32_t* __restrict__ totals) {
     __shared__ uint32_t s_tmp[32];
 #pragma unroll 1
     for (int a = 0; a < 2; a++) {
@@ -295,6 +333,14 @@ __global__ __launch_bounds__(1024) void yk_r1_scan_kernel(uint32_t* __restrict__
         }
         if (threadIdx.x == 0) totals[a] = base;
     }
+}
+__global__ __launch_bounds__(1024) void yk_r1_scan_kernel(uint32_t* __restrict__ blockT, uint32_t* __restrict__ blockP, int nBlocks, uint32_t* __restrict__ totals) {
+    yk_r1_scan_body(blockT, blockP, nBlocks, totals);
+}
+// one workgroup per frame
+__global__ __launch_bounds__(1024) void yk_r1_scan_batch_kernel(const R1Batch Bt, int nBlocks) {
+    const uint32_t f = blockIdx.x;
+    yk_r1_scan_body(Bt.blockT + (size_t)f * Bt.sBlk, Bt.blockP + (size_t)f * Bt.sBlk, nBlocks, Bt.counts + (size_t)f * YK_SB_COUNTS + 7);
 }
 
 // One workgroup = 1024 consecutive tiles of one plane: scans give every tile its stream offsets, then 16 lanes per tile copy
@@ -338,6 +384,41 @@ __global__ __launch_bounds__(1024) void yk_range1d_pack_kernel(const uint32_t* _
 }
 
 __global__ void yk_r1_next_plane_kernel(uint32_t* __restrict__ runBase, const uint32_t* __restrict__ tot) { if (threadIdx.x < 2) runBase[2 + threadIdx.x] = runBase[threadIdx.x] + tot[threadIdx.x]; }
+
+// ---- yk_encode_streams_batch: the 1-D streams of every frame (the sequence and the buffers: yk_streams_batch.hip) ---------------------------
+static int yk_r1_batch_desc(yk_ctx* c, R1Batch& Bt, bool grow) {
+    const size_t F = (size_t)c->nFrames, T8 = (size_t)c->tilesW * c->tilesH, nb = (T8 + 1023) / 1024;
+    Bt.sOff = (T8 + 3) & ~(size_t)3; Bt.sBlk = (nb + 3) & ~(size_t)3;
+    if (grow) { int rc = yk_sb_grow(c, &c->sb.r1Scratch, &c->sb.r1ScratchElems, (size_t)(Bt.sOff + 2 * Bt.sBlk) * F); if (rc) return rc; }
+    Bt.coverage = c->B.coverage; Bt.sCov = c->fs.coverage; Bt.sPlane = F > 1 ? c->fs.plane : 0;
+    Bt.offInBlk = c->sb.r1Scratch; Bt.blockT = Bt.offInBlk + F * Bt.sOff; Bt.blockP = Bt.blockT + F * Bt.sBlk;
+    Bt.counts = c->sb.counts; Bt.tab = reinterpret_cast<const YkStreamRec*>(c->sb.tab);
+    return YK_OK;
+}
+
+// count phase: every tile's stream offsets from the coverage, one scan workgroup per frame -> counts[f][7..8]
+int yk_range1d_batch_count(yk_ctx* c) {
+    R1Batch Bt;
+    { int rc = yk_r1_batch_desc(c, Bt, true); if (rc) return rc; }
+    const size_t T8 = (size_t)c->tilesW * c->tilesH, nb = (T8 + 1023) / 1024;
+    const unsigned F = (unsigned)c->nFrames;
+    hipLaunchKernelGGL(yk_r1_offsets_batch_kernel, dim3((unsigned)nb, F), dim3(1024), 0, c->stream, Bt, c->mtW, c->tilesW, T8);
+    hipLaunchKernelGGL(yk_r1_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, Bt, (int)nb);
+    YK_HIP(c, hipGetLastError());
+    return YK_OK;
+}
+
+// emit phase: the coder writes every frame's pixel bytes and parameters straight to the frame's own bases (c->sb.tab, in HBM)
+int yk_range1d_batch_emit(yk_ctx* c) {
+    R1Batch Bt;
+    { int rc = yk_r1_batch_desc(c, Bt, false); if (rc) return rc; }
+    const size_t T8 = (size_t)c->tilesW * c->tilesH;
+    const unsigned nStrips = (unsigned)(((c->fullW + 63) / 64) * ((c->h + 15) / 16));
+    hipLaunchKernelGGL(yk_range1d_batch_kernel, dim3(nStrips, (unsigned)c->nFrames), dim3(64), 0, c->stream, c->B.plane[0], c->B.plane[1], c->B.plane[2], c->strideElems,
+                       c->fullW, c->h, c->mtW, c->tilesW, T8, Bt);
+    YK_HIP(c, hipGetLastError());
+    return YK_OK;
+}
 
 extern "C" {
 

@@ -63,6 +63,41 @@ def pack_alpha_batch(entries) -> AlphaBatchPack:
     return AlphaBatchPack(modes, bboxes, nbytes, where, staging)
 
 
+def batch_calls_from_table(table, passes=PASSES) -> list:
+    """The call lists of HipTileDecoder.decode_batch_streams from the rows of an encoder's stream table (HipTileEncoder.streams_batch, or any
+    objects with the attributes of encoder.FrameStreams): per frame ("g", sx, sy, bitmap, nbytes, rgb, nbytes) for every pass of `passes`, in
+    that order, followed by ("1", type, nbytes, pix, nbytes) -- addresses and lengths only, nothing is copied.  A pass without tiles in a frame
+    keeps its bitmap and gets the address 0 with length 0; a frame without 1-D bytes gets ("1", 0, 0, 0, 0).  Reads only the table: no GPU.
+    Raises ValueError for a row whose lists do not match `passes`, frames whose bitmaps of a pass differ in length, a length with a NULL
+    address, a corner stream that is not whole RGB triples, 1-D streams that are not three planes of whole cells / whole parameter triples,
+    and a pixel stream that is not 16-byte aligned (yk_decode_1d_batch_device reads it in place)."""
+    passes = list(passes)
+    frames = []
+    for f, t in enumerate(table):
+        if not (len(t.bitmap) == len(t.bitmap_bytes) == len(t.rgb) == len(t.rgb_bytes) == len(passes)):
+            raise ValueError(f"frame {f}: {len(t.bitmap)} bitmaps / {len(t.rgb)} corner streams for {len(passes)} passes")
+        if frames and list(t.bitmap_bytes) != list(table[0].bitmap_bytes):
+            raise ValueError(f"frame {f}: bitmap lengths {list(t.bitmap_bytes)} differ from frame 0's {list(table[0].bitmap_bytes)}")
+        calls = []
+        for p, (sx, sy) in enumerate(passes):
+            bm, nbm, rgb, nrgb = int(t.bitmap[p] or 0), int(t.bitmap_bytes[p]), int(t.rgb[p] or 0), int(t.rgb_bytes[p])
+            if nbm <= 0 or not bm:
+                raise ValueError(f"frame {f} pass {p}: every pass needs its tile bitmap")
+            if nrgb < 0 or nrgb % 3 or (nrgb and not rgb):
+                raise ValueError(f"frame {f} pass {p}: a corner stream of {nrgb} bytes at address {rgb:#x}")
+            calls.append(("g", sx, sy, bm, nbm, rgb if nrgb else 0, nrgb))
+        typ, nty, pix, npx = int(t.type or 0), int(t.type_bytes), int(t.pix or 0), int(t.pix_bytes)
+        if nty < 0 or nty % 9 or (nty and not typ):
+            raise ValueError(f"frame {f}: a 1-D parameter stream of {nty} bytes at address {typ:#x} (three planes of triples expected)")
+        if npx < 0 or npx % 48 or (npx and not pix) or (npx and pix & 15):
+            raise ValueError(f"frame {f}: a 1-D pixel stream of {npx} bytes at address {pix:#x} (three planes of 16-byte cells, 16-byte aligned, expected)")
+        if bool(nty) != bool(npx):
+            raise ValueError(f"frame {f}: {nty} parameter bytes with {npx} pixel bytes")
+        calls.append(("1", typ if nty else 0, nty, pix if npx else 0, npx))
+        frames.append(calls)
+    return frames
+
+
 class HipTileDecoder:
     def __init__(self, device: int = 0):
         h = C.c_void_p()
@@ -167,13 +202,26 @@ class HipTileDecoder:
         if sync:
             _chk(self._h, L.yk_synchronize(self._h))
 
-    def encoder_batch_streams(self, enc) -> list:
-        """The call lists of decode_batch_streams for an encoder that ran encode_batch (same device).  Frame after frame: select_frame, the
-        corner stage, yk_range1d_encode.  The tile bitmaps are per frame in the encoder and are referenced where they lie; the corner and 1-D
-        streams are ONE buffer per encoder handle, overwritten by the next frame's stages, so every frame's are copied device-to-device (on the
-        encoder's stream) into one torch buffer this decoder keeps alive until its next encoder_batch_streams.  Every pass is listed for every
-        frame (a pass without tiles: all-zero bitmap, empty stream).  Fences the encoder once at the end; the lengths cost a read-back per
-        frame.  The bitmap pointers go stale with the encoder's next encode, like those of encoder_streams."""
+    def encoder_batch_streams(self, enc, per_frame: bool = False) -> list:
+        """The call lists of decode_batch_streams for an encoder that ran encode_batch (same device).  Every pass is listed for every frame (a
+        pass without tiles: all-zero bitmap, empty stream).
+        Default: enc.streams_batch() builds the corner and 1-D streams of all frames with one launch per kernel and one read-back, and
+        batch_calls_from_table lists them where they lie in the encoder's HBM: nothing is copied, no buffer is allocated here, the encoder is
+        fenced once.  The corner and 1-D streams then go stale with the encoder's next encode, set_image / set_batch or streams_batch, like the
+        bitmap pointers: decode (or copy) them before that.
+        per_frame=True: the earlier form, kept as the cross-check and the baseline of profiles/encode_streams_batch.  Frame after frame:
+        select_frame, the corner stage, yk_range1d_encode.  The corner and 1-D streams are ONE buffer per encoder handle, overwritten by the next
+        frame's stages, so every frame's are copied device-to-device (on the encoder's stream) into one worst-case-sized torch buffer this decoder
+        keeps alive until its next encoder_batch_streams; the lengths cost two read-backs per frame.  Only the bitmap pointers go stale with the
+        encoder's next encode."""
+        if not per_frame:
+            _chk(self._h, lib().yk_synchronize(self._h))                       # a queued decode may still read streams the encoder's call replaces
+            if (enc.w, enc.h, enc.frames) != (self.w, self.h, self.frames):
+                raise ValueError(f"the encoder holds {enc.frames} frames of {enc.w} x {enc.h}, the decoder batch {self.frames} of {self.w} x {self.h}")
+            frames = batch_calls_from_table(enc.streams_batch(), PASSES)
+            enc.synchronize()
+            self._batch_streams = None
+            return frames
         import torch
         n = enc.frames
         _chk(self._h, lib().yk_synchronize(self._h))                           # a queued decode may still read the buffer this call replaces
@@ -212,10 +260,11 @@ class HipTileDecoder:
         self._batch_streams = keep
         return frames
 
-    def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False) -> None:
-        """decode_batch_streams of encoder_batch_streams(enc); alpha=True also runs the encoder's alpha_values_batch and decodes every frame's
-        'ALPM' payload where the encoder left it in HBM (decompress_alpha_batch; frames without a chunk are opaque)."""
-        frames = self.encoder_batch_streams(enc)
+    def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False, per_frame: bool = False) -> None:
+        """decode_batch_streams of encoder_batch_streams(enc, per_frame); alpha=True also runs the encoder's alpha_values_batch and decodes every
+        frame's 'ALPM' payload where the encoder left it in HBM (decompress_alpha_batch; frames without a chunk are opaque).  With sync=False on
+        the default path the queued decode reads the encoder's own stream buffer: fence this decoder before the encoder's next encode."""
+        frames = self.encoder_batch_streams(enc, per_frame)
         entries = None
         if alpha:
             entries = enc.alpha_payloads_device()

@@ -143,6 +143,43 @@ def u8_planar_batch_layout(pixels) -> PlanarBatchLayout:
     return PlanarBatchLayout(frames, lay.channels, lay.rows, lay.w, lay.row_bytes, lay.plane_bytes, frame_bytes)
 
 
+class _FrameStreamsC(C.Structure):                # yk_frame_streams of include/yaik_hip.h
+    _fields_ = [("bitmap", C.c_void_p * 7), ("bitmapBytes", C.c_size_t * 7), ("rgb", C.c_void_p * 7), ("rgbBytes", C.c_size_t * 7),
+                ("pix", C.c_void_p), ("pixBytes", C.c_size_t), ("type", C.c_void_p), ("typeBytes", C.c_size_t)]
+
+
+class FrameStreams:
+    """One frame's row of yk_batch_streams_table: device addresses (int, 0 = NULL) and byte lengths of its seven tile bitmaps, its seven raw
+    corner streams (CompressF(., 250) bytes, not remapped), its 1-D pixel stream and its 1-D parameter triples.  A stream that is empty or was
+    not requested has address 0 and length 0.  The addresses point into the encoder's own buffers: they go stale with its next encode, set_image /
+    set_batch or streams_batch."""
+    __slots__ = ("bitmap", "bitmap_bytes", "rgb", "rgb_bytes", "pix", "pix_bytes", "type", "type_bytes", "_enc")
+
+    def __init__(self, bitmap, bitmap_bytes, rgb, rgb_bytes, pix, pix_bytes, type, type_bytes, enc=None):
+        self.bitmap, self.bitmap_bytes = [int(v or 0) for v in bitmap], [int(v) for v in bitmap_bytes]
+        self.rgb, self.rgb_bytes = [int(v or 0) for v in rgb], [int(v) for v in rgb_bytes]
+        self.pix, self.pix_bytes, self.type, self.type_bytes = int(pix or 0), int(pix_bytes), int(type or 0), int(type_bytes)
+        self._enc = enc
+
+    def download(self) -> dict:
+        """{"rgb": [7 uint8 arrays], "pix": uint8 array, "type": uint8 array}: the frame's streams copied to the host (yk_device_download: on the
+        encoder's stream, synchronises it).  For tests and file writers."""
+        enc = self._enc
+        if enc is None or not getattr(enc, "_h", None):
+            raise YaikError("these FrameStreams belong to no live encoder")
+
+        def get(ptr, n):
+            out = np.empty(n, dtype=np.uint8)
+            if n:
+                _chk(enc._h, enc._L.yk_device_download(enc._h, out.ctypes.data, C.c_void_p(ptr), n))
+            return out
+
+        return {"rgb": [get(p, n) for p, n in zip(self.rgb, self.rgb_bytes)], "pix": get(self.pix, self.pix_bytes), "type": get(self.type, self.type_bytes)}
+
+
+STREAMS_CORNERS, STREAMS_RANGE1D = 1, 2             # YK_STREAMS_* of include/yaik_hip.h
+
+
 class HipTileEncoder:
     """One handle = one GPU = one image or one row stripe of an image."""
 
@@ -352,6 +389,18 @@ class HipTileEncoder:
 
     def encode_batch(self, reject_factor: int = 3, mode3bit_only: bool = False):
         _chk(self._h, self._L.yk_encode_batch(self._h, reject_factor, int(mode3bit_only)))
+
+    def streams_batch(self, corners: bool = True, range1d: bool = True) -> list:
+        """The corner colour streams and / or the 1-D streams of EVERY frame of the handle (yk_encode_streams_batch + yk_batch_streams_table: one
+        launch per kernel and one read-back for the whole batch), after encode_batch() -- or, with one frame bound, after encode() / encode_frame().
+        Returns one FrameStreams per frame.  The streams lie packed in the encoder's HBM and are written on its stream: synchronize() (or a
+        stream hand-off) before another stream reads them; they stay valid until the next encode, set_image / set_batch or streams_batch.
+        select_frame and the single-image getters (gradient_corners, dynamic_tile_compressor) do not disturb them."""
+        what = (STREAMS_CORNERS if corners else 0) | (STREAMS_RANGE1D if range1d else 0)
+        _chk(self._h, self._L.yk_encode_streams_batch(self._h, what))
+        tab = (_FrameStreamsC * self.frames)()
+        _chk(self._h, self._L.yk_batch_streams_table(self._h, tab))
+        return [FrameStreams(list(t.bitmap), list(t.bitmapBytes), list(t.rgb), list(t.rgbBytes), t.pix, t.pixBytes, t.type, t.typeBytes, self) for t in tab]
 
     def order_fused_after(self, other: "HipTileEncoder"):
         """The next encode() of this handle starts its fused kernel after the fused kernel last launched on `other` has finished
