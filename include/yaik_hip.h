@@ -518,6 +518,47 @@ int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes /* nFrames */, 
                                  const uint8_t* const* devPayload, const size_t* payBytes, int noChunkAlpha);
 int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes);
 
+/* ---- round-trip quality (new): what the decode holds against a source image, both in HBM -----------------------------------------
+ * The codec is lossy; these calls say how lossy a round trip was without moving a pixel to the host.  One kernel reads the decoder's 8x8-tiled
+ * planes (and, with four channels, the decoded 'ALPM' plane) and the source where it lies, a second one folds the workgroups' records; per frame
+ * and channel k (0 = R, 1 = G, 2 = B, 3 = alpha): sse[k] = sum (dec - src)^2, sad[k] = sum |dec - src|, nDiff[k] = samples that differ,
+ * maxAbs[k] = max |dec - src|, over nSamples = w * h samples.  Integers only: the figures are exact and do not depend on summation order
+ * (PSNR = 10 log10(255^2 nSamples / sse) is the caller's one division).  Unused entries of the arrays are 0.
+ *   yk_decode_compare_device        the selected frame (or the single image) against 8-bit pixels;
+ *   yk_decode_compare_batch_device  every frame of the batch, frame f's source at devSrc + f * frameBytes; out[nFrames];
+ *   yk_decode_compare_planes_device every frame against int32 planes as the encoder binds them (yk_bind_device_planes / yk_bind_device_batch:
+ *                                   plane k of frame f at frame0Planes[k] + f * frameStrideElems, row pitch strideElems; the low byte of a
+ *                                   sample is taken, as the fused kernel does); out[nFrames].
+ * 8-bit sources: planeBytes == 0 is HWC, sample (x, y, k) at devSrc[y * rowBytes + x * srcChannels + k], srcChannels = 3 or 4; otherwise CHW, at
+ * devSrc[k * planeBytes + y * rowBytes + x] (srcChannels only has to be 3 or 4 and >= channels).  Any base address and pitch is accepted.
+ * channels = 3 compares R, G, B (the 4th byte of an RGBA source is skipped); 4 also compares alpha against the plane yk_decode_alpha left (single
+ * image) or the planes of yk_decode_alpha_batch_device.
+ * devTileSse (may be NULL): device memory for one uint32 per 8x8 tile, the SSE over the compared channels; row-major (w / 8) x (h / 8), frame f at
+ * f * (w / 8) * (h / 8) elements.  8x8 is the decoder's tile and the range quantiser's, so the map shows which tiles an encoder setting hurt.
+ * Exactly those elements are written; the map stays in HBM and is complete when the call returns.
+ * The calls first zero what no chunk has written yet, as the output calls do: they compare exactly what yk_decode_output[_batch]_device would
+ * write.  The statistics come back to the host: ONE blocking read-back per call, whatever nFrames is (two launches; the records buffer belongs
+ * to the handle and only grows).  ORDERING is the caller's, as for the yk_decode_*_device entry points: the source is read and the map written on
+ * THIS handle's stream, and nothing orders that stream behind the producer's (yk_stream_wait_for(c, producerStream) or a host fence first).
+ * Timed as one YK_STAGE_DEC_COMPARE interval per call.
+ * A refusal launches nothing, writes nothing to out or the map, leaves the handle usable and sets yk_last_error: YK_ERR_BAD_ARG for a NULL
+ * devSrc, out or needed plane pointer, channels other than 3 / 4, srcChannels other than 3 / 4 or < channels, rowBytes < w * srcChannels (HWC) or
+ * rowBytes < w / planeBytes < rowBytes * h (CHW), frameBytes < rowBytes * h (HWC) or < planeBytes * channels (CHW) with more than one frame,
+ * strideElems < w; YK_ERR_STATE before yk_decode_begin[_batch], and for channels = 4 without valid alpha planes. */
+typedef struct yk_quality {
+    uint64_t sse[4], sad[4], nDiff[4];
+    uint32_t maxAbs[4];
+    uint64_t nSamples;          /* w * h */
+} yk_quality;
+int yk_decode_compare_device(yk_ctx* c, const uint8_t* devSrc, size_t rowBytes, size_t planeBytes,
+                             int srcChannels, int channels, yk_quality* out, uint32_t* devTileSse);
+int yk_decode_compare_batch_device(yk_ctx* c, const uint8_t* devSrc, size_t rowBytes, size_t planeBytes,
+                                   size_t frameBytes, int srcChannels, int channels,
+                                   yk_quality* out, uint32_t* devTileSse);
+int yk_decode_compare_planes_device(yk_ctx* c, const int32_t* const frame0Planes[4], int strideElems,
+                                    size_t frameStrideElems, int channels,
+                                    yk_quality* out, uint32_t* devTileSse);
+
 /* ---- timing hooks for bench.py: HIP events on the handle's stream around every alpha stage / fused kernel / compaction.
  * Returns the averages over the yk_encode_tiles calls since the previous query (a ring of 64 event sets, older ones are
  * dropped), so a caller can queue many frames back to back and read the per-kernel times once, without a sync per frame.
@@ -533,7 +574,8 @@ enum { YK_STAGE_CORNERS = 0,       /* yk_gradient_corners: lattice clear + owner
        YK_STAGE_DEC_1D = 4,        /* yk_decode_1d: count / scans / yk_dec1d_kernel */
        YK_STAGE_DEC_DETILE = 5,    /* yk_decode_output / _alpha / _reference_rgba / yk_decode_output_device: yk_dec_detile_kernel */
        YK_STAGE_LUT3D = 6,         /* yk_lut_search: yk_lut_search_kernel (one interval per tile shape) */
-       YK_STAGE_UNPACK = 7 };      /* yk_upload_pixels_u8 / yk_load_device_pixels_u8: yk_unpack_u8_kernel (the host copy is outside the interval) */
+       YK_STAGE_UNPACK = 7,        /* yk_upload_pixels_u8 / yk_load_device_pixels_u8: yk_unpack_u8_kernel (the host copy is outside the interval) */
+       YK_STAGE_DEC_COMPARE = 8 }; /* yk_decode_compare_*: yk_quality_compare_kernel + yk_quality_fold_kernel (the read-back is outside the interval) */
 int yk_stage_ms(yk_ctx* c, int stage, float* msSum, int* intervals);
 
 /* ---- diagnostics: the MEASURED HBM roof of this device (roofline fractions are quoted against the 8 TB/s specification

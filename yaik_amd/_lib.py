@@ -140,6 +140,9 @@ SIGNATURES = {
     "yk_decode_output_batch_device": (C.c_int, [vp, vp, sz, sz, sz, C.c_int, C.c_int]),
     "yk_decode_alpha_batch_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_int]),
     "yk_decode_output_batch_alpha_device": (C.c_int, [vp, vp, sz, sz, sz]),
+    "yk_decode_compare_device": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_int, vp, vp]),
+    "yk_decode_compare_batch_device": (C.c_int, [vp, vp, sz, sz, sz, C.c_int, C.c_int, vp, vp]),
+    "yk_decode_compare_planes_device": (C.c_int, [vp, C.POINTER(vp), C.c_int, sz, C.c_int, vp, vp]),
     "yk_decode_gradient_planes": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, sz]),
     "yk_decode_split_masks": (C.c_int, [vp]),
     "yk_decode_assign_lut": (C.c_int, [vp, vp, sz]),

@@ -12,7 +12,7 @@
 #define YK_LROWS    65
 #define YK_EV_RING  64
 #define YK_SLOT     32      // bytes of nibble slot per 8x8 tile-plane (64 nibbles)
-#define YK_NUM_STAGES 8     // YK_STAGE_* of include/yaik_hip.h
+#define YK_NUM_STAGES 9     // YK_STAGE_* of include/yaik_hip.h
 #define YK_STAGE_RING 16
 
 // Batches: one handle can hold nFrames images of one shape; every per-image array is allocated nFrames times back to back and
@@ -177,6 +177,8 @@ struct yk_ctx {
     struct DStrides { size_t planes, mapRGB, owner, loaded, tile4; } dStride = {};
     // the per-frame tables of the batch calls on their way to HBM: a ring of pinned host buffers, each with the event behind its copy
     void* dTabHost[4] = {}; size_t dTabHostBytes[4] = {}; hipEvent_t dTabEv[4] = {}; unsigned dTabSeq = 0;
+    // yk_decode_compare_*: the folded u64 results of every frame, then one record per workgroup (grow-only; yk_quality.hip)
+    uint8_t* qBuf = nullptr; size_t qBufBytes = 0;
     // timing
     // timing events: a ring of YK_EV_RING sets {alpha begin, alpha end, encode begin, encode end, pack end} so that a caller can
     // run many frames back to back and read the per-kernel averages afterwards without synchronising every frame
@@ -232,6 +234,14 @@ int yk_corners_finish(yk_ctx* c);                         // reads the corner st
 extern "C" int yk_dec_table_host(yk_ctx* c, size_t bytes, int* slot, void** host);
 extern "C" int yk_dec_table_upload(yk_ctx* c, int slot, void* dev, size_t bytes);
 inline const uint8_t* yk_dec_alpha_cur(const yk_ctx* c) { return c->dAlpha + (c->dAlphaBatch ? (size_t)c->dCur * c->dAlphaStride : 0); }
+// yk_decode_compare_* (yk_quality.hip): the source of a comparison -- u8 pixels (planes == nullptr; CHW when planeBytes > 0) or int32 planes --
+// and the two launches + one read-back over frames [firstFrame, firstFrame + nFrames) of the decode batch; the caller has validated and settled
+struct YkQualitySrc {
+    const uint8_t* src; size_t rowBytes, planeBytes; int srcChannels;
+    const int32_t* const* planes; size_t strideElems;
+    size_t frameStride;                                   // bytes (u8) or elements (int32) from one frame's source to the next
+};
+int yk_quality_compare(yk_ctx* c, const YkQualitySrc& q, int firstFrame, int nFrames, int channels, yk_quality* out, uint32_t* devTileSse);
 void yk_dec_free(yk_ctx* c);                              // frees the decode buffers of every frame and the batch tables' host ring (yk_decode.hip)
 void yk_lut_dec_destroy(yk_ctx* c);
 void yk_lut_destroy(yk_ctx* c);                          // frees the 3-D LUT bank and streams (yk_lut3d.hip)

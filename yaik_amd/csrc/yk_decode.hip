@@ -1608,6 +1608,58 @@ int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBy
     return yk_dec_detile(c, devOut, rowBytes, planeBytes, 4, c->dAlpha, w, 0, c->dFrames, frameBytes, c->dAlphaStride);
 }
 
+// ---- round-trip quality: the decode against a source in HBM (kernels and the read-back: yk_quality.hip) ----
+// the checks the three entry points share; batch: every frame (else the selected one)
+static int yk_dec_compare_common(yk_ctx* c, int channels, const void* out, bool batch) {
+    if (!out) return yk_refuse(c, YK_ERR_BAD_ARG, "out is NULL");
+    if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
+    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
+    if (channels == 4 && !c->dAlphaValid)
+        return yk_refuse(c, YK_ERR_STATE, "channels = 4 needs the decoded alpha: yk_decode_alpha or yk_decode_alpha_batch_device first");
+    return YK_OK;
+}
+static int yk_dec_compare_u8(yk_ctx* c, const uint8_t* devSrc, size_t rowBytes, size_t planeBytes, size_t frameBytes, int srcChannels, int channels,
+                             yk_quality* out, uint32_t* devTileSse, bool batch) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!devSrc) return yk_refuse(c, YK_ERR_BAD_ARG, "devSrc is NULL");
+    { const int rc = yk_dec_compare_common(c, channels, out, batch); if (rc) return rc; }
+    if ((srcChannels != 3 && srcChannels != 4) || srcChannels < channels)
+        return yk_refuse(c, YK_ERR_BAD_ARG, "srcChannels must be 3 or 4 and at least channels");
+    const size_t w = (size_t)c->dw, h = (size_t)c->dh;
+    if (planeBytes == 0 ? rowBytes / (size_t)srcChannels < w : (rowBytes < w || planeBytes / h < rowBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "row or plane pitch too small for the image");
+    const int nFrames = batch ? c->dFrames : 1;
+    if (nFrames > 1 && (planeBytes == 0 ? frameBytes / h < rowBytes : frameBytes / (size_t)channels < planeBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "frame stride too small for a frame");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    const YkQualitySrc q = { devSrc, rowBytes, planeBytes, srcChannels, nullptr, 0, nFrames > 1 ? frameBytes : 0 };
+    return yk_quality_compare(c, q, batch ? 0 : c->dCur, nFrames, channels, out, devTileSse);
+}
+
+int yk_decode_compare_device(yk_ctx* c, const uint8_t* devSrc, size_t rowBytes, size_t planeBytes, int srcChannels, int channels, yk_quality* out,
+                             uint32_t* devTileSse) {
+    return yk_dec_compare_u8(c, devSrc, rowBytes, planeBytes, 0, srcChannels, channels, out, devTileSse, false);
+}
+
+int yk_decode_compare_batch_device(yk_ctx* c, const uint8_t* devSrc, size_t rowBytes, size_t planeBytes, size_t frameBytes, int srcChannels, int channels,
+                                   yk_quality* out, uint32_t* devTileSse) {
+    return yk_dec_compare_u8(c, devSrc, rowBytes, planeBytes, frameBytes, srcChannels, channels, out, devTileSse, true);
+}
+
+int yk_decode_compare_planes_device(yk_ctx* c, const int32_t* const frame0Planes[4], int strideElems, size_t frameStrideElems, int channels, yk_quality* out,
+                                    uint32_t* devTileSse) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!frame0Planes) return yk_refuse(c, YK_ERR_BAD_ARG, "frame0Planes is NULL");
+    { const int rc = yk_dec_compare_common(c, channels, out, true); if (rc) return rc; }
+    for (int k = 0; k < channels; k++) if (!frame0Planes[k]) return yk_refuse(c, YK_ERR_BAD_ARG, "a plane the comparison needs is NULL");
+    if (strideElems < c->dw) return yk_refuse(c, YK_ERR_BAD_ARG, "strideElems is smaller than the width");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    const YkQualitySrc q = { nullptr, 0, 0, 0, frame0Planes, (size_t)strideElems, c->dFrames > 1 ? frameStrideElems : 0 };
+    return yk_quality_compare(c, q, 0, c->dFrames, channels, out, devTileSse);
+}
+
 const uint8_t* yk_decode_planes_device(yk_ctx* c, size_t* planeSize) {
     if (!c || !c->dPlanes) return nullptr;
     if (hipSetDevice(c->device) != hipSuccess || yk_dec_settle(c) != YK_OK) return nullptr;

@@ -124,7 +124,7 @@ class HipTileDecoder:
 
     def begin(self, w: int, h: int):
         self.w, self.h, self.frames = w, h, 1
-        self._has_alpha = False
+        self._has_alpha = self._alpha_batch = False
         _chk(self._h, lib().yk_decode_begin(self._h, w, h))
 
     # ---- batches: n images of one shape, every kernel launched once over all of them (yk_decode_begin_batch) --------------------------------
@@ -133,7 +133,7 @@ class HipTileDecoder:
         tile4x4, image, image_device) then act on the frame select_frame chose (0 after begin_batch); begin() goes back to one image."""
         _chk(self._h, lib().yk_decode_begin_batch(self._h, w, h, n))
         self.w, self.h, self.frames = w, h, n
-        self._has_alpha = False
+        self._has_alpha = self._alpha_batch = False
 
     def select_frame(self, f: int):
         _chk(self._h, lib().yk_decode_select_frame(self._h, f))
@@ -510,6 +510,109 @@ class HipTileDecoder:
         _chk(self._h, L.yk_decode_output_device(self._h, out.data_ptr(), row_bytes, plane_bytes, C4, a))
         _chk(self._h, L.yk_stream_handoff(self._h, cur))
         return out
+
+    # ---- round-trip quality: the decode against a source that is already on the device (yk_decode_compare_*) --------------------------------
+    def _compare_channels(self, channels, src_channels: int) -> int:
+        if channels is None:
+            return 4 if src_channels == 4 and (self._has_alpha or self._alpha_batch) else 3
+        return int(channels)
+
+    def _compare_tile_map(self, tile_map, n: int):
+        """tile_map: False / None (no map), True (a new tensor) or a contiguous torch int32 tensor [n, h/8, w/8] on the device to write into"""
+        import torch
+        if tile_map is None or tile_map is False:
+            return None
+        dev, shape = torch.device("cuda", self.device), (n, self.h // 8, self.w // 8)
+        if tile_map is True:
+            return torch.empty(shape, dtype=torch.int32, device=dev)
+        if not isinstance(tile_map, torch.Tensor) or tile_map.device != dev or tile_map.dtype not in (torch.int32, torch.uint32) \
+                or tuple(tile_map.shape) != shape or not tile_map.is_contiguous():
+            raise ValueError(f"tile_map must be True or a contiguous int32 tensor {shape} on {dev}")
+        return tile_map
+
+    def _compare_on_device(self, t, what: str):
+        """the source's address goes to a kernel: anything but a torch tensor on the handle's device is refused here, before any library call"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(t, torch.Tensor) or t.device != dev:
+            raise ValueError(f"{what} must be a torch tensor on {dev}, got {getattr(t, 'device', type(t).__name__)}")
+
+    def _compare_call(self, fn, args, n: int, channels: int, tmap) -> list:
+        """the library call behind the stream hand-over, and its n structs as dicts"""
+        import torch
+        from .quality import YkQuality, quality_dict
+        out = (YkQuality * n)()
+        cur = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        _chk(self._h, lib().yk_stream_wait_for(self._h, cur))              # torch may have just written the source or allocated the map
+        _chk(self._h, fn(self._h, *args, channels, out, tmap.data_ptr() if tmap is not None else None))
+        res = [quality_dict(q, channels) for q in out]                      # the call has synchronised: the map is complete as well
+        if tmap is not None:
+            for f, r in enumerate(res):
+                r["tile_sse"] = tmap[f]
+        return res
+
+    def compare_device(self, src, channels: int | None = None, planar: bool = False, tile_map=False) -> dict:
+        """The decoded image -- or the selected frame of a batch -- against 8-bit source pixels in a torch.uint8 tensor on the handle's device,
+        without moving a pixel to the host (yk_decode_compare_device): src is [h, w, C] (C = 3 or 4), or [C, h, w] with planar=True, any view with
+        unit inner stride and any pitch or offset.  channels = 3 compares R, G, B (the 4th byte of an RGBA source is skipped), 4 also compares
+        alpha against the decoded 'ALPM' plane; the default is 4 when the source has four channels and an alpha plane was decoded, else 3.
+        Returns a dict of exact integers per channel -- sse, sad, n_diff, max_abs -- with psnr_db per channel and psnr_db_all over all compared
+        samples (yaik_amd.quality).  tile_map=True adds tile_sse: an int32 tensor [h/8, w/8] on the device, the SSE of every 8x8 tile over the
+        compared channels (or pass an int32 tensor [1, h/8, w/8] to write into).  What is compared is exactly what image_device() would write."""
+        self._compare_on_device(src, "src")
+        if planar:
+            lay = u8_planar_layout(src)
+            shape, row_bytes, plane_bytes = (lay.rows, lay.w), lay.row_bytes, lay.plane_bytes
+        else:
+            lay = u8_pixel_layout(src)
+            shape, row_bytes, plane_bytes = (lay.rows, lay.w), lay.row_bytes, 0
+        if shape != (self.h, self.w):
+            raise ValueError(f"src is {shape[1]} x {shape[0]}, the image {self.w} x {self.h}")
+        ch = self._compare_channels(channels, lay.channels)
+        tmap = self._compare_tile_map(tile_map, 1)
+        return self._compare_call(lib().yk_decode_compare_device, (src.data_ptr(), row_bytes, plane_bytes, lay.channels), 1, ch, tmap)[0]
+
+    def compare_batch_device(self, src, channels: int | None = None, planar: bool = False, tile_map=False) -> list:
+        """Every frame of the batch against its source in one call (yk_decode_compare_batch_device: two launches and one read-back whatever the
+        frame count): src is [N, h, w, C], or [N, C, h, w] with planar=True, with any row, plane and frame pitch.  Returns one dict per frame as
+        compare_device does; with tile_map=True (or an int32 tensor [N, h/8, w/8] to write into) frame f's dict holds tile_sse = map[f]."""
+        self._compare_on_device(src, "src")
+        if planar:
+            lay = u8_planar_batch_layout(src)
+            plane_bytes = lay.plane_bytes
+        else:
+            lay = u8_pixel_layout(src, batch=True)
+            plane_bytes = 0
+        if (lay.frames, lay.rows, lay.w) != (self.frames, self.h, self.w):
+            raise ValueError(f"src holds {lay.frames} frames of {lay.w} x {lay.rows}, the batch {self.frames} of {self.w} x {self.h}")
+        ch = self._compare_channels(channels, lay.channels)
+        tmap = self._compare_tile_map(tile_map, self.frames)
+        return self._compare_call(lib().yk_decode_compare_batch_device, (src.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, lay.channels),
+                                  self.frames, ch, tmap)
+
+    def compare_planes(self, planes, channels: int | None = None, tile_map=False):
+        """Every frame against int32 planes as the encoder binds them (yk_decode_compare_planes_device): a torch int32 tensor [P, h, w] on the
+        device for a single image (returns a dict) or [N, P, h, w] for the batch (returns a list), P >= channels, unit inner stride and any row,
+        plane and frame stride; the low byte of a sample is compared.  channels defaults to 4 when P == 4 and an alpha plane was decoded."""
+        import torch
+        self._compare_on_device(planes, "planes")
+        if planes.dtype != torch.int32 or planes.dim() not in (3, 4):
+            raise ValueError("planes must be a torch int32 tensor [P, h, w] or [N, P, h, w]")
+        single = planes.dim() == 3
+        p4 = planes[None] if single else planes
+        n, P, h, w = p4.shape
+        if (n, h, w) != (self.frames, self.h, self.w) or P not in (3, 4):
+            raise ValueError(f"planes hold {n} frames of {P} planes of {w} x {h}; the decode holds {self.frames} frames of {self.w} x {self.h}")
+        sf, sp, sr, sx = p4.stride()
+        if sx != 1 or sr < w:
+            raise ValueError(f"the samples of a row must be contiguous and rows may not overlap; got strides {tuple(planes.stride())}")
+        ch = self._compare_channels(channels, P)
+        if ch > P:
+            raise ValueError(f"{ch} channels cannot be compared with {P} planes")
+        tmap = self._compare_tile_map(tile_map, n)
+        ptrs = (C.c_void_p * 4)(*[p4.data_ptr() + k * sp * 4 if k < P else None for k in range(4)])
+        res = self._compare_call(lib().yk_decode_compare_planes_device, (ptrs, sr, sf if n > 1 else 0), n, ch, tmap)
+        return res[0] if single else res
 
     def synchronize(self):
         _chk(self._h, lib().yk_synchronize(self._h))
