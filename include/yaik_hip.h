@@ -199,6 +199,39 @@ typedef struct yk_frame_streams {
 int yk_encode_streams_batch(yk_ctx* c, int what);
 int yk_batch_streams_table(yk_ctx* c, yk_frame_streams* out /* nFrames */);
 
+/* ---- PaletteCompressor on the GPU (new): the 'GTIL' colour payloads, byte-exact ---------------------------------------------------------
+ * EncoderContext.cpp:3259-3502 (registerCodeBook :3231, FindCodeBook :3248): the delta / code-book coder the corner colour streams pass through
+ * before ZStd.  Its output for a stream depends on the streams coded before it: FindCodeBook scans rows 0..63 of a table whose rows survive from
+ * call to call, so the state that carries is exactly 64 rows (all (0,0,0) in a fresh process).  The handle keeps those rows in HBM.
+ *   yk_palette_reset             forgets the carried rows: the next continuing call behaves like the first call of a fresh process.
+ *   yk_palette_compress_streams  nStreams (1..65536) streams anywhere in the device's memory, nBytes[i] each a multiple of 3 (a colour is 3 bytes).
+ *                                chain = K > 0: every run of K consecutive streams starts from the fresh rows and carries them through the run
+ *                                (K = 7: one frame per run); the handle's carried rows are neither read nor written.  chain = 0: the streams
+ *                                continue from the handle's carried rows, in order, and leave theirs behind.  A stream of length 0 is skipped and
+ *                                leaves the rows alone, like a pass without a chunk; its payload is empty.
+ *   yk_palette_compress          the seven corner streams of the selected frame (built first if needed, as by yk_gradient_corners_device), with
+ *                                chain = 0.  Whole images; not after a plane-subset pass.
+ *   yk_palette_compress_batch    the 7 x nFrames corner streams of a valid yk_encode_streams_batch table built with YK_STREAMS_CORNERS, chain = 7:
+ *                                every frame like one image of a fresh process.  Does not touch the carried rows.
+ * A call is eight kernel launches and two clears over all its streams, whatever their number, and ONE blocking read-back at its end (8 bytes per
+ * stream: payload length and offset).  The payloads lie packed in one grow-only buffer of the handle, each at a multiple of 16.
+ *   yk_palette_payload_device    payload `index` (the stream's number in the last call; frame * 7 + pass after the batch call) where it lies in HBM
+ *                                and its length, which is what the chunk header's streamRGBSizeCustomCompressor holds; NULL / 0 for a skipped stream.
+ *   yk_palette_payload           the same copied to the host (hostOut may be NULL: size query); synchronises.
+ * The payloads stay valid under the rule of the streams table: until the next encode, yk_set_image, yk_set_batch, (re)bind or upload of planes or
+ * pixels, yk_encode_streams_batch or yk_palette_compress* of the handle.  The input streams are read on the handle's stream: ORDERING against
+ * their producer is the caller's, as for the yk_decode_*_device entry points.  Timed as one YK_STAGE_PALETTE interval per call.
+ * Refusals launch nothing, leave earlier payloads, the carried rows and the handle usable, and set yk_last_error: YK_ERR_BAD_ARG for a NULL table,
+ * nStreams outside 1..65536, chain < 0, a length that is not a multiple of 3 (plane-subset streams stay with the host coder), a length with a
+ * NULL pointer, more than 2^28 colours in one call, a payload index out of range; YK_ERR_STATE on a stripe, before an encode, after a
+ * plane-subset pass, without a valid table with corner streams (batch), and for the getters before any call; YK_ERR_RANGE for a short buffer. */
+int yk_palette_reset(yk_ctx* c);
+int yk_palette_compress_streams(yk_ctx* c, const uint8_t* const* devStreams, const size_t* nBytes, int nStreams, int chain);
+int yk_palette_compress(yk_ctx* c);
+int yk_palette_compress_batch(yk_ctx* c);
+int yk_palette_payload_device(yk_ctx* c, int index, const uint8_t** dev, size_t* nBytes);
+int yk_palette_payload(yk_ctx* c, int index, uint8_t* hostOut, size_t cap, size_t* nBytes);
+
 /* ---- streams of frames on several handles (new) --------------------------------------------------------------------------
  * With two handles (two streams) in flight the HBM-bound alpha / compaction kernels of one frame run under the fused kernel of
  * the other.  Two fused kernels sharing the chip only slow each other down, so a caller that alternates handles can order them:
@@ -575,7 +608,8 @@ enum { YK_STAGE_CORNERS = 0,       /* yk_gradient_corners: lattice clear + owner
        YK_STAGE_DEC_DETILE = 5,    /* yk_decode_output / _alpha / _reference_rgba / yk_decode_output_device: yk_dec_detile_kernel */
        YK_STAGE_LUT3D = 6,         /* yk_lut_search: yk_lut_search_kernel (one interval per tile shape) */
        YK_STAGE_UNPACK = 7,        /* yk_upload_pixels_u8 / yk_load_device_pixels_u8: yk_unpack_u8_kernel (the host copy is outside the interval) */
-       YK_STAGE_DEC_COMPARE = 8 }; /* yk_decode_compare_*: yk_quality_compare_kernel + yk_quality_fold_kernel (the read-back is outside the interval) */
+       YK_STAGE_DEC_COMPARE = 8,   /* yk_decode_compare_*: yk_quality_compare_kernel + yk_quality_fold_kernel (the read-back is outside the interval) */
+       YK_STAGE_PALETTE = 9 };     /* yk_palette_compress*: the clears and the eight yk_pal_*_kernel launches of a call (the read-back is outside the interval) */
 int yk_stage_ms(yk_ctx* c, int stage, float* msSum, int* intervals);
 
 /* ---- diagnostics: the MEASURED HBM roof of this device (roofline fractions are quoted against the 8 TB/s specification

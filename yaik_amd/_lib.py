@@ -64,6 +64,12 @@ SIGNATURES = {
     "yk_select_frame": (C.c_int, [vp, C.c_int]),
     "yk_encode_streams_batch": (C.c_int, [vp, C.c_int]),
     "yk_batch_streams_table": (C.c_int, [vp, vp]),
+    "yk_palette_reset": (C.c_int, [vp]),
+    "yk_palette_compress_streams": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
+    "yk_palette_compress": (C.c_int, [vp]),
+    "yk_palette_compress_batch": (C.c_int, [vp]),
+    "yk_palette_payload_device": (C.c_int, [vp, C.c_int, C.POINTER(vp), szp]),
+    "yk_palette_payload": (C.c_int, [vp, C.c_int, vp, sz, szp]),
     "yk_order_fused_after": (C.c_int, [vp, vp]),
     "yk_gradient_bitmap_bytes": (sz, [vp, C.c_int]),
     "yk_gradient_bitmap": (C.c_int, [vp, C.c_int, vp, sz]),

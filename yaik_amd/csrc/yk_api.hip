@@ -53,7 +53,7 @@ static void yk_free_image(yk_ctx* c) {
     F(c->pixCache); c->pixCacheValid = false;
     yk_sb_free(c);
     if (c->frameGraph) { (void)hipGraphExecDestroy(c->frameGraph); c->frameGraph = nullptr; }
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
 }
 
 // allocates every per-image array c->nFrames times (geometry fields are set) and points the handle at frame 0
@@ -208,6 +208,7 @@ void yk_destroy(yk_ctx* c) {
     yk_lut_dec_destroy(c);
     auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
     yk_dec_free(c);
+    yk_pal_free(c);
     F(c->ownedPlanes); F(c->pxStage); F(c->dScratch); F(c->dAlpha); F(c->dAvScratch); F(c->avState); F(c->avPay); F(c->av6); F(c->avTab); F(c->qBuf);
     for (int r = 0; r < YK_EV_RING; r++) for (int i = 0; i < 5; i++) if (c->evRing[r][i]) (void)hipEventDestroy(c->evRing[r][i]);
     for (int st = 0; st < YK_NUM_STAGES; st++) for (int k = 0; k < YK_STAGE_RING; k++) for (int i = 0; i < 2; i++) if (c->stEv[st][k][i]) (void)hipEventDestroy(c->stEv[st][k][i]);
@@ -255,7 +256,7 @@ int yk_set_image(yk_ctx* c, int fullW, int fullH, int nPlanes, int y0, int h, in
     YK_HIP(c, hipSetDevice(c->device));
     c->fusedAfter = nullptr;                                                 // an ordering request never outlives the image it was made for
     if (c->fullW == fullW && c->fullH == fullH && c->nPlanes == nPlanes && c->y0 == y0 && c->h == h && c->halo == haloRows && c->tileCount) {
-        c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+        c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
         return YK_OK;
     }
     YK_HIP(c, hipStreamSynchronize(c->stream));
@@ -273,7 +274,7 @@ int yk_set_batch(yk_ctx* c, int nFrames) {
     if (nFrames < 1 || nFrames > 1024) return yk_fail(c, YK_ERR_BAD_ARG, "nFrames must be 1..1024");
     if (c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "batches hold whole images, not stripes");
     YK_HIP(c, hipSetDevice(c->device));
-    c->sb.valid = false;                                                     // as documented: also when the frame count stays
+    c->sb.valid = false; c->pal.valid = false;                                                     // as documented: also when the frame count stays
     if (nFrames != c->nFrames) {
         YK_HIP(c, hipStreamSynchronize(c->stream));
         const int32_t* keepPlanes[4] = { c->B.plane[0], c->B.plane[1], c->B.plane[2], c->B.plane[3] };
@@ -363,7 +364,7 @@ int yk_upload_planes(yk_ctx* c, const int32_t* const hostPlanes[4], int strideEl
     }
     c->fs.plane = 0; yk_rebase(c, 0);
     c->strideElems = c->fullW;
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
     // the 0..255 precondition is enforced where the boundary hands over host planes (a streaming pass over what was just copied: ~0.2 ms next to
     // ~48 ms of PCIe copy for an 8192 x 8192 RGBA image); callers that bind device memory check with yk_validate_planes when they cannot vouch for it
     size_t bad = 0;
@@ -386,7 +387,7 @@ int yk_bind_device_planes(yk_ctx* c, const int32_t* const devPlanes[4], int stri
     }
     c->fs.plane = 0; yk_rebase(c, 0);
     c->strideElems = strideElems;
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
     return YK_OK;
 }
 
@@ -400,7 +401,7 @@ int yk_bind_device_batch(yk_ctx* c, const int32_t* const frame0Planes[4], int st
     }
     c->fs.plane = frameStrideElems; yk_rebase(c, c->curFrame < c->nFrames ? c->curFrame : 0);
     c->strideElems = strideElems;
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
     return YK_OK;
 }
 
@@ -431,7 +432,7 @@ static void yk_bind_owned(yk_ctx* c, size_t planeElems, size_t frameElems) {
     c->fs.plane = c->nFrames > 1 ? frameElems : 0;
     yk_rebase(c, c->curFrame < c->nFrames ? c->curFrame : 0);
     c->strideElems = c->fullW;
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
 }
 
 static int yk_upload_pixels_run(yk_ctx* c, const uint8_t* hostPixels, size_t rowBytes, int channels) {
@@ -616,7 +617,7 @@ int yk_encode_tiles(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst) 
     c->evAlphaInCur = false;
     c->evHead++;
     if (c->evHead - c->evTail > YK_EV_RING) c->evTail = c->evHead - YK_EV_RING;       // the oldest sets were overwritten
-    c->encoded = true; c->dstValid = wantDst != 0; c->sb.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
+    c->encoded = true; c->dstValid = wantDst != 0; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
     return YK_OK;
 }
 
@@ -661,7 +662,7 @@ int yk_encode_batch(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
     c->evAlphaInCur = false; c->evHead++;
     if (c->evHead - c->evTail > YK_EV_RING) c->evTail = c->evHead - YK_EV_RING;
     c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false;
-    c->encoded = true; c->dstValid = false; c->sb.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
+    c->encoded = true; c->dstValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
     return YK_OK;
 }
 
@@ -699,7 +700,7 @@ int yk_encode_frame(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
     c->evAlphaInCur = false; c->evHead++;
     if (c->evHead - c->evTail > YK_EV_RING) c->evTail = c->evHead - YK_EV_RING;
     c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false;
-    c->encoded = true; c->dstValid = false; c->sb.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
+    c->encoded = true; c->dstValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
     return YK_OK;
 }
 

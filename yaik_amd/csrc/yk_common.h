@@ -12,7 +12,7 @@
 #define YK_LROWS    65
 #define YK_EV_RING  64
 #define YK_SLOT     32      // bytes of nibble slot per 8x8 tile-plane (64 nibbles)
-#define YK_NUM_STAGES 9     // YK_STAGE_* of include/yaik_hip.h
+#define YK_NUM_STAGES 10    // YK_STAGE_* of include/yaik_hip.h
 #define YK_STAGE_RING 16
 
 // Batches: one handle can hold nFrames images of one shape; every per-image array is allocated nFrames times back to back and
@@ -72,6 +72,18 @@ struct YkStreamsBatch {
     uint8_t* out = nullptr; size_t outCap = 0;                   // every stream of every frame, each on a multiple of 16
     uint8_t* tab = nullptr; size_t tabCap = 0;                   // [F] YkStreamRec
     std::vector<yk_frame_streams> table; bool valid = false;     // what yk_batch_streams_table hands out
+    int what = 0;                                                // the YK_STREAMS_* the valid table was built with
+};
+
+// yk_palette_compress* (yk_palette.hip): PaletteCompressor over a list of segments.  Everything is grow-only and belongs to the handle.
+struct YkPalette {
+    uint8_t* scratch = nullptr; size_t scratchCap = 0;           // segment table, vote tables, candidates, books, tokens, offsets, lengths
+    uint8_t* out = nullptr; size_t outCap = 0;                   // the payloads of the last call, each on a multiple of 16
+    uint32_t* carry = nullptr;                                   // the 64 find-table rows that carry from call to call (packed deltas)
+    bool carryFresh = true;                                      // the carried rows are those of a fresh process (all zero deltas)
+    std::vector<uint8_t> segHost;                                // the segment table on its way to HBM
+    std::vector<uint32_t> lenBase;                               // read back: [nSeg] payload lengths, [nSeg] payload offsets in `out`
+    int nSeg = 0; bool valid = false;
 };
 
 // The layout of yk_ctx must NOT depend on YK_TEST_HOOKS: the product library and the test-hooks build of the same sources are loaded side by
@@ -197,6 +209,7 @@ struct yk_ctx {
     unsigned long long frameGraphKey[12] = {};
     int kernelVersion = 2;              // 2 = yk_encode2_kernel; 1 = the registered cross-check launcher (tests/csrc/yk_encode_v1.hip)
     YkStreamsBatch sb;                  // yk_encode_streams_batch
+    YkPalette pal;                      // yk_palette_compress*
 };
 
 int yk_fail(yk_ctx* c, int code, const char* what, hipError_t e = hipSuccess);
@@ -229,6 +242,7 @@ inline int yk_sb_grow(yk_ctx* c, uint32_t** p, size_t* capElems, size_t needElem
     size_t cap = *capElems * 4; const int rc = yk_sb_grow_bytes(c, reinterpret_cast<void**>(p), &cap, needElems * 4); *capElems = cap / 4; return rc;
 }
 void yk_sb_free(yk_ctx* c);
+void yk_pal_free(yk_ctx* c);                              // frees the palette coder's buffers (yk_palette.hip); the carried rows become fresh
 int yk_corners_finish(yk_ctx* c);                         // reads the corner streams' lengths back if that is still pending (synchronises)
 // the pinned ring behind the per-frame tables of the decode batch calls (yk_decode.hip)
 extern "C" int yk_dec_table_host(yk_ctx* c, size_t bytes, int* slot, void** host);

@@ -38,7 +38,7 @@ int yk_encode_streams_batch(yk_ctx* c, int what) {
     const int N = c->nFrames;
     const bool corners = (what & YK_STREAMS_CORNERS) != 0, r1 = (what & YK_STREAMS_RANGE1D) != 0;
     YkStreamsBatch& b = c->sb;
-    b.valid = false;
+    b.valid = false; c->pal.valid = false;
     { int rc = yk_sb_grow(c, &b.counts, &b.countsElems, (size_t)N * YK_SB_COUNTS); if (rc) return rc; }
     { void* p = b.tab; int rc = yk_sb_grow_bytes(c, &p, &b.tabCap, (size_t)N * sizeof(YkStreamRec)); b.tab = static_cast<uint8_t*>(p); if (rc) return rc; }
     // ---- count phase ----
@@ -96,7 +96,7 @@ int yk_encode_streams_batch(yk_ctx* c, int what) {
         { int rc = yk_range1d_batch_emit(c); if (rc) return rc; }
         { int rc = yk_stage_end(c, YK_STAGE_RANGE1D); if (rc) return rc; }
     }
-    b.valid = true;
+    b.valid = true; b.what = what;
     return YK_OK;
 }
 

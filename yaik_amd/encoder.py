@@ -402,6 +402,77 @@ class HipTileEncoder:
         _chk(self._h, self._L.yk_batch_streams_table(self._h, tab))
         return [FrameStreams(list(t.bitmap), list(t.bitmapBytes), list(t.rgb), list(t.rgbBytes), t.pix, t.pixBytes, t.type, t.typeBytes, self) for t in tab]
 
+    # ---- PaletteCompressor (EncoderContext.cpp:3259-3502) on the GPU: the 'GTIL' colour payloads -----------------
+    def palette_reset(self):
+        """Forgets the 64 code-book rows that carry from call to call (PaletteResetCodeBook: a fresh process)."""
+        _chk(self._h, self._L.yk_palette_reset(self._h))
+
+    def palette_compress(self) -> int:
+        """The seven corner streams of the selected frame through PaletteCompressor, continuing the handle's carried rows (yk_palette_compress),
+        after encode().  Returns the number of payloads (7); palette_payload(p) / palette_payload_device(p) hand them out."""
+        _chk(self._h, self._L.yk_palette_compress(self._h))
+        self._palette_n = 7
+        return 7
+
+    def palette_compress_batch(self) -> int:
+        """The corner streams of every frame after streams_batch(corners=True), every frame from a fresh book (yk_palette_compress_batch).
+        Payload frame * 7 + pass.  Returns the number of payloads."""
+        _chk(self._h, self._L.yk_palette_compress_batch(self._h))
+        self._palette_n = 7 * self.frames
+        return self._palette_n
+
+    def palette_compress_streams(self, tensors, chain: int = 0) -> int:
+        """PaletteCompressor over arbitrary colour streams in device memory: `tensors` is a sequence of 1-D contiguous uint8 CUDA tensors whose
+        lengths are multiples of 3 (length 0: skipped, the book stays).  chain = K > 0: every run of K consecutive streams starts from a fresh
+        book; chain = 0: the streams continue the handle's carried rows.  CPU tensors and bad chain values are refused before any library
+        call.  Returns the number of payloads."""
+        import torch
+        if isinstance(chain, bool) or not isinstance(chain, int) or chain < 0:
+            raise ValueError(f"chain must be an int >= 0 (0 = continue the carried book, K = run length); got {chain!r}")
+        tensors = list(tensors)
+        if not tensors:
+            raise ValueError("at least one stream is needed")
+        for i, t in enumerate(tensors):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"stream {i} is not a torch tensor")
+            if not t.is_cuda:
+                raise ValueError(f"stream {i} is a CPU tensor: the streams must lie in device memory")
+            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError(f"stream {i} must be a 1-D contiguous uint8 tensor")
+            if t.numel() % 3:
+                raise ValueError(f"stream {i} holds {t.numel()} bytes, not a multiple of 3")
+        n = len(tensors)
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in tensors])
+        lens = (C.c_size_t * n)(*[t.numel() for t in tensors])
+        torch.cuda.current_stream(tensors[0].device).synchronize()          # hand-over fence, see set_image
+        _chk(self._h, self._L.yk_palette_compress_streams(self._h, ptrs, lens, n, chain))
+        self._palette_keepalive = tensors
+        self._palette_n = n
+        return n
+
+    def palette_payload(self, i: int) -> np.ndarray:
+        """Payload i of the last palette_compress* call, copied to the host (synchronises)."""
+        n = C.c_size_t()
+        _chk(self._h, self._L.yk_palette_payload(self._h, i, None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        if out.size:
+            _chk(self._h, self._L.yk_palette_payload(self._h, i, out.ctypes.data, out.size, None))
+        return out
+
+    def palette_payload_device(self, i: int):
+        """Payload i where it lies in HBM, as a uint8 tensor view of the handle's buffer (written on the handle's stream; stale after the next
+        encode, set_image / set_batch, streams_batch or palette_compress*)."""
+        import torch
+        dev, n = C.c_void_p(), C.c_size_t()
+        _chk(self._h, self._L.yk_palette_payload_device(self._h, i, C.byref(dev), C.byref(n)))
+        if not n.value:
+            return torch.empty(0, dtype=torch.uint8, device="cuda")
+
+        class _View:                                                        # __cuda_array_interface__: a view, not a copy
+            __cuda_array_interface__ = {"shape": (int(n.value),), "typestr": "|u1", "data": (int(dev.value), False), "version": 2}
+
+        return torch.as_tensor(_View(), device="cuda")
+
     def order_fused_after(self, other: "HipTileEncoder"):
         """The next encode() of this handle starts its fused kernel after the fused kernel last launched on `other` has finished
         (device-side wait; see yk_order_fused_after)."""

@@ -348,6 +348,18 @@ void EncoderContext::GenerateDynamicTileChunk(u8* stream, int sizeStream) {
         fail(("GenerateDynamicTileChunk: " + e).c_str());
 }
 
+// the seven 'GTIL' colour payloads of the encoded frame from the GPU, from a reset book like a fresh process
+bool EncoderContext::devicePalettePayloads(std::vector<u8> pal[7]) {
+    if (yk_palette_reset(ctx) != YK_OK || yk_palette_compress(ctx) != YK_OK) return fail((std::string("yk_palette_compress: ") + yk_last_error(ctx)).c_str());
+    for (int i = 0; i < 7; i++) {
+        size_t n = 0;
+        if (yk_palette_payload(ctx, i, nullptr, 0, &n) != YK_OK) return fail("yk_palette_payload");
+        pal[i].resize(n);
+        if (n && yk_palette_payload(ctx, i, pal[i].data(), n, nullptr) != YK_OK) return fail("yk_palette_payload");
+    }
+    return true;
+}
+
 bool EncoderContext::ConvertHotPath(FILE* f) {
     if (!bound || !f) return fail("ConvertHotPath: SetImageToEncode and an open file first");
     FILE* saved = outFile; outFile = f; fileOutSize = 0; err.clear();
@@ -357,6 +369,28 @@ bool EncoderContext::ConvertHotPath(FILE* f) {
     if (ok && original->HasAlpha()) MipPrefilter(true);
     if (ok && emitAlpha && original->HasAlpha()) { ProcessAlpha(!alpha6BitDecodable()); ok = err.empty(); }
     PrepareQuadSmooth();
+    if (devicePalette) {
+        // the passes only collect their raw streams; the colour payloads come from the GPU in one call, then the chunks are written in pass order
+        std::vector<u8> bitmap[7], pal[7]; size_t rgbBytes[7] = {};
+        outFile = nullptr;
+        for (int i = 0; ok && i < 7; i++) {
+            FittingQuadSmooth(3, original->GetPlane(0), original->GetPlane(1), original->GetPlane(2), nullptr, false, kPass[i][0], kPass[i][1]);
+            ok = err.empty();
+            bitmap[i] = gradBitmap; rgbBytes[i] = gradRgb.size();
+        }
+        outFile = f;
+        ok = ok && devicePalettePayloads(pal);
+        for (int i = 0; ok && i < 7; i++) {
+            if (!yaikchunk::gradientTileHasChunk(w, h, kPass[i][0], kPass[i][1], bitmap[i].data(), rgbBytes[i])) {
+                if (rgbBytes[i]) ok = fail("ConvertHotPath: a pass has colours but no tile");      // the device coded it, the host coder would have skipped it
+                continue;
+            }
+            std::vector<u8> zBitmap, zRgb; std::string e;
+            ok = yaikchunk::compressStream(bitmap[i].data(), bitmap[i].size(), 18, zBitmap, e) && yaikchunk::compressStream(pal[i].data(), pal[i].size(), 18, zRgb, e) &&
+                 yaikchunk::emitGradientTile(f, w, h, kPass[i][0], kPass[i][1], bitmap[i].data(), rgbBytes[i], (u32)pal[i].size(), zBitmap, zRgb, colorCompressionQuad, 7, e);
+            if (!ok) fail(("ConvertHotPath: " + e).c_str());
+        }
+    } else
     for (int i = 0; ok && i < 7; i++) {
         FittingQuadSmooth(3, original->GetPlane(0), original->GetPlane(1), original->GetPlane(2), nullptr, false, kPass[i][0], kPass[i][1]);
         ok = err.empty();
@@ -507,6 +541,7 @@ private:
 struct EncoderContext::EntropyStage {
     FILE* f = nullptr; int w = 0, h = 0, threads = 1, colorQuad = 250, color1D = 255, range1D = 15;
     std::vector<u8> bitmap[7], rgb[7], pix, type;
+    std::vector<u8> devPal[7]; bool haveDevPal = false;    // SetDevicePalette: the colour payloads came from the GPU, this thread only hands them to ZStd
     std::thread worker; bool ok = true; std::string err;
     void run() {
         PaletteResetCodeBook();                         // like ConvertHotPath: the reference converts one image per process
@@ -523,10 +558,13 @@ struct EncoderContext::EntropyStage {
                 if (has[i]) pool.push([&, i] { std::string e; if (!yaikchunk::compressStream(bitmap[i].data(), bitmap[i].size(), 18, zBitmap[i], e)) bad(e); });
             }
             for (int i = 0; i < 7; i++) {                // PaletteCompressor in pass order on this thread; each result goes straight to a worker
-                if (!has[i]) continue;
-                pal[i].resize(rgb[i].size() * 3); palSize[i] = (u32)pal[i].size();
-                if (!PaletteCompressor(rgb[i].data(), (int)rgb[i].size(), pal[i].data(), &palSize[i])) { bad("PaletteCompressor overflow"); break; }
-                pal[i].resize(palSize[i]);
+                if (!has[i]) { if (haveDevPal && !rgb[i].empty()) { bad("a pass has colours but no tile"); break; } continue; }
+                if (haveDevPal) { pal[i].swap(devPal[i]); palSize[i] = (u32)pal[i].size(); }
+                else {
+                    pal[i].resize(rgb[i].size() * 3); palSize[i] = (u32)pal[i].size();
+                    if (!PaletteCompressor(rgb[i].data(), (int)rgb[i].size(), pal[i].data(), &palSize[i])) { bad("PaletteCompressor overflow"); break; }
+                    pal[i].resize(palSize[i]);
+                }
                 pool.push([&, i] { std::string e; if (!yaikchunk::compressStream(pal[i].data(), pal[i].size(), 18, zRgb[i], e)) bad(e); });
             }
             pool.wait();
@@ -558,6 +596,7 @@ bool EncoderContext::ConvertHotPathBegin(FILE* f, int threads) {
         ok = err.empty();
         st->bitmap[i] = gradBitmap; st->rgb[i] = gradRgb;
     }
+    if (ok && devicePalette) { ok = devicePalettePayloads(st->devPal); st->haveDevPal = ok; }
     if (ok) {
         st->pix.resize((size_t)st->w * st->h * 3 + 64);
         u8* wr = st->pix.data();

@@ -82,6 +82,12 @@ public:
     // waits for all of them.  `f` belongs to its stage between Begin and Finish.
     bool ConvertHotPathBegin(FILE* f, int threads);
     bool ConvertHotPathFinish();
+    // opt-in (off by default): ConvertHotPath and ConvertHotPathBegin take the seven 'GTIL' colour payloads from the GPU (yk_palette_reset +
+    // yk_palette_compress: PaletteCompressor on the corner streams where they lie in HBM) instead of running palette.cpp on the host; the
+    // entropy stage then only hands them to ZStd.  The file is byte for byte the one written with the option off.  The raw corner streams are
+    // still downloaded pass by pass (LastGradientRGBStream keeps working and the chunk header needs their sizes).  Plane-subset passes and the
+    // pass-by-pass form (FittingQuadSmooth with outFile set) keep the host coder.
+    void SetDevicePalette(bool on) { devicePalette = on; }
     bool ConvertHotPathParallel(FILE* f, int threads) { return ConvertHotPathBegin(f, threads) && ConvertHotPathFinish(); }
     // The tile maps of the image, encoded as row stripes on several GPUs of the node by THIS process (the reference is one
     // process, include/YAIK.h:42-47): stripe i = a band of 64-row blocks + one halo row (the BL / BR corner samples at y + T,
@@ -124,6 +130,8 @@ private:
     bool adoptImage(Image* newImage, const u8* pixels, size_t rowBytes);   // SetImageToEncode / LoadImagePixels (pixels != NULL)
     bool fail(const char* what);
     bool alpha6BitDecodable() const;
+    bool devicePalette = false;
+    bool devicePalettePayloads(std::vector<u8> pal[7]);      // yk_palette_reset + yk_palette_compress of the current frame, payloads to the host
     Image* original;
     yk_ctx* ctx;
     bool bound, alphaDone, encoded, enc3, encDst, oneDReady;

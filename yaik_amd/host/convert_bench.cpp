@@ -1,5 +1,6 @@
 // Wall-clock of EncoderContext::ConvertHotPath (sequential entropy stage) against ConvertHotPathBegin/Finish (entropy stages of several
-// images in flight on host threads while the next images go through the GPU passes) on synthetic frames.   usage: convert_bench [W=4096] [images=3] [threads=8]
+// images in flight on host threads while the next images go through the GPU passes) on synthetic frames.   usage: convert_bench [W=4096] [images=8] [threads=2] [devicePalette=0]
+// devicePalette = 1: EncoderContext::SetDevicePalette(true), the 'GTIL' colour payloads come from the GPU instead of palette.cpp on the entropy thread
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -29,7 +30,9 @@ static double now() { return std::chrono::duration<double>(std::chrono::steady_c
 
 int main(int argc, char** argv) {
     const int W = argc > 1 ? atoi(argv[1]) : 4096, N = argc > 2 ? atoi(argv[2]) : 8, T = argc > 3 ? atoi(argv[3]) : 2;
+    const bool devPal = argc > 4 && atoi(argv[4]) != 0;
     EncoderContext ctx;
+    ctx.SetDevicePalette(devPal);
     std::vector<long> sizes[2];
     double secs[2] = { 0, 0 }, gpuSide = 0;
     for (int mode = 0; mode < 2; mode++) {
@@ -52,6 +55,7 @@ int main(int argc, char** argv) {
         ctx.SetImageToEncode(nullptr);
     }
     bool same = sizes[0] == sizes[1];
+    printf("PaletteCompressor on the %s: ", devPal ? "GPU (yk_palette_compress)" : "host (palette.cpp)");
     printf("%d x %dx%d RGBA -> .yaik: sequential entropy stage %.2f s (%.2f s per image), entropy stages of up to 8 images in flight (%d ZStd workers each) while the next images' "
            "upload and GPU passes run %.2f s (%.2f s per image, of which upload + GPU + download %.3f s); file sizes %s (%ld bytes first image)\n",
            N, W, W, secs[0], secs[0] / N, T, secs[1], secs[1] / N, gpuSide / N, same ? "identical" : "DIFFER", sizes[0].empty() ? 0L : sizes[0][0]);

@@ -168,11 +168,41 @@ static int palbench(int n) {
     return ok ? 0 : 1;
 }
 
+// entropy_tool palette <out prefix> <stream 0> [<stream 1> ...]: PaletteCompressor over raw colour streams (3 bytes per colour), in order, from a
+// reset code book; payload i goes to <out prefix><i>.  An empty stream is skipped like a pass without a chunk.  Prints the time of the coder alone.
+static int paletteFiles(const char* prefix, int n, char** paths) {
+    PaletteResetCodeBook();
+    double dt = 0; size_t colours = 0;
+    for (int i = 0; i < n; i++) {
+        FILE* f = fopen(paths[i], "rb"); if (!f) { fprintf(stderr, "cannot read %s\n", paths[i]); return 3; }
+        fseek(f, 0, SEEK_END); const long len = ftell(f); fseek(f, 0, SEEK_SET);
+        Bytes in((size_t)len), out((size_t)len * 3 + 64);
+        if (len && fread(in.data(), 1, (size_t)len, f) != (size_t)len) { fclose(f); return 3; }
+        fclose(f);
+        u32 sz = 0;
+        if (len) {
+            sz = (u32)((size_t)len * 3);
+            timespec t0, t1; clock_gettime(CLOCK_MONOTONIC, &t0);
+            const bool ok = PaletteCompressor(in.data(), (int)len, out.data(), &sz);
+            clock_gettime(CLOCK_MONOTONIC, &t1);
+            dt += (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec); colours += (size_t)len / 3;
+            if (!ok) { fprintf(stderr, "PaletteCompressor failed on %s\n", paths[i]); return 1; }
+        }
+        const std::string name = std::string(prefix) + std::to_string(i);
+        FILE* o = fopen(name.c_str(), "wb"); if (!o) { fprintf(stderr, "cannot write %s\n", name.c_str()); return 3; }
+        if (sz && fwrite(out.data(), 1, sz, o) != sz) { fclose(o); return 3; }
+        fclose(o);
+    }
+    printf("PaletteCompressor: %d streams, %zu colours in %.6f s\n", n, colours, dt);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (!yaikzstd::available()) { fprintf(stderr, "%s\n", yaikzstd::lastError()); return 4; }
     if (argc == 6 && !strcmp(argv[1], "parse")) return parse(argv[2], atoi(argv[3]), atoi(argv[4]), argv[5]);
     if (argc == 4 && !strcmp(argv[1], "write")) return writeFile(argv[2], argv[3]);
     if (argc == 3 && !strcmp(argv[1], "palbench")) return palbench(atoi(argv[2]));
-    fprintf(stderr, "usage: entropy_tool parse <file> <w> <h> <out.blobs> | entropy_tool write <streams.blobs> <out.yaik>\n");
+    if (argc >= 4 && !strcmp(argv[1], "palette")) return paletteFiles(argv[2], argc - 3, argv + 3);
+    fprintf(stderr, "usage: entropy_tool parse <file> <w> <h> <out.blobs> | entropy_tool write <streams.blobs> <out.yaik> | entropy_tool palette <out prefix> <stream> ...\n");
     return 2;
 }

@@ -18,6 +18,9 @@
 //                                                   YAIK_DecodeImageToDevice into a buffer of the driver's own handle (downloaded afterwards), same
 //                                                   tight pitch (bytes per pixel 4 with an 'ALPM' chunk, else 3): blobs dev_info_<i> (int32 host ok, error,
 //                                                   device ok, error, width, height, bytesPerPixel, custom-builder ok, its error), host_image_<i>, dev_image_<i>
+//        host_driver <in.bin> <out.blobs> palette   the image converted four times: ConvertHotPath and ConvertHotPathBegin / Finish, each with
+//                                                   SetDevicePalette off and on (blobs yaik_host, yaik_device, yaik_host_parallel, yaik_device_parallel:
+//                                                   all four files must be identical) and palette_intervals = yk_stage_ms intervals of YK_STAGE_PALETTE (2)
 // With the 4th argument the image is also converted to a .yaik stream (ConvertHotPath) and decoded back through the
 // YAIK_* decoder API, the way an application would use the two libraries.
 #include <cstdio>
@@ -365,6 +368,28 @@ int main(int argc, char** argv) {
         int wb[4] = { ctx->boundX0, ctx->boundY0, ctx->boundX1, ctx->boundY1 };
         blob("wh_bounds", wb, sizeof wb);
         if (*ctx->LastError()) { fprintf(stderr, "%s\n", ctx->LastError()); return 4; }
+        fclose(gOut);
+        ctx->SetImageToEncode(nullptr); ctx->Release(); delete ctx;
+        return 0;
+    }
+    if (argc > 3 && std::string(argv[3]) == "palette") {
+        static const char* names[4] = { "yaik_host", "yaik_device", "yaik_host_parallel", "yaik_device_parallel" };
+        for (int k = 0; k < 4; k++) {
+            ctx->SetDevicePalette((k & 1) != 0);
+            FILE* yf = tmpfile(); if (!yf) return 2;
+            const bool ok = k < 2 ? ctx->ConvertHotPath(yf) : ctx->ConvertHotPathParallel(yf, 4);
+            if (!ok) { fprintf(stderr, "%s: %s\n", names[k], ctx->LastError()); return 4; }
+            fflush(yf);
+            const long n = ftell(yf);
+            std::vector<u8> bytes((size_t)n);
+            fseek(yf, 0, SEEK_SET);
+            if (n && fread(bytes.data(), 1, bytes.size(), yf) != bytes.size()) return 2;
+            fclose(yf);
+            blob(names[k], bytes.data(), bytes.size());
+        }
+        float ms = 0.0f; int intervals = -1;
+        if (yk_stage_ms(ctx->Handle(), YK_STAGE_PALETTE, &ms, &intervals) != YK_OK) return 4;
+        blob("palette_intervals", &intervals, sizeof intervals);
         fclose(gOut);
         ctx->SetImageToEncode(nullptr); ctx->Release(); delete ctx;
         return 0;
