@@ -232,6 +232,43 @@ int yk_palette_compress_batch(yk_ctx* c);
 int yk_palette_payload_device(yk_ctx* c, int index, const uint8_t** dev, size_t* nBytes);
 int yk_palette_payload(yk_ctx* c, int index, uint8_t* hostOut, size_t cap, size_t* nBytes);
 
+/* ---- PaletteDecompressor on the GPU (new): 'GTIL' colour payloads back to colour streams, byte-exact -----------------------------------------
+ * decoder/YAIK_GenericFunctions.cpp:139-241, as the project's CPU restatement (yko_palette_decompress) executes it.  A payload of n bytes is read as if
+ * followed by zeros; a token may start at any offset below n + 385; byte 0 is codeBookSize and 1 + 3 * codeBookSize > n is an error; code index i
+ * (0..127) reads the bytes at 1 + 3i .. 3 + 3i whatever codeBookSize says; outBytes / 3 colours are written and nothing behind the token that
+ * writes the last one is looked at.
+ *   yk_palette_decompress_streams  nStreams (1..65536) payloads anywhere in the device's memory.  outBytes[i] is the chunk header's
+ *                                  streamRGBSizeUncompressed, a multiple of 3; 0 skips the stream (status 0, empty output).  remapRange 1..255
+ *                                  applies PaletteFullRangeRemapping(range) to every output, 0 leaves the bytes as decoded (which is the encoder's
+ *                                  corner stream whenever the round trip is clean).  Six kernel launches over all streams on the handle's stream
+ *                                  and NO host synchronisation (the stream table travels through the pinned ring of the decode batch calls:
+ *                                  a call waits only when the tables of four earlier calls are all still queued); ORDERING against the payloads' producer is the caller's, as for yk_decode_*_device.
+ *                                  The outputs lie packed in one grow-only buffer of the handle, each at a multiple of 16, with 64 bytes the call
+ *                                  never writes in front of the first and behind the last.
+ *   yk_palette_decoded_device      output `index` where it lies in HBM and its length (NULL / 0 for a skipped stream).
+ *   yk_palette_decoded             the same copied to the host (hostOut may be NULL: size query); synchronises.
+ *   yk_palette_decode_status       synchronises and reads one word per stream back: 0 = decoded, non-zero = PaletteDecompressor rejects the payload.
+ *                                  Only zero / non-zero is contract.  The bits say what was found at or before the token that writes the last
+ *                                  colour: 1 header longer than the payload, 2 an extension code (1001xxxx, 101xxxxx), 4 input exhausted (a token
+ *                                  at or beyond n + 385), 8 a back-reference before colour 0.
+ * Malformed payloads are data, not bad arguments: the call returns YK_OK, the other streams are unaffected, the failed stream's slot holds
+ * unspecified bytes and nothing outside a slot is written.  The outputs stay valid until the next yk_palette_decompress_streams or
+ * yk_decode_gradient_palette of the handle.  Timed as one YK_STAGE_PALETTE_DEC interval per call.
+ * Refusals launch nothing, leave earlier outputs and the handle usable and set yk_last_error: YK_ERR_BAD_ARG for a NULL table, nStreams outside
+ * 1..65536, an outBytes that is not a multiple of 3 (plane-subset streams stay with the host coder), outBytes != 0 with payBytes == 0 or a NULL
+ * pointer, more than 2^28 colours or 2^31 payload bytes in one call, remapRange outside 0..255, an index out of range; YK_ERR_STATE for the getters
+ * and the status before any call; YK_ERR_RANGE for a short buffer.
+ *   yk_decode_gradient_palette     yk_decode_gradient fed with the 'GTIL' payload instead of the colour stream (host pointers): uploads bitmap and
+ *                                  payload, decompresses on the device with PaletteFullRangeRemapping(colorCompression) (0 behaves as 1, as in the
+ *                                  reference), checks the status and decodes the pass.  A malformed payload gives YK_ERR_BAD_ARG and a message
+ *                                  before anything of the image is touched. */
+int yk_palette_decompress_streams(yk_ctx* c, const uint8_t* const* devPayloads, const size_t* payBytes, const size_t* outBytes, int nStreams, int remapRange);
+int yk_palette_decoded_device(yk_ctx* c, int index, const uint8_t** dev, size_t* nBytes);
+int yk_palette_decoded(yk_ctx* c, int index, uint8_t* hostOut, size_t cap, size_t* nBytes);
+int yk_palette_decode_status(yk_ctx* c, int32_t* out /* nStreams */);
+int yk_decode_gradient_palette(yk_ctx* c, int tileShiftX, int tileShiftY, const uint8_t* bitmap, size_t bitmapBytes,
+                               const uint8_t* payload, size_t payloadBytes, size_t rgbBytes, int colorCompression);
+
 /* ---- streams of frames on several handles (new) --------------------------------------------------------------------------
  * With two handles (two streams) in flight the HBM-bound alpha / compaction kernels of one frame run under the fused kernel of
  * the other.  Two fused kernels sharing the chip only slow each other down, so a caller that alternates handles can order them:
@@ -609,7 +646,8 @@ enum { YK_STAGE_CORNERS = 0,       /* yk_gradient_corners: lattice clear + owner
        YK_STAGE_LUT3D = 6,         /* yk_lut_search: yk_lut_search_kernel (one interval per tile shape) */
        YK_STAGE_UNPACK = 7,        /* yk_upload_pixels_u8 / yk_load_device_pixels_u8: yk_unpack_u8_kernel (the host copy is outside the interval) */
        YK_STAGE_DEC_COMPARE = 8,   /* yk_decode_compare_*: yk_quality_compare_kernel + yk_quality_fold_kernel (the read-back is outside the interval) */
-       YK_STAGE_PALETTE = 9 };     /* yk_palette_compress*: the clears and the eight yk_pal_*_kernel launches of a call (the read-back is outside the interval) */
+       YK_STAGE_PALETTE = 9,       /* yk_palette_compress*: the clears and the eight yk_pal_*_kernel launches of a call (the read-back is outside the interval) */
+       YK_STAGE_PALETTE_DEC = 10 };/* yk_palette_decompress_streams, yk_decode_gradient_palette: the six yk_pd_*_kernel launches of a call */
 int yk_stage_ms(yk_ctx* c, int stage, float* msSum, int* intervals);
 
 /* ---- diagnostics: the MEASURED HBM roof of this device (roofline fractions are quoted against the 8 TB/s specification

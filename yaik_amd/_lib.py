@@ -70,6 +70,11 @@ SIGNATURES = {
     "yk_palette_compress_batch": (C.c_int, [vp]),
     "yk_palette_payload_device": (C.c_int, [vp, C.c_int, C.POINTER(vp), szp]),
     "yk_palette_payload": (C.c_int, [vp, C.c_int, vp, sz, szp]),
+    "yk_palette_decompress_streams": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int]),
+    "yk_palette_decoded_device": (C.c_int, [vp, C.c_int, C.POINTER(vp), szp]),
+    "yk_palette_decoded": (C.c_int, [vp, C.c_int, vp, sz, szp]),
+    "yk_palette_decode_status": (C.c_int, [vp, vp]),
+    "yk_decode_gradient_palette": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, sz, sz, C.c_int]),
     "yk_order_fused_after": (C.c_int, [vp, vp]),
     "yk_gradient_bitmap_bytes": (sz, [vp, C.c_int]),
     "yk_gradient_bitmap": (C.c_int, [vp, C.c_int, vp, sz]),

@@ -209,6 +209,7 @@ void yk_destroy(yk_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
     yk_dec_free(c);
     yk_pal_free(c);
+    yk_pd_free(c);
     F(c->ownedPlanes); F(c->pxStage); F(c->dScratch); F(c->dAlpha); F(c->dAvScratch); F(c->avState); F(c->avPay); F(c->av6); F(c->avTab); F(c->qBuf);
     for (int r = 0; r < YK_EV_RING; r++) for (int i = 0; i < 5; i++) if (c->evRing[r][i]) (void)hipEventDestroy(c->evRing[r][i]);
     for (int st = 0; st < YK_NUM_STAGES; st++) for (int k = 0; k < YK_STAGE_RING; k++) for (int i = 0; i < 2; i++) if (c->stEv[st][k][i]) (void)hipEventDestroy(c->stEv[st][k][i]);

@@ -12,7 +12,7 @@
 #define YK_LROWS    65
 #define YK_EV_RING  64
 #define YK_SLOT     32      // bytes of nibble slot per 8x8 tile-plane (64 nibbles)
-#define YK_NUM_STAGES 10    // YK_STAGE_* of include/yaik_hip.h
+#define YK_NUM_STAGES 11    // YK_STAGE_* of include/yaik_hip.h
 #define YK_STAGE_RING 16
 
 // Batches: one handle can hold nFrames images of one shape; every per-image array is allocated nFrames times back to back and
@@ -83,6 +83,17 @@ struct YkPalette {
     bool carryFresh = true;                                      // the carried rows are those of a fresh process (all zero deltas)
     std::vector<uint8_t> segHost;                                // the segment table on its way to HBM
     std::vector<uint32_t> lenBase;                               // read back: [nSeg] payload lengths, [nSeg] payload offsets in `out`
+    int nSeg = 0; bool valid = false;
+};
+
+// yk_palette_decompress_streams (yk_palette_dec.hip): PaletteDecompressor over a list of payloads.  Grow-only, owned by the handle.
+struct YkPaletteDec {
+    uint8_t* scratch = nullptr; size_t scratchCap = 0;           // stream table, chunk records, token offsets, colour records, halos, status words
+    uint8_t* out = nullptr; size_t outCap = 0;                   // the decoded streams of the last call, each on a multiple of 16, 64 free bytes around them
+    uint8_t* stage = nullptr; size_t stageCap = 0;               // yk_decode_gradient_palette: the host's tile bitmap and payload on their way in
+    std::vector<size_t> slotOff, slotLen;                        // where every stream's output lies in `out`
+    std::vector<uint32_t> statusHost;
+    size_t statusOff = 0;                                        // the status words inside `scratch`
     int nSeg = 0; bool valid = false;
 };
 
@@ -210,6 +221,7 @@ struct yk_ctx {
     int kernelVersion = 2;              // 2 = yk_encode2_kernel; 1 = the registered cross-check launcher (tests/csrc/yk_encode_v1.hip)
     YkStreamsBatch sb;                  // yk_encode_streams_batch
     YkPalette pal;                      // yk_palette_compress*
+    YkPaletteDec pdec;                  // yk_palette_decompress_streams, yk_decode_gradient_palette
 };
 
 int yk_fail(yk_ctx* c, int code, const char* what, hipError_t e = hipSuccess);
@@ -242,6 +254,7 @@ inline int yk_sb_grow(yk_ctx* c, uint32_t** p, size_t* capElems, size_t needElem
     size_t cap = *capElems * 4; const int rc = yk_sb_grow_bytes(c, reinterpret_cast<void**>(p), &cap, needElems * 4); *capElems = cap / 4; return rc;
 }
 void yk_sb_free(yk_ctx* c);
+void yk_pd_free(yk_ctx* c);                               // frees the palette decoder's buffers (yk_palette_dec.hip)
 void yk_pal_free(yk_ctx* c);                              // frees the palette coder's buffers (yk_palette.hip); the carried rows become fresh
 int yk_corners_finish(yk_ctx* c);                         // reads the corner streams' lengths back if that is still pending (synchronises)
 // the pinned ring behind the per-frame tables of the decode batch calls (yk_decode.hip)

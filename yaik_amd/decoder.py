@@ -260,18 +260,137 @@ class HipTileDecoder:
         self._batch_streams = keep
         return frames
 
-    def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False, per_frame: bool = False) -> None:
+    def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False, per_frame: bool = False, palette: bool = False) -> None:
         """decode_batch_streams of encoder_batch_streams(enc, per_frame); alpha=True also runs the encoder's alpha_values_batch and decodes every
         frame's 'ALPM' payload where the encoder left it in HBM (decompress_alpha_batch; frames without a chunk are opaque).  With sync=False on
-        the default path the queued decode reads the encoder's own stream buffer: fence this decoder before the encoder's next encode."""
-        frames = self.encoder_batch_streams(enc, per_frame)
+        the default path the queued decode reads the encoder's own stream buffer: fence this decoder before the encoder's next encode.
+        palette=True: the corner streams take the way of a file.  The payloads the CALLER made with enc.palette_compress_batch() (after
+        enc.streams_batch(); this method does not touch the encoder's coder state) are decompressed on this handle
+        (palette_decompress_streams, remap_range 250) and the gradient decode reads those outputs with remap off.  Only for streams that
+        round-trip through the 'GTIL' coder: a payload PaletteDecompressor rejects raises YaikError (DESIGN §18 on payloads that decode to
+        other bytes than their stream).  Without payloads of this batch on the encoder the call raises ValueError."""
+        if palette:
+            if per_frame:
+                raise ValueError("palette=True needs the encoder's stream table (per_frame=False)")
+            if not self._encoder_has_payloads(enc, 7 * enc.frames):
+                raise ValueError("palette=True decodes the payloads of enc.palette_compress_batch(): call it first (after enc.streams_batch())")
+            _chk(self._h, lib().yk_synchronize(self._h))
+            if (enc.w, enc.h, enc.frames) != (self.w, self.h, self.frames):
+                raise ValueError(f"the encoder holds {enc.frames} frames of {enc.w} x {enc.h}, the decoder batch {self.frames} of {self.w} x {self.h}")
+            frames = batch_calls_from_table(enc.streams_table(), PASSES)     # the caller's table: building a new one would drop the payloads
+            enc.synchronize()
+            self._batch_streams = None
+        else:
+            frames = self.encoder_batch_streams(enc, per_frame)
         entries = None
         if alpha:
             entries = enc.alpha_payloads_device()
             enc.synchronize()                                              # the payloads are written on the encoder's stream
-        self.decode_batch_streams(frames, sync and not alpha)
+        if palette:
+            frames = self._through_palette(enc, frames)
+        self.decode_batch_streams(frames, sync and not alpha, 0 if palette else 250)
         if alpha:
             self.decompress_alpha_batch(entries, 255, sync)
+
+    # ---- PaletteDecompressor (decoder/YAIK_GenericFunctions.cpp:139-241) on the GPU: 'GTIL' payloads back to colour streams -----------------
+    def palette_decompress_streams(self, payload_tensors, out_bytes, remap_range: int = 250) -> int:
+        """PaletteDecompressor over payloads in device memory: `payload_tensors` is a sequence of 1-D contiguous uint8 CUDA tensors, out_bytes[i]
+        the decoded length of stream i (the chunk header's streamRGBSizeUncompressed, a multiple of 3; 0 skips the stream).  remap_range 1..255:
+        PaletteFullRangeRemapping on the way out, 0: the bytes as decoded.  The call first waits for torch's current stream (the hand-over fence of
+        the payload tensors, as in HipTileEncoder.palette_compress_streams); the library call behind it queues its launches and returns without
+        waiting for them: palette_status() does.  CPU tensors
+        and bad arguments are refused before any library call.  Returns the number of streams."""
+        import torch
+        if isinstance(remap_range, bool) or not isinstance(remap_range, int) or not 0 <= remap_range <= 255:
+            raise ValueError(f"remap_range must be an int in 0..255; got {remap_range!r}")
+        tensors, out_bytes = list(payload_tensors), list(out_bytes)
+        if not tensors or len(tensors) > 65536:
+            raise ValueError("1..65536 payloads are needed")
+        if len(out_bytes) != len(tensors):
+            raise ValueError(f"{len(out_bytes)} output lengths for {len(tensors)} payloads")
+        for i, nb in enumerate(out_bytes):
+            if isinstance(nb, bool) or not isinstance(nb, (int, np.integer)) or nb < 0 or nb % 3:
+                raise ValueError(f"out_bytes[{i}] must be a non-negative multiple of 3; got {nb!r}")
+        for i, (t, nb) in enumerate(zip(tensors, out_bytes)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"payload {i} is not a torch tensor")
+            if not t.is_cuda:
+                raise ValueError(f"payload {i} is a CPU tensor: the payloads must lie in device memory")
+            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError(f"payload {i} must be a 1-D contiguous uint8 tensor")
+            if nb and not t.numel():
+                raise ValueError(f"payload {i} is empty but {nb} bytes are expected from it")
+        n = len(tensors)
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in tensors])
+        lens = (C.c_size_t * n)(*[t.numel() for t in tensors])
+        outs = (C.c_size_t * n)(*[int(v) for v in out_bytes])
+        torch.cuda.current_stream(tensors[0].device).synchronize()          # hand-over fence: the payloads are complete before this handle reads them
+        _chk(self._h, lib().yk_palette_decompress_streams(self._h, ptrs, lens, outs, n, remap_range))
+        self._palette_keepalive = tensors
+        self._palette_n = n
+        return n
+
+    def palette_status(self) -> np.ndarray:
+        """One int32 per stream of the last palette_decompress_streams: 0 = decoded, non-zero = PaletteDecompressor rejects the payload (synchronises)."""
+        n = getattr(self, "_palette_n", 0)
+        out = np.zeros(65536, dtype=np.int32)                               # the most streams a call can have: whatever the handle last decoded fits
+        _chk(self._h, lib().yk_palette_decode_status(self._h, out.ctypes.data))
+        return out[:n].copy()
+
+    def palette_decoded(self, i: int) -> np.ndarray:
+        """Output i of the last palette_decompress_streams, copied to the host (synchronises).  Unspecified bytes where palette_status()[i] != 0."""
+        n = C.c_size_t()
+        _chk(self._h, lib().yk_palette_decoded(self._h, i, None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        if out.size:
+            _chk(self._h, lib().yk_palette_decoded(self._h, i, out.ctypes.data, out.size, None))
+        return out
+
+    def palette_decoded_device(self, i: int):
+        """Output i where it lies in HBM, as a uint8 tensor view of the handle's buffer (written on the handle's stream; stale after the next
+        palette_decompress_streams or 'GTIL' payload decode of the handle)."""
+        import torch
+        dev, n = C.c_void_p(), C.c_size_t()
+        _chk(self._h, lib().yk_palette_decoded_device(self._h, i, C.byref(dev), C.byref(n)))
+        if not n.value:
+            return torch.empty(0, dtype=torch.uint8, device="cuda")
+
+        class _View:                                                        # __cuda_array_interface__: a view, not a copy
+            __cuda_array_interface__ = {"shape": (int(n.value),), "typestr": "|u1", "data": (int(dev.value), False), "version": 2}
+
+        return torch.as_tensor(_View(), device="cuda")
+
+    @staticmethod
+    def _encoder_has_payloads(enc, n: int) -> bool:
+        """True when the encoder's library holds exactly n valid palette payloads (asked of the library: an encode since has dropped them)."""
+        dev, nb = C.c_void_p(), C.c_size_t()
+        return (enc._L.yk_palette_payload_device(enc._h, n - 1, C.byref(dev), C.byref(nb)) == 0
+                and enc._L.yk_palette_payload_device(enc._h, n, C.byref(dev), C.byref(nb)) != 0)
+
+    def _through_palette(self, enc, frames: list) -> list:
+        """The call lists `frames` (one list per image) with every corner stream replaced by the decode of the encoder's 'GTIL' payload for it:
+        payload number frame * 7 + pass of enc.palette_payload_device.  One palette_decompress_streams over all of them; raises on a rejected one."""
+        index = {shape: p for p, shape in enumerate(PASSES)}
+        where, pays, outs = [], [], []
+        for f, calls in enumerate(frames):
+            for k, c in enumerate(calls):
+                if c[0] == "g" and c[6]:
+                    where.append((f, k))
+                    pays.append(enc.palette_payload_device(f * 7 + index[(c[1], c[2])]))
+                    outs.append(int(c[6]))
+        if not where:
+            return frames
+        self.palette_decompress_streams(pays, outs, 250)
+        st = self.palette_status()
+        if st.any():
+            raise YaikError(f"PaletteDecompressor rejects the payload of {int(np.count_nonzero(st))} stream(s); first: frame, call {where[int(np.argmax(st != 0))]}")
+        frames = [list(calls) for calls in frames]
+        for i, (f, k) in enumerate(where):
+            dev, n = C.c_void_p(), C.c_size_t()
+            _chk(self._h, lib().yk_palette_decoded_device(self._h, i, C.byref(dev), C.byref(n)))
+            c = frames[f][k]
+            frames[f][k] = c[:5] + (dev.value, n.value)
+        return frames
 
     def decompress_alpha_batch(self, entries, no_chunk_alpha: int = 255, sync: bool = True) -> None:
         """The 'ALPM' plane of every frame of the batch in one launch (yk_decode_alpha_batch_device).  entries[f] is None (no chunk: the plane is
@@ -368,30 +487,40 @@ class HipTileDecoder:
         enc.synchronize()
         return calls
 
-    def decode_streams(self, calls: list, sync: bool = True, per_pass: bool = False) -> None:
+    def decode_streams(self, calls: list, sync: bool = True, per_pass: bool = False, remap_range: int = 250) -> None:
         """All gradient chunks + the 1-D chunk from device-resident streams (encoder_streams): the corner streams are remapped like
         PaletteFullRangeRemapping(250) on the way in; no PCIe hop, no host synchronisation between the passes.  The gradient chunks go through
-        ONE yk_decode_gradient_all_device call (per_pass=True: one yk_decode_gradient_device call per chunk, same result)."""
+        ONE yk_decode_gradient_all_device call (per_pass=True: one yk_decode_gradient_device call per chunk, same result).  remap_range=0 takes
+        corner streams that are remapped already (the outputs of palette_decompress_streams)."""
         L = lib()
         g = [c for c in calls if c[0] == "g"]
         if per_pass:
             for c in g:
-                _chk(self._h, L.yk_decode_gradient_device(self._h, c[1], c[2], c[3], c[4], c[5], c[6], 250))
+                _chk(self._h, L.yk_decode_gradient_device(self._h, c[1], c[2], c[3], c[4], c[5], c[6], remap_range))
         elif g:
             n = len(g)
             ptr = lambda v: v.value if isinstance(v, C.c_void_p) else v
             sx, sy = (C.c_int * n)(*[c[1] for c in g]), (C.c_int * n)(*[c[2] for c in g])
             bm, nb = (C.c_void_p * n)(*[ptr(c[3]) for c in g]), (C.c_size_t * n)(*[c[4] for c in g])
             rgb, nr = (C.c_void_p * n)(*[ptr(c[5]) for c in g]), (C.c_size_t * n)(*[c[6] for c in g])
-            _chk(self._h, L.yk_decode_gradient_all_device(self._h, n, sx, sy, bm, nb, rgb, nr, 250))
+            _chk(self._h, L.yk_decode_gradient_all_device(self._h, n, sx, sy, bm, nb, rgb, nr, remap_range))
         for c in calls:
             if c[0] == "1":
                 _chk(self._h, L.yk_decode_1d_device(self._h, c[1], c[2], c[3], c[4], 15))
         if sync:
             _chk(self._h, L.yk_synchronize(self._h))
 
-    def decode_from_encoder(self, enc, sync: bool = True, per_pass: bool = False) -> None:
-        self.decode_streams(self.encoder_streams(enc), sync, per_pass)
+    def decode_from_encoder(self, enc, sync: bool = True, per_pass: bool = False, palette: bool = False) -> None:
+        """decode_streams of encoder_streams(enc).  palette=True: the corner streams go through the payloads the CALLER made with
+        enc.palette_compress() (and enc.palette_reset() before it where the image is to start from a fresh code book, like the first image of
+        a file) and this handle's palette_decompress_streams first, like decode_batch_from_encoder(palette=True); only for streams that
+        round-trip.  The encoder's coder state is not touched; without the seven payloads on the encoder the call raises ValueError."""
+        calls = self.encoder_streams(enc)
+        if palette:
+            if not self._encoder_has_payloads(enc, 7):
+                raise ValueError("palette=True decodes the payloads of enc.palette_compress(): call it first")
+            calls = self._through_palette(enc, [calls])[0]
+        self.decode_streams(calls, sync, per_pass, 0 if palette else 250)
 
     def decompress_gradient_planes(self, plane_bit: int, bitmap: np.ndarray, rgb_dq: np.ndarray, consistent_marks: bool = False):
         """DecompressGradient4x4 with planeBit 1..6; consistent_marks=False leaves tile4x4Mask as the reference's loops do (defects included)."""

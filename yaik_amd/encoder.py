@@ -402,6 +402,13 @@ class HipTileEncoder:
         _chk(self._h, self._L.yk_batch_streams_table(self._h, tab))
         return [FrameStreams(list(t.bitmap), list(t.bitmapBytes), list(t.rgb), list(t.rgbBytes), t.pix, t.pixBytes, t.type, t.typeBytes, self) for t in tab]
 
+    def streams_table(self) -> list:
+        """The FrameStreams of the last streams_batch() again (yk_batch_streams_table alone): nothing is launched, and the streams and the
+        palette payloads made from them stay valid.  Refused by the library when there is no valid table."""
+        tab = (_FrameStreamsC * self.frames)()
+        _chk(self._h, self._L.yk_batch_streams_table(self._h, tab))
+        return [FrameStreams(list(t.bitmap), list(t.bitmapBytes), list(t.rgb), list(t.rgbBytes), t.pix, t.pixBytes, t.type, t.typeBytes, self) for t in tab]
+
     # ---- PaletteCompressor (EncoderContext.cpp:3259-3502) on the GPU: the 'GTIL' colour payloads -----------------
     def palette_reset(self):
         """Forgets the 64 code-book rows that carry from call to call (PaletteResetCodeBook: a fresh process)."""

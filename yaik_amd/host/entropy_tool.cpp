@@ -197,12 +197,41 @@ static int paletteFiles(const char* prefix, int n, char** paths) {
     return 0;
 }
 
+// entropy_tool unpalette <out prefix> <range> <payload 0> <bytes 0> [<payload 1> <bytes 1> ...]: PaletteDecompressor over 'GTIL' colour payloads;
+// <bytes i> is the decoded length, stream i goes to <out prefix><i>.  A length of 0 skips the stream.  Prints the time of the coder alone.
+static int unpaletteFiles(const char* prefix, int range, int n, char** args) {
+    double dt = 0; size_t colours = 0;
+    for (int i = 0; i < n; i++) {
+        const long outLen = atol(args[2 * i + 1]);
+        Bytes out((size_t)outLen);
+        if (outLen) {
+            FILE* f = fopen(args[2 * i], "rb"); if (!f) { fprintf(stderr, "cannot read %s\n", args[2 * i]); return 3; }
+            fseek(f, 0, SEEK_END); const long len = ftell(f); fseek(f, 0, SEEK_SET);
+            Bytes in((size_t)len + 128 * 3, 0);
+            if (len && fread(in.data(), 1, (size_t)len, f) != (size_t)len) { fclose(f); return 3; }
+            fclose(f);
+            timespec t0, t1; clock_gettime(CLOCK_MONOTONIC, &t0);
+            const bool ok = PaletteDecompressor(in.data(), (int)len, (int)len + 128 * 3, out.data(), (int)outLen, (u8)range);
+            clock_gettime(CLOCK_MONOTONIC, &t1);
+            dt += (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec); colours += (size_t)outLen / 3;
+            if (!ok) { fprintf(stderr, "PaletteDecompressor rejects %s\n", args[2 * i]); return 1; }
+        }
+        const std::string name = std::string(prefix) + std::to_string(i);
+        FILE* o = fopen(name.c_str(), "wb"); if (!o) { fprintf(stderr, "cannot write %s\n", name.c_str()); return 3; }
+        if (outLen && fwrite(out.data(), 1, (size_t)outLen, o) != (size_t)outLen) { fclose(o); return 3; }
+        fclose(o);
+    }
+    printf("PaletteDecompressor: %d streams, %zu colours in %.6f s\n", n, colours, dt);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (!yaikzstd::available()) { fprintf(stderr, "%s\n", yaikzstd::lastError()); return 4; }
     if (argc == 6 && !strcmp(argv[1], "parse")) return parse(argv[2], atoi(argv[3]), atoi(argv[4]), argv[5]);
     if (argc == 4 && !strcmp(argv[1], "write")) return writeFile(argv[2], argv[3]);
     if (argc == 3 && !strcmp(argv[1], "palbench")) return palbench(atoi(argv[2]));
     if (argc >= 4 && !strcmp(argv[1], "palette")) return paletteFiles(argv[2], argc - 3, argv + 3);
-    fprintf(stderr, "usage: entropy_tool parse <file> <w> <h> <out.blobs> | entropy_tool write <streams.blobs> <out.yaik> | entropy_tool palette <out prefix> <stream> ...\n");
+    if (argc >= 6 && (argc - 4) % 2 == 0 && !strcmp(argv[1], "unpalette")) return unpaletteFiles(argv[2], atoi(argv[3]), (argc - 4) / 2, argv + 4);
+    fprintf(stderr, "usage: entropy_tool parse <file> <w> <h> <out.blobs> | entropy_tool write <streams.blobs> <out.yaik> | entropy_tool palette <out prefix> <stream> ... | entropy_tool unpalette <out prefix> <range> <payload> <bytes> ...\n");
     return 2;
 }

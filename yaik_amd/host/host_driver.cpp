@@ -21,6 +21,10 @@
 //        host_driver <in.bin> <out.blobs> palette   the image converted four times: ConvertHotPath and ConvertHotPathBegin / Finish, each with
 //                                                   SetDevicePalette off and on (blobs yaik_host, yaik_device, yaik_host_parallel, yaik_device_parallel:
 //                                                   all four files must be identical) and palette_intervals = yk_stage_ms intervals of YK_STAGE_PALETTE (2)
+//        host_driver decode_palette <out.blobs> <a.yaik>   the file decoded with YAIK_SetDevicePalette off and on, and a copy whose first
+//                                                   whole-RGB 'GTIL' payload has its first token replaced by an extension code (re-framed with
+//                                                   compressStream / emitGradientTile) decoded both ways too: blobs pal_info_<k> (int32 ok, errorCode,
+//                                                   width, height, bytesPerPixel) and pal_image_<k>, k = off, on, bad_off, bad_on
 // With the 4th argument the image is also converted to a .yaik stream (ConvertHotPath) and decoded back through the
 // YAIK_* decoder API, the way an application would use the two libraries.
 #include <cstdio>
@@ -35,6 +39,7 @@
 #include "chunks.h"
 #include "palette.h"
 #include "yaik_format.h"
+#include "zstd_dl.h"
 
 static FILE* gOut;
 static void blob(const std::string& name, const void* data, size_t len) {
@@ -297,11 +302,94 @@ static int run_decode_device(int n, char** files) {
     return 0;
 }
 
+// decodes one stream through a fresh slot; default builder
+static void decode_once(const std::vector<u8>& file, int devicePalette, const char* tag) {
+    YAIK_SetDevicePalette(devicePalette);
+    YAIK_LIB lib = YAIK_Init(1, nullptr);
+    std::vector<u32> stream((file.size() + 3) / 4 + 1);
+    memcpy(stream.data(), file.data(), file.size());
+    int info[5] = { 0, 0, 0, 0, 0 };
+    std::vector<u8> outImg;
+    YAIK_SDecodedImage di;
+    if (lib && YAIK_DecodeImagePre(lib, stream.data(), (u32)file.size(), &di)) {
+        const int bpp = di.hasAlpha ? 4 : 3;
+        info[2] = di.width; info[3] = di.height; info[4] = bpp;
+        outImg.assign((size_t)di.width * di.height * bpp, 0);
+        di.outputImage = outImg.data(); di.outputImageStride = di.width * bpp;
+        info[0] = YAIK_DecodeImage(stream.data(), (u32)file.size(), &di) ? 1 : 0;
+    }
+    info[1] = (int)YAIK_GetErrorCode();
+    blob(std::string("pal_info_") + tag, info, sizeof info);
+    blob(std::string("pal_image_") + tag, outImg.data(), outImg.size());
+    if (lib) YAIK_Release(lib);
+    YAIK_SetDevicePalette(0);
+}
+
+static int run_decode_palette(const char* path) {
+    using namespace yaikfmt;
+    FILE* fi = fopen(path, "rb"); if (!fi) return 2;
+    fseek(fi, 0, SEEK_END); const long len = ftell(fi); fseek(fi, 0, SEEK_SET);
+    std::vector<u8> file((size_t)len);
+    const bool whole = fread(file.data(), 1, (size_t)len, fi) == (size_t)len;
+    fclose(fi);
+    if (!whole) return 2;
+    decode_once(file, 0, "off");
+    decode_once(file, 1, "on");
+    // the malformed copy: the first 'GTIL' chunk of all three planes with at least two colours
+    FileHeader fh; if (file.size() < sizeof fh) return 6;
+    memcpy(&fh, file.data(), sizeof fh);
+    for (size_t o = sizeof fh; o + sizeof(HeaderBase) <= file.size();) {
+        HeaderBase hb; memcpy(&hb, file.data() + o, sizeof hb);
+        if (hb.tag == TAG_END) break;
+        const size_t next = o + sizeof hb + hb.length;
+        if (next > file.size()) return 6;
+        HeaderGradientTile gh;
+        if (hb.tag == TAG_GRADTILE && hb.length >= sizeof gh) {
+            memcpy(&gh, file.data() + o + sizeof hb, sizeof gh);
+            const int sx = gh.format & 7, sy = (gh.format >> 3) & 7;
+            u32 bigX, bigY, bitCount;
+            if (gh.plane == 7 && gh.streamRGBSizeUncompressed >= 6 && swizzleSize(sx, sy, bigX, bigY, bitCount)) {
+                const u8* after = file.data() + o + sizeof hb + sizeof gh;
+                const size_t sizeBitmap = (size_t)((fh.width + bigX - 1) / bigX) * ((fh.height + bigY - 1) / bigY) * bitCount / 8;
+                std::vector<u8> bitmap(sizeBitmap), pal(gh.streamRGBSizeCustomCompressor), zBitmap, zRgb;
+                if (!yaikzstd::decompress(bitmap.data(), bitmap.size(), after, gh.streamBitmapSize)) return 6;
+                if (!yaikzstd::decompress(pal.data(), pal.size(), after + gh.streamBitmapSize, gh.streamRGBSizeZStd)) return 6;
+                const size_t firstToken = 4 + 3 * (size_t)pal[0];
+                if (firstToken >= pal.size()) return 6;
+                pal[firstToken] = 0x97;                                     // kind 2: an extension code no decoder implements
+                std::string err;
+                if (!yaikchunk::compressStream(bitmap.data(), bitmap.size(), 18, zBitmap, err) || !yaikchunk::compressStream(pal.data(), pal.size(), 18, zRgb, err)) return 6;
+                char* chunk = nullptr; size_t chunkLen = 0;                 // the chunk writers take a FILE*: one that lives in memory
+                FILE* mem = open_memstream(&chunk, &chunkLen); if (!mem) return 6;
+                const bool emitted = yaikchunk::emitGradientTile(mem, fh.width, fh.height, sx, sy, bitmap.data(), gh.streamRGBSizeUncompressed, (u32)pal.size(),
+                                                                 zBitmap, zRgb, gh.colorCompression, gh.plane, err);
+                fclose(mem);                                                // chunk / chunkLen are final now
+                if (!emitted) { free(chunk); return 6; }
+                std::vector<u8> crafted(file.begin(), file.begin() + (long)o);
+                crafted.insert(crafted.end(), (const u8*)chunk, (const u8*)chunk + chunkLen);
+                free(chunk);
+                crafted.insert(crafted.end(), file.begin() + (long)next, file.end());
+                decode_once(crafted, 0, "bad_off");
+                decode_once(crafted, 1, "bad_on");
+                return 0;
+            }
+        }
+        o = next;
+    }
+    return 7;                                                               // no such chunk in the file
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: host_driver in.bin out.blobs [mode3]\n"); return 2; }
     if (argc > 3 && (std::string(argv[1]) == "decode" || std::string(argv[1]) == "decode_device")) {
         gOut = fopen(argv[2], "wb"); if (!gOut) return 2;
         const int rc = std::string(argv[1]) == "decode" ? run_decode_sequence(argc - 3, argv + 3) : run_decode_device(argc - 3, argv + 3);
+        fclose(gOut);
+        return rc;
+    }
+    if (argc > 3 && std::string(argv[1]) == "decode_palette") {
+        gOut = fopen(argv[2], "wb"); if (!gOut) return 2;
+        const int rc = run_decode_palette(argv[3]);
         fclose(gOut);
         return rc;
     }

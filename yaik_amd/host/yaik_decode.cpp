@@ -1,6 +1,7 @@
 // See yaik_decode.h.  Control flow mirrors decoder/YAIK_API.cpp (Init :86-131, Pre :441-497, DecodeImage :600-1342): slot
 // stack, first-error-wins sticky code, chunk state machine, "Pre must be followed by Decode".  The per-pixel work is done by
-// the HIP kernels behind yk_decode_*; ZStd and PaletteDecompressor run on the host like in the reference.
+// the HIP kernels behind yk_decode_*; ZStd runs on the host like in the reference, and so does PaletteDecompressor unless
+// YAIK_SetDevicePalette(1) sends the 'GTIL' payloads of whole-RGB chunks to yk_decode_gradient_palette.
 #include "yaik_decode.h"
 #include <atomic>
 #include <cstdlib>
@@ -49,6 +50,8 @@ bool zexpand(const uint8_t* src, uint32_t n, uint32_t expected, std::vector<uint
 void YAIK_SetDevice(int device) { gDevice = device; }
 static int gConsistentMarks = 0;
 void YAIK_SetPartialPlaneMarks(int consistent) { gConsistentMarks = consistent ? 1 : 0; }
+static int gDevicePalette = 0;
+void YAIK_SetDevicePalette(int on) { gDevicePalette = on ? 1 : 0; }
 
 YAIK_LIB YAIK_Init(uint8_t maxDecodeThreadContext, YAIK_SMemAlloc* libraryMemAllocator) {
     if (maxDecodeThreadContext == 0) { setError(YAIK_INVALID_CONTEXT_COUNT); return nullptr; }
@@ -163,6 +166,12 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
                 const uint32_t sizeBitmap = (uint32_t)(((w + bigX - 1) / bigX) * ((h + bigY - 1) / bigY) * bitCount / 8);
                 if (!zexpand(after, gh.streamBitmapSize, sizeBitmap, bitmap, 0)) { bad = true; break; }
                 if (!zexpand(after + gh.streamBitmapSize, gh.streamRGBSizeZStd, gh.streamRGBSizeCustomCompressor, pal, 128 * 3)) { bad = true; break; }
+                if (gDevicePalette && gh.plane == 7 && gh.streamRGBSizeUncompressed % 3 == 0) {
+                    // YAIK_SetDevicePalette(1): the payload goes to the device as it is; PaletteDecompressor, its status check and the pass run there
+                    if (yk_decode_gradient_palette(s->ctx, sx, sy, bitmap.data(), sizeBitmap, pal.data(), gh.streamRGBSizeCustomCompressor,
+                                                   gh.streamRGBSizeUncompressed, gh.colorCompression) != YK_OK) { setError(YAIK_INVALID_STREAM); bad = true; }
+                    break;
+                }
                 const size_t slack = (size_t)((w + 3) >> 2) * ((h + 3) >> 2) * 12;                          // the reference's "secure buffer" (:901)
                 rgb.assign((size_t)gh.streamRGBSizeUncompressed + slack, 0);
                 if (!PaletteDecompressor(pal.data(), (int)gh.streamRGBSizeCustomCompressor, (int)gh.streamRGBSizeCustomCompressor + 128 * 3, rgb.data(),

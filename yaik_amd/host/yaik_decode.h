@@ -79,3 +79,7 @@ bool            YAIK_DecodeImageToDevice(void* sourceStreamAligned, uint32_t str
 // tile4x4MaskSize/2; decoder/YAIK_Gradient.cpp:1420-2732), after which the reference's own Decompress1D reads a different number of
 // tiles than the encoder wrote; 1 = every pass marks the planes it filled, which decodes such streams correctly.
 void            YAIK_SetPartialPlaneMarks(int consistent);
+// extension: where PaletteDecompressor runs for 'GTIL' chunks of all three planes (HeaderGradientTile::plane 7).  0 (default) = on the host
+// (palette.cpp), the expanded colour stream is uploaded; 1 = the payload is uploaded as ZStd left it and decompressed on the device
+// (yk_decode_gradient_palette).  Same images; a malformed payload gives YAIK_INVALID_STREAM either way.  Plane-subset chunks stay on the host.
+void            YAIK_SetDevicePalette(int on);
