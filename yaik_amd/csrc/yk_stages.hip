@@ -19,9 +19,15 @@
 //
 // ONE kernel (round 3: a clear of the flag map, a flagging kernel over single image rows with idempotent byte stores, and a
 // bounding-box kernel over the flags -- three stream operations in every frame's chain of short kernels).  A work unit is
-// (row of 16x16 tiles, 1024-pixel segment): the workgroup owns its 64 tiles, so it writes their flags outright (nothing to
-// clear) and knows their box.  The plane is streamed with 16-byte loads, eight in flight per lane, a wave instruction covering
-// 1 KB of one row; four adjacent lanes hold the 16 columns of one tile: 268 MB in 41 us = 6.5 TB/s without the box.
+// (YK_ALPHA_ROWS rows of 16x16 tiles, 1024-pixel segment): the workgroup owns its tiles, so it writes their flags outright (nothing
+// to clear) and knows their box.  The plane is read with 16-byte loads, a wave instruction covering 1 KB of one row; four adjacent
+// lanes hold the 16 columns of one tile.  One non-zero sample decides a tile, so a unit reads in two steps: every lane PROBES the
+// first and the last row of each of its tiles (all probe loads of the unit in flight together, addresses clamped, no branch), one
+// ballot per row of tiles gives the tiles already known to be kept, and only the lanes of tiles still undecided read the 14 rows
+// in between, all of them in flight before one wait.  A wave without an undecided tile issues nothing of the second step.  HBM serves 128-byte
+// requests = the lanes of two adjacent tiles: an opaque region costs 2 of its 16 rows, a transparent one all 16 (as before).  The
+// first and the last row are the two that the partly covered tiles along the top and the bottom of an opaque shape have in common with it
+// (tiles along its sides are non-zero in every row); only a blob strictly inside a tile's rows 1..14 needs the second step to be kept.
 // The image-wide box WITHOUT atomics on its four words (every form of guarded atomicMin / atomicMax on them, dealt from the image's
 // outside inwards or not, cost 23-85 us: a single address sustains ~88 atomics per microsecond, coherent guard reads are served by
 // the same L2 channel one after the other): every unit leaves its box in a slot of its own (write-through store), arrivals are
@@ -29,9 +35,6 @@
 // slots into bounds[8..11] = {min x0, min y0, max x1, max y1} ({9999999, 9999999, -1, -1} when nothing is kept).
 // ------------------------------------------------------------------------------------------------------------------
 typedef int yk_i4 __attribute__((ext_vector_type(4)));
-#ifndef YK_ALPHA_INFLIGHT
-#define YK_ALPHA_INFLIGHT 8                                                  // 16-byte loads a lane has in flight (two batches per unit)
-#endif
 #ifndef YK_ALPHA_THREADS
 #define YK_ALPHA_THREADS 256                                                 // 256: a unit = 1024 pixels x 16 rows (four waves); 64: 256 pixels x 16 rows (one wave per workgroup)
 #endif
@@ -63,24 +66,55 @@ __global__ __launch_bounds__(YK_ALPHA_THREADS) void yk_alpha_kernel(const int32_
         const bool tileLane = (lane & 3) == 0;
         const int tx = xv >> 2;
         int colLo = 0x7FFFFFFF, colHi = -1, rowLo = 0x7FFFFFFF, rowHi = -1;      // wave-uniform: kept tile columns / rows of this wave's share of the unit
+        // ---- probe: rows 0 and 15 of every tile of the unit.  Addresses are clamped (column into the row, row 15 onto the image's last row) and
+        // every lane loads: no load sits in a branch, all YK_ALPHA_ROWS * 2 are in flight together; what a clamped lane read is masked afterwards.
+        const int xvc = min(xv, vecPerRow - 1);
+        int nzR[YK_ALPHA_ROWS];
+        bool und[YK_ALPHA_ROWS];
+        {
+            yk_i4 p[YK_ALPHA_ROWS][2];
+#pragma unroll
+            for (int r = 0; r < YK_ALPHA_ROWS; r++) {
+                const int yA = min((tyU * YK_ALPHA_ROWS + r) * 16, h - 1), yB = min(yA + 15, h - 1);
+                p[r][0] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(alpha + (size_t)yA * strideElems + (size_t)xvc * 4));
+                p[r][1] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(alpha + (size_t)yB * strideElems + (size_t)xvc * 4));
+            }
+            bool anyUnd = false;
+#pragma unroll
+            for (int r = 0; r < YK_ALPHA_ROWS; r++) {
+                const bool on = inX && (tyU * YK_ALPHA_ROWS + r) * 16 < h;      // the lane's 4 columns and the tile's first row are inside the image
+                const yk_i4 o = p[r][0] | p[r][1];
+                nzR[r] = on ? (o.x | o.y | o.z | o.w) : 0;
+                const unsigned long long pb = __ballot(nzR[r] != 0);
+                und[r] = on && ((pb >> (lane & ~3)) & 0xFULL) == 0;              // nothing seen in the tile's probed rows: rows 1..14 decide
+                anyUnd |= und[r];
+            }
+            // ---- the rows in between, for undecided tiles only.  One wave-uniform region around all of it (a wave of decided tiles issues none of
+            // these instructions); inside, the YK_ALPHA_ROWS * 14 loads are issued under the lanes' masks and waited for once (128 VGPRs, as many
+            // waves per SIMD as the 116 of the kernel that read 16 rows per tile).
+            if (__ballot(anyUnd) != 0) {
+                yk_i4 a[YK_ALPHA_ROWS][14];
+#pragma unroll
+                for (int r = 0; r < YK_ALPHA_ROWS; r++) {
+                    const int ty = tyU * YK_ALPHA_ROWS + r;
+                    const int32_t* col = alpha + (size_t)(ty * 16) * strideElems + (size_t)xv * 4;
+#pragma unroll
+                    for (int k = 0; k < 14; k++) {
+                        a[r][k] = (yk_i4){0, 0, 0, 0};
+                        if (und[r] && ty * 16 + 1 + k < h) a[r][k] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(col + (size_t)(1 + k) * strideElems));
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < YK_ALPHA_ROWS; r++)
+#pragma unroll
+                    for (int k = 0; k < 14; k++) nzR[r] |= a[r][k].x | a[r][k].y | a[r][k].z | a[r][k].w;
+            }
+        }
 #pragma unroll
         for (int r = 0; r < YK_ALPHA_ROWS; r++) {
             const int ty = tyU * YK_ALPHA_ROWS + r;
             if (ty >= mtH) break;
-            const int32_t* col = alpha + (size_t)(ty * 16) * strideElems + (size_t)xv * 4;
-            int nz = 0;
-#pragma unroll
-            for (int kb = 0; kb < 16 / YK_ALPHA_INFLIGHT; kb++) {
-                yk_i4 a[YK_ALPHA_INFLIGHT];
-#pragma unroll
-                for (int k = 0; k < YK_ALPHA_INFLIGHT; k++) {
-                    const int y = ty * 16 + kb * YK_ALPHA_INFLIGHT + k;
-                    a[k] = (yk_i4){0, 0, 0, 0};
-                    if (inX && y < h) a[k] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(col + (size_t)(kb * YK_ALPHA_INFLIGHT + k) * strideElems));
-                }
-#pragma unroll
-                for (int k = 0; k < YK_ALPHA_INFLIGHT; k++) nz |= a[k].x | a[k].y | a[k].z | a[k].w;
-            }
+            const int nz = nzR[r];
             const unsigned long long b = __ballot(nz != 0);
             const bool kept = ((b >> (lane & ~3)) & 0xFULL) != 0;
             if (tileLane && tx < mtW) keep[(size_t)ty * mtW + tx] = kept ? 1 : 0;
