@@ -273,8 +273,9 @@ int yk_decode_gradient_palette(yk_ctx* c, int tileShiftX, int tileShiftY, const 
  * With two handles (two streams) in flight the HBM-bound alpha / compaction kernels of one frame run under the fused kernel of
  * the other.  Two fused kernels sharing the chip only slow each other down, so a caller that alternates handles can order them:
  * the NEXT yk_encode_tiles of c launches its fused kernel after the fused kernel most recently launched on `other` has finished
- * (a stream-wait on an event, no host synchronisation; the alpha stage and the compaction of c are not held back).  Same device;
- * `other` must stay alive until that encode of c has been issued (the event belongs to it).  The request is consumed by the next
+ * (one stream-wait on the event behind that kernel, queued on c's own stream where the fused kernel is launched; no host synchronisation; the
+ * alpha stage and the compaction of c are not held back).  Same device.  `other` may be destroyed before that encode of c is issued:
+ * the two handles share the ownership of the event.  A handle that has never encoded orders nothing.  The request is consumed by the next
  * yk_encode_tiles / yk_encode_batch / yk_encode_frame of c (the last one holds its whole replay back) and dropped by yk_set_image. */
 int yk_order_fused_after(yk_ctx* c, const yk_ctx* other);
 
@@ -629,8 +630,10 @@ int yk_decode_compare_planes_device(yk_ctx* c, const int32_t* const frame0Planes
                                     size_t frameStrideElems, int channels,
                                     yk_quality* out, uint32_t* devTileSse);
 
-/* ---- timing hooks for bench.py: HIP events on the handle's stream around every alpha stage / fused kernel / compaction.
- * Returns the averages over the yk_encode_tiles calls since the previous query (a ring of 64 event sets, older ones are
+/* ---- timing hooks for bench.py: HIP events on the handle's stream around the alpha stage, the fused kernel (alone) and the compaction.
+ * One record separates the alpha kernel from the fused kernel; it sits behind the wait of yk_order_fused_after, so a handle that is held
+ * back there counts the wait as alpha time.  yk_encode_frame records one interval around its replay, reported as the fused kernel's.
+ * An interval that did not take place (alpha of an RGB image, compaction of a replay) counts as 0.  Returns the averages over the yk_encode_tiles calls since the previous query (a ring of 64 event sets, older ones are
  * dropped), so a caller can queue many frames back to back and read the per-kernel times once, without a sync per frame.
  * Synchronises with the most recent encode. */
 int yk_last_kernel_ms(yk_ctx* c, float* fusedEncodeMs, float* alphaMs, float* packMs);

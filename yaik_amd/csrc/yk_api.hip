@@ -193,7 +193,8 @@ int yk_create(int device, yk_ctx** out) {
     if (hipDeviceGetAttribute(&c->numCU, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->numCU <= 0) c->numCU = 256;
     if (hipStreamCreateWithFlags(&c->ownStream, hipStreamNonBlocking) != hipSuccess) { delete c; return YK_ERR_HIP; }
     c->stream = c->ownStream;
-    for (int r = 0; r < YK_EV_RING; r++) for (int i = 0; i < 5; i++) if (hipEventCreate(&c->evRing[r][i]) != hipSuccess) { delete c; return YK_ERR_HIP; }
+    c->evRing = std::make_shared<YkEvRing>();
+    for (auto& set : c->evRing->ev) for (hipEvent_t& e : set) if (hipEventCreate(&e) != hipSuccess) { delete c; return YK_ERR_HIP; }
     if (yk_qtab_get(c) != YK_OK) { yk_destroy(c); return YK_ERR_HIP; }
     *out = c;
     return YK_OK;
@@ -211,13 +212,11 @@ void yk_destroy(yk_ctx* c) {
     yk_pal_free(c);
     yk_pd_free(c);
     F(c->ownedPlanes); F(c->pxStage); F(c->dScratch); F(c->dAlpha); F(c->dAvScratch); F(c->avState); F(c->avPay); F(c->av6); F(c->avTab); F(c->qBuf);
-    for (int r = 0; r < YK_EV_RING; r++) for (int i = 0; i < 5; i++) if (c->evRing[r][i]) (void)hipEventDestroy(c->evRing[r][i]);
+    c->fusedAfter = nullptr; c->fusedAfterRing.reset(); c->evRing.reset();     // a ring lives on while another handle still waits on one of its events
     for (int st = 0; st < YK_NUM_STAGES; st++) for (int k = 0; k < YK_STAGE_RING; k++) for (int i = 0; i < 2; i++) if (c->stEv[st][k][i]) (void)hipEventDestroy(c->stEv[st][k][i]);
     if (c->frameGraph) (void)hipGraphExecDestroy(c->frameGraph);
     if (c->evHandoff) (void)hipEventDestroy(c->evHandoff);
     if (c->evPixCopy) (void)hipEventDestroy(c->evPixCopy);
-    if (c->evFusedAfter) (void)hipEventDestroy(c->evFusedAfter);
-    if (c->auxStream) (void)hipStreamDestroy(c->auxStream);
     if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     delete c;
 }
@@ -255,7 +254,7 @@ int yk_set_image(yk_ctx* c, int fullW, int fullH, int nPlanes, int y0, int h, in
     if (y0 + h < fullH && ((h & 63) || haloRows != 1)) return yk_fail(c, YK_ERR_BAD_ARG, "inner stripes need h % 64 == 0 and one halo row");
     if (y0 + h == fullH && haloRows != 0) return yk_fail(c, YK_ERR_BAD_ARG, "the last stripe has no halo row");
     YK_HIP(c, hipSetDevice(c->device));
-    c->fusedAfter = nullptr;                                                 // an ordering request never outlives the image it was made for
+    c->fusedAfter = nullptr; c->fusedAfterRing.reset();                      // an ordering request never outlives the image it was made for
     if (c->fullW == fullW && c->fullH == fullH && c->nPlanes == nPlanes && c->y0 == y0 && c->h == h && c->halo == haloRows && c->tileCount) {
         c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
         return YK_OK;
@@ -489,11 +488,10 @@ int yk_alpha_reject(yk_ctx* c) {
     if (!c->plane[0]) return yk_fail(c, YK_ERR_STATE, "bind planes first");
     if (c->nPlanes != 4) return yk_fail(c, YK_ERR_STATE, "image has no alpha plane");
     YK_HIP(c, hipSetDevice(c->device));
-    hipEvent_t* ev = c->evRing[c->evHead % YK_EV_RING];
-    YK_HIP(c, hipEventRecord(ev[0], c->stream));
+    hipEvent_t* ev = c->evRing->ev[c->evHead % YK_EV_RING];
+    YK_HIP(c, hipEventRecord(ev[YK_EV_A0], c->stream));
     int rc = yk_launch_alpha(c); if (rc) return rc;
-    YK_HIP(c, hipEventRecord(ev[1], c->stream));
-    c->evAlphaInCur = true;
+    c->evAlphaInCur = true;                                                  // the interval ends with the record in front of the fused kernel
     c->alphaDone = true; c->alphaFinished = false; c->avBatchValid = false;
     return YK_OK;
 }
@@ -589,6 +587,26 @@ int yk_set_pixel_cache(yk_ctx* c, int enable) {
 
 int yk_set_dst_fill(yk_ctx* c, int32_t fill) { if (!c) return YK_ERR_BAD_ARG; c->dstFill = fill; return YK_OK; }
 
+// In front of a fused kernel (or a whole replay): the one wait of yk_order_fused_after, queued where the launch is queued, and behind it the
+// one record that ends the alpha interval and begins the encode interval.
+static int yk_fused_begin(yk_ctx* c, hipEvent_t* ev) {
+    if (c->fusedAfter) {
+        const hipError_t e = hipStreamWaitEvent(c->stream, c->fusedAfter, 0);
+        c->fusedAfter = nullptr; c->fusedAfterRing.reset();
+        if (e != hipSuccess) return yk_fail(c, YK_ERR_HIP, "hipStreamWaitEvent (yk_order_fused_after)", e);
+    }
+    YK_HIP(c, hipEventRecord(ev[YK_EV_E0], c->stream));
+    return YK_OK;
+}
+
+// the event set of the encode just queued is complete: which of its intervals exist, and the ring moves on
+static void yk_ev_commit(yk_ctx* c, int has) {
+    c->evHas[c->evHead % YK_EV_RING] = (uint8_t)has;
+    c->evAlphaInCur = false;
+    c->evHead++;
+    if (c->evHead - c->evTail > YK_EV_RING) c->evTail = c->evHead - YK_EV_RING;       // the oldest sets were overwritten
+}
+
 int yk_encode_tiles(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst) {
     if (!c) return YK_ERR_BAD_ARG;
     if (!c->plane[0]) return yk_fail(c, YK_ERR_STATE, "bind planes first");
@@ -607,17 +625,13 @@ int yk_encode_tiles(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst) 
             }
         }
     }
-    hipEvent_t* ev = c->evRing[c->evHead % YK_EV_RING];
-    if (!c->evAlphaInCur) { YK_HIP(c, hipEventRecord(ev[0], c->stream)); YK_HIP(c, hipEventRecord(ev[1], c->stream)); }   // no alpha stage: zero-length interval
-    if (c->fusedAfter) { YK_HIP(c, hipStreamWaitEvent(c->stream, c->fusedAfter, 0)); c->fusedAfter = nullptr; }   // yk_order_fused_after
-    YK_HIP(c, hipEventRecord(ev[2], c->stream));
-    int rc = yk_launch_encode(c, rejectFactor, mode3BitOnly, wantDst); if (rc) return rc;
-    YK_HIP(c, hipEventRecord(ev[3], c->stream));
+    hipEvent_t* ev = c->evRing->ev[c->evHead % YK_EV_RING];
+    int rc = yk_fused_begin(c, ev); if (rc) return rc;
+    rc = yk_launch_encode(c, rejectFactor, mode3BitOnly, wantDst); if (rc) return rc;
+    YK_HIP(c, hipEventRecord(ev[YK_EV_E1], c->stream));
     rc = yk_launch_pack(c); if (rc) return rc;
-    YK_HIP(c, hipEventRecord(ev[4], c->stream));
-    c->evAlphaInCur = false;
-    c->evHead++;
-    if (c->evHead - c->evTail > YK_EV_RING) c->evTail = c->evHead - YK_EV_RING;       // the oldest sets were overwritten
+    YK_HIP(c, hipEventRecord(ev[YK_EV_P1], c->stream));
+    yk_ev_commit(c, (c->evAlphaInCur ? YK_EVSET_ALPHA : 0) | YK_EVSET_PACK);
     c->encoded = true; c->dstValid = wantDst != 0; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
     return YK_OK;
 }
@@ -625,18 +639,13 @@ int yk_encode_tiles(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst) 
 int yk_order_fused_after(yk_ctx* c, const yk_ctx* other) {
     if (!c || !other) return YK_ERR_BAD_ARG;
     if (c->device != other->device) return yk_fail(c, YK_ERR_BAD_ARG, "yk_order_fused_after: handles of one device");
-    c->fusedAfter = nullptr;
+    c->fusedAfter = nullptr; c->fusedAfterRing.reset();
     if (!other->evHead) return YK_OK;
-    // Nothing of `other` is kept beyond this call (it may be destroyed before c encodes again): an auxiliary stream of c waits for the end of
-    // other's fused kernel NOW, while that event certainly exists, and an event of c's own is recorded behind the wait; c's next fused
-    // kernel waits for that one.
-    YK_HIP(c, hipSetDevice(c->device));
-    if (!c->auxStream) YK_HIP(c, hipStreamCreateWithFlags(&c->auxStream, hipStreamNonBlocking));
-    if (!c->evFusedAfter) YK_HIP(c, hipEventCreateWithFlags(&c->evFusedAfter, hipEventDisableTiming));
-    static const int afterPack = getenv("YK_ORDER_AFTER_PACK") ? atoi(getenv("YK_ORDER_AFTER_PACK")) : 0;      // experiment switch
-    YK_HIP(c, hipStreamWaitEvent(c->auxStream, other->evRing[(other->evHead - 1) % YK_EV_RING][afterPack ? 4 : 3], 0));
-    YK_HIP(c, hipEventRecord(c->evFusedAfter, c->auxStream));
-    c->fusedAfter = c->evFusedAfter;
+    // Nothing is queued here: c's next encode call waits, on its own stream and directly in front of its fused kernel, for the "encode end" record
+    // behind the fused kernel other queued last.  other may be destroyed before that: c shares the ownership of other's ring.  (Should other queue
+    // YK_EV_RING further encodes before c's next one, the set is in use again and the wait covers a later fused kernel of other's stream.)
+    c->fusedAfterRing = other->evRing;
+    c->fusedAfter = other->evRing->ev[(other->evHead - 1) % YK_EV_RING][YK_EV_E1];
     return YK_OK;
 }
 
@@ -648,20 +657,19 @@ int yk_encode_batch(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
     if (c->kernelVersion != 2) return yk_fail(c, YK_ERR_STATE, "batches need kernel version 2");
     if (c->nFrames > 1 && c->fs.plane == 0) return yk_fail(c, YK_ERR_STATE, "yk_bind_device_batch first");
     YK_HIP(c, hipSetDevice(c->device));
-    hipEvent_t* ev = c->evRing[c->evHead % YK_EV_RING];
-    YK_HIP(c, hipEventRecord(ev[0], c->stream));
+    hipEvent_t* ev = c->evRing->ev[c->evHead % YK_EV_RING];
     int rc = YK_OK;
-    if (c->nPlanes == 4) rc = yk_launch_alpha(c, true);                     // every frame's bbox kernel publishes its own bounds[0..4]
-    if (rc) return rc;
-    YK_HIP(c, hipEventRecord(ev[1], c->stream));
-    if (c->fusedAfter) { YK_HIP(c, hipStreamWaitEvent(c->stream, c->fusedAfter, 0)); c->fusedAfter = nullptr; }   // yk_order_fused_after
-    YK_HIP(c, hipEventRecord(ev[2], c->stream));
+    if (c->nPlanes == 4) {
+        YK_HIP(c, hipEventRecord(ev[YK_EV_A0], c->stream));
+        rc = yk_launch_alpha(c, true);                                      // every frame's bbox kernel publishes its own bounds[0..4]
+        if (rc) return rc;
+    }
+    rc = yk_fused_begin(c, ev); if (rc) return rc;
     rc = yk_launch_encode(c, rejectFactor, mode3BitOnly, 0, true); if (rc) return rc;
-    YK_HIP(c, hipEventRecord(ev[3], c->stream));
+    YK_HIP(c, hipEventRecord(ev[YK_EV_E1], c->stream));
     rc = yk_launch_pack(c, true); if (rc) return rc;
-    YK_HIP(c, hipEventRecord(ev[4], c->stream));
-    c->evAlphaInCur = false; c->evHead++;
-    if (c->evHead - c->evTail > YK_EV_RING) c->evTail = c->evHead - YK_EV_RING;
+    YK_HIP(c, hipEventRecord(ev[YK_EV_P1], c->stream));
+    yk_ev_commit(c, (c->nPlanes == 4 ? YK_EVSET_ALPHA : 0) | YK_EVSET_PACK);
     c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false;
     c->encoded = true; c->dstValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
     return YK_OK;
@@ -693,13 +701,11 @@ int yk_encode_frame(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
         if (e2 != hipSuccess) { c->frameGraph = nullptr; return yk_fail(c, YK_ERR_HIP, "hipGraphInstantiate", e2); }
         memcpy(c->frameGraphKey, key, sizeof key);
     }
-    hipEvent_t* ev = c->evRing[c->evHead % YK_EV_RING];                     // one interval for the whole frame (reported as "encode")
-    if (c->fusedAfter) { YK_HIP(c, hipStreamWaitEvent(c->stream, c->fusedAfter, 0)); c->fusedAfter = nullptr; }   // yk_order_fused_after: the whole replay waits
-    YK_HIP(c, hipEventRecord(ev[0], c->stream)); YK_HIP(c, hipEventRecord(ev[1], c->stream)); YK_HIP(c, hipEventRecord(ev[2], c->stream));
+    hipEvent_t* ev = c->evRing->ev[c->evHead % YK_EV_RING];                 // one interval for the whole frame (reported as "encode"), recorded around the replay
+    { const int rc = yk_fused_begin(c, ev); if (rc) return rc; }            // yk_order_fused_after: the whole replay waits
     YK_HIP(c, hipGraphLaunch(c->frameGraph, c->stream));
-    YK_HIP(c, hipEventRecord(ev[3], c->stream)); YK_HIP(c, hipEventRecord(ev[4], c->stream));
-    c->evAlphaInCur = false; c->evHead++;
-    if (c->evHead - c->evTail > YK_EV_RING) c->evTail = c->evHead - YK_EV_RING;
+    YK_HIP(c, hipEventRecord(ev[YK_EV_E1], c->stream));
+    yk_ev_commit(c, 0);
     c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false;
     c->encoded = true; c->dstValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
     return YK_OK;
@@ -893,15 +899,19 @@ int yk_last_kernel_ms(yk_ctx* c, float* fusedEncodeMs, float* alphaMs, float* pa
     if (!c) return YK_ERR_BAD_ARG;
     if (!c->encoded || c->evHead == c->evTail) return yk_fail(c, YK_ERR_STATE, "yk_encode_tiles first");
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, hipEventSynchronize(c->evRing[(c->evHead - 1) % YK_EV_RING][4]));
+    {
+        const unsigned last = (c->evHead - 1) % YK_EV_RING;
+        YK_HIP(c, hipEventSynchronize(c->evRing->ev[last][(c->evHas[last] & YK_EVSET_PACK) ? YK_EV_P1 : YK_EV_E1]));
+    }
     double a = 0, e = 0, p = 0;
     const unsigned n = c->evHead - c->evTail;
     for (unsigned k = c->evTail; k != c->evHead; k++) {                         // average over the encodes since the last query
-        hipEvent_t* ev = c->evRing[k % YK_EV_RING];
+        hipEvent_t* ev = c->evRing->ev[k % YK_EV_RING];
+        const int has = c->evHas[k % YK_EV_RING];                                // an interval that did not take place (RGB image, graph replay) counts as zero
         float t = 0;
-        YK_HIP(c, hipEventElapsedTime(&t, ev[0], ev[1])); a += t;
-        YK_HIP(c, hipEventElapsedTime(&t, ev[2], ev[3])); e += t;
-        YK_HIP(c, hipEventElapsedTime(&t, ev[3], ev[4])); p += t;
+        if (has & YK_EVSET_ALPHA) { YK_HIP(c, hipEventElapsedTime(&t, ev[YK_EV_A0], ev[YK_EV_E0])); a += t; }
+        YK_HIP(c, hipEventElapsedTime(&t, ev[YK_EV_E0], ev[YK_EV_E1])); e += t;
+        if (has & YK_EVSET_PACK) { YK_HIP(c, hipEventElapsedTime(&t, ev[YK_EV_E1], ev[YK_EV_P1])); p += t; }
     }
     c->evTail = c->evHead;
     if (fusedEncodeMs) *fusedEncodeMs = (float)(e / n);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/yaik_hip.h"
@@ -20,6 +21,19 @@
 struct YkFrameStrides {
     unsigned long long plane, keep, bitmap[7], coverage, tileDef, tileCount, slots, blockN, defsOut, nibOut;   // bounds: 16 ints, totals: 8 u32
     unsigned long long bm0b, tileInfo, runSums;   // the fused kernel's per-strip 16x16 bytes (u8), per-tile records (8 bytes each), run sums (u32)
+};
+
+// The timing events of a handle: sets of {alpha begin, encode begin, encode end, pack end}, stand-alone records on the launch stream.  "encode
+// begin" sits behind the ordering wait and is the end of the alpha interval as well, so ONE record separates the alpha kernel from the fused
+// kernel; "encode end" is also the event another handle's fused kernel waits on (yk_order_fused_after).  Shared ownership: that handle holds
+// on to the ring, so the event outlives this handle.
+enum { YK_EVSET_ALPHA = 1, YK_EVSET_PACK = 2 };
+enum { YK_EV_A0, YK_EV_E0, YK_EV_E1, YK_EV_P1, YK_EV_N };
+struct YkEvRing {
+    hipEvent_t ev[YK_EV_RING][YK_EV_N] = {};
+    YkEvRing() = default;
+    YkEvRing(const YkEvRing&) = delete; YkEvRing& operator=(const YkEvRing&) = delete;
+    ~YkEvRing() { for (auto& set : ev) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e); }
 };
 
 struct YkEncodeParams {
@@ -143,8 +157,9 @@ struct yk_ctx {
     uint32_t* totals = nullptr;         // [3][2] device
     unsigned long long* exportSizes = nullptr;   // [16] total + section sizes of the last yk_export_tile_maps
     hipEvent_t evHandoff = nullptr;              // yk_stream_handoff / yk_stream_wait_for
-    hipEvent_t fusedAfter = nullptr;             // yk_order_fused_after: the next fused kernel waits for this event (= evFusedAfter, never another handle's)
-    hipEvent_t evFusedAfter = nullptr; hipStream_t auxStream = nullptr;   // this handle's own: the event behind a wait for the other handle's fused kernel
+    // yk_order_fused_after: the next fused kernel waits for this event, the end of the other handle's fused kernel.  It belongs to that handle's
+    // ring, which fusedAfterRing keeps alive should the other handle be destroyed before this one encodes.
+    hipEvent_t fusedAfter = nullptr; std::shared_ptr<YkEvRing> fusedAfterRing;
     uint16_t* defsOut = nullptr;        // [3][T8]
     uint8_t*  nibOut = nullptr;         // [3][T8*32 + 8]
     size_t nibStride = 0;
@@ -203,11 +218,12 @@ struct yk_ctx {
     // yk_decode_compare_*: the folded u64 results of every frame, then one record per workgroup (grow-only; yk_quality.hip)
     uint8_t* qBuf = nullptr; size_t qBufBytes = 0;
     // timing
-    // timing events: a ring of YK_EV_RING sets {alpha begin, alpha end, encode begin, encode end, pack end} so that a caller can
-    // run many frames back to back and read the per-kernel averages afterwards without synchronising every frame
-    hipEvent_t evRing[YK_EV_RING][5] = {};
+    // timing events: a ring of YK_EV_RING sets (YkEvRing) so that a caller can run many frames back to back and read the per-kernel
+    // averages afterwards without synchronising every frame
+    std::shared_ptr<YkEvRing> evRing;
     unsigned evHead = 0, evTail = 0;      // sets [evTail, evHead) hold a completed encode; evCur = evHead % YK_EV_RING is being filled
     bool evAlphaInCur = false;
+    uint8_t evHas[YK_EV_RING] = {};       // per set: YK_EVSET_ALPHA, YK_EVSET_PACK = these intervals were taken (the encode interval always is)
     float msEncode = 0, msAlpha = 0, msPack = 0;
     // stage timers (yk_stage_ms): HIP events around the kernel sections of the stages outside the fused encode, on the launch stream
     hipEvent_t stEv[YK_NUM_STAGES][YK_STAGE_RING][2] = {};

@@ -264,16 +264,20 @@ __global__ __launch_bounds__(1024) void yk_scan1r_kernel(const uint32_t* __restr
     }
 }
 
-// One workgroup packs the nibbles of 1024 consecutive tiles, the three planes one after the other: a tile's count is the same in the three
-// planes, so ONE scan serves them all (round 3 ran a workgroup and two block scans per plane).  Every tile holds a multiple of 16 nibbles
-// (16 per uncovered 4x4 quadrant), so every stream offset is a multiple of 8 bytes: after the scan, four lanes per tile copy 8-byte pieces
-// of the tile's slot straight to its place in the stream, reading only the bytes that exist.
-__global__ __launch_bounds__(1024) void yk_pack_kernel(const uint8_t* __restrict__ tileCount, const uint16_t* __restrict__ tileDef, const uint2* __restrict__ tileInfo,
-                                                       const uint8_t* __restrict__ slots, size_t T8, const uint32_t* __restrict__ blockSums, int nBlocks,
-                                                       uint16_t* __restrict__ defsOut, uint32_t* __restrict__ nibOut, size_t nibStrideWords, YkFrameStrides fs,
-                                                       const uint32_t* __restrict__ blockCnt, uint32_t* __restrict__ totals) {
-    __shared__ uint32_t s_tmp[32];
-    __shared__ unsigned long long s_pre[17];
+// One workgroup of four waves packs the nibbles of 1024 consecutive tiles, the three planes one after the other: a tile's count is the same in the
+// three planes, so ONE scan serves them all, and it is a scan of one packed word per tile (nibbles | coded << 16: at most 1023 x 64 and 1023 in
+// front of a tile, no carry between the halves).  A lane holds four consecutive tiles (two 16-byte loads of their records), so the scan is a
+// wave scan of the lanes' sums plus three words across the waves.  Every tile holds a multiple of 16 nibbles (16 per uncovered 4x4 quadrant),
+// so every stream offset is a multiple of 8 bytes: after the scan two lanes per tile copy the halves of its slot straight to their place in
+// the stream, 16 bytes at a time where the half is whole and 8 where it is not, reading only the bytes that exist.  256 threads, because a
+// workgroup of 1024 needs 16 free wave slots on ONE compute unit and waits for them while a fused kernel holds the chip.
+struct __attribute__((aligned(8))) YkPiece16 { uint32_t a, b, c, d; };           // 16 bytes at an 8-byte aligned place of a stream
+__global__ __launch_bounds__(256) void yk_pack_kernel(const uint8_t* __restrict__ tileCount, const uint16_t* __restrict__ tileDef, const uint2* __restrict__ tileInfo,
+                                                      const uint8_t* __restrict__ slots, size_t T8, const uint32_t* __restrict__ blockSums, int nBlocks,
+                                                      uint16_t* __restrict__ defsOut, uint32_t* __restrict__ nibOut, size_t nibStrideWords, YkFrameStrides fs,
+                                                      const uint32_t* __restrict__ blockCnt, uint32_t* __restrict__ totals) {
+    __shared__ uint32_t s_wave[4];
+    __shared__ unsigned long long s_pre;
     __shared__ uint32_t s_off[YK_SCAN_TILE];
     __shared__ uint8_t s_cnt[YK_SCAN_TILE];
     {   // blockIdx.z = frame of a batch
@@ -283,54 +287,72 @@ __global__ __launch_bounds__(1024) void yk_pack_kernel(const uint8_t* __restrict
         defsOut += f * fs.defsOut; nibOut += f * (fs.nibOut / 4);
         if (blockCnt) { blockCnt += f * fs.blockN; totals += f * 8; }
     }
-    // Second scan level inside this kernel (second-generation fused kernel: the per-block sums come from yk_scan1r_kernel): the workgroup adds the
-    // sums of the blocks in front of it (at most 8 KB from L2) instead of waiting for a one-workgroup kernel in the frame's chain of launches.
-    uint32_t preN = 0, preD = 0;
-    if (blockCnt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t i0 = (size_t)blockIdx.x * YK_SCAN_TILE, i = i0 + (size_t)threadIdx.x * 4;
+    // second-generation fused kernel: one record per tile {def0 | def1 << 16, def2 | count << 16}; first generation: count and definition arrays
+    uint32_t c[4] = {0, 0, 0, 0}, d01[4] = {0, 0, 0, 0}, d2[4] = {0, 0, 0, 0};
+    if (tileInfo && i + 4 <= T8) {
+        const uint4 r0 = reinterpret_cast<const uint4*>(tileInfo + i)[0], r1 = reinterpret_cast<const uint4*>(tileInfo + i)[1];   // i is a multiple of 4, a frame starts at a multiple of 16 bytes
+        d01[0] = r0.x; c[0] = r0.y >> 16; d2[0] = r0.y & 0xFFFFu; d01[1] = r0.z; c[1] = r0.w >> 16; d2[1] = r0.w & 0xFFFFu;
+        d01[2] = r1.x; c[2] = r1.y >> 16; d2[2] = r1.y & 0xFFFFu; d01[3] = r1.z; c[3] = r1.w >> 16; d2[3] = r1.w & 0xFFFFu;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (i + j >= T8) continue;
+            if (tileInfo) { const uint2 ti = tileInfo[i + j]; c[j] = ti.y >> 16; d01[j] = ti.x; d2[j] = ti.y & 0xFFFFu; }
+            else { c[j] = tileCount[i + j]; if (c[j]) { d01[j] = (uint32_t)tileDef[i + j] | ((uint32_t)tileDef[T8 + i + j] << 16); d2[j] = tileDef[2 * T8 + i + j]; } }
+        }
+    }
+    // Second scan level inside this kernel (second-generation fused kernel: the per-block sums come from yk_scan1r_kernel): ONE wave adds the sums
+    // of the blocks in front of this one (at most 8 KB from L2, 16 independent loads per lane) while the others scan; nobody waits for another
+    // workgroup or for a one-workgroup kernel in the frame's chain of launches.
+    if (blockCnt && wave == 3) {
         unsigned long long acc = 0;                                               // coded tiles << 32 | nibbles
-        for (int k = threadIdx.x; k < (int)blockIdx.x; k += 1024) { const uint2 v = reinterpret_cast<const uint2*>(blockCnt)[k]; acc += ((unsigned long long)v.y << 32) | v.x; }
+        for (int k = lane; k < (int)blockIdx.x; k += 64) { const uint2 v = reinterpret_cast<const uint2*>(blockCnt)[k]; acc += ((unsigned long long)v.y << 32) | v.x; }
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) acc += __shfl_xor(acc, d);
-        if ((threadIdx.x & 63) == 0) s_pre[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) { unsigned long long t = 0; for (int k = 0; k < 16; k++) t += s_pre[k]; s_pre[16] = t; }
-        __syncthreads();
-        preN = (uint32_t)s_pre[16]; preD = (uint32_t)(s_pre[16] >> 32);
+        if (lane == 0) s_pre = acc;
+    }
+    uint32_t w[4], mine = 0;                                                      // the packed word of each tile, exclusive inside the lane
+#pragma unroll
+    for (int j = 0; j < 4; j++) { w[j] = mine; mine += c[j] | (c[j] ? 0x10000u : 0u); }
+    uint32_t incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t front = incl - mine;                                                 // tiles of this workgroup in front of the lane's
+#pragma unroll
+    for (int k = 0; k < 3; k++) if (k < wave) front += s_wave[k];
+    uint32_t baseN, baseD;
+    if (blockCnt) {
+        baseN = (uint32_t)s_pre; baseD = (uint32_t)(s_pre >> 32);
         if (blockIdx.x == (unsigned)nBlocks - 1 && threadIdx.x < 3) {            // the totals of the three planes (identical)
             const uint2 v = reinterpret_cast<const uint2*>(blockCnt)[nBlocks - 1];
-            totals[threadIdx.x * 2] = preD + v.y; totals[threadIdx.x * 2 + 1] = preN + v.x;
+            totals[threadIdx.x * 2] = baseD + v.y; totals[threadIdx.x * 2 + 1] = baseN + v.x;
         }
-    }
-    const size_t i0 = (size_t)blockIdx.x * YK_SCAN_TILE;
-    {
-        const size_t i = i0 + threadIdx.x;
-        // second-generation fused kernel: one record per tile {def0 | def1 << 16, def2 | count << 16}; first generation: count and definition arrays
-        uint32_t c = 0, d01 = 0, d2 = 0;
-        if (i < T8) {
-            if (tileInfo) { const uint2 ti = tileInfo[i]; c = ti.y >> 16; d01 = ti.x; d2 = ti.y & 0xFFFFu; }
-            else { c = tileCount[i]; if (c) { d01 = (uint32_t)tileDef[i] | ((uint32_t)tileDef[T8 + i] << 16); d2 = tileDef[2 * T8 + i]; } }
-        }
-        uint32_t totN, totD;
-        const uint32_t en = yk_block_exscan(c, s_tmp, &totN);
-        const uint32_t ed = yk_block_exscan(c ? 1u : 0u, s_tmp, &totD);
-        const uint32_t baseN = blockCnt ? preN : blockSums[(size_t)blockIdx.x * 2], baseD = blockCnt ? preD : blockSums[(size_t)blockIdx.x * 2 + 1];     // same for the three planes
-        s_off[threadIdx.x] = (baseN + en) >> 1;                                   // byte offset inside a plane's stream
-        s_cnt[threadIdx.x] = (uint8_t)c;
-        if (c) {
-            defsOut[baseD + ed] = (uint16_t)d01; defsOut[T8 + baseD + ed] = (uint16_t)(d01 >> 16); defsOut[2 * T8 + baseD + ed] = (uint16_t)d2;
-        }
+    } else { baseN = blockSums[(size_t)blockIdx.x * 2]; baseD = blockSums[(size_t)blockIdx.x * 2 + 1]; }     // same for the three planes
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t e = front + w[j], en = e & 0xFFFFu, ed = e >> 16;
+        s_off[threadIdx.x * 4 + j] = (baseN + en) >> 1;                           // byte offset inside a plane's stream
+        s_cnt[threadIdx.x * 4 + j] = (uint8_t)c[j];
+        if (c[j]) { defsOut[baseD + ed] = (uint16_t)d01[j]; defsOut[T8 + baseD + ed] = (uint16_t)(d01[j] >> 16); defsOut[2 * T8 + baseD + ed] = (uint16_t)d2[j]; }
     }
     __syncthreads();
-    const int piece = threadIdx.x & 3;
+    const int half = threadIdx.x & 1;
 #pragma unroll
     for (int p = 0; p < 3; p++) {
         uint8_t* out = reinterpret_cast<uint8_t*>(nibOut + (size_t)p * nibStrideWords);
 #pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int t = it * 256 + (threadIdx.x >> 2);
-            const size_t i = i0 + t;
-            if (i < T8 && piece * 8 < (s_cnt[t] >> 1))
-                *reinterpret_cast<uint2*>(out + s_off[t] + piece * 8) = *reinterpret_cast<const uint2*>(slots + ((size_t)p * T8 + i) * YK_SLOT + piece * 8);
+        for (int it = 0; it < 8; it++) {
+            const int t = it * 128 + (threadIdx.x >> 1);
+            const size_t ti = i0 + t;
+            const int left = (s_cnt[t] >> 1) - half * 16;                         // bytes of this half: a multiple of 8 (tiles past T8 hold 0)
+            const uint8_t* src = slots + ((size_t)p * T8 + ti) * YK_SLOT + half * 16;
+            uint8_t* dst = out + s_off[t] + half * 16;
+            if (left >= 16) { const uint4 v = *reinterpret_cast<const uint4*>(src); *reinterpret_cast<YkPiece16*>(dst) = YkPiece16{v.x, v.y, v.z, v.w}; }
+            else if (left >= 8) *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(src);
         }
     }
 }
@@ -433,7 +455,7 @@ int yk_launch_pack(yk_ctx* c, bool batch) {
                            batch ? c->B.bitmap[0] : c->bitmap[0], (unsigned long long)c->fs.bitmap[0], nB64);
     }
     if (!runSums) hipLaunchKernelGGL(yk_scan2_kernel, dim3(F), dim3(1024), 0, c->stream, blockCnt, blockSums, nb, totals, (unsigned long long)c->fs.blockN);
-    hipLaunchKernelGGL(yk_pack_kernel, dim3(nb, 1, F), dim3(1024), 0, c->stream, batch ? c->B.tileCount : c->tileCount, batch ? c->B.tileDef : c->tileDef, tileInfo,
+    hipLaunchKernelGGL(yk_pack_kernel, dim3(nb, 1, F), dim3(256), 0, c->stream, batch ? c->B.tileCount : c->tileCount, batch ? c->B.tileDef : c->tileDef, tileInfo,
                        batch ? c->B.slots : c->slots, T8, blockSums, nb, batch ? c->B.defsOut : c->defsOut, reinterpret_cast<uint32_t*>(nibOut), c->nibStride / 4, c->fs,
                        runSums ? blockCnt : (const uint32_t*)nullptr, totals);
     YK_HIP(c, hipGetLastError());
