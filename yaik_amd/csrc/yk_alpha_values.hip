@@ -353,22 +353,11 @@ int yk_decode_alpha(yk_ctx* c, int mode, const int32_t bbox[4], const uint8_t* p
     if (n < need) return yk_fail(c, YK_ERR_RANGE, "alpha payload shorter than its box");
     YK_HIP(c, hipSetDevice(c->device));
     const size_t plane = (size_t)W * H;
-    if (c->dAlphaBytes < plane) {
-        YK_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->dAlpha) { (void)hipFree(c->dAlpha); c->dAlpha = nullptr; c->dAlphaBytes = 0; }
-        YK_HIP(c, hipMalloc(&c->dAlpha, plane));
-        c->dAlphaBytes = plane;
-    }
+    YK_HIP(c, c->dAlpha.reserve(c->stream, plane));
     c->dAlphaValid = false; c->dAlphaBatch = false;
     const size_t oPay = 0, oMask = (n + 255) & ~(size_t)255, oRows = oMask + ((maskBytes + 255) & ~(size_t)255);
     const size_t scratch = oRows + ((size_t)bh * 2 + 2) * sizeof(uint32_t) + 64;
-    if (c->dAvScratchBytes < scratch) {
-        YK_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->dAvScratch) (void)hipFree(c->dAvScratch);
-        c->dAvScratch = nullptr; c->dAvScratchBytes = 0;
-        YK_HIP(c, hipMalloc(&c->dAvScratch, scratch));
-        c->dAvScratchBytes = scratch;
-    }
+    YK_HIP(c, c->dAvScratch.reserve(c->stream, scratch));
     uint8_t* S = c->dAvScratch;
     if (n) YK_HIP(c, hipMemcpyAsync(S + oPay, payload, n, hipMemcpyHostToDevice, c->stream));
     if (mode == 2 || mode == 3) {
@@ -422,14 +411,8 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     const int W = c->fullW, H = c->fullH;
     YK_HIP(c, hipSetDevice(c->device));
     c->avBatchValid = false;                                                              // the batch payloads share avState / avPay
-    if (!c->avState) YK_HIP(c, hipMalloc(&c->avState, 8 * sizeof(int32_t)));
-    if (c->avPayCap < (size_t)W * H) {
-        YK_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->avPay) (void)hipFree(c->avPay);
-        c->avPay = nullptr; c->avPayCap = 0;
-        YK_HIP(c, hipMalloc(&c->avPay, (size_t)W * H));
-        c->avPayCap = (size_t)W * H;
-    }
+    if (!c->avState) YK_HIP(c, c->avState.alloc(c->stream, 8));
+    YK_HIP(c, c->avPay.reserve(c->stream, (size_t)W * H));
     const int32_t init[8] = { INT_MAX, INT_MAX, -1, -1, 0, 0, 0, 0 };
     YK_HIP(c, hipMemcpyAsync(c->avState, init, sizeof init, hipMemcpyHostToDevice, c->stream));
     // the search region is at most the image; the kernel clamps it to the bounds the alpha stage left on the device
@@ -461,14 +444,8 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
         const int nb = ((bB - 1) >> 4) - (bT >> 4) + 1, ncol = ((bR - 1) >> 4) - (bL >> 4) + 1;
         const size_t nU32 = (size_t)nb * ncol + 3 * (size_t)nb + 1;
         const size_t oPay = (nU32 * sizeof(uint32_t) + 255) & ~(size_t)255, payCap = (size_t)(bw >> 2) * 3 * bh;
-        if (c->av6Cap < oPay + payCap) {
-            YK_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->av6) (void)hipFree(c->av6);
-            c->av6 = nullptr; c->av6Cap = 0;
-            YK_HIP(c, hipMalloc(&c->av6, oPay + payCap));
-            c->av6Cap = oPay + payCap;
-        }
-        uint32_t* colPre = reinterpret_cast<uint32_t*>(c->av6);
+        YK_HIP(c, c->av6.reserve(c->stream, oPay + payCap));
+        uint32_t* colPre = reinterpret_cast<uint32_t*>(c->av6.p);
         uint32_t* bandS = colPre + (size_t)nb * ncol;
         uint32_t* bandCnt = bandS + nb;
         uint32_t* bandStart = bandCnt + nb;
@@ -527,13 +504,7 @@ int yk_alpha_values_batch(yk_ctx* c, int force8Bit, yk_alpha_info* infos) {
     if (c->nPlanes != 4) { c->avBatchValid = true; return YK_OK; }                        // no alpha: no chunk in any frame (:1674-1680)
     const int W = c->fullW, H = c->fullH;
     YK_HIP(c, hipSetDevice(c->device));
-    if (c->avStateFrames < N) {
-        YK_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->avState) (void)hipFree(c->avState);
-        c->avState = nullptr; c->avStateFrames = 0;
-        YK_HIP(c, hipMalloc(&c->avState, (size_t)N * 8 * sizeof(int32_t)));
-        c->avStateFrames = N;
-    }
+    YK_HIP(c, c->avState.reserve(c->stream, (size_t)N * 8));
     std::vector<int32_t> st((size_t)N * 8);
     for (int f = 0; f < N; f++) { int32_t* s = &st[(size_t)f * 8]; s[0] = s[1] = INT_MAX; s[2] = s[3] = -1; s[4] = s[5] = s[6] = s[7] = 0; }
     YK_HIP(c, hipMemcpyAsync(c->avState, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
@@ -563,23 +534,11 @@ int yk_alpha_values_batch(yk_ctx* c, int force8Bit, yk_alpha_info* infos) {
         maxW = max(maxW, r.bw); maxH = max(maxH, r.bh);
     }
     if (tab.empty()) { c->avBatchValid = true; return YK_OK; }
-    if (c->avPayCap < total) {
-        YK_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->avPay) (void)hipFree(c->avPay);
-        c->avPay = nullptr; c->avPayCap = 0;
-        YK_HIP(c, hipMalloc(&c->avPay, total));
-        c->avPayCap = total;
-    }
+    YK_HIP(c, c->avPay.reserve(c->stream, total));
     const size_t tabBytes = tab.size() * sizeof(YkAvFrame);
-    if (c->avTabBytes < tabBytes) {
-        YK_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->avTab) (void)hipFree(c->avTab);
-        c->avTab = nullptr; c->avTabBytes = 0;
-        YK_HIP(c, hipMalloc(&c->avTab, (size_t)N * sizeof(YkAvFrame)));
-        c->avTabBytes = (size_t)N * sizeof(YkAvFrame);
-    }
+    if (c->avTab.cap < tabBytes) YK_HIP(c, c->avTab.reserve(c->stream, (size_t)N * sizeof(YkAvFrame)));      // grown when the records do not fit, then for every frame
     YK_HIP(c, hipMemcpyAsync(c->avTab, tab.data(), tabBytes, hipMemcpyHostToDevice, c->stream));
-    const YkAvFrame* dTab = reinterpret_cast<const YkAvFrame*>(c->avTab);
+    const YkAvFrame* dTab = reinterpret_cast<const YkAvFrame*>(c->avTab.p);
     const unsigned nBox = (unsigned)tab.size();
     hipLaunchKernelGGL(vec ? yk_ave_class_batch_kernel<true> : yk_ave_class_batch_kernel<false>, dim3((unsigned)((maxW / 4 + 255) / 256), (unsigned)maxH, nBox),
                        dim3(256), 0, c->stream, alpha, fe, c->strideElems, dTab, c->avPay, c->avState);
@@ -669,21 +628,10 @@ int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes, const int32_t*
     }
     YK_HIP(c, hipSetDevice(c->device));
     const size_t plane = (size_t)W * H, stride = (plane + 15) & ~(size_t)15;
-    if (c->dAlphaBytes < stride * N) {
-        YK_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->dAlpha) { (void)hipFree(c->dAlpha); c->dAlpha = nullptr; c->dAlphaBytes = 0; }
-        c->dAlphaValid = false;
-        YK_HIP(c, hipMalloc(&c->dAlpha, stride * N));
-        c->dAlphaBytes = stride * N;
-    }
+    if (c->dAlpha.cap < stride * N) c->dAlphaValid = false;
+    YK_HIP(c, c->dAlpha.reserve(c->stream, stride * N));
     const size_t tabBytes = (size_t)N * sizeof(YkAvDecFrame);
-    if (c->dAvScratchBytes < tabBytes) {
-        YK_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->dAvScratch) (void)hipFree(c->dAvScratch);
-        c->dAvScratch = nullptr; c->dAvScratchBytes = 0;
-        YK_HIP(c, hipMalloc(&c->dAvScratch, tabBytes));
-        c->dAvScratchBytes = tabBytes;
-    }
+    YK_HIP(c, c->dAvScratch.reserve(c->stream, tabBytes));
     int slot; void* host;
     { const int rc = yk_dec_table_host(c, tabBytes, &slot, &host); if (rc) return rc; }
     YkAvDecFrame* tab = static_cast<YkAvDecFrame*>(host);
@@ -697,7 +645,7 @@ int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes, const int32_t*
     c->dAlphaValid = false;
     { const int rc = yk_dec_table_upload(c, slot, c->dAvScratch, tabBytes); if (rc) return rc; }
     hipLaunchKernelGGL((W & 15) ? yk_av_decode_batch_kernel<true> : yk_av_decode_batch_kernel<false>, dim3((unsigned)((plane / 16 + 255) / 256), (unsigned)N),
-                       dim3(256), 0, c->stream, reinterpret_cast<const YkAvDecFrame*>(c->dAvScratch), W, H, c->dAlpha, stride,
+                       dim3(256), 0, c->stream, reinterpret_cast<const YkAvDecFrame*>(c->dAvScratch.p), W, H, c->dAlpha, stride,
                        (uint32_t)noChunkAlpha * 0x01010101u);
     YK_HIP(c, hipGetLastError());
     c->dAlphaValid = true; c->dAlphaBatch = true; c->dAlphaStride = stride;

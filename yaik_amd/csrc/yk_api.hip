@@ -34,42 +34,43 @@ void yk_rebase(yk_ctx* c, int f) {
     c->totals = B.totals + (size_t)f * 8; c->defsOut = B.defsOut + (size_t)f * fs.defsOut; c->nibOut = B.nibOut + (size_t)f * fs.nibOut;
 }
 
+// New input (an image shape, planes, pixels): nothing computed from the previous input may be handed out any more
+static void yk_input_changed(yk_ctx* c) {
+    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->img.sb.valid = false; c->pal.valid = false;
+    c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+}
+
+// A new encode has been queued: everything derived from the previous one is stale, the corner passes and the 1-D path start over
+static void yk_encode_done(yk_ctx* c, int wantDst) {
+    c->encoded = true; c->dstValid = wantDst != 0; c->img.sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false;
+    c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
+}
+
 static void yk_free_image(yk_ctx* c) {
-    auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-    auto& B = c->B;
-    F(B.keep); F(B.bounds); F(c->alphaUnitBox); F(c->alphaArrive);
-    F(B.small);                                                 // bitmaps, coverage, tile records, run sums: one allocation
-    for (int i = 0; i < 7; i++) B.bitmap[i] = nullptr;
-    B.coverage = nullptr; B.bm0b = nullptr; B.tileInfo = nullptr; B.runSums = nullptr;
-    F(B.tileDef); F(B.tileCount); F(B.slots);
-    for (int i = 0; i < 3; i++) F(c->dst[i]);
-    F(B.blockSums); F(B.blockCnt); F(B.totals); F(c->exportSizes); F(B.defsOut); F(B.nibOut);
+    c->img = YkImageBufs();                                     // every per-image buffer; the caller has synchronised the stream
+    { yk_ctx::Bases none = {}; for (int i = 0; i < 4; i++) none.plane[i] = c->B.plane[i]; c->B = none; }   // the views go, the bound planes stay
     c->keep = nullptr; c->bounds = nullptr; for (int i = 0; i < 7; i++) c->bitmap[i] = nullptr;
     c->coverage = nullptr; c->tileDef = nullptr; c->tileCount = nullptr; c->slots = nullptr;
     c->blockSums = nullptr; c->blockCnt = nullptr; c->totals = nullptr; c->defsOut = nullptr; c->nibOut = nullptr;
-    F(c->latticeOwner); F(c->cornerStream); F(c->cornerScratch); F(c->cornerEdgeIdx);
-    F(c->preview); F(c->covCh); F(c->mapped3); F(c->ppBitmap); F(c->ppStream); F(c->ppScratch); c->ppBitmapBytes = c->ppBitmapCap = 0; c->ppStreamCap = c->ppStreamBytes = 0; c->ppScratchElems = 0;
-    F(c->r1Slots); F(c->r1Params); F(c->r1Cnt); F(c->r1Pix); F(c->r1Type); c->r1Ready = false;
-    F(c->pixCache); c->pixCacheValid = false;
-    yk_sb_free(c);
+    c->ppBitmapBytes = c->ppStreamBytes = 0; c->r1Ready = false; c->pixCacheValid = false;
     if (c->frameGraph) { (void)hipGraphExecDestroy(c->frameGraph); c->frameGraph = nullptr; }
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    yk_input_changed(c);
 }
 
 // allocates every per-image array c->nFrames times (geometry fields are set) and points the handle at frame 0
-static int yk_alloc_image(yk_ctx* c) {
+static int yk_alloc_image_run(yk_ctx* c) {
     const size_t F = (size_t)c->nFrames;
     const size_t T8 = (size_t)c->tilesW * c->tilesH, MT = (size_t)c->mtW * c->mtH;
-    auto& B = c->B; YkFrameStrides& fs = c->fs;
+    auto& B = c->B; auto& M = c->img; YkFrameStrides& fs = c->fs; const hipStream_t s = c->stream;
     auto up = [](size_t n, size_t a) { return (n + a - 1) / a * a; };
     fs.keep = up(MT + 4, 16);                                   // read as 4-byte words by yk_alpha_bbox_kernel
-    YK_HIP(c, hipMalloc(&B.keep, fs.keep * F + 16));
-    YK_HIP(c, hipMalloc(&B.bounds, 16 * sizeof(int32_t) * F));
+    YK_HIP(c, M.keep.alloc(s, fs.keep * F, 16));
+    YK_HIP(c, M.bounds.alloc(s, 16 * F));
     {
         const size_t nUnits = (size_t)((c->fullW / 4 + 63) / 64) * c->mtH, nGroups = (nUnits + 63) / 64;     // sized for the smallest unit yk_alpha_kernel may use (64 int4 per segment)
-        YK_HIP(c, hipMalloc(&c->alphaUnitBox, (nUnits + nGroups) * F * 4 * sizeof(int) + 16));
-        YK_HIP(c, hipMalloc(&c->alphaArrive, (nGroups + 1) * F * sizeof(uint32_t) + 16));
-        YK_HIP(c, hipMemset(c->alphaArrive, 0, (nGroups + 1) * F * sizeof(uint32_t) + 16));
+        YK_HIP(c, M.alphaUnitBox.alloc(s, (nUnits + nGroups) * F * 4, 16));
+        YK_HIP(c, M.alphaArrive.alloc(s, (nGroups + 1) * F, 16));
+        YK_HIP(c, hipMemset(M.alphaArrive, 0, (nGroups + 1) * F * sizeof(uint32_t) + 16));
     }
     static const int sh[7][2] = { {4,4},{4,3},{3,4},{3,3},{3,2},{2,3},{2,2} };
     size_t cur = 0, oBm[7], oBm0b, oCov, oInfo, oRun;
@@ -87,29 +88,38 @@ static int yk_alloc_image(yk_ctx* c) {
     fs.tileInfo = up(T8, 2); oInfo = place(fs.tileInfo * sizeof(uint2));
     fs.runSums = up((T8 + 7) / 8, 4); oRun = place(fs.runSums * sizeof(uint32_t));
     if (cur >= ((size_t)1 << 32)) return yk_fail(c, YK_ERR_BAD_ARG, "image too large for 32-bit offsets into the small-output arena");
-    YK_HIP(c, hipMalloc(&B.small, cur));
-    YK_HIP(c, hipMemset(B.small, 0, cur));                      // allocation time only
+    YK_HIP(c, M.small.alloc(s, cur));
+    YK_HIP(c, hipMemset(M.small, 0, cur));                      // allocation time only
+    B.small = M.small;
     for (int i = 0; i < 7; i++) B.bitmap[i] = B.small + oBm[i];
     B.bm0b = B.small + oBm0b; B.coverage = reinterpret_cast<uint16_t*>(B.small + oCov);
     B.tileInfo = reinterpret_cast<uint2*>(B.small + oInfo); B.runSums = reinterpret_cast<uint32_t*>(B.small + oRun);
     fs.tileDef = 3 * T8; fs.tileCount = 3 * T8; fs.slots = 3 * T8 * YK_SLOT;
-    YK_HIP(c, hipMalloc(&B.tileDef, fs.tileDef * F * sizeof(uint16_t) + 16));
-    YK_HIP(c, hipMalloc(&B.tileCount, fs.tileCount * F + 16));
-    YK_HIP(c, hipMalloc(&B.slots, fs.slots * F + 16));
+    YK_HIP(c, M.tileDef.alloc(s, fs.tileDef * F, 16));
+    YK_HIP(c, M.tileCount.alloc(s, fs.tileCount * F, 16));
+    YK_HIP(c, M.slots.alloc(s, fs.slots * F, 16));
     c->nScanBlocks = (int)((T8 + 1023) / 1024);
     fs.blockN = (size_t)c->nScanBlocks * 2;
-    YK_HIP(c, hipMalloc(&B.blockSums, fs.blockN * F * sizeof(uint32_t)));
-    YK_HIP(c, hipMalloc(&B.blockCnt, fs.blockN * F * sizeof(uint32_t)));
-    YK_HIP(c, hipMemset(B.blockCnt, 0, fs.blockN * F * sizeof(uint32_t)));                   // synchronous (allocation time); kept zero between frames by the scan
-    YK_HIP(c, hipMalloc(&B.totals, 8 * sizeof(uint32_t) * F));
+    YK_HIP(c, M.blockSums.alloc(s, fs.blockN * F));
+    YK_HIP(c, M.blockCnt.alloc(s, fs.blockN * F));
+    YK_HIP(c, hipMemset(M.blockCnt, 0, fs.blockN * F * sizeof(uint32_t)));                   // synchronous (allocation time); kept zero between frames by the scan
+    YK_HIP(c, M.totals.alloc(s, 8 * F));
     fs.defsOut = 3 * T8;
-    YK_HIP(c, hipMalloc(&B.defsOut, fs.defsOut * F * sizeof(uint16_t) + 16));
+    YK_HIP(c, M.defsOut.alloc(s, fs.defsOut * F, 16));
     c->nibStride = T8 * YK_SLOT + 64;
     fs.nibOut = 3 * c->nibStride;
-    YK_HIP(c, hipMalloc(&B.nibOut, fs.nibOut * F + 16));
+    YK_HIP(c, M.nibOut.alloc(s, fs.nibOut * F, 16));
+    B.keep = M.keep; B.bounds = M.bounds; B.tileDef = M.tileDef; B.tileCount = M.tileCount; B.slots = M.slots;
+    B.blockSums = M.blockSums; B.blockCnt = M.blockCnt; B.totals = M.totals; B.defsOut = M.defsOut; B.nibOut = M.nibOut;
     c->dstValid = false;
     yk_rebase(c, 0);
     return YK_OK;
+}
+// all or nothing: a shape whose arrays do not all fit leaves no image behind (c->tileCount, the "an image is set" mark, stays null)
+static int yk_alloc_image(yk_ctx* c) {
+    const int rc = yk_alloc_image_run(c);
+    if (rc) yk_free_image(c);
+    return rc;
 }
 
 static int yk_stage_fold(yk_ctx* c, int st) {               // waits for the recorded intervals of a stage and adds them up
@@ -204,20 +214,17 @@ void yk_destroy(yk_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    yk_free_image(c);
     yk_lut_destroy(c);
     yk_lut_dec_destroy(c);
-    auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-    yk_dec_free(c);
-    yk_pal_free(c);
-    yk_pd_free(c);
-    F(c->ownedPlanes); F(c->pxStage); F(c->dScratch); F(c->dAlpha); F(c->dAvScratch); F(c->avState); F(c->avPay); F(c->av6); F(c->avTab); F(c->qBuf);
+    yk_dec_ring_free(c);
     c->fusedAfter = nullptr; c->fusedAfterRing.reset(); c->evRing.reset();     // a ring lives on while another handle still waits on one of its events
     for (int st = 0; st < YK_NUM_STAGES; st++) for (int k = 0; k < YK_STAGE_RING; k++) for (int i = 0; i < 2; i++) if (c->stEv[st][k][i]) (void)hipEventDestroy(c->stEv[st][k][i]);
     if (c->frameGraph) (void)hipGraphExecDestroy(c->frameGraph);
     if (c->evHandoff) (void)hipEventDestroy(c->evHandoff);
     if (c->evPixCopy) (void)hipEventDestroy(c->evPixCopy);
     if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
+    // every device buffer is a member and goes here.  The stream is destroyed before them, which is sound only because it was synchronised
+    // above (nothing queued can still use a buffer) and the handle's device is the current one for the hipFree calls
     delete c;
 }
 
@@ -256,7 +263,7 @@ int yk_set_image(yk_ctx* c, int fullW, int fullH, int nPlanes, int y0, int h, in
     YK_HIP(c, hipSetDevice(c->device));
     c->fusedAfter = nullptr; c->fusedAfterRing.reset();                      // an ordering request never outlives the image it was made for
     if (c->fullW == fullW && c->fullH == fullH && c->nPlanes == nPlanes && c->y0 == y0 && c->h == h && c->halo == haloRows && c->tileCount) {
-        c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+        yk_input_changed(c);
         return YK_OK;
     }
     YK_HIP(c, hipStreamSynchronize(c->stream));
@@ -274,7 +281,7 @@ int yk_set_batch(yk_ctx* c, int nFrames) {
     if (nFrames < 1 || nFrames > 1024) return yk_fail(c, YK_ERR_BAD_ARG, "nFrames must be 1..1024");
     if (c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "batches hold whole images, not stripes");
     YK_HIP(c, hipSetDevice(c->device));
-    c->sb.valid = false; c->pal.valid = false;                                                     // as documented: also when the frame count stays
+    c->img.sb.valid = false; c->pal.valid = false;                                                     // as documented: also when the frame count stays
     if (nFrames != c->nFrames) {
         YK_HIP(c, hipStreamSynchronize(c->stream));
         const int32_t* keepPlanes[4] = { c->B.plane[0], c->B.plane[1], c->B.plane[2], c->B.plane[3] };
@@ -329,8 +336,8 @@ int yk_validate_planes(yk_ctx* c, size_t* nOutOfRange) {
     if (!c || !nOutOfRange) return YK_ERR_BAD_ARG;
     if (!c->B.plane[0]) return yk_fail(c, YK_ERR_STATE, "bind planes first");
     YK_HIP(c, hipSetDevice(c->device));
-    unsigned long long* dBad = nullptr;
-    YK_HIP(c, hipMalloc(&dBad, sizeof(unsigned long long)));
+    YkBuf<unsigned long long> dBad;
+    YK_HIP(c, dBad.alloc(c->stream, 1));
     hipError_t e = hipMemsetAsync(dBad, 0, sizeof(unsigned long long), c->stream);
     const int rows = c->h + c->halo;
     for (int f = 0; f < c->nFrames && e == hipSuccess; f++)
@@ -340,7 +347,6 @@ int yk_validate_planes(yk_ctx* c, size_t* nOutOfRange) {
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, dBad, sizeof bad, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dBad);
     if (e != hipSuccess) return yk_fail(c, YK_ERR_HIP, "yk_validate_planes", e);
     *nOutOfRange = (size_t)bad;
     return YK_OK;
@@ -349,12 +355,8 @@ int yk_validate_planes(yk_ctx* c, size_t* nOutOfRange) {
 int yk_upload_planes(yk_ctx* c, const int32_t* const hostPlanes[4], int strideElems) {
     int rc = yk_check_planes(c, hostPlanes, strideElems); if (rc) return rc;
     YK_HIP(c, hipSetDevice(c->device));
-    const size_t rows = (size_t)c->h + c->halo, planeBytes = rows * c->fullW * sizeof(int32_t);
-    if (c->ownedPlanesBytes < planeBytes * c->nPlanes) {
-        if (c->ownedPlanes) { YK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->ownedPlanes); c->ownedPlanes = nullptr; }
-        YK_HIP(c, hipMalloc(&c->ownedPlanes, planeBytes * c->nPlanes));
-        c->ownedPlanesBytes = planeBytes * c->nPlanes;
-    }
+    const size_t rows = (size_t)c->h + c->halo;
+    YK_HIP(c, c->ownedPlanes.reserve(c->stream, rows * c->fullW * c->nPlanes));
     if (c->nFrames != 1) return yk_fail(c, YK_ERR_STATE, "batches bind device planes (yk_bind_device_batch)");
     for (int i = 0; i < 4; i++) c->B.plane[i] = nullptr;
     for (int i = 0; i < c->nPlanes; i++) {
@@ -364,7 +366,7 @@ int yk_upload_planes(yk_ctx* c, const int32_t* const hostPlanes[4], int strideEl
     }
     c->fs.plane = 0; yk_rebase(c, 0);
     c->strideElems = c->fullW;
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    yk_input_changed(c);
     // the 0..255 precondition is enforced where the boundary hands over host planes (a streaming pass over what was just copied: ~0.2 ms next to
     // ~48 ms of PCIe copy for an 8192 x 8192 RGBA image); callers that bind device memory check with yk_validate_planes when they cannot vouch for it
     size_t bad = 0;
@@ -387,7 +389,7 @@ int yk_bind_device_planes(yk_ctx* c, const int32_t* const devPlanes[4], int stri
     }
     c->fs.plane = 0; yk_rebase(c, 0);
     c->strideElems = strideElems;
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    yk_input_changed(c);
     return YK_OK;
 }
 
@@ -401,7 +403,7 @@ int yk_bind_device_batch(yk_ctx* c, const int32_t* const frame0Planes[4], int st
     }
     c->fs.plane = frameStrideElems; yk_rebase(c, c->curFrame < c->nFrames ? c->curFrame : 0);
     c->strideElems = strideElems;
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    yk_input_changed(c);
     return YK_OK;
 }
 
@@ -418,13 +420,7 @@ static int yk_pixels_check(yk_ctx* c, const uint8_t* px, size_t rowBytes, int ch
 }
 
 // grow-only: while the shape fits, the owned planes keep their address (a replayed yk_encode_frame graph then reads the new contents)
-static int yk_own_planes(yk_ctx* c, size_t bytes) {
-    if (c->ownedPlanesBytes >= bytes) return YK_OK;
-    if (c->ownedPlanes) { YK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->ownedPlanes); c->ownedPlanes = nullptr; c->ownedPlanesBytes = 0; }
-    YK_HIP(c, hipMalloc(&c->ownedPlanes, bytes));
-    c->ownedPlanesBytes = bytes;
-    return YK_OK;
-}
+static int yk_own_planes(yk_ctx* c, size_t elems) { YK_HIP(c, c->ownedPlanes.reserve(c->stream, elems)); return YK_OK; }
 
 // the state yk_upload_planes (one frame) / yk_bind_device_batch (frames) leave: plane p of frame f at ownedPlanes + f * frameElems + p * planeElems
 static void yk_bind_owned(yk_ctx* c, size_t planeElems, size_t frameElems) {
@@ -432,7 +428,7 @@ static void yk_bind_owned(yk_ctx* c, size_t planeElems, size_t frameElems) {
     c->fs.plane = c->nFrames > 1 ? frameElems : 0;
     yk_rebase(c, c->curFrame < c->nFrames ? c->curFrame : 0);
     c->strideElems = c->fullW;
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
+    yk_input_changed(c);
 }
 
 static int yk_upload_pixels_run(yk_ctx* c, const uint8_t* hostPixels, size_t rowBytes, int channels) {
@@ -441,12 +437,8 @@ static int yk_upload_pixels_run(yk_ctx* c, const uint8_t* hostPixels, size_t row
     YK_HIP(c, hipSetDevice(c->device));
     const size_t rows = (size_t)c->h + c->halo, planeElems = rows * c->fullW, rowPx = (size_t)c->fullW * channels;
     const size_t pitch = (rowPx + 15) & ~(size_t)15;                           // 16-byte rows: the kernel's fast path
-    rc = yk_own_planes(c, planeElems * c->nPlanes * sizeof(int32_t)); if (rc) return rc;
-    if (c->pxStageBytes < pitch * rows) {
-        if (c->pxStage) { YK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pxStage); c->pxStage = nullptr; c->pxStageBytes = 0; }
-        YK_HIP(c, hipMalloc(&c->pxStage, pitch * rows));
-        c->pxStageBytes = pitch * rows;
-    }
+    rc = yk_own_planes(c, planeElems * c->nPlanes); if (rc) return rc;
+    YK_HIP(c, c->pxStage.reserve(c->stream, pitch * rows));
     if (rowBytes == pitch) YK_HIP(c, hipMemcpyAsync(c->pxStage, hostPixels, (rows - 1) * pitch + rowPx, hipMemcpyHostToDevice, c->stream));
     else YK_HIP(c, hipMemcpy2DAsync(c->pxStage, pitch, hostPixels, rowBytes, rowPx, rows, hipMemcpyHostToDevice, c->stream));
     if (!c->evPixCopy) YK_HIP(c, hipEventCreateWithFlags(&c->evPixCopy, hipEventDisableTiming));
@@ -462,7 +454,7 @@ static int yk_load_device_pixels_run(yk_ctx* c, const uint8_t* devPixels, size_t
     if (c->nFrames > 1 && frameBytes < rowBytes * (size_t)c->fullH) return yk_fail(c, YK_ERR_BAD_ARG, "frameBytes must cover a frame (>= rowBytes * fullH)");
     YK_HIP(c, hipSetDevice(c->device));
     const size_t rows = (size_t)c->h + c->halo, planeElems = rows * c->fullW, frameElems = planeElems * c->nPlanes;
-    rc = yk_own_planes(c, frameElems * c->nFrames * sizeof(int32_t)); if (rc) return rc;
+    rc = yk_own_planes(c, frameElems * c->nFrames); if (rc) return rc;
     rc = yk_launch_unpack_u8(c, devPixels, rowBytes, frameBytes, channels, (int)rows, c->nFrames, c->ownedPlanes, planeElems, frameElems); if (rc) return rc;
     yk_bind_owned(c, planeElems, frameElems);
     return YK_OK;
@@ -616,11 +608,11 @@ int yk_encode_tiles(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst) 
     if (wantDst) {
         const size_t n = (size_t)c->fullW * c->h;
         for (int p = 0; p < 3; p++) {
-            if (!c->dst[p]) YK_HIP(c, hipMalloc(&c->dst[p], n * sizeof(int32_t)));
-            if (c->dstFill == 0 || c->dstFill == -1) YK_HIP(c, hipMemsetAsync(c->dst[p], c->dstFill & 255, n * sizeof(int32_t), c->stream));
+            if (!c->img.dst[p]) YK_HIP(c, c->img.dst[p].alloc(c->stream, n));
+            if (c->dstFill == 0 || c->dstFill == -1) YK_HIP(c, hipMemsetAsync(c->img.dst[p], c->dstFill & 255, n * sizeof(int32_t), c->stream));
             else {
                 std::vector<int32_t> f(n, c->dstFill);
-                YK_HIP(c, hipMemcpyAsync(c->dst[p], f.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+                YK_HIP(c, hipMemcpyAsync(c->img.dst[p], f.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
                 YK_HIP(c, hipStreamSynchronize(c->stream));
             }
         }
@@ -632,7 +624,7 @@ int yk_encode_tiles(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst) 
     rc = yk_launch_pack(c); if (rc) return rc;
     YK_HIP(c, hipEventRecord(ev[YK_EV_P1], c->stream));
     yk_ev_commit(c, (c->evAlphaInCur ? YK_EVSET_ALPHA : 0) | YK_EVSET_PACK);
-    c->encoded = true; c->dstValid = wantDst != 0; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
+    yk_encode_done(c, wantDst);
     return YK_OK;
 }
 
@@ -671,7 +663,7 @@ int yk_encode_batch(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
     YK_HIP(c, hipEventRecord(ev[YK_EV_P1], c->stream));
     yk_ev_commit(c, (c->nPlanes == 4 ? YK_EVSET_ALPHA : 0) | YK_EVSET_PACK);
     c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false;
-    c->encoded = true; c->dstValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
+    yk_encode_done(c, 0);
     return YK_OK;
 }
 
@@ -707,7 +699,7 @@ int yk_encode_frame(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
     YK_HIP(c, hipEventRecord(ev[YK_EV_E1], c->stream));
     yk_ev_commit(c, 0);
     c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false;
-    c->encoded = true; c->dstValid = false; c->sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
+    yk_encode_done(c, 0);
     return YK_OK;
 }
 
@@ -787,7 +779,7 @@ int yk_range_dst(yk_ctx* c, int plane, int32_t* hostOut, size_t capElems) {
     const size_t n = (size_t)c->fullW * c->h;
     if (capElems < n) return yk_fail(c, YK_ERR_RANGE, "dst buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, hipMemcpyAsync(hostOut, c->dst[plane], n * 4, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(hostOut, c->img.dst[plane], n * 4, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }
@@ -853,10 +845,10 @@ static int yk_export_launch(yk_ctx* c, void* devDst, size_t cap, unsigned long l
 
 int yk_export_tile_maps(yk_ctx* c, void* devDst, size_t cap, uint64_t sizes[15]) {
     if (!c || !devDst || !sizes) return YK_ERR_BAD_ARG;
-    if (!c->exportSizes) { YK_HIP(c, hipSetDevice(c->device)); YK_HIP(c, hipMalloc(&c->exportSizes, 16 * sizeof(unsigned long long))); }
-    int rc = yk_export_launch(c, devDst, cap, c->exportSizes); if (rc) return rc;
+    if (!c->img.exportSizes) { YK_HIP(c, hipSetDevice(c->device)); YK_HIP(c, c->img.exportSizes.alloc(c->stream, 16)); }
+    int rc = yk_export_launch(c, devDst, cap, c->img.exportSizes); if (rc) return rc;
     unsigned long long h[16];
-    YK_HIP(c, hipMemcpyAsync(h, c->exportSizes, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(h, c->img.exportSizes, sizeof h, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));                 // the buffer is complete when this returns
     for (int i = 0; i < 15; i++) sizes[i] = h[1 + i];
     return YK_OK;

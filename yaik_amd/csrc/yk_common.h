@@ -36,6 +36,33 @@ struct YkEvRing {
     ~YkEvRing() { for (auto& set : ev) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e); }
 };
 
+// Device memory a handle owns: pointer and capacity in one place, one owner, freed with it.  `cap` counts elements of T (the bytes of padding
+// some kernels read past the nominal end are asked for separately and are not part of it).  Two ways of getting memory, both on the handle's
+// stream; either leaves the buffer EMPTY when it fails, never dangling and never with a stale capacity.  The caller reports the error
+// (YK_HIP, or yk_refuse where a refusal leaves the handle usable).  Not copyable; movable, so that a group of buffers is released by
+// assigning an empty group (c->img = YkImageBufs()).
+template <class T> struct YkBuf {
+    T* p = nullptr; size_t cap = 0;
+    YkBuf() = default;
+    YkBuf(const YkBuf&) = delete; YkBuf& operator=(const YkBuf&) = delete;
+    YkBuf(YkBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    YkBuf& operator=(YkBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~YkBuf() { release(); }
+    operator T*() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // exact: for the per-shape arrays that are re-made (and may shrink) when the shape or the frame count changes
+    hipError_t alloc(hipStream_t s, size_t n, size_t padBytes = 0) {
+        if (p) { const hipError_t e = hipStreamSynchronize(s); release(); if (e != hipSuccess) return e; }     // queued work may still use the old buffer
+        const size_t bytes = n * sizeof(T) + padBytes;
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), bytes ? bytes : 16);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = n;
+        return hipSuccess;
+    }
+    // grow-only: nothing happens while n elements fit
+    hipError_t reserve(hipStream_t s, size_t n, size_t padBytes = 0) { return (p && cap >= n) ? hipSuccess : alloc(s, n, padBytes); }
+};
+
 struct YkEncodeParams {
     const int32_t* plane[4];
     int strideElems;
@@ -79,21 +106,21 @@ struct YkEncodeParams {
 struct YkStreamRec { uint8_t* rgb[7]; uint8_t* pix; uint8_t* type; };
 // the batch's own buffers (grow-only, freed with the image): they share nothing with the single-image corner / 1-D state
 struct YkStreamsBatch {
-    uint32_t* owner = nullptr; size_t ownerElems = 0;            // [F][lattice]
-    uint32_t* cScratch = nullptr; size_t cScratchElems = 0;      // [F][block sums], [F][ownership words]
-    uint32_t* r1Scratch = nullptr; size_t r1ScratchElems = 0;    // [F][offsets in block], [F][coded tiles per block], [F][pixel bytes per block]
-    uint32_t* counts = nullptr; size_t countsElems = 0;          // [F][YK_SB_COUNTS]
-    uint8_t* out = nullptr; size_t outCap = 0;                   // every stream of every frame, each on a multiple of 16
-    uint8_t* tab = nullptr; size_t tabCap = 0;                   // [F] YkStreamRec
+    YkBuf<uint32_t> owner;                                       // [F][lattice]
+    YkBuf<uint32_t> cScratch;                                    // [F][block sums], [F][ownership words]
+    YkBuf<uint32_t> r1Scratch;                                   // [F][offsets in block], [F][coded tiles per block], [F][pixel bytes per block]
+    YkBuf<uint32_t> counts;                                      // [F][YK_SB_COUNTS]
+    YkBuf<uint8_t> out;                                          // every stream of every frame, each on a multiple of 16
+    YkBuf<YkStreamRec> tab;                                      // [F]
     std::vector<yk_frame_streams> table; bool valid = false;     // what yk_batch_streams_table hands out
     int what = 0;                                                // the YK_STREAMS_* the valid table was built with
 };
 
 // yk_palette_compress* (yk_palette.hip): PaletteCompressor over a list of segments.  Everything is grow-only and belongs to the handle.
 struct YkPalette {
-    uint8_t* scratch = nullptr; size_t scratchCap = 0;           // segment table, vote tables, candidates, books, tokens, offsets, lengths
-    uint8_t* out = nullptr; size_t outCap = 0;                   // the payloads of the last call, each on a multiple of 16
-    uint32_t* carry = nullptr;                                   // the 64 find-table rows that carry from call to call (packed deltas)
+    YkBuf<uint8_t> scratch;                                      // segment table, vote tables, candidates, books, tokens, offsets, lengths
+    YkBuf<uint8_t> out;                                          // the payloads of the last call, each on a multiple of 16
+    YkBuf<uint32_t> carry;                                       // the 64 find-table rows that carry from call to call (packed deltas)
     bool carryFresh = true;                                      // the carried rows are those of a fresh process (all zero deltas)
     std::vector<uint8_t> segHost;                                // the segment table on its way to HBM
     std::vector<uint32_t> lenBase;                               // read back: [nSeg] payload lengths, [nSeg] payload offsets in `out`
@@ -102,13 +129,42 @@ struct YkPalette {
 
 // yk_palette_decompress_streams (yk_palette_dec.hip): PaletteDecompressor over a list of payloads.  Grow-only, owned by the handle.
 struct YkPaletteDec {
-    uint8_t* scratch = nullptr; size_t scratchCap = 0;           // stream table, chunk records, token offsets, colour records, halos, status words
-    uint8_t* out = nullptr; size_t outCap = 0;                   // the decoded streams of the last call, each on a multiple of 16, 64 free bytes around them
-    uint8_t* stage = nullptr; size_t stageCap = 0;               // yk_decode_gradient_palette: the host's tile bitmap and payload on their way in
+    YkBuf<uint8_t> scratch;                                      // stream table, chunk records, token offsets, colour records, halos, status words
+    YkBuf<uint8_t> out;                                          // the decoded streams of the last call, each on a multiple of 16, 64 free bytes around them
+    YkBuf<uint8_t> stage;                                        // yk_decode_gradient_palette: the host's tile bitmap and payload on their way in
     std::vector<size_t> slotOff, slotLen;                        // where every stream's output lies in `out`
     std::vector<uint32_t> statusHost;
     size_t statusOff = 0;                                        // the status words inside `scratch`
     int nSeg = 0; bool valid = false;
+};
+
+// Everything that is allocated for one image shape and frame count (yk_set_image, yk_set_batch) or grows with the work done on it, and goes
+// when the shape changes: released as a whole (yk_free_image).  The pointers the kernels are given -- the frame-0 bases B, the working
+// pointers of yk_rebase, the pieces of `small` -- are views into these.
+struct YkImageBufs {
+    // alpha
+    YkBuf<uint8_t> keep; YkBuf<int32_t> bounds;
+    YkBuf<int> alphaUnitBox;            // yk_alpha_kernel: one box {x0, y0, x1, y1} per work unit (tile row x 1024-pixel segment) and frame
+    YkBuf<uint32_t> alphaArrive;        // its arrival counters: per group of 64 units + one per frame (zero between launches)
+    // encode outputs and compaction
+    YkBuf<uint8_t> small;               // one allocation: bitmap[0..6], bm0b, coverage, tileInfo, runSums (each nFrames times)
+    YkBuf<uint16_t> tileDef; YkBuf<uint8_t> tileCount, slots;
+    YkBuf<int32_t> dst[3];
+    YkBuf<uint32_t> blockSums, blockCnt, totals;
+    YkBuf<unsigned long long> exportSizes;   // [16] total + section sizes of the last yk_export_tile_maps
+    YkBuf<uint16_t> defsOut; YkBuf<uint8_t> nibOut;
+    // corner streams
+    YkBuf<uint32_t> latticeOwner; YkBuf<uint8_t> cornerStream; YkBuf<uint32_t> cornerScratch;
+    YkBuf<uint32_t> cornerEdgeIdx;      // [2][w/4+1]: emission index (in corners, within its pass) of the first / last lattice row
+    // plane-subset passes
+    YkBuf<uint16_t> covCh;              // [3][covChStride]
+    YkBuf<uint8_t> mapped3;             // bit p = plane p's corner at this lattice point has been emitted
+    YkBuf<uint32_t> ppBitmap; YkBuf<uint8_t> ppStream; YkBuf<uint32_t> ppScratch;
+    YkBuf<int32_t> preview;             // FittingQuadSmooth's testOutput planes (3 x w*h int32), INT32_MIN where no tile wrote
+    // live 1-D range path and the pixel cache that feeds it
+    YkBuf<uint8_t> r1Slots, r1Params; YkBuf<uint32_t> r1Cnt; YkBuf<uint8_t> r1Pix, r1Type;
+    YkBuf<uint4> pixCache;              // yk_set_pixel_cache: uncovered cells' packed pixels, fused kernel -> 1-D path
+    YkStreamsBatch sb;                  // yk_encode_streams_batch
 };
 
 // The layout of yk_ctx must NOT depend on YK_TEST_HOOKS: the product library and the test-hooks build of the same sources are loaded side by
@@ -135,14 +191,12 @@ struct yk_ctx {
     // input
     const int32_t* plane[4] = {nullptr, nullptr, nullptr, nullptr};
     int strideElems = 0;
-    int32_t* ownedPlanes = nullptr; size_t ownedPlanesBytes = 0;
-    uint8_t* pxStage = nullptr; size_t pxStageBytes = 0;   // yk_upload_pixels_u8: grow-only HBM copy of the host's 8-bit rows (16-byte pitch)
+    YkBuf<int32_t> ownedPlanes;
+    YkBuf<uint8_t> pxStage;                                 // yk_upload_pixels_u8: grow-only HBM copy of the host's 8-bit rows (16-byte pitch)
     hipEvent_t evPixCopy = nullptr;                         // ... recorded behind that copy: the call returns once the host rows are read
     // alpha
     uint8_t* keep = nullptr;            // mtW*mtH
     int32_t* bounds = nullptr;          // 16 ints: [0..4] the host-combined box of a striped image + its discard flag (yk_alpha_finish), [8..11] the box yk_alpha_kernel accumulates
-    int* alphaUnitBox = nullptr;        // yk_alpha_kernel: one box {x0, y0, x1, y1} per work unit (tile row x 1024-pixel segment) and frame
-    uint32_t* alphaArrive = nullptr;    // its arrival counters: per group of 64 units + one per frame (zero between launches)
     int boundsOff = 8;                  // where the image-wide box is: 8 (whole image, batch) or 0 (stripes, after yk_alpha_finish)
     bool alphaDone = false, alphaFinished = false;
     int32_t hostBounds[4] = {0, 0, 0, 0}; int hostDiscard = 1, hostHasChunk = 0;
@@ -150,12 +204,11 @@ struct yk_ctx {
     uint8_t* bitmap[7] = {}; size_t bitmapBytes[7] = {};
     uint16_t* coverage = nullptr;
     uint16_t* tileDef = nullptr; uint8_t* tileCount = nullptr; uint8_t* slots = nullptr;
-    int32_t* dst[3] = {nullptr, nullptr, nullptr}; int32_t dstFill = -1; bool dstValid = false;
+    int32_t dstFill = -1; bool dstValid = false;
     // compaction
     uint32_t* blockSums = nullptr;      // [nBlocks][2]: exclusive prefix of (nibbles, coded tiles) per block of 1024 tiles, same for the 3 planes
     uint32_t* blockCnt = nullptr;       // [nBlocks][2]: the sums themselves, accumulated by the fused kernel, consumed (and cleared) by the scan
     uint32_t* totals = nullptr;         // [3][2] device
-    unsigned long long* exportSizes = nullptr;   // [16] total + section sizes of the last yk_export_tile_maps
     hipEvent_t evHandoff = nullptr;              // yk_stream_handoff / yk_stream_wait_for
     // yk_order_fused_after: the next fused kernel waits for this event, the end of the other handle's fused kernel.  It belongs to that handle's
     // ring, which fusedAfterRing keeps alive should the other handle be destroyed before this one encodes.
@@ -166,43 +219,37 @@ struct yk_ctx {
     int nScanBlocks = 0;
     bool encoded = false;
     // corner streams
-    uint32_t* latticeOwner = nullptr; size_t latticeElems = 0;
-    uint8_t* cornerStream = nullptr; size_t cornerCap = 0;
-    uint32_t* cornerScratch = nullptr; size_t cornerScratchElems = 0;
-    uint32_t* cornerEdgeIdx = nullptr;  // [2][w/4+1]: emission index (in corners, within its pass) of the first / last lattice row
     bool cornersReady = false; int nextCornerPass = 0;
     size_t cornerOff[7] = {}, cornerBytes[7] = {};
     const uint32_t* cornerTotalsDev = nullptr; bool cornerTotalsPending = false;   // stream lengths still on the device (yk_corners_finish)
     const uint32_t* r1TotalsDev = nullptr; bool r1TotalsPending = false;           // the same for the 1-D path (yk_range1d_finish)
     // partial-plane gradient passes (FittingQuadSmooth with nullable planes): per-plane coverage (mapSmoothTile[p], u16 per 16x16 tile, bit = cell)
-    // and per-plane "corner already emitted" flags per lattice point (mappedRGB[p]); allocated by the first partial pass after an encode
-    uint16_t* covCh = nullptr; size_t covChStride = 0;     // [3][covChStride]
-    uint8_t* mapped3 = nullptr;                            // bit p = plane p's corner at this lattice point has been emitted
-    uint32_t* ppBitmap = nullptr; size_t ppBitmapBytes = 0; uint8_t* ppStream = nullptr; size_t ppStreamCap = 0, ppStreamBytes = 0;
-    uint32_t* ppScratch = nullptr; size_t ppScratchElems = 0, ppBitmapCap = 0; int ppAccepted = 0; bool ppActive = false;
-    int ppLastBit = 0, ppLastSx = 0, ppLastSy = 0;         // the last plane-subset pass (its bitmap is ppBitmap)
-    int32_t* preview = nullptr; bool previewFresh = false; // FittingQuadSmooth's testOutput planes (3 x w*h int32), INT32_MIN where no tile wrote
+    // and per-plane "corner already emitted" flags per lattice point (mappedRGB[p]); allocated by the first partial pass after an encode (img)
+    size_t covChStride = 0;
+    size_t ppBitmapBytes = 0, ppStreamBytes = 0;               // bytes of the last plane-subset pass's bitmap and corner stream
+    int ppAccepted = 0; bool ppActive = false;
+    int ppLastBit = 0, ppLastSx = 0, ppLastSy = 0;         // the last plane-subset pass (its bitmap is img.ppBitmap)
+    bool previewFresh = false;                             // img.preview holds INT32_MIN wherever no tile has written since the encode
     // (f)4 3-D LUT tiles (yk_lut3d.hip): pattern bank + the streams StartCorrelationSearch allocates
     struct YkLutState* lut = nullptr;
     struct YkLutDecState* lutDec = nullptr;      // decoder: the per-orientation tables YAIK_AssignLUT lays out
     // live 1-D range path (a15)
-    uint8_t* r1Slots = nullptr; uint8_t* r1Params = nullptr; uint32_t* r1Cnt = nullptr; uint8_t* r1Pix = nullptr; uint8_t* r1Type = nullptr;
     uint32_t r1Tiles = 0, r1PixCount = 0; bool r1Ready = false;
-    uint4* pixCache = nullptr; bool pixCacheOn = false, pixCacheValid = false;   // yk_set_pixel_cache: uncovered cells' packed pixels, fused kernel -> 1-D path
+    bool pixCacheOn = false, pixCacheValid = false;      // yk_set_pixel_cache (img.pixCache)
     uint32_t r1EndTiles[3] = {}, r1EndPix[3] = {};       // cumulative per plane (equal thirds unless a partial-plane pass ran)
     // decode
     int dw = 0, dh = 0; uint8_t* dPlanes = nullptr; size_t dPlaneSize = 0;
     uint8_t* dMapRGB = nullptr; uint32_t* dLatticeOwner = nullptr; uint8_t* dTile4 = nullptr; size_t dTile4Size = 0;
-    uint8_t* dScratch = nullptr; size_t dScratchBytes = 0;
+    YkBuf<uint8_t> dScratch;
     uint8_t* dLoaded = nullptr;         // lattice point already popped from a colour stream (mapRGBMask)
     bool dSplit = false;
-    uint8_t* dAlpha = nullptr; size_t dAlphaBytes = 0; bool dAlphaValid = false;   // yk_decode_alpha: the w x h alpha plane of the image being decoded
-    uint8_t* dAvScratch = nullptr; size_t dAvScratchBytes = 0;                      // its payload, mask and row counts
-    int32_t* avState = nullptr; uint8_t* avPay = nullptr; size_t avPayCap = 0;      // yk_alpha_values: box + class flags, the payload
-    uint8_t* av6 = nullptr; size_t av6Cap = 0;                                      // its 6-bit mask mode: tile prefixes, band scan, packed payload
-    // yk_alpha_values_batch: avState holds 8 ints per frame (avStateFrames of them), avPay the frames' payload slots back to back, avTab the
-    // per-frame records in HBM; avBatch = what the payload getters hand out (valid while avBatchValid)
-    int avStateFrames = 0; uint8_t* avTab = nullptr; size_t avTabBytes = 0;
+    YkBuf<uint8_t> dAlpha; bool dAlphaValid = false;     // yk_decode_alpha: the w x h alpha plane of the image being decoded
+    YkBuf<uint8_t> dAvScratch;                           // its payload, mask and row counts
+    YkBuf<int32_t> avState; YkBuf<uint8_t> avPay;        // yk_alpha_values: box + class flags, the payload
+    YkBuf<uint8_t> av6;                                  // its 6-bit mask mode: tile prefixes, band scan, packed payload
+    // yk_alpha_values_batch: avState holds 8 ints per frame, avPay the frames' payload slots back to back, avTab the per-frame records in HBM;
+    // avBatch = what the payload getters hand out (valid while avBatchValid)
+    YkBuf<uint8_t> avTab;
     struct AvSlot { int32_t mode; size_t off, bytes; };
     std::vector<AvSlot> avBatch; bool avBatchValid = false;
     // yk_decode_alpha_batch_device: dAlpha holds dFrames planes dAlphaStride bytes apart (the selected frame's is yk_dec_alpha_cur)
@@ -212,11 +259,12 @@ struct yk_ctx {
     // allocations (frame 0) and dStride the distance in BYTES from one frame's array to the next (yk_dec_rebase), like B / fs on the encode side
     int dFrames = 1, dCur = 0;
     struct DBases { uint8_t* planes; uint8_t* mapRGB; uint32_t* owner; uint8_t* loaded; uint8_t* tile4; } dB = {};
+    struct DFrames { YkBuf<uint8_t> planes, mapRGB; YkBuf<uint32_t> owner; YkBuf<uint8_t> loaded, tile4; } dFrm;   // what dB points into
     struct DStrides { size_t planes, mapRGB, owner, loaded, tile4; } dStride = {};
     // the per-frame tables of the batch calls on their way to HBM: a ring of pinned host buffers, each with the event behind its copy
     void* dTabHost[4] = {}; size_t dTabHostBytes[4] = {}; hipEvent_t dTabEv[4] = {}; unsigned dTabSeq = 0;
     // yk_decode_compare_*: the folded u64 results of every frame, then one record per workgroup (grow-only; yk_quality.hip)
-    uint8_t* qBuf = nullptr; size_t qBufBytes = 0;
+    YkBuf<uint8_t> qBuf;
     // timing
     // timing events: a ring of YK_EV_RING sets (YkEvRing) so that a caller can run many frames back to back and read the per-kernel
     // averages afterwards without synchronising every frame
@@ -235,7 +283,7 @@ struct yk_ctx {
     hipGraphExec_t frameGraph = nullptr;
     unsigned long long frameGraphKey[12] = {};
     int kernelVersion = 2;              // 2 = yk_encode2_kernel; 1 = the registered cross-check launcher (tests/csrc/yk_encode_v1.hip)
-    YkStreamsBatch sb;                  // yk_encode_streams_batch
+    YkImageBufs img;                    // the per-image buffers, yk_encode_streams_batch's among them
     YkPalette pal;                      // yk_palette_compress*
     YkPaletteDec pdec;                  // yk_palette_decompress_streams, yk_decode_gradient_palette
 };
@@ -260,18 +308,11 @@ int yk_launch_pack(yk_ctx* c, bool batch = false);
 int yk_launch_corners(yk_ctx* c);
 int yk_launch_unpack_u8(yk_ctx* c, const uint8_t* src, size_t rowBytes, size_t frameBytes, int channels, int rows, int nFrames,
                         int32_t* dst, size_t planeElems, size_t frameElems);   // yk_pixels.hip
-// yk_encode_streams_batch: count and emit phases over all frames (yk_corners.hip, yk_range1d.hip), the grow-only buffers and their release (yk_streams_batch.hip)
+// yk_encode_streams_batch: count and emit phases over all frames (yk_corners.hip, yk_range1d.hip)
 int yk_corners_batch_count(yk_ctx* c);
 int yk_corners_batch_emit(yk_ctx* c);
 int yk_range1d_batch_count(yk_ctx* c);
 int yk_range1d_batch_emit(yk_ctx* c);
-int yk_sb_grow_bytes(yk_ctx* c, void** p, size_t* cap, size_t need);
-inline int yk_sb_grow(yk_ctx* c, uint32_t** p, size_t* capElems, size_t needElems) {
-    size_t cap = *capElems * 4; const int rc = yk_sb_grow_bytes(c, reinterpret_cast<void**>(p), &cap, needElems * 4); *capElems = cap / 4; return rc;
-}
-void yk_sb_free(yk_ctx* c);
-void yk_pd_free(yk_ctx* c);                               // frees the palette decoder's buffers (yk_palette_dec.hip)
-void yk_pal_free(yk_ctx* c);                              // frees the palette coder's buffers (yk_palette.hip); the carried rows become fresh
 int yk_corners_finish(yk_ctx* c);                         // reads the corner streams' lengths back if that is still pending (synchronises)
 // the pinned ring behind the per-frame tables of the decode batch calls (yk_decode.hip)
 extern "C" int yk_dec_table_host(yk_ctx* c, size_t bytes, int* slot, void** host);
@@ -285,9 +326,9 @@ struct YkQualitySrc {
     size_t frameStride;                                   // bytes (u8) or elements (int32) from one frame's source to the next
 };
 int yk_quality_compare(yk_ctx* c, const YkQualitySrc& q, int firstFrame, int nFrames, int channels, yk_quality* out, uint32_t* devTileSse);
-void yk_dec_free(yk_ctx* c);                              // frees the decode buffers of every frame and the batch tables' host ring (yk_decode.hip)
-void yk_lut_dec_destroy(yk_ctx* c);
-void yk_lut_destroy(yk_ctx* c);                          // frees the 3-D LUT bank and streams (yk_lut3d.hip)
+void yk_dec_ring_free(yk_ctx* c);                         // the batch tables' pinned host ring and its events (yk_decode.hip)
+void yk_lut_dec_destroy(yk_ctx* c);                       // deletes the 3-D LUT decode tables and, below, the encoder's bank and streams (yk_lut3d.hip)
+void yk_lut_destroy(yk_ctx* c);
 int yk_pp_activate(yk_ctx* c);                           // per-plane coverage / corner flags for the passes behind the RGB passes
 int yk_launch_encode2(yk_ctx* c, const YkEncodeParams& P);
 int yk_qtab_get(yk_ctx* c);                              // builds the device's quantiser table on first use, sets c->qtab

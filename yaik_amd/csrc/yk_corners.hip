@@ -294,32 +294,32 @@ int yk_launch_corners(yk_ctx* c) {
     const int w = c->fullW, h = c->h;
     const int latW = w / 4 + 1, latH = h / 4 + 1;
     const size_t lat = (size_t)latW * latH;
-    if (!c->latticeOwner) { YK_HIP(c, hipMalloc(&c->latticeOwner, lat * 4)); c->latticeElems = lat; }
+    if (!c->img.latticeOwner) YK_HIP(c, c->img.latticeOwner.alloc(c->stream, lat));
     // every lattice point is emitted at most once over the seven passes, so one buffer of lat*3 bytes holds all streams back to
     // back; the passes are laid out at their worst-case offsets (pass p after everything passes < p could emit) = 7 regions
     const size_t region = lat * 3 + 16;
-    if (!c->cornerStream) { c->cornerCap = region * 7; YK_HIP(c, hipMalloc(&c->cornerStream, c->cornerCap)); }
+    if (!c->img.cornerStream) YK_HIP(c, c->img.cornerStream.alloc(c->stream, region * 7));
     CornerPlan pl;
     yk_corner_plan(c, c->bitmap, pl);
     const size_t nbTot = pl.blockStart[7], nWordsTot = pl.wordStart[7];
     // scratch: [block sums | 7 totals (+ pad) | ownership bits per thread (one word per bitmap byte)]
-    if (!c->cornerScratch) { c->cornerScratchElems = nbTot + 64 + nWordsTot * 4; YK_HIP(c, hipMalloc(&c->cornerScratch, c->cornerScratchElems * 4)); }
-    uint32_t* blockSums = c->cornerScratch;
-    uint32_t* totalDev = c->cornerScratch + nbTot;
-    uint32_t* perThread = c->cornerScratch + nbTot + 64;
-    if (!c->cornerEdgeIdx) YK_HIP(c, hipMalloc(&c->cornerEdgeIdx, (size_t)latW * 2 * 4));
+    if (!c->img.cornerScratch) YK_HIP(c, c->img.cornerScratch.alloc(c->stream, nbTot + 64 + nWordsTot * 4));
+    uint32_t* blockSums = c->img.cornerScratch;
+    uint32_t* totalDev = c->img.cornerScratch + nbTot;
+    uint32_t* perThread = c->img.cornerScratch + nbTot + 64;
+    if (!c->img.cornerEdgeIdx) YK_HIP(c, c->img.cornerEdgeIdx.alloc(c->stream, (size_t)latW * 2));
     { int rc = yk_stage_begin(c, YK_STAGE_CORNERS); if (rc) return rc; }
-    YK_HIP(c, hipMemsetAsync(c->cornerEdgeIdx, 0xFF, (size_t)latW * 2 * 4, c->stream));
-    YK_HIP(c, hipMemsetAsync(c->latticeOwner, 0xFF, lat * 4, c->stream));
+    YK_HIP(c, hipMemsetAsync(c->img.cornerEdgeIdx, 0xFF, (size_t)latW * 2 * 4, c->stream));
+    YK_HIP(c, hipMemsetAsync(c->img.latticeOwner, 0xFF, lat * 4, c->stream));
     for (int p = 0; p < 7; p++)
         if (c->bitmapBytes[p] & 3) YK_HIP(c, hipMemsetAsync(c->bitmap[p] + c->bitmapBytes[p], 0, 4 - (c->bitmapBytes[p] & 3), c->stream));
     // 2 clears + 4 launches for the seven passes (round 1: 2 + 28): owner of every lattice point, corners per block, one scan, emission
-    hipLaunchKernelGGL(yk_corner_owner_kernel, dim3((pl.wordStart[7] * 4u + 255u) / 256u), dim3(256), 0, c->stream, pl, w, latW, c->latticeOwner);
-    hipLaunchKernelGGL(yk_corner_stream_kernel<false>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, latW, c->latticeOwner, blockSums, perThread,
+    hipLaunchKernelGGL(yk_corner_owner_kernel, dim3((pl.wordStart[7] * 4u + 255u) / 256u), dim3(256), 0, c->stream, pl, w, latW, c->img.latticeOwner);
+    hipLaunchKernelGGL(yk_corner_stream_kernel<false>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, latW, c->img.latticeOwner, blockSums, perThread,
                        c->plane[0], c->plane[1], c->plane[2], c->strideElems, (uint8_t*)nullptr, region, (uint32_t*)nullptr, latH, c->h + c->halo);
     hipLaunchKernelGGL(yk_corner_scan_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, pl, totalDev);
-    hipLaunchKernelGGL(yk_corner_stream_kernel<true>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, latW, c->latticeOwner, blockSums, perThread,
-                       c->plane[0], c->plane[1], c->plane[2], c->strideElems, c->cornerStream, region, c->cornerEdgeIdx, latH, c->h + c->halo);
+    hipLaunchKernelGGL(yk_corner_stream_kernel<true>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, latW, c->img.latticeOwner, blockSums, perThread,
+                       c->plane[0], c->plane[1], c->plane[2], c->strideElems, c->img.cornerStream, region, c->img.cornerEdgeIdx, latH, c->h + c->halo);
     YK_HIP(c, hipGetLastError());
     { int rc = yk_stage_end(c, YK_STAGE_CORNERS); if (rc) return rc; }
     // the stream lengths stay on the device until somebody asks for a stream (yk_corners_finish): a caller that keeps frames in flight
@@ -339,8 +339,8 @@ static void yk_corner_batch_desc(const yk_ctx* c, const CornerPlan& pl, CornerBa
     cb.sOwner = (unsigned long long)(c->fullW / 4 + 1) * (c->h / 4 + 1);
     cb.sBlk = ((unsigned long long)pl.blockStart[7] + 3) & ~3ULL;
     cb.sPer = (unsigned long long)pl.wordStart[7] * 4;
-    cb.tab = reinterpret_cast<const YkStreamRec*>(c->sb.tab);
-    blockSums = c->sb.cScratch; perThread = c->sb.cScratch + F * cb.sBlk;
+    cb.tab = c->img.sb.tab;
+    blockSums = c->img.sb.cScratch; perThread = c->img.sb.cScratch + F * cb.sBlk;
 }
 
 // count phase: lattice clear, owners, corners per block (leaves the ownership bits), one scan workgroup per frame -> counts[f][0..6]
@@ -350,26 +350,26 @@ int yk_corners_batch_count(yk_ctx* c) {
     CornerPlan pl; CornerBatch cb; uint32_t* blockSums; uint32_t* perThread;
     yk_corner_plan(c, c->B.bitmap, pl);
     { const unsigned long long lat = (unsigned long long)latW * (c->h / 4 + 1), sBlk = ((unsigned long long)pl.blockStart[7] + 3) & ~3ULL;
-      int rc = yk_sb_grow(c, &c->sb.owner, &c->sb.ownerElems, (size_t)lat * F); if (rc) return rc;
-      rc = yk_sb_grow(c, &c->sb.cScratch, &c->sb.cScratchElems, (size_t)(sBlk + (unsigned long long)pl.wordStart[7] * 4) * F); if (rc) return rc; }
+      YK_HIP(c, c->img.sb.owner.reserve(c->stream, (size_t)lat * F));
+      YK_HIP(c, c->img.sb.cScratch.reserve(c->stream, (size_t)(sBlk + (unsigned long long)pl.wordStart[7] * 4) * F)); }
     yk_corner_batch_desc(c, pl, cb, blockSums, perThread);
-    YK_HIP(c, hipMemsetAsync(c->sb.owner, 0xFF, (size_t)cb.sOwner * F * 4, c->stream));
-    hipLaunchKernelGGL(yk_corner_owner_batch_kernel, dim3((pl.wordStart[7] * 4u + 255u) / 256u, F), dim3(256), 0, c->stream, pl, cb, w, latW, c->sb.owner);
-    hipLaunchKernelGGL(yk_corner_stream_batch_kernel<false>, dim3(pl.blockStart[7], F), dim3(1024), 0, c->stream, pl, cb, w, latW, (const uint32_t*)c->sb.owner,
+    YK_HIP(c, hipMemsetAsync(c->img.sb.owner, 0xFF, (size_t)cb.sOwner * F * 4, c->stream));
+    hipLaunchKernelGGL(yk_corner_owner_batch_kernel, dim3((pl.wordStart[7] * 4u + 255u) / 256u, F), dim3(256), 0, c->stream, pl, cb, w, latW, c->img.sb.owner);
+    hipLaunchKernelGGL(yk_corner_stream_batch_kernel<false>, dim3(pl.blockStart[7], F), dim3(1024), 0, c->stream, pl, cb, w, latW, (const uint32_t*)c->img.sb.owner,
                        blockSums, perThread, c->B.plane[0], c->B.plane[1], c->B.plane[2], c->strideElems, c->h / 4 + 1, c->h);
-    hipLaunchKernelGGL(yk_corner_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, blockSums, pl, cb.sBlk, c->sb.counts);
+    hipLaunchKernelGGL(yk_corner_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, blockSums, pl, cb.sBlk, c->img.sb.counts);
     YK_HIP(c, hipGetLastError());
     return YK_OK;
 }
 
-// emit phase: the table of stream bases is in HBM (c->sb.tab); every workgroup writes its run of its frame's pass
+// emit phase: the table of stream bases is in HBM (c->img.sb.tab); every workgroup writes its run of its frame's pass
 int yk_corners_batch_emit(yk_ctx* c) {
     const int w = c->fullW, latW = w / 4 + 1;
     const unsigned F = (unsigned)c->nFrames;
     CornerPlan pl; CornerBatch cb; uint32_t* blockSums; uint32_t* perThread;
     yk_corner_plan(c, c->B.bitmap, pl);
     yk_corner_batch_desc(c, pl, cb, blockSums, perThread);
-    hipLaunchKernelGGL(yk_corner_stream_batch_kernel<true>, dim3(pl.blockStart[7], F), dim3(1024), 0, c->stream, pl, cb, w, latW, (const uint32_t*)c->sb.owner,
+    hipLaunchKernelGGL(yk_corner_stream_batch_kernel<true>, dim3(pl.blockStart[7], F), dim3(1024), 0, c->stream, pl, cb, w, latW, (const uint32_t*)c->img.sb.owner,
                        blockSums, perThread, c->B.plane[0], c->B.plane[1], c->B.plane[2], c->strideElems, c->h / 4 + 1, c->h);
     YK_HIP(c, hipGetLastError());
     return YK_OK;
@@ -395,7 +395,7 @@ extern "C" int yk_gradient_corners(yk_ctx* c, int pass, uint8_t* hostOut, size_t
     if (hostOut) {
         if (cap < c->cornerBytes[pass]) return yk_fail(c, YK_ERR_RANGE, "corner buffer too small");
         if (c->cornerBytes[pass]) {
-            YK_HIP(c, hipMemcpyAsync(hostOut, c->cornerStream + c->cornerOff[pass], c->cornerBytes[pass], hipMemcpyDeviceToHost, c->stream));
+            YK_HIP(c, hipMemcpyAsync(hostOut, c->img.cornerStream + c->cornerOff[pass], c->cornerBytes[pass], hipMemcpyDeviceToHost, c->stream));
             YK_HIP(c, hipStreamSynchronize(c->stream));
         }
     }
@@ -408,7 +408,7 @@ extern "C" int yk_gradient_corners_device(yk_ctx* c, int pass, const uint8_t** d
     YK_HIP(c, hipSetDevice(c->device));
     if (!c->cornersReady) { int rc = yk_launch_corners(c); if (rc) return rc; }
     { int rc = yk_corners_finish(c); if (rc) return rc; }
-    *dev = c->cornerStream + c->cornerOff[pass]; *nBytes = c->cornerBytes[pass];
+    *dev = c->img.cornerStream + c->cornerOff[pass]; *nBytes = c->cornerBytes[pass];
     return YK_OK;
 }
 
@@ -426,9 +426,9 @@ extern "C" int yk_gradient_corner_edges(yk_ctx* c, uint32_t* hostKeys, uint32_t*
     if (!c->cornersReady) { int rc = yk_launch_corners(c); if (rc) return rc; }
     const size_t latW = (size_t)c->fullW / 4 + 1, latH = (size_t)c->h / 4 + 1;
     if (capElems < 2 * latW) return yk_fail(c, YK_ERR_RANGE, "edge buffers need 2 * (w/4 + 1) elements");
-    YK_HIP(c, hipMemcpyAsync(hostKeys, c->latticeOwner, latW * 4, hipMemcpyDeviceToHost, c->stream));
-    YK_HIP(c, hipMemcpyAsync(hostKeys + latW, c->latticeOwner + (latH - 1) * latW, latW * 4, hipMemcpyDeviceToHost, c->stream));
-    YK_HIP(c, hipMemcpyAsync(hostIndex, c->cornerEdgeIdx, 2 * latW * 4, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(hostKeys, c->img.latticeOwner, latW * 4, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(hostKeys + latW, c->img.latticeOwner + (latH - 1) * latW, latW * 4, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(hostIndex, c->img.cornerEdgeIdx, 2 * latW * 4, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }

@@ -970,13 +970,7 @@ __global__ __launch_bounds__(256) void yk_dec_ref_alpha_kernel(const uint8_t* __
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static int yk_dec_scratch(yk_ctx* c, size_t bytes) {
-    if (c->dScratchBytes >= bytes) return YK_OK;
-    if (c->dScratch) { YK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->dScratch); c->dScratch = nullptr; }
-    YK_HIP(c, hipMalloc(&c->dScratch, bytes));
-    c->dScratchBytes = bytes;
-    return YK_OK;
-}
+static int yk_dec_scratch(yk_ctx* c, size_t bytes) { YK_HIP(c, c->dScratch.reserve(c->stream, bytes)); return YK_OK; }
 
 extern "C" {
 
@@ -1031,15 +1025,13 @@ static void yk_dec_rebase(yk_ctx* c, int f) {
 }
 
 static void yk_dec_free_frames(yk_ctx* c) {
-    auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-    F(c->dB.planes); F(c->dB.mapRGB); F(c->dB.owner); F(c->dB.tile4); F(c->dB.loaded);
+    c->dFrm = yk_ctx::DFrames(); c->dB = {};
     c->dPlanes = nullptr; c->dMapRGB = nullptr; c->dLatticeOwner = nullptr; c->dTile4 = nullptr; c->dLoaded = nullptr;
     c->dw = c->dh = 0; c->dFrames = 1; c->dCur = 0;
 }
 
 }  // extern "C"
-void yk_dec_free(yk_ctx* c) {
-    yk_dec_free_frames(c);
+void yk_dec_ring_free(yk_ctx* c) {
     for (int i = 0; i < 4; i++) {
         if (c->dTabHost[i]) { (void)hipHostFree(c->dTabHost[i]); c->dTabHost[i] = nullptr; c->dTabHostBytes[i] = 0; }
         if (c->dTabEv[i]) { (void)hipEventDestroy(c->dTabEv[i]); c->dTabEv[i] = nullptr; }
@@ -1068,16 +1060,18 @@ static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
         c->dStride.owner = up16(lat * 4);
         c->dStride.loaded = up16(lat);
         c->dStride.tile4 = up16(((3 * c->dTile4Size + 3) & ~(size_t)3) + 4);         // three planes once the masks are split
-        hipError_t e = hipMalloc(&c->dB.planes, c->dStride.planes * N);
-        if (e == hipSuccess) e = hipMalloc(&c->dB.mapRGB, c->dStride.mapRGB * N);
-        if (e == hipSuccess) e = hipMalloc(&c->dB.owner, c->dStride.owner * N);
-        if (e == hipSuccess) e = hipMalloc(&c->dB.loaded, c->dStride.loaded * N);
-        if (e == hipSuccess) e = hipMalloc(&c->dB.tile4, c->dStride.tile4 * N);
+        auto& D = c->dFrm;
+        hipError_t e = D.planes.alloc(c->stream, c->dStride.planes * N);
+        if (e == hipSuccess) e = D.mapRGB.alloc(c->stream, c->dStride.mapRGB * N);
+        if (e == hipSuccess) e = D.owner.alloc(c->stream, c->dStride.owner * N / 4);            // the strides are bytes, multiples of 16
+        if (e == hipSuccess) e = D.loaded.alloc(c->stream, c->dStride.loaded * N);
+        if (e == hipSuccess) e = D.tile4.alloc(c->stream, c->dStride.tile4 * N);
         if (e != hipSuccess) {                                                       // what was allocated is released: the next begin starts afresh
             (void)hipGetLastError();
             yk_dec_free_frames(c);
             return yk_refuse(c, YK_ERR_HIP, "the decode buffers of this shape and frame count do not fit in device memory");
         }
+        c->dB = { D.planes, D.mapRGB, D.owner, D.loaded, D.tile4 };
         c->dw = w; c->dh = h; c->dFrames = nFrames;
     }
     yk_dec_rebase(c, 0);
@@ -1310,7 +1304,7 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
     }
     { const int rc = yk_dec_table_upload(c, slot, c->dScratch, (size_t)N * sizeof(DecPlan)); if (rc) return rc; }
     DecBatch B;
-    B.plans = reinterpret_cast<const DecPlan*>(c->dScratch);
+    B.plans = reinterpret_cast<const DecPlan*>(c->dScratch.p);
     B.loaded = c->dB.loaded; B.owner = reinterpret_cast<uint8_t*>(c->dB.owner); B.mapRGB = c->dB.mapRGB; B.planes = c->dB.planes; B.tile4 = c->dB.tile4;
     B.scratch = c->dScratch + tabBytes;
     B.sLoaded = c->dStride.loaded; B.sOwner = c->dStride.owner; B.sMapRGB = c->dStride.mapRGB; B.sPlanes = c->dStride.planes; B.sTile4 = c->dStride.tile4; B.sScratch = sS;
@@ -1472,7 +1466,7 @@ int yk_decode_1d_batch_device(yk_ctx* c, const uint8_t* const* devType, const si
     for (int f = 0; f < N; f++) { tab[f].type = devType[f]; tab[f].pix = devPix[f]; tab[f].typeBytes = typeBytes[f]; tab[f].pixBytes = pixBytes[f]; }
     { const int rc = yk_dec_table_upload(c, slot, c->dScratch, (size_t)N * sizeof(D1Frame)); if (rc) return rc; }
     D1Batch B;
-    B.frames = reinterpret_cast<const D1Frame*>(c->dScratch);
+    B.frames = reinterpret_cast<const D1Frame*>(c->dScratch.p);
     B.tile4 = c->dB.tile4; B.planes = c->dB.planes; B.scratch = c->dScratch + tabBytes;
     B.sTile4 = c->dStride.tile4; B.sPlanes = c->dStride.planes; B.sScratch = sS;
     B.oBT = oBT; B.oBP = oBP; B.oTot = oTot; B.oOff = oOff;

@@ -26,7 +26,7 @@
 #define LUT_FACTOR 128                      // FACTOR, EncoderContext.cpp:22
 #define LUT_MAXPAT 64
 
-struct YkLutPattern { uint16_t* dist; uint32_t* pos; short4* fac; int count; };      // device pointers
+struct YkLutPattern { YkBuf<uint16_t> dist; uint32_t* pos = nullptr; short4* fac = nullptr; int count = 0; };      // device memory; pos and fac point into posAll / facAll
 // ptab[pair * 8 + j] = the j-th point of a pattern's 3-bit subset as one orientation sees it (yk_lut_point_table).  Orientations of a pattern that
 // see the same SET of points score alike on every tile and the reference keeps the first of them (a strict `<`), so only the first of each
 // such group is a pair: pairs patStart[k] .. patStart[k + 1] - 1 belong to pattern k in the order of their orientations pairMode[pair] (the
@@ -37,19 +37,24 @@ struct YkLutPattern { uint16_t* dist; uint32_t* pos; short4* fac; int count; }; 
 struct YkLutBank { const uint2* ptab; const uint2* ptabM; const uint8_t* pairMode; const int* patStart; const uint32_t* pos; const short4* fac; int nPat, nPairs; };
 struct YkLutState {
     YkLutPattern pat[LUT_MAXPAT]; int nPat = 0;
-    uint2* ptab = nullptr;                  // [<= LUT_MAXPAT * 48 pairs][8], 192 KB
-    uint2* ptabM = nullptr;                 // the same points as rows of the MFMA scoring's A operand (see yk_lut_search_kernel), 64 zero rows behind them
-    uint8_t* pairMode = nullptr; int* patStart = nullptr;
+    YkBuf<uint2> ptab;                      // [<= LUT_MAXPAT * 48 pairs][8], 192 KB
+    YkBuf<uint2> ptabM;                     // the same points as rows of the MFMA scoring's A operand (see yk_lut_search_kernel), 64 zero rows behind them
+    YkBuf<uint8_t> pairMode; YkBuf<int> patStart;
     std::vector<uint2> hPtab, hPtabM; std::vector<uint8_t> hPairMode; std::vector<int> hPatStart = { 0 };      // host copies, grown by every yk_lut_load_pattern
-    uint32_t* posAll = nullptr;             // [LUT_MAXPAT][64^3], 64 MB (allocated with the first pattern)
-    short4* facAll = nullptr;               // [LUT_MAXPAT][4][64]
+    YkBuf<uint32_t> posAll;                 // [LUT_MAXPAT][64^3], 64 MB (allocated with the first pattern)
+    YkBuf<short4> facAll;                   // [LUT_MAXPAT][4][64]
     bool started = false;
-    // corr3D_* streams (StartCorrelationSearch :7316-7364), device
-    uint16_t* tileType = nullptr; uint8_t* color = nullptr; uint8_t* idx[4] = {}; uint8_t* map[6] = {};
-    size_t nType = 0, nColor = 0, nIdx[4] = {}, mapBytes[6] = {};
-    size_t capTiles = 0, capPix = 0; int capW = 0, capH = 0;
-    // per-pass scratch, sized for the 4x4 pass and kept across passes and searches
-    struct LutSlot* slots = nullptr; uint8_t* slotIdx = nullptr; uint32_t* sums = nullptr; uint32_t* list = nullptr;
+    // what is made for one image size (capW x capH) and released as a whole when the size changes
+    struct PerShape {
+        // corr3D_* streams (StartCorrelationSearch :7316-7364), device
+        YkBuf<uint16_t> tileType; YkBuf<uint8_t> color, idx[4];
+        YkBuf<uint8_t> map[6];              // map[k].cap = BitmapSwizzleMapSize of pass k, 16 more bytes behind it
+        // per-pass scratch, sized for the 4x4 pass and kept across passes and searches
+        YkBuf<struct LutSlot> slots; YkBuf<uint8_t> slotIdx; YkBuf<uint32_t> sums, list;
+    };
+    PerShape sh;
+    size_t nType = 0, nColor = 0, nIdx[4] = {};
+    int capW = 0, capH = 0;
 };
 
 // the 48 orientations of EvaluatePoint3D: its axis swap of group n >> 3 is applied to the RUNNING x, y, z on every iteration of its loop
@@ -694,16 +699,7 @@ __global__ __launch_bounds__(1024) void yk_lut_emit_kernel(const LutSlot* __rest
     for (int p = 0; p < s.pixels; p++) dst[p] = src[p];
 }
 
-static void yk_lut_release(yk_ctx* c) {
-    YkLutState* S = c->lut; if (!S) return;
-    auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-    for (int k = 0; k < S->nPat; k++) F(S->pat[k].dist);
-    F(S->ptab); F(S->ptabM); F(S->pairMode); F(S->patStart); F(S->posAll); F(S->facAll); F(S->slots); F(S->slotIdx); F(S->sums); F(S->list); F(S->tileType); F(S->color);
-    for (auto& p : S->idx) F(p);
-    for (auto& p : S->map) F(p);
-    delete S; c->lut = nullptr;
-}
-void yk_lut_destroy(yk_ctx* c) { yk_lut_release(c); }
+void yk_lut_destroy(yk_ctx* c) { delete c->lut; c->lut = nullptr; }
 
 static uint32_t yk_morton3(int r, int g, int b) {                              // morton256_x | _y | _z (:2799-2912): bit k of r, g, b -> bits 3k, 3k+1, 3k+2
     uint32_t m = 0;
@@ -713,7 +709,7 @@ static uint32_t yk_morton3(int r, int g, int b) {                              /
 
 extern "C" {
 
-int yk_lut_clear(yk_ctx* c) { if (!c) return YK_ERR_BAD_ARG; YK_HIP(c, hipSetDevice(c->device)); YK_HIP(c, hipStreamSynchronize(c->stream)); yk_lut_release(c); return YK_OK; }
+int yk_lut_clear(yk_ctx* c) { if (!c) return YK_ERR_BAD_ARG; YK_HIP(c, hipSetDevice(c->device)); YK_HIP(c, hipStreamSynchronize(c->stream)); yk_lut_destroy(c); return YK_OK; }
 
 int yk_lut_load_pattern(yk_ctx* c, const uint8_t* r, const uint8_t* g, const uint8_t* b, int count, int* index) {
     if (!c || !r || !g || !b) return YK_ERR_BAD_ARG;
@@ -723,12 +719,12 @@ int yk_lut_load_pattern(yk_ctx* c, const uint8_t* r, const uint8_t* g, const uin
     YK_HIP(c, hipSetDevice(c->device));
     if (!c->lut) c->lut = new YkLutState();
     YkLutState* S = c->lut;
-    if (!S->ptab) YK_HIP(c, hipMalloc(&S->ptab, (size_t)LUT_MAXPAT * 48 * 8 * sizeof(uint2)));
-    if (!S->ptabM) YK_HIP(c, hipMalloc(&S->ptabM, ((size_t)LUT_MAXPAT * 48 * 8 + 64) * sizeof(uint2)));
-    if (!S->pairMode) YK_HIP(c, hipMalloc(&S->pairMode, (size_t)LUT_MAXPAT * 48));
-    if (!S->patStart) YK_HIP(c, hipMalloc(&S->patStart, (LUT_MAXPAT + 1) * sizeof(int)));
-    if (!S->posAll) YK_HIP(c, hipMalloc(&S->posAll, (size_t)LUT_MAXPAT * LUT_CUBE * sizeof(uint32_t)));
-    if (!S->facAll) YK_HIP(c, hipMalloc(&S->facAll, (size_t)LUT_MAXPAT * 4 * 64 * sizeof(short4)));
+    if (!S->ptab) YK_HIP(c, S->ptab.alloc(c->stream, (size_t)LUT_MAXPAT * 48 * 8));     // the bank's tables: once, with the first pattern
+    if (!S->ptabM) YK_HIP(c, S->ptabM.alloc(c->stream, (size_t)LUT_MAXPAT * 48 * 8 + 64));
+    if (!S->pairMode) YK_HIP(c, S->pairMode.alloc(c->stream, (size_t)LUT_MAXPAT * 48));
+    if (!S->patStart) YK_HIP(c, S->patStart.alloc(c->stream, LUT_MAXPAT + 1));
+    if (!S->posAll) YK_HIP(c, S->posAll.alloc(c->stream, (size_t)LUT_MAXPAT * LUT_CUBE));
+    if (!S->facAll) YK_HIP(c, S->facAll.alloc(c->stream, (size_t)LUT_MAXPAT * 4 * 64));
     if (S->nPat >= LUT_MAXPAT) return yk_fail(c, YK_ERR_RANGE, "LUT 3D more than 64 entries");     // :7912
     uint8_t pts[64 * 3];
     for (int n = 0; n < count; n++) { pts[n * 3] = r[n]; pts[n * 3 + 1] = g[n]; pts[n * 3 + 2] = b[n]; }
@@ -744,14 +740,14 @@ int yk_lut_load_pattern(yk_ctx* c, const uint8_t* r, const uint8_t* g, const uin
             for (int k = 0; k < 3; k++) fac[step][k][p >> step] = (int16_t)((pts[p * 3 + k] / 63.0f) * LUT_FACTOR);
     YkLutPattern& P = S->pat[S->nPat];
     P.count = count;
-    YK_HIP(c, hipMalloc(&P.dist, LUT_CUBE * sizeof(uint16_t)));
+    YK_HIP(c, P.dist.alloc(c->stream, LUT_CUBE));
     P.pos = S->posAll + (size_t)S->nPat * LUT_CUBE;
     P.fac = S->facAll + (size_t)S->nPat * 4 * 64;
     short4 fac4[4][64];
     for (int step = 0; step < 4; step++)
         for (int e = 0; e < 64; e++) fac4[step][e] = make_short4(fac[step][0][e], fac[step][1][e], fac[step][2][e], 0);
-    uint8_t* dPts = nullptr;
-    YK_HIP(c, hipMalloc(&dPts, 64 * 3));
+    YkBuf<uint8_t> dPts;                                                      // a temporary of this call: goes on every return
+    YK_HIP(c, dPts.alloc(c->stream, 64 * 3));
     YK_HIP(c, hipMemcpyAsync(dPts, pts, (size_t)count * 3, hipMemcpyHostToDevice, c->stream));
     YK_HIP(c, hipMemcpyAsync(P.fac, fac4, sizeof fac4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(yk_lut_build_kernel, dim3(LUT_CUBE / 256), dim3(256), 0, c->stream, dPts, count, P.dist, P.pos);
@@ -778,7 +774,6 @@ int yk_lut_load_pattern(yk_ctx* c, const uint8_t* r, const uint8_t* g, const uin
     }
     YK_HIP(c, hipGetLastError());
     YK_HIP(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(dPts);
     if (index) *index = S->nPat;
     S->nPat++;
     return YK_OK;
@@ -815,27 +810,24 @@ int yk_lut_start(yk_ctx* c) {
     static const int sz[6][2] = { {4,3}, {3,4}, {3,3}, {3,2}, {2,3}, {2,2} };
     const size_t capTiles = (size_t)(w / 4) * (h / 4) + 16, capPix = (size_t)w * h + 128;
     if (w != S->capW || h != S->capH) {                      // a new image size: the streams, the maps and the per-pass scratch
-        auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
         YK_HIP(c, hipStreamSynchronize(c->stream));
-        F(S->tileType); F(S->color); for (auto& p : S->idx) F(p); for (auto& p : S->map) F(p); F(S->slots); F(S->slotIdx); F(S->sums); F(S->list);
-        S->capTiles = S->capPix = 0; S->capW = S->capH = 0;
-        YK_HIP(c, hipMalloc(&S->tileType, capTiles * 2));
-        YK_HIP(c, hipMalloc(&S->color, capTiles * 6));
-        for (auto& p : S->idx) YK_HIP(c, hipMalloc(&p, capPix));
+        S->sh = YkLutState::PerShape(); S->capW = S->capH = 0;   // all of the old size go first; no size until every new one is there
+        YK_HIP(c, S->sh.tileType.alloc(c->stream, capTiles));
+        YK_HIP(c, S->sh.color.alloc(c->stream, capTiles * 6));
+        for (auto& b : S->sh.idx) YK_HIP(c, b.alloc(c->stream, capPix));
         size_t maxSlots = 0;
         for (int k = 0; k < 6; k++) {
             const LutGeo g = yk_lut_geo(sz[k][0], sz[k][1], w);
-            S->mapBytes[k] = (size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount;       // BitmapSwizzleMapSize (:7310): a bit count used as the byte size
-            YK_HIP(c, hipMalloc(&S->map[k], S->mapBytes[k] + 16));
-            maxSlots = std::max(maxSlots, S->mapBytes[k]);                                    // = the pass's tile slots
+            YK_HIP(c, S->sh.map[k].alloc(c->stream, (size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount, 16));       // BitmapSwizzleMapSize (:7310): a bit count used as the byte size
+            maxSlots = std::max(maxSlots, S->sh.map[k].cap);                                    // = the pass's tile slots
         }
-        YK_HIP(c, hipMalloc(&S->slots, maxSlots * sizeof(LutSlot)));
-        YK_HIP(c, hipMalloc(&S->slotIdx, (size_t)(w + 64) * (h + 64)));                      // slots x pixels per tile = whole swizzle blocks (64 x 64 at most), any shape
-        YK_HIP(c, hipMalloc(&S->sums, (5 * ((maxSlots + 1023) / 1024) + 16) * sizeof(uint32_t)));
-        YK_HIP(c, hipMalloc(&S->list, (maxSlots + 1) * sizeof(uint2)));
-        S->capTiles = capTiles; S->capPix = capPix; S->capW = w; S->capH = h;
+        YK_HIP(c, S->sh.slots.alloc(c->stream, maxSlots));
+        YK_HIP(c, S->sh.slotIdx.alloc(c->stream, (size_t)(w + 64) * (h + 64)));                      // slots x pixels per tile = whole swizzle blocks (64 x 64 at most), any shape
+        YK_HIP(c, S->sh.sums.alloc(c->stream, 5 * ((maxSlots + 1023) / 1024) + 16));
+        YK_HIP(c, S->sh.list.alloc(c->stream, (maxSlots + 1) * 2));                                  // uint2 entries
+        S->capW = w; S->capH = h;
     }
-    for (int k = 0; k < 6; k++) YK_HIP(c, hipMemsetAsync(S->map[k], 0, S->mapBytes[k] + 16, c->stream));
+    for (int k = 0; k < 6; k++) YK_HIP(c, hipMemsetAsync(S->sh.map[k], 0, S->sh.map[k].cap + 16, c->stream));
     S->nType = S->nColor = 0; for (auto& n : S->nIdx) n = 0;
     { int rc = yk_pp_activate(c); if (rc) return rc; }                          // LUT tiles paint mapSmoothTile only, never smoothMap
     S->started = true;
@@ -852,22 +844,22 @@ int yk_lut_search(yk_ctx* c, int shiftX, int shiftY, int* matched) {
     YkLutState* S = c->lut;
     const int w = c->fullW, h = c->h, nPix = (1 << shiftX) * (1 << shiftY);
     const size_t nSlots = (size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount, nb = (nSlots + 1023) / 1024;
-    LutSlot* const slots = S->slots; uint8_t* const slotIdx = S->slotIdx; uint32_t* const sums = S->sums;    // yk_lut_start sized them
+    LutSlot* const slots = S->sh.slots; uint8_t* const slotIdx = S->sh.slotIdx; uint32_t* const sums = S->sh.sums;    // yk_lut_start sized them
     YkLutBank bank; bank.ptab = S->ptab; bank.ptabM = S->ptabM; bank.pairMode = S->pairMode; bank.patStart = S->patStart; bank.pos = S->posAll; bank.fac = S->facAll;
     bank.nPat = S->nPat; bank.nPairs = (int)S->hPairMode.size();
     uint32_t nCand = 0;
-    YK_HIP(c, hipMemsetAsync(S->list, 0, sizeof(uint32_t), c->stream));
+    YK_HIP(c, hipMemsetAsync(S->sh.list, 0, sizeof(uint32_t), c->stream));
     { int rc = yk_stage_begin(c, YK_STAGE_LUT3D); if (rc) return rc; }
-    hipLaunchKernelGGL(yk_lut_list_kernel, dim3((unsigned)((nSlots + 4095) / 4096)), dim3(1024), 0, c->stream, c->covCh, c->covChStride, c->mtW, g, w, h, nSlots, slots, S->list);
+    hipLaunchKernelGGL(yk_lut_list_kernel, dim3((unsigned)((nSlots + 4095) / 4096)), dim3(1024), 0, c->stream, c->img.covCh, c->covChStride, c->mtW, g, w, h, nSlots, slots, S->sh.list);
     { int rc = yk_stage_end(c, YK_STAGE_LUT3D); if (rc) return rc; }
     YK_HIP(c, hipGetLastError());
-    YK_HIP(c, hipMemcpyAsync(&nCand, S->list, sizeof nCand, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(&nCand, S->sh.list, sizeof nCand, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));                              // the grid of the search is the number of candidates
     if (nCand) {
         { int rc = yk_stage_begin(c, YK_STAGE_LUT3D); if (rc) return rc; }
 #define YK_LUT_LAUNCH(SX_, SY_) hipLaunchKernelGGL((yk_lut_search_kernel<SX_, SY_>), dim3(nCand), dim3(nPix > 64 ? 128 : 64), (size_t)S->nPat * (48 + 1 + 16) * sizeof(int), c->stream,       \
-                           c->plane[0], c->plane[1], c->plane[2], c->strideElems, w, h, g, bank, reinterpret_cast<uint32_t*>(c->covCh), c->covChStride, c->mtW, slots, slotIdx,               \
-                           reinterpret_cast<uint32_t*>(S->map[g.mapId]), S->list)
+                           c->plane[0], c->plane[1], c->plane[2], c->strideElems, w, h, g, bank, reinterpret_cast<uint32_t*>(c->img.covCh.p), c->covChStride, c->mtW, slots, slotIdx,               \
+                           reinterpret_cast<uint32_t*>(S->sh.map[g.mapId].p), S->sh.list)
         switch (g.mapId) {                                                  // one instantiation per tile shape
             case 0: YK_LUT_LAUNCH(4, 3); break;
             case 1: YK_LUT_LAUNCH(3, 4); break;
@@ -881,8 +873,8 @@ int yk_lut_search(yk_ctx* c, int shiftX, int shiftY, int* matched) {
     }
     hipLaunchKernelGGL(yk_lut_count_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, slots, nSlots, sums, nb);
     hipLaunchKernelGGL(yk_lut_scan_kernel, dim3(1), dim3(1024), 0, c->stream, sums, nb, sums + 5 * nb);
-    LutStreams out; out.tileType = S->tileType; out.color = S->color; out.nType = S->nType; out.nColor = S->nColor;
-    for (int m = 0; m < 4; m++) { out.idx[m] = S->idx[m]; out.nIdx[m] = S->nIdx[m]; }
+    LutStreams out; out.tileType = S->sh.tileType; out.color = S->sh.color; out.nType = S->nType; out.nColor = S->nColor;
+    for (int m = 0; m < 4; m++) { out.idx[m] = S->sh.idx[m]; out.nIdx[m] = S->nIdx[m]; }
     hipLaunchKernelGGL(yk_lut_emit_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, slots, slotIdx, nPix, nSlots, sums, nb, out);
     hipError_t e = hipGetLastError();
     uint32_t tot[5] = {};
@@ -903,10 +895,10 @@ int yk_lut_stream(yk_ctx* c, int which, uint8_t* hostOut, size_t cap, size_t* nB
     if (!c->lut || !c->lut->started) return yk_fail(c, YK_ERR_STATE, "yk_lut_start first");
     YkLutState* S = c->lut;
     const void* src; size_t n;
-    if (which == 0) { src = S->tileType; n = S->nType * 2; }
-    else if (which == 1) { src = S->color; n = S->nColor; }
-    else if (which <= 5) { src = S->idx[which - 2]; n = S->nIdx[which - 2]; }
-    else { src = S->map[which - 6]; n = S->mapBytes[which - 6]; }
+    if (which == 0) { src = S->sh.tileType; n = S->nType * 2; }
+    else if (which == 1) { src = S->sh.color; n = S->nColor; }
+    else if (which <= 5) { src = S->sh.idx[which - 2]; n = S->nIdx[which - 2]; }
+    else { src = S->sh.map[which - 6]; n = S->sh.map[which - 6].cap; }
     if (nBytes) *nBytes = n;
     if (hostOut && n) {
         if (cap < n) return yk_fail(c, YK_ERR_RANGE, "stream buffer too small");
@@ -924,7 +916,7 @@ int yk_lut_stream(yk_ctx* c, int which, uint8_t* hostOut, size_t cap, size_t* nB
 // tile maps sequentially, popping 6 colour bytes, a tile word and one pre-multiplied index per still unmarked pixel per tile.  Here a pass
 // is three small launches: rank of every set map bit (= position in the tile / colour streams), index bytes per depth of every tile from
 // its tile word and the tile4x4Mask state (-> offsets in the four index streams), then the fill.  Tiles of a pass are disjoint.
-struct YkLutDecState { uint8_t* tbl[4] = {}; int nPat = 0; };
+struct YkLutDecState { YkBuf<uint8_t> tbl[4]; int nPat = 0; };
 
 __device__ __forceinline__ bool yk_dl_tile(const uint32_t* __restrict__ map, size_t nSlots, size_t pos, const LutGeo& g, int w, int h, int& x0, int& y0) {
     if (pos >= nSlots || !((map[pos >> 5] >> (pos & 31)) & 1u)) return false;
@@ -1007,11 +999,7 @@ __global__ __launch_bounds__(256) void yk_dl_mark_kernel(const uint32_t* __restr
     }
 }
 
-void yk_lut_dec_destroy(yk_ctx* c) {
-    if (!c->lutDec) return;
-    for (auto& p : c->lutDec->tbl) if (p) (void)hipFree(p);
-    delete c->lutDec; c->lutDec = nullptr;
-}
+void yk_lut_dec_destroy(yk_ctx* c) { delete c->lutDec; c->lutDec = nullptr; }
 
 extern "C" {
 
@@ -1037,7 +1025,7 @@ int yk_decode_assign_lut(yk_ctx* c, const uint8_t* lutFile, size_t lutBytes) {
             }
             stream += len * 3;
         }
-        YK_HIP(c, hipMalloc(&c->lutDec->tbl[bit - 3], T.size() + 16));
+        YK_HIP(c, c->lutDec->tbl[bit - 3].alloc(c->stream, T.size() + 16));
         YK_HIP(c, hipMemcpy(c->lutDec->tbl[bit - 3], T.data(), T.size(), hipMemcpyHostToDevice));
     }
     return YK_OK;
@@ -1053,15 +1041,15 @@ int yk_decode_lut3d(yk_ctx* c, const uint8_t* const maps[6], const size_t mapByt
     YK_HIP(c, hipSetDevice(c->device));
     const int w = c->dw, h = c->dh;
     static const int sz[6][2] = { {4,3}, {3,4}, {3,3}, {3,2}, {2,3}, {2,2} };
-    uint16_t* dTiles = nullptr; uint8_t* dColors = nullptr; uint8_t* dIdx[4] = {}; uint32_t* dMap = nullptr; uint32_t* sums = nullptr;
-    auto freeAll = [&]() { (void)hipFree(dTiles); (void)hipFree(dColors); for (auto p : dIdx) (void)hipFree(p); (void)hipFree(dMap); (void)hipFree(sums); };
+    YkBuf<uint16_t> dTiles; YkBuf<uint8_t> dColors, dIdx[4], dMapBytes; YkBuf<uint32_t> sums;   // temporaries of this call
     size_t maxMap = 0; for (int k = 0; k < 6; k++) maxMap = mapBytes[k] > maxMap ? mapBytes[k] : maxMap;
     const size_t maxSlots = maxMap * 8, maxNb = (maxSlots + 1023) / 1024 + 1;
-    hipError_t e = hipMalloc(&dTiles, nTiles * 2 + 64);
-    if (e == hipSuccess) e = hipMalloc(&dColors, nTiles * 6 + 64);
-    for (int f = 0; f < 4 && e == hipSuccess; f++) e = hipMalloc(&dIdx[f], idxBytes[f] + 256);
-    if (e == hipSuccess) e = hipMalloc(&dMap, maxMap + 64);
-    if (e == hipSuccess) e = hipMalloc(&sums, (5 * maxNb + 16) * sizeof(uint32_t));
+    hipError_t e = dTiles.alloc(c->stream, nTiles, 64);
+    if (e == hipSuccess) e = dColors.alloc(c->stream, nTiles * 6 + 64);
+    for (int f = 0; f < 4 && e == hipSuccess; f++) e = dIdx[f].alloc(c->stream, idxBytes[f] + 256);
+    if (e == hipSuccess) e = dMapBytes.alloc(c->stream, maxMap + 64);
+    uint32_t* const dMap = reinterpret_cast<uint32_t*>(dMapBytes.p);
+    if (e == hipSuccess) e = sums.alloc(c->stream, 5 * maxNb + 16);
     if (e == hipSuccess && nTiles) e = hipMemcpyAsync(dTiles, tiles, nTiles * 2, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && nTiles) e = hipMemcpyAsync(dColors, colors, nTiles * 6, hipMemcpyHostToDevice, c->stream);
     for (int f = 0; f < 4 && e == hipSuccess; f++) {
@@ -1105,7 +1093,6 @@ int yk_decode_lut3d(yk_ctx* c, const uint8_t* const maps[6], const size_t mapByt
         for (int f = 0; f < 4; f++) ib[f] += tot[1 + f];
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    freeAll();
     if (e != hipSuccess) return yk_fail(c, YK_ERR_HIP, "3-D LUT decode", e);
     if (shortStream) return yk_fail(c, YK_ERR_RANGE, "tile, colour or index stream shorter than the tile maps need");
     if (consumed) { consumed[0] = (size_t)tileBase * 2; consumed[1] = (size_t)tileBase * 6; for (int f = 0; f < 4; f++) consumed[2 + f] = (size_t)ib[f]; }

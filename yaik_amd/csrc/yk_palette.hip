@@ -354,13 +354,6 @@ __global__ __launch_bounds__(PAL_WG) void yk_pal_emit_kernel(YkPalBufs B, uint8_
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------------
-void yk_pal_free(yk_ctx* c) {
-    YkPalette& P = c->pal;
-    auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-    F(P.scratch); F(P.out); F(P.carry);
-    P.scratchCap = P.outCap = 0; P.valid = false; P.nSeg = 0; P.carryFresh = true;
-}
-
 // the caller has validated: 1 <= nSeg <= PAL_MAX_SEGS, every length a multiple of 3, a pointer for every non-empty stream, chain >= 0
 static int yk_pal_run(yk_ctx* c, const uint8_t* const* dev, const size_t* nBytes, int nSeg, int chain) {
     YkPalette& P = c->pal;
@@ -388,9 +381,9 @@ static int yk_pal_run(yk_ctx* c, const uint8_t* const* dev, const size_t* nBytes
     const size_t oCK = place((size_t)nSlices * 128 * 8), oCD = place((size_t)nSlices * 128 * 4), oSC = place((size_t)nSlices * 4);
     const size_t oBook = place((size_t)nSeg * 128 * 4), oFind = place((size_t)nSeg * 64 * 4);
     const size_t oTok = place((size_t)nCol * 4), oWB = place((size_t)nWg * 4), oWO = place((size_t)nWg * 4), oLen = place((size_t)nSeg * 8);
-    { void* p = P.scratch; int rc = yk_sb_grow_bytes(c, &p, &P.scratchCap, cur); P.scratch = static_cast<uint8_t*>(p); if (rc) return rc; }
-    { void* p = P.out; int rc = yk_sb_grow_bytes(c, &p, &P.outCap, (size_t)outNeed + 16); P.out = static_cast<uint8_t*>(p); if (rc) return rc; }
-    if (!P.carry) YK_HIP(c, hipMalloc(&P.carry, 64 * sizeof(uint32_t)));
+    YK_HIP(c, P.scratch.reserve(c->stream, cur));
+    YK_HIP(c, P.out.reserve(c->stream, (size_t)outNeed + 16));
+    if (!P.carry) YK_HIP(c, P.carry.alloc(c->stream, 64));
     YkPalBufs B;
     B.segs = reinterpret_cast<const YkPalSeg*>(P.scratch + oSeg); B.nSeg = (uint32_t)nSeg;
     B.tKey = reinterpret_cast<uint32_t*>(P.scratch + oKey); B.tVotes = B.tKey + nSlots; B.tFirst = reinterpret_cast<uint32_t*>(P.scratch + oFirst);
@@ -459,7 +452,7 @@ int yk_palette_compress(yk_ctx* c) {
 
 int yk_palette_compress_batch(yk_ctx* c) {
     if (!c) return YK_ERR_BAD_ARG;
-    const YkStreamsBatch& b = c->sb;
+    const YkStreamsBatch& b = c->img.sb;
     if (!b.valid || (int)b.table.size() != c->nFrames || !(b.what & YK_STREAMS_CORNERS))
         return yk_refuse(c, YK_ERR_STATE, "yk_encode_streams_batch with YK_STREAMS_CORNERS first (the table does not outlive an encode, a new image or new planes)");
     const int N = c->nFrames;

@@ -332,13 +332,6 @@ __global__ __launch_bounds__(PD_CC) void yk_pd_apply_kernel(YkPdBufs B, uint8_t*
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------------
-void yk_pd_free(yk_ctx* c) {
-    YkPaletteDec& P = c->pdec;
-    auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-    F(P.scratch); F(P.out); F(P.stage);
-    P.scratchCap = P.outCap = P.stageCap = 0; P.valid = false; P.nSeg = 0;
-}
-
 static int yk_pd_validate(yk_ctx* c, const uint8_t* const* dev, const size_t* payBytes, const size_t* outBytes, int nStreams, int remapRange) {
     if (!dev || !payBytes || !outBytes) return yk_refuse(c, YK_ERR_BAD_ARG, "devPayloads, payBytes or outBytes is NULL");
     if (nStreams < 1 || nStreams > PD_MAX_SEGS) return yk_refuse(c, YK_ERR_BAD_ARG, "nStreams must be 1..65536");
@@ -384,8 +377,8 @@ static int yk_pd_run(yk_ctx* c, const uint8_t* const* dev, const size_t* payByte
     const size_t oTok = place((size_t)nCol * 4), oVal = place((size_t)nCol * 4), oPtr = place((size_t)nCol), oHalo = place((size_t)nCWg * PD_BACK * 4);
     const size_t oStat = place((size_t)nSeg * 8), oCb = place((size_t)nAWg * PD_WGCH * 4), oBk = place((size_t)nCol * 2);
     P.valid = false;
-    { void* p = P.scratch; int rc = yk_sb_grow_bytes(c, &p, &P.scratchCap, cur); P.scratch = static_cast<uint8_t*>(p); if (rc) return rc; }
-    { void* p = P.out; int rc = yk_sb_grow_bytes(c, &p, &P.outCap, outUsed + 2 * PD_MARGIN); P.out = static_cast<uint8_t*>(p); if (rc) return rc; }
+    YK_HIP(c, P.scratch.reserve(c->stream, cur));
+    YK_HIP(c, P.out.reserve(c->stream, outUsed + 2 * PD_MARGIN));
     YkPdBufs B;
     B.segs = reinterpret_cast<const YkPdSeg*>(P.scratch + oSeg); B.nSeg = (uint32_t)nSeg;
     B.rec = reinterpret_cast<uint32_t*>(P.scratch + oRec); B.chunkInfo = reinterpret_cast<uint32_t*>(P.scratch + oInfo);
@@ -465,7 +458,7 @@ int yk_decode_gradient_palette(yk_ctx* c, int sx, int sy, const uint8_t* bitmap,
     YkPaletteDec& P = c->pdec;
     YK_HIP(c, hipSetDevice(c->device));
     const size_t oPay = (bitmapBytes + 15) & ~(size_t)15;
-    { void* p = P.stage; int rc = yk_sb_grow_bytes(c, &p, &P.stageCap, oPay + payloadBytes + 16); P.stage = static_cast<uint8_t*>(p); if (rc) return rc; }
+    YK_HIP(c, P.stage.reserve(c->stream, oPay + payloadBytes + 16));
     const uint8_t* devPay = P.stage + oPay;
     { int rc = yk_pd_validate(c, &devPay, &payloadBytes, &rgbBytes, 1, colorCompression); if (rc) return rc; }
     YK_HIP(c, hipMemcpyAsync(P.stage, bitmap, bitmapBytes, hipMemcpyHostToDevice, c->stream));

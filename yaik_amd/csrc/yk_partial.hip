@@ -177,14 +177,14 @@ int yk_pp_activate(yk_ctx* c) {
     // the corner lattice of the RGB passes must exist: it tells which lattice points every plane already has
     if (!c->cornersReady) { int rc = yk_launch_corners(c); if (rc) return rc; }
     c->covChStride = (nMT + 7) & ~(size_t)7;
-    if (!c->covCh) {
-        YK_HIP(c, hipMalloc(&c->covCh, 3 * c->covChStride * sizeof(uint16_t) + 16));
-        YK_HIP(c, hipMalloc(&c->mapped3, lat + 16));
+    if (!c->img.covCh) {
+        YK_HIP(c, c->img.covCh.alloc(c->stream, 3 * c->covChStride, 16));
+        YK_HIP(c, c->img.mapped3.alloc(c->stream, lat + 16));
     }
-    YK_HIP(c, hipMemsetAsync(c->covCh, 0, 3 * c->covChStride * sizeof(uint16_t) + 16, c->stream));
+    YK_HIP(c, hipMemsetAsync(c->img.covCh, 0, 3 * c->covChStride * sizeof(uint16_t) + 16, c->stream));
     const size_t n = nMT > lat ? nMT : lat;
-    hipLaunchKernelGGL(yk_pp_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->coverage, nMT, c->covCh, c->covChStride,
-                       c->latticeOwner, lat, c->mapped3);
+    hipLaunchKernelGGL(yk_pp_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->coverage, nMT, c->img.covCh, c->covChStride,
+                       c->img.latticeOwner, lat, c->img.mapped3);
     YK_HIP(c, hipGetLastError());
     c->ppActive = true;
     return YK_OK;
@@ -208,24 +208,24 @@ int yk_gradient_partial_pass(yk_ctx* c, int rejectFactor, int planeBit, int sx, 
     const PPGeo g = yk_pp_geo(sx, sy, w);
     const size_t nBits = (size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount, nWords = (nBits + 31) / 32, nb = (nBits + 1023) / 1024;
     const size_t needScratch = lat + nb + 64;
-    if (c->ppBitmapCap < nWords * 4) { if (c->ppBitmap) (void)hipFree(c->ppBitmap); YK_HIP(c, hipMalloc(&c->ppBitmap, nWords * 4 + 16)); c->ppBitmapCap = nWords * 4; }
-    if (c->ppScratchElems < needScratch) { if (c->ppScratch) (void)hipFree(c->ppScratch); YK_HIP(c, hipMalloc(&c->ppScratch, needScratch * 4)); c->ppScratchElems = needScratch; }
-    if (c->ppStreamCap < lat * 3 + 16) { if (c->ppStream) (void)hipFree(c->ppStream); YK_HIP(c, hipMalloc(&c->ppStream, lat * 3 + 16)); c->ppStreamCap = lat * 3 + 16; }
-    uint32_t* owner = c->ppScratch; uint32_t* blockSums = owner + lat; uint32_t* total = blockSums + nb; uint32_t* accepted = total + 1;
-    YK_HIP(c, hipMemsetAsync(c->ppBitmap, 0, nWords * 4, c->stream));
+    YK_HIP(c, c->img.ppBitmap.reserve(c->stream, nWords, 16));
+    YK_HIP(c, c->img.ppScratch.reserve(c->stream, needScratch));
+    YK_HIP(c, c->img.ppStream.reserve(c->stream, lat * 3 + 16));
+    uint32_t* owner = c->img.ppScratch; uint32_t* blockSums = owner + lat; uint32_t* total = blockSums + nb; uint32_t* accepted = total + 1;
+    YK_HIP(c, hipMemsetAsync(c->img.ppBitmap, 0, nWords * 4, c->stream));
     YK_HIP(c, hipMemsetAsync(owner, 0xFF, lat * 4, c->stream));
     YK_HIP(c, hipMemsetAsync(total, 0, 8, c->stream));
     PPPlanes P; for (int n = 0; n < 3; n++) P.p[n] = c->plane[n];
     P.strideElems = c->strideElems; P.w = w; P.h = h; P.hAvail = h + c->halo;
     const unsigned g256 = (unsigned)((nBits + 255) / 256);
-    hipLaunchKernelGGL(yk_pp_decide_kernel, dim3(g256), dim3(256), 0, c->stream, P, g, nBits, planeBit, rejectFactor, c->covCh, c->covChStride, c->mtW, c->ppBitmap, accepted);
-    hipLaunchKernelGGL(yk_pp_paint_kernel, dim3(g256), dim3(256), 0, c->stream, g, nBits, planeBit, c->ppBitmap, reinterpret_cast<uint32_t*>(c->covCh), c->covChStride,
+    hipLaunchKernelGGL(yk_pp_decide_kernel, dim3(g256), dim3(256), 0, c->stream, P, g, nBits, planeBit, rejectFactor, c->img.covCh, c->covChStride, c->mtW, c->img.ppBitmap, accepted);
+    hipLaunchKernelGGL(yk_pp_paint_kernel, dim3(g256), dim3(256), 0, c->stream, g, nBits, planeBit, c->img.ppBitmap, reinterpret_cast<uint32_t*>(c->img.covCh.p), c->covChStride,
                        reinterpret_cast<uint32_t*>(c->coverage), c->mtW);
-    hipLaunchKernelGGL(yk_pp_owner_kernel, dim3(g256), dim3(256), 0, c->stream, g, nBits, planeBit, c->ppBitmap, latW, c->mapped3, owner);
-    hipLaunchKernelGGL(yk_pp_stream_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, c->stream, P, g, nBits, planeBit, c->ppBitmap, latW, c->mapped3, owner, blockSums, (uint8_t*)nullptr);
+    hipLaunchKernelGGL(yk_pp_owner_kernel, dim3(g256), dim3(256), 0, c->stream, g, nBits, planeBit, c->img.ppBitmap, latW, c->img.mapped3, owner);
+    hipLaunchKernelGGL(yk_pp_stream_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, c->stream, P, g, nBits, planeBit, c->img.ppBitmap, latW, c->img.mapped3, owner, blockSums, (uint8_t*)nullptr);
     hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, (int)nb, total);
-    hipLaunchKernelGGL(yk_pp_stream_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, c->stream, P, g, nBits, planeBit, c->ppBitmap, latW, c->mapped3, owner, blockSums, c->ppStream);
-    hipLaunchKernelGGL(yk_pp_mark_kernel, dim3((unsigned)((lat + 255) / 256)), dim3(256), 0, c->stream, owner, lat, planeBit, c->mapped3);
+    hipLaunchKernelGGL(yk_pp_stream_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, c->stream, P, g, nBits, planeBit, c->img.ppBitmap, latW, c->img.mapped3, owner, blockSums, c->img.ppStream);
+    hipLaunchKernelGGL(yk_pp_mark_kernel, dim3((unsigned)((lat + 255) / 256)), dim3(256), 0, c->stream, owner, lat, planeBit, c->img.mapped3);
     YK_HIP(c, hipGetLastError());
     uint32_t res[2];
     YK_HIP(c, hipMemcpyAsync(res, total, sizeof res, hipMemcpyDeviceToHost, c->stream));
@@ -243,13 +243,13 @@ int yk_gradient_preview(yk_ctx* c, int pass, int32_t* hostOut, size_t capElems) 
     if (!c || pass < 0 || pass > 7) return YK_ERR_BAD_ARG;
     if (!c->encoded) return yk_fail(c, YK_ERR_STATE, "yk_encode_tiles first");
     if (c->nFrames != 1 || c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "the preview planes exist for single whole images");
-    if (pass == 7 && (!c->ppActive || !c->ppBitmap || c->ppLastBit == 0)) return yk_fail(c, YK_ERR_STATE, "no plane-subset pass ran since the encode");
+    if (pass == 7 && (!c->ppActive || !c->img.ppBitmap || c->ppLastBit == 0)) return yk_fail(c, YK_ERR_STATE, "no plane-subset pass ran since the encode");
     YK_HIP(c, hipSetDevice(c->device));
     const int w = c->fullW, h = c->h;
     const size_t planeElems = (size_t)w * h;
-    if (!c->preview) { YK_HIP(c, hipMalloc(&c->preview, 3 * planeElems * sizeof(int32_t))); c->previewFresh = false; }
+    if (!c->img.preview) { YK_HIP(c, c->img.preview.alloc(c->stream, 3 * planeElems)); c->previewFresh = false; }
     if (!c->previewFresh) {                                                  // a new encode starts from untouched planes (INT32_MIN = no tile wrote here)
-        hipLaunchKernelGGL(yk_pp_fill_i32_kernel, dim3((unsigned)((3 * planeElems + 255) / 256)), dim3(256), 0, c->stream, c->preview, 3 * planeElems, (int32_t)0x80000000);
+        hipLaunchKernelGGL(yk_pp_fill_i32_kernel, dim3((unsigned)((3 * planeElems + 255) / 256)), dim3(256), 0, c->stream, c->img.preview, 3 * planeElems, (int32_t)0x80000000);
         c->previewFresh = true;
     }
     static const int shp[7][2] = { {4,4},{4,3},{3,4},{3,3},{3,2},{2,3},{2,2} };
@@ -258,13 +258,13 @@ int yk_gradient_preview(yk_ctx* c, int pass, int32_t* hostOut, size_t capElems) 
     const size_t nBits = (size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount;
     PPPlanes P; for (int n = 0; n < 3; n++) P.p[n] = c->plane[n];
     P.strideElems = c->strideElems; P.w = w; P.h = h; P.hAvail = h + c->halo;
-    const uint32_t* bm = pass < 7 ? reinterpret_cast<const uint32_t*>(c->bitmap[pass]) : c->ppBitmap;
+    const uint32_t* bm = pass < 7 ? reinterpret_cast<const uint32_t*>(c->bitmap[pass]) : c->img.ppBitmap;
     if (pass < 7 && (c->bitmapBytes[pass] & 3)) YK_HIP(c, hipMemsetAsync(c->bitmap[pass] + c->bitmapBytes[pass], 0, 4 - (c->bitmapBytes[pass] & 3), c->stream));
-    hipLaunchKernelGGL(yk_pp_preview_kernel, dim3((unsigned)((nBits + 255) / 256)), dim3(256), 0, c->stream, P, g, nBits, planeBit, bm, c->preview, planeElems);
+    hipLaunchKernelGGL(yk_pp_preview_kernel, dim3((unsigned)((nBits + 255) / 256)), dim3(256), 0, c->stream, P, g, nBits, planeBit, bm, c->img.preview, planeElems);
     YK_HIP(c, hipGetLastError());
     if (hostOut) {
         if (capElems < 3 * planeElems) return yk_fail(c, YK_ERR_RANGE, "preview buffer too small (3 planes of w*h int32)");
-        YK_HIP(c, hipMemcpyAsync(hostOut, c->preview, 3 * planeElems * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        YK_HIP(c, hipMemcpyAsync(hostOut, c->img.preview, 3 * planeElems * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     }
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
@@ -272,12 +272,12 @@ int yk_gradient_preview(yk_ctx* c, int pass, int32_t* hostOut, size_t capElems) 
 
 int yk_partial_bitmap(yk_ctx* c, uint8_t* hostOut, size_t cap, size_t* nBytes) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!c->ppBitmap) return yk_fail(c, YK_ERR_STATE, "yk_gradient_partial_pass first");
+    if (!c->img.ppBitmap) return yk_fail(c, YK_ERR_STATE, "yk_gradient_partial_pass first");
     if (nBytes) *nBytes = c->ppBitmapBytes;
     if (hostOut) {
         if (cap < c->ppBitmapBytes) return yk_fail(c, YK_ERR_RANGE, "bitmap buffer too small");
         YK_HIP(c, hipSetDevice(c->device));
-        YK_HIP(c, hipMemcpyAsync(hostOut, c->ppBitmap, c->ppBitmapBytes, hipMemcpyDeviceToHost, c->stream));
+        YK_HIP(c, hipMemcpyAsync(hostOut, c->img.ppBitmap, c->ppBitmapBytes, hipMemcpyDeviceToHost, c->stream));
         YK_HIP(c, hipStreamSynchronize(c->stream));
     }
     return YK_OK;
@@ -285,12 +285,12 @@ int yk_partial_bitmap(yk_ctx* c, uint8_t* hostOut, size_t cap, size_t* nBytes) {
 
 int yk_partial_corners(yk_ctx* c, uint8_t* hostOut, size_t cap, size_t* nBytes) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!c->ppStream) return yk_fail(c, YK_ERR_STATE, "yk_gradient_partial_pass first");
+    if (!c->img.ppStream) return yk_fail(c, YK_ERR_STATE, "yk_gradient_partial_pass first");
     if (nBytes) *nBytes = c->ppStreamBytes;
     if (hostOut && c->ppStreamBytes) {
         if (cap < c->ppStreamBytes) return yk_fail(c, YK_ERR_RANGE, "corner buffer too small");
         YK_HIP(c, hipSetDevice(c->device));
-        YK_HIP(c, hipMemcpyAsync(hostOut, c->ppStream, c->ppStreamBytes, hipMemcpyDeviceToHost, c->stream));
+        YK_HIP(c, hipMemcpyAsync(hostOut, c->img.ppStream, c->ppStreamBytes, hipMemcpyDeviceToHost, c->stream));
         YK_HIP(c, hipStreamSynchronize(c->stream));
     }
     return YK_OK;
@@ -302,7 +302,7 @@ int yk_coverage_plane(yk_ctx* c, int plane, uint16_t* hostOut, size_t capElems) 
     const size_t n = (size_t)c->mtW * c->mtH;
     if (capElems < n) return yk_fail(c, YK_ERR_RANGE, "coverage buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
-    const uint16_t* src = c->ppActive ? c->covCh + (size_t)plane * c->covChStride : c->coverage;      // before any partial pass the planes agree
+    const uint16_t* src = c->ppActive ? c->img.covCh + (size_t)plane * c->covChStride : c->coverage;      // before any partial pass the planes agree
     YK_HIP(c, hipMemcpyAsync(hostOut, src, n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;

@@ -224,12 +224,8 @@ int yk_quality_compare(yk_ctx* c, const YkQualitySrc& q, int firstFrame, int nFr
     const unsigned groups = (a.nTiles + YK_Q_TILES - 1) / YK_Q_TILES;
     // the handle's grow-only buffer: the folded u64 results of every frame, then the workgroups' records
     const size_t resBytes = N * YK_Q_REC * sizeof(unsigned long long), need = resBytes + N * groups * YK_Q_REC * sizeof(uint32_t);
-    if (c->qBufBytes < need) {
-        if (c->qBuf) { YK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->qBuf); c->qBuf = nullptr; c->qBufBytes = 0; }
-        YK_HIP(c, hipMalloc(&c->qBuf, need));
-        c->qBufBytes = need;
-    }
-    unsigned long long* res = reinterpret_cast<unsigned long long*>(c->qBuf);
+    YK_HIP(c, c->qBuf.reserve(c->stream, need));
+    unsigned long long* res = reinterpret_cast<unsigned long long*>(c->qBuf.p);
     a.partials = reinterpret_cast<uint32_t*>(c->qBuf + resBytes);
     a.tileMap = devTileSse;
     const int layout = q.planes ? YK_Q_PLANES : q.planeBytes ? YK_Q_CHW : q.srcChannels == 3 ? YK_Q_HWC3 : YK_Q_HWC4;

@@ -389,10 +389,10 @@ __global__ void yk_r1_next_plane_kernel(uint32_t* __restrict__ runBase, const ui
 static int yk_r1_batch_desc(yk_ctx* c, R1Batch& Bt, bool grow) {
     const size_t F = (size_t)c->nFrames, T8 = (size_t)c->tilesW * c->tilesH, nb = (T8 + 1023) / 1024;
     Bt.sOff = (T8 + 3) & ~(size_t)3; Bt.sBlk = (nb + 3) & ~(size_t)3;
-    if (grow) { int rc = yk_sb_grow(c, &c->sb.r1Scratch, &c->sb.r1ScratchElems, (size_t)(Bt.sOff + 2 * Bt.sBlk) * F); if (rc) return rc; }
+    if (grow) YK_HIP(c, c->img.sb.r1Scratch.reserve(c->stream, (size_t)(Bt.sOff + 2 * Bt.sBlk) * F));
     Bt.coverage = c->B.coverage; Bt.sCov = c->fs.coverage; Bt.sPlane = F > 1 ? c->fs.plane : 0;
-    Bt.offInBlk = c->sb.r1Scratch; Bt.blockT = Bt.offInBlk + F * Bt.sOff; Bt.blockP = Bt.blockT + F * Bt.sBlk;
-    Bt.counts = c->sb.counts; Bt.tab = reinterpret_cast<const YkStreamRec*>(c->sb.tab);
+    Bt.offInBlk = c->img.sb.r1Scratch; Bt.blockT = Bt.offInBlk + F * Bt.sOff; Bt.blockP = Bt.blockT + F * Bt.sBlk;
+    Bt.counts = c->img.sb.counts; Bt.tab = c->img.sb.tab;
     return YK_OK;
 }
 
@@ -408,7 +408,7 @@ int yk_range1d_batch_count(yk_ctx* c) {
     return YK_OK;
 }
 
-// emit phase: the coder writes every frame's pixel bytes and parameters straight to the frame's own bases (c->sb.tab, in HBM)
+// emit phase: the coder writes every frame's pixel bytes and parameters straight to the frame's own bases (c->img.sb.tab, in HBM)
 int yk_range1d_batch_emit(yk_ctx* c) {
     R1Batch Bt;
     { int rc = yk_r1_batch_desc(c, Bt, false); if (rc) return rc; }
@@ -427,14 +427,14 @@ int yk_range1d_encode(yk_ctx* c) {
     if (!c->encoded) return yk_fail(c, YK_ERR_STATE, "yk_encode_tiles first (the 1-D path codes what the gradient passes left uncovered)");
     YK_HIP(c, hipSetDevice(c->device));
     const size_t T8 = (size_t)c->tilesW * c->tilesH, nb = (T8 + 1023) / 1024;
-    if (!c->r1Slots) {
-        YK_HIP(c, hipMalloc(&c->r1Slots, 3 * T8 * 64));
-        YK_HIP(c, hipMalloc(&c->r1Params, 3 * T8 * 4));
-        YK_HIP(c, hipMalloc(&c->r1Cnt, (2 * T8 + 2 * nb + 64) * sizeof(uint32_t)));
-        YK_HIP(c, hipMalloc(&c->r1Pix, 3 * T8 * 64 + 64));
-        YK_HIP(c, hipMalloc(&c->r1Type, 3 * T8 * 3 + 64));
+    if (!c->img.r1Slots) {
+        YK_HIP(c, c->img.r1Slots.alloc(c->stream, 3 * T8 * 64));
+        YK_HIP(c, c->img.r1Params.alloc(c->stream, 3 * T8 * 4));
+        YK_HIP(c, c->img.r1Cnt.alloc(c->stream, 2 * T8 + 2 * nb + 64));
+        YK_HIP(c, c->img.r1Pix.alloc(c->stream, 3 * T8 * 64 + 64));
+        YK_HIP(c, c->img.r1Type.alloc(c->stream, 3 * T8 * 3 + 64));
     }
-    uint32_t* cT = c->r1Cnt; uint32_t* cP = cT + T8; uint32_t* bT = cP + T8; uint32_t* bP = bT + nb + 16; uint32_t* tot = bP + nb + 16;
+    uint32_t* cT = c->img.r1Cnt; uint32_t* cP = cT + T8; uint32_t* bT = cP + T8; uint32_t* bP = bT + nb + 16; uint32_t* tot = bP + nb + 16;
     const unsigned nStrips = (unsigned)(((c->fullW + 63) / 64) * ((c->h + 15) / 16));
     uint32_t t[2];
     if (!c->ppActive) {
@@ -445,8 +445,8 @@ int yk_range1d_encode(yk_ctx* c) {
         hipLaunchKernelGGL(yk_r1_scan_kernel, dim3(1), dim3(1024), 0, c->stream, bT, bP, (int)nb, tot);
         { int rc = yk_stage_end(c, YK_STAGE_RANGE1D_PACK); if (rc) return rc; }
         { int rc = yk_stage_begin(c, YK_STAGE_RANGE1D); if (rc) return rc; }
-        R1Direct D; D.offInBlk = cT; D.blockT = bT; D.blockP = bP; D.totals = tot; D.pixOut = c->r1Pix; D.typeOut = c->r1Type; D.pixCache = c->pixCache;
-        if (c->pixCacheValid && c->pixCache)                                  // the fused kernel left the uncovered cells' pixels: 4 B per pixel instead of 12
+        R1Direct D; D.offInBlk = cT; D.blockT = bT; D.blockP = bP; D.totals = tot; D.pixOut = c->img.r1Pix; D.typeOut = c->img.r1Type; D.pixCache = c->img.pixCache;
+        if (c->pixCacheValid && c->img.pixCache)                                  // the fused kernel left the uncovered cells' pixels: 4 B per pixel instead of 12
             hipLaunchKernelGGL((yk_range1d_kernel<true, true>), dim3(nStrips), dim3(64), 0, c->stream, c->plane[0], c->plane[1], c->plane[2], c->strideElems,
                                c->fullW, c->h, c->coverage, c->mtW, c->tilesW, T8, (uint8_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, -1, D);
         else
@@ -463,12 +463,12 @@ int yk_range1d_encode(yk_ctx* c) {
         YK_HIP(c, hipMemsetAsync(runBase, 0, 2 * sizeof(uint32_t), c->stream));
         for (int p = 0; p < 3; p++, runBase += 2) {
             hipLaunchKernelGGL(yk_range1d_kernel<false>, dim3(nStrips), dim3(64), 0, c->stream, c->plane[0], c->plane[1], c->plane[2], c->strideElems,
-                               c->fullW, c->h, c->covCh + (size_t)p * c->covChStride, c->mtW, c->tilesW, T8, c->r1Slots, c->r1Params, cT, cP, p, R1Direct{});
+                               c->fullW, c->h, c->img.covCh + (size_t)p * c->covChStride, c->mtW, c->tilesW, T8, c->img.r1Slots, c->img.r1Params, cT, cP, p, R1Direct{});
             hipLaunchKernelGGL(yk_u32_blocksum_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, cT, T8, bT);
             hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, bT, (int)nb, tot);
             hipLaunchKernelGGL(yk_u32_blocksum_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, cP, T8, bP);
             hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, bP, (int)nb, tot + 1);
-            hipLaunchKernelGGL(yk_range1d_pack_kernel, dim3((unsigned)nb, 1), dim3(1024), 0, c->stream, cT, cP, bT, bP, tot, T8, c->r1Slots, c->r1Params, c->r1Pix, c->r1Type,
+            hipLaunchKernelGGL(yk_range1d_pack_kernel, dim3((unsigned)nb, 1), dim3(1024), 0, c->stream, cT, cP, bT, bP, tot, T8, c->img.r1Slots, c->img.r1Params, c->img.r1Pix, c->img.r1Type,
                                p, (const uint32_t*)runBase);
             hipLaunchKernelGGL(yk_r1_next_plane_kernel, dim3(1), dim3(64), 0, c->stream, runBase, (const uint32_t*)tot);
         }
@@ -506,7 +506,7 @@ int yk_range1d_streams_device(yk_ctx* c, const uint8_t** devPix, size_t* nPix, c
     if (!c || !devPix || !nPix || !devType || !nType) return YK_ERR_BAD_ARG;
     if (!c->r1Ready) return yk_fail(c, YK_ERR_STATE, "yk_range1d_encode first");
     { int rc = yk_range1d_finish(c); if (rc) return rc; }
-    *devPix = c->r1Pix; *nPix = (size_t)c->r1PixCount; *devType = c->r1Type; *nType = (size_t)c->r1Tiles * 3;
+    *devPix = c->img.r1Pix; *nPix = (size_t)c->r1PixCount; *devType = c->img.r1Type; *nType = (size_t)c->r1Tiles * 3;
     return YK_OK;
 }
 
@@ -518,8 +518,8 @@ int yk_range1d_streams(yk_ctx* c, uint8_t* hostPix, size_t capPix, size_t* nPix,
     if (nPix) *nPix = np;
     if (nType) *nType = nt;
     YK_HIP(c, hipSetDevice(c->device));
-    if (hostPix) { if (capPix < np) return yk_fail(c, YK_ERR_RANGE, "pixel stream buffer too small"); if (np) YK_HIP(c, hipMemcpyAsync(hostPix, c->r1Pix, np, hipMemcpyDeviceToHost, c->stream)); }
-    if (hostType) { if (capType < nt) return yk_fail(c, YK_ERR_RANGE, "type stream buffer too small"); if (nt) YK_HIP(c, hipMemcpyAsync(hostType, c->r1Type, nt, hipMemcpyDeviceToHost, c->stream)); }
+    if (hostPix) { if (capPix < np) return yk_fail(c, YK_ERR_RANGE, "pixel stream buffer too small"); if (np) YK_HIP(c, hipMemcpyAsync(hostPix, c->img.r1Pix, np, hipMemcpyDeviceToHost, c->stream)); }
+    if (hostType) { if (capType < nt) return yk_fail(c, YK_ERR_RANGE, "type stream buffer too small"); if (nt) YK_HIP(c, hipMemcpyAsync(hostType, c->img.r1Type, nt, hipMemcpyDeviceToHost, c->stream)); }
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }

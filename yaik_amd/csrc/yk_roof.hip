@@ -52,16 +52,16 @@ extern "C" int yk_measure_roof(yk_ctx* c, size_t bytes, int reps, double* copyGB
     if (!c || bytes < (1u << 20) || reps < 1 || reps > 100) return c ? yk_fail(c, YK_ERR_BAD_ARG, "yk_measure_roof arguments") : YK_ERR_BAD_ARG;
     YK_HIP(c, hipSetDevice(c->device));
     bytes &= ~(size_t)4095;
-    yk_v4u* a = nullptr; yk_v4u* b = nullptr; uint32_t* sink = nullptr;
+    YkBuf<yk_v4u> a, b; YkBuf<uint32_t> sink;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = YK_OK;
     const size_t n16 = bytes / 16;
     const int grid = c->numCU * 8;                                           // 2048 workgroups of 4 waves: two rounds of full occupancy per sweep step
     auto fail = [&](const char* what, hipError_t e) { rc = yk_fail(c, YK_ERR_HIP, what, e); };
     hipError_t e;
-    if ((e = hipMalloc(&a, bytes)) != hipSuccess) fail("hipMalloc roof src", e);
-    if (!rc && (e = hipMalloc(&b, bytes)) != hipSuccess) fail("hipMalloc roof dst", e);
-    if (!rc && (e = hipMalloc(&sink, (size_t)grid * YK_ROOF_THREADS * 4)) != hipSuccess) fail("hipMalloc roof sink", e);
+    if ((e = a.alloc(c->stream, n16)) != hipSuccess) fail("hipMalloc roof src", e);
+    if (!rc && (e = b.alloc(c->stream, n16)) != hipSuccess) fail("hipMalloc roof dst", e);
+    if (!rc && (e = sink.alloc(c->stream, (size_t)grid * YK_ROOF_THREADS)) != hipSuccess) fail("hipMalloc roof sink", e);
     if (!rc && (e = hipEventCreate(&e0)) != hipSuccess) fail("hipEventCreate", e);
     if (!rc && (e = hipEventCreate(&e1)) != hipSuccess) fail("hipEventCreate", e);
     if (!rc && (e = hipMemsetAsync(a, 0x5A, bytes, c->stream)) != hipSuccess) fail("hipMemsetAsync", e);
@@ -83,9 +83,6 @@ extern "C" int yk_measure_roof(yk_ctx* c, size_t bytes, int reps, double* copyGB
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-    if (sink) (void)hipFree(sink);
     if (rc) return rc;
     if (copyGBs) *copyGBs = bestCopy;
     if (readGBs) *readGBs = bestRead;

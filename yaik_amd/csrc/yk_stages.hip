@@ -375,7 +375,7 @@ int yk_launch_alpha(yk_ctx* c, bool batch) {
     const long long nUnits = (long long)nSeg * ((c->mtH + YK_ALPHA_ROWS - 1) / YK_ALPHA_ROWS) * F;
     const long long maxWG = 4096LL * (256 / YK_ALPHA_THREADS);
     hipLaunchKernelGGL(yk_alpha_kernel, dim3((unsigned)(nUnits < maxWG ? nUnits : maxWG)), dim3(YK_ALPHA_THREADS), 0, c->stream, alpha, c->strideElems, c->fullW, c->h, c->y0,
-                       keep, c->mtW, c->mtH, bounds, F, (unsigned long long)c->fs.plane, (unsigned long long)c->fs.keep, c->alphaUnitBox, c->alphaArrive);
+                       keep, c->mtW, c->mtH, bounds, F, (unsigned long long)c->fs.plane, (unsigned long long)c->fs.keep, c->img.alphaUnitBox, c->img.alphaArrive);
     YK_HIP(c, hipGetLastError());
     c->boundsOff = 8;                                           // whole image / batch: the accumulators are the box; a stripe caller replaces it (yk_alpha_finish)
     return YK_OK;
@@ -403,7 +403,7 @@ int yk_launch_encode(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst,
     P.coverage = batch ? c->B.coverage : c->coverage; P.tileDef = batch ? c->B.tileDef : c->tileDef;
     P.tileCount = batch ? c->B.tileCount : c->tileCount; P.slots = batch ? c->B.slots : c->slots;
     P.blockCnt = c->kernelVersion == 2 ? (batch ? c->B.blockCnt : c->blockCnt) : nullptr;
-    for (int i = 0; i < 3; i++) P.dst[i] = c->dst[i];
+    for (int i = 0; i < 3; i++) P.dst[i] = c->img.dst[i];
     P.tilesW = c->tilesW; P.tilesH = c->tilesH; P.mtW = c->mtW; P.mtH = c->mtH;
     P.xBB64 = (c->fullW + 63) / 64; P.yBB64 = (c->h + 63) / 64; P.xBB32 = (c->fullW + 31) / 32; P.yBB32 = (c->h + 31) / 32;
     P.nFrames = batch ? c->nFrames : 1; P.fs = c->fs;
@@ -419,8 +419,8 @@ int yk_launch_encode(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst,
     }
     P.pixCache = nullptr; c->pixCacheValid = false;
     if (c->pixCacheOn && !batch && c->kernelVersion == 2 && c->nFrames == 1) {
-        if (!c->pixCache) YK_HIP(c, hipMalloc(&c->pixCache, (size_t)P.xBB64 * 64 * ((size_t)(c->h + 15) / 16 * 16) * 4 + 4096));
-        P.pixCache = c->pixCache; c->pixCacheValid = true;
+        if (!c->img.pixCache) YK_HIP(c, c->img.pixCache.alloc(c->stream, (size_t)P.xBB64 * 64 * ((size_t)(c->h + 15) / 16 * 16) / 4, 4096));
+        P.pixCache = c->img.pixCache; c->pixCacheValid = true;
     }
     if (c->kernelVersion == 2) return yk_launch_encode2(c, P);
     // version 1 = the cross-check implementation of the test suite (tests/csrc/yk_encode_v1.hip), registered at run time
@@ -511,18 +511,17 @@ __global__ void yk_selftest_r1magic_kernel(int* mismatches) {
 extern "C" int yk_selftest(yk_ctx* c, int which, int* result) {
     if (!c || !result) return YK_ERR_BAD_ARG;
     YK_HIP(c, hipSetDevice(c->device));
-    int* d = nullptr;
-    YK_HIP(c, hipMalloc(&d, sizeof(int)));
+    YkBuf<int> d;
+    YK_HIP(c, d.alloc(c->stream, 1));
     YK_HIP(c, hipMemsetAsync(d, 0, sizeof(int), c->stream));
     if (which == 0) hipLaunchKernelGGL(yk_selftest_div_kernel, dim3(256), dim3(256), 0, c->stream, d);
     else if (which == 1) hipLaunchKernelGGL(yk_selftest_scale_kernel, dim3(256), dim3(256), 0, c->stream, d);
     else if (which == 2) hipLaunchKernelGGL(yk_selftest_r1div_kernel, dim3(256), dim3(256), 0, c->stream, d);
     else if (which == 3) yk_selftest_qtab_launch(c, d);
     else if (which == 4) hipLaunchKernelGGL(yk_selftest_r1magic_kernel, dim3(256), dim3(256), 0, c->stream, d);
-    else { (void)hipFree(d); return yk_fail(c, YK_ERR_BAD_ARG, "unknown selftest"); }
+    else return yk_fail(c, YK_ERR_BAD_ARG, "unknown selftest");
     YK_HIP(c, hipMemcpyAsync(result, d, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(d);
     return YK_OK;
 }
 #endif

@@ -8,23 +8,6 @@
 //   emit:   corner emit kernel, 1-D coder; every workgroup reads its frame's record
 #include "yk_common.h"
 
-int yk_sb_grow_bytes(yk_ctx* c, void** p, size_t* cap, size_t need) {
-    if (*cap >= need && *p) return YK_OK;
-    if (*p) { YK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    if (!need) need = 16;
-    YK_HIP(c, hipMalloc(p, need));
-    *cap = need;
-    return YK_OK;
-}
-
-void yk_sb_free(yk_ctx* c) {
-    YkStreamsBatch& b = c->sb;
-    auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
-    F(b.owner); F(b.cScratch); F(b.r1Scratch); F(b.counts); F(b.out); F(b.tab);
-    b.ownerElems = b.cScratchElems = b.r1ScratchElems = b.countsElems = 0; b.outCap = b.tabCap = 0;
-    b.table.clear(); b.valid = false;
-}
-
 extern "C" {
 
 int yk_encode_streams_batch(yk_ctx* c, int what) {
@@ -37,10 +20,10 @@ int yk_encode_streams_batch(yk_ctx* c, int what) {
     YK_HIP(c, hipSetDevice(c->device));
     const int N = c->nFrames;
     const bool corners = (what & YK_STREAMS_CORNERS) != 0, r1 = (what & YK_STREAMS_RANGE1D) != 0;
-    YkStreamsBatch& b = c->sb;
+    YkStreamsBatch& b = c->img.sb;
     b.valid = false; c->pal.valid = false;
-    { int rc = yk_sb_grow(c, &b.counts, &b.countsElems, (size_t)N * YK_SB_COUNTS); if (rc) return rc; }
-    { void* p = b.tab; int rc = yk_sb_grow_bytes(c, &p, &b.tabCap, (size_t)N * sizeof(YkStreamRec)); b.tab = static_cast<uint8_t*>(p); if (rc) return rc; }
+    YK_HIP(c, b.counts.reserve(c->stream, (size_t)N * YK_SB_COUNTS));
+    YK_HIP(c, b.tab.reserve(c->stream, (size_t)N));
     // ---- count phase ----
     if (r1) {
         { int rc = yk_stage_begin(c, YK_STAGE_RANGE1D_PACK); if (rc) return rc; }
@@ -74,7 +57,7 @@ int yk_encode_streams_batch(yk_ctx* c, int what) {
         if (t.pixBytes) offs[(size_t)f * 9 + 7] = place(t.pixBytes);
         if (t.typeBytes) offs[(size_t)f * 9 + 8] = place(t.typeBytes);
     }
-    { void* p = b.out; int rc = yk_sb_grow_bytes(c, &p, &b.outCap, total + 64); b.out = static_cast<uint8_t*>(p); if (rc) return rc; }
+    YK_HIP(c, b.out.reserve(c->stream, total + 64));
     int slot; void* host;
     { const int rc = yk_dec_table_host(c, (size_t)N * sizeof(YkStreamRec), &slot, &host); if (rc) return rc; }
     YkStreamRec* rec = static_cast<YkStreamRec*>(host);
@@ -103,8 +86,8 @@ int yk_encode_streams_batch(yk_ctx* c, int what) {
 int yk_batch_streams_table(yk_ctx* c, yk_frame_streams* out) {
     if (!c) return YK_ERR_BAD_ARG;
     if (!out) return yk_refuse(c, YK_ERR_BAD_ARG, "out is NULL");
-    if (!c->sb.valid || (int)c->sb.table.size() != c->nFrames) return yk_refuse(c, YK_ERR_STATE, "yk_encode_streams_batch first (the table does not outlive an encode, a new image or new planes)");
-    for (int f = 0; f < c->nFrames; f++) out[f] = c->sb.table[(size_t)f];
+    if (!c->img.sb.valid || (int)c->img.sb.table.size() != c->nFrames) return yk_refuse(c, YK_ERR_STATE, "yk_encode_streams_batch first (the table does not outlive an encode, a new image or new planes)");
+    for (int f = 0; f < c->nFrames; f++) out[f] = c->img.sb.table[(size_t)f];
     return YK_OK;
 }
 
