@@ -66,12 +66,7 @@ static int yk_alloc_image_run(yk_ctx* c) {
     fs.keep = up(MT + 4, 16);                                   // read as 4-byte words by yk_alpha_bbox_kernel
     YK_HIP(c, M.keep.alloc(s, fs.keep * F, 16));
     YK_HIP(c, M.bounds.alloc(s, 16 * F));
-    {
-        const size_t nUnits = (size_t)((c->fullW / 4 + 63) / 64) * c->mtH, nGroups = (nUnits + 63) / 64;     // sized for the smallest unit yk_alpha_kernel may use (64 int4 per segment)
-        YK_HIP(c, M.alphaUnitBox.alloc(s, (nUnits + nGroups) * F * 4, 16));
-        YK_HIP(c, M.alphaArrive.alloc(s, (nGroups + 1) * F, 16));
-        YK_HIP(c, hipMemset(M.alphaArrive, 0, (nGroups + 1) * F * sizeof(uint32_t) + 16));
-    }
+    YK_HIP(c, M.alphaUnitBox.alloc(s, yk_alpha_units(c->fullW, c->mtH) * F * 4, 16));   // every slot is written by every launch of yk_alpha_kernel
     static const int sh[7][2] = { {4,4},{4,3},{3,4},{3,3},{3,2},{2,3},{2,2} };
     size_t cur = 0, oBm[7], oBm0b, oCov, oInfo, oRun;
     auto place = [&](size_t bytesPerFrame) { const size_t o = cur; cur = up(cur + bytesPerFrame * F + 16, 256); return o; };

@@ -138,14 +138,19 @@ struct YkPaletteDec {
     int nSeg = 0; bool valid = false;
 };
 
+// yk_alpha_kernel's work unit: YK_ALPHA_R rows of 16x16 tiles of one 256-pixel segment (one wave).  Every unit intersects the image.
+#ifndef YK_ALPHA_R
+#define YK_ALPHA_R 4
+#endif
+static inline size_t yk_alpha_units(int fullW, int mtH) { return (size_t)((fullW / 4 + 63) / 64) * (size_t)((mtH + YK_ALPHA_R - 1) / YK_ALPHA_R); }
+
 // Everything that is allocated for one image shape and frame count (yk_set_image, yk_set_batch) or grows with the work done on it, and goes
 // when the shape changes: released as a whole (yk_free_image).  The pointers the kernels are given -- the frame-0 bases B, the working
 // pointers of yk_rebase, the pieces of `small` -- are views into these.
 struct YkImageBufs {
     // alpha
     YkBuf<uint8_t> keep; YkBuf<int32_t> bounds;
-    YkBuf<int> alphaUnitBox;            // yk_alpha_kernel: one box {x0, y0, x1, y1} per work unit (tile row x 1024-pixel segment) and frame
-    YkBuf<uint32_t> alphaArrive;        // its arrival counters: per group of 64 units + one per frame (zero between launches)
+    YkBuf<int> alphaUnitBox;            // yk_alpha_kernel: one box {x0, y0, x1, y1} per work unit (yk_alpha_units) and frame, folded by yk_alpha_box_kernel
     // encode outputs and compaction
     YkBuf<uint8_t> small;               // one allocation: bitmap[0..6], bm0b, coverage, tileInfo, runSums (each nFrames times)
     YkBuf<uint16_t> tileDef; YkBuf<uint8_t> tileCount, slots;
@@ -196,7 +201,7 @@ struct yk_ctx {
     hipEvent_t evPixCopy = nullptr;                         // ... recorded behind that copy: the call returns once the host rows are read
     // alpha
     uint8_t* keep = nullptr;            // mtW*mtH
-    int32_t* bounds = nullptr;          // 16 ints: [0..4] the host-combined box of a striped image + its discard flag (yk_alpha_finish), [8..11] the box yk_alpha_kernel accumulates
+    int32_t* bounds = nullptr;          // 16 ints: [0..4] the host-combined box of a striped image + its discard flag (yk_alpha_finish), [8..11] the box yk_alpha_box_kernel folds from the units of yk_alpha_kernel
     int boundsOff = 8;                  // where the image-wide box is: 8 (whole image, batch) or 0 (stripes, after yk_alpha_finish)
     bool alphaDone = false, alphaFinished = false;
     int32_t hostBounds[4] = {0, 0, 0, 0}; int hostDiscard = 1, hostHasChunk = 0;

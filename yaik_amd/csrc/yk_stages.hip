@@ -17,169 +17,146 @@
 // a9: alpha tile-reject.  keep[mt] = 1 iff any of the 256 alphas of the aligned 16x16 block is non-zero (closed form of
 // quadRecursion with maxMipLevel 3, EncoderContext.cpp:394-423); kept blocks grow the bounding box (boundingL/T/R/B, :416-422).
 //
-// ONE kernel (round 3: a clear of the flag map, a flagging kernel over single image rows with idempotent byte stores, and a
-// bounding-box kernel over the flags -- three stream operations in every frame's chain of short kernels).  A work unit is
-// (YK_ALPHA_ROWS rows of 16x16 tiles, 1024-pixel segment): the workgroup owns its tiles, so it writes their flags outright (nothing
-// to clear) and knows their box.  The plane is read with 16-byte loads, a wave instruction covering 1 KB of one row; four adjacent
-// lanes hold the 16 columns of one tile.  One non-zero sample decides a tile, so a unit reads in two steps: every lane PROBES the
-// first and the last row of each of its tiles (all probe loads of the unit in flight together, addresses clamped, no branch), one
-// ballot per row of tiles gives the tiles already known to be kept, and only the lanes of tiles still undecided read the 14 rows
-// in between, all of them in flight before one wait.  A wave without an undecided tile issues nothing of the second step.  HBM serves 128-byte
-// requests = the lanes of two adjacent tiles: an opaque region costs 2 of its 16 rows, a transparent one all 16 (as before).  The
-// first and the last row are the two that the partly covered tiles along the top and the bottom of an opaque shape have in common with it
-// (tiles along its sides are non-zero in every row); only a blob strictly inside a tile's rows 1..14 needs the second step to be kept.
-// The image-wide box WITHOUT atomics on its four words (every form of guarded atomicMin / atomicMax on them, dealt from the image's
-// outside inwards or not, cost 23-85 us: a single address sustains ~88 atomics per microsecond, coherent guard reads are served by
-// the same L2 channel one after the other): every unit leaves its box in a slot of its own (write-through store), arrivals are
-// counted per group of 64 units and then per frame (<= 64 atomics per address), and the workgroup that arrives last folds the
-// slots into bounds[8..11] = {min x0, min y0, max x1, max y1} ({9999999, 9999999, -1, -1} when nothing is kept).
+// Two kernels: yk_alpha_kernel decides the tiles, yk_alpha_box_kernel folds the image-wide box.  A work unit of yk_alpha_kernel is
+// (YK_ALPHA_R rows of 16x16 tiles, 256-pixel segment) and belongs to ONE wave: the wave owns its tiles, so it writes their flags outright
+// (nothing to clear) and knows their box.  The plane is read with 16-byte loads, a wave instruction covering 1 KB of one row; four adjacent
+// lanes hold the 16 columns of one tile, a wave 16 tiles across.  One non-zero sample decides a tile, so a unit reads in two steps: every
+// lane PROBES the first and the last row of each of its tiles (all 2 * YK_ALPHA_R probe loads of the unit in flight together, addresses
+// clamped, no branch), one ballot per row of tiles gives the tiles already known to be kept, and only the lanes of tiles still undecided
+// read the 14 rows in between: the rows of tiles that still hold an undecided tile are taken two at a time, 28 loads in flight before one
+// wait.  A wave without an undecided tile issues nothing of the second step.  HBM serves 128-byte requests = the lanes of two adjacent
+// tiles: an opaque region costs 2 of its 16 rows, a transparent one all 16.  The first and the last row are the two that the partly covered
+// tiles along the top and the bottom of an opaque shape have in common with it (tiles along its sides are non-zero in every row); only a
+// blob strictly inside a tile's rows 1..14 needs the second step to be kept.
+// A wave only streams: it takes part in no protocol (no atomics, no wait for a store's acknowledgement, no barrier, no LDS) and ends after
+// one to 1 + YK_ALPHA_R / 2 round trips.  The waves of a workgroup share nothing; how many there are decides WHEN the kernel runs beside
+// the other frame's fused kernel (one-wave workgroups, 128 VGPRs, 4 waves per SIMD), because a workgroup starts once that many slots are
+// free on one compute unit.  One-wave workgroups get every slot that kernel frees: they finish 130-160 us before it and lengthen it by
+// 22 us for 11 us less gap behind it.  Two waves: 44 us before its end, +18 us.  Four or eight wait until it drains and end 23 us after it.
+// Three do a part of the work under it (+3 us) and end 13 us after it: the shortest frame of what was measured (DESIGN 3.1,
+// profiles/alpha_stream/variants.txt).
+// The image-wide box: every unit leaves its box {x0, y0, x1, y1} ({9999999, 9999999, -1, -1} when it keeps nothing) in a slot of its own
+// with a plain store -- every slot is rewritten by every launch, nothing is cleared between frames, every unit intersects the image -- and
+// yk_alpha_box_kernel, one workgroup per frame right behind it on the stream, folds the slots into bounds[8..11] (stream order publishes them).
 // ------------------------------------------------------------------------------------------------------------------
 typedef int yk_i4 __attribute__((ext_vector_type(4)));
-#ifndef YK_ALPHA_THREADS
-#define YK_ALPHA_THREADS 256                                                 // 256: a unit = 1024 pixels x 16 rows (four waves); 64: 256 pixels x 16 rows (one wave per workgroup)
+#ifndef YK_ALPHA_WAVES
+#define YK_ALPHA_WAVES 3                                          // waves = units per workgroup; 1, 2, 3, 4 and 8 were measured
 #endif
-#define YK_ALPHA_WAVES (YK_ALPHA_THREADS / 64)
-#ifndef YK_ALPHA_ROWS
-#define YK_ALPHA_ROWS 2                                                      // rows of 16x16 tiles per unit
-#endif
-__global__ __launch_bounds__(YK_ALPHA_THREADS) void yk_alpha_kernel(const int32_t* __restrict__ alpha0, int strideElems, int w, int h, int y0,
-                                                       uint8_t* __restrict__ keep0, int mtW, int mtH, int32_t* __restrict__ bounds,
-                                                       int nFrames, unsigned long long planeStride, unsigned long long keepStride,
-                                                       int* __restrict__ unitBox0, uint32_t* __restrict__ arrive0) {
-    __shared__ int s_box[YK_ALPHA_WAVES][4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+__global__ __launch_bounds__(64 * YK_ALPHA_WAVES, 4) void yk_alpha_kernel(const int32_t* __restrict__ alpha0, int strideElems, int w, int h, int y0,
+                                                      uint8_t* __restrict__ keep0, int mtW, int mtH, unsigned long long planeStride,
+                                                      unsigned long long keepStride, yk_i4* __restrict__ unitBox0, unsigned total) {
+    const int lane = threadIdx.x & 63;
     const int vecPerRow = w >> 2;                                // int4 per image row (w is a multiple of 8)
-    const int nSeg = (vecPerRow + YK_ALPHA_THREADS - 1) / YK_ALPHA_THREADS;   // YK_ALPHA_THREADS int4 per segment
-    // a unit = YK_ALPHA_ROWS rows of tiles of one segment: the arrival protocol at its end (3-5 us in which the first wave keeps a slot of its SIMD)
-    // is paid once per 2 x 16 rows, and the 2048 units of an 8192 x 8192 frame are exactly one round of resident workgroups
-    const int nRowUnits = (mtH + YK_ALPHA_ROWS - 1) / YK_ALPHA_ROWS;
-    const int nUnits = nSeg * nRowUnits, nGroups = (nUnits + 63) >> 6;
-    for (long long uu = blockIdx.x; uu < (long long)nUnits * nFrames; uu += gridDim.x) {
-        const int f = (int)(uu / nUnits), u = (int)(uu - (long long)f * nUnits);
-        const int32_t* alpha = alpha0 + (size_t)f * planeStride;
-        uint8_t* keep = keep0 + (size_t)f * keepStride;
-        int* unitBox = unitBox0 + (size_t)f * (nUnits + nGroups) * 4;
-        uint32_t* arrive = arrive0 + (size_t)f * (nGroups + 1);
-        const int tyU = u / nSeg, seg = u - tyU * nSeg;
-        const int xv = seg * YK_ALPHA_THREADS + (int)threadIdx.x;
-        const bool inX = xv < vecPerRow;
-        const bool tileLane = (lane & 3) == 0;
-        const int tx = xv >> 2;
-        int colLo = 0x7FFFFFFF, colHi = -1, rowLo = 0x7FFFFFFF, rowHi = -1;      // wave-uniform: kept tile columns / rows of this wave's share of the unit
-        // ---- probe: rows 0 and 15 of every tile of the unit.  Addresses are clamped (column into the row, row 15 onto the image's last row) and
-        // every lane loads: no load sits in a branch, all YK_ALPHA_ROWS * 2 are in flight together; what a clamped lane read is masked afterwards.
-        const int xvc = min(xv, vecPerRow - 1);
-        int nzR[YK_ALPHA_ROWS];
-        bool und[YK_ALPHA_ROWS];
-        {
-            yk_i4 p[YK_ALPHA_ROWS][2];
+    const int nSeg = (vecPerRow + 63) >> 6;                      // 64 int4 = 16 tiles per segment
+    const int nUnits = nSeg * ((mtH + YK_ALPHA_R - 1) / YK_ALPHA_R);
+    const unsigned uu = blockIdx.x * YK_ALPHA_WAVES + (threadIdx.x >> 6);        // wave = unit; units x frames in all
+    if (uu >= total) return;
+    const int f = (int)(uu / (unsigned)nUnits), u = (int)(uu - (unsigned)f * (unsigned)nUnits);
+    const int32_t* alpha = alpha0 + (size_t)f * planeStride;
+    uint8_t* keep = keep0 + (size_t)f * keepStride;
+    const int tyU = u / nSeg, seg = u - tyU * nSeg, ty0 = tyU * YK_ALPHA_R;
+    const int xv = seg * 64 + lane;
+    const bool inX = xv < vecPerRow;
+    const bool tileLane = (lane & 3) == 0;
+    const int tx = xv >> 2;
+    // ---- probe: rows 0 and 15 of every tile of the unit.  Addresses are clamped (column into the row, rows onto the image's last row) and
+    // every lane loads: no load sits in a branch, all YK_ALPHA_R * 2 are in flight together; what a clamped lane read is masked afterwards.
+    const int xvc = min(xv, vecPerRow - 1);
+    uint32_t nzBits = 0, undBits = 0, rowsLeft = 0;              // bit r = row r of the unit's tiles: lane saw a sample / lane's tile undecided / (wave-uniform) some tile undecided
+    {
+        yk_i4 p[YK_ALPHA_R][2];
 #pragma unroll
-            for (int r = 0; r < YK_ALPHA_ROWS; r++) {
-                const int yA = min((tyU * YK_ALPHA_ROWS + r) * 16, h - 1), yB = min(yA + 15, h - 1);
-                p[r][0] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(alpha + (size_t)yA * strideElems + (size_t)xvc * 4));
-                p[r][1] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(alpha + (size_t)yB * strideElems + (size_t)xvc * 4));
-            }
-            bool anyUnd = false;
+        for (int r = 0; r < YK_ALPHA_R; r++) {
+            const int yA = min((ty0 + r) * 16, h - 1), yB = min(yA + 15, h - 1);
+            p[r][0] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(alpha + (size_t)yA * strideElems + (size_t)xvc * 4));
+            p[r][1] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(alpha + (size_t)yB * strideElems + (size_t)xvc * 4));
+        }
 #pragma unroll
-            for (int r = 0; r < YK_ALPHA_ROWS; r++) {
-                const bool on = inX && (tyU * YK_ALPHA_ROWS + r) * 16 < h;      // the lane's 4 columns and the tile's first row are inside the image
-                const yk_i4 o = p[r][0] | p[r][1];
-                nzR[r] = on ? (o.x | o.y | o.z | o.w) : 0;
-                const unsigned long long pb = __ballot(nzR[r] != 0);
-                und[r] = on && ((pb >> (lane & ~3)) & 0xFULL) == 0;              // nothing seen in the tile's probed rows: rows 1..14 decide
-                anyUnd |= und[r];
-            }
-            // ---- the rows in between, for undecided tiles only.  One wave-uniform region around all of it (a wave of decided tiles issues none of
-            // these instructions); inside, the YK_ALPHA_ROWS * 14 loads are issued under the lanes' masks and waited for once (128 VGPRs, as many
-            // waves per SIMD as the 116 of the kernel that read 16 rows per tile).
-            if (__ballot(anyUnd) != 0) {
-                yk_i4 a[YK_ALPHA_ROWS][14];
+        for (int r = 0; r < YK_ALPHA_R; r++) {
+            const bool on = inX && (ty0 + r) * 16 < h;          // the lane's 4 columns and the tile's first row are inside the image
+            const yk_i4 o = p[r][0] | p[r][1];
+            const bool nz = ((o.x | o.y | o.z | o.w) != 0) & on;              // bitwise: the loads stay in front of every branch
+            const unsigned long long pb = __ballot(nz);
+            const bool und = on && ((pb >> (lane & ~3)) & 0xFULL) == 0;          // nothing seen in the tile's probed rows: rows 1..14 decide
+            nzBits |= (nz ? 1u : 0u) << r; undBits |= (und ? 1u : 0u) << r;
+            if (__ballot(und) != 0) rowsLeft |= 1u << r;
+        }
+    }
+    // ---- the rows in between, for undecided tiles only, two rows of tiles at a time (the rows of tiles without an undecided tile are skipped:
+    // a wave of decided tiles issues none of these instructions).  The 2 x 14 loads are issued under the lanes' masks and waited for once.
+    while (rowsLeft) {
+        const int rA = __ffs((int)rowsLeft) - 1; rowsLeft &= rowsLeft - 1;
+        const bool two = rowsLeft != 0;
+        const int rB = two ? __ffs((int)rowsLeft) - 1 : rA; rowsLeft &= rowsLeft - 1;
+        yk_i4 a[2][14];
 #pragma unroll
-                for (int r = 0; r < YK_ALPHA_ROWS; r++) {
-                    const int ty = tyU * YK_ALPHA_ROWS + r;
-                    const int32_t* col = alpha + (size_t)(ty * 16) * strideElems + (size_t)xv * 4;
+        for (int j = 0; j < 2; j++) {
+            const int r = j ? rB : rA, ty = ty0 + r;
+            const bool und = (j == 0 || two) && ((undBits >> r) & 1u) != 0;
+            const int32_t* col = alpha + (size_t)(ty * 16) * strideElems + (size_t)xv * 4;
 #pragma unroll
-                    for (int k = 0; k < 14; k++) {
-                        a[r][k] = (yk_i4){0, 0, 0, 0};
-                        if (und[r] && ty * 16 + 1 + k < h) a[r][k] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(col + (size_t)(1 + k) * strideElems));
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < YK_ALPHA_ROWS; r++)
-#pragma unroll
-                    for (int k = 0; k < 14; k++) nzR[r] |= a[r][k].x | a[r][k].y | a[r][k].z | a[r][k].w;
+            for (int k = 0; k < 14; k++) {
+                a[j][k] = (yk_i4){0, 0, 0, 0};
+                if (und && ty * 16 + 1 + k < h) a[j][k] = __builtin_nontemporal_load(reinterpret_cast<const yk_i4*>(col + (size_t)(1 + k) * strideElems));
             }
         }
 #pragma unroll
-        for (int r = 0; r < YK_ALPHA_ROWS; r++) {
-            const int ty = tyU * YK_ALPHA_ROWS + r;
-            if (ty >= mtH) break;
-            const int nz = nzR[r];
-            const unsigned long long b = __ballot(nz != 0);
-            const bool kept = ((b >> (lane & ~3)) & 0xFULL) != 0;
-            if (tileLane && tx < mtW) keep[(size_t)ty * mtW + tx] = kept ? 1 : 0;
-            // the kept tiles of this row (tile columns of this wave's 16 tiles)
-            const unsigned long long kb64 = __ballot(tileLane && kept && tx < mtW);
-            if (kb64) {
-                const int t0 = seg * (YK_ALPHA_THREADS / 4) + wv * 16;
-                colLo = min(colLo, t0 + ((__ffsll((long long)kb64) - 1) >> 2));
-                colHi = max(colHi, t0 + ((63 - __clzll((long long)kb64)) >> 2));
-                rowLo = min(rowLo, ty); rowHi = max(rowHi, ty);
-            }
-        }
-        if (lane == 0) { s_box[wv][0] = colLo; s_box[wv][1] = colHi; s_box[wv][2] = rowLo; s_box[wv][3] = rowHi; }
-        __syncthreads();
-        // Only the first wave takes part in the arrival protocol (its round trips -- store acknowledged, then one or two returning atomics -- are
-        // 4-5 us at the end of a 20 us workgroup); the other three go on (to their next unit, or out).  s_box is read before anything slow, and the
-        // next iteration's barrier in front of its writes keeps the waves in step.
-        if (wv == 0) {
-            // unit boxes live in unitBox[0 .. nUnits), group boxes behind them; a box = two 64-bit words {x0 | y0 << 32, x1 | y1 << 32}, written
-            // through to memory (the XCDs' L2s are not coherent with each other) and acknowledged before its owner counts as arrived
-            unsigned long long* ub = reinterpret_cast<unsigned long long*>(unitBox);
-            auto putBox = [&](const int slot, const int bx0, const int by0, const int bx1, const int by1) {
-                __hip_atomic_store(&ub[slot * 2], ((unsigned long long)(uint32_t)by0 << 32) | (uint32_t)bx0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&ub[slot * 2 + 1], ((unsigned long long)(uint32_t)by1 << 32) | (uint32_t)bx1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __builtin_amdgcn_s_waitcnt(0);                                      // vmcnt(0): both stores have been acknowledged
-            };
-            auto foldBoxes = [&](const int first, const int n, int& x0, int& gy0, int& x1, int& gy1) {   // the whole wave: boxes [first, first + n)
-                x0 = 9999999; gy0 = 9999999; x1 = -1; gy1 = -1;
-                for (int k = lane; k < n; k += 64) {
-                    const unsigned long long a = __hip_atomic_load(&ub[(first + k) * 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned long long bb = __hip_atomic_load(&ub[(first + k) * 2 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    x0 = min(x0, (int)(uint32_t)a); gy0 = min(gy0, (int)(uint32_t)(a >> 32)); x1 = max(x1, (int)(uint32_t)bb); gy1 = max(gy1, (int)(uint32_t)(bb >> 32));
-                }
+        for (int j = 0; j < 2; j++) {
+            int m = 0;
 #pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    x0 = min(x0, __shfl_xor(x0, d)); x1 = max(x1, __shfl_xor(x1, d));
-                    gy0 = min(gy0, __shfl_xor(gy0, d)); gy1 = max(gy1, __shfl_xor(gy1, d));
-                }
-            };
-            const int g = u >> 6, inGroup = min(64, nUnits - (g << 6));
-            uint32_t lastOfGroup = 0;
-            if (lane == 0) {
-                int lo = s_box[0][0], hi = s_box[0][1], rlo = s_box[0][2], rhi = s_box[0][3];
-#pragma unroll
-                for (int k = 1; k < YK_ALPHA_WAVES; k++) { lo = min(lo, s_box[k][0]); hi = max(hi, s_box[k][1]); rlo = min(rlo, s_box[k][2]); rhi = max(rhi, s_box[k][3]); }
-                const bool any = hi >= 0;
-                putBox(u, any ? lo * 16 : 9999999, any ? y0 + rlo * 16 : 9999999, any ? hi * 16 + 16 : -1, any ? y0 + rhi * 16 + 16 : -1);
-                lastOfGroup = __hip_atomic_fetch_add(&arrive[g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)inGroup - 1u ? 1u : 0u;
-            }
-            if (__builtin_amdgcn_readfirstlane((int)lastOfGroup)) {                  // the group's 64 boxes -> its group box (one round trip, anywhere in the launch)
-                int x0, gy0, x1, gy1;
-                foldBoxes(g << 6, inGroup, x0, gy0, x1, gy1);
-                uint32_t lastOfFrame = 0;
-                if (lane == 0) {
-                    putBox(nUnits + g, x0, gy0, x1, gy1);
-                    arrive[g] = 0u;                                                  // for the next frame (nobody else touches it any more)
-                    lastOfFrame = __hip_atomic_fetch_add(&arrive[nGroups], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)nGroups - 1u ? 1u : 0u;
-                }
-                if (__builtin_amdgcn_readfirstlane((int)lastOfFrame)) {              // every unit of the frame has arrived: the group boxes -> the image's box
-                    foldBoxes(nUnits, nGroups, x0, gy0, x1, gy1);
-                    if (lane == 0) { int32_t* acc = bounds + (size_t)f * 16 + 8; acc[0] = x0; acc[1] = gy0; acc[2] = x1; acc[3] = gy1; arrive[nGroups] = 0u; }
-                }
-            }
+            for (int k = 0; k < 14; k++) m |= a[j][k].x | a[j][k].y | a[j][k].z | a[j][k].w;
+            nzBits |= (m != 0 ? 1u : 0u) << (j ? rB : rA);
         }
-        if (uu + gridDim.x < (long long)nUnits * nFrames) __syncthreads();          // another unit follows: s_box is reused
+    }
+    int colLo = 0x7FFFFFFF, colHi = -1, rowLo = 0x7FFFFFFF, rowHi = -1;          // wave-uniform: kept tile columns / rows of the unit
+#pragma unroll
+    for (int r = 0; r < YK_ALPHA_R; r++) {
+        const int ty = ty0 + r;
+        if (ty >= mtH) break;
+        const unsigned long long b = __ballot(((nzBits >> r) & 1u) != 0);
+        const bool kept = ((b >> (lane & ~3)) & 0xFULL) != 0;
+        if (tileLane && tx < mtW) keep[(size_t)ty * mtW + tx] = kept ? 1 : 0;
+        const unsigned long long kb64 = __ballot(tileLane && kept && tx < mtW);  // the kept tiles of this row of tiles
+        if (kb64) {
+            colLo = min(colLo, seg * 16 + ((__ffsll((long long)kb64) - 1) >> 2));
+            colHi = max(colHi, seg * 16 + ((63 - __clzll((long long)kb64)) >> 2));
+            rowLo = min(rowLo, ty); rowHi = max(rowHi, ty);
+        }
+    }
+    if (lane == 0) {
+        const bool any = colHi >= 0;
+        unitBox0[(size_t)f * nUnits + u] = any ? (yk_i4){colLo * 16, y0 + rowLo * 16, colHi * 16 + 16, y0 + rowHi * 16 + 16} : (yk_i4){9999999, 9999999, -1, -1};
+    }
+}
+
+// One workgroup per frame folds the frame's unit boxes into bounds[f * 16 + 8 .. 11] = {min x0, min y0, max x1, max y1} ({9999999, 9999999, -1, -1}
+// when nothing is kept).  16 boxes per lane are in flight before a wait (the 4096 boxes of an 8192 x 8192 frame: one round trip -- as one wave
+// with two round trips the kernel took 10-19 us beside the pack kernel of the other frame); an index past the last box reads the last box
+// again, which changes no minimum and no maximum.
+__global__ __launch_bounds__(256) void yk_alpha_box_kernel(const yk_i4* __restrict__ unitBox0, int nUnits, int32_t* __restrict__ bounds) {
+    __shared__ yk_i4 s_box[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const yk_i4* ub = unitBox0 + (size_t)blockIdx.x * nUnits;
+    int x0 = 9999999, gy0 = 9999999, x1 = -1, gy1 = -1;
+    for (int base = 0; base < nUnits; base += 256 * 16) {
+        yk_i4 v[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) v[j] = ub[min(base + j * 256 + (int)threadIdx.x, nUnits - 1)];
+#pragma unroll
+        for (int j = 0; j < 16; j++) { x0 = min(x0, v[j].x); gy0 = min(gy0, v[j].y); x1 = max(x1, v[j].z); gy1 = max(gy1, v[j].w); }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        x0 = min(x0, __shfl_xor(x0, d)); x1 = max(x1, __shfl_xor(x1, d));
+        gy0 = min(gy0, __shfl_xor(gy0, d)); gy1 = max(gy1, __shfl_xor(gy1, d));
+    }
+    if (lane == 0) s_box[wv] = (yk_i4){x0, gy0, x1, gy1};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 1; k < 4; k++) { x0 = min(x0, s_box[k].x); gy0 = min(gy0, s_box[k].y); x1 = max(x1, s_box[k].z); gy1 = max(gy1, s_box[k].w); }
+        *reinterpret_cast<yk_i4*>(bounds + (size_t)blockIdx.x * 16 + 8) = (yk_i4){x0, gy0, x1, gy1};
     }
 }
 
@@ -371,11 +348,13 @@ int yk_launch_alpha(yk_ctx* c, bool batch) {
     uint8_t* keep = batch ? c->B.keep : c->keep;
     int32_t* bounds = batch ? c->B.bounds : c->bounds;
     const int32_t* alpha = batch ? c->B.plane[3] : c->plane[3];
-    const int nSeg = (c->fullW / 4 + YK_ALPHA_THREADS - 1) / YK_ALPHA_THREADS;
-    const long long nUnits = (long long)nSeg * ((c->mtH + YK_ALPHA_ROWS - 1) / YK_ALPHA_ROWS) * F;
-    const long long maxWG = 4096LL * (256 / YK_ALPHA_THREADS);
-    hipLaunchKernelGGL(yk_alpha_kernel, dim3((unsigned)(nUnits < maxWG ? nUnits : maxWG)), dim3(YK_ALPHA_THREADS), 0, c->stream, alpha, c->strideElems, c->fullW, c->h, c->y0,
-                       keep, c->mtW, c->mtH, bounds, F, (unsigned long long)c->fs.plane, (unsigned long long)c->fs.keep, c->img.alphaUnitBox, c->img.alphaArrive);
+    const long long nUnits = (long long)yk_alpha_units(c->fullW, c->mtH);
+    if (nUnits * F > 0x7FFFFFFFLL) return yk_fail(c, YK_ERR_BAD_ARG, "too many alpha work units for one launch");
+    yk_i4* unitBox = reinterpret_cast<yk_i4*>(static_cast<int*>(c->img.alphaUnitBox));
+    // never fewer waves than units: nothing loops, a wave ends after its unit
+    hipLaunchKernelGGL(yk_alpha_kernel, dim3((unsigned)((nUnits * F + YK_ALPHA_WAVES - 1) / YK_ALPHA_WAVES)), dim3(64 * YK_ALPHA_WAVES), 0, c->stream, alpha, c->strideElems,
+                       c->fullW, c->h, c->y0, keep, c->mtW, c->mtH, (unsigned long long)c->fs.plane, (unsigned long long)c->fs.keep, unitBox, (unsigned)(nUnits * F));
+    hipLaunchKernelGGL(yk_alpha_box_kernel, dim3((unsigned)F), dim3(256), 0, c->stream, unitBox, (int)nUnits, bounds);
     YK_HIP(c, hipGetLastError());
     c->boundsOff = 8;                                           // whole image / batch: the accumulators are the box; a stripe caller replaces it (yk_alpha_finish)
     return YK_OK;
