@@ -406,12 +406,14 @@ int    yk_export_tile_maps_framed(yk_ctx* c, void* devDst, size_t cap, void* con
  *                         every rank, then yk_gather_maps per image / frame;
  *   one process, n GPUs:  yk_comm_init_all over n handles (one per device), then yk_gather_maps_all. */
 /* HBM scratch for hosts that do not link the HIP runtime themselves (the C++ mirror is plain g++): buffers on the handle's device;
- * yk_device_download copies to the host on the handle's stream and synchronises it; yk_device_copy queues a device-to-device copy on the
+ * yk_device_download copies to the host on the handle's stream and synchronises it; yk_device_upload copies from the host (pageable or pinned)
+ * on the handle's stream and returns when `host` may be reused; yk_device_copy queues a device-to-device copy on the
  * handle's stream and does not synchronise (both buffers on the handle's device; e.g. an encoder's per-handle streams into a buffer that
  * outlives its next yk_select_frame). */
 int  yk_device_alloc(yk_ctx* c, size_t bytes, void** dev);
 void yk_device_free(yk_ctx* c, void* dev);
 int  yk_device_download(yk_ctx* c, void* host, const void* dev, size_t bytes);
+int  yk_device_upload(yk_ctx* c, void* dev, const void* host, size_t bytes);
 int  yk_device_copy(yk_ctx* c, void* devDst, const void* devSrc, size_t bytes);
 int  yk_comm_available(void);                                           /* 1 when RCCL could be loaded */
 int  yk_comm_unique_id(void* id128);                                    /* 128 bytes (ncclUniqueId) */
@@ -588,6 +590,22 @@ int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, s
 int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes /* nFrames */, const int32_t* bboxes /* nFrames x {x,y,w,h} */,
                                  const uint8_t* const* devPayload, const size_t* payBytes, int noChunkAlpha);
 int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes);
+/* The mask modes of 'ALPM' in a batch.  yk_decode_alpha_mask_batch_device does everything yk_decode_alpha_batch_device does (same planes, stride,
+ * validity and refusals) and adds modes 2 and 3: frame f's plane is byte for byte what yk_decode_mask(bits, w, h) followed by yk_decode_alpha(mode,
+ * bbox, payload, mask, maskBytes = w * h * 32, maskBBox = the tile box << 4, refQuirk 0) leaves for that frame.  devMipBits[f] / mipBytes[f] = the
+ * 'MIPM' payload as the file holds it (1 bit per 16x16 tile, LSB first) in device memory, read in place: the mask is never expanded, the bit of a
+ * mask position follows from the tile bitmap.  mipBoxes[4 * f ..] = the 'MIPM' box {x, y, w, h} in tiles; w == 0: the frame has no 'MIPM'.  At most
+ * four launches whatever nFrames is (the unmasked one, then row count, per-frame scan and decode over the masked frames; those three are skipped
+ * when no frame is masked), no host synchronisation.  Further refusals, all before the first launch: YK_ERR_BAD_ARG for a NULL mask table, mode 2
+ * or 3 on a frame with w == 0 or NULL bits, mode 2 or 3 with a box width that is not a multiple of 4, a tile box (of a frame with a chunk) with w
+ * or h < 0 or w * h larger than the image's tile grid ((W + 15) >> 4) * ((H + 15) >> 4); YK_ERR_RANGE for mipBytes[f] < (w * h + 7) / 8.
+ * A payload shorter than the mask selects cannot be known without a read-back and is no refusal: the missing bytes read as 0, nothing is read out
+ * of bounds, and yk_decode_alpha_batch_status (synchronises, reads one word per masked frame) reports per frame 0, or 1 when (selected * 6 + 7) / 8
+ * > payBytes[f]; frames of other modes report 0.  YK_ERR_STATE when the batch has no valid alpha planes. */
+int yk_decode_alpha_mask_batch_device(yk_ctx* c, const int32_t* modes /* nFrames */, const int32_t* bboxes /* nFrames x {x,y,w,h} */,
+                                      const uint8_t* const* devPayload, const size_t* payBytes, const uint8_t* const* devMipBits,
+                                      const size_t* mipBytes, const int32_t* mipBoxes /* nFrames x {x,y,w,h} in 16-px tiles */, int noChunkAlpha);
+int yk_decode_alpha_batch_status(yk_ctx* c, int32_t* out /* nFrames */);
 
 /* ---- round-trip quality (new): what the decode holds against a source image, both in HBM -----------------------------------------
  * The codec is lossy; these calls say how lossy a round trip was without moving a pixel to the host.  One kernel reads the decoder's 8x8-tiled

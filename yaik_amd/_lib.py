@@ -111,6 +111,7 @@ SIGNATURES = {
     "yk_device_alloc": (C.c_int, [vp, sz, C.POINTER(vp)]),
     "yk_device_free": (None, [vp, vp]),
     "yk_device_download": (C.c_int, [vp, vp, vp, sz]),
+    "yk_device_upload": (C.c_int, [vp, vp, vp, sz]),
     "yk_device_copy": (C.c_int, [vp, vp, vp, sz]),
     "yk_comm_available": (C.c_int, []),
     "yk_comm_unique_id": (C.c_int, [vp]),
@@ -150,6 +151,8 @@ SIGNATURES = {
     "yk_decode_1d_batch_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_int]),
     "yk_decode_output_batch_device": (C.c_int, [vp, vp, sz, sz, sz, C.c_int, C.c_int]),
     "yk_decode_alpha_batch_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_int]),
+    "yk_decode_alpha_mask_batch_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]),
+    "yk_decode_alpha_batch_status": (C.c_int, [vp, vp]),
     "yk_decode_output_batch_alpha_device": (C.c_int, [vp, vp, sz, sz, sz]),
     "yk_decode_compare_device": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_int, vp, vp]),
     "yk_decode_compare_batch_device": (C.c_int, [vp, vp, sz, sz, sz, C.c_int, C.c_int, vp, vp]),

@@ -4,6 +4,7 @@
 //   yk_decode_alpha   Decompress1BitMaskAlign8NoMask (decoder/YAIK_Alpha.cpp:25-112), Decompress6BitTo8BitAlphaNoMask (:114-235),
 //                     Decompress6BitTo8BitAlphaUsingMipmapMask (:237-376), Decompress8BitTo8BitAlphaNoMask (:377-444): the full w x h plane
 //                     in HBM (0 outside the box), kept for yk_decode_output_alpha.
+//   yk_decode_alpha_[mask_]batch_device   the same planes for every frame of a decode batch; the mask modes read the 'MIPM' tile bitmap in place
 #include "yk_common.h"
 #include <climits>
 
@@ -119,9 +120,8 @@ __global__ __launch_bounds__(64) void yk_av_rowcount_kernel(const uint8_t* __res
     if (threadIdx.x == 0) rowCnt[r] = cnt;
 }
 // one workgroup: exclusive prefix of the row counts, total in rowStart[bh].  Thread t owns a run of ceil(bh / 1024) rows; the run sums are
-// scanned in LDS
-__global__ __launch_bounds__(1024) void yk_av_rowscan_kernel(const uint32_t* __restrict__ rowCnt, int bh, uint32_t* __restrict__ rowStart) {
-    __shared__ uint32_t s[1024];
+// scanned in LDS.  Returns thread t's inclusive sum: thread 1023 holds the total
+__device__ __forceinline__ uint32_t yk_av_rowscan_body(const uint32_t* __restrict__ rowCnt, int bh, uint32_t* __restrict__ rowStart, uint32_t* s) {
     const int t = threadIdx.x, per = (bh + 1023) / 1024, r0 = t * per, r1 = min(r0 + per, bh);
     uint32_t sum = 0;
     for (int r = r0; r < r1; r++) sum += rowCnt[r];
@@ -136,6 +136,11 @@ __global__ __launch_bounds__(1024) void yk_av_rowscan_kernel(const uint32_t* __r
     uint32_t run = s[t] - sum;
     for (int r = r0; r < r1; r++) { rowStart[r] = run; run += rowCnt[r]; }
     if (t == 1023) rowStart[bh] = s[1023];
+    return s[t];
+}
+__global__ __launch_bounds__(1024) void yk_av_rowscan_kernel(const uint32_t* __restrict__ rowCnt, int bh, uint32_t* __restrict__ rowStart) {
+    __shared__ uint32_t s[1024];
+    (void)yk_av_rowscan_body(rowCnt, bh, rowStart, s);
 }
 // one wave per box row: sample index of a selected pixel = rowStart + selected pixels to its left (ballot + popcount); the state of the
 // reference's 4-value cycle is that index, it carries across rows like `state` does (YAIK_Alpha.cpp:313)
@@ -151,6 +156,59 @@ __global__ __launch_bounds__(64) void yk_av_maskdecode_kernel(const uint8_t* __r
         const unsigned long long b = __ballot(sel);
         const uint32_t before = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
         if (c < bw) row[c] = sel ? yk_av_expand6(yk_av_sample6(pay, n, (size_t)k + before), inv != 0) : 0;
+        k += (uint32_t)__popcll(b);
+    }
+}
+
+// ---- mask modes 2 / 3 in a batch (yk_decode_alpha_mask_batch_device) -----------------------------------------------------------------------------
+// One record per masked frame, read through uniform loads.  The mask bit is derived straight from the frame's 'MIPM' tile bitmap (1 bit per
+// 16x16 tile, LSB first, read in place): yk_dec_mask_kernel writes tile (tx, ty) of a tbw x tbh box as the four u64 words ty * 4 * tbw +
+// {2 tx, 2 tx + 1, 2 tbw + 2 tx, 2 tbw + 2 tx + 1}, all ones or all zeros, so bit `pos` of that buffer is the tile bit of word q = pos >> 6.
+// nq = 4 * tbw * tbh words = the maskBytes = tbw * tbh * 32 of the single-image call: bits at or beyond read 0.
+struct YkAvMaskFrame {
+    const uint8_t* pay; unsigned long long n; const uint8_t* bits;
+    uint32_t base, stride, tbw, nq;          // base / stride as in yk_av_maskbit (stride = tbw * 16)
+    int32_t bx, by, bw, bh, inv, frame;
+    uint32_t oRows, pad;                     // rowCnt[bh], rowStart[bh + 1] at rows + oRows
+};
+__device__ __forceinline__ bool yk_av_tilebit(const YkAvMaskFrame& m, int r, int c) {
+    const uint32_t pos = m.base + m.stride * (uint32_t)r + (uint32_t)c, q = pos >> 6;
+    if (q >= m.nq) return false;
+    const uint32_t per = 4u * m.tbw, i = (q / per) * m.tbw + (((q % per) % (2u * m.tbw)) >> 1);
+    return (m.bits[i >> 3] >> (i & 7)) & 1;
+}
+// one wave per box row of masked frame blockIdx.y (the grid is sized from the tallest box: waves below this frame's box leave at once)
+__global__ __launch_bounds__(64) void yk_av_rowcount_batch_kernel(const YkAvMaskFrame* __restrict__ tab, uint32_t* __restrict__ rows) {
+    const YkAvMaskFrame m = tab[blockIdx.y];
+    const int r = blockIdx.x;
+    if (r >= m.bh) return;
+    uint32_t cnt = 0;
+    for (int c = threadIdx.x; c < m.bw; c += 64) cnt += yk_av_tilebit(m, r, c) ? 1u : 0u;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+    if (threadIdx.x == 0) rows[m.oRows + r] = cnt;
+}
+// one workgroup per masked frame: yk_av_rowscan_kernel's scan, and the frame's status word: 1 when the payload is shorter than the mask selects
+__global__ __launch_bounds__(1024) void yk_av_rowscan_batch_kernel(const YkAvMaskFrame* __restrict__ tab, uint32_t* __restrict__ rows,
+                                                                   int32_t* __restrict__ status) {
+    __shared__ uint32_t s[1024];
+    const YkAvMaskFrame m = tab[blockIdx.x];
+    const uint32_t total = yk_av_rowscan_body(rows + m.oRows, m.bh, rows + m.oRows + m.bh, s);
+    if (threadIdx.x == 1023) status[blockIdx.x] = ((unsigned long long)total * 6 + 7) / 8 > m.n ? 1 : 0;
+}
+// one wave per box row, as yk_av_maskdecode_kernel; the plane was zeroed by the unmasked launch in front
+__global__ __launch_bounds__(64) void yk_av_maskdecode_batch_kernel(const YkAvMaskFrame* __restrict__ tab, const uint32_t* __restrict__ rows, int W,
+                                                                    uint8_t* __restrict__ out, size_t planeStride) {
+    const YkAvMaskFrame m = tab[blockIdx.y];
+    const int r = blockIdx.x, lane = threadIdx.x;
+    if (r >= m.bh) return;
+    uint32_t k = rows[m.oRows + m.bh + r];
+    uint8_t* row = out + (size_t)m.frame * planeStride + (size_t)(m.by + r) * W + m.bx;
+    for (int c0 = 0; c0 < m.bw; c0 += 64) {
+        const int c = c0 + lane;
+        const bool sel = c < m.bw && yk_av_tilebit(m, r, c);
+        const unsigned long long b = __ballot(sel);
+        const uint32_t before = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        if (c < m.bw) row[c] = sel ? yk_av_expand6(yk_av_sample6(m.pay, (size_t)m.n, (size_t)k + before), m.inv != 0) : 0;
         k += (uint32_t)__popcll(b);
     }
 }
@@ -600,19 +658,28 @@ int yk_alpha_payload(yk_ctx* c, int frame, uint8_t* hostOut, size_t cap, size_t*
     return YK_OK;
 }
 
-// The 'ALPM' plane of every frame of a decode batch in one launch; records through the pinned ring + an HBM table, no host synchronisation
-int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes, const int32_t* bboxes, const uint8_t* const* devPayload, const size_t* payBytes,
-                                 int noChunkAlpha) {
+// The 'ALPM' plane of every frame of a decode batch; records through the pinned ring + an HBM table, no host synchronisation.  mip* == nullptr:
+// yk_decode_alpha_batch_device (one launch, the mask modes are refused).  Otherwise the frames of modes 2 / 3 get a zero plane from that launch
+// (a record with an empty box) and their values from three more launches over all of them: row count, per-frame scan, decode
+static int yk_av_decode_batch(yk_ctx* c, const int32_t* modes, const int32_t* bboxes, const uint8_t* const* devPayload, const size_t* payBytes,
+                              const uint8_t* const* devMipBits, const size_t* mipBytes, const int32_t* mipBoxes, bool masks, int noChunkAlpha) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!modes || !bboxes || !devPayload || !payBytes) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
+    if (!modes || !bboxes || !devPayload || !payBytes || (masks && (!devMipBits || !mipBytes || !mipBoxes))) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
     if (noChunkAlpha < 0 || noChunkAlpha > 255) return yk_refuse(c, YK_ERR_BAD_ARG, "noChunkAlpha must be 0..255");
     if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
     const int N = c->dFrames, W = c->dw, H = c->dh;
+    const long long tileGrid = (long long)((W + 15) >> 4) * ((H + 15) >> 4);
+    int nMask = 0, maxBh = 0;
+    size_t rowWords = 0;
     for (int f = 0; f < N; f++) {
         const int mode = modes[f];
         if (mode == -1) continue;
         const int bx = bboxes[4 * f], by = bboxes[4 * f + 1], bw = bboxes[4 * f + 2], bh = bboxes[4 * f + 3];
         if (bx < 0 || by < 0 || bw <= 0 || bh <= 0 || bx >= W || by >= H || bx + bw > W || by + bh > H) return yk_refuse(c, YK_ERR_BAD_ARG, "alpha box outside the image");
+        if (masks) {
+            const long long tw = mipBoxes[4 * f + 2], th = mipBoxes[4 * f + 3];
+            if (tw < 0 || th < 0 || tw * th > tileGrid) return yk_refuse(c, YK_ERR_BAD_ARG, "'MIPM' tile box negative or larger than the image's tile grid");
+        }
         size_t need = 0;
         switch (mode) {
         case 1: if (bw & 7) return yk_refuse(c, YK_ERR_BAD_ARG, "1-bit alpha box width not a multiple of 8");
@@ -620,7 +687,14 @@ int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes, const int32_t*
         case 4: case 5: if (bw & 3) return yk_refuse(c, YK_ERR_BAD_ARG, "6-bit alpha box width not a multiple of 4");
                 need = (size_t)bh * (bw >> 2) * 3; break;
         case 6: need = (size_t)bw * bh; break;
-        case 2: case 3: return yk_refuse(c, YK_ERR_BAD_ARG, "the mask modes 2 and 3 are not batched: they need every frame's decoded mipmap mask");
+        case 2: case 3: {
+            if (!masks) return yk_refuse(c, YK_ERR_BAD_ARG, "the mask modes 2 and 3 are not batched: they need every frame's decoded mipmap mask");
+            if (mipBoxes[4 * f + 2] == 0 || !devMipBits[f]) return yk_refuse(c, YK_ERR_BAD_ARG, "mask mode on a frame without a 'MIPM' bitmap");
+            if (bw & 3) return yk_refuse(c, YK_ERR_BAD_ARG, "6-bit alpha box width not a multiple of 4");
+            const size_t tiles = (size_t)mipBoxes[4 * f + 2] * (size_t)mipBoxes[4 * f + 3];
+            if (mipBytes[f] < (tiles + 7) / 8) return yk_refuse(c, YK_ERR_RANGE, "'MIPM' bitmap shorter than its tile box");
+            nMask++; maxBh = max(maxBh, bh); rowWords += 2 * (size_t)bh + 1;
+            break; }
         default: return yk_refuse(c, YK_ERR_BAD_ARG, "alpha mode not decodable");          // 0 (1 bit + mask), 7, anything else
         }
         if (!devPayload[f] && payBytes[f]) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL alpha payload with a length");
@@ -630,25 +704,74 @@ int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes, const int32_t*
     const size_t plane = (size_t)W * H, stride = (plane + 15) & ~(size_t)15;
     if (c->dAlpha.cap < stride * N) c->dAlphaValid = false;
     YK_HIP(c, c->dAlpha.reserve(c->stream, stride * N));
-    const size_t tabBytes = (size_t)N * sizeof(YkAvDecFrame);
-    YK_HIP(c, c->dAvScratch.reserve(c->stream, tabBytes));
+    const size_t oMask = (size_t)N * sizeof(YkAvDecFrame), tabBytes = oMask + (size_t)nMask * sizeof(YkAvMaskFrame);
+    const size_t oRows = (tabBytes + 255) & ~(size_t)255;
+    YK_HIP(c, c->dAvScratch.reserve(c->stream, oRows + rowWords * sizeof(uint32_t)));
+    if (nMask) YK_HIP(c, c->dAvStatus.reserve(c->stream, 1024));                           // the most frames a batch can have: never re-made
     int slot; void* host;
     { const int rc = yk_dec_table_host(c, tabBytes, &slot, &host); if (rc) return rc; }
     YkAvDecFrame* tab = static_cast<YkAvDecFrame*>(host);
+    YkAvMaskFrame* mtab = reinterpret_cast<YkAvMaskFrame*>(static_cast<uint8_t*>(host) + oMask);
+    c->dAvMaskFrames.clear();
+    size_t rowsAt = 0;
     for (int f = 0; f < N; f++) {
         YkAvDecFrame& r = tab[f];
-        r.mode = modes[f]; r.pay = r.mode < 0 ? nullptr : devPayload[f]; r.n = r.mode < 0 ? 0 : payBytes[f];
-        const bool has = r.mode >= 0;
+        const bool masked = modes[f] == 2 || modes[f] == 3;
+        r.mode = masked ? 6 : modes[f]; r.pay = (r.mode < 0 || masked) ? nullptr : devPayload[f]; r.n = (r.mode < 0 || masked) ? 0 : payBytes[f];
+        const bool has = r.mode >= 0 && !masked;                                            // a masked frame: an empty box, every pixel 0
         r.bx = has ? bboxes[4 * f] : 0; r.by = has ? bboxes[4 * f + 1] : 0; r.bw = has ? bboxes[4 * f + 2] : 0; r.bh = has ? bboxes[4 * f + 3] : 0;
         r.pad[0] = r.pad[1] = r.pad[2] = 0;
+        if (!masked) continue;
+        YkAvMaskFrame& m = mtab[c->dAvMaskFrames.size()];
+        m.pay = devPayload[f]; m.n = payBytes[f]; m.bits = devMipBits[f];
+        m.tbw = (uint32_t)mipBoxes[4 * f + 2]; m.nq = 4u * m.tbw * (uint32_t)mipBoxes[4 * f + 3];
+        m.stride = m.tbw << 4;                                                              // maskBBox = the tile box << 4, u32 arithmetic as the reference's mipmapPos
+        m.base = ((uint32_t)bboxes[4 * f] - (uint32_t)mipBoxes[4 * f] * 16u) + m.stride * ((uint32_t)bboxes[4 * f + 1] - (uint32_t)mipBoxes[4 * f + 1] * 16u);
+        m.bx = bboxes[4 * f]; m.by = bboxes[4 * f + 1]; m.bw = bboxes[4 * f + 2]; m.bh = bboxes[4 * f + 3];
+        m.inv = modes[f] == 3 ? 1 : 0; m.frame = f; m.oRows = (uint32_t)rowsAt; m.pad = 0;
+        rowsAt += 2 * (size_t)m.bh + 1;
+        c->dAvMaskFrames.push_back(f);
     }
     c->dAlphaValid = false;
     { const int rc = yk_dec_table_upload(c, slot, c->dAvScratch, tabBytes); if (rc) return rc; }
     hipLaunchKernelGGL((W & 15) ? yk_av_decode_batch_kernel<true> : yk_av_decode_batch_kernel<false>, dim3((unsigned)((plane / 16 + 255) / 256), (unsigned)N),
                        dim3(256), 0, c->stream, reinterpret_cast<const YkAvDecFrame*>(c->dAvScratch.p), W, H, c->dAlpha, stride,
                        (uint32_t)noChunkAlpha * 0x01010101u);
+    if (nMask) {
+        const YkAvMaskFrame* dTab = reinterpret_cast<const YkAvMaskFrame*>(c->dAvScratch + oMask);
+        uint32_t* rows = reinterpret_cast<uint32_t*>(c->dAvScratch + oRows);
+        const dim3 perRow((unsigned)maxBh, (unsigned)nMask);
+        hipLaunchKernelGGL(yk_av_rowcount_batch_kernel, perRow, dim3(64), 0, c->stream, dTab, rows);
+        hipLaunchKernelGGL(yk_av_rowscan_batch_kernel, dim3((unsigned)nMask), dim3(1024), 0, c->stream, dTab, rows, c->dAvStatus.p);
+        hipLaunchKernelGGL(yk_av_maskdecode_batch_kernel, perRow, dim3(64), 0, c->stream, dTab, rows, W, c->dAlpha.p, stride);
+    }
     YK_HIP(c, hipGetLastError());
     c->dAlphaValid = true; c->dAlphaBatch = true; c->dAlphaStride = stride;
+    return YK_OK;
+}
+
+int yk_decode_alpha_batch_device(yk_ctx* c, const int32_t* modes, const int32_t* bboxes, const uint8_t* const* devPayload, const size_t* payBytes,
+                                 int noChunkAlpha) {
+    return yk_av_decode_batch(c, modes, bboxes, devPayload, payBytes, nullptr, nullptr, nullptr, false, noChunkAlpha);
+}
+
+int yk_decode_alpha_mask_batch_device(yk_ctx* c, const int32_t* modes, const int32_t* bboxes, const uint8_t* const* devPayload, const size_t* payBytes,
+                                      const uint8_t* const* devMipBits, const size_t* mipBytes, const int32_t* mipBoxes, int noChunkAlpha) {
+    return yk_av_decode_batch(c, modes, bboxes, devPayload, payBytes, devMipBits, mipBytes, mipBoxes, true, noChunkAlpha);
+}
+
+// the counterpart of yk_palette_decode_status: what the mask call could not know without a read-back
+int yk_decode_alpha_batch_status(yk_ctx* c, int32_t* out) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!out) return yk_refuse(c, YK_ERR_BAD_ARG, "out is NULL");
+    if (!c->dAlphaValid || !c->dAlphaBatch) return yk_refuse(c, YK_ERR_STATE, "yk_decode_alpha_mask_batch_device first: the batch has no decoded alpha planes");
+    YK_HIP(c, hipSetDevice(c->device));
+    for (int f = 0; f < c->dFrames; f++) out[f] = 0;
+    const size_t nMask = c->dAvMaskFrames.size();
+    std::vector<int32_t> st(nMask);
+    if (nMask) YK_HIP(c, hipMemcpyAsync(st.data(), c->dAvStatus, nMask * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < nMask; i++) out[c->dAvMaskFrames[i]] = st[i];
     return YK_OK;
 }
 

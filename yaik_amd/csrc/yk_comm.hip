@@ -76,6 +76,13 @@ int yk_device_download(yk_ctx* c, void* host, const void* dev, size_t bytes) {
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }
+int yk_device_upload(yk_ctx* c, void* dev, const void* host, size_t bytes) {
+    if (!c || (bytes && (!host || !dev))) return YK_ERR_BAD_ARG;
+    YK_HIP(c, hipSetDevice(c->device));
+    if (bytes) YK_HIP(c, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));                               // pageable or pinned: `host` has been read
+    return YK_OK;
+}
 int yk_device_copy(yk_ctx* c, void* devDst, const void* devSrc, size_t bytes) {
     if (!c || (bytes && (!devDst || !devSrc))) return YK_ERR_BAD_ARG;
     YK_HIP(c, hipSetDevice(c->device));

@@ -259,6 +259,8 @@ struct yk_ctx {
     std::vector<AvSlot> avBatch; bool avBatchValid = false;
     // yk_decode_alpha_batch_device: dAlpha holds dFrames planes dAlphaStride bytes apart (the selected frame's is yk_dec_alpha_cur)
     bool dAlphaBatch = false; size_t dAlphaStride = 0;
+    // yk_decode_alpha_mask_batch_device: the frames of modes 2 / 3 of the last batch call, in table order, and one status word for each of them
+    std::vector<int32_t> dAvMaskFrames; YkBuf<int32_t> dAvStatus;
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
     // decode batch (yk_decode_begin_batch): dPlanes / dMapRGB / dLatticeOwner / dLoaded / dTile4 above are those of frame `dCur`; dB holds the
     // allocations (frame 0) and dStride the distance in BYTES from one frame's array to the next (yk_dec_rebase), like B / fs on the encode side

@@ -16,33 +16,41 @@ from .encoder import PASSES, _chk, u8_pixel_layout, u8_planar_batch_layout, u8_p
 
 
 class AlphaBatchPack(NamedTuple):
-    """The tables of yk_decode_alpha_batch_device for a list of per-frame entries: pack_alpha_batch."""
+    """The tables of yk_decode_alpha_batch_device / yk_decode_alpha_mask_batch_device for a list of per-frame entries: pack_alpha_batch."""
     modes: np.ndarray       # int32 [N]: AlphaHeader::parameters & 7, -1 for a frame without a chunk
     bboxes: np.ndarray      # int32 [N, 4]: (x, y, w, h), zeros for a frame without a chunk
     nbytes: np.ndarray      # uint64 [N]: payload lengths
     where: list             # per frame ("h", offset into staging), ("d", device address) or None
     staging: np.ndarray     # uint8: every host payload at its offset, offsets are multiples of 16; empty when no entry is a host array
+    mip_where: list = None  # only when an entry has a mask: per frame the offset of its 'MIPM' bitmap in staging, or None
+    mip_nbytes: np.ndarray = None   # uint64 [N]: bitmap lengths
+    mip_boxes: np.ndarray = None    # int32 [N, 4]: the 'MIPM' box in 16-pixel tiles, zeros (w == 0) for a frame without one
 
 
 def pack_alpha_batch(entries) -> AlphaBatchPack:
     """entries[f]: None (no 'ALPM' chunk), or (mode, bbox, payload[, nbytes]) with payload a numpy uint8 array (nbytes defaults to its size) or a
-    device pointer (int / c_void_p; nbytes required).  Host payloads are laid out back to back in one staging array, each at a 16-byte aligned
-    offset, so that they reach the device in one copy.  Reads only the entries: no GPU."""
+    device pointer (int / c_void_p; nbytes required), or (mode, bbox, payload, mip_bits, mip_box): a numpy payload with the frame's 'MIPM'
+    bitmap (numpy uint8, 1 bit per tile as the file holds it) and its box (x, y, w, h) in 16-pixel tiles, which the mask modes 2 and 3 need.
+    Host payloads and bitmaps are laid out back to back in one staging array, each at a 16-byte aligned offset, so that they reach the device in
+    one copy.  The mip_* fields stay None unless an entry has a mask.  Reads only the entries: no GPU."""
     n = len(entries)
     modes, bboxes, nbytes = np.full(n, -1, dtype=np.int32), np.zeros((n, 4), dtype=np.int32), np.zeros(n, dtype=np.uint64)
     where, chunks, size = [None] * n, [], 0
+    mip_where, mip_nbytes, mip_boxes, masks = [None] * n, np.zeros(n, dtype=np.uint64), np.zeros((n, 4), dtype=np.int32), False
     for f, e in enumerate(entries):
         if e is None:
             continue
-        if len(e) not in (3, 4):
-            raise ValueError(f"entry {f}: (mode, bbox, payload[, nbytes]) or None expected")
+        if len(e) not in (3, 4, 5):
+            raise ValueError(f"entry {f}: (mode, bbox, payload[, nbytes]), (mode, bbox, payload, mip_bits, mip_box) or None expected")
         mode, bbox, pay = int(e[0]), np.asarray(e[1], dtype=np.int64).reshape(-1), e[2]
         if mode < 0 or bbox.size != 4:
             raise ValueError(f"entry {f}: a mode >= 0 and a box (x, y, w, h) expected (None marks a frame without a chunk)")
+        if len(e) == 5 and not (isinstance(pay, np.ndarray) and isinstance(e[3], np.ndarray) and np.asarray(e[4]).size == 4):
+            raise ValueError(f"entry {f}: a mask entry takes numpy arrays for payload and 'MIPM' bitmap and a tile box (x, y, w, h)")
         modes[f], bboxes[f] = mode, bbox
         if isinstance(pay, np.ndarray):
             a = np.ascontiguousarray(pay, dtype=np.uint8).ravel()
-            nb = a.size if len(e) == 3 else int(e[3])
+            nb = a.size if len(e) != 4 else int(e[3])
             if nb < 0 or a.size < nb:
                 raise ValueError(f"entry {f}: a payload of {a.size} bytes was given a length of {nb}")
             where[f] = ("h", size)
@@ -57,10 +65,18 @@ def pack_alpha_batch(entries) -> AlphaBatchPack:
                 raise ValueError(f"entry {f}: negative length")
             where[f] = ("d", int(pay) if pay else 0)
         nbytes[f] = nb
+        if len(e) == 5:
+            bits = np.ascontiguousarray(e[3], dtype=np.uint8).ravel()
+            masks = True
+            mip_where[f], mip_nbytes[f], mip_boxes[f] = size, bits.size, np.asarray(e[4], dtype=np.int64).reshape(4)
+            chunks.append((size, bits))
+            size = (size + bits.size + 15) & ~15
     staging = np.zeros(size, dtype=np.uint8)
     for off, a in chunks:
         staging[off:off + a.size] = a
-    return AlphaBatchPack(modes, bboxes, nbytes, where, staging)
+    if not masks:
+        return AlphaBatchPack(modes, bboxes, nbytes, where, staging)
+    return AlphaBatchPack(modes, bboxes, nbytes, where, staging, mip_where, mip_nbytes, mip_boxes)
 
 
 def batch_calls_from_table(table, passes=PASSES) -> list:
@@ -395,9 +411,11 @@ class HipTileDecoder:
     def decompress_alpha_batch(self, entries, no_chunk_alpha: int = 255, sync: bool = True) -> None:
         """The 'ALPM' plane of every frame of the batch in one launch (yk_decode_alpha_batch_device).  entries[f] is None (no chunk: the plane is
         the constant no_chunk_alpha) or (mode, bbox, payload[, nbytes]) with the DECOMPRESSED payload as a numpy uint8 array or a device pointer
-        with its length (HipTileEncoder.alpha_payloads_device); modes 1, 4, 5 and 6.  Host arrays are packed into one staging tensor
-        (pack_alpha_batch) and sent in one copy.  The planes stay on the device for image_batch_device(alpha_from_planes=True) and, frame by frame,
-        for image_device(alpha=-1) and alpha_plane()."""
+        with its length (HipTileEncoder.alpha_payloads_device); modes 1, 4, 5 and 6.  An entry (mode, bbox, payload, mip_bits, mip_box) carries the
+        frame's 'MIPM' bitmap and tile box as well; when any entry does, the call goes to yk_decode_alpha_mask_batch_device, which also decodes
+        the mask modes 2 and 3 (three more launches over the masked frames; alpha_batch_status() tells whether a payload was shorter than its mask
+        selects).  Host arrays are packed into one staging tensor (pack_alpha_batch) and sent in one copy.  The planes stay on the device for
+        image_batch_device(alpha_from_planes=True) and, frame by frame, for image_device(alpha=-1) and alpha_plane()."""
         import torch
         L = lib()
         if len(entries) != self.frames:
@@ -416,11 +434,24 @@ class HipTileDecoder:
         ptrs = (C.c_void_p * n)(*[None if w is None else ((base + w[1] if w[0] == "h" else w[1]) or None) for w in pk.where])
         sizes = (C.c_size_t * n)(*[int(v) for v in pk.nbytes])
         self._alpha_batch = False
-        _chk(self._h, L.yk_decode_alpha_batch_device(self._h, pk.modes.ctypes.data, np.ascontiguousarray(pk.bboxes).ctypes.data, ptrs, sizes,
-                                                      int(no_chunk_alpha)))
+        if pk.mip_where is None:
+            _chk(self._h, L.yk_decode_alpha_batch_device(self._h, pk.modes.ctypes.data, np.ascontiguousarray(pk.bboxes).ctypes.data, ptrs, sizes,
+                                                          int(no_chunk_alpha)))
+        else:
+            mptrs = (C.c_void_p * n)(*[None if o is None else base + o for o in pk.mip_where])
+            msizes = (C.c_size_t * n)(*[int(v) for v in pk.mip_nbytes])
+            _chk(self._h, L.yk_decode_alpha_mask_batch_device(self._h, pk.modes.ctypes.data, np.ascontiguousarray(pk.bboxes).ctypes.data, ptrs, sizes,
+                                                               mptrs, msizes, np.ascontiguousarray(pk.mip_boxes).ctypes.data, int(no_chunk_alpha)))
         self._alpha_batch = True
         if sync:
             _chk(self._h, L.yk_synchronize(self._h))
+
+    def alpha_batch_status(self) -> np.ndarray:
+        """One int32 per frame of the last decompress_alpha_batch: 1 = a mask-mode frame whose payload is shorter than its mask selects (the
+        missing bytes were read as 0), 0 otherwise (yk_decode_alpha_batch_status; synchronises)."""
+        out = np.zeros(self.frames, dtype=np.int32)
+        _chk(self._h, lib().yk_decode_alpha_batch_status(self._h, out.ctypes.data))
+        return out
 
     def alpha_plane(self) -> np.ndarray:
         """The decoded 'ALPM' plane [h, w] of the image, or of the selected frame of a batch, back on the host (yk_decode_alpha_plane)."""

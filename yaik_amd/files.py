@@ -1,0 +1,220 @@
+"""`.yaik` files to pixels on the GPU: a ctypes binding of the C++ drop-in decoder (yaik_amd/host/libyaik_host.so, yaik_decode.h).
+
+decode_file_device(stream)    one stream through YAIK_DecodeImageToDevice: uint8 [H, W, 3], or [H, W, 4] when the stream has an 'ALPM' chunk
+decode_files_device(streams)  n streams of one shape through YAIK_DecodeImagesToDevice: ZStd on host workers, one upload, every kernel once over
+                              the batch; uint8 [N, H, W, C] or [N, C, H, W]
+
+The process holds ONE decoder library (YAIK_Init allows one); it is created on first use with a single decode slot on `device()`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import struct
+
+import numpy as np
+
+from ._lib import YaikError, lib
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+HOST_LIB_PATH = os.environ.get("YK_HOST_LIB") or os.path.join(HERE, "host", "libyaik_host.so")
+
+_ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
+_FREE = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)
+
+
+class MemAlloc(C.Structure):
+    _fields_ = [("customAlloc", _ALLOC), ("customFree", _FREE), ("customContext", C.c_void_p)]
+
+
+class DecodedImage(C.Structure):
+    """YAIK_SDecodedImage"""
+    _fields_ = [("width", C.c_uint16), ("height", C.c_uint16), ("hasAlpha", C.c_bool), ("customImageOutput", C.c_void_p),
+                ("userContextCustomImage", C.c_void_p), ("userMemoryAllocator", MemAlloc), ("outputImage", C.c_void_p),
+                ("outputImageStride", C.c_int32), ("hasAlpha1Bit", C.c_bool), ("internalTag", C.c_void_p)]
+
+
+vp, u32 = C.c_void_p, C.c_uint32
+# name -> (restype, argtypes): the declarations of yaik_decode.h this module calls
+SIGNATURES = {
+    "YAIK_Init": (vp, [C.c_uint8, vp]),
+    "YAIK_Release": (None, [vp]),
+    "YAIK_GetErrorCode": (C.c_int, []),
+    "YAIK_SetDevice": (None, [C.c_int]),
+    "YAIK_SetDevicePalette": (None, [C.c_int]),
+    "YAIK_DecodeImagePre": (C.c_bool, [vp, vp, u32, vp]),
+    "YAIK_DecodeImageToDevice": (C.c_bool, [vp, u32, vp]),
+    "YAIK_DecodeImagesToDevice": (C.c_bool, [vp, vp, vp, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp]),
+    "YAIK_LastBatchFallbacks": (C.c_int, []),
+    "YAIK_LastBatchStageMs": (None, [vp]),
+}
+# yaik_decode.h repeats the reference's C++ header, so the library exports these with C++ linkage: their names under the Itanium ABI
+SYMBOLS = {
+    "YAIK_Init": "_Z9YAIK_InithP14YAIK_SMemAlloc",
+    "YAIK_Release": "_Z12YAIK_ReleasePv",
+    "YAIK_GetErrorCode": "_Z17YAIK_GetErrorCodev",
+    "YAIK_SetDevice": "_Z14YAIK_SetDevicei",
+    "YAIK_SetDevicePalette": "_Z21YAIK_SetDevicePalettei",
+    "YAIK_DecodeImagePre": "_Z19YAIK_DecodeImagePrePvS_jP18YAIK_SDecodedImage",
+    "YAIK_DecodeImageToDevice": "_Z24YAIK_DecodeImageToDevicePvjP18YAIK_SDecodedImage",
+    "YAIK_DecodeImagesToDevice": "_Z25YAIK_DecodeImagesToDevicePvPKS_PKjiPhmmmiiPi",
+    "YAIK_LastBatchFallbacks": "_Z23YAIK_LastBatchFallbacksv",
+    "YAIK_LastBatchStageMs": "_Z21YAIK_LastBatchStageMsPd",
+}
+ERROR_NAMES = ["YAIK_NO_ERROR", "YAIK_INVALID_LIBRARYCTX", "YAIK_MALLOC_FAIL", "YAIK_INVALID_CONTEXT_COUNT", "YAIK_INIT_FAIL",
+               "YAIK_RELEASE_EMPTY_LIBRARY", "YAIK_INVALID_STREAM", "YAIK_INVALID_HEADER", "YAIK_NO_EMPTYDECODE_SLOT", "YAIK_DECIMG_INVALIDCTX",
+               "YAIK_DECIMG_DIFFSTREAM", "YAIK_DECIMG_BUFFERNOTSET", "YAIK_INVALID_CONTEXT_MEMALLOCATOR", "YAIK_INVALID_DECOMPRESSION",
+               "YAIK_INVALID_LUT", "YAIK_DECOMPRESSION_CREATE_FAIL", "YAIK_INVALID_MIPMAP_LEVEL", "YAIK_ALPHA_FORMAT_IMPOSSIBLE",
+               "YAIK_INVALID_ALPHA_FORMAT", "YAIK_ALPHA_UNSUPPORTED_YET", "YAIK_INVALID_TAG_ID", "YAIK_INVALID_PLANE_ID"]
+
+
+class YaikFileError(YaikError):
+    """A decode the library refused: .code = YAIK_ERROR_CODE (ERROR_NAMES[code]), .index = the lowest failing stream of a batch (or 0)."""
+
+    def __init__(self, code: int, index: int = 0):
+        name = ERROR_NAMES[code] if 0 <= code < len(ERROR_NAMES) else str(code)
+        super().__init__(f"stream {index}: {name}")
+        self.code, self.index = code, index
+
+
+_host = None
+_yaik = None
+_device = 0
+
+
+def host_lib() -> C.CDLL:
+    """libyaik_host.so.  torch and libyaik_hip.so are brought up first (yaik_amd._lib.lib()), so that the process holds one HIP runtime and the
+    host library binds to the libyaik_hip.so already loaded."""
+    global _host
+    if _host is None:
+        lib()
+        if not os.path.exists(HOST_LIB_PATH):
+            raise YaikError(f"{HOST_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+        L = C.CDLL(HOST_LIB_PATH)
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, SYMBOLS[name])
+            fn.restype, fn.argtypes = res, args
+            setattr(L, name, fn)
+        _host = L
+    return _host
+
+
+def device() -> int:
+    return _device
+
+
+def library(dev: int = 0):
+    """The process-wide decoder library (one decode slot), created on first use on HIP device `dev`."""
+    global _yaik, _device
+    if _yaik is None:
+        L = host_lib()
+        L.YAIK_SetDevice(int(dev))
+        h = L.YAIK_Init(1, None)
+        if not h:
+            raise YaikFileError(L.YAIK_GetErrorCode())
+        _yaik, _device = h, int(dev)
+    return _yaik
+
+
+def release() -> None:
+    global _yaik
+    if _yaik is not None:
+        host_lib().YAIK_Release(_yaik)
+        _yaik = None
+
+
+def set_device_palette(on: bool) -> None:
+    """YAIK_SetDevicePalette: where PaletteDecompressor runs for whole-RGB 'GTIL' chunks (False: host cores, True: the GPU)."""
+    host_lib().YAIK_SetDevicePalette(1 if on else 0)
+
+
+def has_alpha_chunk(stream: bytes) -> bool:
+    """True when the chunk list of the stream holds an 'ALPM' chunk before its terminator (the default builder then writes RGBA rows)."""
+    p, n = 12, len(stream)
+    while p + 8 <= n:
+        tag, length = struct.unpack_from("<II", stream, p)
+        if tag == 0xDEADBEEF:
+            return False
+        if tag == 0x4D504C41:
+            return True
+        p += 8 + length
+    return False
+
+
+def _buffer(stream):
+    a = np.frombuffer(stream, dtype=np.uint8)
+    if a.size >= 1 << 32:
+        raise ValueError("a stream must be shorter than 4 GB")
+    return a
+
+
+def decode_file_device(stream: bytes):
+    """One stream through YAIK_DecodeImageToDevice: a torch.uint8 tensor [H, W, 3] on the GPU, or [H, W, 4] when the stream has an 'ALPM' chunk.
+    Raises YaikFileError with the library's error code."""
+    import torch
+    L, h = host_lib(), library()
+    src = _buffer(stream)
+    info = DecodedImage()
+    if not L.YAIK_DecodeImagePre(h, src.ctypes.data, src.size, C.byref(info)):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    dev = torch.device("cuda", _device)
+    c = 4 if has_alpha_chunk(bytes(stream)) else 3
+    out = torch.empty((info.height, info.width, c), dtype=torch.uint8, device=dev)
+    torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
+    info.outputImage, info.outputImageStride = out.data_ptr(), info.width * c
+    if not L.YAIK_DecodeImageToDevice(src.ctypes.data, src.size, C.byref(info)):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    return out
+
+
+def decode_files_device(streams, out=None, channels: int = 3, planar: bool = False, threads: int = 16):
+    """n (1..1024) streams of ONE width x height as a batch (YAIK_DecodeImagesToDevice): a torch.uint8 tensor [N, H, W, C], or [N, C, H, W] with
+    planar=True, on the GPU.  channels 3 = RGB; 4 = RGBA with alpha from each frame's 'ALPM' chunk, 255 for a frame without one.  `out` may be
+    any view with unit inner stride and any row, plane and frame pitch: only its pixel bytes are written.  The call returns once the pixels are
+    in place.  Raises YaikFileError (.code, .index = the lowest failing stream); the frames' pixels are then unspecified."""
+    import torch
+
+    from .encoder import u8_pixel_layout, u8_planar_batch_layout
+    L, h = host_lib(), library()
+    streams = list(streams)
+    n = len(streams)
+    if not 1 <= n <= 1024:
+        raise ValueError("1..1024 streams are needed")
+    if channels not in (3, 4) or not 1 <= int(threads) <= 16:
+        raise ValueError("channels must be 3 or 4 and threads 1..16")
+    bufs = [_buffer(s) for s in streams]
+    dev = torch.device("cuda", _device)
+    W = H = 0
+    if len(streams[0]) >= 12:
+        tag, _, W, H, _ = struct.unpack_from("<IHHHH", streams[0], 0)
+        if tag != 0x4B494159:                                              # not a .yaik header: the library says so, nothing is written
+            W = H = 0
+    if out is None:
+        out = torch.empty((n, channels, H, W) if planar else (n, H, W, channels), dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.device != dev:
+        raise ValueError(f"out must be a torch tensor on {dev}")
+    if planar:
+        lay = u8_planar_batch_layout(out)
+        plane_bytes = lay.plane_bytes
+    else:
+        lay = u8_pixel_layout(out, batch=True)
+        plane_bytes = 0
+    if (lay.frames, lay.channels, lay.rows, lay.w) != (n, channels, H, W):        # the library writes H x W pixels per frame: never into a smaller view
+        raise ValueError(f"out holds {lay.frames} frames of {lay.w} x {lay.rows} x {lay.channels}, the call needs {n} of {W} x {H} x {channels}")
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_uint32 * n)(*[b.size for b in bufs])
+    failed = C.c_int32(-1)
+    torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
+    ok = L.YAIK_DecodeImagesToDevice(h, ptrs, lens, n, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels, int(threads),
+                                     C.byref(failed))
+    if not ok:
+        raise YaikFileError(L.YAIK_GetErrorCode(), max(failed.value, 0))
+    return out
+
+
+def last_batch_info() -> dict:
+    """Of the last decode_files_device: how many streams took the single-image chain, and the host clocks of its stages in ms."""
+    L = host_lib()
+    ms = (C.c_double * 3)()
+    L.YAIK_LastBatchStageMs(ms)
+    return {"fallbacks": L.YAIK_LastBatchFallbacks(), "expand_ms": ms[0], "upload_ms": ms[1], "decode_ms": ms[2]}

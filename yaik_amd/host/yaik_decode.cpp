@@ -4,11 +4,14 @@
 // YAIK_SetDevicePalette(1) sends the 'GTIL' payloads of whole-RGB chunks to yk_decode_gradient_palette.
 #include "yaik_decode.h"
 #include <atomic>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <thread>
 #include <vector>
 #include "../../include/yaik_hip.h"
+#include "batch_plan.h"
 #include "palette.h"
 #include "yaik_format.h"
 #include "zstd_dl.h"
@@ -23,6 +26,7 @@ struct Slot {
     yk_ctx* ctx = nullptr;
     void* srcCheck = nullptr; uint32_t srcLength = 0;
     int width = 0, height = 0; bool isRGBA = false;
+    std::vector<uint8_t> stage; void* devStage = nullptr; size_t devStageCap = 0;   // YAIK_DecodeImagesToDevice: grow-only staging, host and HBM
 };
 struct Library {
     std::vector<Slot> slots;
@@ -88,7 +92,7 @@ void YAIK_AssignLUT(YAIK_LIB lib, uint8_t* lutData, uint32_t lutDataLength) {
 
 void YAIK_Release(YAIK_LIB lib) {
     if (!lib || lib != gLib) { setError(YAIK_RELEASE_EMPTY_LIBRARY); return; }
-    for (auto& s : gLib->slots) if (s.ctx) yk_destroy(s.ctx);
+    for (auto& s : gLib->slots) if (s.ctx) { if (s.devStage) yk_device_free(s.ctx, s.devStage); yk_destroy(s.ctx); }
     delete gLib; gLib = nullptr;
 }
 
@@ -111,25 +115,17 @@ bool YAIK_DecodeImagePre(YAIK_LIB lib, void* stream, uint32_t length, YAIK_SDeco
     return true;
 }
 
-// The chunk state machine of YAIK_DecodeImage and YAIK_DecodeImageToDevice; toDevice: outputImage is in device memory (default builder only)
-static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice) {
-    if (!info || !info->internalTag || !gLib) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
-    Slot* s = (Slot*)info->internalTag;
-    bool res = false;
+// The chunk state machine shared by YAIK_DecodeImage, YAIK_DecodeImageToDevice and the fallback of YAIK_DecodeImagesToDevice: begins a single
+// image on the slot's handle and runs every chunk up to the terminator; hasAlphaPlane = an 'ALPM' chunk was decoded (pCtx->alphaChannel)
+static bool decodeChunks(Slot* s, const void* stream, uint32_t length, bool& hasAlphaPlane) {
     std::vector<uint8_t> bitmap, pal, rgb, types, pix;
-    const YAIK_SMemAlloc& ua = info->userMemoryAllocator;
-    const bool customBuilder = info->customImageOutput && info->customImageOutput != defaultImageBuilder;
-    do {
-        if (toDevice && customBuilder) { setError(YAIK_DECIMG_INVALIDCTX); break; }               // a custom builder takes host planes
-        if (!ua.customAlloc || !ua.customFree) { setError(YAIK_INVALID_CONTEXT_MEMALLOCATOR); break; }
-        if (s->srcCheck != stream || s->srcLength != length) { setError(YAIK_DECIMG_DIFFSTREAM); break; }
-        if (!info->outputImage) { setError(YAIK_DECIMG_BUFFERNOTSET); break; }
+    hasAlphaPlane = false;
+    {
         const int w = s->width, h = s->height;
-        if (yk_decode_begin(s->ctx, w, h) != YK_OK) { setError(YAIK_MALLOC_FAIL); break; }
+        if (yk_decode_begin(s->ctx, w, h) != YK_OK) { setError(YAIK_MALLOC_FAIL); return false; }
         const uint8_t* p = (const uint8_t*)stream + sizeof(FileHeader);
         const uint8_t* const end = (const uint8_t*)stream + length;
         int state = 0; bool bad = false;
-        bool hasAlphaPlane = false;                                                                     // an 'ALPM' chunk was decoded (pCtx->alphaChannel)
         std::vector<uint8_t> mask, alphaRaw; size_t maskBytes = 0; int32_t maskBox[4] = { 0, 0, 0, 0 };
         while (!bad) {
             if (p + 4 > end) { setError(YAIK_INVALID_TAG_ID); bad = true; break; }
@@ -259,7 +255,25 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
             }
             p = endBlock;
         }
-        if (bad) break;
+        return !bad;
+    }
+}
+
+// YAIK_DecodeImage and YAIK_DecodeImageToDevice; toDevice: outputImage is in device memory (default builder only)
+static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice) {
+    if (!info || !info->internalTag || !gLib) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
+    Slot* s = (Slot*)info->internalTag;
+    bool res = false;
+    const YAIK_SMemAlloc& ua = info->userMemoryAllocator;
+    const bool customBuilder = info->customImageOutput && info->customImageOutput != defaultImageBuilder;
+    do {
+        if (toDevice && customBuilder) { setError(YAIK_DECIMG_INVALIDCTX); break; }               // a custom builder takes host planes
+        if (!ua.customAlloc || !ua.customFree) { setError(YAIK_INVALID_CONTEXT_MEMALLOCATOR); break; }
+        if (s->srcCheck != stream || s->srcLength != length) { setError(YAIK_DECIMG_DIFFSTREAM); break; }
+        if (!info->outputImage) { setError(YAIK_DECIMG_BUFFERNOTSET); break; }
+        const int w = s->width, h = s->height;
+        bool hasAlphaPlane = false;
+        if (!decodeChunks(s, stream, length, hasAlphaPlane)) break;
         if (customBuilder) {
             // custom builder: hand over the 8x8-tiled planes exactly like the reference (:1303-1318)
             const size_t planeSize = (size_t)(w / 8) * (h / 8) * 64;
@@ -301,3 +315,211 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
 
 bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) { return decodeImage(stream, length, info, false); }
 bool YAIK_DecodeImageToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info) { return decodeImage(stream, length, info, true); }
+
+// ---- YAIK_DecodeImagesToDevice: n streams of one shape through the device's batch calls (yaik_decode.h) ------------------------------------
+namespace {
+int gBatchFallbacks = 0;
+double gBatchMs[3] = { 0, 0, 0 };
+
+size_t place(size_t& total, size_t bytes) { const size_t at = total; total = (total + bytes + 15) & ~(size_t)15; return at; }
+
+// where the pieces of one batchable stream lie in the staging buffer
+struct FrameStage {
+    size_t bitmap[yaikplan::NUM_PASSES] = {}, color[yaikplan::NUM_PASSES] = {}, type = 0, pix = 0, alpha = 0, mip = 0;
+};
+
+double nowMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+}
+
+int  YAIK_LastBatchFallbacks() { return gBatchFallbacks; }
+void YAIK_LastBatchStageMs(double out[3]) { if (out) for (int i = 0; i < 3; i++) out[i] = gBatchMs[i]; }
+
+bool YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
+                               size_t frameBytes, int channels, int threads, int32_t* failedIndex) {
+    using namespace yaikplan;
+    if (failedIndex) *failedIndex = -1;
+    if (!lib || lib != gLib) { setError(YAIK_INVALID_LIBRARYCTX); return false; }
+    if (!streams || !lengths || n < 1 || n > 1024 || (channels != 3 && channels != 4) || threads < 1 || threads > 16) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
+    if (!devOut) { setError(YAIK_DECIMG_BUFFERNOTSET); return false; }
+    // the headers: the checks of YAIK_DecodeImagePre on every stream, then one shape
+    int w = 0, h = 0;
+    for (int f = 0; f < n; f++) {
+        int fw = 0, fh = 0;
+        const int rc = readHeader(streams[f], lengths[f], &fw, &fh, nullptr);
+        if (rc == 0 && f == 0) { w = fw; h = fh; }
+        if (rc != 0 || fw != w || fh != h) { setError(rc == 1 ? YAIK_INVALID_STREAM : YAIK_INVALID_HEADER); if (failedIndex) *failedIndex = f; return false; }
+    }
+    Slot* s = nullptr;
+    { std::lock_guard<std::mutex> g(gLib->lock); if (!gLib->freeStack.empty()) { s = gLib->freeStack.back(); gLib->freeStack.pop_back(); } }
+    if (!s) { setError(YAIK_NO_EMPTYDECODE_SLOT); return false; }
+    s->width = w; s->height = h;
+    bool res = false;
+    int failed = -1;
+    gBatchFallbacks = 0;
+    do {
+        const double t0 = nowMs();
+        // ---- plan: sizes come from the chunk headers, so every region of the staging buffer is known before anything is expanded
+        std::vector<StreamPlan> plan((size_t)n);
+        std::vector<char> fallback((size_t)n, 0);
+        for (int f = 0; f < n; f++) fallback[(size_t)f] = planStream(streams[f], lengths[f], plan[(size_t)f]) ? 0 : 1;
+        int range1d = 0, colorCompression = -1;
+        bool devicePalette = gDevicePalette != 0, anyAlpha = false, any1d = false;
+        for (int f = 0; f < n; f++) {
+            if (fallback[(size_t)f]) continue;
+            const StreamPlan& P = plan[(size_t)f];
+            if (P.has1d) { if (!range1d) range1d = P.compressionRange; else if (P.compressionRange != range1d) { fallback[(size_t)f] = 1; continue; } }
+            for (int p = 0; p < NUM_PASSES; p++) {
+                const GradChunk& g = P.grad[p];
+                if (!g.present) continue;
+                if (colorCompression < 0) colorCompression = g.colorCompression;
+                if (g.colorCompression != colorCompression || g.rgbBytes % 3 || (g.rgbBytes && !g.payloadBytes)) devicePalette = false;
+            }
+        }
+        size_t total = 0;
+        size_t zeroBitmap[NUM_PASSES], bmBytes[NUM_PASSES];
+        for (int p = 0; p < NUM_PASSES; p++) { bmBytes[p] = bitmapBytes(p, w, h); zeroBitmap[p] = place(total, bmBytes[p]); }
+        std::vector<FrameStage> at((size_t)n);
+        for (int f = 0; f < n; f++) {
+            if (fallback[(size_t)f]) continue;
+            const StreamPlan& P = plan[(size_t)f]; FrameStage& A = at[(size_t)f];
+            for (int p = 0; p < NUM_PASSES; p++) if (P.grad[p].present) {
+                A.bitmap[p] = place(total, bmBytes[p]);
+                // host coder: the colour stream with PaletteDecompressor's slack behind it; device coder: the payload as ZStd left it
+                A.color[p] = place(total, devicePalette ? (size_t)P.grad[p].payloadBytes + 16 : (size_t)P.grad[p].rgbBytes + 16);
+            }
+            if (P.has1d) { A.type = place(total, (size_t)P.typeBytes + 64); A.pix = place(total, (size_t)P.pixBytes + 64); any1d = true; }
+            if (P.hasAlpha) { A.alpha = place(total, P.alphaBytes); anyAlpha = true; }
+            if (P.hasMip) A.mip = place(total, P.mipBytes);
+        }
+        if (s->stage.size() < total) s->stage.resize(total);
+        uint8_t* const S = s->stage.data();
+        for (int p = 0; p < NUM_PASSES; p++) memset(S + zeroBitmap[p], 0, bmBytes[p]);
+        // ---- expand: ZStd (and the host's PaletteDecompressor) on the workers, one stream per task; a stream that fails becomes a fallback stream
+        std::atomic<int> next{0};
+        const bool devPal = devicePalette;
+        auto work = [&]() {
+            std::vector<uint8_t> pal;
+            for (int f; (f = next.fetch_add(1)) < n;) {
+                if (fallback[(size_t)f]) continue;
+                const StreamPlan& P = plan[(size_t)f]; const FrameStage& A = at[(size_t)f];
+                bool ok = true;
+                for (int p = 0; p < NUM_PASSES && ok; p++) {
+                    const GradChunk& g = P.grad[p];
+                    if (!g.present) continue;
+                    ok = yaikzstd::decompress(S + A.bitmap[p], g.bitmapBytes, g.zBitmap, g.zBitmapBytes);
+                    if (!ok) break;
+                    if (devPal) { ok = yaikzstd::decompress(S + A.color[p], g.payloadBytes, g.zColor, g.zColorBytes); continue; }
+                    pal.assign((size_t)g.payloadBytes + 128 * 3, 0);
+                    ok = yaikzstd::decompress(pal.data(), g.payloadBytes, g.zColor, g.zColorBytes);
+                    if (!ok) break;
+                    // PaletteDecompressor writes whole tokens: into a buffer with the single decoder's slack, then the stream itself is kept
+                    std::vector<uint8_t> rgb((size_t)g.rgbBytes + (size_t)((w + 3) >> 2) * ((h + 3) >> 2) * 12, 0);
+                    ok = PaletteDecompressor(pal.data(), (int)g.payloadBytes, (int)g.payloadBytes + 128 * 3, rgb.data(), (int)g.rgbBytes, g.colorCompression);
+                    if (ok) memcpy(S + A.color[p], rgb.data(), g.rgbBytes);
+                }
+                if (ok && P.has1d) ok = yaikzstd::decompress(S + A.type, P.typeBytes, P.zType, P.zTypeBytes) && yaikzstd::decompress(S + A.pix, P.pixBytes, P.zPix, P.zPixBytes);
+                if (ok && P.hasAlpha) ok = yaikzstd::decompress(S + A.alpha, P.alphaBytes, P.zAlpha, P.zAlphaBytes);
+                if (ok && P.hasMip) memcpy(S + A.mip, P.mipBits, P.mipBytes);
+                if (!ok) fallback[(size_t)f] = 1;
+            }
+        };
+        {
+            const int nt = threads < n ? threads : n;
+            std::vector<std::thread> pool;
+            for (int t = 1; t < nt; t++) pool.emplace_back(work);
+            work();
+            for (auto& t : pool) t.join();
+        }
+        const double t1 = nowMs();
+        // ---- upload: one copy
+        if (s->devStageCap < total) {
+            if (s->devStage) { yk_device_free(s->ctx, s->devStage); s->devStage = nullptr; s->devStageCap = 0; }
+            if (yk_device_alloc(s->ctx, total, &s->devStage) != YK_OK) { setError(YAIK_MALLOC_FAIL); break; }
+            s->devStageCap = total;
+        }
+        const uint8_t* const D = (const uint8_t*)s->devStage;
+        if (yk_device_upload(s->ctx, s->devStage, S, total) != YK_OK) { setError(YAIK_MALLOC_FAIL); break; }
+        const double t2 = nowMs();
+        // ---- decode: every kernel once over the n frames; a fallback stream is an empty frame here
+        if (yk_decode_begin_batch(s->ctx, w, h, n) != YK_OK) { setError(YAIK_MALLOC_FAIL); break; }
+        const size_t NP = (size_t)n * NUM_PASSES;
+        std::vector<const uint8_t*> bm(NP), rgb(NP, nullptr);
+        std::vector<size_t> rgbBytes(NP, 0);
+        for (int f = 0; f < n; f++)
+            for (int p = 0; p < NUM_PASSES; p++) {
+                const bool has = !fallback[(size_t)f] && plan[(size_t)f].grad[p].present;
+                bm[(size_t)f * NUM_PASSES + p] = D + (has ? at[(size_t)f].bitmap[p] : zeroBitmap[p]);
+                if (has && plan[(size_t)f].grad[p].rgbBytes) { rgb[(size_t)f * NUM_PASSES + p] = D + at[(size_t)f].color[p]; rgbBytes[(size_t)f * NUM_PASSES + p] = plan[(size_t)f].grad[p].rgbBytes; }
+            }
+        bool bad = false;
+        if (devicePalette) {
+            // the payloads went up as they are: PaletteDecompressor over all of them in one call, its status checked before the gradient launch
+            std::vector<const uint8_t*> pay; std::vector<size_t> payBytes, outBytes; std::vector<size_t> where;
+            for (size_t i = 0; i < NP; i++) if (rgbBytes[i]) {
+                pay.push_back(rgb[i]); payBytes.push_back(plan[i / NUM_PASSES].grad[i % NUM_PASSES].payloadBytes); outBytes.push_back(rgbBytes[i]); where.push_back(i);
+            }
+            if (!pay.empty()) {
+                std::vector<int32_t> st(pay.size());
+                if (pay.size() > 65536 || yk_palette_decompress_streams(s->ctx, pay.data(), payBytes.data(), outBytes.data(), (int)pay.size(), colorCompression > 0 ? colorCompression : 1) != YK_OK ||
+                    yk_palette_decode_status(s->ctx, st.data()) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+                for (size_t k = 0; k < where.size(); k++) {
+                    const uint8_t* dev = nullptr; size_t nb = 0;
+                    if (yk_palette_decoded_device(s->ctx, (int)k, &dev, &nb) != YK_OK) { bad = true; break; }
+                    rgb[where[k]] = dev; rgbBytes[where[k]] = nb;
+                    if (st[k]) fallback[where[k] / NUM_PASSES] = 1;                  // a payload the coder rejects: the single chain reports it
+                }
+            }
+        }
+        if (bad) { setError(YAIK_INVALID_STREAM); break; }
+        int sx[NUM_PASSES], sy[NUM_PASSES];
+        for (int p = 0; p < NUM_PASSES; p++) { sx[p] = PASS_SHIFT[p][0]; sy[p] = PASS_SHIFT[p][1]; }
+        if (yk_decode_gradient_all_batch_device(s->ctx, NUM_PASSES, sx, sy, bm.data(), bmBytes, rgb.data(), rgbBytes.data(), 0) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+        {
+            std::vector<const uint8_t*> ty((size_t)n, nullptr), px((size_t)n, nullptr);
+            std::vector<size_t> tyB((size_t)n, 0), pxB((size_t)n, 0);
+            for (int f = 0; f < n; f++) if (!fallback[(size_t)f] && plan[(size_t)f].has1d) {
+                const StreamPlan& P = plan[(size_t)f];
+                if (P.typeBytes) { ty[(size_t)f] = D + at[(size_t)f].type; tyB[(size_t)f] = P.typeBytes; }
+                if (P.pixBytes) { px[(size_t)f] = D + at[(size_t)f].pix; pxB[(size_t)f] = P.pixBytes; }
+            }
+            if (yk_decode_1d_batch_device(s->ctx, ty.data(), tyB.data(), px.data(), pxB.data(), any1d && range1d ? range1d : 1) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+        }
+        if (anyAlpha) {                                                        // with three channels too: its status is part of the verdict
+            std::vector<int32_t> modes((size_t)n, -1), boxes((size_t)n * 4, 0), mipBoxes((size_t)n * 4, 0), st((size_t)n, 0);
+            std::vector<const uint8_t*> pay((size_t)n, nullptr), bits((size_t)n, nullptr);
+            std::vector<size_t> payB((size_t)n, 0), bitsB((size_t)n, 0);
+            for (int f = 0; f < n; f++) if (!fallback[(size_t)f] && plan[(size_t)f].hasAlpha) {
+                const StreamPlan& P = plan[(size_t)f];
+                modes[(size_t)f] = P.alphaMode; pay[(size_t)f] = D + at[(size_t)f].alpha; payB[(size_t)f] = P.alphaBytes;
+                for (int k = 0; k < 4; k++) boxes[(size_t)f * 4 + k] = P.alphaBox[k];
+                if (P.hasMip) { bits[(size_t)f] = D + at[(size_t)f].mip; bitsB[(size_t)f] = P.mipBytes; for (int k = 0; k < 4; k++) mipBoxes[(size_t)f * 4 + k] = P.mipBox[k]; }
+            }
+            if (yk_decode_alpha_mask_batch_device(s->ctx, modes.data(), boxes.data(), pay.data(), payB.data(), bits.data(), bitsB.data(), mipBoxes.data(), 255) != YK_OK ||
+                yk_decode_alpha_batch_status(s->ctx, st.data()) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+            for (int f = 0; f < n; f++) if (st[(size_t)f]) fallback[(size_t)f] = 1;       // a payload shorter than the mask selects: the single chain reports it
+        }
+        if (anyAlpha && channels == 4) {
+            if (yk_decode_output_batch_alpha_device(s->ctx, devOut, rowBytes, planeBytes, frameBytes) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+        } else if (yk_decode_output_batch_device(s->ctx, devOut, rowBytes, planeBytes, frameBytes, channels, 255) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+        if (yk_synchronize(s->ctx) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+        const double t3 = nowMs();
+        gBatchMs[0] = t1 - t0; gBatchMs[1] = t2 - t1; gBatchMs[2] = t3 - t2;
+        // ---- fallback: the single-image chain on the same slot, into the frame's slice of devOut
+        res = true;
+        for (int f = 0; f < n && res; f++) {
+            if (!fallback[(size_t)f]) continue;
+            gBatchFallbacks++;
+            bool hasAlphaPlane = false;
+            res = decodeChunks(s, streams[f], lengths[f], hasAlphaPlane);
+            if (res) {
+                const bool plane = hasAlphaPlane && channels == 4;
+                res = yk_decode_output_device(s->ctx, devOut + (size_t)f * frameBytes, rowBytes, planeBytes, channels, plane ? -1 : 255) == YK_OK && yk_synchronize(s->ctx) == YK_OK;
+                if (!res) setError(YAIK_INVALID_STREAM);
+            }
+            if (!res) failed = f;
+        }
+    } while (false);
+    { std::lock_guard<std::mutex> g(gLib->lock); gLib->freeStack.push_back(s); }
+    if (failedIndex) *failedIndex = failed;
+    return res;
+}

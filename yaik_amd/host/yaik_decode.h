@@ -83,3 +83,21 @@ void            YAIK_SetPartialPlaneMarks(int consistent);
 // (palette.cpp), the expanded colour stream is uploaded; 1 = the payload is uploaded as ZStd left it and decompressed on the device
 // (yk_decode_gradient_palette).  Same images; a malformed payload gives YAIK_INVALID_STREAM either way.  Plane-subset chunks stay on the host.
 void            YAIK_SetDevicePalette(int on);
+// extension: n (1..1024) streams of ONE width x height decoded as a batch into DEVICE memory: frame f at devOut + f * frameBytes with the layout rules
+// of yk_decode_output_batch_device (HWC rows of rowBytes, or CHW planes planeBytes apart when planeBytes > 0; only pixel bytes are written).
+// channels 3 = RGB; 4 = RGBA, alpha from the frame's 'ALPM' chunk or 255 for a frame without one.  Frame f's pixel bytes are those
+// YAIK_DecodeImageToDevice writes for stream f (255 added as alpha where that call writes RGB).  Streams made of header, optional 'MIPM', optional
+// 'ALPM', the shipped 'GTIL' passes for all planes in order, optional '1DTL' and the terminator go through the device's batch calls: ZStd (and
+// PaletteDecompressor, unless YAIK_SetDevicePalette(1) and one colorCompression for the batch) on `threads` (1..16) workers into one staging
+// buffer, ONE upload, every kernel once over the n frames (batch_plan.h has the rules).  Any other stream -- '3DTL', plane-subset 'GTIL', another
+// order, a structural or ZStd error, a '1DTL' compressionRange other than the batch's first -- is decoded afterwards by the single-image chain
+// on the same slot.  The call takes one free decode slot and returns it.  A stream whose header differs from stream 0's size fails with
+// YAIK_INVALID_HEADER; a stream YAIK_DecodeImageToDevice rejects makes the call return false with that call's error code; *failedIndex (may be NULL)
+// is the lowest failing index, -1 otherwise.  After a failure the pixel bytes of the n frames are unspecified.  Bad arguments (n, channels,
+// threads, NULL tables) give YAIK_DECIMG_INVALIDCTX, a NULL devOut YAIK_DECIMG_BUFFERNOTSET.
+bool            YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes,
+                                          size_t planeBytes, size_t frameBytes, int channels, int threads, int32_t* failedIndex);
+// how many streams of the last YAIK_DecodeImagesToDevice took the single-image chain, and its host clocks in ms: {plan + expansion, upload,
+// batch calls up to the synchronise}
+int             YAIK_LastBatchFallbacks();
+void            YAIK_LastBatchStageMs(double out[3]);
