@@ -143,6 +143,21 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
 int yk_alpha_values_batch(yk_ctx* c, int force8Bit, yk_alpha_info* infos /* nFrames */);
 int yk_alpha_payload_device(yk_ctx* c, int frame, const uint8_t** dev, size_t* nBytes);
 int yk_alpha_payload(yk_ctx* c, int frame, uint8_t* hostOut, size_t cap, size_t* nBytes);
+/* The 'MIPM' bitmaps of every frame of the handle (new), after the alpha stage of all frames: yk_encode_batch, or for a batch of one yk_alpha_reject +
+ * yk_alpha_finish.  infos[f] and frame f's bytes are exactly what yk_select_frame(f) + yk_alpha_result + yk_alpha_bitmap give: hasChunk = 0 and
+ * nBytes = 0 when the box is the whole image, nBytes = 0 when no tile is kept (bounds[2] < bounds[0]), otherwise bit y * tw + x of tileBBox, LSB
+ * first; remainingPixels is not reported (no chunk needs it).  Whatever nFrames is, a call is ONE kernel launch (frame = a grid dimension; a thread
+ * produces one output byte from the keep flags and the box of its frame, both read on the device) and ONE blocking read-back (the boxes).  Every
+ * frame has a slot of (mtW * mtH + 7) / 8 bytes rounded up to 16 in a buffer of the handle that only grows; the kernel writes the whole slot (zeros
+ * behind nBytes), so nothing is cleared.  A handle without an alpha plane launches nothing: hasChunk 0, the whole image as bounds, tileBBox 0.
+ * yk_alpha_bitmap_device hands out frame's slot where it lies in HBM (*dev = NULL, *nBytes = 0 for a frame without bits) without a host
+ * synchronisation; valid until the next encode, yk_alpha_reject, yk_set_image, yk_set_batch or (re)bind of the handle.  Neither call touches the
+ * buffers of yk_alpha_values[_batch].
+ * Refusals launch nothing and leave the handle usable: YK_ERR_BAD_ARG for NULL infos / result pointers and a frame out of range; YK_ERR_STATE on a
+ * stripe, before yk_set_image, before the alpha stage has finished, and for yk_alpha_bitmap_device before yk_alpha_bitmaps_batch. */
+typedef struct yk_mip_info { int32_t hasChunk; int32_t bounds[4]; int32_t tileBBox[4]; uint32_t nBytes; } yk_mip_info;
+int yk_alpha_bitmaps_batch(yk_ctx* c, yk_mip_info* infos /* nFrames */);
+int yk_alpha_bitmap_device(yk_ctx* c, int frame, const uint8_t** dev, size_t* nBytes);
 
 /* ---- a6 + a10..a13  fused tile encode ----------------------------------------------------------
  * One launch does what 7x EncoderContext::FittingQuadSmooth(rejectFactor, R,G,B, .., sx, sy)
@@ -415,6 +430,19 @@ void yk_device_free(yk_ctx* c, void* dev);
 int  yk_device_download(yk_ctx* c, void* host, const void* dev, size_t bytes);
 int  yk_device_upload(yk_ctx* c, void* dev, const void* host, size_t bytes);
 int  yk_device_copy(yk_ctx* c, void* devDst, const void* devSrc, size_t bytes);
+/* yk_device_copy for a list of segments (new): nSeg (1..262144) pieces of device memory into ONE buffer, so that what a batch left in several
+ * handle buffers crosses to the host with one download.  Segment i lands at devDst + offsets[i]: offsets[0] = 0, offsets[i + 1] = offsets[i] +
+ * nBytes[i] rounded up to 16, *total = the end of the last segment rounded up to 16.  devDst == NULL is a size query (offsets and *total only; devSrc
+ * is then not looked at and may be NULL).  One kernel launch on the handle's stream and one table upload (through the pinned ring of the batch tables), no host
+ * synchronisation.  The grid follows the bytes moved: a workgroup of 256 lanes copies one 4 KB piece of one segment, 16 bytes per lane, and finds its
+ * segment by a binary search over the per-segment piece counts.  A source may have any alignment (sources that are not 16-byte aligned are read
+ * through byte pointers); devDst must be a multiple of 16.  Only the segments' own bytes are written: the gaps between them and everything from
+ * *total on keep their contents.  A segment of length 0 is skipped and its pointer may be NULL.  ORDERING against the sources' producers is the
+ * caller's, as for the yk_decode_*_device entry points: they are read on this handle's stream.
+ * Refusals launch nothing and write nothing: YK_ERR_BAD_ARG for a NULL nBytes / offsets / total (or devSrc with a destination), nSeg outside
+ * 1..262144, a length with a NULL source, a devDst that is not a multiple of 16, 2^31 or more 4 KB pieces in one call; YK_ERR_RANGE for cap < *total
+ * (offsets and *total are filled in). */
+int  yk_device_gather(yk_ctx* c, const void* const* devSrc, const size_t* nBytes, int nSeg, void* devDst, size_t cap, size_t* offsets /* nSeg, out */, size_t* total);
 int  yk_comm_available(void);                                           /* 1 when RCCL could be loaded */
 int  yk_comm_unique_id(void* id128);                                    /* 128 bytes (ncclUniqueId) */
 int  yk_comm_init_rank(yk_ctx* c, const void* id128, int nRanks, int rank, void** comm);

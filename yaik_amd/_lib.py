@@ -56,6 +56,8 @@ SIGNATURES = {
     "yk_alpha_values_batch": (C.c_int, [vp, C.c_int, vp]),
     "yk_alpha_payload_device": (C.c_int, [vp, C.c_int, C.POINTER(vp), szp]),
     "yk_alpha_payload": (C.c_int, [vp, C.c_int, vp, sz, szp]),
+    "yk_alpha_bitmaps_batch": (C.c_int, [vp, vp]),
+    "yk_alpha_bitmap_device": (C.c_int, [vp, C.c_int, C.POINTER(vp), szp]),
     "yk_encode_tiles": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
     "yk_encode_frame": (C.c_int, [vp, C.c_int, C.c_int]),
     "yk_set_batch": (C.c_int, [vp, C.c_int]),
@@ -113,6 +115,7 @@ SIGNATURES = {
     "yk_device_download": (C.c_int, [vp, vp, vp, sz]),
     "yk_device_upload": (C.c_int, [vp, vp, vp, sz]),
     "yk_device_copy": (C.c_int, [vp, vp, vp, sz]),
+    "yk_device_gather": (C.c_int, [vp, vp, vp, C.c_int, vp, sz, vp, szp]),
     "yk_comm_available": (C.c_int, []),
     "yk_comm_unique_id": (C.c_int, [vp]),
     "yk_comm_init_rank": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),

@@ -776,3 +776,95 @@ int yk_decode_alpha_batch_status(yk_ctx* c, int32_t* out) {
 }
 
 }  // extern "C"
+
+// ---- 'MIPM' bitmaps of every frame (yk_alpha_bitmaps_batch) -------------------------------------------------------------------------------------
+// The rule is yk_alpha_bitmap's (EncoderContext.cpp:1317-1327): inside the box of kept tiles, in 16-pixel tiles {bx0, by0, tw, th}, bit y * tw + x,
+// LSB first, is the keep flag of tile (bx0 + x, by0 + y); no bits when the box is the whole image or no tile is kept.  blockIdx.y = frame; a thread
+// produces one byte of its frame's slot, i.e. the flags of 8 consecutive bit positions, which cross tile rows wherever tw is no multiple of 8; it
+// divides once and then steps.  The box and the frame's flags are read through uniform loads.  Every byte of the slot is written, zeros behind the bits.
+namespace {
+#define YK_MIP_THREADS 256
+__global__ __launch_bounds__(YK_MIP_THREADS) void yk_mip_bits_batch_kernel(const uint8_t* __restrict__ keep, unsigned long long keepStride, const int32_t* __restrict__ bounds,
+                                                                           int W, int H, int mtW, int mtH, uint32_t slot, uint8_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * YK_MIP_THREADS + threadIdx.x;
+    if (i >= slot) return;
+    const uint32_t f = blockIdx.y;
+    const int32_t* b = bounds + (size_t)f * 16;
+    const int b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
+    const int bx0 = b0 >> 4, by0 = b1 >> 4, tw = (b2 >> 4) - bx0, th = (b3 >> 4) - by0;
+    const bool none = (b0 == 0 && b1 == 0 && b2 == W && b3 == H) || b2 < b0 || tw <= 0 || th <= 0 || bx0 < 0 || by0 < 0;
+    const uint32_t nBits = none ? 0u : (uint32_t)tw * (uint32_t)th;
+    const uint8_t* __restrict__ k = keep + (size_t)f * keepStride;
+    uint32_t v = 0, bp = i * 8u;
+    if (bp < nBits) {
+        uint32_t y = bp / (uint32_t)tw, x = bp - y * (uint32_t)tw;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t mx = (uint32_t)bx0 + x, my = (uint32_t)by0 + y;
+            if (bp + j < nBits && mx < (uint32_t)mtW && my < (uint32_t)mtH && k[(size_t)my * mtW + mx]) v |= 1u << j;
+            if (++x == (uint32_t)tw) { x = 0; y++; }
+        }
+    }
+    out[(size_t)f * slot + i] = (uint8_t)v;
+}
+}  // namespace
+
+extern "C" {
+
+int yk_alpha_bitmaps_batch(yk_ctx* c, yk_mip_info* infos) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!infos) return yk_refuse(c, YK_ERR_BAD_ARG, "infos is NULL");
+    if (c->fullW <= 0 || c->fullH <= 0) return yk_refuse(c, YK_ERR_STATE, "yk_set_image first");
+    if (c->y0 != 0 || c->h != c->fullH) return yk_refuse(c, YK_ERR_STATE, "yk_alpha_bitmaps_batch works on whole images, not on a stripe");
+    const int N = c->nFrames, W = c->fullW, H = c->fullH;
+    if (c->nPlanes == 4) {
+        if (!c->alphaFinished) return yk_refuse(c, YK_ERR_STATE, "the alpha stage first: yk_encode_batch, or yk_alpha_reject + yk_alpha_finish");
+        if (!c->B.keep || !c->B.bounds) return yk_refuse(c, YK_ERR_STATE, "the alpha stage first: yk_encode_batch, or yk_alpha_reject + yk_alpha_finish");
+    }
+    c->mipValid = false;
+    c->mipBytes.assign((size_t)N, 0u);
+    for (int f = 0; f < N; f++) {                                                          // no alpha plane: EncoderContext.cpp:1419-1426
+        yk_mip_info& o = infos[f];
+        o.hasChunk = 0; o.bounds[0] = 0; o.bounds[1] = 0; o.bounds[2] = W; o.bounds[3] = H;
+        o.tileBBox[0] = o.tileBBox[1] = o.tileBBox[2] = o.tileBBox[3] = 0; o.nBytes = 0;
+    }
+    if (c->nPlanes != 4) { c->mipSlot = 0; c->mipValid = true; return YK_OK; }
+    YK_HIP(c, hipSetDevice(c->device));
+    const size_t slot = ((((size_t)c->mtW * c->mtH + 7) / 8) + 15) & ~(size_t)15;
+    YK_HIP(c, c->mipBits.reserve(c->stream, slot * (size_t)N));
+    hipLaunchKernelGGL(yk_mip_bits_batch_kernel, dim3((unsigned)((slot + YK_MIP_THREADS - 1) / YK_MIP_THREADS), (unsigned)N), dim3(YK_MIP_THREADS), 0, c->stream,
+                       c->B.keep, N > 1 ? c->fs.keep : 0ull, c->B.bounds + c->boundsOff, W, H, c->mtW, c->mtH, (uint32_t)slot, c->mipBits.p);
+    YK_HIP(c, hipGetLastError());
+    std::vector<int32_t> bnd((size_t)N * 16);
+    YK_HIP(c, hipMemcpyAsync(bnd.data(), c->B.bounds, bnd.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // the one read-back: every frame's box
+    for (int f = 0; f < N; f++) {
+        const int32_t* b = &bnd[(size_t)f * 16 + c->boundsOff];
+        yk_mip_info& o = infos[f];
+        const bool whole = b[0] == 0 && b[1] == 0 && b[2] == W && b[3] == H;               // every reject discarded (:1294, :1400-1403)
+        o.hasChunk = whole ? 0 : 1;
+        for (int i = 0; i < 4; i++) o.bounds[i] = b[i];
+        o.tileBBox[0] = b[0] >> 4; o.tileBBox[1] = b[1] >> 4; o.tileBBox[2] = (b[2] >> 4) - (b[0] >> 4); o.tileBBox[3] = (b[3] >> 4) - (b[1] >> 4);
+        if (whole || b[2] < b[0] || o.tileBBox[2] <= 0 || o.tileBBox[3] <= 0 || b[0] < 0 || b[1] < 0) continue;
+        const size_t sz = ((size_t)o.tileBBox[2] * o.tileBBox[3] + 7) / 8;
+        if (sz > slot) return yk_refuse(c, YK_ERR_STATE, "alpha box beyond the image");
+        o.nBytes = (uint32_t)sz; c->mipBytes[(size_t)f] = (uint32_t)sz;
+    }
+    c->mipSlot = slot; c->mipValid = true;
+    return YK_OK;
+}
+
+int yk_alpha_bitmap_device(yk_ctx* c, int frame, const uint8_t** dev, size_t* nBytes) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (dev) *dev = nullptr;
+    if (nBytes) *nBytes = 0;
+    if (!dev || !nBytes) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL result pointer");
+    if (!c->mipValid) return yk_refuse(c, YK_ERR_STATE, "yk_alpha_bitmaps_batch first (the bitmaps do not outlive an encode, yk_alpha_reject, a new image or new planes)");
+    if (frame < 0 || frame >= (int)c->mipBytes.size()) return yk_refuse(c, YK_ERR_BAD_ARG, "frame out of range");
+    const uint32_t n = c->mipBytes[(size_t)frame];
+    if (!n) return YK_OK;
+    *dev = c->mipBits.p + (size_t)frame * c->mipSlot; *nBytes = n;
+    return YK_OK;
+}
+
+}  // extern "C"

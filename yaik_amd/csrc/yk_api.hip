@@ -36,14 +36,14 @@ void yk_rebase(yk_ctx* c, int f) {
 
 // New input (an image shape, planes, pixels): nothing computed from the previous input may be handed out any more
 static void yk_input_changed(yk_ctx* c) {
-    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->img.sb.valid = false; c->pal.valid = false;
+    c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->mipValid = false; c->img.sb.valid = false; c->pal.valid = false;
     c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false;
 }
 
 // A new encode has been queued: everything derived from the previous one is stale, the corner passes and the 1-D path start over
 static void yk_encode_done(yk_ctx* c, int wantDst) {
     c->encoded = true; c->dstValid = wantDst != 0; c->img.sb.valid = false; c->pal.valid = false; c->cornersReady = false; c->ppActive = false;
-    c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false;
+    c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false; c->mipValid = false;
 }
 
 static void yk_free_image(yk_ctx* c) {
@@ -479,7 +479,7 @@ int yk_alpha_reject(yk_ctx* c) {
     YK_HIP(c, hipEventRecord(ev[YK_EV_A0], c->stream));
     int rc = yk_launch_alpha(c); if (rc) return rc;
     c->evAlphaInCur = true;                                                  // the interval ends with the record in front of the fused kernel
-    c->alphaDone = true; c->alphaFinished = false; c->avBatchValid = false;
+    c->alphaDone = true; c->alphaFinished = false; c->avBatchValid = false; c->mipValid = false;
     return YK_OK;
 }
 
@@ -657,7 +657,7 @@ int yk_encode_batch(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
     rc = yk_launch_pack(c, true); if (rc) return rc;
     YK_HIP(c, hipEventRecord(ev[YK_EV_P1], c->stream));
     yk_ev_commit(c, (c->nPlanes == 4 ? YK_EVSET_ALPHA : 0) | YK_EVSET_PACK);
-    c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false;
+    c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false; c->mipValid = false;
     yk_encode_done(c, 0);
     return YK_OK;
 }
@@ -693,7 +693,7 @@ int yk_encode_frame(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
     YK_HIP(c, hipGraphLaunch(c->frameGraph, c->stream));
     YK_HIP(c, hipEventRecord(ev[YK_EV_E1], c->stream));
     yk_ev_commit(c, 0);
-    c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false;
+    c->alphaDone = c->nPlanes == 4; c->alphaFinished = true; c->avBatchValid = false; c->mipValid = false;
     yk_encode_done(c, 0);
     return YK_OK;
 }

@@ -257,6 +257,10 @@ struct yk_ctx {
     YkBuf<uint8_t> avTab;
     struct AvSlot { int32_t mode; size_t off, bytes; };
     std::vector<AvSlot> avBatch; bool avBatchValid = false;
+    // yk_alpha_bitmaps_batch: the 'MIPM' bits of every frame, one slot of mipSlot bytes each (written whole by the kernel); mipBytes = the lengths
+    // yk_alpha_bitmap_device hands out (valid while mipValid)
+    YkBuf<uint8_t> mipBits; size_t mipSlot = 0; std::vector<uint32_t> mipBytes; bool mipValid = false;
+    YkBuf<uint8_t> gatherTab;                            // yk_device_gather: piece prefixes and segment records in HBM
     // yk_decode_alpha_batch_device: dAlpha holds dFrames planes dAlphaStride bytes apart (the selected frame's is yk_dec_alpha_cur)
     bool dAlphaBatch = false; size_t dAlphaStride = 0;
     // yk_decode_alpha_mask_batch_device: the frames of modes 2 / 3 of the last batch call, in table order, and one status word for each of them

@@ -143,6 +143,21 @@ def u8_planar_batch_layout(pixels) -> PlanarBatchLayout:
     return PlanarBatchLayout(frames, lay.channels, lay.rows, lay.w, lay.row_bytes, lay.plane_bytes, frame_bytes)
 
 
+def gather_layout(nbytes):
+    """Where HipTileEncoder.gather (yk_device_gather) puts segments of these lengths: (offsets, total) -- offsets[0] = 0, every later offset the
+    previous end rounded up to 16, total = the last end rounded up to 16.  Pure; int64 numpy offsets."""
+    n = np.asarray(nbytes, dtype=np.int64).reshape(-1)
+    if n.size and int(n.min()) < 0:
+        raise ValueError("segment lengths must not be negative")
+    ends = np.cumsum((n + 15) & ~np.int64(15))
+    offsets = np.concatenate([np.zeros(1, np.int64), ends[:-1]]) if n.size else np.zeros(0, np.int64)
+    return offsets, int(ends[-1]) if n.size else 0
+
+
+class _MipInfoC(C.Structure):                     # yk_mip_info of include/yaik_hip.h
+    _fields_ = [("hasChunk", C.c_int32), ("bounds", C.c_int32 * 4), ("tileBBox", C.c_int32 * 4), ("nBytes", C.c_uint32)]
+
+
 class _FrameStreamsC(C.Structure):                # yk_frame_streams of include/yaik_hip.h
     _fields_ = [("bitmap", C.c_void_p * 7), ("bitmapBytes", C.c_size_t * 7), ("rgb", C.c_void_p * 7), ("rgbBytes", C.c_size_t * 7),
                 ("pix", C.c_void_p), ("pixBytes", C.c_size_t), ("type", C.c_void_p), ("typeBytes", C.c_size_t)]
@@ -351,6 +366,55 @@ class HipTileEncoder:
             _chk(self._h, self._L.yk_alpha_payload_device(self._h, f, C.byref(dev), C.byref(n)))
             out.append((e[0], e[1], int(dev.value or 0), int(n.value)))
         return out
+
+    def _alpha_bitmaps_batch(self):
+        infos = (_MipInfoC * self.frames)()
+        _chk(self._h, self._L.yk_alpha_bitmaps_batch(self._h, infos))
+        return infos
+
+    def alpha_bitmaps_device(self) -> list:
+        """The 'MIPM' bitmaps of every frame (yk_alpha_bitmaps_batch: one launch and one read-back for the whole batch), left in HBM: per frame
+        {"has_chunk", "bounds", "tile_bbox", "ptr", "nbytes"} (ptr 0 and nbytes 0 for a frame without bits).  After encode_batch() (or, with one
+        frame, mip_prefilter()).  The bits are written on this handle's stream and stay valid until the next encode, alpha_reject, set_image /
+        set_batch of the handle."""
+        out = []
+        for f, i in enumerate(self._alpha_bitmaps_batch()):
+            dev, n = C.c_void_p(), C.c_size_t()
+            _chk(self._h, self._L.yk_alpha_bitmap_device(self._h, f, C.byref(dev), C.byref(n)))
+            out.append({"has_chunk": bool(i.hasChunk), "bounds": np.array(list(i.bounds), np.int32), "tile_bbox": np.array(list(i.tileBBox), np.int32),
+                        "ptr": int(dev.value or 0), "nbytes": int(n.value)})
+        return out
+
+    def alpha_bitmaps_batch(self) -> list:
+        """alpha_bitmaps_device() with the bits copied out: per frame the dict of alpha_result() without "remaining"."""
+        out = []
+        for e in self.alpha_bitmaps_device():
+            bits = np.zeros(e["nbytes"], np.uint8)
+            if bits.size:
+                _chk(self._h, self._L.yk_device_download(self._h, bits.ctypes.data, C.c_void_p(e["ptr"]), bits.size))
+            out.append({"has_chunk": e["has_chunk"], "bounds": e["bounds"], "tile_bbox": e["tile_bbox"], "bitmap": bits})
+        return out
+
+    gather_layout = staticmethod(gather_layout)
+
+    def gather(self, ptrs, nbytes, out=None):
+        """yk_device_gather: the segments (device addresses `ptrs`, lengths `nbytes`; a length of 0 may come with address 0) into `out`, a
+        contiguous torch uint8 CUDA tensor whose address is a multiple of 16, at the offsets of gather_layout().  One launch on this handle's
+        stream, no synchronisation: synchronize() (or a stream hand-off) before another stream reads `out`.  out=None is the size query.
+        Returns (offsets, total)."""
+        n = len(nbytes)
+        src = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in ptrs])
+        lens = (C.c_size_t * max(n, 1))(*[int(v) for v in nbytes])
+        offs, total = (C.c_size_t * max(n, 1))(), C.c_size_t()
+        if out is None:
+            dst, cap = None, 0
+        else:
+            import torch
+            assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+            torch.cuda.current_stream(out.device).synchronize()           # hand-over fence, see set_image
+            dst, cap = C.c_void_p(out.data_ptr()), out.numel()
+        _chk(self._h, self._L.yk_device_gather(self._h, src, lens, n, dst, cap, offs, C.byref(total)))
+        return np.array(list(offs)[:n], np.int64), int(total.value)
 
     # ---- 7x FittingQuadSmooth + 3x DynamicTileEncode, one launch ---------------------------------------
     def encode(self, reject_factor: int = 3, mode3bit_only: bool = False, want_dst: bool = False, dst_fill: int = -1):

@@ -3,6 +3,9 @@
 decode_file_device(stream)    one stream through YAIK_DecodeImageToDevice: uint8 [H, W, 3], or [H, W, 4] when the stream has an 'ALPM' chunk
 decode_files_device(streams)  n streams of one shape through YAIK_DecodeImagesToDevice: ZStd on host workers, one upload, every kernel once over
                               the batch; uint8 [N, H, W, C] or [N, C, H, W]
+encode_files_device(frames)   the other direction (yaik_encode.h, YAIK_EncodeImagesFromDevice): uint8 [N, H, W, C] frames in device memory to N
+                              streams, every kernel once over the batch, one gather and one download, ZStd and framing on host workers
+encode_file_device(frame)     a batch of one
 
 The process holds ONE decoder library (YAIK_Init allows one); it is created on first use with a single decode slot on `device()`.
 """
@@ -61,6 +64,15 @@ SYMBOLS = {
     "YAIK_LastBatchFallbacks": "_Z23YAIK_LastBatchFallbacksv",
     "YAIK_LastBatchStageMs": "_Z21YAIK_LastBatchStageMsPd",
 }
+# yaik_encode.h: declared extern "C", bound under their own names
+ENC_SIGNATURES = {
+    "YAIK_EncoderCreate": (vp, [C.c_int]),
+    "YAIK_EncoderRelease": (None, [vp]),
+    "YAIK_EncodeImagesFromDevice": (C.c_bool, [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "YAIK_EncodedStream": (C.c_bool, [vp, C.c_int, vp, vp]),
+    "YAIK_EncoderLastError": (C.c_char_p, [vp]),
+    "YAIK_LastEncodeStageMs": (None, [vp, vp]),
+}
 ERROR_NAMES = ["YAIK_NO_ERROR", "YAIK_INVALID_LIBRARYCTX", "YAIK_MALLOC_FAIL", "YAIK_INVALID_CONTEXT_COUNT", "YAIK_INIT_FAIL",
                "YAIK_RELEASE_EMPTY_LIBRARY", "YAIK_INVALID_STREAM", "YAIK_INVALID_HEADER", "YAIK_NO_EMPTYDECODE_SLOT", "YAIK_DECIMG_INVALIDCTX",
                "YAIK_DECIMG_DIFFSTREAM", "YAIK_DECIMG_BUFFERNOTSET", "YAIK_INVALID_CONTEXT_MEMALLOCATOR", "YAIK_INVALID_DECOMPRESSION",
@@ -80,6 +92,8 @@ class YaikFileError(YaikError):
 _host = None
 _yaik = None
 _device = 0
+_encoders: dict = {}               # device index -> YAIK_ENC, created on first use
+_last_encoder = None
 
 
 def host_lib() -> C.CDLL:
@@ -95,6 +109,9 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
+        for name, (res, args) in ENC_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
         _host = L
     return _host
 
@@ -117,10 +134,14 @@ def library(dev: int = 0):
 
 
 def release() -> None:
+    """Drops the decoder library and every cached encoder."""
     global _yaik
     if _yaik is not None:
         host_lib().YAIK_Release(_yaik)
         _yaik = None
+    for e in _encoders.values():
+        host_lib().YAIK_EncoderRelease(e)
+    _encoders.clear()
 
 
 def set_device_palette(on: bool) -> None:
@@ -218,3 +239,69 @@ def last_batch_info() -> dict:
     ms = (C.c_double * 3)()
     L.YAIK_LastBatchStageMs(ms)
     return {"fallbacks": L.YAIK_LastBatchFallbacks(), "expand_ms": ms[0], "upload_ms": ms[1], "decode_ms": ms[2]}
+
+
+class YaikEncodeError(YaikError):
+    """An encode the library refused: .index = the lowest frame that could not be framed, -1 for bad arguments and device errors."""
+
+    def __init__(self, message: str, index: int = -1):
+        super().__init__(message if index < 0 else f"frame {index}: {message}")
+        self.index = index
+
+
+def encoder(dev: int = 0):
+    """The cached YAIK_ENC of HIP device `dev` (one per device, dropped by release())."""
+    e = _encoders.get(int(dev))
+    if e is None:
+        e = host_lib().YAIK_EncoderCreate(int(dev))
+        if not e:
+            raise YaikError(f"YAIK_EncoderCreate({dev}) failed: no usable HIP device -- this path has no CPU fallback")
+        _encoders[int(dev)] = e
+    return e
+
+
+def encode_files_device(frames, emit_alpha: bool = False, level: int = 0, threads: int = 16) -> list:
+    """N (1..1024) frames of one shape as a batch (YAIK_EncodeImagesFromDevice): `frames` is a torch.uint8 CUDA tensor [N, H, W, C], C = 3 (RGB)
+    or 4 (RGBA); stride(1) is the row pitch and stride(0) the frame pitch, the last two dims are dense.  A numpy array is uploaded through
+    torch.  Returns N `bytes`, each a whole .yaik stream.  level 0: byte for byte the file ConvertHotPath writes for the frame alone (ZStd level
+    18, 'ALPM' swept over levels 5..21); level 1..22: every stream at that ZStd level.  emit_alpha writes the 'ALPM' chunk of RGBA frames (8-bit
+    or 1-bit values).  Raises YaikEncodeError (.index) when the library refuses."""
+    global _last_encoder
+    import torch
+
+    from .encoder import u8_pixel_layout
+    if not hasattr(frames, "data_ptr"):
+        frames = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
+    if not frames.is_cuda:
+        raise ValueError("frames must lie in device memory (or be a numpy array, which is uploaded)")
+    lay = u8_pixel_layout(frames, batch=True)
+    L = host_lib()
+    dev = frames.device.index or 0
+    e = encoder(dev)
+    _last_encoder = e
+    failed = C.c_int32(-1)
+    torch.cuda.current_stream(frames.device).synchronize()                 # the library reads on its handle's own stream
+    ok = L.YAIK_EncodeImagesFromDevice(e, frames.data_ptr(), lay.row_bytes, lay.frame_bytes, lay.channels, lay.w, lay.rows, lay.frames,
+                                       int(bool(emit_alpha)), int(level), int(threads), C.byref(failed))
+    if not ok:
+        raise YaikEncodeError((L.YAIK_EncoderLastError(e) or b"?").decode(), failed.value)
+    out = []
+    for f in range(lay.frames):
+        data, n = C.c_void_p(), C.c_uint32()
+        if not L.YAIK_EncodedStream(e, f, C.byref(data), C.byref(n)):
+            raise YaikEncodeError((L.YAIK_EncoderLastError(e) or b"?").decode())
+        out.append(C.string_at(data.value, n.value))
+    return out
+
+
+def encode_file_device(frame, emit_alpha: bool = False, level: int = 0, threads: int = 16) -> bytes:
+    """One frame [H, W, C]: a batch of one."""
+    return encode_files_device(frame[None], emit_alpha, level, threads)[0]
+
+
+def last_encode_info() -> dict:
+    """Of the last encode_files_device: the host clocks of its stages in ms (YAIK_LastEncodeStageMs)."""
+    ms = (C.c_double * 4)()
+    if _last_encoder is not None and _last_encoder in _encoders.values():
+        host_lib().YAIK_LastEncodeStageMs(_last_encoder, ms)
+    return {"device_ms": ms[0], "gather_ms": ms[1], "entropy_ms": ms[2], "total_ms": ms[3]}

@@ -45,24 +45,34 @@ bool writeMipmap(FILE* f, const int tb[4], int mipmapLevel, const u8* bits, size
     return putChunk(f, TAG_MIPMAP, &h, sizeof h, { &payload });
 }
 
-bool writeAlpha(FILE* f, int parameters, const int bbox[4], const u8* payload, size_t nBytes, std::string& err) {
+bool compressAlphaStream(const u8* payload, size_t nBytes, int level, std::vector<u8>& z, std::string& err) {
+    if (level != 0) return zcompress(payload, nBytes, level, z, err);
     if (!yaikzstd::available()) { err = yaikzstd::lastError(); return false; }
-    std::vector<u8> z(yaikzstd::compressBound(nBytes) + 16);
+    z.resize(yaikzstd::compressBound(nBytes) + 16);
     size_t best = (size_t)-1; int bestLevel = 5;
-    for (int level = 5; level < 22; level++) {                                          // :1575-1598
-        const size_t r = yaikzstd::compress(z.data(), z.size(), payload, nBytes, level);
+    for (int lv = 5; lv < 22; lv++) {                                                   // :1575-1598
+        const size_t r = yaikzstd::compress(z.data(), z.size(), payload, nBytes, lv);
         const size_t size = r ? r : (size_t)-1;                                         // an error never wins and ends the sweep
-        if (size < best) { best = size; bestLevel = level; }
+        if (size < best) { best = size; bestLevel = lv; }
         else if (size > best || r == 0) break;
     }
     const size_t r = yaikzstd::compress(z.data(), z.size(), payload, nBytes, bestLevel);
     if (r == 0) { err = "ZSTD_compress failed"; return false; }
     z.resize(r);
+    return true;
+}
+
+bool emitAlpha(FILE* f, int parameters, const int bbox[4], size_t nBytes, const std::vector<u8>& z, std::string& err) {
     AlphaHeader h; memset(&h, 0, sizeof h);
     h.bbox.x = (s16)bbox[0]; h.bbox.y = (s16)bbox[1]; h.bbox.w = (s16)bbox[2]; h.bbox.h = (s16)bbox[3];
-    h.streamSize = (u32)r; h.expectedDecompressionSize = (u32)nBytes; h.version = 1; h.parameters = (u8)parameters;
+    h.streamSize = (u32)z.size(); h.expectedDecompressionSize = (u32)nBytes; h.version = 1; h.parameters = (u8)parameters;
     if (!putChunk(f, TAG_ALPHA, &h, sizeof h, { &z })) { err = "fwrite"; return false; }
     return true;
+}
+
+bool writeAlpha(FILE* f, int parameters, const int bbox[4], const u8* payload, size_t nBytes, std::string& err) {
+    std::vector<u8> z;
+    return compressAlphaStream(payload, nBytes, 0, z, err) && emitAlpha(f, parameters, bbox, nBytes, z, err);
 }
 
 void gradientExtent(int imgW, int imgH, int sx, int sy, const u8* bitmap, int out[4]) {

@@ -37,6 +37,10 @@ bool emitGradientTile(FILE* f, int imgW, int imgH, int tileShiftX, int tileShift
                       const std::vector<u8>& zBitmap, const std::vector<u8>& zRgb, int colorCompression, int planeBit, std::string& err);
 bool emitTile1D(FILE* f, size_t pixBytes, size_t typeBytes, const std::vector<u8>& zPix, const std::vector<u8>& zType,
                 int compressionColor, int compressionRange, std::string& err);
+// 'ALPM' in split form: compressAlphaStream at level 0 is writeAlpha's sweep (the smallest of levels 5..21 under its stopping rule), at level
+// 1..22 plain ZSTD_compress at that level; emitAlpha frames the result.  writeAlpha is these two steps back to back at level 0.
+bool compressAlphaStream(const u8* payload, size_t nBytes, int level, std::vector<u8>& out, std::string& err);
+bool emitAlpha(FILE* f, int parameters, const int bbox[4], size_t nBytes, const std::vector<u8>& zAlpha, std::string& err);
 // extent of the set bits of a swizzled gradient bitmap in pixels: {minX, minY, maxX, maxY} (:3798-3799, :4039-4042)
 void gradientExtent(int imgW, int imgH, int tileShiftX, int tileShiftY, const u8* bitmap, int out[4]);
 }
