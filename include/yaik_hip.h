@@ -484,8 +484,9 @@ int yk_decode_gradient_device(yk_ctx* c, int tileShiftX, int tileShiftY, const u
                               const uint8_t* devRgb, size_t rgbBytes, int remapRange);
 /* All 'GTIL' chunks of a file at once, streams in HBM: the same result as yk_decode_gradient_device for pass 0 .. nPasses-1 in that order
  * (first toucher of every lattice point over ALL passes in one launch, one scan, one launch popping the colours, then ONE render launch
- * in which a workgroup owns a 64x64 block of the image and walks the passes in call order: 5 launches for seven passes instead of 35 + 21 copies / clears).  Up to seven passes per
- * call and 2^25 tile slots per pass; beyond that the call runs the passes one after the other. */
+ * in which a workgroup owns a 64x64 block of the image and walks the passes in call order: one clear and 5 launches for seven passes
+ * instead of 35 launches + 21 copies / clears).  Up to seven passes per call and 2^25 tile slots per pass; beyond that the call runs the
+ * passes one after the other. */
 int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX, const int* tileShiftY, const uint8_t* const* devBitmap,
                                   const size_t* bitmapBytes, const uint8_t* const* devRgb, const size_t* rgbBytes, int remapRange);
 /* DecompressGradient4x4 with a plane subset (decoder/YAIK_Gradient.cpp:1208-1226 -> 4x4R / G / RG / B / RB / GB, :1420-2732): planeBit

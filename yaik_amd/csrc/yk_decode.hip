@@ -84,9 +84,6 @@ __global__ __launch_bounds__(1024) void yk_dec_corner_kernel(const uint32_t* __r
 // One workgroup per bitmap word.  The word's tiles are listed in LDS and the (tile, channel, row, run) items are spread over all 256
 // threads, so small tiles keep the workgroup as busy as large ones.  A thread produces a run of min(TX, 8) pixels of one row
 // and channel: in the 8x8-tiled plane layout that run is contiguous and leaves as ONE 8-byte (or 4-byte) store.
-#ifndef YK_DEC_ROWPAIR
-#define YK_DEC_ROWPAIR 0                                                     // 1: two rows per item (16-byte stores) for tiles 8 or 16 pixels wide -- measured slower (105 against 97 us at 8192 x 8192)
-#endif
 template <int NW> struct DRenderLdsN { int xy[32 * NW][2]; uint8_t c[32 * NW][3][4]; };
 typedef DRenderLdsN<1> DRenderLds;
 // the tiles of NW bitmap words (word k: index wi[k], bits bits[k]) of one pass, rendered together by the whole workgroup (256 threads)
@@ -121,53 +118,25 @@ __device__ __forceinline__ void yk_dec_render_words(DRenderLdsN<NW>& L, const ui
         L.c[k][0][q] = (uint8_t)rgb; L.c[k][1][q] = (uint8_t)(rgb >> 8); L.c[k][2][q] = (uint8_t)(rgb >> 16);
     }
     __syncthreads();
-    if (GW == 8 && YK_DEC_ROWPAIR) {
-        // tiles at least 8 pixels wide: an item = two rows of an 8-pixel run = 16 contiguous bytes of the 8x8-tiled plane (row pitch 8 inside a tile)
-        const int nEl2 = nEl >> 1, lgPer2 = lgPer - 1;
-        for (int item = threadIdx.x; item < nT * nEl2; item += 256) {
-            const int ck = item >> lgPer2, k = ck / 3, c = ck - 3 * k;           // tile of the list, channel
-            const int x = L.xy[k][0], y = L.xy[k][1];
-            if (x < 0) continue;
-            const int r = item & ((perCh >> 1) - 1), ty = (r >> lgGpr) * 2, gx = (r & (gpr - 1)) * 8;
-            const uint32_t c4 = *reinterpret_cast<const uint32_t*>(&L.c[k][c][0]);
-            const int TL = c4 & 255, TR = (c4 >> 8) & 255, BL = c4 >> 16 & 255, BR = c4 >> 24;
-            const int xx = x + gx, yy = y + ty;
-            uint32_t o4[4];
+    for (int item = threadIdx.x; item < nT * nEl; item += 256) {
+        const int ck = item >> lgPer, k = ck / 3, c = ck - 3 * k;           // tile of the list, channel
+        const int x = L.xy[k][0], y = L.xy[k][1];
+        if (x < 0) continue;
+        const int r = item & (perCh - 1), ty = r >> lgGpr, gx = (r & (gpr - 1)) * GW;
+        const uint32_t c4 = *reinterpret_cast<const uint32_t*>(&L.c[k][c][0]);
+        const int TL = c4 & 255, TR = (c4 >> 8) & 255, BL = (c4 >> 16) & 255, BR = c4 >> 24;
+        const int Lf = TL * (TY - ty) + BL * ty, R = TR * (TY - ty) + BR * ty;
+        int v = Lf * (TX - gx) + R * gx;                                    // numerator at the first pixel of the run, + (R - L) per pixel
+        const int xx = x + gx, yy = y + ty;
+        uint8_t* o = planes + (size_t)c * planeSize + ((size_t)(yy >> 3) * tileW + (xx >> 3)) * 64 + (yy & 7) * 8 + (xx & 7);
+        uint32_t lo = 0, hi = 0;
 #pragma unroll
-            for (int rr = 0; rr < 2; rr++) {
-                const int Lf = TL * (TY - ty - rr) + BL * (ty + rr), R = TR * (TY - ty - rr) + BR * (ty + rr);
-                int v = Lf * (TX - gx) + R * gx;                                  // numerator at the first pixel of the run, + (R - L) per pixel
-                uint32_t lo = 0, hi = 0;
+        for (int i = 0; i < 4; i++) { lo |= (uint32_t)((v >> sh) & 255) << (8 * i); v += R - Lf; }
+        if (GW == 8) {
 #pragma unroll
-                for (int i = 0; i < 4; i++) { lo |= (uint32_t)((v >> sh) & 255) << (8 * i); v += R - Lf; }
-#pragma unroll
-                for (int i = 0; i < 4; i++) { hi |= (uint32_t)((v >> sh) & 255) << (8 * i); v += R - Lf; }
-                o4[rr * 2] = lo; o4[rr * 2 + 1] = hi;
-            }
-            uint8_t* o = planes + (size_t)c * planeSize + ((size_t)(yy >> 3) * tileW + (xx >> 3)) * 64 + (yy & 7) * 8;
-            *reinterpret_cast<uint4*>(o) = make_uint4(o4[0], o4[1], o4[2], o4[3]);
-        }
-    } else {
-        for (int item = threadIdx.x; item < nT * nEl; item += 256) {
-            const int ck = item >> lgPer, k = ck / 3, c = ck - 3 * k;           // tile of the list, channel
-            const int x = L.xy[k][0], y = L.xy[k][1];
-            if (x < 0) continue;
-            const int r = item & (perCh - 1), ty = r >> lgGpr, gx = (r & (gpr - 1)) * GW;
-            const uint32_t c4 = *reinterpret_cast<const uint32_t*>(&L.c[k][c][0]);
-            const int TL = c4 & 255, TR = (c4 >> 8) & 255, BL = (c4 >> 16) & 255, BR = c4 >> 24;
-            const int Lf = TL * (TY - ty) + BL * ty, R = TR * (TY - ty) + BR * ty;
-            int v = Lf * (TX - gx) + R * gx;                                    // numerator at the first pixel of the run, + (R - L) per pixel
-            const int xx = x + gx, yy = y + ty;
-            uint8_t* o = planes + (size_t)c * planeSize + ((size_t)(yy >> 3) * tileW + (xx >> 3)) * 64 + (yy & 7) * 8 + (xx & 7);
-            uint32_t lo = 0, hi = 0;
-#pragma unroll
-            for (int i = 0; i < 4; i++) { lo |= (uint32_t)((v >> sh) & 255) << (8 * i); v += R - Lf; }
-            if (GW == 8) {
-#pragma unroll
-                for (int i = 0; i < 4; i++) { hi |= (uint32_t)((v >> sh) & 255) << (8 * i); v += R - Lf; }
-                *reinterpret_cast<uint2*>(o) = make_uint2(lo, hi);
-            } else *reinterpret_cast<uint32_t*>(o) = lo;
-        }
+            for (int i = 0; i < 4; i++) { hi |= (uint32_t)((v >> sh) & 255) << (8 * i); v += R - Lf; }
+            *reinterpret_cast<uint2*>(o) = make_uint2(lo, hi);
+        } else *reinterpret_cast<uint32_t*>(o) = lo;
     }
     // cell (cx,cy) -> byte (cx>>2) + (cy>>1)*stride4, bit ((cx>>1)&1)*4 + (cy&1)*2 + (cx&1)   (e.g. YAIK_Gradient.cpp:951-953).  A tile's
     // cells lie in at most two mask bytes (one per pair of cell rows; tiles are at most 4 cells wide and aligned to their size): one
@@ -202,12 +171,12 @@ __global__ __launch_bounds__(256) void yk_dec_render_kernel(const uint32_t* __re
     yk_dec_render_word(L, wi, bits, g, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4);
 }
 
-// ---- all gradient chunks of a file in one call (yk_decode_gradient_all_device): the passes share every launch except the render --------------
+// ---- all gradient chunks of a file in one call (yk_decode_gradient_all_device): the passes share every launch ---------------------------------
 // What the per-pass sequence above does pass after pass (first toucher among the lattice points no EARLIER pass loaded, count, scan, pop the
 // colours) is one first-toucher problem over all passes when the key carries the pass: owner = min(pass << 27 | bitIndex << 2 | corner), the
 // layout of yk_corners.hip on the encoder side.  Bitmap bytes (8 tile slots) of all passes are laid end to end; 1024 bytes per workgroup.
 struct DecPlan {
-    uint32_t byteStart[8], blockStart[8], wordStart[8];     // first bitmap byte / 1024-byte block / list word of pass p ([n..7] = totals)
+    uint32_t byteStart[8], blockStart[8];                   // first bitmap byte / 1024-byte block of pass p ([n..7] = totals)
     uint32_t nBytes[7], rgbBytes[7];
     const uint8_t* bm[7];
     const uint8_t* rgb[7];
@@ -279,27 +248,18 @@ __global__ __launch_bounds__(256) void yk_decall_owner_kernel(const DecPlan pl, 
     yk_decall_owner_body(pl, w, h, latW, loaded, owner, blockIdx.x);
 }
 
-// COUNT: corners owned per thread (a byte, kept for the emit launch) and per workgroup, non-empty bitmap words per workgroup.
-// EMIT: the owners pop their colours off the pass's stream (offset = scanned corners before them x 3) into the lattice; the workgroup's
-// non-empty words are appended to the pass's render list.
+// COUNT: corners owned per thread (4 bits per tile slot, kept for the emit launch) and per workgroup.
+// EMIT: the owners pop their colours off the pass's stream (offset = scanned corners before them x 3) into the lattice.
 template <bool EMIT>
 __device__ __forceinline__ void yk_decall_stream_body(const DecPlan& pl, int w, int h, int latW, uint8_t* __restrict__ loaded, const uint32_t* __restrict__ owner,
-                                                      uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, uint32_t* __restrict__ perThread,
-                                                      uint8_t* __restrict__ mapRGB, uint32_t* __restrict__ wordList, uint32_t factor, const uint32_t blk) {
+                                                      uint32_t* __restrict__ blockSums, uint32_t* __restrict__ perThread, uint8_t* __restrict__ mapRGB, uint32_t factor,
+                                                      const uint32_t blk) {
     __shared__ uint32_t s_tmp[32];
     const int pass = yk_dplan_find(pl.blockStart, blk);
     const uint32_t bi = (blk - pl.blockStart[pass]) * 1024u + threadIdx.x;
     const uint32_t nBytes = pl.nBytes[pass];
     const size_t ti = (size_t)pl.byteStart[pass] + bi;
-    const uint8_t* const bm = pl.bm[pass];
-    const uint32_t byte = bi < nBytes ? bm[bi] : 0u;
-    // a word of the bitmap is 4 consecutive bytes: its first thread speaks for it
-    bool wordSet = false;
-    if ((threadIdx.x & 3) == 0 && bi < nBytes) {
-        wordSet = byte != 0u;
-#pragma unroll
-        for (int j = 1; j < 4; j++) wordSet |= (bi + j < nBytes) && bm[bi + j] != 0;
-    }
+    const uint32_t byte = bi < nBytes ? pl.bm[pass][bi] : 0u;
     const DPassGeo g = yk_dpass_geo(pl.sx[pass], pl.sy[pass], w);
     const int dx = 1 << (g.sx - 2), dy = 1 << (g.sy - 2);
     // COUNT leaves the thread's ownership bits (4 per tile slot) for EMIT, which then neither repeats the 32 owner look-ups nor waits for them
@@ -336,17 +296,14 @@ __device__ __forceinline__ void yk_decall_stream_body(const DecPlan& pl, int w, 
     if (!EMIT) {
 #pragma unroll
         for (int k = 0; k < 8; k++) { cnt += (uint32_t)__popc(own[k]); ownBits |= own[k] << (4 * k); }
-        uint32_t tot, totW;
+        uint32_t tot;
         yk_block_exscan(cnt, s_tmp, &tot);
-        yk_block_exscan(wordSet ? 1u : 0u, s_tmp, &totW);
         if (bi < nBytes) perThread[ti] = ownBits;
-        if (threadIdx.x == 0) { blockSums[blk] = tot; blockWords[blk] = totW; }
+        if (threadIdx.x == 0) blockSums[blk] = tot;
         return;
     }
-    uint32_t tot, totW;
+    uint32_t tot;
     const uint32_t ex = yk_block_exscan(cnt, s_tmp, &tot);
-    const uint32_t exW = yk_block_exscan(wordSet ? 1u : 0u, s_tmp, &totW);
-    if (wordSet) wordList[pl.wordStart[pass] + (blockWords[blk] - blockWords[pl.blockStart[pass]]) + exW] = bi >> 2;
     constexpr uint32_t kCap = 8192;                                          // colours listed per workgroup
     __shared__ uint32_t s_li[kCap];
     const uint32_t blockOff = (blockSums[blk] - blockSums[pl.blockStart[pass]]) * 3u;
@@ -384,54 +341,25 @@ __device__ __forceinline__ void yk_decall_stream_body(const DecPlan& pl, int w, 
 
 template <bool EMIT>
 __global__ __launch_bounds__(1024) void yk_decall_stream_kernel(const DecPlan pl, int w, int h, int latW, uint8_t* __restrict__ loaded, const uint32_t* __restrict__ owner,
-                                                                uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, uint32_t* __restrict__ perThread,
-                                                                uint8_t* __restrict__ mapRGB, uint32_t* __restrict__ wordList, uint32_t factor) {
-    yk_decall_stream_body<EMIT>(pl, w, h, latW, loaded, owner, blockSums, blockWords, perThread, mapRGB, wordList, factor, blockIdx.x);
+                                                                uint32_t* __restrict__ blockSums, uint32_t* __restrict__ perThread, uint8_t* __restrict__ mapRGB,
+                                                                uint32_t factor) {
+    yk_decall_stream_body<EMIT>(pl, w, h, latW, loaded, owner, blockSums, perThread, mapRGB, factor, blockIdx.x);
 }
 
-// exclusive prefixes of both per-block arrays in place (one workgroup: thread t owns a run of consecutive blocks), words listed per pass
-__device__ __forceinline__ void yk_decall_scan_body(uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, const DecPlan& pl, uint32_t* __restrict__ passWords) {
+// exclusive prefix of the per-block corner counts in place (one workgroup: thread t owns a run of consecutive blocks)
+__device__ __forceinline__ void yk_decall_scan_body(uint32_t* __restrict__ blockSums, const DecPlan& pl) {
     __shared__ uint32_t s_tmp[32];
-    __shared__ uint32_t s_totalW;
     const uint32_t n = pl.blockStart[7], per = (n + 1023) / 1024;
     const uint32_t a = min(threadIdx.x * per, n), b = min(a + per, n);
-    uint32_t sum = 0, sumW = 0;
-    for (uint32_t i = a; i < b; i++) { sum += blockSums[i]; sumW += blockWords[i]; }
-    uint32_t tot, totW;
+    uint32_t sum = 0;
+    for (uint32_t i = a; i < b; i++) sum += blockSums[i];
+    uint32_t tot;
     uint32_t run = yk_block_exscan(sum, s_tmp, &tot);
-    uint32_t runW = yk_block_exscan(sumW, s_tmp, &totW);
-    for (uint32_t i = a; i < b; i++) {
-        const uint32_t v = blockSums[i], vw = blockWords[i];
-        blockSums[i] = run; run += v; blockWords[i] = runW; runW += vw;
-    }
-    if (threadIdx.x == 0) s_totalW = totW;
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const uint32_t lo = pl.blockStart[threadIdx.x] < n ? blockWords[pl.blockStart[threadIdx.x]] : s_totalW;
-        const uint32_t hi = pl.blockStart[threadIdx.x + 1] < n ? blockWords[pl.blockStart[threadIdx.x + 1]] : s_totalW;
-        passWords[threadIdx.x] = hi - lo;
-    }
+    for (uint32_t i = a; i < b; i++) { const uint32_t v = blockSums[i]; blockSums[i] = run; run += v; }
 }
 
-__global__ __launch_bounds__(1024) void yk_decall_scan_kernel(uint32_t* __restrict__ blockSums, uint32_t* __restrict__ blockWords, const DecPlan pl, uint32_t* __restrict__ passWords) {
-    yk_decall_scan_body(blockSums, blockWords, pl, passWords);
-}
-
-// render of one pass from its list of non-empty bitmap words (a launch over every word of a sparse map is mostly workgroups that start and
-// leave: 336 k of them over the seven passes of an 8192 x 8192 frame)
-__global__ __launch_bounds__(256) void yk_decall_render_kernel(const uint8_t* __restrict__ bm, uint32_t nBytes, const uint32_t* __restrict__ wordList, const uint32_t* __restrict__ nListed,
-                                                               DPassGeo g, int w, int h, int latW, const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes,
-                                                               size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4) {
-    __shared__ DRenderLds L;
-    const uint32_t n = *nListed;
-    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-        const uint32_t wi = wordList[i], b0 = wi * 4u;
-        uint32_t bits = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) if (b0 + j < nBytes) bits |= (uint32_t)bm[b0 + j] << (8 * j);
-        yk_dec_render_word(L, wi, bits, g, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4);
-        __syncthreads();
-    }
+__global__ __launch_bounds__(1024) void yk_decall_scan_kernel(uint32_t* __restrict__ blockSums, const DecPlan pl) {
+    yk_decall_scan_body(blockSums, pl);
 }
 
 // ONE render launch for all passes: a workgroup owns a 64x64 block of the image and walks the passes in call order, rendering the tiles of the
@@ -487,15 +415,15 @@ __global__ __launch_bounds__(256) void yk_decall_render_blocks_kernel(const DecP
 }
 
 // ---- the same five launches over a batch: frame = blockIdx.y -------------------------------------------------------------------------------
-// Every frame of a batch has the shape of every other, so byteStart / blockStart / wordStart, the grids and the scratch layout are those of one
-// image; the frames differ in their stream pointers and colour-stream lengths.  A DecPlan is 328 bytes: up to 1024 of them do not fit kernel
+// Every frame of a batch has the shape of every other, so byteStart / blockStart, the grids and the scratch layout are those of one
+// image; the frames differ in their stream pointers and colour-stream lengths.  A DecPlan is 296 bytes: up to 1024 of them do not fit kernel
 // arguments, so the call writes them once into a table in HBM and a workgroup reads its frame's plan through scalar loads (uniform address).
 // Frame f's arrays lie at base + f * stride (bytes), its scratch arrays at scratch + f * sScratch + the offsets of the single-image call.
 struct DecBatch {
     const DecPlan* plans;
     uint8_t* loaded; uint8_t* owner; uint8_t* mapRGB; uint8_t* planes; uint8_t* tile4; uint8_t* scratch;
     size_t sLoaded, sOwner, sMapRGB, sPlanes, sTile4, sScratch;
-    size_t oSums, oWords, oPassWords, oPerThread, oList;
+    size_t oSums, oPerThread;
 };
 __device__ __forceinline__ uint32_t* yk_dbatch_u32(const DecBatch& B, size_t f, size_t off) { return reinterpret_cast<uint32_t*>(B.scratch + f * B.sScratch + off); }
 
@@ -507,11 +435,11 @@ template <bool EMIT>
 __global__ __launch_bounds__(1024) void yk_decall_stream_batch_kernel(const DecBatch B, int w, int h, int latW, uint32_t factor) {
     const size_t f = blockIdx.y;
     yk_decall_stream_body<EMIT>(B.plans[f], w, h, latW, B.loaded + f * B.sLoaded, reinterpret_cast<const uint32_t*>(B.owner + f * B.sOwner), yk_dbatch_u32(B, f, B.oSums),
-                                yk_dbatch_u32(B, f, B.oWords), yk_dbatch_u32(B, f, B.oPerThread), B.mapRGB + f * B.sMapRGB, yk_dbatch_u32(B, f, B.oList), factor, blockIdx.x);
+                                yk_dbatch_u32(B, f, B.oPerThread), B.mapRGB + f * B.sMapRGB, factor, blockIdx.x);
 }
 __global__ __launch_bounds__(1024) void yk_decall_scan_batch_kernel(const DecBatch B) {       // one workgroup per frame
     const size_t f = blockIdx.x;
-    yk_decall_scan_body(yk_dbatch_u32(B, f, B.oSums), yk_dbatch_u32(B, f, B.oWords), B.plans[f], yk_dbatch_u32(B, f, B.oPassWords));
+    yk_decall_scan_body(yk_dbatch_u32(B, f, B.oSums), B.plans[f]);
 }
 __global__ __launch_bounds__(256) void yk_decall_render_blocks_batch_kernel(const DecBatch B, int w, int h, int latW, size_t planeSize, int tileW, int stride4) {
     const size_t f = blockIdx.y;
@@ -1127,47 +1055,77 @@ int yk_dec_table_upload(yk_ctx* c, int slot, void* dev, size_t bytes) {
 }
 
 // PaletteFullRangeRemapping (decoder/YAIK_GenericFunctions.cpp:128-137) of a corner stream that is still in HBM: v * ((255 << 16) / range) >> 16
+static uint32_t yk_dec_remap_factor(int remapRange) { return remapRange > 0 ? (uint32_t)((255u << 16) / (uint32_t)remapRange) : 0u; }
 __global__ void yk_dec_remap_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t n, uint32_t factor) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = (uint8_t)(((uint32_t)src[i] * factor) >> 16);
+}
+
+// ---- what the gradient entry points share; the checks and their messages stay with the callers ---------------------------------------------
+// length in bytes of the tile bitmap of a (sx, sy) pass over a w x h image; 0: not one of the seven tile formats 16x16 .. 4x4 (sides 1:1, 2:1 or 1:2)
+static size_t yk_dpass_bytes(int sx, int sy, int w, int h) {
+    if (sx < 2 || sx > 4 || sy < 2 || sy > 4 || sx - sy > 1 || sy - sx > 1) return 0;
+    const DPassGeo g = yk_dpass_geo(sx, sy, w);
+    return ((size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount) >> 3;
+}
+// the first-toucher key of the all-passes kernels is pass << 27 | tile slot << 2 | corner: a pass has to stay below 2^25 tile slots
+static bool yk_dpass_fits_key(size_t need) { return need * 8 < ((size_t)1 << 25); }
+// the part of a (zeroed) DecPlan that the shape of the image and the order of the passes decide; passes past nPasses are empty 16x16 ones
+static void yk_dplan_shape(DecPlan& pl, int nPasses, const int* sx, const int* sy, const size_t* need) {
+    pl.n = nPasses;
+    for (int p = 0; p < 7; p++) {
+        const size_t nb = p < nPasses ? need[p] : 0;
+        pl.nBytes[p] = (uint32_t)nb;
+        pl.sx[p] = p < nPasses ? sx[p] : 4; pl.sy[p] = p < nPasses ? sy[p] : 4;
+        pl.byteStart[p + 1] = pl.byteStart[p] + (uint32_t)nb;
+        pl.blockStart[p + 1] = pl.blockStart[p] + (uint32_t)((nb + 1023) / 1024);
+    }
+}
+// scratch of one frame of an all-passes call: [corners per 1024-byte block | ownership bits per bitmap byte (one word)], a multiple of 16 bytes
+struct DecAllScratch { size_t oSums, oPerThread, bytes; };
+static DecAllScratch yk_decall_scratch(const DecPlan& pl) {
+    const size_t oPerThread = (size_t)pl.blockStart[7] * 4;
+    return { 0, oPerThread, (oPerThread + (size_t)pl.byteStart[7] * 4 + 15) & ~(size_t)15 };
+}
+// the inputs of the per-pass kernels in scratch, [bitmap, padded to whole words][colours][corners per block of 1024 tile slots][total]: the bitmap
+// behind a clear of its last word, the colours copied or (remapRange > 0, a stream in HBM) remapped on the way; the owner lattice is cleared
+struct DPassIn { size_t nWords, nBits, nb; const uint32_t* bm; const uint8_t* rgb; uint32_t* blockSums; uint32_t* total; };
+static hipError_t yk_dpass_stage(yk_ctx* c, const uint8_t* bitmap, size_t need, const uint8_t* rgb, size_t rgbBytes, hipMemcpyKind kind, int remapRange, DPassIn* in) {
+    const size_t nWords = (need + 3) / 4, nBits = need * 8, nb = (nBits + 1023) / 1024;
+    const size_t oB = 0, oR = oB + nWords * 4 + 16, oBB = (oR + rgbBytes + 19) & ~(size_t)15, oT = oBB + nb * 4 + 16;
+    hipError_t e = c->dScratch.reserve(c->stream, oT + 64);
+    uint8_t* S = c->dScratch;
+    if (e == hipSuccess) e = hipMemsetAsync(S + oB, 0, nWords * 4, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(S + oB, bitmap, need, kind, c->stream);
+    if (e == hipSuccess && rgbBytes) {
+        if (remapRange > 0)
+            hipLaunchKernelGGL(yk_dec_remap_kernel, dim3((unsigned)((rgbBytes + 255) / 256 < 1024 ? (rgbBytes + 255) / 256 : 1024)), dim3(256), 0, c->stream,
+                               rgb, S + oR, rgbBytes, yk_dec_remap_factor(remapRange));
+        else e = hipMemcpyAsync(S + oR, rgb, rgbBytes, kind, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(c->dLatticeOwner, 0xFF, (size_t)(c->dw / 4 + 1) * (c->dh / 4 + 1) * 4, c->stream);
+    *in = { nWords, nBits, nb, reinterpret_cast<const uint32_t*>(S + oB), S + oR, reinterpret_cast<uint32_t*>(S + oBB), reinterpret_cast<uint32_t*>(S + oT) };
+    return e;
 }
 
 static int yk_decode_gradient_impl(yk_ctx* c, int sx, int sy, const uint8_t* bitmap, size_t bitmapBytes, const uint8_t* rgb, size_t rgbBytes, bool onDevice, int remapRange) {
     if (!c || !bitmap) return YK_ERR_BAD_ARG;
     if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
-    static const int ok[7][2] = { {4,4},{4,3},{3,4},{3,3},{3,2},{2,3},{2,2} };
-    bool found = false; for (auto& o : ok) found |= (o[0] == sx && o[1] == sy);
-    if (!found) return yk_fail(c, YK_ERR_BAD_ARG, "unsupported tile format");
-    YK_HIP(c, hipSetDevice(c->device));
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
-    const size_t lat = (size_t)latW * (h / 4 + 1);
-    const DPassGeo g = yk_dpass_geo(sx, sy, w);
-    const size_t need = ((size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount) >> 3;
+    const size_t need = yk_dpass_bytes(sx, sy, w, h);
+    if (!need) return yk_fail(c, YK_ERR_BAD_ARG, "unsupported tile format");
+    YK_HIP(c, hipSetDevice(c->device));
     if (bitmapBytes < need) return yk_fail(c, YK_ERR_RANGE, "tile bitmap shorter than the image needs");
-    const size_t nWords = (need + 3) / 4, nBits = need * 8, nb = (nBits + 1023) / 1024;
-    // scratch: [bitmap words][rgb][blockSums][total]
-    const size_t oB = 0, oR = oB + nWords * 4 + 16, oBB = (oR + rgbBytes + 19) & ~(size_t)15, oT = oBB + nb * 4 + 16;
-    int rc = yk_dec_scratch(c, oT + 64); if (rc) return rc;
-    uint8_t* S = c->dScratch;
-    YK_HIP(c, hipMemsetAsync(S + oB, 0, nWords * 4, c->stream));
-    YK_HIP(c, hipMemcpyAsync(S + oB, bitmap, need, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    if (rgbBytes) {
-        if (onDevice && remapRange > 0)
-            hipLaunchKernelGGL(yk_dec_remap_kernel, dim3((unsigned)((rgbBytes + 255) / 256 < 1024 ? (rgbBytes + 255) / 256 : 1024)), dim3(256), 0, c->stream,
-                               rgb, S + oR, rgbBytes, (uint32_t)((255u << 16) / (uint32_t)remapRange));
-        else YK_HIP(c, hipMemcpyAsync(S + oR, rgb, rgbBytes, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    }
-    YK_HIP(c, hipMemsetAsync(c->dLatticeOwner, 0xFF, lat * 4, c->stream));
-    const uint32_t* bm = reinterpret_cast<const uint32_t*>(S + oB);
-    uint32_t* blockSums = reinterpret_cast<uint32_t*>(S + oBB);
-    uint32_t* total = reinterpret_cast<uint32_t*>(S + oT);
+    const DPassGeo g = yk_dpass_geo(sx, sy, w);
+    DPassIn in;
+    YK_HIP(c, yk_dpass_stage(c, bitmap, need, rgb, rgbBytes, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, onDevice ? remapRange : 0, &in));
     { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
-    hipLaunchKernelGGL(yk_dec_owner_kernel, dim3((unsigned)((nBits + 255) / 256)), dim3(256), 0, c->stream, bm, nBits, g, w, h, latW, c->dLoaded, c->dLatticeOwner);
-    hipLaunchKernelGGL(yk_dec_corner_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, c->stream, bm, nBits, g, w, h, latW, c->dLoaded, c->dLatticeOwner,
-                       blockSums, (const uint8_t*)nullptr, (size_t)0, (uint8_t*)nullptr);
-    hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, (int)nb, total);
-    hipLaunchKernelGGL(yk_dec_corner_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, c->stream, bm, nBits, g, w, h, latW, c->dLoaded, c->dLatticeOwner,
-                       blockSums, S + oR, rgbBytes, c->dMapRGB);
-    hipLaunchKernelGGL(yk_dec_render_kernel, dim3((unsigned)nWords), dim3(256), 0, c->stream, bm, nWords, g, w, h, latW, c->dMapRGB, c->dPlanes, c->dPlaneSize,
+    hipLaunchKernelGGL(yk_dec_owner_kernel, dim3((unsigned)((in.nBits + 255) / 256)), dim3(256), 0, c->stream, in.bm, in.nBits, g, w, h, latW, c->dLoaded, c->dLatticeOwner);
+    hipLaunchKernelGGL(yk_dec_corner_kernel<false>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, g, w, h, latW, c->dLoaded, c->dLatticeOwner,
+                       in.blockSums, (const uint8_t*)nullptr, (size_t)0, (uint8_t*)nullptr);
+    hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, in.blockSums, (int)in.nb, in.total);
+    hipLaunchKernelGGL(yk_dec_corner_kernel<true>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, g, w, h, latW, c->dLoaded, c->dLatticeOwner,
+                       in.blockSums, in.rgb, rgbBytes, c->dMapRGB);
+    hipLaunchKernelGGL(yk_dec_render_kernel, dim3((unsigned)in.nWords), dim3(256), 0, c->stream, in.bm, in.nWords, g, w, h, latW, c->dMapRGB, c->dPlanes, c->dPlaneSize,
                        w >> 3, reinterpret_cast<uint32_t*>(c->dTile4), (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
     { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
@@ -1190,18 +1148,16 @@ int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX,
     if (nPasses == 0) return YK_OK;
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
     const size_t lat = (size_t)latW * (h / 4 + 1);
-    static const int ok[7][2] = { {4,4},{4,3},{3,4},{3,3},{3,2},{2,3},{2,2} };
     bool oneCall = nPasses <= 7;
     size_t need[7] = {};
     for (int p = 0; p < nPasses; p++) {
-        bool found = false; for (auto& o : ok) found |= (o[0] == tileShiftX[p] && o[1] == tileShiftY[p]);
-        if (!found) return yk_fail(c, YK_ERR_BAD_ARG, "unsupported tile format");
+        const size_t n = yk_dpass_bytes(tileShiftX[p], tileShiftY[p], w, h);
+        if (!n) return yk_fail(c, YK_ERR_BAD_ARG, "unsupported tile format");
         if (!devBitmap[p] || (rgbBytes[p] && !devRgb[p])) return yk_fail(c, YK_ERR_BAD_ARG, "NULL tile bitmap, or NULL colour stream with a length");
-        if (p < 7) {
-            const DPassGeo g = yk_dpass_geo(tileShiftX[p], tileShiftY[p], w);
-            need[p] = ((size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount) >> 3;
-            if (bitmapBytes[p] < need[p]) return yk_fail(c, YK_ERR_RANGE, "tile bitmap shorter than the image needs");
-            if (need[p] * 8 >= ((size_t)1 << 25) || rgbBytes[p] > 0xFFFFFFFFu) oneCall = false;      // the key holds 25 bits of tile position
+        if (p < 7) {                                                         // a later chunk is checked by its own pass-after-pass call
+            need[p] = n;
+            if (bitmapBytes[p] < n) return yk_fail(c, YK_ERR_RANGE, "tile bitmap shorter than the image needs");
+            if (!yk_dpass_fits_key(n) || rgbBytes[p] > 0xFFFFFFFFu) oneCall = false;
         }
     }
     if (!oneCall) {                                                          // very large images / more than seven chunks: pass after pass
@@ -1213,37 +1169,23 @@ int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX,
     }
     YK_HIP(c, hipSetDevice(c->device));
     DecPlan pl = {};
-    pl.n = nPasses;
-    for (int p = 0; p < 7; p++) {
-        const size_t nb = p < nPasses ? need[p] : 0;
-        pl.nBytes[p] = (uint32_t)nb; pl.rgbBytes[p] = p < nPasses ? (uint32_t)rgbBytes[p] : 0u;
-        pl.bm[p] = p < nPasses ? devBitmap[p] : nullptr; pl.rgb[p] = p < nPasses ? devRgb[p] : nullptr;
-        pl.sx[p] = p < nPasses ? tileShiftX[p] : 4; pl.sy[p] = p < nPasses ? tileShiftY[p] : 4;
-        pl.byteStart[p + 1] = pl.byteStart[p] + (uint32_t)nb;
-        pl.blockStart[p + 1] = pl.blockStart[p] + (uint32_t)((nb + 1023) / 1024);
-        pl.wordStart[p + 1] = pl.wordStart[p] + (uint32_t)((nb + 3) / 4);
-    }
-    const size_t nbTot = pl.blockStart[7], nBytesTot = pl.byteStart[7], nWordsTot = pl.wordStart[7];
-    // scratch: [corners per block | words per block | words listed per pass | ownership bits per bitmap byte (one word) | render lists]
-    const size_t oS = 0, oW = oS + nbTot * 4, oP = oW + nbTot * 4, oT = oP + 64, oL = (oT + nBytesTot * 4 + 15) & ~(size_t)15;
-    { const int rc = yk_dec_scratch(c, oL + nWordsTot * 4 + 64); if (rc) return rc; }
-    uint8_t* S = c->dScratch;
-    uint32_t* blockSums = reinterpret_cast<uint32_t*>(S + oS);
-    uint32_t* blockWords = reinterpret_cast<uint32_t*>(S + oW);
-    uint32_t* passWords = reinterpret_cast<uint32_t*>(S + oP);
-    uint32_t* perThread = reinterpret_cast<uint32_t*>(S + oT);
-    uint32_t* wordList = reinterpret_cast<uint32_t*>(S + oL);
-    const uint32_t factor = remapRange > 0 ? (uint32_t)((255u << 16) / (uint32_t)remapRange) : 0u;
+    yk_dplan_shape(pl, nPasses, tileShiftX, tileShiftY, need);
+    for (int p = 0; p < nPasses; p++) { pl.bm[p] = devBitmap[p]; pl.rgb[p] = devRgb[p]; pl.rgbBytes[p] = (uint32_t)rgbBytes[p]; }
+    const size_t nbTot = pl.blockStart[7], nBytesTot = pl.byteStart[7];
+    const DecAllScratch L = yk_decall_scratch(pl);
+    { const int rc = yk_dec_scratch(c, L.bytes); if (rc) return rc; }
+    uint32_t* blockSums = reinterpret_cast<uint32_t*>(c->dScratch + L.oSums);
+    uint32_t* perThread = reinterpret_cast<uint32_t*>(c->dScratch + L.oPerThread);
     YK_HIP(c, hipMemsetAsync(c->dLatticeOwner, 0xFF, lat * 4, c->stream));
     { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
-    // 1 clear + 4 launches for all passes + one render per pass (the per-pass form: 3 copies / clears + 5 launches per pass)
+    // 1 clear + 5 launches for all passes (the per-pass form: 3 copies / clears + 5 launches per pass)
     hipLaunchKernelGGL(yk_decall_owner_kernel, dim3((unsigned)((nBytesTot + 255) / 256)), dim3(256), 0, c->stream, pl, w, h, latW, c->dLoaded, c->dLatticeOwner);
-    hipLaunchKernelGGL(yk_decall_stream_kernel<false>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, c->dLoaded, c->dLatticeOwner, blockSums, blockWords,
-                       perThread, (uint8_t*)nullptr, (uint32_t*)nullptr, 0u);
-    hipLaunchKernelGGL(yk_decall_scan_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, blockWords, pl, passWords);
-    hipLaunchKernelGGL(yk_decall_stream_kernel<true>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, c->dLoaded, c->dLatticeOwner, blockSums, blockWords,
-                       perThread, c->dMapRGB, wordList, factor);
-    // one render launch: a workgroup per 64x64 block of the image walks the passes in call order
+    hipLaunchKernelGGL(yk_decall_stream_kernel<false>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, c->dLoaded, c->dLatticeOwner, blockSums, perThread,
+                       (uint8_t*)nullptr, 0u);
+    hipLaunchKernelGGL(yk_decall_scan_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, pl);
+    hipLaunchKernelGGL(yk_decall_stream_kernel<true>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, c->dLoaded, c->dLatticeOwner, blockSums, perThread,
+                       c->dMapRGB, yk_dec_remap_factor(remapRange));
+    // the render: a workgroup per 64x64 block of the image walks the passes in call order
     hipLaunchKernelGGL(yk_decall_render_blocks_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64))), dim3(256), 0, c->stream, pl, w, h, latW,
                        c->dMapRGB, c->dPlanes, c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(c->dTile4), (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
@@ -1260,14 +1202,10 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
     if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
     if (nPasses == 0) return YK_OK;
     const int w = c->dw, h = c->dh, latW = w / 4 + 1, N = c->dFrames;
-    static const int ok[7][2] = { {4,4},{4,3},{3,4},{3,3},{3,2},{2,3},{2,2} };
     size_t need[7] = {};
     for (int p = 0; p < nPasses; p++) {
-        bool found = false; for (auto& o : ok) found |= (o[0] == tileShiftX[p] && o[1] == tileShiftY[p]);
-        if (!found) return yk_refuse(c, YK_ERR_BAD_ARG, "unsupported tile format");
-        const DPassGeo g = yk_dpass_geo(tileShiftX[p], tileShiftY[p], w);
-        need[p] = ((size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount) >> 3;
-        if (need[p] * 8 >= ((size_t)1 << 25)) return yk_refuse(c, YK_ERR_BAD_ARG, "a pass of 2^25 tile slots or more does not fit a batch (decode such images one by one)");
+        if (!(need[p] = yk_dpass_bytes(tileShiftX[p], tileShiftY[p], w, h))) return yk_refuse(c, YK_ERR_BAD_ARG, "unsupported tile format");
+        if (!yk_dpass_fits_key(need[p])) return yk_refuse(c, YK_ERR_BAD_ARG, "a pass of 2^25 tile slots or more does not fit a batch (decode such images one by one)");
         if (bitmapBytes[p] < need[p]) return yk_refuse(c, YK_ERR_RANGE, "tile bitmap shorter than the image needs");
     }
     for (size_t i = 0; i < (size_t)N * nPasses; i++) {
@@ -1277,21 +1215,12 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
     }
     YK_HIP(c, hipSetDevice(c->device));
     DecPlan pl = {};                                                          // what the frames share: the geometry
-    pl.n = nPasses;
-    for (int p = 0; p < 7; p++) {
-        const size_t nb = p < nPasses ? need[p] : 0;
-        pl.nBytes[p] = (uint32_t)nb;
-        pl.sx[p] = p < nPasses ? tileShiftX[p] : 4; pl.sy[p] = p < nPasses ? tileShiftY[p] : 4;
-        pl.byteStart[p + 1] = pl.byteStart[p] + (uint32_t)nb;
-        pl.blockStart[p + 1] = pl.blockStart[p] + (uint32_t)((nb + 1023) / 1024);
-        pl.wordStart[p + 1] = pl.wordStart[p] + (uint32_t)((nb + 3) / 4);
-    }
-    const size_t nbTot = pl.blockStart[7], nBytesTot = pl.byteStart[7], nWordsTot = pl.wordStart[7];
+    yk_dplan_shape(pl, nPasses, tileShiftX, tileShiftY, need);
+    const size_t nbTot = pl.blockStart[7], nBytesTot = pl.byteStart[7];
     // scratch: [plan table] then per frame, at a fixed stride, the arrays of yk_decode_gradient_all_device
     const size_t tabBytes = ((size_t)N * sizeof(DecPlan) + 255) & ~(size_t)255;
-    const size_t oS = 0, oW = oS + nbTot * 4, oP = oW + nbTot * 4, oT = oP + 64, oL = (oT + nBytesTot * 4 + 15) & ~(size_t)15;
-    const size_t sS = (oL + nWordsTot * 4 + 64 + 15) & ~(size_t)15;
-    { const int rc = yk_dec_scratch(c, tabBytes + (size_t)N * sS); if (rc) return rc; }
+    const DecAllScratch L = yk_decall_scratch(pl);
+    { const int rc = yk_dec_scratch(c, tabBytes + (size_t)N * L.bytes); if (rc) return rc; }
     int slot; void* host;
     { const int rc = yk_dec_table_host(c, (size_t)N * sizeof(DecPlan), &slot, &host); if (rc) return rc; }
     DecPlan* tab = static_cast<DecPlan*>(host);
@@ -1307,16 +1236,15 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
     B.plans = reinterpret_cast<const DecPlan*>(c->dScratch.p);
     B.loaded = c->dB.loaded; B.owner = reinterpret_cast<uint8_t*>(c->dB.owner); B.mapRGB = c->dB.mapRGB; B.planes = c->dB.planes; B.tile4 = c->dB.tile4;
     B.scratch = c->dScratch + tabBytes;
-    B.sLoaded = c->dStride.loaded; B.sOwner = c->dStride.owner; B.sMapRGB = c->dStride.mapRGB; B.sPlanes = c->dStride.planes; B.sTile4 = c->dStride.tile4; B.sScratch = sS;
-    B.oSums = oS; B.oWords = oW; B.oPassWords = oP; B.oPerThread = oT; B.oList = oL;
-    const uint32_t factor = remapRange > 0 ? (uint32_t)((255u << 16) / (uint32_t)remapRange) : 0u;
+    B.sLoaded = c->dStride.loaded; B.sOwner = c->dStride.owner; B.sMapRGB = c->dStride.mapRGB; B.sPlanes = c->dStride.planes; B.sTile4 = c->dStride.tile4; B.sScratch = L.bytes;
+    B.oSums = L.oSums; B.oPerThread = L.oPerThread;
     const unsigned F = (unsigned)N;
     YK_HIP(c, hipMemsetAsync(c->dB.owner, 0xFF, c->dStride.owner * (size_t)N, c->stream));
     { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
     hipLaunchKernelGGL(yk_decall_owner_batch_kernel, dim3((unsigned)((nBytesTot + 255) / 256), F), dim3(256), 0, c->stream, B, w, h, latW);
     hipLaunchKernelGGL(yk_decall_stream_batch_kernel<false>, dim3((unsigned)nbTot, F), dim3(1024), 0, c->stream, B, w, h, latW, 0u);
     hipLaunchKernelGGL(yk_decall_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, B);
-    hipLaunchKernelGGL(yk_decall_stream_batch_kernel<true>, dim3((unsigned)nbTot, F), dim3(1024), 0, c->stream, B, w, h, latW, factor);
+    hipLaunchKernelGGL(yk_decall_stream_batch_kernel<true>, dim3((unsigned)nbTot, F), dim3(1024), 0, c->stream, B, w, h, latW, yk_dec_remap_factor(remapRange));
     hipLaunchKernelGGL(yk_decall_render_blocks_batch_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64)), F), dim3(256), 0, c->stream, B, w, h, latW,
                        c->dPlaneSize, w >> 3, (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
@@ -1351,29 +1279,20 @@ int yk_decode_gradient_planes(yk_ctx* c, int planeBit, int consistentMarks, cons
     { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }               // the plane-subset loops write without marking (reference behaviour): from here on the planes are fully defined
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
     const size_t lat = (size_t)latW * (h / 4 + 1);
-    const size_t need = ((size_t)((w + 31) / 32) * ((h + 31) / 32) * 64) >> 3;
+    const size_t need = yk_dpass_bytes(2, 2, w, h);                          // 4x4 tiles
     if (bitmapBytes < need) return yk_fail(c, YK_ERR_RANGE, "tile bitmap shorter than the image needs");
-    const size_t nWords = (need + 3) / 4, nBits = need * 8, nb = (nBits + 1023) / 1024;
-    const size_t oB = 0, oR = oB + nWords * 4 + 16, oBB = (oR + rgbBytes + 19) & ~(size_t)15, oT = oBB + nb * 4 + 16;
-    int rc = yk_dec_scratch(c, oT + 64); if (rc) return rc;
-    rc = yk_dec_split(c); if (rc) return rc;                                 // a chunk whose plane field is not 7 splits the masks first (:875-877)
-    uint8_t* S = c->dScratch;
-    YK_HIP(c, hipMemsetAsync(S + oB, 0, nWords * 4, c->stream));
-    YK_HIP(c, hipMemcpyAsync(S + oB, bitmap, need, hipMemcpyHostToDevice, c->stream));
-    if (rgbBytes) YK_HIP(c, hipMemcpyAsync(S + oR, rgb, rgbBytes, hipMemcpyHostToDevice, c->stream));
-    YK_HIP(c, hipMemsetAsync(c->dLatticeOwner, 0xFF, lat * 4, c->stream));
-    const uint32_t* bm = reinterpret_cast<const uint32_t*>(S + oB);
-    uint32_t* blockSums = reinterpret_cast<uint32_t*>(S + oBB);
-    uint32_t* total = reinterpret_cast<uint32_t*>(S + oT);
-    const unsigned g256 = (unsigned)((nBits + 255) / 256);
-    hipLaunchKernelGGL(yk_dec44p_owner_kernel, dim3(g256), dim3(256), 0, c->stream, bm, nBits, w, h, latW, planeBit, c->dLoaded, c->dLatticeOwner);
-    hipLaunchKernelGGL(yk_dec44p_corner_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, c->stream, bm, nBits, w, h, latW, planeBit, c->dLoaded, c->dLatticeOwner,
-                       blockSums, (const uint8_t*)nullptr, (size_t)0, (uint8_t*)nullptr);
-    hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, (int)nb, total);
-    hipLaunchKernelGGL(yk_dec44p_corner_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, c->stream, bm, nBits, w, h, latW, planeBit, c->dLoaded, c->dLatticeOwner,
-                       blockSums, S + oR, rgbBytes, c->dMapRGB);
+    { const int rc = yk_dec_split(c); if (rc) return rc; }                   // a chunk whose plane field is not 7 splits the masks first (:875-877)
+    DPassIn in;
+    YK_HIP(c, yk_dpass_stage(c, bitmap, need, rgb, rgbBytes, hipMemcpyHostToDevice, 0, &in));
+    const unsigned g256 = (unsigned)((in.nBits + 255) / 256);
+    hipLaunchKernelGGL(yk_dec44p_owner_kernel, dim3(g256), dim3(256), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, c->dLoaded, c->dLatticeOwner);
+    hipLaunchKernelGGL(yk_dec44p_corner_kernel<false>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, c->dLoaded, c->dLatticeOwner,
+                       in.blockSums, (const uint8_t*)nullptr, (size_t)0, (uint8_t*)nullptr);
+    hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, in.blockSums, (int)in.nb, in.total);
+    hipLaunchKernelGGL(yk_dec44p_corner_kernel<true>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, c->dLoaded, c->dLatticeOwner,
+                       in.blockSums, in.rgb, rgbBytes, c->dMapRGB);
     hipLaunchKernelGGL(yk_dec44p_mark_kernel, dim3((unsigned)((lat + 255) / 256)), dim3(256), 0, c->stream, c->dLatticeOwner, lat, planeBit, c->dLoaded);
-    hipLaunchKernelGGL(yk_dec44p_render_kernel, dim3(g256), dim3(256), 0, c->stream, bm, nBits, w, h, latW, planeBit, consistentMarks, c->dMapRGB, c->dPlanes,
+    hipLaunchKernelGGL(yk_dec44p_render_kernel, dim3(g256), dim3(256), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, consistentMarks, c->dMapRGB, c->dPlanes,
                        c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(c->dTile4), c->dTile4Size, (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
     YK_HIP(c, hipStreamSynchronize(c->stream));
