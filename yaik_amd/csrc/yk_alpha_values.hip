@@ -393,7 +393,7 @@ int yk_decode_alpha(yk_ctx* c, int mode, const int32_t bbox[4], const uint8_t* p
                     const int32_t maskBBox[4], int refQuirk) {
     if (!c || !bbox || (!payload && n)) return YK_ERR_BAD_ARG;
     YK_DEC_NO_BATCH(c, "yk_decode_alpha");
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     const int W = c->dw, H = c->dh;
     const int bx = bbox[0], by = bbox[1], bw = bbox[2], bh = bbox[3];
     // CheckInBound2D (YAIK_Alpha.cpp:12-23) read as "in bounds passes" (it has no `return true`), for every mode; an empty box is refused
@@ -467,6 +467,7 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     if (!c->alphaFinished) return yk_fail(c, YK_ERR_STATE, "yk_alpha_reject + yk_alpha_finish first");
     if (c->nFrames != 1 || c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "yk_alpha_values works on a whole single image");
     const int W = c->fullW, H = c->fullH;
+    const YkFrameView V = yk_frame(c);
     YK_HIP(c, hipSetDevice(c->device));
     c->avBatchValid = false;                                                              // the batch payloads share avState / avPay
     if (!c->avState) YK_HIP(c, c->avState.alloc(c->stream, 8));
@@ -474,9 +475,9 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     const int32_t init[8] = { INT_MAX, INT_MAX, -1, -1, 0, 0, 0, 0 };
     YK_HIP(c, hipMemcpyAsync(c->avState, init, sizeof init, hipMemcpyHostToDevice, c->stream));
     // the search region is at most the image; the kernel clamps it to the bounds the alpha stage left on the device
-    const bool vec = ((reinterpret_cast<uintptr_t>(c->plane[3]) & 15) == 0) && ((c->strideElems & 3) == 0);
+    const bool vec = ((reinterpret_cast<uintptr_t>(V.plane[3]) & 15) == 0) && ((c->strideElems & 3) == 0);
     hipLaunchKernelGGL(vec ? yk_ave_box_kernel<true> : yk_ave_box_kernel<false>, dim3((unsigned)((W / 4 + 255) / 256), (unsigned)((H + YK_AV_ROWS - 1) / YK_AV_ROWS)), dim3(256), 0, c->stream,
-                       c->plane[3], c->strideElems, c->bounds + c->boundsOff, W, H, c->avState);
+                       V.plane[3], c->strideElems, V.bounds + c->boundsOff, W, H, c->avState);
     YK_HIP(c, hipGetLastError());
     int32_t st[8];
     YK_HIP(c, hipMemcpyAsync(st, c->avState, sizeof st, hipMemcpyDeviceToHost, c->stream));
@@ -487,7 +488,7 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     if (bR > W) return yk_fail(c, YK_ERR_STATE, "alpha box beyond the image");
     int bw = bR - bL;
     const int bh = bB - bT;
-    hipLaunchKernelGGL(vec ? yk_ave_class_kernel<true> : yk_ave_class_kernel<false>, dim3((unsigned)((bw / 4 + 255) / 256), (unsigned)bh), dim3(256), 0, c->stream, c->plane[3], c->strideElems,
+    hipLaunchKernelGGL(vec ? yk_ave_class_kernel<true> : yk_ave_class_kernel<false>, dim3((unsigned)((bw / 4 + 255) / 256), (unsigned)bh), dim3(256), 0, c->stream, V.plane[3], c->strideElems,
                        bL, bT, bw, bh, c->avPay, c->avState);
     YK_HIP(c, hipGetLastError());
     YK_HIP(c, hipMemcpyAsync(st + 4, c->avState + 4, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -498,7 +499,7 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     if (analog && force8Bit) {
         out->mode = 6; bytes = (size_t)bw * bh;                                           // IS_8_BIT_FULL, payload already written
     } else if (analog) {                                                                  // IS_6_BIT_USEMIPMAPMASK_INVERSE from the u8 box
-        if (!c->keep || (bL & 3) || (bw & 3)) return yk_fail(c, YK_ERR_STATE, "6-bit alpha: no keep flags or a box not aligned to 4");
+        if (!V.keep || (bL & 3) || (bw & 3)) return yk_fail(c, YK_ERR_STATE, "6-bit alpha: no keep flags or a box not aligned to 4");
         const int nb = ((bB - 1) >> 4) - (bT >> 4) + 1, ncol = ((bR - 1) >> 4) - (bL >> 4) + 1;
         const size_t nU32 = (size_t)nb * ncol + 3 * (size_t)nb + 1;
         const size_t oPay = (nU32 * sizeof(uint32_t) + 255) & ~(size_t)255, payCap = (size_t)(bw >> 2) * 3 * bh;
@@ -508,11 +509,11 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
         uint32_t* bandCnt = bandS + nb;
         uint32_t* bandStart = bandCnt + nb;
         uint8_t* pay6 = c->av6 + oPay;
-        const int32_t* bounds = c->bounds + c->boundsOff;
-        hipLaunchKernelGGL(yk_ave_band_kernel, dim3((unsigned)nb), dim3(64), 0, c->stream, c->keep, c->mtW, c->mtH, bounds, W, H, bL, bT, bR, bB, ncol, colPre,
+        const int32_t* bounds = V.bounds + c->boundsOff;
+        hipLaunchKernelGGL(yk_ave_band_kernel, dim3((unsigned)nb), dim3(64), 0, c->stream, V.keep, c->mtW, c->mtH, bounds, W, H, bL, bT, bR, bB, ncol, colPre,
                            bandS, bandCnt);
         hipLaunchKernelGGL(yk_av_rowscan_kernel, dim3(1), dim3(1024), 0, c->stream, bandCnt, nb, bandStart);
-        hipLaunchKernelGGL(yk_ave_pack6_kernel, dim3((unsigned)((bw / 4 + 255) / 256), (unsigned)bh), dim3(256), 0, c->stream, c->avPay, bL, bT, bw, bh, c->keep,
+        hipLaunchKernelGGL(yk_ave_pack6_kernel, dim3((unsigned)((bw / 4 + 255) / 256), (unsigned)bh), dim3(256), 0, c->stream, c->avPay, bL, bT, bw, bh, V.keep,
                            c->mtW, c->mtH, bounds, W, H, ncol, nb, colPre, bandS, bandStart, pay6, payCap);
         YK_HIP(c, hipGetLastError());
         uint32_t total = 0;
@@ -530,7 +531,7 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
         bw = bR - bL;
         bytes = (size_t)(bw >> 3) * bh;
         out->mode = 1;
-        hipLaunchKernelGGL(yk_ave_pack1_kernel, dim3((unsigned)((bytes + 255) / 256)), dim3(256), 0, c->stream, c->plane[3], c->strideElems, bL, bT, bw, bh,
+        hipLaunchKernelGGL(yk_ave_pack1_kernel, dim3((unsigned)((bytes + 255) / 256)), dim3(256), 0, c->stream, V.plane[3], c->strideElems, bL, bT, bw, bh,
                            c->avPay);
         YK_HIP(c, hipGetLastError());
     }
@@ -666,7 +667,7 @@ static int yk_av_decode_batch(yk_ctx* c, const int32_t* modes, const int32_t* bb
     if (!c) return YK_ERR_BAD_ARG;
     if (!modes || !bboxes || !devPayload || !payBytes || (masks && (!devMipBits || !mipBytes || !mipBoxes))) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
     if (noChunkAlpha < 0 || noChunkAlpha > 255) return yk_refuse(c, YK_ERR_BAD_ARG, "noChunkAlpha must be 0..255");
-    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
     const int N = c->dFrames, W = c->dw, H = c->dh;
     const long long tileGrid = (long long)((W + 15) >> 4) * ((H + 15) >> 4);
     int nMask = 0, maxBh = 0;

@@ -22,18 +22,6 @@ int yk_refuse(yk_ctx* c, int code, const char* what) {
     return code;
 }
 
-void yk_rebase(yk_ctx* c, int f) {
-    const YkFrameStrides& fs = c->fs; auto& B = c->B;
-    c->curFrame = f;
-    for (int i = 0; i < 4; i++) c->plane[i] = B.plane[i] ? B.plane[i] + (size_t)f * fs.plane : nullptr;
-    c->keep = B.keep + (size_t)f * fs.keep; c->bounds = B.bounds + (size_t)f * 16;
-    for (int i = 0; i < 7; i++) c->bitmap[i] = B.bitmap[i] + (size_t)f * fs.bitmap[i];
-    c->coverage = B.coverage + (size_t)f * fs.coverage; c->tileDef = B.tileDef + (size_t)f * fs.tileDef;
-    c->tileCount = B.tileCount + (size_t)f * fs.tileCount; c->slots = B.slots + (size_t)f * fs.slots;
-    c->blockSums = B.blockSums + (size_t)f * fs.blockN; c->blockCnt = B.blockCnt + (size_t)f * fs.blockN;
-    c->totals = B.totals + (size_t)f * 8; c->defsOut = B.defsOut + (size_t)f * fs.defsOut; c->nibOut = B.nibOut + (size_t)f * fs.nibOut;
-}
-
 // New input (an image shape, planes, pixels): nothing computed from the previous input may be handed out any more
 static void yk_input_changed(yk_ctx* c) {
     c->encoded = false; c->alphaDone = false; c->alphaFinished = false; c->avBatchValid = false; c->mipValid = false; c->img.sb.valid = false; c->pal.valid = false;
@@ -46,18 +34,18 @@ static void yk_encode_done(yk_ctx* c, int wantDst) {
     c->ppLastBit = 0; c->previewFresh = false; c->nextCornerPass = 0; c->r1Ready = false; c->mipValid = false;
 }
 
+static void yk_unbind_planes(yk_ctx* c) { for (int i = 0; i < 4; i++) c->B.plane[i] = nullptr; }
+
 static void yk_free_image(yk_ctx* c) {
     c->img = YkImageBufs();                                     // every per-image buffer; the caller has synchronised the stream
-    { yk_ctx::Bases none = {}; for (int i = 0; i < 4; i++) none.plane[i] = c->B.plane[i]; c->B = none; }   // the views go, the bound planes stay
-    c->keep = nullptr; c->bounds = nullptr; for (int i = 0; i < 7; i++) c->bitmap[i] = nullptr;
-    c->coverage = nullptr; c->tileDef = nullptr; c->tileCount = nullptr; c->slots = nullptr;
-    c->blockSums = nullptr; c->blockCnt = nullptr; c->totals = nullptr; c->defsOut = nullptr; c->nibOut = nullptr;
+    { yk_ctx::Bases none = {}; for (int i = 0; i < 4; i++) none.plane[i] = c->B.plane[i]; c->B = none; }   // the arrays go, the bound planes stay
+    c->curFrame = 0;
     c->ppBitmapBytes = c->ppStreamBytes = 0; c->r1Ready = false; c->pixCacheValid = false;
     if (c->frameGraph) { (void)hipGraphExecDestroy(c->frameGraph); c->frameGraph = nullptr; }
     yk_input_changed(c);
 }
 
-// allocates every per-image array c->nFrames times (geometry fields are set) and points the handle at frame 0
+// allocates every per-image array c->nFrames times (geometry fields are set); the handle is at frame 0 (yk_free_image)
 static int yk_alloc_image_run(yk_ctx* c) {
     const size_t F = (size_t)c->nFrames;
     const size_t T8 = (size_t)c->tilesW * c->tilesH, MT = (size_t)c->mtW * c->mtH;
@@ -107,10 +95,9 @@ static int yk_alloc_image_run(yk_ctx* c) {
     B.keep = M.keep; B.bounds = M.bounds; B.tileDef = M.tileDef; B.tileCount = M.tileCount; B.slots = M.slots;
     B.blockSums = M.blockSums; B.blockCnt = M.blockCnt; B.totals = M.totals; B.defsOut = M.defsOut; B.nibOut = M.nibOut;
     c->dstValid = false;
-    yk_rebase(c, 0);
     return YK_OK;
 }
-// all or nothing: a shape whose arrays do not all fit leaves no image behind (c->tileCount, the "an image is set" mark, stays null)
+// all or nothing: a shape whose arrays do not all fit leaves no image behind (yk_image_set stays false)
 static int yk_alloc_image(yk_ctx* c) {
     const int rc = yk_alloc_image_run(c);
     if (rc) yk_free_image(c);
@@ -257,7 +244,7 @@ int yk_set_image(yk_ctx* c, int fullW, int fullH, int nPlanes, int y0, int h, in
     if (y0 + h == fullH && haloRows != 0) return yk_fail(c, YK_ERR_BAD_ARG, "the last stripe has no halo row");
     YK_HIP(c, hipSetDevice(c->device));
     c->fusedAfter = nullptr; c->fusedAfterRing.reset();                      // an ordering request never outlives the image it was made for
-    if (c->fullW == fullW && c->fullH == fullH && c->nPlanes == nPlanes && c->y0 == y0 && c->h == h && c->halo == haloRows && c->tileCount) {
+    if (c->fullW == fullW && c->fullH == fullH && c->nPlanes == nPlanes && c->y0 == y0 && c->h == h && c->halo == haloRows && yk_image_set(c)) {
         yk_input_changed(c);
         return YK_OK;
     }
@@ -266,43 +253,38 @@ int yk_set_image(yk_ctx* c, int fullW, int fullH, int nPlanes, int y0, int h, in
     c->fullW = fullW; c->fullH = fullH; c->nPlanes = nPlanes; c->y0 = y0; c->h = h; c->halo = haloRows;
     c->tilesW = fullW / 8; c->tilesH = h / 8; c->mtW = (fullW + 15) / 16; c->mtH = (h + 15) / 16;
     c->nFrames = 1; c->fs.plane = 0;
-    for (int i = 0; i < 4; i++) { c->B.plane[i] = nullptr; c->plane[i] = nullptr; }
+    yk_unbind_planes(c);
     return yk_alloc_image(c);
 }
 
 int yk_set_batch(yk_ctx* c, int nFrames) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!c->tileCount) return yk_fail(c, YK_ERR_STATE, "yk_set_image first");
+    if (!yk_image_set(c)) return yk_fail(c, YK_ERR_STATE, "yk_set_image first");
     if (nFrames < 1 || nFrames > 1024) return yk_fail(c, YK_ERR_BAD_ARG, "nFrames must be 1..1024");
     if (c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "batches hold whole images, not stripes");
     YK_HIP(c, hipSetDevice(c->device));
     c->img.sb.valid = false; c->pal.valid = false;                                                     // as documented: also when the frame count stays
     if (nFrames != c->nFrames) {
         YK_HIP(c, hipStreamSynchronize(c->stream));
-        const int32_t* keepPlanes[4] = { c->B.plane[0], c->B.plane[1], c->B.plane[2], c->B.plane[3] };
-        const unsigned long long planeStride = c->fs.plane;
-        yk_free_image(c);
+        yk_free_image(c);                                       // B.plane and fs.plane, the binding, stay
         c->nFrames = nFrames;
-        int rc = yk_alloc_image(c); if (rc) return rc;
-        for (int i = 0; i < 4; i++) c->B.plane[i] = keepPlanes[i];
-        c->fs.plane = planeStride;
-        yk_rebase(c, 0);
+        return yk_alloc_image(c);
     }
     return YK_OK;
 }
 
 int yk_select_frame(yk_ctx* c, int frame) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!c->tileCount) return yk_fail(c, YK_ERR_STATE, "yk_set_image first");
+    if (!yk_image_set(c)) return yk_fail(c, YK_ERR_STATE, "yk_set_image first");
     if (frame < 0 || frame >= c->nFrames) return yk_fail(c, YK_ERR_BAD_ARG, "frame out of range");
-    yk_rebase(c, frame);
+    c->curFrame = frame;
     c->cornersReady = false; c->ppActive = false; c->ppLastBit = 0; c->previewFresh = false; c->r1Ready = false;
     return YK_OK;
 }
 
 static int yk_check_planes(yk_ctx* c, const int32_t* const p[4], int strideElems) {
     if (!c || !p) return YK_ERR_BAD_ARG;
-    if (!c->tileCount) return yk_fail(c, YK_ERR_STATE, "yk_set_image first");
+    if (!yk_image_set(c)) return yk_fail(c, YK_ERR_STATE, "yk_set_image first");
     if (strideElems < c->fullW || (strideElems & 3)) return yk_fail(c, YK_ERR_BAD_ARG, "row pitch must be >= width and a multiple of 4 elements");
     for (int i = 0; i < c->nPlanes; i++) if (!p[i]) return yk_fail(c, YK_ERR_BAD_ARG, "null plane");
     return YK_OK;
@@ -329,15 +311,17 @@ __global__ __launch_bounds__(256) void yk_validate_kernel(const int32_t* __restr
 
 int yk_validate_planes(yk_ctx* c, size_t* nOutOfRange) {
     if (!c || !nOutOfRange) return YK_ERR_BAD_ARG;
-    if (!c->B.plane[0]) return yk_fail(c, YK_ERR_STATE, "bind planes first");
+    if (!yk_planes_bound(c)) return yk_fail(c, YK_ERR_STATE, "bind planes first");
     YK_HIP(c, hipSetDevice(c->device));
     YkBuf<unsigned long long> dBad;
     YK_HIP(c, dBad.alloc(c->stream, 1));
     hipError_t e = hipMemsetAsync(dBad, 0, sizeof(unsigned long long), c->stream);
     const int rows = c->h + c->halo;
-    for (int f = 0; f < c->nFrames && e == hipSuccess; f++)
+    for (int f = 0; f < c->nFrames && e == hipSuccess; f++) {
+        const YkFrameView V = yk_frame(c, f);
         for (int i = 0; i < c->nPlanes; i++)
-            hipLaunchKernelGGL(yk_validate_kernel, dim3(c->numCU * 8), dim3(256), 0, c->stream, c->B.plane[i] + (size_t)f * c->fs.plane, c->strideElems, c->fullW, rows, dBad);
+            hipLaunchKernelGGL(yk_validate_kernel, dim3(c->numCU * 8), dim3(256), 0, c->stream, V.plane[i], c->strideElems, c->fullW, rows, dBad);
+    }
     unsigned long long bad = 0;
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, dBad, sizeof bad, hipMemcpyDeviceToHost, c->stream);
@@ -353,13 +337,13 @@ int yk_upload_planes(yk_ctx* c, const int32_t* const hostPlanes[4], int strideEl
     const size_t rows = (size_t)c->h + c->halo;
     YK_HIP(c, c->ownedPlanes.reserve(c->stream, rows * c->fullW * c->nPlanes));
     if (c->nFrames != 1) return yk_fail(c, YK_ERR_STATE, "batches bind device planes (yk_bind_device_batch)");
-    for (int i = 0; i < 4; i++) c->B.plane[i] = nullptr;
+    yk_unbind_planes(c);
     for (int i = 0; i < c->nPlanes; i++) {
         int32_t* d = c->ownedPlanes + (size_t)i * rows * c->fullW;
         YK_HIP(c, hipMemcpy2DAsync(d, (size_t)c->fullW * 4, hostPlanes[i], (size_t)strideElems * 4, (size_t)c->fullW * 4, rows, hipMemcpyHostToDevice, c->stream));
         c->B.plane[i] = d;
     }
-    c->fs.plane = 0; yk_rebase(c, 0);
+    c->fs.plane = 0;
     c->strideElems = c->fullW;
     yk_input_changed(c);
     // the 0..255 precondition is enforced where the boundary hands over host planes (a streaming pass over what was just copied: ~0.2 ms next to
@@ -367,48 +351,40 @@ int yk_upload_planes(yk_ctx* c, const int32_t* const hostPlanes[4], int strideEl
     size_t bad = 0;
     rc = yk_validate_planes(c, &bad); if (rc) return rc;
     if (bad) {
-        for (int i = 0; i < 4; i++) c->B.plane[i] = nullptr;
-        yk_rebase(c, 0);
+        yk_unbind_planes(c);
         return yk_fail(c, YK_ERR_BAD_ARG, ("plane samples outside 0..255: " + std::to_string(bad) + " (the tile path is defined for 8-bit samples held in int32 planes)").c_str());
     }
+    return YK_OK;
+}
+
+// Both device binds: every plane is looked at before the handle is touched, so a refused bind leaves the previous binding whole.  The selected
+// frame stays (curFrame < nFrames always holds).
+static int yk_bind_planes(yk_ctx* c, const int32_t* const p[4], int strideElems, size_t frameStrideElems) {
+    for (int i = 0; i < c->nPlanes; i++) if (((uintptr_t)p[i]) & 15) return yk_fail(c, YK_ERR_BAD_ARG, "device planes must be 16-byte aligned");
+    for (int i = 0; i < 4; i++) c->B.plane[i] = i < c->nPlanes ? p[i] : nullptr;
+    c->fs.plane = frameStrideElems; c->strideElems = strideElems;
+    yk_input_changed(c);
     return YK_OK;
 }
 
 int yk_bind_device_planes(yk_ctx* c, const int32_t* const devPlanes[4], int strideElems) {
     int rc = yk_check_planes(c, devPlanes, strideElems); if (rc) return rc;
     if (c->nFrames != 1) return yk_fail(c, YK_ERR_STATE, "batches bind device planes with yk_bind_device_batch");
-    for (int i = 0; i < 4; i++) c->B.plane[i] = nullptr;
-    for (int i = 0; i < c->nPlanes; i++) {
-        if (((uintptr_t)devPlanes[i]) & 15) return yk_fail(c, YK_ERR_BAD_ARG, "device planes must be 16-byte aligned");
-        c->B.plane[i] = devPlanes[i];
-    }
-    c->fs.plane = 0; yk_rebase(c, 0);
-    c->strideElems = strideElems;
-    yk_input_changed(c);
-    return YK_OK;
+    return yk_bind_planes(c, devPlanes, strideElems, 0);
 }
 
 int yk_bind_device_batch(yk_ctx* c, const int32_t* const frame0Planes[4], int strideElems, size_t frameStrideElems) {
     int rc = yk_check_planes(c, frame0Planes, strideElems); if (rc) return rc;
     if (c->nFrames > 1 && (frameStrideElems < (size_t)strideElems * c->fullH || (frameStrideElems & 3))) return yk_fail(c, YK_ERR_BAD_ARG, "frame stride must cover a plane and be a multiple of 4 elements");
-    for (int i = 0; i < 4; i++) c->B.plane[i] = nullptr;
-    for (int i = 0; i < c->nPlanes; i++) {
-        if (((uintptr_t)frame0Planes[i]) & 15) return yk_fail(c, YK_ERR_BAD_ARG, "device planes must be 16-byte aligned");
-        c->B.plane[i] = frame0Planes[i];
-    }
-    c->fs.plane = frameStrideElems; yk_rebase(c, c->curFrame < c->nFrames ? c->curFrame : 0);
-    c->strideElems = strideElems;
-    yk_input_changed(c);
-    return YK_OK;
+    return yk_bind_planes(c, frame0Planes, strideElems, frameStrideElems);
 }
 
 // ---- 8-bit interleaved pixels -> the handle's own planes (the kernel: yk_pixels.hip) -----------------------
-static void yk_unbind_planes(yk_ctx* c) { for (int i = 0; i < 4; i++) { c->B.plane[i] = nullptr; c->plane[i] = nullptr; } }
 
 static int yk_pixels_check(yk_ctx* c, const uint8_t* px, size_t rowBytes, int channels) {
     if (!px) return yk_fail(c, YK_ERR_BAD_ARG, "null pixels");
     if (channels != 3 && channels != 4) return yk_fail(c, YK_ERR_BAD_ARG, "channels must be 3 (RGB) or 4 (RGBA)");
-    if (!c->tileCount) return yk_fail(c, YK_ERR_STATE, "yk_set_image first");
+    if (!yk_image_set(c)) return yk_fail(c, YK_ERR_STATE, "yk_set_image first");
     if (channels < c->nPlanes) return yk_fail(c, YK_ERR_BAD_ARG, "3-channel pixels cannot fill 4 planes");
     if (rowBytes < (size_t)c->fullW * channels) return yk_fail(c, YK_ERR_BAD_ARG, "rowBytes must cover a row of pixels (>= w * channels)");
     return YK_OK;
@@ -421,7 +397,6 @@ static int yk_own_planes(yk_ctx* c, size_t elems) { YK_HIP(c, c->ownedPlanes.res
 static void yk_bind_owned(yk_ctx* c, size_t planeElems, size_t frameElems) {
     for (int i = 0; i < 4; i++) c->B.plane[i] = i < c->nPlanes ? c->ownedPlanes + (size_t)i * planeElems : nullptr;
     c->fs.plane = c->nFrames > 1 ? frameElems : 0;
-    yk_rebase(c, c->curFrame < c->nFrames ? c->curFrame : 0);
     c->strideElems = c->fullW;
     yk_input_changed(c);
 }
@@ -472,7 +447,7 @@ int yk_load_device_pixels_u8(yk_ctx* c, const uint8_t* devPixels, size_t rowByte
 // ---- alpha -----------------------------------------------------------------------------------------
 int yk_alpha_reject(yk_ctx* c) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!c->plane[0]) return yk_fail(c, YK_ERR_STATE, "bind planes first");
+    if (!yk_planes_bound(c)) return yk_fail(c, YK_ERR_STATE, "bind planes first");
     if (c->nPlanes != 4) return yk_fail(c, YK_ERR_STATE, "image has no alpha plane");
     YK_HIP(c, hipSetDevice(c->device));
     hipEvent_t* ev = c->evRing->ev[c->evHead % YK_EV_RING];
@@ -487,7 +462,7 @@ int yk_get_stripe_bbox(yk_ctx* c, int32_t bbox[4]) {
     if (!c || !bbox) return YK_ERR_BAD_ARG;
     if (!c->alphaDone) return yk_fail(c, YK_ERR_STATE, "yk_alpha_reject first");
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, hipMemcpyAsync(bbox, c->bounds + 8, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(bbox, yk_frame(c).bounds + 8, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }
@@ -505,9 +480,10 @@ int yk_alpha_finish(yk_ctx* c, const int32_t globalBBox[4]) {
 static int yk_fetch_alpha(yk_ctx* c, std::vector<uint8_t>& keep, int32_t b[5]) {
     if (!c->alphaFinished) return yk_fail(c, YK_ERR_STATE, "yk_alpha_finish first");
     YK_HIP(c, hipSetDevice(c->device));
+    const YkFrameView V = yk_frame(c);
     keep.resize((size_t)c->mtW * c->mtH);
-    YK_HIP(c, hipMemcpyAsync(keep.data(), c->keep, keep.size(), hipMemcpyDeviceToHost, c->stream));
-    YK_HIP(c, hipMemcpyAsync(b, c->bounds + c->boundsOff, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(keep.data(), V.keep, keep.size(), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(b, V.bounds + c->boundsOff, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     b[4] = (b[0] == 0 && b[1] == 0 && b[2] == c->fullW && b[3] == c->fullH) ? 1 : 0;      // "bbox == whole image -> every reject discarded" (EncoderContext.cpp:1294, :1400-1403)
     return YK_OK;
@@ -596,7 +572,7 @@ static void yk_ev_commit(yk_ctx* c, int has) {
 
 int yk_encode_tiles(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!c->plane[0]) return yk_fail(c, YK_ERR_STATE, "bind planes first");
+    if (!yk_planes_bound(c)) return yk_fail(c, YK_ERR_STATE, "bind planes first");
     if (rejectFactor < 0 || rejectFactor > 64) return yk_fail(c, YK_ERR_BAD_ARG, "rejectFactor out of range");
     if (c->nPlanes == 4 && !c->alphaFinished) return yk_fail(c, YK_ERR_STATE, "RGBA image: run yk_alpha_reject + yk_alpha_finish first (MipPrefilter precedes the tile passes)");
     YK_HIP(c, hipSetDevice(c->device));
@@ -638,11 +614,11 @@ int yk_order_fused_after(yk_ctx* c, const yk_ctx* other) {
 
 int yk_encode_batch(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!c->B.plane[0]) return yk_fail(c, YK_ERR_STATE, "bind planes first");
+    if (!yk_planes_bound(c)) return yk_fail(c, YK_ERR_STATE, "bind planes first");
     if (rejectFactor < 0 || rejectFactor > 64) return yk_fail(c, YK_ERR_BAD_ARG, "rejectFactor out of range");
     if (c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "batches hold whole images");
     if (c->kernelVersion != 2) return yk_fail(c, YK_ERR_STATE, "batches need kernel version 2");
-    if (c->nFrames > 1 && c->fs.plane == 0) return yk_fail(c, YK_ERR_STATE, "yk_bind_device_batch first");
+    if (!yk_batch_planes_bound(c)) return yk_fail(c, YK_ERR_STATE, "yk_bind_device_batch first");
     YK_HIP(c, hipSetDevice(c->device));
     hipEvent_t* ev = c->evRing->ev[c->evHead % YK_EV_RING];
     int rc = YK_OK;
@@ -664,12 +640,13 @@ int yk_encode_batch(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
 
 int yk_encode_frame(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!c->plane[0]) return yk_fail(c, YK_ERR_STATE, "bind planes first");
+    if (!yk_planes_bound(c)) return yk_fail(c, YK_ERR_STATE, "bind planes first");
     if (rejectFactor < 0 || rejectFactor > 64) return yk_fail(c, YK_ERR_BAD_ARG, "rejectFactor out of range");
     if (c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "yk_encode_frame is the whole-image form (stripes need the bbox exchange between the stages)");
     YK_HIP(c, hipSetDevice(c->device));
-    const unsigned long long key[12] = { (unsigned long long)(uintptr_t)c->plane[0], (unsigned long long)(uintptr_t)c->plane[1], (unsigned long long)(uintptr_t)c->plane[2],
-                                         (unsigned long long)(uintptr_t)c->plane[3], (unsigned long long)c->fullW, (unsigned long long)c->fullH, (unsigned long long)c->strideElems,
+    const YkFrameView V = yk_frame(c);
+    const unsigned long long key[12] = { (unsigned long long)(uintptr_t)V.plane[0], (unsigned long long)(uintptr_t)V.plane[1], (unsigned long long)(uintptr_t)V.plane[2],
+                                         (unsigned long long)(uintptr_t)V.plane[3], (unsigned long long)c->fullW, (unsigned long long)c->fullH, (unsigned long long)c->strideElems,
                                          (unsigned long long)rejectFactor, (unsigned long long)(mode3BitOnly != 0), (unsigned long long)c->kernelVersion,
                                          (unsigned long long)c->ablate, (unsigned long long)(uintptr_t)c->stream };
     if (c->frameGraph && memcmp(key, c->frameGraphKey, sizeof key) != 0) { (void)hipGraphExecDestroy(c->frameGraph); c->frameGraph = nullptr; }
@@ -699,14 +676,14 @@ int yk_encode_frame(yk_ctx* c, int rejectFactor, int mode3BitOnly) {
 }
 
 size_t yk_gradient_bitmap_bytes(const yk_ctx* c, int pass) { return (c && pass >= 0 && pass < 7) ? c->bitmapBytes[pass] : 0; }
-const uint8_t* yk_gradient_bitmap_device(const yk_ctx* c, int pass) { return (c && c->encoded && pass >= 0 && pass < 7) ? c->bitmap[pass] : nullptr; }
+const uint8_t* yk_gradient_bitmap_device(const yk_ctx* c, int pass) { return (c && c->encoded && pass >= 0 && pass < 7) ? yk_frame(c).bitmap[pass] : nullptr; }
 
 int yk_gradient_bitmap(yk_ctx* c, int pass, uint8_t* hostOut, size_t cap) {
     if (!c || !hostOut || pass < 0 || pass >= 7) return YK_ERR_BAD_ARG;
     if (!c->encoded) return yk_fail(c, YK_ERR_STATE, "yk_encode_tiles first");
     if (cap < c->bitmapBytes[pass]) return yk_fail(c, YK_ERR_RANGE, "bitmap buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, hipMemcpyAsync(hostOut, c->bitmap[pass], c->bitmapBytes[pass], hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(hostOut, yk_frame(c).bitmap[pass], c->bitmapBytes[pass], hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }
@@ -715,9 +692,10 @@ int yk_gradient_counts(yk_ctx* c, int32_t counts[YK_NUM_PASSES]) {
     if (!c || !counts) return YK_ERR_BAD_ARG;
     if (!c->encoded) return yk_fail(c, YK_ERR_STATE, "yk_encode_tiles first");
     YK_HIP(c, hipSetDevice(c->device));
+    const YkFrameView V = yk_frame(c);
     for (int p = 0; p < 7; p++) {
         std::vector<uint8_t> b(c->bitmapBytes[p] + 8, 0);
-        YK_HIP(c, hipMemcpyAsync(b.data(), c->bitmap[p], c->bitmapBytes[p], hipMemcpyDeviceToHost, c->stream));
+        YK_HIP(c, hipMemcpyAsync(b.data(), V.bitmap[p], c->bitmapBytes[p], hipMemcpyDeviceToHost, c->stream));
         YK_HIP(c, hipStreamSynchronize(c->stream));
         int n = 0;
         for (size_t i = 0; i < c->bitmapBytes[p]; i++) n += __builtin_popcount(b[i]);
@@ -732,7 +710,7 @@ int yk_coverage(yk_ctx* c, uint16_t* hostOut, size_t capElems) {
     const size_t n = (size_t)c->mtW * c->mtH;
     if (capElems < n) return yk_fail(c, YK_ERR_RANGE, "coverage buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, hipMemcpyAsync(hostOut, c->coverage, n * 2, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(hostOut, yk_frame(c).coverage, n * 2, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }
@@ -742,7 +720,7 @@ int yk_range_sizes(yk_ctx* c, int plane, size_t* nDefs, size_t* nNibbles) {
     if (!c->encoded) return yk_fail(c, YK_ERR_STATE, "yk_encode_tiles first");
     uint32_t t[2];
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, hipMemcpyAsync(t, c->totals + plane * 2, sizeof t, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(t, yk_frame(c).totals + plane * 2, sizeof t, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     if (nDefs) *nDefs = t[0];
     if (nNibbles) *nNibbles = t[1];
@@ -755,17 +733,18 @@ int yk_range_streams(yk_ctx* c, int plane, uint16_t* hostDefs, size_t capDefs, u
     const size_t nb = (nn + 1) / 2;                                       // closed to a whole byte (:4525-4527)
     if ((hostDefs && capDefs < nd) || (hostNibbles && capBytes < nb)) return yk_fail(c, YK_ERR_RANGE, "range stream buffer too small");
     const size_t T8 = (size_t)c->tilesW * c->tilesH;
-    if (hostDefs && nd) YK_HIP(c, hipMemcpyAsync(hostDefs, c->defsOut + plane * T8, nd * 2, hipMemcpyDeviceToHost, c->stream));
-    if (hostNibbles && nb) YK_HIP(c, hipMemcpyAsync(hostNibbles, c->nibOut + plane * c->nibStride, nb, hipMemcpyDeviceToHost, c->stream));
+    const YkFrameView V = yk_frame(c);
+    if (hostDefs && nd) YK_HIP(c, hipMemcpyAsync(hostDefs, V.defsOut + plane * T8, nd * 2, hipMemcpyDeviceToHost, c->stream));
+    if (hostNibbles && nb) YK_HIP(c, hipMemcpyAsync(hostNibbles, V.nibOut + plane * c->nibStride, nb, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }
 
 const uint16_t* yk_range_defs_device(const yk_ctx* c, int plane) {
-    return (c && c->encoded && plane >= 0 && plane < 3) ? c->defsOut + (size_t)plane * c->tilesW * c->tilesH : nullptr;
+    return (c && c->encoded && plane >= 0 && plane < 3) ? yk_frame(c).defsOut + (size_t)plane * c->tilesW * c->tilesH : nullptr;
 }
 const uint8_t* yk_range_nibbles_device(const yk_ctx* c, int plane) {
-    return (c && c->encoded && plane >= 0 && plane < 3) ? c->nibOut + (size_t)plane * c->nibStride : nullptr;
+    return (c && c->encoded && plane >= 0 && plane < 3) ? yk_frame(c).nibOut + (size_t)plane * c->nibStride : nullptr;
 }
 
 int yk_range_dst(yk_ctx* c, int plane, int32_t* hostOut, size_t capElems) {
@@ -780,7 +759,7 @@ int yk_range_dst(yk_ctx* c, int plane, int32_t* hostOut, size_t capElems) {
 }
 
 size_t yk_export_capacity(const yk_ctx* c) {
-    if (!c || !c->tileCount) return 0;
+    if (!c || !yk_image_set(c)) return 0;
     size_t n = 0;
     for (int i = 0; i < 7; i++) n += (c->bitmapBytes[i] + 15) & ~(size_t)15;
     n += ((size_t)c->mtW * c->mtH + 15) & ~(size_t)15;
@@ -828,11 +807,12 @@ static int yk_export_launch(yk_ctx* c, void* devDst, size_t cap, unsigned long l
     if (cap < yk_export_capacity(c)) return yk_fail(c, YK_ERR_RANGE, "export buffer smaller than yk_export_capacity");
     YK_HIP(c, hipSetDevice(c->device));
     const size_t T8 = (size_t)c->tilesW * c->tilesH;
+    const YkFrameView V = yk_frame(c);
     YkExportDesc d;
-    for (int i = 0; i < 7; i++) { d.src[i] = c->bitmap[i]; d.fixedBytes[i] = c->bitmapBytes[i]; }
-    d.src[7] = c->keep; d.fixedBytes[7] = (c->nPlanes == 4) ? (unsigned long long)c->mtW * c->mtH : 0;
-    for (int p = 0; p < 3; p++) { d.src[8 + 2 * p] = reinterpret_cast<const uint8_t*>(c->defsOut + p * T8); d.src[9 + 2 * p] = c->nibOut + p * c->nibStride; }
-    d.totals = c->totals; d.sizesOut = devMeta16;
+    for (int i = 0; i < 7; i++) { d.src[i] = V.bitmap[i]; d.fixedBytes[i] = c->bitmapBytes[i]; }
+    d.src[7] = V.keep; d.fixedBytes[7] = (c->nPlanes == 4) ? (unsigned long long)c->mtW * c->mtH : 0;
+    for (int p = 0; p < 3; p++) { d.src[8 + 2 * p] = reinterpret_cast<const uint8_t*>(V.defsOut + p * T8); d.src[9 + 2 * p] = V.nibOut + p * c->nibStride; }
+    d.totals = V.totals; d.sizesOut = devMeta16;
     hipLaunchKernelGGL(yk_export_kernel, dim3(128, 14), dim3(256), 0, c->stream, d, (uint8_t*)devDst);
     YK_HIP(c, hipGetLastError());
     return YK_OK;

@@ -145,8 +145,8 @@ struct YkPaletteDec {
 static inline size_t yk_alpha_units(int fullW, int mtH) { return (size_t)((fullW / 4 + 63) / 64) * (size_t)((mtH + YK_ALPHA_R - 1) / YK_ALPHA_R); }
 
 // Everything that is allocated for one image shape and frame count (yk_set_image, yk_set_batch) or grows with the work done on it, and goes
-// when the shape changes: released as a whole (yk_free_image).  The pointers the kernels are given -- the frame-0 bases B, the working
-// pointers of yk_rebase, the pieces of `small` -- are views into these.
+// when the shape changes: released as a whole (yk_free_image).  The pointers the kernels are given -- the frame-0 bases B, the per-frame
+// views of yk_frame, the pieces of `small` -- point into these.
 struct YkImageBufs {
     // alpha
     YkBuf<uint8_t> keep; YkBuf<int32_t> bounds;
@@ -184,42 +184,40 @@ struct yk_ctx {
     // geometry
     int fullW = 0, fullH = 0, nPlanes = 0, y0 = 0, h = 0, halo = 0;
     int tilesW = 0, tilesH = 0, mtW = 0, mtH = 0;
-    // batch: the pointers below are those of frame `curFrame`; B holds the allocations (frame 0), fs the per-frame strides
+    // batch: B holds the address of every per-frame array for frame 0 and fs the per-frame strides, the one record of where things are;
+    // yk_frame(c, f) computes the arrays of frame f from them, and the single-image entry points work on frame `curFrame`
     int nFrames = 1, curFrame = 0;
     YkFrameStrides fs = {};
     struct Bases {
-        const int32_t* plane[4]; uint8_t* keep; int32_t* bounds; uint8_t* bitmap[7]; uint16_t* coverage; uint16_t* tileDef; uint8_t* tileCount;
-        uint8_t* slots; uint32_t* blockSums; uint32_t* blockCnt; uint32_t* totals; uint16_t* defsOut; uint8_t* nibOut;
+        const int32_t* plane[4];        // the bound input planes (nullptr: not bound)
+        uint8_t* keep;                  // mtW*mtH keep flags of the alpha stage
+        int32_t* bounds;                // 16 ints: [0..4] the host-combined box of a striped image + its discard flag (yk_alpha_finish), [8..11] the box yk_alpha_box_kernel folds from the units of yk_alpha_kernel
+        uint8_t* bitmap[7]; uint16_t* coverage; uint16_t* tileDef; uint8_t* tileCount; uint8_t* slots;   // encode outputs
+        uint32_t* blockSums;            // [nBlocks][2]: exclusive prefix of (nibbles, coded tiles) per block of 1024 tiles, same for the 3 planes
+        uint32_t* blockCnt;             // [nBlocks][2]: the sums themselves, accumulated by the fused kernel, consumed (and cleared) by the scan
+        uint32_t* totals;               // [3][2]
+        uint16_t* defsOut;              // [3][T8]
+        uint8_t* nibOut;                // [3][T8*32 + 8]
         uint8_t* small;                 // one allocation: bitmap[0..6], bm0b, coverage, tileInfo, runSums (each nFrames times; the pointers above point into it)
         uint8_t* bm0b; uint2* tileInfo; uint32_t* runSums;
     } B = {};
-    // input
-    const int32_t* plane[4] = {nullptr, nullptr, nullptr, nullptr};
+    // input (the bound planes are B.plane)
     int strideElems = 0;
     YkBuf<int32_t> ownedPlanes;
     YkBuf<uint8_t> pxStage;                                 // yk_upload_pixels_u8: grow-only HBM copy of the host's 8-bit rows (16-byte pitch)
     hipEvent_t evPixCopy = nullptr;                         // ... recorded behind that copy: the call returns once the host rows are read
     // alpha
-    uint8_t* keep = nullptr;            // mtW*mtH
-    int32_t* bounds = nullptr;          // 16 ints: [0..4] the host-combined box of a striped image + its discard flag (yk_alpha_finish), [8..11] the box yk_alpha_box_kernel folds from the units of yk_alpha_kernel
     int boundsOff = 8;                  // where the image-wide box is: 8 (whole image, batch) or 0 (stripes, after yk_alpha_finish)
     bool alphaDone = false, alphaFinished = false;
     int32_t hostBounds[4] = {0, 0, 0, 0}; int hostDiscard = 1, hostHasChunk = 0;
     // encode outputs
-    uint8_t* bitmap[7] = {}; size_t bitmapBytes[7] = {};
-    uint16_t* coverage = nullptr;
-    uint16_t* tileDef = nullptr; uint8_t* tileCount = nullptr; uint8_t* slots = nullptr;
+    size_t bitmapBytes[7] = {};
     int32_t dstFill = -1; bool dstValid = false;
     // compaction
-    uint32_t* blockSums = nullptr;      // [nBlocks][2]: exclusive prefix of (nibbles, coded tiles) per block of 1024 tiles, same for the 3 planes
-    uint32_t* blockCnt = nullptr;       // [nBlocks][2]: the sums themselves, accumulated by the fused kernel, consumed (and cleared) by the scan
-    uint32_t* totals = nullptr;         // [3][2] device
     hipEvent_t evHandoff = nullptr;              // yk_stream_handoff / yk_stream_wait_for
     // yk_order_fused_after: the next fused kernel waits for this event, the end of the other handle's fused kernel.  It belongs to that handle's
     // ring, which fusedAfterRing keeps alive should the other handle be destroyed before this one encodes.
     hipEvent_t fusedAfter = nullptr; std::shared_ptr<YkEvRing> fusedAfterRing;
-    uint16_t* defsOut = nullptr;        // [3][T8]
-    uint8_t*  nibOut = nullptr;         // [3][T8*32 + 8]
     size_t nibStride = 0;
     int nScanBlocks = 0;
     bool encoded = false;
@@ -243,10 +241,8 @@ struct yk_ctx {
     bool pixCacheOn = false, pixCacheValid = false;      // yk_set_pixel_cache (img.pixCache)
     uint32_t r1EndTiles[3] = {}, r1EndPix[3] = {};       // cumulative per plane (equal thirds unless a partial-plane pass ran)
     // decode
-    int dw = 0, dh = 0; uint8_t* dPlanes = nullptr; size_t dPlaneSize = 0;
-    uint8_t* dMapRGB = nullptr; uint32_t* dLatticeOwner = nullptr; uint8_t* dTile4 = nullptr; size_t dTile4Size = 0;
+    int dw = 0, dh = 0; size_t dPlaneSize = 0, dTile4Size = 0;
     YkBuf<uint8_t> dScratch;
-    uint8_t* dLoaded = nullptr;         // lattice point already popped from a colour stream (mapRGBMask)
     bool dSplit = false;
     YkBuf<uint8_t> dAlpha; bool dAlphaValid = false;     // yk_decode_alpha: the w x h alpha plane of the image being decoded
     YkBuf<uint8_t> dAvScratch;                           // its payload, mask and row counts
@@ -266,8 +262,9 @@ struct yk_ctx {
     // yk_decode_alpha_mask_batch_device: the frames of modes 2 / 3 of the last batch call, in table order, and one status word for each of them
     std::vector<int32_t> dAvMaskFrames; YkBuf<int32_t> dAvStatus;
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
-    // decode batch (yk_decode_begin_batch): dPlanes / dMapRGB / dLatticeOwner / dLoaded / dTile4 above are those of frame `dCur`; dB holds the
-    // allocations (frame 0) and dStride the distance in BYTES from one frame's array to the next (yk_dec_rebase), like B / fs on the encode side
+    // decode batch (yk_decode_begin_batch): dB holds the allocations (frame 0) and dStride the distance in BYTES from one frame's array to the
+    // next, like B / fs on the encode side; yk_dec_frame(c, f) computes the arrays of frame f, and the single-image entry points work on frame
+    // `dCur`.  loaded: lattice point already popped from a colour stream (mapRGBMask)
     int dFrames = 1, dCur = 0;
     struct DBases { uint8_t* planes; uint8_t* mapRGB; uint32_t* owner; uint8_t* loaded; uint8_t* tile4; } dB = {};
     struct DFrames { YkBuf<uint8_t> planes, mapRGB; YkBuf<uint32_t> owner; YkBuf<uint8_t> loaded, tile4; } dFrm;   // what dB points into
@@ -299,6 +296,36 @@ struct yk_ctx {
     YkPaletteDec pdec;                  // yk_palette_decompress_streams, yk_decode_gradient_palette
 };
 
+// The arrays of ONE frame of the handle: yk_ctx::Bases moved on by the frame's strides.  These two functions are the only place where a frame
+// index meets a stride; everything that works on one frame takes a view at its top and reads from it.
+typedef yk_ctx::Bases YkFrameView;
+inline YkFrameView yk_frame(const yk_ctx* c, int f) {
+    const YkFrameStrides& fs = c->fs; const size_t n = (size_t)f;
+    YkFrameView V = c->B;
+    for (int i = 0; i < 4; i++) if (V.plane[i]) V.plane[i] += n * fs.plane;
+    V.keep += n * fs.keep; V.bounds += n * 16; V.totals += n * 8;
+    for (int i = 0; i < 7; i++) V.bitmap[i] += n * fs.bitmap[i];
+    V.coverage += n * fs.coverage; V.tileDef += n * fs.tileDef; V.tileCount += n * fs.tileCount; V.slots += n * fs.slots;
+    V.blockSums += n * fs.blockN; V.blockCnt += n * fs.blockN; V.defsOut += n * fs.defsOut; V.nibOut += n * fs.nibOut;
+    V.bm0b += n * fs.bm0b; V.tileInfo += n * fs.tileInfo; V.runSums += n * fs.runSums;
+    return V;                                                            // V.small stays the allocation: offsets into it are taken from there
+}
+inline YkFrameView yk_frame(const yk_ctx* c) { return yk_frame(c, c->curFrame); }
+typedef yk_ctx::DBases YkDecView;
+inline YkDecView yk_dec_frame(const yk_ctx* c, int f) {
+    const yk_ctx::DStrides& s = c->dStride; const size_t n = (size_t)f;
+    YkDecView V = c->dB;
+    V.planes += n * s.planes; V.mapRGB += n * s.mapRGB; V.owner += n * s.owner / 4; V.loaded += n * s.loaded; V.tile4 += n * s.tile4;   // owner: the stride is bytes, a multiple of 16
+    return V;
+}
+inline YkDecView yk_dec_frame(const yk_ctx* c) { return yk_dec_frame(c, c->dCur); }
+// what the entry points ask before they work: an image is set (yk_set_image has allocated), planes are bound (a batch of more than one frame
+// also needs its frame stride: yk_bind_device_batch), a decode has begun
+inline bool yk_image_set(const yk_ctx* c) { return c->B.tileCount != nullptr; }
+inline bool yk_planes_bound(const yk_ctx* c) { return c->B.plane[0] != nullptr; }
+inline bool yk_batch_planes_bound(const yk_ctx* c) { return c->B.plane[0] && (c->nFrames == 1 || c->fs.plane != 0); }
+inline bool yk_dec_begun(const yk_ctx* c) { return c->dB.planes != nullptr; }
+
 int yk_fail(yk_ctx* c, int code, const char* what, hipError_t e = hipSuccess);
 // yk_fail keeps the FIRST message of a handle (its callers rely on that); yk_refuse is for entry points whose refusals leave the handle usable and are
 // met again and again (the decode batch calls): the message is always that of the latest refusal
@@ -309,7 +336,6 @@ int yk_refuse(yk_ctx* c, int code, const char* what);
 #define YK_DEC_NO_BATCH(c, name) do { if ((c)->dFrames > 1) return yk_refuse((c), YK_ERR_STATE, name " is not supported in a batch (yk_decode_begin_batch with nFrames > 1)"); } while (0)
 
 // launchers implemented in the kernel TUs
-void yk_rebase(yk_ctx* c, int frame);                    // point the working pointers at `frame`
 int yk_stage_begin(yk_ctx* c, int stage);                // records the begin event of a new interval of `stage` on c->stream
 int yk_stage_end(yk_ctx* c, int stage);
 int yk_launch_alpha(yk_ctx* c, bool batch = false);

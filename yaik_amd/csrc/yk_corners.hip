@@ -292,6 +292,7 @@ int yk_launch_corners(yk_ctx* c) {
     // Row stripes: the handle de-duplicates inside its own rows; its first and last lattice rows are shared with the
     // neighbouring stripes and are reconciled on the root from yk_gradient_corner_edges (see distributed.merge_corner_streams).
     const int w = c->fullW, h = c->h;
+    const YkFrameView V = yk_frame(c);
     const int latW = w / 4 + 1, latH = h / 4 + 1;
     const size_t lat = (size_t)latW * latH;
     if (!c->img.latticeOwner) YK_HIP(c, c->img.latticeOwner.alloc(c->stream, lat));
@@ -300,7 +301,7 @@ int yk_launch_corners(yk_ctx* c) {
     const size_t region = lat * 3 + 16;
     if (!c->img.cornerStream) YK_HIP(c, c->img.cornerStream.alloc(c->stream, region * 7));
     CornerPlan pl;
-    yk_corner_plan(c, c->bitmap, pl);
+    yk_corner_plan(c, V.bitmap, pl);
     const size_t nbTot = pl.blockStart[7], nWordsTot = pl.wordStart[7];
     // scratch: [block sums | 7 totals (+ pad) | ownership bits per thread (one word per bitmap byte)]
     if (!c->img.cornerScratch) YK_HIP(c, c->img.cornerScratch.alloc(c->stream, nbTot + 64 + nWordsTot * 4));
@@ -312,14 +313,14 @@ int yk_launch_corners(yk_ctx* c) {
     YK_HIP(c, hipMemsetAsync(c->img.cornerEdgeIdx, 0xFF, (size_t)latW * 2 * 4, c->stream));
     YK_HIP(c, hipMemsetAsync(c->img.latticeOwner, 0xFF, lat * 4, c->stream));
     for (int p = 0; p < 7; p++)
-        if (c->bitmapBytes[p] & 3) YK_HIP(c, hipMemsetAsync(c->bitmap[p] + c->bitmapBytes[p], 0, 4 - (c->bitmapBytes[p] & 3), c->stream));
+        if (c->bitmapBytes[p] & 3) YK_HIP(c, hipMemsetAsync(V.bitmap[p] + c->bitmapBytes[p], 0, 4 - (c->bitmapBytes[p] & 3), c->stream));
     // 2 clears + 4 launches for the seven passes (round 1: 2 + 28): owner of every lattice point, corners per block, one scan, emission
     hipLaunchKernelGGL(yk_corner_owner_kernel, dim3((pl.wordStart[7] * 4u + 255u) / 256u), dim3(256), 0, c->stream, pl, w, latW, c->img.latticeOwner);
     hipLaunchKernelGGL(yk_corner_stream_kernel<false>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, latW, c->img.latticeOwner, blockSums, perThread,
-                       c->plane[0], c->plane[1], c->plane[2], c->strideElems, (uint8_t*)nullptr, region, (uint32_t*)nullptr, latH, c->h + c->halo);
+                       V.plane[0], V.plane[1], V.plane[2], c->strideElems, (uint8_t*)nullptr, region, (uint32_t*)nullptr, latH, c->h + c->halo);
     hipLaunchKernelGGL(yk_corner_scan_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, pl, totalDev);
     hipLaunchKernelGGL(yk_corner_stream_kernel<true>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, latW, c->img.latticeOwner, blockSums, perThread,
-                       c->plane[0], c->plane[1], c->plane[2], c->strideElems, c->img.cornerStream, region, c->img.cornerEdgeIdx, latH, c->h + c->halo);
+                       V.plane[0], V.plane[1], V.plane[2], c->strideElems, c->img.cornerStream, region, c->img.cornerEdgeIdx, latH, c->h + c->halo);
     YK_HIP(c, hipGetLastError());
     { int rc = yk_stage_end(c, YK_STAGE_CORNERS); if (rc) return rc; }
     // the stream lengths stay on the device until somebody asks for a stream (yk_corners_finish): a caller that keeps frames in flight

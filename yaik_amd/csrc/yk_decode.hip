@@ -858,7 +858,7 @@ __global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_batch_kernel(YkDe
     yk_dec_detile_body<C, PLANAR, ASRC>(a, blockIdx.x);
 }
 
-// nFrames == 0: the image c->dPlanes points at (the existing single-image launch); otherwise nFrames frames, planesFrame / outFrame bytes apart
+// nFrames == 0: the selected frame (the existing single-image launch); otherwise nFrames frames, planesFrame / outFrame bytes apart
 template <int C, bool PLANAR, int ASRC>
 static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, size_t planesFrame = 0, size_t outFrame = 0, size_t alphaFrame = 0) {
     const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
@@ -872,7 +872,7 @@ static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, 
 static int yk_dec_detile(yk_ctx* c, uint8_t* out, size_t rowBytes, size_t planeBytes, int channels, const uint8_t* alpha, size_t strideA, int alphaConst,
                          int nFrames = 0, size_t frameBytes = 0, size_t alphaFrame = 0) {
     YkDetileArgs a;
-    a.planes = nFrames ? c->dB.planes : c->dPlanes; a.planeSize = c->dPlaneSize;
+    a.planes = yk_dec_frame(c, nFrames ? 0 : c->dCur).planes; a.planeSize = c->dPlaneSize;
     const size_t pf = c->dStride.planes;
     a.alpha = alpha; a.strideA = strideA; a.alphaConst = (uint32_t)(alphaConst & 255) * 0x01010101u;
     a.out = out; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
@@ -933,8 +933,8 @@ static int yk_dec_settle(yk_ctx* c) {
     const int w = c->dw, h = c->dh;
     const size_t T8 = (size_t)(w >> 3) * (h >> 3);
     if (c->dFrames == 1)
-        hipLaunchKernelGGL(yk_dec_zero_unmarked_kernel, dim3((unsigned)((T8 + 255) / 256), 3), dim3(256), 0, c->stream, c->dTile4, c->dTile4Size, c->dSplit ? 1 : 0,
-                           (w + 15) >> 4, w >> 3, T8, c->dPlanes, c->dPlaneSize);
+        hipLaunchKernelGGL(yk_dec_zero_unmarked_kernel, dim3((unsigned)((T8 + 255) / 256), 3), dim3(256), 0, c->stream, c->dB.tile4, c->dTile4Size, c->dSplit ? 1 : 0,
+                           (w + 15) >> 4, w >> 3, T8, c->dB.planes, c->dPlaneSize);
     else                                                                        // the flag is the handle's: what it says holds for every frame
         hipLaunchKernelGGL(yk_dec_zero_unmarked_batch_kernel, dim3((unsigned)((T8 + 255) / 256), 3, (unsigned)c->dFrames), dim3(256), 0, c->stream, c->dB.tile4, c->dStride.tile4,
                            c->dTile4Size, (w + 15) >> 4, w >> 3, T8, c->dB.planes, c->dStride.planes, c->dPlaneSize);
@@ -944,17 +944,8 @@ static int yk_dec_settle(yk_ctx* c) {
 }
 
 
-// point the working pointers at `frame` (yk_rebase of the decode side)
-static void yk_dec_rebase(yk_ctx* c, int f) {
-    c->dCur = f;
-    c->dPlanes = c->dB.planes + (size_t)f * c->dStride.planes; c->dMapRGB = c->dB.mapRGB + (size_t)f * c->dStride.mapRGB;
-    c->dLatticeOwner = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(c->dB.owner) + (size_t)f * c->dStride.owner);
-    c->dLoaded = c->dB.loaded + (size_t)f * c->dStride.loaded; c->dTile4 = c->dB.tile4 + (size_t)f * c->dStride.tile4;
-}
-
 static void yk_dec_free_frames(yk_ctx* c) {
     c->dFrm = yk_ctx::DFrames(); c->dB = {};
-    c->dPlanes = nullptr; c->dMapRGB = nullptr; c->dLatticeOwner = nullptr; c->dTile4 = nullptr; c->dLoaded = nullptr;
     c->dw = c->dh = 0; c->dFrames = 1; c->dCur = 0;
 }
 
@@ -976,7 +967,7 @@ static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
     YK_HIP(c, hipSetDevice(c->device));
     const size_t lat = (size_t)(w / 4 + 1) * (h / 4 + 1), N = (size_t)nFrames;
     auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
-    if (!c->dB.planes || c->dw != w || c->dh != h || c->dFrames != nFrames) {   // a stream of images (or batches) of one shape keeps its buffers: only the clears below
+    if (!yk_dec_begun(c) || c->dw != w || c->dh != h || c->dFrames != nFrames) {   // a stream of images (or batches) of one shape keeps its buffers: only the clears below
         YK_HIP(c, hipStreamSynchronize(c->stream));
         yk_dec_free_frames(c);
         const int tileW = w >> 3, tileH = h >> 3;
@@ -1002,7 +993,7 @@ static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
         c->dB = { D.planes, D.mapRGB, D.owner, D.loaded, D.tile4 };
         c->dw = w; c->dh = h; c->dFrames = nFrames;
     }
-    yk_dec_rebase(c, 0);
+    c->dCur = 0;
     // The planes (3 B per pixel: 201 MB at 8192 x 8192, 40 us of every frame) are NOT cleared: every renderer marks what it writes in tile4x4Mask and
     // the 1-D decode writes every unmarked quadrant, so after a whole file nothing stale is left; a flow that stops earlier (or writes without
     // marking: the plane-subset loops) gets the unmarked cells zeroed when it needs them (yk_dec_settle).
@@ -1028,9 +1019,9 @@ int yk_decode_begin_batch(yk_ctx* c, int w, int h, int nFrames) {
 
 int yk_decode_select_frame(yk_ctx* c, int frame) {
     if (!c) return YK_ERR_BAD_ARG;
-    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin first");
     if (frame < 0 || frame >= c->dFrames) return yk_refuse(c, YK_ERR_BAD_ARG, "frame out of range");
-    yk_dec_rebase(c, frame);
+    c->dCur = frame;
     return YK_OK;
 }
 
@@ -1102,14 +1093,15 @@ static hipError_t yk_dpass_stage(yk_ctx* c, const uint8_t* bitmap, size_t need, 
                                rgb, S + oR, rgbBytes, yk_dec_remap_factor(remapRange));
         else e = hipMemcpyAsync(S + oR, rgb, rgbBytes, kind, c->stream);
     }
-    if (e == hipSuccess) e = hipMemsetAsync(c->dLatticeOwner, 0xFF, (size_t)(c->dw / 4 + 1) * (c->dh / 4 + 1) * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(yk_dec_frame(c).owner, 0xFF, (size_t)(c->dw / 4 + 1) * (c->dh / 4 + 1) * 4, c->stream);
     *in = { nWords, nBits, nb, reinterpret_cast<const uint32_t*>(S + oB), S + oR, reinterpret_cast<uint32_t*>(S + oBB), reinterpret_cast<uint32_t*>(S + oT) };
     return e;
 }
 
 static int yk_decode_gradient_impl(yk_ctx* c, int sx, int sy, const uint8_t* bitmap, size_t bitmapBytes, const uint8_t* rgb, size_t rgbBytes, bool onDevice, int remapRange) {
     if (!c || !bitmap) return YK_ERR_BAD_ARG;
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    const YkDecView V = yk_dec_frame(c);
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
     const size_t need = yk_dpass_bytes(sx, sy, w, h);
     if (!need) return yk_fail(c, YK_ERR_BAD_ARG, "unsupported tile format");
@@ -1119,14 +1111,14 @@ static int yk_decode_gradient_impl(yk_ctx* c, int sx, int sy, const uint8_t* bit
     DPassIn in;
     YK_HIP(c, yk_dpass_stage(c, bitmap, need, rgb, rgbBytes, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, onDevice ? remapRange : 0, &in));
     { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
-    hipLaunchKernelGGL(yk_dec_owner_kernel, dim3((unsigned)((in.nBits + 255) / 256)), dim3(256), 0, c->stream, in.bm, in.nBits, g, w, h, latW, c->dLoaded, c->dLatticeOwner);
-    hipLaunchKernelGGL(yk_dec_corner_kernel<false>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, g, w, h, latW, c->dLoaded, c->dLatticeOwner,
+    hipLaunchKernelGGL(yk_dec_owner_kernel, dim3((unsigned)((in.nBits + 255) / 256)), dim3(256), 0, c->stream, in.bm, in.nBits, g, w, h, latW, V.loaded, V.owner);
+    hipLaunchKernelGGL(yk_dec_corner_kernel<false>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, g, w, h, latW, V.loaded, V.owner,
                        in.blockSums, (const uint8_t*)nullptr, (size_t)0, (uint8_t*)nullptr);
     hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, in.blockSums, (int)in.nb, in.total);
-    hipLaunchKernelGGL(yk_dec_corner_kernel<true>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, g, w, h, latW, c->dLoaded, c->dLatticeOwner,
-                       in.blockSums, in.rgb, rgbBytes, c->dMapRGB);
-    hipLaunchKernelGGL(yk_dec_render_kernel, dim3((unsigned)in.nWords), dim3(256), 0, c->stream, in.bm, in.nWords, g, w, h, latW, c->dMapRGB, c->dPlanes, c->dPlaneSize,
-                       w >> 3, reinterpret_cast<uint32_t*>(c->dTile4), (w + 15) >> 4);
+    hipLaunchKernelGGL(yk_dec_corner_kernel<true>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, g, w, h, latW, V.loaded, V.owner,
+                       in.blockSums, in.rgb, rgbBytes, V.mapRGB);
+    hipLaunchKernelGGL(yk_dec_render_kernel, dim3((unsigned)in.nWords), dim3(256), 0, c->stream, in.bm, in.nWords, g, w, h, latW, V.mapRGB, V.planes, c->dPlaneSize,
+                       w >> 3, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
     { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
     if (!onDevice) YK_HIP(c, hipStreamSynchronize(c->stream));            // the host buffers may be reused by the caller
@@ -1144,7 +1136,8 @@ int yk_decode_gradient_device(yk_ctx* c, int sx, int sy, const uint8_t* devBitma
 int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX, const int* tileShiftY, const uint8_t* const* devBitmap, const size_t* bitmapBytes,
                                   const uint8_t* const* devRgb, const size_t* rgbBytes, int remapRange) {
     if (!c || nPasses < 0 || (nPasses && (!tileShiftX || !tileShiftY || !devBitmap || !bitmapBytes || !devRgb || !rgbBytes))) return YK_ERR_BAD_ARG;
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    const YkDecView V = yk_dec_frame(c);
     if (nPasses == 0) return YK_OK;
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
     const size_t lat = (size_t)latW * (h / 4 + 1);
@@ -1176,18 +1169,18 @@ int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX,
     { const int rc = yk_dec_scratch(c, L.bytes); if (rc) return rc; }
     uint32_t* blockSums = reinterpret_cast<uint32_t*>(c->dScratch + L.oSums);
     uint32_t* perThread = reinterpret_cast<uint32_t*>(c->dScratch + L.oPerThread);
-    YK_HIP(c, hipMemsetAsync(c->dLatticeOwner, 0xFF, lat * 4, c->stream));
+    YK_HIP(c, hipMemsetAsync(V.owner, 0xFF, lat * 4, c->stream));
     { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
     // 1 clear + 5 launches for all passes (the per-pass form: 3 copies / clears + 5 launches per pass)
-    hipLaunchKernelGGL(yk_decall_owner_kernel, dim3((unsigned)((nBytesTot + 255) / 256)), dim3(256), 0, c->stream, pl, w, h, latW, c->dLoaded, c->dLatticeOwner);
-    hipLaunchKernelGGL(yk_decall_stream_kernel<false>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, c->dLoaded, c->dLatticeOwner, blockSums, perThread,
+    hipLaunchKernelGGL(yk_decall_owner_kernel, dim3((unsigned)((nBytesTot + 255) / 256)), dim3(256), 0, c->stream, pl, w, h, latW, V.loaded, V.owner);
+    hipLaunchKernelGGL(yk_decall_stream_kernel<false>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, V.loaded, V.owner, blockSums, perThread,
                        (uint8_t*)nullptr, 0u);
     hipLaunchKernelGGL(yk_decall_scan_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, pl);
-    hipLaunchKernelGGL(yk_decall_stream_kernel<true>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, c->dLoaded, c->dLatticeOwner, blockSums, perThread,
-                       c->dMapRGB, yk_dec_remap_factor(remapRange));
+    hipLaunchKernelGGL(yk_decall_stream_kernel<true>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, V.loaded, V.owner, blockSums, perThread,
+                       V.mapRGB, yk_dec_remap_factor(remapRange));
     // the render: a workgroup per 64x64 block of the image walks the passes in call order
     hipLaunchKernelGGL(yk_decall_render_blocks_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64))), dim3(256), 0, c->stream, pl, w, h, latW,
-                       c->dMapRGB, c->dPlanes, c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(c->dTile4), (w + 15) >> 4);
+                       V.mapRGB, V.planes, c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
     { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
     return YK_OK;
@@ -1199,7 +1192,7 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
     if (!c) return YK_ERR_BAD_ARG;
     if (nPasses < 0 || nPasses > 7) return yk_refuse(c, YK_ERR_BAD_ARG, "a batch takes 0..7 gradient passes per call");
     if (nPasses && (!tileShiftX || !tileShiftY || !devBitmap || !bitmapBytes || !devRgb || !rgbBytes)) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
-    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
     if (nPasses == 0) return YK_OK;
     const int w = c->dw, h = c->dh, latW = w / 4 + 1, N = c->dFrames;
     size_t need[7] = {};
@@ -1254,8 +1247,9 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
 
 static int yk_dec_split(yk_ctx* c) {                                       // UpdateTileAndRGBMask (YAIK_API.cpp:530-544), once
     if (c->dSplit) return YK_OK;
+    const YkDecView V = yk_dec_frame(c);
     const size_t lat = (size_t)(c->dw / 4 + 1) * (c->dh / 4 + 1), n = lat > c->dTile4Size ? lat : c->dTile4Size;
-    hipLaunchKernelGGL(yk_dec_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->dLoaded, lat, c->dTile4, c->dTile4Size);
+    hipLaunchKernelGGL(yk_dec_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, V.loaded, lat, V.tile4, c->dTile4Size);
     YK_HIP(c, hipGetLastError());
     c->dSplit = true;
     return YK_OK;
@@ -1264,7 +1258,7 @@ static int yk_dec_split(yk_ctx* c) {                                       // Up
 int yk_decode_split_masks(yk_ctx* c) {
     if (!c) return YK_ERR_BAD_ARG;
     YK_DEC_NO_BATCH(c, "yk_decode_split_masks");
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_HIP(c, hipSetDevice(c->device));
     return yk_dec_split(c);
 }
@@ -1274,7 +1268,8 @@ int yk_decode_gradient_planes(yk_ctx* c, int planeBit, int consistentMarks, cons
     YK_DEC_NO_BATCH(c, "yk_decode_gradient_planes");
     if (planeBit == 7) return yk_decode_gradient(c, 2, 2, bitmap, bitmapBytes, rgb, rgbBytes);
     if (planeBit < 1 || planeBit > 6) return yk_fail(c, YK_ERR_BAD_ARG, "planeBit must be 1..7");
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    const YkDecView V = yk_dec_frame(c);
     YK_HIP(c, hipSetDevice(c->device));
     { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }               // the plane-subset loops write without marking (reference behaviour): from here on the planes are fully defined
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
@@ -1285,15 +1280,15 @@ int yk_decode_gradient_planes(yk_ctx* c, int planeBit, int consistentMarks, cons
     DPassIn in;
     YK_HIP(c, yk_dpass_stage(c, bitmap, need, rgb, rgbBytes, hipMemcpyHostToDevice, 0, &in));
     const unsigned g256 = (unsigned)((in.nBits + 255) / 256);
-    hipLaunchKernelGGL(yk_dec44p_owner_kernel, dim3(g256), dim3(256), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, c->dLoaded, c->dLatticeOwner);
-    hipLaunchKernelGGL(yk_dec44p_corner_kernel<false>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, c->dLoaded, c->dLatticeOwner,
+    hipLaunchKernelGGL(yk_dec44p_owner_kernel, dim3(g256), dim3(256), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, V.loaded, V.owner);
+    hipLaunchKernelGGL(yk_dec44p_corner_kernel<false>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, V.loaded, V.owner,
                        in.blockSums, (const uint8_t*)nullptr, (size_t)0, (uint8_t*)nullptr);
     hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, in.blockSums, (int)in.nb, in.total);
-    hipLaunchKernelGGL(yk_dec44p_corner_kernel<true>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, c->dLoaded, c->dLatticeOwner,
-                       in.blockSums, in.rgb, rgbBytes, c->dMapRGB);
-    hipLaunchKernelGGL(yk_dec44p_mark_kernel, dim3((unsigned)((lat + 255) / 256)), dim3(256), 0, c->stream, c->dLatticeOwner, lat, planeBit, c->dLoaded);
-    hipLaunchKernelGGL(yk_dec44p_render_kernel, dim3(g256), dim3(256), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, consistentMarks, c->dMapRGB, c->dPlanes,
-                       c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(c->dTile4), c->dTile4Size, (w + 15) >> 4);
+    hipLaunchKernelGGL(yk_dec44p_corner_kernel<true>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, V.loaded, V.owner,
+                       in.blockSums, in.rgb, rgbBytes, V.mapRGB);
+    hipLaunchKernelGGL(yk_dec44p_mark_kernel, dim3((unsigned)((lat + 255) / 256)), dim3(256), 0, c->stream, V.owner, lat, planeBit, V.loaded);
+    hipLaunchKernelGGL(yk_dec44p_render_kernel, dim3(g256), dim3(256), 0, c->stream, in.bm, in.nBits, w, h, latW, planeBit, consistentMarks, V.mapRGB, V.planes,
+                       c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(V.tile4), c->dTile4Size, (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
@@ -1303,7 +1298,8 @@ __global__ void yk_dec1d_next_plane_kernel(uint32_t* __restrict__ runBase, const
 
 static int yk_decode_1d_impl(yk_ctx* c, const uint8_t* typeStream, size_t typeBytes, const uint8_t* pixStream, size_t pixBytes, int compressionRange, bool onDevice) {
     if (!c || !typeStream || !pixStream || compressionRange <= 0) return YK_ERR_BAD_ARG;
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    const YkDecView V = yk_dec_frame(c);
     YK_HIP(c, hipSetDevice(c->device));
     // dPlanesStale is the handle's: this call writes the unmarked quadrants of the SELECTED frame only, so on a batch the other frames get theirs zeroed first
     if (c->dFrames > 1) { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
@@ -1327,21 +1323,21 @@ static int yk_decode_1d_impl(yk_ctx* c, const uint8_t* typeStream, size_t typeBy
     { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
     if (!c->dSplit) {
         // no partial-plane pass ran: the three planes share one mask, one count / scan serves all of them (3 launches)
-        hipLaunchKernelGGL(yk_dec1d_count_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, c->dTile4, (w + 15) >> 4, tilesW, T8, bT, bP, offInBlk);
+        hipLaunchKernelGGL(yk_dec1d_count_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, V.tile4, (w + 15) >> 4, tilesW, T8, bT, bP, offInBlk);
         hipLaunchKernelGGL(yk_dec1d_scan_kernel, dim3(1), dim3(1024), 0, c->stream, bT, bP, (int)nb, tot);
         hipLaunchKernelGGL(yk_dec1d_kernel, dim3(gTiles, 3), dim3(256), 0, c->stream, (const uint32_t*)offInBlk, T8, bT, bP, tot,
-                           tyS, typeBytes, pxS, pixBytes, (1 << 24) / compressionRange, c->dPlanes, c->dPlaneSize, -1, (const uint32_t*)nullptr);
+                           tyS, typeBytes, pxS, pixBytes, (1 << 24) / compressionRange, V.planes, c->dPlaneSize, -1, (const uint32_t*)nullptr);
     } else {
         // per-plane masks (Decompress1D reads tile4x4Mask + planeID * tile4x4MaskSize, YAIK_3DTile.cpp:41): one plane after the other,
         // every plane's streams start where the plane before it stopped
         uint32_t* runBase = tot + 4;
         YK_HIP(c, hipMemsetAsync(runBase, 0, 2 * sizeof(uint32_t), c->stream));
         for (int p = 0; p < 3; p++) {
-            const uint8_t* t4 = c->dTile4 + (size_t)p * c->dTile4Size;
+            const uint8_t* t4 = V.tile4 + (size_t)p * c->dTile4Size;
             hipLaunchKernelGGL(yk_dec1d_count_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, t4, (w + 15) >> 4, tilesW, T8, bT, bP, offInBlk);
             hipLaunchKernelGGL(yk_dec1d_scan_kernel, dim3(1), dim3(1024), 0, c->stream, bT, bP, (int)nb, tot);
             hipLaunchKernelGGL(yk_dec1d_kernel, dim3(gTiles, 1), dim3(256), 0, c->stream, (const uint32_t*)offInBlk, T8, bT, bP, tot,
-                               tyS, typeBytes, pxS, pixBytes, (1 << 24) / compressionRange, c->dPlanes, c->dPlaneSize, p, (const uint32_t*)runBase);
+                               tyS, typeBytes, pxS, pixBytes, (1 << 24) / compressionRange, V.planes, c->dPlaneSize, p, (const uint32_t*)runBase);
             hipLaunchKernelGGL(yk_dec1d_next_plane_kernel, dim3(1), dim3(64), 0, c->stream, runBase, (const uint32_t*)tot);
         }
     }
@@ -1366,7 +1362,7 @@ int yk_decode_1d_batch_device(yk_ctx* c, const uint8_t* const* devType, const si
     if (!c) return YK_ERR_BAD_ARG;
     if (!devType || !typeBytes || !devPix || !pixBytes) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
     if (compressionRange <= 0) return yk_refuse(c, YK_ERR_BAD_ARG, "compressionRange must be positive");
-    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
     const int N = c->dFrames;
     for (int f = 0; f < N; f++) {
         if ((typeBytes[f] && !devType[f]) || (pixBytes[f] && !devPix[f])) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL 1-D stream with a length");
@@ -1418,12 +1414,13 @@ int yk_decode_mask(yk_ctx* c, const uint8_t* bits, int bw, int bh, uint8_t* host
 
 int yk_decode_planes(yk_ctx* c, uint8_t* hostR, uint8_t* hostG, uint8_t* hostB, size_t capEach) {
     if (!c || !hostR || !hostG || !hostB) return YK_ERR_BAD_ARG;
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    const YkDecView V = yk_dec_frame(c);
     if (capEach < c->dPlaneSize) return yk_fail(c, YK_ERR_RANGE, "plane buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
     { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
     uint8_t* dst[3] = { hostR, hostG, hostB };
-    for (int p = 0; p < 3; p++) YK_HIP(c, hipMemcpyAsync(dst[p], c->dPlanes + p * c->dPlaneSize, c->dPlaneSize, hipMemcpyDeviceToHost, c->stream));
+    for (int p = 0; p < 3; p++) YK_HIP(c, hipMemcpyAsync(dst[p], V.planes + p * c->dPlaneSize, c->dPlaneSize, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }
@@ -1434,7 +1431,7 @@ int yk_decode_planes(yk_ctx* c, uint8_t* hostR, uint8_t* hostG, uint8_t* hostB, 
 static int yk_decode_output_impl(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, const uint8_t* hostAlpha, int strideA, bool refRGBA,
                                  const uint8_t* devAlpha = nullptr) {
     if (!c || !hostOut) return YK_ERR_BAD_ARG;
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     if (devAlpha) { hostAlpha = devAlpha; strideA = c->dw; }                   // the plane yk_decode_alpha left in HBM: no host copy
     const int w = c->dw, h = c->dh, bpp = (hostAlpha && !refRGBA) ? 4 : 3;
     const size_t rowBytes = (size_t)w * bpp + (refRGBA && hostAlpha ? 1 : 0);
@@ -1478,7 +1475,7 @@ int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t 
     if (!devOut) return yk_fail(c, YK_ERR_BAD_ARG, "devOut is NULL");
     if (channels != 3 && channels != 4) return yk_fail(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
     if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_fail(c, YK_ERR_BAD_ARG, "alpha must be -1 (the decoded plane) or 0..255");
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     const size_t w = (size_t)c->dw, h = (size_t)c->dh;
     if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
         return yk_fail(c, YK_ERR_BAD_ARG, "row or plane pitch too small for the image");
@@ -1494,7 +1491,7 @@ int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, s
     if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "devOut is NULL");
     if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
     if (channels == 4 && (alpha < 0 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "alpha must be 0..255 (a batch has no decoded alpha plane)");
-    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
     const size_t w = (size_t)c->dw, h = (size_t)c->dh;
     if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
         return yk_refuse(c, YK_ERR_BAD_ARG, "row or plane pitch too small for the image");
@@ -1509,7 +1506,7 @@ int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, s
 int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes) {
     if (!c) return YK_ERR_BAD_ARG;
     if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "devOut is NULL");
-    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
     if (!c->dAlphaValid || !c->dAlphaBatch) return yk_refuse(c, YK_ERR_STATE, "yk_decode_alpha_batch_device first: the batch has no decoded alpha planes");
     const size_t w = (size_t)c->dw, h = (size_t)c->dh;
     if (planeBytes == 0 ? rowBytes < w * 4 : (rowBytes < w || planeBytes / h < rowBytes))
@@ -1526,7 +1523,7 @@ int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBy
 static int yk_dec_compare_common(yk_ctx* c, int channels, const void* out, bool batch) {
     if (!out) return yk_refuse(c, YK_ERR_BAD_ARG, "out is NULL");
     if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
-    if (!c->dB.planes) return yk_refuse(c, YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
     if (channels == 4 && !c->dAlphaValid)
         return yk_refuse(c, YK_ERR_STATE, "channels = 4 needs the decoded alpha: yk_decode_alpha or yk_decode_alpha_batch_device first");
     return YK_OK;
@@ -1574,28 +1571,28 @@ int yk_decode_compare_planes_device(yk_ctx* c, const int32_t* const frame0Planes
 }
 
 const uint8_t* yk_decode_planes_device(yk_ctx* c, size_t* planeSize) {
-    if (!c || !c->dPlanes) return nullptr;
+    if (!c || !yk_dec_begun(c)) return nullptr;
     if (hipSetDevice(c->device) != hipSuccess || yk_dec_settle(c) != YK_OK) return nullptr;
     if (planeSize) *planeSize = c->dPlaneSize;
-    return c->dPlanes;
+    return yk_dec_frame(c).planes;
 }
 
 int yk_decode_tile4x4_planes(yk_ctx* c, uint8_t* hostOut, size_t cap) {     // the three planes of tile4x4Mask (planes 1, 2 are meaningful once split)
     if (!c || !hostOut) return YK_ERR_BAD_ARG;
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     if (cap < 3 * c->dTile4Size) return yk_fail(c, YK_ERR_RANGE, "tile4x4 buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, hipMemcpyAsync(hostOut, c->dTile4, 3 * c->dTile4Size, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(hostOut, yk_dec_frame(c).tile4, 3 * c->dTile4Size, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }
 
 int yk_decode_tile4x4(yk_ctx* c, uint8_t* hostOut, size_t cap) {
     if (!c || !hostOut) return YK_ERR_BAD_ARG;
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     if (cap < c->dTile4Size) return yk_fail(c, YK_ERR_RANGE, "tile4x4 buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, hipMemcpyAsync(hostOut, c->dTile4, c->dTile4Size, hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipMemcpyAsync(hostOut, yk_dec_frame(c).tile4, c->dTile4Size, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
 }

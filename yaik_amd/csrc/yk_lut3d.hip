@@ -843,6 +843,7 @@ int yk_lut_search(yk_ctx* c, int shiftX, int shiftY, int* matched) {
     YK_HIP(c, hipSetDevice(c->device));
     YkLutState* S = c->lut;
     const int w = c->fullW, h = c->h, nPix = (1 << shiftX) * (1 << shiftY);
+    const YkFrameView V = yk_frame(c);
     const size_t nSlots = (size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount, nb = (nSlots + 1023) / 1024;
     LutSlot* const slots = S->sh.slots; uint8_t* const slotIdx = S->sh.slotIdx; uint32_t* const sums = S->sh.sums;    // yk_lut_start sized them
     YkLutBank bank; bank.ptab = S->ptab; bank.ptabM = S->ptabM; bank.pairMode = S->pairMode; bank.patStart = S->patStart; bank.pos = S->posAll; bank.fac = S->facAll;
@@ -858,7 +859,7 @@ int yk_lut_search(yk_ctx* c, int shiftX, int shiftY, int* matched) {
     if (nCand) {
         { int rc = yk_stage_begin(c, YK_STAGE_LUT3D); if (rc) return rc; }
 #define YK_LUT_LAUNCH(SX_, SY_) hipLaunchKernelGGL((yk_lut_search_kernel<SX_, SY_>), dim3(nCand), dim3(nPix > 64 ? 128 : 64), (size_t)S->nPat * (48 + 1 + 16) * sizeof(int), c->stream,       \
-                           c->plane[0], c->plane[1], c->plane[2], c->strideElems, w, h, g, bank, reinterpret_cast<uint32_t*>(c->img.covCh.p), c->covChStride, c->mtW, slots, slotIdx,               \
+                           V.plane[0], V.plane[1], V.plane[2], c->strideElems, w, h, g, bank, reinterpret_cast<uint32_t*>(c->img.covCh.p), c->covChStride, c->mtW, slots, slotIdx,               \
                            reinterpret_cast<uint32_t*>(S->sh.map[g.mapId].p), S->sh.list)
         switch (g.mapId) {                                                  // one instantiation per tile shape
             case 0: YK_LUT_LAUNCH(4, 3); break;
@@ -1035,7 +1036,8 @@ int yk_decode_lut3d(yk_ctx* c, const uint8_t* const maps[6], const size_t mapByt
                     const uint8_t* const idx[4], const size_t idxBytes[4], size_t consumed[6]) {
     if (!c || !maps || !mapBytes || !idx || !idxBytes) return YK_ERR_BAD_ARG;
     YK_DEC_NO_BATCH(c, "yk_decode_lut3d");
-    if (!c->dPlanes) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    const YkDecView V = yk_dec_frame(c);
     if (!c->lutDec) return yk_fail(c, YK_ERR_STATE, "yk_decode_assign_lut first");
     if (c->dSplit) return yk_fail(c, YK_ERR_STATE, "a '3DTL' chunk comes before the masks are split ('1DTL', plane-subset chunks)");
     YK_HIP(c, hipSetDevice(c->device));
@@ -1071,7 +1073,7 @@ int yk_decode_lut3d(yk_ctx* c, const uint8_t* const maps[6], const size_t mapByt
         hipLaunchKernelGGL(yk_dl_rank_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, dMap, nSlots, g, w, h, rankBase);
         hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, rankBase, (int)nb, totals);
 #define YK_DL_ARGS dMap, nSlots, g, w, h, rankBase, nb, byteSums, dTiles, tileBase, (unsigned long long)nTiles, dColors, dIdx[0], dIdx[1], dIdx[2], dIdx[3], ib[0], ib[1], ib[2], ib[3], \
-                   c->lutDec->tbl[0], c->lutDec->tbl[1], c->lutDec->tbl[2], c->lutDec->tbl[3], c->lutDec->nPat, c->dPlanes, c->dPlaneSize, w >> 3, c->dTile4, (w + 15) >> 4
+                   c->lutDec->tbl[0], c->lutDec->tbl[1], c->lutDec->tbl[2], c->lutDec->tbl[3], c->lutDec->nPat, V.planes, c->dPlaneSize, w >> 3, V.tile4, (w + 15) >> 4
         hipLaunchKernelGGL(yk_dl_tile_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, c->stream, YK_DL_ARGS);
         for (int f = 0; f < 4; f++) hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, byteSums + f * nb, (int)nb, totals + 1 + f);
         // The counting launch and the scans know what this pass would consume: tiles / colours and index bytes per depth.  The fill reads the
@@ -1087,7 +1089,7 @@ int yk_decode_lut3d(yk_ctx* c, const uint8_t* const maps[6], const size_t mapByt
         if (!fits) { shortStream = true; break; }
         hipLaunchKernelGGL(yk_dl_tile_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, c->stream, YK_DL_ARGS);
 #undef YK_DL_ARGS
-        hipLaunchKernelGGL(yk_dl_mark_kernel, dim3((unsigned)((nSlots + 255) / 256)), dim3(256), 0, c->stream, dMap, nSlots, g, w, h, reinterpret_cast<uint32_t*>(c->dTile4), (w + 15) >> 4);
+        hipLaunchKernelGGL(yk_dl_mark_kernel, dim3((unsigned)((nSlots + 255) / 256)), dim3(256), 0, c->stream, dMap, nSlots, g, w, h, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4);
         e = hipGetLastError();
         tileBase += tot[0];
         for (int f = 0; f < 4; f++) ib[f] += tot[1 + f];

@@ -177,13 +177,14 @@ int yk_pp_activate(yk_ctx* c) {
     // the corner lattice of the RGB passes must exist: it tells which lattice points every plane already has
     if (!c->cornersReady) { int rc = yk_launch_corners(c); if (rc) return rc; }
     c->covChStride = (nMT + 7) & ~(size_t)7;
+    const YkFrameView V = yk_frame(c);
     if (!c->img.covCh) {
         YK_HIP(c, c->img.covCh.alloc(c->stream, 3 * c->covChStride, 16));
         YK_HIP(c, c->img.mapped3.alloc(c->stream, lat + 16));
     }
     YK_HIP(c, hipMemsetAsync(c->img.covCh, 0, 3 * c->covChStride * sizeof(uint16_t) + 16, c->stream));
     const size_t n = nMT > lat ? nMT : lat;
-    hipLaunchKernelGGL(yk_pp_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->coverage, nMT, c->img.covCh, c->covChStride,
+    hipLaunchKernelGGL(yk_pp_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, V.coverage, nMT, c->img.covCh, c->covChStride,
                        c->img.latticeOwner, lat, c->img.mapped3);
     YK_HIP(c, hipGetLastError());
     c->ppActive = true;
@@ -206,6 +207,7 @@ int yk_gradient_partial_pass(yk_ctx* c, int rejectFactor, int planeBit, int sx, 
     const size_t lat = (size_t)latW * latH, nMT = (size_t)c->mtW * c->mtH;
     { int rc = yk_pp_activate(c); if (rc) return rc; }
     const PPGeo g = yk_pp_geo(sx, sy, w);
+    const YkFrameView V = yk_frame(c);
     const size_t nBits = (size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount, nWords = (nBits + 31) / 32, nb = (nBits + 1023) / 1024;
     const size_t needScratch = lat + nb + 64;
     YK_HIP(c, c->img.ppBitmap.reserve(c->stream, nWords, 16));
@@ -215,12 +217,12 @@ int yk_gradient_partial_pass(yk_ctx* c, int rejectFactor, int planeBit, int sx, 
     YK_HIP(c, hipMemsetAsync(c->img.ppBitmap, 0, nWords * 4, c->stream));
     YK_HIP(c, hipMemsetAsync(owner, 0xFF, lat * 4, c->stream));
     YK_HIP(c, hipMemsetAsync(total, 0, 8, c->stream));
-    PPPlanes P; for (int n = 0; n < 3; n++) P.p[n] = c->plane[n];
+    PPPlanes P; for (int n = 0; n < 3; n++) P.p[n] = V.plane[n];
     P.strideElems = c->strideElems; P.w = w; P.h = h; P.hAvail = h + c->halo;
     const unsigned g256 = (unsigned)((nBits + 255) / 256);
     hipLaunchKernelGGL(yk_pp_decide_kernel, dim3(g256), dim3(256), 0, c->stream, P, g, nBits, planeBit, rejectFactor, c->img.covCh, c->covChStride, c->mtW, c->img.ppBitmap, accepted);
     hipLaunchKernelGGL(yk_pp_paint_kernel, dim3(g256), dim3(256), 0, c->stream, g, nBits, planeBit, c->img.ppBitmap, reinterpret_cast<uint32_t*>(c->img.covCh.p), c->covChStride,
-                       reinterpret_cast<uint32_t*>(c->coverage), c->mtW);
+                       reinterpret_cast<uint32_t*>(V.coverage), c->mtW);
     hipLaunchKernelGGL(yk_pp_owner_kernel, dim3(g256), dim3(256), 0, c->stream, g, nBits, planeBit, c->img.ppBitmap, latW, c->img.mapped3, owner);
     hipLaunchKernelGGL(yk_pp_stream_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, c->stream, P, g, nBits, planeBit, c->img.ppBitmap, latW, c->img.mapped3, owner, blockSums, (uint8_t*)nullptr);
     hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, (int)nb, total);
@@ -247,6 +249,7 @@ int yk_gradient_preview(yk_ctx* c, int pass, int32_t* hostOut, size_t capElems) 
     YK_HIP(c, hipSetDevice(c->device));
     const int w = c->fullW, h = c->h;
     const size_t planeElems = (size_t)w * h;
+    const YkFrameView V = yk_frame(c);
     if (!c->img.preview) { YK_HIP(c, c->img.preview.alloc(c->stream, 3 * planeElems)); c->previewFresh = false; }
     if (!c->previewFresh) {                                                  // a new encode starts from untouched planes (INT32_MIN = no tile wrote here)
         hipLaunchKernelGGL(yk_pp_fill_i32_kernel, dim3((unsigned)((3 * planeElems + 255) / 256)), dim3(256), 0, c->stream, c->img.preview, 3 * planeElems, (int32_t)0x80000000);
@@ -256,10 +259,10 @@ int yk_gradient_preview(yk_ctx* c, int pass, int32_t* hostOut, size_t capElems) 
     const int sx = pass < 7 ? shp[pass][0] : c->ppLastSx, sy = pass < 7 ? shp[pass][1] : c->ppLastSy, planeBit = pass < 7 ? 7 : c->ppLastBit;
     const PPGeo g = yk_pp_geo(sx, sy, w);
     const size_t nBits = (size_t)g.xBB * ((h + g.bigY - 1) / g.bigY) * g.bitCount;
-    PPPlanes P; for (int n = 0; n < 3; n++) P.p[n] = c->plane[n];
+    PPPlanes P; for (int n = 0; n < 3; n++) P.p[n] = V.plane[n];
     P.strideElems = c->strideElems; P.w = w; P.h = h; P.hAvail = h + c->halo;
-    const uint32_t* bm = pass < 7 ? reinterpret_cast<const uint32_t*>(c->bitmap[pass]) : c->img.ppBitmap;
-    if (pass < 7 && (c->bitmapBytes[pass] & 3)) YK_HIP(c, hipMemsetAsync(c->bitmap[pass] + c->bitmapBytes[pass], 0, 4 - (c->bitmapBytes[pass] & 3), c->stream));
+    const uint32_t* bm = pass < 7 ? reinterpret_cast<const uint32_t*>(V.bitmap[pass]) : c->img.ppBitmap;
+    if (pass < 7 && (c->bitmapBytes[pass] & 3)) YK_HIP(c, hipMemsetAsync(V.bitmap[pass] + c->bitmapBytes[pass], 0, 4 - (c->bitmapBytes[pass] & 3), c->stream));
     hipLaunchKernelGGL(yk_pp_preview_kernel, dim3((unsigned)((nBits + 255) / 256)), dim3(256), 0, c->stream, P, g, nBits, planeBit, bm, c->img.preview, planeElems);
     YK_HIP(c, hipGetLastError());
     if (hostOut) {
@@ -302,7 +305,7 @@ int yk_coverage_plane(yk_ctx* c, int plane, uint16_t* hostOut, size_t capElems) 
     const size_t n = (size_t)c->mtW * c->mtH;
     if (capElems < n) return yk_fail(c, YK_ERR_RANGE, "coverage buffer too small");
     YK_HIP(c, hipSetDevice(c->device));
-    const uint16_t* src = c->ppActive ? c->img.covCh + (size_t)plane * c->covChStride : c->coverage;      // before any partial pass the planes agree
+    const uint16_t* src = c->ppActive ? c->img.covCh + (size_t)plane * c->covChStride : yk_frame(c).coverage;      // before any partial pass the planes agree
     YK_HIP(c, hipMemcpyAsync(hostOut, src, n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;

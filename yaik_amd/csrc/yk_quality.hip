@@ -212,7 +212,7 @@ static void yk_q_launch(const YkQArgs& a, unsigned groups, unsigned nFrames, hip
 int yk_quality_compare(yk_ctx* c, const YkQualitySrc& q, int firstFrame, int nFrames, int channels, yk_quality* out, uint32_t* devTileSse) {
     YkQArgs a = {};
     const size_t w = (size_t)c->dw, h = (size_t)c->dh, N = (size_t)nFrames;
-    a.planes = c->dB.planes + (size_t)firstFrame * c->dStride.planes; a.planeSize = c->dPlaneSize; a.planesFrame = c->dStride.planes;
+    a.planes = yk_dec_frame(c, firstFrame).planes; a.planeSize = c->dPlaneSize; a.planesFrame = c->dStride.planes;
     if (channels == 4) {
         a.alphaFrame = c->dAlphaBatch ? c->dAlphaStride : 0;
         a.alpha = c->dAlpha + (size_t)firstFrame * a.alphaFrame; a.strideA = w;

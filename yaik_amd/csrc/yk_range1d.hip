@@ -426,6 +426,7 @@ int yk_range1d_encode(yk_ctx* c) {
     if (!c) return YK_ERR_BAD_ARG;
     if (!c->encoded) return yk_fail(c, YK_ERR_STATE, "yk_encode_tiles first (the 1-D path codes what the gradient passes left uncovered)");
     YK_HIP(c, hipSetDevice(c->device));
+    const YkFrameView V = yk_frame(c);
     const size_t T8 = (size_t)c->tilesW * c->tilesH, nb = (T8 + 1023) / 1024;
     if (!c->img.r1Slots) {
         YK_HIP(c, c->img.r1Slots.alloc(c->stream, 3 * T8 * 64));
@@ -441,17 +442,17 @@ int yk_range1d_encode(yk_ctx* c) {
         // three launches: offsets of every tile from the coverage, one scan, the coder writing straight into the streams (before: coder into
         // per-tile slots, two block sums, two scans, a compaction pass re-reading the slots)
         { int rc = yk_stage_begin(c, YK_STAGE_RANGE1D_PACK); if (rc) return rc; }
-        hipLaunchKernelGGL(yk_r1_offsets_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, c->coverage, c->mtW, c->tilesW, T8, cT, bT, bP);
+        hipLaunchKernelGGL(yk_r1_offsets_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, V.coverage, c->mtW, c->tilesW, T8, cT, bT, bP);
         hipLaunchKernelGGL(yk_r1_scan_kernel, dim3(1), dim3(1024), 0, c->stream, bT, bP, (int)nb, tot);
         { int rc = yk_stage_end(c, YK_STAGE_RANGE1D_PACK); if (rc) return rc; }
         { int rc = yk_stage_begin(c, YK_STAGE_RANGE1D); if (rc) return rc; }
         R1Direct D; D.offInBlk = cT; D.blockT = bT; D.blockP = bP; D.totals = tot; D.pixOut = c->img.r1Pix; D.typeOut = c->img.r1Type; D.pixCache = c->img.pixCache;
         if (c->pixCacheValid && c->img.pixCache)                                  // the fused kernel left the uncovered cells' pixels: 4 B per pixel instead of 12
-            hipLaunchKernelGGL((yk_range1d_kernel<true, true>), dim3(nStrips), dim3(64), 0, c->stream, c->plane[0], c->plane[1], c->plane[2], c->strideElems,
-                               c->fullW, c->h, c->coverage, c->mtW, c->tilesW, T8, (uint8_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, -1, D);
+            hipLaunchKernelGGL((yk_range1d_kernel<true, true>), dim3(nStrips), dim3(64), 0, c->stream, V.plane[0], V.plane[1], V.plane[2], c->strideElems,
+                               c->fullW, c->h, V.coverage, c->mtW, c->tilesW, T8, (uint8_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, -1, D);
         else
-            hipLaunchKernelGGL(yk_range1d_kernel<true>, dim3(nStrips), dim3(64), 0, c->stream, c->plane[0], c->plane[1], c->plane[2], c->strideElems,
-                               c->fullW, c->h, c->coverage, c->mtW, c->tilesW, T8, (uint8_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, -1, D);
+            hipLaunchKernelGGL(yk_range1d_kernel<true>, dim3(nStrips), dim3(64), 0, c->stream, V.plane[0], V.plane[1], V.plane[2], c->strideElems,
+                               c->fullW, c->h, V.coverage, c->mtW, c->tilesW, T8, (uint8_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, -1, D);
         YK_HIP(c, hipGetLastError());
         { int rc = yk_stage_end(c, YK_STAGE_RANGE1D); if (rc) return rc; }
         // the totals stay on the device until a getter needs them (yk_range1d_finish): callers that keep frames in flight are not stopped here
@@ -462,7 +463,7 @@ int yk_range1d_encode(yk_ctx* c) {
         uint32_t* runBase = tot + 4;                                         // [4][2]: (tile-planes, pixel bytes) before plane p; [3] = totals
         YK_HIP(c, hipMemsetAsync(runBase, 0, 2 * sizeof(uint32_t), c->stream));
         for (int p = 0; p < 3; p++, runBase += 2) {
-            hipLaunchKernelGGL(yk_range1d_kernel<false>, dim3(nStrips), dim3(64), 0, c->stream, c->plane[0], c->plane[1], c->plane[2], c->strideElems,
+            hipLaunchKernelGGL(yk_range1d_kernel<false>, dim3(nStrips), dim3(64), 0, c->stream, V.plane[0], V.plane[1], V.plane[2], c->strideElems,
                                c->fullW, c->h, c->img.covCh + (size_t)p * c->covChStride, c->mtW, c->tilesW, T8, c->img.r1Slots, c->img.r1Params, cT, cP, p, R1Direct{});
             hipLaunchKernelGGL(yk_u32_blocksum_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, cT, T8, bT);
             hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, bT, (int)nb, tot);

@@ -345,16 +345,14 @@ extern "C" int yk_set_cross_check_launcher(void* fn) { g_crossCheckLauncher = re
 
 int yk_launch_alpha(yk_ctx* c, bool batch) {
     const int F = batch ? c->nFrames : 1;
-    uint8_t* keep = batch ? c->B.keep : c->keep;
-    int32_t* bounds = batch ? c->B.bounds : c->bounds;
-    const int32_t* alpha = batch ? c->B.plane[3] : c->plane[3];
+    const YkFrameView V = yk_frame(c, batch ? 0 : c->curFrame);   // a batch launch starts at frame 0 and strides on by fs
     const long long nUnits = (long long)yk_alpha_units(c->fullW, c->mtH);
     if (nUnits * F > 0x7FFFFFFFLL) return yk_fail(c, YK_ERR_BAD_ARG, "too many alpha work units for one launch");
     yk_i4* unitBox = reinterpret_cast<yk_i4*>(static_cast<int*>(c->img.alphaUnitBox));
     // never fewer waves than units: nothing loops, a wave ends after its unit
-    hipLaunchKernelGGL(yk_alpha_kernel, dim3((unsigned)((nUnits * F + YK_ALPHA_WAVES - 1) / YK_ALPHA_WAVES)), dim3(64 * YK_ALPHA_WAVES), 0, c->stream, alpha, c->strideElems,
-                       c->fullW, c->h, c->y0, keep, c->mtW, c->mtH, (unsigned long long)c->fs.plane, (unsigned long long)c->fs.keep, unitBox, (unsigned)(nUnits * F));
-    hipLaunchKernelGGL(yk_alpha_box_kernel, dim3((unsigned)F), dim3(256), 0, c->stream, unitBox, (int)nUnits, bounds);
+    hipLaunchKernelGGL(yk_alpha_kernel, dim3((unsigned)((nUnits * F + YK_ALPHA_WAVES - 1) / YK_ALPHA_WAVES)), dim3(64 * YK_ALPHA_WAVES), 0, c->stream, V.plane[3], c->strideElems,
+                       c->fullW, c->h, c->y0, V.keep, c->mtW, c->mtH, (unsigned long long)c->fs.plane, (unsigned long long)c->fs.keep, unitBox, (unsigned)(nUnits * F));
+    hipLaunchKernelGGL(yk_alpha_box_kernel, dim3((unsigned)F), dim3(256), 0, c->stream, unitBox, (int)nUnits, V.bounds);
     YK_HIP(c, hipGetLastError());
     c->boundsOff = 8;                                           // whole image / batch: the accumulators are the box; a stripe caller replaces it (yk_alpha_finish)
     return YK_OK;
@@ -365,37 +363,32 @@ int yk_launch_alpha_finish(yk_ctx* c, const int32_t* globalBBox) {
     if (globalBBox) {
         int32_t b[5] = { globalBBox[0], globalBBox[1], globalBBox[2], globalBBox[3], 0 };
         b[4] = (b[0] == 0 && b[1] == 0 && b[2] == c->fullW && b[3] == c->fullH) ? 1 : 0;
-        YK_HIP(c, hipMemcpyAsync(c->bounds, b, sizeof b, hipMemcpyHostToDevice, c->stream));
+        YK_HIP(c, hipMemcpyAsync(yk_frame(c).bounds, b, sizeof b, hipMemcpyHostToDevice, c->stream));
         c->boundsOff = 0;
     }
     return YK_OK;
 }
 
 int yk_launch_encode(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst, bool batch) {
+    const YkFrameView V = yk_frame(c, batch ? 0 : c->curFrame);   // a batch launch starts at frame 0 and strides on by fs
     YkEncodeParams P;
-    for (int i = 0; i < 4; i++) P.plane[i] = batch ? c->B.plane[i] : c->plane[i];
+    for (int i = 0; i < 4; i++) P.plane[i] = V.plane[i];
     P.strideElems = c->strideElems; P.w = c->fullW; P.h = c->h; P.hAvail = c->h + c->halo; P.y0 = c->y0; P.fullH = c->fullH;
     P.rejectFactor = rejectFactor; P.startMode = mode3BitOnly ? 3 : 0; P.wantDst = wantDst; P.ablate = c->ablate;
-    P.keep = (c->nPlanes == 4) ? (batch ? c->B.keep : c->keep) : nullptr;
-    P.bounds = (c->nPlanes == 4) ? (batch ? c->B.bounds : c->bounds) + c->boundsOff : nullptr;   // {x0, y0, x1, y1}; the kernel derives the discard rule
-    for (int i = 0; i < 7; i++) P.bitmap[i] = batch ? c->B.bitmap[i] : c->bitmap[i];
-    P.coverage = batch ? c->B.coverage : c->coverage; P.tileDef = batch ? c->B.tileDef : c->tileDef;
-    P.tileCount = batch ? c->B.tileCount : c->tileCount; P.slots = batch ? c->B.slots : c->slots;
-    P.blockCnt = c->kernelVersion == 2 ? (batch ? c->B.blockCnt : c->blockCnt) : nullptr;
+    P.keep = (c->nPlanes == 4) ? V.keep : nullptr;
+    P.bounds = (c->nPlanes == 4) ? V.bounds + c->boundsOff : nullptr;   // {x0, y0, x1, y1}; the kernel derives the discard rule
+    for (int i = 0; i < 7; i++) P.bitmap[i] = V.bitmap[i];
+    P.coverage = V.coverage; P.tileDef = V.tileDef; P.tileCount = V.tileCount; P.slots = V.slots;
+    P.blockCnt = c->kernelVersion == 2 ? V.blockCnt : nullptr;
     for (int i = 0; i < 3; i++) P.dst[i] = c->img.dst[i];
     P.tilesW = c->tilesW; P.tilesH = c->tilesH; P.mtW = c->mtW; P.mtH = c->mtH;
     P.xBB64 = (c->fullW + 63) / 64; P.yBB64 = (c->h + 63) / 64; P.xBB32 = (c->fullW + 31) / 32; P.yBB32 = (c->h + 31) / 32;
     P.nFrames = batch ? c->nFrames : 1; P.fs = c->fs;
     P.qtab = c->qtab;
-    P.small = c->B.small;                                       // frame f of an array sits at its offset + f * stride (yk_alloc_image)
-    for (int i = 0; i < 7; i++) P.oBm[i] = (uint32_t)(c->B.bitmap[i] - c->B.small);
-    P.oBm0b = (uint32_t)(c->B.bm0b - c->B.small); P.oCov = (uint32_t)(reinterpret_cast<uint8_t*>(c->B.coverage) - c->B.small);
-    P.oInfo = (uint32_t)(reinterpret_cast<uint8_t*>(c->B.tileInfo) - c->B.small); P.oRun = (uint32_t)(reinterpret_cast<uint8_t*>(c->B.runSums) - c->B.small);
-    if (!batch && c->curFrame) {                                // a selected frame of a batch encoded on its own
-        for (int i = 0; i < 7; i++) P.oBm[i] += (uint32_t)(c->curFrame * c->fs.bitmap[i]);
-        P.oBm0b += (uint32_t)(c->curFrame * c->fs.bm0b); P.oCov += (uint32_t)(c->curFrame * c->fs.coverage * 2);
-        P.oInfo += (uint32_t)(c->curFrame * c->fs.tileInfo * 8); P.oRun += (uint32_t)(c->curFrame * c->fs.runSums * 4);
-    }
+    P.small = V.small;                                          // the view's arrays of the small-output arena, as byte offsets into it
+    auto off = [&](const void* p) { return (uint32_t)(static_cast<const uint8_t*>(p) - V.small); };
+    for (int i = 0; i < 7; i++) P.oBm[i] = off(V.bitmap[i]);
+    P.oBm0b = off(V.bm0b); P.oCov = off(V.coverage); P.oInfo = off(V.tileInfo); P.oRun = off(V.runSums);
     P.pixCache = nullptr; c->pixCacheValid = false;
     if (c->pixCacheOn && !batch && c->kernelVersion == 2 && c->nFrames == 1) {
         if (!c->img.pixCache) YK_HIP(c, c->img.pixCache.alloc(c->stream, (size_t)P.xBB64 * 64 * ((size_t)(c->h + 15) / 16 * 16) / 4, 4096));
@@ -405,8 +398,8 @@ int yk_launch_encode(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst,
     // version 1 = the cross-check implementation of the test suite (tests/csrc/yk_encode_v1.hip), registered at run time
     if (batch) return yk_fail(c, YK_ERR_STATE, "batches need kernel version 2");
     if (c->nPlanes == 4) {                                      // it reads the published form bounds[0..4]
-        hipLaunchKernelGGL(yk_alpha_publish_kernel, dim3(1), dim3(1), 0, c->stream, c->bounds, c->boundsOff, c->fullW, c->fullH);
-        P.bounds = c->bounds;
+        hipLaunchKernelGGL(yk_alpha_publish_kernel, dim3(1), dim3(1), 0, c->stream, V.bounds, c->boundsOff, c->fullW, c->fullH);
+        P.bounds = V.bounds;
     }
     if (!g_crossCheckLauncher) return yk_fail(c, YK_ERR_STATE, "kernel version 1 is not part of this library: register it with yk_set_cross_check_launcher");
     if (g_crossCheckLauncher(c->stream, &P) != 0) return yk_fail(c, YK_ERR_HIP, "cross-check kernel launch", hipGetLastError());
@@ -416,27 +409,25 @@ int yk_launch_encode(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst,
 int yk_launch_pack(yk_ctx* c, bool batch) {
     const size_t T8 = (size_t)c->tilesW * c->tilesH;
     const int nb = c->nScanBlocks, F = batch ? c->nFrames : 1;
-    uint32_t* blockCnt = batch ? c->B.blockCnt : c->blockCnt; uint32_t* blockSums = batch ? c->B.blockSums : c->blockSums;
-    uint32_t* totals = batch ? c->B.totals : c->totals; uint8_t* nibOut = batch ? c->B.nibOut : c->nibOut;
-    if (c->kernelVersion != 2) hipLaunchKernelGGL(yk_scan1_kernel, dim3(nb), dim3(1024), 0, c->stream, c->tileCount, T8, c->blockCnt);
+    const YkFrameView V = yk_frame(c, batch ? 0 : c->curFrame);   // a batch launch starts at frame 0 and strides on by fs
+    if (c->kernelVersion != 2) hipLaunchKernelGGL(yk_scan1_kernel, dim3(nb), dim3(1024), 0, c->stream, V.tileCount, T8, V.blockCnt);
     // second-generation fused kernel: per-run sums and per-strip 16x16 bytes instead of atomics, per-tile records instead of count / definition arrays
     const bool v2 = c->kernelVersion == 2;
-    const size_t f0 = batch ? 0 : (size_t)c->curFrame;
-    const uint32_t* runSums = (v2 && (c->tilesW & 7) == 0) ? c->B.runSums + f0 * c->fs.runSums : nullptr;
-    const uint8_t* bm0b = v2 ? c->B.bm0b + f0 * c->fs.bm0b : nullptr;
-    const uint2* tileInfo = v2 ? c->B.tileInfo + f0 * c->fs.tileInfo : nullptr;
+    const uint32_t* runSums = (v2 && (c->tilesW & 7) == 0) ? V.runSums : nullptr;
+    const uint8_t* bm0b = v2 ? V.bm0b : nullptr;
+    const uint2* tileInfo = v2 ? V.tileInfo : nullptr;
     const int nB64 = ((c->fullW + 63) / 64) * ((c->h + 63) / 64);
     if (v2) {
         const int nRuns = (int)((T8 + 7) / 8), n4 = (nRuns + 3) >> 2;
         const int items = runSums ? (n4 > nB64 ? n4 : nB64) : nB64;
         hipLaunchKernelGGL(yk_scan1r_kernel, dim3((unsigned)((items + 1023) / 1024), F), dim3(1024), 0, c->stream, runSums, (unsigned long long)c->fs.runSums, nRuns,
-                           blockCnt, (unsigned long long)c->fs.blockN, nb, bm0b, (unsigned long long)c->fs.bm0b,
-                           batch ? c->B.bitmap[0] : c->bitmap[0], (unsigned long long)c->fs.bitmap[0], nB64);
+                           V.blockCnt, (unsigned long long)c->fs.blockN, nb, bm0b, (unsigned long long)c->fs.bm0b,
+                           V.bitmap[0], (unsigned long long)c->fs.bitmap[0], nB64);
     }
-    if (!runSums) hipLaunchKernelGGL(yk_scan2_kernel, dim3(F), dim3(1024), 0, c->stream, blockCnt, blockSums, nb, totals, (unsigned long long)c->fs.blockN);
-    hipLaunchKernelGGL(yk_pack_kernel, dim3(nb, 1, F), dim3(256), 0, c->stream, batch ? c->B.tileCount : c->tileCount, batch ? c->B.tileDef : c->tileDef, tileInfo,
-                       batch ? c->B.slots : c->slots, T8, blockSums, nb, batch ? c->B.defsOut : c->defsOut, reinterpret_cast<uint32_t*>(nibOut), c->nibStride / 4, c->fs,
-                       runSums ? blockCnt : (const uint32_t*)nullptr, totals);
+    if (!runSums) hipLaunchKernelGGL(yk_scan2_kernel, dim3(F), dim3(1024), 0, c->stream, V.blockCnt, V.blockSums, nb, V.totals, (unsigned long long)c->fs.blockN);
+    hipLaunchKernelGGL(yk_pack_kernel, dim3(nb, 1, F), dim3(256), 0, c->stream, V.tileCount, V.tileDef, tileInfo,
+                       V.slots, T8, V.blockSums, nb, V.defsOut, reinterpret_cast<uint32_t*>(V.nibOut), c->nibStride / 4, c->fs,
+                       runSums ? V.blockCnt : (const uint32_t*)nullptr, V.totals);
     YK_HIP(c, hipGetLastError());
     return YK_OK;
 }

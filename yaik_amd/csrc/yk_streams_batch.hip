@@ -14,7 +14,7 @@ int yk_encode_streams_batch(yk_ctx* c, int what) {
     if (!c) return YK_ERR_BAD_ARG;
     if (what < 1 || what > 3) return yk_refuse(c, YK_ERR_BAD_ARG, "what must be YK_STREAMS_CORNERS (1), YK_STREAMS_RANGE1D (2) or both (3)");
     if (c->y0 != 0 || c->h != c->fullH) return yk_refuse(c, YK_ERR_STATE, "yk_encode_streams_batch works on whole images, not on a stripe");
-    if (!c->B.plane[0] || !c->B.plane[1] || !c->B.plane[2] || (c->nFrames > 1 && c->fs.plane == 0)) return yk_refuse(c, YK_ERR_STATE, "bind planes first");
+    if (!yk_batch_planes_bound(c)) return yk_refuse(c, YK_ERR_STATE, "bind planes first");
     if (!c->encoded) return yk_refuse(c, YK_ERR_STATE, "yk_encode_batch first (or, for one frame, yk_encode_tiles / yk_encode_frame)");
     if (c->ppActive) return yk_refuse(c, YK_ERR_STATE, "a plane-subset pass ran: its per-plane coverage is not batched");
     YK_HIP(c, hipSetDevice(c->device));
@@ -48,8 +48,9 @@ int yk_encode_streams_batch(yk_ctx* c, int what) {
     for (int f = 0; f < N; f++) {
         const uint32_t* k = &cnt[(size_t)f * YK_SB_COUNTS];
         yk_frame_streams& t = b.table[(size_t)f];
+        const YkFrameView V = yk_frame(c, f);
         for (int p = 0; p < 7; p++) {
-            t.bitmap[p] = c->B.bitmap[p] + (size_t)f * c->fs.bitmap[p]; t.bitmapBytes[p] = c->bitmapBytes[p];
+            t.bitmap[p] = V.bitmap[p]; t.bitmapBytes[p] = c->bitmapBytes[p];
             t.rgbBytes[p] = corners ? (size_t)k[p] * 3 : 0;
             if (t.rgbBytes[p]) offs[(size_t)f * 9 + p] = place(t.rgbBytes[p]);
         }
