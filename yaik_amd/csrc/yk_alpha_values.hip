@@ -1,10 +1,14 @@
 // 'ALPM' alpha value chunk on the device.
 //   yk_alpha_values   EncoderContext::ProcessAlpha (encoder/EncoderContext.cpp:1429-1682, make1BitStream :317-355): box, class, payload
 //                     (8-bit, 1-bit, and the 6-bit mask mode of force8Bit = false)
+//   yk_alpha_values_batch   the same for every frame of the handle.  There is one encode path: yk_ave_classify (box, slots, class) and
+//                     yk_ave_chunk (class -> mode, box, bytes) serve both entry points, the single image is a batch of one that copies its
+//                     payload out and, for force8Bit = false, packs the 6-bit payload from its slot
 //   yk_decode_alpha   Decompress1BitMaskAlign8NoMask (decoder/YAIK_Alpha.cpp:25-112), Decompress6BitTo8BitAlphaNoMask (:114-235),
 //                     Decompress6BitTo8BitAlphaUsingMipmapMask (:237-376), Decompress8BitTo8BitAlphaNoMask (:377-444): the full w x h plane
 //                     in HBM (0 outside the box), kept for yk_decode_output_alpha.
 //   yk_decode_alpha_[mask_]batch_device   the same planes for every frame of a decode batch; the mask modes read the 'MIPM' tile bitmap in place
+//                     (their two loops are written once, over the source of the mask bit)
 #include "yk_common.h"
 #include <climits>
 
@@ -104,20 +108,59 @@ __global__ __launch_bounds__(256) void yk_av_decode_batch_kernel(const YkAvDecFr
     yk_av_decode_body<RAGGED>(r.pay, (size_t)r.n, r.mode, 0, r.bx, r.by, r.bw, r.bh, W, H, out, blockIdx.x);
 }
 
-// mask modes 2 / 3: the bit of box pixel (c, r) in the decoder's mipMapMask (read linearly with stride maskBBox.w from the alpha box's
+// mask modes 2 / 3.  The row-count and the decode loop are written once, over a bit source `m` that answers "is box pixel (r, c) selected"
+// through yk_av_selected: YkAvMaskBits (the decoded mask buffer of yk_decode_alpha) or YkAvMaskFrame (a batch frame's 'MIPM' tile bitmap).
+// YkAvMaskBits: the bit of box pixel (c, r) in the decoder's mipMapMask (read linearly with stride maskBBox.w from the alpha box's
 // origin, in 32-bit arithmetic like the reference's u32 mipmapPos); bits outside the mask buffer read 0
+struct YkAvMaskBits { const uint8_t* mask; size_t maskBytes; uint32_t base, stride; };
 __device__ __forceinline__ bool yk_av_maskbit(const uint8_t* __restrict__ mask, size_t maskBytes, uint32_t base, uint32_t stride, int r, int c) {
     const uint32_t pos = base + stride * (uint32_t)r + (uint32_t)c;
     return (size_t)(pos >> 3) < maskBytes && ((mask[pos >> 3] >> (pos & 7)) & 1);
 }
+__device__ __forceinline__ bool yk_av_selected(const YkAvMaskBits& m, int r, int c) { return yk_av_maskbit(m.mask, m.maskBytes, m.base, m.stride, r, c); }
+// One record per masked frame of a batch (yk_decode_alpha_mask_batch_device), read through uniform loads.  The mask bit is derived straight from
+// the frame's 'MIPM' tile bitmap (1 bit per 16x16 tile, LSB first, read in place): yk_dec_mask_kernel writes tile (tx, ty) of a tbw x tbh box as
+// the four u64 words ty * 4 * tbw + {2 tx, 2 tx + 1, 2 tbw + 2 tx, 2 tbw + 2 tx + 1}, all ones or all zeros, so bit `pos` of that buffer is the
+// tile bit of word q = pos >> 6.  nq = 4 * tbw * tbh words = the maskBytes = tbw * tbh * 32 of the single-image call: bits at or beyond read 0.
+struct YkAvMaskFrame {
+    const uint8_t* pay; unsigned long long n; const uint8_t* bits;
+    uint32_t base, stride, tbw, nq;          // base / stride as in YkAvMaskBits (stride = tbw * 16)
+    int32_t bx, by, bw, bh, inv, frame;
+    uint32_t oRows, pad;                     // rowCnt[bh], rowStart[bh + 1] at rows + oRows
+};
+__device__ __forceinline__ bool yk_av_tilebit(const YkAvMaskFrame& m, int r, int c) {
+    const uint32_t pos = m.base + m.stride * (uint32_t)r + (uint32_t)c, q = pos >> 6;
+    if (q >= m.nq) return false;
+    const uint32_t per = 4u * m.tbw, i = (q / per) * m.tbw + (((q % per) % (2u * m.tbw)) >> 1);
+    return (m.bits[i >> 3] >> (i & 7)) & 1;
+}
+__device__ __forceinline__ bool yk_av_selected(const YkAvMaskFrame& m, int r, int c) { return yk_av_tilebit(m, r, c); }
 // one wave per box row: count of mask-selected pixels
-__global__ __launch_bounds__(64) void yk_av_rowcount_kernel(const uint8_t* __restrict__ mask, size_t maskBytes, uint32_t base, uint32_t stride, int bw,
-                                                            uint32_t* __restrict__ rowCnt) {
-    const int r = blockIdx.x;
+template <class BITS>
+__device__ __forceinline__ void yk_av_rowcount_body(const BITS& m, int r, int bw, uint32_t* __restrict__ rowCnt) {
     uint32_t cnt = 0;
-    for (int c = threadIdx.x; c < bw; c += 64) cnt += yk_av_maskbit(mask, maskBytes, base, stride, r, c) ? 1u : 0u;
+    for (int c = threadIdx.x; c < bw; c += 64) cnt += yk_av_selected(m, r, c) ? 1u : 0u;
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
     if (threadIdx.x == 0) rowCnt[r] = cnt;
+}
+// one wave per box row: sample index of a selected pixel = the row's start k + selected pixels to its left (ballot + popcount); the state of the
+// reference's 4-value cycle is that index, it carries across rows like `state` does (YAIK_Alpha.cpp:313).  `row` = the box row in the plane
+template <class BITS>
+__device__ __forceinline__ void yk_av_maskdecode_body(const BITS& m, int r, int bw, const uint8_t* __restrict__ pay, size_t n, bool inv, uint32_t k,
+                                                      uint8_t* __restrict__ row) {
+    const int lane = threadIdx.x;
+    for (int c0 = 0; c0 < bw; c0 += 64) {
+        const int c = c0 + lane;
+        const bool sel = c < bw && yk_av_selected(m, r, c);
+        const unsigned long long b = __ballot(sel);
+        const uint32_t before = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        if (c < bw) row[c] = sel ? yk_av_expand6(yk_av_sample6(pay, n, (size_t)k + before), inv) : 0;
+        k += (uint32_t)__popcll(b);
+    }
+}
+__global__ __launch_bounds__(64) void yk_av_rowcount_kernel(const uint8_t* __restrict__ mask, size_t maskBytes, uint32_t base, uint32_t stride, int bw,
+                                                            uint32_t* __restrict__ rowCnt) {
+    yk_av_rowcount_body(YkAvMaskBits{ mask, maskBytes, base, stride }, (int)blockIdx.x, bw, rowCnt);
 }
 // one workgroup: exclusive prefix of the row counts, total in rowStart[bh].  Thread t owns a run of ceil(bh / 1024) rows; the run sums are
 // scanned in LDS.  Returns thread t's inclusive sum: thread 1023 holds the total
@@ -142,50 +185,16 @@ __global__ __launch_bounds__(1024) void yk_av_rowscan_kernel(const uint32_t* __r
     __shared__ uint32_t s[1024];
     (void)yk_av_rowscan_body(rowCnt, bh, rowStart, s);
 }
-// one wave per box row: sample index of a selected pixel = rowStart + selected pixels to its left (ballot + popcount); the state of the
-// reference's 4-value cycle is that index, it carries across rows like `state` does (YAIK_Alpha.cpp:313)
 __global__ __launch_bounds__(64) void yk_av_maskdecode_kernel(const uint8_t* __restrict__ pay, size_t n, const uint8_t* __restrict__ mask, size_t maskBytes,
                                                               uint32_t base, uint32_t stride, int bx, int by, int bw, int inv,
                                                               const uint32_t* __restrict__ rowStart, int W, uint8_t* __restrict__ out) {
-    const int r = blockIdx.x, lane = threadIdx.x;
-    uint32_t k = rowStart[r];
-    uint8_t* row = out + (size_t)(by + r) * W + bx;
-    for (int c0 = 0; c0 < bw; c0 += 64) {
-        const int c = c0 + lane;
-        const bool sel = c < bw && yk_av_maskbit(mask, maskBytes, base, stride, r, c);
-        const unsigned long long b = __ballot(sel);
-        const uint32_t before = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-        if (c < bw) row[c] = sel ? yk_av_expand6(yk_av_sample6(pay, n, (size_t)k + before), inv != 0) : 0;
-        k += (uint32_t)__popcll(b);
-    }
+    const int r = blockIdx.x;
+    yk_av_maskdecode_body(YkAvMaskBits{ mask, maskBytes, base, stride }, r, bw, pay, n, inv != 0, rowStart[r], out + (size_t)(by + r) * W + bx);
 }
-
-// ---- mask modes 2 / 3 in a batch (yk_decode_alpha_mask_batch_device) -----------------------------------------------------------------------------
-// One record per masked frame, read through uniform loads.  The mask bit is derived straight from the frame's 'MIPM' tile bitmap (1 bit per
-// 16x16 tile, LSB first, read in place): yk_dec_mask_kernel writes tile (tx, ty) of a tbw x tbh box as the four u64 words ty * 4 * tbw +
-// {2 tx, 2 tx + 1, 2 tbw + 2 tx, 2 tbw + 2 tx + 1}, all ones or all zeros, so bit `pos` of that buffer is the tile bit of word q = pos >> 6.
-// nq = 4 * tbw * tbh words = the maskBytes = tbw * tbh * 32 of the single-image call: bits at or beyond read 0.
-struct YkAvMaskFrame {
-    const uint8_t* pay; unsigned long long n; const uint8_t* bits;
-    uint32_t base, stride, tbw, nq;          // base / stride as in yk_av_maskbit (stride = tbw * 16)
-    int32_t bx, by, bw, bh, inv, frame;
-    uint32_t oRows, pad;                     // rowCnt[bh], rowStart[bh + 1] at rows + oRows
-};
-__device__ __forceinline__ bool yk_av_tilebit(const YkAvMaskFrame& m, int r, int c) {
-    const uint32_t pos = m.base + m.stride * (uint32_t)r + (uint32_t)c, q = pos >> 6;
-    if (q >= m.nq) return false;
-    const uint32_t per = 4u * m.tbw, i = (q / per) * m.tbw + (((q % per) % (2u * m.tbw)) >> 1);
-    return (m.bits[i >> 3] >> (i & 7)) & 1;
-}
-// one wave per box row of masked frame blockIdx.y (the grid is sized from the tallest box: waves below this frame's box leave at once)
+// the same three in a batch: masked frame blockIdx.y's record (the grids are sized from the tallest box: waves below this frame's box leave at once)
 __global__ __launch_bounds__(64) void yk_av_rowcount_batch_kernel(const YkAvMaskFrame* __restrict__ tab, uint32_t* __restrict__ rows) {
     const YkAvMaskFrame m = tab[blockIdx.y];
-    const int r = blockIdx.x;
-    if (r >= m.bh) return;
-    uint32_t cnt = 0;
-    for (int c = threadIdx.x; c < m.bw; c += 64) cnt += yk_av_tilebit(m, r, c) ? 1u : 0u;
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
-    if (threadIdx.x == 0) rows[m.oRows + r] = cnt;
+    if ((int)blockIdx.x < m.bh) yk_av_rowcount_body(m, (int)blockIdx.x, m.bw, rows + m.oRows);
 }
 // one workgroup per masked frame: yk_av_rowscan_kernel's scan, and the frame's status word: 1 when the payload is shorter than the mask selects
 __global__ __launch_bounds__(1024) void yk_av_rowscan_batch_kernel(const YkAvMaskFrame* __restrict__ tab, uint32_t* __restrict__ rows,
@@ -195,41 +204,37 @@ __global__ __launch_bounds__(1024) void yk_av_rowscan_batch_kernel(const YkAvMas
     const uint32_t total = yk_av_rowscan_body(rows + m.oRows, m.bh, rows + m.oRows + m.bh, s);
     if (threadIdx.x == 1023) status[blockIdx.x] = ((unsigned long long)total * 6 + 7) / 8 > m.n ? 1 : 0;
 }
-// one wave per box row, as yk_av_maskdecode_kernel; the plane was zeroed by the unmasked launch in front
+// the plane was zeroed by the unmasked launch in front
 __global__ __launch_bounds__(64) void yk_av_maskdecode_batch_kernel(const YkAvMaskFrame* __restrict__ tab, const uint32_t* __restrict__ rows, int W,
                                                                     uint8_t* __restrict__ out, size_t planeStride) {
     const YkAvMaskFrame m = tab[blockIdx.y];
-    const int r = blockIdx.x, lane = threadIdx.x;
+    const int r = blockIdx.x;
     if (r >= m.bh) return;
-    uint32_t k = rows[m.oRows + m.bh + r];
-    uint8_t* row = out + (size_t)m.frame * planeStride + (size_t)(m.by + r) * W + m.bx;
-    for (int c0 = 0; c0 < m.bw; c0 += 64) {
-        const int c = c0 + lane;
-        const bool sel = c < m.bw && yk_av_tilebit(m, r, c);
-        const unsigned long long b = __ballot(sel);
-        const uint32_t before = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-        if (c < m.bw) row[c] = sel ? yk_av_expand6(yk_av_sample6(m.pay, (size_t)m.n, (size_t)k + before), m.inv != 0) : 0;
-        k += (uint32_t)__popcll(b);
-    }
+    yk_av_maskdecode_body(m, r, m.bw, m.pay, (size_t)m.n, m.inv != 0, rows[m.oRows + m.bh + r],
+                          out + (size_t)m.frame * planeStride + (size_t)(m.by + r) * W + m.bx);
 }
 
 // ---- encode: EncoderContext::ProcessAlpha (encoder/EncoderContext.cpp:1429-1682) --------------------------------------------------
+// One set of kernels for yk_alpha_values (one frame) and yk_alpha_values_batch (N): blockIdx.z = frame (box) or record (class, pack1), frame f's
+// plane at alpha + f * frameElems (frameElems = 0 with one frame), its bounds 16 ints, its state 8 ints:
 // st[0..3] = bL, bT, bR, bB of the samples with v >> 2 != 0 (min / min / max / max, inclusive); st[4] = "a sample in 1..254 in the rounded box",
 // st[5] = "a sample != 255 in the rounded box".
 #define YK_AV_ROWS 16
-// box of v >> 2 != 0 inside the MipPrefilter bounds (read on the device from the alpha stage's result); one thread = 4 pixels of YK_AV_ROWS rows
 // 4 samples at p: one 16-byte load when the plane's rows are 16-byte aligned (VEC), 4 loads otherwise
 template <bool VEC>
 __device__ __forceinline__ int4 yk_ave_load4(const int32_t* __restrict__ p) {
     if (VEC) return *reinterpret_cast<const int4*>(p);
     return make_int4(p[0], p[1], p[2], p[3]);
 }
+// box of v >> 2 != 0 inside the MipPrefilter bounds (read on the device from the alpha stage's result); one thread = 4 pixels of YK_AV_ROWS rows
 template <bool VEC>
-__device__ __forceinline__ void yk_ave_box_body(const int32_t* __restrict__ alpha, int stride, const int32_t* __restrict__ bounds, int W, int H,
-                                                int32_t* __restrict__ st, int blkX, int blkY) {
+__global__ __launch_bounds__(256) void yk_ave_box_batch_kernel(const int32_t* __restrict__ alpha, unsigned long long frameElems, int stride,
+                                                               const int32_t* __restrict__ bounds, int W, int H, int32_t* __restrict__ st) {
+    const size_t f = blockIdx.z;
+    alpha += f * frameElems; bounds += f * 16; st += f * 8;
     // the region starts on a multiple of 16 (kept 16x16 tiles); the loads start on the multiple of 4 at or below it whatever it is
     const int xs = max(bounds[0], 0), x0 = xs & ~3, y0 = max(bounds[1], 0), x1 = min(bounds[2], W), y1 = min(bounds[3], H);
-    const int x = x0 + (blkX * 256 + (int)threadIdx.x) * 4, yb = y0 + blkY * YK_AV_ROWS;
+    const int x = x0 + ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4, yb = y0 + (int)blockIdx.y * YK_AV_ROWS;
     int mnx = INT_MAX, mny = INT_MAX, mxx = -1, mxy = -1;
     if (x < x1)
         for (int y = yb; y < min(yb + YK_AV_ROWS, y1); y++) {
@@ -253,27 +258,21 @@ __device__ __forceinline__ void yk_ave_box_body(const int32_t* __restrict__ alph
         if (mxy > v[3]) atomicMax(&st[3], mxy);
     }
 }
-template <bool VEC>
-__global__ __launch_bounds__(256) void yk_ave_box_kernel(const int32_t* __restrict__ alpha, int stride, const int32_t* __restrict__ bounds, int W, int H,
-                                                         int32_t* __restrict__ st) {
-    yk_ave_box_body<VEC>(alpha, stride, bounds, W, H, st, (int)blockIdx.x, (int)blockIdx.y);
-}
-// every frame of a batch: frame = blockIdx.z, its plane frameElems further, its bounds 16 ints, its state 8 ints
-template <bool VEC>
-__global__ __launch_bounds__(256) void yk_ave_box_batch_kernel(const int32_t* __restrict__ alpha, unsigned long long frameElems, int stride,
-                                                               const int32_t* __restrict__ bounds, int W, int H, int32_t* __restrict__ st) {
-    const size_t f = blockIdx.z;
-    yk_ave_box_body<VEC>(alpha + f * frameElems, stride, bounds + f * 16, W, H, st + f * 8, (int)blockIdx.x, (int)blockIdx.y);
-}
+// one record per frame that has a box (the box rounded to 4 in x, the frame, the offset of its payload slot); record blockIdx.z is read through
+// uniform loads.  The grids are sized from the largest box: workgroups outside this frame's box leave at once.
+struct YkAvFrame { int32_t bL, bT, bw, bh; unsigned long long off; int32_t frame, pad; };
 // the three class flags over the box rounded to 4 in x (isAnalogAlpha, isAll1; isAll0 is false once the box is not empty) and, in the same
-// read, the 8-bit payload (every sample of the box, row-major): one thread = 4 pixels = one 4-byte store
+// read, the 8-bit payload (every sample of the box, row-major, in the frame's slot): one thread = 4 pixels = one 4-byte store
 template <bool VEC>
-__device__ __forceinline__ void yk_ave_class_body(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh, uint8_t* __restrict__ pay,
-                                                  int32_t* __restrict__ st, int blkX, int r) {
-    const int c = (blkX * 256 + (int)threadIdx.x) * 4;
+__global__ __launch_bounds__(256) void yk_ave_class_batch_kernel(const int32_t* __restrict__ alpha, unsigned long long frameElems, int stride,
+                                                                 const YkAvFrame* __restrict__ tab, uint8_t* __restrict__ pay, int32_t* __restrict__ st) {
+    const YkAvFrame f = tab[blockIdx.z];
+    if ((int)blockIdx.y >= f.bh || (int)blockIdx.x * 1024 >= f.bw) return;
+    alpha += (size_t)f.frame * frameElems; pay += f.off; st += (size_t)f.frame * 8;
+    const int r = blockIdx.y, c = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
     bool analog = false, not255 = false;
-    if (c < bw) {
-        const int4 q = yk_ave_load4<VEC>(alpha + (size_t)(bT + r) * stride + bL + c);   // bL and c are multiples of 4
+    if (c < f.bw) {
+        const int4 q = yk_ave_load4<VEC>(alpha + (size_t)(f.bT + r) * stride + f.bL + c);   // bL and c are multiples of 4
         const int vs[4] = { q.x, q.y, q.z, q.w };
         uint32_t word = 0;
 #pragma unroll
@@ -282,7 +281,7 @@ __device__ __forceinline__ void yk_ave_class_body(const int32_t* __restrict__ al
             analog |= v > 0 && v < 255; not255 |= v != 255;
             word |= (uint32_t)(v & 255) << (8 * k);
         }
-        *reinterpret_cast<uint32_t*>(pay + (size_t)r * bw + c) = word;      // bw and c are multiples of 4
+        *reinterpret_cast<uint32_t*>(pay + (size_t)r * f.bw + c) = word;    // off, bw and c are multiples of 4
     }
     const unsigned long long a = __ballot(analog), n = __ballot(not255);
     if ((threadIdx.x & 63) == 0) {                                         // a flag is set once: later waves only read it
@@ -291,47 +290,23 @@ __device__ __forceinline__ void yk_ave_class_body(const int32_t* __restrict__ al
         if (n && !v[5]) atomicOr(&st[5], 1);
     }
 }
-template <bool VEC>
-__global__ __launch_bounds__(256) void yk_ave_class_kernel(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh,
-                                                           uint8_t* __restrict__ pay, int32_t* __restrict__ st) {
-    yk_ave_class_body<VEC>(alpha, stride, bL, bT, bw, bh, pay, st, (int)blockIdx.x, (int)blockIdx.y);
-}
-// make1BitStream (:317-355) on the box re-aligned to 8: bit (v & 1) of every sample, LSB first; one thread = one output byte
-__device__ __forceinline__ void yk_ave_pack1_body(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh, uint8_t* __restrict__ pay,
-                                                  uint32_t blk) {
-    const size_t i = (size_t)blk * 256 + threadIdx.x, perRow = (size_t)(bw >> 3);
-    if (i >= perRow * bh) return;
+// make1BitStream (:317-355) for the frames the class kernel found binary (flags: not analog, not all 255), on the box re-aligned to 8 as
+// yk_ave_chunk does it on the host: bit (v & 1) of every sample, LSB first; one thread = one output byte.  The 1-bit payload replaces the
+// 8-bit one in the frame's slot (it is never longer)
+__global__ __launch_bounds__(256) void yk_ave_pack1_batch_kernel(const int32_t* __restrict__ alpha, unsigned long long frameElems, int stride,
+                                                                 const YkAvFrame* __restrict__ tab, uint8_t* __restrict__ pay, const int32_t* __restrict__ st) {
+    const YkAvFrame f = tab[blockIdx.z];
+    const int32_t* s = st + (size_t)f.frame * 8;
+    if (s[4] != 0 || s[5] == 0) return;
+    const int bL = (f.bL >> 3) << 3, bR = ((f.bL + f.bw + 7) >> 3) << 3;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, perRow = (size_t)((bR - bL) >> 3);
+    if (i >= perRow * f.bh) return;
     const int r = (int)(i / perRow), c = (int)(i % perRow) * 8;
-    const int32_t* p = alpha + (size_t)(bT + r) * stride + bL + c;
+    const int32_t* p = alpha + (size_t)f.frame * frameElems + (size_t)(f.bT + r) * stride + bL + c;
     uint32_t b = 0;
 #pragma unroll
     for (int k = 0; k < 8; k++) b |= (uint32_t)(p[k] & 1) << k;
-    pay[i] = (uint8_t)b;
-}
-__global__ __launch_bounds__(256) void yk_ave_pack1_kernel(const int32_t* __restrict__ alpha, int stride, int bL, int bT, int bw, int bh,
-                                                           uint8_t* __restrict__ pay) {
-    yk_ave_pack1_body(alpha, stride, bL, bT, bw, bh, pay, blockIdx.x);
-}
-// yk_alpha_values_batch: one record per frame that has a box (the box rounded to 4 in x, the frame, the offset of its payload slot); record
-// blockIdx.z is read through uniform loads.  The grids are sized from the largest box: workgroups outside this frame's box leave at once.
-struct YkAvFrame { int32_t bL, bT, bw, bh; unsigned long long off; int32_t frame, pad; };
-template <bool VEC>
-__global__ __launch_bounds__(256) void yk_ave_class_batch_kernel(const int32_t* __restrict__ alpha, unsigned long long frameElems, int stride,
-                                                                 const YkAvFrame* __restrict__ tab, uint8_t* __restrict__ pay, int32_t* __restrict__ st) {
-    const YkAvFrame r = tab[blockIdx.z];
-    if ((int)blockIdx.y >= r.bh || (int)blockIdx.x * 1024 >= r.bw) return;
-    yk_ave_class_body<VEC>(alpha + (size_t)r.frame * frameElems, stride, r.bL, r.bT, r.bw, r.bh, pay + r.off, st + (size_t)r.frame * 8, (int)blockIdx.x,
-                           (int)blockIdx.y);
-}
-// the frames the class kernel found binary (flags: not analog, not all 255): the box is re-aligned to 8 here as the host does it, the 1-bit
-// payload replaces the 8-bit one in the frame's slot (it is never longer)
-__global__ __launch_bounds__(256) void yk_ave_pack1_batch_kernel(const int32_t* __restrict__ alpha, unsigned long long frameElems, int stride,
-                                                                 const YkAvFrame* __restrict__ tab, uint8_t* __restrict__ pay, const int32_t* __restrict__ st) {
-    const YkAvFrame r = tab[blockIdx.z];
-    const int32_t* s = st + (size_t)r.frame * 8;
-    if (s[4] != 0 || s[5] == 0) return;
-    const int bL = (r.bL >> 3) << 3, bR = ((r.bL + r.bw + 7) >> 3) << 3;
-    yk_ave_pack1_body(alpha + (size_t)r.frame * frameElems, stride, bL, r.bT, bR - bL, r.bh, pay + r.off, blockIdx.x);
+    pay[f.off + i] = (uint8_t)b;
 }
 
 // ---- force8Bit = false: IS_6_BIT_USEMIPMAPMASK_INVERSE (:1503-1565) -----------------------------------------------------------------------
@@ -457,6 +432,86 @@ int yk_decode_alpha_plane(yk_ctx* c, uint8_t* hostOut, size_t cap) {
 
 }  // extern "C"
 
+// ---- encode, host side: yk_alpha_values is yk_alpha_values_batch's path with one frame ---------------------------------------------------------
+static unsigned long long yk_ave_frame_elems(const yk_ctx* c) { return c->nFrames > 1 ? c->fs.plane : 0; }
+// 16-byte loads: the base aligned to 16, the row and the frame pitch multiples of 4 samples
+static bool yk_ave_vec(const yk_ctx* c) {
+    return ((reinterpret_cast<uintptr_t>(c->B.plane[3]) & 15) == 0) && ((c->strideElems & 3) == 0) && ((yk_ave_frame_elems(c) & 3) == 0);
+}
+// Box and class of every frame of the handle: st = the 8 state words per frame after the class kernel, tab = one record per frame that has a
+// box, also in avTab; the frames' 8-bit payloads are in their slots of avPay.  Two launches, two blocking read-backs and one table upload
+// whatever nFrames is.  The entry points have checked the handle; the only failure of its own is "alpha box beyond the image"
+static int yk_ave_classify(yk_ctx* c, std::vector<int32_t>& st, std::vector<YkAvFrame>& tab) {
+    const int N = c->nFrames, W = c->fullW, H = c->fullH;
+    YK_HIP(c, c->avState.reserve(c->stream, (size_t)N * 8));
+    st.resize((size_t)N * 8);
+    for (int f = 0; f < N; f++) { int32_t* s = &st[(size_t)f * 8]; s[0] = s[1] = INT_MAX; s[2] = s[3] = -1; s[4] = s[5] = s[6] = s[7] = 0; }
+    YK_HIP(c, hipMemcpyAsync(c->avState, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    const int32_t* alpha = c->B.plane[3];
+    const unsigned long long fe = yk_ave_frame_elems(c);
+    const bool vec = yk_ave_vec(c);
+    // the search region is at most the image; the kernel clamps it to the bounds the alpha stage left on the device
+    hipLaunchKernelGGL(vec ? yk_ave_box_batch_kernel<true> : yk_ave_box_batch_kernel<false>,
+                       dim3((unsigned)((W / 4 + 255) / 256), (unsigned)((H + YK_AV_ROWS - 1) / YK_AV_ROWS), (unsigned)N), dim3(256), 0, c->stream, alpha, fe,
+                       c->strideElems, c->B.bounds + c->boundsOff, W, H, c->avState);
+    YK_HIP(c, hipGetLastError());
+    YK_HIP(c, hipMemcpyAsync(st.data(), c->avState, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 1: every frame's box sizes every later launch
+    // the payload slots back to back, each on a multiple of 16: bw * bh bytes of the box rounded to 4 (the 1-bit payload of the box re-aligned
+    // to 8 is never longer)
+    tab.clear();
+    size_t total = 0;
+    int maxW = 0, maxH = 0;
+    for (int f = 0; f < N; f++) {
+        const int32_t* s = &st[(size_t)f * 8];
+        if (s[2] < 0) continue;                                                           // empty box: isAll0 and isAll1 stay true, no chunk
+        const int bL = (s[0] >> 2) << 2, bR = ((s[2] + 1 + 3) >> 2) << 2, bT = s[1], bB = s[3] + 1;   // :1465-1466
+        // the one bounds check, for the box re-aligned to 8 too (yk_ave_chunk): W is a multiple of 8 (yk_set_image), so ((bR + 7) & ~7) > W is bR > W
+        if (bL < 0 || bT < 0 || bR > W || bB > H || ((bR + 7) & ~7) > W) return yk_fail(c, YK_ERR_STATE, "alpha box beyond the image");
+        YkAvFrame r;
+        r.bL = bL; r.bT = bT; r.bw = bR - bL; r.bh = bB - bT; r.off = total; r.frame = f; r.pad = 0;
+        tab.push_back(r);
+        total = (total + (size_t)r.bw * r.bh + 15) & ~(size_t)15;
+        maxW = max(maxW, r.bw); maxH = max(maxH, r.bh);
+    }
+    if (tab.empty()) return YK_OK;
+    YK_HIP(c, c->avPay.reserve(c->stream, total));
+    const size_t tabBytes = tab.size() * sizeof(YkAvFrame);
+    if (c->avTab.cap < tabBytes) YK_HIP(c, c->avTab.reserve(c->stream, (size_t)N * sizeof(YkAvFrame)));      // grown when the records do not fit, then for every frame
+    YK_HIP(c, hipMemcpyAsync(c->avTab, tab.data(), tabBytes, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(vec ? yk_ave_class_batch_kernel<true> : yk_ave_class_batch_kernel<false>,
+                       dim3((unsigned)((maxW / 4 + 255) / 256), (unsigned)maxH, (unsigned)tab.size()), dim3(256), 0, c->stream, alpha, fe, c->strideElems,
+                       reinterpret_cast<const YkAvFrame*>(c->avTab.p), c->avPay, c->avState);
+    YK_HIP(c, hipGetLastError());
+    YK_HIP(c, hipMemcpyAsync(st.data(), c->avState, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 2: every frame's class decides its payload
+    return YK_OK;
+}
+// The class decision of ProcessAlpha(true), the only copy: a record and its frame's two flags -> the chunk's mode and box in `o`, its payload
+// length returned.  Analog: IS_8_BIT_FULL, the slot as the class kernel wrote it.  All 255: no chunk, o.mode stays -1.  Binary: IS_1_BIT_FULL
+// on the box re-aligned to 8, which yk_ave_pack1_batch_kernel writes into the slot
+static size_t yk_ave_chunk(const YkAvFrame& r, const int32_t* s, yk_alpha_info& o) {
+    const bool analog = s[4] != 0, all1 = s[5] == 0;
+    int bL = r.bL, bw = r.bw;
+    size_t bytes;
+    if (analog) { o.mode = 6; bytes = (size_t)bw * r.bh; }
+    else if (all1) return 0;
+    else {
+        const int bR = ((bL + bw + 7) >> 3) << 3;
+        bL = (bL >> 3) << 3; bw = bR - bL;
+        o.mode = 1; bytes = (size_t)(bw >> 3) * r.bh;
+    }
+    o.bbox[0] = bL; o.bbox[1] = r.bT; o.bbox[2] = bw; o.bbox[3] = r.bh; o.rawSize = (uint32_t)bytes;
+    return bytes;
+}
+// maxBytes1 = the longest 1-bit payload among the nBox records in avTab (sizes the grid)
+static int yk_ave_pack1(yk_ctx* c, size_t nBox, size_t maxBytes1) {
+    hipLaunchKernelGGL(yk_ave_pack1_batch_kernel, dim3((unsigned)((maxBytes1 + 255) / 256), 1, (unsigned)nBox), dim3(256), 0, c->stream, c->B.plane[3],
+                       yk_ave_frame_elems(c), c->strideElems, reinterpret_cast<const YkAvFrame*>(c->avTab.p), c->avPay, c->avState);
+    YK_HIP(c, hipGetLastError());
+    return YK_OK;
+}
+
 extern "C" {
 
 int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostPayload, size_t cap, size_t* n) {
@@ -467,38 +522,22 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     if (!c->alphaFinished) return yk_fail(c, YK_ERR_STATE, "yk_alpha_reject + yk_alpha_finish first");
     if (c->nFrames != 1 || c->y0 != 0 || c->h != c->fullH) return yk_fail(c, YK_ERR_STATE, "yk_alpha_values works on a whole single image");
     const int W = c->fullW, H = c->fullH;
-    const YkFrameView V = yk_frame(c);
     YK_HIP(c, hipSetDevice(c->device));
-    c->avBatchValid = false;                                                              // the batch payloads share avState / avPay
-    if (!c->avState) YK_HIP(c, c->avState.alloc(c->stream, 8));
-    YK_HIP(c, c->avPay.reserve(c->stream, (size_t)W * H));
-    const int32_t init[8] = { INT_MAX, INT_MAX, -1, -1, 0, 0, 0, 0 };
-    YK_HIP(c, hipMemcpyAsync(c->avState, init, sizeof init, hipMemcpyHostToDevice, c->stream));
-    // the search region is at most the image; the kernel clamps it to the bounds the alpha stage left on the device
-    const bool vec = ((reinterpret_cast<uintptr_t>(V.plane[3]) & 15) == 0) && ((c->strideElems & 3) == 0);
-    hipLaunchKernelGGL(vec ? yk_ave_box_kernel<true> : yk_ave_box_kernel<false>, dim3((unsigned)((W / 4 + 255) / 256), (unsigned)((H + YK_AV_ROWS - 1) / YK_AV_ROWS)), dim3(256), 0, c->stream,
-                       V.plane[3], c->strideElems, V.bounds + c->boundsOff, W, H, c->avState);
-    YK_HIP(c, hipGetLastError());
-    int32_t st[8];
-    YK_HIP(c, hipMemcpyAsync(st, c->avState, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 1: the box sizes every later launch
-    if (st[2] < 0) return YK_OK;                                                          // empty box: isAll0 and isAll1 stay true, no chunk
-    int bL = (st[0] >> 2) << 2, bR = ((st[2] + 1 + 3) >> 2) << 2;                         // :1465-1466
-    const int bT = st[1], bB = st[3] + 1;
-    if (bR > W) return yk_fail(c, YK_ERR_STATE, "alpha box beyond the image");
-    int bw = bR - bL;
-    const int bh = bB - bT;
-    hipLaunchKernelGGL(vec ? yk_ave_class_kernel<true> : yk_ave_class_kernel<false>, dim3((unsigned)((bw / 4 + 255) / 256), (unsigned)bh), dim3(256), 0, c->stream, V.plane[3], c->strideElems,
-                       bL, bT, bw, bh, c->avPay, c->avState);
-    YK_HIP(c, hipGetLastError());
-    YK_HIP(c, hipMemcpyAsync(st + 4, c->avState + 4, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 2: the class decides the payload
-    const bool analog = st[4] != 0, all1 = st[5] == 0;
-    size_t bytes;
+    c->avBatchValid = false;                                                              // the batch payloads share avState / avPay / avTab: no slot is published here
+    std::vector<int32_t> st;
+    std::vector<YkAvFrame> tab;
+    { const int rc = yk_ave_classify(c, st, tab); if (rc) return rc; }
+    if (tab.empty()) return YK_OK;                                                        // empty box: no chunk
+    const YkAvFrame& r = tab[0];                                                          // its slot is at avPay + 0
+    yk_alpha_info o = *out;
+    size_t bytes = yk_ave_chunk(r, &st[0], o);
+    if (o.mode < 0) return YK_OK;                                                         // all 255: no chunk
     const uint8_t* src = c->avPay;
-    if (analog && force8Bit) {
-        out->mode = 6; bytes = (size_t)bw * bh;                                           // IS_8_BIT_FULL, payload already written
-    } else if (analog) {                                                                  // IS_6_BIT_USEMIPMAPMASK_INVERSE from the u8 box
+    if (o.mode == 1) {
+        const int rc = yk_ave_pack1(c, 1, bytes); if (rc) return rc;
+    } else if (!force8Bit) {                                                              // analog: IS_6_BIT_USEMIPMAPMASK_INVERSE from the u8 box in the slot
+        const YkFrameView V = yk_frame(c);
+        const int bL = r.bL, bT = r.bT, bw = r.bw, bh = r.bh, bR = bL + bw, bB = bT + bh;
         if (!V.keep || (bL & 3) || (bw & 3)) return yk_fail(c, YK_ERR_STATE, "6-bit alpha: no keep flags or a box not aligned to 4");
         const int nb = ((bB - 1) >> 4) - (bT >> 4) + 1, ncol = ((bR - 1) >> 4) - (bL >> 4) + 1;
         const size_t nU32 = (size_t)nb * ncol + 3 * (size_t)nb + 1;
@@ -522,20 +561,9 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
         static const size_t tail[4] = { 0, 1, 2, 3 };
         bytes = (size_t)(total >> 2) * 3 + tail[total & 3];                                // :1549-1551 (total is a multiple of 4 here)
         if (bytes > payCap) return yk_fail(c, YK_ERR_STATE, "6-bit alpha: selected count beyond the box");
-        out->mode = 3; src = pay6;
-    } else if (all1) {
-        return YK_OK;                                                                     // all 255: no chunk
-    } else {                                                                              // binary: IS_1_BIT_FULL on the box re-aligned to 8
-        bL = (bL >> 3) << 3; bR = ((bR + 7) >> 3) << 3;
-        if (bR > W) return yk_fail(c, YK_ERR_STATE, "alpha box beyond the image");
-        bw = bR - bL;
-        bytes = (size_t)(bw >> 3) * bh;
-        out->mode = 1;
-        hipLaunchKernelGGL(yk_ave_pack1_kernel, dim3((unsigned)((bytes + 255) / 256)), dim3(256), 0, c->stream, V.plane[3], c->strideElems, bL, bT, bw, bh,
-                           c->avPay);
-        YK_HIP(c, hipGetLastError());
+        o.mode = 3; o.rawSize = (uint32_t)bytes; src = pay6;
     }
-    out->bbox[0] = bL; out->bbox[1] = bT; out->bbox[2] = bw; out->bbox[3] = bh; out->rawSize = (uint32_t)bytes;
+    *out = o;
     if (n) *n = bytes;
     if (hostPayload) {
         if (cap < bytes) return yk_fail(c, YK_ERR_RANGE, "alpha payload buffer too small");
@@ -545,8 +573,7 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
     return YK_OK;
 }
 
-
-// ProcessAlpha(true) for every frame of the handle: the three kernels above over all frames, the two read-backs and one record table per batch
+// ProcessAlpha(true) for every frame of the handle: at most three launches, two read-backs and one record table per batch
 int yk_alpha_values_batch(yk_ctx* c, int force8Bit, yk_alpha_info* infos) {
     if (!c) return YK_ERR_BAD_ARG;
     if (!infos) return yk_refuse(c, YK_ERR_BAD_ARG, "infos is NULL");
@@ -561,73 +588,19 @@ int yk_alpha_values_batch(yk_ctx* c, int force8Bit, yk_alpha_info* infos) {
     c->avBatchValid = false;
     c->avBatch.assign((size_t)N, yk_ctx::AvSlot{ -1, 0, 0 });
     if (c->nPlanes != 4) { c->avBatchValid = true; return YK_OK; }                        // no alpha: no chunk in any frame (:1674-1680)
-    const int W = c->fullW, H = c->fullH;
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, c->avState.reserve(c->stream, (size_t)N * 8));
-    std::vector<int32_t> st((size_t)N * 8);
-    for (int f = 0; f < N; f++) { int32_t* s = &st[(size_t)f * 8]; s[0] = s[1] = INT_MAX; s[2] = s[3] = -1; s[4] = s[5] = s[6] = s[7] = 0; }
-    YK_HIP(c, hipMemcpyAsync(c->avState, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    const int32_t* alpha = c->B.plane[3];
-    const unsigned long long fe = N > 1 ? c->fs.plane : 0;
-    const bool vec = ((reinterpret_cast<uintptr_t>(alpha) & 15) == 0) && ((c->strideElems & 3) == 0) && ((fe & 3) == 0);
-    hipLaunchKernelGGL(vec ? yk_ave_box_batch_kernel<true> : yk_ave_box_batch_kernel<false>,
-                       dim3((unsigned)((W / 4 + 255) / 256), (unsigned)((H + YK_AV_ROWS - 1) / YK_AV_ROWS), (unsigned)N), dim3(256), 0, c->stream, alpha, fe,
-                       c->strideElems, c->B.bounds + c->boundsOff, W, H, c->avState);
-    YK_HIP(c, hipGetLastError());
-    YK_HIP(c, hipMemcpyAsync(st.data(), c->avState, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 1: every frame's box
-    // the payload slots back to back, each on a multiple of 16: bw * bh bytes of the box rounded to 4 (the 1-bit payload of the box re-aligned
-    // to 8 is never longer)
+    std::vector<int32_t> st;
     std::vector<YkAvFrame> tab;
-    size_t total = 0;
-    int maxW = 0, maxH = 0;
-    for (int f = 0; f < N; f++) {
-        const int32_t* s = &st[(size_t)f * 8];
-        if (s[2] < 0) continue;                                                           // empty box: no chunk
-        const int bL = (s[0] >> 2) << 2, bR = ((s[2] + 1 + 3) >> 2) << 2, bT = s[1], bB = s[3] + 1;   // :1465-1466
-        if (bL < 0 || bT < 0 || bR > W || bB > H || ((bR + 7) & ~7) > W) return yk_fail(c, YK_ERR_STATE, "alpha box beyond the image");
-        YkAvFrame r;
-        r.bL = bL; r.bT = bT; r.bw = bR - bL; r.bh = bB - bT; r.off = total; r.frame = f; r.pad = 0;
-        tab.push_back(r);
-        total = (total + (size_t)r.bw * r.bh + 15) & ~(size_t)15;
-        maxW = max(maxW, r.bw); maxH = max(maxH, r.bh);
-    }
-    if (tab.empty()) { c->avBatchValid = true; return YK_OK; }
-    YK_HIP(c, c->avPay.reserve(c->stream, total));
-    const size_t tabBytes = tab.size() * sizeof(YkAvFrame);
-    if (c->avTab.cap < tabBytes) YK_HIP(c, c->avTab.reserve(c->stream, (size_t)N * sizeof(YkAvFrame)));      // grown when the records do not fit, then for every frame
-    YK_HIP(c, hipMemcpyAsync(c->avTab, tab.data(), tabBytes, hipMemcpyHostToDevice, c->stream));
-    const YkAvFrame* dTab = reinterpret_cast<const YkAvFrame*>(c->avTab.p);
-    const unsigned nBox = (unsigned)tab.size();
-    hipLaunchKernelGGL(vec ? yk_ave_class_batch_kernel<true> : yk_ave_class_batch_kernel<false>, dim3((unsigned)((maxW / 4 + 255) / 256), (unsigned)maxH, nBox),
-                       dim3(256), 0, c->stream, alpha, fe, c->strideElems, dTab, c->avPay, c->avState);
-    YK_HIP(c, hipGetLastError());
-    YK_HIP(c, hipMemcpyAsync(st.data(), c->avState, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    YK_HIP(c, hipStreamSynchronize(c->stream));                                           // readback 2: every frame's class
+    { const int rc = yk_ave_classify(c, st, tab); if (rc) return rc; }
     size_t maxBytes1 = 0;
     for (const YkAvFrame& r : tab) {
-        const int32_t* s = &st[(size_t)r.frame * 8];
-        const bool analog = s[4] != 0, all1 = s[5] == 0;
         yk_alpha_info& o = infos[r.frame];
-        int bL = r.bL, bw = r.bw;
-        size_t bytes;
-        if (analog) { o.mode = 6; bytes = (size_t)bw * r.bh; }                            // IS_8_BIT_FULL, payload already written
-        else if (all1) continue;                                                          // all 255: no chunk
-        else {                                                                            // binary: IS_1_BIT_FULL on the box re-aligned to 8
-            const int bR = ((bL + bw + 7) >> 3) << 3;
-            bL = (bL >> 3) << 3; bw = bR - bL;
-            bytes = (size_t)(bw >> 3) * r.bh;
-            o.mode = 1;
-            maxBytes1 = bytes > maxBytes1 ? bytes : maxBytes1;
-        }
-        o.bbox[0] = bL; o.bbox[1] = r.bT; o.bbox[2] = bw; o.bbox[3] = r.bh; o.rawSize = (uint32_t)bytes;
+        const size_t bytes = yk_ave_chunk(r, &st[(size_t)r.frame * 8], o);
+        if (o.mode < 0) continue;                                                         // all 255: no chunk
+        if (o.mode == 1) maxBytes1 = bytes > maxBytes1 ? bytes : maxBytes1;
         c->avBatch[(size_t)r.frame] = yk_ctx::AvSlot{ o.mode, (size_t)r.off, bytes };
     }
-    if (maxBytes1) {
-        hipLaunchKernelGGL(yk_ave_pack1_batch_kernel, dim3((unsigned)((maxBytes1 + 255) / 256), 1, nBox), dim3(256), 0, c->stream, alpha, fe, c->strideElems, dTab,
-                           c->avPay, c->avState);
-        YK_HIP(c, hipGetLastError());
-    }
+    if (maxBytes1) { const int rc = yk_ave_pack1(c, tab.size(), maxBytes1); if (rc) return rc; }
     c->avBatchValid = true;
     return YK_OK;
 }

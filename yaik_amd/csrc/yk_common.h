@@ -246,11 +246,11 @@ struct yk_ctx {
     bool dSplit = false;
     YkBuf<uint8_t> dAlpha; bool dAlphaValid = false;     // yk_decode_alpha: the w x h alpha plane of the image being decoded
     YkBuf<uint8_t> dAvScratch;                           // its payload, mask and row counts
-    YkBuf<int32_t> avState; YkBuf<uint8_t> avPay;        // yk_alpha_values: box + class flags, the payload
-    YkBuf<uint8_t> av6;                                  // its 6-bit mask mode: tile prefixes, band scan, packed payload
-    // yk_alpha_values_batch: avState holds 8 ints per frame, avPay the frames' payload slots back to back, avTab the per-frame records in HBM;
-    // avBatch = what the payload getters hand out (valid while avBatchValid)
-    YkBuf<uint8_t> avTab;
+    // yk_alpha_values[_batch], one layout: avState holds 8 ints per frame (box + class flags), avPay the frames' payload slots back to back
+    // (each on a multiple of 16), avTab the records of the frames that have a box, in HBM
+    YkBuf<int32_t> avState; YkBuf<uint8_t> avPay, avTab;
+    YkBuf<uint8_t> av6;                                  // yk_alpha_values' 6-bit mask mode: tile prefixes, band scan, packed payload
+    // avBatch = what the payload getters hand out after yk_alpha_values_batch (valid while avBatchValid; yk_alpha_values publishes no slot)
     struct AvSlot { int32_t mode; size_t off, bytes; };
     std::vector<AvSlot> avBatch; bool avBatchValid = false;
     // yk_alpha_bitmaps_batch: the 'MIPM' bits of every frame, one slot of mipSlot bytes each (written whole by the kernel); mipBytes = the lengths
