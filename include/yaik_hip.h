@@ -143,6 +143,17 @@ int yk_alpha_values(yk_ctx* c, int force8Bit, yk_alpha_info* out, uint8_t* hostP
 int yk_alpha_values_batch(yk_ctx* c, int force8Bit, yk_alpha_info* infos /* nFrames */);
 int yk_alpha_payload_device(yk_ctx* c, int frame, const uint8_t** dev, size_t* nBytes);
 int yk_alpha_payload(yk_ctx* c, int frame, uint8_t* hostOut, size_t cap, size_t* nBytes);
+/* yk_alpha_values(force8Bit[f]) for every frame of the handle, the 6-bit mask mode included; force8Bit = NULL is 0 for every frame.  Valid in the
+ * states of yk_alpha_values_batch.  infos[f] and frame f's payload are byte for byte what yk_alpha_values(c, force8Bit[f], ..) returns for that
+ * frame bound alone: mode -1, 1, 3 or 6.  Box, class and 1-bit pack are yk_alpha_values_batch's; the frames classed analog whose force8Bit is 0 get
+ * one record each (keep flags, bounds, the u8 box in the frame's 8-bit slot, a 6-bit slot of (bw / 4) * 3 * bh bytes on a multiple of 16 in a second
+ * grow-only buffer) and three launches over all of them: band prefixes (one wave per tile band), one wave per record scanning its bands, the pack.
+ * Whatever nFrames is: at most six launches, three blocking read-backs (boxes, class flags, selected counts) and two table uploads; when no frame
+ * takes the 6-bit path the call costs what yk_alpha_values_batch costs.  A selected count beyond the box fails with YK_ERR_STATE.
+ * The getters above hand out the 6-bit slot for mode 3 and the 8-bit slot for modes 1 and 6, under the same validity rule.
+ * Refusals launch nothing and leave the handle and earlier published payloads usable: YK_ERR_BAD_ARG for NULL infos; YK_ERR_STATE before the alpha
+ * stage has finished, on a stripe, without bound planes, and for a handle without keep flags.  No alpha plane: mode -1 for all, nothing launched. */
+int yk_alpha_values_mask_batch(yk_ctx* c, const uint8_t* force8Bit /* nFrames, or NULL */, yk_alpha_info* infos /* nFrames */);
 /* The 'MIPM' bitmaps of every frame of the handle (new), after the alpha stage of all frames: yk_encode_batch, or for a batch of one yk_alpha_reject +
  * yk_alpha_finish.  infos[f] and frame f's bytes are exactly what yk_select_frame(f) + yk_alpha_result + yk_alpha_bitmap give: hasChunk = 0 and
  * nBytes = 0 when the box is the whole image, nBytes = 0 when no tile is kept (bounds[2] < bounds[0]), otherwise bit y * tw + x of tileBBox, LSB

@@ -54,6 +54,7 @@ SIGNATURES = {
     "yk_alpha_bitmap": (C.c_int, [vp, vp, sz, szp]),
     "yk_alpha_values": (C.c_int, [vp, C.c_int, vp, vp, sz, szp]),
     "yk_alpha_values_batch": (C.c_int, [vp, C.c_int, vp]),
+    "yk_alpha_values_mask_batch": (C.c_int, [vp, vp, vp]),
     "yk_alpha_payload_device": (C.c_int, [vp, C.c_int, C.POINTER(vp), szp]),
     "yk_alpha_payload": (C.c_int, [vp, C.c_int, vp, sz, szp]),
     "yk_alpha_bitmaps_batch": (C.c_int, [vp, vp]),

@@ -4,6 +4,8 @@
 //   yk_alpha_values_batch   the same for every frame of the handle.  There is one encode path: yk_ave_classify (box, slots, class) and
 //                     yk_ave_chunk (class -> mode, box, bytes) serve both entry points, the single image is a batch of one that copies its
 //                     payload out and, for force8Bit = false, packs the 6-bit payload from its slot
+//   yk_alpha_values_mask_batch   ProcessAlpha(force8Bit[f]) per frame: the same path, and batch forms of the three 6-bit kernels over the analog
+//                     frames whose force8Bit is 0, each into a 6-bit slot of its own
 //   yk_decode_alpha   Decompress1BitMaskAlign8NoMask (decoder/YAIK_Alpha.cpp:25-112), Decompress6BitTo8BitAlphaNoMask (:114-235),
 //                     Decompress6BitTo8BitAlphaUsingMipmapMask (:237-376), Decompress8BitTo8BitAlphaNoMask (:377-444): the full w x h plane
 //                     in HBM (0 outside the box), kept for yk_decode_output_alpha.
@@ -317,9 +319,9 @@ __global__ __launch_bounds__(256) void yk_ave_pack1_batch_kernel(const int32_t* 
 __device__ __forceinline__ bool yk_ave_all_kept(const int32_t* __restrict__ b, int W, int H) { return b[0] == 0 && b[1] == 0 && b[2] == W && b[3] == H; }
 // one wave per tile band of the box: colPre[band][i] = selected samples of one band row left of tile column txB + i, bandS = per row,
 // bandCnt = per band (bandS x the band's rows in the box)
-__global__ __launch_bounds__(64) void yk_ave_band_kernel(const uint8_t* __restrict__ keep, int mtW, int mtH, const int32_t* __restrict__ bounds, int W, int H,
-                                                         int bL, int bT, int bR, int bB, int ncol, uint32_t* __restrict__ colPre, uint32_t* __restrict__ bandS,
-                                                         uint32_t* __restrict__ bandCnt) {
+__device__ __forceinline__ void yk_ave_band_body(const uint8_t* __restrict__ keep, int mtW, int mtH, const int32_t* __restrict__ bounds, int W, int H,
+                                                 int bL, int bT, int bR, int bB, int ncol, uint32_t* __restrict__ colPre, uint32_t* __restrict__ bandS,
+                                                 uint32_t* __restrict__ bandCnt) {
     const int b = blockIdx.x, lane = threadIdx.x, ty = (bT >> 4) + b, txB = bL >> 4;
     const bool all = yk_ave_all_kept(bounds, W, H);
     uint32_t carry = 0;
@@ -337,12 +339,17 @@ __global__ __launch_bounds__(64) void yk_ave_band_kernel(const uint8_t* __restri
         bandCnt[b] = carry * (uint32_t)(min(bB, ty * 16 + 16) - max(bT, ty * 16));
     }
 }
+__global__ __launch_bounds__(64) void yk_ave_band_kernel(const uint8_t* __restrict__ keep, int mtW, int mtH, const int32_t* __restrict__ bounds, int W, int H,
+                                                         int bL, int bT, int bR, int bB, int ncol, uint32_t* __restrict__ colPre, uint32_t* __restrict__ bandS,
+                                                         uint32_t* __restrict__ bandCnt) {
+    yk_ave_band_body(keep, mtW, mtH, bounds, W, H, bL, bT, bR, bB, ncol, colPre, bandS, bandCnt);
+}
 // one thread = one 4-sample group of the u8 box the class kernel wrote (one 4-byte load) = one 3-byte group of the payload when its tile is
 // selected: index = band start + rows of the band above it x bandS + colPre + its offset in the tile's run; values 63 - (v >> 2), LSB first
-__global__ __launch_bounds__(256) void yk_ave_pack6_kernel(const uint8_t* __restrict__ box, int bL, int bT, int bw, int bh, const uint8_t* __restrict__ keep,
-                                                           int mtW, int mtH, const int32_t* __restrict__ bounds, int W, int H, int ncol, int nb,
-                                                           const uint32_t* __restrict__ colPre, const uint32_t* __restrict__ bandS,
-                                                           const uint32_t* __restrict__ bandStart, uint8_t* __restrict__ out, size_t cap) {
+__device__ __forceinline__ void yk_ave_pack6_body(const uint8_t* __restrict__ box, int bL, int bT, int bw, int bh, const uint8_t* __restrict__ keep,
+                                                  int mtW, int mtH, const int32_t* __restrict__ bounds, int W, int H, int ncol, int nb,
+                                                  const uint32_t* __restrict__ colPre, const uint32_t* __restrict__ bandS,
+                                                  const uint32_t* __restrict__ bandStart, uint8_t* __restrict__ out, size_t cap) {
     const int c = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4, r = blockIdx.y;
     if (c >= bw || r >= bh) return;
     const int x = bL + c, y = bT + r, tx = x >> 4, ty = y >> 4;
@@ -358,6 +365,54 @@ __global__ __launch_bounds__(256) void yk_ave_pack6_kernel(const uint8_t* __rest
     out[o] = (uint8_t)(q0 | (q1 << 6));
     out[o + 1] = (uint8_t)((q1 >> 2) | (q2 << 4));
     out[o + 2] = (uint8_t)((q2 >> 4) | (q3 << 2));
+}
+__global__ __launch_bounds__(256) void yk_ave_pack6_kernel(const uint8_t* __restrict__ box, int bL, int bT, int bw, int bh, const uint8_t* __restrict__ keep,
+                                                           int mtW, int mtH, const int32_t* __restrict__ bounds, int W, int H, int ncol, int nb,
+                                                           const uint32_t* __restrict__ colPre, const uint32_t* __restrict__ bandS,
+                                                           const uint32_t* __restrict__ bandStart, uint8_t* __restrict__ out, size_t cap) {
+    yk_ave_pack6_body(box, bL, bT, bw, bh, keep, mtW, mtH, bounds, W, H, ncol, nb, colPre, bandS, bandStart, out, cap);
+}
+// the same three in a batch (yk_alpha_values_mask_batch): one record per frame classed analog whose force8Bit is 0, record blockIdx.z read through
+// uniform loads.  keep / bounds = the frame's keep flags and image-wide box, box = its u8 slot in avPay, out = its 6-bit slot of `cap` bytes;
+// its prefixes lie in one u32 arena at `arena`: colPre[nb * ncol], bandS[nb], bandCnt[nb], bandStart[nb + 1].  The grids are sized from the
+// largest record: workgroups outside their frame's box leave at once.
+struct YkAv6Rec {
+    const uint8_t* keep; const int32_t* bounds; const uint8_t* box; uint8_t* out;
+    unsigned long long cap, arena;
+    int32_t bL, bT, bR, bB, ncol, nb;
+};
+__global__ __launch_bounds__(64) void yk_ave_band_batch_kernel(const YkAv6Rec* __restrict__ tab, int mtW, int mtH, int W, int H, uint32_t* __restrict__ u32s) {
+    const YkAv6Rec r = tab[blockIdx.z];
+    if ((int)blockIdx.x >= r.nb) return;
+    uint32_t* colPre = u32s + r.arena;
+    uint32_t* bandS = colPre + (size_t)r.nb * r.ncol;
+    yk_ave_band_body(r.keep, mtW, mtH, r.bounds, W, H, r.bL, r.bT, r.bR, r.bB, r.ncol, colPre, bandS, bandS + r.nb);
+}
+// one wave per record: exclusive prefix of its bandCnt with the carry across the 64-band steps, the total in bandStart[nb] and in totals[record]
+// (one contiguous array: the selected counts of every record come back in one copy)
+__global__ __launch_bounds__(64) void yk_ave_bandscan_batch_kernel(const YkAv6Rec* __restrict__ tab, uint32_t* __restrict__ u32s, uint32_t* __restrict__ totals) {
+    const YkAv6Rec r = tab[blockIdx.z];
+    const int lane = threadIdx.x;
+    const uint32_t* bandCnt = u32s + r.arena + (size_t)r.nb * r.ncol + r.nb;
+    uint32_t* bandStart = u32s + r.arena + (size_t)r.nb * r.ncol + 2 * (size_t)r.nb;
+    uint32_t carry = 0;
+    for (int i0 = 0; i0 < r.nb; i0 += 64) {
+        const int i = i0 + lane;
+        const uint32_t v = i < r.nb ? bandCnt[i] : 0u;
+        uint32_t s = v;
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(s, o, 64); if (lane >= o) s += t; }
+        if (i < r.nb) bandStart[i] = carry + s - v;
+        carry += __shfl(s, 63, 64);
+    }
+    if (lane == 0) { bandStart[r.nb] = carry; totals[blockIdx.z] = carry; }
+}
+__global__ __launch_bounds__(256) void yk_ave_pack6_batch_kernel(const YkAv6Rec* __restrict__ tab, int mtW, int mtH, int W, int H, const uint32_t* __restrict__ u32s) {
+    const YkAv6Rec r = tab[blockIdx.z];
+    const int bw = r.bR - r.bL, bh = r.bB - r.bT;
+    if ((int)blockIdx.y >= bh || (int)blockIdx.x * 1024 >= bw) return;
+    const uint32_t* colPre = u32s + r.arena;
+    const uint32_t* bandS = colPre + (size_t)r.nb * r.ncol;
+    yk_ave_pack6_body(r.box, r.bL, r.bT, bw, bh, r.keep, mtW, mtH, r.bounds, W, H, r.ncol, r.nb, colPre, bandS, bandS + 2 * (size_t)r.nb, r.out, (size_t)r.cap);
 }
 
 }  // namespace
@@ -605,6 +660,87 @@ int yk_alpha_values_batch(yk_ctx* c, int force8Bit, yk_alpha_info* infos) {
     return YK_OK;
 }
 
+// ProcessAlpha(force8Bit[f] != 0) for every frame of the handle: yk_alpha_values_batch's path, and for the frames classed analog whose force8Bit is 0
+// the three 6-bit launches over all of them, one more record table and the read-back of their selected counts
+int yk_alpha_values_mask_batch(yk_ctx* c, const uint8_t* force8Bit, yk_alpha_info* infos) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!infos) return yk_refuse(c, YK_ERR_BAD_ARG, "infos is NULL");
+    const int N = c->nFrames, W = c->fullW, H = c->fullH;
+    if (c->nPlanes == 4) {
+        if (!c->alphaFinished) return yk_refuse(c, YK_ERR_STATE, "the alpha stage first: yk_encode_batch, or yk_alpha_reject + yk_alpha_finish");
+        if (c->y0 != 0 || c->h != c->fullH) return yk_refuse(c, YK_ERR_STATE, "yk_alpha_values_mask_batch works on whole images, not on a stripe");
+        if (!c->B.plane[3] || (N > 1 && c->fs.plane == 0)) return yk_refuse(c, YK_ERR_STATE, "bind planes first");
+        if (!c->B.keep || !c->B.bounds) return yk_refuse(c, YK_ERR_STATE, "6-bit alpha: the handle has no keep flags");
+    }
+    for (int f = 0; f < N; f++) { infos[f].mode = -1; infos[f].bbox[0] = infos[f].bbox[1] = infos[f].bbox[2] = infos[f].bbox[3] = 0; infos[f].rawSize = 0; }
+    c->avBatchValid = false;
+    c->avBatch.assign((size_t)N, yk_ctx::AvSlot{ -1, 0, 0 });
+    if (c->nPlanes != 4) { c->avBatchValid = true; return YK_OK; }                        // no alpha: no chunk in any frame (:1674-1680)
+    YK_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> st;
+    std::vector<YkAvFrame> tab;
+    { const int rc = yk_ave_classify(c, st, tab); if (rc) return rc; }
+    // the class decision of every frame; an analog frame with force8Bit = 0 gets a record: its 6-bit slot ((bw / 4) * 3 * bh bytes, on a multiple of
+    // 16) and its region of the u32 arena
+    std::vector<YkAv6Rec> recs;
+    std::vector<int> frameOf;                                                             // record -> frame
+    size_t maxBytes1 = 0, paySize = 0, arena = 0;
+    int maxNb = 0, maxBw = 0, maxBh = 0;
+    for (const YkAvFrame& r : tab) {
+        yk_alpha_info& o = infos[r.frame];
+        const size_t bytes = yk_ave_chunk(r, &st[(size_t)r.frame * 8], o);
+        if (o.mode < 0) continue;                                                         // all 255: no chunk
+        if (o.mode == 1) maxBytes1 = bytes > maxBytes1 ? bytes : maxBytes1;
+        c->avBatch[(size_t)r.frame] = yk_ctx::AvSlot{ o.mode, (size_t)r.off, bytes };
+        if (o.mode != 6 || (force8Bit && force8Bit[r.frame])) continue;
+        const YkFrameView V = yk_frame(c, r.frame);
+        YkAv6Rec q;
+        q.keep = V.keep; q.bounds = V.bounds + c->boundsOff; q.box = c->avPay + r.off; q.out = nullptr;
+        q.bL = r.bL; q.bT = r.bT; q.bR = r.bL + r.bw; q.bB = r.bT + r.bh;
+        q.nb = ((q.bB - 1) >> 4) - (q.bT >> 4) + 1; q.ncol = ((q.bR - 1) >> 4) - (q.bL >> 4) + 1;
+        q.cap = (unsigned long long)(r.bw >> 2) * 3 * r.bh; q.arena = arena;
+        arena += (size_t)q.nb * q.ncol + 3 * (size_t)q.nb + 1;
+        c->avBatch[(size_t)r.frame] = yk_ctx::AvSlot{ 3, paySize, 0 };                    // the slot's offset behind the tables: added below
+        paySize = (paySize + (size_t)q.cap + 15) & ~(size_t)15;
+        maxNb = max(maxNb, q.nb); maxBw = max(maxBw, r.bw); maxBh = max(maxBh, r.bh);
+        recs.push_back(q); frameOf.push_back(r.frame);
+    }
+    if (maxBytes1) { const int rc = yk_ave_pack1(c, tab.size(), maxBytes1); if (rc) return rc; }
+    const size_t n6 = recs.size();
+    if (n6) {
+        // av6: the record table, the n6 totals, the u32 arena, the 6-bit slots
+        const size_t oTot = (n6 * sizeof(YkAv6Rec) + 15) & ~(size_t)15, oArena = (oTot + n6 * sizeof(uint32_t) + 15) & ~(size_t)15;
+        const size_t oPay = (oArena + arena * sizeof(uint32_t) + 255) & ~(size_t)255;
+        YK_HIP(c, c->av6.reserve(c->stream, oPay + paySize));
+        for (size_t k = 0; k < n6; k++) {
+            yk_ctx::AvSlot& s = c->avBatch[(size_t)frameOf[k]];
+            s.off += oPay; recs[k].out = c->av6 + s.off;
+        }
+        YK_HIP(c, hipMemcpyAsync(c->av6, recs.data(), n6 * sizeof(YkAv6Rec), hipMemcpyHostToDevice, c->stream));
+        const YkAv6Rec* dTab = reinterpret_cast<const YkAv6Rec*>(c->av6.p);
+        uint32_t* dTot = reinterpret_cast<uint32_t*>(c->av6 + oTot);
+        uint32_t* u32s = reinterpret_cast<uint32_t*>(c->av6 + oArena);
+        hipLaunchKernelGGL(yk_ave_band_batch_kernel, dim3((unsigned)maxNb, 1, (unsigned)n6), dim3(64), 0, c->stream, dTab, c->mtW, c->mtH, W, H, u32s);
+        hipLaunchKernelGGL(yk_ave_bandscan_batch_kernel, dim3(1, 1, (unsigned)n6), dim3(64), 0, c->stream, dTab, u32s, dTot);
+        hipLaunchKernelGGL(yk_ave_pack6_batch_kernel, dim3((unsigned)((maxBw / 4 + 255) / 256), (unsigned)maxBh, (unsigned)n6), dim3(256), 0, c->stream, dTab,
+                           c->mtW, c->mtH, W, H, u32s);
+        YK_HIP(c, hipGetLastError());
+        std::vector<uint32_t> totals(n6);
+        YK_HIP(c, hipMemcpyAsync(totals.data(), dTot, n6 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        YK_HIP(c, hipStreamSynchronize(c->stream));                                       // readback 3: the selected counts size the payloads
+        for (size_t k = 0; k < n6; k++) {
+            const uint32_t total = totals[k];
+            static const size_t tail[4] = { 0, 1, 2, 3 };
+            const size_t bytes = (size_t)(total >> 2) * 3 + tail[total & 3];               // :1549-1551 (total is a multiple of 4 here)
+            if (bytes > (size_t)recs[k].cap) return yk_fail(c, YK_ERR_STATE, "6-bit alpha: selected count beyond the box");
+            c->avBatch[(size_t)frameOf[k]].bytes = bytes;
+            infos[frameOf[k]].mode = 3; infos[frameOf[k]].rawSize = (uint32_t)bytes;
+        }
+    }
+    c->avBatchValid = true;
+    return YK_OK;
+}
+
 int yk_alpha_payload_device(yk_ctx* c, int frame, const uint8_t** dev, size_t* nBytes) {
     if (!c) return YK_ERR_BAD_ARG;
     if (dev) *dev = nullptr;
@@ -614,7 +750,7 @@ int yk_alpha_payload_device(yk_ctx* c, int frame, const uint8_t** dev, size_t* n
     if (frame < 0 || frame >= (int)c->avBatch.size()) return yk_refuse(c, YK_ERR_BAD_ARG, "frame out of range");
     const yk_ctx::AvSlot& s = c->avBatch[(size_t)frame];
     if (s.mode < 0) return YK_OK;
-    *dev = c->avPay + s.off; *nBytes = s.bytes;
+    *dev = (s.mode == 3 ? c->av6.p : c->avPay.p) + s.off; *nBytes = s.bytes;   // mode 3: the 6-bit slot of yk_alpha_values_mask_batch
     return YK_OK;
 }
 

@@ -249,8 +249,11 @@ struct yk_ctx {
     // yk_alpha_values[_batch], one layout: avState holds 8 ints per frame (box + class flags), avPay the frames' payload slots back to back
     // (each on a multiple of 16), avTab the records of the frames that have a box, in HBM
     YkBuf<int32_t> avState; YkBuf<uint8_t> avPay, avTab;
-    YkBuf<uint8_t> av6;                                  // yk_alpha_values' 6-bit mask mode: tile prefixes, band scan, packed payload
-    // avBatch = what the payload getters hand out after yk_alpha_values_batch (valid while avBatchValid; yk_alpha_values publishes no slot)
+    // the 6-bit mask mode: tile prefixes, band scan, packed payload (yk_alpha_values); the record table, selected counts, prefix arena and 6-bit
+    // slots of every such frame (yk_alpha_values_mask_batch)
+    YkBuf<uint8_t> av6;
+    // avBatch = what the payload getters hand out after yk_alpha_values[_mask]_batch (valid while avBatchValid; yk_alpha_values publishes no slot):
+    // off is into avPay, for mode 3 into av6
     struct AvSlot { int32_t mode; size_t off, bytes; };
     std::vector<AvSlot> avBatch; bool avBatchValid = false;
     // yk_alpha_bitmaps_batch: the 'MIPM' bits of every frame, one slot of mipSlot bytes each (written whole by the kernel); mipBytes = the lengths

@@ -22,7 +22,7 @@ class AlphaBatchPack(NamedTuple):
     nbytes: np.ndarray      # uint64 [N]: payload lengths
     where: list             # per frame ("h", offset into staging), ("d", device address) or None
     staging: np.ndarray     # uint8: every host payload at its offset, offsets are multiples of 16; empty when no entry is a host array
-    mip_where: list = None  # only when an entry has a mask: per frame the offset of its 'MIPM' bitmap in staging, or None
+    mip_where: list = None  # only when an entry has a mask: per frame the offset of its 'MIPM' bitmap in staging, ("d", device address) or None
     mip_nbytes: np.ndarray = None   # uint64 [N]: bitmap lengths
     mip_boxes: np.ndarray = None    # int32 [N, 4]: the 'MIPM' box in 16-pixel tiles, zeros (w == 0) for a frame without one
 
@@ -30,7 +30,8 @@ class AlphaBatchPack(NamedTuple):
 def pack_alpha_batch(entries) -> AlphaBatchPack:
     """entries[f]: None (no 'ALPM' chunk), or (mode, bbox, payload[, nbytes]) with payload a numpy uint8 array (nbytes defaults to its size) or a
     device pointer (int / c_void_p; nbytes required), or (mode, bbox, payload, mip_bits, mip_box): a numpy payload with the frame's 'MIPM'
-    bitmap (numpy uint8, 1 bit per tile as the file holds it) and its box (x, y, w, h) in 16-pixel tiles, which the mask modes 2 and 3 need.
+    bitmap (numpy uint8, 1 bit per tile as the file holds it) and its box (x, y, w, h) in 16-pixel tiles, which the mask modes 2 and 3 need,
+    or (mode, bbox, payload ptr, nbytes, mip ptr, mip nbytes, mip_box): the same with payload and bitmap in device memory.
     Host payloads and bitmaps are laid out back to back in one staging array, each at a 16-byte aligned offset, so that they reach the device in
     one copy.  The mip_* fields stay None unless an entry has a mask.  Reads only the entries: no GPU."""
     n = len(entries)
@@ -40,11 +41,14 @@ def pack_alpha_batch(entries) -> AlphaBatchPack:
     for f, e in enumerate(entries):
         if e is None:
             continue
-        if len(e) not in (3, 4, 5):
-            raise ValueError(f"entry {f}: (mode, bbox, payload[, nbytes]), (mode, bbox, payload, mip_bits, mip_box) or None expected")
+        if len(e) not in (3, 4, 5, 7):
+            raise ValueError(f"entry {f}: (mode, bbox, payload[, nbytes]), (mode, bbox, payload, mip_bits, mip_box), "
+                             "(mode, bbox, payload ptr, nbytes, mip ptr, mip nbytes, mip_box) or None expected")
         mode, bbox, pay = int(e[0]), np.asarray(e[1], dtype=np.int64).reshape(-1), e[2]
         if mode < 0 or bbox.size != 4:
             raise ValueError(f"entry {f}: a mode >= 0 and a box (x, y, w, h) expected (None marks a frame without a chunk)")
+        if len(e) == 7 and (isinstance(pay, np.ndarray) or isinstance(e[4], np.ndarray) or np.asarray(e[6]).size != 4 or int(e[5]) < 0):
+            raise ValueError(f"entry {f}: a device mask entry takes device pointers with their lengths and a tile box (x, y, w, h)")
         if len(e) == 5 and not (isinstance(pay, np.ndarray) and isinstance(e[3], np.ndarray) and np.asarray(e[4]).size == 4):
             raise ValueError(f"entry {f}: a mask entry takes numpy arrays for payload and 'MIPM' bitmap and a tile box (x, y, w, h)")
         modes[f], bboxes[f] = mode, bbox
@@ -57,7 +61,7 @@ def pack_alpha_batch(entries) -> AlphaBatchPack:
             chunks.append((size, a[:nb]))
             size = (size + nb + 15) & ~15
         else:
-            if len(e) != 4:
+            if len(e) not in (4, 7):
                 raise ValueError(f"entry {f}: a device payload needs its length")
             pay = pay.value if isinstance(pay, C.c_void_p) else pay
             nb = int(e[3])
@@ -71,6 +75,10 @@ def pack_alpha_batch(entries) -> AlphaBatchPack:
             mip_where[f], mip_nbytes[f], mip_boxes[f] = size, bits.size, np.asarray(e[4], dtype=np.int64).reshape(4)
             chunks.append((size, bits))
             size = (size + bits.size + 15) & ~15
+        if len(e) == 7:                                                    # the bits lie in device memory (HipTileEncoder.alpha_mask_payloads_device)
+            mp = e[4].value if isinstance(e[4], C.c_void_p) else e[4]
+            masks = True
+            mip_where[f], mip_nbytes[f], mip_boxes[f] = ("d", int(mp) if mp else 0), int(e[5]), np.asarray(e[6], dtype=np.int64).reshape(4)
     staging = np.zeros(size, dtype=np.uint8)
     for off, a in chunks:
         staging[off:off + a.size] = a
@@ -276,10 +284,14 @@ class HipTileDecoder:
         self._batch_streams = keep
         return frames
 
-    def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False, per_frame: bool = False, palette: bool = False) -> None:
+    def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False, per_frame: bool = False, palette: bool = False,
+                                  alpha_6bit: bool = False) -> None:
         """decode_batch_streams of encoder_batch_streams(enc, per_frame); alpha=True also runs the encoder's alpha_values_batch and decodes every
         frame's 'ALPM' payload where the encoder left it in HBM (decompress_alpha_batch; frames without a chunk are opaque).  With sync=False on
         the default path the queued decode reads the encoder's own stream buffer: fence this decoder before the encoder's next encode.
+        alpha_6bit=True (with alpha): the alpha goes through the encoder's alpha_bitmaps_device + alpha_mask_payloads_device and
+        yk_decode_alpha_mask_batch_device, bits and payloads read where they lie in HBM: analog frames that have 'MIPM' bits are written and read
+        in the 6-bit mask mode (3); a frame without bits has no mask to decode against and keeps the 8-bit mode.
         palette=True: the corner streams take the way of a file.  The payloads the CALLER made with enc.palette_compress_batch() (after
         enc.streams_batch(); this method does not touch the encoder's coder state) are decompressed on this handle
         (palette_decompress_streams, remap_range 250) and the gradient decode reads those outputs with remap off.  Only for streams that
@@ -299,7 +311,10 @@ class HipTileDecoder:
         else:
             frames = self.encoder_batch_streams(enc, per_frame)
         entries = None
-        if alpha:
+        if alpha and alpha_6bit:
+            entries = enc.alpha_mask_payloads_device([m["nbytes"] == 0 for m in enc.alpha_bitmaps_device()])
+            enc.synchronize()
+        elif alpha:
             entries = enc.alpha_payloads_device()
             enc.synchronize()                                              # the payloads are written on the encoder's stream
         if palette:
@@ -412,7 +427,8 @@ class HipTileDecoder:
         """The 'ALPM' plane of every frame of the batch in one launch (yk_decode_alpha_batch_device).  entries[f] is None (no chunk: the plane is
         the constant no_chunk_alpha) or (mode, bbox, payload[, nbytes]) with the DECOMPRESSED payload as a numpy uint8 array or a device pointer
         with its length (HipTileEncoder.alpha_payloads_device); modes 1, 4, 5 and 6.  An entry (mode, bbox, payload, mip_bits, mip_box) carries the
-        frame's 'MIPM' bitmap and tile box as well; when any entry does, the call goes to yk_decode_alpha_mask_batch_device, which also decodes
+        frame's 'MIPM' bitmap and tile box as well, and so does (mode, bbox, payload ptr, nbytes, mip ptr, mip nbytes, mip_box) with both in device
+        memory (HipTileEncoder.alpha_mask_payloads_device); when any entry does, the call goes to yk_decode_alpha_mask_batch_device, which also decodes
         the mask modes 2 and 3 (three more launches over the masked frames; alpha_batch_status() tells whether a payload was shorter than its mask
         selects).  Host arrays are packed into one staging tensor (pack_alpha_batch) and sent in one copy.  The planes stay on the device for
         image_batch_device(alpha_from_planes=True) and, frame by frame, for image_device(alpha=-1) and alpha_plane()."""
@@ -438,7 +454,7 @@ class HipTileDecoder:
             _chk(self._h, L.yk_decode_alpha_batch_device(self._h, pk.modes.ctypes.data, np.ascontiguousarray(pk.bboxes).ctypes.data, ptrs, sizes,
                                                           int(no_chunk_alpha)))
         else:
-            mptrs = (C.c_void_p * n)(*[None if o is None else base + o for o in pk.mip_where])
+            mptrs = (C.c_void_p * n)(*[None if o is None else ((o[1] or None) if isinstance(o, tuple) else base + o) for o in pk.mip_where])
             msizes = (C.c_size_t * n)(*[int(v) for v in pk.mip_nbytes])
             _chk(self._h, L.yk_decode_alpha_mask_batch_device(self._h, pk.modes.ctypes.data, np.ascontiguousarray(pk.bboxes).ctypes.data, ptrs, sizes,
                                                                mptrs, msizes, np.ascontiguousarray(pk.mip_boxes).ctypes.data, int(no_chunk_alpha)))

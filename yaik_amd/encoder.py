@@ -211,6 +211,7 @@ class HipTileEncoder:
         self._h = h
         _HANDLE_LIB[h.value] = L
         self._keepalive = None
+        self._mip_boxes = None          # the tile boxes of the last yk_alpha_bitmaps_batch; whether its bits still hold is the library's to say
         self.w = self.h = self.n = 0
         self.frames = 1                 # images bound: 1, or the F of set_batch / set_batch_u8
 
@@ -367,9 +368,65 @@ class HipTileEncoder:
             out.append((e[0], e[1], int(dev.value or 0), int(n.value)))
         return out
 
+    def _force8bit_flags(self, force8bit):
+        """None (0 for every frame: NULL), a bool (every frame) or a sequence of `frames` bools -> the uint8 array yk_alpha_values_mask_batch
+        takes, or None.  A wrong length raises ValueError: nothing has been called yet."""
+        if force8bit is None:
+            return None
+        if isinstance(force8bit, (bool, np.bool_)):
+            return np.full(self.frames, 1 if force8bit else 0, dtype=np.uint8)
+        flags = np.array([1 if v else 0 for v in force8bit], dtype=np.uint8)
+        if flags.size != self.frames:
+            raise ValueError(f"{flags.size} force8bit flags for a batch of {self.frames} frames")
+        return flags
+
+    def _alpha_values_mask_batch(self, force8bit) -> list:
+        class _Info(C.Structure):
+            _fields_ = [("mode", C.c_int32), ("bbox", C.c_int32 * 4), ("rawSize", C.c_uint32)]
+
+        flags = self._force8bit_flags(force8bit)
+        infos = (_Info * self.frames)()
+        _chk(self._h, self._L.yk_alpha_values_mask_batch(self._h, None if flags is None else flags.ctypes.data, infos))
+        return [None if i.mode < 0 else (int(i.mode), tuple(int(v) for v in i.bbox), int(i.rawSize)) for i in infos]
+
+    def alpha_values_mask_batch(self, force8bit=None) -> list:
+        """ProcessAlpha(force8bit[f]) for every frame of the handle (yk_alpha_values_mask_batch), after encode_batch() (or, for one frame,
+        mip_prefilter()): per frame the dict of alpha_values(force8bit[f]), or None where no 'ALPM' chunk is written.  force8bit is None (the
+        6-bit mask mode for every analog frame), a bool, or one bool per frame.  At most six launches and three read-backs for the whole batch;
+        the payloads are then copied out frame by frame (alpha_mask_payloads_device leaves them in HBM)."""
+        out = []
+        for f, e in enumerate(self._alpha_values_mask_batch(force8bit)):
+            if e is None:
+                out.append(None)
+                continue
+            pay, n = np.empty(e[2], dtype=np.uint8), C.c_size_t()
+            _chk(self._h, self._L.yk_alpha_payload(self._h, f, pay.ctypes.data if pay.size else None, pay.size, C.byref(n)))
+            out.append({"mode": e[0], "bbox": e[1], "payload": pay[:n.value]})
+        return out
+
+    def alpha_mask_payloads_device(self, force8bit=None) -> list:
+        """alpha_values_mask_batch() without copying the payloads out: per frame None or (mode, bbox, device pointer, nbytes, 'MIPM' bits
+        pointer, their length, tile box), the entries HipTileDecoder.decompress_alpha_batch takes for masked frames.  The bits are those of the
+        last alpha_bitmaps_device() of this handle while yk_alpha_bitmap_device still hands them out (until the next encode, alpha_reject,
+        set_image / set_batch), else pointer 0, length 0 and the box (0, 0, 0, 0) -- a mode-3 entry then cannot be decoded.  Validity as for alpha_payloads_device."""
+        entries = self._alpha_values_mask_batch(force8bit)
+        out = []
+        for f, e in enumerate(entries):
+            if e is None:
+                out.append(None)
+                continue
+            dev, n = C.c_void_p(), C.c_size_t()
+            _chk(self._h, self._L.yk_alpha_payload_device(self._h, f, C.byref(dev), C.byref(n)))
+            # the library says whether the bits of yk_alpha_bitmaps_batch still hold (it refuses once they are gone): one validity rule
+            bits, nbits = C.c_void_p(), C.c_size_t()
+            have = self._mip_boxes is not None and self._L.yk_alpha_bitmap_device(self._h, f, C.byref(bits), C.byref(nbits)) == 0 and nbits.value
+            out.append((e[0], e[1], int(dev.value or 0), int(n.value)) + ((int(bits.value), int(nbits.value), self._mip_boxes[f]) if have else (0, 0, (0, 0, 0, 0))))
+        return out
+
     def _alpha_bitmaps_batch(self):
         infos = (_MipInfoC * self.frames)()
         _chk(self._h, self._L.yk_alpha_bitmaps_batch(self._h, infos))
+        self._mip_boxes = [tuple(int(v) for v in i.tileBBox) for i in infos]       # alpha_mask_payloads_device hands them on with the bits
         return infos
 
     def alpha_bitmaps_device(self) -> list:

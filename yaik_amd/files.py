@@ -73,6 +73,10 @@ ENC_SIGNATURES = {
     "YAIK_EncoderLastError": (C.c_char_p, [vp]),
     "YAIK_LastEncodeStageMs": (None, [vp, vp]),
 }
+# yaik_encode_alpha6.h: the same library, C linkage
+ENC6_SIGNATURES = {
+    "YAIK_EncodeImagesFromDeviceAlpha6": (C.c_bool, [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+}
 ERROR_NAMES = ["YAIK_NO_ERROR", "YAIK_INVALID_LIBRARYCTX", "YAIK_MALLOC_FAIL", "YAIK_INVALID_CONTEXT_COUNT", "YAIK_INIT_FAIL",
                "YAIK_RELEASE_EMPTY_LIBRARY", "YAIK_INVALID_STREAM", "YAIK_INVALID_HEADER", "YAIK_NO_EMPTYDECODE_SLOT", "YAIK_DECIMG_INVALIDCTX",
                "YAIK_DECIMG_DIFFSTREAM", "YAIK_DECIMG_BUFFERNOTSET", "YAIK_INVALID_CONTEXT_MEMALLOCATOR", "YAIK_INVALID_DECOMPRESSION",
@@ -109,7 +113,7 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
-        for name, (res, args) in ENC_SIGNATURES.items():
+        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _host = L
@@ -260,12 +264,23 @@ def encoder(dev: int = 0):
     return e
 
 
-def encode_files_device(frames, emit_alpha: bool = False, level: int = 0, threads: int = 16) -> list:
+def alpha6_decodable(has_chunk, tile_bbox, bits) -> bool:
+    """The alpha6Bit fallback rule of ConvertHotPath and YAIK_EncodeImagesFromDeviceAlpha6 (yaik_amd/host/alpha6_rule.h) on numpy: True when the
+    frame's 'MIPM' chunk exists, has bits, and every bit of its tile box (x, y, w, h), LSB first, is set.  Bits behind w * h do not count."""
+    bits = np.asarray(bits, dtype=np.uint8).ravel()
+    w, h = int(tile_bbox[2]), int(tile_bbox[3])
+    if not has_chunk or bits.size == 0 or w <= 0 or h <= 0 or bits.size * 8 < w * h:
+        return False
+    return bool(np.unpackbits(bits, bitorder="little")[:w * h].all())
+
+
+def encode_files_device(frames, emit_alpha: bool = False, level: int = 0, threads: int = 16, alpha_6bit: bool = False) -> list:
     """N (1..1024) frames of one shape as a batch (YAIK_EncodeImagesFromDevice): `frames` is a torch.uint8 CUDA tensor [N, H, W, C], C = 3 (RGB)
     or 4 (RGBA); stride(1) is the row pitch and stride(0) the frame pitch, the last two dims are dense.  A numpy array is uploaded through
     torch.  Returns N `bytes`, each a whole .yaik stream.  level 0: byte for byte the file ConvertHotPath writes for the frame alone (ZStd level
     18, 'ALPM' swept over levels 5..21); level 1..22: every stream at that ZStd level.  emit_alpha writes the 'ALPM' chunk of RGBA frames (8-bit
-    or 1-bit values).  Raises YaikEncodeError (.index) when the library refuses."""
+    or 1-bit values); alpha_6bit (with emit_alpha) is ConvertHotPath's alpha6Bit: analog alpha of a frame that satisfies alpha6_decodable takes the
+    6-bit mask mode (YAIK_EncodeImagesFromDeviceAlpha6).  Raises YaikEncodeError (.index) when the library refuses."""
     global _last_encoder
     import torch
 
@@ -281,8 +296,12 @@ def encode_files_device(frames, emit_alpha: bool = False, level: int = 0, thread
     _last_encoder = e
     failed = C.c_int32(-1)
     torch.cuda.current_stream(frames.device).synchronize()                 # the library reads on its handle's own stream
-    ok = L.YAIK_EncodeImagesFromDevice(e, frames.data_ptr(), lay.row_bytes, lay.frame_bytes, lay.channels, lay.w, lay.rows, lay.frames,
-                                       int(bool(emit_alpha)), int(level), int(threads), C.byref(failed))
+    if alpha_6bit:
+        ok = L.YAIK_EncodeImagesFromDeviceAlpha6(e, frames.data_ptr(), lay.row_bytes, lay.frame_bytes, lay.channels, lay.w, lay.rows, lay.frames,
+                                                 int(bool(emit_alpha)), 1, int(level), int(threads), C.byref(failed))
+    else:
+        ok = L.YAIK_EncodeImagesFromDevice(e, frames.data_ptr(), lay.row_bytes, lay.frame_bytes, lay.channels, lay.w, lay.rows, lay.frames,
+                                           int(bool(emit_alpha)), int(level), int(threads), C.byref(failed))
     if not ok:
         raise YaikEncodeError((L.YAIK_EncoderLastError(e) or b"?").decode(), failed.value)
     out = []
@@ -294,9 +313,9 @@ def encode_files_device(frames, emit_alpha: bool = False, level: int = 0, thread
     return out
 
 
-def encode_file_device(frame, emit_alpha: bool = False, level: int = 0, threads: int = 16) -> bytes:
+def encode_file_device(frame, emit_alpha: bool = False, level: int = 0, threads: int = 16, alpha_6bit: bool = False) -> bytes:
     """One frame [H, W, C]: a batch of one."""
-    return encode_files_device(frame[None], emit_alpha, level, threads)[0]
+    return encode_files_device(frame[None], emit_alpha, level, threads, alpha_6bit)[0]
 
 
 def last_encode_info() -> dict:

@@ -10,6 +10,7 @@
 #include <mutex>
 #include <thread>
 #include "../../include/yaik_hip.h"
+#include "alpha6_rule.h"
 #include "chunks.h"
 #include "yaik_format.h"
 #include "palette.h"
@@ -134,11 +135,8 @@ void EncoderContext::ProcessAlpha(bool force8Bit) {
 
 // the alpha6Bit fallback rule of the ConvertHotPath* family (ours, not the reference's): a 'MIPM' chunk with every tile bit set
 bool EncoderContext::alpha6BitDecodable() const {
-    if (!alpha6Bit || !mipHasChunk || mipBitmap.empty()) return false;
-    const size_t nBits = (size_t)mipTiles[2] * mipTiles[3];
-    for (size_t i = 0; i < nBits; i++)
-        if (!((mipBitmap[i >> 3] >> (i & 7)) & 1)) return false;
-    return nBits > 0;
+    const int32_t box[4] = { mipTiles[0], mipTiles[1], mipTiles[2], mipTiles[3] };
+    return alpha6Bit && yaikalpha6::decodable(mipHasChunk, box, mipBitmap.data(), mipBitmap.size());
 }
 
 bool EncoderContext::ensureEncoded(int rejectFactor, bool mode3, bool wantDst) {

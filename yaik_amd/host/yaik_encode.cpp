@@ -1,10 +1,11 @@
-// YAIK_EncodeImagesFromDevice: the device's batch calls, one gather, one download, then the entropy stage of encode_frame.cpp.
-#include "yaik_encode.h"
+// YAIK_EncodeImagesFromDevice[Alpha6]: the device's batch calls, one gather, one download, then the entropy stage of encode_frame.cpp.
+#include "yaik_encode_alpha6.h"
 #include <chrono>
 #include <cstdlib>
 #include <string>
 #include <vector>
 #include "../../include/yaik_hip.h"
+#include "alpha6_rule.h"
 #include "encode_frame.h"
 #include "zstd_dl.h"
 
@@ -20,6 +21,8 @@ struct YAIK_Encoder {
     std::vector<yk_frame_streams> table; std::vector<yk_mip_info> mip; std::vector<yk_alpha_info> alpha;
     std::vector<const void*> src; std::vector<size_t> len, off;
     std::vector<yaikenc::FramePieces> pieces;
+    std::vector<u8> bits, force8;                       // alpha6Bit: every frame's 'MIPM' slot on the host, and the force8Bit flags the rule gives
+    std::vector<const uint8_t*> bitAt;                  // ... and where the library keeps frame f's bits in HBM (NULL: none)
 };
 
 namespace {
@@ -73,8 +76,11 @@ bool YAIK_EncodedStream(YAIK_ENC e, int frame, const uint8_t** data, uint32_t* l
     return true;
 }
 
-bool YAIK_EncodeImagesFromDevice(YAIK_ENC e, const uint8_t* devPixels, size_t rowBytes, size_t frameBytes, int channels, int width, int height, int n,
-                                 int emitAlpha, int zstdLevel, int threads, int32_t* failedIndex) {
+}  // extern "C"
+
+// the one body of YAIK_EncodeImagesFromDevice (alpha6Bit = 0) and YAIK_EncodeImagesFromDeviceAlpha6
+static bool encodeImages(YAIK_ENC e, const uint8_t* devPixels, size_t rowBytes, size_t frameBytes, int channels, int width, int height, int n,
+                         int emitAlpha, int alpha6Bit, int zstdLevel, int threads, int32_t* failedIndex) {
     if (failedIndex) *failedIndex = -1;
     if (!e) return false;
     e->valid = false; e->err.clear();
@@ -86,6 +92,7 @@ bool YAIK_EncodeImagesFromDevice(YAIK_ENC e, const uint8_t* devPixels, size_t ro
     if (rowBytes < (size_t)width * channels) return refuse(e, "rowBytes is shorter than a row");
     if (n > 1 && frameBytes < rowBytes * (size_t)height) return refuse(e, "frameBytes is shorter than a frame");
     if (emitAlpha != 0 && emitAlpha != 1) return refuse(e, "emitAlpha must be 0 or 1");
+    if (alpha6Bit != 0 && alpha6Bit != 1) return refuse(e, "alpha6Bit must be 0 or 1");
     if (zstdLevel < 0 || zstdLevel > 22) return refuse(e, "zstdLevel must be 0 (as ConvertHotPath) or 1..22");
     if (threads < 1 || threads > 16) return refuse(e, "threads must be 1..16");
     if (!yaikzstd::available()) return refuse(e, yaikzstd::lastError());
@@ -104,7 +111,30 @@ bool YAIK_EncodeImagesFromDevice(YAIK_ENC e, const uint8_t* devPixels, size_t ro
     if (yk_palette_compress_batch(c) != YK_OK) return deviceFail(e, "yk_palette_compress_batch");
     e->mip.assign((size_t)n, yk_mip_info{}); e->alpha.assign((size_t)n, yk_alpha_info{ -1, { 0, 0, 0, 0 }, 0 });
     if (rgba && yk_alpha_bitmaps_batch(c, e->mip.data()) != YK_OK) return deviceFail(e, "yk_alpha_bitmaps_batch");
-    if (wantAlpha && yk_alpha_values_batch(c, 1, e->alpha.data()) != YK_OK) return deviceFail(e, "yk_alpha_values_batch");
+    if (wantAlpha && !alpha6Bit && yk_alpha_values_batch(c, 1, e->alpha.data()) != YK_OK) return deviceFail(e, "yk_alpha_values_batch");
+    if (wantAlpha && alpha6Bit) {
+        // alpha6BitDecodable's rule per frame, on the bits of every frame in one download: the slots lie in one buffer of the handle
+        // (yk_alpha_bitmaps_batch), so the span from the lowest slot to the end of the highest is fetched whole and frame f's bits are read
+        // at the address the library hands out for it -- no layout is assumed beyond "one buffer"
+        e->bitAt.assign((size_t)n, nullptr);
+        const uint8_t* lo = nullptr; const uint8_t* hi = nullptr;
+        for (int f = 0; f < n; f++) {
+            const uint8_t* d = nullptr; size_t nb = 0;
+            if (yk_alpha_bitmap_device(c, f, &d, &nb) != YK_OK) return deviceFail(e, "yk_alpha_bitmap_device");
+            if (!d || nb != e->mip[(size_t)f].nBytes) continue;
+            e->bitAt[(size_t)f] = d;
+            if (!lo || d < lo) lo = d;
+            if (!hi || d + nb > hi) hi = d + nb;
+        }
+        e->bits.resize(lo ? (size_t)(hi - lo) : 0);
+        if (lo && yk_device_download(c, e->bits.data(), lo, e->bits.size()) != YK_OK) return deviceFail(e, "yk_device_download");
+        e->force8.assign((size_t)n, 1);
+        for (int f = 0; f < n; f++) {
+            const yk_mip_info& m = e->mip[(size_t)f];
+            if (e->bitAt[(size_t)f] && yaikalpha6::decodable(m.hasChunk != 0, m.tileBBox, e->bits.data() + (e->bitAt[(size_t)f] - lo), m.nBytes)) e->force8[(size_t)f] = 0;
+        }
+        if (yk_alpha_values_mask_batch(c, e->force8.data(), e->alpha.data()) != YK_OK) return deviceFail(e, "yk_alpha_values_mask_batch");
+    }
     // ---- the segment list: every frame's pieces in file order
     const size_t nSeg = (size_t)n * SEGS_PER_FRAME;
     e->src.assign(nSeg, nullptr); e->len.assign(nSeg, 0); e->off.assign(nSeg, 0);
@@ -166,6 +196,18 @@ bool YAIK_EncodeImagesFromDevice(YAIK_ENC e, const uint8_t* devPixels, size_t ro
     for (const auto& s : e->streams) if (s.size() > 0xFFFFFFFFu) return refuse(e, "a stream of 4 GB or more");
     e->valid = true;
     return true;
+}
+
+extern "C" {
+
+bool YAIK_EncodeImagesFromDevice(YAIK_ENC e, const uint8_t* devPixels, size_t rowBytes, size_t frameBytes, int channels, int width, int height, int n,
+                                 int emitAlpha, int zstdLevel, int threads, int32_t* failedIndex) {
+    return encodeImages(e, devPixels, rowBytes, frameBytes, channels, width, height, n, emitAlpha, 0, zstdLevel, threads, failedIndex);
+}
+
+bool YAIK_EncodeImagesFromDeviceAlpha6(YAIK_ENC e, const uint8_t* devPixels, size_t rowBytes, size_t frameBytes, int channels, int width, int height,
+                                       int n, int emitAlpha, int alpha6Bit, int zstdLevel, int threads, int32_t* failedIndex) {
+    return encodeImages(e, devPixels, rowBytes, frameBytes, channels, width, height, n, emitAlpha, alpha6Bit, zstdLevel, threads, failedIndex);
 }
 
 }  // extern "C"
