@@ -34,7 +34,7 @@ assert L.yk_debug_path_stats(st.ctypes.data, 1) == 0
 n = float(st[75])
 names = ["16x16", "16x8", "8x16", "8x8", "8x4", "4x8", "4x4"]
 print(f"{cls}: strips {int(n)}, all-dead strips {st[76] / n:.3f}, dead lanes per strip {st[77] / n:.1f}")
-print("pass    entered compact  exit1   exit2   exit4x4 fullA   walkP   accept  cells/entered  compactCells restCells/walkP")
+print("pass    entered compact  exit1   exit2   exitRow1 fullA   walkP   accept  cells/entered  compactCells restCells/walkP")
 for p in range(7):
     r = st[p * 10:p * 10 + 10].astype(float)
     e = max(r[0], 1.0)

@@ -56,7 +56,13 @@ __device__ __forceinline__ y2u2 y2_u2(uint32_t w) { return __builtin_bit_cast(y2
 __device__ __forceinline__ y2s2 y2_s2(y2u2 v) { return __builtin_bit_cast(y2s2, v); }
 __device__ __forceinline__ y2u2 y2_splat(int v) { const unsigned short t = (unsigned short)v; return (y2u2){ t, t }; }
 __device__ __forceinline__ y2s2 y2_splats(int v) { const short t = (short)v; return (y2s2){ t, t }; }
-#define YK2_LATN 85                                                      // 17 x 5 lattice points (every 4th pixel incl. the halo) per strip
+// Pixels in stream layout: the operands of the packed subtract, 256 * (cur - 128) per 16-bit half, made ONCE per pixel from the packed
+// 0x00BBGGRR (the bytes are the same in all seven passes).  rg = channel 0 | channel 1 of a pixel (stream 3 as it is, streams 0 / 1 one
+// half of it); bb = channel 2 of the pixels at columns (x, x + 1), x even (stream 4 as it is: it walks two pixels per operation;
+// stream 2 one half of it).  The broadcasts of one half are operand selects (op_sel) of the packed subtract.
+__device__ __forceinline__ y2s2 y2_rg(uint32_t p) { return y2_s2(y2_u2(__builtin_amdgcn_perm(0u, p, 0x010C000Cu) ^ 0x80008000u)); }
+__device__ __forceinline__ y2s2 y2_bb(uint32_t pEven, uint32_t pOdd) { return y2_s2(y2_u2(__builtin_amdgcn_perm(pOdd, pEven, 0x060C020Cu) ^ 0x80008000u)); }
+#define YK2_LATN 85                                                     // 17 x 5 lattice points (every 4th pixel incl. the halo) per strip
 // -DYK2_STATS (tools/path_stats.py only, never shipped): how often every path of the kernel is taken, summed over the launch
 #ifdef YK2_STATS
 __device__ unsigned long long g_y2_stats[128];
@@ -97,7 +103,7 @@ template <int NX, int NY> __device__ __forceinline__ unsigned long long y2_sprea
 
 template <int SX, int SY, bool SMOOTH = false>
 __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int lat, const int cx, const int cy,
-                                             const uint32_t (&pwb)[16], unsigned long long& cov, const unsigned long long deadLanes, const bool stripInside,
+                                             const y2s2 (&rg)[16], const y2s2 (&bb)[8], unsigned long long& cov, const unsigned long long deadLanes, const bool stripInside,
                                              const int gxCell, const int gyCell, const int w, const int h, const int rf,
                                              uint32_t* s_bm, const int bxCell, const int byCell, const uint32_t* s_pix, uint8_t* s_list, uint32_t* s_tf, const int lane) {
     constexpr int TX = 1 << SX, TY = 1 << SY, NX = TX / 4, NY = TY / 4;
@@ -142,7 +148,8 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
         const y2u2 wyr = y2_splat(16 - ((dcy2 * 4 + r) << (4 - SY)));       // weight of row r of the cell
         const y2u2 lxc = y2_splat(16 - ((dcx2 * 4) << (4 - SX)));           // weight of the cell's first pixel column
         const uint4 pr = *reinterpret_cast<const uint4*>(&s_pix[(cy2 * 4 + r) * LS + q2 * 16 + cx2 * 4]);
-        const uint32_t px[4] = { pr.x ^ 0x00808080u, pr.y ^ 0x00808080u, pr.z ^ 0x00808080u, pr.w ^ 0x00808080u };   // bias of the packed arithmetic
+        // the row's pixels in stream layout (y2_rg / y2_bb), built once for both stages
+        const y2s2 rgc[4] = { y2_rg(pr.x), y2_rg(pr.y), y2_rg(pr.z), y2_rg(pr.w) }, bbc[2] = { y2_bb(pr.x, pr.y), y2_bb(pr.z, pr.w) };
         y2s2 mnc[5], mxc[5];
         auto rowC = [&](const unsigned mask) {                               // the row's four pixels for the streams in `mask`
             y2u2 Sc[5], stc[5];
@@ -158,17 +165,22 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const uint32_t p = px[i];
-                const y2s2 c01 = y2_s2(y2_u2(__builtin_amdgcn_perm(0u, p, 0x010C000Cu))), c22 = y2_s2(y2_u2(__builtin_amdgcn_perm(0u, p, 0x020C020Cu)));
-                const y2s2 cc[4] = { __builtin_shufflevector(c01, c01, 0, 0), __builtin_shufflevector(c01, c01, 1, 1), c22, c01 };
+                const y2s2 c01 = rgc[i], cb = bbc[i >> 1];
+                const y2s2 cc[4] = { __builtin_shufflevector(c01, c01, 0, 0), __builtin_shufflevector(c01, c01, 1, 1),
+                                     (i & 1) ? __builtin_shufflevector(cb, cb, 1, 1) : __builtin_shufflevector(cb, cb, 0, 0), c01 };
 #pragma unroll
-                for (int t = 0; t < 5; t++) {
+                for (int t = 0; t < 4; t++) {
                     if (!((mask >> t) & 1u)) continue;
-                    const y2s2 D = __builtin_elementwise_sub_sat(y2_s2(Sc[t]), cc[t == 4 ? 2 : t]);
+                    const y2s2 D = __builtin_elementwise_sub_sat(y2_s2(Sc[t]), cc[t]);
                     if (i == 0) { mnc[t] = D; mxc[t] = D; }
                     else { mnc[t] = __builtin_elementwise_min(mnc[t], D); mxc[t] = __builtin_elementwise_max(mxc[t], D); }
                     if (i < 3) Sc[t] = Sc[t] - stc[t];
                 }
+            }
+            if (mask & 0x10u) {                                              // stream 4: columns (0, 1) and (2, 3), two pixels per operation
+                const y2s2 Da = __builtin_elementwise_sub_sat(y2_s2(Sc[4] - stc[4] * (y2u2){ 0, 1 }), bbc[0]);
+                const y2s2 Db = __builtin_elementwise_sub_sat(y2_s2(Sc[4] - stc[4] * (y2u2){ 2, 3 }), bbc[1]);
+                mnc[4] = __builtin_elementwise_min(Da, Db); mxc[4] = __builtin_elementwise_max(Da, Db);
             }
         };
         // the lane's failing variants as bits 31, 30 (raw / Round6 corners without the rounding term), 15, 14 (with it), 29, 13 (Round6P corners)
@@ -224,43 +236,59 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
     const int lo = lat - dcy * 17 - dcx;                                 // lattice index of the tile origin
     const y2u2 wy2 = y2_splat(16 - ((dcy * 4) << (4 - SY)));             // weight of the cell's first pixel row
     const y2u2 lx2 = y2_splat(16 - ((dcx * 4) << (4 - SX)));             // weight of the cell's first pixel column
-    y2u2 S[5], st[5], dS0[5], dS3[5], dst[5];
+    // Stream 4 carries the same corner value in both halves, so it walks two pixels per operation instead: Sa = S' at columns (0 | 1) of the
+    // cell, Sb = at columns (2 | 3), no step along x; S'(x0+k, r) - S'(x0+k, r+1) = dS0 - k dst gives their row steps rsA, rsB.
+    y2u2 S[4], st[4], dS0[4], dS3[4], dst[4], Sa, Sb, rsA, rsB;
     auto setup = [&](const int t) {
         const uint32_t* lt = s_lat + t * YK2_LATN + lo;
         const y2u2 TL = y2_u2(lt[0]), TR = y2_u2(lt[NX]), BL = y2_u2(lt[NY * 17]), BR = y2_u2(lt[NY * 17 + NX]);
         // L(r) = 16 BL + (TL-BL) wy, R(r) = 16 BR + (TR-BR) wy, dL = L - R, S'(x0) = 16 R + dL lx0, step = dL * 16/TX, wy(r) = wy0 - r * 16/TY
         const y2u2 e16 = (BL - BR) << 4, g = TR - BR, f = TL - BL - g;
         const y2u2 c2 = (g << 4) + f * lx2;
-        S[t] = ((BR << 8) + e16 * lx2 + c2 * wy2) ^ y2_splat(0x8000);
-        dS0[t] = c2 << (4 - SY);                                         // S'(x0, r) - S'(x0, r+1)
-        st[t] = (e16 + f * wy2) << (4 - SX);                             // S'(x, r) - S'(x+1, r)
-        dst[t] = f << (8 - SX - SY);                                     // step(r) - step(r+1)
-        dS3[t] = dS0[t] - dst[t] * (unsigned short)3;                    // S'(x0+3, r) - S'(x0+3, r+1)
+        const y2u2 s0 = ((BR << 8) + e16 * lx2 + c2 * wy2) ^ y2_splat(0x8000);
+        const y2u2 d0 = c2 << (4 - SY);                                  // S'(x0, r) - S'(x0, r+1)
+        const y2u2 sx = (e16 + f * wy2) << (4 - SX);                     // S'(x, r) - S'(x+1, r)
+        const y2u2 dx = f << (8 - SX - SY);                              // step(r) - step(r+1)
+        if (t < 4) {
+            S[t] = s0; dS0[t] = d0; st[t] = sx; dst[t] = dx;
+            dS3[t] = d0 - dx * (unsigned short)3;                        // S'(x0+3, r) - S'(x0+3, r+1)
+        } else {
+            const y2u2 k01 = { 0, 1 }, k23 = { 2, 3 };
+            Sa = s0 - sx * k01; Sb = s0 - sx * k23;
+            rsA = d0 - dx * k01; rsB = d0 - dx * k23;
+        }
     };
     y2s2 mn[5], mx[5];
     // one row of the cell for the streams in `mask`; `first`: these streams' running extremes start with this row's first pixel
     auto pixelRow = [&](const int r, const unsigned mask, const bool first) {
+        if (mask & 0x0Fu) {
 #pragma unroll
-        for (int ii = 0; ii < 4; ii++) {
-            const int i = (r & 1) ? 3 - ii : ii;                         // serpentine: odd rows right to left
-            const uint32_t p = pwb[r * 4 + i];
-            // 256 * (cur - 128) of channel c in both halves; stream 3: channel 0 | channel 1
-            // two byte permutations per pixel; the broadcasts of one half are operand selects (op_sel) of the packed subtract
-            const y2s2 c01 = y2_s2(y2_u2(__builtin_amdgcn_perm(0u, p, 0x010C000Cu))), c22 = y2_s2(y2_u2(__builtin_amdgcn_perm(0u, p, 0x020C020Cu)));
-            const y2s2 cc[4] = { __builtin_shufflevector(c01, c01, 0, 0), __builtin_shufflevector(c01, c01, 1, 1), c22, c01 };
+            for (int ii = 0; ii < 4; ii++) {
+                const int i = (r & 1) ? 3 - ii : ii;                     // serpentine: odd rows right to left
+                const y2s2 c01 = rg[r * 4 + i], cb = bb[r * 2 + (i >> 1)];
+                const y2s2 cc[4] = { __builtin_shufflevector(c01, c01, 0, 0), __builtin_shufflevector(c01, c01, 1, 1),
+                                     (i & 1) ? __builtin_shufflevector(cb, cb, 1, 1) : __builtin_shufflevector(cb, cb, 0, 0), c01 };
 #pragma unroll
-            for (int t = 0; t < 5; t++) {
-                if (!((mask >> t) & 1u)) continue;
-                const y2s2 D = __builtin_elementwise_sub_sat(y2_s2(S[t]), cc[t == 4 ? 2 : t]);
-                if (first && ii == 0) { mn[t] = D; mx[t] = D; }
-                else { mn[t] = __builtin_elementwise_min(mn[t], D); mx[t] = __builtin_elementwise_max(mx[t], D); }
-                if (ii < 3) S[t] = (r & 1) ? S[t] + st[t] : S[t] - st[t];
+                for (int t = 0; t < 4; t++) {
+                    if (!((mask >> t) & 1u)) continue;
+                    const y2s2 D = __builtin_elementwise_sub_sat(y2_s2(S[t]), cc[t]);
+                    if (first && ii == 0) { mn[t] = D; mx[t] = D; }
+                    else { mn[t] = __builtin_elementwise_min(mn[t], D); mx[t] = __builtin_elementwise_max(mx[t], D); }
+                    if (ii < 3) S[t] = (r & 1) ? S[t] + st[t] : S[t] - st[t];
+                }
             }
+        }
+        if (mask & 0x10u) {
+            const y2s2 Da = __builtin_elementwise_sub_sat(y2_s2(Sa), bb[r * 2]), Db = __builtin_elementwise_sub_sat(y2_s2(Sb), bb[r * 2 + 1]);
+            const y2s2 lo4 = __builtin_elementwise_min(Da, Db), hi4 = __builtin_elementwise_max(Da, Db);
+            if (first) { mn[4] = lo4; mx[4] = hi4; }
+            else { mn[4] = __builtin_elementwise_min(mn[4], lo4); mx[4] = __builtin_elementwise_max(mx[4], hi4); }
         }
     };
     auto nextRow = [&](const int r, const unsigned mask) {               // from the end of row r to the start of row r + 1, streams in `mask`
 #pragma unroll
-        for (int t = 0; t < 5; t++) if ((mask >> t) & 1u) { S[t] -= (r & 1) ? dS0[t] : dS3[t]; st[t] -= dst[t]; }
+        for (int t = 0; t < 4; t++) if ((mask >> t) & 1u) { S[t] -= (r & 1) ? dS0[t] : dS3[t]; st[t] -= dst[t]; }
+        if (mask & 0x10u) { Sa -= rsA; Sb -= rsB; }
     };
     // Lanes failing a variant -> tiles (origin bits) with a failing lane.  The six variants of :3929-3991 are range tests on the running
     // extremes: A = the (raw | Round6) streams merged over their channels, halves x / y = raw / Round6 corners; P = the Round6P streams
@@ -305,14 +333,16 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
         accept = viable & ~failA4(mnAll(), mxAll());
 #ifdef YK2_STATS
         {   // which variants accept the tiles of smooth strips (never shipped)
-            y2u2 S_[5], st_[5], a_[5], b_[5], c_[5]; y2s2 mn_[5], mx_[5];
-            for (int t = 0; t < 5; t++) { S_[t] = S[t]; st_[t] = st[t]; a_[t] = dS0[t]; b_[t] = dS3[t]; c_[t] = dst[t]; mn_[t] = mn[t]; mx_[t] = mx[t]; }
+            y2u2 S_[4], st_[4], a_[4], b_[4], c_[4]; y2s2 mn_[5], mx_[5];
+            for (int t = 0; t < 4; t++) { S_[t] = S[t]; st_[t] = st[t]; a_[t] = dS0[t]; b_[t] = dS3[t]; c_[t] = dst[t]; }
+            for (int t = 0; t < 5; t++) { mn_[t] = mn[t]; mx_[t] = mx[t]; }
             setup(3); setup(4);
             pixelRow(0, kP, true); nextRow(0, kP); pixelRow(1, kP, false); nextRow(1, kP); pixelRow(2, kP, false); nextRow(2, kP); pixelRow(3, kP, false);
             const unsigned long long accP = viable & ~failP2(__builtin_elementwise_min(mn[3], mn[4]), __builtin_elementwise_max(mx[3], mx[4]));
             YK2_STAT(97, __popcll(accept)); YK2_STAT(98, __popcll(accP)); YK2_STAT(99, __popcll(accept | accP)); YK2_STAT(96 + 0 * kPassId, 0);
             YK2_STAT(107, __popcll(viable));
-            for (int t = 0; t < 5; t++) { S[t] = S_[t]; st[t] = st_[t]; dS0[t] = a_[t]; dS3[t] = b_[t]; dst[t] = c_[t]; mn[t] = mn_[t]; mx[t] = mx_[t]; }
+            for (int t = 0; t < 4; t++) { S[t] = S_[t]; st[t] = st_[t]; dS0[t] = a_[t]; dS3[t] = b_[t]; dst[t] = c_[t]; }   // stream 4 is set up again before its walk
+            for (int t = 0; t < 5; t++) { mn[t] = mn_[t]; mx[t] = mx_[t]; }
         }
 #endif
         const unsigned long long rest = viable & ~accept;
@@ -353,7 +383,8 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
         if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 3, 1); return; }
         nextRow(0, 0x1Fu);
         pixelRow(1, 0x1Fu, false);
-        if (NX * NY == 1) {                                              // 4x4 tiles: one lane per tile, a second look after half of the tile
+        if (NX * NY <= 2) {                                              // one- and two-cell tiles: a second look after half of the rows (nearly every wave of
+                                                                         // 8x4 / 4x8 tiles on mild noise that outlives row 0 leaves here: DESIGN 3.2 round 5)
             viable &= ~(failA4(mnAll(), mxAll()) & failP2(__builtin_elementwise_min(mn[3], mn[4]), __builtin_elementwise_max(mx[3], mx[4])));
             if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 9, 1); return; }
         }
@@ -777,20 +808,29 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
             latticePoint(lane);
             if (lane < YK2_LATN - 64) latticePoint(lane + 64);
             __syncthreads();
+            // the lane's pixels in stream layout for the seven passes (the bias of the packed arithmetic, bytes - 128, is part of it);
+            // the packed words are not live meanwhile
+            y2s2 rg[16], bb[8];
 #pragma unroll
-            for (int k = 0; k < 16; k++) pw[k] ^= 0x00808080u;                // bias of the packed passes (bytes - 128)
-            if (deadLanes == 0ULL) y2_grad_pass<4, 4, true>(s_lat, lat, cx, cy, pw, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-            else y2_grad_pass<4, 4>(s_lat, lat, cx, cy, pw, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+            for (int k = 0; k < 16; k++) rg[k] = y2_rg(pw[k]);
+#pragma unroll
+            for (int k = 0; k < 8; k++) bb[k] = y2_bb(pw[2 * k], pw[2 * k + 1]);
+            if (deadLanes == 0ULL) y2_grad_pass<4, 4, true>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+            else y2_grad_pass<4, 4>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
             if (~(cov | deadLanes) != 0ULL) {
-                y2_grad_pass<4, 3>(s_lat, lat, cx, cy, pw, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<3, 4>(s_lat, lat, cx, cy, pw, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<3, 3>(s_lat, lat, cx, cy, pw, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<3, 2>(s_lat, lat, cx, cy, pw, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<2, 3>(s_lat, lat, cx, cy, pw, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<2, 2>(s_lat, lat, cx, cy, pw, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<4, 3>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<3, 4>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<3, 3>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<3, 2>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<2, 3>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<2, 2>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
             }
+            // the packed pixels come back from the staged strip (intact until the fence below)
 #pragma unroll
-            for (int k = 0; k < 16; k++) pw[k] ^= 0x00808080u;
+            for (int r = 0; r < 4; r++) {
+                const uint4 t = *reinterpret_cast<const uint4*>(&s_pix[lcell + r * LS]);
+                pw[r * 4 + 0] = t.x; pw[r * 4 + 1] = t.y; pw[r * 4 + 2] = t.z; pw[r * 4 + 3] = t.w;
+            }
         }
     }
     const int mtIdx = ((BY * 64 + wave * 16) >> 4) * P.mtW + ((BX * 64 + q * 16) >> 4);
