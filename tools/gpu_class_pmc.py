@@ -1,6 +1,8 @@
 """One content class of YAIK-synth v1 as a whole 8192x8192 RGB frame, encoded 3 times: run under
 `rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES` to get the instruction budget per class.
-usage: gpu_class_pmc.py ramp|mild|noise|mild16|mild32|mild64"""
+usage: gpu_class_pmc.py ramp|mild|noise|mild16|mild32|mild64|border|frame
+border: 64x64 blocks in a checkerboard of ramp and mild noise, so that every ramp block has mild noise to its right and below (what a ramp
+block of the bench frame has)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -20,6 +22,8 @@ if cls.startswith("mild"):
     img = (img + torch.randint(0, amp, (3, W, W), device=dev, generator=g)) % 256
 elif cls == "noise":
     img = torch.randint(0, 256, (3, W, W), device=dev, generator=g)
+elif cls == "border":
+    img = torch.where((((x >> 6) + (y >> 6)) & 1).bool()[None], (img + torch.randint(0, 8, (3, W, W), device=dev, generator=g)) % 256, img)
 if cls == "frame":
     from yaik_amd.synth import synth_planes_torch
     img = synth_planes_torch(W, W, 4, device=dev)

@@ -1,5 +1,7 @@
 """How often every path of yk_encode2_kernel is taken on one frame (needs a -DYK2_STATS build: YK_LIB=build/libS.so).
-usage: YK_LIB=build/libS.so python tools/path_stats.py [frame|ramp|mild|noise]"""
+usage: YK_LIB=build/libS.so python tools/path_stats.py [frame|ramp|mild|noise|border]
+The "would fit" rows are what decides the size of a grouped compact sweep: take them from a -DYK2_STATS -DYK2_NO_GROUP build (every pass
+enters on its own there); the "grouped sweeps" rows are what a build with the grouped sweep did."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -20,13 +22,15 @@ else:
     g = torch.Generator(device=dev); g.manual_seed(1)
     if cls == "mild": img = (img + torch.randint(0, 8, (3, W, W), device=dev, generator=g)) % 256
     elif cls == "noise": img = torch.randint(0, 256, (3, W, W), device=dev, generator=g)
+    elif cls == "border":                                # 64x64 blocks in a checkerboard of ramp and mild noise: every ramp block has mild noise to its right and below
+        img = torch.where((((x >> 6) + (y >> 6)) & 1).bool()[None], (img + torch.randint(0, 8, (3, W, W), device=dev, generator=g)) % 256, img)
 enc = HipTileEncoder(0)
 enc.set_image(img.to(torch.int32).contiguous())
 if cls == "frame":
     enc.alpha_reject(); enc.alpha_finish(None)
 L = lib()
 L.yk_debug_path_stats.argtypes = [C.c_void_p, C.c_int]; L.yk_debug_path_stats.restype = C.c_int
-st = np.zeros(128, np.uint64)
+st = np.zeros(192, np.uint64)
 enc.encode(3, False, False); torch.cuda.synchronize()
 assert L.yk_debug_path_stats(st.ctypes.data, 1) == 0
 enc.encode(3, False, False); torch.cuda.synchronize()
@@ -45,3 +49,10 @@ print("smooth 16x16 strips: tiles viable / accepted by raw|Round6 / by Round6P /
 print("valid lanes per strip (0, 1-4, 5-8, 9-16, 17-32, 33-63, 64):", [round(float(st[120 + i]) / n, 3) for i in range(7)])
 print(f"range: strips coded {st[70] / n:.3f}, valid lanes per coded strip {st[74] / max(float(st[70]), 1):.1f}, plane-waves with ambiguous tiles {st[71] / n:.4f} "
       f"(tiles {st[72] / n:.4f} per strip), tie blocks {st[73] / n:.4f} per strip")
+pairs = ["8x8+8x4", "8x4+4x8", "4x8+4x4"]
+print("compact pass whose next pass has cells under the coverage as it stands (per strip):", {pairs[k]: round(float(st[136 + k]) / n, 4) for k in range(3)})
+print("  of these, would fit one sweep (own + speculative next <= 16 cells):", {pairs[k]: round(float(st[130 + k]) / n, 4) for k in range(3)},
+      " runs of three:", {"8x8..4x8": round(float(st[133]) / n, 4), "8x4..4x4": round(float(st[134]) / n, 4)}, " run of four:", round(float(st[135]) / n, 4))
+print("grouped sweeps: formed", {pairs[k]: round(float(st[140 + k]) / n, 4) for k in range(3)}, " sweeps saved (the next pass had a tile left)", {pairs[k]: round(float(st[143 + k]) / n, 4) for k in range(3)},
+      " left after stage 1", {pairs[k]: round(float(st[146 + k]) / n, 4) for k in range(3)}, " next pass's cells per group", {pairs[k]: round(float(st[150 + k]) / max(float(st[140 + k]), 1), 1) for k in range(3)},
+      " groups whose next pass accepted", {pairs[k]: round(float(st[153 + k]) / n, 4) for k in range(3)})

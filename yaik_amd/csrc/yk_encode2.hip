@@ -13,6 +13,8 @@
 //   * a 4x4 tile is one lane, an 8x8 tile four lanes: tile-level reductions are ballots against a lane mask or two shuffles;
 //   * every pass first tests ONE row of every cell; if that already rejects every viable tile of the wave (noise, mild noise)
 //     the other three rows are never evaluated;
+//   * a pass with few viable cells evaluates one (cell, row) per lane instead (the compact path), and from 8x8 on takes the next pass's cells
+//     along in the same sweep when both fit its 16 cell slots;
 //   * range quantiser: index and minDiff of the nearest LUT entry of all six modes come from ONE gather per pixel out of a
 //     per-device table indexed by (rangeDecode, v - BN) — every LUT the reference builds is BN + K[rangeDecode][mode];
 //   * the mode-selection sums are summed in tree order and accepted only when a rigorous rounding margin separates the
@@ -65,11 +67,11 @@ __device__ __forceinline__ y2s2 y2_bb(uint32_t pEven, uint32_t pOdd) { return y2
 #define YK2_LATN 85                                                     // 17 x 5 lattice points (every 4th pixel incl. the halo) per strip
 // -DYK2_STATS (tools/path_stats.py only, never shipped): how often every path of the kernel is taken, summed over the launch
 #ifdef YK2_STATS
-__device__ unsigned long long g_y2_stats[128];
+__device__ unsigned long long g_y2_stats[192];
 #define YK2_STAT(i, n) do { if (lane == 0) atomicAdd(&g_y2_stats[(i)], (unsigned long long)(n)); } while (0)
 extern "C" int yk_debug_path_stats(unsigned long long* out, int clear) {
     hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_y2_stats), sizeof(g_y2_stats));
-    if (e == hipSuccess && clear) { static unsigned long long z[128]; e = hipMemcpyToSymbol(HIP_SYMBOL(g_y2_stats), z, sizeof(z)); }
+    if (e == hipSuccess && clear) { static unsigned long long z[192]; e = hipMemcpyToSymbol(HIP_SYMBOL(g_y2_stats), z, sizeof(z)); }
     return (int)e;
 }
 #else
@@ -101,20 +103,43 @@ template <int NX, int NY> __device__ __forceinline__ unsigned long long y2_sprea
     return m;
 }
 
+// the seven passes in the reference's order: tile = 2^SX x 2^SY pixels
+__device__ __forceinline__ constexpr int y2_pass_sx(int id) { return id < 2 ? 4 : (id < 5 ? 3 : 2); }
+__device__ __forceinline__ constexpr int y2_pass_sy(int id) { return id == 0 || id == 2 ? 4 : (id == 1 || id == 3 || id == 5 ? 3 : 2); }
+// viable tiles of a pass (origin bits): top-left pixel uncovered (:3871-3875), no cell killed by the curvature test, whole tile inside the image
+template <int SX, int SY> __device__ __forceinline__ unsigned long long y2_viable(const unsigned long long cov, const unsigned long long deadLanes, const bool stripInside,
+                                                                                  const int cx, const int cy, const int gxCell, const int gyCell, const int w, const int h) {
+    constexpr int TX = 1 << SX, TY = 1 << SY, NX = TX / 4, NY = TY / 4;
+    unsigned long long viable = y2_origin<NX, NY>() & ~cov & ~y2_fold<NX, NY>(deadLanes);
+    if (!stripInside) {
+        const int tgx = gxCell - (cx & (NX - 1)) * 4, tgy = gyCell - (cy & (NY - 1)) * 4;   // tile origin, stripe-local pixels
+        viable &= __ballot((tgx + TX <= w) && (tgy + TY <= h));
+    }
+    return viable;
+}
+// the bit of the tile whose origin is the lane's cell in the strip's share of the pass's swizzled bitmap (:4026)
+template <int SX, int SY> __device__ __forceinline__ int y2_bitmap_bit(const int bxCell, const int byCell) {
+    const int tbx = bxCell >> SX, tby = byCell >> SY;                    // tile coordinates inside the 64x64 block
+    if (SX == 4 && SY == 4) return 0 + tby * 4 + tbx;
+    if (SX == 4 && SY == 3) return 32 + tby * 4 + tbx;
+    if (SX == 3 && SY == 4) return 64 + tby * 8 + tbx;
+    if (SX == 3 && SY == 3) return 96 + tby * 8 + tbx;
+    if (SX == 3 && SY == 2) return 160 + (tby >> 3) * 64 + (tby & 7) * 8 + tbx;
+    if (SX == 2 && SY == 3) return 288 + (tbx >> 3) * 64 + tby * 8 + (tbx & 7);
+    return 416 + ((tby >> 3) * 2 + (tbx >> 3)) * 64 + (tby & 7) * 8 + (tbx & 7);
+}
+
+// `evaluated`: the tiles of THIS pass (origin bits) that the pass before it has already decided in a grouped compact sweep (below); on return
+// those of the next pass.  It is data, not a flag the caller branches on: a skipped pass finds no viable tile and leaves like any such pass.
 template <int SX, int SY, bool SMOOTH = false>
 __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int lat, const int cx, const int cy,
-                                             const y2s2 (&rg)[16], const y2s2 (&bb)[8], unsigned long long& cov, const unsigned long long deadLanes, const bool stripInside,
+                                             const y2s2 (&rg)[16], const y2s2 (&bb)[8], unsigned long long& cov, unsigned long long& evaluated, const unsigned long long deadLanes, const bool stripInside,
                                              const int gxCell, const int gyCell, const int w, const int h, const int rf,
                                              uint32_t* s_bm, const int bxCell, const int byCell, const uint32_t* s_pix, uint8_t* s_list, uint32_t* s_tf, const int lane) {
     constexpr int TX = 1 << SX, TY = 1 << SY, NX = TX / 4, NY = TY / 4;
-    constexpr unsigned long long ORG = y2_origin<NX, NY>();
     const int dcx = cx & (NX - 1), dcy = cy & (NY - 1);                  // this cell's offset inside its tile, in cells
-    // viable tiles (origin bits): top-left pixel uncovered (:3871-3875), no cell killed by the curvature test, whole tile inside the image
-    unsigned long long viable = ORG & ~cov & ~y2_fold<NX, NY>(deadLanes);
-    if (!stripInside) {
-        const int tgx = gxCell - dcx * 4, tgy = gyCell - dcy * 4;        // tile origin, stripe-local pixels
-        viable &= __ballot((tgx + TX <= w) && (tgy + TY <= h));
-    }
+    unsigned long long viable = y2_viable<SX, SY>(cov, deadLanes, stripInside, cx, cy, gxCell, gyCell, w, h) & ~evaluated;
+    evaluated = 0ULL;
     if (viable == 0ULL) return;
     constexpr int kPassId = (SX == 4 && SY == 4) ? 0 : (SX == 4 && SY == 3) ? 1 : (SX == 3 && SY == 4) ? 2 : (SX == 3 && SY == 3) ? 3 : (SX == 3 && SY == 2) ? 4 : (SX == 2 && SY == 3) ? 5 : 6;
     YK2_STAT(kPassId * 10 + 0, 1); YK2_STAT(kPassId * 10 + 8, __popcll(y2_spread<NX, NY>(viable)));
@@ -132,21 +157,70 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
     const int nCells = __popcll(cells);
     if (nCells <= 16) {
         YK2_STAT(kPassId * 10 + 1, 1); YK2_STAT(kPassId * 10 + 7, nCells);
+        // ---- grouped sweep (8x8, 8x4 and 4x8): on a strip that borders other content the small passes follow each other with 4..8 cells
+        // each.  When the NEXT pass's cells, taken with the coverage as it stands now (a superset of what that pass will find), fit into the
+        // cell slots this pass leaves free, the lanes (j, r) with j >= nCells evaluate them in the same sweep: the shape (cells per tile, lattice
+        // offsets, weight shifts, origin lane) is then the lane's own, and the next pass's failures are the same six bits three places lower in
+        // the tile's word (two passes' tiles may share an origin lane).  The scalar side resolves the two in the reference's order.
+        constexpr bool kHasNext = kPassId >= 3 && kPassId <= 5;
+        constexpr int SXB = kHasNext ? y2_pass_sx(kPassId + 1) : SX, SYB = kHasNext ? y2_pass_sy(kPassId + 1) : SY;
+        constexpr int NXB = (1 << SXB) / 4, NYB = (1 << SYB) / 4;
+        unsigned long long viableB = 0ULL, cellsB = 0ULL;
+        int nB = 0;
+#if !defined(YK2_NO_GROUP) || defined(YK2_STATS)
+        if (kHasNext) {
+            viableB = y2_viable<SXB, SYB>(cov, deadLanes, stripInside, cx, cy, gxCell, gyCell, w, h);
+            cellsB = y2_spread<NXB, NYB>(viableB);
+            nB = __popcll(cellsB);
+#ifdef YK2_STATS
+            {   // would this pass and the next one, two or three fit one sweep (never shipped: counted before the grouped sweep was built)
+                constexpr int k = kPassId - 3;
+                constexpr int SXC = y2_pass_sx(kPassId <= 4 ? kPassId + 2 : 6), SYC = y2_pass_sy(kPassId <= 4 ? kPassId + 2 : 6);
+                int n2 = 0, n3 = 0;
+                if (kPassId <= 4) n2 = __popcll(y2_spread<(1 << SXC) / 4, (1 << SYC) / 4>(y2_viable<SXC, SYC>(cov, deadLanes, stripInside, cx, cy, gxCell, gyCell, w, h)));
+                if (kPassId == 3) n3 = __popcll(y2_viable<2, 2>(cov, deadLanes, stripInside, cx, cy, gxCell, gyCell, w, h));
+                if (nB > 0) {
+                    YK2_STAT(136 + k, 1);
+                    if (nCells + nB <= 16) YK2_STAT(130 + k, 1);
+                    if (kPassId <= 4 && n2 > 0 && nCells + nB + n2 <= 16) YK2_STAT(133 + k, 1);
+                    if (kPassId == 3 && n2 > 0 && n3 > 0 && nCells + nB + n2 + n3 <= 16) YK2_STAT(135, 1);
+                }
+            }
+#endif
+#ifdef YK2_NO_GROUP
+            nB = 0;
+#endif
+            if (nB == 0 || nCells + nB > 16) { viableB = 0ULL; cellsB = 0ULL; nB = 0; }
+        }
+#endif
         const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cells >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cells, 0u));
         const bool mine = __builtin_amdgcn_inverse_ballot_w64(cells);
         if (mine) s_list[rank] = (uint8_t)lane;
+        if (kHasNext && nB != 0) {                                           // wave-uniform: the next pass's cells behind this pass's
+            YK2_STAT(140 + kPassId - 3, 1); YK2_STAT(150 + kPassId - 3, nB);
+            const int rankB = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cellsB >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cellsB, 0u));
+            if (__builtin_amdgcn_inverse_ballot_w64(cellsB)) s_list[nCells + rankB] = (uint8_t)lane;
+        }
         s_tf[lane] = 0u; s_tf[64 + lane] = 0u;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const int j = lane & 15, r = lane >> 4;
-        const bool act = j < nCells;
+        const bool act = j < nCells + nB;
+        const bool isB = kHasNext && j >= nCells;                            // the lane's cell belongs to the next pass (idle lanes: harmless either way)
         const int c = (int)s_list[act ? j : 0];
         const int q2 = c >> 4, cy2 = y2_cell_y(c & 15), cx2 = y2_cell_x(c & 15);
-        const int dcx2 = cx2 & (NX - 1), dcy2 = cy2 & (NY - 1);
         constexpr int kInTile = (NX > 1 ? 1 : 0) | (NY > 1 ? 2 : 0) | (NX > 2 ? 4 : 0) | (NY > 2 ? 8 : 0);   // Morton bits of a cell inside its tile
-        const int orig = c & ~kInTile;                                       // lane of the tile's origin cell
+        constexpr int kInTileB = (NXB > 1 ? 1 : 0) | (NYB > 1 ? 2 : 0) | (NXB > 2 ? 4 : 0) | (NYB > 2 ? 8 : 0);
+        // the lane's shape: constants unless a next pass can ride along
+        const int nxL = isB ? NXB : NX, nyL = isB ? NYB : NY;                // cells per tile
+        const int shx = isB ? 4 - SXB : 4 - SX, shy = isB ? 4 - SYB : 4 - SY; // weight shifts
+        const int dcx2 = cx2 & (nxL - 1), dcy2 = cy2 & (nyL - 1);
+        const int orig = c & ~(isB ? kInTileB : kInTile);                    // lane of the tile's origin cell
+        const int fsh = isB ? 3 : 0;                                         // place of the lane's failure bits in the tile's word
         const int lo2 = cy2 * 17 + q2 * 4 + cx2 - dcy2 * 17 - dcx2;          // lattice index of the tile origin
-        const y2u2 wyr = y2_splat(16 - ((dcy2 * 4 + r) << (4 - SY)));       // weight of row r of the cell
-        const y2u2 lxc = y2_splat(16 - ((dcx2 * 4) << (4 - SX)));           // weight of the cell's first pixel column
+        const int oTR = nxL, oBL = nyL * 17;                                 // lattice offsets of the far corners
+        const y2u2 wyr = y2_splat(16 - ((dcy2 * 4 + r) << shy));            // weight of row r of the cell
+        const y2u2 lxc = y2_splat(16 - ((dcx2 * 4) << shx));                // weight of the cell's first pixel column
+        const y2u2 shx2 = y2_splat(shx);
         const uint4 pr = *reinterpret_cast<const uint4*>(&s_pix[(cy2 * 4 + r) * LS + q2 * 16 + cx2 * 4]);
         // the row's pixels in stream layout (y2_rg / y2_bb), built once for both stages
         const y2s2 rgc[4] = { y2_rg(pr.x), y2_rg(pr.y), y2_rg(pr.z), y2_rg(pr.w) }, bbc[2] = { y2_bb(pr.x, pr.y), y2_bb(pr.z, pr.w) };
@@ -157,11 +231,11 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
             for (int t = 0; t < 5; t++) {
                 if (!((mask >> t) & 1u)) continue;
                 const uint32_t* lt = s_lat + t * YK2_LATN + lo2;
-                const y2u2 TL = y2_u2(lt[0]), TR = y2_u2(lt[NX]), BL = y2_u2(lt[NY * 17]), BR = y2_u2(lt[NY * 17 + NX]);
+                const y2u2 TL = y2_u2(lt[0]), TR = y2_u2(lt[oTR]), BL = y2_u2(lt[oBL]), BR = y2_u2(lt[oBL + oTR]);
                 const y2u2 e16 = (BL - BR) << 4, g = TR - BR, f = TL - BL - g;
                 const y2u2 c2 = (g << 4) + f * lxc;
                 Sc[t] = ((BR << 8) + e16 * lxc + c2 * wyr) ^ y2_splat(0x8000);   // S'(x0, row r), biased
-                stc[t] = (e16 + f * wyr) << (4 - SX);                            // S'(x, r) - S'(x+1, r)
+                stc[t] = (e16 + f * wyr) << shx2;                                // S'(x, r) - S'(x+1, r)
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -199,35 +273,45 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
             m |= (((cR >> 16) | cR) >> 2) & 0x00002000u;
             return m;
         };
+        constexpr uint32_t kAllFailB = kAllFail >> 3;                        // the next pass's six bits
         rowC(0x09u);
-        if (act) atomicOr(&s_tf[orig], failBits(mnc[0], mxc[0], mnc[3], mxc[3]));
+        if (act) atomicOr(&s_tf[orig], failBits(mnc[0], mxc[0], mnc[3], mxc[3]) >> fsh);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const unsigned long long alive = viable & __ballot(s_tf[lane] != kAllFail);
-        if (alive == 0ULL) { YK2_STAT(100 + kPassId, 1); return; }
+        const uint32_t w1 = s_tf[lane];
+        const unsigned long long alive = viable & __ballot((kHasNext ? (w1 & kAllFail) : w1) != kAllFail);
+        unsigned long long aliveB = 0ULL;
+        if (kHasNext && nB != 0) aliveB = viableB & __ballot((w1 & kAllFailB) != kAllFailB);
+        // a group leaves after stage 1 only when BOTH passes have lost all their tiles; a pass without a tile adds nothing to stage 2
+        if ((alive | aliveB) == 0ULL) { YK2_STAT(100 + kPassId, 1); if (nB != 0) { YK2_STAT(146 + kPassId - 3, 1); YK2_STAT(143 + kPassId - 3, 1); } evaluated = viableB; return; }
         rowC(0x16u);
         {
             const y2s2 mnA = __builtin_elementwise_min(__builtin_elementwise_min(mnc[0], mnc[1]), mnc[2]), mxA = __builtin_elementwise_max(__builtin_elementwise_max(mxc[0], mxc[1]), mxc[2]);
             const y2s2 mnP = __builtin_elementwise_min(mnc[3], mnc[4]), mxP = __builtin_elementwise_max(mxc[3], mxc[4]);
-            if (act) atomicOr(&s_tf[64 + orig], failBits(mnA, mxA, mnP, mxP));
+            if (act) atomicOr(&s_tf[64 + orig], failBits(mnA, mxA, mnP, mxP) >> fsh);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const unsigned long long acceptC = alive & __ballot(s_tf[64 + lane] != kAllFail);   // some variant never failed (:3998)
-        if (acceptC != 0ULL) {
-            YK2_STAT(110 + kPassId, 1);
-            cov |= y2_spread<NX, NY>(acceptC);
-            if (__builtin_amdgcn_inverse_ballot_w64(acceptC)) {
-                const int tbx = bxCell >> SX, tby = byCell >> SY;
-                int bit;
-                if (SX == 4 && SY == 4) bit = 0 + tby * 4 + tbx;
-                else if (SX == 4 && SY == 3) bit = 32 + tby * 4 + tbx;
-                else if (SX == 3 && SY == 4) bit = 64 + tby * 8 + tbx;
-                else if (SX == 3 && SY == 3) bit = 96 + tby * 8 + tbx;
-                else if (SX == 3 && SY == 2) bit = 160 + (tby >> 3) * 64 + (tby & 7) * 8 + tbx;
-                else if (SX == 2 && SY == 3) bit = 288 + (tbx >> 3) * 64 + tby * 8 + (tbx & 7);
-                else bit = 416 + ((tby >> 3) * 2 + (tbx >> 3)) * 64 + (tby & 7) * 8 + (tbx & 7);
-                atomicOr(&s_bm[bit >> 5], 1u << (bit & 31));
-            }
+        const uint32_t w2 = s_tf[64 + lane];
+        const unsigned long long acceptC = alive & __ballot((kHasNext ? (w2 & kAllFail) : w2) != kAllFail);   // some variant never failed (:3998)
+        if (acceptC != 0ULL) { YK2_STAT(110 + kPassId, 1); }
+        cov |= y2_spread<NX, NY>(acceptC);
+        unsigned long long acceptB = 0ULL;
+        if (kHasNext && nB != 0) {
+            // the next pass, in the reference's order: only the ORIGIN cell decides whether a tile is still viable (:3871-3875) once this pass's
+            // tiles are painted; a tile whose origin stays free is accepted even where it overlaps one of them
+            const unsigned long long stillB = aliveB & ~cov;
+            if (viableB & ~cov) YK2_STAT(143 + kPassId - 3, 1);              // the next pass would have run a sweep of its own
+            acceptB = stillB & __ballot((w2 & kAllFailB) != kAllFailB);
+            if (acceptB != 0ULL) { YK2_STAT(153 + kPassId - 3, 1); }
+            cov |= y2_spread<NXB, NYB>(acceptB);
         }
+        // the accepted tiles' origin lanes set their bitmap bits; the two passes' sets are disjoint (an accepted tile of this pass covers its origin)
+        if ((acceptC | acceptB) != 0ULL && __builtin_amdgcn_inverse_ballot_w64(acceptC | acceptB)) {
+            int bit = y2_bitmap_bit<SX, SY>(bxCell, byCell);
+            if (kHasNext && __builtin_amdgcn_inverse_ballot_w64(acceptB)) bit = y2_bitmap_bit<SXB, SYB>(bxCell, byCell);
+            atomicOr(&s_bm[bit >> 5], 1u << (bit & 31));
+        }
+        __builtin_amdgcn_wave_barrier();                                     // no instruction: keeps what follows from being duplicated into the divergent branch above
+        evaluated = viableB;                                                 // the next pass is done (nothing without a group)
         return;
     }
 #endif
@@ -416,18 +500,11 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
     if (accept == 0ULL) return;
     YK2_STAT(kPassId * 10 + 6, 1);
     cov |= y2_spread<NX, NY>(accept);                                    // paint coverage (:4029-4037): bit = lane = cell
-    if (__builtin_amdgcn_inverse_ballot_w64(accept)) {                   // the origin cell's lane sets the bitmap bit (:4026)
-        const int tbx = bxCell >> SX, tby = byCell >> SY;                // tile coordinates inside the 64x64 block
-        int bit;
-        if (SX == 4 && SY == 4) bit = 0 + tby * 4 + tbx;
-        else if (SX == 4 && SY == 3) bit = 32 + tby * 4 + tbx;
-        else if (SX == 3 && SY == 4) bit = 64 + tby * 8 + tbx;
-        else if (SX == 3 && SY == 3) bit = 96 + tby * 8 + tbx;
-        else if (SX == 3 && SY == 2) bit = 160 + (tby >> 3) * 64 + (tby & 7) * 8 + tbx;
-        else if (SX == 2 && SY == 3) bit = 288 + (tbx >> 3) * 64 + tby * 8 + (tbx & 7);
-        else bit = 416 + ((tby >> 3) * 2 + (tbx >> 3)) * 64 + (tby & 7) * 8 + (tbx & 7);
+    if (__builtin_amdgcn_inverse_ballot_w64(accept)) {                   // the origin cell's lane sets the bitmap bit
+        const int bit = y2_bitmap_bit<SX, SY>(bxCell, byCell);
         atomicOr(&s_bm[bit >> 5], 1u << (bit & 31));
     }
+    __builtin_amdgcn_wave_barrier();                                     // as in the compact path
 }
 
 // ---- quantiser table: for every rangeDecode R (32..255) and every offset o = v - BN (-2..255) the index and minDiff of the first
@@ -770,6 +847,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
 
     // ---- a6: seven passes --------------------------------------------------------------------------------------
     unsigned long long cov = 0ULL;                                           // bit = lane = 4x4 cell covered
+    unsigned long long evaluated = 0ULL;                                     // tiles of the next gradient pass that a grouped sweep has decided
     {
         // S' is linear in x inside any tile, so |c(x-1)-2c(x)+c(x+1)| <= 4*rejectFactor+1 is necessary for acceptance of every
         // tile containing the three pixels (see tests/csrc/yk_encode_v1.hip).  Row 0 of the cell is tested: six tests already leave a cell of
@@ -815,15 +893,16 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
             for (int k = 0; k < 16; k++) rg[k] = y2_rg(pw[k]);
 #pragma unroll
             for (int k = 0; k < 8; k++) bb[k] = y2_bb(pw[2 * k], pw[2 * k + 1]);
-            if (deadLanes == 0ULL) y2_grad_pass<4, 4, true>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-            else y2_grad_pass<4, 4>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+            if (deadLanes == 0ULL) y2_grad_pass<4, 4, true>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+            else y2_grad_pass<4, 4>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
             if (~(cov | deadLanes) != 0ULL) {
-                y2_grad_pass<4, 3>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<3, 4>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<3, 3>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<3, 2>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<2, 3>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<2, 2>(s_lat, lat, cx, cy, rg, bb, cov, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<4, 3>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<3, 4>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                // from 8x8 on a compact pass may have evaluated the pass behind it in the same sweep: that one then finds its tiles in `evaluated`
+                y2_grad_pass<3, 3>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<3, 2>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<2, 3>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<2, 2>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
             }
             // the packed pixels come back from the staged strip (intact until the fence below)
 #pragma unroll
