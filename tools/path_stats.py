@@ -1,7 +1,6 @@
 """How often every path of yk_encode2_kernel is taken on one frame (needs a -DYK2_STATS build: YK_LIB=build/libS.so).
 usage: YK_LIB=build/libS.so python tools/path_stats.py [frame|ramp|mild|noise|border]
-The "would fit" rows are what decides the size of a grouped compact sweep: take them from a -DYK2_STATS -DYK2_NO_GROUP build (every pass
-enters on its own there); the "grouped sweeps" rows are what a build with the grouped sweep did."""
+The "grouped sweeps" rows are what a build with the grouped sweep did (a -DYK2_NO_GROUP build leaves them zero)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -45,14 +44,10 @@ for p in range(7):
     print(f"{names[p]:6s} {r[0] / n:7.3f} {r[1] / n:7.3f} {r[2] / n:7.3f} {r[3] / n:7.3f} {r[9] / n:7.3f} {r[4] / n:7.3f} {r[5] / n:7.3f} {r[6] / n:7.3f} "
           f"{r[8] / e:8.1f} {r[7] / max(r[1], 1):8.1f} {float(st[90 + p]) / max(r[5], 1):8.1f}")
 print("compact: exits after stage 1 per strip", [round(float(st[100 + p]) / n, 3) for p in range(7)], " accepts", [round(float(st[110 + p]) / n, 3) for p in range(7)])
-print("smooth 16x16 strips: tiles viable / accepted by raw|Round6 / by Round6P / by either, per strip:", [round(float(st[i]) / n, 3) for i in (107, 97, 98, 99)])
 print("valid lanes per strip (0, 1-4, 5-8, 9-16, 17-32, 33-63, 64):", [round(float(st[120 + i]) / n, 3) for i in range(7)])
 print(f"range: strips coded {st[70] / n:.3f}, valid lanes per coded strip {st[74] / max(float(st[70]), 1):.1f}, plane-waves with ambiguous tiles {st[71] / n:.4f} "
       f"(tiles {st[72] / n:.4f} per strip), tie blocks {st[73] / n:.4f} per strip")
 pairs = ["8x8+8x4", "8x4+4x8", "4x8+4x4"]
-print("compact pass whose next pass has cells under the coverage as it stands (per strip):", {pairs[k]: round(float(st[136 + k]) / n, 4) for k in range(3)})
-print("  of these, would fit one sweep (own + speculative next <= 16 cells):", {pairs[k]: round(float(st[130 + k]) / n, 4) for k in range(3)},
-      " runs of three:", {"8x8..4x8": round(float(st[133]) / n, 4), "8x4..4x4": round(float(st[134]) / n, 4)}, " run of four:", round(float(st[135]) / n, 4))
 print("grouped sweeps: formed", {pairs[k]: round(float(st[140 + k]) / n, 4) for k in range(3)}, " sweeps saved (the next pass had a tile left)", {pairs[k]: round(float(st[143 + k]) / n, 4) for k in range(3)},
       " left after stage 1", {pairs[k]: round(float(st[146 + k]) / n, 4) for k in range(3)}, " next pass's cells per group", {pairs[k]: round(float(st[150 + k]) / max(float(st[140 + k]), 1), 1) for k in range(3)},
       " groups whose next pass accepted", {pairs[k]: round(float(st[153 + k]) / n, 4) for k in range(3)})

@@ -20,6 +20,12 @@
 //   * the mode-selection sums are summed in tree order and accepted only when a rigorous rounding margin separates the
 //     modes; ambiguous tiles (rare) are re-summed in the reference's exact sequential order;
 //   * the grid is XCD-aware (runs of 16 blocks per XCD, rotated per group) so halo lines are served by the neighbour's L2.
+//
+// A gradient pass in pieces (all inlined; a strip hands them one record, Y2Pass): y2_grad_pass = the viable tiles (y2_viable), then
+// y2_compact_sweep (the (cell, row) path with the grouped sweep; it says whether it took the pass) or y2_full_pass (the wave walk; it returns
+// the accepted tiles), and y2_accept, the tail of both (coverage, bitmap bits, wave barrier).
+// Build switches, none of them shipped: -DYK_TEST_HOOKS (ablations, the forced exact path), -DYK2_STATS (path counters, tools/path_stats.py),
+// -DYK2_TIMING (per-wave clocks), -DYK2_NO_GROUP (the kernel without the grouped sweep, for A/B runs).
 #include "yk_common.h"
 #include "yk_curves.h"
 #include "yk_device.h"
@@ -106,14 +112,37 @@ template <int NX, int NY> __device__ __forceinline__ unsigned long long y2_sprea
 // the seven passes in the reference's order: tile = 2^SX x 2^SY pixels
 __device__ __forceinline__ constexpr int y2_pass_sx(int id) { return id < 2 ? 4 : (id < 5 ? 3 : 2); }
 __device__ __forceinline__ constexpr int y2_pass_sy(int id) { return id == 0 || id == 2 ? 4 : (id == 1 || id == 3 || id == 5 ? 3 : 2); }
+template <int SX, int SY> __device__ __forceinline__ constexpr int y2_pass_id() {
+    for (int id = 0; id < 7; id++) if (y2_pass_sx(id) == SX && y2_pass_sy(id) == SY) return id;
+    return -1;
+}
+// What a strip hands to every one of its gradient passes (built once in front of the seven calls; everything that takes it is inlined, so the
+// members are the kernel's own values, not memory).  It is passed BY VALUE: through a const reference the same code came out with three more
+// vector instructions per strip in the range phase (profiles/encode2_tidy).
+struct Y2Pass {
+    const uint32_t* s_lat; int lat;                                      // the corner lattice (LDS) and the index of the lane's cell origin in it
+    int cx, cy;                                                          // the lane's cell inside its macro-tile
+    const y2s2 (&rg)[16]; const y2s2 (&bb)[8];                           // the lane's pixels in stream layout (y2_rg / y2_bb)
+    unsigned long long deadLanes; bool stripInside;                      // cells killed by the curvature test; no tile of the strip crosses the image's edge
+    int gxCell, gyCell, w, h;                                            // cell origin (stripe-local pixels) and image size
+    int rf;                                                              // rejectFactor
+    uint32_t* s_bm; int bxCell, byCell;                                  // the strip's bitmap words (LDS) and the cell origin inside the 64x64 block
+    const uint32_t* s_pix; uint8_t* s_list; uint32_t* s_tf;              // compact sweep: the staged strip, the list of its cells, the tiles' failure words (LDS)
+    int lane;
+};
+// the acceptance windows on D of the six variants (:3929-3991): O / R = without / with the rounding term
+struct Y2Window { y2s2 loO, hiO, loR, hiR; };
+__device__ __forceinline__ Y2Window y2_window(const int rf) {
+    const int loO = -256 * rf, hiO = 256 * rf + 255;
+    return { y2_splats(loO), y2_splats(hiO), y2_splats(loO - 127), y2_splats(hiO - 127) };
+}
 // viable tiles of a pass (origin bits): top-left pixel uncovered (:3871-3875), no cell killed by the curvature test, whole tile inside the image
-template <int SX, int SY> __device__ __forceinline__ unsigned long long y2_viable(const unsigned long long cov, const unsigned long long deadLanes, const bool stripInside,
-                                                                                  const int cx, const int cy, const int gxCell, const int gyCell, const int w, const int h) {
+template <int SX, int SY> __device__ __forceinline__ unsigned long long y2_viable(const Y2Pass pass, const unsigned long long cov) {
     constexpr int TX = 1 << SX, TY = 1 << SY, NX = TX / 4, NY = TY / 4;
-    unsigned long long viable = y2_origin<NX, NY>() & ~cov & ~y2_fold<NX, NY>(deadLanes);
-    if (!stripInside) {
-        const int tgx = gxCell - (cx & (NX - 1)) * 4, tgy = gyCell - (cy & (NY - 1)) * 4;   // tile origin, stripe-local pixels
-        viable &= __ballot((tgx + TX <= w) && (tgy + TY <= h));
+    unsigned long long viable = y2_origin<NX, NY>() & ~cov & ~y2_fold<NX, NY>(pass.deadLanes);
+    if (!pass.stripInside) {
+        const int tgx = pass.gxCell - (pass.cx & (NX - 1)) * 4, tgy = pass.gyCell - (pass.cy & (NY - 1)) * 4;   // tile origin, stripe-local pixels
+        viable &= __ballot((tgx + TX <= pass.w) && (tgy + TY <= pass.h));
     }
     return viable;
 }
@@ -129,192 +158,177 @@ template <int SX, int SY> __device__ __forceinline__ int y2_bitmap_bit(const int
     return 416 + ((tby >> 3) * 2 + (tbx >> 3)) * 64 + (tby & 7) * 8 + (tbx & 7);
 }
 
-// `evaluated`: the tiles of THIS pass (origin bits) that the pass before it has already decided in a grouped compact sweep (below); on return
-// those of the next pass.  It is data, not a flag the caller branches on: a skipped pass finds no viable tile and leaves like any such pass.
-template <int SX, int SY, bool SMOOTH = false>
-__device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int lat, const int cx, const int cy,
-                                             const y2s2 (&rg)[16], const y2s2 (&bb)[8], unsigned long long& cov, unsigned long long& evaluated, const unsigned long long deadLanes, const bool stripInside,
-                                             const int gxCell, const int gyCell, const int w, const int h, const int rf,
-                                             uint32_t* s_bm, const int bxCell, const int byCell, const uint32_t* s_pix, uint8_t* s_list, uint32_t* s_tf, const int lane) {
-    constexpr int TX = 1 << SX, TY = 1 << SY, NX = TX / 4, NY = TY / 4;
-    const int dcx = cx & (NX - 1), dcy = cy & (NY - 1);                  // this cell's offset inside its tile, in cells
-    unsigned long long viable = y2_viable<SX, SY>(cov, deadLanes, stripInside, cx, cy, gxCell, gyCell, w, h) & ~evaluated;
-    evaluated = 0ULL;
-    if (viable == 0ULL) return;
-    constexpr int kPassId = (SX == 4 && SY == 4) ? 0 : (SX == 4 && SY == 3) ? 1 : (SX == 3 && SY == 4) ? 2 : (SX == 3 && SY == 3) ? 3 : (SX == 3 && SY == 2) ? 4 : (SX == 2 && SY == 3) ? 5 : 6;
-    YK2_STAT(kPassId * 10 + 0, 1); YK2_STAT(kPassId * 10 + 8, __popcll(y2_spread<NX, NY>(viable)));
-    const int loO = -256 * rf, hiO = 256 * rf + 255;
-    const y2s2 loO2 = y2_splats(loO), hiO2 = y2_splats(hiO), loR2 = y2_splats(loO - 127), hiR2 = y2_splats(hiO - 127);
+// The tail of a pass: its accepted tiles (origin bits) and, behind a grouped compact sweep, those of the next pass (`acceptB`, tile 2^SXB x 2^SYB)
+// paint the coverage (:4029-4037: bit = lane = cell) and their origin cells' lanes set the bitmap bits.  The two passes' bits are set in ONE
+// place: their sets of origin lanes are disjoint (an accepted tile of this pass covers its origin).
+template <int SX, int SY, int SXB = SX, int SYB = SY>
+__device__ __forceinline__ void y2_accept(const Y2Pass pass, unsigned long long& cov, const unsigned long long accept, const unsigned long long acceptB = 0ULL) {
+    cov |= y2_spread<(1 << SX) / 4, (1 << SY) / 4>(accept) | y2_spread<(1 << SXB) / 4, (1 << SYB) / 4>(acceptB);
+    if ((accept | acceptB) != 0ULL && __builtin_amdgcn_inverse_ballot_w64(accept | acceptB)) {
+        int bit = y2_bitmap_bit<SX, SY>(pass.bxCell, pass.byCell);
+        if ((SXB != SX || SYB != SY) && __builtin_amdgcn_inverse_ballot_w64(acceptB)) bit = y2_bitmap_bit<SXB, SYB>(pass.bxCell, pass.byCell);
+        atomicOr(&pass.s_bm[bit >> 5], 1u << (bit & 31));
+    }
+    __builtin_amdgcn_wave_barrier();                                     // no instruction: keeps what follows from being duplicated into the divergent branch above
+}
 
-
-#ifndef YK2_NO_COMPACT
-    // ---- few viable cells (a strip whose larger tiles failed along an edge, the usual case next to contours): a pass over 64 lanes
-    // would keep at most a quarter of them busy for four rows.  Instead lane (j, r) = (j-th viable cell, row r of it) evaluates ONE row
-    // of a viable cell; the pixels come from the staged strip in LDS.  A lane's failures are six bits (one per variant) OR-ed into a
-    // word of its tile in LDS; a tile is lost when all six are set.  Two stages like the full pass: streams {0, 3} first (a tile whose
-    // far corners sit on other content fails there), the other three only for waves that still hold a tile afterwards.
+// ---- few viable cells (a strip whose larger tiles failed along an edge, the usual case next to contours): a pass over 64 lanes
+// would keep at most a quarter of them busy for four rows.  Instead lane (j, r) = (j-th viable cell, row r of it) evaluates ONE row
+// of a viable cell; the pixels come from the staged strip in LDS.  A lane's failures are six bits (one per variant) OR-ed into a
+// word of its tile in LDS; a tile is lost when all six are set.  Two stages like the full pass: streams {0, 3} first (a tile whose
+// far corners sit on other content fails there), the other three only for waves that still hold a tile afterwards.
+// Returns whether it took the pass (at most 16 viable cells); it then has painted `cov` and handed on `evaluated` (y2_grad_pass).
+template <int SX, int SY>
+__device__ __forceinline__ bool y2_compact_sweep(const Y2Pass pass, const unsigned long long viable, unsigned long long& cov, unsigned long long& evaluated) {
+    constexpr int NX = (1 << SX) / 4, NY = (1 << SY) / 4, kPassId = y2_pass_id<SX, SY>();
+    const uint32_t* const s_lat = pass.s_lat; const uint32_t* const s_pix = pass.s_pix; uint8_t* const s_list = pass.s_list; uint32_t* const s_tf = pass.s_tf;
+    const int lane = pass.lane;
+    const Y2Window W = y2_window(pass.rf);
     const unsigned long long cells = y2_spread<NX, NY>(viable);
     const int nCells = __popcll(cells);
-    if (nCells <= 16) {
-        YK2_STAT(kPassId * 10 + 1, 1); YK2_STAT(kPassId * 10 + 7, nCells);
-        // ---- grouped sweep (8x8, 8x4 and 4x8): on a strip that borders other content the small passes follow each other with 4..8 cells
-        // each.  When the NEXT pass's cells, taken with the coverage as it stands now (a superset of what that pass will find), fit into the
-        // cell slots this pass leaves free, the lanes (j, r) with j >= nCells evaluate them in the same sweep: the shape (cells per tile, lattice
-        // offsets, weight shifts, origin lane) is then the lane's own, and the next pass's failures are the same six bits three places lower in
-        // the tile's word (two passes' tiles may share an origin lane).  The scalar side resolves the two in the reference's order.
-        constexpr bool kHasNext = kPassId >= 3 && kPassId <= 5;
-        constexpr int SXB = kHasNext ? y2_pass_sx(kPassId + 1) : SX, SYB = kHasNext ? y2_pass_sy(kPassId + 1) : SY;
-        constexpr int NXB = (1 << SXB) / 4, NYB = (1 << SYB) / 4;
-        unsigned long long viableB = 0ULL, cellsB = 0ULL;
-        int nB = 0;
-#if !defined(YK2_NO_GROUP) || defined(YK2_STATS)
-        if (kHasNext) {
-            viableB = y2_viable<SXB, SYB>(cov, deadLanes, stripInside, cx, cy, gxCell, gyCell, w, h);
-            cellsB = y2_spread<NXB, NYB>(viableB);
-            nB = __popcll(cellsB);
-#ifdef YK2_STATS
-            {   // would this pass and the next one, two or three fit one sweep (never shipped: counted before the grouped sweep was built)
-                constexpr int k = kPassId - 3;
-                constexpr int SXC = y2_pass_sx(kPassId <= 4 ? kPassId + 2 : 6), SYC = y2_pass_sy(kPassId <= 4 ? kPassId + 2 : 6);
-                int n2 = 0, n3 = 0;
-                if (kPassId <= 4) n2 = __popcll(y2_spread<(1 << SXC) / 4, (1 << SYC) / 4>(y2_viable<SXC, SYC>(cov, deadLanes, stripInside, cx, cy, gxCell, gyCell, w, h)));
-                if (kPassId == 3) n3 = __popcll(y2_viable<2, 2>(cov, deadLanes, stripInside, cx, cy, gxCell, gyCell, w, h));
-                if (nB > 0) {
-                    YK2_STAT(136 + k, 1);
-                    if (nCells + nB <= 16) YK2_STAT(130 + k, 1);
-                    if (kPassId <= 4 && n2 > 0 && nCells + nB + n2 <= 16) YK2_STAT(133 + k, 1);
-                    if (kPassId == 3 && n2 > 0 && n3 > 0 && nCells + nB + n2 + n3 <= 16) YK2_STAT(135, 1);
-                }
-            }
-#endif
-#ifdef YK2_NO_GROUP
-            nB = 0;
-#endif
-            if (nB == 0 || nCells + nB > 16) { viableB = 0ULL; cellsB = 0ULL; nB = 0; }
-        }
-#endif
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cells >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cells, 0u));
-        const bool mine = __builtin_amdgcn_inverse_ballot_w64(cells);
-        if (mine) s_list[rank] = (uint8_t)lane;
-        if (kHasNext && nB != 0) {                                           // wave-uniform: the next pass's cells behind this pass's
-            YK2_STAT(140 + kPassId - 3, 1); YK2_STAT(150 + kPassId - 3, nB);
-            const int rankB = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cellsB >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cellsB, 0u));
-            if (__builtin_amdgcn_inverse_ballot_w64(cellsB)) s_list[nCells + rankB] = (uint8_t)lane;
-        }
-        s_tf[lane] = 0u; s_tf[64 + lane] = 0u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int j = lane & 15, r = lane >> 4;
-        const bool act = j < nCells + nB;
-        const bool isB = kHasNext && j >= nCells;                            // the lane's cell belongs to the next pass (idle lanes: harmless either way)
-        const int c = (int)s_list[act ? j : 0];
-        const int q2 = c >> 4, cy2 = y2_cell_y(c & 15), cx2 = y2_cell_x(c & 15);
-        constexpr int kInTile = (NX > 1 ? 1 : 0) | (NY > 1 ? 2 : 0) | (NX > 2 ? 4 : 0) | (NY > 2 ? 8 : 0);   // Morton bits of a cell inside its tile
-        constexpr int kInTileB = (NXB > 1 ? 1 : 0) | (NYB > 1 ? 2 : 0) | (NXB > 2 ? 4 : 0) | (NYB > 2 ? 8 : 0);
-        // the lane's shape: constants unless a next pass can ride along
-        const int nxL = isB ? NXB : NX, nyL = isB ? NYB : NY;                // cells per tile
-        const int shx = isB ? 4 - SXB : 4 - SX, shy = isB ? 4 - SYB : 4 - SY; // weight shifts
-        const int dcx2 = cx2 & (nxL - 1), dcy2 = cy2 & (nyL - 1);
-        const int orig = c & ~(isB ? kInTileB : kInTile);                    // lane of the tile's origin cell
-        const int fsh = isB ? 3 : 0;                                         // place of the lane's failure bits in the tile's word
-        const int lo2 = cy2 * 17 + q2 * 4 + cx2 - dcy2 * 17 - dcx2;          // lattice index of the tile origin
-        const int oTR = nxL, oBL = nyL * 17;                                 // lattice offsets of the far corners
-        const y2u2 wyr = y2_splat(16 - ((dcy2 * 4 + r) << shy));            // weight of row r of the cell
-        const y2u2 lxc = y2_splat(16 - ((dcx2 * 4) << shx));                // weight of the cell's first pixel column
-        const y2u2 shx2 = y2_splat(shx);
-        const uint4 pr = *reinterpret_cast<const uint4*>(&s_pix[(cy2 * 4 + r) * LS + q2 * 16 + cx2 * 4]);
-        // the row's pixels in stream layout (y2_rg / y2_bb), built once for both stages
-        const y2s2 rgc[4] = { y2_rg(pr.x), y2_rg(pr.y), y2_rg(pr.z), y2_rg(pr.w) }, bbc[2] = { y2_bb(pr.x, pr.y), y2_bb(pr.z, pr.w) };
-        y2s2 mnc[5], mxc[5];
-        auto rowC = [&](const unsigned mask) {                               // the row's four pixels for the streams in `mask`
-            y2u2 Sc[5], stc[5];
-#pragma unroll
-            for (int t = 0; t < 5; t++) {
-                if (!((mask >> t) & 1u)) continue;
-                const uint32_t* lt = s_lat + t * YK2_LATN + lo2;
-                const y2u2 TL = y2_u2(lt[0]), TR = y2_u2(lt[oTR]), BL = y2_u2(lt[oBL]), BR = y2_u2(lt[oBL + oTR]);
-                const y2u2 e16 = (BL - BR) << 4, g = TR - BR, f = TL - BL - g;
-                const y2u2 c2 = (g << 4) + f * lxc;
-                Sc[t] = ((BR << 8) + e16 * lxc + c2 * wyr) ^ y2_splat(0x8000);   // S'(x0, row r), biased
-                stc[t] = (e16 + f * wyr) << shx2;                                // S'(x, r) - S'(x+1, r)
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const y2s2 c01 = rgc[i], cb = bbc[i >> 1];
-                const y2s2 cc[4] = { __builtin_shufflevector(c01, c01, 0, 0), __builtin_shufflevector(c01, c01, 1, 1),
-                                     (i & 1) ? __builtin_shufflevector(cb, cb, 1, 1) : __builtin_shufflevector(cb, cb, 0, 0), c01 };
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    if (!((mask >> t) & 1u)) continue;
-                    const y2s2 D = __builtin_elementwise_sub_sat(y2_s2(Sc[t]), cc[t]);
-                    if (i == 0) { mnc[t] = D; mxc[t] = D; }
-                    else { mnc[t] = __builtin_elementwise_min(mnc[t], D); mxc[t] = __builtin_elementwise_max(mxc[t], D); }
-                    if (i < 3) Sc[t] = Sc[t] - stc[t];
-                }
-            }
-            if (mask & 0x10u) {                                              // stream 4: columns (0, 1) and (2, 3), two pixels per operation
-                const y2s2 Da = __builtin_elementwise_sub_sat(y2_s2(Sc[4] - stc[4] * (y2u2){ 0, 1 }), bbc[0]);
-                const y2s2 Db = __builtin_elementwise_sub_sat(y2_s2(Sc[4] - stc[4] * (y2u2){ 2, 3 }), bbc[1]);
-                mnc[4] = __builtin_elementwise_min(Da, Db); mxc[4] = __builtin_elementwise_max(Da, Db);
-            }
-        };
-        // the lane's failing variants as bits 31, 30 (raw / Round6 corners without the rounding term), 15, 14 (with it), 29, 13 (Round6P corners)
-        constexpr uint32_t kAllFail = 0xE000E000u;
-        auto failBits = [&](const y2s2 mnA, const y2s2 mxA, const y2s2 mnP, const y2s2 mxP) -> uint32_t {
-            const y2s2 zero = y2_splats(0);
-            // a half is negative when its variant has a pixel outside the window (x = raw corners, y = Round6 corners)
-            const y2s2 oA = __builtin_elementwise_sub_sat(zero, __builtin_elementwise_max(__builtin_elementwise_sub_sat(loO2, mnA), __builtin_elementwise_sub_sat(mxA, hiO2)));
-            const y2s2 rA = __builtin_elementwise_sub_sat(zero, __builtin_elementwise_max(__builtin_elementwise_sub_sat(loR2, mnA), __builtin_elementwise_sub_sat(mxA, hiR2)));
-            const y2s2 oP = __builtin_elementwise_sub_sat(zero, __builtin_elementwise_max(__builtin_elementwise_sub_sat(loO2, mnP), __builtin_elementwise_sub_sat(mxP, hiO2)));
-            const y2s2 rP = __builtin_elementwise_sub_sat(zero, __builtin_elementwise_max(__builtin_elementwise_sub_sat(loR2, mnP), __builtin_elementwise_sub_sat(mxP, hiR2)));
-            const uint32_t a = __builtin_bit_cast(uint32_t, oA), b = __builtin_bit_cast(uint32_t, rA), cO = __builtin_bit_cast(uint32_t, oP), cR = __builtin_bit_cast(uint32_t, rP);
-            // raw-O -> bit 15, Round6-O -> bit 31, raw-R -> 14, Round6-R -> 30, Round6P-O (either half) -> 29, Round6P-R -> 13
-            uint32_t m = (a & 0x80008000u) | ((b >> 1) & 0x40004000u);
-            m |= (((cO << 16) | cO) >> 2) & 0x20000000u;
-            m |= (((cR >> 16) | cR) >> 2) & 0x00002000u;
-            return m;
-        };
-        constexpr uint32_t kAllFailB = kAllFail >> 3;                        // the next pass's six bits
-        rowC(0x09u);
-        if (act) atomicOr(&s_tf[orig], failBits(mnc[0], mxc[0], mnc[3], mxc[3]) >> fsh);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t w1 = s_tf[lane];
-        const unsigned long long alive = viable & __ballot((kHasNext ? (w1 & kAllFail) : w1) != kAllFail);
-        unsigned long long aliveB = 0ULL;
-        if (kHasNext && nB != 0) aliveB = viableB & __ballot((w1 & kAllFailB) != kAllFailB);
-        // a group leaves after stage 1 only when BOTH passes have lost all their tiles; a pass without a tile adds nothing to stage 2
-        if ((alive | aliveB) == 0ULL) { YK2_STAT(100 + kPassId, 1); if (nB != 0) { YK2_STAT(146 + kPassId - 3, 1); YK2_STAT(143 + kPassId - 3, 1); } evaluated = viableB; return; }
-        rowC(0x16u);
-        {
-            const y2s2 mnA = __builtin_elementwise_min(__builtin_elementwise_min(mnc[0], mnc[1]), mnc[2]), mxA = __builtin_elementwise_max(__builtin_elementwise_max(mxc[0], mxc[1]), mxc[2]);
-            const y2s2 mnP = __builtin_elementwise_min(mnc[3], mnc[4]), mxP = __builtin_elementwise_max(mxc[3], mxc[4]);
-            if (act) atomicOr(&s_tf[64 + orig], failBits(mnA, mxA, mnP, mxP) >> fsh);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t w2 = s_tf[64 + lane];
-        const unsigned long long acceptC = alive & __ballot((kHasNext ? (w2 & kAllFail) : w2) != kAllFail);   // some variant never failed (:3998)
-        if (acceptC != 0ULL) { YK2_STAT(110 + kPassId, 1); }
-        cov |= y2_spread<NX, NY>(acceptC);
-        unsigned long long acceptB = 0ULL;
-        if (kHasNext && nB != 0) {
-            // the next pass, in the reference's order: only the ORIGIN cell decides whether a tile is still viable (:3871-3875) once this pass's
-            // tiles are painted; a tile whose origin stays free is accepted even where it overlaps one of them
-            const unsigned long long stillB = aliveB & ~cov;
-            if (viableB & ~cov) YK2_STAT(143 + kPassId - 3, 1);              // the next pass would have run a sweep of its own
-            acceptB = stillB & __ballot((w2 & kAllFailB) != kAllFailB);
-            if (acceptB != 0ULL) { YK2_STAT(153 + kPassId - 3, 1); }
-            cov |= y2_spread<NXB, NYB>(acceptB);
-        }
-        // the accepted tiles' origin lanes set their bitmap bits; the two passes' sets are disjoint (an accepted tile of this pass covers its origin)
-        if ((acceptC | acceptB) != 0ULL && __builtin_amdgcn_inverse_ballot_w64(acceptC | acceptB)) {
-            int bit = y2_bitmap_bit<SX, SY>(bxCell, byCell);
-            if (kHasNext && __builtin_amdgcn_inverse_ballot_w64(acceptB)) bit = y2_bitmap_bit<SXB, SYB>(bxCell, byCell);
-            atomicOr(&s_bm[bit >> 5], 1u << (bit & 31));
-        }
-        __builtin_amdgcn_wave_barrier();                                     // no instruction: keeps what follows from being duplicated into the divergent branch above
-        evaluated = viableB;                                                 // the next pass is done (nothing without a group)
-        return;
+    if (nCells > 16) return false;
+    YK2_STAT(kPassId * 10 + 1, 1); YK2_STAT(kPassId * 10 + 7, nCells);
+    // ---- grouped sweep (8x8, 8x4 and 4x8): on a strip that borders other content the small passes follow each other with 4..8 cells
+    // each.  When the NEXT pass's cells, taken with the coverage as it stands now (a superset of what that pass will find), fit into the
+    // cell slots this pass leaves free, the lanes (j, r) with j >= nCells evaluate them in the same sweep: the shape (cells per tile, lattice
+    // offsets, weight shifts, origin lane) is then the lane's own, and the next pass's failures are the same six bits three places lower in
+    // the tile's word (two passes' tiles may share an origin lane).  The scalar side resolves the two in the reference's order.
+    constexpr bool kHasNext = kPassId >= 3 && kPassId <= 5;
+    constexpr int SXB = kHasNext ? y2_pass_sx(kPassId + 1) : SX, SYB = kHasNext ? y2_pass_sy(kPassId + 1) : SY;
+    constexpr int NXB = (1 << SXB) / 4, NYB = (1 << SYB) / 4;
+    unsigned long long viableB = 0ULL, cellsB = 0ULL;
+    int nB = 0;
+#ifndef YK2_NO_GROUP
+    if (kHasNext) {
+        viableB = y2_viable<SXB, SYB>(pass, cov);
+        cellsB = y2_spread<NXB, NYB>(viableB);
+        nB = __popcll(cellsB);
+        if (nB == 0 || nCells + nB > 16) { viableB = 0ULL; cellsB = 0ULL; nB = 0; }
     }
 #endif
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cells >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cells, 0u));
+    const bool mine = __builtin_amdgcn_inverse_ballot_w64(cells);
+    if (mine) s_list[rank] = (uint8_t)lane;
+    if (kHasNext && nB != 0) {                                           // wave-uniform: the next pass's cells behind this pass's
+        YK2_STAT(140 + kPassId - 3, 1); YK2_STAT(150 + kPassId - 3, nB);
+        const int rankB = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cellsB >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cellsB, 0u));
+        if (__builtin_amdgcn_inverse_ballot_w64(cellsB)) s_list[nCells + rankB] = (uint8_t)lane;
+    }
+    s_tf[lane] = 0u; s_tf[64 + lane] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int j = lane & 15, r = lane >> 4;
+    const bool act = j < nCells + nB;
+    const bool isB = kHasNext && j >= nCells;                            // the lane's cell belongs to the next pass (idle lanes: harmless either way)
+    const int c = (int)s_list[act ? j : 0];
+    const int q2 = c >> 4, cy2 = y2_cell_y(c & 15), cx2 = y2_cell_x(c & 15);
+    constexpr int kInTile = (NX > 1 ? 1 : 0) | (NY > 1 ? 2 : 0) | (NX > 2 ? 4 : 0) | (NY > 2 ? 8 : 0);   // Morton bits of a cell inside its tile
+    constexpr int kInTileB = (NXB > 1 ? 1 : 0) | (NYB > 1 ? 2 : 0) | (NXB > 2 ? 4 : 0) | (NYB > 2 ? 8 : 0);
+    // the lane's shape: constants unless a next pass can ride along
+    const int nxL = isB ? NXB : NX, nyL = isB ? NYB : NY;                // cells per tile
+    const int shx = isB ? 4 - SXB : 4 - SX, shy = isB ? 4 - SYB : 4 - SY; // weight shifts
+    const int dcx2 = cx2 & (nxL - 1), dcy2 = cy2 & (nyL - 1);
+    const int orig = c & ~(isB ? kInTileB : kInTile);                    // lane of the tile's origin cell
+    const int fsh = isB ? 3 : 0;                                         // place of the lane's failure bits in the tile's word
+    const int lo2 = cy2 * 17 + q2 * 4 + cx2 - dcy2 * 17 - dcx2;          // lattice index of the tile origin
+    const int oTR = nxL, oBL = nyL * 17;                                 // lattice offsets of the far corners
+    const y2u2 wyr = y2_splat(16 - ((dcy2 * 4 + r) << shy));            // weight of row r of the cell
+    const y2u2 lxc = y2_splat(16 - ((dcx2 * 4) << shx));                // weight of the cell's first pixel column
+    const y2u2 shx2 = y2_splat(shx);
+    const uint4 pr = *reinterpret_cast<const uint4*>(&s_pix[(cy2 * 4 + r) * LS + q2 * 16 + cx2 * 4]);
+    // the row's pixels in stream layout (y2_rg / y2_bb), built once for both stages
+    const y2s2 rgc[4] = { y2_rg(pr.x), y2_rg(pr.y), y2_rg(pr.z), y2_rg(pr.w) }, bbc[2] = { y2_bb(pr.x, pr.y), y2_bb(pr.z, pr.w) };
+    y2s2 mnc[5], mxc[5];
+    auto rowC = [&](const unsigned mask) {                               // the row's four pixels for the streams in `mask`
+        y2u2 Sc[5], stc[5];
+#pragma unroll
+        for (int t = 0; t < 5; t++) {
+            if (!((mask >> t) & 1u)) continue;
+            const uint32_t* lt = s_lat + t * YK2_LATN + lo2;
+            const y2u2 TL = y2_u2(lt[0]), TR = y2_u2(lt[oTR]), BL = y2_u2(lt[oBL]), BR = y2_u2(lt[oBL + oTR]);
+            const y2u2 e16 = (BL - BR) << 4, g = TR - BR, f = TL - BL - g;
+            const y2u2 c2 = (g << 4) + f * lxc;
+            Sc[t] = ((BR << 8) + e16 * lxc + c2 * wyr) ^ y2_splat(0x8000);   // S'(x0, row r), biased
+            stc[t] = (e16 + f * wyr) << shx2;                                // S'(x, r) - S'(x+1, r)
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const y2s2 c01 = rgc[i], cb = bbc[i >> 1];
+            const y2s2 cc[4] = { __builtin_shufflevector(c01, c01, 0, 0), __builtin_shufflevector(c01, c01, 1, 1),
+                                 (i & 1) ? __builtin_shufflevector(cb, cb, 1, 1) : __builtin_shufflevector(cb, cb, 0, 0), c01 };
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                if (!((mask >> t) & 1u)) continue;
+                const y2s2 D = __builtin_elementwise_sub_sat(y2_s2(Sc[t]), cc[t]);
+                if (i == 0) { mnc[t] = D; mxc[t] = D; }
+                else { mnc[t] = __builtin_elementwise_min(mnc[t], D); mxc[t] = __builtin_elementwise_max(mxc[t], D); }
+                if (i < 3) Sc[t] = Sc[t] - stc[t];
+            }
+        }
+        if (mask & 0x10u) {                                              // stream 4: columns (0, 1) and (2, 3), two pixels per operation
+            const y2s2 Da = __builtin_elementwise_sub_sat(y2_s2(Sc[4] - stc[4] * (y2u2){ 0, 1 }), bbc[0]);
+            const y2s2 Db = __builtin_elementwise_sub_sat(y2_s2(Sc[4] - stc[4] * (y2u2){ 2, 3 }), bbc[1]);
+            mnc[4] = __builtin_elementwise_min(Da, Db); mxc[4] = __builtin_elementwise_max(Da, Db);
+        }
+    };
+    // the lane's failing variants as bits 31, 30 (raw / Round6 corners without the rounding term), 15, 14 (with it), 29, 13 (Round6P corners)
+    constexpr uint32_t kAllFail = 0xE000E000u;
+    auto failBits = [&](const y2s2 mnA, const y2s2 mxA, const y2s2 mnP, const y2s2 mxP) -> uint32_t {
+        const y2s2 zero = y2_splats(0);
+        // a half is negative when its variant has a pixel outside the window (x = raw corners, y = Round6 corners)
+        const y2s2 oA = __builtin_elementwise_sub_sat(zero, __builtin_elementwise_max(__builtin_elementwise_sub_sat(W.loO, mnA), __builtin_elementwise_sub_sat(mxA, W.hiO)));
+        const y2s2 rA = __builtin_elementwise_sub_sat(zero, __builtin_elementwise_max(__builtin_elementwise_sub_sat(W.loR, mnA), __builtin_elementwise_sub_sat(mxA, W.hiR)));
+        const y2s2 oP = __builtin_elementwise_sub_sat(zero, __builtin_elementwise_max(__builtin_elementwise_sub_sat(W.loO, mnP), __builtin_elementwise_sub_sat(mxP, W.hiO)));
+        const y2s2 rP = __builtin_elementwise_sub_sat(zero, __builtin_elementwise_max(__builtin_elementwise_sub_sat(W.loR, mnP), __builtin_elementwise_sub_sat(mxP, W.hiR)));
+        const uint32_t a = __builtin_bit_cast(uint32_t, oA), b = __builtin_bit_cast(uint32_t, rA), cO = __builtin_bit_cast(uint32_t, oP), cR = __builtin_bit_cast(uint32_t, rP);
+        // raw-O -> bit 15, Round6-O -> bit 31, raw-R -> 14, Round6-R -> 30, Round6P-O (either half) -> 29, Round6P-R -> 13
+        uint32_t m = (a & 0x80008000u) | ((b >> 1) & 0x40004000u);
+        m |= (((cO << 16) | cO) >> 2) & 0x20000000u;
+        m |= (((cR >> 16) | cR) >> 2) & 0x00002000u;
+        return m;
+    };
+    constexpr uint32_t kAllFailB = kAllFail >> 3;                        // the next pass's six bits
+    rowC(0x09u);
+    if (act) atomicOr(&s_tf[orig], failBits(mnc[0], mxc[0], mnc[3], mxc[3]) >> fsh);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint32_t w1 = s_tf[lane];
+    const unsigned long long alive = viable & __ballot((kHasNext ? (w1 & kAllFail) : w1) != kAllFail);
+    unsigned long long aliveB = 0ULL;
+    if (kHasNext && nB != 0) aliveB = viableB & __ballot((w1 & kAllFailB) != kAllFailB);
+    // a group leaves after stage 1 only when BOTH passes have lost all their tiles; a pass without a tile adds nothing to stage 2
+    if ((alive | aliveB) == 0ULL) { YK2_STAT(100 + kPassId, 1); if (nB != 0) { YK2_STAT(146 + kPassId - 3, 1); YK2_STAT(143 + kPassId - 3, 1); } evaluated = viableB; return true; }
+    rowC(0x16u);
+    {
+        const y2s2 mnA = __builtin_elementwise_min(__builtin_elementwise_min(mnc[0], mnc[1]), mnc[2]), mxA = __builtin_elementwise_max(__builtin_elementwise_max(mxc[0], mxc[1]), mxc[2]);
+        const y2s2 mnP = __builtin_elementwise_min(mnc[3], mnc[4]), mxP = __builtin_elementwise_max(mxc[3], mxc[4]);
+        if (act) atomicOr(&s_tf[64 + orig], failBits(mnA, mxA, mnP, mxP) >> fsh);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint32_t w2 = s_tf[64 + lane];
+    const unsigned long long acceptC = alive & __ballot((kHasNext ? (w2 & kAllFail) : w2) != kAllFail);   // some variant never failed (:3998)
+    if (acceptC != 0ULL) { YK2_STAT(110 + kPassId, 1); }
+    unsigned long long acceptB = 0ULL;
+    if (kHasNext && nB != 0) {
+        // the next pass, in the reference's order: only the ORIGIN cell decides whether a tile is still viable (:3871-3875) once this pass's
+        // tiles are painted; a tile whose origin stays free is accepted even where it overlaps one of them
+        const unsigned long long covC = cov | y2_spread<NX, NY>(acceptC);   // the coverage with this pass's tiles (y2_accept paints both below)
+        const unsigned long long stillB = aliveB & ~covC;
+        if (viableB & ~covC) YK2_STAT(143 + kPassId - 3, 1);             // the next pass would have run a sweep of its own
+        acceptB = stillB & __ballot((w2 & kAllFailB) != kAllFailB);
+        if (acceptB != 0ULL) { YK2_STAT(153 + kPassId - 3, 1); }
+    }
+    y2_accept<SX, SY, SXB, SYB>(pass, cov, acceptC, acceptB);
+    evaluated = viableB;                                                 // the next pass is done (nothing without a group)
+    return true;
+}
+
+// The wave walk: every lane evaluates its own cell.  Returns the accepted tiles (origin bits).
+template <int SX, int SY, bool SMOOTH>
+__device__ __forceinline__ unsigned long long y2_full_pass(const Y2Pass pass, unsigned long long viable) {
+    constexpr int NX = (1 << SX) / 4, NY = (1 << SY) / 4, kPassId = y2_pass_id<SX, SY>();
+    const uint32_t* const s_lat = pass.s_lat; const y2s2 (&rg)[16] = pass.rg; const y2s2 (&bb)[8] = pass.bb;
+    const int lat = pass.lat, lane = pass.lane;
+    const int dcx = pass.cx & (NX - 1), dcy = pass.cy & (NY - 1);        // this cell's offset inside its tile, in cells
+    const Y2Window W = y2_window(pass.rf);
 
     // per stream: S (at the current pixel, biased), step along x, and the constants of the walk
     const int lo = lat - dcy * 17 - dcx;                                 // lattice index of the tile origin
@@ -378,8 +392,8 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
     // extremes: A = the (raw | Round6) streams merged over their channels, halves x / y = raw / Round6 corners; P = the Round6P streams
     // (either half); O / R = the window without / with the rounding term.
     auto failA4 = [&](const y2s2 mnA, const y2s2 mxA) -> unsigned long long {      // tiles in which raw-O, raw-R, Round6-O and Round6-R all have a failing lane
-        const y2s2 oA = __builtin_elementwise_max(__builtin_elementwise_sub_sat(loO2, mnA), __builtin_elementwise_sub_sat(mxA, hiO2));
-        const y2s2 rA = __builtin_elementwise_max(__builtin_elementwise_sub_sat(loR2, mnA), __builtin_elementwise_sub_sat(mxA, hiR2));
+        const y2s2 oA = __builtin_elementwise_max(__builtin_elementwise_sub_sat(W.loO, mnA), __builtin_elementwise_sub_sat(mxA, W.hiO));
+        const y2s2 rA = __builtin_elementwise_max(__builtin_elementwise_sub_sat(W.loR, mnA), __builtin_elementwise_sub_sat(mxA, W.hiR));
         unsigned long long f = y2_fold<NX, NY>(__ballot(oA.x > 0));
         f &= y2_fold<NX, NY>(__ballot(oA.y > 0));
         f &= y2_fold<NX, NY>(__ballot(rA.x > 0));
@@ -387,8 +401,8 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
         return f;
     };
     auto failP2 = [&](const y2s2 mnP, const y2s2 mxP) -> unsigned long long {      // tiles in which Round6P-O and Round6P-R both have a failing lane
-        const y2s2 oP = __builtin_elementwise_max(__builtin_elementwise_sub_sat(loO2, mnP), __builtin_elementwise_sub_sat(mxP, hiO2));
-        const y2s2 rP = __builtin_elementwise_max(__builtin_elementwise_sub_sat(loR2, mnP), __builtin_elementwise_sub_sat(mxP, hiR2));
+        const y2s2 oP = __builtin_elementwise_max(__builtin_elementwise_sub_sat(W.loO, mnP), __builtin_elementwise_sub_sat(mxP, W.hiO));
+        const y2s2 rP = __builtin_elementwise_max(__builtin_elementwise_sub_sat(W.loR, mnP), __builtin_elementwise_sub_sat(mxP, W.hiR));
         return y2_fold<NX, NY>(__ballot((oP.x > 0) | (oP.y > 0))) & y2_fold<NX, NY>(__ballot((rP.x > 0) | (rP.y > 0)));
     };
     auto mnAll = [&]() { return __builtin_elementwise_min(__builtin_elementwise_min(mn[0], mn[1]), mn[2]); };   // (raw | Round6) over the channels
@@ -415,20 +429,6 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
         nextRow(2, kA); pixelRow(3, kA, false);
         YK2_STAT(kPassId * 10 + 4, 1);
         accept = viable & ~failA4(mnAll(), mxAll());
-#ifdef YK2_STATS
-        {   // which variants accept the tiles of smooth strips (never shipped)
-            y2u2 S_[4], st_[4], a_[4], b_[4], c_[4]; y2s2 mn_[5], mx_[5];
-            for (int t = 0; t < 4; t++) { S_[t] = S[t]; st_[t] = st[t]; a_[t] = dS0[t]; b_[t] = dS3[t]; c_[t] = dst[t]; }
-            for (int t = 0; t < 5; t++) { mn_[t] = mn[t]; mx_[t] = mx[t]; }
-            setup(3); setup(4);
-            pixelRow(0, kP, true); nextRow(0, kP); pixelRow(1, kP, false); nextRow(1, kP); pixelRow(2, kP, false); nextRow(2, kP); pixelRow(3, kP, false);
-            const unsigned long long accP = viable & ~failP2(__builtin_elementwise_min(mn[3], mn[4]), __builtin_elementwise_max(mx[3], mx[4]));
-            YK2_STAT(97, __popcll(accept)); YK2_STAT(98, __popcll(accP)); YK2_STAT(99, __popcll(accept | accP)); YK2_STAT(96 + 0 * kPassId, 0);
-            YK2_STAT(107, __popcll(viable));
-            for (int t = 0; t < 4; t++) { S[t] = S_[t]; st[t] = st_[t]; dS0[t] = a_[t]; dS3[t] = b_[t]; dst[t] = c_[t]; }   // stream 4 is set up again before its walk
-            for (int t = 0; t < 5; t++) { mn[t] = mn_[t]; mx[t] = mx_[t]; }
-        }
-#endif
         const unsigned long long rest = viable & ~accept;
         if (rest != 0ULL) {
             YK2_STAT(kPassId * 10 + 5, 1); YK2_STAT(90 + kPassId, __popcll(y2_spread<NX, NY>(rest)));
@@ -446,65 +446,72 @@ __device__ __forceinline__ void y2_grad_pass(const uint32_t* s_lat, const int la
             }
         }
     } else {
-    int pRows;                                                           // rows the Round6P streams have walked so far
-    if (kScreen) {
-        setup(0); setup(3);
-        pixelRow(0, 0x09u, true);
-        viable &= ~(failA4(mn[0], mx[0]) & failP2(mn[3], mx[3]));
-        if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 2, 1); return; }
-        setup(1); setup(2);
-        pixelRow(0, 0x06u, true);
-        viable &= ~(failA4(mnAll(), mxAll()) & failP2(mn[3], mx[3]));      // after one row: lost tiles cannot be accepted by later rows
-        if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 3, 1); return; }
-        nextRow(0, kA);
-        pixelRow(1, kA, false);
-        pRows = 0;                                                       // stream 3 has walked row 0, stream 4 nothing yet
-    } else {
+        if (kScreen) {                                                   // afterwards stream 3 has walked row 0, stream 4 nothing yet
+            setup(0); setup(3);
+            pixelRow(0, 0x09u, true);
+            viable &= ~(failA4(mn[0], mx[0]) & failP2(mn[3], mx[3]));
+            if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 2, 1); return 0ULL; }
+            setup(1); setup(2);
+            pixelRow(0, 0x06u, true);
+            viable &= ~(failA4(mnAll(), mxAll()) & failP2(mn[3], mx[3]));  // after one row: lost tiles cannot be accepted by later rows
+            if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 3, 1); return 0ULL; }
+            nextRow(0, kA);
+            pixelRow(1, kA, false);
+        } else {                                                         // afterwards all five streams have walked rows 0 and 1
 #pragma unroll
-        for (int t = 0; t < 5; t++) setup(t);
-        pixelRow(0, 0x1Fu, true);
-        viable &= ~(failA4(mnAll(), mxAll()) & failP2(__builtin_elementwise_min(mn[3], mn[4]), __builtin_elementwise_max(mx[3], mx[4])));
-        if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 3, 1); return; }
-        nextRow(0, 0x1Fu);
-        pixelRow(1, 0x1Fu, false);
-        if (NX * NY <= 2) {                                              // one- and two-cell tiles: a second look after half of the rows (nearly every wave of
-                                                                         // 8x4 / 4x8 tiles on mild noise that outlives row 0 leaves here: DESIGN 3.2 round 5)
+            for (int t = 0; t < 5; t++) setup(t);
+            pixelRow(0, 0x1Fu, true);
             viable &= ~(failA4(mnAll(), mxAll()) & failP2(__builtin_elementwise_min(mn[3], mn[4]), __builtin_elementwise_max(mx[3], mx[4])));
-            if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 9, 1); return; }
+            if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 3, 1); return 0ULL; }
+            nextRow(0, 0x1Fu);
+            pixelRow(1, 0x1Fu, false);
+            if (NX * NY <= 2) {                                          // one- and two-cell tiles: a second look after half of the rows (nearly every wave of
+                                                                         // 8x4 / 4x8 tiles on mild noise that outlives row 0 leaves here: DESIGN 3.2 round 5)
+                viable &= ~(failA4(mnAll(), mxAll()) & failP2(__builtin_elementwise_min(mn[3], mn[4]), __builtin_elementwise_max(mx[3], mx[4])));
+                if (viable == 0ULL) { YK2_STAT(kPassId * 10 + 9, 1); return 0ULL; }
+            }
         }
-        pRows = 2;
-    }
-    YK2_STAT(kPassId * 10 + 4, 1);
-    nextRow(1, kA);
-    pixelRow(2, kA, false);
-    nextRow(2, kA);
-    pixelRow(3, kA, false);
-    accept = viable & ~failA4(mnAll(), mxAll());                         // some raw / Round6 variant never failed (:3998)
-    const unsigned long long rest = viable & ~accept;
-    if (rest != 0ULL) {                                                  // wave-uniform: the Round6P variants decide the remaining tiles
-        YK2_STAT(kPassId * 10 + 5, 1); YK2_STAT(90 + kPassId, __popcll(y2_spread<NX, NY>(rest)));
-        if (kScreen) {
-            setup(4);
-            pixelRow(0, 0x10u, true);
-            nextRow(0, kP);
-            pixelRow(1, kP, false);
+        YK2_STAT(kPassId * 10 + 4, 1);
+        nextRow(1, kA);
+        pixelRow(2, kA, false);
+        nextRow(2, kA);
+        pixelRow(3, kA, false);
+        accept = viable & ~failA4(mnAll(), mxAll());                     // some raw / Round6 variant never failed (:3998)
+        const unsigned long long rest = viable & ~accept;
+        if (rest != 0ULL) {                                              // wave-uniform: the Round6P variants decide the remaining tiles
+            YK2_STAT(kPassId * 10 + 5, 1); YK2_STAT(90 + kPassId, __popcll(y2_spread<NX, NY>(rest)));
+            if (kScreen) {
+                setup(4);
+                pixelRow(0, 0x10u, true);
+                nextRow(0, kP);
+                pixelRow(1, kP, false);
+            }
+            nextRow(1, kP);
+            pixelRow(2, kP, false);
+            nextRow(2, kP);
+            pixelRow(3, kP, false);
+            accept |= rest & ~failP2(__builtin_elementwise_min(mn[3], mn[4]), __builtin_elementwise_max(mx[3], mx[4]));
         }
-        nextRow(1, kP);
-        pixelRow(2, kP, false);
-        nextRow(2, kP);
-        pixelRow(3, kP, false);
-        accept |= rest & ~failP2(__builtin_elementwise_min(mn[3], mn[4]), __builtin_elementwise_max(mx[3], mx[4]));
     }
-    (void)pRows;
-    }
+    return accept;
+}
+
+// One gradient pass of a strip: the viable tiles, then the compact sweep when few cells are viable, the wave walk otherwise.
+// `evaluated`: the tiles of THIS pass (origin bits) that the pass before it has already decided in a grouped compact sweep; on return
+// those of the next pass.  It is data, not a flag the caller branches on: a skipped pass finds no viable tile and leaves like any such pass.
+template <int SX, int SY, bool SMOOTH = false>
+__device__ __forceinline__ void y2_grad_pass(const Y2Pass pass, unsigned long long& cov, unsigned long long& evaluated) {
+    constexpr int NX = (1 << SX) / 4, NY = (1 << SY) / 4, kPassId = y2_pass_id<SX, SY>();
+    const int lane = pass.lane;
+    const unsigned long long viable = y2_viable<SX, SY>(pass, cov) & ~evaluated;
+    evaluated = 0ULL;
+    if (viable == 0ULL) return;
+    YK2_STAT(kPassId * 10 + 0, 1); YK2_STAT(kPassId * 10 + 8, __popcll(y2_spread<NX, NY>(viable)));
+    if (y2_compact_sweep<SX, SY>(pass, viable, cov, evaluated)) return;
+    const unsigned long long accept = y2_full_pass<SX, SY, SMOOTH>(pass, viable);
     if (accept == 0ULL) return;
     YK2_STAT(kPassId * 10 + 6, 1);
-    cov |= y2_spread<NX, NY>(accept);                                    // paint coverage (:4029-4037): bit = lane = cell
-    if (__builtin_amdgcn_inverse_ballot_w64(accept)) {                   // the origin cell's lane sets the bitmap bit
-        const int bit = y2_bitmap_bit<SX, SY>(bxCell, byCell);
-        atomicOr(&s_bm[bit >> 5], 1u << (bit & 31));
-    }
-    __builtin_amdgcn_wave_barrier();                                     // as in the compact path
+    y2_accept<SX, SY>(pass, cov, accept);
 }
 
 // ---- quantiser table: for every rangeDecode R (32..255) and every offset o = v - BN (-2..255) the index and minDiff of the first
@@ -610,19 +617,6 @@ __device__ __forceinline__ uint32_t y2_writelane(uint32_t v, int k, uint32_t old
         case 3: return y2_writelane_k<3>(v, old); case 4: return y2_writelane_k<4>(v, old); default: return y2_writelane_k<5>(v, old);
     }
 }
-__device__ __forceinline__ uint32_t y2_sinkable(uint32_t v) { return v; }
-__device__ __forceinline__ uint32_t y2_sinkable(uint2 v) { return v.x ^ v.y; }
-// -DYK2_NOSTORE=<bits> (timing experiments only, never shipped): output stores of the fused kernel feed a checksum instead (the arithmetic stays):
-// 1 = the nibble slots, 2 = per-tile counts and definitions, 4 = the atomics (16x16 map, scan sums), 8 = bitmaps, 16 = coverage
-#ifdef YK2_NOSTORE
-#define Y2_SINK(val) do { y2sink ^= (uint32_t)(val); } while (0)
-#else
-#define YK2_NOSTORE 0
-#define Y2_SINK(val) do { } while (0)
-#endif
-#define Y2_STORE_IF(bit, lhs, val) do { if (YK2_NOSTORE & (bit)) Y2_SINK(y2_sinkable(val)); else lhs = (val); } while (0)
-#define Y2_STORE(lhs, val) Y2_STORE_IF(2, lhs, val)
-#define Y2_ATOMIC(call, val) do { if (YK2_NOSTORE & 4) Y2_SINK(val); else { call; } } while (0)
 // -DYK2_TIMING (tools/wave_timeline.sh only, never shipped): every wave records the shader clock and the 100 MHz real-time counter at
 // five points, its entry time and its hardware slot (HW_ID, XCC_ID) into a device array that yk_debug_wave_times copies out.
 #ifdef YK2_TIMING
@@ -731,14 +725,12 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
 #endif
     // one 64x16 strip; `slot`, `xcd`: position in the XCD-aware unit order (below).  The kernel arguments are read through the kernel-argument
     // segment pointer where they are used (scalar loads from the constant cache) instead of being copied into SGPRs at the top: 16 spilled
-    // SGPRs fewer.  (The lambda is what is left of the round-4 persistent-wave experiment, commit b2a2a39, profiles/r04/a*: DESIGN 5.3.)
+    // SGPRs fewer.  (The lambda is what is left of the round-4 persistent-wave experiment, commit b2a2a39, profiles/r04/a*: DESIGN 5.3.  Writing
+    // its body into the kernel changes the register allocation of the MODE3 instantiations, +4 and +3 VGPRs: DESIGN 3.2, profiles/encode2_tidy.)
     typedef const __attribute__((address_space(4))) YkEncodeParams* Y2ParamPtr;
     auto strip = [&](const int slot, const int xcd, const int lane, Y2ParamPtr const Pp) {
     const __attribute__((address_space(4))) YkEncodeParams& P = *Pp;
     const int nBf = P.xBB64 * P.yBB64, nB = nBf * P.nFrames;             // blocks per frame / of the whole batch
-#if YK2_NOSTORE
-    uint32_t y2sink = 0u;
-#endif
     // XCD-aware unit order: consecutive workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2).  Units are
     // taken in row-major runs of YK2_RUN blocks (4 strips each); XCD k gets a rotating run of every group of 8 runs, so the
     // halo column of a block and the halo row of a strip are lines a neighbour streams through the same L2 at about the same
@@ -893,16 +885,18 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
             for (int k = 0; k < 16; k++) rg[k] = y2_rg(pw[k]);
 #pragma unroll
             for (int k = 0; k < 8; k++) bb[k] = y2_bb(pw[2 * k], pw[2 * k + 1]);
-            if (deadLanes == 0ULL) y2_grad_pass<4, 4, true>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-            else y2_grad_pass<4, 4>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+            // the tiles' failure words of the compact sweep live in s_range (the range phase's, not in use yet)
+            const Y2Pass S = { s_lat, lat, cx, cy, rg, bb, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane };
+            if (deadLanes == 0ULL) y2_grad_pass<4, 4, true>(S, cov, evaluated);
+            else y2_grad_pass<4, 4>(S, cov, evaluated);
             if (~(cov | deadLanes) != 0ULL) {
-                y2_grad_pass<4, 3>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<3, 4>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<4, 3>(S, cov, evaluated);
+                y2_grad_pass<3, 4>(S, cov, evaluated);
                 // from 8x8 on a compact pass may have evaluated the pass behind it in the same sweep: that one then finds its tiles in `evaluated`
-                y2_grad_pass<3, 3>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<3, 2>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<2, 3>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
-                y2_grad_pass<2, 2>(s_lat, lat, cx, cy, rg, bb, cov, evaluated, deadLanes, stripInside, gxCell, gyCell, w, h, P.rejectFactor, s_bm, bxCell, byCell, s_pix, s_list, s_range, lane);
+                y2_grad_pass<3, 3>(S, cov, evaluated);
+                y2_grad_pass<3, 2>(S, cov, evaluated);
+                y2_grad_pass<2, 3>(S, cov, evaluated);
+                y2_grad_pass<2, 2>(S, cov, evaluated);
             }
             // the packed pixels come back from the staged strip (intact until the fence below)
 #pragma unroll
@@ -937,7 +931,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
         val8 = y2_writelane(bmWord(1) >> (8 * wave), 1, val8);
         off8 = y2_writelane(P.oBm[2] + frU * (uint32_t)P.fs.bitmap[2] + i64 * 4u + (uint32_t)wave, 2, off8);
         val8 = y2_writelane(bmWord(2) >> (8 * wave), 2, val8);
-        if (lane < 3) Y2_STORE_IF(8, *(small + off8), (uint8_t)val8);
+        if (lane < 3) *(small + off8) = (uint8_t)val8;
         // 16-bit words: lanes 0, 16, 32, 48 = coverage of the four macro-tiles (bit = cellY*4 + cellX: row-major, the Morton index with its two
         // middle bits exchanged), lane 1 = 8x8 (tile rows 2w, 2w+1), lanes 2, 3 = 4x8 (32x64 swizzle blocks, tile rows 2w, 2w+1)
         const unsigned long long t = ((cov >> 2) ^ cov) & 0x0C0C0C0C0C0C0C0CULL;
@@ -952,7 +946,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
             off16 = y2_writelane(in ? P.oBm[5] + frU * (uint32_t)P.fs.bitmap[5] + ((uint32_t)((BY * P.xBB32 + BX * 2 + sx) * 4 + wave)) * 2u : ~0u, 2 + sx, off16);
             val16 = y2_writelane(bmWord(9 + sx * 2 + (int)w2) >> (16 * w1), 2 + sx, val16);
         }
-        if (off16 != ~0u) Y2_STORE_IF(8, *reinterpret_cast<uint16_t*>(small + off16), (uint16_t)val16);
+        if (off16 != ~0u) *reinterpret_cast<uint16_t*>(small + off16) = (uint16_t)val16;
         // optional: the packed pixels of the cells nothing covered, for the live 1-D path (yk_set_pixel_cache): [strip][cell row][lane] 16-byte pieces
         if (P.pixCache != nullptr) {
             const bool cellIn = (gxCell < w) && (gyCell < h);
@@ -1004,11 +998,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     const bool writer = ((lane & 3) == 0) && tileIn;                         // one lane per tile writes count / def
     const unsigned long long validMask = __ballot(valid);
     // wave-uniform: every live tile has all four quadrants to code (then every lane of its quad is valid) -- the wide slot stores below
-#ifdef YK2_NO_WIDE_STORE
-    const bool fullTiles = false;
-#else
     const bool fullTiles = !WANT_DST && __ballot(tileLive && quadN != 15u && quadN != 0u) == 0ULL;
-#endif
 
     // ---- first level of the stream compaction's scan, fused: nibbles and coded tiles per run of 8 consecutive tiles (row-major tile order =
     // LeftRightOrder; the counts are the same for the three planes).  A strip holds two runs; when the tile grid is a multiple of 8 wide a run
@@ -1028,10 +1018,10 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
                 val32 = y2_writelane((uint32_t)(__popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2)) | ((uint32_t)__popcll(bd) << 16), 4 + r, val32);
             }
         } else if (writer && n16 > 0) {
-            Y2_ATOMIC(atomicAdd(&blockCntP[((size_t)tileIdx >> 10) * 2], 16u * (uint32_t)n16), n16);
-            Y2_ATOMIC(atomicAdd(&blockCntP[((size_t)tileIdx >> 10) * 2 + 1], 1u), 1);
+            atomicAdd(&blockCntP[((size_t)tileIdx >> 10) * 2], 16u * (uint32_t)n16);
+            atomicAdd(&blockCntP[((size_t)tileIdx >> 10) * 2 + 1], 1u);
         }
-        if (off32 != ~0u) Y2_STORE_IF(8, *reinterpret_cast<uint32_t*>(small + off32), val32);
+        if (off32 != ~0u) *reinterpret_cast<uint32_t*>(small + off32) = val32;
     }
 
     YK2_STAT(70, validMask != 0ULL ? 1 : 0); YK2_STAT(74, __popcll(validMask));
@@ -1039,8 +1029,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     // one 8-byte record per tile: the three planes' definition words and the tile's nibble count (the same for the three planes), stored once
     // behind the plane loop by the tile's first lane: 16 lanes x 8 bytes = two runs of 64 contiguous bytes per strip (round 3: six stores)
     uint32_t defs01 = 0u, defs2c = 0u;
-    if (validMask == 0ULL || YK2_ABLATE(1)) {
-    } else {
+    if (validMask != 0ULL && !YK2_ABLATE(1)) {
         uint32_t* lut = &s_lut[WANT_DST ? tw : 0][0];
         // curve constants for buildLut (test-only reconstruction); fetched here, off the path of the strip's pixel loads
         if (WANT_DST) {
@@ -1398,7 +1387,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
                     asm volatile("" : "+v"(so));
                     const uint4 half = make_uint4(__builtin_amdgcn_perm(nLo, cLo, 0x05040100u), __builtin_amdgcn_perm(nLo, cLo, 0x07060302u),
                                                   __builtin_amdgcn_perm(nHi, cHi, 0x05040100u), __builtin_amdgcn_perm(nHi, cHi, 0x07060302u));
-                    if (YK2_NOSTORE & 1) Y2_SINK(half.x ^ half.y ^ half.z ^ half.w); else *reinterpret_cast<uint4*>(slotPlane + so) = half;
+                    *reinterpret_cast<uint4*>(slotPlane + so) = half;
                 }
             } else if (valid) {
                 uint8_t* const slotPlane = slotsP + (size_t)p * T8 * YK_SLOT;      // wave-uniform base + 32-bit lane offsets (3 * T8 * 32 < 2^32)
@@ -1409,7 +1398,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
                     // the store takes the scalar base + 32-bit offset form (hoisted 64-bit offsets cost 8 registers and a spill)
                     uint32_t so = slotOff[r];
                     asm volatile("" : "+v"(so));
-                    Y2_STORE_IF(1, *reinterpret_cast<uint16_t*>(slotPlane + so), (uint16_t)code16);
+                    *reinterpret_cast<uint16_t*>(slotPlane + so) = (uint16_t)code16;
                     if (WANT_DST) {
                         const uint32_t* lb = lut + (bestMode < 3 ? bestMode * 20 : 60 + (bestMode - 3) * 8);
                         int32_t* drow = P.dst[p] + (uint32_t)((gyCell + r) * w + gxCell);     // 32-bit element offset from a scalar base (w, h <= 32760)
@@ -1429,12 +1418,9 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     }
     if (writer) {
         const uint32_t offI = P.oInfo + (frU * (uint32_t)P.fs.tileInfo + (uint32_t)tileIdx) * 8u;      // scalar base + 32-bit lane offset
-        Y2_STORE(*reinterpret_cast<uint2*>(small + offI), make_uint2(defs01, defs2c));
+        *reinterpret_cast<uint2*>(small + offI) = make_uint2(defs01, defs2c);
     }
     YK2_PROBE(4);
-#if YK2_NOSTORE
-    if (y2sink == 0x9E3779B9u) P.coverage[lane] = 1;
-#endif
     };   // strip
     strip((int)blockIdx.x >> 3, (int)blockIdx.x & 7, lane, (Y2ParamPtr)__builtin_amdgcn_kernarg_segment_ptr());
 }
