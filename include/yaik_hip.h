@@ -529,7 +529,9 @@ int yk_decode_1d(yk_ctx* c, const uint8_t* typeStream, size_t typeBytes, const u
 int yk_decode_1d_device(yk_ctx* c, const uint8_t* devType, size_t typeBytes, const uint8_t* devPix, size_t pixBytes, int compressionRange);
 /* Decompress1BitTiled (decoder/YAIK_Mipmap.cpp:23-154): 1 bit / 16x16 tile -> swizzled 1 bit / pixel mask */
 int yk_decode_mask(yk_ctx* c, const uint8_t* bits, int tileBBoxW, int tileBBoxH, uint8_t* hostOut, size_t cap);
-/* 8x8-tiled u8 planes exactly as YAIK_SCustomDataSource hands them to imageBuilderFunc (include/YAIK.h:205-224) */
+/* 8x8-tiled u8 planes exactly as YAIK_SCustomDataSource hands them to imageBuilderFunc (include/YAIK.h:205-224).  Under a decode window
+ * (yk_decode_set_window, below) the planes are exact inside the window and unspecified outside it; yk_decode_tile4x4[_planes] stay whole-image
+ * and exact. */
 int yk_decode_planes(yk_ctx* c, uint8_t* hostR, uint8_t* hostG, uint8_t* hostB, size_t capEach);
 const uint8_t* yk_decode_planes_device(yk_ctx* c, size_t* planeSize);
 /* internal_imageBuilderFunc (decoder/YAIK_DefaultCallback.cpp:24-191): de-tile into interleaved rows at outputImageStride.
@@ -572,6 +574,27 @@ int yk_decode_output_alpha(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride
 int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha);
 /* the three planes of tile4x4Mask back to back (planes 1 and 2 are meaningful once a partial-plane pass has split the masks) */
 int yk_decode_tile4x4_planes(yk_ctx* c, uint8_t* hostOut, size_t cap);
+
+/* ---- decode windows: only the tiles a rectangle of the image needs ----
+ * yk_decode_set_window: with a window W = (x0, y0, ww, wh) set on the handle, the decode calls leave in the handle's planes, for every pixel
+ * inside W, exactly what the whole-image decode leaves there; outside W the planes hold whatever they held.  Any stage may ignore the window and
+ * write more, none writes less: the all-planes gradient passes (either path) render only the 64x64 blocks W touches and still mark every tile in
+ * tile4x4Mask, the shared-mask 1-D chunk counts and scans the whole image (stream offsets are global prefix sums) and decodes only W's tiles; in
+ * that flow no byte of the planes outside W rounded out to multiples of 64 (clipped to the image) is written.  '3DTL' and plane-subset chunks, and
+ * the 1-D chunk behind a plane-subset chunk, write the whole image as before.
+ * Valid after yk_decode_begin and before any chunk of that image is decoded (gradient, plane-subset, mask split, '3DTL', 1-D); otherwise, and on a
+ * handle begun with yk_decode_begin_batch, YK_ERR_STATE.  x0, y0, ww, wh: multiples of 8, ww, wh >= 8, the rectangle inside the image; otherwise
+ * YK_ERR_BAD_ARG.  ww == wh == 0 clears the window; yk_decode_begin always clears it.
+ * While a window is set, the calls that need the whole image return YK_ERR_STATE with a message that names the window: yk_decode_output,
+ * yk_decode_output_alpha, yk_decode_output_reference_rgba, yk_decode_output_device and yk_decode_compare_*.  yk_decode_planes[_device] and
+ * yk_decode_tile4x4[_planes] stay allowed: the planes are exact inside W (unspecified outside), the marks are whole-image and exact.
+ * yk_decode_alpha is not affected: the 'ALPM' plane stays whole.
+ * yk_decode_output_window_device: yk_decode_output_device for the window: tile (x0 / 8 + jx, y0 / 8 + jy) of the planes goes to pixel (8 jx, 8 jy)
+ * of a ww x wh destination with the layout rules of yk_decode_output_device (HWC or CHW, any pitch, only pixel bytes written; the pitch checks
+ * are made against ww x wh).  alpha = -1 reads the decoded 'ALPM' plane at the window's offset.  With no window set it is
+ * yk_decode_output_device.  Timed as one YK_STAGE_DEC_DETILE interval. */
+int yk_decode_set_window(yk_ctx* c, int x0, int y0, int ww, int wh);
+int yk_decode_output_window_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha);
 
 /* ---- decode batches: nFrames images of ONE shape on a handle, every kernel launched once over nFrames x blocks ----
  * A frame of 2048 x 2048 or less is a fraction of the grids the decode kernels were tuned on, and one image costs about a dozen dependent stream

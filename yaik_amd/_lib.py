@@ -147,6 +147,8 @@ SIGNATURES = {
     "yk_decode_alpha_plane": (C.c_int, [vp, vp, sz]),
     "yk_decode_output_alpha": (C.c_int, [vp, vp, sz]),
     "yk_decode_output_device": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_int]),
+    "yk_decode_set_window": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "yk_decode_output_window_device": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_int]),
     "yk_decode_tile4x4": (C.c_int, [vp, vp, sz]),
     "yk_decode_tile4x4_planes": (C.c_int, [vp, vp, sz]),
     "yk_decode_begin_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),

@@ -264,6 +264,10 @@ struct yk_ctx {
     bool dAlphaBatch = false; size_t dAlphaStride = 0;
     // yk_decode_alpha_mask_batch_device: the frames of modes 2 / 3 of the last batch call, in table order, and one status word for each of them
     std::vector<int32_t> dAvMaskFrames; YkBuf<int32_t> dAvStatus;
+    // yk_decode_set_window: the rectangle (pixels, multiples of 8) the decode of this image has to produce; dWinSet false = the whole image.
+    // dBatchBegun: the handle was begun by yk_decode_begin_batch (no windows there); dChunkSeen: a chunk of the image has been decoded
+    int dWinX = 0, dWinY = 0, dWinW = 0, dWinH = 0;
+    bool dWinSet = false, dBatchBegun = false, dChunkSeen = false;
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
     // decode batch (yk_decode_begin_batch): dB holds the allocations (frame 0) and dStride the distance in BYTES from one frame's array to the
     // next, like B / fs on the encode side; yk_dec_frame(c, f) computes the arrays of frame f, and the single-image entry points work on frame
@@ -337,6 +341,9 @@ int yk_refuse(yk_ctx* c, int code, const char* what);
 
 // 'ALPM', 'MIPM', '3DTL' and plane-subset chunks act on one image: with a decode batch of more than one frame they refuse, touching nothing
 #define YK_DEC_NO_BATCH(c, name) do { if ((c)->dFrames > 1) return yk_refuse((c), YK_ERR_STATE, name " is not supported in a batch (yk_decode_begin_batch with nFrames > 1)"); } while (0)
+
+// the calls that hand out or compare the whole image refuse while a window is set: outside it the planes hold whatever they held before
+#define YK_DEC_NO_WINDOW(c, name) do { if ((c)->dWinSet) return yk_refuse((c), YK_ERR_STATE, name " needs the whole image, but a window is set on this decode (yk_decode_set_window): use yk_decode_output_window_device"); } while (0)
 
 // launchers implemented in the kernel TUs
 int yk_stage_begin(yk_ctx* c, int stage);                // records the begin event of a new interval of `stage` on c->stream

@@ -86,11 +86,18 @@ __global__ __launch_bounds__(1024) void yk_dec_corner_kernel(const uint32_t* __r
 // and channel: in the 8x8-tiled plane layout that run is contiguous and leaves as ONE 8-byte (or 4-byte) store.
 template <int NW> struct DRenderLdsN { int xy[32 * NW][2]; uint8_t c[32 * NW][3][4]; };
 typedef DRenderLdsN<1> DRenderLds;
+// A decode window (yk_decode_set_window) rounded out to 64-pixel blocks and clipped to the image: [x0, x1) x [y0, y1) in pixels.  Every tile
+// shape's swizzle blocks are 32 or 64 pixels wide and high, so a gradient tile lies inside this rectangle or outside it, never across its border.
+struct DWinRect { int x0, y0, x1, y1; };
+// WIN of yk_dec_render_words: the whole-image form; every tile of the words lies outside the window (marks only: the tile list and the atomicOr
+// marks, no lattice fetch and no plane store); the tiles are tested one by one against the rectangle (a 16x16 word holds two 64x64 blocks)
+enum { YK_DR_WHOLE = 0, YK_DR_MARKS = 1, YK_DR_PER_TILE = 2 };
+#define YK_DR_SKIP 0x40000000                               // in L.xy[k][1] (YK_DR_PER_TILE): the tile lies outside the window
 // the tiles of NW bitmap words (word k: index wi[k], bits bits[k]) of one pass, rendered together by the whole workgroup (256 threads)
-template <int NW>
+template <int NW, int WIN = YK_DR_WHOLE>
 __device__ __forceinline__ void yk_dec_render_words(DRenderLdsN<NW>& L, const uint32_t* wi, const uint32_t* bitsN, const DPassGeo& g, int w, int h, int latW,
                                                     const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes, size_t planeSize, int tileW,
-                                                    uint32_t* __restrict__ tile4, int stride4) {
+                                                    uint32_t* __restrict__ tile4, int stride4, const DWinRect wr = DWinRect{ 0, 0, 0, 0 }) {
     const int TX = 1 << g.sx, TY = 1 << g.sy, dx = TX >> 2, dy = TY >> 2;
     const int lgGpr = g.sx > 3 ? g.sx - 3 : 0, lgPer = g.sy + lgGpr;            // runs per row, runs per channel (powers of two)
     const int GW = TX < 8 ? TX : 8, gpr = 1 << lgGpr, perCh = 1 << lgPer, nEl = 3 * perCh, sh = g.sx + g.sy;
@@ -103,16 +110,19 @@ __device__ __forceinline__ void yk_dec_render_words(DRenderLdsN<NW>& L, const ui
         if (wk < NW && ((bitsN[wk] >> bit) & 1u)) {
             int x, y; yk_dtile_from_bit(g, wi[wk] * 32u + (uint32_t)bit, x, y);
             const int k = before + __popc(bitsN[wk] & ((1u << bit) - 1u));
-            L.xy[k][0] = (x + TX > w || y + TY > h) ? -1 : x; L.xy[k][1] = y;
+            L.xy[k][0] = (x + TX > w || y + TY > h) ? -1 : x;
+            if (WIN == YK_DR_PER_TILE && (x < wr.x0 || x >= wr.x1 || y < wr.y0 || y >= wr.y1)) y |= YK_DR_SKIP;
+            L.xy[k][1] = y;
         }
     }
     __syncthreads();
+    if (WIN != YK_DR_MARKS) {                                                   // fetch and fill (kept at its indentation): not for marks only
     // the four corner colours of the word's tiles, once (every run of a tile used to fetch them again: 4 byte loads per 8-byte store)
     // one (unaligned) 4-byte load per corner = its three colours (the lattice array is allocated four bytes longer), not three byte loads
     for (int i = threadIdx.x; i < nT * 4; i += 256) {
         const int k = i >> 2, q = i & 3;
         const int x = L.xy[k][0], y = L.xy[k][1];
-        if (x < 0) continue;
+        if (x < 0 || (WIN == YK_DR_PER_TILE && (y & YK_DR_SKIP))) continue;
         const size_t li = (size_t)((y >> 2) + ((q & 2) ? dy : 0)) * latW + (x >> 2) + ((q & 1) ? dx : 0);
         uint32_t rgb; __builtin_memcpy(&rgb, mapRGB + li * 3, 4);
         L.c[k][0][q] = (uint8_t)rgb; L.c[k][1][q] = (uint8_t)(rgb >> 8); L.c[k][2][q] = (uint8_t)(rgb >> 16);
@@ -121,7 +131,7 @@ __device__ __forceinline__ void yk_dec_render_words(DRenderLdsN<NW>& L, const ui
     for (int item = threadIdx.x; item < nT * nEl; item += 256) {
         const int ck = item >> lgPer, k = ck / 3, c = ck - 3 * k;           // tile of the list, channel
         const int x = L.xy[k][0], y = L.xy[k][1];
-        if (x < 0) continue;
+        if (x < 0 || (WIN == YK_DR_PER_TILE && (y & YK_DR_SKIP))) continue;
         const int r = item & (perCh - 1), ty = r >> lgGpr, gx = (r & (gpr - 1)) * GW;
         const uint32_t c4 = *reinterpret_cast<const uint32_t*>(&L.c[k][c][0]);
         const int TL = c4 & 255, TR = (c4 >> 8) & 255, BL = (c4 >> 16) & 255, BR = c4 >> 24;
@@ -138,12 +148,13 @@ __device__ __forceinline__ void yk_dec_render_words(DRenderLdsN<NW>& L, const ui
             *reinterpret_cast<uint2*>(o) = make_uint2(lo, hi);
         } else *reinterpret_cast<uint32_t*>(o) = lo;
     }
+    }                                                                           // WIN != YK_DR_MARKS
     // cell (cx,cy) -> byte (cx>>2) + (cy>>1)*stride4, bit ((cx>>1)&1)*4 + (cy&1)*2 + (cx&1)   (e.g. YAIK_Gradient.cpp:951-953).  A tile's
     // cells lie in at most two mask bytes (one per pair of cell rows; tiles are at most 4 cells wide and aligned to their size): one
     // atomic per byte with all of the tile's bits in it (one per CELL was 16 device-scope atomics per 16x16 tile: most of this kernel)
     for (int item = threadIdx.x; item < nT * 2; item += 256) {
         const int k = item >> 1, j = item & 1;
-        const int x = L.xy[k][0], y = L.xy[k][1];
+        const int x = L.xy[k][0], y = WIN == YK_DR_PER_TILE ? L.xy[k][1] & ~YK_DR_SKIP : L.xy[k][1];
         if (x < 0) continue;
         const int cx0 = x >> 2, cy0 = y >> 2, br = (cy0 >> 1) + j;                // byte row
         if (br > ((cy0 + dy - 1) >> 1)) continue;
@@ -169,6 +180,16 @@ __global__ __launch_bounds__(256) void yk_dec_render_kernel(const uint32_t* __re
     const uint32_t bits = bitmap[wi];
     if (!bits) return;
     yk_dec_render_word(L, wi, bits, g, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4);
+}
+
+// the same under a decode window: tiles outside the window's 64-blocks are marked, not rendered
+__global__ __launch_bounds__(256) void yk_dec_render_win_kernel(const uint32_t* __restrict__ bitmap, size_t nWords, DPassGeo g, int w, int h, int latW,
+                                                                const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes, size_t planeSize, int tileW,
+                                                                uint32_t* __restrict__ tile4, int stride4, const DWinRect wr) {
+    __shared__ DRenderLds L;
+    const uint32_t wi1[1] = { blockIdx.x }, b1[1] = { bitmap[blockIdx.x] };
+    if (!b1[0]) return;
+    yk_dec_render_words<1, YK_DR_PER_TILE>(L, wi1, b1, g, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4, wr);
 }
 
 // ---- all gradient chunks of a file in one call (yk_decode_gradient_all_device): the passes share every launch ---------------------------------
@@ -367,8 +388,12 @@ __global__ __launch_bounds__(1024) void yk_decall_scan_kernel(uint32_t* __restri
 // A later, overlapping tile still overwrites an earlier one like the reference (same workgroup, passes in order, stores of a pass acknowledged
 // before the next one starts); no lists of non-empty words are needed (an empty block costs its workgroup seven small loads), and seven dependent
 // launches of 16 us each (0.11 ms of the 0.33 ms decode of an 8192 x 8192 frame) become one.
+// WIN: under a decode window a workgroup whose block lies outside wr (the window in whole 64-blocks) only marks its tiles in tile4x4Mask, which
+// the 1-D count reads for every tile of the image; the decision is uniform over the workgroup
+template <bool WIN>
 __device__ __forceinline__ void yk_decall_render_blocks_body(const DecPlan& pl, int w, int h, int latW, const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes,
-                                                             size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4, const uint32_t blk) {
+                                                             size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4, const uint32_t blk,
+                                                             const DWinRect wr = DWinRect{ 0, 0, 0, 0 }) {
     __shared__ DRenderLdsN<8> L;
     __shared__ uint32_t s_word[7][8], s_idx[7][8];
     const int xB64 = (w + 63) >> 6;
@@ -396,6 +421,20 @@ __device__ __forceinline__ void yk_decall_render_blocks_body(const DecPlan& pl, 
         s_word[p][k] = bits; s_idx[p][k] = wi;
     }
     __syncthreads();
+    if (WIN && (bx64 * 64 < wr.x0 || bx64 * 64 >= wr.x1 || by64 * 64 < wr.y0 || by64 * 64 >= wr.y1)) {
+        bool listed = false;
+        for (int p = 0; p < pl.n; p++) {
+            uint32_t bits8[8], idx8[8], any = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) { bits8[k] = s_word[p][k]; idx8[k] = s_idx[p][k]; any |= bits8[k]; }
+            if (!any) continue;
+            if (listed) __syncthreads();                                          // the previous pass's tile list has been read
+            const DPassGeo g = yk_dpass_geo(pl.sx[p], pl.sy[p], w);
+            yk_dec_render_words<8, YK_DR_MARKS>(L, idx8, bits8, g, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4);
+            listed = true;
+        }
+        return;
+    }
     bool wrote = false;
     for (int p = 0; p < pl.n; p++) {
         uint32_t bits8[8], idx8[8], any = 0;
@@ -411,7 +450,11 @@ __device__ __forceinline__ void yk_decall_render_blocks_body(const DecPlan& pl, 
 
 __global__ __launch_bounds__(256) void yk_decall_render_blocks_kernel(const DecPlan pl, int w, int h, int latW, const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes,
                                                                       size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4) {
-    yk_decall_render_blocks_body(pl, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4, blockIdx.x);
+    yk_decall_render_blocks_body<false>(pl, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void yk_decall_render_blocks_win_kernel(const DecPlan pl, int w, int h, int latW, const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes,
+                                                                          size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4, const DWinRect wr) {
+    yk_decall_render_blocks_body<true>(pl, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4, blockIdx.x, wr);
 }
 
 // ---- the same five launches over a batch: frame = blockIdx.y -------------------------------------------------------------------------------
@@ -443,7 +486,7 @@ __global__ __launch_bounds__(1024) void yk_decall_scan_batch_kernel(const DecBat
 }
 __global__ __launch_bounds__(256) void yk_decall_render_blocks_batch_kernel(const DecBatch B, int w, int h, int latW, size_t planeSize, int tileW, int stride4) {
     const size_t f = blockIdx.y;
-    yk_decall_render_blocks_body(B.plans[f], w, h, latW, B.mapRGB + f * B.sMapRGB, B.planes + f * B.sPlanes, planeSize, tileW,
+    yk_decall_render_blocks_body<false>(B.plans[f], w, h, latW, B.mapRGB + f * B.sMapRGB, B.planes + f * B.sPlanes, planeSize, tileW,
                                  reinterpret_cast<uint32_t*>(B.tile4 + f * B.sTile4), stride4, blockIdx.x);
 }
 
@@ -602,11 +645,17 @@ __global__ __launch_bounds__(1024) void yk_dec1d_scan_kernel(uint32_t* __restric
 #ifndef YK_D1_TPL
 #define YK_D1_TPL 4
 #endif
+// WIN (a decode window, yk_decode_set_window): the lanes enumerate the window's tiles row-major, tile j of the window being tile
+// (ty0 + j / wtW) * tilesW + tx0 + j % wtW of the image; T8 is then the window's tile count.  The 64 tiles of a round no longer lie in one scan
+// block (a window row may end in one block and the next begin in another), so the two block bases are loaded per lane there.
+struct D1Win { uint32_t tx0, ty0, wtW, tilesW; };
+template <bool WIN>
 __device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offInBlk, size_t T8,
                                               const uint32_t* __restrict__ baseTiles, const uint32_t* __restrict__ basePix,
                                               const uint32_t* __restrict__ totals /*[0]=tiles,[1]=pix*/, const uint8_t* __restrict__ type, size_t typeBytes,
                                               const uint8_t* __restrict__ pix, size_t pixBytes, int invRange,
-                                              uint8_t* __restrict__ planes, size_t planeSize, int planeOverride, const uint32_t* __restrict__ runBase, const uint32_t bx) {
+                                              uint8_t* __restrict__ planes, size_t planeSize, int planeOverride, const uint32_t* __restrict__ runBase, const uint32_t bx,
+                                              const D1Win wn = D1Win{ 0, 0, 1, 0 }) {
     // planeOverride < 0: the three planes share one mask (no partial-plane pass ran): plane = blockIdx.y, its streams start at
     // plane * totals.  Otherwise one plane per launch with its own mask, streams start at runBase (tiles, pixels of the planes before it).
     const int p = planeOverride < 0 ? (int)blockIdx.y : planeOverride;
@@ -617,10 +666,16 @@ __device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offIn
     // following each other: all offset words, then all parameter bytes and stream bytes, then the arithmetic and the stores.  (Tile after tile
     // a wave made eight dependent round trips; with eight waves per SIMD and 48 waves per SIMD to run, those chains were the launch's duration.)
     uint32_t ow[YK_D1_TPL];
+    size_t ti[YK_D1_TPL];                                                       // WIN: the tile of the image that window tile j is
 #pragma unroll
     for (int rep = 0; rep < YK_D1_TPL; rep++) {
         const size_t i = ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
-        ow[rep] = i < T8 ? offInBlk[i] : 0xF0000000u;                           // past the end: a tile with nothing to decode
+        if (WIN) {
+            const uint32_t jy = (uint32_t)i / wn.wtW, jx = (uint32_t)i - jy * wn.wtW;
+            ti[rep] = i < T8 ? (size_t)(wn.ty0 + jy) * wn.tilesW + wn.tx0 + jx : 0;
+            ow[rep] = i < T8 ? offInBlk[ti[rep]] : 0xF0000000u;
+        } else
+            ow[rep] = i < T8 ? offInBlk[i] : 0xF0000000u;                       // past the end: a tile with nothing to decode
     }
     int tb[YK_D1_TPL]; uint4 L[YK_D1_TPL]; bool coded[YK_D1_TPL], live[YK_D1_TPL];
 #pragma unroll
@@ -628,8 +683,8 @@ __device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offIn
         const int q = (int)(ow[rep] >> 28);
         const int qh = (q >> (half * 2)) & 3;                                    // bit 0: left quadrant filled, bit 1: right
         // the 64 tiles of a workgroup's round lie in one scan block: its two bases are scalar loads
-        const size_t blk = (((size_t)bx * YK_D1_TPL + rep) * 64) >> 10;
-        const bool inRange = (((size_t)bx * YK_D1_TPL + rep) * 64) < T8;
+        const size_t blk = WIN ? ti[rep] >> 10 : (((size_t)bx * YK_D1_TPL + rep) * 64) >> 10;
+        const bool inRange = WIN ? ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2) < T8 : (((size_t)bx * YK_D1_TPL + rep) * 64) < T8;
         const uint32_t offT = (inRange ? baseTiles[blk] : 0u) + (ow[rep] & 2047u), offP = (inRange ? basePix[blk] : 0u) + ((ow[rep] >> 11) & 0x1FFFFu);
         const int nTop = 2 - (q & 1) - ((q >> 1) & 1);
         const size_t to = (baseT + offT) * 3;
@@ -651,7 +706,7 @@ __device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offIn
     }
 #pragma unroll
     for (int rep = 0; rep < YK_D1_TPL; rep++) {
-        const size_t i = ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
+        const size_t i = WIN ? ti[rep] : ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
         const int q = (int)(ow[rep] >> 28);
         const int qh = (q >> (half * 2)) & 3;
         const int color0 = __builtin_amdgcn_update_dpp(0, tb[rep], 0x00, 0xF, 0xF, true), base = __builtin_amdgcn_update_dpp(0, tb[rep], 0x55, 0xF, 0xF, true),
@@ -692,7 +747,14 @@ __global__ __launch_bounds__(256) void yk_dec1d_kernel(const uint32_t* __restric
                                                        const uint32_t* __restrict__ totals /*[0]=tiles,[1]=pix*/, const uint8_t* __restrict__ type, size_t typeBytes,
                                                        const uint8_t* __restrict__ pix, size_t pixBytes, int invRange,
                                                        uint8_t* __restrict__ planes, size_t planeSize, int planeOverride, const uint32_t* __restrict__ runBase) {
-    yk_dec1d_body(offInBlk, T8, baseTiles, basePix, totals, type, typeBytes, pix, pixBytes, invRange, planes, planeSize, planeOverride, runBase, blockIdx.x);
+    yk_dec1d_body<false>(offInBlk, T8, baseTiles, basePix, totals, type, typeBytes, pix, pixBytes, invRange, planes, planeSize, planeOverride, runBase, blockIdx.x);
+}
+// the shared-mask mode (plane = blockIdx.y) over the tiles of a decode window; nWin = its tile count
+__global__ __launch_bounds__(256) void yk_dec1d_win_kernel(const uint32_t* __restrict__ offInBlk, size_t nWin, const D1Win wn,
+                                                           const uint32_t* __restrict__ baseTiles, const uint32_t* __restrict__ basePix,
+                                                           const uint32_t* __restrict__ totals, const uint8_t* __restrict__ type, size_t typeBytes,
+                                                           const uint8_t* __restrict__ pix, size_t pixBytes, int invRange, uint8_t* __restrict__ planes, size_t planeSize) {
+    yk_dec1d_body<true>(offInBlk, nWin, baseTiles, basePix, totals, type, typeBytes, pix, pixBytes, invRange, planes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x, wn);
 }
 
 // ---- the 1-D chunk over a batch: the same three launches, frame = blockIdx.y (count), blockIdx.x (scan: one workgroup per frame), blockIdx.z
@@ -718,7 +780,7 @@ __global__ __launch_bounds__(1024) void yk_dec1d_scan_batch_kernel(const D1Batch
 __global__ __launch_bounds__(256) void yk_dec1d_batch_kernel(const D1Batch B, size_t T8, int invRange, size_t planeSize) {
     const size_t f = blockIdx.z;
     const D1Frame& fr = B.frames[f];
-    yk_dec1d_body(yk_d1batch_u32(B, f, B.oOff), T8, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oTot), fr.type, (size_t)fr.typeBytes,
+    yk_dec1d_body<false>(yk_d1batch_u32(B, f, B.oOff), T8, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oTot), fr.type, (size_t)fr.typeBytes,
                   fr.pix, (size_t)fr.pixBytes, invRange, B.planes + f * B.sPlanes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x);
 }
 
@@ -798,6 +860,10 @@ __device__ __forceinline__ void yk_dt_emit(uint8_t* o, size_t planeBytes, uint32
 
 struct YkDtUnit { yk_dt4 r, g, b; uint32_t a[4]; size_t o; };
 
+// A decode window (yk_decode_set_window) in tiles: tile (tx0 + jx, ty0 + jy) of the planes goes to pixel (8 jx, 8 jy) of the destination.  The
+// window forms walk the window's wtW x wtH tiles row-major (a.nTiles = their count; a.alpha points at the window's first alpha byte).
+struct YkDetileWin { uint32_t tx0, ty0, wtW; };
+
 template <int C, bool PLANAR, int ASRC>
 __device__ __forceinline__ void yk_dt_load(const YkDetileArgs& a, uint32_t t, uint32_t rp, YkDtUnit& u) {
     const size_t ti = (size_t)t * 64 + rp * 16;
@@ -806,6 +872,21 @@ __device__ __forceinline__ void yk_dt_load(const YkDetileArgs& a, uint32_t t, ui
     u.b = *reinterpret_cast<const yk_dt4*>(a.planes + 2 * a.planeSize + ti);
     const uint32_t ty = t / a.tileW, tx = t - ty * a.tileW;
     const size_t y = (size_t)ty * 8 + rp * 2, x = (size_t)tx * 8;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) {
+        __builtin_memcpy(&u.a[0], a.alpha + y * a.strideA + x, 8);
+        __builtin_memcpy(&u.a[2], a.alpha + (y + 1) * a.strideA + x, 8);
+    }
+    u.o = y * a.rowBytes + x * (PLANAR ? 1 : C);
+}
+// window tile j = (jx, jy): the planes are read at tile (tx0 + jx, ty0 + jy), alpha and destination are addressed by (jx, jy)
+template <int C, bool PLANAR, int ASRC>
+__device__ __forceinline__ void yk_dt_load_win(const YkDetileArgs& a, const YkDetileWin& wn, uint32_t j, uint32_t rp, YkDtUnit& u) {
+    const uint32_t jy = j / wn.wtW, jx = j - jy * wn.wtW;
+    const size_t ti = ((size_t)(wn.ty0 + jy) * a.tileW + wn.tx0 + jx) * 64 + rp * 16;
+    u.r = *reinterpret_cast<const yk_dt4*>(a.planes + ti);
+    u.g = *reinterpret_cast<const yk_dt4*>(a.planes + a.planeSize + ti);
+    u.b = *reinterpret_cast<const yk_dt4*>(a.planes + 2 * a.planeSize + ti);
+    const size_t y = (size_t)jy * 8 + rp * 2, x = (size_t)jx * 8;
     if constexpr (ASRC == YK_DT_ALPHA_PLANE) {
         __builtin_memcpy(&u.a[0], a.alpha + y * a.strideA + x, 8);
         __builtin_memcpy(&u.a[2], a.alpha + (y + 1) * a.strideA + x, 8);
@@ -849,6 +930,27 @@ template <int C, bool PLANAR, int ASRC>
 __global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_kernel(YkDetileArgs a) {
     yk_dec_detile_body<C, PLANAR, ASRC>(a, blockIdx.x);
 }
+// the window form: the same lanes and steps over the window's tiles (a row of the window is contiguous in the planes, rows are tileW tiles apart)
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_win_kernel(YkDetileArgs a, const YkDetileWin wn) {
+    const uint32_t lane = threadIdx.x & 63, rp = lane & 3;
+    const uint32_t j0 = (blockIdx.x * (YK_DT_K * 4) + (threadIdx.x >> 6)) * 16 + (lane >> 2);
+    if ((blockIdx.x + 1) * (uint32_t)YK_DT_TILES <= a.nTiles) {
+        YkDtUnit u[YK_DT_K];
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) yk_dt_load_win<C, PLANAR, ASRC>(a, wn, j0 + k * 64, rp, u[k]);
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) yk_dt_store<C, PLANAR, ASRC>(a, u[k]);
+        return;
+    }
+    for (int k = 0; k < YK_DT_K; k++) {
+        const uint32_t j = j0 + k * 64;
+        if (j >= a.nTiles) continue;
+        YkDtUnit u;
+        yk_dt_load_win<C, PLANAR, ASRC>(a, wn, j, rp, u);
+        yk_dt_store<C, PLANAR, ASRC>(a, u);
+    }
+}
 // a batch: frame blockIdx.y's planes at a.planes + f * planesFrame, its pixels at a.out + f * outFrame
 // (YK_DT_ALPHA_PLANE: its alpha plane at a.alpha + f * alphaFrame, the planes of yk_decode_alpha_batch_device)
 template <int C, bool PLANAR, int ASRC>
@@ -860,8 +962,10 @@ __global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_batch_kernel(YkDe
 
 // nFrames == 0: the selected frame (the existing single-image launch); otherwise nFrames frames, planesFrame / outFrame bytes apart
 template <int C, bool PLANAR, int ASRC>
-static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, size_t planesFrame = 0, size_t outFrame = 0, size_t alphaFrame = 0) {
+static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, size_t planesFrame = 0, size_t outFrame = 0, size_t alphaFrame = 0,
+                         const YkDetileWin* wn = nullptr) {
     const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
+    if (wn) { hipLaunchKernelGGL((yk_dec_detile_win_kernel<C, PLANAR, ASRC>), dim3(gx), dim3(YK_DT_THREADS), 0, s, a, *wn); return; }
     if (nFrames) { hipLaunchKernelGGL((yk_dec_detile_batch_kernel<C, PLANAR, ASRC>), dim3(gx, (unsigned)nFrames), dim3(YK_DT_THREADS), 0, s, a, planesFrame, outFrame, alphaFrame); return; }
     hipLaunchKernelGGL((yk_dec_detile_kernel<C, PLANAR, ASRC>), dim3(gx), dim3(YK_DT_THREADS), 0, s, a);
 }
@@ -869,19 +973,26 @@ static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, 
 // the de-tile of the image begun on c into out; alpha: a plane (strideA bytes per row) or NULL with alphaConst 0..255 (channels 4)
 // frameBytes / nFrames: every frame of a batch in one launch, frame f at out + f * frameBytes, its alpha plane (if any) at alpha + f * alphaFrame;
 // nFrames == 0: the selected frame
+// window: the window set on c (yk_decode_set_window) into a ww x wh destination, alpha read at the window's offset (single image only)
 static int yk_dec_detile(yk_ctx* c, uint8_t* out, size_t rowBytes, size_t planeBytes, int channels, const uint8_t* alpha, size_t strideA, int alphaConst,
-                         int nFrames = 0, size_t frameBytes = 0, size_t alphaFrame = 0) {
+                         int nFrames = 0, size_t frameBytes = 0, size_t alphaFrame = 0, bool window = false) {
     YkDetileArgs a;
     a.planes = yk_dec_frame(c, nFrames ? 0 : c->dCur).planes; a.planeSize = c->dPlaneSize;
     const size_t pf = c->dStride.planes;
     a.alpha = alpha; a.strideA = strideA; a.alphaConst = (uint32_t)(alphaConst & 255) * 0x01010101u;
     a.out = out; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
     a.tileW = (uint32_t)(c->dw >> 3); a.nTiles = (uint32_t)(c->dw >> 3) * (uint32_t)(c->dh >> 3);
+    const YkDetileWin win = { (uint32_t)(c->dWinX >> 3), (uint32_t)(c->dWinY >> 3), (uint32_t)(c->dWinW >> 3) };
+    const YkDetileWin* wn = window ? &win : nullptr;
+    if (window) {
+        a.nTiles = (uint32_t)(c->dWinW >> 3) * (uint32_t)(c->dWinH >> 3);
+        if (alpha) a.alpha = alpha + (size_t)c->dWinY * strideA + (size_t)c->dWinX;
+    }
     const bool planar = planeBytes > 0;
     { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
-    if (channels == 3) { if (planar) yk_dt_launch<3, true, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes); else yk_dt_launch<3, false, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes); }
-    else if (alpha)    { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_PLANE>(a, c->stream, nFrames, pf, frameBytes, alphaFrame); else yk_dt_launch<4, false, YK_DT_ALPHA_PLANE>(a, c->stream, nFrames, pf, frameBytes, alphaFrame); }
-    else               { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes); else yk_dt_launch<4, false, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes); }
+    if (channels == 3) { if (planar) yk_dt_launch<3, true, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes, 0, wn); else yk_dt_launch<3, false, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes, 0, wn); }
+    else if (alpha)    { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_PLANE>(a, c->stream, nFrames, pf, frameBytes, alphaFrame, wn); else yk_dt_launch<4, false, YK_DT_ALPHA_PLANE>(a, c->stream, nFrames, pf, frameBytes, alphaFrame, wn); }
+    else               { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes, 0, wn); else yk_dt_launch<4, false, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes, 0, wn); }
     YK_HIP(c, hipGetLastError());
     return yk_stage_end(c, YK_STAGE_DEC_DETILE);
 }
@@ -903,11 +1014,9 @@ static int yk_dec_scratch(yk_ctx* c, size_t bytes) { YK_HIP(c, c->dScratch.reser
 extern "C" {
 
 // zero every 4x4 cell tile4x4Mask does not mark (thread = 8x8 tile and plane; the mask is shared by the planes until a plane-subset pass splits it)
-__device__ __forceinline__ void yk_dec_zero_unmarked_body(const uint8_t* __restrict__ tile4, size_t tile4Size, int split, int stride4, int tilesW, size_t T8,
+__device__ __forceinline__ void yk_dec_zero_unmarked_tile(const uint8_t* __restrict__ tile4, size_t tile4Size, int split, int stride4, int tilesW, const size_t i,
                                                           uint8_t* __restrict__ planes, size_t planeSize) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int p = blockIdx.y;
-    if (i >= T8) return;
     const int tx = (int)(i % (size_t)tilesW), ty = (int)(i / (size_t)tilesW);
     const uint8_t m = tile4[(split ? (size_t)p * tile4Size : 0) + (size_t)(tx >> 1) + (size_t)ty * stride4];     // byte = 16x8 pixels: bit ((cx>>1)&1)*4 + (cy&1)*2 + (cx&1)
     const int sh = (tx & 1) * 4;
@@ -918,6 +1027,19 @@ __device__ __forceinline__ void yk_dec_zero_unmarked_body(const uint8_t* __restr
         for (int qx = 0; qx < 2; qx++)
             if (!((m >> (sh + qy * 2 + qx)) & 1))
                 for (int r = 0; r < 4; r++) *reinterpret_cast<uint32_t*>(o + (qy * 4 + r) * 8 + qx * 4) = 0u;
+}
+__device__ __forceinline__ void yk_dec_zero_unmarked_body(const uint8_t* __restrict__ tile4, size_t tile4Size, int split, int stride4, int tilesW, size_t T8,
+                                                          uint8_t* __restrict__ planes, size_t planeSize) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < T8) yk_dec_zero_unmarked_tile(tile4, tile4Size, split, stride4, tilesW, i, planes, planeSize);
+}
+// under a decode window: the window's tiles only (thread j of nWin = window tile (j % wtW, j / wtW)); outside it the planes are nobody's to read
+__global__ __launch_bounds__(256) void yk_dec_zero_unmarked_win_kernel(const uint8_t* __restrict__ tile4, size_t tile4Size, int split, int stride4, int tilesW,
+                                                                       uint32_t tx0, uint32_t ty0, uint32_t wtW, uint32_t nWin, uint8_t* __restrict__ planes, size_t planeSize) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nWin) return;
+    const uint32_t jy = j / wtW, jx = j - jy * wtW;
+    yk_dec_zero_unmarked_tile(tile4, tile4Size, split, stride4, tilesW, (size_t)(ty0 + jy) * tilesW + tx0 + jx, planes, planeSize);
 }
 __global__ __launch_bounds__(256) void yk_dec_zero_unmarked_kernel(const uint8_t* __restrict__ tile4, size_t tile4Size, int split, int stride4, int tilesW, size_t T8,
                                                                    uint8_t* __restrict__ planes, size_t planeSize) {
@@ -932,7 +1054,11 @@ static int yk_dec_settle(yk_ctx* c) {
     if (!c->dPlanesStale) return YK_OK;
     const int w = c->dw, h = c->dh;
     const size_t T8 = (size_t)(w >> 3) * (h >> 3);
-    if (c->dFrames == 1)
+    if (c->dWinSet) {                                                           // a window is a single image's
+        const uint32_t wtW = (uint32_t)(c->dWinW >> 3), nWin = wtW * (uint32_t)(c->dWinH >> 3);
+        hipLaunchKernelGGL(yk_dec_zero_unmarked_win_kernel, dim3((nWin + 255) / 256, 3), dim3(256), 0, c->stream, c->dB.tile4, c->dTile4Size, c->dSplit ? 1 : 0,
+                           (w + 15) >> 4, w >> 3, (uint32_t)(c->dWinX >> 3), (uint32_t)(c->dWinY >> 3), wtW, nWin, c->dB.planes, c->dPlaneSize);
+    } else if (c->dFrames == 1)
         hipLaunchKernelGGL(yk_dec_zero_unmarked_kernel, dim3((unsigned)((T8 + 255) / 256), 3), dim3(256), 0, c->stream, c->dB.tile4, c->dTile4Size, c->dSplit ? 1 : 0,
                            (w + 15) >> 4, w >> 3, T8, c->dB.planes, c->dPlaneSize);
     else                                                                        // the flag is the handle's: what it says holds for every frame
@@ -994,6 +1120,7 @@ static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
         c->dw = w; c->dh = h; c->dFrames = nFrames;
     }
     c->dCur = 0;
+    c->dWinSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; c->dChunkSeen = false; c->dBatchBegun = false;
     // The planes (3 B per pixel: 201 MB at 8192 x 8192, 40 us of every frame) are NOT cleared: every renderer marks what it writes in tile4x4Mask and
     // the 1-D decode writes every unmarked quadrant, so after a whole file nothing stale is left; a flow that stops earlier (or writes without
     // marking: the plane-subset loops) gets the unmarked cells zeroed when it needs them (yk_dec_settle).
@@ -1014,7 +1141,29 @@ int yk_decode_begin(yk_ctx* c, int w, int h) {
 int yk_decode_begin_batch(yk_ctx* c, int w, int h, int nFrames) {
     if (!c) return YK_ERR_BAD_ARG;
     if (nFrames < 1 || nFrames > 1024) return yk_refuse(c, YK_ERR_BAD_ARG, "nFrames must be 1..1024");
-    return yk_dec_begin(c, w, h, nFrames);
+    const int rc = yk_dec_begin(c, w, h, nFrames);
+    if (rc == YK_OK) c->dBatchBegun = true;
+    return rc;
+}
+
+// The window of the image begun by yk_decode_begin: from here on the decode calls owe the planes only the pixels inside it (include/yaik_hip.h)
+int yk_decode_set_window(yk_ctx* c, int x0, int y0, int ww, int wh) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window: yk_decode_begin first");
+    if (c->dBatchBegun || c->dFrames > 1) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window: a window belongs to a single image (yk_decode_begin), not to a batch");
+    if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window: a chunk of this image has been decoded already; set the window right after yk_decode_begin");
+    if (ww == 0 && wh == 0) { c->dWinSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; return YK_OK; }
+    if (((x0 | y0 | ww | wh) & 7) || x0 < 0 || y0 < 0 || ww < 8 || wh < 8 || x0 > c->dw - ww || y0 > c->dh - wh)
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_window: x0, y0, ww, wh must be multiples of 8 with ww, wh >= 8 and the window inside the image");
+    c->dWinX = x0; c->dWinY = y0; c->dWinW = ww; c->dWinH = wh; c->dWinSet = true;
+    return YK_OK;
+}
+// the window rounded out to 64-pixel blocks, clipped to the image: what the gradient render fills
+static DWinRect yk_dec_win_rect(const yk_ctx* c) {
+    DWinRect r = { c->dWinX & ~63, c->dWinY & ~63, (c->dWinX + c->dWinW + 63) & ~63, (c->dWinY + c->dWinH + 63) & ~63 };
+    if (r.x1 > c->dw) r.x1 = c->dw;
+    if (r.y1 > c->dh) r.y1 = c->dh;
+    return r;
 }
 
 int yk_decode_select_frame(yk_ctx* c, int frame) {
@@ -1107,6 +1256,7 @@ static int yk_decode_gradient_impl(yk_ctx* c, int sx, int sy, const uint8_t* bit
     if (!need) return yk_fail(c, YK_ERR_BAD_ARG, "unsupported tile format");
     YK_HIP(c, hipSetDevice(c->device));
     if (bitmapBytes < need) return yk_fail(c, YK_ERR_RANGE, "tile bitmap shorter than the image needs");
+    c->dChunkSeen = true;
     const DPassGeo g = yk_dpass_geo(sx, sy, w);
     DPassIn in;
     YK_HIP(c, yk_dpass_stage(c, bitmap, need, rgb, rgbBytes, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, onDevice ? remapRange : 0, &in));
@@ -1117,8 +1267,12 @@ static int yk_decode_gradient_impl(yk_ctx* c, int sx, int sy, const uint8_t* bit
     hipLaunchKernelGGL(yk_u32_scanblocks_kernel, dim3(1), dim3(1024), 0, c->stream, in.blockSums, (int)in.nb, in.total);
     hipLaunchKernelGGL(yk_dec_corner_kernel<true>, dim3((unsigned)in.nb), dim3(1024), 0, c->stream, in.bm, in.nBits, g, w, h, latW, V.loaded, V.owner,
                        in.blockSums, in.rgb, rgbBytes, V.mapRGB);
-    hipLaunchKernelGGL(yk_dec_render_kernel, dim3((unsigned)in.nWords), dim3(256), 0, c->stream, in.bm, in.nWords, g, w, h, latW, V.mapRGB, V.planes, c->dPlaneSize,
-                       w >> 3, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4);
+    if (c->dWinSet)
+        hipLaunchKernelGGL(yk_dec_render_win_kernel, dim3((unsigned)in.nWords), dim3(256), 0, c->stream, in.bm, in.nWords, g, w, h, latW, V.mapRGB, V.planes, c->dPlaneSize,
+                           w >> 3, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4, yk_dec_win_rect(c));
+    else
+        hipLaunchKernelGGL(yk_dec_render_kernel, dim3((unsigned)in.nWords), dim3(256), 0, c->stream, in.bm, in.nWords, g, w, h, latW, V.mapRGB, V.planes, c->dPlaneSize,
+                           w >> 3, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
     { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
     if (!onDevice) YK_HIP(c, hipStreamSynchronize(c->stream));            // the host buffers may be reused by the caller
@@ -1161,6 +1315,7 @@ int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX,
         return YK_OK;
     }
     YK_HIP(c, hipSetDevice(c->device));
+    c->dChunkSeen = true;
     DecPlan pl = {};
     yk_dplan_shape(pl, nPasses, tileShiftX, tileShiftY, need);
     for (int p = 0; p < nPasses; p++) { pl.bm[p] = devBitmap[p]; pl.rgb[p] = devRgb[p]; pl.rgbBytes[p] = (uint32_t)rgbBytes[p]; }
@@ -1179,8 +1334,12 @@ int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX,
     hipLaunchKernelGGL(yk_decall_stream_kernel<true>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, V.loaded, V.owner, blockSums, perThread,
                        V.mapRGB, yk_dec_remap_factor(remapRange));
     // the render: a workgroup per 64x64 block of the image walks the passes in call order
-    hipLaunchKernelGGL(yk_decall_render_blocks_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64))), dim3(256), 0, c->stream, pl, w, h, latW,
-                       V.mapRGB, V.planes, c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4);
+    if (c->dWinSet)
+        hipLaunchKernelGGL(yk_decall_render_blocks_win_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64))), dim3(256), 0, c->stream, pl, w, h, latW,
+                           V.mapRGB, V.planes, c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4, yk_dec_win_rect(c));
+    else
+        hipLaunchKernelGGL(yk_decall_render_blocks_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64))), dim3(256), 0, c->stream, pl, w, h, latW,
+                           V.mapRGB, V.planes, c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
     { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
     return YK_OK;
@@ -1260,6 +1419,7 @@ int yk_decode_split_masks(yk_ctx* c) {
     YK_DEC_NO_BATCH(c, "yk_decode_split_masks");
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_HIP(c, hipSetDevice(c->device));
+    c->dChunkSeen = true;
     return yk_dec_split(c);
 }
 
@@ -1271,6 +1431,7 @@ int yk_decode_gradient_planes(yk_ctx* c, int planeBit, int consistentMarks, cons
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     const YkDecView V = yk_dec_frame(c);
     YK_HIP(c, hipSetDevice(c->device));
+    c->dChunkSeen = true;
     { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }               // the plane-subset loops write without marking (reference behaviour): from here on the planes are fully defined
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
     const size_t lat = (size_t)latW * (h / 4 + 1);
@@ -1301,6 +1462,7 @@ static int yk_decode_1d_impl(yk_ctx* c, const uint8_t* typeStream, size_t typeBy
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     const YkDecView V = yk_dec_frame(c);
     YK_HIP(c, hipSetDevice(c->device));
+    c->dChunkSeen = true;
     // dPlanesStale is the handle's: this call writes the unmarked quadrants of the SELECTED frame only, so on a batch the other frames get theirs zeroed first
     if (c->dFrames > 1) { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
     const int w = c->dw, h = c->dh, tilesW = w >> 3;
@@ -1325,8 +1487,15 @@ static int yk_decode_1d_impl(yk_ctx* c, const uint8_t* typeStream, size_t typeBy
         // no partial-plane pass ran: the three planes share one mask, one count / scan serves all of them (3 launches)
         hipLaunchKernelGGL(yk_dec1d_count_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, V.tile4, (w + 15) >> 4, tilesW, T8, bT, bP, offInBlk);
         hipLaunchKernelGGL(yk_dec1d_scan_kernel, dim3(1), dim3(1024), 0, c->stream, bT, bP, (int)nb, tot);
-        hipLaunchKernelGGL(yk_dec1d_kernel, dim3(gTiles, 3), dim3(256), 0, c->stream, (const uint32_t*)offInBlk, T8, bT, bP, tot,
-                           tyS, typeBytes, pxS, pixBytes, (1 << 24) / compressionRange, V.planes, c->dPlaneSize, -1, (const uint32_t*)nullptr);
+        if (c->dWinSet) {
+            // count and scan stay whole (stream offsets are prefix sums over every tile of the image); only the window's tiles are decoded
+            const D1Win wn = { (uint32_t)(c->dWinX >> 3), (uint32_t)(c->dWinY >> 3), (uint32_t)(c->dWinW >> 3), (uint32_t)tilesW };
+            const size_t nWin = (size_t)(c->dWinW >> 3) * (c->dWinH >> 3);
+            hipLaunchKernelGGL(yk_dec1d_win_kernel, dim3((unsigned)((nWin + 64 * YK_D1_TPL - 1) / (64 * YK_D1_TPL)), 3), dim3(256), 0, c->stream, (const uint32_t*)offInBlk, nWin, wn,
+                               bT, bP, tot, tyS, typeBytes, pxS, pixBytes, (1 << 24) / compressionRange, V.planes, c->dPlaneSize);
+        } else
+            hipLaunchKernelGGL(yk_dec1d_kernel, dim3(gTiles, 3), dim3(256), 0, c->stream, (const uint32_t*)offInBlk, T8, bT, bP, tot,
+                               tyS, typeBytes, pxS, pixBytes, (1 << 24) / compressionRange, V.planes, c->dPlaneSize, -1, (const uint32_t*)nullptr);
     } else {
         // per-plane masks (Decompress1D reads tile4x4Mask + planeID * tile4x4MaskSize, YAIK_3DTile.cpp:41): one plane after the other,
         // every plane's streams start where the plane before it stopped
@@ -1432,6 +1601,7 @@ static int yk_decode_output_impl(yk_ctx* c, uint8_t* hostOut, size_t outputImage
                                  const uint8_t* devAlpha = nullptr) {
     if (!c || !hostOut) return YK_ERR_BAD_ARG;
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    YK_DEC_NO_WINDOW(c, "yk_decode_output / yk_decode_output_alpha / yk_decode_output_reference_rgba");
     if (devAlpha) { hostAlpha = devAlpha; strideA = c->dw; }                   // the plane yk_decode_alpha left in HBM: no host copy
     const int w = c->dw, h = c->dh, bpp = (hostAlpha && !refRGBA) ? 4 : 3;
     const size_t rowBytes = (size_t)w * bpp + (refRGBA && hostAlpha ? 1 : 0);
@@ -1460,6 +1630,7 @@ int yk_decode_output(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride, cons
 int yk_decode_output_alpha(yk_ctx* c, uint8_t* hostOut, size_t outputImageStride) {
     if (!c) return YK_ERR_BAD_ARG;
     YK_DEC_NO_BATCH(c, "yk_decode_output_alpha");
+    YK_DEC_NO_WINDOW(c, "yk_decode_output_alpha");
     if (!c->dAlphaValid) return yk_fail(c, YK_ERR_STATE, "yk_decode_alpha first");
     return yk_decode_output_impl(c, hostOut, outputImageStride, nullptr, 0, false, yk_dec_alpha_cur(c));
 }
@@ -1470,20 +1641,31 @@ int yk_decode_output_reference_rgba(yk_ctx* c, uint8_t* hostOut, size_t outputIm
     return yk_decode_output_impl(c, hostOut, outputImageStride, hostAlpha, strideA, true);
 }
 
-int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha) {
-    if (!c) return YK_ERR_BAD_ARG;
+// yk_decode_output_device and yk_decode_output_window_device: the same checks against the size of what is written
+static int yk_dec_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha, bool window) {
     if (!devOut) return yk_fail(c, YK_ERR_BAD_ARG, "devOut is NULL");
     if (channels != 3 && channels != 4) return yk_fail(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
     if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_fail(c, YK_ERR_BAD_ARG, "alpha must be -1 (the decoded plane) or 0..255");
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
-    const size_t w = (size_t)c->dw, h = (size_t)c->dh;
+    const size_t w = (size_t)(window ? c->dWinW : c->dw), h = (size_t)(window ? c->dWinH : c->dh);
     if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
-        return yk_fail(c, YK_ERR_BAD_ARG, "row or plane pitch too small for the image");
+        return yk_fail(c, YK_ERR_BAD_ARG, window ? "row or plane pitch too small for the window" : "row or plane pitch too small for the image");
     const bool fromPlane = channels == 4 && alpha < 0;
     if (fromPlane && !c->dAlphaValid) return yk_fail(c, YK_ERR_STATE, "alpha = -1 needs yk_decode_alpha first");
     YK_HIP(c, hipSetDevice(c->device));
     { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
-    return yk_dec_detile(c, devOut, rowBytes, planeBytes, channels, fromPlane ? yk_dec_alpha_cur(c) : nullptr, w, fromPlane ? 0 : alpha);
+    return yk_dec_detile(c, devOut, rowBytes, planeBytes, channels, fromPlane ? yk_dec_alpha_cur(c) : nullptr, (size_t)c->dw, fromPlane ? 0 : alpha, 0, 0, 0, window);
+}
+
+int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    YK_DEC_NO_WINDOW(c, "yk_decode_output_device");
+    return yk_dec_output_device(c, devOut, rowBytes, planeBytes, channels, alpha, false);
+}
+
+int yk_decode_output_window_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    return yk_dec_output_device(c, devOut, rowBytes, planeBytes, channels, alpha, c->dWinSet);
 }
 
 int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha) {
@@ -1524,6 +1706,7 @@ static int yk_dec_compare_common(yk_ctx* c, int channels, const void* out, bool 
     if (!out) return yk_refuse(c, YK_ERR_BAD_ARG, "out is NULL");
     if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
+    YK_DEC_NO_WINDOW(c, "yk_decode_compare_*");
     if (channels == 4 && !c->dAlphaValid)
         return yk_refuse(c, YK_ERR_STATE, "channels = 4 needs the decoded alpha: yk_decode_alpha or yk_decode_alpha_batch_device first");
     return YK_OK;

@@ -1041,6 +1041,7 @@ int yk_decode_lut3d(yk_ctx* c, const uint8_t* const maps[6], const size_t mapByt
     if (!c->lutDec) return yk_fail(c, YK_ERR_STATE, "yk_decode_assign_lut first");
     if (c->dSplit) return yk_fail(c, YK_ERR_STATE, "a '3DTL' chunk comes before the masks are split ('1DTL', plane-subset chunks)");
     YK_HIP(c, hipSetDevice(c->device));
+    c->dChunkSeen = true;                                                       // a window (yk_decode_set_window) is ignored here: the chunk writes the whole image
     const int w = c->dw, h = c->dh;
     static const int sz[6][2] = { {4,3}, {3,4}, {3,3}, {3,2}, {2,3}, {2,2} };
     YkBuf<uint16_t> dTiles; YkBuf<uint8_t> dColors, dIdx[4], dMapBytes; YkBuf<uint32_t> sums;   // temporaries of this call

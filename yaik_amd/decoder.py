@@ -137,6 +137,7 @@ class HipTileDecoder:
         self._batch_stage = None         # torch buffers a queued batch decode may still read: the staging tensor of host streams ...
         self._batch_streams = None       # ... and the copy of an encoder's per-handle streams (encoder_batch_streams)
         self._alpha_stage = None         # ... and the staging tensor of decompress_alpha_batch's host payloads
+        self._window = None              # set_window: (x0, y0, w, h) of the image begun, None = the whole image
 
     def close(self):
         if getattr(self, "_h", None):
@@ -149,7 +150,31 @@ class HipTileDecoder:
     def begin(self, w: int, h: int):
         self.w, self.h, self.frames = w, h, 1
         self._has_alpha = self._alpha_batch = False
+        self._window = None                                                # yk_decode_begin always clears the window
         _chk(self._h, lib().yk_decode_begin(self._h, w, h))
+
+    # ---- windows: decode only the tiles a rectangle of the image needs (yk_decode_set_window) -----------------------------------
+    @property
+    def window(self):
+        """(x0, y0, w, h) of the window set on the image begun, None when the decode is of the whole image (always after begin)."""
+        return self._window
+
+    def set_window(self, x0: int, y0: int, w: int, h: int) -> None:
+        """From here on the decode calls of this image owe only the pixels of the rectangle (x0, y0, w, h): the gradient render skips the 64x64
+        blocks it does not touch and the 1-D chunk decodes its tiles only.  Call it right after begin(), before any chunk is decoded; x0, y0, w, h
+        are multiples of 8 with w, h >= 8 inside the image; (0, 0, 0, 0) clears the window.  Read the result with image_window_device(); image(),
+        image_device() and the compare calls raise the library's state error while a window is set, planes() is exact inside the window only,
+        tile4x4() is whole and exact.  Bad arguments raise before any library call; a batch, or chunks decoded already, are the library's to
+        refuse."""
+        v = (x0, y0, w, h)
+        if any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) for a in v):
+            raise TypeError(f"window (x0, y0, w, h) must be four ints; got {v!r}")
+        x0, y0, w, h = (int(a) for a in v)
+        clear = w == 0 and h == 0 and x0 == 0 and y0 == 0
+        if not clear and ((x0 | y0 | w | h) & 7 or x0 < 0 or y0 < 0 or w < 8 or h < 8 or x0 + w > self.w or y0 + h > self.h):
+            raise ValueError(f"window {(x0, y0, w, h)}: x0, y0, w, h must be multiples of 8 with w, h >= 8, inside the {self.w} x {self.h} image")
+        _chk(self._h, lib().yk_decode_set_window(self._h, x0, y0, w, h))
+        self._window = None if clear else (x0, y0, w, h)
 
     # ---- batches: n images of one shape, every kernel launched once over all of them (yk_decode_begin_batch) --------------------------------
     def begin_batch(self, w: int, h: int, n: int):
@@ -158,6 +183,7 @@ class HipTileDecoder:
         _chk(self._h, lib().yk_decode_begin_batch(self._h, w, h, n))
         self.w, self.h, self.frames = w, h, n
         self._has_alpha = self._alpha_batch = False
+        self._window = None
 
     def select_frame(self, f: int):
         _chk(self._h, lib().yk_decode_select_frame(self._h, f))
@@ -656,19 +682,32 @@ class HipTileDecoder:
         """RGB rows into a caller-owned [h, stride] uint8 array (no allocation per call)."""
         _chk(self._h, lib().yk_decode_output(self._h, out.ctypes.data, out.shape[1], None, 0))
 
+    def image_window_device(self, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
+        """image_device() for the window set by set_window (yk_decode_output_window_device): the window's pixels as a torch.uint8 tensor
+        [wh, ww, C], or [C, wh, ww] with planar=True, equal to the same slice of the whole decode's image_device().  channels, alpha, `out`
+        (any view with unit inner strides and any pitch, of the window's shape) and the stream hand-over are those of image_device; a decoded
+        'ALPM' plane is read at the window's offset.  Without a window the call is image_device()."""
+        return self._image_device(lib().yk_decode_output_window_device, self._window, out, channels, alpha, planar)
+
     def image_device(self, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
         """The decoded image as 8-bit pixels in a torch.uint8 tensor on the handle's device (yk_decode_output_device): [h, w, C], or
         [C, h, w] with planar=True.  channels defaults to 4 when an 'ALPM' plane was decoded, else 3 (as in image()).  With 4 channels,
         alpha=None takes the decoded plane when there is one and 255 otherwise; an int 0..255 is a constant alpha.  `out` may be any view with
         unit inner strides and any row or plane pitch (frames[f] of a batch, row-padded slices): only its pixel bytes are written.
         No host fence: the handle's stream waits for torch's current stream before the write, and torch's current stream waits for the
-        write after it, so torch work queued afterwards sees the pixels.  Returns the tensor written."""
+        write after it, so torch work queued afterwards sees the pixels.  Returns the tensor written.  Under a window (set_window) the library
+        refuses with its state error: image_window_device() is the call."""
+        return self._image_device(lib().yk_decode_output_device, None, out, channels, alpha, planar)
+
+    def _image_device(self, fn, window, out, channels, alpha, planar):
+        """image_device / image_window_device: the layout checks against the size written (the window's, or the image's), then fn between the hand-overs"""
         import torch
+        ww, wh = (window[2], window[3]) if window is not None else (self.w, self.h)
         C4 = channels if channels is not None else (4 if self._has_alpha else 3)
         a = (-1 if self._has_alpha else 255) if alpha is None else int(alpha)
         dev = torch.device("cuda", self.device)
         if out is None:
-            out = torch.empty((C4, self.h, self.w) if planar else (self.h, self.w, C4), dtype=torch.uint8, device=dev)
+            out = torch.empty((C4, wh, ww) if planar else (wh, ww, C4), dtype=torch.uint8, device=dev)
         elif not isinstance(out, torch.Tensor) or out.device != dev:
             raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
         if planar:
@@ -677,13 +716,13 @@ class HipTileDecoder:
         else:
             lay = u8_pixel_layout(out)
             shape, row_bytes, plane_bytes = (lay.rows, lay.w, lay.channels), lay.row_bytes, 0
-        want = (C4, self.h, self.w) if planar else (self.h, self.w, C4)
+        want = (C4, wh, ww) if planar else (wh, ww, C4)
         if shape != want:
-            raise ValueError(f"out has shape {shape}, the image needs {want}")
+            raise ValueError(f"out has shape {shape}, the {'window' if window is not None else 'image'} needs {want}")
         L = lib()
         cur = torch.cuda.current_stream(dev).cuda_stream
         _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
-        _chk(self._h, L.yk_decode_output_device(self._h, out.data_ptr(), row_bytes, plane_bytes, C4, a))
+        _chk(self._h, fn(self._h, out.data_ptr(), row_bytes, plane_bytes, C4, a))
         _chk(self._h, L.yk_stream_handoff(self._h, cur))
         return out
 

@@ -1,6 +1,7 @@
 """`.yaik` files to pixels on the GPU: a ctypes binding of the C++ drop-in decoder (yaik_amd/host/libyaik_host.so, yaik_decode.h).
 
 decode_file_device(stream)    one stream through YAIK_DecodeImageToDevice: uint8 [H, W, 3], or [H, W, 4] when the stream has an 'ALPM' chunk
+decode_file_window_device(stream, window)   a rectangle of it through YAIK_DecodeImageWindowToDevice: only the tiles the window needs are rendered
 decode_files_device(streams)  n streams of one shape through YAIK_DecodeImagesToDevice: ZStd on host workers, one upload, every kernel once over
                               the batch; uint8 [N, H, W, C] or [N, C, H, W]
 encode_files_device(frames)   the other direction (yaik_encode.h, YAIK_EncodeImagesFromDevice): uint8 [N, H, W, C] frames in device memory to N
@@ -77,6 +78,10 @@ ENC_SIGNATURES = {
 ENC6_SIGNATURES = {
     "YAIK_EncodeImagesFromDeviceAlpha6": (C.c_bool, [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
 }
+# yaik_decode_window.h: the same library, C linkage
+WINDOW_SIGNATURES = {
+    "YAIK_DecodeImageWindowToDevice": (C.c_bool, [vp, u32, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+}
 ERROR_NAMES = ["YAIK_NO_ERROR", "YAIK_INVALID_LIBRARYCTX", "YAIK_MALLOC_FAIL", "YAIK_INVALID_CONTEXT_COUNT", "YAIK_INIT_FAIL",
                "YAIK_RELEASE_EMPTY_LIBRARY", "YAIK_INVALID_STREAM", "YAIK_INVALID_HEADER", "YAIK_NO_EMPTYDECODE_SLOT", "YAIK_DECIMG_INVALIDCTX",
                "YAIK_DECIMG_DIFFSTREAM", "YAIK_DECIMG_BUFFERNOTSET", "YAIK_INVALID_CONTEXT_MEMALLOCATOR", "YAIK_INVALID_DECOMPRESSION",
@@ -113,7 +118,7 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
-        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES}.items():
+        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _host = L
@@ -188,6 +193,40 @@ def decode_file_device(stream: bytes):
     torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
     info.outputImage, info.outputImageStride = out.data_ptr(), info.width * c
     if not L.YAIK_DecodeImageToDevice(src.ctypes.data, src.size, C.byref(info)):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    return out
+
+
+def _window_of(window) -> tuple:
+    """(x0, y0, ww, wh) as ints: multiples of 8, ww, wh >= 8, not negative (that it lies inside the image is the library's to check)"""
+    if isinstance(window, (str, bytes)) or not hasattr(window, "__len__") or len(window) != 4:
+        raise TypeError(f"window must be (x0, y0, w, h); got {window!r}")
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in window):
+        raise TypeError(f"window must hold four ints; got {window!r}")
+    x0, y0, ww, wh = (int(v) for v in window)
+    if (x0 | y0 | ww | wh) & 7 or x0 < 0 or y0 < 0 or ww < 8 or wh < 8:
+        raise ValueError(f"window {(x0, y0, ww, wh)}: x0, y0, w, h must be multiples of 8 with w, h >= 8")
+    return x0, y0, ww, wh
+
+
+def decode_file_window_device(stream: bytes, window):
+    """The rectangle window = (x0, y0, w, h) of one stream through YAIK_DecodeImageWindowToDevice: a torch.uint8 tensor [h, w, 3] on the GPU, or
+    [h, w, 4] when the stream has an 'ALPM' chunk, equal to decode_file_device(stream)[y0:y0 + h, x0:x0 + w]; only the tiles the window needs are
+    rendered.  x0, y0, w, h are multiples of 8 inside the image.  Raises YaikFileError with the library's error code (a window outside the image:
+    YAIK_DECIMG_INVALIDCTX)."""
+    import torch
+    x0, y0, ww, wh = _window_of(window)
+    L, h = host_lib(), library()
+    src = _buffer(stream)
+    info = DecodedImage()
+    if not L.YAIK_DecodeImagePre(h, src.ctypes.data, src.size, C.byref(info)):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    dev = torch.device("cuda", _device)
+    c = 4 if has_alpha_chunk(bytes(stream)) else 3
+    out = torch.empty((wh, ww, c), dtype=torch.uint8, device=dev)
+    torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
+    info.outputImage, info.outputImageStride = out.data_ptr(), ww * c
+    if not L.YAIK_DecodeImageWindowToDevice(src.ctypes.data, src.size, C.byref(info), x0, y0, ww, wh):
         raise YaikFileError(L.YAIK_GetErrorCode())
     return out
 

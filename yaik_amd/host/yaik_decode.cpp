@@ -3,6 +3,7 @@
 // the HIP kernels behind yk_decode_*; ZStd runs on the host like in the reference, and so does PaletteDecompressor unless
 // YAIK_SetDevicePalette(1) sends the 'GTIL' payloads of whole-RGB chunks to yk_decode_gradient_palette.
 #include "yaik_decode.h"
+#include "yaik_decode_window.h"
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -116,13 +117,15 @@ bool YAIK_DecodeImagePre(YAIK_LIB lib, void* stream, uint32_t length, YAIK_SDeco
 }
 
 // The chunk state machine shared by YAIK_DecodeImage, YAIK_DecodeImageToDevice and the fallback of YAIK_DecodeImagesToDevice: begins a single
-// image on the slot's handle and runs every chunk up to the terminator; hasAlphaPlane = an 'ALPM' chunk was decoded (pCtx->alphaChannel)
-static bool decodeChunks(Slot* s, const void* stream, uint32_t length, bool& hasAlphaPlane) {
+// image on the slot's handle and runs every chunk up to the terminator; hasAlphaPlane = an 'ALPM' chunk was decoded (pCtx->alphaChannel).
+// window = {x0, y0, ww, wh} (YAIK_DecodeImageWindowToDevice): set on the handle right after the begin, so every chunk may skip what lies outside it
+static bool decodeChunks(Slot* s, const void* stream, uint32_t length, bool& hasAlphaPlane, const int* window = nullptr) {
     std::vector<uint8_t> bitmap, pal, rgb, types, pix;
     hasAlphaPlane = false;
     {
         const int w = s->width, h = s->height;
         if (yk_decode_begin(s->ctx, w, h) != YK_OK) { setError(YAIK_MALLOC_FAIL); return false; }
+        if (window && yk_decode_set_window(s->ctx, window[0], window[1], window[2], window[3]) != YK_OK) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
         const uint8_t* p = (const uint8_t*)stream + sizeof(FileHeader);
         const uint8_t* const end = (const uint8_t*)stream + length;
         int state = 0; bool bad = false;
@@ -259,8 +262,9 @@ static bool decodeChunks(Slot* s, const void* stream, uint32_t length, bool& has
     }
 }
 
-// YAIK_DecodeImage and YAIK_DecodeImageToDevice; toDevice: outputImage is in device memory (default builder only)
-static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice) {
+// YAIK_DecodeImage, YAIK_DecodeImageToDevice and YAIK_DecodeImageWindowToDevice; toDevice: outputImage is in device memory (default builder only);
+// window (with toDevice): only that rectangle is decoded and written
+static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice, const int* window = nullptr) {
     if (!info || !info->internalTag || !gLib) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
     Slot* s = (Slot*)info->internalTag;
     bool res = false;
@@ -273,7 +277,9 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
         if (!info->outputImage) { setError(YAIK_DECIMG_BUFFERNOTSET); break; }
         const int w = s->width, h = s->height;
         bool hasAlphaPlane = false;
-        if (!decodeChunks(s, stream, length, hasAlphaPlane)) break;
+        if (window && (((window[0] | window[1] | window[2] | window[3]) & 7) || window[0] < 0 || window[1] < 0 || window[2] < 8 || window[3] < 8 ||
+                       window[0] > w - window[2] || window[1] > h - window[3])) { setError(YAIK_DECIMG_INVALIDCTX); break; }
+        if (!decodeChunks(s, stream, length, hasAlphaPlane, window)) break;
         if (customBuilder) {
             // custom builder: hand over the 8x8-tiled planes exactly like the reference (:1303-1318)
             const size_t planeSize = (size_t)(w / 8) * (h / 8) * 64;
@@ -300,7 +306,9 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
             // with an 'ALPM' chunk: RGBA 4 B/pixel from the alpha plane kept in HBM (YAIK.h documents RGBA rows; the reference's own RGBA
             // branch is defective)
             if (toDevice)                                                                           // the same kernel into device rows, then a fence:
-                res = info->outputImageStride > 0 && yk_decode_output_device(s->ctx, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1) == YK_OK &&
+                res = info->outputImageStride > 0 &&
+                      (window ? yk_decode_output_window_device(s->ctx, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1)
+                              : yk_decode_output_device(s->ctx, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1)) == YK_OK &&
                       yk_synchronize(s->ctx) == YK_OK;                                              // the slot's stream is idle before it is released
             else
                 res = (hasAlphaPlane ? yk_decode_output_alpha(s->ctx, info->outputImage, (size_t)info->outputImageStride)
@@ -315,6 +323,10 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
 
 bool YAIK_DecodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info) { return decodeImage(stream, length, info, false); }
 bool YAIK_DecodeImageToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info) { return decodeImage(stream, length, info, true); }
+extern "C" bool YAIK_DecodeImageWindowToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int x0, int y0, int ww, int wh) {
+    const int window[4] = { x0, y0, ww, wh };
+    return decodeImage(stream, length, info, true, window);
+}
 
 // ---- YAIK_DecodeImagesToDevice: n streams of one shape through the device's batch calls (yaik_decode.h) ------------------------------------
 namespace {
