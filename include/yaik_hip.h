@@ -596,6 +596,43 @@ int yk_decode_tile4x4_planes(yk_ctx* c, uint8_t* hostOut, size_t cap);
 int yk_decode_set_window(yk_ctx* c, int x0, int y0, int ww, int wh);
 int yk_decode_output_window_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha);
 
+/* ---- many windows of one image: prepare once, render 64x64 blocks on demand ----
+ * A viewer fetching tiles, a texture pager or a trainer taking crops asks for many windows of the same image.  yk_decode_prepare_device does the
+ * map-sized work of the image once -- the corner lattice (mapRGB), the marks of every tile in tile4x4Mask, the per-tile offsets into the 1-D
+ * streams -- and writes no byte of the planes.  yk_decode_render_windows_device then writes K windows of one size: it renders the 64x64 blocks
+ * its windows touch that no earlier call rendered (gradient tiles, 1-D tiles, zeros in unmarked cells where the image has no 1-D chunk), each
+ * block at most once per prepared image, and de-tiles the K windows.  Every window is, byte for byte, the crop of the whole-image decode.
+ * yk_decode_prepare_device: the gradient arguments of yk_decode_gradient_all_device and the 1-D arguments of yk_decode_1d_device, all in device
+ * memory; an image without a 1-D chunk passes typeBytes == pixBytes == 0 (devType, devPix and compressionRange are then not looked at).  Valid
+ * right after yk_decode_begin: not on a batch, not under a window, before any gradient, plane-subset, mask-split, '3DTL' or 1-D call of the image
+ * and not twice; otherwise YK_ERR_STATE.  yk_decode_alpha and yk_decode_mask are free to come before or after.  At most 7 passes, every pass below
+ * 2^25 tile slots, colour streams below 4 GB: anything larger is YK_ERR_BAD_ARG (decode such an image window by window, yk_decode_set_window).
+ * Every argument is checked before the first launch and a refusal leaves the handle usable.  The handle's buffers are grown before the first
+ * launch too: an allocation that fails (YK_ERR_HIP) leaves the image as yk_decode_begin left it.  A HIP error after the first launch leaves the
+ * image neither fresh nor prepared: yk_decode_begin again.  A yk_decode_begin that fails for device memory ends the prepared image with the
+ * decode buffers it releases: the render calls then return YK_ERR_STATE.  The tile bitmaps and the 1-D streams are copied
+ * into buffers of the handle and the colour streams are consumed, so once the call's work has completed on the handle's stream the caller may
+ * free or overwrite every input.  Timed as one YK_STAGE_DEC_GRADIENT interval and, with 1-D streams, one YK_STAGE_DEC_1D interval.
+ * yk_decode_render_windows_device: nWindows (1..1024) windows of ww x wh with origins xy[2k], xy[2k + 1] (host memory), each under the rule of
+ * yk_decode_set_window; window k goes to devOut + k * windowBytes with the layout, pitch, channels and alpha rules of
+ * yk_decode_output_window_device (alpha = -1 reads the decoded 'ALPM' plane at each window's offset); windowBytes is checked like frameBytes of
+ * yk_decode_output_batch_device.  Before prepare: YK_ERR_STATE.  Bad arguments: YK_ERR_BAD_ARG before anything is queued, with the rendered
+ * blocks and the planes untouched.  A call that finds a block to render queues one YK_STAGE_DEC_GRADIENT interval (the render over the sorted
+ * list of new blocks; for an image without a 1-D chunk also the zeroing of their unmarked cells), one YK_STAGE_DEC_1D interval when the image
+ * has 1-D streams, and one YK_STAGE_DEC_DETILE interval; a call whose blocks are all rendered queues the de-tile alone.
+ * yk_decode_prepared_blocks: how many 64x64 blocks are rendered and how many the image has ((w + 63) / 64 x (h + 63) / 64); either pointer may be
+ * NULL.  Before prepare: YK_ERR_STATE.
+ * While an image is prepared, until the next yk_decode_begin[_batch]: the chunk calls above, yk_decode_set_window, yk_decode_output_window_device
+ * and the whole-image calls (yk_decode_output*, yk_decode_compare_*) return YK_ERR_STATE with a message that names
+ * yk_decode_render_windows_device.  yk_decode_planes[_device] stay: exact inside rendered blocks, untouched outside them;
+ * yk_decode_tile4x4[_planes] stay: whole and exact, no render changes them. */
+int yk_decode_prepare_device(yk_ctx* c, int nPasses, const int* tileShiftX, const int* tileShiftY,
+                             const uint8_t* const* devBitmap, const size_t* bitmapBytes, const uint8_t* const* devRgb, const size_t* rgbBytes, int remapRange,
+                             const uint8_t* devType, size_t typeBytes, const uint8_t* devPix, size_t pixBytes, int compressionRange);
+int yk_decode_render_windows_device(yk_ctx* c, int nWindows, const int* xy, int ww, int wh,
+                                    uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t windowBytes, int channels, int alpha);
+int yk_decode_prepared_blocks(yk_ctx* c, int* rendered, int* total);
+
 /* ---- decode batches: nFrames images of ONE shape on a handle, every kernel launched once over nFrames x blocks ----
  * A frame of 2048 x 2048 or less is a fraction of the grids the decode kernels were tuned on, and one image costs about a dozen dependent stream
  * operations; a batch costs the same dozen.  yk_decode_begin_batch allocates the 8x8-tiled planes, the mapRGB lattice, its `loaded` flags, the

@@ -199,6 +199,7 @@ void yk_destroy(yk_ctx* c) {
     yk_lut_destroy(c);
     yk_lut_dec_destroy(c);
     yk_dec_ring_free(c);
+    yk_dec_prepared_free(c);
     c->fusedAfter = nullptr; c->fusedAfterRing.reset(); c->evRing.reset();     // a ring lives on while another handle still waits on one of its events
     for (int st = 0; st < YK_NUM_STAGES; st++) for (int k = 0; k < YK_STAGE_RING; k++) for (int i = 0; i < 2; i++) if (c->stEv[st][k][i]) (void)hipEventDestroy(c->stEv[st][k][i]);
     if (c->frameGraph) (void)hipGraphExecDestroy(c->frameGraph);

@@ -269,6 +269,10 @@ struct yk_ctx {
     int dWinX = 0, dWinY = 0, dWinW = 0, dWinH = 0;
     bool dWinSet = false, dBatchBegun = false, dChunkSeen = false;
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
+    // yk_decode_prepare_device: the map-sized work of this image is done and what a render needs is kept in dPrep (yk_decode.hip) until the next
+    // yk_decode_begin[_batch]; the buffers in dPrep are grow-only and go with the handle (yk_dec_prepared_free)
+    bool dPrepared = false;
+    struct YkDecPrepared* dPrep = nullptr;
     // decode batch (yk_decode_begin_batch): dB holds the allocations (frame 0) and dStride the distance in BYTES from one frame's array to the
     // next, like B / fs on the encode side; yk_dec_frame(c, f) computes the arrays of frame f, and the single-image entry points work on frame
     // `dCur`.  loaded: lattice point already popped from a colour stream (mapRGBMask)
@@ -343,7 +347,12 @@ int yk_refuse(yk_ctx* c, int code, const char* what);
 #define YK_DEC_NO_BATCH(c, name) do { if ((c)->dFrames > 1) return yk_refuse((c), YK_ERR_STATE, name " is not supported in a batch (yk_decode_begin_batch with nFrames > 1)"); } while (0)
 
 // the calls that hand out or compare the whole image refuse while a window is set: outside it the planes hold whatever they held before
-#define YK_DEC_NO_WINDOW(c, name) do { if ((c)->dWinSet) return yk_refuse((c), YK_ERR_STATE, name " needs the whole image, but a window is set on this decode (yk_decode_set_window): use yk_decode_output_window_device"); } while (0)
+// ... and while the image is prepared for windows (yk_decode_prepare_device): only the blocks some window asked for are rendered
+#define YK_DEC_NO_WINDOW(c, name) do { \
+    if ((c)->dWinSet) return yk_refuse((c), YK_ERR_STATE, name " needs the whole image, but a window is set on this decode (yk_decode_set_window): use yk_decode_output_window_device"); \
+    if ((c)->dPrepared) return yk_refuse((c), YK_ERR_STATE, name " needs the whole image, but this image is prepared for windows (yk_decode_prepare_device): use yk_decode_render_windows_device"); } while (0)
+// the chunk calls and the single-window calls: a prepared image takes no further chunk and hands out pixels through yk_decode_render_windows_device
+#define YK_DEC_NO_PREPARED(c, name) do { if ((c)->dPrepared) return yk_refuse((c), YK_ERR_STATE, name ": this image is prepared for windows (yk_decode_prepare_device); yk_decode_render_windows_device reads it, yk_decode_begin starts the next image"); } while (0)
 
 // launchers implemented in the kernel TUs
 int yk_stage_begin(yk_ctx* c, int stage);                // records the begin event of a new interval of `stage` on c->stream
@@ -374,6 +383,7 @@ struct YkQualitySrc {
 };
 int yk_quality_compare(yk_ctx* c, const YkQualitySrc& q, int firstFrame, int nFrames, int channels, yk_quality* out, uint32_t* devTileSse);
 void yk_dec_ring_free(yk_ctx* c);                         // the batch tables' pinned host ring and its events (yk_decode.hip)
+void yk_dec_prepared_free(yk_ctx* c);                     // what yk_decode_prepare_device keeps (yk_decode.hip)
 void yk_lut_dec_destroy(yk_ctx* c);                       // deletes the 3-D LUT decode tables and, below, the encoder's bank and streams (yk_lut3d.hip)
 void yk_lut_destroy(yk_ctx* c);
 int yk_pp_activate(yk_ctx* c);                           // per-plane coverage / corner flags for the passes behind the RGB passes

@@ -13,6 +13,7 @@
 // Passes are launched in call order, so a later, overlapping tile overwrites an earlier one exactly like the reference.
 #include "yk_common.h"
 #include "yk_device.h"
+#include "yk_window_blocks.h"
 
 struct DPassGeo { int sx, sy, bigX, bigY, bitCount, xBB, tilesPerRow; };
 
@@ -456,6 +457,12 @@ __global__ __launch_bounds__(256) void yk_decall_render_blocks_win_kernel(const 
                                                                           size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4, const DWinRect wr) {
     yk_decall_render_blocks_body<true>(pl, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4, blockIdx.x, wr);
 }
+// a prepared image (yk_decode_prepare_device): the blocks of a list (ascending, each once: two workgroups on one block would break the order of
+// the passes inside it).  The marks are issued again; tile4x4Mask holds them already, so it does not change.
+__global__ __launch_bounds__(256) void yk_decall_render_blocks_list_kernel(const DecPlan pl, int w, int h, int latW, const uint8_t* __restrict__ mapRGB, uint8_t* __restrict__ planes,
+                                                                           size_t planeSize, int tileW, uint32_t* __restrict__ tile4, int stride4, const uint32_t* __restrict__ list) {
+    yk_decall_render_blocks_body<false>(pl, w, h, latW, mapRGB, planes, planeSize, tileW, tile4, stride4, list[blockIdx.x]);
+}
 
 // ---- the same five launches over a batch: frame = blockIdx.y -------------------------------------------------------------------------------
 // Every frame of a batch has the shape of every other, so byteStart / blockStart, the grids and the scratch layout are those of one
@@ -649,13 +656,20 @@ __global__ __launch_bounds__(1024) void yk_dec1d_scan_kernel(uint32_t* __restric
 // (ty0 + j / wtW) * tilesW + tx0 + j % wtW of the image; T8 is then the window's tile count.  The 64 tiles of a round no longer lie in one scan
 // block (a window row may end in one block and the next begin in another), so the two block bases are loaded per lane there.
 struct D1Win { uint32_t tx0, ty0, wtW, tilesW; };
-template <bool WIN>
+// LIST (a prepared image, yk_decode_render_windows_device): the lanes enumerate the 64 tiles of every 64x64 block of a list: tile j of the launch is
+// tile (by * 8 + (j & 63) / 8, bx * 8 + (j & 7)) of block list[j >> 6] = (bx, by); T8 is then 64 x the list's length.  Tiles past the right or bottom
+// edge of the image (a partial block) are inactive.  As under a window the two block bases are loaded per lane: on a 520-wide image one tile row of
+// a block already straddles the boundary between two scan blocks.
+struct D1List { const uint32_t* list; uint32_t xB64, tilesW, tilesH; };
+enum { YK_D1_ALL = 0, YK_D1_WIN = 1, YK_D1_LIST = 2 };
+template <int MODE>
 __device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offInBlk, size_t T8,
                                               const uint32_t* __restrict__ baseTiles, const uint32_t* __restrict__ basePix,
                                               const uint32_t* __restrict__ totals /*[0]=tiles,[1]=pix*/, const uint8_t* __restrict__ type, size_t typeBytes,
                                               const uint8_t* __restrict__ pix, size_t pixBytes, int invRange,
                                               uint8_t* __restrict__ planes, size_t planeSize, int planeOverride, const uint32_t* __restrict__ runBase, const uint32_t bx,
-                                              const D1Win wn = D1Win{ 0, 0, 1, 0 }) {
+                                              const D1Win wn = D1Win{ 0, 0, 1, 0 }, const D1List ls = D1List{ nullptr, 1, 0, 0 }) {
+    constexpr bool WIN = MODE == YK_D1_WIN, LIST = MODE == YK_D1_LIST;
     // planeOverride < 0: the three planes share one mask (no partial-plane pass ran): plane = blockIdx.y, its streams start at
     // plane * totals.  Otherwise one plane per launch with its own mask, streams start at runBase (tiles, pixels of the planes before it).
     const int p = planeOverride < 0 ? (int)blockIdx.y : planeOverride;
@@ -666,11 +680,19 @@ __device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offIn
     // following each other: all offset words, then all parameter bytes and stream bytes, then the arithmetic and the stores.  (Tile after tile
     // a wave made eight dependent round trips; with eight waves per SIMD and 48 waves per SIMD to run, those chains were the launch's duration.)
     uint32_t ow[YK_D1_TPL];
-    size_t ti[YK_D1_TPL];                                                       // WIN: the tile of the image that window tile j is
+    size_t ti[YK_D1_TPL];                                                       // WIN, LIST: the tile of the image that tile j of the launch is
+    bool act[YK_D1_TPL];                                                        // LIST: ... and whether it lies inside the image
 #pragma unroll
     for (int rep = 0; rep < YK_D1_TPL; rep++) {
         const size_t i = ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
-        if (WIN) {
+        if (LIST) {
+            const bool in = i < T8;
+            const uint32_t b = in ? ls.list[i >> 6] : 0u, t = (uint32_t)i & 63u;
+            const uint32_t by = b / ls.xB64, tx = (b - by * ls.xB64) * 8u + (t & 7u), ty = by * 8u + (t >> 3);
+            act[rep] = in && tx < ls.tilesW && ty < ls.tilesH;
+            ti[rep] = act[rep] ? (size_t)ty * ls.tilesW + tx : 0;
+            ow[rep] = act[rep] ? offInBlk[ti[rep]] : 0xF0000000u;
+        } else if (WIN) {
             const uint32_t jy = (uint32_t)i / wn.wtW, jx = (uint32_t)i - jy * wn.wtW;
             ti[rep] = i < T8 ? (size_t)(wn.ty0 + jy) * wn.tilesW + wn.tx0 + jx : 0;
             ow[rep] = i < T8 ? offInBlk[ti[rep]] : 0xF0000000u;
@@ -683,8 +705,8 @@ __device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offIn
         const int q = (int)(ow[rep] >> 28);
         const int qh = (q >> (half * 2)) & 3;                                    // bit 0: left quadrant filled, bit 1: right
         // the 64 tiles of a workgroup's round lie in one scan block: its two bases are scalar loads
-        const size_t blk = WIN ? ti[rep] >> 10 : (((size_t)bx * YK_D1_TPL + rep) * 64) >> 10;
-        const bool inRange = WIN ? ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2) < T8 : (((size_t)bx * YK_D1_TPL + rep) * 64) < T8;
+        const size_t blk = (WIN || LIST) ? ti[rep] >> 10 : (((size_t)bx * YK_D1_TPL + rep) * 64) >> 10;
+        const bool inRange = LIST ? act[rep] : WIN ? ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2) < T8 : (((size_t)bx * YK_D1_TPL + rep) * 64) < T8;
         const uint32_t offT = (inRange ? baseTiles[blk] : 0u) + (ow[rep] & 2047u), offP = (inRange ? basePix[blk] : 0u) + ((ow[rep] >> 11) & 0x1FFFFu);
         const int nTop = 2 - (q & 1) - ((q >> 1) & 1);
         const size_t to = (baseT + offT) * 3;
@@ -706,7 +728,7 @@ __device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offIn
     }
 #pragma unroll
     for (int rep = 0; rep < YK_D1_TPL; rep++) {
-        const size_t i = WIN ? ti[rep] : ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
+        const size_t i = (WIN || LIST) ? ti[rep] : ((size_t)bx * YK_D1_TPL + rep) * 64 + (threadIdx.x >> 2);
         const int q = (int)(ow[rep] >> 28);
         const int qh = (q >> (half * 2)) & 3;
         const int color0 = __builtin_amdgcn_update_dpp(0, tb[rep], 0x00, 0xF, 0xF, true), base = __builtin_amdgcn_update_dpp(0, tb[rep], 0x55, 0xF, 0xF, true),
@@ -747,14 +769,23 @@ __global__ __launch_bounds__(256) void yk_dec1d_kernel(const uint32_t* __restric
                                                        const uint32_t* __restrict__ totals /*[0]=tiles,[1]=pix*/, const uint8_t* __restrict__ type, size_t typeBytes,
                                                        const uint8_t* __restrict__ pix, size_t pixBytes, int invRange,
                                                        uint8_t* __restrict__ planes, size_t planeSize, int planeOverride, const uint32_t* __restrict__ runBase) {
-    yk_dec1d_body<false>(offInBlk, T8, baseTiles, basePix, totals, type, typeBytes, pix, pixBytes, invRange, planes, planeSize, planeOverride, runBase, blockIdx.x);
+    yk_dec1d_body<YK_D1_ALL>(offInBlk, T8, baseTiles, basePix, totals, type, typeBytes, pix, pixBytes, invRange, planes, planeSize, planeOverride, runBase, blockIdx.x);
 }
 // the shared-mask mode (plane = blockIdx.y) over the tiles of a decode window; nWin = its tile count
 __global__ __launch_bounds__(256) void yk_dec1d_win_kernel(const uint32_t* __restrict__ offInBlk, size_t nWin, const D1Win wn,
                                                            const uint32_t* __restrict__ baseTiles, const uint32_t* __restrict__ basePix,
                                                            const uint32_t* __restrict__ totals, const uint8_t* __restrict__ type, size_t typeBytes,
                                                            const uint8_t* __restrict__ pix, size_t pixBytes, int invRange, uint8_t* __restrict__ planes, size_t planeSize) {
-    yk_dec1d_body<true>(offInBlk, nWin, baseTiles, basePix, totals, type, typeBytes, pix, pixBytes, invRange, planes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x, wn);
+    yk_dec1d_body<YK_D1_WIN>(offInBlk, nWin, baseTiles, basePix, totals, type, typeBytes, pix, pixBytes, invRange, planes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x, wn);
+}
+
+// the shared-mask mode over the tiles of the blocks of a list (a prepared image); nTiles = 64 x the list's length
+__global__ __launch_bounds__(256) void yk_dec1d_list_kernel(const uint32_t* __restrict__ offInBlk, size_t nTiles, const D1List ls,
+                                                            const uint32_t* __restrict__ baseTiles, const uint32_t* __restrict__ basePix,
+                                                            const uint32_t* __restrict__ totals, const uint8_t* __restrict__ type, size_t typeBytes,
+                                                            const uint8_t* __restrict__ pix, size_t pixBytes, int invRange, uint8_t* __restrict__ planes, size_t planeSize) {
+    yk_dec1d_body<YK_D1_LIST>(offInBlk, nTiles, baseTiles, basePix, totals, type, typeBytes, pix, pixBytes, invRange, planes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x,
+                              D1Win{ 0, 0, 1, 0 }, ls);
 }
 
 // ---- the 1-D chunk over a batch: the same three launches, frame = blockIdx.y (count), blockIdx.x (scan: one workgroup per frame), blockIdx.z
@@ -780,7 +811,7 @@ __global__ __launch_bounds__(1024) void yk_dec1d_scan_batch_kernel(const D1Batch
 __global__ __launch_bounds__(256) void yk_dec1d_batch_kernel(const D1Batch B, size_t T8, int invRange, size_t planeSize) {
     const size_t f = blockIdx.z;
     const D1Frame& fr = B.frames[f];
-    yk_dec1d_body<false>(yk_d1batch_u32(B, f, B.oOff), T8, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oTot), fr.type, (size_t)fr.typeBytes,
+    yk_dec1d_body<YK_D1_ALL>(yk_d1batch_u32(B, f, B.oOff), T8, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oTot), fr.type, (size_t)fr.typeBytes,
                   fr.pix, (size_t)fr.pixBytes, invRange, B.planes + f * B.sPlanes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x);
 }
 
@@ -932,10 +963,10 @@ __global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_kernel(YkDetileAr
 }
 // the window form: the same lanes and steps over the window's tiles (a row of the window is contiguous in the planes, rows are tileW tiles apart)
 template <int C, bool PLANAR, int ASRC>
-__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_win_kernel(YkDetileArgs a, const YkDetileWin wn) {
+__device__ __forceinline__ void yk_dec_detile_win_body(const YkDetileArgs a, const YkDetileWin wn, const uint32_t bx) {
     const uint32_t lane = threadIdx.x & 63, rp = lane & 3;
-    const uint32_t j0 = (blockIdx.x * (YK_DT_K * 4) + (threadIdx.x >> 6)) * 16 + (lane >> 2);
-    if ((blockIdx.x + 1) * (uint32_t)YK_DT_TILES <= a.nTiles) {
+    const uint32_t j0 = (bx * (YK_DT_K * 4) + (threadIdx.x >> 6)) * 16 + (lane >> 2);
+    if ((bx + 1) * (uint32_t)YK_DT_TILES <= a.nTiles) {
         YkDtUnit u[YK_DT_K];
 #pragma unroll
         for (int k = 0; k < YK_DT_K; k++) yk_dt_load_win<C, PLANAR, ASRC>(a, wn, j0 + k * 64, rp, u[k]);
@@ -950,6 +981,26 @@ __global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_win_kernel(YkDeti
         yk_dt_load_win<C, PLANAR, ASRC>(a, wn, j, rp, u);
         yk_dt_store<C, PLANAR, ASRC>(a, u);
     }
+}
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_win_kernel(YkDetileArgs a, const YkDetileWin wn) {
+    yk_dec_detile_win_body<C, PLANAR, ASRC>(a, wn, blockIdx.x);
+}
+// K windows of one size of a prepared image (yk_decode_render_windows_device): window blockIdx.y, its origin (pixels) from a table in HBM, goes to
+// a.out + k * windowBytes; a.alpha (YK_DT_ALPHA_PLANE) is the whole plane and is read at the window's own offset
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_wins_kernel(YkDetileArgs a, const int* __restrict__ xy, uint32_t wtW, size_t windowBytes) {
+    const uint32_t k = blockIdx.y;
+    const uint32_t x0 = (uint32_t)xy[2 * k], y0 = (uint32_t)xy[2 * k + 1];
+    a.out += (size_t)k * windowBytes;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) a.alpha += (size_t)y0 * a.strideA + x0;
+    const YkDetileWin wn = { x0 >> 3, y0 >> 3, wtW };
+    yk_dec_detile_win_body<C, PLANAR, ASRC>(a, wn, blockIdx.x);
+}
+template <int C, bool PLANAR, int ASRC>
+static void yk_dt_launch_wins(const YkDetileArgs& a, hipStream_t s, int nWindows, const int* devXY, uint32_t wtW, size_t windowBytes) {
+    const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
+    hipLaunchKernelGGL((yk_dec_detile_wins_kernel<C, PLANAR, ASRC>), dim3(gx, (unsigned)nWindows), dim3(YK_DT_THREADS), 0, s, a, devXY, wtW, windowBytes);
 }
 // a batch: frame blockIdx.y's planes at a.planes + f * planesFrame, its pixels at a.out + f * outFrame
 // (YK_DT_ALPHA_PLANE: its alpha plane at a.alpha + f * alphaFrame, the planes of yk_decode_alpha_batch_device)
@@ -1041,6 +1092,16 @@ __global__ __launch_bounds__(256) void yk_dec_zero_unmarked_win_kernel(const uin
     const uint32_t jy = j / wtW, jx = j - jy * wtW;
     yk_dec_zero_unmarked_tile(tile4, tile4Size, split, stride4, tilesW, (size_t)(ty0 + jy) * tilesW + tx0 + jx, planes, planeSize);
 }
+// a prepared image without a 1-D chunk: the tiles of the blocks of a list, enumerated as yk_dec1d_list_kernel does (nTiles = 64 x the list's length)
+__global__ __launch_bounds__(256) void yk_dec_zero_unmarked_list_kernel(const uint8_t* __restrict__ tile4, size_t tile4Size, int stride4, int tilesW, int tilesH,
+                                                                        const uint32_t* __restrict__ list, uint32_t xB64, uint32_t nTiles, uint8_t* __restrict__ planes, size_t planeSize) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nTiles) return;
+    const uint32_t b = list[j >> 6], t = j & 63u;
+    const uint32_t by = b / xB64, tx = (b - by * xB64) * 8u + (t & 7u), ty = by * 8u + (t >> 3);
+    if (tx >= (uint32_t)tilesW || ty >= (uint32_t)tilesH) return;
+    yk_dec_zero_unmarked_tile(tile4, tile4Size, 0, stride4, tilesW, (size_t)ty * tilesW + tx, planes, planeSize);
+}
 __global__ __launch_bounds__(256) void yk_dec_zero_unmarked_kernel(const uint8_t* __restrict__ tile4, size_t tile4Size, int split, int stride4, int tilesW, size_t T8,
                                                                    uint8_t* __restrict__ planes, size_t planeSize) {
     yk_dec_zero_unmarked_body(tile4, tile4Size, split, stride4, tilesW, T8, planes, planeSize);
@@ -1073,9 +1134,25 @@ static int yk_dec_settle(yk_ctx* c) {
 static void yk_dec_free_frames(yk_ctx* c) {
     c->dFrm = yk_ctx::DFrames(); c->dB = {};
     c->dw = c->dh = 0; c->dFrames = 1; c->dCur = 0;
+    c->dPrepared = false;                                                       // a prepared image lives in these buffers: it goes with them
 }
 
 }  // extern "C"
+// What yk_decode_prepare_device leaves for yk_decode_render_windows_device (valid while c->dPrepared): the plan of the gradient passes with its
+// bitmaps pointing at the handle's copies, the copies of the 1-D streams, the per-tile and per-block offsets of the 1-D count and scan, and one
+// bit per 64x64 block that has been rendered.  mapRGB and tile4x4Mask are the image's own arrays.  The buffers are grow-only.
+struct YkDecPrepared {
+    DecPlan pl = {};
+    YkBuf<uint8_t> streams;                                  // [bitmap of pass 0] .. [bitmap of pass n-1][type][pix], each on a multiple of 16
+    YkBuf<uint32_t> d1;                                      // [blockTiles][blockPix][totals][offInBlk]
+    YkBuf<uint32_t> table;                                   // a render call's [block list][window origins]
+    bool has1d = false;
+    const uint8_t* type = nullptr; const uint8_t* pix = nullptr; size_t typeBytes = 0, pixBytes = 0; int invRange = 0;
+    uint32_t* bT = nullptr; uint32_t* bP = nullptr; uint32_t* tot = nullptr; uint32_t* offInBlk = nullptr;
+    YkWindowBlocks blocks;
+    std::vector<uint32_t> list;
+};
+void yk_dec_prepared_free(yk_ctx* c) { delete c->dPrep; c->dPrep = nullptr; c->dPrepared = false; }
 void yk_dec_ring_free(yk_ctx* c) {
     for (int i = 0; i < 4; i++) {
         if (c->dTabHost[i]) { (void)hipHostFree(c->dTabHost[i]); c->dTabHost[i] = nullptr; c->dTabHostBytes[i] = 0; }
@@ -1121,6 +1198,7 @@ static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
     }
     c->dCur = 0;
     c->dWinSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; c->dChunkSeen = false; c->dBatchBegun = false;
+    c->dPrepared = false;                                                       // a prepared image ends here; what it kept is overwritten by the next prepare
     // The planes (3 B per pixel: 201 MB at 8192 x 8192, 40 us of every frame) are NOT cleared: every renderer marks what it writes in tile4x4Mask and
     // the 1-D decode writes every unmarked quadrant, so after a whole file nothing stale is left; a flow that stops earlier (or writes without
     // marking: the plane-subset loops) gets the unmarked cells zeroed when it needs them (yk_dec_settle).
@@ -1150,6 +1228,7 @@ int yk_decode_begin_batch(yk_ctx* c, int w, int h, int nFrames) {
 int yk_decode_set_window(yk_ctx* c, int x0, int y0, int ww, int wh) {
     if (!c) return YK_ERR_BAD_ARG;
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window: yk_decode_begin first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_set_window");
     if (c->dBatchBegun || c->dFrames > 1) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window: a window belongs to a single image (yk_decode_begin), not to a batch");
     if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window: a chunk of this image has been decoded already; set the window right after yk_decode_begin");
     if (ww == 0 && wh == 0) { c->dWinSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; return YK_OK; }
@@ -1250,6 +1329,7 @@ static hipError_t yk_dpass_stage(yk_ctx* c, const uint8_t* bitmap, size_t need, 
 static int yk_decode_gradient_impl(yk_ctx* c, int sx, int sy, const uint8_t* bitmap, size_t bitmapBytes, const uint8_t* rgb, size_t rgbBytes, bool onDevice, int remapRange) {
     if (!c || !bitmap) return YK_ERR_BAD_ARG;
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_gradient[_device]");
     const YkDecView V = yk_dec_frame(c);
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
     const size_t need = yk_dpass_bytes(sx, sy, w, h);
@@ -1291,6 +1371,7 @@ int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX,
                                   const uint8_t* const* devRgb, const size_t* rgbBytes, int remapRange) {
     if (!c || nPasses < 0 || (nPasses && (!tileShiftX || !tileShiftY || !devBitmap || !bitmapBytes || !devRgb || !rgbBytes))) return YK_ERR_BAD_ARG;
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_gradient_all_device");
     const YkDecView V = yk_dec_frame(c);
     if (nPasses == 0) return YK_OK;
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
@@ -1352,6 +1433,7 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
     if (nPasses < 0 || nPasses > 7) return yk_refuse(c, YK_ERR_BAD_ARG, "a batch takes 0..7 gradient passes per call");
     if (nPasses && (!tileShiftX || !tileShiftY || !devBitmap || !bitmapBytes || !devRgb || !rgbBytes)) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_gradient_all_batch_device");
     if (nPasses == 0) return YK_OK;
     const int w = c->dw, h = c->dh, latW = w / 4 + 1, N = c->dFrames;
     size_t need[7] = {};
@@ -1418,6 +1500,7 @@ int yk_decode_split_masks(yk_ctx* c) {
     if (!c) return YK_ERR_BAD_ARG;
     YK_DEC_NO_BATCH(c, "yk_decode_split_masks");
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_split_masks");
     YK_HIP(c, hipSetDevice(c->device));
     c->dChunkSeen = true;
     return yk_dec_split(c);
@@ -1426,6 +1509,7 @@ int yk_decode_split_masks(yk_ctx* c) {
 int yk_decode_gradient_planes(yk_ctx* c, int planeBit, int consistentMarks, const uint8_t* bitmap, size_t bitmapBytes, const uint8_t* rgb, size_t rgbBytes) {
     if (!c || !bitmap) return YK_ERR_BAD_ARG;
     YK_DEC_NO_BATCH(c, "yk_decode_gradient_planes");
+    YK_DEC_NO_PREPARED(c, "yk_decode_gradient_planes");
     if (planeBit == 7) return yk_decode_gradient(c, 2, 2, bitmap, bitmapBytes, rgb, rgbBytes);
     if (planeBit < 1 || planeBit > 6) return yk_fail(c, YK_ERR_BAD_ARG, "planeBit must be 1..7");
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
@@ -1460,6 +1544,7 @@ __global__ void yk_dec1d_next_plane_kernel(uint32_t* __restrict__ runBase, const
 static int yk_decode_1d_impl(yk_ctx* c, const uint8_t* typeStream, size_t typeBytes, const uint8_t* pixStream, size_t pixBytes, int compressionRange, bool onDevice) {
     if (!c || !typeStream || !pixStream || compressionRange <= 0) return YK_ERR_BAD_ARG;
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_1d[_device]");
     const YkDecView V = yk_dec_frame(c);
     YK_HIP(c, hipSetDevice(c->device));
     c->dChunkSeen = true;
@@ -1532,6 +1617,7 @@ int yk_decode_1d_batch_device(yk_ctx* c, const uint8_t* const* devType, const si
     if (!devType || !typeBytes || !devPix || !pixBytes) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL table");
     if (compressionRange <= 0) return yk_refuse(c, YK_ERR_BAD_ARG, "compressionRange must be positive");
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_1d_batch_device");
     const int N = c->dFrames;
     for (int f = 0; f < N; f++) {
         if ((typeBytes[f] && !devType[f]) || (pixBytes[f] && !devPix[f])) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL 1-D stream with a length");
@@ -1665,6 +1751,7 @@ int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t 
 
 int yk_decode_output_window_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha) {
     if (!c) return YK_ERR_BAD_ARG;
+    YK_DEC_NO_PREPARED(c, "yk_decode_output_window_device");
     return yk_dec_output_device(c, devOut, rowBytes, planeBytes, channels, alpha, c->dWinSet);
 }
 
@@ -1674,6 +1761,7 @@ int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, s
     if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
     if (channels == 4 && (alpha < 0 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "alpha must be 0..255 (a batch has no decoded alpha plane)");
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_output_batch_device");
     const size_t w = (size_t)c->dw, h = (size_t)c->dh;
     if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
         return yk_refuse(c, YK_ERR_BAD_ARG, "row or plane pitch too small for the image");
@@ -1778,6 +1866,178 @@ int yk_decode_tile4x4(yk_ctx* c, uint8_t* hostOut, size_t cap) {
     YK_HIP(c, hipMemcpyAsync(hostOut, yk_dec_frame(c).tile4, c->dTile4Size, hipMemcpyDeviceToHost, c->stream));
     YK_HIP(c, hipStreamSynchronize(c->stream));
     return YK_OK;
+}
+
+// ---- many windows of one image: the map-sized work once, 64x64 blocks rendered on demand (include/yaik_hip.h) ------------------
+int yk_decode_prepare_device(yk_ctx* c, int nPasses, const int* tileShiftX, const int* tileShiftY, const uint8_t* const* devBitmap, const size_t* bitmapBytes,
+                             const uint8_t* const* devRgb, const size_t* rgbBytes, int remapRange, const uint8_t* devType, size_t typeBytes, const uint8_t* devPix,
+                             size_t pixBytes, int compressionRange) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_prepare_device: yk_decode_begin first");
+    if (c->dPrepared) return yk_refuse(c, YK_ERR_STATE, "yk_decode_prepare_device: this image is prepared already; yk_decode_begin starts the next one");
+    if (c->dBatchBegun || c->dFrames > 1) return yk_refuse(c, YK_ERR_STATE, "yk_decode_prepare_device: a single image (yk_decode_begin) is prepared, not a batch");
+    if (c->dWinSet) return yk_refuse(c, YK_ERR_STATE, "yk_decode_prepare_device: a window is set on this decode (yk_decode_set_window); prepare takes the whole image");
+    if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_prepare_device: a chunk of this image has been decoded already; prepare right after yk_decode_begin");
+    if (nPasses < 0 || (nPasses && (!tileShiftX || !tileShiftY || !devBitmap || !bitmapBytes || !devRgb || !rgbBytes)))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_prepare_device: negative pass count or NULL table");
+    if (nPasses > 7) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_prepare_device takes at most 7 gradient passes; decode such an image window by window (yk_decode_set_window)");
+    const int w = c->dw, h = c->dh, latW = w / 4 + 1, tilesW = w >> 3;
+    size_t need[7] = {};
+    for (int p = 0; p < nPasses; p++) {
+        if (!(need[p] = yk_dpass_bytes(tileShiftX[p], tileShiftY[p], w, h))) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_prepare_device: unsupported tile format");
+        if (!devBitmap[p] || (rgbBytes[p] && !devRgb[p])) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_prepare_device: NULL tile bitmap, or NULL colour stream with a length");
+        if (bitmapBytes[p] < need[p]) return yk_refuse(c, YK_ERR_RANGE, "yk_decode_prepare_device: tile bitmap shorter than the image needs");
+        if (!yk_dpass_fits_key(need[p]) || rgbBytes[p] > 0xFFFFFFFFu)
+            return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_prepare_device: a pass of 2^25 tile slots or more, or a colour stream of 4 GB or more; decode such an image window by window (yk_decode_set_window)");
+    }
+    const bool has1d = typeBytes != 0 || pixBytes != 0;
+    if (has1d && (!devType || !devPix || compressionRange <= 0))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_prepare_device: 1-D streams need both pointers and a positive compressionRange (no 1-D chunk: both lengths 0)");
+    YK_HIP(c, hipSetDevice(c->device));
+    if (!c->dPrep) c->dPrep = new YkDecPrepared();
+    YkDecPrepared& P = *c->dPrep;
+    const YkDecView V = yk_dec_frame(c);
+    // 1. the tile bitmaps and the 1-D streams into the handle's own buffer: the caller's may go once this call's work is done
+    auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    size_t oBm[7] = {}, at = 0;
+    for (int p = 0; p < nPasses; p++) { oBm[p] = at; at += up16(need[p]); }
+    const size_t oTy = at, oPx = oTy + up16(typeBytes);
+    at = oPx + up16(pixBytes);
+    // every allocation first: a failure up to the first launch leaves the image as yk_decode_begin left it, and prepare may be called again
+    const size_t T8 = (size_t)tilesW * (h >> 3), nb = (T8 + 1023) / 1024;
+    const size_t oBT = 0, oBP = oBT + nb + 4, oTot = oBP + nb + 4, oOff = oTot + 16;          // in words
+    const size_t nBlocks64 = (size_t)((w + 63) / 64) * ((h + 63) / 64);
+    YK_HIP(c, P.streams.reserve(c->stream, at + 64));
+    if (has1d) YK_HIP(c, P.d1.reserve(c->stream, oOff + T8 + 16));
+    YK_HIP(c, P.table.reserve(c->stream, nBlocks64 + 2 * 1024));                // a render call's largest table: no allocation on the render path
+    P.pl = DecPlan{};
+    yk_dplan_shape(P.pl, nPasses, tileShiftX, tileShiftY, need);
+    const DecAllScratch L = yk_decall_scratch(P.pl);
+    if (nPasses) { const int rc = yk_dec_scratch(c, L.bytes); if (rc) return rc; }
+    for (int p = 0; p < nPasses; p++) YK_HIP(c, hipMemcpyAsync(P.streams + oBm[p], devBitmap[p], need[p], hipMemcpyDeviceToDevice, c->stream));
+    if (typeBytes) YK_HIP(c, hipMemcpyAsync(P.streams + oTy, devType, typeBytes, hipMemcpyDeviceToDevice, c->stream));
+    if (pixBytes) YK_HIP(c, hipMemcpyAsync(P.streams + oPx, devPix, pixBytes, hipMemcpyDeviceToDevice, c->stream));
+    for (int p = 0; p < nPasses; p++) { P.pl.bm[p] = P.streams + oBm[p]; P.pl.rgb[p] = devRgb[p]; P.pl.rgbBytes[p] = (uint32_t)rgbBytes[p]; }
+    P.has1d = has1d; P.type = P.streams + oTy; P.typeBytes = typeBytes; P.pix = P.streams + oPx; P.pixBytes = pixBytes;
+    P.invRange = has1d ? (1 << 24) / compressionRange : 0;
+    if (has1d) { P.bT = P.d1 + oBT; P.bP = P.d1 + oBP; P.tot = P.d1 + oTot; P.offInBlk = P.d1 + oOff; }
+    // from the first launch on the image's arrays are written: a HIP failure below leaves the image neither fresh nor prepared, and the chunk
+    // calls, yk_decode_set_window and a second prepare refuse until the next yk_decode_begin
+    c->dChunkSeen = true;
+    if (nPasses) {
+        // 2. the lattice: first touchers, count, scan, emit -- the launches of yk_decode_gradient_all_device; the corner colours are consumed here
+        const DecPlan& pl = P.pl;
+        const size_t nbTot = pl.blockStart[7], nBytesTot = pl.byteStart[7], lat = (size_t)latW * (h / 4 + 1);
+        uint32_t* blockSums = reinterpret_cast<uint32_t*>(c->dScratch + L.oSums);
+        uint32_t* perThread = reinterpret_cast<uint32_t*>(c->dScratch + L.oPerThread);
+        YK_HIP(c, hipMemsetAsync(V.owner, 0xFF, lat * 4, c->stream));
+        { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
+        hipLaunchKernelGGL(yk_decall_owner_kernel, dim3((unsigned)((nBytesTot + 255) / 256)), dim3(256), 0, c->stream, pl, w, h, latW, V.loaded, V.owner);
+        hipLaunchKernelGGL(yk_decall_stream_kernel<false>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, V.loaded, V.owner, blockSums, perThread,
+                           (uint8_t*)nullptr, 0u);
+        hipLaunchKernelGGL(yk_decall_scan_kernel, dim3(1), dim3(1024), 0, c->stream, blockSums, pl);
+        hipLaunchKernelGGL(yk_decall_stream_kernel<true>, dim3((unsigned)nbTot), dim3(1024), 0, c->stream, pl, w, h, latW, V.loaded, V.owner, blockSums, perThread,
+                           V.mapRGB, yk_dec_remap_factor(remapRange));
+        // the emit launch above was the last reader of the corner colours (it took the plan by value): the kept plan forgets the caller's buffers
+        for (int p = 0; p < nPasses; p++) { P.pl.rgb[p] = nullptr; P.pl.rgbBytes[p] = 0; }
+        // 3. the marks of every block and no pixel: the window form with an empty rectangle
+        hipLaunchKernelGGL(yk_decall_render_blocks_win_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64))), dim3(256), 0, c->stream, pl, w, h, latW,
+                           V.mapRGB, V.planes, c->dPlaneSize, w >> 3, reinterpret_cast<uint32_t*>(V.tile4), (w + 15) >> 4, DWinRect{ 0, 0, 0, 0 });
+        YK_HIP(c, hipGetLastError());
+        { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
+    }
+    if (has1d) {
+        // 4. where every tile's parameters and pixels lie in the 1-D streams, from the whole mask
+        { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
+        hipLaunchKernelGGL(yk_dec1d_count_kernel, dim3((unsigned)nb), dim3(1024), 0, c->stream, V.tile4, (w + 15) >> 4, tilesW, T8, P.bT, P.bP, P.offInBlk);
+        hipLaunchKernelGGL(yk_dec1d_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.bT, P.bP, (int)nb, P.tot);
+        YK_HIP(c, hipGetLastError());
+        { int rc2 = yk_stage_end(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
+    }
+    yk_wb_reset(P.blocks, w, h);
+    // every rendered block gets its unmarked cells from the render call (the 1-D tiles, or zeros): nothing is left for yk_dec_settle, which
+    // would write blocks no window asked for
+    c->dPlanesStale = false;
+    c->dPrepared = true;
+    return YK_OK;
+}
+
+int yk_decode_prepared_blocks(yk_ctx* c, int* rendered, int* total) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!yk_dec_begun(c) || !c->dPrepared) return yk_refuse(c, YK_ERR_STATE, "yk_decode_prepared_blocks: yk_decode_prepare_device first");
+    if (rendered) *rendered = c->dPrep->blocks.rendered;
+    if (total) *total = yk_wb_total(c->dPrep->blocks);
+    return YK_OK;
+}
+
+int yk_decode_render_windows_device(yk_ctx* c, int nWindows, const int* xy, int ww, int wh, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t windowBytes,
+                                    int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!yk_dec_begun(c) || !c->dPrepared) return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_device: yk_decode_prepare_device first");
+    YkDecPrepared& P = *c->dPrep;
+    if (P.blocks.w != c->dw || P.blocks.h != c->dh)                             // the kept state describes the image the buffers hold, or nothing is launched
+        return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_device: the prepared image is not the one this handle holds; yk_decode_begin and yk_decode_prepare_device again");
+    if (nWindows < 1 || nWindows > 1024) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_device: nWindows must be 1..1024");
+    if (!xy) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_device: the window table is NULL");
+    if (!yk_wb_windows_ok(P.blocks, nWindows, xy, ww, wh))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_device: x0, y0, ww, wh must be multiples of 8 with ww, wh >= 8 and every window inside the image");
+    if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_device: devOut is NULL");
+    if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_device: channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_device: alpha must be -1 (the decoded plane) or 0..255");
+    if (planeBytes == 0 ? rowBytes < (size_t)ww * channels : (rowBytes < (size_t)ww || planeBytes / (size_t)wh < rowBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_device: row or plane pitch too small for the window");
+    if (nWindows > 1 && (planeBytes == 0 ? windowBytes / (size_t)wh < rowBytes : windowBytes / (size_t)channels < planeBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_device: window stride too small for a window");
+    const bool fromPlane = channels == 4 && alpha < 0;
+    if (fromPlane && !c->dAlphaValid) return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_device: alpha = -1 needs yk_decode_alpha first");
+    YK_HIP(c, hipSetDevice(c->device));
+    const int w = c->dw, h = c->dh, latW = w / 4 + 1, tilesW = w >> 3, tilesH = h >> 3, stride4 = (w + 15) >> 4;
+    const YkDecView V = yk_dec_frame(c);
+    // the table's buffer and its pinned slot before the bitmap changes: a refusal up to here leaves every block as it was
+    const size_t maxList = (size_t)yk_wb_total(P.blocks), words = maxList + 2 * (size_t)nWindows;
+    YK_HIP(c, P.table.reserve(c->stream, maxList + 2 * 1024));                  // prepare has reserved this: no allocation here
+    int slot; void* host;
+    { const int rc = yk_dec_table_host(c, words * 4, &slot, &host); if (rc) return rc; }
+    yk_wb_take(P.blocks, nWindows, xy, ww, wh, P.list);
+    const size_t nList = P.list.size();
+    uint32_t* tab = static_cast<uint32_t*>(host);
+    for (size_t i = 0; i < nList; i++) tab[i] = P.list[i];
+    for (int i = 0; i < 2 * nWindows; i++) tab[nList + i] = (uint32_t)xy[i];
+    { const int rc = yk_dec_table_upload(c, slot, P.table, (nList + 2 * (size_t)nWindows) * 4); if (rc) return rc; }
+    const uint32_t* devList = P.table;
+    const int* devXY = reinterpret_cast<const int*>(P.table + nList);
+    if (nList) {
+        const uint32_t xB64 = (uint32_t)P.blocks.nbx, nTiles = (uint32_t)nList * 64u;
+        { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
+        hipLaunchKernelGGL(yk_decall_render_blocks_list_kernel, dim3((unsigned)nList), dim3(256), 0, c->stream, P.pl, w, h, latW, V.mapRGB, V.planes, c->dPlaneSize, tilesW,
+                           reinterpret_cast<uint32_t*>(V.tile4), stride4, devList);
+        if (!P.has1d)                                                           // no 1-D chunk: what no gradient tile covers reads as zero
+            hipLaunchKernelGGL(yk_dec_zero_unmarked_list_kernel, dim3((nTiles + 255) / 256, 3), dim3(256), 0, c->stream, V.tile4, c->dTile4Size, stride4, tilesW, tilesH,
+                               devList, xB64, nTiles, V.planes, c->dPlaneSize);
+        YK_HIP(c, hipGetLastError());
+        { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
+        if (P.has1d) {
+            const D1List ls = { devList, xB64, (uint32_t)tilesW, (uint32_t)tilesH };
+            { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
+            hipLaunchKernelGGL(yk_dec1d_list_kernel, dim3((nTiles + 64 * YK_D1_TPL - 1) / (64 * YK_D1_TPL), 3), dim3(256), 0, c->stream, (const uint32_t*)P.offInBlk, (size_t)nTiles, ls,
+                               (const uint32_t*)P.bT, (const uint32_t*)P.bP, (const uint32_t*)P.tot, P.type, P.typeBytes, P.pix, P.pixBytes, P.invRange, V.planes, c->dPlaneSize);
+            YK_HIP(c, hipGetLastError());
+            { int rc2 = yk_stage_end(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
+        }
+    }
+    YkDetileArgs a;
+    a.planes = V.planes; a.planeSize = c->dPlaneSize;
+    a.alpha = fromPlane ? yk_dec_alpha_cur(c) : nullptr; a.strideA = (size_t)w; a.alphaConst = (uint32_t)((fromPlane ? 0 : alpha) & 255) * 0x01010101u;
+    a.out = devOut; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
+    a.tileW = (uint32_t)tilesW; a.nTiles = (uint32_t)(ww >> 3) * (uint32_t)(wh >> 3);
+    const uint32_t wtW = (uint32_t)(ww >> 3);
+    const bool planar = planeBytes > 0;
+    { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    if (channels == 3) { if (planar) yk_dt_launch_wins<3, true, YK_DT_ALPHA_NONE>(a, c->stream, nWindows, devXY, wtW, windowBytes); else yk_dt_launch_wins<3, false, YK_DT_ALPHA_NONE>(a, c->stream, nWindows, devXY, wtW, windowBytes); }
+    else if (fromPlane) { if (planar) yk_dt_launch_wins<4, true, YK_DT_ALPHA_PLANE>(a, c->stream, nWindows, devXY, wtW, windowBytes); else yk_dt_launch_wins<4, false, YK_DT_ALPHA_PLANE>(a, c->stream, nWindows, devXY, wtW, windowBytes); }
+    else { if (planar) yk_dt_launch_wins<4, true, YK_DT_ALPHA_CONST>(a, c->stream, nWindows, devXY, wtW, windowBytes); else yk_dt_launch_wins<4, false, YK_DT_ALPHA_CONST>(a, c->stream, nWindows, devXY, wtW, windowBytes); }
+    YK_HIP(c, hipGetLastError());
+    return yk_stage_end(c, YK_STAGE_DEC_DETILE);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@ import numpy as np
 
 from ._lib import YaikError, lib
 from .encoder import PASSES, _chk, u8_pixel_layout, u8_planar_batch_layout, u8_planar_layout
+from .files import window_origins
 
 
 class AlphaBatchPack(NamedTuple):
@@ -175,6 +176,91 @@ class HipTileDecoder:
             raise ValueError(f"window {(x0, y0, w, h)}: x0, y0, w, h must be multiples of 8 with w, h >= 8, inside the {self.w} x {self.h} image")
         _chk(self._h, lib().yk_decode_set_window(self._h, x0, y0, w, h))
         self._window = None if clear else (x0, y0, w, h)
+
+    # ---- many windows of one image: prepare once, render 64x64 blocks on demand (yk_decode_prepare_device) ---------------------
+    def prepare(self, calls: list, remap_range: int = 250, sync: bool = True) -> None:
+        """The map-sized work of the image begun, once, from the call list of decode_streams (device-resident streams; at most one "1" entry, none
+        for an image without a 1-D chunk): the corner lattice, the marks of every tile and the offsets into the 1-D streams.  No pixel is
+        written.  From here on render_window / render_windows hand out windows, each paying only for the 64x64 blocks no earlier window needed
+        and its own de-tile.  The tile bitmaps and 1-D streams are copied into the handle: with sync=True (or after synchronize()) every input
+        may be freed or overwritten.  Call it right after begin(); a window, a batch, chunks decoded already or a second prepare are the
+        library's to refuse.  Until the next begin(), decode_streams, set_window, image(), image_device(), image_window_device() and the compare
+        calls raise the library's state error; planes() is exact inside rendered blocks, tile4x4() is whole and exact."""
+        L = lib()
+        g = [c for c in calls if c[0] == "g"]
+        d1 = [c for c in calls if c[0] == "1"]
+        if len(d1) > 1 or len(g) + len(d1) != len(calls):
+            raise ValueError('prepare takes ("g", ...) entries and at most one ("1", ...) entry')
+        n = len(g)
+        ptr = lambda v: v.value if isinstance(v, C.c_void_p) else v
+        sx, sy = (C.c_int * n)(*[c[1] for c in g]), (C.c_int * n)(*[c[2] for c in g])
+        bm, nb = (C.c_void_p * n)(*[ptr(c[3]) for c in g]), (C.c_size_t * n)(*[c[4] for c in g])
+        rgb, nr = (C.c_void_p * n)(*[ptr(c[5]) for c in g]), (C.c_size_t * n)(*[c[6] for c in g])
+        typ, nty, pix, npx = (ptr(d1[0][1]), d1[0][2], ptr(d1[0][3]), d1[0][4]) if d1 else (None, 0, None, 0)
+        _chk(self._h, L.yk_decode_prepare_device(self._h, n, sx, sy, bm, nb, rgb, nr, remap_range, typ, nty, pix, npx, 15))
+        if sync:
+            _chk(self._h, L.yk_synchronize(self._h))
+
+    def prepare_from_encoder(self, enc, sync: bool = True) -> None:
+        """prepare(encoder_streams(enc)): the streams where the encoder left them in HBM, remapped like decode_from_encoder."""
+        self.prepare(self.encoder_streams(enc), 250, sync)
+
+    @property
+    def prepared_blocks(self) -> tuple:
+        """(rendered, total): how many 64x64 blocks of the prepared image have been rendered, and how many it has (yk_decode_prepared_blocks)."""
+        r, t = C.c_int(), C.c_int()
+        _chk(self._h, lib().yk_decode_prepared_blocks(self._h, C.byref(r), C.byref(t)))
+        return int(r.value), int(t.value)
+
+    def _check_windows(self, origins, w, h) -> list:
+        """x0, y0 of every window, flat, after the checks of set_window on every one of them (raises before any library call)"""
+        flat, w, h = window_origins(origins, w, h)
+        for x0, y0 in zip(flat[::2], flat[1::2]):
+            if x0 + w > self.w or y0 + h > self.h:
+                raise ValueError(f"window {(x0, y0, w, h)} is not inside the {self.w} x {self.h} image")
+        return flat
+
+    def render_windows(self, origins, w: int, h: int, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
+        """K = len(origins) windows of w x h of the prepared image, window k at origins[k] = (x0, y0), in ONE call (yk_decode_render_windows_device):
+        a torch.uint8 tensor [K, h, w, C], or [K, C, h, w] with planar=True, window k equal to the same slice of the whole decode's
+        image_device().  The blocks the windows touch that no earlier call rendered are rendered once, however many windows share them; a call
+        that finds none only de-tiles.  channels and alpha are those of image_device (a decoded 'ALPM' plane is read at each window's offset);
+        `out` follows the rules of image_batch_device: any view with unit inner stride and any row, plane and window pitch, only its pixel bytes
+        are written.  1..1024 origins; x0, y0, w, h multiples of 8 inside the image: anything else raises before any library call."""
+        import torch
+        flat = self._check_windows(origins, w, h)
+        K, ww, wh = len(flat) // 2, int(w), int(h)
+        C4 = channels if channels is not None else (4 if self._has_alpha else 3)
+        a = (-1 if self._has_alpha else 255) if alpha is None else int(alpha)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((K, C4, wh, ww) if planar else (K, wh, ww, C4), dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        if planar:
+            lay = u8_planar_batch_layout(out)
+            shape, plane_bytes = (lay.frames, lay.channels, lay.rows, lay.w), lay.plane_bytes
+        else:
+            lay = u8_pixel_layout(out, batch=True)
+            shape, plane_bytes = (lay.frames, lay.rows, lay.w, lay.channels), 0
+        want = (K, C4, wh, ww) if planar else (K, wh, ww, C4)
+        if shape != want:
+            raise ValueError(f"out has shape {shape}, the windows need {want}")
+        L = lib()
+        xy = (C.c_int * (2 * K))(*flat)
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_render_windows_device(self._h, K, xy, ww, wh, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, C4, a))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
+
+    def render_window(self, x0: int, y0: int, w: int, h: int, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
+        """One window of the prepared image: [h, w, C], or [C, h, w] with planar=True (render_windows with one origin; `out` of that shape)."""
+        self._check_windows([(x0, y0)], w, h)
+        if out is not None and hasattr(out, "unsqueeze"):
+            self.render_windows([(x0, y0)], w, h, out.unsqueeze(0), channels, alpha, planar)
+            return out
+        return self.render_windows([(x0, y0)], w, h, out, channels, alpha, planar)[0]
 
     # ---- batches: n images of one shape, every kernel launched once over all of them (yk_decode_begin_batch) --------------------------------
     def begin_batch(self, w: int, h: int, n: int):

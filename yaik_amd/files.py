@@ -2,6 +2,8 @@
 
 decode_file_device(stream)    one stream through YAIK_DecodeImageToDevice: uint8 [H, W, 3], or [H, W, 4] when the stream has an 'ALPM' chunk
 decode_file_window_device(stream, window)   a rectangle of it through YAIK_DecodeImageWindowToDevice: only the tiles the window needs are rendered
+decode_file_windows_device(stream, origins, w, h)   K windows of one size through YAIK_DecodeImageWindowsToDevice: the map-sized work of the image
+                              once, every 64x64 block the windows touch rendered once; uint8 [K, h, w, C]
 decode_files_device(streams)  n streams of one shape through YAIK_DecodeImagesToDevice: ZStd on host workers, one upload, every kernel once over
                               the batch; uint8 [N, H, W, C] or [N, C, H, W]
 encode_files_device(frames)   the other direction (yaik_encode.h, YAIK_EncodeImagesFromDevice): uint8 [N, H, W, C] frames in device memory to N
@@ -82,6 +84,11 @@ ENC6_SIGNATURES = {
 WINDOW_SIGNATURES = {
     "YAIK_DecodeImageWindowToDevice": (C.c_bool, [vp, u32, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
 }
+# yaik_decode_multiwindow.h: the same library, C linkage
+MULTIWINDOW_SIGNATURES = {
+    "YAIK_DecodeImageWindowsToDevice": (C.c_bool, [vp, u32, vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t]),
+    "YAIK_LastWindowsPrepared": (C.c_int, []),
+}
 ERROR_NAMES = ["YAIK_NO_ERROR", "YAIK_INVALID_LIBRARYCTX", "YAIK_MALLOC_FAIL", "YAIK_INVALID_CONTEXT_COUNT", "YAIK_INIT_FAIL",
                "YAIK_RELEASE_EMPTY_LIBRARY", "YAIK_INVALID_STREAM", "YAIK_INVALID_HEADER", "YAIK_NO_EMPTYDECODE_SLOT", "YAIK_DECIMG_INVALIDCTX",
                "YAIK_DECIMG_DIFFSTREAM", "YAIK_DECIMG_BUFFERNOTSET", "YAIK_INVALID_CONTEXT_MEMALLOCATOR", "YAIK_INVALID_DECOMPRESSION",
@@ -118,7 +125,7 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
-        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES}.items():
+        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _host = L
@@ -229,6 +236,57 @@ def decode_file_window_device(stream: bytes, window):
     if not L.YAIK_DecodeImageWindowToDevice(src.ctypes.data, src.size, C.byref(info), x0, y0, ww, wh):
         raise YaikFileError(L.YAIK_GetErrorCode())
     return out
+
+
+def window_origins(origins, w, h) -> tuple:
+    """((x0, y0), ...) and (w, h) as ints, (flat x0, y0 list, w, h): 1..1024 pairs, everything a multiple of 8, w, h >= 8, nothing negative.
+    Shared with HipTileDecoder.render_windows, which adds the image's bounds; here that a window lies inside the image is the library's to check."""
+    if isinstance(origins, (str, bytes)) or not hasattr(origins, "__len__"):
+        raise TypeError(f"window origins must be a sequence of (x0, y0) pairs; got {origins!r}")
+    if not 1 <= len(origins) <= 1024:
+        raise ValueError(f"1..1024 window origins are needed; got {len(origins)}")
+    flat = []
+    for o in origins:
+        if isinstance(o, (str, bytes)) or not hasattr(o, "__len__") or len(o) != 2:
+            raise TypeError(f"a window origin must be (x0, y0); got {o!r}")
+        flat += list(o)
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in flat + [w, h]):
+        raise TypeError(f"window origins and the window size must be ints; got {origins!r}, {w!r}, {h!r}")
+    flat, w, h = [int(v) for v in flat], int(w), int(h)
+    if any(v & 7 or v < 0 for v in flat) or (w | h) & 7 or w < 8 or h < 8:
+        raise ValueError(f"windows {origins!r} of {w} x {h}: x0, y0, w, h must be multiples of 8 with w, h >= 8")
+    return flat, w, h
+
+
+def decode_file_windows_device(stream: bytes, origins, w: int, h: int):
+    """K = len(origins) windows of w x h, window k at origins[k] = (x0, y0), of one stream through YAIK_DecodeImageWindowsToDevice: a torch.uint8
+    tensor [K, h, w, 3] on the GPU, or [K, h, w, 4] when the stream has an 'ALPM' chunk; window k equals
+    decode_file_device(stream)[y0:y0 + h, x0:x0 + w].  The map-sized work of the image runs once and every 64x64 block the windows touch is
+    rendered once (last_windows_prepared() tells whether the stream could take that path).  Raises YaikFileError with the library's error code (a
+    window outside the image: YAIK_DECIMG_INVALIDCTX)."""
+    import torch
+    flat, ww, wh = window_origins(origins, w, h)
+    k = len(flat) // 2
+    L, lh = host_lib(), library()
+    src = _buffer(stream)
+    info = DecodedImage()
+    if not L.YAIK_DecodeImagePre(lh, src.ctypes.data, src.size, C.byref(info)):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    dev = torch.device("cuda", _device)
+    c = 4 if has_alpha_chunk(bytes(stream)) else 3
+    out = torch.empty((k, wh, ww, c), dtype=torch.uint8, device=dev)
+    torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
+    info.outputImage, info.outputImageStride = out.data_ptr(), ww * c
+    xy = (C.c_int * (2 * k))(*flat)
+    if not L.YAIK_DecodeImageWindowsToDevice(src.ctypes.data, src.size, C.byref(info), k, xy, ww, wh, wh * ww * c):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    return out
+
+
+def last_windows_prepared() -> bool:
+    """Of the last decode_file_windows_device: True when the stream went through yk_decode_prepare_device, False when every window ran the
+    single-window chain (a '3DTL' chunk, plane-subset chunks, a chunk order of its own)."""
+    return bool(host_lib().YAIK_LastWindowsPrepared())
 
 
 def decode_files_device(streams, out=None, channels: int = 3, planar: bool = False, threads: int = 16):

@@ -4,6 +4,7 @@
 // YAIK_SetDevicePalette(1) sends the 'GTIL' payloads of whole-RGB chunks to yk_decode_gradient_palette.
 #include "yaik_decode.h"
 #include "yaik_decode_window.h"
+#include "yaik_decode_multiwindow.h"
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -533,5 +534,118 @@ bool YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_
     } while (false);
     { std::lock_guard<std::mutex> g(gLib->lock); gLib->freeStack.push_back(s); }
     if (failedIndex) *failedIndex = failed;
+    return res;
+}
+
+// ---- YAIK_DecodeImageWindowsToDevice: many windows of one stream (yaik_decode_multiwindow.h) ------------------------------------------------
+namespace { int gWindowsPrepared = 0; }
+extern "C" int YAIK_LastWindowsPrepared(void) { return gWindowsPrepared; }
+
+// the prepared path for a batchable stream: expand into the slot's staging buffer, one upload, prepare, alpha, one render call
+static bool decodeWindowsPrepared(Slot* s, const yaikplan::StreamPlan& P, uint8_t* devOut, size_t rowBytes, int nWindows, const int* xy, int ww, int wh, size_t windowBytes) {
+    using namespace yaikplan;
+    const int w = s->width, h = s->height;
+    size_t total = 0;
+    FrameStage A;
+    size_t bmBytes[NUM_PASSES];
+    for (int p = 0; p < NUM_PASSES; p++) {
+        bmBytes[p] = bitmapBytes(p, w, h);
+        if (P.grad[p].present) { A.bitmap[p] = place(total, bmBytes[p]); A.color[p] = place(total, (size_t)P.grad[p].rgbBytes + 16); }
+    }
+    if (P.has1d) { A.type = place(total, (size_t)P.typeBytes + 64); A.pix = place(total, (size_t)P.pixBytes + 64); }
+    if (P.hasAlpha) A.alpha = place(total, P.alphaBytes);
+    if (s->stage.size() < total + 16) s->stage.resize(total + 16);
+    uint8_t* const S = s->stage.data();
+    std::vector<uint8_t> pal, rgb;
+    for (int p = 0; p < NUM_PASSES; p++) {
+        const GradChunk& g = P.grad[p];
+        if (!g.present) continue;
+        if (!yaikzstd::decompress(S + A.bitmap[p], g.bitmapBytes, g.zBitmap, g.zBitmapBytes)) { setError(YAIK_INVALID_DECOMPRESSION); return false; }
+        pal.assign((size_t)g.payloadBytes + 128 * 3, 0);
+        if (!yaikzstd::decompress(pal.data(), g.payloadBytes, g.zColor, g.zColorBytes)) { setError(YAIK_INVALID_DECOMPRESSION); return false; }
+        rgb.assign((size_t)g.rgbBytes + (size_t)((w + 3) >> 2) * ((h + 3) >> 2) * 12, 0);              // PaletteDecompressor writes whole tokens: the single decoder's slack
+        if (!PaletteDecompressor(pal.data(), (int)g.payloadBytes, (int)g.payloadBytes + 128 * 3, rgb.data(), (int)g.rgbBytes, g.colorCompression)) { setError(YAIK_INVALID_STREAM); return false; }
+        memcpy(S + A.color[p], rgb.data(), g.rgbBytes);
+    }
+    if (P.has1d && !(yaikzstd::decompress(S + A.type, P.typeBytes, P.zType, P.zTypeBytes) && yaikzstd::decompress(S + A.pix, P.pixBytes, P.zPix, P.zPixBytes))) {
+        setError(YAIK_INVALID_DECOMPRESSION); return false;
+    }
+    if (P.hasAlpha && !yaikzstd::decompress(S + A.alpha, P.alphaBytes, P.zAlpha, P.zAlphaBytes)) { setError(YAIK_INVALID_DECOMPRESSION); return false; }
+    if (s->devStageCap < total + 16) {
+        if (s->devStage) { yk_device_free(s->ctx, s->devStage); s->devStage = nullptr; s->devStageCap = 0; }
+        if (yk_device_alloc(s->ctx, total + 16, &s->devStage) != YK_OK) { setError(YAIK_MALLOC_FAIL); return false; }
+        s->devStageCap = total + 16;
+    }
+    const uint8_t* const D = (const uint8_t*)s->devStage;
+    if (total && yk_device_upload(s->ctx, s->devStage, S, total) != YK_OK) { setError(YAIK_MALLOC_FAIL); return false; }
+    if (yk_decode_begin(s->ctx, w, h) != YK_OK) { setError(YAIK_MALLOC_FAIL); return false; }
+    // 'MIPM' and 'ALPM' as the single chain runs them: the mask on the host, the plane left in HBM
+    std::vector<uint8_t> mask; size_t maskBytes = 0; int32_t maskBox[4] = { 0, 0, 0, 0 };
+    if (P.hasMip) {
+        mask.assign((size_t)((w + 15) >> 4) * ((h + 15) >> 4) * 32 + 64, 0);
+        if (yk_decode_mask(s->ctx, P.mipBits, P.mipBox[2], P.mipBox[3], mask.data(), mask.size()) != YK_OK) { setError(YAIK_INVALID_STREAM); return false; }
+        maskBytes = (size_t)P.mipBox[2] * P.mipBox[3] * 32;
+        for (int k = 0; k < 4; k++) maskBox[k] = P.mipBox[k] << 4;
+    }
+    if (P.hasAlpha) {
+        const bool masked = P.alphaMode == AlphaHeader::IS_6_BIT_USEMIPMAPMASK || P.alphaMode == AlphaHeader::IS_6_BIT_USEMIPMAPMASK_INVERSE;
+        if (yk_decode_alpha(s->ctx, P.alphaMode, P.alphaBox, S + A.alpha, P.alphaBytes, masked ? mask.data() : nullptr, masked ? maskBytes : 0,
+                            masked ? maskBox : nullptr, 0) != YK_OK) { setError(YAIK_INVALID_STREAM); return false; }
+    }
+    int sx[NUM_PASSES], sy[NUM_PASSES], n = 0;
+    const uint8_t* bm[NUM_PASSES]; const uint8_t* col[NUM_PASSES]; size_t bmB[NUM_PASSES], colB[NUM_PASSES];
+    for (int p = 0; p < NUM_PASSES; p++) {
+        if (!P.grad[p].present) continue;
+        sx[n] = PASS_SHIFT[p][0]; sy[n] = PASS_SHIFT[p][1];
+        bm[n] = D + A.bitmap[p]; bmB[n] = bmBytes[p];
+        colB[n] = P.grad[p].rgbBytes; col[n] = colB[n] ? D + A.color[p] : nullptr;
+        n++;
+    }
+    if (yk_decode_prepare_device(s->ctx, n, sx, sy, bm, bmB, col, colB, 0, P.has1d ? D + A.type : nullptr, P.has1d ? P.typeBytes : 0,
+                                 P.has1d ? D + A.pix : nullptr, P.has1d ? P.pixBytes : 0, P.has1d ? P.compressionRange : 0) != YK_OK) { setError(YAIK_INVALID_STREAM); return false; }
+    if (yk_decode_render_windows_device(s->ctx, nWindows, xy, ww, wh, devOut, rowBytes, 0, windowBytes, P.hasAlpha ? 4 : 3, -1) != YK_OK ||
+        yk_synchronize(s->ctx) != YK_OK) { setError(YAIK_INVALID_STREAM); return false; }
+    return true;
+}
+
+extern "C" bool YAIK_DecodeImageWindowsToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int nWindows, const int* xy, int ww, int wh, size_t windowBytes) {
+    if (!info || !info->internalTag || !gLib) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
+    Slot* s = (Slot*)info->internalTag;
+    bool res = false;
+    gWindowsPrepared = 0;
+    do {
+        if (info->customImageOutput && info->customImageOutput != defaultImageBuilder) { setError(YAIK_DECIMG_INVALIDCTX); break; }   // a custom builder takes host planes
+        if (!info->userMemoryAllocator.customAlloc || !info->userMemoryAllocator.customFree) { setError(YAIK_INVALID_CONTEXT_MEMALLOCATOR); break; }
+        if (s->srcCheck != stream || s->srcLength != length) { setError(YAIK_DECIMG_DIFFSTREAM); break; }
+        if (!info->outputImage) { setError(YAIK_DECIMG_BUFFERNOTSET); break; }
+        const int w = s->width, h = s->height;
+        bool ok = nWindows >= 1 && nWindows <= 1024 && xy && !((ww | wh) & 7) && ww >= 8 && wh >= 8 && ww <= w && wh <= h && info->outputImageStride > 0 &&
+                  (nWindows == 1 || windowBytes / (size_t)wh >= (size_t)info->outputImageStride);
+        for (int k = 0; ok && k < nWindows; k++)
+            ok = !((xy[2 * k] | xy[2 * k + 1]) & 7) && xy[2 * k] >= 0 && xy[2 * k + 1] >= 0 && xy[2 * k] <= w - ww && xy[2 * k + 1] <= h - wh;
+        if (!ok) { setError(YAIK_DECIMG_INVALIDCTX); break; }
+        const size_t rowBytes = (size_t)info->outputImageStride;
+        yaikplan::StreamPlan P;
+        if (yaikplan::planStream(stream, length, P)) {
+            // a 1-D chunk with one empty stream decodes to zeros in the single chain; prepare takes both lengths or none
+            if (P.has1d && (!P.typeBytes || !P.pixBytes)) P.has1d = false;
+            gWindowsPrepared = 1;
+            res = decodeWindowsPrepared(s, P, info->outputImage, rowBytes, nWindows, xy, ww, wh, windowBytes);
+            break;
+        }
+        res = true;
+        for (int k = 0; k < nWindows && res; k++) {                                                   // the single-window chain, window after window
+            const int window[4] = { xy[2 * k], xy[2 * k + 1], ww, wh };
+            bool hasAlphaPlane = false;
+            res = decodeChunks(s, stream, length, hasAlphaPlane, window);
+            if (res) {
+                res = yk_decode_output_window_device(s->ctx, info->outputImage + (size_t)k * windowBytes, rowBytes, 0, hasAlphaPlane ? 4 : 3, -1) == YK_OK &&
+                      yk_synchronize(s->ctx) == YK_OK;
+                if (!res) setError(YAIK_INVALID_STREAM);
+            }
+        }
+    } while (false);
+    { std::lock_guard<std::mutex> g(gLib->lock); gLib->freeStack.push_back(s); }
+    info->internalTag = nullptr;
     return res;
 }
