@@ -633,6 +633,32 @@ int yk_decode_render_windows_device(yk_ctx* c, int nWindows, const int* xy, int 
                                     uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t windowBytes, int channels, int alpha);
 int yk_decode_prepared_blocks(yk_ctx* c, int* rendered, int* total);
 
+/* ---- outputs at reduced resolution: 1/2, 1/4 and 1/8 size ----
+ * level = 0..3, s = 1 << level.  Where the full-size call writes dec[y][x][k] of a w x h image or window, the scaled call writes
+ * (w >> level) x (h >> level) pixels
+ *     out[Y][X][k] = (sum over dy, dx < s of dec[s Y + dy][s X + dx][k]  +  s s / 2) >> (2 level):
+ * the box mean, halves rounded up, computed from the level-0 bytes in integers (not from the rounded means of the level before).  Alpha is
+ * averaged like a colour channel, without premultiplication: alpha = -1 averages the decoded plane, a constant stays that constant.  Sides and
+ * windows are multiples of 8, so every level divides exactly and the reduced window is the crop of the reduced image.  The reduction runs in the
+ * de-tile kernel on the lanes that hold a tile's bytes: the planes are read once and only the reduced pixels are written; the planes are not
+ * changed.  level = 0 forwards to the full-size call.  Layout rules are those of the full-size calls (HWC with planeBytes == 0, CHW otherwise, any
+ * base and pitch, only pixel bytes written); every pitch, plane, frame and window check is made against the REDUCED width and height.  A level
+ * outside 0..3 is YK_ERR_BAD_ARG; the further refusals are those of the full-size calls; every refusal comes before the first launch and writes
+ * nothing.  No host synchronisation: ordering is the caller's, as for yk_decode_output_device.  Each call is one YK_STAGE_DEC_DETILE interval.
+ * yk_decode_output_scaled_device: the image begun, or the selected frame of a batch; with a window set (yk_decode_set_window) the reduced window,
+ * under the state rules of yk_decode_output_window_device.  Unmarked cells are settled first.  On a prepared image: YK_ERR_STATE, with a message
+ * that names yk_decode_render_windows_scaled_device.
+ * yk_decode_output_scaled_batch_device: every frame of a decode batch in one launch, frame f at devOut + f * frameBytes; alpha = -1 reads the
+ * planes of yk_decode_alpha[_mask]_batch_device (YK_ERR_STATE when the batch has none), 0..255 is a constant.
+ * yk_decode_render_windows_scaled_device: yk_decode_render_windows_device with reduced crops.  xy, ww and wh are full-resolution pixels under the
+ * rule of yk_decode_set_window; the blocks the windows touch are rendered at full size, each at most once per prepared image -- the bitmap of
+ * rendered blocks is the one of the full-size call, so the two may be mixed freely -- and the gradient and 1-D intervals are recorded as there;
+ * window k goes to devOut + k * windowBytes at (ww >> level) x (wh >> level). */
+int yk_decode_output_scaled_device(yk_ctx* c, int level, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha);
+int yk_decode_output_scaled_batch_device(yk_ctx* c, int level, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha);
+int yk_decode_render_windows_scaled_device(yk_ctx* c, int level, int nWindows, const int* xy, int ww, int wh,
+                                           uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t windowBytes, int channels, int alpha);
+
 /* ---- decode batches: nFrames images of ONE shape on a handle, every kernel launched once over nFrames x blocks ----
  * A frame of 2048 x 2048 or less is a fraction of the grids the decode kernels were tuned on, and one image costs about a dozen dependent stream
  * operations; a batch costs the same dozen.  yk_decode_begin_batch allocates the 8x8-tiled planes, the mapRGB lattice, its `loaded` flags, the

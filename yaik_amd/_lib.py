@@ -152,6 +152,9 @@ SIGNATURES = {
     "yk_decode_prepare_device": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, sz, vp, sz, C.c_int]),
     "yk_decode_render_windows_device": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, sz, sz, sz, C.c_int, C.c_int]),
     "yk_decode_prepared_blocks": (C.c_int, [vp, ip, ip]),
+    "yk_decode_output_scaled_device": (C.c_int, [vp, C.c_int, vp, sz, sz, C.c_int, C.c_int]),
+    "yk_decode_output_scaled_batch_device": (C.c_int, [vp, C.c_int, vp, sz, sz, sz, C.c_int, C.c_int]),
+    "yk_decode_render_windows_scaled_device": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, sz, sz, sz, C.c_int, C.c_int]),
     "yk_decode_tile4x4": (C.c_int, [vp, vp, sz]),
     "yk_decode_tile4x4_planes": (C.c_int, [vp, vp, sz]),
     "yk_decode_begin_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),

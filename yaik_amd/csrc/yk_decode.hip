@@ -1048,6 +1048,196 @@ static int yk_dec_detile(yk_ctx* c, uint8_t* out, size_t rowBytes, size_t planeB
     return yk_stage_end(c, YK_STAGE_DEC_DETILE);
 }
 
+// ---- the de-tile at reduced resolution (yk_decode_output_scaled_device and its kin) ---------------------------------------------
+// LEVEL 1, 2, 3: s = 1 << LEVEL, out[Y][X][k] = (sum of the s x s box of the whole decode at (s X, s Y) + s s / 2) >> (2 LEVEL), straight from the
+// level-0 bytes.  A box never crosses an 8x8 tile, so the lanes that hold a tile's bytes reduce them: the loads, the lane mapping, the units and
+// the steps are those of the kernels above (a lane owns the row pair rp of a tile, four lanes a tile, all loads of a workgroup before its first
+// store); only what is stored differs.  Sums stay packed: a dword holds two 16-bit sums (the largest, 64 * 255, fits), rounded once at the end.
+//   LEVEL 1: the row pair is one output row of 4 pixels; every lane stores, at row 4 ty + rp.
+//   LEVEL 2: the row pair gives the upper or lower half of 2 pixels; lanes rp ^ 1 exchange halves (DPP quad_perm, no LDS), the even lane stores
+//            at row 2 ty + rp / 2.
+//   LEVEL 3: the 16 bytes of the lane are summed (v_sad_u8), lanes rp ^ 1 and then rp ^ 2 add up, lane rp == 0 stores the tile's pixel.
+// The four lanes of a tile share its index, so a quad is active or idle as a whole on the last-workgroup path and the exchanges read live lanes.
+// Adjacent tiles of a wave write adjacent bytes of an output row, as above.  The alpha plane (linear, two 8-byte rows per lane) has the shape
+// of a lane's plane bytes and takes the same reduction.
+__device__ __forceinline__ uint32_t yk_dts_quad_xor1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true); }   // quad_perm [1, 0, 3, 2]
+__device__ __forceinline__ uint32_t yk_dts_quad_xor2(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true); }   // quad_perm [2, 3, 0, 1]
+// the two 2x2 box sums of 4 columns of a row pair, as 16-bit halves (each <= 1020)
+__device__ __forceinline__ uint32_t yk_dts_pairs(uint32_t top, uint32_t bot) {
+    const uint32_t m = 0x00ff00ffu;
+    return (top & m) + ((top >> 8) & m) + (bot & m) + ((bot >> 8) & m);
+}
+// a lane's 16 bytes of one plane (.x .y = row 0, .z .w = row 1) -> the 4 >> (LEVEL - 1) pixels its quad owes for them, pixel p in byte p
+// (LEVEL 2: valid in both lanes of a pair; LEVEL 3: in all four)
+template <int LEVEL>
+__device__ __forceinline__ uint32_t yk_dts_reduce(const yk_dt4 p) {
+    if constexpr (LEVEL == 1) {
+        const uint32_t lo = ((yk_dts_pairs(p.x, p.z) + 0x00020002u) >> 2) & 0x00ff00ffu;          // pixels 0, 1 in bytes 0, 2
+        const uint32_t hi = ((yk_dts_pairs(p.y, p.w) + 0x00020002u) >> 2) & 0x00ff00ffu;          // pixels 2, 3
+        return __builtin_amdgcn_perm(hi, lo, 0x06040200u);
+    } else if constexpr (LEVEL == 2) {
+        // 2 rows x 4 columns: the left box in the low half, the right box in the high half (each <= 2040, <= 4080 with the other lane's)
+        uint32_t t = __builtin_amdgcn_sad_u8(p.x, 0u, __builtin_amdgcn_sad_u8(p.z, 0u, 0u)) | (__builtin_amdgcn_sad_u8(p.y, 0u, __builtin_amdgcn_sad_u8(p.w, 0u, 0u)) << 16);
+        t += yk_dts_quad_xor1(t);
+        t = ((t + 0x00080008u) >> 4) & 0x00ff00ffu;
+        return __builtin_amdgcn_perm(0u, t, 0x0c0c0200u);
+    } else {
+        uint32_t s = __builtin_amdgcn_sad_u8(p.x, 0u, __builtin_amdgcn_sad_u8(p.y, 0u, __builtin_amdgcn_sad_u8(p.z, 0u, __builtin_amdgcn_sad_u8(p.w, 0u, 0u))));
+        s += yk_dts_quad_xor1(s);
+        s += yk_dts_quad_xor2(s);                                                                  // <= 64 * 255
+        return (s + 32u) >> 6;
+    }
+}
+// NP = 4 >> (LEVEL - 1) pixels of an output row (pixel p of a channel in byte p of its dword) -> their bytes at o (HWC) or o + k * planeBytes (CHW)
+template <int C, bool PLANAR, int LEVEL>
+__device__ __forceinline__ void yk_dts_emit(uint8_t* o, size_t planeBytes, uint32_t r, uint32_t g, uint32_t b, uint32_t al) {
+    constexpr int NP = 4 >> (LEVEL - 1);
+    if constexpr (PLANAR) {
+        const uint32_t v[4] = { r, g, b, al };
+#pragma unroll
+        for (int k = 0; k < C; k++) __builtin_memcpy(o + (size_t)k * planeBytes, &v[k], NP);
+    } else if constexpr (LEVEL == 1 && C == 3) {
+        const uint32_t rg0 = __builtin_amdgcn_perm(g, r, 0x05010400u), rg1 = __builtin_amdgcn_perm(g, r, 0x07030602u);
+        const uint32_t wd[3] = { __builtin_amdgcn_perm(b, rg0, 0x02040100u), __builtin_amdgcn_perm(rg1, __builtin_amdgcn_perm(b, g, 0x05010400u), 0x05040302u),
+                                 __builtin_amdgcn_perm(b, rg1, 0x07030206u) };
+        __builtin_memcpy(o, wd, 12);
+    } else if constexpr (LEVEL == 1) {
+        const uint32_t rgL = __builtin_amdgcn_perm(g, r, 0x05010400u), rgH = __builtin_amdgcn_perm(g, r, 0x07030602u);
+        const uint32_t baL = __builtin_amdgcn_perm(al, b, 0x05010400u), baH = __builtin_amdgcn_perm(al, b, 0x07030602u);
+        const yk_dt4 px = { __builtin_amdgcn_perm(baL, rgL, 0x05040100u), __builtin_amdgcn_perm(baL, rgL, 0x07060302u),
+                            __builtin_amdgcn_perm(baH, rgH, 0x05040100u), __builtin_amdgcn_perm(baH, rgH, 0x07060302u) };
+        __builtin_memcpy(o, &px, 16);
+    } else {
+        const uint32_t rg = __builtin_amdgcn_perm(g, r, 0x05010400u);                              // r0 g0 r1 g1
+        if constexpr (C == 3) {
+            const uint32_t wd[2] = { __builtin_amdgcn_perm(b, rg, 0x02040100u), __builtin_amdgcn_perm(b, rg, 0x0c0c0503u) };   // r0 g0 b0 r1 | g1 b1
+            __builtin_memcpy(o, wd, 3 * NP);
+        } else {
+            const uint32_t ba = __builtin_amdgcn_perm(al, b, 0x05010400u);                         // b0 a0 b1 a1
+            const uint32_t wd[2] = { __builtin_amdgcn_perm(ba, rg, 0x05040100u), __builtin_amdgcn_perm(ba, rg, 0x07060302u) };
+            __builtin_memcpy(o, wd, 4 * NP);
+        }
+    }
+}
+
+struct YkDtsUnit { yk_dt4 r, g, b, a; size_t o; };
+
+// tile `src` of the planes, whose reduced pixels go to tile position (jx, jy) of the destination; the alpha plane is read at (8 jx, 8 jy)
+template <int C, bool PLANAR, int ASRC, int LEVEL>
+__device__ __forceinline__ void yk_dts_load(const YkDetileArgs& a, size_t src, uint32_t jx, uint32_t jy, uint32_t rp, YkDtsUnit& u) {
+    const size_t ti = src * 64 + rp * 16;
+    u.r = *reinterpret_cast<const yk_dt4*>(a.planes + ti);
+    u.g = *reinterpret_cast<const yk_dt4*>(a.planes + a.planeSize + ti);
+    u.b = *reinterpret_cast<const yk_dt4*>(a.planes + 2 * a.planeSize + ti);
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) {
+        const size_t y = (size_t)jy * 8 + rp * 2, x = (size_t)jx * 8;
+        uint32_t al[4];
+        __builtin_memcpy(&al[0], a.alpha + y * a.strideA + x, 8);
+        __builtin_memcpy(&al[2], a.alpha + (y + 1) * a.strideA + x, 8);
+        u.a = yk_dt4{ al[0], al[1], al[2], al[3] };
+    }
+    u.o = ((size_t)jy * (8 >> LEVEL) + (rp >> (LEVEL - 1))) * a.rowBytes + (size_t)jx * (8 >> LEVEL) * (PLANAR ? 1 : C);
+}
+template <int C, bool PLANAR, int ASRC, int LEVEL>
+__device__ __forceinline__ void yk_dts_store(const YkDetileArgs& a, const YkDtsUnit& u, uint32_t rp) {
+    const uint32_t r = yk_dts_reduce<LEVEL>(u.r), g = yk_dts_reduce<LEVEL>(u.g), b = yk_dts_reduce<LEVEL>(u.b);
+    uint32_t al = a.alphaConst;                                               // a constant is its own mean
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) al = yk_dts_reduce<LEVEL>(u.a);
+    if ((rp & ((1u << (LEVEL - 1)) - 1)) == 0) yk_dts_emit<C, PLANAR, LEVEL>(a.out + u.o, a.planeBytes, r, g, b, al);
+}
+// WIN: the tiles of the window wn, row-major (yk_dt_load_win's addressing); otherwise the image's tiles in plane order
+template <int C, bool PLANAR, int ASRC, int LEVEL, bool WIN>
+__device__ __forceinline__ void yk_dts_unit(const YkDetileArgs& a, const YkDetileWin& wn, uint32_t j, uint32_t rp, YkDtsUnit& u) {
+    const uint32_t rowW = WIN ? wn.wtW : a.tileW;
+    const uint32_t jy = j / rowW, jx = j - jy * rowW;
+    const size_t src = WIN ? (size_t)(wn.ty0 + jy) * a.tileW + wn.tx0 + jx : (size_t)j;
+    yk_dts_load<C, PLANAR, ASRC, LEVEL>(a, src, jx, jy, rp, u);
+}
+template <int C, bool PLANAR, int ASRC, int LEVEL, bool WIN>
+__device__ __forceinline__ void yk_dec_detile_scaled_body(const YkDetileArgs& a, const YkDetileWin& wn, const uint32_t bx) {
+    const uint32_t lane = threadIdx.x & 63, rp = lane & 3;
+    const uint32_t j0 = (bx * (YK_DT_K * 4) + (threadIdx.x >> 6)) * 16 + (lane >> 2);
+    if ((bx + 1) * (uint32_t)YK_DT_TILES <= a.nTiles) {
+        YkDtsUnit u[YK_DT_K];                                                 // every unit of the workgroup exists: all loads first
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) yk_dts_unit<C, PLANAR, ASRC, LEVEL, WIN>(a, wn, j0 + k * 64, rp, u[k]);
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) yk_dts_store<C, PLANAR, ASRC, LEVEL>(a, u[k], rp);
+        return;
+    }
+    for (int k = 0; k < YK_DT_K; k++) {                                       // the last workgroup: tiles up to nTiles, whole quads
+        const uint32_t j = j0 + k * 64;
+        if (j >= a.nTiles) continue;
+        YkDtsUnit u;
+        yk_dts_unit<C, PLANAR, ASRC, LEVEL, WIN>(a, wn, j, rp, u);
+        yk_dts_store<C, PLANAR, ASRC, LEVEL>(a, u, rp);
+    }
+}
+// the selected frame (gridDim.y == 1, strides unused) or every frame of a batch: frame blockIdx.y as in yk_dec_detile_batch_kernel
+template <int C, bool PLANAR, int ASRC, int LEVEL>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_scaled_batch_kernel(YkDetileArgs a, size_t planesFrame, size_t outFrame, size_t alphaFrame) {
+    a.planes += (size_t)blockIdx.y * planesFrame; a.out += (size_t)blockIdx.y * outFrame;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) a.alpha += (size_t)blockIdx.y * alphaFrame;
+    yk_dec_detile_scaled_body<C, PLANAR, ASRC, LEVEL, false>(a, YkDetileWin{ 0, 0, a.tileW }, blockIdx.x);
+}
+template <int C, bool PLANAR, int ASRC, int LEVEL>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_scaled_win_kernel(YkDetileArgs a, const YkDetileWin wn) {
+    yk_dec_detile_scaled_body<C, PLANAR, ASRC, LEVEL, true>(a, wn, blockIdx.x);
+}
+// K windows of a prepared image, as in yk_dec_detile_wins_kernel; windowBytes apart at the reduced size
+template <int C, bool PLANAR, int ASRC, int LEVEL>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_scaled_wins_kernel(YkDetileArgs a, const int* __restrict__ xy, uint32_t wtW, size_t windowBytes) {
+    const uint32_t k = blockIdx.y;
+    const uint32_t x0 = (uint32_t)xy[2 * k], y0 = (uint32_t)xy[2 * k + 1];
+    a.out += (size_t)k * windowBytes;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) a.alpha += (size_t)y0 * a.strideA + x0;
+    yk_dec_detile_scaled_body<C, PLANAR, ASRC, LEVEL, true>(a, YkDetileWin{ x0 >> 3, y0 >> 3, wtW }, blockIdx.x);
+}
+
+// which of the three kernels a scaled de-tile is: K windows from a table (nWindows > 0), the window *wn, or nFrames frames (0: the selected one)
+struct YkDtsForm { int nFrames; size_t planesFrame, outFrame, alphaFrame; const YkDetileWin* wn; int nWindows; const int* devXY; uint32_t wtW; size_t windowBytes; };
+
+template <int C, bool PLANAR, int ASRC, int LEVEL>
+static void yk_dts_launch_level(const YkDetileArgs& a, hipStream_t s, const YkDtsForm& f) {
+    const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
+    if (f.nWindows) hipLaunchKernelGGL((yk_dec_detile_scaled_wins_kernel<C, PLANAR, ASRC, LEVEL>), dim3(gx, (unsigned)f.nWindows), dim3(YK_DT_THREADS), 0, s, a, f.devXY, f.wtW, f.windowBytes);
+    else if (f.wn) hipLaunchKernelGGL((yk_dec_detile_scaled_win_kernel<C, PLANAR, ASRC, LEVEL>), dim3(gx), dim3(YK_DT_THREADS), 0, s, a, *f.wn);
+    else hipLaunchKernelGGL((yk_dec_detile_scaled_batch_kernel<C, PLANAR, ASRC, LEVEL>), dim3(gx, (unsigned)(f.nFrames ? f.nFrames : 1)), dim3(YK_DT_THREADS), 0, s, a,
+                            f.planesFrame, f.outFrame, f.alphaFrame);
+}
+template <int C, bool PLANAR, int ASRC>
+static void yk_dts_launch(const YkDetileArgs& a, hipStream_t s, const YkDtsForm& f, int level) {
+    if (level == 1) yk_dts_launch_level<C, PLANAR, ASRC, 1>(a, s, f);
+    else if (level == 2) yk_dts_launch_level<C, PLANAR, ASRC, 2>(a, s, f);
+    else yk_dts_launch_level<C, PLANAR, ASRC, 3>(a, s, f);
+}
+// level 1..3; a: the arguments of the full-size launch (tiles, pitches of the REDUCED destination); one YK_STAGE_DEC_DETILE interval
+static int yk_dts_run(yk_ctx* c, const YkDetileArgs& a, const YkDtsForm& f, int level, int channels) {
+    const bool planar = a.planeBytes > 0;
+    { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    if (channels == 3) { if (planar) yk_dts_launch<3, true, YK_DT_ALPHA_NONE>(a, c->stream, f, level); else yk_dts_launch<3, false, YK_DT_ALPHA_NONE>(a, c->stream, f, level); }
+    else if (a.alpha)  { if (planar) yk_dts_launch<4, true, YK_DT_ALPHA_PLANE>(a, c->stream, f, level); else yk_dts_launch<4, false, YK_DT_ALPHA_PLANE>(a, c->stream, f, level); }
+    else               { if (planar) yk_dts_launch<4, true, YK_DT_ALPHA_CONST>(a, c->stream, f, level); else yk_dts_launch<4, false, YK_DT_ALPHA_CONST>(a, c->stream, f, level); }
+    YK_HIP(c, hipGetLastError());
+    return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+}
+// yk_dec_detile at level 1..3: the same arguments, the destination at the reduced size
+static int yk_dec_detile_scaled(yk_ctx* c, int level, uint8_t* out, size_t rowBytes, size_t planeBytes, int channels, const uint8_t* alpha, size_t strideA, int alphaConst,
+                                int nFrames = 0, size_t frameBytes = 0, size_t alphaFrame = 0, bool window = false) {
+    YkDetileArgs a;
+    a.planes = yk_dec_frame(c, nFrames ? 0 : c->dCur).planes; a.planeSize = c->dPlaneSize;
+    a.alpha = alpha; a.strideA = strideA; a.alphaConst = (uint32_t)(alphaConst & 255) * 0x01010101u;
+    a.out = out; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
+    a.tileW = (uint32_t)(c->dw >> 3); a.nTiles = (uint32_t)(c->dw >> 3) * (uint32_t)(c->dh >> 3);
+    const YkDetileWin win = { (uint32_t)(c->dWinX >> 3), (uint32_t)(c->dWinY >> 3), (uint32_t)(c->dWinW >> 3) };
+    if (window) {
+        a.nTiles = (uint32_t)(c->dWinW >> 3) * (uint32_t)(c->dWinH >> 3);
+        if (alpha) a.alpha = alpha + (size_t)c->dWinY * strideA + (size_t)c->dWinX;
+    }
+    const YkDtsForm f = { nFrames, c->dStride.planes, frameBytes, alphaFrame, window ? &win : nullptr, 0, nullptr, 0, 0 };
+    return yk_dts_run(c, a, f, level, channels);
+}
+
 // The reference's RGBA branch as it executes (decoder/YAIK_DefaultCallback.cpp:45-62): the alpha store does not advance dst, so a row is
 // w RGB triples followed by ONE alpha byte; the alpha row cursors advance w bytes per tile row instead of 8 * strideA (:36-39 vs
 // :128-130), so row y ends on the byte alpha[strideA * (y & 7) + w * (y >> 3) + w - 1].  One thread per row writes that byte.
@@ -1788,6 +1978,55 @@ int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBy
     return yk_dec_detile(c, devOut, rowBytes, planeBytes, 4, c->dAlpha, w, 0, c->dFrames, frameBytes, c->dAlphaStride);
 }
 
+// ---- outputs at reduced resolution (include/yaik_hip.h): level 0 is the full-size call, 1..3 the box means of 2x2, 4x4, 8x8 ----------
+int yk_decode_output_scaled_device(yk_ctx* c, int level, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (level < 0 || level > 3) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: level must be 0..3");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_device: yk_decode_begin first");
+    if (c->dPrepared)
+        return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_device: this image is prepared for windows (yk_decode_prepare_device); yk_decode_render_windows_scaled_device reads it");
+    if (level == 0) return yk_decode_output_window_device(c, devOut, rowBytes, planeBytes, channels, alpha);
+    if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: devOut is NULL");
+    if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: alpha must be -1 (the decoded plane) or 0..255");
+    const bool window = c->dWinSet;
+    const size_t w = (size_t)(window ? c->dWinW : c->dw) >> level, h = (size_t)(window ? c->dWinH : c->dh) >> level;
+    if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: row or plane pitch too small for the reduced image or window");
+    const bool fromPlane = channels == 4 && alpha < 0;
+    if (fromPlane && !c->dAlphaValid) return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_device: alpha = -1 needs yk_decode_alpha first");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    return yk_dec_detile_scaled(c, level, devOut, rowBytes, planeBytes, channels, fromPlane ? yk_dec_alpha_cur(c) : nullptr, (size_t)c->dw, fromPlane ? 0 : alpha, 0, 0, 0, window);
+}
+
+int yk_decode_output_scaled_batch_device(yk_ctx* c, int level, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (level < 0 || level > 3) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_batch_device: level must be 0..3");
+    if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_batch_device: channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_batch_device: alpha must be -1 (the planes of yk_decode_alpha[_mask]_batch_device) or 0..255");
+    const bool fromPlanes = channels == 4 && alpha < 0;
+    if (level == 0) {
+        if (fromPlanes) return yk_decode_output_batch_alpha_device(c, devOut, rowBytes, planeBytes, frameBytes);
+        return yk_decode_output_batch_device(c, devOut, rowBytes, planeBytes, frameBytes, channels, channels == 4 ? alpha : 255);
+    }
+    if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_batch_device: devOut is NULL");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_batch_device: yk_decode_begin_batch first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_output_scaled_batch_device");
+    if (fromPlanes && (!c->dAlphaValid || !c->dAlphaBatch))
+        return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_batch_device: alpha = -1 needs yk_decode_alpha_batch_device first: the batch has no decoded alpha planes");
+    const size_t w = (size_t)c->dw >> level, h = (size_t)c->dh >> level;
+    if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_batch_device: row or plane pitch too small for the reduced image");
+    if (c->dFrames > 1 && (planeBytes == 0 ? frameBytes / h < rowBytes : frameBytes / (size_t)channels < planeBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_batch_device: frame stride too small for a reduced frame");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    return yk_dec_detile_scaled(c, level, devOut, rowBytes, planeBytes, channels, fromPlanes ? c->dAlpha : nullptr, (size_t)c->dw, fromPlanes ? 0 : alpha, c->dFrames, frameBytes,
+                                fromPlanes ? c->dAlphaStride : 0);
+}
+
 // ---- round-trip quality: the decode against a source in HBM (kernels and the read-back: yk_quality.hip) ----
 // the checks the three entry points share; batch: every frame (else the selected one)
 static int yk_dec_compare_common(yk_ctx* c, int channels, const void* out, bool batch) {
@@ -1970,6 +2209,48 @@ int yk_decode_prepared_blocks(yk_ctx* c, int* rendered, int* total) {
     return YK_OK;
 }
 
+// The render half of yk_decode_render_windows[_scaled]_device, after every check: the 64x64 blocks the windows touch that no earlier call rendered
+// (full size, the bitmap is shared by both calls), and the windows' origins in HBM behind the block list (*devXYOut)
+static int yk_dec_render_new_blocks(yk_ctx* c, int nWindows, const int* xy, int ww, int wh, const int** devXYOut) {
+    YkDecPrepared& P = *c->dPrep;
+    YK_HIP(c, hipSetDevice(c->device));
+    const int w = c->dw, h = c->dh, latW = w / 4 + 1, tilesW = w >> 3, tilesH = h >> 3, stride4 = (w + 15) >> 4;
+    const YkDecView V = yk_dec_frame(c);
+    // the table's buffer and its pinned slot before the bitmap changes: a refusal up to here leaves every block as it was
+    const size_t maxList = (size_t)yk_wb_total(P.blocks), words = maxList + 2 * (size_t)nWindows;
+    YK_HIP(c, P.table.reserve(c->stream, maxList + 2 * 1024));                  // prepare has reserved this: no allocation here
+    int slot; void* host;
+    { const int rc = yk_dec_table_host(c, words * 4, &slot, &host); if (rc) return rc; }
+    yk_wb_take(P.blocks, nWindows, xy, ww, wh, P.list);
+    const size_t nList = P.list.size();
+    uint32_t* tab = static_cast<uint32_t*>(host);
+    for (size_t i = 0; i < nList; i++) tab[i] = P.list[i];
+    for (int i = 0; i < 2 * nWindows; i++) tab[nList + i] = (uint32_t)xy[i];
+    { const int rc = yk_dec_table_upload(c, slot, P.table, (nList + 2 * (size_t)nWindows) * 4); if (rc) return rc; }
+    const uint32_t* devList = P.table;
+    *devXYOut = reinterpret_cast<const int*>(P.table + nList);
+    if (nList) {
+        const uint32_t xB64 = (uint32_t)P.blocks.nbx, nTiles = (uint32_t)nList * 64u;
+        { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
+        hipLaunchKernelGGL(yk_decall_render_blocks_list_kernel, dim3((unsigned)nList), dim3(256), 0, c->stream, P.pl, w, h, latW, V.mapRGB, V.planes, c->dPlaneSize, tilesW,
+                           reinterpret_cast<uint32_t*>(V.tile4), stride4, devList);
+        if (!P.has1d)                                                           // no 1-D chunk: what no gradient tile covers reads as zero
+            hipLaunchKernelGGL(yk_dec_zero_unmarked_list_kernel, dim3((nTiles + 255) / 256, 3), dim3(256), 0, c->stream, V.tile4, c->dTile4Size, stride4, tilesW, tilesH,
+                               devList, xB64, nTiles, V.planes, c->dPlaneSize);
+        YK_HIP(c, hipGetLastError());
+        { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
+        if (P.has1d) {
+            const D1List ls = { devList, xB64, (uint32_t)tilesW, (uint32_t)tilesH };
+            { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
+            hipLaunchKernelGGL(yk_dec1d_list_kernel, dim3((nTiles + 64 * YK_D1_TPL - 1) / (64 * YK_D1_TPL), 3), dim3(256), 0, c->stream, (const uint32_t*)P.offInBlk, (size_t)nTiles, ls,
+                               (const uint32_t*)P.bT, (const uint32_t*)P.bP, (const uint32_t*)P.tot, P.type, P.typeBytes, P.pix, P.pixBytes, P.invRange, V.planes, c->dPlaneSize);
+            YK_HIP(c, hipGetLastError());
+            { int rc2 = yk_stage_end(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
+        }
+    }
+    return YK_OK;
+}
+
 int yk_decode_render_windows_device(yk_ctx* c, int nWindows, const int* xy, int ww, int wh, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t windowBytes,
                                     int channels, int alpha) {
     if (!c) return YK_ERR_BAD_ARG;
@@ -1990,41 +2271,10 @@ int yk_decode_render_windows_device(yk_ctx* c, int nWindows, const int* xy, int 
         return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_device: window stride too small for a window");
     const bool fromPlane = channels == 4 && alpha < 0;
     if (fromPlane && !c->dAlphaValid) return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_device: alpha = -1 needs yk_decode_alpha first");
-    YK_HIP(c, hipSetDevice(c->device));
-    const int w = c->dw, h = c->dh, latW = w / 4 + 1, tilesW = w >> 3, tilesH = h >> 3, stride4 = (w + 15) >> 4;
+    const int* devXY = nullptr;
+    { const int rc = yk_dec_render_new_blocks(c, nWindows, xy, ww, wh, &devXY); if (rc) return rc; }
     const YkDecView V = yk_dec_frame(c);
-    // the table's buffer and its pinned slot before the bitmap changes: a refusal up to here leaves every block as it was
-    const size_t maxList = (size_t)yk_wb_total(P.blocks), words = maxList + 2 * (size_t)nWindows;
-    YK_HIP(c, P.table.reserve(c->stream, maxList + 2 * 1024));                  // prepare has reserved this: no allocation here
-    int slot; void* host;
-    { const int rc = yk_dec_table_host(c, words * 4, &slot, &host); if (rc) return rc; }
-    yk_wb_take(P.blocks, nWindows, xy, ww, wh, P.list);
-    const size_t nList = P.list.size();
-    uint32_t* tab = static_cast<uint32_t*>(host);
-    for (size_t i = 0; i < nList; i++) tab[i] = P.list[i];
-    for (int i = 0; i < 2 * nWindows; i++) tab[nList + i] = (uint32_t)xy[i];
-    { const int rc = yk_dec_table_upload(c, slot, P.table, (nList + 2 * (size_t)nWindows) * 4); if (rc) return rc; }
-    const uint32_t* devList = P.table;
-    const int* devXY = reinterpret_cast<const int*>(P.table + nList);
-    if (nList) {
-        const uint32_t xB64 = (uint32_t)P.blocks.nbx, nTiles = (uint32_t)nList * 64u;
-        { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
-        hipLaunchKernelGGL(yk_decall_render_blocks_list_kernel, dim3((unsigned)nList), dim3(256), 0, c->stream, P.pl, w, h, latW, V.mapRGB, V.planes, c->dPlaneSize, tilesW,
-                           reinterpret_cast<uint32_t*>(V.tile4), stride4, devList);
-        if (!P.has1d)                                                           // no 1-D chunk: what no gradient tile covers reads as zero
-            hipLaunchKernelGGL(yk_dec_zero_unmarked_list_kernel, dim3((nTiles + 255) / 256, 3), dim3(256), 0, c->stream, V.tile4, c->dTile4Size, stride4, tilesW, tilesH,
-                               devList, xB64, nTiles, V.planes, c->dPlaneSize);
-        YK_HIP(c, hipGetLastError());
-        { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
-        if (P.has1d) {
-            const D1List ls = { devList, xB64, (uint32_t)tilesW, (uint32_t)tilesH };
-            { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
-            hipLaunchKernelGGL(yk_dec1d_list_kernel, dim3((nTiles + 64 * YK_D1_TPL - 1) / (64 * YK_D1_TPL), 3), dim3(256), 0, c->stream, (const uint32_t*)P.offInBlk, (size_t)nTiles, ls,
-                               (const uint32_t*)P.bT, (const uint32_t*)P.bP, (const uint32_t*)P.tot, P.type, P.typeBytes, P.pix, P.pixBytes, P.invRange, V.planes, c->dPlaneSize);
-            YK_HIP(c, hipGetLastError());
-            { int rc2 = yk_stage_end(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
-        }
-    }
+    const int w = c->dw, tilesW = w >> 3;
     YkDetileArgs a;
     a.planes = V.planes; a.planeSize = c->dPlaneSize;
     a.alpha = fromPlane ? yk_dec_alpha_cur(c) : nullptr; a.strideA = (size_t)w; a.alphaConst = (uint32_t)((fromPlane ? 0 : alpha) & 255) * 0x01010101u;
@@ -2038,6 +2288,41 @@ int yk_decode_render_windows_device(yk_ctx* c, int nWindows, const int* xy, int 
     else { if (planar) yk_dt_launch_wins<4, true, YK_DT_ALPHA_CONST>(a, c->stream, nWindows, devXY, wtW, windowBytes); else yk_dt_launch_wins<4, false, YK_DT_ALPHA_CONST>(a, c->stream, nWindows, devXY, wtW, windowBytes); }
     YK_HIP(c, hipGetLastError());
     return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+}
+
+// yk_decode_render_windows_device with reduced crops: the same render of new blocks (full size, the shared bitmap), then the scaled de-tile
+int yk_decode_render_windows_scaled_device(yk_ctx* c, int level, int nWindows, const int* xy, int ww, int wh, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
+                                           size_t windowBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (level < 0 || level > 3) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_scaled_device: level must be 0..3");
+    if (level == 0) return yk_decode_render_windows_device(c, nWindows, xy, ww, wh, devOut, rowBytes, planeBytes, windowBytes, channels, alpha);
+    if (!yk_dec_begun(c) || !c->dPrepared) return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_scaled_device: yk_decode_prepare_device first");
+    YkDecPrepared& P = *c->dPrep;
+    if (P.blocks.w != c->dw || P.blocks.h != c->dh)
+        return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_scaled_device: the prepared image is not the one this handle holds; yk_decode_begin and yk_decode_prepare_device again");
+    if (nWindows < 1 || nWindows > 1024) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_scaled_device: nWindows must be 1..1024");
+    if (!xy) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_scaled_device: the window table is NULL");
+    if (!yk_wb_windows_ok(P.blocks, nWindows, xy, ww, wh))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_scaled_device: x0, y0, ww, wh (full-resolution pixels) must be multiples of 8 with ww, wh >= 8 and every window inside the image");
+    if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_scaled_device: devOut is NULL");
+    if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_scaled_device: channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_scaled_device: alpha must be -1 (the decoded plane) or 0..255");
+    const size_t rw = (size_t)ww >> level, rh = (size_t)wh >> level;
+    if (planeBytes == 0 ? rowBytes < rw * channels : (rowBytes < rw || planeBytes / rh < rowBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_scaled_device: row or plane pitch too small for the reduced window");
+    if (nWindows > 1 && (planeBytes == 0 ? windowBytes / rh < rowBytes : windowBytes / (size_t)channels < planeBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_scaled_device: window stride too small for a reduced window");
+    const bool fromPlane = channels == 4 && alpha < 0;
+    if (fromPlane && !c->dAlphaValid) return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_scaled_device: alpha = -1 needs yk_decode_alpha first");
+    const int* devXY = nullptr;
+    { const int rc = yk_dec_render_new_blocks(c, nWindows, xy, ww, wh, &devXY); if (rc) return rc; }
+    YkDetileArgs a;
+    a.planes = yk_dec_frame(c).planes; a.planeSize = c->dPlaneSize;
+    a.alpha = fromPlane ? yk_dec_alpha_cur(c) : nullptr; a.strideA = (size_t)c->dw; a.alphaConst = (uint32_t)((fromPlane ? 0 : alpha) & 255) * 0x01010101u;
+    a.out = devOut; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
+    a.tileW = (uint32_t)(c->dw >> 3); a.nTiles = (uint32_t)(ww >> 3) * (uint32_t)(wh >> 3);
+    const YkDtsForm f = { 0, 0, 0, 0, nullptr, nWindows, devXY, (uint32_t)(ww >> 3), windowBytes };
+    return yk_dts_run(c, a, f, level, channels);
 }
 
 }  // extern "C"

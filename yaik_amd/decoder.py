@@ -785,10 +785,13 @@ class HipTileDecoder:
         refuses with its state error: image_window_device() is the call."""
         return self._image_device(lib().yk_decode_output_device, None, out, channels, alpha, planar)
 
-    def _image_device(self, fn, window, out, channels, alpha, planar):
-        """image_device / image_window_device: the layout checks against the size written (the window's, or the image's), then fn between the hand-overs"""
+    def _image_device(self, fn, window, out, channels, alpha, planar, level=None):
+        """image_device / image_window_device / image_scaled_device: the layout checks against the size written (the window's, or the image's, reduced
+        by `level` when fn takes one), then fn between the hand-overs"""
         import torch
         ww, wh = (window[2], window[3]) if window is not None else (self.w, self.h)
+        if level is not None:
+            ww, wh = ww >> level, wh >> level
         C4 = channels if channels is not None else (4 if self._has_alpha else 3)
         a = (-1 if self._has_alpha else 255) if alpha is None else int(alpha)
         dev = torch.device("cuda", self.device)
@@ -808,7 +811,105 @@ class HipTileDecoder:
         L = lib()
         cur = torch.cuda.current_stream(dev).cuda_stream
         _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
-        _chk(self._h, fn(self._h, out.data_ptr(), row_bytes, plane_bytes, C4, a))
+        if level is None:
+            _chk(self._h, fn(self._h, out.data_ptr(), row_bytes, plane_bytes, C4, a))
+        else:
+            _chk(self._h, fn(self._h, level, out.data_ptr(), row_bytes, plane_bytes, C4, a))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
+
+    # ---- outputs at reduced resolution: 1/2, 1/4, 1/8 size box means straight from the de-tile kernel (yk_decode_output_scaled_device) ----
+    @staticmethod
+    def _check_level(level) -> int:
+        """level as an int 0..3 (raises before any library call)"""
+        if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+            raise TypeError(f"level must be an int 0..3; got {level!r}")
+        if not 0 <= int(level) <= 3:
+            raise ValueError(f"level must be 0..3 (1/1, 1/2, 1/4, 1/8 size); got {level}")
+        return int(level)
+
+    @staticmethod
+    def _check_out_shape(out, want, what: str) -> None:
+        """an `out` of another shape than the reduced one (the full-size shape, say) is refused before anything else looks at it"""
+        if out is not None and hasattr(out, "shape") and tuple(out.shape) != tuple(want):
+            raise ValueError(f"out has shape {tuple(out.shape)}, the {what} needs {tuple(want)}")
+
+    def image_scaled_device(self, level: int, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
+        """The decoded image at 1 / (1 << level) size (level 0..3) as a torch.uint8 tensor on the handle's device: [h >> level, w >> level, C], or
+        [C, h >> level, w >> level] with planar=True (yk_decode_output_scaled_device).  With a window set (set_window) it is the window that is
+        reduced, otherwise the whole image; level 0 is image_window_device().  Every output pixel is the mean of its (1 << level)^2 box of the
+        full-size decode, halves rounded up, computed from the full-size bytes inside the de-tile kernel: no full-size image is written.  Alpha
+        is averaged like a colour channel (a constant stays that constant).  channels, alpha, `out` (of the reduced shape) and the stream
+        hand-over are those of image_device.  level and the shape of `out` are checked before any library call."""
+        level = self._check_level(level)
+        win = self._window
+        ww, wh = ((win[2], win[3]) if win is not None else (self.w, self.h))
+        C4 = channels if channels is not None else (4 if self._has_alpha else 3)
+        self._check_out_shape(out, (C4, wh >> level, ww >> level) if planar else (wh >> level, ww >> level, C4), "reduced window" if win is not None else "reduced image")
+        return self._image_device(lib().yk_decode_output_scaled_device, win, out, channels, alpha, planar, level)
+
+    def image_scaled_batch_device(self, level: int, out=None, channels: int = 3, alpha: int = 255, planar: bool = False, alpha_from_planes: bool = False):
+        """image_batch_device() at 1 / (1 << level) size (yk_decode_output_scaled_batch_device, one launch): [N, h >> level, w >> level, C], or
+        [N, C, h >> level, w >> level] with planar=True, every frame reduced by the rule of image_scaled_device.  alpha_from_planes=True
+        (channels=4 only) averages the planes decompress_alpha_batch left on the device.  `out` follows image_batch_device at the reduced shape.
+        level and the shape of `out` are checked before any library call."""
+        import torch
+        level = self._check_level(level)
+        if alpha_from_planes and channels != 4:
+            raise ValueError("alpha_from_planes needs channels=4")
+        N, rw, rh = self.frames, self.w >> level, self.h >> level
+        want = (N, channels, rh, rw) if planar else (N, rh, rw, channels)
+        self._check_out_shape(out, want, "reduced batch")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty(want, dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        if planar:
+            lay = u8_planar_batch_layout(out)
+            plane_bytes = lay.plane_bytes
+        else:
+            lay = u8_pixel_layout(out, batch=True)
+            plane_bytes = 0
+        L = lib()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_output_scaled_batch_device(self._h, level, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels,
+                                                             -1 if alpha_from_planes else int(alpha)))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
+
+    def render_windows_scaled(self, level: int, origins, w: int, h: int, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
+        """render_windows() with reduced crops (yk_decode_render_windows_scaled_device): K windows of w x h FULL-RESOLUTION pixels at origins[k], each
+        returned at 1 / (1 << level) size, [K, h >> level, w >> level, C] or [K, C, h >> level, w >> level] with planar=True, window k equal to the
+        reduction (image_scaled_device's rule) of the same slice of the whole decode.  The blocks the windows touch are rendered at full size,
+        once per prepared image, shared with render_windows: the two may be mixed freely.  level, the windows and the shape of `out` are checked
+        before any library call."""
+        import torch
+        level = self._check_level(level)
+        flat = self._check_windows(origins, w, h)
+        K, ww, wh = len(flat) // 2, int(w), int(h)
+        rw, rh = ww >> level, wh >> level
+        C4 = channels if channels is not None else (4 if self._has_alpha else 3)
+        a = (-1 if self._has_alpha else 255) if alpha is None else int(alpha)
+        want = (K, C4, rh, rw) if planar else (K, rh, rw, C4)
+        self._check_out_shape(out, want, "reduced windows")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty(want, dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        if planar:
+            lay = u8_planar_batch_layout(out)
+            plane_bytes = lay.plane_bytes
+        else:
+            lay = u8_pixel_layout(out, batch=True)
+            plane_bytes = 0
+        L = lib()
+        xy = (C.c_int * (2 * K))(*flat)
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_render_windows_scaled_device(self._h, level, K, xy, ww, wh, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, C4, a))
         _chk(self._h, L.yk_stream_handoff(self._h, cur))
         return out
 

@@ -89,6 +89,10 @@ MULTIWINDOW_SIGNATURES = {
     "YAIK_DecodeImageWindowsToDevice": (C.c_bool, [vp, u32, vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t]),
     "YAIK_LastWindowsPrepared": (C.c_int, []),
 }
+# yaik_decode_scaled.h: the same library, C linkage
+SCALED_SIGNATURES = {
+    "YAIK_DecodeImageScaledToDevice": (C.c_bool, [vp, u32, vp, C.c_int]),
+}
 ERROR_NAMES = ["YAIK_NO_ERROR", "YAIK_INVALID_LIBRARYCTX", "YAIK_MALLOC_FAIL", "YAIK_INVALID_CONTEXT_COUNT", "YAIK_INIT_FAIL",
                "YAIK_RELEASE_EMPTY_LIBRARY", "YAIK_INVALID_STREAM", "YAIK_INVALID_HEADER", "YAIK_NO_EMPTYDECODE_SLOT", "YAIK_DECIMG_INVALIDCTX",
                "YAIK_DECIMG_DIFFSTREAM", "YAIK_DECIMG_BUFFERNOTSET", "YAIK_INVALID_CONTEXT_MEMALLOCATOR", "YAIK_INVALID_DECOMPRESSION",
@@ -125,7 +129,7 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
-        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES}.items():
+        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **SCALED_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _host = L
@@ -279,6 +283,32 @@ def decode_file_windows_device(stream: bytes, origins, w: int, h: int):
     info.outputImage, info.outputImageStride = out.data_ptr(), ww * c
     xy = (C.c_int * (2 * k))(*flat)
     if not L.YAIK_DecodeImageWindowsToDevice(src.ctypes.data, src.size, C.byref(info), k, xy, ww, wh, wh * ww * c):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    return out
+
+
+def decode_file_scaled_device(stream: bytes, level: int):
+    """One stream through YAIK_DecodeImageScaledToDevice: the image at 1 / (1 << level) size (level 0..3) as a torch.uint8 tensor
+    [H >> level, W >> level, 3] on the GPU, or [..., 4] when the stream has an 'ALPM' chunk.  Every pixel is the mean of its (1 << level)^2 box of
+    decode_file_device(stream), halves rounded up, alpha included; no full-size image is written.  A level that is no int raises TypeError, one
+    outside 0..3 ValueError, both before any library call.  Raises YaikFileError with the library's error code."""
+    import torch
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        raise TypeError(f"level must be an int 0..3; got {level!r}")
+    level = int(level)
+    if not 0 <= level <= 3:
+        raise ValueError(f"level must be 0..3 (1/1, 1/2, 1/4, 1/8 size); got {level}")
+    L, h = host_lib(), library()
+    src = _buffer(stream)
+    info = DecodedImage()
+    if not L.YAIK_DecodeImagePre(h, src.ctypes.data, src.size, C.byref(info)):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    dev = torch.device("cuda", _device)
+    c = 4 if has_alpha_chunk(bytes(stream)) else 3
+    out = torch.empty((info.height >> level, info.width >> level, c), dtype=torch.uint8, device=dev)
+    torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
+    info.outputImage, info.outputImageStride = out.data_ptr(), (info.width >> level) * c
+    if not L.YAIK_DecodeImageScaledToDevice(src.ctypes.data, src.size, C.byref(info), level):
         raise YaikFileError(L.YAIK_GetErrorCode())
     return out
 

@@ -5,6 +5,7 @@
 #include "yaik_decode.h"
 #include "yaik_decode_window.h"
 #include "yaik_decode_multiwindow.h"
+#include "yaik_decode_scaled.h"
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -264,8 +265,9 @@ static bool decodeChunks(Slot* s, const void* stream, uint32_t length, bool& has
 }
 
 // YAIK_DecodeImage, YAIK_DecodeImageToDevice and YAIK_DecodeImageWindowToDevice; toDevice: outputImage is in device memory (default builder only);
-// window (with toDevice): only that rectangle is decoded and written
-static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice, const int* window = nullptr) {
+// window (with toDevice): only that rectangle is decoded and written; level (with toDevice, YAIK_DecodeImageScaledToDevice): the output is the
+// image at 1 / (1 << level) size
+static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice, const int* window = nullptr, int level = 0) {
     if (!info || !info->internalTag || !gLib) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
     Slot* s = (Slot*)info->internalTag;
     bool res = false;
@@ -273,6 +275,7 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
     const bool customBuilder = info->customImageOutput && info->customImageOutput != defaultImageBuilder;
     do {
         if (toDevice && customBuilder) { setError(YAIK_DECIMG_INVALIDCTX); break; }               // a custom builder takes host planes
+        if (level < 0 || level > 3) { setError(YAIK_DECIMG_INVALIDCTX); break; }                  // before any chunk is decoded or a byte written
         if (!ua.customAlloc || !ua.customFree) { setError(YAIK_INVALID_CONTEXT_MEMALLOCATOR); break; }
         if (s->srcCheck != stream || s->srcLength != length) { setError(YAIK_DECIMG_DIFFSTREAM); break; }
         if (!info->outputImage) { setError(YAIK_DECIMG_BUFFERNOTSET); break; }
@@ -308,7 +311,8 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
             // branch is defective)
             if (toDevice)                                                                           // the same kernel into device rows, then a fence:
                 res = info->outputImageStride > 0 &&
-                      (window ? yk_decode_output_window_device(s->ctx, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1)
+                      (level  ? yk_decode_output_scaled_device(s->ctx, level, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1)
+                       : window ? yk_decode_output_window_device(s->ctx, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1)
                               : yk_decode_output_device(s->ctx, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1)) == YK_OK &&
                       yk_synchronize(s->ctx) == YK_OK;                                              // the slot's stream is idle before it is released
             else
@@ -327,6 +331,9 @@ bool YAIK_DecodeImageToDevice(void* stream, uint32_t length, YAIK_SDecodedImage*
 extern "C" bool YAIK_DecodeImageWindowToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int x0, int y0, int ww, int wh) {
     const int window[4] = { x0, y0, ww, wh };
     return decodeImage(stream, length, info, true, window);
+}
+extern "C" bool YAIK_DecodeImageScaledToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int level) {
+    return decodeImage(stream, length, info, true, nullptr, level);
 }
 
 // ---- YAIK_DecodeImagesToDevice: n streams of one shape through the device's batch calls (yaik_decode.h) ------------------------------------
