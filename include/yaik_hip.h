@@ -659,6 +659,32 @@ int yk_decode_output_scaled_batch_device(yk_ctx* c, int level, uint8_t* devOut, 
 int yk_decode_render_windows_scaled_device(yk_ctx* c, int level, int nWindows, const int* xy, int ww, int wh,
                                            uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t windowBytes, int channels, int alpha);
 
+/* ---- a full mip chain in one call: every level down to the last, the planes read once ----
+ * A w x h image has levels 0 .. top, top = floor(log2(min(w, h))) (yk_decode_mip_levels gives top + 1, at most YK_MIP_MAX_LEVELS).  Level k has
+ * (w >> k) x (h >> k) pixels, s = 1 << k:
+ *     out_k[Y][X][c] = (sum over dy, dx < s of dec[s Y + dy][s X + dx][c]  +  s s / 2) >> (2 k):
+ * the box mean of the level-0 bytes in integers, halves rounded up, never the mean of another level's rounded means.  Levels 0..3 are byte for
+ * byte what yk_decode_output_device and yk_decode_output_scaled_device write.  From level 4 on w and h need not divide by s: the w - s (w >> k)
+ * rightmost columns and h - s (h >> k) bottom rows are in no box and are ignored (the floor convention of texture mip chains).  Levels where a
+ * side would become 0 do not exist.  Alpha is averaged like a colour channel; a constant stays that constant.  Sums are exact at every size.
+ * levels[i] (a host array, read at call time) is the destination of level firstLevel + i, laid out as in yk_decode_output_device: HWC with
+ * planeBytes == 0, CHW otherwise, any base, any pitch that holds the level's row, only pixel bytes written; frameBytes is used by the batch call.
+ * Any contiguous run may be asked for: firstLevel = 0 is the whole chain with the full-size pixels, firstLevel = 5, nLevels = 1 one 1/32
+ * thumbnail.  All levels of a call share `channels` and the HWC / CHW form (mixing them: YK_ERR_BAD_ARG).  alpha as in the scaled calls: -1 the
+ * decoded 'ALPM' plane (batch call: the planes of yk_decode_alpha[_mask]_batch_device, YK_ERR_STATE when there are none), 0..255 a constant.
+ * yk_decode_output_mipchain_device: the image begun, or the selected frame of a batch; unmarked cells are settled first.  With a window set, or on
+ * a prepared image: YK_ERR_STATE (windows have no chain).  yk_decode_output_mipchain_batch_device: every frame, frame f of a level at
+ * devOut + f * frameBytes.  Every check (level range, NULL pointers, pitches, channels, state) is made against the level's own size, every
+ * refusal comes before the first launch and writes nothing, and the handle stays usable.  At most two launches however many levels and frames:
+ * one kernel reads the planes once and writes levels 0..6 and a sum per 64x64 block, a small second one makes the levels from 7 up of those sums
+ * (it runs only when such a level is asked for).  No host synchronisation (the handle's scratch may grow on the first call of a size); one
+ * YK_STAGE_DEC_DETILE interval per call.  The planes are not changed.  Level buffers that overlap are the caller's error and are not detected. */
+#define YK_MIP_MAX_LEVELS 15
+typedef struct { uint8_t* devOut; size_t rowBytes, planeBytes, frameBytes; } yk_mip_level;
+int yk_decode_mip_levels(int w, int h);                         /* top + 1, or YK_ERR_BAD_ARG for sides the decoder does not take */
+int yk_decode_output_mipchain_device(yk_ctx* c, int firstLevel, int nLevels, const yk_mip_level* levels, int channels, int alpha);
+int yk_decode_output_mipchain_batch_device(yk_ctx* c, int firstLevel, int nLevels, const yk_mip_level* levels, int channels, int alpha);
+
 /* ---- decode batches: nFrames images of ONE shape on a handle, every kernel launched once over nFrames x blocks ----
  * A frame of 2048 x 2048 or less is a fraction of the grids the decode kernels were tuned on, and one image costs about a dozen dependent stream
  * operations; a batch costs the same dozen.  yk_decode_begin_batch allocates the 8x8-tiled planes, the mapRGB lattice, its `loaded` flags, the

@@ -33,6 +33,14 @@ vp, ip = C.c_void_p, C.POINTER(C.c_int)
 sz, szp = C.c_size_t, C.POINTER(C.c_size_t)
 i32p = C.POINTER(C.c_int32)
 
+YK_MIP_MAX_LEVELS = 15
+
+
+class MipLevel(C.Structure):
+    """yk_mip_level: one level's destination of yk_decode_output_mipchain[_batch]_device"""
+    _fields_ = [("devOut", vp), ("rowBytes", sz), ("planeBytes", sz), ("frameBytes", sz)]
+
+
 # name -> (restype, argtypes); every exported symbol of include/yaik_hip.h
 SIGNATURES = {
     "yk_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
@@ -155,6 +163,9 @@ SIGNATURES = {
     "yk_decode_output_scaled_device": (C.c_int, [vp, C.c_int, vp, sz, sz, C.c_int, C.c_int]),
     "yk_decode_output_scaled_batch_device": (C.c_int, [vp, C.c_int, vp, sz, sz, sz, C.c_int, C.c_int]),
     "yk_decode_render_windows_scaled_device": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, sz, sz, sz, C.c_int, C.c_int]),
+    "yk_decode_mip_levels": (C.c_int, [C.c_int, C.c_int]),
+    "yk_decode_output_mipchain_device": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]),
+    "yk_decode_output_mipchain_batch_device": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]),
     "yk_decode_tile4x4": (C.c_int, [vp, vp, sz]),
     "yk_decode_tile4x4_planes": (C.c_int, [vp, vp, sz]),
     "yk_decode_begin_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),

@@ -1238,6 +1238,165 @@ static int yk_dec_detile_scaled(yk_ctx* c, int level, uint8_t* out, size_t rowBy
     return yk_dts_run(c, a, f, level, channels);
 }
 
+// ---- the de-tile of a mip chain (yk_decode_output_mipchain[_batch]_device) -------------------------------------------------------
+// Level k of a w x h image: out_k[Y][X][c] = (sum of the (1 << k)^2 box of the whole decode at (X << k, Y << k) + (1 << 2k) / 2) >> 2k for
+// X < w >> k, Y < h >> k, every level straight from the level-0 bytes.  Two kernels, the planes read once:
+//   the block kernel: a workgroup owns one 64x64 block (blockIdx.x = by * nbx + bx, frame blockIdx.y): lane tid holds the row pair tid & 3 of tile
+//     tid >> 2 of the block (tile (t & 7, t >> 3)), so a wave loads two tile rows of 512 contiguous bytes per plane with the 16-byte loads of
+//     yk_dts_load, and the quads of a tile are those of yk_dts_reduce.  Tiles past the right or bottom edge leave their quads idle.  From its
+//     registers a lane stores the levels 0..3 that are asked for (yk_dt_emit, yk_dts_reduce + yk_dts_emit: wave-uniform branches on the
+//     destination pointers).  For the levels above, the unrounded sum of a tile (<= 16320) goes to LDS, one dword per lane (lane rp keeps
+//     channel rp); wave 0 then holds output o = lane >> 2 (4 x 4 per block), channel lane & 3 of level 4 as the sum of 2x2 tiles and folds it
+//     with __shfl_xor to the 2x2 outputs of level 5 and to the block's own sum, which is level 6 and, for the tail, one dword per channel at
+//     sums[frame][by][bx][channel].  Every sum is exact in 32 bits (64 * 64 * 255 = 1044480) and is rounded once.  A 16-, 32- or 64-pixel box is
+//     stored, and a block sum written, only when it lies wholly inside the image.
+//   the tail kernel: a workgroup per output pixel of the levels >= 7 (all of them and every frame in one launch): 64 lanes per channel add the
+//     n x n block sums of the box (n = 1 << (k - 6)) in 64 bits, a tree in LDS adds the lanes, the pixel is rounded once.
+// A constant alpha is its own mean at every level and is stored as it is.
+struct YkMipDst { uint8_t* out; size_t rowBytes, planeBytes, frameBytes; };
+struct YkMipArgs {
+    const uint8_t* planes; size_t planeSize, planesFrame;
+    const uint8_t* alpha; size_t strideA, alphaFrame;        // YK_DT_ALPHA_PLANE
+    uint32_t alphaConst;                                      // the byte in all four lanes of a dword
+    uint32_t w, h, nbx;                                       // nbx: blocks per block row, the partial one included
+    uint32_t high;                                            // a level >= 4 is asked for
+    uint32_t* sums; uint32_t sbx, sby;                        // a level >= 7 is asked for: the whole blocks' sums, sbx = w >> 6, sby = h >> 6
+    YkMipDst lv[7];                                           // levels 0..6; out == NULL: not asked for
+};
+struct YkMipTailArgs {
+    const uint32_t* sums; uint32_t sbx, sby, w, h, alphaConst;
+    int first, last;                                          // levels first..last, 7 <= first
+    YkMipDst lv[YK_MIP_MAX_LEVELS - 7];                       // level k at lv[k - 7]
+};
+
+// the sum of a tile's 64 bytes of one plane, in all four lanes of its quad
+__device__ __forceinline__ uint32_t yk_mip_tile_sum(const yk_dt4 p) {
+    uint32_t s = __builtin_amdgcn_sad_u8(p.x, 0u, __builtin_amdgcn_sad_u8(p.y, 0u, __builtin_amdgcn_sad_u8(p.z, 0u, __builtin_amdgcn_sad_u8(p.w, 0u, 0u))));
+    s += yk_dts_quad_xor1(s);
+    s += yk_dts_quad_xor2(s);
+    return s;
+}
+template <int C, bool PLANAR, int ASRC, int LEVEL>
+__device__ __forceinline__ void yk_mip_store_low(const YkMipArgs& a, const YkMipDst& d, const YkDtsUnit& u, uint32_t tx, uint32_t ty, uint32_t rp) {
+    const uint32_t r = yk_dts_reduce<LEVEL>(u.r), g = yk_dts_reduce<LEVEL>(u.g), b = yk_dts_reduce<LEVEL>(u.b);
+    uint32_t al = a.alphaConst;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) al = yk_dts_reduce<LEVEL>(u.a);
+    const size_t o = (size_t)blockIdx.y * d.frameBytes + ((size_t)ty * (8 >> LEVEL) + (rp >> (LEVEL - 1))) * d.rowBytes + (size_t)tx * (8 >> LEVEL) * (PLANAR ? 1 : C);
+    if ((rp & ((1u << (LEVEL - 1)) - 1)) == 0) yk_dts_emit<C, PLANAR, LEVEL>(d.out + o, d.planeBytes, r, g, b, al);
+}
+// channel ch of pixel (X, Y) of a level
+template <int C, bool PLANAR>
+__device__ __forceinline__ void yk_mip_store_byte(const YkMipDst& d, uint32_t X, uint32_t Y, uint32_t ch, uint32_t v) {
+    uint8_t* o = d.out + (size_t)blockIdx.y * d.frameBytes + (size_t)Y * d.rowBytes;
+    if constexpr (PLANAR) o[(size_t)ch * d.planeBytes + X] = (uint8_t)v; else o[(size_t)X * C + ch] = (uint8_t)v;
+}
+
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_mip_block_kernel(const YkMipArgs a) {
+    __shared__ uint32_t tileSum[YK_DT_THREADS];                               // [tile of the block][channel]
+    const uint32_t tid = threadIdx.x, rp = tid & 3, t = tid >> 2;
+    const uint32_t by = blockIdx.x / a.nbx, bx = blockIdx.x - by * a.nbx;
+    const uint32_t tx = bx * 8 + (t & 7), ty = by * 8 + (t >> 3), tileW = a.w >> 3;
+    uint32_t mine = 0;
+    if (tx < tileW && ty * 8 < a.h) {                                         // whole quads: the four lanes of a tile share t
+        YkDtsUnit u;
+        const uint8_t* pl = a.planes + (size_t)blockIdx.y * a.planesFrame + ((size_t)ty * tileW + tx) * 64 + rp * 16;
+        u.r = *reinterpret_cast<const yk_dt4*>(pl);
+        u.g = *reinterpret_cast<const yk_dt4*>(pl + a.planeSize);
+        u.b = *reinterpret_cast<const yk_dt4*>(pl + 2 * a.planeSize);
+        const size_t y = (size_t)ty * 8 + rp * 2, x = (size_t)tx * 8;
+        if constexpr (ASRC == YK_DT_ALPHA_PLANE) {
+            const uint8_t* ap = a.alpha + (size_t)blockIdx.y * a.alphaFrame + y * a.strideA + x;
+            uint32_t al[4];
+            __builtin_memcpy(&al[0], ap, 8);
+            __builtin_memcpy(&al[2], ap + a.strideA, 8);
+            u.a = yk_dt4{ al[0], al[1], al[2], al[3] };
+        } else u.a = yk_dt4{ a.alphaConst, a.alphaConst, a.alphaConst, a.alphaConst };
+        if (a.lv[0].out) {
+            const YkMipDst& d = a.lv[0];
+            uint8_t* o = d.out + (size_t)blockIdx.y * d.frameBytes + y * d.rowBytes + x * (PLANAR ? 1 : C);
+            yk_dt_emit<C, PLANAR>(o, d.planeBytes, u.r.x, u.r.y, u.g.x, u.g.y, u.b.x, u.b.y, u.a.x, u.a.y);
+            yk_dt_emit<C, PLANAR>(o + d.rowBytes, d.planeBytes, u.r.z, u.r.w, u.g.z, u.g.w, u.b.z, u.b.w, u.a.z, u.a.w);
+        }
+        if (a.lv[1].out) yk_mip_store_low<C, PLANAR, ASRC, 1>(a, a.lv[1], u, tx, ty, rp);
+        if (a.lv[2].out) yk_mip_store_low<C, PLANAR, ASRC, 2>(a, a.lv[2], u, tx, ty, rp);
+        if (a.lv[3].out) yk_mip_store_low<C, PLANAR, ASRC, 3>(a, a.lv[3], u, tx, ty, rp);
+        if (a.high) {
+            const uint32_t sr = yk_mip_tile_sum(u.r), sg = yk_mip_tile_sum(u.g), sb = yk_mip_tile_sum(u.b);
+            uint32_t sa = 0;
+            if constexpr (ASRC == YK_DT_ALPHA_PLANE) sa = yk_mip_tile_sum(u.a);
+            mine = rp == 0 ? sr : rp == 1 ? sg : rp == 2 ? sb : sa;
+        }
+    }
+    if (!a.high) return;
+    tileSum[tid] = mine;                                                      // a tile outside the image adds nothing
+    __syncthreads();
+    if (tid >= 64) return;
+    // wave 0: lane = (oy, ox, ch), output (ox, oy) of the block's 4 x 4 at level 4
+    const uint32_t ch = tid & 3, ox = (tid >> 2) & 3, oy = tid >> 4;
+    const uint32_t t0 = (oy * 16 + ox * 2) * 4 + ch;                          // tile (2 ox, 2 oy)
+    const uint32_t s4 = tileSum[t0] + tileSum[t0 + 4] + tileSum[t0 + 32] + tileSum[t0 + 36];
+    uint32_t s5 = s4 + (uint32_t)__shfl_xor((int)s4, 4);                      // ox ^ 1
+    s5 += (uint32_t)__shfl_xor((int)s5, 16);                                  // oy ^ 1
+    uint32_t s6 = s5 + (uint32_t)__shfl_xor((int)s5, 8);                      // ox ^ 2
+    s6 += (uint32_t)__shfl_xor((int)s6, 32);                                  // oy ^ 2
+    const bool fixed = ch == 3 && ASRC != YK_DT_ALPHA_PLANE;                  // a constant alpha
+    const uint32_t ac = a.alphaConst & 255u;
+    if (ch < (uint32_t)C) {
+        if (a.lv[4].out && bx * 4 + ox < (a.w >> 4) && by * 4 + oy < (a.h >> 4))
+            yk_mip_store_byte<C, PLANAR>(a.lv[4], bx * 4 + ox, by * 4 + oy, ch, fixed ? ac : (s4 + 128u) >> 8);
+        if (a.lv[5].out && !((ox | oy) & 1) && bx * 2 + (ox >> 1) < (a.w >> 5) && by * 2 + (oy >> 1) < (a.h >> 5))
+            yk_mip_store_byte<C, PLANAR>(a.lv[5], bx * 2 + (ox >> 1), by * 2 + (oy >> 1), ch, fixed ? ac : (s5 + 512u) >> 10);
+        if (a.lv[6].out && !(ox | oy) && bx < a.sbx && by < a.sby)
+            yk_mip_store_byte<C, PLANAR>(a.lv[6], bx, by, ch, fixed ? ac : (s6 + 2048u) >> 12);
+    }
+    if (a.sums && !(ox | oy) && bx < a.sbx && by < a.sby)
+        a.sums[(((size_t)blockIdx.y * a.sby + by) * a.sbx + bx) * 4 + ch] = s6;
+}
+
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(256) void yk_dec_mip_tail_kernel(const YkMipTailArgs a) {
+    __shared__ unsigned long long acc[256];
+    uint32_t i = blockIdx.x, Lw = 0;
+    int k = a.first;
+    for (; k <= a.last; k++) {                                                // the levels' pixels are numbered one level after the other
+        Lw = a.w >> k;
+        const uint32_t n = Lw * (a.h >> k);
+        if (i < n) break;
+        i -= n;
+    }
+    if (k > a.last) return;
+    const uint32_t Y = i / Lw, X = i - Y * Lw, sh = (uint32_t)k - 6, n = 1u << sh;
+    const uint32_t tid = threadIdx.x, ch = tid & 3;
+    const bool fixed = ch == 3 && ASRC != YK_DT_ALPHA_PLANE;
+    unsigned long long s = 0;
+    if (ch < (uint32_t)C && !fixed) {
+        const uint32_t* base = a.sums + (((size_t)blockIdx.y * a.sby + (size_t)Y * n) * a.sbx + (size_t)X * n) * 4 + ch;
+        for (uint32_t j = tid >> 2; j < n * n; j += 64) s += base[((size_t)(j >> sh) * a.sbx + (j & (n - 1))) * 4];
+    }
+    acc[tid] = s;
+    __syncthreads();
+    for (uint32_t st = 128; st >= 4; st >>= 1) {                              // st is a multiple of 4: a lane adds its own channel
+        if (tid < st) acc[tid] += acc[tid + st];
+        __syncthreads();
+    }
+    if (tid < (uint32_t)C) {
+        const YkMipDst& d = a.lv[k - 7];
+        const uint32_t v = fixed ? (a.alphaConst & 255u) : (uint32_t)((acc[tid] + (1ull << (2 * k - 1))) >> (2 * k));
+        yk_mip_store_byte<C, PLANAR>(d, X, Y, ch, v);
+    }
+}
+
+template <int C, bool PLANAR, int ASRC>
+static void yk_mip_launch(const YkMipArgs& a, const YkMipTailArgs& t, hipStream_t s, unsigned nFrames) {
+    const unsigned nby = (a.h + 63) >> 6;
+    hipLaunchKernelGGL((yk_dec_mip_block_kernel<C, PLANAR, ASRC>), dim3(a.nbx * nby, nFrames), dim3(YK_DT_THREADS), 0, s, a);
+    if (t.first > t.last) return;
+    unsigned px = 0;
+    for (int k = t.first; k <= t.last; k++) px += (t.w >> k) * (t.h >> k);
+    hipLaunchKernelGGL((yk_dec_mip_tail_kernel<C, PLANAR, ASRC>), dim3(px, nFrames), dim3(256), 0, s, t);
+}
+
 // The reference's RGBA branch as it executes (decoder/YAIK_DefaultCallback.cpp:45-62): the alpha store does not advance dst, so a row is
 // w RGB triples followed by ONE alpha byte; the alpha row cursors advance w bytes per tile row instead of 8 * strideA (:36-39 vs
 // :128-130), so row y ends on the byte alpha[strideA * (y & 7) + w * (y >> 3) + w - 1].  One thread per row writes that byte.
@@ -2025,6 +2184,81 @@ int yk_decode_output_scaled_batch_device(yk_ctx* c, int level, uint8_t* devOut, 
     { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
     return yk_dec_detile_scaled(c, level, devOut, rowBytes, planeBytes, channels, fromPlanes ? c->dAlpha : nullptr, (size_t)c->dw, fromPlanes ? 0 : alpha, c->dFrames, frameBytes,
                                 fromPlanes ? c->dAlphaStride : 0);
+}
+
+// ---- a mip chain in one call (include/yaik_hip.h): levels firstLevel .. firstLevel + nLevels - 1, the planes read once ---------------
+int yk_decode_mip_levels(int w, int h) {
+    if (w < 8 || h < 8 || (w & 7) || (h & 7) || w > 32760 || h > 32760) return YK_ERR_BAD_ARG;
+    int n = 0;
+    for (int m = w < h ? w : h; m; m >>= 1) n++;
+    return n;                                                                   // floor(log2(min(w, h))) + 1
+}
+
+// both entry points: every check against the level's own size, then at most two launches inside one YK_STAGE_DEC_DETILE interval
+static int yk_dec_mipchain(yk_ctx* c, const char* name, int firstLevel, int nLevels, const yk_mip_level* levels, int channels, int alpha, bool batch) {
+    auto refuse = [&](int code, const char* what) { return yk_refuse(c, code, (std::string(name) + ": " + what).c_str()); };
+    if (!yk_dec_begun(c)) return refuse(YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
+    if (c->dPrepared) return refuse(YK_ERR_STATE, "this image is prepared for windows (yk_decode_prepare_device) and windows have no chain");
+    if (!batch && c->dWinSet) return refuse(YK_ERR_STATE, "a window is set on this decode (yk_decode_set_window) and windows have no chain");
+    const int total = yk_decode_mip_levels(c->dw, c->dh);
+    if (firstLevel < 0 || nLevels < 1 || nLevels > YK_MIP_MAX_LEVELS || firstLevel > total - nLevels)
+        return refuse(YK_ERR_BAD_ARG, "firstLevel .. firstLevel + nLevels - 1 must lie inside the image's levels (yk_decode_mip_levels)");
+    if (!levels) return refuse(YK_ERR_BAD_ARG, "levels is NULL");
+    if (channels != 3 && channels != 4) return refuse(YK_ERR_BAD_ARG, "channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255)) return refuse(YK_ERR_BAD_ARG, "alpha must be -1 (the decoded alpha) or 0..255");
+    const bool planar = levels[0].planeBytes > 0;
+    const int nFrames = batch ? c->dFrames : 1;
+    for (int i = 0; i < nLevels; i++) {
+        const yk_mip_level& L = levels[i];
+        const size_t w = (size_t)c->dw >> (firstLevel + i), h = (size_t)c->dh >> (firstLevel + i);
+        if (!L.devOut) return refuse(YK_ERR_BAD_ARG, "a level's devOut is NULL");
+        if ((L.planeBytes > 0) != planar) return refuse(YK_ERR_BAD_ARG, "the levels of one call are all HWC (planeBytes == 0) or all CHW");
+        if (!planar ? L.rowBytes < w * channels : (L.rowBytes < w || L.planeBytes / h < L.rowBytes))
+            return refuse(YK_ERR_BAD_ARG, "row or plane pitch too small for a level");
+        if (nFrames > 1 && (!planar ? L.frameBytes / h < L.rowBytes : L.frameBytes / (size_t)channels < L.planeBytes))
+            return refuse(YK_ERR_BAD_ARG, "frame stride too small for a level's frame");
+    }
+    const bool fromPlane = channels == 4 && alpha < 0;
+    if (fromPlane && batch && (!c->dAlphaValid || !c->dAlphaBatch))
+        return refuse(YK_ERR_STATE, "alpha = -1 needs yk_decode_alpha_batch_device first: the batch has no decoded alpha planes");
+    if (fromPlane && !c->dAlphaValid) return refuse(YK_ERR_STATE, "alpha = -1 needs yk_decode_alpha first");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    const int lastLevel = firstLevel + nLevels - 1;
+    YkMipArgs a = {};
+    YkMipTailArgs t = {};
+    a.planes = yk_dec_frame(c, batch ? 0 : c->dCur).planes; a.planeSize = c->dPlaneSize; a.planesFrame = c->dStride.planes;
+    a.alpha = fromPlane ? (batch ? (const uint8_t*)c->dAlpha : yk_dec_alpha_cur(c)) : nullptr; a.strideA = (size_t)c->dw; a.alphaFrame = fromPlane && batch ? c->dAlphaStride : 0;
+    a.alphaConst = (uint32_t)((fromPlane ? 0 : alpha) & 255) * 0x01010101u;
+    a.w = (uint32_t)c->dw; a.h = (uint32_t)c->dh; a.nbx = (a.w + 63) >> 6;
+    a.high = lastLevel >= 4; a.sbx = a.w >> 6; a.sby = a.h >> 6;
+    t.first = firstLevel > 7 ? firstLevel : 7; t.last = lastLevel;
+    if (lastLevel >= 7) {
+        { const int rc = yk_dec_scratch(c, (size_t)nFrames * a.sbx * a.sby * 16); if (rc) return rc; }
+        a.sums = reinterpret_cast<uint32_t*>(c->dScratch.p);
+        t.sums = a.sums; t.sbx = a.sbx; t.sby = a.sby; t.w = a.w; t.h = a.h; t.alphaConst = a.alphaConst;
+    }
+    for (int i = 0; i < nLevels; i++) {
+        const YkMipDst d = { levels[i].devOut, levels[i].rowBytes, levels[i].planeBytes, levels[i].frameBytes };
+        if (firstLevel + i < 7) a.lv[firstLevel + i] = d; else t.lv[firstLevel + i - 7] = d;
+    }
+    { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    const unsigned nf = (unsigned)nFrames;
+    if (channels == 3)  { if (planar) yk_mip_launch<3, true, YK_DT_ALPHA_NONE>(a, t, c->stream, nf); else yk_mip_launch<3, false, YK_DT_ALPHA_NONE>(a, t, c->stream, nf); }
+    else if (fromPlane) { if (planar) yk_mip_launch<4, true, YK_DT_ALPHA_PLANE>(a, t, c->stream, nf); else yk_mip_launch<4, false, YK_DT_ALPHA_PLANE>(a, t, c->stream, nf); }
+    else                { if (planar) yk_mip_launch<4, true, YK_DT_ALPHA_CONST>(a, t, c->stream, nf); else yk_mip_launch<4, false, YK_DT_ALPHA_CONST>(a, t, c->stream, nf); }
+    YK_HIP(c, hipGetLastError());
+    return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+}
+
+int yk_decode_output_mipchain_device(yk_ctx* c, int firstLevel, int nLevels, const yk_mip_level* levels, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    return yk_dec_mipchain(c, "yk_decode_output_mipchain_device", firstLevel, nLevels, levels, channels, alpha, false);
+}
+
+int yk_decode_output_mipchain_batch_device(yk_ctx* c, int firstLevel, int nLevels, const yk_mip_level* levels, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    return yk_dec_mipchain(c, "yk_decode_output_mipchain_batch_device", firstLevel, nLevels, levels, channels, alpha, true);
 }
 
 // ---- round-trip quality: the decode against a source in HBM (kernels and the read-back: yk_quality.hip) ----

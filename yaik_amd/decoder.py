@@ -913,6 +913,87 @@ class HipTileDecoder:
         _chk(self._h, L.yk_stream_handoff(self._h, cur))
         return out
 
+    # ---- a full mip chain in one call: every level a box mean of level 0, the planes read once (yk_decode_output_mipchain_device) ----
+    def mip_levels(self) -> int:
+        """how many levels the image's chain has: floor(log2(min(w, h))) + 1, level k being (w >> k) x (h >> k)"""
+        return min(self.w, self.h).bit_length()
+
+    def _check_mip_range(self, first, count) -> tuple:
+        """(first, count) as ints inside the chain (raises before any library call); count=None: every level from `first` down"""
+        total = self.mip_levels()
+        for name, v in (("first", first), ("count", count)):
+            if (v is not None or name == "first") and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise TypeError(f"{name} must be an int; got {v!r}")
+        first = int(first)
+        if not 0 <= first < total:
+            raise ValueError(f"first must be a level 0..{total - 1} of this {self.w} x {self.h} image; got {first}")
+        count = total - first if count is None else int(count)
+        if not 1 <= count <= total - first:
+            raise ValueError(f"count must be 1..{total - first} for first = {first} (the chain has {total} levels); got {count}")
+        return first, count
+
+    def _mipchain(self, fn, first, count, out, C4, a, planar, frames):
+        """the two chain calls: the range, the list `out` and every shape first, then one table of the levels' layouts and fn between the hand-overs"""
+        import torch
+        from ._lib import MipLevel
+        first, count = self._check_mip_range(first, count)
+        if isinstance(C4, bool) or not isinstance(C4, (int, np.integer)):
+            raise TypeError(f"channels must be 3 or 4; got {C4!r}")
+        if C4 not in (3, 4):
+            raise ValueError(f"channels must be 3 or 4; got {C4}")
+        lead = () if frames is None else (frames,)
+        wants = [lead + ((C4, self.h >> k, self.w >> k) if planar else (self.h >> k, self.w >> k, C4)) for k in range(first, first + count)]
+        if out is not None:
+            if not isinstance(out, (list, tuple)):
+                raise TypeError(f"out must be a list of {count} tensors, one per level; got {type(out).__name__}")
+            if len(out) != count:
+                raise ValueError(f"out has {len(out)} tensors, levels {first}..{first + count - 1} need {count}")
+            for k, (o, want) in enumerate(zip(out, wants), first):
+                if not hasattr(o, "shape"):
+                    raise TypeError(f"out[{k - first}] must be a torch tensor; got {type(o).__name__}")
+                self._check_out_shape(o, want, f"level {k}")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = [torch.empty(want, dtype=torch.uint8, device=dev) for want in wants]
+        table = (MipLevel * count)()
+        for i, o in enumerate(out):
+            if not isinstance(o, torch.Tensor) or o.device != dev:
+                raise ValueError(f"out[{i}] must be a torch tensor on {dev}, got {getattr(o, 'device', type(o).__name__)}")
+            if planar:
+                lay = u8_planar_layout(o) if frames is None else u8_planar_batch_layout(o)
+                plane_bytes = lay.plane_bytes
+            else:
+                lay = u8_pixel_layout(o, batch=frames is not None)
+                plane_bytes = 0
+            table[i] = MipLevel(o.data_ptr(), lay.row_bytes, plane_bytes, 0 if frames is None else lay.frame_bytes)
+        L = lib()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written the levels
+        _chk(self._h, fn(L)(self._h, first, count, table, C4, a))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return list(out)
+
+    def image_mipchain_device(self, first: int = 0, count: int | None = None, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
+        """Levels first .. first + count - 1 of the decoded image's mip chain (count=None: down to the last, mip_levels() - 1) as a list of torch.uint8
+        tensors on the handle's device, level k [h >> k, w >> k, C], or [C, h >> k, w >> k] with planar=True (yk_decode_output_mipchain_device).
+        Every pixel of level k is the mean of its (1 << k)^2 box of the full-size decode, halves rounded up, computed from the full-size bytes:
+        levels 0..3 are image_device() and image_scaled_device(), the levels above ignore the columns and rows that fill no whole box.  One
+        call reads the decoded planes once, however many levels it writes.  Alpha is averaged like a colour channel (a constant stays that
+        constant).  channels, alpha and the stream hand-over are those of image_device; `out` is a list of views under image_device's stride
+        rules, each of exactly its level's shape.  first, count, the length of `out` and every shape are checked before any library call."""
+        C4 = channels if channels is not None else (4 if self._has_alpha else 3)
+        a = (-1 if self._has_alpha else 255) if alpha is None else int(alpha)
+        return self._mipchain(lambda L: L.yk_decode_output_mipchain_device, first, count, out, C4, a, planar, None)
+
+    def image_mipchain_batch_device(self, first: int = 0, count: int | None = None, out=None, channels: int = 3, alpha: int = 255, planar: bool = False,
+                                    alpha_from_planes: bool = False):
+        """image_mipchain_device() for every frame of a batch in one call (yk_decode_output_mipchain_batch_device): a list of [N, h >> k, w >> k, C]
+        tensors, or [N, C, h >> k, w >> k] with planar=True.  alpha_from_planes=True (channels=4 only) averages the planes decompress_alpha_batch
+        left on the device.  `out` is a list of views under image_batch_device's stride rules."""
+        if alpha_from_planes and channels != 4:
+            raise ValueError("alpha_from_planes needs channels=4")
+        return self._mipchain(lambda L: L.yk_decode_output_mipchain_batch_device, first, count, out, channels, -1 if alpha_from_planes else int(alpha), planar, self.frames)
+
     # ---- round-trip quality: the decode against a source that is already on the device (yk_decode_compare_*) --------------------------------
     def _compare_channels(self, channels, src_channels: int) -> int:
         if channels is None:

@@ -93,6 +93,10 @@ MULTIWINDOW_SIGNATURES = {
 SCALED_SIGNATURES = {
     "YAIK_DecodeImageScaledToDevice": (C.c_bool, [vp, u32, vp, C.c_int]),
 }
+# yaik_decode_mipchain.h: the same library, C linkage
+MIPCHAIN_SIGNATURES = {
+    "YAIK_DecodeImageMipchainToDevice": (C.c_bool, [vp, u32, vp, C.c_int, C.c_int, vp, vp]),
+}
 ERROR_NAMES = ["YAIK_NO_ERROR", "YAIK_INVALID_LIBRARYCTX", "YAIK_MALLOC_FAIL", "YAIK_INVALID_CONTEXT_COUNT", "YAIK_INIT_FAIL",
                "YAIK_RELEASE_EMPTY_LIBRARY", "YAIK_INVALID_STREAM", "YAIK_INVALID_HEADER", "YAIK_NO_EMPTYDECODE_SLOT", "YAIK_DECIMG_INVALIDCTX",
                "YAIK_DECIMG_DIFFSTREAM", "YAIK_DECIMG_BUFFERNOTSET", "YAIK_INVALID_CONTEXT_MEMALLOCATOR", "YAIK_INVALID_DECOMPRESSION",
@@ -129,7 +133,7 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
-        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **SCALED_SIGNATURES}.items():
+        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **SCALED_SIGNATURES, **MIPCHAIN_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _host = L
@@ -309,6 +313,42 @@ def decode_file_scaled_device(stream: bytes, level: int):
     torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
     info.outputImage, info.outputImageStride = out.data_ptr(), (info.width >> level) * c
     if not L.YAIK_DecodeImageScaledToDevice(src.ctypes.data, src.size, C.byref(info), level):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    return out
+
+
+def decode_file_mipchain_device(stream: bytes, first: int = 0, count: int | None = None):
+    """One stream through YAIK_DecodeImageMipchainToDevice: levels first .. first + count - 1 of the image's mip chain (count=None: down to the
+    last) as a list of torch.uint8 tensors on the GPU, level k [H >> k, W >> k, 3], or [..., 4] when the stream has an 'ALPM' chunk.  Every pixel of
+    level k is the mean of its (1 << k)^2 box of decode_file_device(stream), halves rounded up, alpha included; the decoded planes are read once.
+    A first or count that is no int raises TypeError, a range outside the chain ValueError, both before any chunk is decoded.  Raises
+    YaikFileError with the library's error code."""
+    import torch
+    for name, v in (("first", first), ("count", count)):
+        if (v is not None or name == "first") and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+            raise TypeError(f"{name} must be an int; got {v!r}")
+    first = int(first)
+    if first < 0 or (count is not None and int(count) < 1):
+        raise ValueError(f"first must be >= 0 and count >= 1; got first = {first}, count = {count}")
+    L, h = host_lib(), library()
+    src = _buffer(stream)
+    info = DecodedImage()
+    if not L.YAIK_DecodeImagePre(h, src.ctypes.data, src.size, C.byref(info)):
+        raise YaikFileError(L.YAIK_GetErrorCode())
+    total = min(info.width, info.height).bit_length()
+    n = total - first if count is None else int(count)
+    if first >= total or n > total - first:
+        info.outputImage = 0                                               # the call releases the slot and refuses before any chunk is decoded
+        L.YAIK_DecodeImageMipchainToDevice(src.ctypes.data, src.size, C.byref(info), first, max(n, 1), None, None)
+        L.YAIK_GetErrorCode()
+        raise ValueError(f"levels {first}..{first + n - 1} are not inside the {total} levels of this {info.width} x {info.height} image")
+    dev = torch.device("cuda", _device)
+    c = 4 if has_alpha_chunk(bytes(stream)) else 3
+    out = [torch.empty((info.height >> k, info.width >> k, c), dtype=torch.uint8, device=dev) for k in range(first, first + n)]
+    torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
+    images = (C.c_void_p * n)(*[o.data_ptr() for o in out])
+    strides = (C.c_uint32 * n)(*[(info.width >> k) * c for k in range(first, first + n)])
+    if not L.YAIK_DecodeImageMipchainToDevice(src.ctypes.data, src.size, C.byref(info), first, n, images, strides):
         raise YaikFileError(L.YAIK_GetErrorCode())
     return out
 

@@ -6,6 +6,7 @@
 #include "yaik_decode_window.h"
 #include "yaik_decode_multiwindow.h"
 #include "yaik_decode_scaled.h"
+#include "yaik_decode_mipchain.h"
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -266,8 +267,9 @@ static bool decodeChunks(Slot* s, const void* stream, uint32_t length, bool& has
 
 // YAIK_DecodeImage, YAIK_DecodeImageToDevice and YAIK_DecodeImageWindowToDevice; toDevice: outputImage is in device memory (default builder only);
 // window (with toDevice): only that rectangle is decoded and written; level (with toDevice, YAIK_DecodeImageScaledToDevice): the output is the
-// image at 1 / (1 << level) size
-static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice, const int* window = nullptr, int level = 0) {
+// image at 1 / (1 << level) size; mip (with toDevice, YAIK_DecodeImageMipchainToDevice): the outputs are the levels of a mip chain, outputImage is unused
+namespace { struct MipRequest { int first, n; void* const* images; const uint32_t* strides; }; }
+static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice, const int* window = nullptr, int level = 0, const MipRequest* mip = nullptr) {
     if (!info || !info->internalTag || !gLib) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
     Slot* s = (Slot*)info->internalTag;
     bool res = false;
@@ -278,9 +280,15 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
         if (level < 0 || level > 3) { setError(YAIK_DECIMG_INVALIDCTX); break; }                  // before any chunk is decoded or a byte written
         if (!ua.customAlloc || !ua.customFree) { setError(YAIK_INVALID_CONTEXT_MEMALLOCATOR); break; }
         if (s->srcCheck != stream || s->srcLength != length) { setError(YAIK_DECIMG_DIFFSTREAM); break; }
-        if (!info->outputImage) { setError(YAIK_DECIMG_BUFFERNOTSET); break; }
+        if (!mip && !info->outputImage) { setError(YAIK_DECIMG_BUFFERNOTSET); break; }
         const int w = s->width, h = s->height;
         bool hasAlphaPlane = false;
+        if (mip) {                                                                                  // range and pointers before any chunk is decoded
+            const int total = yk_decode_mip_levels(w, h);
+            bool ok = mip->first >= 0 && mip->n >= 1 && mip->n <= YK_MIP_MAX_LEVELS && mip->first <= total - mip->n && mip->images && mip->strides;
+            for (int i = 0; ok && i < mip->n; i++) ok = mip->images[i] != nullptr;
+            if (!ok) { setError(YAIK_DECIMG_INVALIDCTX); break; }
+        }
         if (window && (((window[0] | window[1] | window[2] | window[3]) & 7) || window[0] < 0 || window[1] < 0 || window[2] < 8 || window[3] < 8 ||
                        window[0] > w - window[2] || window[1] > h - window[3])) { setError(YAIK_DECIMG_INVALIDCTX); break; }
         if (!decodeChunks(s, stream, length, hasAlphaPlane, window)) break;
@@ -309,7 +317,11 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
             // YAIK_DefaultCallback.cpp:44,63); row padding is left untouched.
             // with an 'ALPM' chunk: RGBA 4 B/pixel from the alpha plane kept in HBM (YAIK.h documents RGBA rows; the reference's own RGBA
             // branch is defective)
-            if (toDevice)                                                                           // the same kernel into device rows, then a fence:
+            if (mip) {
+                yk_mip_level lv[YK_MIP_MAX_LEVELS];
+                for (int i = 0; i < mip->n; i++) lv[i] = { (uint8_t*)mip->images[i], (size_t)mip->strides[i], 0, 0 };
+                res = yk_decode_output_mipchain_device(s->ctx, mip->first, mip->n, lv, hasAlphaPlane ? 4 : 3, -1) == YK_OK && yk_synchronize(s->ctx) == YK_OK;
+            } else if (toDevice)                                                                    // the same kernel into device rows, then a fence:
                 res = info->outputImageStride > 0 &&
                       (level  ? yk_decode_output_scaled_device(s->ctx, level, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1)
                        : window ? yk_decode_output_window_device(s->ctx, info->outputImage, (size_t)info->outputImageStride, 0, hasAlphaPlane ? 4 : 3, -1)
@@ -334,6 +346,11 @@ extern "C" bool YAIK_DecodeImageWindowToDevice(void* stream, uint32_t length, YA
 }
 extern "C" bool YAIK_DecodeImageScaledToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int level) {
     return decodeImage(stream, length, info, true, nullptr, level);
+}
+extern "C" bool YAIK_DecodeImageMipchainToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int firstLevel, int nLevels, void* const* levelImages,
+                                                 const uint32_t* levelStrides) {
+    const MipRequest mip = { firstLevel, nLevels, levelImages, levelStrides };
+    return decodeImage(stream, length, info, true, nullptr, 0, &mip);
 }
 
 // ---- YAIK_DecodeImagesToDevice: n streams of one shape through the device's batch calls (yaik_decode.h) ------------------------------------
