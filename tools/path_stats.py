@@ -1,5 +1,6 @@
 """How often every path of yk_encode2_kernel is taken on one frame (needs a -DYK2_STATS build: YK_LIB=build/libS.so).
-usage: YK_LIB=build/libS.so python tools/path_stats.py [frame|ramp|mild|noise|border]
+usage: YK_LIB=build/libS.so python tools/path_stats.py [frame|ramp|mild|noise|border|empty]
+empty: noise whose alpha plane is all zero (every strip alpha-rejected and dead behind the curvature screen).
 The "grouped sweeps" rows are what a build with the grouped sweep did (a -DYK2_NO_GROUP build leaves them zero)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,12 +21,13 @@ else:
     img = torch.stack([(255 * x) // W, (255 * y) // W, (255 * (x + y)) // (2 * W)])
     g = torch.Generator(device=dev); g.manual_seed(1)
     if cls == "mild": img = (img + torch.randint(0, 8, (3, W, W), device=dev, generator=g)) % 256
-    elif cls == "noise": img = torch.randint(0, 256, (3, W, W), device=dev, generator=g)
+    elif cls in ("noise", "empty"): img = torch.randint(0, 256, (3, W, W), device=dev, generator=g)
+    if cls == "empty": img = torch.cat([img, torch.zeros((1, W, W), dtype=img.dtype, device=dev)])
     elif cls == "border":                                # 64x64 blocks in a checkerboard of ramp and mild noise: every ramp block has mild noise to its right and below
         img = torch.where((((x >> 6) + (y >> 6)) & 1).bool()[None], (img + torch.randint(0, 8, (3, W, W), device=dev, generator=g)) % 256, img)
 enc = HipTileEncoder(0)
 enc.set_image(img.to(torch.int32).contiguous())
-if cls == "frame":
+if cls in ("frame", "empty"):
     enc.alpha_reject(); enc.alpha_finish(None)
 L = lib()
 L.yk_debug_path_stats.argtypes = [C.c_void_p, C.c_int]; L.yk_debug_path_stats.restype = C.c_int

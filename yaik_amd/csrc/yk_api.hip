@@ -77,6 +77,17 @@ static int yk_alloc_image_run(yk_ctx* c) {
     for (int i = 0; i < 7; i++) B.bitmap[i] = B.small + oBm[i];
     B.bm0b = B.small + oBm0b; B.coverage = reinterpret_cast<uint16_t*>(B.small + oCov);
     B.tileInfo = reinterpret_cast<uint2*>(B.small + oInfo); B.runSums = reinterpret_cast<uint32_t*>(B.small + oRun);
+    {   // what a strip of the fused kernel stores where, and its unit decode: both fixed by the shape and the arena's layout
+        YkOutGeom g;
+        for (int i = 0; i < 7; i++) g.oBm[i] = (uint32_t)oBm[i];
+        g.oBm0b = (uint32_t)oBm0b; g.oRun = (uint32_t)oRun;
+        g.xBB64 = (c->fullW + 63) / 64; g.xBB32 = (c->fullW + 31) / 32; g.yBB32 = (c->h + 31) / 32; g.tilesW = c->tilesW; g.tilesH = c->tilesH;
+        YkOutRow tab[4][YK2_OT_ROWS];
+        yk_out_table_fill(tab, g, fs);
+        YK_HIP(c, M.outTab.alloc(s, sizeof tab / sizeof(uint4)));
+        YK_HIP(c, hipMemcpy(M.outTab, tab, sizeof tab, hipMemcpyHostToDevice));              // synchronous (allocation time)
+        c->divXBB64 = yk_udiv_make((uint32_t)g.xBB64); c->divNBf = yk_udiv_make((uint32_t)nB64);
+    }
     fs.tileDef = 3 * T8; fs.tileCount = 3 * T8; fs.slots = 3 * T8 * YK_SLOT;
     YK_HIP(c, M.tileDef.alloc(s, fs.tileDef * F, 16));
     YK_HIP(c, M.tileCount.alloc(s, fs.tileCount * F, 16));

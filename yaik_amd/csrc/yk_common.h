@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "../../include/yaik_hip.h"
+#include "yk_udiv.h"
 
 #define YK_BLK      64      // pixels per workgroup block side (= the 64x64 swizzle block of include/YAIK_private.h:212)
 #define YK_LSTRIDE  68      // LDS row pitch in 32-bit words (65 used, 16-byte aligned rows)
@@ -98,7 +99,57 @@ struct YkEncodeParams {
     // 16-byte pieces, lane in this kernel's (Morton) order.  nullptr = not wanted.
     uint4* pixCache;
     YkFrameStrides fs;
+    // yk_encode2_kernel's unit decode: block -> frame and block -> block row without the runtime's integer division (yk_udiv.h; computed when
+    // the image or batch is set).  A launch keeps every block index below YK_UDIV_LIMIT (yk_launch_encode2).
+    YkUdiv divXBB64, divNBf;
+    // yk_encode2_kernel's per-strip bitmap words and run sums: where lane k of a strip stores, as a table built once per handle
+    // (yk_out_table_fill) instead of ~200 scalar instructions per strip.  The rows hold offsets of frame 0; outFrame0 is the frame a
+    // single-frame launch works on (its oBm.. above are already moved on to that frame).
+    const uint4* outTab;
+    uint32_t outFrame0;
 };
+
+// ---- yk_encode2_kernel's output table.  A strip (block BX, BY, strip `wave` of the block, frame fr) stores its share of the seven swizzled
+// bitmaps and its two run sums at offsets into the small-output arena that are all affine in (fr, BX, BY) once `wave` is fixed.  Row
+// [wave][k] describes what lane k < 16 of such a strip stores:
+//   offset = base + fr * sF + BX * sX + BY * sY   if BX < limX and BY < limY, else nothing (the bitmaps of 32-pixel blocks and the run sums end
+//            inside a 64x64 block at the right and bottom edges; a row nothing is stored from has limX = 0)
+//   value  = (s_bm[sel & 31] >> ((sel >> 8) & 31)) & (~0u >> (sel >> 16))     (rows 11, 12: the run sums, computed by the strip)
+// lanes 1..3 store bytes, 4..6 16-bit words, 8..12 32-bit words: one store per access width, every lane with at most one output.
+#define YK2_OT_ROWS 16
+#define YK2_OT_NONE 0xFFFFFFFFu
+struct YkOutRow { uint32_t base, sF, sX, sY, limX, limY, sel, pad; };
+static_assert(sizeof(YkOutRow) == 32, "two 16-byte loads per row");
+struct YkOutGeom { uint32_t oBm[7], oBm0b, oRun; int xBB64, xBB32, yBB32, tilesW, tilesH; };   // offsets of frame 0 inside the arena
+inline void yk_out_table_fill(YkOutRow (*T)[YK2_OT_ROWS], const YkOutGeom& g, const YkFrameStrides& fs) {
+    const uint32_t none = YK2_OT_NONE;
+    auto lim = [](int n, int step) -> uint32_t { return n <= 0 ? 0u : (uint32_t)((n + step - 1) / step); };   // count of B >= 0 with B * step < n
+    for (int wv = 0; wv < 4; wv++) {
+        const uint32_t w1 = (uint32_t)wv & 1u, w2 = (uint32_t)wv >> 1, X64 = (uint32_t)g.xBB64, X32 = (uint32_t)g.xBB32;
+        YkOutRow* R = T[wv];
+        for (int k = 0; k < YK2_OT_ROWS; k++) R[k] = YkOutRow{ 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+        auto sel = [](uint32_t idx, uint32_t sh, uint32_t bits) { return idx | (sh << 8) | ((32u - bits) << 16); };
+        // bytes: 16x16 (4 bits of the strip), 16x8, 8x16 -- byte `wave` of the block's word
+        R[1] = YkOutRow{ g.oBm0b + wv, (uint32_t)fs.bm0b, 4u, 4u * X64, none, none, sel(0, 4u * wv, 4), 0u };
+        R[2] = YkOutRow{ g.oBm[1] + wv, (uint32_t)fs.bitmap[1], 4u, 4u * X64, none, none, sel(1, 8u * wv, 32), 0u };
+        R[3] = YkOutRow{ g.oBm[2] + wv, (uint32_t)fs.bitmap[2], 4u, 4u * X64, none, none, sel(2, 8u * wv, 32), 0u };
+        // 16-bit words: 8x8, then 4x8 in the two 32x64 swizzle blocks of the 64x64 block
+        R[4] = YkOutRow{ g.oBm[3] + 2u * wv, (uint32_t)fs.bitmap[3], 8u, 8u * X64, none, none, sel(3 + w2, 16u * w1, 32), 0u };
+        for (uint32_t sx = 0; sx < 2; sx++)
+            R[5 + sx] = YkOutRow{ g.oBm[5] + (sx * 4u + wv) * 2u, (uint32_t)fs.bitmap[5], 16u, 8u * X32, lim(g.xBB32 - (int)sx, 2), none, sel(9 + sx * 2 + w2, 16u * w1, 32), 0u };
+        // 32-bit words: 8x4 (64x32 swizzle blocks), 4x4 (32x32 swizzle blocks), the sums of the strip's two runs of eight tiles
+        const uint32_t limY32 = lim(g.yBB32 - (int)w2, 2);
+        R[8] = YkOutRow{ g.oBm[4] + w2 * 8u * X64 + w1 * 4u, (uint32_t)fs.bitmap[4], 8u, 16u * X64, none, limY32, sel(5 + w2 * 2 + w1, 0, 32), 0u };
+        for (uint32_t sx = 0; sx < 2; sx++)
+            R[9 + sx] = YkOutRow{ g.oBm[6] + w2 * 8u * X32 + sx * 8u + w1 * 4u, (uint32_t)fs.bitmap[6], 16u, 16u * X32, lim(g.xBB32 - (int)sx, 2), limY32,
+                                  sel(13 + (w2 * 2 + sx) * 2 + w1, 0, 32), 0u };
+        if ((g.tilesW & 7) == 0) {                              // other widths add to the scan block's counters instead
+            const uint32_t runsW = (uint32_t)(g.tilesW >> 3);
+            for (int r = 0; r < 2; r++)
+                R[11 + r] = YkOutRow{ g.oRun + (uint32_t)(wv * 2 + r) * runsW * 4u, (uint32_t)fs.runSums * 4u, 4u, 32u * runsW, none, lim(g.tilesH - wv * 2 - r, 8), 0u, 0u };
+        }
+    }
+}
 
 // yk_encode_streams_batch (yk_streams_batch.hip): one record per frame in HBM, the bases of the frame's streams in the batch's output buffer
 // (nullptr: empty or not requested); the emit kernels read the record of their frame through uniform loads
@@ -153,6 +204,7 @@ struct YkImageBufs {
     YkBuf<int> alphaUnitBox;            // yk_alpha_kernel: one box {x0, y0, x1, y1} per work unit (yk_alpha_units) and frame, folded by yk_alpha_box_kernel
     // encode outputs and compaction
     YkBuf<uint8_t> small;               // one allocation: bitmap[0..6], bm0b, coverage, tileInfo, runSums (each nFrames times)
+    YkBuf<uint4> outTab;                // yk_encode2_kernel's output table (yk_out_table_fill): [4 strips of a block][YK2_OT_ROWS] rows of 32 bytes
     YkBuf<uint16_t> tileDef; YkBuf<uint8_t> tileCount, slots;
     YkBuf<int32_t> dst[3];
     YkBuf<uint32_t> blockSums, blockCnt, totals;
@@ -188,6 +240,7 @@ struct yk_ctx {
     // yk_frame(c, f) computes the arrays of frame f from them, and the single-image entry points work on frame `curFrame`
     int nFrames = 1, curFrame = 0;
     YkFrameStrides fs = {};
+    YkUdiv divXBB64 = {}, divNBf = {};   // yk_encode2_kernel's unit decode (yk_udiv.h), set with the image
     struct Bases {
         const int32_t* plane[4];        // the bound input planes (nullptr: not bound)
         uint8_t* keep;                  // mtW*mtH keep flags of the alpha stage

@@ -614,7 +614,8 @@ template <int K> __device__ __forceinline__ uint32_t y2_writelane_k(uint32_t v, 
 __device__ __forceinline__ uint32_t y2_writelane(uint32_t v, int k, uint32_t old) {
     switch (k) {
         case 0: return y2_writelane_k<0>(v, old); case 1: return y2_writelane_k<1>(v, old); case 2: return y2_writelane_k<2>(v, old);
-        case 3: return y2_writelane_k<3>(v, old); case 4: return y2_writelane_k<4>(v, old); default: return y2_writelane_k<5>(v, old);
+        case 3: return y2_writelane_k<3>(v, old); case 4: return y2_writelane_k<4>(v, old); case 5: return y2_writelane_k<5>(v, old);
+        case 11: return y2_writelane_k<11>(v, old); default: return y2_writelane_k<12>(v, old);      // 11, 12: the run sums' lanes (output table)
     }
 }
 // -DYK2_TIMING (tools/wave_timeline.sh only, never shipped): every wave records the shader clock and the 100 MHz real-time counter at
@@ -712,6 +713,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     // range phase: the index words of a plane's sixteen rows per lane; the staged pixels are dead by then (the test build's LUTs live there)
     __shared__ uint32_t s_iwTest[WANT_DST ? 1024 : 1];
     uint32_t* const s_iw = WANT_DST ? s_iwTest : s_mem;
+    uint32_t* const s_park = WANT_DST ? s_iwTest : s_sp;                     // 128 words the load stage leaves for the outputs section: the range phase's, idle until then
     static_assert(WANT_DST || kPixWords >= 1024, "index words need 4 KB");
 
     const int lane = threadIdx.x;
@@ -739,20 +741,26 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     const int grp = slot / (YK2_RUN * 4);
     const int unit = (grp * 8 + ((xcd + grp) & 7)) * (YK2_RUN * 4) + (slot - grp * (YK2_RUN * 4));
     int L = unit >> 2; const int wave = unit & 3;                            // block (row-major, frames back to back) and strip inside the block
-    if (L >= nB) return;
-    // batch: per-image pointers of this block's frame (wave-uniform scalars; the kernel argument itself is never copied)
-    size_t fr = 0;
-    if (P.nFrames > 1) { fr = (size_t)(L / nBf); L -= (int)fr * nBf; }
+    // A unit behind the last block (the grid is rounded up) leaves once its loads are out, as block 0: up to there the code is one basic
+    // block, so the kernel arguments it needs are fetched in one go instead of one round trip to the constant cache per branch.
+    const bool spare = L >= nB;
+    L = spare ? 0 : L;
+    // batch: per-image pointers of this block's frame (wave-uniform scalars; the kernel argument itself is never copied).  The two divisions
+    // of the unit decode are a multiplication and a shift each, exact for every block index a launch produces (yk_udiv.h; a single image has
+    // nBf = nB: frame 0 comes out by itself); only what the pixel loads need is derived in front of them.
+    const uint32_t frU = yk_udiv((uint32_t)L, P.divNBf.mul, P.divNBf.shift);
+    L -= (int)frU * nBf;
+    const size_t fr = frU;
     const int32_t* const pl0 = P.plane[0] + fr * P.fs.plane; const int32_t* const pl1 = P.plane[1] + fr * P.fs.plane; const int32_t* const pl2 = P.plane[2] + fr * P.fs.plane;
-    const uint8_t* const keepP = P.keep ? P.keep + fr * P.fs.keep : nullptr;
-    const int32_t* const boundsP = P.bounds ? P.bounds + fr * 16 : nullptr;
-    uint8_t* const slotsP = P.slots + fr * P.fs.slots;
-    uint32_t* const blockCntP = P.blockCnt + fr * P.fs.blockN;
-    const int BY = L / P.xBB64, BX = L - BY * P.xBB64;
+    const int BY = (int)yk_udiv((uint32_t)L, P.divXBB64.mul, P.divXBB64.shift), BX = L - BY * P.xBB64;
     const int w = P.w, h = P.h;
+    const int mt0 = (BY * 4 + wave) * P.mtW + BX * 4;                        // the strip's first macro-tile
 
     YK2_PROBE(0);
     if (lane < 24) s_bm[lane] = 0;
+    typedef uint32_t y2_u32x2 __attribute__((ext_vector_type(2)));
+    typedef int32_t y2_i32x4 __attribute__((ext_vector_type(4)));
+    y2_u32x2 keep8; y2_i32x4 bnd;                                            // the alpha stage's results for this strip (read with the pixels, used by the range phase)
     // ---- stage the clamped 65x17 strip (Plane::GetPixelValue clamp, encoder/framework.h:116-121).  All 18 loads of a lane are
     // issued before the first use and none sits in a divergent branch (a branch ends in a wait for the loads it holds: the round
     // trips would run one after the other): addresses are clamped instead, every lane loads, and strips on the image's right edge
@@ -798,8 +806,32 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
         // the reciprocals of the range phase's error terms ride along (every strip pays one load and one LDS store; a coded strip used to
         // compute its 256 quotients itself, four correctly rounded divisions per lane)
         const float4 rc4 = *reinterpret_cast<const float4*>(P.qtab + YK2_QBYTES + (size_t)lane * 16);
+        // so does the lane's row of the output table (yk_common.h): where this strip's bitmap words and run sums go
+        const uint4* const orow = P.outTab + (wave * YK2_OT_ROWS + (lane & (YK2_OT_ROWS - 1))) * 2;
+        const uint4 ta = orow[0], tb = orow[1];
+        // and what the alpha stage left for this strip, through the scalar cache: the kept box and the keep bytes of the strip's four macro-tiles
+        // (the eight bytes around them; the keep array is padded).  Read at the range phase they were two round trips one behind the other in
+        // front of its first ballot.  Strips without them read the kernel arguments instead, so that no load hangs in a branch.
+        // The two loads are written out, because the compiler moves a scalar load to the block of its first use, behind the wait for the pixels;
+        // it then knows nothing of them, so the wait stands at the fence behind the staging.
+        {
+            const bool rowIn = BY * 64 + wave * 16 < h;
+            const uintptr_t args = reinterpret_cast<uintptr_t>(Pp);
+            const uintptr_t kpIn = reinterpret_cast<uintptr_t>(P.keep) + fr * P.fs.keep + (uintptr_t)(mt0 & ~3);
+            const uintptr_t bpIn = reinterpret_cast<uintptr_t>(P.bounds) + fr * 64;
+            const uintptr_t kp = (P.keep != nullptr && rowIn) ? kpIn : args, bp = P.bounds != nullptr ? bpIn : args;
+            asm volatile("s_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx4 %1, %3, 0x0" : "=&s"(keep8), "=&s"(bnd) : "s"(kp), "s"(bp));
+        }
 
         __builtin_amdgcn_s_setprio(0);                                       // all loads are out
+        if (spare) return;
+        {
+            const uint32_t frT = frU + P.outFrame0;
+            const uint32_t o = ta.x + frT * ta.y + (uint32_t)BX * ta.z + (uint32_t)BY * ta.w;
+            // parked in LDS over the gradient passes (s_park): the lane's offset, or none, and how it picks its value
+            s_park[lane] = ((uint32_t)BX < tb.x && (uint32_t)BY < tb.y) ? o : YK2_OT_NONE;
+            s_park[64 + lane] = tb.z;
+        }
         uint4 o[4], ob;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -819,6 +851,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
         *reinterpret_cast<float4*>(&s_rcp[lane * 4]) = rc4;
 
     }
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(keep8), "+s"(bnd));           // the two scalar loads are in: the fence below waits on this counter anyway
     __syncthreads();                                                         // single-wave workgroup: an LDS fence
     YK2_PROBE(1);
 
@@ -906,7 +939,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
             }
         }
     }
-    const int mtIdx = ((BY * 64 + wave * 16) >> 4) * P.mtW + ((BX * 64 + q * 16) >> 4);
+    const int mtIdx = mt0 + q;
     // ---- the strip's small outputs: its share of the seven swizzled bitmaps (word index = swizzle-block index, :3801-3805; every pass packs the
     // strip's tiles into whole bytes of the block's words except 16x16: 4 bits per strip, kept as a byte of their own that yk_scan2_kernel folds
     // into the map), the coverage words of its four macro-tiles and, further down, the sums of its two runs of eight tiles and one 8-byte record
@@ -916,36 +949,22 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     __syncthreads();                                                         // fence: s_bm complete; s_pix dead, its LDS becomes s_lut
     YK2_PROBE(2);
     uint8_t* const small = P.small;
-    const uint32_t bmv = s_bm[lane < 24 ? lane : 0];                         // word k of the strip's bitmap image in lane k
-    auto bmWord = [&](const int k) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)bmv, k); };
-    const uint32_t i64 = (uint32_t)(BY * P.xBB64 + BX);
-    const uint32_t frU = (uint32_t)fr;
-    uint32_t off32 = ~0u, val32 = 0u;                                        // the 4-byte class is stored further down, with the run sums
+    // Lane k < 16 holds at most one of these outputs: its offset was formed from row k of the output table while the pixels were on their way
+    // (load stage) and waited in LDS with the row's selector: which word of the strip's bitmap image (s_bm), shifted and masked how.
+    const uint32_t tabOff = s_park[lane], tabSel = s_park[64 + lane];
+    const uint32_t tabVal = (s_bm[tabSel & 31u] >> ((tabSel >> 8) & 31u)) & (~0u >> (tabSel >> 16));
+    uint32_t off32 = (uint32_t)lane - 8u < 5u ? tabOff : ~0u;                // the 4-byte class is stored further down, with the run sums
+    uint32_t val32 = (uint32_t)lane - 8u < 3u ? tabVal : 0u;
     {
-        const uint32_t w1 = (uint32_t)wave & 1u, w2 = (uint32_t)wave >> 1;
-        // bytes: lane 0 = 16x16 (4 bits), lane 1 = 16x8 (tile rows 2w, 2w+1), lane 2 = 8x16 (tile row w)
-        uint32_t off8 = 0u, val8 = 0u;
-        off8 = y2_writelane(P.oBm0b + frU * (uint32_t)P.fs.bm0b + i64 * 4u + (uint32_t)wave, 0, off8);
-        val8 = y2_writelane((bmWord(0) >> (4 * wave)) & 0xFu, 0, val8);
-        off8 = y2_writelane(P.oBm[1] + frU * (uint32_t)P.fs.bitmap[1] + i64 * 4u + (uint32_t)wave, 1, off8);
-        val8 = y2_writelane(bmWord(1) >> (8 * wave), 1, val8);
-        off8 = y2_writelane(P.oBm[2] + frU * (uint32_t)P.fs.bitmap[2] + i64 * 4u + (uint32_t)wave, 2, off8);
-        val8 = y2_writelane(bmWord(2) >> (8 * wave), 2, val8);
-        if (lane < 3) *(small + off8) = (uint8_t)val8;
+        // bytes: lane 1 = 16x16 (4 bits), lane 2 = 16x8 (tile rows 2w, 2w+1), lane 3 = 8x16 (tile row w)
+        if ((uint32_t)lane - 1u < 3u) *(small + tabOff) = (uint8_t)tabVal;
         // 16-bit words: lanes 0, 16, 32, 48 = coverage of the four macro-tiles (bit = cellY*4 + cellX: row-major, the Morton index with its two
-        // middle bits exchanged), lane 1 = 8x8 (tile rows 2w, 2w+1), lanes 2, 3 = 4x8 (32x64 swizzle blocks, tile rows 2w, 2w+1)
+        // middle bits exchanged), lane 4 = 8x8 (tile rows 2w, 2w+1), lanes 5, 6 = 4x8 (32x64 swizzle blocks, tile rows 2w, 2w+1)
         const unsigned long long t = ((cov >> 2) ^ cov) & 0x0C0C0C0C0C0C0C0CULL;
         const unsigned long long covRM = cov ^ t ^ (t << 2);
         uint32_t off16 = ((lane & 15) == 0 && mtIn) ? P.oCov + (frU * (uint32_t)P.fs.coverage + (uint32_t)mtIdx) * 2u : ~0u;
         uint32_t val16 = (uint32_t)((covRM >> (q * 16)) & 0xFFFFULL);
-        off16 = y2_writelane(P.oBm[3] + frU * (uint32_t)P.fs.bitmap[3] + (i64 * 4u + (uint32_t)wave) * 2u, 1, off16);
-        val16 = y2_writelane(bmWord(3 + (int)w2) >> (16 * w1), 1, val16);
-#pragma unroll
-        for (int sx = 0; sx < 2; sx++) {
-            const bool in = BX * 2 + sx < P.xBB32;
-            off16 = y2_writelane(in ? P.oBm[5] + frU * (uint32_t)P.fs.bitmap[5] + ((uint32_t)((BY * P.xBB32 + BX * 2 + sx) * 4 + wave)) * 2u : ~0u, 2 + sx, off16);
-            val16 = y2_writelane(bmWord(9 + sx * 2 + (int)w2) >> (16 * w1), 2 + sx, val16);
-        }
+        if ((uint32_t)lane - 4u < 3u) { off16 = tabOff; val16 = tabVal; }
         if (off16 != ~0u) *reinterpret_cast<uint16_t*>(small + off16) = (uint16_t)val16;
         // optional: the packed pixels of the cells nothing covered, for the live 1-D path (yk_set_pixel_cache): [strip][cell row][lane] 16-byte pieces
         if (P.pixCache != nullptr) {
@@ -957,24 +976,13 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
                 for (int r = 0; r < 4; r++) dstp[r * 64] = make_uint4(pw[r * 4 + 0], pw[r * 4 + 1], pw[r * 4 + 2], pw[r * 4 + 3]);
             }
         }
-        // 32-bit words: lane 1 = 8x4 (64x32 swizzle blocks, tile rows 4w..4w+3), lanes 2, 3 = 4x4 (32x32 swizzle blocks); lanes 4, 5 = the run sums
-        {
-            const bool in = BY * 2 + (int)w2 < P.yBB32;
-            off32 = y2_writelane(in ? P.oBm[4] + frU * (uint32_t)P.fs.bitmap[4] + ((uint32_t)(((BY * 2 + (int)w2) * P.xBB64 + BX) * 2) + w1) * 4u : ~0u, 1, off32);
-            val32 = y2_writelane(bmWord(5 + (int)w2 * 2 + (int)w1), 1, val32);
-#pragma unroll
-            for (int sx = 0; sx < 2; sx++) {
-                const bool in6 = in && (BX * 2 + sx < P.xBB32);
-                off32 = y2_writelane(in6 ? P.oBm[6] + frU * (uint32_t)P.fs.bitmap[6] + ((uint32_t)(((BY * 2 + (int)w2) * P.xBB32 + BX * 2 + sx) * 2) + w1) * 4u : ~0u, 2 + sx, off32);
-                val32 = y2_writelane(bmWord(13 + ((int)w2 * 2 + sx) * 2 + (int)w1), 2 + sx, val32);
-            }
-        }
+        // 32-bit words: lane 8 = 8x4 (64x32 swizzle blocks, tile rows 4w..4w+3), lanes 9, 10 = 4x4 (32x32 swizzle blocks); lanes 11, 12 = the run sums
     }
     YK2_PROBE(3);
     // ---- a10-a13: range quantiser; an 8x8 tile = the quad of lanes {l & ~3 .. l | 3} -----------------------------------
     int cxB = 0, cyB = 0, cw = w, chh = P.fullH, discard = 1;                 // constraint box of DynamicTileEncode (:4386-4391)
-    if (boundsP) {
-        const int b0 = boundsP[0], b1 = boundsP[1], b2 = boundsP[2], b3 = boundsP[3];
+    if (P.bounds != nullptr) {
+        const int b0 = bnd.x, b1 = bnd.y, b2 = bnd.z, b3 = bnd.w;
         discard = (b0 == 0 && b1 == 0 && b2 == w && b3 == P.fullH) ? 1 : 0;    // bbox == whole image: every reject is discarded (EncoderContext.cpp:1294, :1400-1403)
         cxB = (b0 >> 3) << 3; cyB = (b1 >> 3) << 3;
         cw = (((b2 + 7) >> 3) << 3) - cxB; chh = (((b3 + 7) >> 3) << 3) - cyB;
@@ -984,7 +992,9 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     const bool tileIn = (tgx + 8 <= w) && (tgyl + 8 <= h);
     // LeftRightOrder over the constraint box incl. its zero-size rule (encoder/framework.h:239-255)
     const bool part = tileIn && tgx >= cxB && tgx < cxB + cw && tgy >= cyB && tgy < cyB + chh && (tgx + 8 <= cw) && (tgy + 8 <= chh);
-    const bool keepMT = (keepP == nullptr) || discard || (mtIn && keepP[mtIdx] != 0);
+    // the strip's four keep bytes out of the eight that were read around them
+    const uint32_t keep4 = (uint32_t)((((unsigned long long)keep8.y << 32) | keep8.x) >> (8 * (mt0 & 3)));
+    const bool keepMT = (P.keep == nullptr) || discard || (mtIn && ((keep4 >> (8 * q)) & 0xFFu) != 0u);
     const bool tileLive = part && keepMT;
     const int l00 = lane & ~3;                                               // lane of the tile's top-left cell
     // uncovered quadrants of the lane's 8x8 tile: bits 0..3 = top-left, top-right, bottom-left, bottom-right (the quad's lanes in order)
@@ -1008,16 +1018,18 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     {
         const int n16 = (tileLive && !YK2_ABLATE(1)) ? (nTop + nBot) : 0;   // nibbles / 16 of this tile-plane
         if ((P.tilesW & 7) == 0) {
+            // a strip with nothing to code (no valid lane: every live tile is covered, n16 = 0 throughout) stores the zeros lanes 11, 12 already hold
+            if (validMask != 0ULL) {
 #pragma unroll
-            for (int r = 0; r < 2; r++) {
-                const bool mine = writer && ((cy >> 1) == r);
-                const unsigned long long b0 = __ballot(mine && (n16 & 1)), b1 = __ballot(mine && (n16 & 2)), b2 = __ballot(mine && (n16 & 4));
-                const unsigned long long bd = __ballot(mine && n16 > 0);
-                const int row = ((BY * 64 + wave * 16) >> 3) + r;
-                off32 = y2_writelane(row < P.tilesH ? P.oRun + (frU * (uint32_t)P.fs.runSums + (uint32_t)(row * (P.tilesW >> 3) + BX)) * 4u : ~0u, 4 + r, off32);
-                val32 = y2_writelane((uint32_t)(__popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2)) | ((uint32_t)__popcll(bd) << 16), 4 + r, val32);
+                for (int r = 0; r < 2; r++) {
+                    const bool mine = writer && ((cy >> 1) == r);
+                    const unsigned long long b0 = __ballot(mine && (n16 & 1)), b1 = __ballot(mine && (n16 & 2)), b2 = __ballot(mine && (n16 & 4));
+                    const unsigned long long bd = __ballot(mine && n16 > 0);
+                    val32 = y2_writelane((uint32_t)(__popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2)) | ((uint32_t)__popcll(bd) << 16), 11 + r, val32);
+                }
             }
         } else if (writer && n16 > 0) {
+            uint32_t* const blockCntP = P.blockCnt + fr * P.fs.blockN;
             atomicAdd(&blockCntP[((size_t)tileIdx >> 10) * 2], 16u * (uint32_t)n16);
             atomicAdd(&blockCntP[((size_t)tileIdx >> 10) * 2 + 1], 1u);
         }
@@ -1030,6 +1042,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     // behind the plane loop by the tile's first lane: 16 lanes x 8 bytes = two runs of 64 contiguous bytes per strip (round 3: six stores)
     uint32_t defs01 = 0u, defs2c = 0u;
     if (validMask != 0ULL && !YK2_ABLATE(1)) {
+        uint8_t* const slotsP = P.slots + fr * P.fs.slots;
         uint32_t* lut = &s_lut[WANT_DST ? tw : 0][0];
         // curve constants for buildLut (test-only reconstruction); fetched here, off the path of the strip's pixel loads
         if (WANT_DST) {
@@ -1460,6 +1473,10 @@ int yk_launch_encode2(yk_ctx* c, const YkEncodeParams& P) {
     if (!P.qtab) return yk_fail(c, YK_ERR_STATE, "quantiser table missing");
     if (P.startMode != 0 && P.startMode != 3) return yk_fail(c, YK_ERR_BAD_ARG, "startMode must be 0 or 3");
     const int nB = P.xBB64 * P.yBB64 * P.nFrames, group = 8 * YK2_RUN;
+    // the unit decode divides block indices below the rounded-up grid by multiply and shift: exact below YK_UDIV_LIMIT (yk_udiv.h).  The C-ABI
+    // admits 512 x 512 blocks per frame and 1024 frames, 2^28 blocks.
+    if ((long long)P.xBB64 * P.yBB64 * P.nFrames + group > (long long)YK_UDIV_LIMIT) return yk_fail(c, YK_ERR_BAD_ARG, "too many blocks for one launch");
+    if (!P.outTab) return yk_fail(c, YK_ERR_STATE, "output table missing");
     // (the 16x16 map needs no clearing any more: the strips store their 4 bits as bytes of their own, yk_scan2_kernel folds them into the map)
     dim3 grid(((nB + group - 1) / group) * group * 4);
     if (P.wantDst) {

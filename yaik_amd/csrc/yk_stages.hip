@@ -389,6 +389,8 @@ int yk_launch_encode(yk_ctx* c, int rejectFactor, int mode3BitOnly, int wantDst,
     auto off = [&](const void* p) { return (uint32_t)(static_cast<const uint8_t*>(p) - V.small); };
     for (int i = 0; i < 7; i++) P.oBm[i] = off(V.bitmap[i]);
     P.oBm0b = off(V.bm0b); P.oCov = off(V.coverage); P.oInfo = off(V.tileInfo); P.oRun = off(V.runSums);
+    P.divXBB64 = c->divXBB64; P.divNBf = c->divNBf;
+    P.outTab = c->img.outTab; P.outFrame0 = batch ? 0u : (uint32_t)c->curFrame;    // the table holds frame 0's offsets
     P.pixCache = nullptr; c->pixCacheValid = false;
     if (c->pixCacheOn && !batch && c->kernelVersion == 2 && c->nFrames == 1) {
         if (!c->img.pixCache) YK_HIP(c, c->img.pixCache.alloc(c->stream, (size_t)P.xBB64 * 64 * ((size_t)(c->h + 15) / 16 * 16) / 4, 4096));
