@@ -759,6 +759,33 @@ int yk_decode_alpha_mask_batch_device(yk_ctx* c, const int32_t* modes /* nFrames
                                       const size_t* mipBytes, const int32_t* mipBoxes /* nFrames x {x,y,w,h} in 16-px tiles */, int noChunkAlpha);
 int yk_decode_alpha_batch_status(yk_ctx* c, int32_t* out /* nFrames */);
 
+/* ---- a window of every frame of a batch: one rectangle size, one origin per frame ----
+ * yk_decode_set_batch_windows gives frame f of the batch begun by yk_decode_begin_batch the window (xy[2 f], xy[2 f + 1], ww, wh); xy is host
+ * memory, nFrames pairs, read before the call returns.  From here on the batch chunk calls owe frame f's planes only the pixels inside its window,
+ * exactly as yk_decode_set_window does for a single image: yk_decode_gradient_all_batch_device does the map-sized work of every frame whole (owner
+ * lattice, corner count, scan and emit, the marks of every block in tile4x4Mask) and renders only the 64x64 blocks a frame's window touches,
+ * yk_decode_1d_batch_device counts and scans every tile and decodes only the window's; for every pixel inside its window frame f holds what the whole
+ * batch decode leaves there, its tile4x4Mask is whole and exact, and no byte of its planes outside its window rounded out to multiples of 64
+ * (clipped to the image) is written.  yk_decode_alpha[_mask]_batch_device are not affected: the 'ALPM' planes stay whole.
+ * Valid after yk_decode_begin_batch (a batch of one frame included) and before any chunk of that batch is decoded (gradient, plane-subset, mask
+ * split, '3DTL', 1-D); otherwise, and on a handle begun with yk_decode_begin, YK_ERR_STATE.  Every rectangle obeys the rule of
+ * yk_decode_set_window (x0, y0, ww, wh multiples of 8, ww, wh >= 8, inside the image); anything else, and a NULL xy, is YK_ERR_BAD_ARG.  Every
+ * argument is checked before anything is queued; a refused argument leaves the batch with no windows.  ww == wh == 0 clears the windows (xy is not
+ * looked at); yk_decode_begin and yk_decode_begin_batch always clear them.  yk_decode_set_window stays refused on a batch.
+ * The rectangles travel through the pinned ring into a table in HBM that the handle owns, on the handle's stream: kernels of an earlier batch that
+ * are still queued read the earlier rectangles.  No host synchronisation (a ring slot is waited for only when four later table copies are queued).
+ * While windows are set, the calls that need whole frames return YK_ERR_STATE with a message that names the windows:
+ * yk_decode_output_batch_device, yk_decode_output_batch_alpha_device, yk_decode_output_scaled_batch_device,
+ * yk_decode_output_mipchain_batch_device, yk_decode_compare_*, and every single-image output and chunk call on the selected frame.
+ * yk_decode_select_frame, yk_decode_planes[_device] and yk_decode_tile4x4[_planes] stay allowed: the selected frame's planes are exact inside its
+ * window (unspecified outside), its marks whole and exact.
+ * yk_decode_output_batch_windows_device: frame f's window goes to devOut + f * frameBytes as ww x wh pixels, with the layout, pitch and channel
+ * rules of yk_decode_output_batch_device (the pitch checks are made against ww x wh).  alpha = 0..255 is a constant; alpha = -1 reads frame f's
+ * plane of yk_decode_alpha[_mask]_batch_device at its window's offset (YK_ERR_STATE when the batch has no valid alpha planes).  YK_ERR_STATE with
+ * no windows set.  One launch, timed as one YK_STAGE_DEC_DETILE interval. */
+int yk_decode_set_batch_windows(yk_ctx* c, const int* xy /* nFrames x {x0, y0}, host memory */, int ww, int wh);
+int yk_decode_output_batch_windows_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha);
+
 /* ---- round-trip quality (new): what the decode holds against a source image, both in HBM -----------------------------------------
  * The codec is lossy; these calls say how lossy a round trip was without moving a pixel to the host.  One kernel reads the decoder's 8x8-tiled
  * planes (and, with four channels, the decoded 'ALPM' plane) and the source where it lies, a second one folds the workgroups' records; per frame

@@ -177,6 +177,8 @@ SIGNATURES = {
     "yk_decode_alpha_mask_batch_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]),
     "yk_decode_alpha_batch_status": (C.c_int, [vp, vp]),
     "yk_decode_output_batch_alpha_device": (C.c_int, [vp, vp, sz, sz, sz]),
+    "yk_decode_set_batch_windows": (C.c_int, [vp, vp, C.c_int, C.c_int]),
+    "yk_decode_output_batch_windows_device": (C.c_int, [vp, vp, sz, sz, sz, C.c_int, C.c_int]),
     "yk_decode_compare_device": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_int, vp, vp]),
     "yk_decode_compare_batch_device": (C.c_int, [vp, vp, sz, sz, sz, C.c_int, C.c_int, vp, vp]),
     "yk_decode_compare_planes_device": (C.c_int, [vp, C.POINTER(vp), C.c_int, sz, C.c_int, vp, vp]),

@@ -321,6 +321,10 @@ struct yk_ctx {
     // dBatchBegun: the handle was begun by yk_decode_begin_batch (no windows there); dChunkSeen: a chunk of the image has been decoded
     int dWinX = 0, dWinY = 0, dWinW = 0, dWinH = 0;
     bool dWinSet = false, dBatchBegun = false, dChunkSeen = false;
+    // yk_decode_set_batch_windows: one window per frame of the batch, all of dBWinW x dBWinH pixels.  dBWinTab holds frame f's exact rectangle
+    // {x0, y0, x1, y1} (pixels) in HBM for the batch x window kernels: 1024 entries, allocated once, written through the pinned ring below
+    bool dBWinSet = false; int dBWinW = 0, dBWinH = 0;
+    YkBuf<int> dBWinTab;
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
     // yk_decode_prepare_device: the map-sized work of this image is done and what a render needs is kept in dPrep (yk_decode.hip) until the next
     // yk_decode_begin[_batch]; the buffers in dPrep are grow-only and go with the handle (yk_dec_prepared_free)
@@ -401,7 +405,11 @@ int yk_refuse(yk_ctx* c, int code, const char* what);
 
 // the calls that hand out or compare the whole image refuse while a window is set: outside it the planes hold whatever they held before
 // ... and while the image is prepared for windows (yk_decode_prepare_device): only the blocks some window asked for are rendered
+// ... and while the frames of a batch have windows (yk_decode_set_batch_windows): the same holds per frame
+#define YK_DEC_NO_BATCH_WINDOWS(c, name) do { \
+    if ((c)->dBWinSet) return yk_refuse((c), YK_ERR_STATE, name " needs whole frames, but windows are set on this batch (yk_decode_set_batch_windows): use yk_decode_output_batch_windows_device"); } while (0)
 #define YK_DEC_NO_WINDOW(c, name) do { \
+    YK_DEC_NO_BATCH_WINDOWS(c, name); \
     if ((c)->dWinSet) return yk_refuse((c), YK_ERR_STATE, name " needs the whole image, but a window is set on this decode (yk_decode_set_window): use yk_decode_output_window_device"); \
     if ((c)->dPrepared) return yk_refuse((c), YK_ERR_STATE, name " needs the whole image, but this image is prepared for windows (yk_decode_prepare_device): use yk_decode_render_windows_device"); } while (0)
 // the chunk calls and the single-window calls: a prepared image takes no further chunk and hands out pixels through yk_decode_render_windows_device

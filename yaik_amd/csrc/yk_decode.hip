@@ -496,6 +496,20 @@ __global__ __launch_bounds__(256) void yk_decall_render_blocks_batch_kernel(cons
     yk_decall_render_blocks_body<false>(B.plans[f], w, h, latW, B.mapRGB + f * B.sMapRGB, B.planes + f * B.sPlanes, planeSize, tileW,
                                  reinterpret_cast<uint32_t*>(B.tile4 + f * B.sTile4), stride4, blockIdx.x);
 }
+// A batch whose frames have windows (yk_decode_set_batch_windows): frame f's exact rectangle {x0, y0, x1, y1} is entry f of a table in HBM (like the
+// plans: up to 1024 of them do not fit kernel arguments), read by every workgroup of the frame through a uniform address
+__device__ __forceinline__ DWinRect yk_bwin_rect64(const DWinRect e, int w, int h) {      // ... rounded out to 64-pixel blocks, clipped to the image
+    DWinRect r = { e.x0 & ~63, e.y0 & ~63, (e.x1 + 63) & ~63, (e.y1 + 63) & ~63 };
+    if (r.x1 > w) r.x1 = w;
+    if (r.y1 > h) r.y1 = h;
+    return r;
+}
+__global__ __launch_bounds__(256) void yk_decall_render_blocks_batch_win_kernel(const DecBatch B, const DWinRect* __restrict__ wins, int w, int h, int latW, size_t planeSize,
+                                                                                int tileW, int stride4) {
+    const size_t f = blockIdx.y;
+    yk_decall_render_blocks_body<true>(B.plans[f], w, h, latW, B.mapRGB + f * B.sMapRGB, B.planes + f * B.sPlanes, planeSize, tileW,
+                                 reinterpret_cast<uint32_t*>(B.tile4 + f * B.sTile4), stride4, blockIdx.x, yk_bwin_rect64(wins[f], w, h));
+}
 
 // ---- partial planes: DecompressGradient4x4R / G / B / RG / GB / RB (decoder/YAIK_Gradient.cpp:1208-1226, :1420-2732) ------------
 // `loaded` holds one bit per plane and lattice point (the three planes of mapRGBMask); the masks are split first (UpdateTileAndRGBMask).
@@ -814,6 +828,16 @@ __global__ __launch_bounds__(256) void yk_dec1d_batch_kernel(const D1Batch B, si
     yk_dec1d_body<YK_D1_ALL>(yk_d1batch_u32(B, f, B.oOff), T8, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oTot), fr.type, (size_t)fr.typeBytes,
                   fr.pix, (size_t)fr.pixBytes, invRange, B.planes + f * B.sPlanes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x);
 }
+// ... with a window per frame (yk_decode_set_batch_windows): the tiles of frame f's window, its origin from the table; the windows of a batch have
+// one size, so nWin, wtW and the grid are every frame's
+__global__ __launch_bounds__(256) void yk_dec1d_batch_win_kernel(const D1Batch B, const DWinRect* __restrict__ wins, size_t nWin, uint32_t wtW, uint32_t tilesW, int invRange,
+                                                                 size_t planeSize) {
+    const size_t f = blockIdx.z;
+    const D1Frame& fr = B.frames[f];
+    const D1Win wn = { (uint32_t)wins[f].x0 >> 3, (uint32_t)wins[f].y0 >> 3, wtW, tilesW };
+    yk_dec1d_body<YK_D1_WIN>(yk_d1batch_u32(B, f, B.oOff), nWin, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oTot), fr.type, (size_t)fr.typeBytes,
+                  fr.pix, (size_t)fr.pixBytes, invRange, B.planes + f * B.sPlanes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x, wn);
+}
 
 __global__ void yk_dec_mask_kernel(const uint8_t* __restrict__ bits, int bw, int bh, unsigned long long* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1009,6 +1033,23 @@ __global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_batch_kernel(YkDe
     a.planes += (size_t)blockIdx.y * planesFrame; a.out += (size_t)blockIdx.y * outFrame;
     if constexpr (ASRC == YK_DT_ALPHA_PLANE) a.alpha += (size_t)blockIdx.y * alphaFrame;
     yk_dec_detile_body<C, PLANAR, ASRC>(a, blockIdx.x);
+}
+// a batch with a window per frame (yk_decode_set_batch_windows): frame blockIdx.y's window, its origin from the table in HBM, goes to
+// a.out + f * outFrame as a.nTiles = wtW x wtH tiles; YK_DT_ALPHA_PLANE reads frame f's whole alpha plane at the window's own offset
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_batch_win_kernel(YkDetileArgs a, const DWinRect* __restrict__ wins, uint32_t wtW, size_t planesFrame,
+                                                                                size_t outFrame, size_t alphaFrame) {
+    const uint32_t f = blockIdx.y;
+    const uint32_t x0 = (uint32_t)wins[f].x0, y0 = (uint32_t)wins[f].y0;
+    a.planes += (size_t)f * planesFrame; a.out += (size_t)f * outFrame;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) a.alpha += (size_t)f * alphaFrame + (size_t)y0 * a.strideA + x0;
+    const YkDetileWin wn = { x0 >> 3, y0 >> 3, wtW };
+    yk_dec_detile_win_body<C, PLANAR, ASRC>(a, wn, blockIdx.x);
+}
+template <int C, bool PLANAR, int ASRC>
+static void yk_dt_launch_batch_win(const YkDetileArgs& a, hipStream_t s, int nFrames, const DWinRect* wins, uint32_t wtW, size_t planesFrame, size_t outFrame, size_t alphaFrame) {
+    const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
+    hipLaunchKernelGGL((yk_dec_detile_batch_win_kernel<C, PLANAR, ASRC>), dim3(gx, (unsigned)nFrames), dim3(YK_DT_THREADS), 0, s, a, wins, wtW, planesFrame, outFrame, alphaFrame);
 }
 
 // nFrames == 0: the selected frame (the existing single-image launch); otherwise nFrames frames, planesFrame / outFrame bytes apart
@@ -1460,11 +1501,26 @@ __global__ __launch_bounds__(256) void yk_dec_zero_unmarked_batch_kernel(const u
                                                                          uint8_t* __restrict__ planes, size_t sPlanes, size_t planeSize) {
     yk_dec_zero_unmarked_body(tile4 + (size_t)blockIdx.z * sTile4, tile4Size, 0, stride4, tilesW, T8, planes + (size_t)blockIdx.z * sPlanes, planeSize);
 }
+// a batch with a window per frame: frame = blockIdx.z, the tiles of its window only (thread j of nWin as in the window form above)
+__global__ __launch_bounds__(256) void yk_dec_zero_unmarked_batch_win_kernel(const uint8_t* __restrict__ tile4, size_t sTile4, size_t tile4Size, int stride4, int tilesW,
+                                                                             const DWinRect* __restrict__ wins, uint32_t wtW, uint32_t nWin, uint8_t* __restrict__ planes,
+                                                                             size_t sPlanes, size_t planeSize) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nWin) return;
+    const size_t f = blockIdx.z;
+    const uint32_t tx0 = (uint32_t)wins[f].x0 >> 3, ty0 = (uint32_t)wins[f].y0 >> 3;
+    const uint32_t jy = j / wtW, jx = j - jy * wtW;
+    yk_dec_zero_unmarked_tile(tile4 + f * sTile4, tile4Size, 0, stride4, tilesW, (size_t)(ty0 + jy) * tilesW + tx0 + jx, planes + f * sPlanes, planeSize);
+}
 static int yk_dec_settle(yk_ctx* c) {
     if (!c->dPlanesStale) return YK_OK;
     const int w = c->dw, h = c->dh;
     const size_t T8 = (size_t)(w >> 3) * (h >> 3);
-    if (c->dWinSet) {                                                           // a window is a single image's
+    if (c->dBWinSet) {                                                          // every frame of the batch inside its own window
+        const uint32_t wtW = (uint32_t)(c->dBWinW >> 3), nWin = wtW * (uint32_t)(c->dBWinH >> 3);
+        hipLaunchKernelGGL(yk_dec_zero_unmarked_batch_win_kernel, dim3((nWin + 255) / 256, 3, (unsigned)c->dFrames), dim3(256), 0, c->stream, c->dB.tile4, c->dStride.tile4,
+                           c->dTile4Size, (w + 15) >> 4, w >> 3, reinterpret_cast<const DWinRect*>(c->dBWinTab.p), wtW, nWin, c->dB.planes, c->dStride.planes, c->dPlaneSize);
+    } else if (c->dWinSet) {                                                    // a window is a single image's
         const uint32_t wtW = (uint32_t)(c->dWinW >> 3), nWin = wtW * (uint32_t)(c->dWinH >> 3);
         hipLaunchKernelGGL(yk_dec_zero_unmarked_win_kernel, dim3((nWin + 255) / 256, 3), dim3(256), 0, c->stream, c->dB.tile4, c->dTile4Size, c->dSplit ? 1 : 0,
                            (w + 15) >> 4, w >> 3, (uint32_t)(c->dWinX >> 3), (uint32_t)(c->dWinY >> 3), wtW, nWin, c->dB.planes, c->dPlaneSize);
@@ -1547,6 +1603,7 @@ static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
     }
     c->dCur = 0;
     c->dWinSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; c->dChunkSeen = false; c->dBatchBegun = false;
+    c->dBWinSet = false; c->dBWinW = c->dBWinH = 0;                             // the table stays queued kernels' to read: the next set writes it behind them
     c->dPrepared = false;                                                       // a prepared image ends here; what it kept is overwritten by the next prepare
     // The planes (3 B per pixel: 201 MB at 8192 x 8192, 40 us of every frame) are NOT cleared: every renderer marks what it writes in tile4x4Mask and
     // the 1-D decode writes every unmarked quadrant, so after a whole file nothing stale is left; a flow that stops earlier (or writes without
@@ -1622,6 +1679,35 @@ int yk_dec_table_upload(yk_ctx* c, int slot, void* dev, size_t bytes) {
     return YK_OK;
 }
 
+// One window per frame of the batch begun by yk_decode_begin_batch (include/yaik_hip.h).  The rectangles go through the pinned ring
+// into a table of the handle's own (not the scratch buffer, which every chunk call lays out anew): the copy is queued on the handle's stream, so the
+// kernels of an earlier batch that are still queued read the earlier rectangles, and the ring slot is reused only once its copy has run.
+int yk_decode_set_batch_windows(yk_ctx* c, const int* xy, int ww, int wh) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!yk_dec_begun(c) || !c->dBatchBegun) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows: yk_decode_begin_batch first (the window of a single image is yk_decode_set_window's)");
+    if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows: a chunk of this batch has been decoded already; set the windows right after yk_decode_begin_batch");
+    c->dBWinSet = false; c->dBWinW = c->dBWinH = 0;                              // a refusal below leaves the batch without windows
+    if (ww == 0 && wh == 0) return YK_OK;
+    if (!xy) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_batch_windows: the origin table is NULL");
+    const int N = c->dFrames;
+    bool ok = !((ww | wh) & 7) && ww >= 8 && wh >= 8 && ww <= c->dw && wh <= c->dh;
+    for (int f = 0; ok && f < N; f++) {
+        const int x0 = xy[2 * f], y0 = xy[2 * f + 1];
+        ok = !((x0 | y0) & 7) && x0 >= 0 && y0 >= 0 && x0 <= c->dw - ww && y0 <= c->dh - wh;
+    }
+    if (!ok) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_batch_windows: x0, y0, ww, wh must be multiples of 8 with ww, wh >= 8 and every frame's window inside the image");
+    YK_HIP(c, hipSetDevice(c->device));
+    YK_HIP(c, c->dBWinTab.reserve(c->stream, (size_t)1024 * 4));                // every batch fits: allocated once, so no later call waits for queued readers
+    int slot; void* host;
+    { const int rc = yk_dec_table_host(c, (size_t)N * sizeof(DWinRect), &slot, &host); if (rc) return rc; }
+    DWinRect* tab = static_cast<DWinRect*>(host);
+    for (int f = 0; f < N; f++) tab[f] = DWinRect{ xy[2 * f], xy[2 * f + 1], xy[2 * f] + ww, xy[2 * f + 1] + wh };
+    { const int rc = yk_dec_table_upload(c, slot, c->dBWinTab.p, (size_t)N * sizeof(DWinRect)); if (rc) return rc; }
+    c->dBWinW = ww; c->dBWinH = wh; c->dBWinSet = true;
+    return YK_OK;
+}
+static const DWinRect* yk_dec_bwin_tab(const yk_ctx* c) { return reinterpret_cast<const DWinRect*>(c->dBWinTab.p); }
+
 // PaletteFullRangeRemapping (decoder/YAIK_GenericFunctions.cpp:128-137) of a corner stream that is still in HBM: v * ((255 << 16) / range) >> 16
 static uint32_t yk_dec_remap_factor(int remapRange) { return remapRange > 0 ? (uint32_t)((255u << 16) / (uint32_t)remapRange) : 0u; }
 __global__ void yk_dec_remap_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t n, uint32_t factor) {
@@ -1679,6 +1765,7 @@ static int yk_decode_gradient_impl(yk_ctx* c, int sx, int sy, const uint8_t* bit
     if (!c || !bitmap) return YK_ERR_BAD_ARG;
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_DEC_NO_PREPARED(c, "yk_decode_gradient[_device]");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_gradient[_device]");
     const YkDecView V = yk_dec_frame(c);
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
     const size_t need = yk_dpass_bytes(sx, sy, w, h);
@@ -1721,6 +1808,7 @@ int yk_decode_gradient_all_device(yk_ctx* c, int nPasses, const int* tileShiftX,
     if (!c || nPasses < 0 || (nPasses && (!tileShiftX || !tileShiftY || !devBitmap || !bitmapBytes || !devRgb || !rgbBytes))) return YK_ERR_BAD_ARG;
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_DEC_NO_PREPARED(c, "yk_decode_gradient_all_device");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_gradient_all_device");
     const YkDecView V = yk_dec_frame(c);
     if (nPasses == 0) return YK_OK;
     const int w = c->dw, h = c->dh, latW = w / 4 + 1;
@@ -1797,6 +1885,7 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
         if (rgbBytes[i] > 0xFFFFFFFFu) return yk_refuse(c, YK_ERR_BAD_ARG, "colour stream of 4 GB or more");
     }
     YK_HIP(c, hipSetDevice(c->device));
+    if (c->dBatchBegun) c->dChunkSeen = true;                                 // from here on yk_decode_set_batch_windows refuses
     DecPlan pl = {};                                                          // what the frames share: the geometry
     yk_dplan_shape(pl, nPasses, tileShiftX, tileShiftY, need);
     const size_t nbTot = pl.blockStart[7], nBytesTot = pl.byteStart[7];
@@ -1828,8 +1917,12 @@ int yk_decode_gradient_all_batch_device(yk_ctx* c, int nPasses, const int* tileS
     hipLaunchKernelGGL(yk_decall_stream_batch_kernel<false>, dim3((unsigned)nbTot, F), dim3(1024), 0, c->stream, B, w, h, latW, 0u);
     hipLaunchKernelGGL(yk_decall_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, B);
     hipLaunchKernelGGL(yk_decall_stream_batch_kernel<true>, dim3((unsigned)nbTot, F), dim3(1024), 0, c->stream, B, w, h, latW, yk_dec_remap_factor(remapRange));
-    hipLaunchKernelGGL(yk_decall_render_blocks_batch_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64)), F), dim3(256), 0, c->stream, B, w, h, latW,
-                       c->dPlaneSize, w >> 3, (w + 15) >> 4);
+    if (c->dBWinSet)                                                          // the map-sized work above stays whole; the blocks outside a frame's window are marked, not rendered
+        hipLaunchKernelGGL(yk_decall_render_blocks_batch_win_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64)), F), dim3(256), 0, c->stream, B, yk_dec_bwin_tab(c),
+                           w, h, latW, c->dPlaneSize, w >> 3, (w + 15) >> 4);
+    else
+        hipLaunchKernelGGL(yk_decall_render_blocks_batch_kernel, dim3((unsigned)(((w + 63) / 64) * ((h + 63) / 64)), F), dim3(256), 0, c->stream, B, w, h, latW,
+                           c->dPlaneSize, w >> 3, (w + 15) >> 4);
     YK_HIP(c, hipGetLastError());
     { int rc2 = yk_stage_end(c, YK_STAGE_DEC_GRADIENT); if (rc2) return rc2; }
     return YK_OK;
@@ -1850,6 +1943,7 @@ int yk_decode_split_masks(yk_ctx* c) {
     YK_DEC_NO_BATCH(c, "yk_decode_split_masks");
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_DEC_NO_PREPARED(c, "yk_decode_split_masks");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_split_masks");
     YK_HIP(c, hipSetDevice(c->device));
     c->dChunkSeen = true;
     return yk_dec_split(c);
@@ -1859,6 +1953,7 @@ int yk_decode_gradient_planes(yk_ctx* c, int planeBit, int consistentMarks, cons
     if (!c || !bitmap) return YK_ERR_BAD_ARG;
     YK_DEC_NO_BATCH(c, "yk_decode_gradient_planes");
     YK_DEC_NO_PREPARED(c, "yk_decode_gradient_planes");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_gradient_planes");
     if (planeBit == 7) return yk_decode_gradient(c, 2, 2, bitmap, bitmapBytes, rgb, rgbBytes);
     if (planeBit < 1 || planeBit > 6) return yk_fail(c, YK_ERR_BAD_ARG, "planeBit must be 1..7");
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
@@ -1894,6 +1989,7 @@ static int yk_decode_1d_impl(yk_ctx* c, const uint8_t* typeStream, size_t typeBy
     if (!c || !typeStream || !pixStream || compressionRange <= 0) return YK_ERR_BAD_ARG;
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_DEC_NO_PREPARED(c, "yk_decode_1d[_device]");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_1d[_device]");
     const YkDecView V = yk_dec_frame(c);
     YK_HIP(c, hipSetDevice(c->device));
     c->dChunkSeen = true;
@@ -1974,6 +2070,7 @@ int yk_decode_1d_batch_device(yk_ctx* c, const uint8_t* const* devType, const si
     }
     if (c->dSplit) return yk_decode_1d_impl(c, devType[0], typeBytes[0], devPix[0], pixBytes[0], compressionRange, true);   // a batch of one behind a plane-subset chunk: per-plane masks
     YK_HIP(c, hipSetDevice(c->device));
+    if (c->dBatchBegun) c->dChunkSeen = true;
     const int w = c->dw, h = c->dh, tilesW = w >> 3;
     const size_t T8 = (size_t)tilesW * (h >> 3), nb = (T8 + 1023) / 1024;
     const size_t tabBytes = ((size_t)N * sizeof(D1Frame) + 255) & ~(size_t)255;
@@ -1993,7 +2090,13 @@ int yk_decode_1d_batch_device(yk_ctx* c, const uint8_t* const* devType, const si
     { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
     hipLaunchKernelGGL(yk_dec1d_count_batch_kernel, dim3((unsigned)nb, F), dim3(1024), 0, c->stream, B, (w + 15) >> 4, tilesW, T8);
     hipLaunchKernelGGL(yk_dec1d_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, B, (int)nb);
-    hipLaunchKernelGGL(yk_dec1d_batch_kernel, dim3(gTiles, 3, F), dim3(256), 0, c->stream, B, T8, (1 << 24) / compressionRange, c->dPlaneSize);
+    if (c->dBWinSet) {                                                        // count and scan stay whole for every frame; only the tiles of its window are decoded
+        const uint32_t wtW = (uint32_t)(c->dBWinW >> 3);
+        const size_t nWin = (size_t)wtW * (c->dBWinH >> 3);
+        hipLaunchKernelGGL(yk_dec1d_batch_win_kernel, dim3((unsigned)((nWin + 64 * YK_D1_TPL - 1) / (64 * YK_D1_TPL)), 3, F), dim3(256), 0, c->stream, B, yk_dec_bwin_tab(c), nWin,
+                           wtW, (uint32_t)tilesW, (1 << 24) / compressionRange, c->dPlaneSize);
+    } else
+        hipLaunchKernelGGL(yk_dec1d_batch_kernel, dim3(gTiles, 3, F), dim3(256), 0, c->stream, B, T8, (1 << 24) / compressionRange, c->dPlaneSize);
     YK_HIP(c, hipGetLastError());
     { int rc2 = yk_stage_end(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
     c->dPlanesStale = false;                                                 // every unmarked quadrant of every plane of every frame has been written
@@ -2101,6 +2204,7 @@ int yk_decode_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t 
 int yk_decode_output_window_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha) {
     if (!c) return YK_ERR_BAD_ARG;
     YK_DEC_NO_PREPARED(c, "yk_decode_output_window_device");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_output_window_device");
     return yk_dec_output_device(c, devOut, rowBytes, planeBytes, channels, alpha, c->dWinSet);
 }
 
@@ -2111,6 +2215,7 @@ int yk_decode_output_batch_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, s
     if (channels == 4 && (alpha < 0 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "alpha must be 0..255 (a batch has no decoded alpha plane)");
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
     YK_DEC_NO_PREPARED(c, "yk_decode_output_batch_device");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_output_batch_device");
     const size_t w = (size_t)c->dw, h = (size_t)c->dh;
     if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
         return yk_refuse(c, YK_ERR_BAD_ARG, "row or plane pitch too small for the image");
@@ -2126,6 +2231,7 @@ int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBy
     if (!c) return YK_ERR_BAD_ARG;
     if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "devOut is NULL");
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin_batch first");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_output_batch_alpha_device");
     if (!c->dAlphaValid || !c->dAlphaBatch) return yk_refuse(c, YK_ERR_STATE, "yk_decode_alpha_batch_device first: the batch has no decoded alpha planes");
     const size_t w = (size_t)c->dw, h = (size_t)c->dh;
     if (planeBytes == 0 ? rowBytes < w * 4 : (rowBytes < w || planeBytes / h < rowBytes))
@@ -2137,6 +2243,43 @@ int yk_decode_output_batch_alpha_device(yk_ctx* c, uint8_t* devOut, size_t rowBy
     return yk_dec_detile(c, devOut, rowBytes, planeBytes, 4, c->dAlpha, w, 0, c->dFrames, frameBytes, c->dAlphaStride);
 }
 
+// The window of every frame of a batch with windows (yk_decode_set_batch_windows): frame f's ww x wh pixels at devOut + f * frameBytes, one launch
+int yk_decode_output_batch_windows_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_batch_windows_device: devOut is NULL");
+    if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_batch_windows_device: channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_batch_windows_device: alpha must be -1 (the planes of yk_decode_alpha[_mask]_batch_device) or 0..255");
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_batch_windows_device: yk_decode_begin_batch first");
+    if (!c->dBWinSet) return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_batch_windows_device: no windows are set on this batch (yk_decode_set_batch_windows)");
+    const bool fromPlanes = channels == 4 && alpha < 0;
+    if (fromPlanes && (!c->dAlphaValid || !c->dAlphaBatch))
+        return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_batch_windows_device: alpha = -1 needs yk_decode_alpha_batch_device first: the batch has no decoded alpha planes");
+    const size_t w = (size_t)c->dBWinW, h = (size_t)c->dBWinH;
+    if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_batch_windows_device: row or plane pitch too small for the window");
+    if (c->dFrames > 1 && (planeBytes == 0 ? frameBytes / h < rowBytes : frameBytes / (size_t)channels < planeBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_batch_windows_device: frame stride too small for a window");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    YkDetileArgs a;
+    a.planes = c->dB.planes; a.planeSize = c->dPlaneSize;
+    a.alpha = fromPlanes ? (const uint8_t*)c->dAlpha : nullptr; a.strideA = (size_t)c->dw; a.alphaConst = (uint32_t)((fromPlanes ? 0 : alpha) & 255) * 0x01010101u;
+    a.out = devOut; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
+    a.tileW = (uint32_t)(c->dw >> 3); a.nTiles = (uint32_t)(w >> 3) * (uint32_t)(h >> 3);
+    const uint32_t wtW = (uint32_t)(w >> 3);
+    const size_t pf = c->dStride.planes, af = fromPlanes ? c->dAlphaStride : 0;
+    const DWinRect* wins = yk_dec_bwin_tab(c);
+    const bool planar = planeBytes > 0;
+    const int N = c->dFrames;
+    { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    if (channels == 3)   { if (planar) yk_dt_launch_batch_win<3, true, YK_DT_ALPHA_NONE>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); else yk_dt_launch_batch_win<3, false, YK_DT_ALPHA_NONE>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); }
+    else if (fromPlanes) { if (planar) yk_dt_launch_batch_win<4, true, YK_DT_ALPHA_PLANE>(a, c->stream, N, wins, wtW, pf, frameBytes, af); else yk_dt_launch_batch_win<4, false, YK_DT_ALPHA_PLANE>(a, c->stream, N, wins, wtW, pf, frameBytes, af); }
+    else                 { if (planar) yk_dt_launch_batch_win<4, true, YK_DT_ALPHA_CONST>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); else yk_dt_launch_batch_win<4, false, YK_DT_ALPHA_CONST>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); }
+    YK_HIP(c, hipGetLastError());
+    return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+}
+
 // ---- outputs at reduced resolution (include/yaik_hip.h): level 0 is the full-size call, 1..3 the box means of 2x2, 4x4, 8x8 ----------
 int yk_decode_output_scaled_device(yk_ctx* c, int level, uint8_t* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha) {
     if (!c) return YK_ERR_BAD_ARG;
@@ -2145,6 +2288,7 @@ int yk_decode_output_scaled_device(yk_ctx* c, int level, uint8_t* devOut, size_t
     if (c->dPrepared)
         return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_device: this image is prepared for windows (yk_decode_prepare_device); yk_decode_render_windows_scaled_device reads it");
     if (level == 0) return yk_decode_output_window_device(c, devOut, rowBytes, planeBytes, channels, alpha);
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_output_scaled_device");
     if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: devOut is NULL");
     if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: channels must be 3 or 4");
     if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: alpha must be -1 (the decoded plane) or 0..255");
@@ -2173,6 +2317,7 @@ int yk_decode_output_scaled_batch_device(yk_ctx* c, int level, uint8_t* devOut, 
     if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_batch_device: devOut is NULL");
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_batch_device: yk_decode_begin_batch first");
     YK_DEC_NO_PREPARED(c, "yk_decode_output_scaled_batch_device");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_output_scaled_batch_device");
     if (fromPlanes && (!c->dAlphaValid || !c->dAlphaBatch))
         return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_batch_device: alpha = -1 needs yk_decode_alpha_batch_device first: the batch has no decoded alpha planes");
     const size_t w = (size_t)c->dw >> level, h = (size_t)c->dh >> level;
@@ -2200,6 +2345,7 @@ static int yk_dec_mipchain(yk_ctx* c, const char* name, int firstLevel, int nLev
     if (!yk_dec_begun(c)) return refuse(YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
     if (c->dPrepared) return refuse(YK_ERR_STATE, "this image is prepared for windows (yk_decode_prepare_device) and windows have no chain");
     if (!batch && c->dWinSet) return refuse(YK_ERR_STATE, "a window is set on this decode (yk_decode_set_window) and windows have no chain");
+    if (c->dBWinSet) return refuse(YK_ERR_STATE, "windows are set on this batch (yk_decode_set_batch_windows) and windows have no chain");
     const int total = yk_decode_mip_levels(c->dw, c->dh);
     if (firstLevel < 0 || nLevels < 1 || nLevels > YK_MIP_MAX_LEVELS || firstLevel > total - nLevels)
         return refuse(YK_ERR_BAD_ARG, "firstLevel .. firstLevel + nLevels - 1 must lie inside the image's levels (yk_decode_mip_levels)");

@@ -1038,6 +1038,7 @@ int yk_decode_lut3d(yk_ctx* c, const uint8_t* const maps[6], const size_t mapByt
     YK_DEC_NO_BATCH(c, "yk_decode_lut3d");
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_DEC_NO_PREPARED(c, "yk_decode_lut3d");
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_lut3d");
     const YkDecView V = yk_dec_frame(c);
     if (!c->lutDec) return yk_fail(c, YK_ERR_STATE, "yk_decode_assign_lut first");
     if (c->dSplit) return yk_fail(c, YK_ERR_STATE, "a '3DTL' chunk comes before the masks are split ('1DTL', plane-subset chunks)");

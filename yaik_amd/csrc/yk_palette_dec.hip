@@ -454,6 +454,7 @@ int yk_decode_gradient_palette(yk_ctx* c, int sx, int sy, const uint8_t* bitmap,
     if (!bitmap || !bitmapBytes) return yk_refuse(c, YK_ERR_BAD_ARG, "NULL or empty tile bitmap");
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_begin first");
     YK_DEC_NO_PREPARED(c, "yk_decode_gradient_palette");                        // before the palette decode, not only in the pass behind it
+    YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_gradient_palette");
     if (colorCompression < 0 || colorCompression > 255) return yk_refuse(c, YK_ERR_BAD_ARG, "colorCompression must be 0..255");
     if (rgbBytes && !payload) return yk_refuse(c, YK_ERR_BAD_ARG, "a stream has an output length and an empty payload or a NULL pointer");
     YkPaletteDec& P = c->pdec;

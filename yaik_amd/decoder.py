@@ -139,6 +139,7 @@ class HipTileDecoder:
         self._batch_streams = None       # ... and the copy of an encoder's per-handle streams (encoder_batch_streams)
         self._alpha_stage = None         # ... and the staging tensor of decompress_alpha_batch's host payloads
         self._window = None              # set_window: (x0, y0, w, h) of the image begun, None = the whole image
+        self._batch_windows = None       # set_batch_windows: (origins [N, 2], w, h) of the batch begun, None = whole frames
 
     def close(self):
         if getattr(self, "_h", None):
@@ -152,6 +153,7 @@ class HipTileDecoder:
         self.w, self.h, self.frames = w, h, 1
         self._has_alpha = self._alpha_batch = False
         self._window = None                                                # yk_decode_begin always clears the window
+        self._batch_windows = None                                         # ... and the windows of a batch
         _chk(self._h, lib().yk_decode_begin(self._h, w, h))
 
     # ---- windows: decode only the tiles a rectangle of the image needs (yk_decode_set_window) -----------------------------------
@@ -270,9 +272,83 @@ class HipTileDecoder:
         self.w, self.h, self.frames = w, h, n
         self._has_alpha = self._alpha_batch = False
         self._window = None
+        self._batch_windows = None                                         # yk_decode_begin_batch always clears the windows
 
     def select_frame(self, f: int):
         _chk(self._h, lib().yk_decode_select_frame(self._h, f))
+
+    # ---- a window of every frame of a batch: one size, one origin per frame (yk_decode_set_batch_windows) -----------------------
+    @property
+    def batch_windows(self):
+        """(origins int32 [N, 2], w, h) of the windows set on the batch begun, None when the frames are decoded whole (always after begin_batch)."""
+        if self._batch_windows is None:
+            return None
+        o, w, h = self._batch_windows
+        return o.copy(), w, h
+
+    def set_batch_windows(self, origins, w: int, h: int) -> None:
+        """From here on the batch decode calls owe frame f only the pixels of the rectangle (origins[f][0], origins[f][1], w, h): the gradient
+        render skips the 64x64 blocks of a frame its window does not touch and the 1-D chunk decodes the window's tiles only.  `origins` is an
+        [N, 2] integer array or a sequence of N (x0, y0) pairs, N = the frames of the batch.  Call it right after begin_batch(), before any
+        chunk is decoded; everything is a multiple of 8 with w, h >= 8 and every rectangle inside the image; w = h = 0 clears the windows.  Read
+        the result with image_batch_windows_device(); image_batch_device() and the other whole-frame outputs raise the library's state error
+        while windows are set, planes() of a selected frame is exact inside its window only, tile4x4() is whole and exact.  Bad arguments raise
+        before any library call; a handle begun with begin(), or chunks decoded already, are the library's to refuse."""
+        if isinstance(w, bool) or isinstance(h, bool) or not isinstance(w, (int, np.integer)) or not isinstance(h, (int, np.integer)):
+            raise TypeError(f"the window size must be two ints; got {w!r}, {h!r}")
+        if int(w) == 0 and int(h) == 0:
+            _chk(self._h, lib().yk_decode_set_batch_windows(self._h, None, 0, 0))
+            self._batch_windows = None
+            return
+        if isinstance(origins, np.ndarray):
+            if origins.ndim != 2 or origins.shape[1] != 2 or not np.issubdtype(origins.dtype, np.integer):
+                raise TypeError(f"window origins must be an integer array [N, 2]; got {origins.dtype} {origins.shape}")
+            origins = [(int(x), int(y)) for x, y in origins]
+        flat = self._check_windows(origins, w, h)
+        if len(flat) != 2 * self.frames:
+            raise ValueError(f"{len(flat) // 2} window origins for a batch of {self.frames} frames")
+        xy = (C.c_int * len(flat))(*flat)
+        self._batch_windows = None
+        _chk(self._h, lib().yk_decode_set_batch_windows(self._h, xy, int(w), int(h)))
+        self._batch_windows = (np.asarray(flat, dtype=np.int32).reshape(-1, 2), int(w), int(h))
+
+    def image_batch_windows_device(self, out=None, channels: int = 3, alpha: int = 255, planar: bool = False, alpha_from_planes: bool = False):
+        """The window of every frame of the batch as 8-bit pixels in one torch.uint8 tensor on the handle's device
+        (yk_decode_output_batch_windows_device, one launch): [N, h, w, C], or [N, C, h, w] with planar=True, of the windows' size; frame f equals
+        image_batch_device()[f] of the whole decode cut to its window.  channels, alpha, alpha_from_planes (each frame's decoded 'ALPM' plane,
+        read at its window's offset) and `out` follow image_batch_device; ordering against torch's current stream is the same: no host fence."""
+        import torch
+        if self._batch_windows is None:
+            raise ValueError("no windows are set on this batch: set_batch_windows() first")
+        if channels not in (3, 4):
+            raise ValueError("channels must be 3 or 4")
+        if alpha_from_planes and channels != 4:
+            raise ValueError("alpha_from_planes needs channels=4")
+        if not alpha_from_planes and not 0 <= int(alpha) <= 255:
+            raise ValueError(f"alpha must be 0..255; got {alpha!r}")
+        _, ww, wh = self._batch_windows
+        dev = torch.device("cuda", self.device)
+        N = self.frames
+        if out is None:
+            out = torch.empty((N, channels, wh, ww) if planar else (N, wh, ww, channels), dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        if planar:
+            lay = u8_planar_batch_layout(out)
+            shape, plane_bytes = (lay.frames, lay.channels, lay.rows, lay.w), lay.plane_bytes
+        else:
+            lay = u8_pixel_layout(out, batch=True)
+            shape, plane_bytes = (lay.frames, lay.rows, lay.w, lay.channels), 0
+        want = (N, channels, wh, ww) if planar else (N, wh, ww, channels)
+        if shape != want:
+            raise ValueError(f"out has shape {shape}, the windows need {want}")
+        L = lib()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_output_batch_windows_device(self._h, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels,
+                                                               -1 if alpha_from_planes else int(alpha)))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
 
     def decode_batch_streams(self, frames: list, sync: bool = True, remap_range: int = 250) -> None:
         """The gradient chunks + the 1-D chunk of every frame of the batch, one launch per kernel over all frames.  frames[f] is the call list
@@ -397,8 +473,9 @@ class HipTileDecoder:
         return frames
 
     def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False, per_frame: bool = False, palette: bool = False,
-                                  alpha_6bit: bool = False) -> None:
-        """decode_batch_streams of encoder_batch_streams(enc, per_frame); alpha=True also runs the encoder's alpha_values_batch and decodes every
+                                  alpha_6bit: bool = False, windows=None) -> None:
+        """decode_batch_streams of encoder_batch_streams(enc, per_frame); windows=(origins, w, h) first gives every frame its window
+        (set_batch_windows, checked before anything else happens), so that the batch begun just before decodes those rectangles only; alpha=True also runs the encoder's alpha_values_batch and decodes every
         frame's 'ALPM' payload where the encoder left it in HBM (decompress_alpha_batch; frames without a chunk are opaque).  With sync=False on
         the default path the queued decode reads the encoder's own stream buffer: fence this decoder before the encoder's next encode.
         alpha_6bit=True (with alpha): the alpha goes through the encoder's alpha_bitmaps_device + alpha_mask_payloads_device and
@@ -409,6 +486,10 @@ class HipTileDecoder:
         (palette_decompress_streams, remap_range 250) and the gradient decode reads those outputs with remap off.  Only for streams that
         round-trip through the 'GTIL' coder: a payload PaletteDecompressor rejects raises YaikError (DESIGN §18 on payloads that decode to
         other bytes than their stream).  Without payloads of this batch on the encoder the call raises ValueError."""
+        if windows is not None:
+            if not isinstance(windows, (tuple, list)) or len(windows) != 3:
+                raise TypeError(f"windows must be (origins, w, h); got {windows!r}")
+            self.set_batch_windows(*windows)
         if palette:
             if per_frame:
                 raise ValueError("palette=True needs the encoder's stream table (per_frame=False)")

@@ -6,6 +6,8 @@ decode_file_windows_device(stream, origins, w, h)   K windows of one size throug
                               once, every 64x64 block the windows touch rendered once; uint8 [K, h, w, C]
 decode_files_device(streams)  n streams of one shape through YAIK_DecodeImagesToDevice: ZStd on host workers, one upload, every kernel once over
                               the batch; uint8 [N, H, W, C] or [N, C, H, W]
+decode_files_windows_device(streams, origins, size)   one window of each of them through YAIK_DecodeImagesWindowsToDevice: the same batch with
+                              the pixel-sized work of a frame only inside its window; uint8 [N, h, w, C] or [N, C, h, w]
 encode_files_device(frames)   the other direction (yaik_encode.h, YAIK_EncodeImagesFromDevice): uint8 [N, H, W, C] frames in device memory to N
                               streams, every kernel once over the batch, one gather and one download, ZStd and framing on host workers
 encode_file_device(frame)     a batch of one
@@ -89,6 +91,10 @@ MULTIWINDOW_SIGNATURES = {
     "YAIK_DecodeImageWindowsToDevice": (C.c_bool, [vp, u32, vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t]),
     "YAIK_LastWindowsPrepared": (C.c_int, []),
 }
+# yaik_decode_batch_windows.h: the same library, C linkage
+BATCH_WINDOWS_SIGNATURES = {
+    "YAIK_DecodeImagesWindowsToDevice": (C.c_bool, [vp, vp, vp, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int]),
+}
 # yaik_decode_scaled.h: the same library, C linkage
 SCALED_SIGNATURES = {
     "YAIK_DecodeImageScaledToDevice": (C.c_bool, [vp, u32, vp, C.c_int]),
@@ -133,7 +139,7 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
-        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **SCALED_SIGNATURES, **MIPCHAIN_SIGNATURES}.items():
+        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **BATCH_WINDOWS_SIGNATURES, **SCALED_SIGNATURES, **MIPCHAIN_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _host = L
@@ -404,8 +410,57 @@ def decode_files_device(streams, out=None, channels: int = 3, planar: bool = Fal
     return out
 
 
+def decode_files_windows_device(streams, origins, size, out=None, channels: int = 3, planar: bool = False, threads: int = 16):
+    """One window of each of n (1..1024) streams of ONE width x height (YAIK_DecodeImagesWindowsToDevice): origins[f] = (x0, y0) of stream f's
+    window, size = (w, h) of every window; a torch.uint8 tensor [N, h, w, C], or [N, C, h, w] with planar=True, on the GPU, frame f equal to
+    decode_files_device(streams)[f] cut to its window.  channels, `out` and threads follow decode_files_device, with the windows' size as the
+    frame size.  A wrong number of origins, an origin or size that is no multiple of 8 and a wrong `out` raise before any library call; a window
+    outside the image is the library's to refuse (YaikFileError, YAIK_DECIMG_INVALIDCTX; nothing is written)."""
+    import torch
+
+    from .encoder import u8_pixel_layout, u8_planar_batch_layout
+    streams = list(streams)
+    n = len(streams)
+    if not 1 <= n <= 1024:
+        raise ValueError("1..1024 streams are needed")
+    if channels not in (3, 4) or not 1 <= int(threads) <= 16:
+        raise ValueError("channels must be 3 or 4 and threads 1..16")
+    if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != 2:
+        raise TypeError(f"size must be (w, h); got {size!r}")
+    if isinstance(origins, np.ndarray):
+        origins = origins.tolist() if origins.ndim == 2 and np.issubdtype(origins.dtype, np.integer) else origins
+    flat, ww, wh = window_origins(origins, size[0], size[1])
+    if len(flat) != 2 * n:
+        raise ValueError(f"{len(flat) // 2} window origins for {n} streams")
+    L, h = host_lib(), library()
+    bufs = [_buffer(s) for s in streams]
+    dev = torch.device("cuda", _device)
+    if out is None:
+        out = torch.empty((n, channels, wh, ww) if planar else (n, wh, ww, channels), dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.device != dev:
+        raise ValueError(f"out must be a torch tensor on {dev}")
+    if planar:
+        lay = u8_planar_batch_layout(out)
+        plane_bytes = lay.plane_bytes
+    else:
+        lay = u8_pixel_layout(out, batch=True)
+        plane_bytes = 0
+    if (lay.frames, lay.channels, lay.rows, lay.w) != (n, channels, wh, ww):      # the library writes wh x ww pixels per frame: never into a smaller view
+        raise ValueError(f"out holds {lay.frames} frames of {lay.w} x {lay.rows} x {lay.channels}, the call needs {n} of {ww} x {wh} x {channels}")
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_uint32 * n)(*[b.size for b in bufs])
+    xy = (C.c_int * (2 * n))(*flat)
+    failed = C.c_int32(-1)
+    torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
+    ok = L.YAIK_DecodeImagesWindowsToDevice(h, ptrs, lens, n, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels, int(threads),
+                                            C.byref(failed), xy, ww, wh)
+    if not ok:
+        raise YaikFileError(L.YAIK_GetErrorCode(), max(failed.value, 0))
+    return out
+
+
 def last_batch_info() -> dict:
-    """Of the last decode_files_device: how many streams took the single-image chain, and the host clocks of its stages in ms."""
+    """Of the last decode_files_device or decode_files_windows_device: how many streams took the single-image chain, and the host clocks of its stages in ms."""
     L = host_lib()
     ms = (C.c_double * 3)()
     L.YAIK_LastBatchStageMs(ms)

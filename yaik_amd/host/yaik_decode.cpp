@@ -5,6 +5,7 @@
 #include "yaik_decode.h"
 #include "yaik_decode_window.h"
 #include "yaik_decode_multiwindow.h"
+#include "yaik_decode_batch_windows.h"
 #include "yaik_decode_scaled.h"
 #include "yaik_decode_mipchain.h"
 #include <atomic>
@@ -371,8 +372,11 @@ double nowMs() { return std::chrono::duration<double, std::milli>(std::chrono::s
 int  YAIK_LastBatchFallbacks() { return gBatchFallbacks; }
 void YAIK_LastBatchStageMs(double out[3]) { if (out) for (int i = 0; i < 3; i++) out[i] = gBatchMs[i]; }
 
-bool YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
-                               size_t frameBytes, int channels, int threads, int32_t* failedIndex) {
+// YAIK_DecodeImagesToDevice and, with xy (one origin per stream) and the window size ww x wh, YAIK_DecodeImagesWindowsToDevice: the same plan,
+// expansion, upload and batch calls; with windows the batch is given them right after yk_decode_begin_batch, the output is the windows' and a
+// fallback stream takes the single-image window chain
+static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
+                         size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh) {
     using namespace yaikplan;
     if (failedIndex) *failedIndex = -1;
     if (!lib || lib != gLib) { setError(YAIK_INVALID_LIBRARYCTX); return false; }
@@ -385,6 +389,11 @@ bool YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_
         const int rc = readHeader(streams[f], lengths[f], &fw, &fh, nullptr);
         if (rc == 0 && f == 0) { w = fw; h = fh; }
         if (rc != 0 || fw != w || fh != h) { setError(rc == 1 ? YAIK_INVALID_STREAM : YAIK_INVALID_HEADER); if (failedIndex) *failedIndex = f; return false; }
+    }
+    if (xy) {                                                                   // the rule of yk_decode_set_window for every stream, before a slot is taken or a byte written
+        bool ok = !((ww | wh) & 7) && ww >= 8 && wh >= 8 && ww <= w && wh <= h;
+        for (int f = 0; ok && f < n; f++) ok = !((xy[2 * f] | xy[2 * f + 1]) & 7) && xy[2 * f] >= 0 && xy[2 * f + 1] >= 0 && xy[2 * f] <= w - ww && xy[2 * f + 1] <= h - wh;
+        if (!ok) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
     }
     Slot* s = nullptr;
     { std::lock_guard<std::mutex> g(gLib->lock); if (!gLib->freeStack.empty()) { s = gLib->freeStack.back(); gLib->freeStack.pop_back(); } }
@@ -479,6 +488,7 @@ bool YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_
         const double t2 = nowMs();
         // ---- decode: every kernel once over the n frames; a fallback stream is an empty frame here
         if (yk_decode_begin_batch(s->ctx, w, h, n) != YK_OK) { setError(YAIK_MALLOC_FAIL); break; }
+        if (xy && yk_decode_set_batch_windows(s->ctx, xy, ww, wh) != YK_OK) { setError(YAIK_DECIMG_INVALIDCTX); break; }
         const size_t NP = (size_t)n * NUM_PASSES;
         std::vector<const uint8_t*> bm(NP), rgb(NP, nullptr);
         std::vector<size_t> rgbBytes(NP, 0);
@@ -535,7 +545,9 @@ bool YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_
                 yk_decode_alpha_batch_status(s->ctx, st.data()) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
             for (int f = 0; f < n; f++) if (st[(size_t)f]) fallback[(size_t)f] = 1;       // a payload shorter than the mask selects: the single chain reports it
         }
-        if (anyAlpha && channels == 4) {
+        if (xy) {
+            if (yk_decode_output_batch_windows_device(s->ctx, devOut, rowBytes, planeBytes, frameBytes, channels, anyAlpha && channels == 4 ? -1 : 255) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+        } else if (anyAlpha && channels == 4) {
             if (yk_decode_output_batch_alpha_device(s->ctx, devOut, rowBytes, planeBytes, frameBytes) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
         } else if (yk_decode_output_batch_device(s->ctx, devOut, rowBytes, planeBytes, frameBytes, channels, 255) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
         if (yk_synchronize(s->ctx) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
@@ -547,10 +559,13 @@ bool YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_
             if (!fallback[(size_t)f]) continue;
             gBatchFallbacks++;
             bool hasAlphaPlane = false;
-            res = decodeChunks(s, streams[f], lengths[f], hasAlphaPlane);
+            const int window[4] = { xy ? xy[2 * f] : 0, xy ? xy[2 * f + 1] : 0, ww, wh };
+            res = decodeChunks(s, streams[f], lengths[f], hasAlphaPlane, xy ? window : nullptr);
             if (res) {
                 const bool plane = hasAlphaPlane && channels == 4;
-                res = yk_decode_output_device(s->ctx, devOut + (size_t)f * frameBytes, rowBytes, planeBytes, channels, plane ? -1 : 255) == YK_OK && yk_synchronize(s->ctx) == YK_OK;
+                uint8_t* const dst = devOut + (size_t)f * frameBytes;
+                res = (xy ? yk_decode_output_window_device(s->ctx, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)
+                          : yk_decode_output_device(s->ctx, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)) == YK_OK && yk_synchronize(s->ctx) == YK_OK;
                 if (!res) setError(YAIK_INVALID_STREAM);
             }
             if (!res) failed = f;
@@ -559,6 +574,17 @@ bool YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_
     { std::lock_guard<std::mutex> g(gLib->lock); gLib->freeStack.push_back(s); }
     if (failedIndex) *failedIndex = failed;
     return res;
+}
+
+bool YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
+                               size_t frameBytes, int channels, int threads, int32_t* failedIndex) {
+    return decodeImages(lib, streams, lengths, n, devOut, rowBytes, planeBytes, frameBytes, channels, threads, failedIndex, nullptr, 0, 0);
+}
+// yaik_decode_batch_windows.h
+extern "C" bool YAIK_DecodeImagesWindowsToDevice(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
+                                                 size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh) {
+    if (!xy) { if (failedIndex) *failedIndex = -1; setError(YAIK_DECIMG_INVALIDCTX); return false; }
+    return decodeImages(lib, streams, lengths, n, devOut, rowBytes, planeBytes, frameBytes, channels, threads, failedIndex, xy, ww, wh);
 }
 
 // ---- YAIK_DecodeImageWindowsToDevice: many windows of one stream (yaik_decode_multiwindow.h) ------------------------------------------------
