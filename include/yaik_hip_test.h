@@ -23,8 +23,9 @@ int yk_selftest(yk_ctx* c, int which, int* result);
 /* TIMING ONLY: ablation switches for profiling the fused kernel (results are WRONG while non-zero; default 0).
  * 1 = skip the range quantiser, 2 = skip the gradient passes, 4 = skip the nearest-entry lookups (table gathers; LUT search in
  * the first-generation kernel), 8 = skip the error sums (first-generation kernel).
- * One flag only selects a code path and leaves the results exact (used by the parity tests): 16 = re-sum every tile in the
- * reference's sequential order. */
+ * Two flags only select a code path and leave the results exact (used by the parity tests): 16 = re-sum every tile in the
+ * reference's sequential order; 32 = launch the general instantiation of the fused kernel on a frame that qualifies for the
+ * whole-block one (one whole image, sides multiples of 64: yk_launch_encode2), so that both can be compared in one library. */
 int yk_set_ablation(yk_ctx* c, int flags);
 /* which implementation of the fused kernel yk_encode_tiles launches: 2 (default) = the library's kernel (lane per 4x4 cell); 1 = an
  * external cross-check implementation registered with yk_set_cross_check_launcher (the test suite's first-generation kernel,

@@ -685,7 +685,13 @@ __device__ __forceinline__ uint32_t y2_pack3(int r, int g, int b) {
 // WANT_DST: the test-only reconstruction of the coded pixels into P.dst (yk_range_dst).  It is a separate instantiation because its extra
 // live state costs the product kernel spilled VGPRs, and with them a scratch allocation per wave launch.
 // MODE3: DynamicTileEncode's mode3BitOnly (modes 3..5 only).
-template <bool WANT_DST, bool MODE3>
+// WHOLE: one whole image whose sides are multiples of 64 (no batch, no stripe, no halo rows: yk_launch_encode2 selects it).  What every strip pays
+// for the cases such a frame never has is gone: the frame division and the frame strides, the clamps of the pixel loads (three survive: the halo
+// column of the last block column, the halo row of the last strip row and the halo column's row 16 there), the right-edge patch, the inside-the-
+// image tests and the output table's limits.  A strip that lies wholly inside the constraint box decides on the scalar unit which lanes are
+// live and which have something to code, before any per-lane value of the range phase exists; one with nothing to code stores its zero run
+// sums and tile records and ends.  The general instantiations are the code as it was.
+template <bool WANT_DST, bool MODE3, bool WHOLE = false>
 __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams P) {
     // One wave64 per workgroup: a work unit is a 64x16 strip (four macro-tiles) of a 64x64 swizzle block, so nothing in the
     // kernel waits on another wave.  The staged pixels are only read by the gradient passes (afterwards every lane holds its
@@ -732,7 +738,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     typedef const __attribute__((address_space(4))) YkEncodeParams* Y2ParamPtr;
     auto strip = [&](const int slot, const int xcd, const int lane, Y2ParamPtr const Pp) {
     const __attribute__((address_space(4))) YkEncodeParams& P = *Pp;
-    const int nBf = P.xBB64 * P.yBB64, nB = nBf * P.nFrames;             // blocks per frame / of the whole batch
+    const int nBf = P.xBB64 * P.yBB64, nB = WHOLE ? nBf : nBf * P.nFrames;   // blocks per frame / of the whole batch
     // XCD-aware unit order: consecutive workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2).  Units are
     // taken in row-major runs of YK2_RUN blocks (4 strips each); XCD k gets a rotating run of every group of 8 runs, so the
     // halo column of a block and the halo row of a strip are lines a neighbour streams through the same L2 at about the same
@@ -748,7 +754,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     // batch: per-image pointers of this block's frame (wave-uniform scalars; the kernel argument itself is never copied).  The two divisions
     // of the unit decode are a multiplication and a shift each, exact for every block index a launch produces (yk_udiv.h; a single image has
     // nBf = nB: frame 0 comes out by itself); only what the pixel loads need is derived in front of them.
-    const uint32_t frU = yk_udiv((uint32_t)L, P.divNBf.mul, P.divNBf.shift);
+    const uint32_t frU = WHOLE ? 0u : yk_udiv((uint32_t)L, P.divNBf.mul, P.divNBf.shift);   // WHOLE: frame 0, every `fr *` term below is 0
     L -= (int)frU * nBf;
     const size_t fr = frU;
     const int32_t* const pl0 = P.plane[0] + fr * P.fs.plane; const int32_t* const pl1 = P.plane[1] + fr * P.fs.plane; const int32_t* const pl2 = P.plane[2] + fr * P.fs.plane;
@@ -769,15 +775,49 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     {
         const int g4 = (lane & 15) * 4, r0 = lane >> 4;
         const int gx = BX * 64 + g4;
-        const bool inX = gx + 3 < w;                                         // w is a multiple of 8: otherwise gx >= w
-        const int gxc = min(gx, w - 4);
+        const bool inX = WHOLE || gx + 3 < w;                                // w is a multiple of 8: otherwise gx >= w
+        const int gxc = WHOLE ? gx : min(gx, w - 4);
         const int gyS = BY * 64 + wave * 16;
+        int4 R[4], G[4], B[4], Rb, Gb, Bb;
+        uint32_t hcol;
+        int hr;                                                              // the lane's row of the right halo column
+        if constexpr (WHOLE) {
+            // every row and column of the strip itself is inside the image: the scalar base is the strip's first pixel, the lane's offset
+            // (r0 * stride + g4) * 4 once, the row groups a multiple of the stride further on
+            const int stride = P.strideElems;
+            const size_t base = (size_t)gyS * (size_t)stride + (size_t)(BX * 64);
+            const char* const b0 = reinterpret_cast<const char*>(pl0 + base);
+            const char* const b1 = reinterpret_cast<const char*>(pl1 + base);
+            const char* const b2 = reinterpret_cast<const char*>(pl2 + base);
+            const uint32_t offL = (uint32_t)(r0 * stride + g4) * 4u;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t off = offL + (uint32_t)(k * 16 * stride);
+                R[k] = *reinterpret_cast<const int4*>(b0 + off);
+                G[k] = *reinterpret_cast<const int4*>(b1 + off);
+                B[k] = *reinterpret_cast<const int4*>(b2 + off);
+            }
+            // bottom halo row, clamped on the scalar unit: row 16 of the strip, or 15 in the image's last strip row
+            const int relB = min(gyS + 16, h - 1) - gyS;
+            {
+                const uint32_t off = (uint32_t)(relB * stride) * 4u + (uint32_t)g4 * 4u;
+                Rb = *reinterpret_cast<const int4*>(b0 + off);
+                Gb = *reinterpret_cast<const int4*>(b1 + off);
+                Bb = *reinterpret_cast<const int4*>(b2 + off);
+            }
+            // right halo column: its row 16 takes the halo row's clamp, its column the scalar clamp of the last block column
+            hr = min(max(lane - 32, 0), 16);
+            {
+                const int colH = min(BX * 64 + 64, w - 1) - BX * 64;
+                const uint32_t off = (uint32_t)(min(hr, relB) * stride + colH) * 4u;
+                hcol = y2_pack3(*reinterpret_cast<const int32_t*>(b0 + off), *reinterpret_cast<const int32_t*>(b1 + off), *reinterpret_cast<const int32_t*>(b2 + off));
+            }
+        } else {
         const int gyB = min(gyS, P.hAvail - 1);                              // wave-uniform
         const size_t rowBase = (size_t)gyB * (size_t)P.strideElems;
         const char* const b0 = reinterpret_cast<const char*>(pl0 + rowBase);
         const char* const b1 = reinterpret_cast<const char*>(pl1 + rowBase);
         const char* const b2 = reinterpret_cast<const char*>(pl2 + rowBase);
-        int4 R[4], G[4], B[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int rel = min(gyS + r0 + 4 * k, P.hAvail - 1) - gyB;
@@ -787,7 +827,6 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
             B[k] = *reinterpret_cast<const int4*>(b2 + off);
         }
         // bottom halo row: the 16 segments are loaded by lanes 0..15 (the other lanes repeat them: same lines, coalesced)
-        int4 Rb, Gb, Bb;
         {
             const int rel = min(gyS + 16, P.hAvail - 1) - gyB;
             const uint32_t off = (uint32_t)(rel * P.strideElems + gxc) * 4u;
@@ -796,12 +835,12 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
             Bb = *reinterpret_cast<const int4*>(b2 + off);
         }
         // right halo column: 17 samples, lanes 32..48 (the other lanes repeat the first / last one)
-        uint32_t hcol;
-        const int hr = min(max(lane - 32, 0), 16);
+        hr = min(max(lane - 32, 0), 16);
         {
             const int rel = min(gyS + hr, P.hAvail - 1) - gyB;
             const uint32_t off = (uint32_t)(rel * P.strideElems + min(BX * 64 + 64, w - 1)) * 4u;
             hcol = y2_pack3(*reinterpret_cast<const int32_t*>(b0 + off), *reinterpret_cast<const int32_t*>(b1 + off), *reinterpret_cast<const int32_t*>(b2 + off));
+        }
         }
         // the reciprocals of the range phase's error terms ride along (every strip pays one load and one LDS store; a coded strip used to
         // compute its 256 quotients itself, four correctly rounded divisions per lane)
@@ -815,7 +854,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
         // The two loads are written out, because the compiler moves a scalar load to the block of its first use, behind the wait for the pixels;
         // it then knows nothing of them, so the wait stands at the fence behind the staging.
         {
-            const bool rowIn = BY * 64 + wave * 16 < h;
+            const bool rowIn = WHOLE || BY * 64 + wave * 16 < h;
             const uintptr_t args = reinterpret_cast<uintptr_t>(Pp);
             const uintptr_t kpIn = reinterpret_cast<uintptr_t>(P.keep) + fr * P.fs.keep + (uintptr_t)(mt0 & ~3);
             const uintptr_t bpIn = reinterpret_cast<uintptr_t>(P.bounds) + fr * 64;
@@ -829,7 +868,8 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
             const uint32_t frT = frU + P.outFrame0;
             const uint32_t o = ta.x + frT * ta.y + (uint32_t)BX * ta.z + (uint32_t)BY * ta.w;
             // parked in LDS over the gradient passes (s_park): the lane's offset, or none, and how it picks its value
-            s_park[lane] = ((uint32_t)BX < tb.x && (uint32_t)BY < tb.y) ? o : YK2_OT_NONE;
+            // (WHOLE: every row a lane stores from holds the whole image, and the lanes of the empty rows never store)
+            s_park[lane] = (WHOLE || ((uint32_t)BX < tb.x && (uint32_t)BY < tb.y)) ? o : YK2_OT_NONE;
             s_park[64 + lane] = tb.z;
         }
         uint4 o[4], ob;
@@ -840,7 +880,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
         }
         ob = make_uint4(y2_pack3(Rb.x, Gb.x, Bb.x), y2_pack3(Rb.y, Gb.y, Bb.y), y2_pack3(Rb.z, Gb.z, Bb.z), y2_pack3(Rb.w, Gb.w, Bb.w));
         if (lane < 16) *reinterpret_cast<uint4*>(&s_pix[16 * LS + g4]) = ob;
-        if (BX * 64 + 64 > w) {                                              // wave-uniform, rare: lanes beyond the right edge replicate column w - 1 (their loads were clamped to columns w-4 .. w-1)
+        if (!WHOLE && BX * 64 + 64 > w) {                                    // wave-uniform, rare: lanes beyond the right edge replicate column w - 1 (their loads were clamped to columns w-4 .. w-1)
             if (!inX) {
 #pragma unroll
                 for (int k = 0; k < 4; k++) *reinterpret_cast<uint4*>(&s_pix[(r0 + 4 * k) * LS + g4]) = make_uint4(o[k].w, o[k].w, o[k].w, o[k].w);
@@ -861,7 +901,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     const int gxCell = BX * 64 + bxCell, gyCell = BY * 64 + byCell;          // stripe-local pixels
     const int lcell = (cy * 4) * LS + bxCell;                                // strip-local LDS word of the cell origin
     const int lat = cy * 17 + q * 4 + cx;                                    // lattice index of the cell origin
-    const bool mtIn = (BX * 64 + q * 16 < w) && (BY * 64 + wave * 16 < h);    // macro-tile origin inside the image
+    const bool mtIn = WHOLE || ((BX * 64 + q * 16 < w) && (BY * 64 + wave * 16 < h));   // macro-tile origin inside the image
 
     uint32_t pw[16];
 #pragma unroll
@@ -869,6 +909,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
         const uint4 t = *reinterpret_cast<const uint4*>(&s_pix[lcell + r * LS]);
         pw[r * 4 + 0] = t.x; pw[r * 4 + 1] = t.y; pw[r * 4 + 2] = t.z; pw[r * 4 + 3] = t.w;
     }
+    bool ranPasses = false;                                                  // WHOLE: the gradient passes ran, pw[] is spent (wave-uniform)
 
     // ---- a6: seven passes --------------------------------------------------------------------------------------
     unsigned long long cov = 0ULL;                                           // bit = lane = 4x4 cell covered
@@ -891,7 +932,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
         }
         const unsigned long long deadLanes = __ballot(dead);
         YK2_STAT(75, 1); YK2_STAT(76, ~deadLanes == 0ULL ? 1 : 0); YK2_STAT(77, __popcll(deadLanes));
-        const bool stripInside = (BX * 64 + 64 <= w) && (BY * 64 + wave * 16 + 16 <= h);     // no tile of the strip crosses the image's edge
+        const bool stripInside = WHOLE || ((BX * 64 + 64 <= w) && (BY * 64 + wave * 16 + 16 <= h));   // no tile of the strip crosses the image's edge
         if (~deadLanes != 0ULL && !YK2_ABLATE(2)) {
             // corner lattice (every 4th pixel, 17 x 5 points incl. the halo): Round6 / Round6P of the three channels at once (SWAR)
             // and the five packed streams of y2_grad_pass
@@ -931,11 +972,15 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
                 y2_grad_pass<2, 3>(S, cov, evaluated);
                 y2_grad_pass<2, 2>(S, cov, evaluated);
             }
-            // the packed pixels come back from the staged strip (intact until the fence below)
+            // the packed pixels come back from the staged strip (intact until the fence below; WHOLE: until the range phase parks its first index
+            // word, and only a strip with something to code fetches them, there)
+            if constexpr (WHOLE) ranPasses = true;
+            else {
 #pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const uint4 t = *reinterpret_cast<const uint4*>(&s_pix[lcell + r * LS]);
-                pw[r * 4 + 0] = t.x; pw[r * 4 + 1] = t.y; pw[r * 4 + 2] = t.z; pw[r * 4 + 3] = t.w;
+                for (int r = 0; r < 4; r++) {
+                    const uint4 t = *reinterpret_cast<const uint4*>(&s_pix[lcell + r * LS]);
+                    pw[r * 4 + 0] = t.x; pw[r * 4 + 1] = t.y; pw[r * 4 + 2] = t.z; pw[r * 4 + 3] = t.w;
+                }
             }
         }
     }
@@ -968,47 +1013,76 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
         if (off16 != ~0u) *reinterpret_cast<uint16_t*>(small + off16) = (uint16_t)val16;
         // optional: the packed pixels of the cells nothing covered, for the live 1-D path (yk_set_pixel_cache): [strip][cell row][lane] 16-byte pieces
         if (P.pixCache != nullptr) {
-            const bool cellIn = (gxCell < w) && (gyCell < h);
+            const bool cellIn = WHOLE || ((gxCell < w) && (gyCell < h));
             if (cellIn && !((cov >> lane) & 1ULL)) {
                 const uint32_t strip = (uint32_t)((BY * 4 + wave) * P.xBB64 + BX);
                 uint4* dstp = P.pixCache + (size_t)strip * 256 + lane;
 #pragma unroll
-                for (int r = 0; r < 4; r++) dstp[r * 64] = make_uint4(pw[r * 4 + 0], pw[r * 4 + 1], pw[r * 4 + 2], pw[r * 4 + 3]);
+                for (int r = 0; r < 4; r++)                                  // WHOLE: pw[] is not back yet, the staged strip is still whole
+                    dstp[r * 64] = WHOLE ? *reinterpret_cast<const uint4*>(&s_pix[lcell + r * LS]) : make_uint4(pw[r * 4 + 0], pw[r * 4 + 1], pw[r * 4 + 2], pw[r * 4 + 3]);
             }
         }
         // 32-bit words: lane 8 = 8x4 (64x32 swizzle blocks, tile rows 4w..4w+3), lanes 9, 10 = 4x4 (32x32 swizzle blocks); lanes 11, 12 = the run sums
     }
     YK2_PROBE(3);
     // ---- a10-a13: range quantiser; an 8x8 tile = the quad of lanes {l & ~3 .. l | 3} -----------------------------------
-    int cxB = 0, cyB = 0, cw = w, chh = P.fullH, discard = 1;                 // constraint box of DynamicTileEncode (:4386-4391)
+    int cxB = 0, cyB = 0, cw = w, chh = WHOLE ? h : P.fullH, discard = 1;     // constraint box of DynamicTileEncode (:4386-4391)
     if (P.bounds != nullptr) {
         const int b0 = bnd.x, b1 = bnd.y, b2 = bnd.z, b3 = bnd.w;
-        discard = (b0 == 0 && b1 == 0 && b2 == w && b3 == P.fullH) ? 1 : 0;    // bbox == whole image: every reject is discarded (EncoderContext.cpp:1294, :1400-1403)
+        discard = (b0 == 0 && b1 == 0 && b2 == w && b3 == (WHOLE ? h : P.fullH)) ? 1 : 0;   // bbox == whole image: every reject is discarded (EncoderContext.cpp:1294, :1400-1403)
         cxB = (b0 >> 3) << 3; cyB = (b1 >> 3) << 3;
         cw = (((b2 + 7) >> 3) << 3) - cxB; chh = (((b3 + 7) >> 3) << 3) - cyB;
     }
     const int cxl = cx & 1, cyl = cy & 1;
-    const int tgx = gxCell - cxl * 4, tgyl = gyCell - cyl * 4, tgy = tgyl + P.y0;   // tile origin (stripe-local / full-image row)
-    const bool tileIn = (tgx + 8 <= w) && (tgyl + 8 <= h);
-    // LeftRightOrder over the constraint box incl. its zero-size rule (encoder/framework.h:239-255)
-    const bool part = tileIn && tgx >= cxB && tgx < cxB + cw && tgy >= cyB && tgy < cyB + chh && (tgx + 8 <= cw) && (tgy + 8 <= chh);
-    // the strip's four keep bytes out of the eight that were read around them
-    const uint32_t keep4 = (uint32_t)((((unsigned long long)keep8.y << 32) | keep8.x) >> (8 * (mt0 & 3)));
-    const bool keepMT = (P.keep == nullptr) || discard || (mtIn && ((keep4 >> (8 * q)) & 0xFFu) != 0u);
-    const bool tileLive = part && keepMT;
+    const int tgx = gxCell - cxl * 4, tgyl = gyCell - cyl * 4, tgy = WHOLE ? tgyl : tgyl + P.y0;   // tile origin (stripe-local / full-image row)
+    const bool tileIn = WHOLE || ((tgx + 8 <= w) && (tgyl + 8 <= h));
+    bool tileLive, valid;
+    unsigned long long validMask, liveMask = 0ULL;
+    bool askLanes = false;                                                   // WHOLE: the box's edge crosses the strip, liveness is per lane
+    if constexpr (WHOLE) {
+        // On the scalar unit: `part` below is monotonic in the tile's column and row, so it holds for the strip's sixteen tiles (columns sx0 ..
+        // sx0 + 56, rows sy0, sy0 + 8) when it holds at the corner tiles, the zero-size rule's terms included; the keep bytes are the four bytes
+        // of an SGPR (a row of macro-tiles is a multiple of four long).  A strip the box's edge crosses asks its lanes, as the general kernel does.
+        const int sx0 = BX * 64, sy0 = BY * 64 + wave * 16;
+        const bool inBox = sx0 >= cxB && sx0 + 56 < cxB + cw && sy0 >= cyB && sy0 + 8 < cyB + chh && (sx0 + 64 <= cw) && (sy0 + 16 <= chh);
+        askLanes = !inBox;
+        if (inBox) {
+            const uint32_t k4 = keep8.x;
+            liveMask = ~0ULL;
+            if (P.keep != nullptr && !discard)
+                liveMask = ((k4 & 0x000000FFu) ? 0x000000000000FFFFULL : 0ULL) | ((k4 & 0x0000FF00u) ? 0x00000000FFFF0000ULL : 0ULL) |
+                           ((k4 & 0x00FF0000u) ? 0x0000FFFF00000000ULL : 0ULL) | ((k4 & 0xFF000000u) ? 0xFFFF000000000000ULL : 0ULL);
+        }
+    }
+    if (!WHOLE || askLanes) {
+        // LeftRightOrder over the constraint box incl. its zero-size rule (encoder/framework.h:239-255)
+        const bool part = tileIn && tgx >= cxB && tgx < cxB + cw && tgy >= cyB && tgy < cyB + chh && (tgx + 8 <= cw) && (tgy + 8 <= chh);
+        // the strip's four keep bytes out of the eight that were read around them
+        const uint32_t keep4 = (uint32_t)((((unsigned long long)keep8.y << 32) | keep8.x) >> (8 * (mt0 & 3)));
+        const bool keepMT = (P.keep == nullptr) || discard || (mtIn && ((keep4 >> (8 * q)) & 0xFFu) != 0u);
+        tileLive = part && keepMT;
+        if constexpr (WHOLE) liveMask = __ballot(tileLive);
+    }
+    if constexpr (WHOLE) {                                                   // back to the lanes: two SGPR pairs
+        validMask = liveMask & ~cov;                                         // valid = mipmapMask && !smoothMap (Plane.cpp:527)
+        tileLive = __builtin_amdgcn_inverse_ballot_w64(liveMask);
+        valid = __builtin_amdgcn_inverse_ballot_w64(validMask);
+    }
     const int l00 = lane & ~3;                                               // lane of the tile's top-left cell
     // uncovered quadrants of the lane's 8x8 tile: bits 0..3 = top-left, top-right, bottom-left, bottom-right (the quad's lanes in order)
     const uint32_t quadN = (uint32_t)((~cov) >> l00) & 15u;
     const int v00 = (int)(quadN & 1u), v01 = (int)((quadN >> 2) & 1u);
-    const bool valid = tileLive && ((quadN >> (lane & 3)) & 1u);              // valid = mipmapMask && !smoothMap (Plane.cpp:527)
+    if constexpr (!WHOLE) valid = tileLive && ((quadN >> (lane & 3)) & 1u);  // valid = mipmapMask && !smoothMap (Plane.cpp:527)
     const int nTop = __popc(quadN & 3u), nBot = __popc(quadN >> 2);
     const int tileIdx = (tgyl >> 3) * P.tilesW + (tgx >> 3);
     const size_t T8 = (size_t)P.tilesW * P.tilesH;
     const int tw = lane >> 2;                                                // tile index inside the wave (0..15)
     const bool writer = ((lane & 3) == 0) && tileIn;                         // one lane per tile writes count / def
-    const unsigned long long validMask = __ballot(valid);
+    if constexpr (!WHOLE) validMask = __ballot(valid);
     // wave-uniform: every live tile has all four quadrants to code (then every lane of its quad is valid) -- the wide slot stores below
-    const bool fullTiles = !WANT_DST && __ballot(tileLive && quadN != 15u && quadN != 0u) == 0ULL;
+    // (WHOLE: asked in the range phase, by the strips that have something to code)
+    bool fullTiles = false;
+    if constexpr (!WHOLE) fullTiles = !WANT_DST && __ballot(tileLive && quadN != 15u && quadN != 0u) == 0ULL;
 
     // ---- first level of the stream compaction's scan, fused: nibbles and coded tiles per run of 8 consecutive tiles (row-major tile order =
     // LeftRightOrder; the counts are the same for the three planes).  A strip holds two runs; when the tile grid is a multiple of 8 wide a run
@@ -1017,7 +1091,7 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     // one address, 15-23 % of the kernel on noisy frames.)  Other widths keep the atomics.
     {
         const int n16 = (tileLive && !YK2_ABLATE(1)) ? (nTop + nBot) : 0;   // nibbles / 16 of this tile-plane
-        if ((P.tilesW & 7) == 0) {
+        if (WHOLE || (P.tilesW & 7) == 0) {
             // a strip with nothing to code (no valid lane: every live tile is covered, n16 = 0 throughout) stores the zeros lanes 11, 12 already hold
             if (validMask != 0ULL) {
 #pragma unroll
@@ -1042,6 +1116,17 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
     // behind the plane loop by the tile's first lane: 16 lanes x 8 bytes = two runs of 64 contiguous bytes per strip (round 3: six stores)
     uint32_t defs01 = 0u, defs2c = 0u;
     if (validMask != 0ULL && !YK2_ABLATE(1)) {
+        if constexpr (WHOLE) {
+            // what a strip with nothing to code never needs.  Its pixels: back from the staged strip, intact until the first index word is parked
+            if (ranPasses) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const uint4 t = *reinterpret_cast<const uint4*>(&s_pix[lcell + r * LS]);
+                    pw[r * 4 + 0] = t.x; pw[r * 4 + 1] = t.y; pw[r * 4 + 2] = t.z; pw[r * 4 + 3] = t.w;
+                }
+            }
+            fullTiles = __ballot(tileLive && quadN != 15u && quadN != 0u) == 0ULL;
+        }
         uint8_t* const slotsP = P.slots + fr * P.fs.slots;
         uint32_t* lut = &s_lut[WANT_DST ? tw : 0][0];
         // curve constants for buildLut (test-only reconstruction); fetched here, off the path of the strip's pixel loads
@@ -1429,6 +1514,8 @@ __global__ __launch_bounds__(64, 4) void yk_encode2_kernel(const YkEncodeParams 
         }
         defs2c |= (uint32_t)(tileLive ? 16 * (nTop + nBot) : 0) << 16;
     }
+    // (a WHOLE strip with nothing to code has come here from the scalar test of validMask with its zero run sums stored above and stores its
+    // sixteen zero tile records: no per-lane value of the range phase was formed for it but quadN and the tile index)
     if (writer) {
         const uint32_t offI = P.oInfo + (frU * (uint32_t)P.fs.tileInfo + (uint32_t)tileIdx) * 8u;      // scalar base + 32-bit lane offset
         *reinterpret_cast<uint2*>(small + offI) = make_uint2(defs01, defs2c);
@@ -1479,7 +1566,18 @@ int yk_launch_encode2(yk_ctx* c, const YkEncodeParams& P) {
     if (!P.outTab) return yk_fail(c, YK_ERR_STATE, "output table missing");
     // (the 16x16 map needs no clearing any more: the strips store their 4 bits as bytes of their own, yk_scan2_kernel folds them into the map)
     dim3 grid(((nB + group - 1) / group) * group * 4);
-    if (P.wantDst) {
+    // the WHOLE instantiation: one whole image (no batch; no stripe and no halo rows: y0 = 0, every present row owned, the full height) whose
+    // sides are multiples of 64, so that every block and every strip is complete; the tile grid is then a multiple of 8 wide (the run sums,
+    // not the atomics) and a row of macro-tiles a multiple of 4 long (mtW = w / 16: a strip's keep bytes are one aligned word) -- both follow
+    // from the width, and the kernel relies on them.  Everything else keeps the general kernels.
+    bool whole = !P.wantDst && P.nFrames == 1 && P.y0 == 0 && P.hAvail == P.h && P.fullH == P.h && (P.w & 63) == 0 && (P.h & 63) == 0 && (P.tilesW & 7) == 0;
+#ifdef YK_TEST_HOOKS
+    if (P.ablate & 32) whole = false;                                       // test hook: the general instantiation on a frame that qualifies
+#endif
+    if (whole) {
+        if (P.startMode) hipLaunchKernelGGL((yk_encode2_kernel<false, true, true>), grid, dim3(64), 0, c->stream, P);
+        else hipLaunchKernelGGL((yk_encode2_kernel<false, false, true>), grid, dim3(64), 0, c->stream, P);
+    } else if (P.wantDst) {
         if (P.startMode) hipLaunchKernelGGL((yk_encode2_kernel<true, true>), grid, dim3(64), 0, c->stream, P);
         else hipLaunchKernelGGL((yk_encode2_kernel<true, false>), grid, dim3(64), 0, c->stream, P);
     } else {
