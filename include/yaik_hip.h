@@ -786,6 +786,30 @@ int yk_decode_alpha_batch_status(yk_ctx* c, int32_t* out /* nFrames */);
 int yk_decode_set_batch_windows(yk_ctx* c, const int* xy /* nFrames x {x0, y0}, host memory */, int ww, int wh);
 int yk_decode_output_batch_windows_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha);
 
+/* ---- windows at any pixel offset and size, cropped in the de-tile ----
+ * The three window calls above for rectangles that obey no alignment: a pixel window is x0, y0 >= 0, ww, wh >= 1, x0 + ww <= w, y0 + wh <= h.
+ * Everything upstream of the de-tile works on an 8-aligned COVER of the rectangle (yaik_amd/csrc/yk_window_px.h); the de-tile kernel clips the
+ * cover's 8-pixel row segments to the rectangle and writes exactly its ww x wh pixels -- no second buffer, no second pass, no second launch.
+ * No existing call changes what it accepts or refuses.  Every refusal below comes before the first launch, writes nothing, leaves the handle as
+ * the aligned namesake leaves it and names the call in yk_last_error.
+ * yk_decode_set_window_px: the state rules of yk_decode_set_window.  The handle's window becomes the smallest 8-aligned rectangle that contains
+ * (x0, y0, ww, wh), so every chunk call behaves exactly as under yk_decode_set_window(cover): yk_decode_planes* are exact inside the cover,
+ * yk_decode_tile4x4* whole and exact.  ww == wh == 0 clears the window, yk_decode_begin clears it, yk_decode_set_window replaces it.
+ * yk_decode_output_window_device then writes the ww x wh crop: the pitch checks are made against ww x wh and alpha = -1 reads the 'ALPM' plane at
+ * (x0, y0).  yk_decode_output_scaled_device (levels 1..3) returns YK_ERR_STATE with a message that names the pixel window: its boxes would not be
+ * aligned.  The whole-image outputs, the mip chain and yk_decode_prepare_device refuse as under any window.
+ * yk_decode_render_windows_px_device: yk_decode_render_windows_device for pixel windows of a prepared image.  It renders the 64x64 blocks the pixel
+ * rectangles touch that no earlier call rendered -- one bitmap for this call, the aligned and the scaled one, so the three may be mixed freely --
+ * and queues the same intervals: one YK_STAGE_DEC_DETILE, and the render intervals only when a block was new.
+ * yk_decode_set_batch_windows_px: yk_decode_set_batch_windows for pixel windows.  Every frame gets a cover of one size, min(w, 8 ceil((ww + 7) / 8))
+ * wide (likewise in y), at x0 & ~7 or pulled back to the image's edge; the batch chunk calls treat it as the frame's window.
+ * yk_decode_output_batch_windows_device then writes ww x wh per frame (pitch checks against ww x wh, alpha = -1 at each window's own offset).
+ * Rectangles that are all 8-aligned with 8-aligned sizes run the kernels of the aligned calls. */
+int yk_decode_set_window_px(yk_ctx* c, int x0, int y0, int ww, int wh);
+int yk_decode_render_windows_px_device(yk_ctx* c, int nWindows, const int* xy, int ww, int wh,
+                                       uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t windowBytes, int channels, int alpha);
+int yk_decode_set_batch_windows_px(yk_ctx* c, const int* xy /* nFrames x {x0, y0}, host memory */, int ww, int wh);
+
 /* ---- round-trip quality (new): what the decode holds against a source image, both in HBM -----------------------------------------
  * The codec is lossy; these calls say how lossy a round trip was without moving a pixel to the host.  One kernel reads the decoder's 8x8-tiled
  * planes (and, with four channels, the decoded 'ALPM' plane) and the source where it lies, a second one folds the workgroups' records; per frame

@@ -325,6 +325,10 @@ struct yk_ctx {
     // {x0, y0, x1, y1} (pixels) in HBM for the batch x window kernels: 1024 entries, allocated once, written through the pinned ring below
     bool dBWinSet = false; int dBWinW = 0, dBWinH = 0;
     YkBuf<int> dBWinTab;
+    // yk_decode_set_window_px / yk_decode_set_batch_windows_px: the window above is the 8-aligned cover the chunk calls decode, and this
+    // is the pixel rectangle the output call writes: dPx{X,Y} the single image's origin, dPx{W,H} the size (of every frame's window in a batch, whose
+    // per-frame offsets into the cover lie in dBWinTab behind the rectangles, at int 4 * dFrames)
+    bool dPxSet = false; int dPxX = 0, dPxY = 0, dPxW = 0, dPxH = 0;
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
     // yk_decode_prepare_device: the map-sized work of this image is done and what a render needs is kept in dPrep (yk_decode.hip) until the next
     // yk_decode_begin[_batch]; the buffers in dPrep are grow-only and go with the handle (yk_dec_prepared_free)

@@ -14,6 +14,7 @@
 #include "yk_common.h"
 #include "yk_device.h"
 #include "yk_window_blocks.h"
+#include "yk_window_px.h"
 
 struct DPassGeo { int sx, sy, bigX, bigY, bitCount, xBB, tilesPerRow; };
 
@@ -1052,6 +1053,129 @@ static void yk_dt_launch_batch_win(const YkDetileArgs& a, hipStream_t s, int nFr
     hipLaunchKernelGGL((yk_dec_detile_batch_win_kernel<C, PLANAR, ASRC>), dim3(gx, (unsigned)nFrames), dim3(YK_DT_THREADS), 0, s, a, wins, wtW, planesFrame, outFrame, alphaFrame);
 }
 
+// ---- the clipping forms: windows at any pixel offset and size (yk_decode_set_window_px and its kin, yk_window_px.h) -----------------
+// The window forms above over the tiles of the window's 8-aligned COVER: the same lanes, units, steps and loads (dense 16-byte loads per lane,
+// all loads of a workgroup before its first store; the cover lies inside the image, so the 8-byte alpha loads of a cover tile stay inside the
+// plane).  Only the store differs.  Pixel (X, Y) of the cover is pixel (X - dx, Y - dy) of the ww x wh destination: a row outside [0, wh) is
+// skipped, a segment wholly inside [0, ww) goes through yk_dt_emit at its shifted address (unaligned, which that path serves), a segment the
+// left or right edge cuts -- the first and last tile column of a cover, and the columns before dx of a shared cover -- is written pixel by
+// pixel.  Rows and columns are clipped by the one function the CPU tool checks exhaustively (yk_wpx_clip), so no byte outside the pixels is written.
+struct YkDetileClip { int dx, dy, ww, wh; };
+
+// columns src0 .. src0 + n - 1 (n < 8) of a row segment -> their bytes from o on.  CHW: the kept bytes of a plane are one run, written as at most
+// a dword, a word and a byte; HWC: a predicated store per pixel (a dword, or a word and a byte), the pixel's bytes picked by constant shifts
+template <int C, bool PLANAR>
+__device__ __forceinline__ void yk_dt_emit_px(uint8_t* o, size_t planeBytes, int src0, int n, uint32_t r0, uint32_t r1, uint32_t g0, uint32_t g1, uint32_t b0, uint32_t b1,
+                                              uint32_t a0, uint32_t a1) {
+    if constexpr (PLANAR) {
+        const uint64_t v[4] = { r0 | (uint64_t)r1 << 32, g0 | (uint64_t)g1 << 32, b0 | (uint64_t)b1 << 32, a0 | (uint64_t)a1 << 32 };
+#pragma unroll
+        for (int k = 0; k < C; k++) {
+            uint64_t t = v[k] >> (8 * src0);
+            uint8_t* p = o + (size_t)k * planeBytes;
+            if (n & 4) { const uint32_t d = (uint32_t)t; __builtin_memcpy(p, &d, 4); t >>= 32; p += 4; }
+            if (n & 2) { const uint16_t d = (uint16_t)t; __builtin_memcpy(p, &d, 2); t >>= 16; p += 2; }
+            if (n & 1) *p = (uint8_t)t;
+        }
+    } else {
+        const uint32_t rr[2] = { r0, r1 }, gg[2] = { g0, g1 }, bb[2] = { b0, b1 }, aa[2] = { a0, a1 };
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            if (i < src0 || i >= src0 + n) continue;
+            const int sh = 8 * (i & 3);
+            const uint32_t r = (rr[i >> 2] >> sh) & 255u, g = (gg[i >> 2] >> sh) & 255u, b = (bb[i >> 2] >> sh) & 255u;
+            uint8_t* p = o + (i - src0) * C;
+            if constexpr (C == 4) {
+                const uint32_t d = r | g << 8 | b << 16 | ((aa[i >> 2] >> sh) & 255u) << 24;
+                __builtin_memcpy(p, &d, 4);
+            } else {
+                const uint16_t d = (uint16_t)(r | g << 8);
+                __builtin_memcpy(p, &d, 2);
+                p[2] = (uint8_t)b;
+            }
+        }
+    }
+}
+// the two rows of cover tile (jx, jy) this lane holds, clipped against the window
+template <int C, bool PLANAR, int ASRC>
+__device__ __forceinline__ void yk_dt_store_px(const YkDetileArgs& a, const YkDetileClip& cl, const YkDtUnit& u, uint32_t jx, uint32_t jy, uint32_t rp) {
+    const YkPxClip kx = yk_wpx_clip((int)jx, cl.dx, cl.ww), ky = yk_wpx_clip((int)jy, cl.dy, cl.wh);
+    if (kx.n == 0 || ky.n == 0) return;
+    uint32_t al[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) al[i] = ASRC == YK_DT_ALPHA_PLANE ? u.a[i] : a.alphaConst;
+    const uint32_t rr[4] = { u.r.x, u.r.y, u.r.z, u.r.w }, gg[4] = { u.g.x, u.g.y, u.g.z, u.g.w }, bb[4] = { u.b.x, u.b.y, u.b.z, u.b.w };
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int row = (int)rp * 2 + i;                                      // of the tile
+        if (row < ky.src0 || row >= ky.src0 + ky.n) continue;
+        uint8_t* o = a.out + (size_t)(ky.dst + row - ky.src0) * a.rowBytes + (size_t)kx.dst * (PLANAR ? 1 : C);
+        if (kx.n == 8) yk_dt_emit<C, PLANAR>(o, a.planeBytes, rr[2 * i], rr[2 * i + 1], gg[2 * i], gg[2 * i + 1], bb[2 * i], bb[2 * i + 1], al[2 * i], al[2 * i + 1]);
+        else yk_dt_emit_px<C, PLANAR>(o, a.planeBytes, kx.src0, kx.n, rr[2 * i], rr[2 * i + 1], gg[2 * i], gg[2 * i + 1], bb[2 * i], bb[2 * i + 1], al[2 * i], al[2 * i + 1]);
+    }
+}
+// wn: the cover in tiles; a.nTiles its tile count; a.alpha (YK_DT_ALPHA_PLANE) points at the cover's first alpha byte
+template <int C, bool PLANAR, int ASRC>
+__device__ __forceinline__ void yk_dec_detile_win_px_body(const YkDetileArgs a, const YkDetileWin wn, const YkDetileClip cl, const uint32_t bx) {
+    const uint32_t lane = threadIdx.x & 63, rp = lane & 3;
+    const uint32_t j0 = (bx * (YK_DT_K * 4) + (threadIdx.x >> 6)) * 16 + (lane >> 2);
+    if ((bx + 1) * (uint32_t)YK_DT_TILES <= a.nTiles) {
+        YkDtUnit u[YK_DT_K];
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) yk_dt_load_win<C, PLANAR, ASRC>(a, wn, j0 + k * 64, rp, u[k]);
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) {
+            const uint32_t j = j0 + k * 64, jy = j / wn.wtW;
+            yk_dt_store_px<C, PLANAR, ASRC>(a, cl, u[k], j - jy * wn.wtW, jy, rp);
+        }
+        return;
+    }
+    for (int k = 0; k < YK_DT_K; k++) {
+        const uint32_t j = j0 + k * 64, jy = j / wn.wtW;
+        if (j >= a.nTiles) continue;
+        YkDtUnit u;
+        yk_dt_load_win<C, PLANAR, ASRC>(a, wn, j, rp, u);
+        yk_dt_store_px<C, PLANAR, ASRC>(a, cl, u, j - jy * wn.wtW, jy, rp);
+    }
+}
+// one pixel window of the image begun (yk_decode_set_window_px)
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_win_px_kernel(YkDetileArgs a, const YkDetileWin wn, const YkDetileClip cl) {
+    yk_dec_detile_win_px_body<C, PLANAR, ASRC>(a, wn, cl, blockIdx.x);
+}
+// K pixel windows of ww x wh of a prepared image of w x h (yk_decode_render_windows_px_device): window blockIdx.y's pixel origin from the table in
+// HBM, its shared cover (one size for every origin, a.nTiles tiles) worked out here by the functions that sized the launch
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_wins_px_kernel(YkDetileArgs a, const int* __restrict__ xy, int ww, int wh, int w, int h, size_t windowBytes) {
+    const uint32_t k = blockIdx.y;
+    const int x0 = xy[2 * k], y0 = xy[2 * k + 1];
+    const YkPxCover cx = yk_wpx_shared_cover(x0, ww, w), cy = yk_wpx_shared_cover(y0, wh, h);
+    a.out += (size_t)k * windowBytes;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) a.alpha += (size_t)cy.c0 * a.strideA + (size_t)cx.c0;
+    const YkDetileWin wn = { (uint32_t)cx.c0 >> 3, (uint32_t)cy.c0 >> 3, (uint32_t)cx.cw >> 3 };
+    yk_dec_detile_win_px_body<C, PLANAR, ASRC>(a, wn, YkDetileClip{ x0 - cx.c0, y0 - cy.c0, ww, wh }, blockIdx.x);
+}
+// a batch with a pixel window per frame (yk_decode_set_batch_windows_px): wins[f] is frame f's cover (what the upstream kernels decoded), off[2f],
+// off[2f + 1] the window's offset inside it
+template <int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_batch_win_px_kernel(YkDetileArgs a, const DWinRect* __restrict__ wins, const int* __restrict__ off, uint32_t wtW,
+                                                                                   int ww, int wh, size_t planesFrame, size_t outFrame, size_t alphaFrame) {
+    const uint32_t f = blockIdx.y;
+    const uint32_t x0 = (uint32_t)wins[f].x0, y0 = (uint32_t)wins[f].y0;
+    a.planes += (size_t)f * planesFrame; a.out += (size_t)f * outFrame;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) a.alpha += (size_t)f * alphaFrame + (size_t)y0 * a.strideA + x0;
+    const YkDetileWin wn = { x0 >> 3, y0 >> 3, wtW };
+    yk_dec_detile_win_px_body<C, PLANAR, ASRC>(a, wn, YkDetileClip{ off[2 * f], off[2 * f + 1], ww, wh }, blockIdx.x);
+}
+// the template space of the de-tile kernels, for the launches of the clipping forms: f(tag) with tag.c, tag.planar, tag.asrc
+template <int C, bool PLANAR, int ASRC> struct YkDtTag { static constexpr int c = C; static constexpr bool planar = PLANAR; static constexpr int asrc = ASRC; };
+template <typename F>
+static void yk_dt_each(int channels, bool planar, bool fromPlane, F f) {
+    if (channels == 3) { if (planar) f(YkDtTag<3, true, YK_DT_ALPHA_NONE>{}); else f(YkDtTag<3, false, YK_DT_ALPHA_NONE>{}); }
+    else if (fromPlane) { if (planar) f(YkDtTag<4, true, YK_DT_ALPHA_PLANE>{}); else f(YkDtTag<4, false, YK_DT_ALPHA_PLANE>{}); }
+    else { if (planar) f(YkDtTag<4, true, YK_DT_ALPHA_CONST>{}); else f(YkDtTag<4, false, YK_DT_ALPHA_CONST>{}); }
+}
+
 // nFrames == 0: the selected frame (the existing single-image launch); otherwise nFrames frames, planesFrame / outFrame bytes apart
 template <int C, bool PLANAR, int ASRC>
 static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, size_t planesFrame = 0, size_t outFrame = 0, size_t alphaFrame = 0,
@@ -1082,6 +1206,16 @@ static int yk_dec_detile(yk_ctx* c, uint8_t* out, size_t rowBytes, size_t planeB
     }
     const bool planar = planeBytes > 0;
     { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    if (window && c->dPxSet && !yk_wpx_aligned(c->dPxX, c->dPxY, c->dPxW, c->dPxH)) {   // the cover's tiles, clipped to the pixel window (an aligned one is its own cover)
+        const YkDetileClip cl = { c->dPxX - c->dWinX, c->dPxY - c->dWinY, c->dPxW, c->dPxH };
+        const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
+        yk_dt_each(channels, planar, alpha != nullptr, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((yk_dec_detile_win_px_kernel<T::c, T::planar, T::asrc>), dim3(gx), dim3(YK_DT_THREADS), 0, c->stream, a, win, cl);
+        });
+        YK_HIP(c, hipGetLastError());
+        return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+    }
     if (channels == 3) { if (planar) yk_dt_launch<3, true, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes, 0, wn); else yk_dt_launch<3, false, YK_DT_ALPHA_NONE>(a, c->stream, nFrames, pf, frameBytes, 0, wn); }
     else if (alpha)    { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_PLANE>(a, c->stream, nFrames, pf, frameBytes, alphaFrame, wn); else yk_dt_launch<4, false, YK_DT_ALPHA_PLANE>(a, c->stream, nFrames, pf, frameBytes, alphaFrame, wn); }
     else               { if (planar) yk_dt_launch<4, true, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes, 0, wn); else yk_dt_launch<4, false, YK_DT_ALPHA_CONST>(a, c->stream, nFrames, pf, frameBytes, 0, wn); }
@@ -1603,6 +1737,7 @@ static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
     }
     c->dCur = 0;
     c->dWinSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; c->dChunkSeen = false; c->dBatchBegun = false;
+    c->dPxSet = false; c->dPxX = c->dPxY = c->dPxW = c->dPxH = 0;
     c->dBWinSet = false; c->dBWinW = c->dBWinH = 0;                             // the table stays queued kernels' to read: the next set writes it behind them
     c->dPrepared = false;                                                       // a prepared image ends here; what it kept is overwritten by the next prepare
     // The planes (3 B per pixel: 201 MB at 8192 x 8192, 40 us of every frame) are NOT cleared: every renderer marks what it writes in tile4x4Mask and
@@ -1637,10 +1772,26 @@ int yk_decode_set_window(yk_ctx* c, int x0, int y0, int ww, int wh) {
     YK_DEC_NO_PREPARED(c, "yk_decode_set_window");
     if (c->dBatchBegun || c->dFrames > 1) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window: a window belongs to a single image (yk_decode_begin), not to a batch");
     if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window: a chunk of this image has been decoded already; set the window right after yk_decode_begin");
-    if (ww == 0 && wh == 0) { c->dWinSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; return YK_OK; }
+    if (ww == 0 && wh == 0) { c->dWinSet = false; c->dPxSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; return YK_OK; }
     if (((x0 | y0 | ww | wh) & 7) || x0 < 0 || y0 < 0 || ww < 8 || wh < 8 || x0 > c->dw - ww || y0 > c->dh - wh)
         return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_window: x0, y0, ww, wh must be multiples of 8 with ww, wh >= 8 and the window inside the image");
-    c->dWinX = x0; c->dWinY = y0; c->dWinW = ww; c->dWinH = wh; c->dWinSet = true;
+    c->dWinX = x0; c->dWinY = y0; c->dWinW = ww; c->dWinH = wh; c->dWinSet = true; c->dPxSet = false;
+    return YK_OK;
+}
+// yk_decode_set_window for a rectangle at any pixel offset and size (include/yaik_hip.h): the handle's window becomes the rectangle's
+// 8-aligned cover, so every chunk call runs as under yk_decode_set_window(cover); the pixel rectangle is kept for yk_decode_output_window_device
+int yk_decode_set_window_px(yk_ctx* c, int x0, int y0, int ww, int wh) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window_px: yk_decode_begin first");
+    YK_DEC_NO_PREPARED(c, "yk_decode_set_window_px");
+    if (c->dBatchBegun || c->dFrames > 1) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window_px: a window belongs to a single image (yk_decode_begin), not to a batch");
+    if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_window_px: a chunk of this image has been decoded already; set the window right after yk_decode_begin");
+    if (ww == 0 && wh == 0) { c->dWinSet = false; c->dPxSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; return YK_OK; }
+    if (!yk_wpx_window_ok(x0, y0, ww, wh, c->dw, c->dh))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_window_px: x0, y0 >= 0, ww, wh >= 1 and the window inside the image");
+    const YkPxCover cx = yk_wpx_cover(x0, ww), cy = yk_wpx_cover(y0, wh);
+    c->dWinX = cx.c0; c->dWinY = cy.c0; c->dWinW = cx.cw; c->dWinH = cy.cw; c->dWinSet = true;
+    c->dPxX = x0; c->dPxY = y0; c->dPxW = ww; c->dPxH = wh; c->dPxSet = true;
     return YK_OK;
 }
 // the window rounded out to 64-pixel blocks, clipped to the image: what the gradient render fills
@@ -1686,7 +1837,7 @@ int yk_decode_set_batch_windows(yk_ctx* c, const int* xy, int ww, int wh) {
     if (!c) return YK_ERR_BAD_ARG;
     if (!yk_dec_begun(c) || !c->dBatchBegun) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows: yk_decode_begin_batch first (the window of a single image is yk_decode_set_window's)");
     if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows: a chunk of this batch has been decoded already; set the windows right after yk_decode_begin_batch");
-    c->dBWinSet = false; c->dBWinW = c->dBWinH = 0;                              // a refusal below leaves the batch without windows
+    c->dBWinSet = false; c->dBWinW = c->dBWinH = 0; c->dPxSet = false;           // a refusal below leaves the batch without windows
     if (ww == 0 && wh == 0) return YK_OK;
     if (!xy) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_batch_windows: the origin table is NULL");
     const int N = c->dFrames;
@@ -1697,13 +1848,45 @@ int yk_decode_set_batch_windows(yk_ctx* c, const int* xy, int ww, int wh) {
     }
     if (!ok) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_batch_windows: x0, y0, ww, wh must be multiples of 8 with ww, wh >= 8 and every frame's window inside the image");
     YK_HIP(c, hipSetDevice(c->device));
-    YK_HIP(c, c->dBWinTab.reserve(c->stream, (size_t)1024 * 4));                // every batch fits: allocated once, so no later call waits for queued readers
+    YK_HIP(c, c->dBWinTab.reserve(c->stream, (size_t)1024 * 6));                // every batch fits (yk_decode_set_batch_windows_px adds two ints per frame): allocated once, so no later call waits for queued readers
     int slot; void* host;
     { const int rc = yk_dec_table_host(c, (size_t)N * sizeof(DWinRect), &slot, &host); if (rc) return rc; }
     DWinRect* tab = static_cast<DWinRect*>(host);
     for (int f = 0; f < N; f++) tab[f] = DWinRect{ xy[2 * f], xy[2 * f + 1], xy[2 * f] + ww, xy[2 * f + 1] + wh };
     { const int rc = yk_dec_table_upload(c, slot, c->dBWinTab.p, (size_t)N * sizeof(DWinRect)); if (rc) return rc; }
     c->dBWinW = ww; c->dBWinH = wh; c->dBWinSet = true;
+    return YK_OK;
+}
+// yk_decode_set_batch_windows for rectangles at any pixel offset (include/yaik_hip.h).  The batch kernels take one tile count for every
+// frame, so every frame gets the shared cover of yk_window_px.h: the table's rectangles are the covers, which is all the upstream kernels read, and
+// the windows' offsets inside their covers follow them in the same upload, for the clipping de-tile alone.
+int yk_decode_set_batch_windows_px(yk_ctx* c, const int* xy, int ww, int wh) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!yk_dec_begun(c) || !c->dBatchBegun) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows_px: yk_decode_begin_batch first (the window of a single image is yk_decode_set_window_px's)");
+    if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows_px: a chunk of this batch has been decoded already; set the windows right after yk_decode_begin_batch");
+    c->dBWinSet = false; c->dBWinW = c->dBWinH = 0; c->dPxSet = false;           // a refusal below leaves the batch without windows
+    if (ww == 0 && wh == 0) return YK_OK;
+    if (!xy) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_batch_windows_px: the origin table is NULL");
+    const int N = c->dFrames, w = c->dw, h = c->dh;
+    if (!yk_wpx_windows_ok(N, xy, ww, wh, w, h))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_batch_windows_px: x0, y0 >= 0, ww, wh >= 1 and every frame's window inside the image");
+    bool aligned = true;
+    for (int f = 0; aligned && f < N; f++) aligned = yk_wpx_aligned(xy[2 * f], xy[2 * f + 1], ww, wh);
+    if (aligned) return yk_decode_set_batch_windows(c, xy, ww, wh);             // every window is its own cover: the aligned kernels
+    YK_HIP(c, hipSetDevice(c->device));
+    YK_HIP(c, c->dBWinTab.reserve(c->stream, (size_t)1024 * 6));                // the rectangles and the offsets of every batch: allocated once per handle
+    int slot; void* host;
+    { const int rc = yk_dec_table_host(c, (size_t)N * 6 * sizeof(int), &slot, &host); if (rc) return rc; }
+    DWinRect* tab = static_cast<DWinRect*>(host);
+    int* off = static_cast<int*>(host) + 4 * (size_t)N;
+    for (int f = 0; f < N; f++) {
+        const YkPxCover cx = yk_wpx_shared_cover(xy[2 * f], ww, w), cy = yk_wpx_shared_cover(xy[2 * f + 1], wh, h);
+        tab[f] = DWinRect{ cx.c0, cy.c0, cx.c0 + cx.cw, cy.c0 + cy.cw };
+        off[2 * f] = xy[2 * f] - cx.c0; off[2 * f + 1] = xy[2 * f + 1] - cy.c0;
+    }
+    { const int rc = yk_dec_table_upload(c, slot, c->dBWinTab.p, (size_t)N * 6 * sizeof(int)); if (rc) return rc; }
+    c->dBWinW = yk_wpx_shared_size(ww, w); c->dBWinH = yk_wpx_shared_size(wh, h); c->dBWinSet = true;
+    c->dPxW = ww; c->dPxH = wh; c->dPxSet = true;
     return YK_OK;
 }
 static const DWinRect* yk_dec_bwin_tab(const yk_ctx* c) { return reinterpret_cast<const DWinRect*>(c->dBWinTab.p); }
@@ -2185,7 +2368,8 @@ static int yk_dec_output_device(yk_ctx* c, uint8_t* devOut, size_t rowBytes, siz
     if (channels != 3 && channels != 4) return yk_fail(c, YK_ERR_BAD_ARG, "channels must be 3 or 4");
     if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_fail(c, YK_ERR_BAD_ARG, "alpha must be -1 (the decoded plane) or 0..255");
     if (!yk_dec_begun(c)) return yk_fail(c, YK_ERR_STATE, "yk_decode_begin first");
-    const size_t w = (size_t)(window ? c->dWinW : c->dw), h = (size_t)(window ? c->dWinH : c->dh);
+    const bool px = window && c->dPxSet;                                      // a pixel window: what is written is dPxW x dPxH of the cover
+    const size_t w = (size_t)(px ? c->dPxW : window ? c->dWinW : c->dw), h = (size_t)(px ? c->dPxH : window ? c->dWinH : c->dh);
     if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
         return yk_fail(c, YK_ERR_BAD_ARG, window ? "row or plane pitch too small for the window" : "row or plane pitch too small for the image");
     const bool fromPlane = channels == 4 && alpha < 0;
@@ -2255,7 +2439,8 @@ int yk_decode_output_batch_windows_device(yk_ctx* c, uint8_t* devOut, size_t row
     const bool fromPlanes = channels == 4 && alpha < 0;
     if (fromPlanes && (!c->dAlphaValid || !c->dAlphaBatch))
         return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_batch_windows_device: alpha = -1 needs yk_decode_alpha_batch_device first: the batch has no decoded alpha planes");
-    const size_t w = (size_t)c->dBWinW, h = (size_t)c->dBWinH;
+    const bool px = c->dPxSet;                                                // pixel windows: dPxW x dPxH of every frame's cover is written
+    const size_t w = (size_t)(px ? c->dPxW : c->dBWinW), h = (size_t)(px ? c->dPxH : c->dBWinH);
     if (planeBytes == 0 ? rowBytes < w * channels : (rowBytes < w || planeBytes / h < rowBytes))
         return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_batch_windows_device: row or plane pitch too small for the window");
     if (c->dFrames > 1 && (planeBytes == 0 ? frameBytes / h < rowBytes : frameBytes / (size_t)channels < planeBytes))
@@ -2266,13 +2451,25 @@ int yk_decode_output_batch_windows_device(yk_ctx* c, uint8_t* devOut, size_t row
     a.planes = c->dB.planes; a.planeSize = c->dPlaneSize;
     a.alpha = fromPlanes ? (const uint8_t*)c->dAlpha : nullptr; a.strideA = (size_t)c->dw; a.alphaConst = (uint32_t)((fromPlanes ? 0 : alpha) & 255) * 0x01010101u;
     a.out = devOut; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
-    a.tileW = (uint32_t)(c->dw >> 3); a.nTiles = (uint32_t)(w >> 3) * (uint32_t)(h >> 3);
-    const uint32_t wtW = (uint32_t)(w >> 3);
+    a.tileW = (uint32_t)(c->dw >> 3); a.nTiles = (uint32_t)(c->dBWinW >> 3) * (uint32_t)(c->dBWinH >> 3);
+    const uint32_t wtW = (uint32_t)(c->dBWinW >> 3);
     const size_t pf = c->dStride.planes, af = fromPlanes ? c->dAlphaStride : 0;
     const DWinRect* wins = yk_dec_bwin_tab(c);
     const bool planar = planeBytes > 0;
     const int N = c->dFrames;
     { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    if (px) {                                                                 // the covers' tiles, each frame clipped to its window; the offsets follow the rectangles
+        const int* off = c->dBWinTab.p + 4 * (size_t)N;
+        const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
+        const int pw = c->dPxW, ph = c->dPxH;
+        yk_dt_each(channels, planar, fromPlanes, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((yk_dec_detile_batch_win_px_kernel<T::c, T::planar, T::asrc>), dim3(gx, (unsigned)N), dim3(YK_DT_THREADS), 0, c->stream, a, wins, off, wtW, pw, ph,
+                               pf, frameBytes, af);
+        });
+        YK_HIP(c, hipGetLastError());
+        return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+    }
     if (channels == 3)   { if (planar) yk_dt_launch_batch_win<3, true, YK_DT_ALPHA_NONE>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); else yk_dt_launch_batch_win<3, false, YK_DT_ALPHA_NONE>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); }
     else if (fromPlanes) { if (planar) yk_dt_launch_batch_win<4, true, YK_DT_ALPHA_PLANE>(a, c->stream, N, wins, wtW, pf, frameBytes, af); else yk_dt_launch_batch_win<4, false, YK_DT_ALPHA_PLANE>(a, c->stream, N, wins, wtW, pf, frameBytes, af); }
     else                 { if (planar) yk_dt_launch_batch_win<4, true, YK_DT_ALPHA_CONST>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); else yk_dt_launch_batch_win<4, false, YK_DT_ALPHA_CONST>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); }
@@ -2289,6 +2486,8 @@ int yk_decode_output_scaled_device(yk_ctx* c, int level, uint8_t* devOut, size_t
         return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_device: this image is prepared for windows (yk_decode_prepare_device); yk_decode_render_windows_scaled_device reads it");
     if (level == 0) return yk_decode_output_window_device(c, devOut, rowBytes, planeBytes, channels, alpha);
     YK_DEC_NO_BATCH_WINDOWS(c, "yk_decode_output_scaled_device");
+    if (c->dWinSet && c->dPxSet)
+        return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_scaled_device: a pixel window is set on this decode (yk_decode_set_window_px) and its boxes would not be aligned; yk_decode_output_window_device writes it at full size");
     if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: devOut is NULL");
     if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: channels must be 3 or 4");
     if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_scaled_device: alpha must be -1 (the decoded plane) or 0..255");
@@ -2666,6 +2865,52 @@ int yk_decode_render_windows_device(yk_ctx* c, int nWindows, const int* xy, int 
     if (channels == 3) { if (planar) yk_dt_launch_wins<3, true, YK_DT_ALPHA_NONE>(a, c->stream, nWindows, devXY, wtW, windowBytes); else yk_dt_launch_wins<3, false, YK_DT_ALPHA_NONE>(a, c->stream, nWindows, devXY, wtW, windowBytes); }
     else if (fromPlane) { if (planar) yk_dt_launch_wins<4, true, YK_DT_ALPHA_PLANE>(a, c->stream, nWindows, devXY, wtW, windowBytes); else yk_dt_launch_wins<4, false, YK_DT_ALPHA_PLANE>(a, c->stream, nWindows, devXY, wtW, windowBytes); }
     else { if (planar) yk_dt_launch_wins<4, true, YK_DT_ALPHA_CONST>(a, c->stream, nWindows, devXY, wtW, windowBytes); else yk_dt_launch_wins<4, false, YK_DT_ALPHA_CONST>(a, c->stream, nWindows, devXY, wtW, windowBytes); }
+    YK_HIP(c, hipGetLastError());
+    return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+}
+
+// yk_decode_render_windows_device for windows at any pixel offset and size: the blocks the pixel rectangles touch are rendered (the
+// bitmap shared with the aligned and the scaled call), then every window's shared cover is de-tiled and clipped.  A cover may reach into a block
+// no window touches: its bytes are loaded and clipped away, never written.
+int yk_decode_render_windows_px_device(yk_ctx* c, int nWindows, const int* xy, int ww, int wh, uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t windowBytes,
+                                       int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!yk_dec_begun(c) || !c->dPrepared) return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_px_device: yk_decode_prepare_device first");
+    YkDecPrepared& P = *c->dPrep;
+    if (P.blocks.w != c->dw || P.blocks.h != c->dh)
+        return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_px_device: the prepared image is not the one this handle holds; yk_decode_begin and yk_decode_prepare_device again");
+    if (nWindows < 1 || nWindows > 1024) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_px_device: nWindows must be 1..1024");
+    if (!xy) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_px_device: the window table is NULL");
+    const int w = c->dw, h = c->dh;
+    if (!yk_wpx_windows_ok(nWindows, xy, ww, wh, w, h))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_px_device: x0, y0 >= 0, ww, wh >= 1 and every window inside the image");
+    if (!devOut) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_px_device: devOut is NULL");
+    if (channels != 3 && channels != 4) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_px_device: channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255)) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_px_device: alpha must be -1 (the decoded plane) or 0..255");
+    if (planeBytes == 0 ? rowBytes < (size_t)ww * channels : (rowBytes < (size_t)ww || planeBytes / (size_t)wh < rowBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_px_device: row or plane pitch too small for the window");
+    if (nWindows > 1 && (planeBytes == 0 ? windowBytes / (size_t)wh < rowBytes : windowBytes / (size_t)channels < planeBytes))
+        return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_render_windows_px_device: window stride too small for a window");
+    const bool fromPlane = channels == 4 && alpha < 0;
+    if (fromPlane && !c->dAlphaValid) return yk_refuse(c, YK_ERR_STATE, "yk_decode_render_windows_px_device: alpha = -1 needs yk_decode_alpha first");
+    bool aligned = true;
+    for (int k = 0; aligned && k < nWindows; k++) aligned = yk_wpx_aligned(xy[2 * k], xy[2 * k + 1], ww, wh);
+    if (aligned) return yk_decode_render_windows_device(c, nWindows, xy, ww, wh, devOut, rowBytes, planeBytes, windowBytes, channels, alpha);
+    const int* devXY = nullptr;
+    { const int rc = yk_dec_render_new_blocks(c, nWindows, xy, ww, wh, &devXY); if (rc) return rc; }   // yk_wb_take works in pixels: any rectangle
+    YkDetileArgs a;
+    a.planes = yk_dec_frame(c).planes; a.planeSize = c->dPlaneSize;
+    a.alpha = fromPlane ? yk_dec_alpha_cur(c) : nullptr; a.strideA = (size_t)w; a.alphaConst = (uint32_t)((fromPlane ? 0 : alpha) & 255) * 0x01010101u;
+    a.out = devOut; a.rowBytes = rowBytes; a.planeBytes = planeBytes;
+    a.tileW = (uint32_t)(w >> 3); a.nTiles = (uint32_t)(yk_wpx_shared_size(ww, w) >> 3) * (uint32_t)(yk_wpx_shared_size(wh, h) >> 3);
+    const bool planar = planeBytes > 0;
+    const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
+    { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    yk_dt_each(channels, planar, fromPlane, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((yk_dec_detile_wins_px_kernel<T::c, T::planar, T::asrc>), dim3(gx, (unsigned)nWindows), dim3(YK_DT_THREADS), 0, c->stream, a, devXY, ww, wh, w, h,
+                           windowBytes);
+    });
     YK_HIP(c, hipGetLastError());
     return yk_stage_end(c, YK_STAGE_DEC_DETILE);
 }

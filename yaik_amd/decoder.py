@@ -162,18 +162,35 @@ class HipTileDecoder:
         """(x0, y0, w, h) of the window set on the image begun, None when the decode is of the whole image (always after begin)."""
         return self._window
 
-    def set_window(self, x0: int, y0: int, w: int, h: int) -> None:
+    @property
+    def window_cover(self):
+        """The 8-aligned rectangle (x0, y0, w, h) the chunk calls decode for the window set: the window itself, or with set_window(px=True) the
+        smallest 8-aligned rectangle that contains it; planes() is exact inside it.  None without a window."""
+        if self._window is None:
+            return None
+        x0, y0, w, h = self._window
+        cx, cy = x0 & ~7, y0 & ~7
+        return cx, cy, ((x0 + w + 7) & ~7) - cx, ((y0 + h + 7) & ~7) - cy
+
+    def set_window(self, x0: int, y0: int, w: int, h: int, *, px: bool = False) -> None:
         """From here on the decode calls of this image owe only the pixels of the rectangle (x0, y0, w, h): the gradient render skips the 64x64
         blocks it does not touch and the 1-D chunk decodes its tiles only.  Call it right after begin(), before any chunk is decoded; x0, y0, w, h
         are multiples of 8 with w, h >= 8 inside the image; (0, 0, 0, 0) clears the window.  Read the result with image_window_device(); image(),
         image_device() and the compare calls raise the library's state error while a window is set, planes() is exact inside the window only,
         tile4x4() is whole and exact.  Bad arguments raise before any library call; a batch, or chunks decoded already, are the library's to
-        refuse."""
+        refuse.  px=True (yk_decode_set_window_px): any rectangle inside the image, w, h >= 1; the chunk calls decode window_cover,
+        image_window_device() writes exactly the rectangle, and image_scaled_device() at levels 1..3 is the library's to refuse."""
         v = (x0, y0, w, h)
         if any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) for a in v):
             raise TypeError(f"window (x0, y0, w, h) must be four ints; got {v!r}")
         x0, y0, w, h = (int(a) for a in v)
         clear = w == 0 and h == 0 and x0 == 0 and y0 == 0
+        if px:
+            if not clear and (x0 < 0 or y0 < 0 or w < 1 or h < 1 or x0 + w > self.w or y0 + h > self.h):
+                raise ValueError(f"window {(x0, y0, w, h)}: x0, y0 >= 0 and w, h >= 1 are needed, inside the {self.w} x {self.h} image")
+            _chk(self._h, lib().yk_decode_set_window_px(self._h, x0, y0, w, h))
+            self._window = None if clear else (x0, y0, w, h)
+            return
         if not clear and ((x0 | y0 | w | h) & 7 or x0 < 0 or y0 < 0 or w < 8 or h < 8 or x0 + w > self.w or y0 + h > self.h):
             raise ValueError(f"window {(x0, y0, w, h)}: x0, y0, w, h must be multiples of 8 with w, h >= 8, inside the {self.w} x {self.h} image")
         _chk(self._h, lib().yk_decode_set_window(self._h, x0, y0, w, h))
@@ -214,23 +231,26 @@ class HipTileDecoder:
         _chk(self._h, lib().yk_decode_prepared_blocks(self._h, C.byref(r), C.byref(t)))
         return int(r.value), int(t.value)
 
-    def _check_windows(self, origins, w, h) -> list:
+    def _check_windows(self, origins, w, h, px: bool = False) -> list:
         """x0, y0 of every window, flat, after the checks of set_window on every one of them (raises before any library call)"""
-        flat, w, h = window_origins(origins, w, h)
+        flat, w, h = window_origins(origins, w, h, px)
         for x0, y0 in zip(flat[::2], flat[1::2]):
             if x0 + w > self.w or y0 + h > self.h:
                 raise ValueError(f"window {(x0, y0, w, h)} is not inside the {self.w} x {self.h} image")
         return flat
 
-    def render_windows(self, origins, w: int, h: int, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
+    def render_windows(self, origins, w: int, h: int, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False, *,
+                       px: bool = False):
         """K = len(origins) windows of w x h of the prepared image, window k at origins[k] = (x0, y0), in ONE call (yk_decode_render_windows_device):
         a torch.uint8 tensor [K, h, w, C], or [K, C, h, w] with planar=True, window k equal to the same slice of the whole decode's
         image_device().  The blocks the windows touch that no earlier call rendered are rendered once, however many windows share them; a call
         that finds none only de-tiles.  channels and alpha are those of image_device (a decoded 'ALPM' plane is read at each window's offset);
         `out` follows the rules of image_batch_device: any view with unit inner stride and any row, plane and window pitch, only its pixel bytes
-        are written.  1..1024 origins; x0, y0, w, h multiples of 8 inside the image: anything else raises before any library call."""
+        are written.  1..1024 origins; x0, y0, w, h multiples of 8 inside the image: anything else raises before any library call.  px=True
+        (yk_decode_render_windows_px_device): any rectangles inside the image, w, h >= 1; the blocks they touch are shared with the
+        aligned and the scaled calls."""
         import torch
-        flat = self._check_windows(origins, w, h)
+        flat = self._check_windows(origins, w, h, px)
         K, ww, wh = len(flat) // 2, int(w), int(h)
         C4 = channels if channels is not None else (4 if self._has_alpha else 3)
         a = (-1 if self._has_alpha else 255) if alpha is None else int(alpha)
@@ -252,17 +272,19 @@ class HipTileDecoder:
         xy = (C.c_int * (2 * K))(*flat)
         cur = torch.cuda.current_stream(dev).cuda_stream
         _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
-        _chk(self._h, L.yk_decode_render_windows_device(self._h, K, xy, ww, wh, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, C4, a))
+        fn = L.yk_decode_render_windows_px_device if px else L.yk_decode_render_windows_device
+        _chk(self._h, fn(self._h, K, xy, ww, wh, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, C4, a))
         _chk(self._h, L.yk_stream_handoff(self._h, cur))
         return out
 
-    def render_window(self, x0: int, y0: int, w: int, h: int, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False):
+    def render_window(self, x0: int, y0: int, w: int, h: int, out=None, channels: int | None = None, alpha: int | None = None, planar: bool = False, *,
+                      px: bool = False):
         """One window of the prepared image: [h, w, C], or [C, h, w] with planar=True (render_windows with one origin; `out` of that shape)."""
-        self._check_windows([(x0, y0)], w, h)
+        self._check_windows([(x0, y0)], w, h, px)
         if out is not None and hasattr(out, "unsqueeze"):
-            self.render_windows([(x0, y0)], w, h, out.unsqueeze(0), channels, alpha, planar)
+            self.render_windows([(x0, y0)], w, h, out.unsqueeze(0), channels, alpha, planar, px=px)
             return out
-        return self.render_windows([(x0, y0)], w, h, out, channels, alpha, planar)[0]
+        return self.render_windows([(x0, y0)], w, h, out, channels, alpha, planar, px=px)[0]
 
     # ---- batches: n images of one shape, every kernel launched once over all of them (yk_decode_begin_batch) --------------------------------
     def begin_batch(self, w: int, h: int, n: int):
@@ -286,14 +308,31 @@ class HipTileDecoder:
         o, w, h = self._batch_windows
         return o.copy(), w, h
 
-    def set_batch_windows(self, origins, w: int, h: int) -> None:
+    @property
+    def batch_window_covers(self):
+        """(origins int32 [N, 2], w, h) of the 8-aligned rectangles the batch chunk calls decode: the windows themselves, or with
+        set_batch_windows(px=True) every frame's cover of one shared size; planes() of a frame is exact inside its cover.  None
+        without windows."""
+        if self._batch_windows is None:
+            return None
+        o, w, h = self._batch_windows
+        if not ((o | w | h) & 7).any():                                    # aligned windows are their own covers
+            return o.copy(), w, h
+        cw, ch = min(self.w, (w + 14) >> 3 << 3), min(self.h, (h + 14) >> 3 << 3)
+        c = o & ~7
+        c[:, 0] = np.minimum(c[:, 0], self.w - cw)
+        c[:, 1] = np.minimum(c[:, 1], self.h - ch)
+        return c.astype(np.int32), cw, ch
+
+    def set_batch_windows(self, origins, w: int, h: int, *, px: bool = False) -> None:
         """From here on the batch decode calls owe frame f only the pixels of the rectangle (origins[f][0], origins[f][1], w, h): the gradient
         render skips the 64x64 blocks of a frame its window does not touch and the 1-D chunk decodes the window's tiles only.  `origins` is an
         [N, 2] integer array or a sequence of N (x0, y0) pairs, N = the frames of the batch.  Call it right after begin_batch(), before any
         chunk is decoded; everything is a multiple of 8 with w, h >= 8 and every rectangle inside the image; w = h = 0 clears the windows.  Read
         the result with image_batch_windows_device(); image_batch_device() and the other whole-frame outputs raise the library's state error
         while windows are set, planes() of a selected frame is exact inside its window only, tile4x4() is whole and exact.  Bad arguments raise
-        before any library call; a handle begun with begin(), or chunks decoded already, are the library's to refuse."""
+        before any library call; a handle begun with begin(), or chunks decoded already, are the library's to refuse.  px=True
+        (yk_decode_set_batch_windows_px): any rectangles inside the image, w, h >= 1; the chunk calls decode batch_window_covers."""
         if isinstance(w, bool) or isinstance(h, bool) or not isinstance(w, (int, np.integer)) or not isinstance(h, (int, np.integer)):
             raise TypeError(f"the window size must be two ints; got {w!r}, {h!r}")
         if int(w) == 0 and int(h) == 0:
@@ -304,12 +343,12 @@ class HipTileDecoder:
             if origins.ndim != 2 or origins.shape[1] != 2 or not np.issubdtype(origins.dtype, np.integer):
                 raise TypeError(f"window origins must be an integer array [N, 2]; got {origins.dtype} {origins.shape}")
             origins = [(int(x), int(y)) for x, y in origins]
-        flat = self._check_windows(origins, w, h)
+        flat = self._check_windows(origins, w, h, px)
         if len(flat) != 2 * self.frames:
             raise ValueError(f"{len(flat) // 2} window origins for a batch of {self.frames} frames")
         xy = (C.c_int * len(flat))(*flat)
         self._batch_windows = None
-        _chk(self._h, lib().yk_decode_set_batch_windows(self._h, xy, int(w), int(h)))
+        _chk(self._h, (lib().yk_decode_set_batch_windows_px if px else lib().yk_decode_set_batch_windows)(self._h, xy, int(w), int(h)))
         self._batch_windows = (np.asarray(flat, dtype=np.int32).reshape(-1, 2), int(w), int(h))
 
     def image_batch_windows_device(self, out=None, channels: int = 3, alpha: int = 255, planar: bool = False, alpha_from_planes: bool = False):
@@ -473,9 +512,9 @@ class HipTileDecoder:
         return frames
 
     def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False, per_frame: bool = False, palette: bool = False,
-                                  alpha_6bit: bool = False, windows=None) -> None:
+                                  alpha_6bit: bool = False, windows=None, *, px: bool = False) -> None:
         """decode_batch_streams of encoder_batch_streams(enc, per_frame); windows=(origins, w, h) first gives every frame its window
-        (set_batch_windows, checked before anything else happens), so that the batch begun just before decodes those rectangles only; alpha=True also runs the encoder's alpha_values_batch and decodes every
+        (set_batch_windows, with px=True pixel windows; checked before anything else happens), so that the batch begun just before decodes those rectangles only; alpha=True also runs the encoder's alpha_values_batch and decodes every
         frame's 'ALPM' payload where the encoder left it in HBM (decompress_alpha_batch; frames without a chunk are opaque).  With sync=False on
         the default path the queued decode reads the encoder's own stream buffer: fence this decoder before the encoder's next encode.
         alpha_6bit=True (with alpha): the alpha goes through the encoder's alpha_bitmaps_device + alpha_mask_payloads_device and
@@ -489,7 +528,7 @@ class HipTileDecoder:
         if windows is not None:
             if not isinstance(windows, (tuple, list)) or len(windows) != 3:
                 raise TypeError(f"windows must be (origins, w, h); got {windows!r}")
-            self.set_batch_windows(*windows)
+            self.set_batch_windows(*windows, px=px)
         if palette:
             if per_frame:
                 raise ValueError("palette=True needs the encoder's stream table (per_frame=False)")

@@ -95,6 +95,12 @@ MULTIWINDOW_SIGNATURES = {
 BATCH_WINDOWS_SIGNATURES = {
     "YAIK_DecodeImagesWindowsToDevice": (C.c_bool, [vp, vp, vp, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int]),
 }
+# yaik_decode_window_px.h: the same library, C linkage; the arguments of the aligned namesakes
+WINDOW_PX_SIGNATURES = {
+    "YAIK_DecodeImageWindowPxToDevice": WINDOW_SIGNATURES["YAIK_DecodeImageWindowToDevice"],
+    "YAIK_DecodeImageWindowsPxToDevice": MULTIWINDOW_SIGNATURES["YAIK_DecodeImageWindowsToDevice"],
+    "YAIK_DecodeImagesWindowsPxToDevice": BATCH_WINDOWS_SIGNATURES["YAIK_DecodeImagesWindowsToDevice"],
+}
 # yaik_decode_scaled.h: the same library, C linkage
 SCALED_SIGNATURES = {
     "YAIK_DecodeImageScaledToDevice": (C.c_bool, [vp, u32, vp, C.c_int]),
@@ -139,7 +145,7 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
-        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **BATCH_WINDOWS_SIGNATURES, **SCALED_SIGNATURES, **MIPCHAIN_SIGNATURES}.items():
+        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **BATCH_WINDOWS_SIGNATURES, **WINDOW_PX_SIGNATURES, **SCALED_SIGNATURES, **MIPCHAIN_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _host = L
@@ -218,25 +224,30 @@ def decode_file_device(stream: bytes):
     return out
 
 
-def _window_of(window) -> tuple:
-    """(x0, y0, ww, wh) as ints: multiples of 8, ww, wh >= 8, not negative (that it lies inside the image is the library's to check)"""
+def _window_of(window, px: bool = False) -> tuple:
+    """(x0, y0, ww, wh) as ints: multiples of 8, ww, wh >= 8, not negative -- with px any x0, y0 >= 0, ww, wh >= 1 (that it lies inside the image
+    is the library's to check)"""
     if isinstance(window, (str, bytes)) or not hasattr(window, "__len__") or len(window) != 4:
         raise TypeError(f"window must be (x0, y0, w, h); got {window!r}")
     if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in window):
         raise TypeError(f"window must hold four ints; got {window!r}")
     x0, y0, ww, wh = (int(v) for v in window)
-    if (x0 | y0 | ww | wh) & 7 or x0 < 0 or y0 < 0 or ww < 8 or wh < 8:
+    if px:
+        if x0 < 0 or y0 < 0 or ww < 1 or wh < 1:
+            raise ValueError(f"window {(x0, y0, ww, wh)}: x0, y0 >= 0 and w, h >= 1 are needed")
+    elif (x0 | y0 | ww | wh) & 7 or x0 < 0 or y0 < 0 or ww < 8 or wh < 8:
         raise ValueError(f"window {(x0, y0, ww, wh)}: x0, y0, w, h must be multiples of 8 with w, h >= 8")
     return x0, y0, ww, wh
 
 
-def decode_file_window_device(stream: bytes, window):
+def decode_file_window_device(stream: bytes, window, *, px: bool = False):
     """The rectangle window = (x0, y0, w, h) of one stream through YAIK_DecodeImageWindowToDevice: a torch.uint8 tensor [h, w, 3] on the GPU, or
     [h, w, 4] when the stream has an 'ALPM' chunk, equal to decode_file_device(stream)[y0:y0 + h, x0:x0 + w]; only the tiles the window needs are
-    rendered.  x0, y0, w, h are multiples of 8 inside the image.  Raises YaikFileError with the library's error code (a window outside the image:
+    rendered.  x0, y0, w, h are multiples of 8 inside the image; with px=True any rectangle inside the image (YAIK_DecodeImageWindowPxToDevice: the
+    window's 8-aligned cover is decoded and the de-tile clips it).  Raises YaikFileError with the library's error code (a window outside the image:
     YAIK_DECIMG_INVALIDCTX)."""
     import torch
-    x0, y0, ww, wh = _window_of(window)
+    x0, y0, ww, wh = _window_of(window, px)
     L, h = host_lib(), library()
     src = _buffer(stream)
     info = DecodedImage()
@@ -247,14 +258,15 @@ def decode_file_window_device(stream: bytes, window):
     out = torch.empty((wh, ww, c), dtype=torch.uint8, device=dev)
     torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
     info.outputImage, info.outputImageStride = out.data_ptr(), ww * c
-    if not L.YAIK_DecodeImageWindowToDevice(src.ctypes.data, src.size, C.byref(info), x0, y0, ww, wh):
+    if not (L.YAIK_DecodeImageWindowPxToDevice if px else L.YAIK_DecodeImageWindowToDevice)(src.ctypes.data, src.size, C.byref(info), x0, y0, ww, wh):
         raise YaikFileError(L.YAIK_GetErrorCode())
     return out
 
 
-def window_origins(origins, w, h) -> tuple:
+def window_origins(origins, w, h, px: bool = False) -> tuple:
     """((x0, y0), ...) and (w, h) as ints, (flat x0, y0 list, w, h): 1..1024 pairs, everything a multiple of 8, w, h >= 8, nothing negative.
-    Shared with HipTileDecoder.render_windows, which adds the image's bounds; here that a window lies inside the image is the library's to check."""
+    Shared with HipTileDecoder.render_windows, which adds the image's bounds; here that a window lies inside the image is the library's to check.
+    px: pixel windows, nothing negative and w, h >= 1 is all that is asked."""
     if isinstance(origins, (str, bytes)) or not hasattr(origins, "__len__"):
         raise TypeError(f"window origins must be a sequence of (x0, y0) pairs; got {origins!r}")
     if not 1 <= len(origins) <= 1024:
@@ -267,19 +279,23 @@ def window_origins(origins, w, h) -> tuple:
     if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in flat + [w, h]):
         raise TypeError(f"window origins and the window size must be ints; got {origins!r}, {w!r}, {h!r}")
     flat, w, h = [int(v) for v in flat], int(w), int(h)
-    if any(v & 7 or v < 0 for v in flat) or (w | h) & 7 or w < 8 or h < 8:
+    if px:
+        if any(v < 0 for v in flat) or w < 1 or h < 1:
+            raise ValueError(f"windows {origins!r} of {w} x {h}: x0, y0 >= 0 and w, h >= 1 are needed")
+    elif any(v & 7 or v < 0 for v in flat) or (w | h) & 7 or w < 8 or h < 8:
         raise ValueError(f"windows {origins!r} of {w} x {h}: x0, y0, w, h must be multiples of 8 with w, h >= 8")
     return flat, w, h
 
 
-def decode_file_windows_device(stream: bytes, origins, w: int, h: int):
+def decode_file_windows_device(stream: bytes, origins, w: int, h: int, *, px: bool = False):
     """K = len(origins) windows of w x h, window k at origins[k] = (x0, y0), of one stream through YAIK_DecodeImageWindowsToDevice: a torch.uint8
     tensor [K, h, w, 3] on the GPU, or [K, h, w, 4] when the stream has an 'ALPM' chunk; window k equals
     decode_file_device(stream)[y0:y0 + h, x0:x0 + w].  The map-sized work of the image runs once and every 64x64 block the windows touch is
-    rendered once (last_windows_prepared() tells whether the stream could take that path).  Raises YaikFileError with the library's error code (a
+    rendered once (last_windows_prepared() tells whether the stream could take that path).  px=True: windows at any pixel offset and size
+    (YAIK_DecodeImageWindowsPxToDevice).  Raises YaikFileError with the library's error code (a
     window outside the image: YAIK_DECIMG_INVALIDCTX)."""
     import torch
-    flat, ww, wh = window_origins(origins, w, h)
+    flat, ww, wh = window_origins(origins, w, h, px)
     k = len(flat) // 2
     L, lh = host_lib(), library()
     src = _buffer(stream)
@@ -292,7 +308,7 @@ def decode_file_windows_device(stream: bytes, origins, w: int, h: int):
     torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
     info.outputImage, info.outputImageStride = out.data_ptr(), ww * c
     xy = (C.c_int * (2 * k))(*flat)
-    if not L.YAIK_DecodeImageWindowsToDevice(src.ctypes.data, src.size, C.byref(info), k, xy, ww, wh, wh * ww * c):
+    if not (L.YAIK_DecodeImageWindowsPxToDevice if px else L.YAIK_DecodeImageWindowsToDevice)(src.ctypes.data, src.size, C.byref(info), k, xy, ww, wh, wh * ww * c):
         raise YaikFileError(L.YAIK_GetErrorCode())
     return out
 
@@ -410,12 +426,13 @@ def decode_files_device(streams, out=None, channels: int = 3, planar: bool = Fal
     return out
 
 
-def decode_files_windows_device(streams, origins, size, out=None, channels: int = 3, planar: bool = False, threads: int = 16):
+def decode_files_windows_device(streams, origins, size, out=None, channels: int = 3, planar: bool = False, threads: int = 16, *, px: bool = False):
     """One window of each of n (1..1024) streams of ONE width x height (YAIK_DecodeImagesWindowsToDevice): origins[f] = (x0, y0) of stream f's
     window, size = (w, h) of every window; a torch.uint8 tensor [N, h, w, C], or [N, C, h, w] with planar=True, on the GPU, frame f equal to
     decode_files_device(streams)[f] cut to its window.  channels, `out` and threads follow decode_files_device, with the windows' size as the
     frame size.  A wrong number of origins, an origin or size that is no multiple of 8 and a wrong `out` raise before any library call; a window
-    outside the image is the library's to refuse (YaikFileError, YAIK_DECIMG_INVALIDCTX; nothing is written)."""
+    outside the image is the library's to refuse (YaikFileError, YAIK_DECIMG_INVALIDCTX; nothing is written).  px=True: windows at any pixel offset
+    and size (YAIK_DecodeImagesWindowsPxToDevice)."""
     import torch
 
     from .encoder import u8_pixel_layout, u8_planar_batch_layout
@@ -429,7 +446,7 @@ def decode_files_windows_device(streams, origins, size, out=None, channels: int 
         raise TypeError(f"size must be (w, h); got {size!r}")
     if isinstance(origins, np.ndarray):
         origins = origins.tolist() if origins.ndim == 2 and np.issubdtype(origins.dtype, np.integer) else origins
-    flat, ww, wh = window_origins(origins, size[0], size[1])
+    flat, ww, wh = window_origins(origins, size[0], size[1], px)
     if len(flat) != 2 * n:
         raise ValueError(f"{len(flat) // 2} window origins for {n} streams")
     L, h = host_lib(), library()
@@ -452,8 +469,8 @@ def decode_files_windows_device(streams, origins, size, out=None, channels: int 
     xy = (C.c_int * (2 * n))(*flat)
     failed = C.c_int32(-1)
     torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
-    ok = L.YAIK_DecodeImagesWindowsToDevice(h, ptrs, lens, n, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels, int(threads),
-                                            C.byref(failed), xy, ww, wh)
+    fn = L.YAIK_DecodeImagesWindowsPxToDevice if px else L.YAIK_DecodeImagesWindowsToDevice
+    ok = fn(h, ptrs, lens, n, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels, int(threads), C.byref(failed), xy, ww, wh)
     if not ok:
         raise YaikFileError(L.YAIK_GetErrorCode(), max(failed.value, 0))
     return out

@@ -6,6 +6,8 @@
 #include "yaik_decode_window.h"
 #include "yaik_decode_multiwindow.h"
 #include "yaik_decode_batch_windows.h"
+#include "yaik_decode_window_px.h"
+#include "../csrc/yk_window_px.h"
 #include "yaik_decode_scaled.h"
 #include "yaik_decode_mipchain.h"
 #include <atomic>
@@ -123,13 +125,14 @@ bool YAIK_DecodeImagePre(YAIK_LIB lib, void* stream, uint32_t length, YAIK_SDeco
 // The chunk state machine shared by YAIK_DecodeImage, YAIK_DecodeImageToDevice and the fallback of YAIK_DecodeImagesToDevice: begins a single
 // image on the slot's handle and runs every chunk up to the terminator; hasAlphaPlane = an 'ALPM' chunk was decoded (pCtx->alphaChannel).
 // window = {x0, y0, ww, wh} (YAIK_DecodeImageWindowToDevice): set on the handle right after the begin, so every chunk may skip what lies outside it
-static bool decodeChunks(Slot* s, const void* stream, uint32_t length, bool& hasAlphaPlane, const int* window = nullptr) {
+static bool decodeChunks(Slot* s, const void* stream, uint32_t length, bool& hasAlphaPlane, const int* window = nullptr, bool px = false) {
     std::vector<uint8_t> bitmap, pal, rgb, types, pix;
     hasAlphaPlane = false;
     {
         const int w = s->width, h = s->height;
         if (yk_decode_begin(s->ctx, w, h) != YK_OK) { setError(YAIK_MALLOC_FAIL); return false; }
-        if (window && yk_decode_set_window(s->ctx, window[0], window[1], window[2], window[3]) != YK_OK) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
+        if (window && (px ? yk_decode_set_window_px(s->ctx, window[0], window[1], window[2], window[3])
+                          : yk_decode_set_window(s->ctx, window[0], window[1], window[2], window[3])) != YK_OK) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
         const uint8_t* p = (const uint8_t*)stream + sizeof(FileHeader);
         const uint8_t* const end = (const uint8_t*)stream + length;
         int state = 0; bool bad = false;
@@ -270,7 +273,8 @@ static bool decodeChunks(Slot* s, const void* stream, uint32_t length, bool& has
 // window (with toDevice): only that rectangle is decoded and written; level (with toDevice, YAIK_DecodeImageScaledToDevice): the output is the
 // image at 1 / (1 << level) size; mip (with toDevice, YAIK_DecodeImageMipchainToDevice): the outputs are the levels of a mip chain, outputImage is unused
 namespace { struct MipRequest { int first, n; void* const* images; const uint32_t* strides; }; }
-static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice, const int* window = nullptr, int level = 0, const MipRequest* mip = nullptr) {
+static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info, bool toDevice, const int* window = nullptr, int level = 0, const MipRequest* mip = nullptr,
+                        bool px = false) {
     if (!info || !info->internalTag || !gLib) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
     Slot* s = (Slot*)info->internalTag;
     bool res = false;
@@ -290,9 +294,10 @@ static bool decodeImage(void* stream, uint32_t length, YAIK_SDecodedImage* info,
             for (int i = 0; ok && i < mip->n; i++) ok = mip->images[i] != nullptr;
             if (!ok) { setError(YAIK_DECIMG_INVALIDCTX); break; }
         }
-        if (window && (((window[0] | window[1] | window[2] | window[3]) & 7) || window[0] < 0 || window[1] < 0 || window[2] < 8 || window[3] < 8 ||
+        if (window && px && !yk_wpx_window_ok(window[0], window[1], window[2], window[3], w, h)) { setError(YAIK_DECIMG_INVALIDCTX); break; }   // a pixel window: any rectangle inside the image
+        if (window && !px && (((window[0] | window[1] | window[2] | window[3]) & 7) || window[0] < 0 || window[1] < 0 || window[2] < 8 || window[3] < 8 ||
                        window[0] > w - window[2] || window[1] > h - window[3])) { setError(YAIK_DECIMG_INVALIDCTX); break; }
-        if (!decodeChunks(s, stream, length, hasAlphaPlane, window)) break;
+        if (!decodeChunks(s, stream, length, hasAlphaPlane, window, px)) break;
         if (customBuilder) {
             // custom builder: hand over the 8x8-tiled planes exactly like the reference (:1303-1318)
             const size_t planeSize = (size_t)(w / 8) * (h / 8) * 64;
@@ -345,6 +350,11 @@ extern "C" bool YAIK_DecodeImageWindowToDevice(void* stream, uint32_t length, YA
     const int window[4] = { x0, y0, ww, wh };
     return decodeImage(stream, length, info, true, window);
 }
+// yaik_decode_window_px.h
+extern "C" bool YAIK_DecodeImageWindowPxToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int x0, int y0, int ww, int wh) {
+    const int window[4] = { x0, y0, ww, wh };
+    return decodeImage(stream, length, info, true, window, 0, nullptr, true);
+}
 extern "C" bool YAIK_DecodeImageScaledToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int level) {
     return decodeImage(stream, length, info, true, nullptr, level);
 }
@@ -376,7 +386,7 @@ void YAIK_LastBatchStageMs(double out[3]) { if (out) for (int i = 0; i < 3; i++)
 // expansion, upload and batch calls; with windows the batch is given them right after yk_decode_begin_batch, the output is the windows' and a
 // fallback stream takes the single-image window chain
 static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
-                         size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh) {
+                         size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh, bool px = false) {
     using namespace yaikplan;
     if (failedIndex) *failedIndex = -1;
     if (!lib || lib != gLib) { setError(YAIK_INVALID_LIBRARYCTX); return false; }
@@ -390,7 +400,9 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
         if (rc == 0 && f == 0) { w = fw; h = fh; }
         if (rc != 0 || fw != w || fh != h) { setError(rc == 1 ? YAIK_INVALID_STREAM : YAIK_INVALID_HEADER); if (failedIndex) *failedIndex = f; return false; }
     }
-    if (xy) {                                                                   // the rule of yk_decode_set_window for every stream, before a slot is taken or a byte written
+    if (xy && px) {                                                             // pixel windows: any rectangle inside the image
+        if (!yk_wpx_windows_ok(n, xy, ww, wh, w, h)) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
+    } else if (xy) {                                                            // the rule of yk_decode_set_window for every stream, before a slot is taken or a byte written
         bool ok = !((ww | wh) & 7) && ww >= 8 && wh >= 8 && ww <= w && wh <= h;
         for (int f = 0; ok && f < n; f++) ok = !((xy[2 * f] | xy[2 * f + 1]) & 7) && xy[2 * f] >= 0 && xy[2 * f + 1] >= 0 && xy[2 * f] <= w - ww && xy[2 * f + 1] <= h - wh;
         if (!ok) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
@@ -488,7 +500,7 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
         const double t2 = nowMs();
         // ---- decode: every kernel once over the n frames; a fallback stream is an empty frame here
         if (yk_decode_begin_batch(s->ctx, w, h, n) != YK_OK) { setError(YAIK_MALLOC_FAIL); break; }
-        if (xy && yk_decode_set_batch_windows(s->ctx, xy, ww, wh) != YK_OK) { setError(YAIK_DECIMG_INVALIDCTX); break; }
+        if (xy && (px ? yk_decode_set_batch_windows_px(s->ctx, xy, ww, wh) : yk_decode_set_batch_windows(s->ctx, xy, ww, wh)) != YK_OK) { setError(YAIK_DECIMG_INVALIDCTX); break; }
         const size_t NP = (size_t)n * NUM_PASSES;
         std::vector<const uint8_t*> bm(NP), rgb(NP, nullptr);
         std::vector<size_t> rgbBytes(NP, 0);
@@ -560,7 +572,7 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
             gBatchFallbacks++;
             bool hasAlphaPlane = false;
             const int window[4] = { xy ? xy[2 * f] : 0, xy ? xy[2 * f + 1] : 0, ww, wh };
-            res = decodeChunks(s, streams[f], lengths[f], hasAlphaPlane, xy ? window : nullptr);
+            res = decodeChunks(s, streams[f], lengths[f], hasAlphaPlane, xy ? window : nullptr, px);
             if (res) {
                 const bool plane = hasAlphaPlane && channels == 4;
                 uint8_t* const dst = devOut + (size_t)f * frameBytes;
@@ -587,12 +599,20 @@ extern "C" bool YAIK_DecodeImagesWindowsToDevice(YAIK_LIB lib, void* const* stre
     return decodeImages(lib, streams, lengths, n, devOut, rowBytes, planeBytes, frameBytes, channels, threads, failedIndex, xy, ww, wh);
 }
 
+// yaik_decode_window_px.h
+extern "C" bool YAIK_DecodeImagesWindowsPxToDevice(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
+                                                   size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh) {
+    if (!xy) { if (failedIndex) *failedIndex = -1; setError(YAIK_DECIMG_INVALIDCTX); return false; }
+    return decodeImages(lib, streams, lengths, n, devOut, rowBytes, planeBytes, frameBytes, channels, threads, failedIndex, xy, ww, wh, true);
+}
+
 // ---- YAIK_DecodeImageWindowsToDevice: many windows of one stream (yaik_decode_multiwindow.h) ------------------------------------------------
 namespace { int gWindowsPrepared = 0; }
 extern "C" int YAIK_LastWindowsPrepared(void) { return gWindowsPrepared; }
 
 // the prepared path for a batchable stream: expand into the slot's staging buffer, one upload, prepare, alpha, one render call
-static bool decodeWindowsPrepared(Slot* s, const yaikplan::StreamPlan& P, uint8_t* devOut, size_t rowBytes, int nWindows, const int* xy, int ww, int wh, size_t windowBytes) {
+static bool decodeWindowsPrepared(Slot* s, const yaikplan::StreamPlan& P, uint8_t* devOut, size_t rowBytes, int nWindows, const int* xy, int ww, int wh, size_t windowBytes,
+                                  bool px) {
     using namespace yaikplan;
     const int w = s->width, h = s->height;
     size_t total = 0;
@@ -653,12 +673,14 @@ static bool decodeWindowsPrepared(Slot* s, const yaikplan::StreamPlan& P, uint8_
     }
     if (yk_decode_prepare_device(s->ctx, n, sx, sy, bm, bmB, col, colB, 0, P.has1d ? D + A.type : nullptr, P.has1d ? P.typeBytes : 0,
                                  P.has1d ? D + A.pix : nullptr, P.has1d ? P.pixBytes : 0, P.has1d ? P.compressionRange : 0) != YK_OK) { setError(YAIK_INVALID_STREAM); return false; }
-    if (yk_decode_render_windows_device(s->ctx, nWindows, xy, ww, wh, devOut, rowBytes, 0, windowBytes, P.hasAlpha ? 4 : 3, -1) != YK_OK ||
+    if ((px ? yk_decode_render_windows_px_device(s->ctx, nWindows, xy, ww, wh, devOut, rowBytes, 0, windowBytes, P.hasAlpha ? 4 : 3, -1)
+            : yk_decode_render_windows_device(s->ctx, nWindows, xy, ww, wh, devOut, rowBytes, 0, windowBytes, P.hasAlpha ? 4 : 3, -1)) != YK_OK ||
         yk_synchronize(s->ctx) != YK_OK) { setError(YAIK_INVALID_STREAM); return false; }
     return true;
 }
 
-extern "C" bool YAIK_DecodeImageWindowsToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int nWindows, const int* xy, int ww, int wh, size_t windowBytes) {
+// YAIK_DecodeImageWindowsToDevice and, with px, YAIK_DecodeImageWindowsPxToDevice (yaik_decode_window_px.h): the same chain under the other rule
+static bool decodeImageWindows(void* stream, uint32_t length, YAIK_SDecodedImage* info, int nWindows, const int* xy, int ww, int wh, size_t windowBytes, bool px) {
     if (!info || !info->internalTag || !gLib) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
     Slot* s = (Slot*)info->internalTag;
     bool res = false;
@@ -669,10 +691,10 @@ extern "C" bool YAIK_DecodeImageWindowsToDevice(void* stream, uint32_t length, Y
         if (s->srcCheck != stream || s->srcLength != length) { setError(YAIK_DECIMG_DIFFSTREAM); break; }
         if (!info->outputImage) { setError(YAIK_DECIMG_BUFFERNOTSET); break; }
         const int w = s->width, h = s->height;
-        bool ok = nWindows >= 1 && nWindows <= 1024 && xy && !((ww | wh) & 7) && ww >= 8 && wh >= 8 && ww <= w && wh <= h && info->outputImageStride > 0 &&
-                  (nWindows == 1 || windowBytes / (size_t)wh >= (size_t)info->outputImageStride);
+        bool ok = nWindows >= 1 && nWindows <= 1024 && xy && (px || !((ww | wh) & 7)) && ww >= (px ? 1 : 8) && wh >= (px ? 1 : 8) && ww <= w && wh <= h &&
+                  info->outputImageStride > 0 && (nWindows == 1 || windowBytes / (size_t)wh >= (size_t)info->outputImageStride);
         for (int k = 0; ok && k < nWindows; k++)
-            ok = !((xy[2 * k] | xy[2 * k + 1]) & 7) && xy[2 * k] >= 0 && xy[2 * k + 1] >= 0 && xy[2 * k] <= w - ww && xy[2 * k + 1] <= h - wh;
+            ok = (px || !((xy[2 * k] | xy[2 * k + 1]) & 7)) && xy[2 * k] >= 0 && xy[2 * k + 1] >= 0 && xy[2 * k] <= w - ww && xy[2 * k + 1] <= h - wh;
         if (!ok) { setError(YAIK_DECIMG_INVALIDCTX); break; }
         const size_t rowBytes = (size_t)info->outputImageStride;
         yaikplan::StreamPlan P;
@@ -680,14 +702,14 @@ extern "C" bool YAIK_DecodeImageWindowsToDevice(void* stream, uint32_t length, Y
             // a 1-D chunk with one empty stream decodes to zeros in the single chain; prepare takes both lengths or none
             if (P.has1d && (!P.typeBytes || !P.pixBytes)) P.has1d = false;
             gWindowsPrepared = 1;
-            res = decodeWindowsPrepared(s, P, info->outputImage, rowBytes, nWindows, xy, ww, wh, windowBytes);
+            res = decodeWindowsPrepared(s, P, info->outputImage, rowBytes, nWindows, xy, ww, wh, windowBytes, px);
             break;
         }
         res = true;
         for (int k = 0; k < nWindows && res; k++) {                                                   // the single-window chain, window after window
             const int window[4] = { xy[2 * k], xy[2 * k + 1], ww, wh };
             bool hasAlphaPlane = false;
-            res = decodeChunks(s, stream, length, hasAlphaPlane, window);
+            res = decodeChunks(s, stream, length, hasAlphaPlane, window, px);
             if (res) {
                 res = yk_decode_output_window_device(s->ctx, info->outputImage + (size_t)k * windowBytes, rowBytes, 0, hasAlphaPlane ? 4 : 3, -1) == YK_OK &&
                       yk_synchronize(s->ctx) == YK_OK;
@@ -698,4 +720,10 @@ extern "C" bool YAIK_DecodeImageWindowsToDevice(void* stream, uint32_t length, Y
     { std::lock_guard<std::mutex> g(gLib->lock); gLib->freeStack.push_back(s); }
     info->internalTag = nullptr;
     return res;
+}
+extern "C" bool YAIK_DecodeImageWindowsToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int nWindows, const int* xy, int ww, int wh, size_t windowBytes) {
+    return decodeImageWindows(stream, length, info, nWindows, xy, ww, wh, windowBytes, false);
+}
+extern "C" bool YAIK_DecodeImageWindowsPxToDevice(void* stream, uint32_t length, YAIK_SDecodedImage* info, int nWindows, const int* xy, int ww, int wh, size_t windowBytes) {
+    return decodeImageWindows(stream, length, info, nWindows, xy, ww, wh, windowBytes, true);
 }
