@@ -810,6 +810,31 @@ int yk_decode_render_windows_px_device(yk_ctx* c, int nWindows, const int* xy, i
                                        uint8_t* devOut, size_t rowBytes, size_t planeBytes, size_t windowBytes, int channels, int alpha);
 int yk_decode_set_batch_windows_px(yk_ctx* c, const int* xy /* nFrames x {x0, y0}, host memory */, int ww, int wh);
 
+/* ---- normalised fp16 / bf16 / fp32 outputs with a per-frame horizontal mirror ----
+ * "Crop - mirror - normalize" in the de-tile store: what the uint8 device outputs write, converted on the way out.  For a decoded byte v (0..255)
+ * of channel k (R, G, B, A = 0..3; alpha is treated like a colour channel, whether it comes from a decoded plane or is the constant)
+ *     f   = fp32_add_rn(fp32_mul_rn((float)v, scale[k]), bias[k])          two roundings, never an fma
+ *     out = f (YK_ELEM_F32), or f rounded to nearest even (YK_ELEM_F16, YK_ELEM_BF16; IEEE overflow to +-inf, fp16 subnormals kept).
+ * scale[k] and bias[k] must be finite and either 0 or of magnitude in [2^-100, 2^100]: then no fp32 intermediate is subnormal or overflows and the
+ * result does not depend on a denormal mode.  mirror != 0 flips horizontally: pixel x of the (cropped) frame goes to column ww - 1 - x.
+ * yk_decode_output_norm_device writes the image begun (or the selected frame of a batch without windows), or the window set on it by
+ * yk_decode_set_window or yk_decode_set_window_px.  yk_decode_output_norm_batch_device writes every frame of a batch, frame f at
+ * devOut + f * frameBytes: whole frames, or each frame's window if yk_decode_set_batch_windows[_px] is set; mirror is NULL (no frame is flipped) or
+ * nFrames flags in host memory, which travel through the pinned ring like the window tables.
+ * Pitches are in BYTES.  channels, alpha (-1 = the decoded plane or planes, 0..255 = a constant byte, which is normalised like any other),
+ * planeBytes == 0 (HWC: element (x, y, k) at y * rowBytes + (x * channels + k) * es) and planeBytes > 0 (CHW: k * planeBytes + y * rowBytes + x * es)
+ * follow the uint8 namesakes, with the pitch-size rules taken against elements of es = sizeof(dtype) bytes.  devOut and every pitch must be
+ * multiples of es.  YK_ERR_BAD_ARG: NULL arguments, a dtype that is none of YK_ELEM_*, parameters outside the rule above, misalignment, pitches too
+ * small, channels / alpha out of range.  YK_ERR_STATE: nothing begun, a prepared image, the single call on a batch with windows, the batch call on
+ * an image with a window, alpha = -1 without valid decoded planes.  Every refusal comes before the first launch, sets yk_last_error, writes nothing
+ * and leaves the handle decoding correctly.  One launch, timed as one YK_STAGE_DEC_DETILE interval; no host synchronisation.  Only pixel elements
+ * are written: padding keeps what it held.  No other call changes what it accepts, refuses or launches. */
+enum { YK_ELEM_F16 = 1, YK_ELEM_BF16 = 2, YK_ELEM_F32 = 3 };
+typedef struct yk_norm { int32_t dtype; float scale[4]; float bias[4]; } yk_norm;
+int yk_decode_output_norm_device(yk_ctx* c, const yk_norm* norm, int mirror, void* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha);
+int yk_decode_output_norm_batch_device(yk_ctx* c, const yk_norm* norm, const uint8_t* mirror /* nFrames, host memory, or NULL */, void* devOut,
+                                       size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha);
+
 /* ---- round-trip quality (new): what the decode holds against a source image, both in HBM -----------------------------------------
  * The codec is lossy; these calls say how lossy a round trip was without moving a pixel to the host.  One kernel reads the decoder's 8x8-tiled
  * planes (and, with four channels, the decoded 'ALPM' plane) and the source where it lies, a second one folds the workgroups' records; per frame

@@ -329,6 +329,8 @@ struct yk_ctx {
     // is the pixel rectangle the output call writes: dPx{X,Y} the single image's origin, dPx{W,H} the size (of every frame's window in a batch, whose
     // per-frame offsets into the cover lie in dBWinTab behind the rectangles, at int 4 * dFrames)
     bool dPxSet = false; int dPxX = 0, dPxY = 0, dPxW = 0, dPxH = 0;
+    // yk_decode_output_norm_batch_device: the per-frame mirror flags in HBM: 1024 entries, allocated once, written through the pinned ring
+    YkBuf<uint32_t> dNormTab;
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
     // yk_decode_prepare_device: the map-sized work of this image is done and what a render needs is kept in dPrep (yk_decode.hip) until the next
     // yk_decode_begin[_batch]; the buffers in dPrep are grow-only and go with the handle (yk_dec_prepared_free)

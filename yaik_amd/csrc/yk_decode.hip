@@ -15,6 +15,7 @@
 #include "yk_device.h"
 #include "yk_window_blocks.h"
 #include "yk_window_px.h"
+#include "yk_window_mirror.h"
 
 struct DPassGeo { int sx, sy, bigX, bigY, bitCount, xBB, tilesPerRow; };
 
@@ -1174,6 +1175,146 @@ static void yk_dt_each(int channels, bool planar, bool fromPlane, F f) {
     if (channels == 3) { if (planar) f(YkDtTag<3, true, YK_DT_ALPHA_NONE>{}); else f(YkDtTag<3, false, YK_DT_ALPHA_NONE>{}); }
     else if (fromPlane) { if (planar) f(YkDtTag<4, true, YK_DT_ALPHA_PLANE>{}); else f(YkDtTag<4, false, YK_DT_ALPHA_PLANE>{}); }
     else { if (planar) f(YkDtTag<4, true, YK_DT_ALPHA_CONST>{}); else f(YkDtTag<4, false, YK_DT_ALPHA_CONST>{}); }
+}
+
+// ---- the normalising form: fp16 / bf16 / fp32 elements, per-frame mirror (yk_decode_output_norm_device and its kin) ------------------
+// The clipping forms above with another store: the same lanes, units, steps and loads, the alpha plane read at the cover's offset.  One kernel form
+// serves every call: the per-frame cover and clip of yk_dec_detile_batch_win_px_kernel, where a whole frame is a cover at (0, 0) with ww x wh = w x h,
+// an aligned window a cover with offset (0, 0) and a single image a batch of one; the cover, the offset and the mirror flag come from tables in HBM
+// where the call has them and from the arguments where it has not.  Every decoded byte v of channel k becomes
+//     f = fp32_add_rn(fp32_mul_rn((float)v, scale[k]), bias[k])          two roundings: contraction is off in yk_dn_value
+// stored as fp32, or rounded to nearest even to fp16 / bf16 (the casts below; gfx950 has v_cvt_pk_bf16_f32).  A mirrored row segment is reversed in
+// registers (column c -> 7 - c: the two dwords of a plane swapped and byte-reversed) and stored at the mirrored address yk_wpx_clip_mirror gives, so
+// everything after the reversal is the unmirrored path.  A whole segment is one run of 8 C elements (HWC) or 8 elements per plane (CHW), stored
+// through byte pointers like yk_dt_emit: 16-byte stores wherever the count allows (fp16 CHW row: one dwordx4; fp32 HWC4: eight).  A cut segment
+// is stored pixel by pixel.  Pitches are in bytes and multiples of the element size.
+struct YkDetileNorm {
+    float scale[4], bias[4];
+    uint32_t cx0, cy0;                                // the cover's origin in the planes (pixels, multiples of 8) where no table gives it
+    int dx, dy, ww, wh;                               // the window inside the cover (dx, dy where no table gives them) and its size
+    uint32_t mirror;                                  // where no table gives it
+};
+template <int E> struct YkNormElem;
+template <> struct YkNormElem<YK_ELEM_F16> { typedef _Float16 T; };
+template <> struct YkNormElem<YK_ELEM_BF16> { typedef __bf16 T; };
+template <> struct YkNormElem<YK_ELEM_F32> { typedef float T; };
+
+template <class T>
+__device__ __forceinline__ T yk_dn_value(uint32_t word, int byte, float scale, float bias) {
+#pragma clang fp contract(off)
+    const float v = (float)((word >> (8 * byte)) & 255u);
+    const float m = v * scale;
+    const float f = m + bias;
+    return (T)f;
+}
+// a whole row segment (lo, hi: the dwords of each plane, already reversed if mirrored) -> 8 pixels from o on
+template <class T, int C, bool PLANAR>
+__device__ __forceinline__ void yk_dn_emit(uint8_t* o, size_t planeBytes, const YkDetileNorm& nm, const uint32_t (&lo)[4], const uint32_t (&hi)[4]) {
+    if constexpr (PLANAR) {
+#pragma unroll
+        for (int k = 0; k < C; k++) {
+            T e[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) e[i] = yk_dn_value<T>(i < 4 ? lo[k] : hi[k], i & 3, nm.scale[k], nm.bias[k]);
+            __builtin_memcpy(o + (size_t)k * planeBytes, e, sizeof(e));
+        }
+    } else {
+        T e[8 * C];
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+#pragma unroll
+            for (int k = 0; k < C; k++) e[i * C + k] = yk_dn_value<T>(i < 4 ? lo[k] : hi[k], i & 3, nm.scale[k], nm.bias[k]);
+        __builtin_memcpy(o, e, sizeof(e));
+    }
+}
+// columns src0 .. src0 + n - 1 (n < 8) of a row segment -> n pixels from o on, a predicated store (or C of them, CHW) per pixel
+template <class T, int C, bool PLANAR>
+__device__ __forceinline__ void yk_dn_emit_px(uint8_t* o, size_t planeBytes, const YkDetileNorm& nm, int src0, int n, const uint32_t (&lo)[4], const uint32_t (&hi)[4]) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        if (i < src0 || i >= src0 + n) continue;
+        T e[C];
+#pragma unroll
+        for (int k = 0; k < C; k++) e[k] = yk_dn_value<T>(i < 4 ? lo[k] : hi[k], i & 3, nm.scale[k], nm.bias[k]);
+        if constexpr (PLANAR) {
+#pragma unroll
+            for (int k = 0; k < C; k++) __builtin_memcpy(o + (size_t)k * planeBytes + (size_t)(i - src0) * sizeof(T), &e[k], sizeof(T));
+        } else {
+            __builtin_memcpy(o + (size_t)(i - src0) * (C * sizeof(T)), e, sizeof(e));
+        }
+    }
+}
+// the two rows of cover tile (jx, jy) this lane holds, clipped against the window, mirrored if asked, converted
+template <int E, int C, bool PLANAR, int ASRC>
+__device__ __forceinline__ void yk_dn_store(const YkDetileArgs& a, const YkDetileNorm& nm, const YkDtUnit& u, uint32_t jx, uint32_t jy, uint32_t rp) {
+    typedef typename YkNormElem<E>::T T;
+    const YkPxMirrorClip kx = yk_wpx_clip_mirror((int)jx, nm.dx, nm.ww, (int)nm.mirror);
+    const YkPxClip ky = yk_wpx_clip((int)jy, nm.dy, nm.wh);
+    if (kx.n == 0 || ky.n == 0) return;
+    const int src0 = yk_wpx_mirror_src0(kx, (int)nm.mirror);
+    uint32_t al[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) al[i] = ASRC == YK_DT_ALPHA_PLANE ? u.a[i] : a.alphaConst;
+    const uint32_t pl[4][4] = { { u.r.x, u.r.y, u.r.z, u.r.w }, { u.g.x, u.g.y, u.g.z, u.g.w }, { u.b.x, u.b.y, u.b.z, u.b.w }, { al[0], al[1], al[2], al[3] } };
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int row = (int)rp * 2 + i;                                      // of the tile
+        if (row < ky.src0 || row >= ky.src0 + ky.n) continue;
+        uint32_t lo[4], hi[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t l = pl[k][2 * i], h = pl[k][2 * i + 1];
+            lo[k] = nm.mirror ? __builtin_bswap32(h) : l;
+            hi[k] = nm.mirror ? __builtin_bswap32(l) : h;
+        }
+        uint8_t* o = a.out + (size_t)(ky.dst + row - ky.src0) * a.rowBytes + (size_t)kx.dst * ((PLANAR ? 1 : C) * sizeof(T));
+        if (kx.n == 8) yk_dn_emit<T, C, PLANAR>(o, a.planeBytes, nm, lo, hi);
+        else yk_dn_emit_px<T, C, PLANAR>(o, a.planeBytes, nm, src0, kx.n, lo, hi);
+    }
+}
+// frame blockIdx.y of nFrames: its cover from wins[f] (or nm.cx0, nm.cy0), the window's offset inside it from off[2f], off[2f + 1] (or nm.dx, nm.dy),
+// its mirror flag from mirror[f] (or nm.mirror); a.nTiles = the cover's wtW x wtH tiles; a.alpha (YK_DT_ALPHA_PLANE) is frame 0's whole plane
+template <int E, int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(YK_DT_THREADS) void yk_dec_detile_norm_kernel(YkDetileArgs a, YkDetileNorm nm, const DWinRect* __restrict__ wins, const int* __restrict__ off,
+                                                                           const uint32_t* __restrict__ mirror, uint32_t wtW, size_t planesFrame, size_t outFrame,
+                                                                           size_t alphaFrame) {
+    const uint32_t f = blockIdx.y;
+    if (wins) { nm.cx0 = (uint32_t)wins[f].x0; nm.cy0 = (uint32_t)wins[f].y0; }
+    if (off) { nm.dx = off[2 * f]; nm.dy = off[2 * f + 1]; }
+    if (mirror) nm.mirror = mirror[f];
+    a.planes += (size_t)f * planesFrame; a.out += (size_t)f * outFrame;
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) a.alpha += (size_t)f * alphaFrame + (size_t)nm.cy0 * a.strideA + nm.cx0;
+    const YkDetileWin wn = { nm.cx0 >> 3, nm.cy0 >> 3, wtW };
+    const uint32_t bx = blockIdx.x, lane = threadIdx.x & 63, rp = lane & 3;
+    const uint32_t j0 = (bx * (YK_DT_K * 4) + (threadIdx.x >> 6)) * 16 + (lane >> 2);
+    if ((bx + 1) * (uint32_t)YK_DT_TILES <= a.nTiles) {
+        YkDtUnit u[YK_DT_K];                                                  // every unit of the workgroup exists: all loads first
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) yk_dt_load_win<C, PLANAR, ASRC>(a, wn, j0 + k * 64, rp, u[k]);
+#pragma unroll
+        for (int k = 0; k < YK_DT_K; k++) {
+            const uint32_t j = j0 + k * 64, jy = j / wn.wtW;
+            yk_dn_store<E, C, PLANAR, ASRC>(a, nm, u[k], j - jy * wn.wtW, jy, rp);
+        }
+        return;
+    }
+    for (int k = 0; k < YK_DT_K; k++) {
+        const uint32_t j = j0 + k * 64, jy = j / wn.wtW;
+        if (j >= a.nTiles) continue;
+        YkDtUnit u;
+        yk_dt_load_win<C, PLANAR, ASRC>(a, wn, j, rp, u);
+        yk_dn_store<E, C, PLANAR, ASRC>(a, nm, u, j - jy * wn.wtW, jy, rp);
+    }
+}
+template <int E>
+static void yk_dn_launch(const YkDetileArgs& a, const YkDetileNorm& nm, hipStream_t s, int channels, bool planar, bool fromPlane, int nFrames, const DWinRect* wins,
+                         const int* off, const uint32_t* mirror, uint32_t wtW, size_t planesFrame, size_t outFrame, size_t alphaFrame) {
+    const unsigned gx = (a.nTiles + YK_DT_TILES - 1) / YK_DT_TILES;
+    yk_dt_each(channels, planar, fromPlane, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((yk_dec_detile_norm_kernel<E, T::c, T::planar, T::asrc>), dim3(gx, (unsigned)nFrames), dim3(YK_DT_THREADS), 0, s, a, nm, wins, off, mirror, wtW,
+                           planesFrame, outFrame, alphaFrame);
+    });
 }
 
 // nFrames == 0: the selected frame (the existing single-image launch); otherwise nFrames frames, planesFrame / outFrame bytes apart
@@ -2475,6 +2616,78 @@ int yk_decode_output_batch_windows_device(yk_ctx* c, uint8_t* devOut, size_t row
     else                 { if (planar) yk_dt_launch_batch_win<4, true, YK_DT_ALPHA_CONST>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); else yk_dt_launch_batch_win<4, false, YK_DT_ALPHA_CONST>(a, c->stream, N, wins, wtW, pf, frameBytes, 0); }
     YK_HIP(c, hipGetLastError());
     return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+}
+
+// ---- normalised outputs (include/yaik_hip.h): both entry points, every check before anything is queued, then one launch ------------
+static int yk_dec_output_norm(yk_ctx* c, const char* name, const yk_norm* nrm, int mirrorOne, const uint8_t* mirrorTab, void* devOut, size_t rowBytes, size_t planeBytes,
+                              size_t frameBytes, int channels, int alpha, bool batch) {
+    auto refuse = [&](int code, const char* what) { return yk_refuse(c, code, (std::string(name) + ": " + what).c_str()); };
+    if (!nrm) return refuse(YK_ERR_BAD_ARG, "norm is NULL");
+    if (!devOut) return refuse(YK_ERR_BAD_ARG, "devOut is NULL");
+    if (nrm->dtype != YK_ELEM_F16 && nrm->dtype != YK_ELEM_BF16 && nrm->dtype != YK_ELEM_F32) return refuse(YK_ERR_BAD_ARG, "dtype must be YK_ELEM_F16, YK_ELEM_BF16 or YK_ELEM_F32");
+    for (int k = 0; k < 4; k++)
+        if (!yk_norm_param_ok(nrm->scale[k]) || !yk_norm_param_ok(nrm->bias[k]))
+            return refuse(YK_ERR_BAD_ARG, "every scale and bias must be finite and 0 or of magnitude in [2^-100, 2^100]");
+    if (channels != 3 && channels != 4) return refuse(YK_ERR_BAD_ARG, "channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255)) return refuse(YK_ERR_BAD_ARG, "alpha must be -1 (the decoded plane) or 0..255");
+    const size_t es = nrm->dtype == YK_ELEM_F32 ? 4 : 2;
+    if (((uintptr_t)devOut | rowBytes | planeBytes | (batch ? frameBytes : 0)) & (es - 1)) return refuse(YK_ERR_BAD_ARG, "devOut and every pitch must be multiples of the element size");
+    if (!yk_dec_begun(c)) return refuse(YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
+    if (c->dPrepared) return refuse(YK_ERR_STATE, "this image is prepared for windows (yk_decode_prepare_device), which have no normalised output");
+    if (!batch && c->dBWinSet) return refuse(YK_ERR_STATE, "windows are set on this batch (yk_decode_set_batch_windows): yk_decode_output_norm_batch_device writes them");
+    if (batch && c->dWinSet) return refuse(YK_ERR_STATE, "a window is set on this image (yk_decode_set_window): yk_decode_output_norm_device writes it");
+    const bool fromPlane = channels == 4 && alpha < 0;
+    if (fromPlane && (!c->dAlphaValid || (batch && !c->dAlphaBatch)))
+        return refuse(YK_ERR_STATE, batch ? "alpha = -1 needs yk_decode_alpha_batch_device first: the batch has no decoded alpha planes" : "alpha = -1 needs yk_decode_alpha first");
+    // what is written, and the cover whose tiles the kernel walks
+    const bool bwin = batch && c->dBWinSet, win = !batch && c->dWinSet, px = (bwin || win) && c->dPxSet;
+    const int cw = bwin ? c->dBWinW : win ? c->dWinW : c->dw, ch = bwin ? c->dBWinH : win ? c->dWinH : c->dh;
+    const size_t w = (size_t)(px ? c->dPxW : cw), h = (size_t)(px ? c->dPxH : ch);
+    if (planeBytes == 0 ? rowBytes / es < w * (size_t)channels : (rowBytes / es < w || planeBytes / h < rowBytes))
+        return refuse(YK_ERR_BAD_ARG, "row or plane pitch too small for what is written");
+    const int N = batch ? c->dFrames : 1;
+    if (N > 1 && (planeBytes == 0 ? frameBytes / h < rowBytes : frameBytes / (size_t)channels < planeBytes)) return refuse(YK_ERR_BAD_ARG, "frame stride too small for a frame");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    const uint32_t* devMirror = nullptr;
+    if (batch && mirrorTab) {                                                 // the flags through the pinned ring, behind the kernels of an earlier call
+        YK_HIP(c, c->dNormTab.reserve(c->stream, 1024));
+        int slot; void* host;
+        { const int rc = yk_dec_table_host(c, (size_t)N * sizeof(uint32_t), &slot, &host); if (rc) return rc; }
+        for (int f = 0; f < N; f++) static_cast<uint32_t*>(host)[f] = mirrorTab[f] ? 1u : 0u;
+        { const int rc = yk_dec_table_upload(c, slot, c->dNormTab.p, (size_t)N * sizeof(uint32_t)); if (rc) return rc; }
+        devMirror = c->dNormTab.p;
+    }
+    YkDetileArgs a;
+    a.planes = batch ? c->dB.planes : yk_dec_frame(c, c->dCur).planes; a.planeSize = c->dPlaneSize;
+    a.alpha = fromPlane ? (batch ? (const uint8_t*)c->dAlpha : yk_dec_alpha_cur(c)) : nullptr; a.strideA = (size_t)c->dw;
+    a.alphaConst = (uint32_t)((fromPlane ? 0 : alpha) & 255) * 0x01010101u;
+    a.out = static_cast<uint8_t*>(devOut); a.rowBytes = rowBytes; a.planeBytes = planeBytes;
+    a.tileW = (uint32_t)(c->dw >> 3); a.nTiles = (uint32_t)(cw >> 3) * (uint32_t)(ch >> 3);
+    YkDetileNorm nm;
+    for (int k = 0; k < 4; k++) { nm.scale[k] = nrm->scale[k]; nm.bias[k] = nrm->bias[k]; }
+    nm.cx0 = win ? (uint32_t)c->dWinX : 0; nm.cy0 = win ? (uint32_t)c->dWinY : 0;
+    nm.dx = win && px ? c->dPxX - c->dWinX : 0; nm.dy = win && px ? c->dPxY - c->dWinY : 0;
+    nm.ww = (int)w; nm.wh = (int)h; nm.mirror = !batch && mirrorOne ? 1u : 0u;
+    const DWinRect* wins = bwin ? yk_dec_bwin_tab(c) : nullptr;
+    const int* off = bwin && px ? c->dBWinTab.p + 4 * (size_t)N : nullptr;
+    const size_t pf = batch ? c->dStride.planes : 0, af = batch && fromPlane ? c->dAlphaStride : 0;
+    const bool planar = planeBytes > 0;
+    { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    if (nrm->dtype == YK_ELEM_F16) yk_dn_launch<YK_ELEM_F16>(a, nm, c->stream, channels, planar, fromPlane, N, wins, off, devMirror, (uint32_t)(cw >> 3), pf, frameBytes, af);
+    else if (nrm->dtype == YK_ELEM_BF16) yk_dn_launch<YK_ELEM_BF16>(a, nm, c->stream, channels, planar, fromPlane, N, wins, off, devMirror, (uint32_t)(cw >> 3), pf, frameBytes, af);
+    else yk_dn_launch<YK_ELEM_F32>(a, nm, c->stream, channels, planar, fromPlane, N, wins, off, devMirror, (uint32_t)(cw >> 3), pf, frameBytes, af);
+    YK_HIP(c, hipGetLastError());
+    return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+}
+int yk_decode_output_norm_device(yk_ctx* c, const yk_norm* norm, int mirror, void* devOut, size_t rowBytes, size_t planeBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    return yk_dec_output_norm(c, "yk_decode_output_norm_device", norm, mirror, nullptr, devOut, rowBytes, planeBytes, 0, channels, alpha, false);
+}
+int yk_decode_output_norm_batch_device(yk_ctx* c, const yk_norm* norm, const uint8_t* mirror, void* devOut, size_t rowBytes, size_t planeBytes, size_t frameBytes,
+                                       int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    return yk_dec_output_norm(c, "yk_decode_output_norm_batch_device", norm, 0, mirror, devOut, rowBytes, planeBytes, frameBytes, channels, alpha, true);
 }
 
 // ---- outputs at reduced resolution (include/yaik_hip.h): level 0 is the full-size call, 1..3 the box means of 2x2, 4x4, 8x8 ----------

@@ -12,7 +12,7 @@ from typing import NamedTuple
 import numpy as np
 
 from ._lib import YaikError, lib
-from .encoder import PASSES, _chk, u8_pixel_layout, u8_planar_batch_layout, u8_planar_layout
+from .encoder import PASSES, NormC, _chk, elem_layout, mirror_flags, norm_params, norm_struct, u8_pixel_layout, u8_planar_batch_layout, u8_planar_layout  # noqa: F401  (norm_params: public here)
 from .files import window_origins
 
 
@@ -738,6 +738,92 @@ class HipTileDecoder:
             _chk(self._h, L.yk_decode_output_batch_alpha_device(self._h, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes))
         else:
             _chk(self._h, L.yk_decode_output_batch_device(self._h, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels, int(alpha)))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
+
+    # ---- normalised fp16 / bf16 / fp32 outputs with a per-frame mirror, converted in the de-tile store (yk_decode_output_norm_device) ----
+    @staticmethod
+    def _norm_args(dtype, scale, bias, mean, std) -> NormC:
+        """dtype and the affine pair as the library's yk_norm; every check raises before any library call"""
+        return norm_struct(dtype, scale, bias, mean, std)
+
+    def image_norm_device(self, dtype, scale=None, bias=None, mean=None, std=None, mirror: bool = False, out=None, channels: int | None = None,
+                          alpha: int | None = None, planar: bool = False):
+        """What image_window_device() writes -- the image begun, or the window set on it by set_window (aligned or px=True) -- as a
+        torch.float16 / bfloat16 / float32 tensor [h, w, C], or [C, h, w] with planar=True (yk_decode_output_norm_device, one launch, no uint8
+        intermediate).  Every decoded byte v of channel k becomes fp32(v) * scale[k], then + bias[k] (two fp32 roundings, never an fma), kept
+        as fp32 or rounded to nearest even; alpha counts as channel 3 whether it is the decoded plane or a constant.  scale / bias: a scalar
+        for every channel, or 3 or 4 values (three leave alpha at 1, 0); finite and 0 or of magnitude in [2^-100, 2^100].  mean / std instead
+        go through norm_params(); giving both pairs raises.  mirror=True flips horizontally: pixel x lands at column w - 1 - x.  channels,
+        alpha, `out` (any view of `dtype` with unit inner stride and any pitch: elem_layout) and the stream hand-over follow image_device."""
+        import torch
+        nrm = self._norm_args(dtype, scale, bias, mean, std)
+        window = self._window
+        ww, wh = (window[2], window[3]) if window is not None else (self.w, self.h)
+        C4 = channels if channels is not None else (4 if self._has_alpha else 3)
+        if C4 not in (3, 4):
+            raise ValueError("channels must be 3 or 4")
+        a = (-1 if self._has_alpha else 255) if alpha is None else int(alpha)
+        if not -1 <= a <= 255:
+            raise ValueError(f"alpha must be None or 0..255; got {alpha!r}")
+        dev = torch.device("cuda", self.device)
+        tdt = getattr(torch, str(dtype).replace("torch.", ""))
+        if out is None:
+            out = torch.empty((C4, wh, ww) if planar else (wh, ww, C4), dtype=tdt, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        elif out.dtype != tdt:
+            raise TypeError(f"out has dtype {out.dtype}, the call asks for {tdt}")
+        lay = elem_layout(out, planar=planar)
+        shape = (lay.channels, lay.rows, lay.w) if planar else (lay.rows, lay.w, lay.channels)
+        want = (C4, wh, ww) if planar else (wh, ww, C4)
+        if shape != want:
+            raise ValueError(f"out has shape {shape}, the {'window' if window is not None else 'image'} needs {want}")
+        L = lib()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_output_norm_device(self._h, C.byref(nrm), 1 if mirror else 0, out.data_ptr(), lay.row_bytes, lay.plane_bytes, C4, a))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
+
+    def image_norm_batch_device(self, dtype, scale=None, bias=None, mean=None, std=None, mirror=None, out=None, channels: int = 3, alpha: int = 255,
+                                planar: bool = False, alpha_from_planes: bool = False):
+        """image_norm_device for every frame of the batch in one launch (yk_decode_output_norm_batch_device): whole frames, or each frame's window
+        if set_batch_windows (aligned or px=True) is set; [N, h, w, C], or [N, C, h, w] with planar=True.  mirror: None (no frame is flipped), or
+        a sequence or bool tensor of N flags, one per frame.  channels, alpha, alpha_from_planes and `out` follow image_batch_windows_device, and
+        so does the ordering against torch's current stream: no host fence."""
+        import torch
+        nrm = self._norm_args(dtype, scale, bias, mean, std)
+        if channels not in (3, 4):
+            raise ValueError("channels must be 3 or 4")
+        if alpha_from_planes and channels != 4:
+            raise ValueError("alpha_from_planes needs channels=4")
+        if not alpha_from_planes and not 0 <= int(alpha) <= 255:
+            raise ValueError(f"alpha must be 0..255; got {alpha!r}")
+        N = self.frames
+        flags = mirror_flags(mirror, N)
+        if self._batch_windows is not None:
+            _, ww, wh = self._batch_windows
+        else:
+            ww, wh = self.w, self.h
+        dev = torch.device("cuda", self.device)
+        tdt = getattr(torch, str(dtype).replace("torch.", ""))
+        if out is None:
+            out = torch.empty((N, channels, wh, ww) if planar else (N, wh, ww, channels), dtype=tdt, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        elif out.dtype != tdt:
+            raise TypeError(f"out has dtype {out.dtype}, the call asks for {tdt}")
+        lay = elem_layout(out, planar=planar, batch=True)
+        shape = (lay.frames, lay.channels, lay.rows, lay.w) if planar else (lay.frames, lay.rows, lay.w, lay.channels)
+        want = (N, channels, wh, ww) if planar else (N, wh, ww, channels)
+        if shape != want:
+            raise ValueError(f"out has shape {shape}, the batch needs {want}")
+        L = lib()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_output_norm_batch_device(self._h, C.byref(nrm), None if flags is None else flags.ctypes.data, out.data_ptr(), lay.row_bytes,
+                                                           lay.plane_bytes, lay.frame_bytes, channels, -1 if alpha_from_planes else int(alpha)))
         _chk(self._h, L.yk_stream_handoff(self._h, cur))
         return out
 

@@ -143,6 +143,124 @@ def u8_planar_batch_layout(pixels) -> PlanarBatchLayout:
     return PlanarBatchLayout(frames, lay.channels, lay.rows, lay.w, lay.row_bytes, lay.plane_bytes, frame_bytes)
 
 
+class ElemLayout(NamedTuple):
+    """How the normalised outputs (yk_decode_output_norm_device and its batch form) write a float16 / bfloat16 / float32 tensor: elem_layout.
+    Every pitch is in BYTES and a multiple of elem_bytes."""
+    dtype: int              # YK_ELEM_F16 = 1, YK_ELEM_BF16 = 2, YK_ELEM_F32 = 3
+    elem_bytes: int
+    frames: int
+    channels: int
+    rows: int
+    w: int
+    row_bytes: int
+    plane_bytes: int        # 0: interleaved [rows, w, C]
+    frame_bytes: int        # a whole frame's bytes for a single image, where the library ignores it
+
+
+ELEM_DTYPES = {"float16": (1, 2), "bfloat16": (2, 2), "float32": (3, 4)}          # name -> (YK_ELEM_*, bytes)
+
+
+def elem_layout(pixels, planar: bool = False, batch: bool = False) -> ElemLayout:
+    """Layout of a torch (or, for float16 / float32, numpy) tensor [rows, w, C], or [C, rows, w] with planar=True, with a leading frame axis if
+    batch=True; C = 3 or 4; dtype float16, bfloat16 or float32.  The element-size-aware sibling of u8_pixel_layout, u8_planar_layout and
+    u8_planar_batch_layout: pitches are the tensor's own strides times the element size, so padded or sliced views need no copy; the elements
+    of a row must be contiguous (inner stride 1, and pixel stride C when interleaved), and rows, planes and frames may not overlap.  Reads
+    only dtype, shape and strides."""
+    name = str(pixels.dtype).replace("torch.", "")
+    if name not in ELEM_DTYPES:
+        raise TypeError(f"float16, bfloat16 or float32 elements expected, got {pixels.dtype}")
+    code, es = ELEM_DTYPES[name]
+    if hasattr(pixels, "data_ptr"):
+        shape, strides = tuple(pixels.shape), tuple(pixels.stride())      # in elements
+    else:
+        shape, strides = tuple(pixels.shape), tuple(s // es for s in pixels.strides)
+    what = ("F, " if batch else "") + ("C, rows, w" if planar else "rows, w, C")
+    if len(shape) != (4 if batch else 3):
+        raise ValueError(f"pixels must be [{what}], got shape {shape}")
+    if batch and shape[0] < 1:
+        raise ValueError("a batch holds at least one frame")
+    if planar:
+        ch, rows, w = shape[-3:]
+        inner_ok, row, plane = strides[-1] == 1, strides[-2], strides[-3]
+    else:
+        rows, w, ch = shape[-3:]
+        inner_ok, row, plane = strides[-1] == 1 and strides[-2] == ch, strides[-3], 0
+    if ch not in (3, 4):
+        raise ValueError(f"C must be 3 (RGB) or 4 (RGBA); got C = {ch}")
+    if not inner_ok:
+        raise ValueError(f"the elements of a row must be contiguous (inner stride 1{'' if planar else f', pixel stride {ch}'}); got strides {strides}")
+    if row < w * (1 if planar else ch):
+        raise ValueError(f"row stride {row} is shorter than a row of {w * (1 if planar else ch)} elements")
+    if planar and plane < rows * row:
+        raise ValueError(f"plane stride {plane} is shorter than a plane of {rows * row} elements")
+    whole = ch * plane if planar else rows * row
+    frames, frame = (shape[0], strides[0] if shape[0] > 1 else whole) if batch else (1, whole)
+    if frame < whole:
+        raise ValueError(f"frame stride {frame} is shorter than a frame of {whole} elements")
+    return ElemLayout(code, es, frames, ch, rows, w, row * es, plane * es, frame * es)
+
+
+def norm_params(mean, std):
+    """(scale, bias) as float32 arrays of four for the normalised outputs from a per-channel mean and std (scalars, or sequences of 3 or 4 in the
+    units of the decoded bytes, 0..255): scale = fp32(1 / std), bias = fp32(-mean / std), both computed in float64 and rounded once.  Three
+    values leave alpha at scale 1, bias 0.  The bit-exact contract of the outputs is on scale and bias; this is the convenience in front of it."""
+    def four(v, fill, what):
+        a = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        if a.ndim != 1 or a.size not in (1, 3, 4):
+            raise ValueError(f"{what} must be a scalar or 3 or 4 values; got shape {a.shape}")
+        return np.full(4, a[0]) if a.size == 1 else np.concatenate([a, np.full(4 - a.size, fill)])
+    m, s = four(mean, 0.0, "mean"), four(std, 1.0, "std")
+    if not np.all(np.isfinite(m)) or not np.all(np.isfinite(s)) or np.any(s == 0):
+        raise ValueError(f"mean and std must be finite and std non-zero; got {mean!r}, {std!r}")
+    return (1.0 / s).astype(np.float32), (-m / s).astype(np.float32)
+
+
+def check_norm(scale, bias):
+    """scale and bias of a normalised output as float32 arrays of four (a scalar serves every channel, three values leave alpha at 1, 0), checked
+    against the library's rule before any library call: finite, and 0 or of magnitude in [2^-100, 2^100]."""
+    out = []
+    for v, fill, what in ((scale, 1.0, "scale"), (bias, 0.0, "bias")):
+        a = np.atleast_1d(np.asarray(v, dtype=np.float32))
+        if a.ndim != 1 or a.size not in (1, 3, 4):
+            raise ValueError(f"{what} must be a scalar or 3 or 4 values; got shape {a.shape}")
+        a = np.full(4, a[0], np.float32) if a.size == 1 else np.concatenate([a, np.full(4 - a.size, fill, np.float32)])
+        mag = np.abs(a.astype(np.float64))
+        if not np.all(np.isfinite(a)) or np.any((mag != 0) & ((mag < 2.0 ** -100) | (mag > 2.0 ** 100))):
+            raise ValueError(f"{what} must be finite and 0 or of magnitude in [2^-100, 2^100]; got {a.tolist()}")
+        out.append(a)
+    return out[0], out[1]
+
+
+class NormC(C.Structure):                         # yk_norm of include/yaik_hip.h
+    _fields_ = [("dtype", C.c_int32), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
+def norm_struct(dtype, scale=None, bias=None, mean=None, std=None) -> NormC:
+    """dtype (a torch or numpy dtype, or its name) and the affine pair of a normalised output as the library's yk_norm: scale / bias (default 1, 0),
+    or mean / std through norm_params; giving both pairs raises, like everything else here, before any library call."""
+    name = str(dtype).replace("torch.", "")
+    if name not in ELEM_DTYPES:
+        raise TypeError(f"dtype must be float16, bfloat16 or float32; got {dtype!r}")
+    if (mean is not None or std is not None) and (scale is not None or bias is not None):
+        raise ValueError("give scale / bias or mean / std, not both")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if mean is not None:
+        scale, bias = norm_params(mean, std)
+    s, b = check_norm(1.0 if scale is None else scale, 0.0 if bias is None else bias)
+    return NormC(ELEM_DTYPES[name][0], (C.c_float * 4)(*s.tolist()), (C.c_float * 4)(*b.tolist()))
+
+
+def mirror_flags(mirror, n: int):
+    """None, or the per-frame mirror flags of a normalised batch output as n contiguous uint8: a sequence, array or bool / integer tensor of n"""
+    if mirror is None:
+        return None
+    m = mirror.detach().cpu().numpy() if hasattr(mirror, "detach") else np.asarray(mirror)
+    if m.ndim != 1 or m.shape[0] != n or not (m.dtype == np.bool_ or np.issubdtype(m.dtype, np.integer)):
+        raise ValueError(f"mirror must be None or {n} flags, one per frame; got {m.dtype} {m.shape}")
+    return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+
 def gather_layout(nbytes):
     """Where HipTileEncoder.gather (yk_device_gather) puts segments of these lengths: (offsets, total) -- offsets[0] = 0, every later offset the
     previous end rounded up to 16, total = the last end rounded up to 16.  Pure; int64 numpy offsets."""

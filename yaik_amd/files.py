@@ -8,6 +8,8 @@ decode_files_device(streams)  n streams of one shape through YAIK_DecodeImagesTo
                               the batch; uint8 [N, H, W, C] or [N, C, H, W]
 decode_files_windows_device(streams, origins, size)   one window of each of them through YAIK_DecodeImagesWindowsToDevice: the same batch with
                               the pixel-sized work of a frame only inside its window; uint8 [N, h, w, C] or [N, C, h, w]
+decode_files_norm_device(streams, dtype, ...)   the frames, or a pixel window of each, as normalised float16 / bfloat16 / float32 elements with a
+                              mirror flag per stream through YAIK_DecodeImagesNormToDevice: converted in the de-tile store, no uint8 intermediate
 encode_files_device(frames)   the other direction (yaik_encode.h, YAIK_EncodeImagesFromDevice): uint8 [N, H, W, C] frames in device memory to N
                               streams, every kernel once over the batch, one gather and one download, ZStd and framing on host workers
 encode_file_device(frame)     a batch of one
@@ -101,6 +103,10 @@ WINDOW_PX_SIGNATURES = {
     "YAIK_DecodeImageWindowsPxToDevice": MULTIWINDOW_SIGNATURES["YAIK_DecodeImageWindowsToDevice"],
     "YAIK_DecodeImagesWindowsPxToDevice": BATCH_WINDOWS_SIGNATURES["YAIK_DecodeImagesWindowsToDevice"],
 }
+# yaik_decode_norm.h: the same library, C linkage; the arguments of YAIK_DecodeImagesWindowsPxToDevice, then yk_norm* and the mirror flags
+NORM_SIGNATURES = {
+    "YAIK_DecodeImagesNormToDevice": (C.c_bool, BATCH_WINDOWS_SIGNATURES["YAIK_DecodeImagesWindowsToDevice"][1] + [vp, vp]),
+}
 # yaik_decode_scaled.h: the same library, C linkage
 SCALED_SIGNATURES = {
     "YAIK_DecodeImageScaledToDevice": (C.c_bool, [vp, u32, vp, C.c_int]),
@@ -145,7 +151,7 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
-        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **BATCH_WINDOWS_SIGNATURES, **WINDOW_PX_SIGNATURES, **SCALED_SIGNATURES, **MIPCHAIN_SIGNATURES}.items():
+        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **BATCH_WINDOWS_SIGNATURES, **WINDOW_PX_SIGNATURES, **NORM_SIGNATURES, **SCALED_SIGNATURES, **MIPCHAIN_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _host = L
@@ -471,6 +477,68 @@ def decode_files_windows_device(streams, origins, size, out=None, channels: int 
     torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
     fn = L.YAIK_DecodeImagesWindowsPxToDevice if px else L.YAIK_DecodeImagesWindowsToDevice
     ok = fn(h, ptrs, lens, n, out.data_ptr(), lay.row_bytes, plane_bytes, lay.frame_bytes, channels, int(threads), C.byref(failed), xy, ww, wh)
+    if not ok:
+        raise YaikFileError(L.YAIK_GetErrorCode(), max(failed.value, 0))
+    return out
+
+
+def decode_files_norm_device(streams, dtype, scale=None, bias=None, mean=None, std=None, origins=None, size=None, mirror=None, out=None, channels: int = 3,
+                             planar: bool = False, threads: int = 16):
+    """n (1..1024) streams of ONE width x height as normalised elements (YAIK_DecodeImagesNormToDevice): a torch.float16 / bfloat16 /
+    float32 tensor [N, h, w, C], or [N, C, h, w] with planar=True, on the GPU -- whole frames, or with origins and size=(w, h) stream f's pixel
+    window at origins[f] (any rectangle inside the image, as with decode_files_windows_device(px=True)).  Every decoded byte v of channel k
+    becomes fp32(v) * scale[k], then + bias[k], kept as fp32 or rounded to nearest even (HipTileDecoder.image_norm_device has the rule for scale /
+    bias and mean / std); mirror: None, or n flags, a set one flips that stream's output horizontally.  channels 4 takes alpha from each frame's
+    'ALPM' chunk, 255 for a frame without one, normalised like a colour.  `out`, threads and the errors follow decode_files_device."""
+    import torch
+
+    from .encoder import elem_layout, mirror_flags, norm_struct
+    nrm = norm_struct(dtype, scale, bias, mean, std)
+    streams = list(streams)
+    n = len(streams)
+    if not 1 <= n <= 1024:
+        raise ValueError("1..1024 streams are needed")
+    if channels not in (3, 4) or not 1 <= int(threads) <= 16:
+        raise ValueError("channels must be 3 or 4 and threads 1..16")
+    if (origins is None) != (size is None):
+        raise ValueError("origins and size go together")
+    flags = mirror_flags(mirror, n)
+    xy = None
+    if origins is not None:
+        if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != 2:
+            raise TypeError(f"size must be (w, h); got {size!r}")
+        if isinstance(origins, np.ndarray):
+            origins = origins.tolist() if origins.ndim == 2 and np.issubdtype(origins.dtype, np.integer) else origins
+        flat, ww, wh = window_origins(origins, size[0], size[1], True)
+        if len(flat) != 2 * n:
+            raise ValueError(f"{len(flat) // 2} window origins for {n} streams")
+        xy = (C.c_int * (2 * n))(*flat)
+    else:
+        ww = wh = 0
+        if len(streams[0]) >= 12:
+            tag, _, W, H, _ = struct.unpack_from("<IHHHH", streams[0], 0)
+            if tag == 0x4B494159:                                          # else: the library says so, nothing is written
+                ww, wh = W, H
+    L, h = host_lib(), library()
+    bufs = [_buffer(s) for s in streams]
+    dev = torch.device("cuda", _device)
+    tdt = getattr(torch, str(dtype).replace("torch.", ""))
+    if out is None:
+        out = torch.empty((n, channels, wh, ww) if planar else (n, wh, ww, channels), dtype=tdt, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.device != dev:
+        raise ValueError(f"out must be a torch tensor on {dev}")
+    elif out.dtype != tdt:
+        raise TypeError(f"out has dtype {out.dtype}, the call asks for {tdt}")
+    lay = elem_layout(out, planar=planar, batch=True)
+    if (lay.frames, lay.channels, lay.rows, lay.w) != (n, channels, wh, ww):      # the library writes wh x ww pixels per frame: never into a smaller view
+        raise ValueError(f"out holds {lay.frames} frames of {lay.w} x {lay.rows} x {lay.channels}, the call needs {n} of {ww} x {wh} x {channels}")
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_uint32 * n)(*[b.size for b in bufs])
+    failed = C.c_int32(-1)
+    torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
+    ok = L.YAIK_DecodeImagesNormToDevice(h, ptrs, lens, n, out.data_ptr(), lay.row_bytes, lay.plane_bytes, lay.frame_bytes, channels, int(threads),
+                                         C.byref(failed), xy, ww if xy is not None else 0, wh if xy is not None else 0, C.byref(nrm),
+                                         None if flags is None else flags.ctypes.data)
     if not ok:
         raise YaikFileError(L.YAIK_GetErrorCode(), max(failed.value, 0))
     return out

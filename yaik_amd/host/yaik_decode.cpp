@@ -8,6 +8,8 @@
 #include "yaik_decode_batch_windows.h"
 #include "yaik_decode_window_px.h"
 #include "../csrc/yk_window_px.h"
+#include "../csrc/yk_window_mirror.h"
+#include "yaik_decode_norm.h"
 #include "yaik_decode_scaled.h"
 #include "yaik_decode_mipchain.h"
 #include <atomic>
@@ -384,14 +386,22 @@ void YAIK_LastBatchStageMs(double out[3]) { if (out) for (int i = 0; i < 3; i++)
 
 // YAIK_DecodeImagesToDevice and, with xy (one origin per stream) and the window size ww x wh, YAIK_DecodeImagesWindowsToDevice: the same plan,
 // expansion, upload and batch calls; with windows the batch is given them right after yk_decode_begin_batch, the output is the windows' and a
-// fallback stream takes the single-image window chain
+// fallback stream takes the single-image window chain; with norm (YAIK_DecodeImagesNormToDevice, yaik_decode_norm.h) both end in the normalised outputs:
+// devOut holds elements of norm->dtype, the pitches stay in bytes, mirror is NULL or one flag per stream
 static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
-                         size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh, bool px = false) {
+                         size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh, bool px = false, const yk_norm* norm = nullptr,
+                         const uint8_t* mirror = nullptr) {
     using namespace yaikplan;
     if (failedIndex) *failedIndex = -1;
     if (!lib || lib != gLib) { setError(YAIK_INVALID_LIBRARYCTX); return false; }
     if (!streams || !lengths || n < 1 || n > 1024 || (channels != 3 && channels != 4) || threads < 1 || threads > 16) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
     if (!devOut) { setError(YAIK_DECIMG_BUFFERNOTSET); return false; }
+    if (norm) {                                                                 // the device call's own rule, before a slot is taken
+        bool ok = norm->dtype == YK_ELEM_F16 || norm->dtype == YK_ELEM_BF16 || norm->dtype == YK_ELEM_F32;
+        for (int k = 0; ok && k < 4; k++) ok = yk_norm_param_ok(norm->scale[k]) && yk_norm_param_ok(norm->bias[k]);
+        const size_t es = norm->dtype == YK_ELEM_F32 ? 4 : 2;
+        if (!ok || (((uintptr_t)devOut | rowBytes | planeBytes | frameBytes) & (es - 1))) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
+    }
     // the headers: the checks of YAIK_DecodeImagePre on every stream, then one shape
     int w = 0, h = 0;
     for (int f = 0; f < n; f++) {
@@ -557,7 +567,9 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
                 yk_decode_alpha_batch_status(s->ctx, st.data()) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
             for (int f = 0; f < n; f++) if (st[(size_t)f]) fallback[(size_t)f] = 1;       // a payload shorter than the mask selects: the single chain reports it
         }
-        if (xy) {
+        if (norm) {
+            if (yk_decode_output_norm_batch_device(s->ctx, norm, mirror, devOut, rowBytes, planeBytes, frameBytes, channels, anyAlpha && channels == 4 ? -1 : 255) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+        } else if (xy) {
             if (yk_decode_output_batch_windows_device(s->ctx, devOut, rowBytes, planeBytes, frameBytes, channels, anyAlpha && channels == 4 ? -1 : 255) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
         } else if (anyAlpha && channels == 4) {
             if (yk_decode_output_batch_alpha_device(s->ctx, devOut, rowBytes, planeBytes, frameBytes) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
@@ -576,7 +588,8 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
             if (res) {
                 const bool plane = hasAlphaPlane && channels == 4;
                 uint8_t* const dst = devOut + (size_t)f * frameBytes;
-                res = (xy ? yk_decode_output_window_device(s->ctx, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)
+                res = (norm ? yk_decode_output_norm_device(s->ctx, norm, mirror ? mirror[f] : 0, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)
+                       : xy ? yk_decode_output_window_device(s->ctx, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)
                           : yk_decode_output_device(s->ctx, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)) == YK_OK && yk_synchronize(s->ctx) == YK_OK;
                 if (!res) setError(YAIK_INVALID_STREAM);
             }
@@ -604,6 +617,14 @@ extern "C" bool YAIK_DecodeImagesWindowsPxToDevice(YAIK_LIB lib, void* const* st
                                                    size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh) {
     if (!xy) { if (failedIndex) *failedIndex = -1; setError(YAIK_DECIMG_INVALIDCTX); return false; }
     return decodeImages(lib, streams, lengths, n, devOut, rowBytes, planeBytes, frameBytes, channels, threads, failedIndex, xy, ww, wh, true);
+}
+
+// yaik_decode_norm.h
+extern "C" bool YAIK_DecodeImagesNormToDevice(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, void* devOut, size_t rowBytes, size_t planeBytes,
+                                              size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh, const yk_norm* norm,
+                                              const uint8_t* mirror) {
+    if (!norm) { if (failedIndex) *failedIndex = -1; setError(YAIK_DECIMG_INVALIDCTX); return false; }
+    return decodeImages(lib, streams, lengths, n, static_cast<uint8_t*>(devOut), rowBytes, planeBytes, frameBytes, channels, threads, failedIndex, xy, ww, wh, true, norm, mirror);
 }
 
 // ---- YAIK_DecodeImageWindowsToDevice: many windows of one stream (yaik_decode_multiwindow.h) ------------------------------------------------
