@@ -835,6 +835,40 @@ int yk_decode_output_norm_device(yk_ctx* c, const yk_norm* norm, int mirror, voi
 int yk_decode_output_norm_batch_device(yk_ctx* c, const yk_norm* norm, const uint8_t* mirror /* nFrames, host memory, or NULL */, void* devOut,
                                        size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha);
 
+/* ---- per-frame rectangles resampled to one output size ----
+ * A random resized crop in the decoder: frame f has a source rectangle (x0, y0, sw, sh) of its own size and aspect, and every rectangle is resampled
+ * to one ow x oh.  x0, y0 >= 0, sw, sh >= 1, x0 + sw <= w, y0 + sh <= h, no alignment; 1 <= ow, oh <= 16384 and sw, sh <= 16384.  Per axis, in
+ * integers (x shown; y the same with sh, oh):
+ *     step   = floor(sw * 65536 / ow)                         16.16 source pixels per output pixel
+ *     off    = (step >> 1) - 32768                            half-pixel centres: (i + 0.5) * sw / ow - 0.5
+ *     pos(i) = clamp(off + i * step, 0, (sw - 1) << 16)       i = 0 .. ow - 1
+ *     ix = pos >> 16,  fx = (pos >> 8) & 255,  ix1 = min(ix + 1, sw - 1)
+ * so taps never leave the rectangle ("crop, then resize": torch's bilinear with align_corners=False, antialias=False on the crop).  With the bytes
+ * a = S(ix, iy), b = S(ix1, iy), c = S(ix, iy1), d = S(ix1, iy1) of a channel, S being the whole decode at (x0 + ., y0 + .):
+ *     v = ((a (256 - fx) + b fx) (256 - fy) + (c (256 - fx) + d fx) fy + 32768) >> 16            0 .. 255
+ * Alpha is resampled like a colour channel, from the 'ALPM' plane or the constant.  Mirror is horizontal and applied to the OUTPUT: output column i
+ * lands at ow - 1 - i.  The element is v itself (norm == NULL: uint8) or the normalised element of the section above computed from v.  sw == ow and
+ * sh == oh give the pixel-window outputs byte for byte; sw == 2 ow, sh == 2 oh give (a + b + c + d + 2) >> 2.  There is NO antialiasing filter: a
+ * rectangle more than twice the output size aliases.
+ * yk_decode_set_batch_rects has the state rules of yk_decode_set_batch_windows (after yk_decode_begin_batch, before any chunk).  Frame f's window for
+ * the chunk calls becomes the smallest 8-aligned rectangle that contains its rectangle; inside it the frame holds what the whole batch decode leaves
+ * there, tile4x4Mask is whole and exact, and no byte of its planes outside that cover rounded out to 64 is written.  rects == NULL clears the
+ * rectangles.  Rectangles and windows replace each other; yk_decode_begin[_batch] clears both.  While rectangles are set every call that refuses
+ * under batch windows refuses (YK_ERR_STATE, naming the rectangles), and so do yk_decode_output_batch_windows_device and
+ * yk_decode_output_norm_batch_device.
+ * yk_decode_output_resampled_batch_device writes frame f at devOut + f * frameBytes: its rectangle, or the whole frame if neither rectangles nor
+ * windows are set (YK_ERR_STATE with windows).  yk_decode_output_resampled_device does the same for an image begun with yk_decode_begin or the
+ * selected frame of a batch that has neither: rect = {x0, y0, sw, sh} must lie inside the window set on the handle (aligned or pixel), NULL means
+ * that window or the whole image; a prepared image is refused.  Layout, pitches, channels, alpha and alignment follow
+ * yk_decode_output_norm_batch_device, taken against ow x oh elements of 1 byte (norm == NULL) or of the dtype.  One launch under
+ * YK_STAGE_DEC_DETILE, no host synchronisation, only pixel elements are written.  Every refusal comes before anything is queued, names the call in
+ * yk_last_error, writes nothing and leaves the handle decoding correctly. */
+int yk_decode_set_batch_rects(yk_ctx* c, const int* rects /* nFrames x {x0, y0, sw, sh}, host memory, or NULL */);
+int yk_decode_output_resampled_batch_device(yk_ctx* c, const yk_norm* norm /* NULL = uint8 */, const uint8_t* mirror /* NULL or nFrames, host memory */,
+                                            void* devOut, int ow, int oh, size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha);
+int yk_decode_output_resampled_device(yk_ctx* c, const int* rect /* 4 ints, or NULL */, const yk_norm* norm, int mirror, void* devOut, int ow, int oh,
+                                      size_t rowBytes, size_t planeBytes, int channels, int alpha);
+
 /* ---- round-trip quality (new): what the decode holds against a source image, both in HBM -----------------------------------------
  * The codec is lossy; these calls say how lossy a round trip was without moving a pixel to the host.  One kernel reads the decoder's 8x8-tiled
  * planes (and, with four channels, the decoded 'ALPM' plane) and the source where it lies, a second one folds the workgroups' records; per frame

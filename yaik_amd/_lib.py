@@ -184,6 +184,9 @@ SIGNATURES = {
     "yk_decode_set_batch_windows_px": (C.c_int, [vp, vp, C.c_int, C.c_int]),
     "yk_decode_output_norm_device": (C.c_int, [vp, vp, C.c_int, vp, sz, sz, C.c_int, C.c_int]),
     "yk_decode_output_norm_batch_device": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, C.c_int, C.c_int]),
+    "yk_decode_set_batch_rects": (C.c_int, [vp, vp]),
+    "yk_decode_output_resampled_batch_device": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, sz, sz, sz, C.c_int, C.c_int]),
+    "yk_decode_output_resampled_device": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, sz, sz, C.c_int, C.c_int]),
     "yk_decode_compare_device": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_int, vp, vp]),
     "yk_decode_compare_batch_device": (C.c_int, [vp, vp, sz, sz, sz, C.c_int, C.c_int, vp, vp]),
     "yk_decode_compare_planes_device": (C.c_int, [vp, C.POINTER(vp), C.c_int, sz, C.c_int, vp, vp]),

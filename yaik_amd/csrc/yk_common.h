@@ -331,6 +331,13 @@ struct yk_ctx {
     bool dPxSet = false; int dPxX = 0, dPxY = 0, dPxW = 0, dPxH = 0;
     // yk_decode_output_norm_batch_device: the per-frame mirror flags in HBM: 1024 entries, allocated once, written through the pinned ring
     YkBuf<uint32_t> dNormTab;
+    // yk_decode_set_batch_rects: a source rectangle per frame, each with its own 8-aligned cover.  The covers lie in dBWinTab like windows
+    // and dBWinSet is set with them, so every call that refuses under windows refuses here; dBWinW x dBWinH is then the bounding size of the covers and
+    // dBRectMaxTiles the largest cover's tile count (what the grids of the per-frame launches are sized by).  dBRects keeps the exact rectangles
+    // {x0, y0, sw, sh} on the host for yk_decode_output_resampled_batch_device, whose nine words per frame go into dRsTab (1024 frames, allocated once)
+    bool dBRectSet = false; uint32_t dBRectMaxTiles = 0;
+    std::vector<int> dBRects;
+    YkBuf<int> dRsTab;
     bool dPlanesStale = false;          // the planes were not cleared for this image: cells tile4x4Mask does not mark hold the previous image (yk_dec_settle)
     // yk_decode_prepare_device: the map-sized work of this image is done and what a render needs is kept in dPrep (yk_decode.hip) until the next
     // yk_decode_begin[_batch]; the buffers in dPrep are grow-only and go with the handle (yk_dec_prepared_free)
@@ -413,6 +420,7 @@ int yk_refuse(yk_ctx* c, int code, const char* what);
 // ... and while the image is prepared for windows (yk_decode_prepare_device): only the blocks some window asked for are rendered
 // ... and while the frames of a batch have windows (yk_decode_set_batch_windows): the same holds per frame
 #define YK_DEC_NO_BATCH_WINDOWS(c, name) do { \
+    if ((c)->dBRectSet) return yk_refuse((c), YK_ERR_STATE, name " needs whole frames, but rectangles are set on this batch (yk_decode_set_batch_rects): use yk_decode_output_resampled_batch_device"); \
     if ((c)->dBWinSet) return yk_refuse((c), YK_ERR_STATE, name " needs whole frames, but windows are set on this batch (yk_decode_set_batch_windows): use yk_decode_output_batch_windows_device"); } while (0)
 #define YK_DEC_NO_WINDOW(c, name) do { \
     YK_DEC_NO_BATCH_WINDOWS(c, name); \

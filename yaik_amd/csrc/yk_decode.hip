@@ -16,6 +16,7 @@
 #include "yk_window_blocks.h"
 #include "yk_window_px.h"
 #include "yk_window_mirror.h"
+#include "yk_resample.h"
 
 struct DPassGeo { int sx, sy, bigX, bigY, bitCount, xBB, tilesPerRow; };
 
@@ -840,6 +841,18 @@ __global__ __launch_bounds__(256) void yk_dec1d_batch_win_kernel(const D1Batch B
     yk_dec1d_body<YK_D1_WIN>(yk_d1batch_u32(B, f, B.oOff), nWin, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oTot), fr.type, (size_t)fr.typeBytes,
                   fr.pix, (size_t)fr.pixBytes, invRange, B.planes + f * B.sPlanes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x, wn);
 }
+// ... with a rectangle per frame (yk_decode_set_batch_rects): wins[f] is the rectangle's own 8-aligned cover, so the tile counts differ
+// from frame to frame.  The grid is the largest cover's; a workgroup past its frame's count leaves before it loads anything (the body has no barrier).
+__global__ __launch_bounds__(256) void yk_dec1d_batch_rects_kernel(const D1Batch B, const DWinRect* __restrict__ wins, uint32_t tilesW, int invRange, size_t planeSize) {
+    const size_t f = blockIdx.z;
+    const DWinRect wr = wins[f];
+    const uint32_t wtW = (uint32_t)(wr.x1 - wr.x0) >> 3, nWin = wtW * ((uint32_t)(wr.y1 - wr.y0) >> 3);
+    if (blockIdx.x * (uint32_t)(64 * YK_D1_TPL) >= nWin) return;
+    const D1Frame& fr = B.frames[f];
+    const D1Win wn = { (uint32_t)wr.x0 >> 3, (uint32_t)wr.y0 >> 3, wtW, tilesW };
+    yk_dec1d_body<YK_D1_WIN>(yk_d1batch_u32(B, f, B.oOff), (size_t)nWin, yk_d1batch_u32(B, f, B.oBT), yk_d1batch_u32(B, f, B.oBP), yk_d1batch_u32(B, f, B.oTot), fr.type,
+                  (size_t)fr.typeBytes, fr.pix, (size_t)fr.pixBytes, invRange, B.planes + f * B.sPlanes, planeSize, -1, (const uint32_t*)nullptr, blockIdx.x, wn);
+}
 
 __global__ void yk_dec_mask_kernel(const uint8_t* __restrict__ bits, int bw, int bh, unsigned long long* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1317,6 +1330,112 @@ static void yk_dn_launch(const YkDetileArgs& a, const YkDetileNorm& nm, hipStrea
     });
 }
 
+// ---- the resampling output: a rectangle per frame, bilinear in 16.16 fixed point, to one ow x oh (yk_decode_output_resampled_*) ------
+// Not a de-tile: the lanes enumerate OUTPUT pixels and gather their four taps from the 8x8-tiled planes (tap (X, Y) of a colour plane is byte
+// ((Y >> 3) * tileW + (X >> 3)) * 64 + (Y & 7) * 8 + (X & 7); alpha taps come from the linear 'ALPM' plane).  The arithmetic is yk_resample.h's,
+// the same functions the CPU tool checks.  Frame blockIdx.y reads its nine words {x0, y0, sw - 1, sh - 1, stepX, offX, stepY, offY, mirror} through
+// a uniform address (scalar loads).  A workgroup owns 64 x 16 output pixels, so its source footprint is one compact patch that stays in L1 / L2; a
+// lane owns four consecutive output columns of one row: it issues every tap load (2 rows x 2 taps x 4 columns per plane, byte loads) before the
+// first blend, and stores 4 C elements (HWC) or 4 elements per plane (CHW) through byte pointers like yk_dt_emit, so one path serves every base and
+// pitch.  Mirror is applied to the output: the lane's destination column d reads output index ow - 1 - d, and the stores stay rising.  The float
+// elements are yk_dn_value's (contraction off: two roundings).  No LDS, no barrier; a lane past the right or bottom edge leaves at once.
+#define YK_RS_BW 64                                 // output columns per workgroup: 16 lanes x 4
+#define YK_RS_BH 16                                 // output rows per workgroup
+struct YkResampleArgs {
+    const uint8_t* planes; size_t planeSize, planesFrame;
+    const uint8_t* alpha; size_t strideA, alphaFrame;   // YK_DT_ALPHA_PLANE: frame 0's whole plane
+    uint32_t alphaConst;                                // YK_DT_ALPHA_CONST: the byte (a constant resamples to itself)
+    uint8_t* out; size_t rowBytes, planeBytes, outFrame;
+    uint32_t tileW, nbx; int ow, oh;
+    float scale[4], bias[4];
+    const int* tab;                                     // YK_RS_WORDS per frame
+};
+template <int E> struct YkRsElem { typedef typename YkNormElem<E>::T T; };
+template <> struct YkRsElem<0> { typedef uint8_t T; };
+template <class T>
+__device__ __forceinline__ T yk_rs_value(uint32_t v, float scale, float bias) {
+    if constexpr (sizeof(T) == 1) return (T)v;
+    else return yk_dn_value<T>(v, 0, scale, bias);
+}
+template <int E, int C, bool PLANAR, int ASRC>
+__global__ __launch_bounds__(256) void yk_dec_resample_kernel(const YkResampleArgs a) {
+    typedef typename YkRsElem<E>::T T;
+    const uint32_t f = blockIdx.y;
+    const int* __restrict__ t = a.tab + (size_t)f * YK_RS_WORDS;
+    const int x0 = t[0], y0 = t[1], sw = t[2] + 1, sh = t[3] + 1, mirror = t[8];
+    const YkRsAxis ax = { t[4], t[5] }, ay = { t[6], t[7] };
+    const uint32_t by = blockIdx.x / a.nbx, bx = blockIdx.x - by * a.nbx;
+    const int oy = (int)(by * YK_RS_BH + (threadIdx.x >> 4)), d0 = (int)((bx * 16 + (threadIdx.x & 15)) * 4);
+    if (oy >= a.oh || d0 >= a.ow) return;
+    const int nk = a.ow - d0 < 4 ? a.ow - d0 : 4;
+    const YkRsTap ty = yk_rs_tap(ay, oy, sh);
+    const uint32_t Y0 = (uint32_t)(y0 + ty.i0), Y1 = (uint32_t)(y0 + ty.i1);
+    const size_t r0 = (size_t)(Y0 >> 3) * a.tileW * 64 + (Y0 & 7) * 8, r1 = (size_t)(Y1 >> 3) * a.tileW * 64 + (Y1 & 7) * 8;
+    uint32_t X0[4], X1[4]; int fx[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int d = d0 + (k < nk ? k : nk - 1);                              // a column past the edge repeats the last one: its loads stay inside, nothing is stored
+        const YkRsTap tx = yk_rs_tap(ax, mirror ? a.ow - 1 - d : d, sw);
+        X0[k] = (uint32_t)(x0 + tx.i0); X1[k] = (uint32_t)(x0 + tx.i1); fx[k] = tx.f;
+    }
+    constexpr int NP = ASRC == YK_DT_ALPHA_PLANE ? 4 : 3;                     // planes that are loaded
+    const uint8_t* const P = a.planes + (size_t)f * a.planesFrame;
+    uint32_t s[NP][4][4];                                                     // [plane][column][a b c d]: every load before the arithmetic
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        const uint8_t* const pl = P + (size_t)p * a.planeSize;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t ca = (X0[k] >> 3) * 64 + (X0[k] & 7), cb = (X1[k] >> 3) * 64 + (X1[k] & 7);
+            s[p][k][0] = pl[r0 + ca]; s[p][k][1] = pl[r0 + cb]; s[p][k][2] = pl[r1 + ca]; s[p][k][3] = pl[r1 + cb];
+        }
+    }
+    if constexpr (ASRC == YK_DT_ALPHA_PLANE) {
+        const uint8_t* const A = a.alpha + (size_t)f * a.alphaFrame;
+        const size_t q0 = (size_t)Y0 * a.strideA, q1 = (size_t)Y1 * a.strideA;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { s[3][k][0] = A[q0 + X0[k]]; s[3][k][1] = A[q0 + X1[k]]; s[3][k][2] = A[q1 + X0[k]]; s[3][k][3] = A[q1 + X1[k]]; }
+    }
+    T e[4][C];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int p = 0; p < C; p++) {
+            const uint32_t v = p < NP ? (uint32_t)yk_rs_blend((int)s[p < NP ? p : 0][k][0], (int)s[p < NP ? p : 0][k][1], (int)s[p < NP ? p : 0][k][2], (int)s[p < NP ? p : 0][k][3], fx[k], ty.f)
+                                      : a.alphaConst;
+            e[k][p] = yk_rs_value<T>(v, a.scale[p], a.bias[p]);
+        }
+    uint8_t* const o = a.out + (size_t)f * a.outFrame + (size_t)oy * a.rowBytes + (size_t)d0 * ((PLANAR ? 1 : C) * sizeof(T));
+    if (nk == 4) {
+        if constexpr (PLANAR) {
+#pragma unroll
+            for (int p = 0; p < C; p++) {
+                T q[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) q[k] = e[k][p];
+                __builtin_memcpy(o + (size_t)p * a.planeBytes, q, sizeof(q));
+            }
+        } else __builtin_memcpy(o, e, sizeof(e));
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (k >= nk) break;
+        if constexpr (PLANAR) {
+#pragma unroll
+            for (int p = 0; p < C; p++) __builtin_memcpy(o + (size_t)p * a.planeBytes + (size_t)k * sizeof(T), &e[k][p], sizeof(T));
+        } else __builtin_memcpy(o + (size_t)k * (C * sizeof(T)), e[k], sizeof(e[k]));
+    }
+}
+template <int E>
+static void yk_rs_launch(const YkResampleArgs& a, hipStream_t s, int channels, bool planar, bool fromPlane, int nFrames) {
+    const unsigned nby = ((unsigned)a.oh + YK_RS_BH - 1) / YK_RS_BH;
+    yk_dt_each(channels, planar, fromPlane, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((yk_dec_resample_kernel<E, T::c, T::planar, T::asrc>), dim3(a.nbx * nby, (unsigned)nFrames), dim3(256), 0, s, a);
+    });
+}
+
 // nFrames == 0: the selected frame (the existing single-image launch); otherwise nFrames frames, planesFrame / outFrame bytes apart
 template <int C, bool PLANAR, int ASRC>
 static void yk_dt_launch(const YkDetileArgs& a, hipStream_t s, int nFrames = 0, size_t planesFrame = 0, size_t outFrame = 0, size_t alphaFrame = 0,
@@ -1787,11 +1906,26 @@ __global__ __launch_bounds__(256) void yk_dec_zero_unmarked_batch_win_kernel(con
     const uint32_t jy = j / wtW, jx = j - jy * wtW;
     yk_dec_zero_unmarked_tile(tile4 + f * sTile4, tile4Size, 0, stride4, tilesW, (size_t)(ty0 + jy) * tilesW + tx0 + jx, planes + f * sPlanes, planeSize);
 }
+// a batch with a rectangle per frame (yk_decode_set_batch_rects): the tiles of frame f's own cover; the grid is the largest cover's
+__global__ __launch_bounds__(256) void yk_dec_zero_unmarked_batch_rects_kernel(const uint8_t* __restrict__ tile4, size_t sTile4, size_t tile4Size, int stride4, int tilesW,
+                                                                               const DWinRect* __restrict__ wins, uint8_t* __restrict__ planes, size_t sPlanes, size_t planeSize) {
+    const size_t f = blockIdx.z;
+    const DWinRect wr = wins[f];
+    const uint32_t wtW = (uint32_t)(wr.x1 - wr.x0) >> 3, nWin = wtW * ((uint32_t)(wr.y1 - wr.y0) >> 3);
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nWin) return;
+    const uint32_t jy = j / wtW, jx = j - jy * wtW;
+    yk_dec_zero_unmarked_tile(tile4 + f * sTile4, tile4Size, 0, stride4, tilesW, (size_t)(((uint32_t)wr.y0 >> 3) + jy) * tilesW + ((uint32_t)wr.x0 >> 3) + jx, planes + f * sPlanes,
+                              planeSize);
+}
 static int yk_dec_settle(yk_ctx* c) {
     if (!c->dPlanesStale) return YK_OK;
     const int w = c->dw, h = c->dh;
     const size_t T8 = (size_t)(w >> 3) * (h >> 3);
-    if (c->dBWinSet) {                                                          // every frame of the batch inside its own window
+    if (c->dBRectSet) {                                                         // every frame of the batch inside its rectangle's own cover
+        hipLaunchKernelGGL(yk_dec_zero_unmarked_batch_rects_kernel, dim3((c->dBRectMaxTiles + 255) / 256, 3, (unsigned)c->dFrames), dim3(256), 0, c->stream, c->dB.tile4,
+                           c->dStride.tile4, c->dTile4Size, (w + 15) >> 4, w >> 3, reinterpret_cast<const DWinRect*>(c->dBWinTab.p), c->dB.planes, c->dStride.planes, c->dPlaneSize);
+    } else if (c->dBWinSet) {                                                        // every frame of the batch inside its own window
         const uint32_t wtW = (uint32_t)(c->dBWinW >> 3), nWin = wtW * (uint32_t)(c->dBWinH >> 3);
         hipLaunchKernelGGL(yk_dec_zero_unmarked_batch_win_kernel, dim3((nWin + 255) / 256, 3, (unsigned)c->dFrames), dim3(256), 0, c->stream, c->dB.tile4, c->dStride.tile4,
                            c->dTile4Size, (w + 15) >> 4, w >> 3, reinterpret_cast<const DWinRect*>(c->dBWinTab.p), wtW, nWin, c->dB.planes, c->dStride.planes, c->dPlaneSize);
@@ -1880,6 +2014,7 @@ static int yk_dec_begin(yk_ctx* c, int w, int h, int nFrames) {
     c->dWinSet = false; c->dWinX = c->dWinY = c->dWinW = c->dWinH = 0; c->dChunkSeen = false; c->dBatchBegun = false;
     c->dPxSet = false; c->dPxX = c->dPxY = c->dPxW = c->dPxH = 0;
     c->dBWinSet = false; c->dBWinW = c->dBWinH = 0;                             // the table stays queued kernels' to read: the next set writes it behind them
+    c->dBRectSet = false; c->dBRectMaxTiles = 0;
     c->dPrepared = false;                                                       // a prepared image ends here; what it kept is overwritten by the next prepare
     // The planes (3 B per pixel: 201 MB at 8192 x 8192, 40 us of every frame) are NOT cleared: every renderer marks what it writes in tile4x4Mask and
     // the 1-D decode writes every unmarked quadrant, so after a whole file nothing stale is left; a flow that stops earlier (or writes without
@@ -1979,6 +2114,7 @@ int yk_decode_set_batch_windows(yk_ctx* c, const int* xy, int ww, int wh) {
     if (!yk_dec_begun(c) || !c->dBatchBegun) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows: yk_decode_begin_batch first (the window of a single image is yk_decode_set_window's)");
     if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows: a chunk of this batch has been decoded already; set the windows right after yk_decode_begin_batch");
     c->dBWinSet = false; c->dBWinW = c->dBWinH = 0; c->dPxSet = false;           // a refusal below leaves the batch without windows
+    c->dBRectSet = false; c->dBRectMaxTiles = 0;                                // windows replace rectangles (yk_decode_set_batch_rects)
     if (ww == 0 && wh == 0) return YK_OK;
     if (!xy) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_batch_windows: the origin table is NULL");
     const int N = c->dFrames;
@@ -2006,6 +2142,7 @@ int yk_decode_set_batch_windows_px(yk_ctx* c, const int* xy, int ww, int wh) {
     if (!yk_dec_begun(c) || !c->dBatchBegun) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows_px: yk_decode_begin_batch first (the window of a single image is yk_decode_set_window_px's)");
     if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_windows_px: a chunk of this batch has been decoded already; set the windows right after yk_decode_begin_batch");
     c->dBWinSet = false; c->dBWinW = c->dBWinH = 0; c->dPxSet = false;           // a refusal below leaves the batch without windows
+    c->dBRectSet = false; c->dBRectMaxTiles = 0;                                // windows replace rectangles (yk_decode_set_batch_rects)
     if (ww == 0 && wh == 0) return YK_OK;
     if (!xy) return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_batch_windows_px: the origin table is NULL");
     const int N = c->dFrames, w = c->dw, h = c->dh;
@@ -2031,6 +2168,40 @@ int yk_decode_set_batch_windows_px(yk_ctx* c, const int* xy, int ww, int wh) {
     return YK_OK;
 }
 static const DWinRect* yk_dec_bwin_tab(const yk_ctx* c) { return reinterpret_cast<const DWinRect*>(c->dBWinTab.p); }
+
+// One source rectangle per frame, each of its own size (include/yaik_hip.h).  The taps of a resampled output never leave the rectangle,
+// so frame f's window for the chunk calls is the rectangle's own 8-aligned cover: the covers go where windows go (dBWinTab, through the pinned ring)
+// and the kernels that took one tile count for the batch have siblings that read frame f's own.  The exact rectangles stay on the host.
+int yk_decode_set_batch_rects(yk_ctx* c, const int* rects) {
+    if (!c) return YK_ERR_BAD_ARG;
+    if (!yk_dec_begun(c) || !c->dBatchBegun) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_rects: yk_decode_begin_batch first (a single image takes its rectangle in yk_decode_output_resampled_device)");
+    if (c->dChunkSeen) return yk_refuse(c, YK_ERR_STATE, "yk_decode_set_batch_rects: a chunk of this batch has been decoded already; set the rectangles right after yk_decode_begin_batch");
+    c->dBWinSet = false; c->dBWinW = c->dBWinH = 0; c->dPxSet = false;           // rectangles replace windows; a refusal below leaves the batch with neither
+    c->dBRectSet = false; c->dBRectMaxTiles = 0;
+    if (!rects) return YK_OK;
+    const int N = c->dFrames, w = c->dw, h = c->dh;
+    for (int f = 0; f < N; f++)
+        if (!yk_rs_src_ok(rects[4 * f], rects[4 * f + 1], rects[4 * f + 2], rects[4 * f + 3], w, h))
+            return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_set_batch_rects: x0, y0 >= 0, 1 <= sw, sh <= 16384 and every frame's rectangle inside the image");
+    YK_HIP(c, hipSetDevice(c->device));
+    YK_HIP(c, c->dBWinTab.reserve(c->stream, (size_t)1024 * 6));                // the table of the window calls: allocated once per handle
+    int slot; void* host;
+    { const int rc = yk_dec_table_host(c, (size_t)N * sizeof(DWinRect), &slot, &host); if (rc) return rc; }
+    DWinRect* tab = static_cast<DWinRect*>(host);
+    int mw = 0, mh = 0; uint32_t mt = 0;
+    for (int f = 0; f < N; f++) {
+        const YkRsCover k = yk_rs_cover(rects[4 * f], rects[4 * f + 1], rects[4 * f + 2], rects[4 * f + 3]);
+        tab[f] = DWinRect{ k.x0, k.y0, k.x1, k.y1 };
+        const int cw = k.x1 - k.x0, ch = k.y1 - k.y0;
+        const uint32_t t = (uint32_t)(cw >> 3) * (uint32_t)(ch >> 3);
+        mw = cw > mw ? cw : mw; mh = ch > mh ? ch : mh; mt = t > mt ? t : mt;
+    }
+    { const int rc = yk_dec_table_upload(c, slot, c->dBWinTab.p, (size_t)N * sizeof(DWinRect)); if (rc) return rc; }
+    c->dBRects.assign(rects, rects + 4 * (size_t)N);
+    c->dBWinW = mw; c->dBWinH = mh; c->dBWinSet = true;
+    c->dBRectMaxTiles = mt; c->dBRectSet = true;
+    return YK_OK;
+}
 
 // PaletteFullRangeRemapping (decoder/YAIK_GenericFunctions.cpp:128-137) of a corner stream that is still in HBM: v * ((255 << 16) / range) >> 16
 static uint32_t yk_dec_remap_factor(int remapRange) { return remapRange > 0 ? (uint32_t)((255u << 16) / (uint32_t)remapRange) : 0u; }
@@ -2414,7 +2585,10 @@ int yk_decode_1d_batch_device(yk_ctx* c, const uint8_t* const* devType, const si
     { int rc2 = yk_stage_begin(c, YK_STAGE_DEC_1D); if (rc2) return rc2; }
     hipLaunchKernelGGL(yk_dec1d_count_batch_kernel, dim3((unsigned)nb, F), dim3(1024), 0, c->stream, B, (w + 15) >> 4, tilesW, T8);
     hipLaunchKernelGGL(yk_dec1d_scan_batch_kernel, dim3(F), dim3(1024), 0, c->stream, B, (int)nb);
-    if (c->dBWinSet) {                                                        // count and scan stay whole for every frame; only the tiles of its window are decoded
+    if (c->dBRectSet)                                                         // ... of its rectangle's own cover: the grid is the largest cover's
+        hipLaunchKernelGGL(yk_dec1d_batch_rects_kernel, dim3((c->dBRectMaxTiles + 64 * YK_D1_TPL - 1) / (64 * YK_D1_TPL), 3, F), dim3(256), 0, c->stream, B, yk_dec_bwin_tab(c),
+                           (uint32_t)tilesW, (1 << 24) / compressionRange, c->dPlaneSize);
+    else if (c->dBWinSet) {                                                   // count and scan stay whole for every frame; only the tiles of its window are decoded
         const uint32_t wtW = (uint32_t)(c->dBWinW >> 3);
         const size_t nWin = (size_t)wtW * (c->dBWinH >> 3);
         hipLaunchKernelGGL(yk_dec1d_batch_win_kernel, dim3((unsigned)((nWin + 64 * YK_D1_TPL - 1) / (64 * YK_D1_TPL)), 3, F), dim3(256), 0, c->stream, B, yk_dec_bwin_tab(c), nWin,
@@ -2576,6 +2750,7 @@ int yk_decode_output_batch_windows_device(yk_ctx* c, uint8_t* devOut, size_t row
     if (channels == 4 && (alpha < -1 || alpha > 255))
         return yk_refuse(c, YK_ERR_BAD_ARG, "yk_decode_output_batch_windows_device: alpha must be -1 (the planes of yk_decode_alpha[_mask]_batch_device) or 0..255");
     if (!yk_dec_begun(c)) return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_batch_windows_device: yk_decode_begin_batch first");
+    if (c->dBRectSet) return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_batch_windows_device: rectangles are set on this batch (yk_decode_set_batch_rects): yk_decode_output_resampled_batch_device writes them");
     if (!c->dBWinSet) return yk_refuse(c, YK_ERR_STATE, "yk_decode_output_batch_windows_device: no windows are set on this batch (yk_decode_set_batch_windows)");
     const bool fromPlanes = channels == 4 && alpha < 0;
     if (fromPlanes && (!c->dAlphaValid || !c->dAlphaBatch))
@@ -2634,6 +2809,7 @@ static int yk_dec_output_norm(yk_ctx* c, const char* name, const yk_norm* nrm, i
     if (((uintptr_t)devOut | rowBytes | planeBytes | (batch ? frameBytes : 0)) & (es - 1)) return refuse(YK_ERR_BAD_ARG, "devOut and every pitch must be multiples of the element size");
     if (!yk_dec_begun(c)) return refuse(YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
     if (c->dPrepared) return refuse(YK_ERR_STATE, "this image is prepared for windows (yk_decode_prepare_device), which have no normalised output");
+    if (c->dBRectSet) return refuse(YK_ERR_STATE, "rectangles are set on this batch (yk_decode_set_batch_rects): yk_decode_output_resampled_batch_device writes them");
     if (!batch && c->dBWinSet) return refuse(YK_ERR_STATE, "windows are set on this batch (yk_decode_set_batch_windows): yk_decode_output_norm_batch_device writes them");
     if (batch && c->dWinSet) return refuse(YK_ERR_STATE, "a window is set on this image (yk_decode_set_window): yk_decode_output_norm_device writes it");
     const bool fromPlane = channels == 4 && alpha < 0;
@@ -2688,6 +2864,89 @@ int yk_decode_output_norm_batch_device(yk_ctx* c, const yk_norm* norm, const uin
                                        int channels, int alpha) {
     if (!c) return YK_ERR_BAD_ARG;
     return yk_dec_output_norm(c, "yk_decode_output_norm_batch_device", norm, 0, mirror, devOut, rowBytes, planeBytes, frameBytes, channels, alpha, true);
+}
+
+// ---- resampled outputs (include/yaik_hip.h): both entry points, every check before anything is queued (the table upload included),
+// then the nine words per frame through the pinned ring and one launch
+static int yk_dec_output_resampled(yk_ctx* c, const char* name, const int* rectOne, const yk_norm* nrm, int mirrorOne, const uint8_t* mirrorTab, void* devOut, int ow, int oh,
+                                   size_t rowBytes, size_t planeBytes, size_t frameBytes, int channels, int alpha, bool batch) {
+    auto refuse = [&](int code, const char* what) { return yk_refuse(c, code, (std::string(name) + ": " + what).c_str()); };
+    if (!devOut) return refuse(YK_ERR_BAD_ARG, "devOut is NULL");
+    if (nrm) {
+        if (nrm->dtype != YK_ELEM_F16 && nrm->dtype != YK_ELEM_BF16 && nrm->dtype != YK_ELEM_F32) return refuse(YK_ERR_BAD_ARG, "dtype must be YK_ELEM_F16, YK_ELEM_BF16 or YK_ELEM_F32");
+        for (int k = 0; k < 4; k++)
+            if (!yk_norm_param_ok(nrm->scale[k]) || !yk_norm_param_ok(nrm->bias[k]))
+                return refuse(YK_ERR_BAD_ARG, "every scale and bias must be finite and 0 or of magnitude in [2^-100, 2^100]");
+    }
+    if (channels != 3 && channels != 4) return refuse(YK_ERR_BAD_ARG, "channels must be 3 or 4");
+    if (channels == 4 && (alpha < -1 || alpha > 255)) return refuse(YK_ERR_BAD_ARG, "alpha must be -1 (the decoded plane) or 0..255");
+    if (!yk_rs_size_ok(ow, oh)) return refuse(YK_ERR_BAD_ARG, "the output size must be 1..16384 on both sides");
+    const size_t es = !nrm ? 1 : nrm->dtype == YK_ELEM_F32 ? 4 : 2;
+    if (((uintptr_t)devOut | rowBytes | planeBytes | (batch ? frameBytes : 0)) & (es - 1)) return refuse(YK_ERR_BAD_ARG, "devOut and every pitch must be multiples of the element size");
+    if (!yk_dec_begun(c)) return refuse(YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
+    if (c->dPrepared) return refuse(YK_ERR_STATE, "this image is prepared for windows (yk_decode_prepare_device), which have no resampled output");
+    if (!batch && c->dBRectSet) return refuse(YK_ERR_STATE, "rectangles are set on this batch (yk_decode_set_batch_rects): yk_decode_output_resampled_batch_device writes them");
+    if (!batch && c->dBWinSet) return refuse(YK_ERR_STATE, "windows are set on this batch (yk_decode_set_batch_windows), which have no resampled output");
+    if (batch && c->dBWinSet && !c->dBRectSet) return refuse(YK_ERR_STATE, "windows are set on this batch (yk_decode_set_batch_windows): set rectangles (yk_decode_set_batch_rects) or neither");
+    if (batch && c->dWinSet) return refuse(YK_ERR_STATE, "a window is set on this image (yk_decode_set_window): yk_decode_output_resampled_device reads it");
+    const bool fromPlane = channels == 4 && alpha < 0;
+    if (fromPlane && (!c->dAlphaValid || (batch && !c->dAlphaBatch)))
+        return refuse(YK_ERR_STATE, batch ? "alpha = -1 needs yk_decode_alpha_batch_device first: the batch has no decoded alpha planes" : "alpha = -1 needs yk_decode_alpha first");
+    // the single call's rectangle: inside the window (the pixel window if one is set), which is all the planes hold
+    int one[4] = { 0, 0, c->dw, c->dh };
+    if (!batch) {
+        if (c->dWinSet) { const bool px = c->dPxSet; one[0] = px ? c->dPxX : c->dWinX; one[1] = px ? c->dPxY : c->dWinY; one[2] = px ? c->dPxW : c->dWinW; one[3] = px ? c->dPxH : c->dWinH; }
+        if (rectOne) {
+            const int bx0 = one[0], by0 = one[1], bw = one[2], bh = one[3];
+            if (!yk_rs_src_ok(rectOne[0], rectOne[1], rectOne[2], rectOne[3], c->dw, c->dh))
+                return refuse(YK_ERR_BAD_ARG, "x0, y0 >= 0, 1 <= sw, sh <= 16384 and the rectangle inside the image");
+            if (rectOne[0] < bx0 || rectOne[1] < by0 || rectOne[0] - bx0 > bw - rectOne[2] || rectOne[1] - by0 > bh - rectOne[3])
+                return refuse(YK_ERR_BAD_ARG, "the rectangle must lie inside the window set on this image");
+            for (int k = 0; k < 4; k++) one[k] = rectOne[k];
+        }
+    }
+    const int N = batch ? c->dFrames : 1;
+    if (!(batch && c->dBRectSet) && (one[2] > YK_RS_MAX || one[3] > YK_RS_MAX)) return refuse(YK_ERR_BAD_ARG, "the source rectangle must be 16384 pixels or less on both sides");
+    const size_t w = (size_t)ow, h = (size_t)oh;
+    if (planeBytes == 0 ? rowBytes / es < w * (size_t)channels : (rowBytes / es < w || planeBytes / h < rowBytes))
+        return refuse(YK_ERR_BAD_ARG, "row or plane pitch too small for what is written");
+    if (N > 1 && (planeBytes == 0 ? frameBytes / h < rowBytes : frameBytes / (size_t)channels < planeBytes)) return refuse(YK_ERR_BAD_ARG, "frame stride too small for a frame");
+    YK_HIP(c, hipSetDevice(c->device));
+    { const int rcs = yk_dec_settle(c); if (rcs) return rcs; }
+    YK_HIP(c, c->dRsTab.reserve(c->stream, (size_t)1024 * YK_RS_WORDS));        // allocated once: a queued earlier call has read its words before this call's copy runs
+    int slot; void* host;
+    { const int rc = yk_dec_table_host(c, (size_t)N * YK_RS_WORDS * sizeof(int), &slot, &host); if (rc) return rc; }
+    for (int f = 0; f < N; f++) {
+        const int* r = batch && c->dBRectSet ? &c->dBRects[4 * (size_t)f] : one;
+        yk_rs_words(r[0], r[1], r[2], r[3], ow, oh, batch ? (mirrorTab && mirrorTab[f]) : mirrorOne != 0, static_cast<int*>(host) + (size_t)f * YK_RS_WORDS);
+    }
+    { const int rc = yk_dec_table_upload(c, slot, c->dRsTab.p, (size_t)N * YK_RS_WORDS * sizeof(int)); if (rc) return rc; }
+    YkResampleArgs a;
+    a.planes = batch ? c->dB.planes : yk_dec_frame(c, c->dCur).planes; a.planeSize = c->dPlaneSize; a.planesFrame = batch ? c->dStride.planes : 0;
+    a.alpha = fromPlane ? (batch ? (const uint8_t*)c->dAlpha : yk_dec_alpha_cur(c)) : nullptr; a.strideA = (size_t)c->dw; a.alphaFrame = batch && fromPlane ? c->dAlphaStride : 0;
+    a.alphaConst = (uint32_t)((fromPlane ? 0 : alpha) & 255);
+    a.out = static_cast<uint8_t*>(devOut); a.rowBytes = rowBytes; a.planeBytes = planeBytes; a.outFrame = batch ? frameBytes : 0;
+    a.tileW = (uint32_t)(c->dw >> 3); a.nbx = ((uint32_t)ow + YK_RS_BW - 1) / YK_RS_BW; a.ow = ow; a.oh = oh;
+    for (int k = 0; k < 4; k++) { a.scale[k] = nrm ? nrm->scale[k] : 1.0f; a.bias[k] = nrm ? nrm->bias[k] : 0.0f; }
+    a.tab = c->dRsTab.p;
+    const bool planar = planeBytes > 0;
+    { int rc = yk_stage_begin(c, YK_STAGE_DEC_DETILE); if (rc) return rc; }
+    if (!nrm) yk_rs_launch<0>(a, c->stream, channels, planar, fromPlane, N);
+    else if (nrm->dtype == YK_ELEM_F16) yk_rs_launch<YK_ELEM_F16>(a, c->stream, channels, planar, fromPlane, N);
+    else if (nrm->dtype == YK_ELEM_BF16) yk_rs_launch<YK_ELEM_BF16>(a, c->stream, channels, planar, fromPlane, N);
+    else yk_rs_launch<YK_ELEM_F32>(a, c->stream, channels, planar, fromPlane, N);
+    YK_HIP(c, hipGetLastError());
+    return yk_stage_end(c, YK_STAGE_DEC_DETILE);
+}
+int yk_decode_output_resampled_batch_device(yk_ctx* c, const yk_norm* norm, const uint8_t* mirror, void* devOut, int ow, int oh, size_t rowBytes, size_t planeBytes,
+                                            size_t frameBytes, int channels, int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    return yk_dec_output_resampled(c, "yk_decode_output_resampled_batch_device", nullptr, norm, 0, mirror, devOut, ow, oh, rowBytes, planeBytes, frameBytes, channels, alpha, true);
+}
+int yk_decode_output_resampled_device(yk_ctx* c, const int* rect, const yk_norm* norm, int mirror, void* devOut, int ow, int oh, size_t rowBytes, size_t planeBytes, int channels,
+                                      int alpha) {
+    if (!c) return YK_ERR_BAD_ARG;
+    return yk_dec_output_resampled(c, "yk_decode_output_resampled_device", rect, norm, mirror, nullptr, devOut, ow, oh, rowBytes, planeBytes, 0, channels, alpha, false);
 }
 
 // ---- outputs at reduced resolution (include/yaik_hip.h): level 0 is the full-size call, 1..3 the box means of 2x2, 4x4, 8x8 ----------
@@ -2757,6 +3016,7 @@ static int yk_dec_mipchain(yk_ctx* c, const char* name, int firstLevel, int nLev
     if (!yk_dec_begun(c)) return refuse(YK_ERR_STATE, batch ? "yk_decode_begin_batch first" : "yk_decode_begin first");
     if (c->dPrepared) return refuse(YK_ERR_STATE, "this image is prepared for windows (yk_decode_prepare_device) and windows have no chain");
     if (!batch && c->dWinSet) return refuse(YK_ERR_STATE, "a window is set on this decode (yk_decode_set_window) and windows have no chain");
+    if (c->dBRectSet) return refuse(YK_ERR_STATE, "rectangles are set on this batch (yk_decode_set_batch_rects) and rectangles have no chain");
     if (c->dBWinSet) return refuse(YK_ERR_STATE, "windows are set on this batch (yk_decode_set_batch_windows) and windows have no chain");
     const int total = yk_decode_mip_levels(c->dw, c->dh);
     if (firstLevel < 0 || nLevels < 1 || nLevels > YK_MIP_MAX_LEVELS || firstLevel > total - nLevels)

@@ -12,7 +12,8 @@ from typing import NamedTuple
 import numpy as np
 
 from ._lib import YaikError, lib
-from .encoder import PASSES, NormC, _chk, elem_layout, mirror_flags, norm_params, norm_struct, u8_pixel_layout, u8_planar_batch_layout, u8_planar_layout  # noqa: F401  (norm_params: public here)
+from .augment import output_size, rect_table
+from .encoder import PASSES, NormC, _chk, elem_layout, mirror_flags, norm_params, norm_struct, resample_layout, u8_pixel_layout, u8_planar_batch_layout, u8_planar_layout  # noqa: F401  (norm_params: public here)
 from .files import window_origins
 
 
@@ -140,6 +141,7 @@ class HipTileDecoder:
         self._alpha_stage = None         # ... and the staging tensor of decompress_alpha_batch's host payloads
         self._window = None              # set_window: (x0, y0, w, h) of the image begun, None = the whole image
         self._batch_windows = None       # set_batch_windows: (origins [N, 2], w, h) of the batch begun, None = whole frames
+        self._batch_rects = None         # set_batch_rects: int32 [N, 4] of (x0, y0, sw, sh), None = no rectangles
 
     def close(self):
         if getattr(self, "_h", None):
@@ -154,6 +156,7 @@ class HipTileDecoder:
         self._has_alpha = self._alpha_batch = False
         self._window = None                                                # yk_decode_begin always clears the window
         self._batch_windows = None                                         # ... and the windows of a batch
+        self._batch_rects = None
         _chk(self._h, lib().yk_decode_begin(self._h, w, h))
 
     # ---- windows: decode only the tiles a rectangle of the image needs (yk_decode_set_window) -----------------------------------
@@ -295,6 +298,7 @@ class HipTileDecoder:
         self._has_alpha = self._alpha_batch = False
         self._window = None
         self._batch_windows = None                                         # yk_decode_begin_batch always clears the windows
+        self._batch_rects = None                                           # ... and the rectangles
 
     def select_frame(self, f: int):
         _chk(self._h, lib().yk_decode_select_frame(self._h, f))
@@ -338,6 +342,7 @@ class HipTileDecoder:
         if int(w) == 0 and int(h) == 0:
             _chk(self._h, lib().yk_decode_set_batch_windows(self._h, None, 0, 0))
             self._batch_windows = None
+            self._batch_rects = None                                       # windows and rectangles replace each other, a clear included
             return
         if isinstance(origins, np.ndarray):
             if origins.ndim != 2 or origins.shape[1] != 2 or not np.issubdtype(origins.dtype, np.integer):
@@ -350,6 +355,7 @@ class HipTileDecoder:
         self._batch_windows = None
         _chk(self._h, (lib().yk_decode_set_batch_windows_px if px else lib().yk_decode_set_batch_windows)(self._h, xy, int(w), int(h)))
         self._batch_windows = (np.asarray(flat, dtype=np.int32).reshape(-1, 2), int(w), int(h))
+        self._batch_rects = None                                           # windows replace rectangles
 
     def image_batch_windows_device(self, out=None, channels: int = 3, alpha: int = 255, planar: bool = False, alpha_from_planes: bool = False):
         """The window of every frame of the batch as 8-bit pixels in one torch.uint8 tensor on the handle's device
@@ -357,6 +363,8 @@ class HipTileDecoder:
         image_batch_device()[f] of the whole decode cut to its window.  channels, alpha, alpha_from_planes (each frame's decoded 'ALPM' plane,
         read at its window's offset) and `out` follow image_batch_device; ordering against torch's current stream is the same: no host fence."""
         import torch
+        if self._batch_windows is None and getattr(self, "_batch_rects", None) is not None:
+            raise ValueError("rectangles are set on this batch (set_batch_rects): image_resampled_batch_device() writes them")
         if self._batch_windows is None:
             raise ValueError("no windows are set on this batch: set_batch_windows() first")
         if channels not in (3, 4):
@@ -512,7 +520,7 @@ class HipTileDecoder:
         return frames
 
     def decode_batch_from_encoder(self, enc, sync: bool = True, alpha: bool = False, per_frame: bool = False, palette: bool = False,
-                                  alpha_6bit: bool = False, windows=None, *, px: bool = False) -> None:
+                                  alpha_6bit: bool = False, windows=None, *, px: bool = False, rects=None) -> None:
         """decode_batch_streams of encoder_batch_streams(enc, per_frame); windows=(origins, w, h) first gives every frame its window
         (set_batch_windows, with px=True pixel windows; checked before anything else happens), so that the batch begun just before decodes those rectangles only; alpha=True also runs the encoder's alpha_values_batch and decodes every
         frame's 'ALPM' payload where the encoder left it in HBM (decompress_alpha_batch; frames without a chunk are opaque).  With sync=False on
@@ -525,10 +533,14 @@ class HipTileDecoder:
         (palette_decompress_streams, remap_range 250) and the gradient decode reads those outputs with remap off.  Only for streams that
         round-trip through the 'GTIL' coder: a payload PaletteDecompressor rejects raises YaikError (DESIGN §18 on payloads that decode to
         other bytes than their stream).  Without payloads of this batch on the encoder the call raises ValueError."""
+        if windows is not None and rects is not None:
+            raise ValueError("windows and rects replace each other: give one")
         if windows is not None:
             if not isinstance(windows, (tuple, list)) or len(windows) != 3:
                 raise TypeError(f"windows must be (origins, w, h); got {windows!r}")
             self.set_batch_windows(*windows, px=px)
+        if rects is not None:                                              # a rectangle per frame (set_batch_rects, DESIGN §29), checked before anything else happens
+            self.set_batch_rects(rects)
         if palette:
             if per_frame:
                 raise ValueError("palette=True needs the encoder's stream table (per_frame=False)")
@@ -824,6 +836,119 @@ class HipTileDecoder:
         _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
         _chk(self._h, L.yk_decode_output_norm_batch_device(self._h, C.byref(nrm), None if flags is None else flags.ctypes.data, out.data_ptr(), lay.row_bytes,
                                                            lay.plane_bytes, lay.frame_bytes, channels, -1 if alpha_from_planes else int(alpha)))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
+
+    # ---- per-frame rectangles resampled to one output size: a random resized crop in the decoder (yk_decode_set_batch_rects) ------
+    @property
+    def batch_rects(self):
+        """int32 [N, 4] of the source rectangles (x0, y0, sw, sh) set on the batch begun, None when there are none (always after begin_batch)."""
+        return None if self._batch_rects is None else self._batch_rects.copy()
+
+    def set_batch_rects(self, rects) -> None:
+        """From here on the batch decode calls owe frame f only the pixels of its own rectangle rects[f] = (x0, y0, sw, sh): any offset, any size
+        (1..16384) inside the image, a different size and aspect per frame.  The chunk calls decode the smallest 8-aligned rectangle round each;
+        image_resampled_batch_device() resamples every rectangle to one output size.  Call it right after begin_batch(), before any chunk; None
+        clears the rectangles.  Rectangles and windows (set_batch_windows) replace each other; while rectangles are set the whole-frame, window
+        and normalised batch outputs raise the library's state error, planes() of a selected frame is exact inside its cover only, tile4x4() is
+        whole and exact.  Bad rectangles raise before any library call."""
+        if rects is None:
+            _chk(self._h, lib().yk_decode_set_batch_rects(self._h, None))
+            self._batch_rects = None
+            self._batch_windows = None
+            return
+        tab = rect_table(rects, self.frames, self.w, self.h)
+        _chk(self._h, lib().yk_decode_set_batch_rects(self._h, tab.ctypes.data))
+        self._batch_rects = tab
+        self._batch_windows = None                                         # rectangles replace windows
+
+    @staticmethod
+    def _resample_elem(dtype, scale, bias, mean, std):
+        """(yk_norm or None, torch dtype) of a resampled output: dtype None is uint8, which takes no scale, bias, mean or std"""
+        import torch
+        if dtype is None or str(dtype).replace("torch.", "") == "uint8":
+            if any(v is not None for v in (scale, bias, mean, std)):
+                raise ValueError("uint8 elements take no scale, bias, mean or std: give a float dtype")
+            return None, torch.uint8
+        return norm_struct(dtype, scale, bias, mean, std), getattr(torch, str(dtype).replace("torch.", ""))
+
+    def image_resampled_batch_device(self, size, dtype=None, scale=None, bias=None, mean=None, std=None, mirror=None, out=None, channels: int = 3,
+                                     alpha: int = 255, planar: bool = False, alpha_from_planes: bool = False):
+        """Every frame's rectangle (set_batch_rects; the whole frame if neither rectangles nor windows are set) resampled to size=(ow, oh) in one
+        launch (yk_decode_output_resampled_batch_device): [N, oh, ow, C], or [N, C, oh, ow] with planar=True.  Bilinear in 16.16 fixed point with
+        half-pixel centres and taps clamped to the rectangle -- "crop, then resize", torch's align_corners=False, antialias=False, within 2.5 grey
+        levels of it and fully defined in integers; there is no antialiasing filter, so a rectangle more than twice the output size
+        aliases.  dtype None gives torch.uint8; float16 / bfloat16 / float32 apply image_norm_batch_device's scale / bias (or mean / std) to the
+        resampled byte.  mirror: None or N flags; a set one flips that frame's output horizontally.  channels, alpha, alpha_from_planes, `out`
+        and the ordering against torch's current stream follow image_norm_batch_device."""
+        import torch
+        ow, oh = output_size(size)
+        nrm, tdt = self._resample_elem(dtype, scale, bias, mean, std)
+        if channels not in (3, 4):
+            raise ValueError("channels must be 3 or 4")
+        if alpha_from_planes and channels != 4:
+            raise ValueError("alpha_from_planes needs channels=4")
+        if not alpha_from_planes and not 0 <= int(alpha) <= 255:
+            raise ValueError(f"alpha must be 0..255; got {alpha!r}")
+        N = self.frames
+        flags = mirror_flags(mirror, N)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((N, channels, oh, ow) if planar else (N, oh, ow, channels), dtype=tdt, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        elif out.dtype != tdt:
+            raise TypeError(f"out has dtype {out.dtype}, the call asks for {tdt}")
+        lay = resample_layout(out, planar=planar, batch=True)
+        if (lay.frames, lay.channels, lay.rows, lay.w) != (N, channels, oh, ow):
+            raise ValueError(f"out holds {lay.frames} frames of {lay.w} x {lay.rows} x {lay.channels}, the call needs {N} of {ow} x {oh} x {channels}")
+        L = lib()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_output_resampled_batch_device(self._h, None if nrm is None else C.byref(nrm), None if flags is None else flags.ctypes.data,
+                                                                out.data_ptr(), ow, oh, lay.row_bytes, lay.plane_bytes, lay.frame_bytes, channels,
+                                                                -1 if alpha_from_planes else int(alpha)))
+        _chk(self._h, L.yk_stream_handoff(self._h, cur))
+        return out
+
+    def image_resampled_device(self, size, rect=None, dtype=None, scale=None, bias=None, mean=None, std=None, mirror: bool = False, out=None,
+                               channels: int | None = None, alpha: int | None = None, planar: bool = False):
+        """image_resampled_batch_device for the image begun, or the selected frame of a batch without rectangles or windows
+        (yk_decode_output_resampled_device): rect = (x0, y0, sw, sh) inside the window set on the image (set_window, aligned or px=True), None for
+        that window or the whole image, resampled to size=(ow, oh): [oh, ow, C], or [C, oh, ow] with planar=True.  channels, alpha and `out`
+        follow image_norm_device."""
+        import torch
+        ow, oh = output_size(size)
+        nrm, tdt = self._resample_elem(dtype, scale, bias, mean, std)
+        rc = None
+        if rect is not None:
+            window = self._window
+            bx, by, bw, bh = window if window is not None else (0, 0, self.w, self.h)
+            rc = rect_table([rect], 1, self.w, self.h)
+            x0, y0, sw, sh = (int(v) for v in rc[0])
+            if x0 < bx or y0 < by or x0 + sw > bx + bw or y0 + sh > by + bh:
+                raise ValueError(f"rectangle {tuple(int(v) for v in rc[0])} must lie inside the window {(bx, by, bw, bh)} set on this image")
+        C4 = channels if channels is not None else (4 if self._has_alpha else 3)
+        if C4 not in (3, 4):
+            raise ValueError("channels must be 3 or 4")
+        a = (-1 if self._has_alpha else 255) if alpha is None else int(alpha)
+        if not -1 <= a <= 255:
+            raise ValueError(f"alpha must be None or 0..255; got {alpha!r}")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((C4, oh, ow) if planar else (oh, ow, C4), dtype=tdt, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev:
+            raise ValueError(f"out must be a torch tensor on {dev}, got {getattr(out, 'device', type(out).__name__)}")
+        elif out.dtype != tdt:
+            raise TypeError(f"out has dtype {out.dtype}, the call asks for {tdt}")
+        lay = resample_layout(out, planar=planar)
+        if (lay.channels, lay.rows, lay.w) != (C4, oh, ow):
+            raise ValueError(f"out holds {lay.w} x {lay.rows} x {lay.channels}, the call needs {ow} x {oh} x {C4}")
+        L = lib()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _chk(self._h, L.yk_stream_wait_for(self._h, cur))                  # torch may have just allocated or written `out`
+        _chk(self._h, L.yk_decode_output_resampled_device(self._h, None if rc is None else rc.ctypes.data, None if nrm is None else C.byref(nrm), 1 if mirror else 0,
+                                                          out.data_ptr(), ow, oh, lay.row_bytes, lay.plane_bytes, C4, a))
         _chk(self._h, L.yk_stream_handoff(self._h, cur))
         return out
 

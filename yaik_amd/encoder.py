@@ -200,6 +200,19 @@ def elem_layout(pixels, planar: bool = False, batch: bool = False) -> ElemLayout
     return ElemLayout(code, es, frames, ch, rows, w, row * es, plane * es, frame * es)
 
 
+def resample_layout(pixels, planar: bool = False, batch: bool = False) -> ElemLayout:
+    """elem_layout for the resampled outputs, which also write uint8: such a tensor goes through the uint8 layout functions and comes
+    back as an ElemLayout of dtype 0 and one byte per element"""
+    if str(pixels.dtype).replace("torch.", "") != "uint8":
+        return elem_layout(pixels, planar=planar, batch=batch)
+    if planar:
+        lay = u8_planar_batch_layout(pixels) if batch else u8_planar_layout(pixels)
+        frames, frame = (lay.frames, lay.frame_bytes) if batch else (1, lay.channels * lay.plane_bytes)
+        return ElemLayout(0, 1, frames, lay.channels, lay.rows, lay.w, lay.row_bytes, lay.plane_bytes, frame)
+    lay = u8_pixel_layout(pixels, batch=batch)
+    return ElemLayout(0, 1, lay.frames, lay.channels, lay.rows, lay.w, lay.row_bytes, 0, lay.frame_bytes)
+
+
 def norm_params(mean, std):
     """(scale, bias) as float32 arrays of four for the normalised outputs from a per-channel mean and std (scalars, or sequences of 3 or 4 in the
     units of the decoded bytes, 0..255): scale = fp32(1 / std), bias = fp32(-mean / std), both computed in float64 and rounded once.  Three

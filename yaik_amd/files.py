@@ -10,6 +10,8 @@ decode_files_windows_device(streams, origins, size)   one window of each of them
                               the pixel-sized work of a frame only inside its window; uint8 [N, h, w, C] or [N, C, h, w]
 decode_files_norm_device(streams, dtype, ...)   the frames, or a pixel window of each, as normalised float16 / bfloat16 / float32 elements with a
                               mirror flag per stream through YAIK_DecodeImagesNormToDevice: converted in the de-tile store, no uint8 intermediate
+decode_files_resampled_device(streams, size, rects=None, ...)   a rectangle of each stream (its own size and aspect), or the whole frame, resampled
+                              to one size through YAIK_DecodeImagesResampledToDevice: uint8, or normalised elements with a mirror flag per stream
 encode_files_device(frames)   the other direction (yaik_encode.h, YAIK_EncodeImagesFromDevice): uint8 [N, H, W, C] frames in device memory to N
                               streams, every kernel once over the batch, one gather and one download, ZStd and framing on host workers
 encode_file_device(frame)     a batch of one
@@ -107,6 +109,10 @@ WINDOW_PX_SIGNATURES = {
 NORM_SIGNATURES = {
     "YAIK_DecodeImagesNormToDevice": (C.c_bool, BATCH_WINDOWS_SIGNATURES["YAIK_DecodeImagesWindowsToDevice"][1] + [vp, vp]),
 }
+# yaik_decode_resample.h: the arguments of YAIK_DecodeImagesNormToDevice with rects, ow, oh in place of xy, ww, wh
+RESAMPLE_SIGNATURES = {
+    "YAIK_DecodeImagesResampledToDevice": NORM_SIGNATURES["YAIK_DecodeImagesNormToDevice"],
+}
 # yaik_decode_scaled.h: the same library, C linkage
 SCALED_SIGNATURES = {
     "YAIK_DecodeImageScaledToDevice": (C.c_bool, [vp, u32, vp, C.c_int]),
@@ -151,7 +157,7 @@ def host_lib() -> C.CDLL:
             fn = getattr(L, SYMBOLS[name])
             fn.restype, fn.argtypes = res, args
             setattr(L, name, fn)
-        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **BATCH_WINDOWS_SIGNATURES, **WINDOW_PX_SIGNATURES, **NORM_SIGNATURES, **SCALED_SIGNATURES, **MIPCHAIN_SIGNATURES}.items():
+        for name, (res, args) in {**ENC_SIGNATURES, **ENC6_SIGNATURES, **WINDOW_SIGNATURES, **MULTIWINDOW_SIGNATURES, **BATCH_WINDOWS_SIGNATURES, **WINDOW_PX_SIGNATURES, **NORM_SIGNATURES, **RESAMPLE_SIGNATURES, **SCALED_SIGNATURES, **MIPCHAIN_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _host = L
@@ -539,6 +545,65 @@ def decode_files_norm_device(streams, dtype, scale=None, bias=None, mean=None, s
     ok = L.YAIK_DecodeImagesNormToDevice(h, ptrs, lens, n, out.data_ptr(), lay.row_bytes, lay.plane_bytes, lay.frame_bytes, channels, int(threads),
                                          C.byref(failed), xy, ww if xy is not None else 0, wh if xy is not None else 0, C.byref(nrm),
                                          None if flags is None else flags.ctypes.data)
+    if not ok:
+        raise YaikFileError(L.YAIK_GetErrorCode(), max(failed.value, 0))
+    return out
+
+
+def decode_files_resampled_device(streams, size, rects=None, dtype=None, scale=None, bias=None, mean=None, std=None, mirror=None, out=None, channels: int = 3,
+                                  planar: bool = False, threads: int = 16):
+    """n (1..1024) streams of ONE width x height, a rectangle of each resampled to size=(ow, oh) (YAIK_DecodeImagesResampledToDevice):
+    [N, oh, ow, C], or [N, C, oh, ow] with planar=True, on the GPU.  rects: None (whole frames), or n rectangles (x0, y0, sw, sh), stream f's own,
+    at any offset and of any size 1..16384 inside the image (yaik_amd.augment.random_resized_crop_rects samples them); only the tiles a
+    rectangle needs are decoded.  dtype None gives torch.uint8; float16 / bfloat16 / float32 apply scale / bias (or mean / std) to the resampled
+    byte as decode_files_norm_device does.  mirror: None, or n flags, a set one flips that stream's output horizontally.  Bilinear in 16.16 fixed
+    point, taps clamped to the rectangle, no antialiasing filter (HipTileDecoder.image_resampled_batch_device has the rule).  channels 4 takes
+    alpha from each frame's 'ALPM' chunk, 255 for a frame without one.  `out`, threads and the errors follow decode_files_device."""
+    import torch
+
+    from .augment import output_size, rect_table
+    from .encoder import mirror_flags, norm_struct, resample_layout
+    ow, oh = output_size(size)
+    if dtype is None or str(dtype).replace("torch.", "") == "uint8":
+        if any(v is not None for v in (scale, bias, mean, std)):
+            raise ValueError("uint8 elements take no scale, bias, mean or std: give a float dtype")
+        nrm, tdt = None, torch.uint8
+    else:
+        nrm, tdt = norm_struct(dtype, scale, bias, mean, std), getattr(torch, str(dtype).replace("torch.", ""))
+    streams = list(streams)
+    n = len(streams)
+    if not 1 <= n <= 1024:
+        raise ValueError("1..1024 streams are needed")
+    if channels not in (3, 4) or not 1 <= int(threads) <= 16:
+        raise ValueError("channels must be 3 or 4 and threads 1..16")
+    flags = mirror_flags(mirror, n)
+    tab = None
+    if rects is not None:
+        W = H = 1 << 30                                                    # without a readable header the library says so, nothing is written
+        if len(streams[0]) >= 12:
+            tag, _, w0, h0, _ = struct.unpack_from("<IHHHH", streams[0], 0)
+            if tag == 0x4B494159:
+                W, H = w0, h0
+        tab = rect_table(rects, n, W, H)
+    L, h = host_lib(), library()
+    bufs = [_buffer(s) for s in streams]
+    dev = torch.device("cuda", _device)
+    if out is None:
+        out = torch.empty((n, channels, oh, ow) if planar else (n, oh, ow, channels), dtype=tdt, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.device != dev:
+        raise ValueError(f"out must be a torch tensor on {dev}")
+    elif out.dtype != tdt:
+        raise TypeError(f"out has dtype {out.dtype}, the call asks for {tdt}")
+    lay = resample_layout(out, planar=planar, batch=True)
+    if (lay.frames, lay.channels, lay.rows, lay.w) != (n, channels, oh, ow):      # the library writes oh x ow pixels per frame: never into a smaller view
+        raise ValueError(f"out holds {lay.frames} frames of {lay.w} x {lay.rows} x {lay.channels}, the call needs {n} of {ow} x {oh} x {channels}")
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_uint32 * n)(*[b.size for b in bufs])
+    failed = C.c_int32(-1)
+    torch.cuda.current_stream(dev).synchronize()                           # the library writes on its slot's own stream
+    ok = L.YAIK_DecodeImagesResampledToDevice(h, ptrs, lens, n, out.data_ptr(), lay.row_bytes, lay.plane_bytes, lay.frame_bytes, channels, int(threads),
+                                              C.byref(failed), None if tab is None else tab.ctypes.data, ow, oh, None if nrm is None else C.byref(nrm),
+                                              None if flags is None else flags.ctypes.data)
     if not ok:
         raise YaikFileError(L.YAIK_GetErrorCode(), max(failed.value, 0))
     return out

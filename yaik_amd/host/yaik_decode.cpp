@@ -10,6 +10,8 @@
 #include "../csrc/yk_window_px.h"
 #include "../csrc/yk_window_mirror.h"
 #include "yaik_decode_norm.h"
+#include "../csrc/yk_resample.h"
+#include "yaik_decode_resample.h"
 #include "yaik_decode_scaled.h"
 #include "yaik_decode_mipchain.h"
 #include <atomic>
@@ -387,10 +389,12 @@ void YAIK_LastBatchStageMs(double out[3]) { if (out) for (int i = 0; i < 3; i++)
 // YAIK_DecodeImagesToDevice and, with xy (one origin per stream) and the window size ww x wh, YAIK_DecodeImagesWindowsToDevice: the same plan,
 // expansion, upload and batch calls; with windows the batch is given them right after yk_decode_begin_batch, the output is the windows' and a
 // fallback stream takes the single-image window chain; with norm (YAIK_DecodeImagesNormToDevice, yaik_decode_norm.h) both end in the normalised outputs:
-// devOut holds elements of norm->dtype, the pitches stay in bytes, mirror is NULL or one flag per stream
+// devOut holds elements of norm->dtype, the pitches stay in bytes, mirror is NULL or one flag per stream; with ow > 0
+// (YAIK_DecodeImagesResampledToDevice, yaik_decode_resample.h) the batch gets rsRects (NULL: whole frames) through yk_decode_set_batch_rects and both
+// end in the resampled outputs of ow x oh, uint8 if norm is NULL; a fallback stream decodes its rectangle as a pixel window
 static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes, size_t planeBytes,
                          size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* xy, int ww, int wh, bool px = false, const yk_norm* norm = nullptr,
-                         const uint8_t* mirror = nullptr) {
+                         const uint8_t* mirror = nullptr, const int* rsRects = nullptr, int ow = 0, int oh = 0) {
     using namespace yaikplan;
     if (failedIndex) *failedIndex = -1;
     if (!lib || lib != gLib) { setError(YAIK_INVALID_LIBRARYCTX); return false; }
@@ -409,6 +413,12 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
         const int rc = readHeader(streams[f], lengths[f], &fw, &fh, nullptr);
         if (rc == 0 && f == 0) { w = fw; h = fh; }
         if (rc != 0 || fw != w || fh != h) { setError(rc == 1 ? YAIK_INVALID_STREAM : YAIK_INVALID_HEADER); if (failedIndex) *failedIndex = f; return false; }
+    }
+    const bool rs = ow > 0;
+    if (rs) {                                                                   // the rule of yk_resample.h for every stream, before a slot is taken
+        bool ok = yk_rs_size_ok(ow, oh) && (rsRects || yk_rs_src_ok(0, 0, w, h, w, h));
+        for (int f = 0; ok && rsRects && f < n; f++) ok = yk_rs_src_ok(rsRects[4 * f], rsRects[4 * f + 1], rsRects[4 * f + 2], rsRects[4 * f + 3], w, h);
+        if (!ok) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
     }
     if (xy && px) {                                                             // pixel windows: any rectangle inside the image
         if (!yk_wpx_windows_ok(n, xy, ww, wh, w, h)) { setError(YAIK_DECIMG_INVALIDCTX); return false; }
@@ -511,6 +521,7 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
         // ---- decode: every kernel once over the n frames; a fallback stream is an empty frame here
         if (yk_decode_begin_batch(s->ctx, w, h, n) != YK_OK) { setError(YAIK_MALLOC_FAIL); break; }
         if (xy && (px ? yk_decode_set_batch_windows_px(s->ctx, xy, ww, wh) : yk_decode_set_batch_windows(s->ctx, xy, ww, wh)) != YK_OK) { setError(YAIK_DECIMG_INVALIDCTX); break; }
+        if (rs && rsRects && yk_decode_set_batch_rects(s->ctx, rsRects) != YK_OK) { setError(YAIK_DECIMG_INVALIDCTX); break; }
         const size_t NP = (size_t)n * NUM_PASSES;
         std::vector<const uint8_t*> bm(NP), rgb(NP, nullptr);
         std::vector<size_t> rgbBytes(NP, 0);
@@ -567,7 +578,9 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
                 yk_decode_alpha_batch_status(s->ctx, st.data()) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
             for (int f = 0; f < n; f++) if (st[(size_t)f]) fallback[(size_t)f] = 1;       // a payload shorter than the mask selects: the single chain reports it
         }
-        if (norm) {
+        if (rs) {
+            if (yk_decode_output_resampled_batch_device(s->ctx, norm, mirror, devOut, ow, oh, rowBytes, planeBytes, frameBytes, channels, anyAlpha && channels == 4 ? -1 : 255) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
+        } else if (norm) {
             if (yk_decode_output_norm_batch_device(s->ctx, norm, mirror, devOut, rowBytes, planeBytes, frameBytes, channels, anyAlpha && channels == 4 ? -1 : 255) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
         } else if (xy) {
             if (yk_decode_output_batch_windows_device(s->ctx, devOut, rowBytes, planeBytes, frameBytes, channels, anyAlpha && channels == 4 ? -1 : 255) != YK_OK) { setError(YAIK_INVALID_STREAM); break; }
@@ -583,12 +596,14 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
             if (!fallback[(size_t)f]) continue;
             gBatchFallbacks++;
             bool hasAlphaPlane = false;
-            const int window[4] = { xy ? xy[2 * f] : 0, xy ? xy[2 * f + 1] : 0, ww, wh };
-            res = decodeChunks(s, streams[f], lengths[f], hasAlphaPlane, xy ? window : nullptr, px);
+            const int window[4] = { rsRects ? rsRects[4 * f] : xy ? xy[2 * f] : 0, rsRects ? rsRects[4 * f + 1] : xy ? xy[2 * f + 1] : 0, rsRects ? rsRects[4 * f + 2] : ww,
+                                    rsRects ? rsRects[4 * f + 3] : wh };
+            res = decodeChunks(s, streams[f], lengths[f], hasAlphaPlane, xy || rsRects ? window : nullptr, px || rsRects);
             if (res) {
                 const bool plane = hasAlphaPlane && channels == 4;
                 uint8_t* const dst = devOut + (size_t)f * frameBytes;
-                res = (norm ? yk_decode_output_norm_device(s->ctx, norm, mirror ? mirror[f] : 0, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)
+                res = (rs ? yk_decode_output_resampled_device(s->ctx, nullptr, norm, mirror ? mirror[f] : 0, dst, ow, oh, rowBytes, planeBytes, channels, plane ? -1 : 255)
+                       : norm ? yk_decode_output_norm_device(s->ctx, norm, mirror ? mirror[f] : 0, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)
                        : xy ? yk_decode_output_window_device(s->ctx, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)
                           : yk_decode_output_device(s->ctx, dst, rowBytes, planeBytes, channels, plane ? -1 : 255)) == YK_OK && yk_synchronize(s->ctx) == YK_OK;
                 if (!res) setError(YAIK_INVALID_STREAM);
@@ -625,6 +640,15 @@ extern "C" bool YAIK_DecodeImagesNormToDevice(YAIK_LIB lib, void* const* streams
                                               const uint8_t* mirror) {
     if (!norm) { if (failedIndex) *failedIndex = -1; setError(YAIK_DECIMG_INVALIDCTX); return false; }
     return decodeImages(lib, streams, lengths, n, static_cast<uint8_t*>(devOut), rowBytes, planeBytes, frameBytes, channels, threads, failedIndex, xy, ww, wh, true, norm, mirror);
+}
+
+// yaik_decode_resample.h
+extern "C" bool YAIK_DecodeImagesResampledToDevice(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, void* devOut, size_t rowBytes, size_t planeBytes,
+                                                   size_t frameBytes, int channels, int threads, int32_t* failedIndex, const int* rects, int ow, int oh, const yk_norm* norm,
+                                                   const uint8_t* mirror) {
+    if (ow < 1 || oh < 1) { if (failedIndex) *failedIndex = -1; setError(YAIK_DECIMG_INVALIDCTX); return false; }
+    return decodeImages(lib, streams, lengths, n, static_cast<uint8_t*>(devOut), rowBytes, planeBytes, frameBytes, channels, threads, failedIndex, nullptr, 0, 0, false, norm, mirror,
+                        rects, ow, oh);
 }
 
 // ---- YAIK_DecodeImageWindowsToDevice: many windows of one stream (yaik_decode_multiwindow.h) ------------------------------------------------
