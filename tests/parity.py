@@ -10,7 +10,13 @@ def cells_from_plane(p8: np.ndarray) -> np.ndarray:
 
 
 def compare_encode(planes: np.ndarray, hip, mode3bit_only: bool, want_dst: bool = True, check_corners: bool = False):
-    """Runs the whole encode on both sides; returns list of mismatch descriptions (empty = bit-exact)."""
+    """Runs the whole encode on both sides; returns list of mismatch descriptions (empty = bit-exact).
+
+    want_dst selects the instantiation of the fused kernel.  True (the default here) is the TEST-ONLY one, WANT_DST = true: it builds the
+    tile's LUTs and writes the reconstructed `dst` planes, which are compared too.  False is the SHIPPED one, WANT_DST = false; only there
+    exist the `spread` path of the range phase (a strip with at most four valid cells), the wide stores of strips whose live tiles are all whole
+    (`fullTiles`) and the WHOLE instantiation (one frame, both sides multiples of 64).  A test of the quantiser that leaves the default
+    switches all three off: pass want_dst=False as well."""
     n, h, w = planes.shape
     bad = []
 
