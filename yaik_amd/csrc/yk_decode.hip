@@ -643,6 +643,7 @@ __device__ __forceinline__ void yk_dec1d_scan_body(uint32_t* __restrict__ blockT
     for (int a = 0; a < 2; a++) {
         uint32_t* arr = a ? blockPix : blockTiles;
         uint32_t base = 0;
+        // more than one trip needs more than 1024 scan blocks = 2^20 tiles, an image above 8192 x 8192: no test reaches the second trip
         for (int start = 0; start < nBlocks; start += 1024) {
             const int i = start + threadIdx.x;
             const uint32_t v = i < nBlocks ? arr[i] : 0u;
@@ -755,8 +756,11 @@ __device__ __forceinline__ void yk_dec1d_body(const uint32_t* __restrict__ offIn
         if (qh == 3 || !live[rep]) continue;
         const int delta2 = ((delta * invRange) >> 8) + 1;                       // :66, :86
         // v = L ? base + (((L - 1) * delta2) >> 16) : color0 (:113-124), four pixels of a dword at a time: for L >= 1 the value is byte 2 of
-        // K + L * delta2 with K = (base << 16) - delta2 (delta2 < 2^21, L a byte: a 24-bit multiply with the byte selected by the instruction);
+        // K + L * delta2 with K = (base << 16) - delta2 (delta2 <= 255 * 65536 + 1 < 2^24 for every compressionRange 1..255 -- below 2^21 only
+        // from range 8 up, 8355841 at range 2 -- and L a byte: a 24-bit multiply with the byte selected by the instruction, L * delta2 < 2^32;
+        // the sum wraps at 32 bits, which byte 2 does not see: it is (base + (((L - 1) * delta2) >> 16)) & 255, the reference's store into a u8);
         // the bytes with L == 0 are found with the carry-free zero-byte mask and take color0.  4.5 operations per pixel instead of 8.
+        // (Range 1 with delta >= 128 overflows delta * invRange here as in the reference: unspecified)
         const uint32_t Kc = ((uint32_t)base << 16) - (uint32_t)delta2, d2u = (uint32_t)delta2, c0x4 = (uint32_t)color0 * 0x01010101u;
         auto dec4 = [&](uint32_t L4) {
             uint32_t t0, t1, t2, t3;

@@ -200,12 +200,13 @@ class HipTileDecoder:
         self._window = None if clear else (x0, y0, w, h)
 
     # ---- many windows of one image: prepare once, render 64x64 blocks on demand (yk_decode_prepare_device) ---------------------
-    def prepare(self, calls: list, remap_range: int = 250, sync: bool = True) -> None:
+    def prepare(self, calls: list, remap_range: int = 250, sync: bool = True, compression_range: int = 15) -> None:
         """The map-sized work of the image begun, once, from the call list of decode_streams (device-resident streams; at most one "1" entry, none
         for an image without a 1-D chunk): the corner lattice, the marks of every tile and the offsets into the 1-D streams.  No pixel is
         written.  From here on render_window / render_windows hand out windows, each paying only for the 64x64 blocks no earlier window needed
         and its own de-tile.  The tile bitmaps and 1-D streams are copied into the handle: with sync=True (or after synchronize()) every input
-        may be freed or overwritten.  Call it right after begin(); a window, a batch, chunks decoded already or a second prepare are the
+        may be freed or overwritten.  compression_range: the '1DTL' chunk header's compressionRange (15 is what the encoder writes).  Call it
+        right after begin(); a window, a batch, chunks decoded already or a second prepare are the
         library's to refuse.  Until the next begin(), decode_streams, set_window, image(), image_device(), image_window_device() and the compare
         calls raise the library's state error; planes() is exact inside rendered blocks, tile4x4() is whole and exact."""
         L = lib()
@@ -219,7 +220,7 @@ class HipTileDecoder:
         bm, nb = (C.c_void_p * n)(*[ptr(c[3]) for c in g]), (C.c_size_t * n)(*[c[4] for c in g])
         rgb, nr = (C.c_void_p * n)(*[ptr(c[5]) for c in g]), (C.c_size_t * n)(*[c[6] for c in g])
         typ, nty, pix, npx = (ptr(d1[0][1]), d1[0][2], ptr(d1[0][3]), d1[0][4]) if d1 else (None, 0, None, 0)
-        _chk(self._h, L.yk_decode_prepare_device(self._h, n, sx, sy, bm, nb, rgb, nr, remap_range, typ, nty, pix, npx, 15))
+        _chk(self._h, L.yk_decode_prepare_device(self._h, n, sx, sy, bm, nb, rgb, nr, remap_range, typ, nty, pix, npx, int(compression_range)))
         if sync:
             _chk(self._h, L.yk_synchronize(self._h))
 
@@ -397,13 +398,14 @@ class HipTileDecoder:
         _chk(self._h, L.yk_stream_handoff(self._h, cur))
         return out
 
-    def decode_batch_streams(self, frames: list, sync: bool = True, remap_range: int = 250) -> None:
+    def decode_batch_streams(self, frames: list, sync: bool = True, remap_range: int = 250, compression_range: int = 15) -> None:
         """The gradient chunks + the 1-D chunk of every frame of the batch, one launch per kernel over all frames.  frames[f] is the call list
         of encoder_streams for frame f: ("g", sx, sy, bitmap, nbytes, rgb, nbytes) entries, the same passes in the same order in every frame (a
         pass without tiles in a frame: its all-zero bitmap and an empty stream), and at most one ("1", type, nbytes, pix, nbytes).  bitmap / rgb /
         type / pix are device pointers (int, c_void_p) or numpy uint8 arrays; all host arrays are packed, each 16-byte aligned, into one torch
         staging tensor that goes to the device in a single copy.  remap_range: PaletteFullRangeRemapping of the corner streams on the way in
-        (250 for an encoder's streams, 0 for streams that are remapped already)."""
+        (250 for an encoder's streams, 0 for streams that are remapped already).  compression_range: the compressionRange of every frame's
+        '1DTL' chunk (one value per batch; 15 is what the encoder writes)."""
         import torch
         L = lib()
         if len(frames) != self.frames:
@@ -457,7 +459,7 @@ class HipTileDecoder:
             npx = [x[0][4] if x else 0 for x in d1]
             t_ty = (C.c_void_p * n)(*[addr(typ[f]) if nt[f] else None for f in range(n)])
             t_px = (C.c_void_p * n)(*[addr(pix[f]) if npx[f] else None for f in range(n)])
-            _chk(self._h, L.yk_decode_1d_batch_device(self._h, t_ty, (C.c_size_t * n)(*nt), t_px, (C.c_size_t * n)(*npx), 15))
+            _chk(self._h, L.yk_decode_1d_batch_device(self._h, t_ty, (C.c_size_t * n)(*nt), t_px, (C.c_size_t * n)(*npx), int(compression_range)))
         if sync:
             _chk(self._h, L.yk_synchronize(self._h))
 
@@ -977,11 +979,12 @@ class HipTileDecoder:
         enc.synchronize()
         return calls
 
-    def decode_streams(self, calls: list, sync: bool = True, per_pass: bool = False, remap_range: int = 250) -> None:
+    def decode_streams(self, calls: list, sync: bool = True, per_pass: bool = False, remap_range: int = 250, compression_range: int = 15) -> None:
         """All gradient chunks + the 1-D chunk from device-resident streams (encoder_streams): the corner streams are remapped like
         PaletteFullRangeRemapping(250) on the way in; no PCIe hop, no host synchronisation between the passes.  The gradient chunks go through
         ONE yk_decode_gradient_all_device call (per_pass=True: one yk_decode_gradient_device call per chunk, same result).  remap_range=0 takes
-        corner streams that are remapped already (the outputs of palette_decompress_streams)."""
+        corner streams that are remapped already (the outputs of palette_decompress_streams).  compression_range: the '1DTL' chunk header's
+        compressionRange (15 is what the encoder writes)."""
         L = lib()
         g = [c for c in calls if c[0] == "g"]
         if per_pass:
@@ -996,7 +999,7 @@ class HipTileDecoder:
             _chk(self._h, L.yk_decode_gradient_all_device(self._h, n, sx, sy, bm, nb, rgb, nr, remap_range))
         for c in calls:
             if c[0] == "1":
-                _chk(self._h, L.yk_decode_1d_device(self._h, c[1], c[2], c[3], c[4], 15))
+                _chk(self._h, L.yk_decode_1d_device(self._h, c[1], c[2], c[3], c[4], int(compression_range)))
         if sync:
             _chk(self._h, L.yk_synchronize(self._h))
 
@@ -1040,9 +1043,11 @@ class HipTileDecoder:
     def decompress_1d(self, type_stream: np.ndarray, pix_stream: np.ndarray, compression_range: int = 15):
         t = np.ascontiguousarray(type_stream, dtype=np.uint8)
         p = np.ascontiguousarray(pix_stream, dtype=np.uint8)
-        if t.size == 0 or p.size == 0:
+        if t.size == 0 and p.size == 0:
             return
-        _chk(self._h, lib().yk_decode_1d(self._h, t.ctypes.data, t.size, p.ctypes.data, p.size, compression_range))
+        # one stream empty: the other is still decoded against it (missing bytes read as 0: no type bytes give zeros, no pixel bytes give color0)
+        none = np.zeros(16, dtype=np.uint8)
+        _chk(self._h, lib().yk_decode_1d(self._h, (t if t.size else none).ctypes.data, t.size, (p if p.size else none).ctypes.data, p.size, compression_range))
 
     def decompress_1bit_tiled(self, bits: np.ndarray, bw: int, bh: int) -> np.ndarray:
         bits = np.ascontiguousarray(bits, dtype=np.uint8)

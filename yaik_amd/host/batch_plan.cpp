@@ -105,7 +105,8 @@ bool planStream(const void* stream, uint32_t length, StreamPlan& out) {
             const uint8_t* zt = body + sizeof dh;
             if ((uint64_t)dh.streamTypeCnt + dh.streamPixelBit > (uint64_t)(endBlock - zt)) FALLBACK("'1DTL' streams");
             if (dh.streamTypeCnt == 0 || dh.streamPixelBit == 0) FALLBACK("'1DTL' empty ZStd frame");
-            if (dh.streamTypeUncmp > maxStream || dh.streamPixelUncmp > maxStream || dh.compressionRange == 0) FALLBACK("'1DTL' sizes");
+            if (dh.streamTypeUncmp > maxStream || dh.streamPixelUncmp > maxStream) FALLBACK("'1DTL' sizes");
+            if (dh.compressionRange == 0) { out.range0 = true; FALLBACK("'1DTL' compressionRange 0"); }
             out.has1d = true; out.zType = zt; out.zTypeBytes = dh.streamTypeCnt; out.typeBytes = dh.streamTypeUncmp;
             out.zPix = zt + dh.streamTypeCnt; out.zPixBytes = dh.streamPixelBit; out.pixBytes = dh.streamPixelUncmp;
             out.compressionRange = dh.compressionRange;

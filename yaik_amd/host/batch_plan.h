@@ -31,6 +31,9 @@ struct StreamPlan {
     GradChunk grad[NUM_PASSES];
     bool has1d = false; const uint8_t* zType = nullptr; const uint8_t* zPix = nullptr;
     uint32_t zTypeBytes = 0, typeBytes = 0, zPixBytes = 0, pixBytes = 0; uint8_t compressionRange = 0;
+    // a fallback stream whose chunks were in order up to a '1DTL' with compressionRange 0: no decoder takes it (the range divides), so the batch
+    // call can fail before it writes a byte instead of after the other frames
+    bool range0 = false;
 };
 
 // the checks of YAIK_DecodeImagePre: 0 = fine (width, height, rgba filled), 1 = no stream at all (YAIK_INVALID_STREAM), 2 = YAIK_INVALID_HEADER

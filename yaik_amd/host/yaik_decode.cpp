@@ -440,6 +440,10 @@ static bool decodeImages(YAIK_LIB lib, void* const* streams, const uint32_t* len
         std::vector<StreamPlan> plan((size_t)n);
         std::vector<char> fallback((size_t)n, 0);
         for (int f = 0; f < n; f++) fallback[(size_t)f] = planStream(streams[f], lengths[f], plan[(size_t)f]) ? 0 : 1;
+        // a '1DTL' chunk with compressionRange 0 is refused by the single-image chain whatever else the stream holds: the call fails here, before
+        // a byte of devOut is written
+        for (int f = 0; f < n && failed < 0; f++) if (plan[(size_t)f].range0) failed = f;
+        if (failed >= 0) { setError(YAIK_INVALID_STREAM); break; }
         int range1d = 0, colorCompression = -1;
         bool devicePalette = gDevicePalette != 0, anyAlpha = false, any1d = false;
         for (int f = 0; f < n; f++) {

@@ -93,7 +93,8 @@ void            YAIK_SetDevicePalette(int on);
 // order, a structural or ZStd error, a '1DTL' compressionRange other than the batch's first -- is decoded afterwards by the single-image chain
 // on the same slot.  The call takes one free decode slot and returns it.  A stream whose header differs from stream 0's size fails with
 // YAIK_INVALID_HEADER; a stream YAIK_DecodeImageToDevice rejects makes the call return false with that call's error code; *failedIndex (may be NULL)
-// is the lowest failing index, -1 otherwise.  After a failure the pixel bytes of the n frames are unspecified.  Bad arguments (n, channels,
+// is the lowest failing index, -1 otherwise.  After a failure the pixel bytes of the n frames are unspecified, except that a stream whose chunks
+// are in batch order up to a '1DTL' chunk with compressionRange 0 fails the call (YAIK_INVALID_STREAM) before a byte is written.  Bad arguments (n, channels,
 // threads, NULL tables) give YAIK_DECIMG_INVALIDCTX, a NULL devOut YAIK_DECIMG_BUFFERNOTSET.
 bool            YAIK_DecodeImagesToDevice(YAIK_LIB lib, void* const* streams, const uint32_t* lengths, int n, uint8_t* devOut, size_t rowBytes,
                                           size_t planeBytes, size_t frameBytes, int channels, int threads, int32_t* failedIndex);
